@@ -37,14 +37,23 @@ SCLK_HZ = 2.4e9         # max shader clock (MI355X_MICROARCH.md); the chip may r
 N_CUS, N_SIMDS = 256, 1024
 
 
+def count_arg(least: int):
+    def parse_count(text: str) -> int:
+        v = int(text)
+        if v < least:
+            raise argparse.ArgumentTypeError(f"must be >= {least}, got {v}")
+        return v
+    return parse_count
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: a timed region of 100 steps (36 ms at the headline workload) -- the region starts on an idle GPU and ends with the
     # last batch's tail kernels running alone, which costs 20 steps 3 % and 100 steps 0.6 % (708 k / 721 k / 728 k frames/s at
     # 20 / 60 / 200 steps on one box, tools/experiments/dist_steps.sh)
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=count_arg(1), default=100, help="timed steps (ms_per_step = timed region / steps)")
+    ap.add_argument("--warmup", type=count_arg(0), default=5)
     ap.add_argument("--frames", type=int, default=None,
                     help="frames per GPU per step; default 256 (BASELINE configs[1]), and 512 with --gpus 8 (configs[3]: 4 096 frames over 8 GPUs)")
     ap.add_argument("--width", type=int, default=640)
@@ -68,6 +77,9 @@ def parse():
                     help="initialise the process group and run the per-step all-gather even with ONE rank (launch through "
                          "torch.distributed.run --nproc-per-node 1): executes the RCCL path on a one-GPU box")
     ap.add_argument("--dump-poses", default=None, help="rank 0 writes the gathered pose records of the last timed step (all ranks, rank order) as .npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step returned (all ranks, rank order) as DIR/mid_point.npy (float32 "
+                         "[N, 3], mm) and DIR/rotation.npy (float64 [N, 3], rad), for comparing two builds output for output")
     return ap.parse_args()
 
 
@@ -178,6 +190,8 @@ def main():
     last_was_b = (not args.graph) and (((step_no[0] - 1) // depth) % 2 == 1)   # which of the two batches that step processed
     if args.dump_poses and rank == 0:
         np.save(args.dump_poses, gpu_poses)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gpu_poses)
     # run-to-run spread: the same K-step region twice more (untimed for `value`, which stays the first region)
     repeats = [elapsed / args.steps * 1e3]
     if not args.no_extras:
@@ -463,6 +477,24 @@ def rate(hp, frames_t, n, w, h, intr, stream, steps=5, warmup=2, graph=False, la
     from depthhead_amd._lib import POSE_DTYPE
     poses = np.frombuffer(out.cpu().numpy().tobytes(), dtype=POSE_DTYPE).copy()
     return (round(dt / steps * 1e6, 1) if latency else round(steps * n / dt, 1)), poses
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, poses) -> None:
+    """The pose records a caller of the timed path receives, one float .npy per field (the u32 `reserved` padding is not an
+    output).  Above DUMP_MAX_BYTES a fixed seeded sample of frames is written, with their indices in frame_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    mid = np.ascontiguousarray(poses["mid_point"], dtype=np.float32)
+    rot = np.ascontiguousarray(poses["rotation"], dtype=np.float64)
+    per_frame = mid[0].nbytes + rot[0].nbytes
+    if mid.shape[0] * per_frame > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(mid.shape[0], DUMP_MAX_BYTES // (per_frame + 8), replace=False))
+        mid, rot = mid[keep], rot[keep]
+        np.save(os.path.join(out_dir, "frame_index.npy"), keep.astype(np.float64))
+    np.save(os.path.join(out_dir, "mid_point.npy"), mid)
+    np.save(os.path.join(out_dir, "rotation.npy"), rot)
 
 
 def pose_l2(poses, ref) -> float:
