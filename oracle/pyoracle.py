@@ -57,15 +57,28 @@ def build(force: bool = False) -> str:
 _lib = None
 
 
+def _bind(path: str):
+    lb = C.CDLL(path)
+    lb.orc_predict.restype = C.c_int
+    lb.orc_predict_batch.restype = C.c_int
+    lb.orc_mat3_det_f64.restype = C.c_double
+    lb.orc_trace_f64.restype = C.c_double
+    lb.orc_average_value_in_rect.restype = C.c_double
+    return lb
+
+
 def lib():
     global _lib
     if _lib is None:
-        _lib = C.CDLL(build())
-        _lib.orc_predict.restype = C.c_int
-        _lib.orc_predict_batch.restype = C.c_int
-        _lib.orc_mat3_det_f64.restype = C.c_double
-        _lib.orc_trace_f64.restype = C.c_double
-        _lib.orc_average_value_in_rect.restype = C.c_double
+        _lib = _bind(build())
+    return _lib
+
+
+def use_library(path: str):
+    """Route every call of this module through another build of dh_oracle.c (tests/test_edge_pyref.py loads the
+    sanitizer build this way, in a child process of its own)."""
+    global _lib
+    _lib = _bind(path)
     return _lib
 
 

@@ -1,9 +1,10 @@
 """pyref.py -- a SECOND, independent CPU restatement of the hot path, written from the Rust text of the reference
-(/root/reference/src/hough/prediction.rs:421-753, src/meanshift.rs:228-407, src/types.rs:317-339 and :424-445,
+(/root/reference/src/hough/prediction.rs:421-753 and the sibling consumers predict_mask / the voting stage of
+build_hough_image, :760-905; src/meanshift.rs:228-407, src/types.rs:317-339 and :424-445,
 src/meancov_estimation.rs:201-216, :339-378, src/hough/houghforest.rs:185-193) and NOT from oracle/dh_oracle.c.
 
-TEST INFRASTRUCTURE ONLY (tests/test_pyref.py): nothing under depthhead_amd/ imports it.  PARITY UNPINNED like the C
-oracle -- the reference holds no golden vector for these stages and cannot be run here (Rust, no toolchain; the tree walk
+TEST INFRASTRUCTURE ONLY (tests/test_pyref.py, tests/test_edge_pyref.py, tests/test_gpu_edge_families.py): nothing under
+depthhead_amd/ imports it.  PARITY UNPINNED like the C oracle -- the reference holds no golden vector for these stages and cannot be run here (Rust, no toolchain; the tree walk
 lives in the un-vendored crate stamm 0.2.0).  What this file adds is a defence against a shared misreading: two restatements
 by different routes (plain Python objects, a dict for the HashMap, numpy scalars for the f32 / f64 arithmetic, loops in
 the reference's order) have to agree on every intermediate of the committed goldens and of the paper case.
@@ -326,3 +327,91 @@ def predict(forest, model, img, K, midp_guess=None, rot_guess=None) -> dict:
                 guess_rot=np.array(guessrot, dtype=np.int32), mid_cells=cells(mid), rot_cells=cells(rot),
                 ms_trace_mid=np.array(trace_mid, dtype=np.int32), ms_trace_rot=np.array(trace_rot, dtype=np.int32),
                 mid_point=mid_point, rotation=rotation)
+
+
+# ---------------------------------------------------------------- sibling consumers (prediction.rs:760-905)
+def as_u8(v) -> int:
+    v = float(v)
+    if v != v or v <= 0.0:
+        return 0
+    if v >= 255.0:
+        return 255
+    return int(v)
+
+
+def _windows(model, w, h):
+    """The sliding-window loops of build_hough_image / predict_mask (:767-775, :853-860): (x, y) in the reference's order."""
+    sw, sh, step = int(model.subimage_width), int(model.subimage_height), int(model.stepwidth)
+    left_w, left_h = sw // 2, sh // 2
+    right_w, right_h = sw - left_w, sh - left_h
+    y = left_h
+    while y < h - right_h:
+        x = left_w
+        while x < w - right_w:
+            yield x, y, x - left_w, y - left_h
+            x += step
+        y += step
+
+
+def _leafs(forest, model, img, ox, oy):
+    """The background test and forest_predictions of :783-799 / :862-879: None for a background window."""
+    if not average_value_in_rect(img, ox, oy, (0, 0, int(model.subimage_width), int(model.subimage_height))) > 0.0:
+        return None
+    return [walk(forest, img, ox, oy, t) for t in range(forest.n_trees)]
+
+
+def predict_mask(forest, model, img) -> np.ndarray:
+    """HoughPrediction::predict_mask (:850-905) -> uint8 [h, w]: the mean leaf probability of a window times 255, `as u8`,
+    over the stepwidth x stepwidth square centred on the window (u32 arithmetic, clipped at every border)."""
+    img = np.asarray(img, dtype=np.uint16)
+    h, w = img.shape
+    step = int(model.stepwidth)
+    mask = np.zeros((h, w), dtype=np.uint8)                     # ImageBuffer::new zero-fills (:852)
+    for x, y, ox, oy in _windows(model, w, h):
+        leafs = _leafs(forest, model, img, ox, oy)
+        if leafs is None:
+            continue
+        s = F64(0.0)
+        for L in leafs:
+            s = F64(s + F64(forest.leaf_prob[L]))
+        prob = F64(s / F64(len(leafs)))                         # :881-882
+        pv = as_u8(F64(prob * F64(255.0)))                      # :883
+        for i in range(step):                                   # :884-897
+            for j in range(step):
+                if x + i < step // 2 or y + j < step // 2:
+                    continue
+                if x + i - step // 2 >= w or y + j - step // 2 >= h:
+                    continue
+                mask[y + j - step // 2, x + i - step // 2] = pv
+    return mask
+
+
+def hough_votes(forest, model, img, K):
+    """Voting stage of HoughPrediction::build_hough_image (:760-840), before the blur of :844.  Returns (the u16 image,
+    an object array of the same shape holding every pixel's sum of `valtoadd` as an unbounded Python int): the reference's
+    `+=` on u16 (:832) leaves the residue modulo 2^16 of that sum."""
+    img = np.asarray(img, dtype=np.uint16)
+    h, w = img.shape
+    intr = Intrinsic(K)
+    sums = np.zeros((h, w), dtype=object)
+    for x, y, ox, oy in _windows(model, w, h):
+        p3 = intr.img_to_space([F32(x), F32(y)], F32(img[y, x]))            # :777-779
+        leafs = _leafs(forest, model, img, ox, oy)
+        if leafs is None:
+            continue
+        for L in leafs:
+            lp = F64(forest.leaf_prob[L])
+            if not lp >= 0.95:                                              # :805
+                continue
+            offs = forest.offsets[forest.off_begin[L]:forest.off_begin[L + 1]]
+            valtoadd = (as_usize(F64(F64(255.0) * lp)) // len(offs)) & 0xFFFF   # `as usize / len`, then `as u16` (:807-808)
+            for o in offs:                                                  # :813
+                with np.errstate(over="ignore", invalid="ignore"):
+                    np_ = [F32(p3[k] - F32(o[k])) for k in range(3)]        # :814
+                p2 = intr.space_to_img(np_)                                 # :815
+                nx, ny = as_i32(p2[0]), as_i32(p2[1])                       # :816
+                if nx < 0 or nx >= w or ny < 0 or ny >= h:                  # :818-831
+                    continue
+                sums[ny, nx] += valtoadd                                    # :832
+    image = np.array([[int(v) & 0xFFFF for v in row] for row in sums], dtype=np.uint16).reshape(h, w)
+    return image, sums
