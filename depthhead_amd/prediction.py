@@ -236,6 +236,31 @@ class HoughPrediction:
         check(self._lib.dh_predict_from2dhough(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), vp(K), vp(out)))
         return PredictionResult(out["mid_point"][0].copy(), out["rotation"][0].copy()) if single else out
 
+    # device-resident twins of the four calls above: raw device addresses ([n][h][w] u16 frames; outputs of n*h*w bytes,
+    # n*h*w u16 or n poses) and a hipStream_t handle, as `predict_batch_device`.  Asynchronous.
+    def predict_mask_device(self, frames_ptr: int, n: int, w: int, h: int, mask_ptr: int, stream: int = 0) -> None:
+        check(self._lib.dh_predict_mask_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), vp(mask_ptr),
+                                               C.c_void_p(stream) if stream else None))
+
+    def hough_image_device(self, frames_ptr: int, n: int, w: int, h: int, intrinsic: IntrinsicMatrix, out_ptr: int,
+                           stream: int = 0) -> None:
+        """The votes alone (`build_hough_votes`), before the blur."""
+        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
+        check(self._lib.dh_hough_image_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), vp(K), vp(out_ptr),
+                                              C.c_void_p(stream) if stream else None))
+
+    def build_hough_image_device(self, frames_ptr: int, n: int, w: int, h: int, intrinsic: IntrinsicMatrix, out_ptr: int,
+                                 stream: int = 0) -> None:
+        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
+        check(self._lib.dh_build_hough_image_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), vp(K),
+                                                    vp(out_ptr), C.c_void_p(stream) if stream else None))
+
+    def predict_from2dhough_device(self, frames_ptr: int, n: int, w: int, h: int, intrinsic: IntrinsicMatrix, out_ptr: int,
+                                   stream: int = 0) -> None:
+        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
+        check(self._lib.dh_predict_from2dhough_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), vp(K),
+                                                      vp(out_ptr), C.c_void_p(stream) if stream else None))
+
     def graph_capture(self, frames_ptr: int, n: int, w: int, h: int, intrinsic: IntrinsicMatrix, out_ptr: int,
                       midp_guess_ptr: int | None = None, rot_guess_ptr: int | None = None,
                       guess_mask_ptr: int | None = None) -> None:

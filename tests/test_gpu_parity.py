@@ -488,7 +488,7 @@ def test_batches_larger_than_the_resident_slice(hp_mod, oracle, monkeypatch, tmp
     ref = oracle.predict_batch(forest, model, frames, K)
     # the limit is read once per process: drive the C entry point of a child process with a small slice
     import subprocess, sys, os, json
-    frames_path = str(tmp_path / "dh_slice_frames.npy")
+    frames_path, mask_path = str(tmp_path / "dh_slice_frames.npy"), str(tmp_path / "dh_slice_mask.npy")
     np.save(frames_path, frames)
     code = (
         "import numpy as np, os, sys, json\n"
@@ -498,14 +498,17 @@ def test_batches_larger_than_the_resident_slice(hp_mod, oracle, monkeypatch, tmp
         f"forest = synth.synth_forest(5, 8, {synth.FOREST_SEED_BASE + 180}); model = synth.ModelParams(stepwidth=6)\n"
         f"K = synth.default_intrinsic({w}, {h})\n"
         "with HoughPrediction(forest, model) as hp:\n"
-        "    p = hp.predict_batch(frames, IntrinsicMatrix(K)); m = hp.predict_mask(frames)\n"
-        "print(json.dumps({'mid': p['mid_point'].tolist(), 'rot': p['rotation'].tolist(), 'mask': int(m.astype(np.int64).sum())}))\n")
+        "    p = hp.predict_batch(frames, IntrinsicMatrix(K)); np.save(sys.argv[2], hp.predict_mask(frames))\n"
+        "print(json.dumps({'mid': p['mid_point'].tolist(), 'rot': p['rotation'].tolist()}))\n")
     env = dict(os.environ, DH_MAX_RESIDENT_FRAMES="4")
-    out = subprocess.run([sys.executable, "-c", code, frames_path], capture_output=True, text=True, env=env, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), timeout=300)
+    out = subprocess.run([sys.executable, "-c", code, frames_path, mask_path], capture_output=True, text=True, env=env, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     got = json.loads(out.stdout.strip().splitlines()[-1])
     assert np.array_equal(np.array(got["mid"], dtype=np.float32), ref["mid_point"]) and np.array_equal(np.array(got["rot"]), ref["rotation"])
-    assert got["mask"] == sum(int(oracle.predict_mask(forest, model, f).astype(np.int64).sum()) for f in frames)
+    masks = np.load(mask_path)
+    assert masks.shape == frames.shape
+    for i in range(n):
+        assert np.array_equal(masks[i], oracle.predict_mask(forest, model, frames[i])), f"frame {i}: mask"
 
 
 def test_randomized_differential(hp_mod, oracle):
