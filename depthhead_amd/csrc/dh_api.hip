@@ -80,7 +80,8 @@ static int patch_grid_(const dh_params *p, int w, int h, int *nx, int *ny) {
     return dh_patch_grid_(*p, w, h, nx, ny);
 }
 
-// Entry points run on the predictor's device and leave the caller's current device as they found it.
+// Entry points run on the predictor's device and leave the caller's current device as they found it.  A guard that cannot
+// select the device has set the error message: its owner returns DH_EHIP.
 struct DeviceGuard {
     int prev = -1;
     bool ok = true;
@@ -88,6 +89,7 @@ struct DeviceGuard {
         if (hipGetDevice(&prev) != hipSuccess) prev = -1;
         if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
         else prev = -1;
+        if (!ok) (void)fail(DH_EHIP, "cannot select device %d", dev);
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
@@ -247,7 +249,7 @@ static void free_workspace(dh_predictor *p) {
 
 static int predictor_destroy_(dh_predictor *p) {
     if (!p) return DH_OK;
-    (void)hipSetDevice(p->device);
+    DeviceGuard guard(p->device);
     if (p->own_stream) (void)hipStreamSynchronize(p->own_stream);
     drop_graph(p);
     free_workspace(p);
@@ -290,7 +292,8 @@ static int predictor_create_(const dh_forest *f, const dh_params *prm, int devic
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(DH_EINVAL, "device %d out of range (%d visible)", device, ndev);
-    HIP_TRY(hipSetDevice(device));
+    DeviceGuard guard(device);
+    if (!guard.ok) return DH_EHIP;
 
     dh_predictor *p = new (std::nothrow) dh_predictor;
     if (!p) return fail(DH_ENOMEM, "out of host memory");
@@ -418,7 +421,8 @@ static int predictor_build(dh_predictor *p, const dh_forest *f, const dh_params 
 static int predictor_update_sigma_(dh_predictor *p, float val) {
     if (!p) return fail(DH_EINVAL, "NULL predictor");
     if (val == p->params.gaussian_sigma || val <= 0.0f || val != val) return DH_OK;   // prediction.rs:321-323
-    HIP_TRY(hipSetDevice(p->device));
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
     HIP_TRY(hipDeviceSynchronize());
     p->params.gaussian_sigma = val;
     return build_kernel_table(p);
@@ -549,6 +553,8 @@ static int predictor_set_forking_(dh_predictor *p, int chunks) {
 }
 static int predictor_reserve_(dh_predictor *p, int n, int w, int h) {
     if (!p) return fail(DH_EINVAL, "NULL predictor");
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
     return reserve(p, n, w, h);
 }
 
@@ -754,7 +760,7 @@ static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n,
     if (n == 0) return DH_OK;
     if (n < 0) return fail(DH_EINVAL, "negative batch size");
     DeviceGuard guard(p->device);
-    if (!guard.ok) return fail(DH_EHIP, "cannot select device %d", p->device);
+    if (!guard.ok) return DH_EHIP;
     const int slice = p->debug ? n : std::min(n, max_resident_frames(p));   // the taps index the whole batch
     int rc = reserve(p, slice, w, h);
     if (rc) return rc;
@@ -807,30 +813,38 @@ static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n,
     return DH_OK;
 }
 
-static int stage_frames(dh_predictor *p, const uint16_t *frames, int n, int w, int h);
-static int ensure_frame_staging(dh_predictor *p, size_t fbytes);
-
-template <typename T>
-static int grow_pinned(T **buf, size_t *cap, size_t need) {
-    if (need <= *cap) return DH_OK;
-    if (*buf) (void)hipHostFree(*buf);
-    *buf = nullptr; *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    void *q = nullptr;
-    hipError_t e = hipHostMalloc(&q, want * sizeof(T), hipHostMallocDefault);
-    if (e != hipSuccess) return fail(DH_ENOMEM, "hipHostMalloc(%zu bytes): %s", want * sizeof(T), hipGetErrorString(e));
-    *buf = (T *)q; *cap = want;
+static int ensure_frame_staging(dh_predictor *p, size_t fbytes) {
+    if (fbytes > p->ws_frames_bytes) {
+        HIP_TRY(hipStreamSynchronize(p->own_stream));
+        HIP_TRY(hipStreamSynchronize(p->copy_stream));
+        if (p->ws_frames) (void)hipFree(p->ws_frames);
+        p->ws_frames = nullptr; p->ws_frames_bytes = 0;
+        size_t want = fbytes;
+        int rc = dev_alloc(p, &p->ws_frames, want / sizeof(uint16_t));
+        if (rc) return rc;
+        p->ws_frames_bytes = want;
+    }
     return DH_OK;
 }
+static int stage_frames(dh_predictor *p, const uint16_t *frames, int n, int w, int h) {
+    size_t fbytes = (size_t)n * w * h * sizeof(uint16_t);
+    int rc = ensure_frame_staging(p, fbytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(p->ws_frames, frames, fbytes, hipMemcpyHostToDevice, p->own_stream));
+    return DH_OK;
+}
+
+// Staging buffers that only ever grow: a quarter and 4 096 elements of headroom over `need`, the old contents dropped.
+enum Mem { PINNED, DEVICE };
 template <typename T>
-static int grow_device(T **buf, size_t *cap, size_t need) {
+static int grow(T **buf, size_t *cap, size_t need, Mem mem) {
     if (need <= *cap) return DH_OK;
-    if (*buf) (void)hipFree(*buf);
+    if (*buf) (void)(mem == PINNED ? hipHostFree(*buf) : hipFree(*buf));
     *buf = nullptr; *cap = 0;
     const size_t want = need + need / 4 + 4096;
     void *q = nullptr;
-    hipError_t e = hipMalloc(&q, want * sizeof(T));
-    if (e != hipSuccess) return fail(DH_ENOMEM, "hipMalloc(%zu bytes): %s", want * sizeof(T), hipGetErrorString(e));
+    hipError_t e = mem == PINNED ? hipHostMalloc(&q, want * sizeof(T), hipHostMallocDefault) : hipMalloc(&q, want * sizeof(T));
+    if (e != hipSuccess) return fail(DH_ENOMEM, "%s(%zu bytes): %s", mem == PINNED ? "hipHostMalloc" : "hipMalloc", want * sizeof(T), hipGetErrorString(e));
     *buf = (T *)q; *cap = want;
     return DH_OK;
 }
@@ -845,7 +859,7 @@ struct SmallStage {
 };
 static int small_stage(dh_predictor *p, int m, SmallStage *st) {
     const size_t need = (size_t)m * (sizeof(dh_pose) + 3 * sizeof(double) + 3 * sizeof(float) + 1) + 64;
-    int rc = grow_pinned(&p->pin_small, &p->pin_small_cap, need);      // (only between slices: both streams are idle)
+    int rc = grow(&p->pin_small, &p->pin_small_cap, need, PINNED);      // (only between slices: both streams are idle)
     if (rc) return rc;
     st->poses = (dh_pose *)p->pin_small;
     st->rot = (double *)(st->poses + m);
@@ -853,28 +867,56 @@ static int small_stage(dh_predictor *p, int m, SmallStage *st) {
     st->mask = (uint8_t *)(st->midp + (size_t)m * 3);
     return DH_OK;
 }
-// guesses of frames [f0, f0 + m) -> staging -> the workspace's device arrays, on stream s
-static int upload_guesses(dh_predictor *p, const SmallStage &st, int f0, int m, const float *midp_guess, const double *rot_guess,
-                          const uint8_t *guess_mask, hipStream_t s) {
-    if (midp_guess) {
-        memcpy(st.midp, midp_guess + (size_t)f0 * 3, (size_t)m * 3 * sizeof(float));
-        HIP_TRY(hipMemcpyAsync(p->ws_midp, st.midp, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, s));
+// Per-frame host guesses of a batch, each optional.
+struct Guesses {
+    const float *midp; const double *rot; const uint8_t *mask;
+};
+// Per-slice setup of the host batch paths: the workspace and frame staging for m frames of w x h, and the guesses of
+// frames [f0, f0 + m) through the pinned staging block into the workspace's device arrays on own_stream.
+static int slice_setup(dh_predictor *p, int f0, int m, int w, int h, const Guesses &g, SmallStage *st) {
+    int rc = reserve(p, m, w, h);
+    if (rc == DH_OK) rc = ensure_frame_staging(p, (size_t)m * w * h * sizeof(uint16_t));
+    if (rc == DH_OK) rc = small_stage(p, m, st);
+    if (rc) return rc;
+    hipStream_t s = p->own_stream;
+    if (g.midp) {
+        memcpy(st->midp, g.midp + (size_t)f0 * 3, (size_t)m * 3 * sizeof(float));
+        HIP_TRY(hipMemcpyAsync(p->ws_midp, st->midp, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, s));
     }
-    if (rot_guess) {
-        memcpy(st.rot, rot_guess + (size_t)f0 * 3, (size_t)m * 3 * sizeof(double));
-        HIP_TRY(hipMemcpyAsync(p->ws_rot, st.rot, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (g.rot) {
+        memcpy(st->rot, g.rot + (size_t)f0 * 3, (size_t)m * 3 * sizeof(double));
+        HIP_TRY(hipMemcpyAsync(p->ws_rot, st->rot, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    if (guess_mask) {
-        memcpy(st.mask, guess_mask + f0, (size_t)m);
-        HIP_TRY(hipMemcpyAsync(p->ws_mask, st.mask, (size_t)m, hipMemcpyHostToDevice, s));
+    if (g.mask) {
+        memcpy(st->mask, g.mask + f0, (size_t)m);
+        HIP_TRY(hipMemcpyAsync(p->ws_mask, st->mask, (size_t)m, hipMemcpyHostToDevice, s));
     }
     return DH_OK;
+}
+// Chunk [c0, c0 + cm) of a staged slice -- frames, guesses and poses in the workspace -- on stream s.
+static int predict_staged(dh_predictor *p, int c0, int cm, int w, int h, const float K[9], const Guesses &g, hipStream_t s) {
+    return dh_predict_batch_device(p, p->ws_frames + (size_t)c0 * w * h, cm, w, h, K, g.midp ? p->ws_midp + (size_t)c0 * 3 : nullptr,
+                                   g.rot ? p->ws_rot + (size_t)c0 * 3 : nullptr, g.mask ? p->ws_mask + c0 : nullptr, p->ws_poses + c0, s);
 }
 // poses of the slice: device -> staging on s, wait, -> the caller's array
 static int download_poses(dh_predictor *p, const SmallStage &st, int m, dh_pose *out, hipStream_t s) {
     HIP_TRY(hipMemcpyAsync(st.poses, p->ws_poses, (size_t)m * sizeof(dh_pose), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     memcpy(out, st.poses, (size_t)m * sizeof(dh_pose));
+    return DH_OK;
+}
+// The slice loop of the host batch paths: enqueue(f0, m, &st) sets slice [f0, f0 + m) up (slice_setup) and enqueues its
+// prediction on own_stream; its poses then come back in one copy.  With the taps on, the whole batch is one slice.
+template <typename F>
+static int host_slices(dh_predictor *p, int n, dh_pose *out, F enqueue) {
+    const int slice = p->debug ? n : std::min(n, max_resident_frames(p));
+    for (int f0 = 0; f0 < n; f0 += slice) {
+        const int m = std::min(slice, n - f0);
+        SmallStage st;
+        int rc = enqueue(f0, m, &st);
+        if (rc == DH_OK) rc = download_poses(p, st, m, out + f0, p->own_stream);
+        if (rc) return rc;
+    }
     return DH_OK;
 }
 
@@ -886,31 +928,21 @@ static int predict_batch_(dh_predictor *p, const uint16_t *frames, int n, int w,
     if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch: NULL argument");
     if (n == 0) return DH_OK;
     if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    HIP_TRY(hipSetDevice(p->device));
-    const int slice = p->debug ? n : std::min(n, max_resident_frames(p));
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    const Guesses g{midp_guess, rot_guess, guess_mask};
     hipStream_t s = p->own_stream, cs = p->copy_stream;
     const size_t fpx = (size_t)w * h;
-    for (int f0 = 0; f0 < n; f0 += slice) {      // host batches are staged slice by slice
-        const int m = std::min(slice, n - f0);
-        int rc = reserve(p, m, w, h);
-        if (rc) return rc;
-        rc = ensure_frame_staging(p, (size_t)m * fpx * sizeof(uint16_t));
-        if (rc) return rc;
-        SmallStage st;
-        rc = small_stage(p, m, &st);
-        if (rc == DH_OK) rc = upload_guesses(p, st, f0, m, midp_guess, rot_guess, guess_mask, s);
+    return host_slices(p, n, out, [&](int f0, int m, SmallStage *st) -> int {
+        int rc = slice_setup(p, f0, m, w, h, g, st);
         if (rc) return rc;
         // the parity taps describe ONE device batch: with them on, the slice is a single chunk
         int cstart[DH_STAGE_EVENTS + 1];
         const int nchunks = dh_chunk_plan_(m, p->knobs.stage_chunk, p->debug, cstart);
-        auto predict_chunk = [&](int c0, int cm) {
-            return dh_predict_batch_device(p, p->ws_frames + (size_t)c0 * fpx, cm, w, h, K, midp_guess ? p->ws_midp + (size_t)c0 * 3 : nullptr,
-                                           rot_guess ? p->ws_rot + (size_t)c0 * 3 : nullptr, guess_mask ? p->ws_mask + c0 : nullptr, p->ws_poses + c0, s);
-        };
         if (nchunks == 1) {
             // latency path (single frames, small batches): one copy on the compute stream itself
             HIP_TRY(hipMemcpyAsync(p->ws_frames, frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-            rc = predict_chunk(0, m);
+            rc = predict_staged(p, 0, m, w, h, K, g, s);
             if (rc) { (void)hipStreamSynchronize(s); return rc; }
         } else {
             // Chunk k + 1 is uploaded on copy_stream while the kernels of chunk k run on own_stream.  From page-locked host
@@ -925,15 +957,13 @@ static int predict_batch_(dh_predictor *p, const uint16_t *frames, int n, int w,
                 HIP_TRY(hipMemcpyAsync(p->ws_frames + (size_t)c0 * fpx, frames + (size_t)(f0 + c0) * fpx, (size_t)cm * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, cs));
                 HIP_TRY(hipEventRecord(p->ev_stage[k], cs));
                 HIP_TRY(hipStreamWaitEvent(s, p->ev_stage[k], 0));
-                rc = predict_chunk(c0, cm);
+                rc = predict_staged(p, c0, cm, w, h, K, g, s);
                 if (rc) { (void)hipStreamSynchronize(cs); (void)hipStreamSynchronize(s); return rc; }
             }
         }
         HIP_TRY(hipEventRecord(p->ev_slice, s));
-        rc = download_poses(p, st, m, out + f0, s);
-        if (rc) return rc;
-    }
-    return DH_OK;
+        return DH_OK;
+    });
 }
 
 // Page-locked host memory for frame buffers: uploads from it are asynchronous DMA at PCIe speed.
@@ -957,12 +987,12 @@ static int rle_prepare(dh_predictor *p, const uint8_t *const *bufs, const size_t
     int rc = dh_rle_plan_(bufs, lens, n, p->knobs.host_threads, plan);
     if (rc) return rc;
     const size_t blob_bytes = plan.blob_off[n];
-    rc = grow_pinned(&p->pin_begin, &p->pin_begin_cap, (size_t)n + 1);
-    if (rc == DH_OK) rc = grow_pinned(&p->pin_blob, &p->pin_blob_cap, blob_bytes);
-    if (rc == DH_OK) rc = grow_pinned(&p->pin_runs, &p->pin_runs_cap, std::max<size_t>(plan.nruns, 1));
-    if (rc == DH_OK) rc = grow_device(&p->dev_blob, &p->dev_blob_cap, blob_bytes);
-    if (rc == DH_OK) rc = grow_device(&p->dev_runs, &p->dev_runs_cap, std::max<size_t>(plan.nruns, 1));
-    if (rc == DH_OK) rc = grow_device(&p->dev_begin, &p->dev_begin_cap, (size_t)n + 1);
+    rc = grow(&p->pin_begin, &p->pin_begin_cap, (size_t)n + 1, PINNED);
+    if (rc == DH_OK) rc = grow(&p->pin_blob, &p->pin_blob_cap, blob_bytes, PINNED);
+    if (rc == DH_OK) rc = grow(&p->pin_runs, &p->pin_runs_cap, std::max<size_t>(plan.nruns, 1), PINNED);
+    if (rc == DH_OK) rc = grow(&p->dev_blob, &p->dev_blob_cap, blob_bytes, DEVICE);
+    if (rc == DH_OK) rc = grow(&p->dev_runs, &p->dev_runs_cap, std::max<size_t>(plan.nruns, 1), DEVICE);
+    if (rc == DH_OK) rc = grow(&p->dev_begin, &p->dev_begin_cap, (size_t)n + 1, DEVICE);
     if (rc) return rc;
     memcpy(p->pin_begin, plan.run_begin.data(), ((size_t)n + 1) * sizeof(uint32_t));
     dh_rle_pack_(bufs, lens, n, p->knobs.host_threads, plan, p->pin_blob, (DhRun *)p->pin_runs);
@@ -995,7 +1025,8 @@ static int rle_upload_decode(dh_predictor *p, const std::vector<size_t> &blob_of
 static int biwi_decode_depth_device_(dh_predictor *p, const uint8_t *const *bufs, const size_t *lens, int n, uint16_t *frames_dev,
                                            size_t cap_px, uint32_t *w, uint32_t *h) {
     if (!p || !bufs || !lens || !w || !h) return fail(DH_EINVAL, "dh_biwi_decode_depth_device: NULL argument");
-    HIP_TRY(hipSetDevice(p->device));
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
     HIP_TRY(hipStreamSynchronize(p->own_stream));             // the pinned staging buffers are free
     HIP_TRY(hipStreamSynchronize(p->copy_stream));
     RlePlan plan;
@@ -1023,42 +1054,30 @@ static int predict_batch_rle_(dh_predictor *p, const uint8_t *const *bufs, const
     if (!p || !bufs || !lens || !K || !out) return fail(DH_EINVAL, "dh_predict_batch_rle: NULL argument");
     if (n == 0) return DH_OK;
     if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    HIP_TRY(hipSetDevice(p->device));
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    const Guesses g{midp_guess, rot_guess, guess_mask};
     hipStream_t s = p->own_stream;
-    const int slice = p->debug ? n : std::min(n, max_resident_frames(p));
-    for (int f0 = 0; f0 < n; f0 += slice) {
-        const int m = std::min(slice, n - f0);
+    return host_slices(p, n, out, [&](int f0, int m, SmallStage *st) -> int {
         HIP_TRY(hipStreamSynchronize(s));                         // pinned staging and device blob of the previous slice are free
         HIP_TRY(hipStreamSynchronize(p->copy_stream));
         RlePlan plan;
         int rc = rle_prepare(p, bufs + f0, lens + f0, m, plan);   // validates: nothing launched on failure
         if (rc) return rc;
-        const std::vector<size_t> &blob_off = plan.blob_off;
         const uint32_t W = plan.W, H = plan.H;
-        const int w = (int)W, h = (int)H;
-        rc = reserve(p, m, w, h);
-        if (rc == DH_OK) rc = ensure_frame_staging(p, (size_t)m * W * H * sizeof(uint16_t));
+        rc = slice_setup(p, f0, m, (int)W, (int)H, g, st);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(p->dev_begin, p->pin_begin, ((size_t)m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        SmallStage st;
-        rc = small_stage(p, m, &st);
-        if (rc == DH_OK) rc = upload_guesses(p, st, f0, m, midp_guess, rot_guess, guess_mask, s);
-        if (rc) return rc;
         const int chunk = p->debug ? m : std::min(m, p->knobs.stage_chunk * 2);   // compressed chunks are small: twice the raw chunk
         int ci = 0;
         for (int c0 = 0; c0 < m; c0 += chunk, ++ci) {
             const int cm = std::min(chunk, m - c0);
-            uint16_t *fr = p->ws_frames + (size_t)c0 * W * H;
-            rc = rle_upload_decode(p, blob_off, c0, cm, ci, W, H, fr, s);
-            if (rc == DH_OK)
-                rc = dh_predict_batch_device(p, fr, cm, w, h, K, midp_guess ? p->ws_midp + (size_t)c0 * 3 : nullptr,
-                                             rot_guess ? p->ws_rot + (size_t)c0 * 3 : nullptr, guess_mask ? p->ws_mask + c0 : nullptr, p->ws_poses + c0, s);
+            rc = rle_upload_decode(p, plan.blob_off, c0, cm, ci, W, H, p->ws_frames + (size_t)c0 * W * H, s);
+            if (rc == DH_OK) rc = predict_staged(p, c0, cm, (int)W, (int)H, K, g, s);
             if (rc) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamSynchronize(s); return rc; }
         }
-        rc = download_poses(p, st, m, out + f0, s);
-        if (rc) return rc;
-    }
-    return DH_OK;
+        return DH_OK;
+    });
 }
 
 // ------------------------------------------------------------------ hipGraph capture of one batch
@@ -1066,6 +1085,8 @@ static int predict_batch_rle_(dh_predictor *p, const uint8_t *const *bufs, const
 // launches (k_boxsum ... k_cluster) of one dh_predict_batch_device call are captured once and replayed with one host call.
 static int graph_destroy_(dh_predictor *p) {
     if (!p) return fail(DH_EINVAL, "NULL predictor");
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
     drop_graph(p);
     p->graph_stale = false;
     return DH_OK;
@@ -1076,7 +1097,8 @@ static int graph_capture_(dh_predictor *p, const uint16_t *frames, int n, int w,
     if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_graph_capture: NULL argument");
     if (n <= 0) return fail(DH_EINVAL, "batch size must be positive");
     if (p->debug || p->profiling) return fail(DH_ESTATE, "taps / profiling cannot be captured");
-    HIP_TRY(hipSetDevice(p->device));
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
     int rc = reserve(p, std::min(n, max_resident_frames(p)), w, h);   // every allocation happens before the capture starts
     if (rc) return rc;
     dh_graph_destroy(p);
@@ -1098,6 +1120,8 @@ static int graph_launch_(dh_predictor *p, void *stream) {
     if (!p) return fail(DH_EINVAL, "NULL predictor");
     if (p->graph_stale) return fail(DH_ESTATE, "the captured batch is stale: the workspace was reallocated after dh_graph_capture (larger batch, other frame size or debug taps); capture again");
     if (!p->graph_exec) return fail(DH_ESTATE, "no captured batch (dh_graph_capture)");
+    DeviceGuard guard(p->device);      // (stream 0: the null stream of the predictor's device, where the graph was captured)
+    if (!guard.ok) return DH_EHIP;
     HIP_TRY(hipGraphLaunch(p->graph_exec, (hipStream_t)stream));
     return DH_OK;
 }
@@ -1146,8 +1170,11 @@ static int blur_kernel(dh_predictor *p) {
     return DH_OK;
 }
 
-static int aux_run(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], uint8_t *mask,
-                   uint16_t *hough, hipStream_t s, bool blur = false, dh_pose *poses2d = nullptr) {
+enum : unsigned { AUX_MASK = 1, AUX_VOTES = 2, AUX_BLUR = 4, AUX_POSES = 8 };   // what a call produces (poses: from the blurred votes)
+
+// One resident slice of frames: the mask (AUX_MASK) or the vote image into `img`, the 2-D poses into `poses2d`.
+static int aux_run(dh_predictor *p, unsigned req, const uint16_t *frames, int n, int w, int h, const float K[9], void *img,
+                   dh_pose *poses2d, hipStream_t s) {
     const Geom &g = p->geom;
     float kinv[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, kid[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     if (K) dh_mat3_inv_f32_(K, kinv);
@@ -1164,183 +1191,84 @@ static int aux_run(dh_predictor *p, const uint16_t *frames, int n, int w, int h,
     a.lw = a.sw / 2; a.lh = a.sh / 2; a.nx = g.nx; a.ny = g.ny;
     memcpy(a.k, K ? K : kid, sizeof a.k); memcpy(a.kinv, kinv, sizeof a.kinv);
     a.f = p->dev; a.leaf = p->aux_leaf; a.flags = p->aux_flags;
-    if (mask) {
-        HIP_TRY(hipMemsetAsync(mask, 0, (size_t)n * w * h, s));          // ImageBuffer::new zero-fills (prediction.rs:852)
-        a.mask = mask;
+    if (req & AUX_MASK) {
+        HIP_TRY(hipMemsetAsync(img, 0, (size_t)n * w * h, s));          // ImageBuffer::new zero-fills (prediction.rs:852)
+        a.mask = (uint8_t *)img;
         HIP_TRY(dh_launch_mask(a, s));
     }
-    if (hough) {
+    if (req & AUX_VOTES) {
+        uint16_t *hough = (uint16_t *)img;
         HIP_TRY(hipMemsetAsync(p->aux_u32, 0, (size_t)n * w * h * sizeof(uint32_t), s));
         a.hough32 = p->aux_u32;
         HIP_TRY(dh_launch_hough2d(a, hough, s));
         // gaussian_blur_f32 (prediction.rs:844): horizontal pass into the (now free) 32-bit scratch, vertical pass back
-        if (blur) HIP_TRY(dh_launch_blur_u16(hough, (uint16_t *)p->aux_u32, hough, n, w, h, p->blur_kern, p->blur_klen, s));
-        if (poses2d) HIP_TRY(dh_launch_argmax2d(hough, frames, n, w, h, kinv, poses2d, s));
+        if (req & AUX_BLUR) HIP_TRY(dh_launch_blur_u16(hough, (uint16_t *)p->aux_u32, hough, n, w, h, p->blur_kern, p->blur_klen, s));
+        if (req & AUX_POSES) HIP_TRY(dh_launch_argmax2d(hough, frames, n, w, h, kinv, poses2d, s));
     }
     p->last_n = 0;   // the pose taps do not refer to this run
     return DH_OK;
 }
 
-static int predict_mask_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, uint8_t *mask, void *stream) {
-    if (!p || !frames || !mask) return fail(DH_EINVAL, "dh_predict_mask_device: NULL argument");
+// The mask / 2-D Hough calls: `out` holds n masks (u8 per pixel), n vote images (u16 per pixel) or n poses.  The device twins
+// run on stream s from and into the caller's buffers.  The host twins stage each slice's frames into ws_frames, run it on
+// own_stream into the scratch output (poses: ws_poses), copy that back and wait for it before the next slice.
+static int aux_call(dh_predictor *p, const char *fn, unsigned req, const uint16_t *frames, int n, int w, int h, const float K[9],
+                    void *out, bool host, hipStream_t s = nullptr) {
+    if (!p || !frames || (!K && !(req & AUX_MASK)) || !out) return fail(DH_EINVAL, "%s: NULL argument", fn);
     if (n <= 0) return n == 0 ? DH_OK : fail(DH_EINVAL, "negative batch size");
     DeviceGuard guard(p->device);
-    if (!guard.ok) return fail(DH_EHIP, "cannot select device %d", p->device);
-    const int slice = std::min(n, max_resident_frames(p));
-    for (int f0 = 0; f0 < n; f0 += slice) {
-        const int m = std::min(slice, n - f0);
-        int rc = aux_reserve(p, m, w, h, 0);
-        if (rc == DH_OK) rc = aux_run(p, frames + (size_t)f0 * w * h, m, w, h, nullptr, mask + (size_t)f0 * w * h, nullptr, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return DH_OK;
-}
-
-static int hough_image_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
-                                     uint16_t *out, void *stream) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_hough_image_device: NULL argument");
-    if (n <= 0) return n == 0 ? DH_OK : fail(DH_EINVAL, "negative batch size");
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return fail(DH_EHIP, "cannot select device %d", p->device);
-    const int slice = std::min(n, max_resident_frames(p));
-    for (int f0 = 0; f0 < n; f0 += slice) {
-        const int m = std::min(slice, n - f0);
-        int rc = aux_reserve(p, m, w, h, 0);
-        if (rc == DH_OK) rc = aux_run(p, frames + (size_t)f0 * w * h, m, w, h, K, nullptr, out + (size_t)f0 * w * h, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return DH_OK;
-}
-
-static int ensure_frame_staging(dh_predictor *p, size_t fbytes) {
-    if (fbytes > p->ws_frames_bytes) {
-        HIP_TRY(hipStreamSynchronize(p->own_stream));
-        HIP_TRY(hipStreamSynchronize(p->copy_stream));
-        if (p->ws_frames) (void)hipFree(p->ws_frames);
-        p->ws_frames = nullptr; p->ws_frames_bytes = 0;
-        size_t want = fbytes;
-        int rc = dev_alloc(p, &p->ws_frames, want / sizeof(uint16_t));
-        if (rc) return rc;
-        p->ws_frames_bytes = want;
-    }
-    return DH_OK;
-}
-static int stage_frames(dh_predictor *p, const uint16_t *frames, int n, int w, int h) {
-    size_t fbytes = (size_t)n * w * h * sizeof(uint16_t);
-    int rc = ensure_frame_staging(p, fbytes);
+    if (!guard.ok) return DH_EHIP;
+    int rc = req & AUX_BLUR ? blur_kernel(p) : DH_OK;
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(p->ws_frames, frames, fbytes, hipMemcpyHostToDevice, p->own_stream));
-    return DH_OK;
-}
-
-static int predict_mask_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, uint8_t *mask) {
-    if (!p || !frames || !mask) return fail(DH_EINVAL, "dh_predict_mask: NULL argument");
-    if (n <= 0) return n == 0 ? DH_OK : fail(DH_EINVAL, "negative batch size");
-    HIP_TRY(hipSetDevice(p->device));
+    if (host) s = p->own_stream;
+    const bool poses = req & AUX_POSES;
+    const size_t px = (size_t)w * h, opx = req & AUX_MASK ? 1 : sizeof(uint16_t);    // output bytes per pixel
     const int slice = std::min(n, max_resident_frames(p));
     for (int f0 = 0; f0 < n; f0 += slice) {
         const int m = std::min(slice, n - f0);
-        const size_t ob = (size_t)m * w * h;
-        int rc = aux_reserve(p, m, w, h, ob);
-        if (rc == DH_OK) rc = stage_frames(p, frames + (size_t)f0 * w * h, m, w, h);
-        if (rc == DH_OK) rc = aux_run(p, p->ws_frames, m, w, h, nullptr, (uint8_t *)p->aux_out, nullptr, p->own_stream);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(mask + (size_t)f0 * w * h, p->aux_out, ob, hipMemcpyDeviceToHost, p->own_stream));
-        HIP_TRY(hipStreamSynchronize(p->own_stream));
-    }
-    return DH_OK;
-}
-
-static int hough_image_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], uint16_t *out) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_hough_image: NULL argument");
-    if (n <= 0) return n == 0 ? DH_OK : fail(DH_EINVAL, "negative batch size");
-    HIP_TRY(hipSetDevice(p->device));
-    const int slice = std::min(n, max_resident_frames(p));
-    for (int f0 = 0; f0 < n; f0 += slice) {
-        const int m = std::min(slice, n - f0);
-        const size_t ob = (size_t)m * w * h * sizeof(uint16_t);
-        int rc = aux_reserve(p, m, w, h, ob);
-        if (rc == DH_OK) rc = stage_frames(p, frames + (size_t)f0 * w * h, m, w, h);
-        if (rc == DH_OK) rc = aux_run(p, p->ws_frames, m, w, h, K, nullptr, (uint16_t *)p->aux_out, p->own_stream);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(out + (size_t)f0 * w * h, p->aux_out, ob, hipMemcpyDeviceToHost, p->own_stream));
-        HIP_TRY(hipStreamSynchronize(p->own_stream));
-    }
-    return DH_OK;
-}
-
-// HoughPrediction::build_hough_image in full (prediction.rs:760-845) and predict_parameter_from2dhough (:343-367).
-static int hough2d_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], uint16_t *img_out,
-                          dh_pose *pose_out, hipStream_t s) {
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return fail(DH_EHIP, "cannot select device %d", p->device);
-    int rc = blur_kernel(p);
-    if (rc) return rc;
-    const int slice = std::min(n, max_resident_frames(p));
-    for (int f0 = 0; f0 < n; f0 += slice) {
-        const int m = std::min(slice, n - f0);
-        const size_t ob = (size_t)m * w * h * sizeof(uint16_t);
-        rc = aux_reserve(p, m, w, h, img_out ? 0 : ob);       // no caller image: the blurred image lives in the scratch output
-        if (rc) return rc;
-        uint16_t *img = img_out ? img_out + (size_t)f0 * w * h : (uint16_t *)p->aux_out;
-        rc = aux_run(p, frames + (size_t)f0 * w * h, m, w, h, K, nullptr, img, s, true, pose_out ? pose_out + f0 : nullptr);
-        if (rc) return rc;
-    }
-    return DH_OK;
-}
-
-static int build_hough_image_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
-                                           uint16_t *out, void *stream) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_build_hough_image_device: NULL argument");
-    if (n <= 0) return n == 0 ? DH_OK : fail(DH_EINVAL, "negative batch size");
-    return hough2d_device(p, frames, n, w, h, K, out, nullptr, (hipStream_t)stream);
-}
-
-static int predict_from2dhough_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
-                                             dh_pose *out, void *stream) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_from2dhough_device: NULL argument");
-    if (n <= 0) return n == 0 ? DH_OK : fail(DH_EINVAL, "negative batch size");
-    return hough2d_device(p, frames, n, w, h, K, nullptr, out, (hipStream_t)stream);
-}
-
-static int build_hough_image_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], uint16_t *out) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_build_hough_image: NULL argument");
-    if (n <= 0) return n == 0 ? DH_OK : fail(DH_EINVAL, "negative batch size");
-    HIP_TRY(hipSetDevice(p->device));
-    int rc = blur_kernel(p);
-    if (rc) return rc;
-    const int slice = std::min(n, max_resident_frames(p));
-    for (int f0 = 0; f0 < n; f0 += slice) {
-        const int m = std::min(slice, n - f0);
-        const size_t ob = (size_t)m * w * h * sizeof(uint16_t);
-        rc = aux_reserve(p, m, w, h, ob);
-        if (rc == DH_OK) rc = stage_frames(p, frames + (size_t)f0 * w * h, m, w, h);
-        if (rc == DH_OK) rc = aux_run(p, p->ws_frames, m, w, h, K, nullptr, (uint16_t *)p->aux_out, p->own_stream, true, nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(out + (size_t)f0 * w * h, p->aux_out, ob, hipMemcpyDeviceToHost, p->own_stream));
-        HIP_TRY(hipStreamSynchronize(p->own_stream));
-    }
-    return DH_OK;
-}
-
-static int predict_from2dhough_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], dh_pose *out) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_from2dhough: NULL argument");
-    if (n <= 0) return n == 0 ? DH_OK : fail(DH_EINVAL, "negative batch size");
-    HIP_TRY(hipSetDevice(p->device));
-    int rc = blur_kernel(p);
-    if (rc) return rc;
-    const int slice = std::min(n, max_resident_frames(p));
-    for (int f0 = 0; f0 < n; f0 += slice) {
-        const int m = std::min(slice, n - f0);
-        rc = aux_reserve(p, m, w, h, (size_t)m * w * h * sizeof(uint16_t));
-        if (rc == DH_OK) rc = stage_frames(p, frames + (size_t)f0 * w * h, m, w, h);
+        const size_t ob = (size_t)m * px * opx;
+        uint8_t *dst = poses ? nullptr : (uint8_t *)out + f0 * px * opx;     // the caller's images of the slice
         SmallStage st;
-        if (rc == DH_OK) rc = small_stage(p, m, &st);
-        if (rc == DH_OK) rc = aux_run(p, p->ws_frames, m, w, h, K, nullptr, (uint16_t *)p->aux_out, p->own_stream, true, p->ws_poses);
-        if (rc == DH_OK) rc = download_poses(p, st, m, out + f0, p->own_stream);
+        rc = aux_reserve(p, m, w, h, host || poses ? ob : 0);    // (host twins and poses: the image goes to the scratch output)
+        if (rc == DH_OK && host) rc = stage_frames(p, frames + f0 * px, m, w, h);
+        if (rc == DH_OK && host && poses) rc = small_stage(p, m, &st);
+        if (rc == DH_OK)
+            rc = aux_run(p, req, host ? p->ws_frames : frames + f0 * px, m, w, h, K, host || poses ? p->aux_out : dst,
+                         !poses ? nullptr : host ? p->ws_poses : (dh_pose *)out + f0, s);
+        if (rc == DH_OK && host && poses) rc = download_poses(p, st, m, (dh_pose *)out + f0, s);
         if (rc) return rc;
+        if (host && !poses) {
+            HIP_TRY(hipMemcpyAsync(dst, p->aux_out, ob, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
     }
     return DH_OK;
+}
+
+static int predict_mask_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, uint8_t *mask, void *stream) {
+    return aux_call(p, "dh_predict_mask_device", AUX_MASK, frames, n, w, h, nullptr, mask, false, (hipStream_t)stream);
+}
+static int hough_image_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], uint16_t *out, void *stream) {
+    return aux_call(p, "dh_hough_image_device", AUX_VOTES, frames, n, w, h, K, out, false, (hipStream_t)stream);
+}
+// HoughPrediction::build_hough_image in full (prediction.rs:760-845) and predict_parameter_from2dhough (:343-367).
+static int build_hough_image_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], uint16_t *out, void *stream) {
+    return aux_call(p, "dh_build_hough_image_device", AUX_VOTES | AUX_BLUR, frames, n, w, h, K, out, false, (hipStream_t)stream);
+}
+static int predict_from2dhough_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], dh_pose *out, void *stream) {
+    return aux_call(p, "dh_predict_from2dhough_device", AUX_VOTES | AUX_BLUR | AUX_POSES, frames, n, w, h, K, out, false, (hipStream_t)stream);
+}
+static int predict_mask_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, uint8_t *mask) {
+    return aux_call(p, "dh_predict_mask", AUX_MASK, frames, n, w, h, nullptr, mask, true);
+}
+static int hough_image_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], uint16_t *out) {
+    return aux_call(p, "dh_hough_image", AUX_VOTES, frames, n, w, h, K, out, true);
+}
+static int build_hough_image_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], uint16_t *out) {
+    return aux_call(p, "dh_build_hough_image", AUX_VOTES | AUX_BLUR, frames, n, w, h, K, out, true);
+}
+static int predict_from2dhough_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], dh_pose *out) {
+    return aux_call(p, "dh_predict_from2dhough", AUX_VOTES | AUX_BLUR | AUX_POSES, frames, n, w, h, K, out, true);
 }
 
 // ------------------------------------------------------------------ profiling
@@ -1353,6 +1281,8 @@ static int set_profiling_(dh_predictor *p, int on) {
 static int get_timing_(dh_predictor *p, dh_timing *out) {
     if (!p || !out) return fail(DH_EINVAL, "NULL argument");
     if (!p->ev_valid) return fail(DH_ESTATE, "no profiled batch yet (dh_set_profiling + a batch)");
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
     HIP_TRY(hipEventSynchronize(p->ev[3]));
     HIP_TRY(hipEventElapsedTime(&out->boxsum_ms, p->ev[0], p->ev[4]));
     HIP_TRY(hipEventElapsedTime(&out->traverse_ms, p->ev[4], p->ev[5]));
@@ -1372,50 +1302,48 @@ static int debug_enable_(dh_predictor *p, int on) {
     if (!p->debug) p->dbg_valid = false;
     return DH_OK;
 }
-static int tap_ready(dh_predictor *p) {
+// Runs a tap's body on the predictor's device once the last batch is complete (dbg: a batch that ran with the taps on).
+template <typename F>
+static int with_taps(dh_predictor *p, bool dbg, F body) {
     if (!p) return fail(DH_EINVAL, "NULL predictor");
     if (p->last_n == 0) return fail(DH_ESTATE, "no batch has run on this predictor");
-    hipError_t e = hipSetDevice(p->device);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return fail(DH_EHIP, "sync: %s", hipGetErrorString(e));
-    return DH_OK;
-}
-static int tap_ready_dbg(dh_predictor *p) {
-    int rc = tap_ready(p);
-    if (rc) return rc;
-    if (!p->dbg_valid) return fail(DH_ESTATE, "debug taps were not enabled for the last batch");
-    return DH_OK;
+    if (dbg && !p->dbg_valid) return fail(DH_ESTATE, "debug taps were not enabled for the last batch");
+    return body();
 }
 static int debug_leaf_indices_(dh_predictor *p, int32_t *out, size_t cap) {
-    int rc = tap_ready_dbg(p);
-    if (rc) return rc;
-    size_t n = (size_t)p->last_n * p->geom.npatch * p->n_trees;
-    if (!out || cap < n) return fail(DH_EINVAL, "buffer too small: need %zu elements", n);
-    if (n) HIP_TRY(hipMemcpy(out, p->dbg_leaf, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return DH_OK;
+    return with_taps(p, true, [&]() -> int {
+        size_t n = (size_t)p->last_n * p->geom.npatch * p->n_trees;
+        if (!out || cap < n) return fail(DH_EINVAL, "buffer too small: need %zu elements", n);
+        if (n) HIP_TRY(hipMemcpy(out, p->dbg_leaf, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
 }
 static int debug_patch_flags_(dh_predictor *p, uint8_t *out, size_t cap) {
-    int rc = tap_ready_dbg(p);
-    if (rc) return rc;
-    size_t n = (size_t)p->last_n * p->geom.npatch;
-    if (!out || cap < n) return fail(DH_EINVAL, "buffer too small: need %zu elements", n);
-    if (n) HIP_TRY(hipMemcpy(out, p->dbg_flags, n, hipMemcpyDeviceToHost));
-    return DH_OK;
+    return with_taps(p, true, [&]() -> int {
+        size_t n = (size_t)p->last_n * p->geom.npatch;
+        if (!out || cap < n) return fail(DH_EINVAL, "buffer too small: need %zu elements", n);
+        if (n) HIP_TRY(hipMemcpy(out, p->dbg_flags, n, hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
 }
 static int debug_grids_(dh_predictor *p, uint32_t *pos_grid, uint32_t *rot_grid) {
-    int rc = tap_ready(p);
-    if (rc) return rc;
-    const uint32_t *pg = p->counters + p->cap_frames, *rg = pg + (size_t)p->cap_frames * DH_POSGRID;
-    if (pos_grid) HIP_TRY(hipMemcpy(pos_grid, pg, (size_t)p->last_n * DH_POSGRID * 4, hipMemcpyDeviceToHost));
-    if (rot_grid) HIP_TRY(hipMemcpy(rot_grid, rg, (size_t)p->last_n * DH_GRID3 * 4, hipMemcpyDeviceToHost));
-    return DH_OK;
+    return with_taps(p, false, [&]() -> int {
+        const uint32_t *pg = p->counters + p->cap_frames, *rg = pg + (size_t)p->cap_frames * DH_POSGRID;
+        if (pos_grid) HIP_TRY(hipMemcpy(pos_grid, pg, (size_t)p->last_n * DH_POSGRID * 4, hipMemcpyDeviceToHost));
+        if (rot_grid) HIP_TRY(hipMemcpy(rot_grid, rg, (size_t)p->last_n * DH_GRID3 * 4, hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
 }
 static int debug_hit_counts_(dh_predictor *p, uint32_t *out) {
-    int rc = tap_ready(p);
-    if (rc) return rc;
-    if (!out) return fail(DH_EINVAL, "NULL output");
-    HIP_TRY(hipMemcpy(out, p->counters, (size_t)p->last_n * 4, hipMemcpyDeviceToHost));
-    return DH_OK;
+    return with_taps(p, false, [&]() -> int {
+        if (!out) return fail(DH_EINVAL, "NULL output");
+        HIP_TRY(hipMemcpy(out, p->counters, (size_t)p->last_n * 4, hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
 }
 static int debug_geometry_(dh_predictor *p, int32_t out[10]) {
     if (!p || !out) return fail(DH_EINVAL, "NULL argument");
@@ -1427,49 +1355,50 @@ static int debug_geometry_(dh_predictor *p, int32_t out[10]) {
     return DH_OK;
 }
 static int debug_guesses_(dh_predictor *p, int32_t *out) {
-    int rc = tap_ready_dbg(p);
-    if (rc) return rc;
-    if (!out) return fail(DH_EINVAL, "NULL output");
-    HIP_TRY(hipMemcpy(out, p->dbg_guess, (size_t)p->last_n * 6 * 4, hipMemcpyDeviceToHost));
-    return DH_OK;
+    return with_taps(p, true, [&]() -> int {
+        if (!out) return fail(DH_EINVAL, "NULL output");
+        HIP_TRY(hipMemcpy(out, p->dbg_guess, (size_t)p->last_n * 6 * 4, hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
 }
 static int debug_meanshift_(dh_predictor *p, int which, int32_t *trace, uint32_t *steps) {
-    int rc = tap_ready_dbg(p);
-    if (rc) return rc;
-    if (which < 0 || which > 1) return fail(DH_EINVAL, "which must be 0 or 1");
-    size_t per = (size_t)(p->params.meanshift_iterations + 1) * 3;
-    // device layout is [2][last batch n][...]: the kernel indexed with n_frames = last_n
-    if (trace) HIP_TRY(hipMemcpy(trace, p->dbg_trace + (size_t)which * p->last_n * per, (size_t)p->last_n * per * 4, hipMemcpyDeviceToHost));
-    if (steps) HIP_TRY(hipMemcpy(steps, p->dbg_steps + (size_t)which * p->last_n, (size_t)p->last_n * 4, hipMemcpyDeviceToHost));
-    return DH_OK;
+    return with_taps(p, true, [&]() -> int {
+        if (which < 0 || which > 1) return fail(DH_EINVAL, "which must be 0 or 1");
+        size_t per = (size_t)(p->params.meanshift_iterations + 1) * 3;
+        // device layout is [2][last batch n][...]: the kernel indexed with n_frames = last_n
+        if (trace) HIP_TRY(hipMemcpy(trace, p->dbg_trace + (size_t)which * p->last_n * per, (size_t)p->last_n * per * 4, hipMemcpyDeviceToHost));
+        if (steps) HIP_TRY(hipMemcpy(steps, p->dbg_steps + (size_t)which * p->last_n, (size_t)p->last_n * 4, hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
 }
 static int debug_votes_(dh_predictor *p, int frame, int which, int32_t *out, size_t cap, size_t *count) {
-    int rc = tap_ready(p);
-    if (rc) return rc;
-    if (frame < 0 || frame >= p->last_n || which < 0 || which > 1 || !count) return fail(DH_EINVAL, "bad frame / which / count");
-    // k_emit writes the rotation records only without the leaf histogram or with the taps on
-    if (which == 1 && p->leaf_hits && !p->dbg_valid) return fail(DH_ESTATE, "rotation votes need dh_debug_enable(1) before the batch");
-    if (cap > 0xffffffffull) cap = 0xffffffffull;
-    if (!p->dbg_vcount) { rc = dev_alloc(p, &p->dbg_vcount, 1); if (rc) return rc; }
-    if (cap > p->dbg_votes_cap) {
-        if (p->dbg_votes) (void)hipFree(p->dbg_votes);
-        p->dbg_votes = nullptr; p->dbg_votes_cap = 0;
-        rc = dev_alloc(p, &p->dbg_votes, cap * 4);
+    return with_taps(p, false, [&]() -> int {
+        if (frame < 0 || frame >= p->last_n || which < 0 || which > 1 || !count) return fail(DH_EINVAL, "bad frame / which / count");
+        // k_emit writes the rotation records only without the leaf histogram or with the taps on
+        if (which == 1 && p->leaf_hits && !p->dbg_valid) return fail(DH_ESTATE, "rotation votes need dh_debug_enable(1) before the batch");
+        if (cap > 0xffffffffull) cap = 0xffffffffull;
+        int rc = p->dbg_vcount ? DH_OK : dev_alloc(p, &p->dbg_vcount, 1);
         if (rc) return rc;
-        p->dbg_votes_cap = cap;
-    }
-    HIP_TRY(hipMemset(p->dbg_vcount, 0, 4));
-    VotesDumpArgs a{};
-    a.frame = frame; a.which = which; a.f = p->dev; a.hits = p->hits; a.hit_box = p->hit_box; a.hit_rot = p->hit_rot; a.hit_count = p->counters; a.hits_cap = p->hits_cap;
-    a.out = p->dbg_votes; a.cap = (uint32_t)cap; a.count = p->dbg_vcount;
-    HIP_TRY(dh_launch_votes_dump(a, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    uint32_t c = 0;
-    HIP_TRY(hipMemcpy(&c, p->dbg_vcount, 4, hipMemcpyDeviceToHost));
-    *count = c;
-    size_t ncopy = std::min<size_t>(c, cap);
-    if (ncopy && out) HIP_TRY(hipMemcpy(out, p->dbg_votes, ncopy * 16, hipMemcpyDeviceToHost));
-    return DH_OK;
+        if (cap > p->dbg_votes_cap) {
+            if (p->dbg_votes) (void)hipFree(p->dbg_votes);
+            p->dbg_votes = nullptr; p->dbg_votes_cap = 0;
+            rc = dev_alloc(p, &p->dbg_votes, cap * 4);
+            if (rc) return rc;
+            p->dbg_votes_cap = cap;
+        }
+        HIP_TRY(hipMemset(p->dbg_vcount, 0, 4));
+        VotesDumpArgs a{};
+        a.frame = frame; a.which = which; a.f = p->dev; a.hits = p->hits; a.hit_box = p->hit_box; a.hit_rot = p->hit_rot; a.hit_count = p->counters; a.hits_cap = p->hits_cap;
+        a.out = p->dbg_votes; a.cap = (uint32_t)cap; a.count = p->dbg_vcount;
+        HIP_TRY(dh_launch_votes_dump(a, nullptr));
+        HIP_TRY(hipDeviceSynchronize());
+        uint32_t c = 0;
+        HIP_TRY(hipMemcpy(&c, p->dbg_vcount, 4, hipMemcpyDeviceToHost));
+        *count = c;
+        size_t ncopy = std::min<size_t>(c, cap);
+        if (ncopy && out) HIP_TRY(hipMemcpy(out, p->dbg_votes, ncopy * 16, hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
 }
 
 // ------------------------------------------------------------------ the C ABI

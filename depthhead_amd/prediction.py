@@ -24,6 +24,34 @@ from .forest import Forest
 from .synth import ModelParams
 
 
+def _host_frames(img):
+    """One [H, W] frame or a batch [n, H, W] -> (frames [n, H, W] uint16, single, n, h, w)."""
+    frames = np.ascontiguousarray(img, dtype=np.uint16)
+    single = frames.ndim == 2
+    if single:
+        frames = frames[None]
+    n, h, w = frames.shape
+    return frames, single, n, h, w
+
+
+def _kmat(intrinsic: "IntrinsicMatrix"):
+    """The camera matrix as a C float[9]: passed as an argument, it lives until the call returns."""
+    return (C.c_float * 9).from_buffer_copy(np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9))
+
+
+def _guesses(n: int, midp_guess, rot_guess, guess_mask):
+    """Per-frame host guesses as contiguous [n, 3] f32, [n, 3] f64 and [n] u8 arrays; None stays None."""
+    mg = None if midp_guess is None else np.ascontiguousarray(midp_guess, dtype=np.float32).reshape(n, 3)
+    rg = None if rot_guess is None else np.ascontiguousarray(rot_guess, dtype=np.float64).reshape(n, 3)
+    gm = None if guess_mask is None else np.ascontiguousarray(guess_mask, dtype=np.uint8).reshape(n)
+    return mg, rg, gm
+
+
+def _stream(stream: int):
+    """hipStream_t argument: 0 is the null stream."""
+    return C.c_void_p(stream) if stream else None
+
+
 class IntrinsicMatrix:
     """Row-major 3x3 f32 camera matrix (src/types.rs:405)."""
 
@@ -136,12 +164,9 @@ class HoughPrediction:
         if frames.ndim != 3:
             raise ValueError("frames must be [n, H, W]")
         n, h, w = frames.shape
-        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
-        mg = None if midp_guess is None else np.ascontiguousarray(midp_guess, dtype=np.float32).reshape(n, 3)
-        rg = None if rot_guess is None else np.ascontiguousarray(rot_guess, dtype=np.float64).reshape(n, 3)
-        gm = None if guess_mask is None else np.ascontiguousarray(guess_mask, dtype=np.uint8).reshape(n)
+        mg, rg, gm = _guesses(n, midp_guess, rot_guess, guess_mask)
         out = np.zeros(n, dtype=POSE_DTYPE)
-        check(self._lib.dh_predict_batch(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), vp(K), vp(mg),
+        check(self._lib.dh_predict_batch(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic), vp(mg),
                                          vp(rg), vp(gm), vp(out)))
         return out
 
@@ -157,12 +182,9 @@ class HoughPrediction:
         biwi.rs:81-103): decoded on the device, then predicted.  -> POSE_DTYPE[n]."""
         n = len(payloads)
         bufs, ptrs, lens = self._payload_arrays(payloads)
-        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
-        mg = None if midp_guess is None else np.ascontiguousarray(midp_guess, dtype=np.float32).reshape(n, 3)
-        rg = None if rot_guess is None else np.ascontiguousarray(rot_guess, dtype=np.float64).reshape(n, 3)
-        gm = None if guess_mask is None else np.ascontiguousarray(guess_mask, dtype=np.uint8).reshape(n)
+        mg, rg, gm = _guesses(n, midp_guess, rot_guess, guess_mask)
         out = np.zeros(n, dtype=POSE_DTYPE)
-        check(self._lib.dh_predict_batch_rle(self._ph, ptrs, lens, C.c_int(n), vp(K), vp(mg), vp(rg), vp(gm), vp(out)))
+        check(self._lib.dh_predict_batch_rle(self._ph, ptrs, lens, C.c_int(n), _kmat(intrinsic), vp(mg), vp(rg), vp(gm), vp(out)))
         return out
 
     def decode_depth_device(self, payloads, frames_ptr: int | None = None, cap_px: int = 0) -> tuple[int, int]:
@@ -179,20 +201,15 @@ class HoughPrediction:
                              guess_mask_ptr: int | None = None, stream: int = 0) -> None:
         """Device-resident batch: raw device addresses (e.g. `tensor.data_ptr()`) and a hipStream_t
         handle (`torch.cuda.current_stream().cuda_stream`).  Asynchronous."""
-        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
-        check(self._lib.dh_predict_batch_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), vp(K),
+        check(self._lib.dh_predict_batch_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic),
                                                 vp(midp_guess_ptr), vp(rot_guess_ptr), vp(guess_mask_ptr), vp(out_ptr),
-                                                C.c_void_p(stream) if stream else None))
+                                                _stream(stream)))
 
     # ---- sibling consumers of the walk (prediction.rs:760-905) -----------------------------
     def predict_mask(self, img) -> np.ndarray:
         """prediction.rs:850-905: uint8 mask [H, W] (or [n, H, W] for a batch) of per-window head
         probability * 255."""
-        frames = np.ascontiguousarray(img, dtype=np.uint16)
-        single = frames.ndim == 2
-        if single:
-            frames = frames[None]
-        n, h, w = frames.shape
+        frames, single, n, h, w = _host_frames(img)
         out = np.zeros((n, h, w), dtype=np.uint8)
         check(self._lib.dh_predict_mask(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), vp(out)))
         return out[0] if single else out
@@ -200,77 +217,60 @@ class HoughPrediction:
     def build_hough_votes(self, img, intrinsic: IntrinsicMatrix) -> np.ndarray:
         """Voting stage of `build_hough_image` (prediction.rs:760-840): the uint16 image BEFORE
         imageproc's gaussian_blur_f32 (:844), which is an external crate and is not applied here."""
-        frames = np.ascontiguousarray(img, dtype=np.uint16)
-        single = frames.ndim == 2
-        if single:
-            frames = frames[None]
-        n, h, w = frames.shape
-        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
+        frames, single, n, h, w = _host_frames(img)
         out = np.zeros((n, h, w), dtype=np.uint16)
-        check(self._lib.dh_hough_image(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), vp(K), vp(out)))
+        check(self._lib.dh_hough_image(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic), vp(out)))
         return out[0] if single else out
 
     def build_hough_image(self, img, intrinsic: IntrinsicMatrix) -> np.ndarray:
         """prediction.rs:760-845 in full: the votes blurred by imageproc's gaussian_blur_f32(sigma = gaussian_sigma)
         (external crate, restated from its published algorithm: parity unpinned)."""
-        frames = np.ascontiguousarray(img, dtype=np.uint16)
-        single = frames.ndim == 2
-        if single:
-            frames = frames[None]
-        n, h, w = frames.shape
-        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
+        frames, single, n, h, w = _host_frames(img)
         out = np.zeros((n, h, w), dtype=np.uint16)
-        check(self._lib.dh_build_hough_image(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), vp(K), vp(out)))
+        check(self._lib.dh_build_hough_image(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic),
+                                             vp(out)))
         return out[0] if single else out
 
     def predict_parameter_from2dhough(self, img, intrinsic: IntrinsicMatrix):
         """prediction.rs:343-367: head position from the argmax of the blurred 2-D Hough image; rotation is always
         zero there.  One frame -> PredictionResult, a batch [n, H, W] -> POSE_DTYPE[n]."""
-        frames = np.ascontiguousarray(img, dtype=np.uint16)
-        single = frames.ndim == 2
-        if single:
-            frames = frames[None]
-        n, h, w = frames.shape
-        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
+        frames, single, n, h, w = _host_frames(img)
         out = np.zeros(n, dtype=POSE_DTYPE)
-        check(self._lib.dh_predict_from2dhough(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), vp(K), vp(out)))
+        check(self._lib.dh_predict_from2dhough(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic),
+                                               vp(out)))
         return PredictionResult(out["mid_point"][0].copy(), out["rotation"][0].copy()) if single else out
 
     # device-resident twins of the four calls above: raw device addresses ([n][h][w] u16 frames; outputs of n*h*w bytes,
     # n*h*w u16 or n poses) and a hipStream_t handle, as `predict_batch_device`.  Asynchronous.
     def predict_mask_device(self, frames_ptr: int, n: int, w: int, h: int, mask_ptr: int, stream: int = 0) -> None:
         check(self._lib.dh_predict_mask_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), vp(mask_ptr),
-                                               C.c_void_p(stream) if stream else None))
+                                               _stream(stream)))
 
     def hough_image_device(self, frames_ptr: int, n: int, w: int, h: int, intrinsic: IntrinsicMatrix, out_ptr: int,
                            stream: int = 0) -> None:
         """The votes alone (`build_hough_votes`), before the blur."""
-        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
-        check(self._lib.dh_hough_image_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), vp(K), vp(out_ptr),
-                                              C.c_void_p(stream) if stream else None))
+        check(self._lib.dh_hough_image_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic),
+                                              vp(out_ptr), _stream(stream)))
 
     def build_hough_image_device(self, frames_ptr: int, n: int, w: int, h: int, intrinsic: IntrinsicMatrix, out_ptr: int,
                                  stream: int = 0) -> None:
-        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
-        check(self._lib.dh_build_hough_image_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), vp(K),
-                                                    vp(out_ptr), C.c_void_p(stream) if stream else None))
+        check(self._lib.dh_build_hough_image_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h),
+                                                    _kmat(intrinsic), vp(out_ptr), _stream(stream)))
 
     def predict_from2dhough_device(self, frames_ptr: int, n: int, w: int, h: int, intrinsic: IntrinsicMatrix, out_ptr: int,
                                    stream: int = 0) -> None:
-        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
-        check(self._lib.dh_predict_from2dhough_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), vp(K),
-                                                      vp(out_ptr), C.c_void_p(stream) if stream else None))
+        check(self._lib.dh_predict_from2dhough_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h),
+                                                      _kmat(intrinsic), vp(out_ptr), _stream(stream)))
 
     def graph_capture(self, frames_ptr: int, n: int, w: int, h: int, intrinsic: IntrinsicMatrix, out_ptr: int,
                       midp_guess_ptr: int | None = None, rot_guess_ptr: int | None = None,
                       guess_mask_ptr: int | None = None) -> None:
         """Capture one device-resident batch into a hipGraph (pointers are baked in)."""
-        K = np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9)
-        check(self._lib.dh_graph_capture(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), vp(K),
+        check(self._lib.dh_graph_capture(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic),
                                          vp(midp_guess_ptr), vp(rot_guess_ptr), vp(guess_mask_ptr), vp(out_ptr)))
 
     def graph_launch(self, stream: int = 0) -> None:
-        check(self._lib.dh_graph_launch(self._ph, C.c_void_p(stream) if stream else None))
+        check(self._lib.dh_graph_launch(self._ph, _stream(stream)))
 
     def reserve(self, n: int, w: int, h: int) -> None:
         check(self._lib.dh_predictor_reserve(self._ph, C.c_int(n), C.c_int(w), C.c_int(h)))
