@@ -24,6 +24,9 @@
         hipError_t e_ = (expr);                                                                    \
         if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? DH_ENOMEM : DH_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+#define TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)      // a DH_* call's failure returns at once
+// a failed HIP call as DH_EHIP, the message naming the step
+static int hip_step(hipError_t e, const char *what) { return e == hipSuccess ? DH_OK : fail(DH_EHIP, "%s: %s", what, hipGetErrorString(e)); }
 
 // ------------------------------------------------------------------ roctx ranges (tracing)
 // With profiling on (dh_set_profiling) every kernel launch of a batch sits inside a named roctx range on the host thread --
@@ -94,9 +97,97 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
+// ------------------------------------------------------------------ owned memory
+// One device (hipMalloc) or page-locked host (hipHostMalloc) allocation of cap() elements of T.  Move-only: the memory goes
+// with reset(), the next alloc(), an assignment and the destructor.  Every buffer of a predictor is one of these.
+enum Mem { DEVICE, PINNED };
+template <typename T, Mem M = DEVICE>
+class Buf {
+    T *ptr_ = nullptr;
+    size_t cap_ = 0;
+  public:
+    Buf() = default;
+    Buf(Buf &&o) noexcept : ptr_(o.ptr_), cap_(o.cap_) { o.ptr_ = nullptr; o.cap_ = 0; }
+    Buf &operator=(Buf &&o) noexcept {
+        if (this != &o) { reset(); ptr_ = o.ptr_; cap_ = o.cap_; o.ptr_ = nullptr; o.cap_ = 0; }
+        return *this;
+    }
+    ~Buf() { reset(); }
+    T *get() const { return ptr_; }
+    size_t cap() const { return cap_; }
+    explicit operator bool() const { return ptr_ != nullptr; }
+    void reset() {
+        if (ptr_) (void)(M == PINNED ? hipHostFree(ptr_) : hipFree(ptr_));
+        ptr_ = nullptr; cap_ = 0;
+    }
+    // The old memory is freed first.  At least one element is allocated: an empty buffer still has an address.
+    int alloc(size_t count) {
+        reset();
+        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+        void *q = nullptr;
+        hipError_t e = M == PINNED ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
+        if (e != hipSuccess) return fail(DH_ENOMEM, "%s(%zu bytes): %s", M == PINNED ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
+        ptr_ = (T *)q; cap_ = count;
+        return DH_OK;
+    }
+    // Staging that only ever grows: a quarter and 4 096 elements of headroom over `need`, the old contents dropped.
+    int grow(size_t need) { return need <= cap_ ? DH_OK : alloc(need + need / 4 + 4096); }
+};
+
 // ------------------------------------------------------------------ predictor
 #define DH_MAX_CHUNKS 8
 #define DH_MIN_CHUNK_FRAMES 16
+
+// Everything reserve() sizes for a batch of frames of one geometry.  It is replaced as a whole: a captured batch has its
+// pointers baked in, so replacing it drops the graph (free_workspace).
+struct Workspace {
+    Geom geom;
+    int cap_frames = 0;
+    Buf<HitRec> hits;
+    Buf<HitBox> hit_box;
+    Buf<HitRot> hit_rot;
+    uint32_t hits_cap = 0;             // hit records per frame
+    Buf<uint32_t> box;                 // [cap][box_rows][m][box_plane] rectangle-sum images (uniform path)
+    Buf<unsigned long long> box_mask;  // [cap][ceil(box_rows / 32)][box_parts] which lanes wrote non-zero sums last time (BoxArgs::blk_mask)
+    int blk_shift = 5;                 // log2 height of k_boxsum's mask blocks in this workspace (BoxArgs::blk_shift)
+    Buf<uint32_t> tile_list;           // [DH_MAX_CHUNKS][8][ceil(cap / 8) * tiles] + [DH_MAX_CHUNKS][8] counts behind it (k_tile_list)
+    size_t tile_list_stride = 0;       // entries per x
+    Buf<uint32_t> win_patch;           // [cap][win_cap] window list: position in the window grid
+    Buf<uint8_t> win_leaf;             // [cap][T][win_cap] window list: leaf per tree (u16 entries for forests of <= 65 535 leaves, else i32)
+    int leaf_ls = 2;                   // log2 of its entry size
+    Buf<uint32_t> pre_region;          // [pre_cap][2][64^3] the cells of both accumulators around the initial guesses, gathered by k_region (small batches with many hit records)
+    int pre_cap = 0;
+    uint32_t pre_min_hits = 0;         // frames with fewer hit records are gathered by k_cluster alone
+    Buf<uint32_t> counters;            // the per-batch counter block: reached only through `lay` and the accessors below
+    CounterLayout lay;
+    Buf<dh_pose> poses;                // [cap] host entry points: poses and guesses of a slice on the device
+    Buf<float> midp;
+    Buf<double> rot;
+    Buf<uint8_t> mask;
+    Buf<uint16_t> frames;              // host entry points: frame staging (ensure_frame_staging)
+    // leaf-id outputs for predict_mask / the 2-D Hough image, allocated on first use (aux_reserve)
+    Buf<int32_t> aux_leaf;
+    Buf<uint8_t> aux_flags;
+    Buf<uint32_t> aux_u32;
+    int aux_cap = 0;
+    Buf<uint8_t> aux_out;
+    // taps
+    Buf<int32_t> dbg_leaf;
+    Buf<uint8_t> dbg_flags;
+    Buf<int32_t> dbg_guess, dbg_trace;
+    Buf<uint32_t> dbg_steps;
+    Buf<int32_t> dbg_votes;            // 16-byte vote records (debug_votes_)
+    Buf<uint32_t> dbg_vcount;
+    bool dbg_valid = false;
+
+    // frame f0's entries of the counter block (CounterLayout, dh_host.h)
+    uint32_t *hit_count(int f0) const { return counters.get() + lay.hit_count + f0; }
+    uint32_t *pos_grid(int f0) const { return counters.get() + lay.pos_grid + (size_t)f0 * DH_POSGRID; }
+    uint32_t *rot_grid(int f0) const { return counters.get() + lay.rot_grid + (size_t)f0 * DH_GRID3; }
+    uint8_t *tile_flags(int f0) const { return (uint8_t *)(counters.get() + lay.tile_flags) + (size_t)f0 * lay.tiles; }
+    uint32_t *win_count(int f0) const { return counters.get() + lay.win_count + (size_t)f0 * lay.tiles; }
+    uint32_t *leaf_hits(int f0) const { return lay.leaves ? counters.get() + lay.leaf_hits + (size_t)f0 * lay.leaves : nullptr; }
+};
 
 struct dh_predictor {
     int device = 0;
@@ -104,90 +195,47 @@ struct dh_predictor {
     dh_params params{};
     uint32_t n_trees = 0, n_nodes = 0, n_leaves = 0, n_off = 0, n_rot = 0, max_depth = 0;
     DevForest dev{};
-    std::vector<void *> forest_allocs;
-    float *kern_r2 = nullptr;    // device, DH_KERN_R2 floats: the mean-shift kernel by squared distance
-    uint16_t *zeros = nullptr;   // device, 64 zero bytes (k_boxsum reads them for columns right of the image)
+    std::vector<Buf<uint8_t>> forest;   // the tables `dev` points into (forest_alloc)
+    Buf<float> kern_r2;          // DH_KERN_R2 floats: the mean-shift kernel by squared distance
+    Buf<uint16_t> zeros;         // 64 zero bytes (k_boxsum reads them for columns right of the image)
     bool f_uniform = false;      // forest has one split-rectangle size
     int f_rw = 0, f_rh = 0;
-    void *nodes_g = nullptr;     // NodeG[n_nodes]: general-path nodes with integer split bounds (patches up to 255 x 255), else NULL
-    void *nodes_u = nullptr;     // 16-byte compact nodes for the current region layout (uniform path)
-    void *nodes_a = nullptr;     // NodeU[n_nodes + n_amb + 1]: the same nodes as the walk table of walk_absorb (children as byte offsets), or NULL
-    uint32_t *amb_flag = nullptr; // device word: number of nodes with an ambiguity band (k_nodes_compact's probe pass)
-    uint32_t *amb_list = nullptr; // device: their indices (at most DH_AMB_CAP)
+    Buf<NodeG> nodes_g;          // [n_nodes] general-path nodes with integer split bounds (patches up to 255 x 255), else empty
+    Buf<uint4> nodes_u;          // 16-byte compact nodes for the current region layout (uniform path)
+    Buf<uint4> nodes_a;          // NodeU[n_nodes + n_amb + 1]: the same nodes as the walk table of walk_absorb (children as byte offsets), or empty
+    Buf<uint32_t> amb_flag;      // one word: number of nodes with an ambiguity band (k_nodes_compact's probe pass)
+    Buf<uint32_t> amb_list;      // their indices (at most DH_AMB_CAP)
     uint32_t n_amb = 0;
     bool absorb_ok = false;      // the uniform path walks nodes_a (at most DH_AMB_CAP ambiguous nodes, table offsets fit 32 bits)
-    uint32_t *top_tab = nullptr; // [T][2^top_levels] {offsets, ilo} heap + [T][2^top_levels] entry offsets (k_top_build), copied to LDS by every tile
+    Buf<uint32_t> top_tab;       // [T][2^top_levels] {offsets, ilo} heap + [T][2^top_levels] entry offsets (k_top_build), copied to LDS by every tile
     int top_levels = -1;         // DH_TOP_LEVELS, or -1: choose_tile decides per geometry
     long long nodes_u_key = 0;   // (ss_row, swizzle) the compact nodes were built for
+    Buf<uint32_t> gen;           // [DH_MAX_CHUNKS] tile-flag tags, one per kernel sequence in flight (BoxArgs::gen)
     hipStream_t own_stream = nullptr;
     hipStream_t copy_stream = nullptr;    // host entry points: uploads run here, ahead of the kernels on own_stream
     hipEvent_t ev_stage[DH_STAGE_EVENTS] = {};   // chunk k uploaded (recorded on an upload stream, waited for on own_stream)
     hipEvent_t ev_slice = nullptr;        // the kernels that read the staging buffers are done (recorded on own_stream)
+    Buf<uint8_t, PINNED> pin_small;       // page-locked staging of a slice's small host arrays: poses out, guesses in (small_stage)
     // run-length coded input (dh_predict_batch_rle): pinned staging + device copies of payload blob and run table
-    uint8_t *pin_small = nullptr; size_t pin_small_cap = 0;   // page-locked staging of a slice's small host arrays: poses out, guesses in (small_stage)
-    uint8_t *pin_blob = nullptr;  size_t pin_blob_cap = 0;
-    uint2 *pin_runs = nullptr;    size_t pin_runs_cap = 0;
-    uint32_t *pin_begin = nullptr; size_t pin_begin_cap = 0;
-    uint8_t *dev_blob = nullptr;  size_t dev_blob_cap = 0;
-    uint2 *dev_runs = nullptr;    size_t dev_runs_cap = 0;
-    uint32_t *dev_begin = nullptr; size_t dev_begin_cap = 0;
+    Buf<uint8_t, PINNED> pin_blob;
+    Buf<uint2, PINNED> pin_runs;
+    Buf<uint32_t, PINNED> pin_begin;
+    Buf<uint8_t> dev_blob;
+    Buf<uint2> dev_runs;
+    Buf<uint32_t> dev_begin;
     int chunks = 1;                       // sub-batches per call (env DH_CHUNKS)
     hipStream_t aux_stream[DH_MAX_CHUNKS - 1] = {};
     hipEvent_t ev_fork = nullptr, ev_join[DH_MAX_CHUNKS - 1] = {};
-    // workspace
-    Geom geom;
-    int cap_frames = 0;
-    uint16_t *ws_frames = nullptr;   // host-API staging only
-    size_t ws_frames_bytes = 0;
-    HitRec *hits = nullptr;
-    HitBox *hit_box = nullptr;
-    HitRot *hit_rot = nullptr;
-    uint32_t *box = nullptr;         // [cap][box_rows][m][box_plane] rectangle-sum images (uniform path)
-    uint32_t *tile_list = nullptr;  // [DH_MAX_CHUNKS][8][ceil(cap / 8) * tiles] + [DH_MAX_CHUNKS][8] counts behind it (k_tile_list)
-    size_t tile_list_stride = 0;    // entries per x
-    unsigned long long *box_mask = nullptr;   // [cap][ceil(box_rows / 32)][box_parts] which lanes wrote non-zero sums last time (BoxArgs::blk_mask)
-    uint32_t *win_patch = nullptr;   // [cap][win_cap] window list: position in the window grid
-    uint8_t *win_leaf = nullptr;     // [cap][T][win_cap] window list: leaf per tree (u16 entries for forests of <= 65 535 leaves, else i32)
-    int leaf_ls = 2;                 // log2 of its entry size
-    uint32_t *leaf_hits = nullptr;   // [cap][n_leaves] rotation-vote histogram (inside `counters`), only for forests of <= DH_LEAF_HIST_MAX leaves
-    size_t zero_words = 0;           // words of `counters` zeroed before every batch
-    uint32_t *gen = nullptr;         // [DH_MAX_CHUNKS] tile-flag tags, one per kernel sequence in flight (BoxArgs::gen)
-    size_t zero_lo = 0, zero_hi = 0; // the tile flags' words inside `counters`: [zero_lo, zero_hi)
-    int blk_shift = 5;               // log2 height of k_boxsum's mask blocks in this workspace (BoxArgs::blk_shift)
-    uint32_t hits_cap = 0;
-    uint32_t *pre_region = nullptr;  // [pre_cap][2][64^3] the cells of both accumulators around the initial guesses, gathered by k_region (small batches with many hit records)
-    int pre_cap = 0;
-    uint32_t pre_min_hits = 0;       // frames with fewer hit records are gathered by k_cluster alone
-    uint32_t *counters = nullptr;    // [n] hit_count | [n][400] pos_grid | [n][8000] rot_grid (one memset)
-    dh_pose *ws_poses = nullptr;
-    float *ws_midp = nullptr;
-    double *ws_rot = nullptr;
-    uint8_t *ws_mask = nullptr;
-    float *blur_kern = nullptr;      // device: gaussian_kernel_f32(gaussian_sigma) of the 2-D Hough variant, built on first use
+    Workspace ws;
+    Buf<float> blur_kern;        // gaussian_kernel_f32(gaussian_sigma) of the 2-D Hough variant, built on first use
     int blur_klen = 0;
     float blur_sigma = 0.0f;
-    // leaf-id outputs for predict_mask / the 2-D Hough image, allocated on first use
-    int32_t *aux_leaf = nullptr;
-    uint8_t *aux_flags = nullptr;
-    uint32_t *aux_u32 = nullptr;
-    void *aux_out = nullptr;
-    size_t aux_out_bytes = 0;
-    int aux_cap = 0;
     // captured batch (hipGraph)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     bool capturing = false;          // inside dh_graph_capture: one ordered pass on the capture stream
     bool graph_stale = false;        // the workspace a captured batch points into was reallocated: dh_graph_launch refuses
-    // taps
-    bool debug = false;
-    int32_t *dbg_leaf = nullptr;
-    uint8_t *dbg_flags = nullptr;
-    int32_t *dbg_guess = nullptr, *dbg_trace = nullptr;
-    uint32_t *dbg_steps = nullptr;
-    int32_t *dbg_votes = nullptr;
-    size_t dbg_votes_cap = 0;
-    uint32_t *dbg_vcount = nullptr;
-    bool dbg_valid = false;
+    bool debug = false;              // taps
     // last batch
     int last_n = 0;
     const uint16_t *last_frames = nullptr;
@@ -195,23 +243,24 @@ struct dh_predictor {
     bool profiling = false;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // start, emit end, vote end, cluster end, boxsum end, traverse end
     bool ev_valid = false;
+#ifdef DH_PROFILING_KNOBS
+    Buf<unsigned long long> trav_stamps, cl_stamps;   // DH_TRAV_STAMPS / DH_CL_STAMPS: cycles per phase, allocated on first use
+#endif
 };
 
+// A table of the forest, owned by p->forest; the kernels see it through DevForest.
 template <typename T>
-static int dev_alloc(dh_predictor *p, T **out, size_t count, bool track_forest = false) {
-    void *ptr = nullptr;
-    size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    hipError_t e = hipMalloc(&ptr, bytes);
-    if (e != hipSuccess) return fail(DH_ENOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
-    if (track_forest) p->forest_allocs.push_back(ptr);
-    *out = (T *)ptr;
+static int forest_alloc(dh_predictor *p, T **out, size_t count) {
+    Buf<uint8_t> b;
+    TRY(b.alloc(std::max<size_t>(count, 1) * sizeof(T)));
+    *out = (T *)b.get();
+    p->forest.push_back(std::move(b));
     return DH_OK;
 }
 template <typename T>
 static int upload(dh_predictor *p, const T **out, const std::vector<T> &v) {
     T *d = nullptr;
-    int rc = dev_alloc(p, &d, v.size(), true);
-    if (rc) return rc;
+    TRY(forest_alloc(p, &d, v.size()));
     if (!v.empty()) HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     *out = d;
     return DH_OK;
@@ -220,7 +269,7 @@ static int upload(dh_predictor *p, const T **out, const std::vector<T> &v) {
 static int build_kernel_table(dh_predictor *p) {
     std::vector<float> r2;
     dh_build_kernel_r2_(p->params.gaussian_sigma, r2, DH_KERN_R2);    // get_or_build_kernel caches it per sigma (prediction.rs:310-317)
-    HIP_TRY(hipMemcpy(p->kern_r2, r2.data(), r2.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->kern_r2.get(), r2.data(), r2.size() * sizeof(float), hipMemcpyHostToDevice));
     return DH_OK;
 }
 
@@ -233,45 +282,23 @@ static void drop_graph(dh_predictor *p) {
 static void free_workspace(dh_predictor *p) {
     // a captured batch has the old workspace pointers baked in: replaying it would touch freed memory
     if (p->graph_exec) { drop_graph(p); p->graph_stale = true; }
-    void *ptrs[] = {p->tile_list, p->box_mask, p->pre_region, p->box, p->win_patch, p->win_leaf, p->aux_leaf, p->aux_flags, p->aux_u32, p->aux_out, p->ws_frames, p->hits, p->hit_box, p->hit_rot, p->counters, p->ws_poses, p->ws_midp, p->ws_rot, p->ws_mask, p->dbg_leaf,
-                    p->dbg_flags, p->dbg_guess, p->dbg_trace, p->dbg_steps, p->dbg_votes, p->dbg_vcount};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
-    p->pre_region = nullptr; p->pre_cap = 0; p->box_mask = nullptr; p->tile_list = nullptr; p->tile_list_stride = 0;
-    p->box = nullptr; p->win_patch = nullptr; p->win_leaf = nullptr; p->leaf_hits = nullptr; p->zero_words = 0;
-    p->aux_leaf = nullptr; p->aux_flags = nullptr; p->aux_u32 = nullptr; p->aux_out = nullptr; p->aux_out_bytes = 0; p->aux_cap = 0;
-    p->ws_frames = nullptr; p->hits = nullptr; p->hit_box = nullptr; p->hit_rot = nullptr; p->counters = nullptr; p->ws_poses = nullptr; p->ws_midp = nullptr;
-    p->ws_rot = nullptr; p->ws_mask = nullptr; p->dbg_leaf = nullptr; p->dbg_flags = nullptr; p->dbg_guess = nullptr;
-    p->dbg_trace = nullptr; p->dbg_steps = nullptr; p->dbg_votes = nullptr; p->dbg_vcount = nullptr;
-    p->ws_frames_bytes = 0; p->dbg_votes_cap = 0; p->cap_frames = 0; p->hits_cap = 0; p->dbg_valid = false;
-    p->geom = Geom();
+    p->ws = Workspace{};
 }
 
 static int predictor_destroy_(dh_predictor *p) {
     if (!p) return DH_OK;
-    DeviceGuard guard(p->device);
+    DeviceGuard guard(p->device);      // (alive until the buffers have gone with `delete p`)
     if (p->own_stream) (void)hipStreamSynchronize(p->own_stream);
+    for (auto &st : p->aux_stream) if (st) (void)hipStreamSynchronize(st);
+    if (p->copy_stream) (void)hipStreamSynchronize(p->copy_stream);
     drop_graph(p);
-    free_workspace(p);
-    for (void *q : p->forest_allocs) (void)hipFree(q);
-    if (p->kern_r2) (void)hipFree(p->kern_r2);
-    if (p->blur_kern) (void)hipFree(p->blur_kern);
-    if (p->zeros) (void)hipFree(p->zeros);
-    if (p->gen) (void)hipFree(p->gen);
     for (auto &e : p->ev) if (e) (void)hipEventDestroy(e);
     if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
     for (auto &e : p->ev_join) if (e) (void)hipEventDestroy(e);
-    for (auto &st : p->aux_stream) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-    if (p->copy_stream) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamDestroy(p->copy_stream); }
     for (auto &e : p->ev_stage) if (e) (void)hipEventDestroy(e);
     if (p->ev_slice) (void)hipEventDestroy(p->ev_slice);
-    if (p->pin_small) (void)hipHostFree(p->pin_small);
-    if (p->pin_blob) (void)hipHostFree(p->pin_blob);
-    if (p->pin_runs) (void)hipHostFree(p->pin_runs);
-    if (p->pin_begin) (void)hipHostFree(p->pin_begin);
-    if (p->dev_blob) (void)hipFree(p->dev_blob);
-    if (p->dev_runs) (void)hipFree(p->dev_runs);
-    if (p->dev_begin) (void)hipFree(p->dev_begin);
+    for (auto &st : p->aux_stream) if (st) (void)hipStreamDestroy(st);
+    if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
     delete p;
     return DH_OK;
@@ -309,24 +336,24 @@ static int predictor_create_(const dh_forest *f, const dh_params *prm, int devic
     return DH_OK;
 }
 
+// A failure returns at once: predictor_create_ destroys what has been built.
 static int predictor_build(dh_predictor *p, const dh_forest *f, const dh_params *prm, int device) {
     p->device = device;
     p->params = *prm;
     p->knobs = dh_read_knobs_();   // the only place the environment is read
+    p->chunks = p->knobs.chunks;
     p->n_trees = (uint32_t)f->roots.size(); p->n_nodes = (uint32_t)f->nodes.size(); p->n_leaves = (uint32_t)f->leaf_prob.size();
     p->n_off = f->off_begin.back(); p->n_rot = f->rot_begin.back(); p->max_depth = f->max_depth;
     p->f_uniform = f->uniform; p->f_rw = f->rw; p->f_rh = f->rh;
-    int rc = DH_OK;
     DevForest &d = p->dev;
     d.n_trees = p->n_trees; d.n_nodes = p->n_nodes; d.n_leaves = p->n_leaves; d.n_off = p->n_off; d.n_rot = p->n_rot;
-#define STEP(x) if (rc == DH_OK) rc = (x)
-    STEP(upload(p, &d.roots, f->roots));
-    STEP(upload(p, &d.nodes, f->nodes));
-    STEP(upload(p, &d.leaf_prob, f->leaf_prob));
-    STEP(upload(p, &d.off_begin, f->off_begin));
-    STEP(upload(p, &d.rot_begin, f->rot_begin));
-    STEP(upload(p, &d.offsets, f->offsets));
-    if (rc == DH_OK) {
+    TRY(upload(p, &d.roots, f->roots));
+    TRY(upload(p, &d.nodes, f->nodes));
+    TRY(upload(p, &d.leaf_prob, f->leaf_prob));
+    TRY(upload(p, &d.off_begin, f->off_begin));
+    TRY(upload(p, &d.rot_begin, f->rot_begin));
+    TRY(upload(p, &d.offsets, f->offsets));
+    {
         // the offset votes once more as (x, y, z, 0) records, every leaf's run on a 64-byte boundary: the kernels
         // that walk a leaf's votes (k_vote, k_cluster) then touch whole cache lines with one 16-byte load per lane
         std::vector<uint32_t> b4;
@@ -334,88 +361,72 @@ static int predictor_build(dh_predictor *p, const dh_forest *f, const dh_params 
         dh_pack_off4_(*f, b4, o4f);
         std::vector<float4> o4(o4f.size() / 4);
         memcpy(o4.data(), o4f.data(), o4f.size() * sizeof(float));
-        STEP(upload(p, &d.off4, o4));
-        STEP(upload(p, &d.off4_begin, b4));
+        TRY(upload(p, &d.off4, o4));
+        TRY(upload(p, &d.off4_begin, b4));
     }
-    STEP(upload(p, &d.rotations, f->rotations));
-    STEP(dev_alloc(p, &d.leaf_v, p->n_leaves, true));
-    STEP(dev_alloc(p, &d.leaf_flags, p->n_leaves, true));
-    STEP(dev_alloc(p, &d.rot_bin, p->n_rot, true));
-    STEP(dev_alloc(p, &d.rot_rough, p->n_rot, true));
-    STEP(dev_alloc(p, &d.rot_mult, p->n_rot, true));
-    STEP(dev_alloc(p, &d.rough_mult, p->n_rot, true));
-    STEP(dev_alloc(p, &d.rough_cell, p->n_rot, true));
-    STEP(dev_alloc(p, &d.off_min, (size_t)p->n_leaves * 3, true));
-    STEP(dev_alloc(p, &d.off_max, (size_t)p->n_leaves * 3, true));
-    STEP(dev_alloc(p, &d.rbin_box, p->n_leaves, true));
-    STEP(dev_alloc(p, &d.rbin_box_hi, p->n_leaves, true));
-    STEP(dev_alloc(p, &d.tpl, p->n_leaves, true));
-    STEP(dev_alloc(p, &d.rot_dir, p->n_leaves, true));
-    STEP(dev_alloc(p, &p->kern_r2, DH_KERN_R2));
-    STEP(dev_alloc(p, &p->zeros, 32));
-    STEP(dev_alloc(p, &p->gen, DH_MAX_CHUNKS));
-    { uint4 *nu = nullptr; STEP(dev_alloc(p, &nu, p->n_nodes, true)); p->nodes_u = nu; }
+    TRY(upload(p, &d.rotations, f->rotations));
+    TRY(forest_alloc(p, &d.leaf_v, p->n_leaves));
+    TRY(forest_alloc(p, &d.leaf_flags, p->n_leaves));
+    TRY(forest_alloc(p, &d.rot_bin, p->n_rot));
+    TRY(forest_alloc(p, &d.rot_rough, p->n_rot));
+    TRY(forest_alloc(p, &d.rot_mult, p->n_rot));
+    TRY(forest_alloc(p, &d.rough_mult, p->n_rot));
+    TRY(forest_alloc(p, &d.rough_cell, p->n_rot));
+    TRY(forest_alloc(p, &d.off_min, (size_t)p->n_leaves * 3));
+    TRY(forest_alloc(p, &d.off_max, (size_t)p->n_leaves * 3));
+    TRY(forest_alloc(p, &d.rbin_box, p->n_leaves));
+    TRY(forest_alloc(p, &d.rbin_box_hi, p->n_leaves));
+    TRY(forest_alloc(p, &d.tpl, p->n_leaves));
+    TRY(forest_alloc(p, &d.rot_dir, p->n_leaves));
+    TRY(p->kern_r2.alloc(DH_KERN_R2));
+    TRY(p->zeros.alloc(32));
+    TRY(p->gen.alloc(DH_MAX_CHUNKS));
+    TRY(p->nodes_u.alloc(p->n_nodes));
     if (p->n_nodes > 0 && (size_t)p->n_nodes + p->n_leaves + 2 * DH_AMB_CAP < ((size_t)1 << 27) && !p->knobs.no_absorb) {   // (byte offsets into the table stay below 2^31)
-        STEP(dev_alloc(p, &p->amb_flag, 1, true));
-        STEP(dev_alloc(p, &p->amb_list, DH_AMB_CAP, true));
+        TRY(p->amb_flag.alloc(1));
+        TRY(p->amb_list.alloc(DH_AMB_CAP));
     }
-    if (rc == DH_OK && prm->subimage_width <= 255 && prm->subimage_height <= 255 && p->n_nodes > 0) {
+    if (prm->subimage_width <= 255 && prm->subimage_height <= 255 && p->n_nodes > 0) {
         // Integer split bounds of the general path (NodeG: dh_host.h, k_traverse.hip)
         std::vector<NodeG> ng;
         dh_build_nodes_g_(*f, ng);
-        NodeG *dg = nullptr;
-        STEP(dev_alloc(p, &dg, p->n_nodes, true));
-        if (rc == DH_OK && hipMemcpy(dg, ng.data(), ng.size() * sizeof(NodeG), hipMemcpyHostToDevice) != hipSuccess) rc = fail(DH_EHIP, "hipMemcpy(NodeG)");
-        p->nodes_g = dg;
+        TRY(p->nodes_g.alloc(p->n_nodes));
+        if (hipMemcpy(p->nodes_g.get(), ng.data(), ng.size() * sizeof(NodeG), hipMemcpyHostToDevice) != hipSuccess) return fail(DH_EHIP, "hipMemcpy(NodeG)");
     }
-#undef STEP
-    auto hipstep = [&](hipError_t e, const char *what) {
-        if (rc == DH_OK && e != hipSuccess) rc = fail(DH_EHIP, "%s: %s", what, hipGetErrorString(e));
-    };
-    if (rc == DH_OK) hipstep(hipMemset(p->zeros, 0, 64), "hipMemset");
-    if (rc == DH_OK) { const uint32_t ones[DH_MAX_CHUNKS] = {1, 1, 1, 1, 1, 1, 1, 1}; hipstep(hipMemcpy(p->gen, ones, sizeof ones, hipMemcpyHostToDevice), "hipMemcpy(gen)"); }
-    if (rc == DH_OK) hipstep(dh_kernels_init(device), "hipFuncSetAttribute");
-    if (rc == DH_OK) hipstep(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking), "hipStreamCreate");
-    if (rc == DH_OK) hipstep(dh_launch_leaf_prepare(d, p->own_stream), "k_leaf_prepare launch");
-    if (rc == DH_OK) hipstep(hipStreamSynchronize(p->own_stream), "k_leaf_prepare");
-    if (rc == DH_OK && p->amb_flag && p->f_uniform) {
+    TRY(hip_step(hipMemset(p->zeros.get(), 0, 64), "hipMemset"));
+    const uint32_t ones[DH_MAX_CHUNKS] = {1, 1, 1, 1, 1, 1, 1, 1};
+    TRY(hip_step(hipMemcpy(p->gen.get(), ones, sizeof ones, hipMemcpyHostToDevice), "hipMemcpy(gen)"));
+    TRY(hip_step(dh_kernels_init(device), "hipFuncSetAttribute"));
+    TRY(hip_step(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking), "hipStreamCreate"));
+    TRY(hip_step(dh_launch_leaf_prepare(d, p->own_stream), "k_leaf_prepare launch"));
+    TRY(hip_step(hipStreamSynchronize(p->own_stream), "k_leaf_prepare"));
+    if (p->amb_flag && p->f_uniform) {
         // which nodes carry an ambiguity band?  (independent of the region layout: probed once with a dummy one)
         uint32_t n_amb = DH_AMB_CAP + 1;
-        hipstep(hipMemsetAsync(p->amb_flag, 0, sizeof(uint32_t), p->own_stream), "hipMemset");
-        if (rc == DH_OK) hipstep(dh_launch_nodes_compact(d, 1, 0, 4, (uint32_t)(p->f_rw * p->f_rh), nullptr, nullptr, p->amb_flag, p->amb_list, 0, p->own_stream), "k_nodes_compact launch");
-        if (rc == DH_OK) hipstep(hipMemcpyAsync(&n_amb, p->amb_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, p->own_stream), "hipMemcpy");
-        if (rc == DH_OK) hipstep(hipStreamSynchronize(p->own_stream), "k_nodes_compact");
+        TRY(hip_step(hipMemsetAsync(p->amb_flag.get(), 0, sizeof(uint32_t), p->own_stream), "hipMemset"));
+        TRY(hip_step(dh_launch_nodes_compact(d, 1, 0, 4, (uint32_t)(p->f_rw * p->f_rh), nullptr, nullptr, p->amb_flag.get(), p->amb_list.get(), 0, p->own_stream), "k_nodes_compact launch"));
+        TRY(hip_step(hipMemcpyAsync(&n_amb, p->amb_flag.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, p->own_stream), "hipMemcpy"));
+        TRY(hip_step(hipStreamSynchronize(p->own_stream), "k_nodes_compact"));
         // (the walk table keeps 12 bytes of LDS per tree even with no level in LDS: not for forests of thousands of trees)
-        p->absorb_ok = rc == DH_OK && n_amb <= DH_AMB_CAP && (size_t)p->n_trees * 12 <= 8 * 1024;
+        p->absorb_ok = n_amb <= DH_AMB_CAP && (size_t)p->n_trees * 12 <= 8 * 1024;
         if (p->absorb_ok) {
             p->n_amb = n_amb;
-            uint4 *na = nullptr;
-            int r2 = dev_alloc(p, &na, (size_t)p->n_nodes + n_amb + 1, true);
-            if (r2) rc = r2;
-            p->nodes_a = na;
+            TRY(p->nodes_a.alloc((size_t)p->n_nodes + n_amb + 1));
             p->top_levels = p->knobs.top_levels;          // -1: choose_tile decides per geometry
-            if (rc == DH_OK) {
-                uint32_t *tt = nullptr;
-                r2 = dev_alloc(p, &tt, (size_t)p->n_trees * (1u << 8) * 3, true);      // room for the 8 levels choose_tile may go to
-                if (r2) rc = r2;
-                p->top_tab = tt;
-            }
+            TRY(p->top_tab.alloc((size_t)p->n_trees * (1u << 8) * 3));      // room for the 8 levels choose_tile may go to
         }
     }
-    if (rc == DH_OK) rc = build_kernel_table(p);
-    for (auto &e : p->ev)
-        if (rc == DH_OK) hipstep(hipEventCreate(&e), "hipEventCreate");
-    p->chunks = p->knobs.chunks;
-    if (rc == DH_OK) hipstep(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming), "hipEventCreate");
-    if (rc == DH_OK) hipstep(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking), "hipStreamCreate");
-    for (auto &e : p->ev_stage)
-        if (rc == DH_OK) hipstep(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-    if (rc == DH_OK) hipstep(hipEventCreateWithFlags(&p->ev_slice, hipEventDisableTiming), "hipEventCreate");
+    TRY(build_kernel_table(p));
+    for (auto &e : p->ev) TRY(hip_step(hipEventCreate(&e), "hipEventCreate"));
+    TRY(hip_step(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming), "hipEventCreate"));
+    TRY(hip_step(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking), "hipStreamCreate"));
+    for (auto &e : p->ev_stage) TRY(hip_step(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate"));
+    TRY(hip_step(hipEventCreateWithFlags(&p->ev_slice, hipEventDisableTiming), "hipEventCreate"));
     for (int i = 0; i < DH_MAX_CHUNKS - 1; ++i) {
-        if (rc == DH_OK) hipstep(hipStreamCreateWithFlags(&p->aux_stream[i], hipStreamNonBlocking), "hipStreamCreate");
-        if (rc == DH_OK) hipstep(hipEventCreateWithFlags(&p->ev_join[i], hipEventDisableTiming), "hipEventCreate");
+        TRY(hip_step(hipStreamCreateWithFlags(&p->aux_stream[i], hipStreamNonBlocking), "hipStreamCreate"));
+        TRY(hip_step(hipEventCreateWithFlags(&p->ev_join[i], hipEventDisableTiming), "hipEventCreate"));
     }
-    return rc;
+    return DH_OK;
 }
 
 static int predictor_update_sigma_(dh_predictor *p, float val) {
@@ -441,107 +452,103 @@ static int choose_tile(const dh_predictor *p, Geom &g, int cap) {
     return dh_choose_tile_(q, g);
 }
 
+// A workspace for at least n frames of w x h.  The old one is freed before the new one is allocated, so the two never hold
+// memory at once; a failure leaves none.
 static int reserve(dh_predictor *p, int n, int w, int h) {
     if (n <= 0) return fail(DH_EINVAL, "batch size must be positive");
     Geom g;
     g.w = w; g.h = h;
-    int rc = dh_patch_grid_(p->params, w, h, &g.nx, &g.ny);
-    if (rc) return rc;
+    TRY(dh_patch_grid_(p->params, w, h, &g.nx, &g.ny));
     g.npatch = g.nx * g.ny;
-    bool same_geom = p->geom.w == w && p->geom.h == h;
-    bool dbg_ok = !p->debug || p->dbg_leaf;
-    if (same_geom && n <= p->cap_frames && dbg_ok) return DH_OK;
+    bool same_geom = p->ws.geom.w == w && p->ws.geom.h == h;
+    bool dbg_ok = !p->debug || p->ws.dbg_leaf;
+    if (same_geom && n <= p->ws.cap_frames && dbg_ok) return DH_OK;
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipDeviceSynchronize());
-    int cap = std::max(n, same_geom ? p->cap_frames : 0);
+    int cap = std::max(n, same_geom ? p->ws.cap_frames : 0);
     free_workspace(p);
     if (g.npatch > 0) {
         // uniform-rectangle fast path: one rectangle size (<= 96 x 96, so a k_boxsum wave yields
         // >= 160 columns), rectangle sums fit i32
         g.uniform = p->f_uniform && (long)p->f_rw * p->f_rh <= 32768 && p->f_rw <= kBoxMaxRect && p->f_rh <= kBoxMaxRect && !p->knobs.force_general;
-        rc = choose_tile(p, g, cap);
+        int rc = choose_tile(p, g, cap);
         if (rc > 0) { g.uniform = false; rc = choose_tile(p, g, cap); }   // no tile fits the uniform layout
         if (rc) return rc;
     }
+    Workspace ws;
     // k_boxsum's band / mask-block height: the shortest of 8, 16, 32 rows whose waves (12 per CU) still fit the chip at once for a
     // workspace of this many frames -- with few frames a wave's march of band + rh - 1 rows IS that kernel's duration
-    p->blk_shift = 5;
     if (g.uniform && g.box_rows > 0)
         for (int sh = 3; sh < 5; ++sh)
-            if ((long)cap * g.box_parts * ((g.box_rows + (1 << sh) - 1) >> sh) <= 12L * 256) { p->blk_shift = sh; break; }
+            if ((long)cap * g.box_parts * ((g.box_rows + (1 << sh) - 1) >> sh) <= 12L * 256) { ws.blk_shift = sh; break; }
     size_t hits_cap = std::max<size_t>((size_t)g.npatch * p->n_trees, 1);
     if (hits_cap > 0xffffffffull) return fail(DH_ESIZE, "too many (patch, tree) pairs per frame");
-    p->hits_cap = (uint32_t)hits_cap;
-#define STEP(x) if (rc == DH_OK) rc = (x)
-    STEP(dev_alloc(p, &p->hits, (size_t)cap * hits_cap));
-    STEP(dev_alloc(p, &p->hit_box, (size_t)cap * hits_cap));
-    STEP(dev_alloc(p, &p->hit_rot, (size_t)cap * hits_cap));
+    ws.hits_cap = (uint32_t)hits_cap;
+    TRY(ws.hits.alloc((size_t)cap * hits_cap));
+    TRY(ws.hit_box.alloc((size_t)cap * hits_cap));
+    TRY(ws.hit_rot.alloc((size_t)cap * hits_cap));
     const bool leaf_hist = p->n_leaves <= p->knobs.leaf_hist_max && !p->knobs.no_leaf_hist;
     // k_region pays a fixed ~20 us (second initial guess, flush, launch) for spreading the first region gather over
     // several workgroups: worth it from ~8 k hit records per frame on the rotation-record path of large forests, from
     // ~65 k with the leaf histogram (measured: config 3 cluster 0.77 -> 0.34 ms; config 5, 38 k records per frame, would lose)
-    p->pre_min_hits = p->knobs.region_min_hits > 0 ? (uint32_t)p->knobs.region_min_hits : (leaf_hist ? 65536u : 8192u);
+    ws.pre_min_hits = p->knobs.region_min_hits > 0 ? (uint32_t)p->knobs.region_min_hits : (leaf_hist ? 65536u : 8192u);
     // (only where a frame of this geometry can plausibly hold that many records: a few per cent of its (window, tree) pairs vote)
-    if (!p->knobs.no_region && hits_cap >= (leaf_hist ? 8 : 4) * (size_t)p->pre_min_hits) {
+    if (!p->knobs.no_region && hits_cap >= (leaf_hist ? 8 : 4) * (size_t)ws.pre_min_hits) {
         // k_region serves batches of up to 128 frames (beyond that the (frame, accumulator) workgroups of k_cluster fill the chip themselves)
-        p->pre_cap = std::min(cap, 128);
-        STEP(dev_alloc(p, &p->pre_region, (size_t)p->pre_cap * 2 * DH_SUPER_CELLS));   // (2 MB per frame; zeroed per batch, before k_region)
+        ws.pre_cap = std::min(cap, 128);
+        TRY(ws.pre_region.alloc((size_t)ws.pre_cap * 2 * DH_SUPER_CELLS));   // (2 MB per frame; zeroed per batch, before k_region)
     }
-    STEP(dev_alloc(p, &p->win_patch, (size_t)cap * std::max(g.win_cap, 1)));
-    p->leaf_ls = p->n_leaves <= 65535u ? 1 : 2;
-    STEP(dev_alloc(p, &p->win_leaf, ((size_t)cap * std::max(g.win_cap, 1) * p->n_trees) << p->leaf_ls));
+    TRY(ws.win_patch.alloc((size_t)cap * std::max(g.win_cap, 1)));
+    ws.leaf_ls = p->n_leaves <= 65535u ? 1 : 2;
+    TRY(ws.win_leaf.alloc(((size_t)cap * std::max(g.win_cap, 1) * p->n_trees) << ws.leaf_ls));
     if (!p->knobs.no_tile_list && g.npatch > 0) {
-        p->tile_list_stride = (size_t)((cap + 7) / 8) * g.tiles_x * g.tiles_y;
-        if (p->tile_list_stride < ((size_t)1 << 31)) STEP(dev_alloc(p, &p->tile_list, (size_t)DH_MAX_CHUNKS * 8 * (p->tile_list_stride + 1)));
+        ws.tile_list_stride = (size_t)((cap + 7) / 8) * g.tiles_x * g.tiles_y;
+        if (ws.tile_list_stride < ((size_t)1 << 31)) TRY(ws.tile_list.alloc((size_t)DH_MAX_CHUNKS * 8 * (ws.tile_list_stride + 1)));
     }
     if (g.uniform) {
         const size_t words = (size_t)cap * g.box_rows * ((size_t)g.box_plane << g.swz_log2);
-        STEP(dev_alloc(p, &p->box, words));
+        TRY(ws.box.alloc(words));
         // (the slack columns stay 0.  Zero-fills of a new workspace are ordered explicitly: issued on the predictor's stream and
         // waited for below -- the streams here are non-blocking ones, which the legacy stream of a plain hipMemset does not order)
-        if (rc == DH_OK && hipMemsetAsync(p->box, 0, words * sizeof(uint32_t), p->own_stream) != hipSuccess) rc = fail(DH_EHIP, "hipMemset(box)");
+        if (hipMemsetAsync(ws.box.get(), 0, words * sizeof(uint32_t), p->own_stream) != hipSuccess) return fail(DH_EHIP, "hipMemset(box)");
         if (!p->knobs.box_dense) {
             // zeroed together with the images: "cell non-zero => mask bit set" holds from the start
             const size_t mw = (size_t)cap * ((g.box_rows + 7) / 8) * g.box_parts;        // (sized for 8-row blocks: single-frame workspaces)
-            STEP(dev_alloc(p, &p->box_mask, mw));
-            if (rc == DH_OK && hipMemsetAsync(p->box_mask, 0, mw * sizeof(unsigned long long), p->own_stream) != hipSuccess) rc = fail(DH_EHIP, "hipMemset(box_mask)");
+            TRY(ws.box_mask.alloc(mw));
+            if (hipMemsetAsync(ws.box_mask.get(), 0, mw * sizeof(unsigned long long), p->own_stream) != hipSuccess) return fail(DH_EHIP, "hipMemset(box_mask)");
         }
     }
-    if (rc == DH_OK && hipStreamSynchronize(p->own_stream) != hipSuccess) rc = fail(DH_EHIP, "zero-fill of the rectangle-sum images");
+    if (hipStreamSynchronize(p->own_stream) != hipSuccess) return fail(DH_EHIP, "zero-fill of the rectangle-sum images");
     // one block, one memset per batch: hit counters | guess grids | tile flags | window counts | leaf histogram
-    const size_t counter_words = (size_t)cap * (1 + DH_POSGRID + DH_GRID3 + (size_t)g.flag_words + (size_t)g.tiles_x * g.tiles_y);
-    STEP(dev_alloc(p, &p->counters, counter_words + (leaf_hist ? (size_t)cap * p->n_leaves : 0) + 4));   // (+4: the zero-fill kernel rounds up to 16 bytes)
-    if (rc == DH_OK) p->leaf_hits = leaf_hist ? p->counters + counter_words : nullptr;
-    p->zero_words = counter_words + (leaf_hist ? (size_t)cap * p->n_leaves : 0);
+    ws.lay = dh_counter_layout_(cap, g.flag_words, (size_t)g.tiles_x * g.tiles_y, leaf_hist ? p->n_leaves : 0);
+    TRY(ws.counters.alloc(ws.lay.alloc_words));
     // (zeroed once here: the tile flags carry tags and get no fill of their own when k_boxsum clears the other counters)
-    if (rc == DH_OK && (hipMemsetAsync(p->counters, 0, (p->zero_words + 4) * sizeof(uint32_t), p->own_stream) != hipSuccess ||
-                        hipStreamSynchronize(p->own_stream) != hipSuccess)) rc = fail(DH_EHIP, "zero-fill of the counters");
-    p->zero_lo = (size_t)cap * (1 + DH_POSGRID + DH_GRID3); p->zero_hi = p->zero_lo + (size_t)cap * g.flag_words;
-    STEP(dev_alloc(p, &p->ws_poses, cap));
-    STEP(dev_alloc(p, &p->ws_midp, (size_t)cap * 3));
-    STEP(dev_alloc(p, &p->ws_rot, (size_t)cap * 3));
-    STEP(dev_alloc(p, &p->ws_mask, cap));
+    if (hipMemsetAsync(ws.counters.get(), 0, ws.lay.alloc_words * sizeof(uint32_t), p->own_stream) != hipSuccess ||
+        hipStreamSynchronize(p->own_stream) != hipSuccess) return fail(DH_EHIP, "zero-fill of the counters");
+    TRY(ws.poses.alloc(cap));
+    TRY(ws.midp.alloc((size_t)cap * 3));
+    TRY(ws.rot.alloc((size_t)cap * 3));
+    TRY(ws.mask.alloc(cap));
     if (p->debug) {
-        STEP(dev_alloc(p, &p->dbg_leaf, (size_t)cap * std::max(g.npatch, 1) * p->n_trees));
-        STEP(dev_alloc(p, &p->dbg_flags, (size_t)cap * std::max(g.npatch, 1)));
-        STEP(dev_alloc(p, &p->dbg_guess, (size_t)cap * 6));
-        STEP(dev_alloc(p, &p->dbg_trace, (size_t)2 * cap * (p->params.meanshift_iterations + 1) * 3));
-        STEP(dev_alloc(p, &p->dbg_steps, (size_t)2 * cap));
-        STEP(dev_alloc(p, &p->dbg_vcount, 1));
+        TRY(ws.dbg_leaf.alloc((size_t)cap * std::max(g.npatch, 1) * p->n_trees));
+        TRY(ws.dbg_flags.alloc((size_t)cap * std::max(g.npatch, 1)));
+        TRY(ws.dbg_guess.alloc((size_t)cap * 6));
+        TRY(ws.dbg_trace.alloc((size_t)2 * cap * (p->params.meanshift_iterations + 1) * 3));
+        TRY(ws.dbg_steps.alloc((size_t)2 * cap));
+        TRY(ws.dbg_vcount.alloc(1));
     }
-#undef STEP
-    if (rc != DH_OK) { free_workspace(p); return rc; }
     const long long nkey = ((long long)g.ss_row << 32) | ((long long)g.top_levels << 24) | ((long long)g.swz_q << 4) | g.swz_log2;
     if (g.npatch > 0 && g.uniform && p->nodes_u_key != nkey) {     // compact nodes carry LDS offsets for this row stride
-        hipError_t e = dh_launch_nodes_compact(p->dev, g.ss_row, g.swz_log2, g.swz_q, (uint32_t)(p->f_rw * p->f_rh), p->nodes_u,
-                                               p->absorb_ok ? p->nodes_a : nullptr, nullptr, p->amb_list, p->n_amb, p->own_stream);
-        if (e == hipSuccess && p->absorb_ok) e = dh_launch_top_build(p->dev, p->nodes_a, p->n_amb, g.top_levels, p->top_tab, p->own_stream);
+        hipError_t e = dh_launch_nodes_compact(p->dev, g.ss_row, g.swz_log2, g.swz_q, (uint32_t)(p->f_rw * p->f_rh), p->nodes_u.get(),
+                                               p->absorb_ok ? p->nodes_a.get() : nullptr, nullptr, p->amb_list.get(), p->n_amb, p->own_stream);
+        if (e == hipSuccess && p->absorb_ok) e = dh_launch_top_build(p->dev, p->nodes_a.get(), p->n_amb, g.top_levels, p->top_tab.get(), p->own_stream);
         if (e == hipSuccess) e = hipStreamSynchronize(p->own_stream);
-        if (e != hipSuccess) { free_workspace(p); return fail(DH_EHIP, "k_nodes_compact: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(DH_EHIP, "k_nodes_compact: %s", hipGetErrorString(e));
         p->nodes_u_key = nkey;
     }
-    p->geom = g;
-    p->cap_frames = cap;
+    ws.geom = g;
+    ws.cap_frames = cap;
+    p->ws = std::move(ws);
     return DH_OK;
 }
 
@@ -558,30 +565,38 @@ static int predictor_reserve_(dh_predictor *p, int n, int w, int h) {
     return reserve(p, n, w, h);
 }
 
+// How enqueue_range runs besides the product batch.
+struct EnqueueOpts {
+    bool profile = false;           // events and roctx ranges (dh_set_profiling)
+    int32_t *leaf_out = nullptr;    // k_traverse's leaf ids and patch flags into these instead of the taps (mask / 2-D Hough)
+    uint8_t *flags_out = nullptr;
+    bool traverse_only = false;     // stop after k_traverse
+    int chunk = 0;                  // forked sub-batch: its tile-flag tag and tile list
+    bool zero_fold = false;         // k_boxsum zeroes the counters: no fill of their own
+};
+
 // Enqueue the kernels (k_boxsum / k_pixflags, k_traverse, k_emit, k_vote, [k_region,] k_cluster) for frames [f0, f0 + n) of the batch on stream s.
 static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n, int w, int h, const float K[9],
                          const float kinv[9], const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
-                         dh_pose *out, hipStream_t s, bool profile, int32_t *leaf_out = nullptr, uint8_t *flags_out = nullptr,
-                         bool traverse_only = false, int chunk = 0, bool zero_fold = false) {
-    const Geom &g = p->geom;
-    uint32_t *gen = p->gen + chunk;      // this kernel sequence's tile-flag tag
-    uint32_t *hit_count = p->counters + f0;
-    uint32_t *pos_grid = p->counters + p->cap_frames + (size_t)f0 * DH_POSGRID;
-    uint32_t *rot_grid = p->counters + p->cap_frames + (size_t)p->cap_frames * DH_POSGRID + (size_t)f0 * DH_GRID3;
-    const size_t hoff = (size_t)f0 * p->hits_cap;
+                         dh_pose *out, hipStream_t s, const EnqueueOpts &o) {
+    const Workspace &ws = p->ws;
+    const Geom &g = ws.geom;
+    uint32_t *gen = p->gen.get() + o.chunk;      // this kernel sequence's tile-flag tag
+    uint32_t *hit_count = ws.hit_count(f0), *pos_grid = ws.pos_grid(f0), *rot_grid = ws.rot_grid(f0), *leaf_hits = ws.leaf_hits(f0);
+    const size_t hoff = (size_t)f0 * ws.hits_cap;
     const uint16_t *fr = frames + (size_t)f0 * w * h;
     char batch_name[48];
     snprintf(batch_name, sizeof batch_name, "dh:batch n=%d %dx%d", n, w, h);
-    Range batch_range(profile, batch_name);
-    if (profile) HIP_TRY(hipEventRecord(p->ev[0], s));
-    uint32_t *box = g.uniform ? p->box + (size_t)f0 * g.box_rows * ((size_t)g.box_plane << g.swz_log2) : nullptr;
+    Range batch_range(o.profile, batch_name);
+    if (o.profile) HIP_TRY(hipEventRecord(p->ev[0], s));
+    uint32_t *box = g.uniform ? ws.box.get() + (size_t)f0 * g.box_rows * ((size_t)g.box_plane << g.swz_log2) : nullptr;
     // tile flags: one byte per tile, frames packed back to back (the slice always starts at the frame the memset covered)
-    uint8_t *tile_flags = (uint8_t *)(p->counters + (size_t)p->cap_frames * (1 + DH_POSGRID + DH_GRID3)) + (size_t)f0 * g.tiles_x * g.tiles_y;
+    uint8_t *tile_flags = ws.tile_flags(f0);
     if (g.npatch > 0 && g.uniform) {
         BoxArgs ba{};
-        ba.frames = fr; ba.zeros = p->zeros; ba.n_frames = n; ba.w = w; ba.h = h; ba.rw = p->f_rw; ba.rh = p->f_rh;
+        ba.frames = fr; ba.zeros = p->zeros.get(); ba.n_frames = n; ba.w = w; ba.h = h; ba.rw = p->f_rw; ba.rh = p->f_rh;
         ba.tile_flags = tile_flags; ba.tiles_x = g.tiles_x; ba.tiles_y = g.tiles_y; ba.gen = gen;
-        if (zero_fold) { ba.zero_ptr = p->counters; ba.zero_lo = (uint32_t)p->zero_lo; ba.zero_hi = (uint32_t)p->zero_hi; ba.zero_end = (uint32_t)p->zero_words; }
+        if (o.zero_fold) { ba.zero_ptr = ws.counters.get(); ba.zero_lo = (uint32_t)ws.lay.zero_lo; ba.zero_hi = (uint32_t)ws.lay.zero_hi; ba.zero_end = (uint32_t)ws.lay.zero_words; }
         ba.tpx = g.px * (int)p->params.stepwidth; ba.tpy = g.py * (int)p->params.stepwidth;
         ba.tbw = (g.px - 1) * (int)p->params.stepwidth + (int)p->params.subimage_width - p->f_rw + 1;
         ba.tbh = (g.py - 1) * (int)p->params.stepwidth + (int)p->params.subimage_height - p->f_rh + 1;
@@ -593,7 +608,7 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         if (ring_on && p->f_rh >= 2 && p->f_rh - 1 <= 28) {      // 4 x 28 x 512 B + the prefix rows < 64 KB
             // (a single-frame workspace: 8-row bands and mask blocks -- a wave's march of band + rh - 1 rows IS the kernel's
             // duration there: 31 instead of 55 rows at rh = 24; one 320 x 240 frame 86 -> 79 us with 16-row bands, 76 with 8)
-            const int blk = 1 << p->blk_shift;
+            const int blk = 1 << ws.blk_shift;
             int oh = 0;
             // workgroups the chip holds at once: per CU what the ring's LDS leaves room for (53 KB at rh = 24: three), at most the six
             // that 76 VGPRs allow; 256 CUs
@@ -608,11 +623,11 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
             ba.bands = (g.box_rows + ba.oh - 1) / ba.oh;
             ba.ring = 1;
         }
-        ba.blk_shift = p->blk_shift;
-        ba.mask_blocks = (g.box_rows + (1 << p->blk_shift) - 1) >> p->blk_shift;
-        ba.blk_mask = p->box_mask ? p->box_mask + (size_t)f0 * ba.mask_blocks * g.box_parts : nullptr;
+        ba.blk_shift = ws.blk_shift;
+        ba.mask_blocks = (g.box_rows + (1 << ws.blk_shift) - 1) >> ws.blk_shift;
+        ba.blk_mask = ws.box_mask ? ws.box_mask.get() + (size_t)f0 * ba.mask_blocks * g.box_parts : nullptr;
         ba.blocks_per_frame = (ba.parts * ba.bands + 3) / 4;
-        { Range r(profile, "dh:boxsum"); HIP_TRY(dh_launch_boxsum(ba, s)); }
+        { Range r(o.profile, "dh:boxsum"); HIP_TRY(dh_launch_boxsum(ba, s)); }
     }
     if (g.npatch > 0 && !g.uniform) {
         PixFlagArgs fa{};
@@ -621,17 +636,17 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         fa.tpx = g.px * (int)p->params.stepwidth; fa.tpy = g.py * (int)p->params.stepwidth;
         fa.tfw = (g.px - 1) * (int)p->params.stepwidth + (int)p->params.subimage_width;
         fa.tfh = (g.py - 1) * (int)p->params.stepwidth + (int)p->params.subimage_height;
-        { Range r(profile, "dh:pixflags"); HIP_TRY(dh_launch_pixflags(fa, s)); }
+        { Range r(o.profile, "dh:pixflags"); HIP_TRY(dh_launch_pixflags(fa, s)); }
     }
     // product mode: the flagged tiles as compact lists, so that the workgroups of empty tiles sit at the end of k_traverse's grid
     // (with the taps on, every tile position keeps its workgroup: those of empty tiles write the taps' "background")
     // (the list moves the empty tiles' workgroups behind the flagged ones; a batch whose tiles all fit the chip's 512 workgroup
     // slots at once gains nothing from that and saves the dispatch: 3 us of a single frame's 96)
-    const bool use_list = p->tile_list && g.npatch > 0 && !leaf_out && !flags_out && !p->debug && (long)n * g.tiles_x * g.tiles_y > 512;
-    uint32_t *tl_list = use_list ? p->tile_list + (size_t)chunk * 8 * (p->tile_list_stride + 1) : nullptr;
-    uint32_t *tl_count = use_list ? tl_list + 8 * p->tile_list_stride : nullptr;
-    if (use_list) { Range r(profile, "dh:tile_list"); HIP_TRY(dh_launch_tile_list(tile_flags, gen, n, g.tiles_x * g.tiles_y, tl_list, tl_count, (uint32_t)p->tile_list_stride, s)); }
-    if (profile) HIP_TRY(hipEventRecord(p->ev[4], s));
+    const bool use_list = ws.tile_list && g.npatch > 0 && !o.leaf_out && !o.flags_out && !p->debug && (long)n * g.tiles_x * g.tiles_y > 512;
+    uint32_t *tl_list = use_list ? ws.tile_list.get() + (size_t)o.chunk * 8 * (ws.tile_list_stride + 1) : nullptr;
+    uint32_t *tl_count = use_list ? tl_list + 8 * ws.tile_list_stride : nullptr;
+    if (use_list) { Range r(o.profile, "dh:tile_list"); HIP_TRY(dh_launch_tile_list(tile_flags, gen, n, g.tiles_x * g.tiles_y, tl_list, tl_count, (uint32_t)ws.tile_list_stride, s)); }
+    if (o.profile) HIP_TRY(hipEventRecord(p->ev[4], s));
     if (g.npatch > 0) {
         TraverseArgs ta{};
         ta.frames = fr; ta.n_frames = n; ta.w = w; ta.h = h;
@@ -639,14 +654,14 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         ta.nx = g.nx; ta.ny = g.ny; ta.px = g.px; ta.py = g.py; ta.tiles_x = g.tiles_x; ta.tiles_y = g.tiles_y;
         ta.ss_max = g.ss_max; ta.ss_row = g.ss_row; ta.swz_log2 = g.swz_log2; ta.swz_q = g.swz_q;
         ta.uniform = g.uniform ? 1 : 0; ta.rw = p->f_rw; ta.rh = p->f_rh; ta.area = (uint32_t)(p->f_rw * p->f_rh);
-        ta.nodes_u = p->nodes_u; ta.nodes_a = p->absorb_ok ? p->nodes_a : nullptr; ta.walk_lb = (p->n_nodes + p->n_amb) << 4; ta.amb_list = p->amb_list; ta.top_tab = p->top_tab; ta.top_levels = g.top_levels; ta.nodes_g = p->knobs.no_general_int ? nullptr : p->nodes_g;
+        ta.nodes_u = p->nodes_u.get(); ta.nodes_a = p->absorb_ok ? p->nodes_a.get() : nullptr; ta.walk_lb = (p->n_nodes + p->n_amb) << 4; ta.amb_list = p->amb_list.get(); ta.top_tab = p->top_tab.get(); ta.top_levels = g.top_levels; ta.nodes_g = p->knobs.no_general_int ? nullptr : p->nodes_g.get();
         ta.box = box; ta.box_plane = g.box_plane; ta.box_rows = g.box_rows;
         ta.tile_flags = tile_flags; ta.gen = gen;
 #ifdef DH_PROFILING_KNOBS
         ta.stop_phase = p->knobs.trav_stop;
-        static unsigned long long *stamps = nullptr;
         if (p->knobs.trav_stamps) {
-            if (!stamps) { HIP_TRY(hipMalloc((void **)&stamps, 64)); HIP_TRY(hipMemset(stamps, 0, 64)); }
+            unsigned long long *stamps = p->trav_stamps.get();
+            if (!stamps) { TRY(p->trav_stamps.alloc(8)); stamps = p->trav_stamps.get(); HIP_TRY(hipMemset(stamps, 0, 64)); }
             else {
                 unsigned long long hst[8];
                 HIP_TRY(hipMemcpy(hst, stamps, 64, hipMemcpyDeviceToHost));
@@ -658,63 +673,63 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
 #endif
         ta.f = p->dev;
         const int tiles = g.tiles_x * g.tiles_y;
-        uint32_t *win_count = p->counters + (size_t)p->cap_frames * (1 + DH_POSGRID + DH_GRID3 + (size_t)g.flag_words) + (size_t)f0 * tiles;
+        uint32_t *win_count = ws.win_count(f0);
         ta.win_count = win_count; ta.win_cap = g.win_cap;
-        ta.win_patch = p->win_patch + (size_t)f0 * g.win_cap; ta.win_leaf = p->win_leaf + (((size_t)f0 * g.win_cap * p->n_trees) << p->leaf_ls); ta.leaf_ls = p->leaf_ls;
-        ta.dbg_leaf = leaf_out ? leaf_out : p->debug ? p->dbg_leaf + (size_t)f0 * g.npatch * p->n_trees : nullptr;
-        ta.dbg_flags = flags_out ? flags_out : p->debug ? p->dbg_flags + (size_t)f0 * g.npatch : nullptr;
-        if (use_list) { ta.tile_list = tl_list; ta.tile_list_count = tl_count; ta.tile_list_stride = (uint32_t)p->tile_list_stride; }
-        { Range r(profile, "dh:traverse"); HIP_TRY(dh_launch_traverse(ta, g.lds, s)); }
-        if (profile) HIP_TRY(hipEventRecord(p->ev[5], s));
-        if (!traverse_only) {
+        ta.win_patch = ws.win_patch.get() + (size_t)f0 * g.win_cap; ta.win_leaf = ws.win_leaf.get() + (((size_t)f0 * g.win_cap * p->n_trees) << ws.leaf_ls); ta.leaf_ls = ws.leaf_ls;
+        ta.dbg_leaf = o.leaf_out ? o.leaf_out : p->debug ? ws.dbg_leaf.get() + (size_t)f0 * g.npatch * p->n_trees : nullptr;
+        ta.dbg_flags = o.flags_out ? o.flags_out : p->debug ? ws.dbg_flags.get() + (size_t)f0 * g.npatch : nullptr;
+        if (use_list) { ta.tile_list = tl_list; ta.tile_list_count = tl_count; ta.tile_list_stride = (uint32_t)ws.tile_list_stride; }
+        { Range r(o.profile, "dh:traverse"); HIP_TRY(dh_launch_traverse(ta, g.lds, s)); }
+        if (o.profile) HIP_TRY(hipEventRecord(p->ev[5], s));
+        if (!o.traverse_only) {
             EmitArgs ea{};
             ea.frames = fr; ea.n_frames = n; ea.w = w; ea.h = h;
             ea.step = ta.step; ea.lw = ta.sw / 2; ea.lh = ta.sh / 2; ea.nx = g.nx; ea.npatch = g.npatch;
             ea.px = g.px; ea.py = g.py; ea.tiles = tiles;
             memcpy(ea.kinv, kinv, 9 * sizeof(float));
             ea.f = p->dev;
-            ea.win_count = win_count; ea.win_patch = ta.win_patch; ea.win_leaf = ta.win_leaf; ea.leaf_ls = p->leaf_ls; ea.win_cap = g.win_cap;
-            ea.hits = p->hits + hoff; ea.hit_box = p->hit_box + hoff; ea.hit_rot = p->hit_rot + hoff;
-            ea.hit_count = hit_count; ea.hits_cap = p->hits_cap;
-            ea.leaf_hits = p->leaf_hits ? p->leaf_hits + (size_t)f0 * p->n_leaves : nullptr;
+            ea.win_count = win_count; ea.win_patch = ta.win_patch; ea.win_leaf = ta.win_leaf; ea.leaf_ls = ws.leaf_ls; ea.win_cap = g.win_cap;
+            ea.hits = ws.hits.get() + hoff; ea.hit_box = ws.hit_box.get() + hoff; ea.hit_rot = ws.hit_rot.get() + hoff;
+            ea.hit_count = hit_count; ea.hits_cap = ws.hits_cap;
+            ea.leaf_hits = leaf_hits;
             ea.gen = gen;
             ea.dbg_flags = ta.dbg_flags;
 #ifdef DH_PROFILING_KNOBS
             ea.stop = p->knobs.emit_stop;
 #endif
-            { Range r(profile, "dh:emit"); HIP_TRY(dh_launch_emit(ea, s)); }
+            { Range r(o.profile, "dh:emit"); HIP_TRY(dh_launch_emit(ea, s)); }
         }
-    } else if (profile) HIP_TRY(hipEventRecord(p->ev[5], s));
-    if (profile) HIP_TRY(hipEventRecord(p->ev[1], s));
-    if (traverse_only) return DH_OK;
+    } else if (o.profile) HIP_TRY(hipEventRecord(p->ev[5], s));
+    if (o.profile) HIP_TRY(hipEventRecord(p->ev[1], s));
+    if (o.traverse_only) return DH_OK;
     {
         VoteArgs va{};
         va.n_frames = n; va.w = w; va.h = h; va.cell_fast = p->knobs.vote_exact ? 0 : 1;
         memcpy(va.k, K, sizeof va.k);
-        va.f = p->dev; va.hits = p->hits + hoff; va.hit_box = p->hit_box + hoff; va.hit_rot = p->hit_rot + hoff;
-        va.hit_count = hit_count; va.hits_cap = p->hits_cap;
+        va.f = p->dev; va.hits = ws.hits.get() + hoff; va.hit_box = ws.hit_box.get() + hoff; va.hit_rot = ws.hit_rot.get() + hoff;
+        va.hit_count = hit_count; va.hits_cap = ws.hits_cap;
         va.pos_grid = pos_grid; va.rot_grid = rot_grid;
-        va.leaf_hits = p->leaf_hits ? p->leaf_hits + (size_t)f0 * p->n_leaves : nullptr;
+        va.leaf_hits = leaf_hits;
 #ifdef DH_PROFILING_KNOBS
         va.stop = p->knobs.vote_stop;
 #endif
-        { Range r(profile, "dh:vote"); HIP_TRY(dh_launch_vote(va, s)); }
+        { Range r(o.profile, "dh:vote"); HIP_TRY(dh_launch_vote(va, s)); }
     }
-    if (profile) HIP_TRY(hipEventRecord(p->ev[2], s));
+    if (o.profile) HIP_TRY(hipEventRecord(p->ev[2], s));
     {
         ClusterArgs ca{};
         ca.frames = fr; ca.n_frames = n; ca.w = w; ca.h = h;
         memcpy(ca.kinv, kinv, 9 * sizeof(float));
-        ca.f = p->dev; ca.hits = p->hits + hoff; ca.hit_box = p->hit_box + hoff; ca.hit_rot = p->hit_rot + hoff;
-        ca.hit_count = hit_count; ca.hits_cap = p->hits_cap;
-        ca.leaf_hits = p->leaf_hits ? p->leaf_hits + (size_t)f0 * p->n_leaves : nullptr;
-        ca.pos_grid = pos_grid; ca.rot_grid = rot_grid; ca.kern_r2 = p->kern_r2;
+        ca.f = p->dev; ca.hits = ws.hits.get() + hoff; ca.hit_box = ws.hit_box.get() + hoff; ca.hit_rot = ws.hit_rot.get() + hoff;
+        ca.hit_count = hit_count; ca.hits_cap = ws.hits_cap;
+        ca.leaf_hits = leaf_hits;
+        ca.pos_grid = pos_grid; ca.rot_grid = rot_grid; ca.kern_r2 = p->kern_r2.get();
         ca.iterations = p->params.meanshift_iterations;
 #ifdef DH_PROFILING_KNOBS
         ca.stop = p->knobs.cl_stop;
-        static unsigned long long *cl_stamps = nullptr;
         if (p->knobs.cl_stamps) {
-            if (!cl_stamps) { HIP_TRY(hipMalloc((void **)&cl_stamps, 128)); HIP_TRY(hipMemset(cl_stamps, 0, 128)); }
+            unsigned long long *cl_stamps = p->cl_stamps.get();
+            if (!cl_stamps) { TRY(p->cl_stamps.alloc(16)); cl_stamps = p->cl_stamps.get(); HIP_TRY(hipMemset(cl_stamps, 0, 128)); }
             else {
                 unsigned long long hst[16];
                 HIP_TRY(hipMemcpy(hst, cl_stamps, 128, hipMemcpyDeviceToHost));
@@ -729,22 +744,22 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         ca.rot_guess = rot_guess ? rot_guess + (size_t)f0 * 3 : nullptr;
         ca.guess_mask = guess_mask ? guess_mask + f0 : nullptr;
         ca.out = out + f0;
-        if (p->debug) { ca.dbg_guess = p->dbg_guess; ca.dbg_trace = p->dbg_trace; ca.dbg_steps = p->dbg_steps; }
+        if (p->debug) { ca.dbg_guess = ws.dbg_guess.get(); ca.dbg_trace = ws.dbg_trace.get(); ca.dbg_steps = ws.dbg_steps.get(); }
         // few frames with many hit records each: the first region of every accumulator is gathered by several workgroups
         const int slices = std::min(16, 256 / std::max(n, 1));
-        if (p->pre_region && slices >= 2 && f0 + n <= p->pre_cap && ca.iterations > 0) {
-            ca.pre_region = p->pre_region + (size_t)f0 * 2 * DH_SUPER_CELLS;
+        if (ws.pre_region && slices >= 2 && f0 + n <= ws.pre_cap && ca.iterations > 0) {
+            ca.pre_region = ws.pre_region.get() + (size_t)f0 * 2 * DH_SUPER_CELLS;
             ca.pre_slices = slices;
-            ca.pre_min_hits = p->pre_min_hits;
+            ca.pre_min_hits = ws.pre_min_hits;
             // (a kernel node inside a captured graph, like the counters' fill)
             const size_t pre_bytes = (size_t)n * 2 * DH_SUPER_CELLS * sizeof(uint32_t);
             if (p->capturing) HIP_TRY(dh_launch_zero(ca.pre_region, pre_bytes, s));
             else HIP_TRY(hipMemsetAsync(ca.pre_region, 0, pre_bytes, s));
-            { Range r(profile, "dh:region"); HIP_TRY(dh_launch_region(ca, s)); }
+            { Range r(o.profile, "dh:region"); HIP_TRY(dh_launch_region(ca, s)); }
         }
-        { Range r(profile, "dh:cluster"); HIP_TRY(dh_launch_cluster(ca, s)); }
+        { Range r(o.profile, "dh:cluster"); HIP_TRY(dh_launch_cluster(ca, s)); }
     }
-    if (profile) { HIP_TRY(hipEventRecord(p->ev[3], s)); p->ev_valid = true; }
+    if (o.profile) { HIP_TRY(hipEventRecord(p->ev[3], s)); p->ev_valid = true; }
     return DH_OK;
 }
 
@@ -783,23 +798,26 @@ static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n,
         // The per-batch counters: one kernel sequence on the uniform path has them cleared by its first kernel (k_boxsum: every
         // wave of its grid takes a share; the tile flags carry tags and need no fill) -- one dispatch less per batch, 4.7 us of a
         // single frame's 95.  Forked sub-batches, the general path and frames smaller than the patch keep the fill.
-        const bool fold = chunks <= 1 && p->geom.uniform && p->geom.npatch > 0 && p->zero_words < 0xffffffffull && !p->knobs.no_zero_fold;
+        const Workspace &ws = p->ws;
+        const bool fold = chunks <= 1 && ws.geom.uniform && ws.geom.npatch > 0 && ws.lay.zero_words < 0xffffffffull && !p->knobs.no_zero_fold;
         if (!fold) {
             // (inside a captured graph the zero-fill is a kernel node: see k_zero)
-            if (p->capturing) HIP_TRY(dh_launch_zero(p->counters, (p->zero_words * sizeof(uint32_t) + 15) & ~(size_t)15, s));
-            else HIP_TRY(hipMemsetAsync(p->counters, 0, p->zero_words * sizeof(uint32_t), s));
+            if (p->capturing) HIP_TRY(dh_launch_zero(ws.counters.get(), (ws.lay.zero_words * sizeof(uint32_t) + 15) & ~(size_t)15, s));
+            else HIP_TRY(hipMemsetAsync(ws.counters.get(), 0, ws.lay.zero_words * sizeof(uint32_t), s));
         }
         if (chunks <= 1) {
-            rc = enqueue_range(p, fr, 0, m, w, h, K, kinv, mg, rg, gm, out + f0, s, p->profiling, nullptr, nullptr, false, 0, fold);
-            if (rc) return rc;
+            EnqueueOpts o;
+            o.profile = p->profiling; o.zero_fold = fold;
+            TRY(enqueue_range(p, fr, 0, m, w, h, K, kinv, mg, rg, gm, out + f0, s, o));
         } else {
             HIP_TRY(hipEventRecord(p->ev_fork, s));
             for (int c = 0; c < chunks; ++c) {
                 const int c0 = (int)((long long)m * c / chunks), c1 = (int)((long long)m * (c + 1) / chunks);
                 hipStream_t cs = c == 0 ? s : p->aux_stream[c - 1];
                 if (c > 0) HIP_TRY(hipStreamWaitEvent(cs, p->ev_fork, 0));
-                rc = enqueue_range(p, fr, c0, c1 - c0, w, h, K, kinv, mg, rg, gm, out + f0, cs, false, nullptr, nullptr, false, c);
-                if (rc) return rc;
+                EnqueueOpts o;
+                o.chunk = c;
+                TRY(enqueue_range(p, fr, c0, c1 - c0, w, h, K, kinv, mg, rg, gm, out + f0, cs, o));
                 if (c > 0) {
                     HIP_TRY(hipEventRecord(p->ev_join[c - 1], cs));
                     HIP_TRY(hipStreamWaitEvent(s, p->ev_join[c - 1], 0));
@@ -809,43 +827,21 @@ static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n,
     }
     p->last_n = std::min(n, slice);   // the taps describe the last resident slice
     p->last_frames = frames;
-    p->dbg_valid = p->debug;
+    p->ws.dbg_valid = p->debug;
     return DH_OK;
 }
 
-static int ensure_frame_staging(dh_predictor *p, size_t fbytes) {
-    if (fbytes > p->ws_frames_bytes) {
-        HIP_TRY(hipStreamSynchronize(p->own_stream));
-        HIP_TRY(hipStreamSynchronize(p->copy_stream));
-        if (p->ws_frames) (void)hipFree(p->ws_frames);
-        p->ws_frames = nullptr; p->ws_frames_bytes = 0;
-        size_t want = fbytes;
-        int rc = dev_alloc(p, &p->ws_frames, want / sizeof(uint16_t));
-        if (rc) return rc;
-        p->ws_frames_bytes = want;
-    }
-    return DH_OK;
+// n frames of w x h in ws.frames
+static int ensure_frame_staging(dh_predictor *p, int n, int w, int h) {
+    const size_t px = (size_t)n * w * h;
+    if (px <= p->ws.frames.cap()) return DH_OK;
+    HIP_TRY(hipStreamSynchronize(p->own_stream));
+    HIP_TRY(hipStreamSynchronize(p->copy_stream));
+    return p->ws.frames.alloc(px);
 }
 static int stage_frames(dh_predictor *p, const uint16_t *frames, int n, int w, int h) {
-    size_t fbytes = (size_t)n * w * h * sizeof(uint16_t);
-    int rc = ensure_frame_staging(p, fbytes);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(p->ws_frames, frames, fbytes, hipMemcpyHostToDevice, p->own_stream));
-    return DH_OK;
-}
-
-// Staging buffers that only ever grow: a quarter and 4 096 elements of headroom over `need`, the old contents dropped.
-enum Mem { PINNED, DEVICE };
-template <typename T>
-static int grow(T **buf, size_t *cap, size_t need, Mem mem) {
-    if (need <= *cap) return DH_OK;
-    if (*buf) (void)(mem == PINNED ? hipHostFree(*buf) : hipFree(*buf));
-    *buf = nullptr; *cap = 0;
-    const size_t want = need + need / 4 + 4096;
-    void *q = nullptr;
-    hipError_t e = mem == PINNED ? hipHostMalloc(&q, want * sizeof(T), hipHostMallocDefault) : hipMalloc(&q, want * sizeof(T));
-    if (e != hipSuccess) return fail(DH_ENOMEM, "%s(%zu bytes): %s", mem == PINNED ? "hipHostMalloc" : "hipMalloc", want * sizeof(T), hipGetErrorString(e));
-    *buf = (T *)q; *cap = want;
+    TRY(ensure_frame_staging(p, n, w, h));
+    HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), frames, (size_t)n * w * h * sizeof(uint16_t), hipMemcpyHostToDevice, p->own_stream));
     return DH_OK;
 }
 
@@ -859,9 +855,8 @@ struct SmallStage {
 };
 static int small_stage(dh_predictor *p, int m, SmallStage *st) {
     const size_t need = (size_t)m * (sizeof(dh_pose) + 3 * sizeof(double) + 3 * sizeof(float) + 1) + 64;
-    int rc = grow(&p->pin_small, &p->pin_small_cap, need, PINNED);      // (only between slices: both streams are idle)
-    if (rc) return rc;
-    st->poses = (dh_pose *)p->pin_small;
+    TRY(p->pin_small.grow(need));      // (only between slices: both streams are idle)
+    st->poses = (dh_pose *)p->pin_small.get();
     st->rot = (double *)(st->poses + m);
     st->midp = (float *)(st->rot + (size_t)m * 3);
     st->mask = (uint8_t *)(st->midp + (size_t)m * 3);
@@ -874,33 +869,33 @@ struct Guesses {
 // Per-slice setup of the host batch paths: the workspace and frame staging for m frames of w x h, and the guesses of
 // frames [f0, f0 + m) through the pinned staging block into the workspace's device arrays on own_stream.
 static int slice_setup(dh_predictor *p, int f0, int m, int w, int h, const Guesses &g, SmallStage *st) {
-    int rc = reserve(p, m, w, h);
-    if (rc == DH_OK) rc = ensure_frame_staging(p, (size_t)m * w * h * sizeof(uint16_t));
-    if (rc == DH_OK) rc = small_stage(p, m, st);
-    if (rc) return rc;
+    TRY(reserve(p, m, w, h));
+    TRY(ensure_frame_staging(p, m, w, h));
+    TRY(small_stage(p, m, st));
     hipStream_t s = p->own_stream;
     if (g.midp) {
         memcpy(st->midp, g.midp + (size_t)f0 * 3, (size_t)m * 3 * sizeof(float));
-        HIP_TRY(hipMemcpyAsync(p->ws_midp, st->midp, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->ws.midp.get(), st->midp, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, s));
     }
     if (g.rot) {
         memcpy(st->rot, g.rot + (size_t)f0 * 3, (size_t)m * 3 * sizeof(double));
-        HIP_TRY(hipMemcpyAsync(p->ws_rot, st->rot, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->ws.rot.get(), st->rot, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
     }
     if (g.mask) {
         memcpy(st->mask, g.mask + f0, (size_t)m);
-        HIP_TRY(hipMemcpyAsync(p->ws_mask, st->mask, (size_t)m, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->ws.mask.get(), st->mask, (size_t)m, hipMemcpyHostToDevice, s));
     }
     return DH_OK;
 }
 // Chunk [c0, c0 + cm) of a staged slice -- frames, guesses and poses in the workspace -- on stream s.
 static int predict_staged(dh_predictor *p, int c0, int cm, int w, int h, const float K[9], const Guesses &g, hipStream_t s) {
-    return dh_predict_batch_device(p, p->ws_frames + (size_t)c0 * w * h, cm, w, h, K, g.midp ? p->ws_midp + (size_t)c0 * 3 : nullptr,
-                                   g.rot ? p->ws_rot + (size_t)c0 * 3 : nullptr, g.mask ? p->ws_mask + c0 : nullptr, p->ws_poses + c0, s);
+    const Workspace &ws = p->ws;
+    return dh_predict_batch_device(p, ws.frames.get() + (size_t)c0 * w * h, cm, w, h, K, g.midp ? ws.midp.get() + (size_t)c0 * 3 : nullptr,
+                                   g.rot ? ws.rot.get() + (size_t)c0 * 3 : nullptr, g.mask ? ws.mask.get() + c0 : nullptr, ws.poses.get() + c0, s);
 }
 // poses of the slice: device -> staging on s, wait, -> the caller's array
 static int download_poses(dh_predictor *p, const SmallStage &st, int m, dh_pose *out, hipStream_t s) {
-    HIP_TRY(hipMemcpyAsync(st.poses, p->ws_poses, (size_t)m * sizeof(dh_pose), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(st.poses, p->ws.poses.get(), (size_t)m * sizeof(dh_pose), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     memcpy(out, st.poses, (size_t)m * sizeof(dh_pose));
     return DH_OK;
@@ -941,7 +936,7 @@ static int predict_batch_(dh_predictor *p, const uint16_t *frames, int n, int w,
         const int nchunks = dh_chunk_plan_(m, p->knobs.stage_chunk, p->debug, cstart);
         if (nchunks == 1) {
             // latency path (single frames, small batches): one copy on the compute stream itself
-            HIP_TRY(hipMemcpyAsync(p->ws_frames, frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
             rc = predict_staged(p, 0, m, w, h, K, g, s);
             if (rc) { (void)hipStreamSynchronize(s); return rc; }
         } else {
@@ -954,7 +949,7 @@ static int predict_batch_(dh_predictor *p, const uint16_t *frames, int n, int w,
             HIP_TRY(hipStreamWaitEvent(cs, p->ev_slice, 0));          // the previous slice's kernels have read the staging buffer
             for (int k = 0; k < nchunks; ++k) {
                 const int c0 = cstart[k], cm = cstart[k + 1] - c0;
-                HIP_TRY(hipMemcpyAsync(p->ws_frames + (size_t)c0 * fpx, frames + (size_t)(f0 + c0) * fpx, (size_t)cm * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, cs));
+                HIP_TRY(hipMemcpyAsync(p->ws.frames.get() + (size_t)c0 * fpx, frames + (size_t)(f0 + c0) * fpx, (size_t)cm * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, cs));
                 HIP_TRY(hipEventRecord(p->ev_stage[k], cs));
                 HIP_TRY(hipStreamWaitEvent(s, p->ev_stage[k], 0));
                 rc = predict_staged(p, c0, cm, w, h, K, g, s);
@@ -987,15 +982,14 @@ static int rle_prepare(dh_predictor *p, const uint8_t *const *bufs, const size_t
     int rc = dh_rle_plan_(bufs, lens, n, p->knobs.host_threads, plan);
     if (rc) return rc;
     const size_t blob_bytes = plan.blob_off[n];
-    rc = grow(&p->pin_begin, &p->pin_begin_cap, (size_t)n + 1, PINNED);
-    if (rc == DH_OK) rc = grow(&p->pin_blob, &p->pin_blob_cap, blob_bytes, PINNED);
-    if (rc == DH_OK) rc = grow(&p->pin_runs, &p->pin_runs_cap, std::max<size_t>(plan.nruns, 1), PINNED);
-    if (rc == DH_OK) rc = grow(&p->dev_blob, &p->dev_blob_cap, blob_bytes, DEVICE);
-    if (rc == DH_OK) rc = grow(&p->dev_runs, &p->dev_runs_cap, std::max<size_t>(plan.nruns, 1), DEVICE);
-    if (rc == DH_OK) rc = grow(&p->dev_begin, &p->dev_begin_cap, (size_t)n + 1, DEVICE);
-    if (rc) return rc;
-    memcpy(p->pin_begin, plan.run_begin.data(), ((size_t)n + 1) * sizeof(uint32_t));
-    dh_rle_pack_(bufs, lens, n, p->knobs.host_threads, plan, p->pin_blob, (DhRun *)p->pin_runs);
+    TRY(p->pin_begin.grow((size_t)n + 1));
+    TRY(p->pin_blob.grow(blob_bytes));
+    TRY(p->pin_runs.grow(std::max<size_t>(plan.nruns, 1)));
+    TRY(p->dev_blob.grow(blob_bytes));
+    TRY(p->dev_runs.grow(std::max<size_t>(plan.nruns, 1)));
+    TRY(p->dev_begin.grow((size_t)n + 1));
+    memcpy(p->pin_begin.get(), plan.run_begin.data(), ((size_t)n + 1) * sizeof(uint32_t));
+    dh_rle_pack_(bufs, lens, n, p->knobs.host_threads, plan, p->pin_blob.get(), (DhRun *)p->pin_runs.get());
     return DH_OK;
 }
 
@@ -1005,15 +999,15 @@ static int rle_upload_decode(dh_predictor *p, const std::vector<size_t> &blob_of
                              uint16_t *frames_dev, hipStream_t s) {
     hipStream_t cs = p->copy_stream;
     const size_t b0 = blob_off[c0], b1 = blob_off[c0 + cm];
-    const uint32_t r0 = p->pin_begin[c0], r1 = p->pin_begin[c0 + cm];
-    HIP_TRY(hipMemcpyAsync(p->dev_blob + b0, p->pin_blob + b0, b1 - b0, hipMemcpyHostToDevice, cs));
-    if (r1 > r0) HIP_TRY(hipMemcpyAsync(p->dev_runs + r0, p->pin_runs + r0, (size_t)(r1 - r0) * sizeof(uint2), hipMemcpyHostToDevice, cs));
+    const uint32_t r0 = p->pin_begin.get()[c0], r1 = p->pin_begin.get()[c0 + cm];
+    HIP_TRY(hipMemcpyAsync(p->dev_blob.get() + b0, p->pin_blob.get() + b0, b1 - b0, hipMemcpyHostToDevice, cs));
+    if (r1 > r0) HIP_TRY(hipMemcpyAsync(p->dev_runs.get() + r0, p->pin_runs.get() + r0, (size_t)(r1 - r0) * sizeof(uint2), hipMemcpyHostToDevice, cs));
     hipEvent_t ev = p->ev_stage[ci % DH_STAGE_EVENTS];
     HIP_TRY(hipEventRecord(ev, cs));
     HIP_TRY(hipStreamWaitEvent(s, ev, 0));
     HIP_TRY(hipMemsetAsync(frames_dev, 0, (size_t)cm * W * H * sizeof(uint16_t), s));          // the empty runs (biwi.rs:90-93)
     RleArgs ra{};
-    ra.blob = (const uint16_t *)p->dev_blob; ra.runs = p->dev_runs; ra.run_begin = p->dev_begin + c0;
+    ra.blob = (const uint16_t *)p->dev_blob.get(); ra.runs = p->dev_runs.get(); ra.run_begin = p->dev_begin.get() + c0;
     // the run table addresses pixels of the whole batch: frame c0 of the chunk is pixel c0 * W * H there
     ra.frames = frames_dev - (size_t)c0 * W * H; ra.n_frames = cm;
     const uint32_t per_frame = (r1 - r0 + (uint32_t)cm - 1) / (uint32_t)cm;
@@ -1037,7 +1031,7 @@ static int biwi_decode_depth_device_(dh_predictor *p, const uint8_t *const *bufs
     *w = W; *h = H;
     if (!frames_dev) return DH_OK;                            // size query (validates as well)
     if (cap_px < (size_t)n * W * H) return fail(DH_EINVAL, "output holds %zu pixels, the batch has %zu", cap_px, (size_t)n * W * H);
-    HIP_TRY(hipMemcpyAsync(p->dev_begin, p->pin_begin, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p->own_stream));
+    HIP_TRY(hipMemcpyAsync(p->dev_begin.get(), p->pin_begin.get(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, p->own_stream));
     const int chunk = std::min(n, p->knobs.stage_chunk * 2);
     int ci = 0;
     for (int c0 = 0; c0 < n; c0 += chunk, ++ci) {
@@ -1067,12 +1061,12 @@ static int predict_batch_rle_(dh_predictor *p, const uint8_t *const *bufs, const
         const uint32_t W = plan.W, H = plan.H;
         rc = slice_setup(p, f0, m, (int)W, (int)H, g, st);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(p->dev_begin, p->pin_begin, ((size_t)m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->dev_begin.get(), p->pin_begin.get(), ((size_t)m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         const int chunk = p->debug ? m : std::min(m, p->knobs.stage_chunk * 2);   // compressed chunks are small: twice the raw chunk
         int ci = 0;
         for (int c0 = 0; c0 < m; c0 += chunk, ++ci) {
             const int cm = std::min(chunk, m - c0);
-            rc = rle_upload_decode(p, plan.blob_off, c0, cm, ci, W, H, p->ws_frames + (size_t)c0 * W * H, s);
+            rc = rle_upload_decode(p, plan.blob_off, c0, cm, ci, W, H, p->ws.frames.get() + (size_t)c0 * W * H, s);
             if (rc == DH_OK) rc = predict_staged(p, c0, cm, (int)W, (int)H, K, g, s);
             if (rc) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamSynchronize(s); return rc; }
         }
@@ -1128,27 +1122,20 @@ static int graph_launch_(dh_predictor *p, void *stream) {
 
 // ------------------------------------------------------------------ predict_mask / 2-D Hough votes
 static int aux_reserve(dh_predictor *p, int n, int w, int h, size_t out_bytes) {
-    int rc = reserve(p, n, w, h);
-    if (rc) return rc;
-    const Geom &g = p->geom;
-    if (p->aux_cap < p->cap_frames || !p->aux_leaf) {
+    TRY(reserve(p, n, w, h));
+    Workspace &ws = p->ws;
+    const size_t cap = ws.cap_frames, npatch = std::max(ws.geom.npatch, 1);
+    if (ws.aux_cap < ws.cap_frames || !ws.aux_leaf) {
         HIP_TRY(hipDeviceSynchronize());
-        for (void *q : {(void *)p->aux_leaf, (void *)p->aux_flags, (void *)p->aux_u32}) if (q) (void)hipFree(q);
-        p->aux_leaf = nullptr; p->aux_flags = nullptr; p->aux_u32 = nullptr; p->aux_cap = 0;
-        rc = dev_alloc(p, &p->aux_leaf, (size_t)p->cap_frames * std::max(g.npatch, 1) * p->n_trees);
-        if (rc == DH_OK) rc = dev_alloc(p, &p->aux_flags, (size_t)p->cap_frames * std::max(g.npatch, 1));
-        if (rc == DH_OK) rc = dev_alloc(p, &p->aux_u32, (size_t)p->cap_frames * w * h);
-        if (rc) return rc;
-        p->aux_cap = p->cap_frames;
+        ws.aux_cap = 0;
+        TRY(ws.aux_leaf.alloc(cap * npatch * p->n_trees));
+        TRY(ws.aux_flags.alloc(cap * npatch));
+        TRY(ws.aux_u32.alloc(cap * w * h));
+        ws.aux_cap = ws.cap_frames;
     }
-    if (out_bytes > p->aux_out_bytes) {
+    if (out_bytes > ws.aux_out.cap()) {
         HIP_TRY(hipDeviceSynchronize());
-        if (p->aux_out) (void)hipFree(p->aux_out);
-        p->aux_out = nullptr; p->aux_out_bytes = 0;
-        uint8_t *q = nullptr;
-        rc = dev_alloc(p, &q, out_bytes);
-        if (rc) return rc;
-        p->aux_out = q; p->aux_out_bytes = out_bytes;
+        TRY(ws.aux_out.alloc(out_bytes));
     }
     return DH_OK;
 }
@@ -1158,14 +1145,10 @@ static int blur_kernel(dh_predictor *p) {
     const float sigma = p->params.gaussian_sigma;
     if (p->blur_kern && p->blur_sigma == sigma) return DH_OK;
     std::vector<float> k;
-    int rc0 = dh_blur_taps_(sigma, k);
-    if (rc0) return rc0;
+    TRY(dh_blur_taps_(sigma, k));
     HIP_TRY(hipDeviceSynchronize());
-    if (p->blur_kern) (void)hipFree(p->blur_kern);
-    p->blur_kern = nullptr;
-    int rc = dev_alloc(p, &p->blur_kern, k.size());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(p->blur_kern, k.data(), k.size() * sizeof(float), hipMemcpyHostToDevice));
+    TRY(p->blur_kern.alloc(k.size()));
+    HIP_TRY(hipMemcpy(p->blur_kern.get(), k.data(), k.size() * sizeof(float), hipMemcpyHostToDevice));
     p->blur_klen = (int)k.size(); p->blur_sigma = sigma;
     return DH_OK;
 }
@@ -1175,22 +1158,22 @@ enum : unsigned { AUX_MASK = 1, AUX_VOTES = 2, AUX_BLUR = 4, AUX_POSES = 8 };   
 // One resident slice of frames: the mask (AUX_MASK) or the vote image into `img`, the 2-D poses into `poses2d`.
 static int aux_run(dh_predictor *p, unsigned req, const uint16_t *frames, int n, int w, int h, const float K[9], void *img,
                    dh_pose *poses2d, hipStream_t s) {
-    const Geom &g = p->geom;
+    const Workspace &ws = p->ws;
+    const Geom &g = ws.geom;
     float kinv[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, kid[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     if (K) dh_mat3_inv_f32_(K, kinv);
-    HIP_TRY(hipMemsetAsync(p->counters, 0, (size_t)p->cap_frames * sizeof(uint32_t), s));   // hit counters only
-    HIP_TRY(hipMemsetAsync(p->counters + (size_t)p->cap_frames * (1 + DH_POSGRID + DH_GRID3), 0,
-                           (size_t)p->cap_frames * ((size_t)p->geom.flag_words + (size_t)p->geom.tiles_x * p->geom.tiles_y) * sizeof(uint32_t), s));   // tile flags, window counts
-    HIP_TRY(hipMemsetAsync(p->aux_flags, 0, (size_t)n * std::max(g.npatch, 1), s));
-    int rc = enqueue_range(p, frames, 0, n, w, h, K ? K : kid, kinv, nullptr, nullptr, nullptr, p->ws_poses, s, false,
-                           p->aux_leaf, p->aux_flags, true);
-    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(ws.hit_count(0), 0, (ws.lay.pos_grid - ws.lay.hit_count) * sizeof(uint32_t), s));   // hit counters only
+    HIP_TRY(hipMemsetAsync(ws.tile_flags(0), 0, (ws.lay.leaf_hits - ws.lay.tile_flags) * sizeof(uint32_t), s));   // tile flags, window counts
+    HIP_TRY(hipMemsetAsync(ws.aux_flags.get(), 0, (size_t)n * std::max(g.npatch, 1), s));
+    EnqueueOpts o;
+    o.leaf_out = ws.aux_leaf.get(); o.flags_out = ws.aux_flags.get(); o.traverse_only = true;
+    TRY(enqueue_range(p, frames, 0, n, w, h, K ? K : kid, kinv, nullptr, nullptr, nullptr, ws.poses.get(), s, o));
     AuxArgs a{};
     a.frames = frames; a.n_frames = n; a.w = w; a.h = h;
     a.step = (int)p->params.stepwidth; a.sw = (int)p->params.subimage_width; a.sh = (int)p->params.subimage_height;
     a.lw = a.sw / 2; a.lh = a.sh / 2; a.nx = g.nx; a.ny = g.ny;
     memcpy(a.k, K ? K : kid, sizeof a.k); memcpy(a.kinv, kinv, sizeof a.kinv);
-    a.f = p->dev; a.leaf = p->aux_leaf; a.flags = p->aux_flags;
+    a.f = p->dev; a.leaf = ws.aux_leaf.get(); a.flags = ws.aux_flags.get();
     if (req & AUX_MASK) {
         HIP_TRY(hipMemsetAsync(img, 0, (size_t)n * w * h, s));          // ImageBuffer::new zero-fills (prediction.rs:852)
         a.mask = (uint8_t *)img;
@@ -1198,11 +1181,11 @@ static int aux_run(dh_predictor *p, unsigned req, const uint16_t *frames, int n,
     }
     if (req & AUX_VOTES) {
         uint16_t *hough = (uint16_t *)img;
-        HIP_TRY(hipMemsetAsync(p->aux_u32, 0, (size_t)n * w * h * sizeof(uint32_t), s));
-        a.hough32 = p->aux_u32;
+        HIP_TRY(hipMemsetAsync(ws.aux_u32.get(), 0, (size_t)n * w * h * sizeof(uint32_t), s));
+        a.hough32 = ws.aux_u32.get();
         HIP_TRY(dh_launch_hough2d(a, hough, s));
         // gaussian_blur_f32 (prediction.rs:844): horizontal pass into the (now free) 32-bit scratch, vertical pass back
-        if (req & AUX_BLUR) HIP_TRY(dh_launch_blur_u16(hough, (uint16_t *)p->aux_u32, hough, n, w, h, p->blur_kern, p->blur_klen, s));
+        if (req & AUX_BLUR) HIP_TRY(dh_launch_blur_u16(hough, (uint16_t *)ws.aux_u32.get(), hough, n, w, h, p->blur_kern.get(), p->blur_klen, s));
         if (req & AUX_POSES) HIP_TRY(dh_launch_argmax2d(hough, frames, n, w, h, kinv, poses2d, s));
     }
     p->last_n = 0;   // the pose taps do not refer to this run
@@ -1233,12 +1216,12 @@ static int aux_call(dh_predictor *p, const char *fn, unsigned req, const uint16_
         if (rc == DH_OK && host) rc = stage_frames(p, frames + f0 * px, m, w, h);
         if (rc == DH_OK && host && poses) rc = small_stage(p, m, &st);
         if (rc == DH_OK)
-            rc = aux_run(p, req, host ? p->ws_frames : frames + f0 * px, m, w, h, K, host || poses ? p->aux_out : dst,
-                         !poses ? nullptr : host ? p->ws_poses : (dh_pose *)out + f0, s);
+            rc = aux_run(p, req, host ? p->ws.frames.get() : frames + f0 * px, m, w, h, K, host || poses ? p->ws.aux_out.get() : dst,
+                         !poses ? nullptr : host ? p->ws.poses.get() : (dh_pose *)out + f0, s);
         if (rc == DH_OK && host && poses) rc = download_poses(p, st, m, (dh_pose *)out + f0, s);
         if (rc) return rc;
         if (host && !poses) {
-            HIP_TRY(hipMemcpyAsync(dst, p->aux_out, ob, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(dst, p->ws.aux_out.get(), ob, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
     }
@@ -1299,7 +1282,7 @@ static int get_timing_(dh_predictor *p, dh_timing *out) {
 static int debug_enable_(dh_predictor *p, int on) {
     if (!p) return fail(DH_EINVAL, "NULL predictor");
     p->debug = on != 0;
-    if (!p->debug) p->dbg_valid = false;
+    if (!p->debug) p->ws.dbg_valid = false;
     return DH_OK;
 }
 // Runs a tap's body on the predictor's device once the last batch is complete (dbg: a batch that ran with the taps on).
@@ -1311,44 +1294,44 @@ static int with_taps(dh_predictor *p, bool dbg, F body) {
     if (!guard.ok) return DH_EHIP;
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return fail(DH_EHIP, "sync: %s", hipGetErrorString(e));
-    if (dbg && !p->dbg_valid) return fail(DH_ESTATE, "debug taps were not enabled for the last batch");
+    if (dbg && !p->ws.dbg_valid) return fail(DH_ESTATE, "debug taps were not enabled for the last batch");
     return body();
 }
 static int debug_leaf_indices_(dh_predictor *p, int32_t *out, size_t cap) {
     return with_taps(p, true, [&]() -> int {
-        size_t n = (size_t)p->last_n * p->geom.npatch * p->n_trees;
+        size_t n = (size_t)p->last_n * p->ws.geom.npatch * p->n_trees;
         if (!out || cap < n) return fail(DH_EINVAL, "buffer too small: need %zu elements", n);
-        if (n) HIP_TRY(hipMemcpy(out, p->dbg_leaf, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (n) HIP_TRY(hipMemcpy(out, p->ws.dbg_leaf.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
         return DH_OK;
     });
 }
 static int debug_patch_flags_(dh_predictor *p, uint8_t *out, size_t cap) {
     return with_taps(p, true, [&]() -> int {
-        size_t n = (size_t)p->last_n * p->geom.npatch;
+        size_t n = (size_t)p->last_n * p->ws.geom.npatch;
         if (!out || cap < n) return fail(DH_EINVAL, "buffer too small: need %zu elements", n);
-        if (n) HIP_TRY(hipMemcpy(out, p->dbg_flags, n, hipMemcpyDeviceToHost));
+        if (n) HIP_TRY(hipMemcpy(out, p->ws.dbg_flags.get(), n, hipMemcpyDeviceToHost));
         return DH_OK;
     });
 }
 static int debug_grids_(dh_predictor *p, uint32_t *pos_grid, uint32_t *rot_grid) {
     return with_taps(p, false, [&]() -> int {
-        const uint32_t *pg = p->counters + p->cap_frames, *rg = pg + (size_t)p->cap_frames * DH_POSGRID;
-        if (pos_grid) HIP_TRY(hipMemcpy(pos_grid, pg, (size_t)p->last_n * DH_POSGRID * 4, hipMemcpyDeviceToHost));
-        if (rot_grid) HIP_TRY(hipMemcpy(rot_grid, rg, (size_t)p->last_n * DH_GRID3 * 4, hipMemcpyDeviceToHost));
+        const Workspace &ws = p->ws;       // (frames [0, last_n) of each grid)
+        if (pos_grid) HIP_TRY(hipMemcpy(pos_grid, ws.pos_grid(0), (ws.pos_grid(p->last_n) - ws.pos_grid(0)) * 4, hipMemcpyDeviceToHost));
+        if (rot_grid) HIP_TRY(hipMemcpy(rot_grid, ws.rot_grid(0), (ws.rot_grid(p->last_n) - ws.rot_grid(0)) * 4, hipMemcpyDeviceToHost));
         return DH_OK;
     });
 }
 static int debug_hit_counts_(dh_predictor *p, uint32_t *out) {
     return with_taps(p, false, [&]() -> int {
         if (!out) return fail(DH_EINVAL, "NULL output");
-        HIP_TRY(hipMemcpy(out, p->counters, (size_t)p->last_n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, p->ws.hit_count(0), (size_t)p->last_n * 4, hipMemcpyDeviceToHost));
         return DH_OK;
     });
 }
 static int debug_geometry_(dh_predictor *p, int32_t out[10]) {
     if (!p || !out) return fail(DH_EINVAL, "NULL argument");
-    if (p->cap_frames == 0) return fail(DH_ESTATE, "no workspace yet (dh_predictor_reserve or a batch)");
-    const Geom &g = p->geom;
+    if (p->ws.cap_frames == 0) return fail(DH_ESTATE, "no workspace yet (dh_predictor_reserve or a batch)");
+    const Geom &g = p->ws.geom;
     const bool walk_tab = g.uniform && p->absorb_ok;
     const int32_t v[10] = {(g.uniform ? 1 : 0) | (walk_tab ? 1 << 8 : 0) | (walk_tab ? g.top_levels << 16 : 0), g.px, g.py, g.tiles_x, g.tiles_y, g.swz_log2, g.swz_q, g.ss_row, p->f_rw, p->f_rh};
     memcpy(out, v, sizeof v);
@@ -1357,7 +1340,7 @@ static int debug_geometry_(dh_predictor *p, int32_t out[10]) {
 static int debug_guesses_(dh_predictor *p, int32_t *out) {
     return with_taps(p, true, [&]() -> int {
         if (!out) return fail(DH_EINVAL, "NULL output");
-        HIP_TRY(hipMemcpy(out, p->dbg_guess, (size_t)p->last_n * 6 * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, p->ws.dbg_guess.get(), (size_t)p->last_n * 6 * 4, hipMemcpyDeviceToHost));
         return DH_OK;
     });
 }
@@ -1366,8 +1349,8 @@ static int debug_meanshift_(dh_predictor *p, int which, int32_t *trace, uint32_t
         if (which < 0 || which > 1) return fail(DH_EINVAL, "which must be 0 or 1");
         size_t per = (size_t)(p->params.meanshift_iterations + 1) * 3;
         // device layout is [2][last batch n][...]: the kernel indexed with n_frames = last_n
-        if (trace) HIP_TRY(hipMemcpy(trace, p->dbg_trace + (size_t)which * p->last_n * per, (size_t)p->last_n * per * 4, hipMemcpyDeviceToHost));
-        if (steps) HIP_TRY(hipMemcpy(steps, p->dbg_steps + (size_t)which * p->last_n, (size_t)p->last_n * 4, hipMemcpyDeviceToHost));
+        if (trace) HIP_TRY(hipMemcpy(trace, p->ws.dbg_trace.get() + (size_t)which * p->last_n * per, (size_t)p->last_n * per * 4, hipMemcpyDeviceToHost));
+        if (steps) HIP_TRY(hipMemcpy(steps, p->ws.dbg_steps.get() + (size_t)which * p->last_n, (size_t)p->last_n * 4, hipMemcpyDeviceToHost));
         return DH_OK;
     });
 }
@@ -1375,28 +1358,22 @@ static int debug_votes_(dh_predictor *p, int frame, int which, int32_t *out, siz
     return with_taps(p, false, [&]() -> int {
         if (frame < 0 || frame >= p->last_n || which < 0 || which > 1 || !count) return fail(DH_EINVAL, "bad frame / which / count");
         // k_emit writes the rotation records only without the leaf histogram or with the taps on
-        if (which == 1 && p->leaf_hits && !p->dbg_valid) return fail(DH_ESTATE, "rotation votes need dh_debug_enable(1) before the batch");
+        Workspace &ws = p->ws;
+        if (which == 1 && ws.lay.leaves && !ws.dbg_valid) return fail(DH_ESTATE, "rotation votes need dh_debug_enable(1) before the batch");
         if (cap > 0xffffffffull) cap = 0xffffffffull;
-        int rc = p->dbg_vcount ? DH_OK : dev_alloc(p, &p->dbg_vcount, 1);
-        if (rc) return rc;
-        if (cap > p->dbg_votes_cap) {
-            if (p->dbg_votes) (void)hipFree(p->dbg_votes);
-            p->dbg_votes = nullptr; p->dbg_votes_cap = 0;
-            rc = dev_alloc(p, &p->dbg_votes, cap * 4);
-            if (rc) return rc;
-            p->dbg_votes_cap = cap;
-        }
-        HIP_TRY(hipMemset(p->dbg_vcount, 0, 4));
+        if (!ws.dbg_vcount) TRY(ws.dbg_vcount.alloc(1));
+        if (cap * 4 > ws.dbg_votes.cap()) TRY(ws.dbg_votes.alloc(cap * 4));
+        HIP_TRY(hipMemset(ws.dbg_vcount.get(), 0, 4));
         VotesDumpArgs a{};
-        a.frame = frame; a.which = which; a.f = p->dev; a.hits = p->hits; a.hit_box = p->hit_box; a.hit_rot = p->hit_rot; a.hit_count = p->counters; a.hits_cap = p->hits_cap;
-        a.out = p->dbg_votes; a.cap = (uint32_t)cap; a.count = p->dbg_vcount;
+        a.frame = frame; a.which = which; a.f = p->dev; a.hits = ws.hits.get(); a.hit_box = ws.hit_box.get(); a.hit_rot = ws.hit_rot.get(); a.hit_count = ws.hit_count(0); a.hits_cap = ws.hits_cap;
+        a.out = ws.dbg_votes.get(); a.cap = (uint32_t)cap; a.count = ws.dbg_vcount.get();
         HIP_TRY(dh_launch_votes_dump(a, nullptr));
         HIP_TRY(hipDeviceSynchronize());
         uint32_t c = 0;
-        HIP_TRY(hipMemcpy(&c, p->dbg_vcount, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&c, ws.dbg_vcount.get(), 4, hipMemcpyDeviceToHost));
         *count = c;
         size_t ncopy = std::min<size_t>(c, cap);
-        if (ncopy && out) HIP_TRY(hipMemcpy(out, p->dbg_votes, ncopy * 16, hipMemcpyDeviceToHost));
+        if (ncopy && out) HIP_TRY(hipMemcpy(out, ws.dbg_votes.get(), ncopy * 16, hipMemcpyDeviceToHost));
         return DH_OK;
     });
 }

@@ -355,6 +355,22 @@ int dh_choose_tile_(const TileQuery &p, Geom &g) {
     return DH_OK;
 }
 
+// ------------------------------------------------------------------ per-batch counter block
+CounterLayout dh_counter_layout_(size_t cap, size_t flag_words, size_t tiles, size_t leaf_hist_leaves) {
+    CounterLayout l;
+    l.tiles = tiles; l.leaves = leaf_hist_leaves;
+    l.hit_count = 0;
+    l.pos_grid = l.hit_count + cap;
+    l.rot_grid = l.pos_grid + cap * DH_POSGRID;
+    l.tile_flags = l.rot_grid + cap * DH_GRID3;
+    l.win_count = l.tile_flags + cap * flag_words;
+    l.leaf_hits = l.win_count + cap * tiles;
+    l.zero_words = l.leaf_hits + cap * leaf_hist_leaves;
+    l.zero_lo = l.tile_flags; l.zero_hi = l.win_count;
+    l.alloc_words = l.zero_words + 4;
+    return l;
+}
+
 // ------------------------------------------------------------------ small numeric tables
 // Mat3<f32>::inv = adjugate / det, element-wise (meancov_estimation.rs:339-352); f32, no FMA
 // k_boxsum's bands (dh_host.h).  Measured on MI355X, 640 x 480, 24 x 24 rectangles, 3 parts (tools/experiments/box_bands_sweep.sh,

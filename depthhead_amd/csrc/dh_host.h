@@ -138,6 +138,22 @@ static const int kBoxSpan = 256, kBoxMaxRect = 96;   // image columns one k_boxs
 // ring's LDS); a wave marches its band + rh - 1 rows.  Picks the band count with the smallest (march) x (rounds of workgroups).
 int dh_box_bands_(int n, int parts, int rows, int blk, int rh, int wg_slots, int *oh);
 
+// ------------------------------------------------------------------ per-batch counter block
+#define DH_GRID3 8000          // 20^3
+#define DH_POSGRID 400         // 20^2
+// A workspace of `cap` frames keeps its per-batch counters in ONE allocation of u32 words, zeroed by one fill, region after
+// region: hit counts [cap] | position grids [cap][20^2] | rotation grids [cap][20^3] | tile flags [cap * flag_words] |
+// window counts [cap][tiles] | leaf histogram [cap][leaves] (absent: leaves = 0).  The tile flags are one byte per tile and
+// frame f's start at byte f * tiles of their region (flag_words * 4 >= tiles).
+struct CounterLayout {
+    size_t tiles = 0, leaves = 0;      // tile-flag bytes and window counts per frame; histogram words per frame
+    size_t hit_count = 0, pos_grid = 0, rot_grid = 0, tile_flags = 0, win_count = 0, leaf_hits = 0;   // first word of each region
+    size_t zero_lo = 0, zero_hi = 0;   // the tile flags' words: they carry tags, so k_boxsum's fold of the fill skips them
+    size_t zero_words = 0;             // the whole block: what the per-batch fill zeroes
+    size_t alloc_words = 0;            // zero_words + 4 (the zero-fill kernel rounds up to 16 bytes)
+};
+CounterLayout dh_counter_layout_(size_t cap, size_t flag_words, size_t tiles, size_t leaf_hist_leaves);
+
 // ------------------------------------------------------------------ small numeric tables (f32, no FMA: -ffp-contract=off)
 void dh_mat3_inv_f32_(const float m[9], float o[9]);                 // Mat3<f32>::inv (meancov_estimation.rs:339-352)
 void dh_build_kernel_r2_(float sigma, std::vector<float> &k, size_t padded);   // the same weights indexed by dx^2 + dy^2 + dz^2 (0 .. 300)

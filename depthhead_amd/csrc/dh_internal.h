@@ -7,8 +7,6 @@
 #include "dh_host.h"
 
 #define DH_GRID 20             // GUESS_GRID_PARTS and the mean-shift kernel edge
-#define DH_GRID3 8000          // 20^3
-#define DH_POSGRID 400         // 20^2
 #define DH_ROTPARTS 120
 #define DH_REGION_CELLS (26 * 26 * 26)   // k_cluster's LDS region of an accumulator (RG^3 in k_cluster.hip)
 #define DH_KERN_R2 304                    // Gaussian weights by squared distance 0 .. 300 (the 20^3 kernel holds 301 distinct values), padded

@@ -2,9 +2,9 @@
 // sanitizers: built by tests/test_host_sanitize.py with g++ -fsanitize=address,undefined and once more with
 // -fsanitize=thread.  Prints "host_check ok" and exits 0; any check that fails prints its line and exits 1.
 // Covers: forest validation (good / every refused kind), patch grids, tile selection across geometries (with the invariants
-// the kernels rely on), upload chunk plans, the run-length payload scanner / packer on well-formed, redundant and malformed
-// payloads (incl. every truncation point of a payload), the host BIWI parsers, knob parsing, the exception guard, and
-// dh_parallel_for_ / the thread-local error slots under concurrency.
+// the kernels rely on), the per-batch counter block's layout, upload chunk plans, the run-length payload scanner / packer on
+// well-formed, redundant and malformed payloads (incl. every truncation point of a payload), the host BIWI parsers, knob
+// parsing, the exception guard, and dh_parallel_for_ / the thread-local error slots under concurrency.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -199,6 +199,50 @@ static void test_geometry() {
         CHECK(dh_patch_grid_(q.params, 640, 480, &g.nx, &g.ny) == DH_OK && g.nx == 140 && g.ny == 100);
         g.npatch = g.nx * g.ny;
         CHECK(dh_choose_tile_(q, g) == DH_OK && g.px % 4 == 0 && g.lds <= 79u * 1024u);
+    }
+}
+
+// The per-batch counter block: the regions in order with no gap or overlap, the tile flags exactly [zero_lo, zero_hi), every
+// frame's flag bytes inside them, the leaf histogram last (or absent), +4 words of slack.  Geometries come from dh_choose_tile_.
+static void check_layout(size_t cap, size_t flag_words, size_t tiles, size_t leaves) {
+    const CounterLayout l = dh_counter_layout_(cap, flag_words, tiles, leaves);
+    CHECK(l.tiles == tiles && l.leaves == leaves);
+    const size_t start[6] = {l.hit_count, l.pos_grid, l.rot_grid, l.tile_flags, l.win_count, l.leaf_hits};
+    const size_t words[6] = {cap, cap * 400, cap * 8000, cap * flag_words, cap * tiles, cap * leaves};
+    size_t at = 0;
+    for (int r = 0; r < 6; ++r) { CHECK(start[r] == at); at += words[r]; }
+    CHECK(l.zero_words == at && l.alloc_words == at + 4);
+    CHECK(l.zero_lo == l.tile_flags && l.zero_hi == l.win_count && l.zero_hi - l.zero_lo == cap * flag_words);
+    CHECK(leaves ? l.leaf_hits + cap * leaves == l.zero_words : l.leaf_hits == l.zero_words);
+    for (size_t f0 = 0; f0 < cap; ++f0) {
+        const size_t b0 = l.tile_flags * 4 + f0 * l.tiles;      // frame f0's flag bytes: [b0, b0 + tiles)
+        CHECK(b0 >= l.zero_lo * 4 && b0 + tiles <= l.zero_hi * 4);
+    }
+}
+static void test_counter_layout() {
+    for (size_t cap : {1, 2, 3, 7, 64, 512})
+        for (size_t leaves : {0, 1, 1000, 16384}) {
+            check_layout(cap, 0, 0, leaves);                   // frames smaller than a patch: no tiles
+            check_layout(cap, 1, 1, leaves);
+            check_layout(cap, 1, 3, leaves);                   // flag_words * 4 > tiles
+            check_layout(cap, 2, 5, leaves);
+            check_layout(cap, 875, 3500, leaves);
+        }
+    // the flag words of real geometries
+    for (int it = 0; it < 200; ++it) {
+        dh_params p{};
+        p.stepwidth = 1 + rnd(12); p.subimage_width = 8 + rnd(120); p.subimage_height = 8 + rnd(120); p.gaussian_sigma = 8.0f; p.meanshift_iterations = 20;
+        Geom g;
+        g.w = (int)p.subimage_width + (int)rnd(700); g.h = (int)p.subimage_height + (int)rnd(500);
+        CHECK(dh_patch_grid_(p, g.w, g.h, &g.nx, &g.ny) == DH_OK);
+        g.npatch = g.nx * g.ny;
+        if (g.npatch == 0) continue;
+        TileQuery q;
+        q.params = p; q.n_trees = 1 + rnd(60);
+        if (dh_choose_tile_(q, g) != DH_OK) continue;
+        const size_t tiles = (size_t)g.tiles_x * g.tiles_y;
+        CHECK((size_t)g.flag_words * 4 >= tiles);
+        check_layout(1 + rnd(40), g.flag_words, tiles, rnd(2) ? 0 : 1 + rnd(5000));
     }
 }
 
@@ -439,6 +483,7 @@ int main() {
     test_rle();
     test_biwi_text();
     test_tables_and_knobs();
+    test_counter_layout();
     test_guard_and_threads();
     if (g_fail) { fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     printf("host_check ok\n");
