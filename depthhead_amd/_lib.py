@@ -49,7 +49,20 @@ EXPORTS = [
     "dh_graph_capture", "dh_graph_launch", "dh_graph_destroy",
     "dh_set_profiling", "dh_get_timing", "dh_debug_enable", "dh_debug_leaf_indices", "dh_debug_patch_flags",
     "dh_debug_grids", "dh_debug_guesses", "dh_debug_votes", "dh_debug_meanshift", "dh_debug_hit_counts", "dh_debug_geometry",
+    "dh_trainer_create", "dh_trainer_destroy", "dh_trainer_add_frames", "dh_trainer_fit", "dh_trainer_stats", "dh_forest_export",
 ]
+
+
+class TrainParams(C.Structure):
+    _fields_ = [("stepwidth", C.c_uint32), ("subimage_width", C.c_uint32), ("subimage_height", C.c_uint32),
+                ("max_depth", C.c_uint32), ("n_trees", C.c_uint32), ("subset_per_tree", C.c_uint32),
+                ("subrect_feature_scale", C.c_double), ("features_per_node", C.c_uint32), ("min_subset_size", C.c_uint32),
+                ("steepness", C.c_double), ("seed", C.c_uint64)]
+
+
+class TrainStats(C.Structure):
+    _fields_ = [("frames", C.c_uint64), ("pool_size", C.c_uint64), ("pool_positives", C.c_uint64), ("neg_det", C.c_uint64),
+                ("levels", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class DepthheadError(RuntimeError):

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "dh_host.h"
+#include "dh_train.h"
 
 #define DH_GRID 20             // GUESS_GRID_PARTS and the mean-shift kernel edge
 #define DH_ROTPARTS 120
@@ -273,6 +274,60 @@ struct RleArgs {
     uint16_t       *frames;     // [n_frames][h][w], zero-filled before the launch
     int n_frames, blocks_per_frame;
 };
+
+// ------------------------------------------------------------------ trainer (k_train.hip)
+// Window pass of one upload chunk: summed-area tables modulo 2^32 [n][h+1][w+1], then per frame the kept windows.
+struct TrainWinArgs {
+    const uint16_t *frames;     // [n][h][w]
+    const uint8_t  *masks;      // [n][h][w]
+    uint32_t       *sat;        // [n][h+1][w+1]
+    int n, w, h;
+    uint32_t W, H, step, lw, lh, nx, ny;
+    uint64_t seed, frame0;      // global index of the chunk's first frame (the window draws are keyed by it)
+    uint32_t *sel;              // [n][2 * DH_TRAIN_KEEP] kept window indices: negatives, then positives, each by ascending key
+    uint32_t *cnt;              // [n][2] kept negatives, positives
+};
+// Materialisation of the kept windows into the sample pool.
+struct TrainExtractArgs {
+    const uint16_t *frames;
+    const uint8_t  *masks;
+    const uint32_t *sat;
+    int w, h;
+    uint32_t W, H, step, lw, lh, nx;
+    uint32_t rw, rh, bw, bh;
+    const uint4    *list;       // per new sample: {frame in chunk, window index, pool slot, 0}
+    uint32_t        n_list;
+    const float    *kinv;       // [n][9] Mat3<f32>::inv of each frame's intrinsic
+    const float    *pos3d;      // [n][3]
+    const float    *rot_deg;    // [n][3]
+    uint32_t *box;              // pool: [slot][bh][bw] rectangle sums
+    uint8_t  *lab;              // [slot]
+    float    *off;              // [slot][3]
+    double   *rot;              // [slot][3]
+};
+// Split search of one tree level.
+struct TrainLevelArgs {
+    const uint32_t *box;
+    size_t stride;              // bw * bh
+    uint32_t bw;
+    double area;                // rw * rh (0: every rectangle mean is 0)
+    const uint8_t  *lab;
+    const float    *off;
+    const double   *rot;
+    const uint32_t *idx;        // the level's samples, node after node
+    const TrainNode *nodes;     // [n_nodes] the nodes to split
+    uint32_t n_nodes, F, cblocks;
+    uint64_t seed;
+    uint32_t W, H, rw, rh;
+    double scale, wdepth;       // wdepth = 1 - exp(-depth / steepness), computed on the host
+    double   *score;            // [n_nodes][F]
+    TrainBest *best;            // [n_nodes]
+    uint8_t  *side;             // [idx]: 1 = Binar::One under the node's best split
+    unsigned long long *neg_det;
+};
+hipError_t dh_launch_train_windows(const TrainWinArgs &a, hipStream_t s);
+hipError_t dh_launch_train_extract(const TrainExtractArgs &a, hipStream_t s);
+hipError_t dh_launch_train_level(const TrainLevelArgs &a, hipStream_t s);
 
 struct Mat3Arg { float m[9]; };
 

@@ -234,6 +234,62 @@ int dh_biwi_parse_cal(const char *text, size_t len, float K[9]);
 /* read_gt (biwi.rs:63-77): 24-byte pose file -> head position (mm), its projection, rotation (deg). */
 int dh_biwi_parse_pose(const uint8_t *buf, size_t len, const float K[9], float pos3d[3], float pos2d[2], float rot[3]);
 
+/* ---- training: HoughLearning (src/hough/prediction.rs:103-234) ----
+ * HoughLearning::new(...).learn(sigma, data) grows the forests every HoughPrediction uses.  The parts the reference pins
+ * (sample extraction, the feature generator, binarize, impurity, early_stop, comp_leaf_data) are restated exactly; the
+ * random draws (thread_rng there) and stamm's tree growing are defined here, keyed by `seed` (DESIGN.md section 11:
+ * PARITY UNPINNED).  A trainer is not thread-safe. */
+typedef struct dh_train_params {
+    uint32_t stepwidth;             /* sliding-window step (iterate_subimage, types.rs:352-384)              */
+    uint32_t subimage_width;
+    uint32_t subimage_height;
+    uint32_t max_depth;             /* a node at depth >= max_depth is a leaf; the root has depth 0           */
+    uint32_t n_trees;
+    uint32_t subset_per_tree;       /* samples drawn (with replacement) from the pool for each tree           */
+    double   subrect_feature_scale; /* in (0, 1]: every split rectangle is trunc(W * s) x trunc(H * s)        */
+    uint32_t features_per_node;     /* candidates generated per node (>= 1)                                   */
+    uint32_t min_subset_size;       /* a node with fewer samples is a leaf                                    */
+    double   steepness;             /* > 0: regression weight 1 - exp(-depth / steepness)                     */
+    uint64_t seed;
+} dh_train_params; /* 56 bytes */
+
+/* Statistics of a trainer: the pool after the last dh_trainer_add_frames, the rest of the last dh_trainer_fit. */
+typedef struct dh_train_stats {
+    uint64_t frames;          /* frames added                                                                  */
+    uint64_t pool_size;       /* samples kept (at most 20 negatives + 20 positives per frame)                   */
+    uint64_t pool_positives;
+    uint64_t neg_det;         /* impurity evaluations whose det sum fell below -0.001 (the reference panics there,
+                               * houghforest.rs:283); scored as 0                                               */
+    uint32_t levels;          /* tree levels the last fit ran                                                   */
+    uint32_t reserved;
+} dh_train_stats; /* 40 bytes */
+
+typedef struct dh_trainer dh_trainer;
+
+/* Rejected with DH_EINVAL where HoughLearning::new returns None or the first node would panic: a factor outside (0, 1],
+ * features == 0, steepness <= 0 (HoughTreeFunctions::new :143-158, random_subrect_iterator types.rs:106-109); also
+ * n_trees == 0, stepwidth == 0, an empty patch, and (DH_ESIZE) a patch whose pixel sum can reach 2^32. */
+int dh_trainer_create(const dh_train_params *p, int device, dh_trainer **out);
+int dh_trainer_destroy(dh_trainer *t);
+/* Sample extraction of learn (prediction.rs:145-215) for n frames (row-major u16 depth, u8 mask, index y*w+x); K: [n][9]
+ * row-major intrinsics, pos3d [n][3] mm, rot_deg [n][3] degrees.  Frames are uploaded in chunks and windowed on the device;
+ * only the kept samples stay resident.  The pool does not depend on how frames are split across calls.  Frames smaller
+ * than the patch: DH_ESIZE. */
+int dh_trainer_add_frames(dh_trainer *t, const uint16_t *frames, const uint8_t *masks, int n, int w, int h, const float *K,
+                          const float *pos3d, const float *rot_deg);
+/* Grow n_trees trees on the device from the pool; *out is an ordinary forest (validated like dh_forest_create; child_one
+ * is the Binar::One side).  The pool is kept: fitting again gives the same forest. */
+int dh_trainer_fit(dh_trainer *t, dh_forest **out);
+/* nodes_per_level / leaves_per_level / level_ms: [cap_levels] each, may be NULL (split nodes and leaves made at each
+ * depth; device time of each level's kernels). */
+int dh_trainer_stats(const dh_trainer *t, dh_train_stats *out, uint32_t *nodes_per_level, uint32_t *leaves_per_level,
+                     float *level_ms, uint32_t cap_levels);
+
+/* Copy a forest back into caller arrays sized by dh_forest_info and *n_off / *n_rot.  NULL array pointers are skipped:
+ * call with all NULL to obtain the vote counts. */
+int dh_forest_export(const dh_forest *f, int32_t *roots, dh_node *nodes, double *leaf_prob, uint32_t *off_begin,
+                     uint32_t *rot_begin, float *offsets, double *rotations, uint32_t *n_off, uint32_t *n_rot);
+
 /* ---- profiling ---- */
 int dh_set_profiling(dh_predictor *p, int on); /* HIP events around each kernel, on the launch stream; and roctx ranges
                                                 * ("dh:batch ...", "dh:boxsum", "dh:traverse", "dh:emit", "dh:vote", "dh:cluster") around the
