@@ -566,6 +566,29 @@ static int predictor_reserve_(dh_predictor *p, int n, int w, int h) {
     return reserve(p, n, w, h);
 }
 
+// ------------------------------------------------------------------ camera tables (dh_cameras)
+// One record per camera on one device (DhCam), built once on the host: kinv by the same dh_mat3_inv_f32_ a single-K batch
+// uses, and the pinhole bit by the test dh_launch_vote applies to a single K.
+struct dh_cameras {
+    int device = 0;
+    int n = 0;
+    Buf<DhCam> dev;
+    std::vector<DhCam> host;     // the same records (kernel-argument stand-ins, the PIN decision of a launch)
+};
+
+// Which intrinsics a batch's frames see: one K for the whole batch (no table), or frame i -> camera c0 + i of a table.
+struct CamSel {
+    const dh_cameras *c = nullptr;
+    int c0 = 0;
+    CamSel at(int f) const { return CamSel{c, c0 + f}; }
+    const DhCam *dev() const { return c ? c->dev.get() + c0 : nullptr; }
+    // every camera of frames [0, n) is pinhole: the launch may take k_vote's PIN instance
+    bool all_pin(int n) const {
+        for (int i = 0; i < n; ++i) if (!c->host[(size_t)c0 + i].pin) return false;
+        return true;
+    }
+};
+
 // How enqueue_range runs besides the product batch.
 struct EnqueueOpts {
     bool profile = false;           // events and roctx ranges (dh_set_profiling)
@@ -577,10 +600,12 @@ struct EnqueueOpts {
 };
 
 // Enqueue the kernels (k_boxsum / k_pixflags, k_traverse, k_emit, k_vote, [k_region,] k_cluster) for frames [f0, f0 + n) of the batch on stream s.
+// With a camera table (`cams`, camera of frame 0 of `frames`) frame f0 + i reads camera cams.c0 + f0 + i; K and kinv are unused.
 static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n, int w, int h, const float K[9],
-                         const float kinv[9], const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
+                         const float kinv[9], const CamSel &cams, const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
                          dh_pose *out, hipStream_t s, const EnqueueOpts &o) {
     const Workspace &ws = p->ws;
+    const CamSel cs = cams.at(f0);
     const Geom &g = ws.geom;
     uint32_t *gen = p->gen.get() + o.chunk;      // this kernel sequence's tile-flag tag
     uint32_t *hit_count = ws.hit_count(f0), *pos_grid = ws.pos_grid(f0), *rot_grid = ws.rot_grid(f0), *leaf_hits = ws.leaf_hits(f0);
@@ -688,6 +713,7 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
             ea.step = ta.step; ea.lw = ta.sw / 2; ea.lh = ta.sh / 2; ea.nx = g.nx; ea.npatch = g.npatch;
             ea.px = g.px; ea.py = g.py; ea.tiles = tiles;
             memcpy(ea.kinv, kinv, 9 * sizeof(float));
+            ea.cams = cs.dev();
             ea.f = p->dev;
             ea.win_count = win_count; ea.win_patch = ta.win_patch; ea.win_leaf = ta.win_leaf; ea.leaf_ls = ws.leaf_ls; ea.win_cap = g.win_cap;
             ea.hits = ws.hits.get() + hoff; ea.hit_box = ws.hit_box.get() + hoff; ea.hit_rot = ws.hit_rot.get() + hoff;
@@ -707,6 +733,7 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         VoteArgs va{};
         va.n_frames = n; va.w = w; va.h = h; va.cell_fast = p->knobs.vote_exact ? 0 : 1;
         memcpy(va.k, K, sizeof va.k);
+        va.cams = cs.dev(); va.cams_pin = cs.c && cs.all_pin(n) ? 1 : 0;
         va.f = p->dev; va.hits = ws.hits.get() + hoff; va.hit_box = ws.hit_box.get() + hoff; va.hit_rot = ws.hit_rot.get() + hoff;
         va.hit_count = hit_count; va.hits_cap = ws.hits_cap;
         va.pos_grid = pos_grid; va.rot_grid = rot_grid;
@@ -721,6 +748,7 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         ClusterArgs ca{};
         ca.frames = fr; ca.n_frames = n; ca.w = w; ca.h = h;
         memcpy(ca.kinv, kinv, 9 * sizeof(float));
+        ca.cams = cs.dev();
         ca.f = p->dev; ca.hits = ws.hits.get() + hoff; ca.hit_box = ws.hit_box.get() + hoff; ca.hit_rot = ws.hit_rot.get() + hoff;
         ca.hit_count = hit_count; ca.hits_cap = ws.hits_cap;
         ca.leaf_hits = leaf_hits;
@@ -769,20 +797,20 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
 // stream, reusing the workspace.
 static int max_resident_frames(const dh_predictor *p) { return p->knobs.max_resident; }
 
-static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
-                                       const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
-                                       dh_pose *out, void *stream_) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch_device: NULL argument");
-    if (n == 0) return DH_OK;
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
+// The device batch behind dh_predict_batch_device and the camera / tracker calls (arguments checked, device selected): one K
+// (cams.c == NULL) or frame i -> camera cams.c0 + i.  Slices and forked sub-batches offset the camera as they offset guesses.
+static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const CamSel &cams,
+                        const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out, hipStream_t s) {
     const int slice = p->debug ? n : std::min(n, max_resident_frames(p));   // the taps index the whole batch
     int rc = reserve(p, slice, w, h);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream_;
     float kinv[9];
-    dh_mat3_inv_f32_(K, kinv);   // cached in a RefCell by the reference (types.rs:436-441)
+    if (cams.c) {                // (kernel-argument stand-ins: the CAM instances read the records)
+        K = cams.c->host[cams.c0].k;
+        memcpy(kinv, cams.c->host[cams.c0].kinv, sizeof kinv);
+    } else {
+        dh_mat3_inv_f32_(K, kinv);   // cached in a RefCell by the reference (types.rs:436-441)
+    }
     for (int f0 = 0; f0 < n; f0 += slice) {
         const int m = std::min(slice, n - f0);
         const uint16_t *fr = frames + (size_t)f0 * w * h;
@@ -809,7 +837,7 @@ static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n,
         if (chunks <= 1) {
             EnqueueOpts o;
             o.profile = p->profiling; o.zero_fold = fold;
-            TRY(enqueue_range(p, fr, 0, m, w, h, K, kinv, mg, rg, gm, out + f0, s, o));
+            TRY(enqueue_range(p, fr, 0, m, w, h, K, kinv, cams.at(f0), mg, rg, gm, out + f0, s, o));
         } else {
             HIP_TRY(hipEventRecord(p->ev_fork, s));
             for (int c = 0; c < chunks; ++c) {
@@ -818,7 +846,7 @@ static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n,
                 if (c > 0) HIP_TRY(hipStreamWaitEvent(cs, p->ev_fork, 0));
                 EnqueueOpts o;
                 o.chunk = c;
-                TRY(enqueue_range(p, fr, c0, c1 - c0, w, h, K, kinv, mg, rg, gm, out + f0, cs, o));
+                TRY(enqueue_range(p, fr, c0, c1 - c0, w, h, K, kinv, cams.at(f0), mg, rg, gm, out + f0, cs, o));
                 if (c > 0) {
                     HIP_TRY(hipEventRecord(p->ev_join[c - 1], cs));
                     HIP_TRY(hipStreamWaitEvent(s, p->ev_join[c - 1], 0));
@@ -830,6 +858,17 @@ static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n,
     p->last_frames = frames;
     p->ws.dbg_valid = p->debug;
     return DH_OK;
+}
+
+static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
+                                       const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
+                                       dh_pose *out, void *stream_) {
+    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch_device: NULL argument");
+    if (n == 0) return DH_OK;
+    if (n < 0) return fail(DH_EINVAL, "negative batch size");
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    return batch_device(p, frames, n, w, h, K, CamSel{}, midp_guess, rot_guess, guess_mask, out, (hipStream_t)stream_);
 }
 
 // n frames of w x h in ws.frames
@@ -888,9 +927,13 @@ static int slice_setup(dh_predictor *p, int f0, int m, int w, int h, const Guess
     }
     return DH_OK;
 }
-// Chunk [c0, c0 + cm) of a staged slice -- frames, guesses and poses in the workspace -- on stream s.
-static int predict_staged(dh_predictor *p, int c0, int cm, int w, int h, const float K[9], const Guesses &g, hipStream_t s) {
+// Chunk [c0, c0 + cm) of a staged slice -- frames, guesses and poses in the workspace -- on stream s; with a camera table
+// (`cams`: the slice's first frame) frame c0 + i reads camera cams.c0 + c0 + i.
+static int predict_staged(dh_predictor *p, int c0, int cm, int w, int h, const float K[9], const CamSel &cams, const Guesses &g, hipStream_t s) {
     const Workspace &ws = p->ws;
+    if (cams.c)
+        return batch_device(p, ws.frames.get() + (size_t)c0 * w * h, cm, w, h, nullptr, cams.at(c0), g.midp ? ws.midp.get() + (size_t)c0 * 3 : nullptr,
+                            g.rot ? ws.rot.get() + (size_t)c0 * 3 : nullptr, g.mask ? ws.mask.get() + c0 : nullptr, ws.poses.get() + c0, s);
     return dh_predict_batch_device(p, ws.frames.get() + (size_t)c0 * w * h, cm, w, h, K, g.midp ? ws.midp.get() + (size_t)c0 * 3 : nullptr,
                                    g.rot ? ws.rot.get() + (size_t)c0 * 3 : nullptr, g.mask ? ws.mask.get() + c0 : nullptr, ws.poses.get() + c0, s);
 }
@@ -919,13 +962,8 @@ static int host_slices(dh_predictor *p, int n, dh_pose *out, F enqueue) {
 // Host entry point.  The frames cross PCIe in chunks on copy_stream while the kernels of the previous chunk run on
 // own_stream (the path is PCIe-bound: 614 KB per frame in, 40 bytes out), so a batch takes about its upload time plus
 // the kernels of the last chunk.  The poses of a slice come back in one copy.
-static int predict_batch_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
-                                const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch: NULL argument");
-    if (n == 0) return DH_OK;
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
+static int batch_host(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const CamSel &cams,
+                      const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
     const Guesses g{midp_guess, rot_guess, guess_mask};
     hipStream_t s = p->own_stream, cs = p->copy_stream;
     const size_t fpx = (size_t)w * h;
@@ -938,7 +976,7 @@ static int predict_batch_(dh_predictor *p, const uint16_t *frames, int n, int w,
         if (nchunks == 1) {
             // latency path (single frames, small batches): one copy on the compute stream itself
             HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-            rc = predict_staged(p, 0, m, w, h, K, g, s);
+            rc = predict_staged(p, 0, m, w, h, K, cams.at(f0), g, s);
             if (rc) { (void)hipStreamSynchronize(s); return rc; }
         } else {
             // Chunk k + 1 is uploaded on copy_stream while the kernels of chunk k run on own_stream.  From page-locked host
@@ -953,13 +991,22 @@ static int predict_batch_(dh_predictor *p, const uint16_t *frames, int n, int w,
                 HIP_TRY(hipMemcpyAsync(p->ws.frames.get() + (size_t)c0 * fpx, frames + (size_t)(f0 + c0) * fpx, (size_t)cm * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, cs));
                 HIP_TRY(hipEventRecord(p->ev_stage[k], cs));
                 HIP_TRY(hipStreamWaitEvent(s, p->ev_stage[k], 0));
-                rc = predict_staged(p, c0, cm, w, h, K, g, s);
+                rc = predict_staged(p, c0, cm, w, h, K, cams.at(f0), g, s);
                 if (rc) { (void)hipStreamSynchronize(cs); (void)hipStreamSynchronize(s); return rc; }
             }
         }
         HIP_TRY(hipEventRecord(p->ev_slice, s));
         return DH_OK;
     });
+}
+static int predict_batch_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
+                                const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
+    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch: NULL argument");
+    if (n == 0) return DH_OK;
+    if (n < 0) return fail(DH_EINVAL, "negative batch size");
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    return batch_host(p, frames, n, w, h, K, CamSel{}, midp_guess, rot_guess, guess_mask, out);
 }
 
 // Page-locked host memory for frame buffers: uploads from it are asynchronous DMA at PCIe speed.
@@ -1068,7 +1115,7 @@ static int predict_batch_rle_(dh_predictor *p, const uint8_t *const *bufs, const
         for (int c0 = 0; c0 < m; c0 += chunk, ++ci) {
             const int cm = std::min(chunk, m - c0);
             rc = rle_upload_decode(p, plan.blob_off, c0, cm, ci, W, H, p->ws.frames.get() + (size_t)c0 * W * H, s);
-            if (rc == DH_OK) rc = predict_staged(p, c0, cm, (int)W, (int)H, K, g, s);
+            if (rc == DH_OK) rc = predict_staged(p, c0, cm, (int)W, (int)H, K, CamSel{}, g, s);
             if (rc) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamSynchronize(s); return rc; }
         }
         return DH_OK;
@@ -1121,6 +1168,196 @@ static int graph_launch_(dh_predictor *p, void *stream) {
     return DH_OK;
 }
 
+// ------------------------------------------------------------------ camera batches and live tracking
+static int cameras_create_(const float *K, int n, int device, dh_cameras **out) {
+    if (!K || !out) return fail(DH_EINVAL, "dh_cameras_create: NULL argument");
+    *out = nullptr;
+    if (n <= 0) return fail(DH_EINVAL, "dh_cameras_create: n = %d, expected at least one camera", n);
+    std::unique_ptr<dh_cameras> c(new dh_cameras);
+    c->device = device; c->n = n;
+    c->host.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        DhCam &r = c->host[(size_t)i];
+        memset(&r, 0, sizeof r);
+        memcpy(r.k, K + (size_t)i * 9, sizeof r.k);
+        dh_mat3_inv_f32_(r.k, r.kinv);      // IntrinsicMatrix::inv (types.rs:436-441), as every single-K batch
+        r.pin = r.k[1] == 0.0f && r.k[3] == 0.0f && r.k[6] == 0.0f && r.k[7] == 0.0f && r.k[8] == 1.0f ? 1u : 0u;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(c->dev.alloc((size_t)n));
+    HIP_TRY(hipMemcpy(c->dev.get(), c->host.data(), (size_t)n * sizeof(DhCam), hipMemcpyHostToDevice));
+    *out = c.release();
+    return DH_OK;
+}
+static int cameras_destroy_(dh_cameras *c) {
+    if (!c) return DH_OK;
+    DeviceGuard guard(c->device);      // (the buffer is freed on its device)
+    delete c;
+    return DH_OK;
+}
+// shared checks of the camera calls: n frames against the table, the table on the predictor's device
+static int cameras_check(const dh_predictor *p, const dh_cameras *c, int n, const char *fn) {
+    if (c->device != p->device) return fail(DH_EINVAL, "%s: camera table on device %d, predictor on device %d", fn, c->device, p->device);
+    if (n > c->n) return fail(DH_EINVAL, "%s: %d frames, the camera table has %d cameras", fn, n, c->n);
+    return DH_OK;
+}
+static int predict_batch_cameras_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                         const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out, void *stream) {
+    if (!p || !frames || !c || !out) return fail(DH_EINVAL, "dh_predict_batch_cameras_device: NULL argument");
+    if (n < 0) return fail(DH_EINVAL, "negative batch size");
+    TRY(cameras_check(p, c, n, "dh_predict_batch_cameras_device"));
+    if (n == 0) return DH_OK;
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    return batch_device(p, frames, n, w, h, nullptr, CamSel{c, 0}, midp_guess, rot_guess, guess_mask, out, (hipStream_t)stream);
+}
+static int predict_batch_cameras_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                  const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
+    if (!p || !frames || !c || !out) return fail(DH_EINVAL, "dh_predict_batch_cameras: NULL argument");
+    if (n < 0) return fail(DH_EINVAL, "negative batch size");
+    TRY(cameras_check(p, c, n, "dh_predict_batch_cameras"));
+    if (n == 0) return DH_OK;
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    return batch_host(p, frames, n, w, h, nullptr, CamSel{c, 0}, midp_guess, rot_guess, guess_mask, out);
+}
+
+// A tracker's state is exactly the guess arrays of a camera batch (midp_guess, rot_guess, guess_mask): a step predicts with them
+// and k_track then rewrites them from the step's poses (dh_track.h: live_prediction.rs:79-101).
+struct dh_tracker {
+    const dh_cameras *cams = nullptr;
+    int n = 0;
+    uint32_t flags = 0;
+    Buf<float> midp;         // [n][3]
+    Buf<double> rot;         // [n][3]
+    Buf<uint8_t> mask;       // [n] bit0 midpoint guess, bit1 rotation guess
+    Buf<uint8_t> has_rot;    // [n]
+    Buf<uint8_t> present;    // [n] host steps: the caller's present bytes on the device
+};
+static int tracker_create_(const dh_cameras *c, uint32_t flags, dh_tracker **out) {
+    if (!c || !out) return fail(DH_EINVAL, "dh_tracker_create: NULL argument");
+    *out = nullptr;
+    if (flags & ~(DH_TRACK_PREV_GUESS | DH_TRACK_SLUGGISH)) return fail(DH_EINVAL, "dh_tracker_create: unknown flags 0x%x", flags);
+    DeviceGuard guard(c->device);
+    if (!guard.ok) return DH_EHIP;
+    std::unique_ptr<dh_tracker> t(new dh_tracker);
+    t->cams = c; t->n = c->n; t->flags = flags;
+    const size_t n = (size_t)c->n;
+    TRY(t->midp.alloc(n * 3));
+    TRY(t->rot.alloc(n * 3));
+    TRY(t->mask.alloc(n));
+    TRY(t->has_rot.alloc(n));
+    TRY(t->present.alloc(n));
+    HIP_TRY(hipMemset(t->midp.get(), 0, n * 3 * sizeof(float)));
+    HIP_TRY(hipMemset(t->rot.get(), 0, n * 3 * sizeof(double)));
+    HIP_TRY(hipMemset(t->mask.get(), 0, n));
+    HIP_TRY(hipMemset(t->has_rot.get(), 0, n));
+    *out = t.release();
+    return DH_OK;
+}
+static int tracker_destroy_(dh_tracker *t) {
+    if (!t) return DH_OK;
+    DeviceGuard guard(t->cams->device);
+    delete t;
+    return DH_OK;
+}
+static int tracker_reset_(dh_tracker *t, int camera, void *stream) {
+    if (!t) return fail(DH_EINVAL, "dh_tracker_reset: NULL tracker");
+    if (camera < -1 || camera >= t->n) return fail(DH_EINVAL, "dh_tracker_reset: camera %d of %d", camera, t->n);
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t c0 = camera < 0 ? 0 : (size_t)camera, m = camera < 0 ? (size_t)t->n : 1;
+    // live_prediction.rs:63-64: latest_midp = [0, 0, 0], latest_rot = None
+    HIP_TRY(hipMemsetAsync(t->midp.get() + c0 * 3, 0, m * 3 * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(t->rot.get() + c0 * 3, 0, m * 3 * sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(t->mask.get() + c0, 0, m, s));
+    HIP_TRY(hipMemsetAsync(t->has_rot.get() + c0, 0, m, s));
+    return DH_OK;
+}
+// Cameras [c0, c0 + m) of a step (device frames / poses / present of those cameras): their batch with the tracker's guesses, then
+// k_track over their poses, both on stream s.
+static int track_enqueue(dh_predictor *p, dh_tracker *t, int c0, int m, const uint16_t *frames, int w, int h, const uint8_t *present,
+                         dh_pose *out, hipStream_t s) {
+    TRY(batch_device(p, frames, m, w, h, nullptr, CamSel{t->cams, c0}, t->midp.get() + (size_t)c0 * 3, t->rot.get() + (size_t)c0 * 3,
+                     t->mask.get() + c0, out, s));
+    TrackArgs a{};
+    a.poses = out; a.present = present; a.n = m; a.flags = t->flags;
+    a.midp = t->midp.get() + (size_t)c0 * 3; a.rot = t->rot.get() + (size_t)c0 * 3; a.mask = t->mask.get() + c0; a.has_rot = t->has_rot.get() + c0;
+    { Range r(p->profiling, "dh:track"); HIP_TRY(dh_launch_track(a, s)); }
+    return DH_OK;
+}
+static int tracker_args(const dh_predictor *p, const dh_tracker *t, const uint16_t *frames, const dh_pose *out, const char *fn) {
+    if (!p || !t || !frames || !out) return fail(DH_EINVAL, "%s: NULL argument", fn);
+    return cameras_check(p, t->cams, t->n, fn);
+}
+static int tracker_step_device_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out,
+                                void *stream) {
+    TRY(tracker_args(p, t, frames, out, "dh_tracker_step_device"));
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    return track_enqueue(p, t, 0, t->n, frames, w, h, present, out, (hipStream_t)stream);
+}
+static int tracker_step_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out) {
+    TRY(tracker_args(p, t, frames, out, "dh_tracker_step"));
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    hipStream_t s = p->own_stream;
+    const size_t fpx = (size_t)w * h;
+    // resident slices of the host batch paths: cameras [f0, f0 + m) are staged, predicted and updated, their poses copied back
+    return host_slices(p, t->n, out, [&](int f0, int m, SmallStage *st) -> int {
+        TRY(slice_setup(p, f0, m, w, h, Guesses{nullptr, nullptr, nullptr}, st));
+        HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        if (present) {
+            memcpy(st->mask, present + f0, (size_t)m);       // (the slice's guess-mask staging: a tracker's guesses are on the device)
+            HIP_TRY(hipMemcpyAsync(t->present.get() + f0, st->mask, (size_t)m, hipMemcpyHostToDevice, s));
+        }
+        int rc = track_enqueue(p, t, f0, m, p->ws.frames.get(), w, h, present ? t->present.get() + f0 : nullptr, p->ws.poses.get(), s);
+        if (rc) { (void)hipStreamSynchronize(s); return rc; }
+        HIP_TRY(hipEventRecord(p->ev_slice, s));
+        return DH_OK;
+    });
+}
+static int tracker_state_(dh_tracker *t, float *midp, double *rot, uint8_t *flags) {
+    if (!t) return fail(DH_EINVAL, "dh_tracker_state: NULL tracker");
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    HIP_TRY(hipDeviceSynchronize());          // the steps may run on any stream of the device
+    const size_t n = (size_t)t->n;
+    if (midp) HIP_TRY(hipMemcpy(midp, t->midp.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (rot) HIP_TRY(hipMemcpy(rot, t->rot.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (flags) {
+        std::vector<uint8_t> hr(n);
+        HIP_TRY(hipMemcpy(flags, t->mask.get(), n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hr.data(), t->has_rot.get(), n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) flags[i] = (uint8_t)(flags[i] | (hr[i] ? 4u : 0u));
+    }
+    return DH_OK;
+}
+// One device step captured into the predictor's graph slot (graph_capture_'s rules: no taps or profiling, every allocation before
+// the capture, refused by dh_graph_launch once the workspace is reallocated).
+static int tracker_capture_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out) {
+    TRY(tracker_args(p, t, frames, out, "dh_tracker_capture"));
+    if (p->debug || p->profiling) return fail(DH_ESTATE, "taps / profiling cannot be captured");
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(reserve(p, std::min(t->n, max_resident_frames(p)), w, h));
+    dh_graph_destroy(p);
+    HIP_TRY(hipStreamSynchronize(p->own_stream));
+    HIP_TRY(hipStreamBeginCapture(p->own_stream, hipStreamCaptureModeThreadLocal));
+    p->capturing = true;
+    int rc = track_enqueue(p, t, 0, t->n, frames, w, h, present, out, p->own_stream);
+    p->capturing = false;
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(p->own_stream, &g);
+    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+    if (e != hipSuccess) return fail(DH_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+    p->graph = g;
+    HIP_TRY(hipGraphInstantiate(&p->graph_exec, p->graph, nullptr, nullptr, 0));
+    return DH_OK;
+}
+
 // ------------------------------------------------------------------ predict_mask / 2-D Hough votes
 static int aux_reserve(dh_predictor *p, int n, int w, int h, size_t out_bytes) {
     TRY(reserve(p, n, w, h));
@@ -1168,7 +1405,7 @@ static int aux_run(dh_predictor *p, unsigned req, const uint16_t *frames, int n,
     HIP_TRY(hipMemsetAsync(ws.aux_flags.get(), 0, (size_t)n * std::max(g.npatch, 1), s));
     EnqueueOpts o;
     o.leaf_out = ws.aux_leaf.get(); o.flags_out = ws.aux_flags.get(); o.traverse_only = true;
-    TRY(enqueue_range(p, frames, 0, n, w, h, K ? K : kid, kinv, nullptr, nullptr, nullptr, ws.poses.get(), s, o));
+    TRY(enqueue_range(p, frames, 0, n, w, h, K ? K : kid, kinv, CamSel{}, nullptr, nullptr, nullptr, ws.poses.get(), s, o));
     AuxArgs a{};
     a.frames = frames; a.n_frames = n; a.w = w; a.h = h;
     a.step = (int)p->params.stepwidth; a.sw = (int)p->params.subimage_width; a.sh = (int)p->params.subimage_height;
@@ -1689,4 +1926,15 @@ DH_API(trainer_add_frames, (dh_trainer *t, const uint16_t *frames, const uint8_t
 DH_API(trainer_fit, (dh_trainer *t, dh_forest **out), (t, out))
 DH_API(trainer_stats, (const dh_trainer *t, dh_train_stats *out, uint32_t *nodes_per_level, uint32_t *leaves_per_level, float *level_ms, uint32_t cap_levels), (t, out, nodes_per_level, leaves_per_level, level_ms, cap_levels))
 DH_API(forest_export, (const dh_forest *f, int32_t *roots, dh_node *nodes, double *leaf_prob, uint32_t *off_begin, uint32_t *rot_begin, float *offsets, double *rotations, uint32_t *n_off, uint32_t *n_rot), (f, roots, nodes, leaf_prob, off_begin, rot_begin, offsets, rotations, n_off, n_rot))
+DH_API(cameras_create, (const float *K, int n, int device, dh_cameras **out), (K, n, device, out))
+DH_API(cameras_destroy, (dh_cameras *c), (c))
+DH_API(predict_batch_cameras, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out), (p, frames, n, w, h, c, midp_guess, rot_guess, guess_mask, out))
+DH_API(predict_batch_cameras_device, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out, void *stream), (p, frames, n, w, h, c, midp_guess, rot_guess, guess_mask, out, stream))
+DH_API(tracker_create, (const dh_cameras *c, uint32_t flags, dh_tracker **out), (c, flags, out))
+DH_API(tracker_destroy, (dh_tracker *t), (t))
+DH_API(tracker_reset, (dh_tracker *t, int camera, void *stream), (t, camera, stream))
+DH_API(tracker_step, (dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out), (p, t, frames, w, h, present, out))
+DH_API(tracker_step_device, (dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out, void *stream), (p, t, frames, w, h, present, out, stream))
+DH_API(tracker_state, (dh_tracker *t, float *midp, double *rot, uint8_t *flags), (t, midp, rot, flags))
+DH_API(tracker_capture, (dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out), (p, t, frames, w, h, present, out))
 #undef DH_API

@@ -60,6 +60,12 @@ __device__ __forceinline__ void to3d(const float *kinv, float px, float py, floa
     out[2] = __fmul_rn(r[2], c);
 }
 
+// A camera record's matrices (DhCam, read by the CAM kernel instances): frame-uniform, so scalar loads.
+__device__ __forceinline__ void cam_kinv(float kinv[9], const DhCam *c) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) kinv[i] = c->kinv[i];
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 __device__ __forceinline__ uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 

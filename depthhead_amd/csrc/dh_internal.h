@@ -19,6 +19,17 @@
 #define LF_OFF 4u    // trace(cov(offsets))  <= 5200.0  (prediction.rs:643)
 #define LF_FIN 8u    // every offset vote of the leaf is finite and below 1e30 in magnitude (k_vote's pinhole fast path relies on it)
 
+// One camera of a dh_cameras table (device-resident, immutable).  A batch given a table reads camera f0 + f for its frame f
+// in k_emit, k_vote, k_region and k_cluster (their CAM instances) in place of the kernel-argument matrices; the record index
+// is the workgroup's frame (blockIdx.y), so the loads are scalar, once per wave.
+struct __attribute__((aligned(16))) DhCam {
+    float k[9];                  // the intrinsic matrix, row-major
+    float kinv[9];               // dh_mat3_inv_f32_(k): the matrix every single-K batch passes
+    uint32_t pin;                // 1: k[1] = k[3] = k[6] = k[7] = 0 and k[8] = 1 (the test dh_launch_vote applies to a single K)
+    uint32_t pad;
+};
+static_assert(sizeof(DhCam) == 80, "DhCam is five 16-byte rows");
+
 // Everything k_traverse needs to turn (patch, leaf) into its three hit records: 4 x 16-byte loads.
 struct __attribute__((aligned(16))) LeafTpl {
     float    omin[3], omax[3];   // offset bounding box (off_min / off_max)
@@ -150,6 +161,7 @@ struct EmitArgs {
     uint32_t *gen;          // nullable: the tile-flag tag of this kernel sequence, moved on here (every reader of the batch's flags has run)
     uint8_t  *dbg_flags;    // nullable [n][npatch]: bit 1 set for windows that pass the gate
     int stop;               // profiling knob (env DH_EMIT_STOP): 1 / 2 = return after the window lookup / after the gate
+    const DhCam *cams;      // nullable [n_frames]: per-frame cameras (the CAM instance reads cams[frame].kinv, not kinv)
 };
 
 // k_boxsum: per frame the image of all rw x rh rectangle sums, out[y][x] = sum of the rectangle whose
@@ -207,6 +219,8 @@ struct VoteArgs {
     int cell_fast;          // w and h are multiples of 20: a vote's guess-grid cell may be taken from an approximate quotient (vote_positions)
     float sx, sy;           // 20 / w, 20 / h
     float kxs, cxs, kys, cys; // pinhole intrinsics: fx * sx, cx * sx, fy * sy, cy * sy (k_vote's approximate cell quotient)
+    const DhCam *cams;      // nullable [n_frames]: per-frame cameras (the CAM instance takes k and kxs .. cys from cams[frame])
+    int cams_pin;           // with cams: every camera of the launch is pinhole (selects the PIN instance)
 };
 
 struct ClusterArgs {
@@ -237,6 +251,19 @@ struct ClusterArgs {
     int32_t  *dbg_trace;       // nullable [2][n][iterations+1][3]
     uint32_t *dbg_steps;       // nullable [2][n]
     int stop;               // profiling knob (env DH_CL_STOP): low 4 bits 1 / 2 / 3 = return after the initial guess / the first region build / the first weighted sum; + 16 / 32: the position / rotation workgroups return at once
+    const DhCam *cams;      // nullable [n_frames]: per-frame cameras (k_cluster's and k_region's CAM instances read cams[frame].kinv)
+};
+
+// k_track: one live-tracking step's state update (dh_track.h) for every camera of a tracker, after the step's k_cluster.
+struct TrackArgs {
+    const dh_pose *poses;   // [n] the step's poses
+    const uint8_t *present; // nullable [n]: only cameras whose byte is non-zero are updated
+    float   *midp;          // [n][3] latest midpoint = the next step's midpoint guesses
+    double  *rot;           // [n][3] latest rotation = the next step's rotation guesses
+    uint8_t *mask;          // [n] the next step's guess mask (bit0 midpoint, bit1 rotation)
+    uint8_t *has_rot;       // [n] a rotation has been stored since the last reset
+    int n;
+    uint32_t flags;         // DH_TRACK_*
 };
 
 struct VotesDumpArgs {
@@ -351,6 +378,7 @@ hipError_t dh_launch_vote(const VoteArgs &a, hipStream_t s);
 hipError_t dh_launch_cluster(const ClusterArgs &a, hipStream_t s);
 hipError_t dh_launch_region(const ClusterArgs &a, hipStream_t s);
 hipError_t dh_launch_votes_dump(const VotesDumpArgs &a, hipStream_t s);
+hipError_t dh_launch_track(const TrackArgs &a, hipStream_t s);
 hipError_t dh_launch_boxsum(const BoxArgs &a, hipStream_t s);
 hipError_t dh_launch_pixflags(const PixFlagArgs &a, hipStream_t s);
 hipError_t dh_launch_top_build(const DevForest &f, const void *nodes_a, uint32_t n_amb, int top_levels, uint32_t *out, hipStream_t s);

@@ -336,7 +336,8 @@ __device__ __forceinline__ void cl_gather(const ClusterArgs &a, const int which,
 
 // SUP: the batch has blocks of both accumulators in global memory (k_region; a.pre_region != NULL); a separate instance so that
 // the code of batches without them keeps its registers.
-template <bool SUP>
+// CAM: the batch has a camera table (ClusterArgs::cams): the initial position guess un-projects with the frame's record.
+template <bool SUP, bool CAM>
 __global__ void __launch_bounds__(CL_THREADS, 8) k_cluster(ClusterArgs a) {
     __shared__ uint32_t region[RG3];
     __shared__ __attribute__((aligned(16))) float prod[CL_PROD_CAP * 4];
@@ -350,6 +351,7 @@ __global__ void __launch_bounds__(CL_THREADS, 8) k_cluster(ClusterArgs a) {
     __shared__ float s_kr2[DH_KERN_R2];     // Gaussian weights by squared distance: no global load inside a weighted sum
 
     const int which = blockIdx.x, frame = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+    if (CAM) cam_kinv(a.kinv, a.cams + frame);
 
     const ClShared sh{prod, red64, red32, s_pos, &s_total};
     if (tid < DH_KERN_R2) s_kr2[tid] = a.kern_r2[tid];        // (visible after the barriers of the initial guess)
@@ -535,8 +537,13 @@ __global__ void __launch_bounds__(CL_THREADS, 8) k_cluster(ClusterArgs a) {
 
 hipError_t dh_launch_cluster(const ClusterArgs &a, hipStream_t s) {
     if (a.n_frames == 0) return hipSuccess;
-    if (a.pre_region) hipLaunchKernelGGL(k_cluster<true>, dim3(2, a.n_frames), dim3(CL_THREADS), 0, s, a);
-    else hipLaunchKernelGGL(k_cluster<false>, dim3(2, a.n_frames), dim3(CL_THREADS), 0, s, a);
+    if (a.cams) {
+        if (a.pre_region) hipLaunchKernelGGL((k_cluster<true, true>), dim3(2, a.n_frames), dim3(CL_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((k_cluster<false, true>), dim3(2, a.n_frames), dim3(CL_THREADS), 0, s, a);
+    } else {
+        if (a.pre_region) hipLaunchKernelGGL((k_cluster<true, false>), dim3(2, a.n_frames), dim3(CL_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((k_cluster<false, false>), dim3(2, a.n_frames), dim3(CL_THREADS), 0, s, a);
+    }
     return hipGetLastError();
 }
 
@@ -551,7 +558,7 @@ hipError_t dh_launch_cluster(const ClusterArgs &a, hipStream_t s) {
 // the regions it needs out of the blocks: on the config-3 workload the position window drifts a cell per iteration on some
 // frames (up to 18 cells in 20 iterations) and the rotation window up to 4 cells, and every 26^3 region a window outgrew used to
 // cost a scan of all the frame's records by one workgroup (0.55 ms of that step for one rotation rebuild).
-template <int WHICH>
+template <int WHICH, bool CAM>      // CAM: as k_cluster's
 __global__ void __launch_bounds__(CL_THREADS, 8) k_region(ClusterArgs a) {
     extern __shared__ uint32_t block[];                             // WHICH == 1: [RRG3]
     __shared__ __attribute__((aligned(16))) float prod[CL_PROD_CAP * 4];
@@ -560,6 +567,7 @@ __global__ void __launch_bounds__(CL_THREADS, 8) k_region(ClusterArgs a) {
     __shared__ int32_t s_pos[3];
     __shared__ uint32_t s_total;
     const int slice = blockIdx.x, frame = blockIdx.y, which = WHICH, tid = threadIdx.x;
+    if (CAM && WHICH == 0) cam_kinv(a.kinv, a.cams + frame);        // (only the position guess un-projects)
     const ClShared sh{prod, red64, red32, s_pos, &s_total};
     uint32_t n_hits = a.hit_count[frame];
     if (n_hits > a.hits_cap) n_hits = a.hits_cap;
@@ -598,7 +606,9 @@ __global__ void __launch_bounds__(CL_THREADS, 8) k_region(ClusterArgs a) {
 
 // (the rotation instance takes 128 KB of dynamic LDS: a per-device attribute, set with k_traverse's by dh_kernels_init)
 hipError_t dh_region_init() {
-    return hipFuncSetAttribute((const void *)k_region<1>, hipFuncAttributeMaxDynamicSharedMemorySize, RRG3 * (int)sizeof(uint32_t));
+    hipError_t e = hipFuncSetAttribute((const void *)k_region<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RRG3 * (int)sizeof(uint32_t));
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void *)k_region<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RRG3 * (int)sizeof(uint32_t));
 }
 
 hipError_t dh_launch_region(const ClusterArgs &a, hipStream_t s) {
@@ -606,8 +616,13 @@ hipError_t dh_launch_region(const ClusterArgs &a, hipStream_t s) {
     if (a.n_frames > 65535) return hipErrorInvalidConfiguration;
     // (the rotation instance holds a CU's LDS alone; half as many, twice as long shares -- one round on the chip at 32 frames -- take
     // 0.23 instead of 0.12 ms: the time goes with the length of a share; four of a record's cells in flight change nothing)
-    hipLaunchKernelGGL(k_region<1>, dim3(a.pre_slices, a.n_frames), dim3(CL_THREADS), RRG3 * sizeof(uint32_t), s, a);
-    hipLaunchKernelGGL(k_region<0>, dim3(a.pre_slices, a.n_frames), dim3(CL_THREADS), 0, s, a);
+    if (a.cams) {
+        hipLaunchKernelGGL((k_region<1, true>), dim3(a.pre_slices, a.n_frames), dim3(CL_THREADS), RRG3 * sizeof(uint32_t), s, a);
+        hipLaunchKernelGGL((k_region<0, true>), dim3(a.pre_slices, a.n_frames), dim3(CL_THREADS), 0, s, a);
+    } else {
+        hipLaunchKernelGGL((k_region<1, false>), dim3(a.pre_slices, a.n_frames), dim3(CL_THREADS), RRG3 * sizeof(uint32_t), s, a);
+        hipLaunchKernelGGL((k_region<0, false>), dim3(a.pre_slices, a.n_frames), dim3(CL_THREADS), 0, s, a);
+    }
     return hipGetLastError();
 }
 

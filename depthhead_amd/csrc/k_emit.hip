@@ -13,9 +13,12 @@
 #define EMIT_THREADS 256
 // EB = trees handled per batch of gathers: the smallest instance that holds all T trees keeps the registers (and with them the
 // occupancy of this latency-bound kernel) in proportion to the forest: 62 VGPRs at EB = 8, 80 at 10, 122 at 16.
-template <int EB, int LS>      // LS: log2 of the window list's leaf entry size (dh_device.h: load_leaf)
+// CAM: the batch has a camera table (EmitArgs::cams): the frame's inverse intrinsic comes from its record (an instance of its
+// own: the instances without a table keep their code and registers).
+template <int EB, int LS, bool CAM>      // LS: log2 of the window list's leaf entry size (dh_device.h: load_leaf)
 __global__ void __launch_bounds__(EMIT_THREADS) k_emit(EmitArgs a) {
     const int frame = blockIdx.y, lane = threadIdx.x & (WAVE - 1);
+    if (CAM) cam_kinv(a.kinv, a.cams + frame);
     // every reader of this batch's tile flags (k_tile_list, k_traverse) has run: the next batch of this kernel sequence takes
     // the next tag, 1 .. 255 (BoxArgs::gen)
     if (a.gen && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.gen = *a.gen % 255u + 1u;
@@ -201,8 +204,13 @@ hipError_t dh_launch_emit(const EmitArgs &a, hipStream_t s) {
     const uint32_t T = a.f.n_trees;
 #define EMIT_LAUNCH(EB_)                                                                       \
     do {                                                                                       \
-        if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1>), grid, block, 0, s, a);        \
-        else hipLaunchKernelGGL((k_emit<EB_, 2>), grid, block, 0, s, a);                       \
+        if (a.cams) {                                                                          \
+            if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1, true>), grid, block, 0, s, a);  \
+            else hipLaunchKernelGGL((k_emit<EB_, 2, true>), grid, block, 0, s, a);                 \
+        } else {                                                                               \
+            if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1, false>), grid, block, 0, s, a); \
+            else hipLaunchKernelGGL((k_emit<EB_, 2, false>), grid, block, 0, s, a);                \
+        }                                                                                      \
     } while (0)
     if (T <= 4) EMIT_LAUNCH(4);
     else if (T <= 8) EMIT_LAUNCH(8);

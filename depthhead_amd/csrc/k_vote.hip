@@ -98,12 +98,24 @@ __device__ __forceinline__ void vote_positions(const VoteArgs &a, uint32_t *pos,
 // leaf offsets are not finite and small (LF_FIN) take the general expression (there 0 * inf = NaN must propagate).
 // LH: the batch has a leaf histogram (VoteArgs::leaf_hits): rotation cells come from the leaves that voted, not from the hit
 // records (an instance of its own: the other path's registers would cost the 80-VGPR instance a wave per SIMD).
-template <bool TAB, bool PIN, bool LH>
+__device__ __forceinline__ float sgpr_f32(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+
+// CAM: the batch has a camera table (VoteArgs::cams): k and the pinhole constants come from the frame's record.  The host rounds
+// kxs .. cys once in f32 (dh_launch_vote); __fmul_rn of the same operands here is that same rounding, so both give one bit pattern.
+template <bool TAB, bool PIN, bool LH, bool CAM>
 __global__ void __launch_bounds__(VOTE_THREADS) k_vote(VoteArgs a) {
     __shared__ uint32_t pos[DH_POSGRID];
     __shared__ uint32_t rot[DH_GRID3];
     __shared__ uint8_t gxt[VOTE_TAB], gyt[VOTE_TAB];   // pixel -> guess-grid column / row: x * 20 / w (:671-674) without a division per vote
     const int frame = blockIdx.y, tid = threadIdx.x;
+    if (CAM) {
+        const DhCam *c = a.cams + frame;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) a.k[i] = c->k[i];
+        // (gfx950 has no scalar f32 multiply: the products come back to scalar registers, where the kernel-argument constants live)
+        a.kxs = sgpr_f32(__fmul_rn(a.k[0], a.sx)); a.cxs = sgpr_f32(__fmul_rn(a.k[2], a.sx));
+        a.kys = sgpr_f32(__fmul_rn(a.k[4], a.sy)); a.cys = sgpr_f32(__fmul_rn(a.k[5], a.sy));
+    }
     uint32_t n = a.hit_count[frame];
     if (n > a.hits_cap) n = a.hits_cap;
     const uint32_t slices = gridDim.x;
@@ -174,7 +186,8 @@ __global__ void __launch_bounds__(VOTE_THREADS) k_vote(VoteArgs a) {
 
 hipError_t dh_launch_vote(const VoteArgs &a, hipStream_t s) {
     if (a.n_frames == 0) return hipSuccess;
-    const bool pin = a.k[1] == 0.0f && a.k[3] == 0.0f && a.k[6] == 0.0f && a.k[7] == 0.0f && a.k[8] == 1.0f;
+    // (a camera table: the host has checked every camera of the launch -- one that is not pinhole takes the general instance)
+    const bool pin = a.cams ? a.cams_pin != 0 : a.k[1] == 0.0f && a.k[3] == 0.0f && a.k[6] == 0.0f && a.k[7] == 0.0f && a.k[8] == 1.0f;
     // slices per frame: 8 for batches that fill the chip by their frames, more for small batches (a slice flushes at most
     // 8 400 cells with atomics, so 128 slices of one frame still cost less than a mostly idle chip: one 320 x 240 frame at stride 1
     // 18.6 / 12.7 / 10.2 / 8.0 / 8.0 us with at most 16 / 32 / 64 / 128 / 256 slices)
@@ -186,8 +199,13 @@ hipError_t dh_launch_vote(const VoteArgs &a, hipStream_t s) {
     b.kxs = a.k[0] * b.sx; b.cxs = a.k[2] * b.sx; b.kys = a.k[4] * b.sy; b.cys = a.k[5] * b.sy;   // (one f32 rounding each: see vote_positions)
 #define VOTE_LAUNCH(TAB_, PIN_)                                                                       \
     do {                                                                                             \
-        if (b.leaf_hits) hipLaunchKernelGGL((k_vote<TAB_, PIN_, true>), grid, block, 0, s, b);       \
-        else hipLaunchKernelGGL((k_vote<TAB_, PIN_, false>), grid, block, 0, s, b);                  \
+        if (b.cams) {                                                                                \
+            if (b.leaf_hits) hipLaunchKernelGGL((k_vote<TAB_, PIN_, true, true>), grid, block, 0, s, b);   \
+            else hipLaunchKernelGGL((k_vote<TAB_, PIN_, false, true>), grid, block, 0, s, b);              \
+        } else {                                                                                     \
+            if (b.leaf_hits) hipLaunchKernelGGL((k_vote<TAB_, PIN_, true, false>), grid, block, 0, s, b);  \
+            else hipLaunchKernelGGL((k_vote<TAB_, PIN_, false, false>), grid, block, 0, s, b);             \
+        }                                                                                            \
     } while (0)
     if (a.w <= VOTE_TAB && a.h <= VOTE_TAB) {
         if (pin) VOTE_LAUNCH(true, true);

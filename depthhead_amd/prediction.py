@@ -170,6 +170,27 @@ class HoughPrediction:
                                          vp(rg), vp(gm), vp(out)))
         return out
 
+    def predict_batch_cameras(self, frames, cameras, midp_guess=None, rot_guess=None, guess_mask=None) -> np.ndarray:
+        """Host frames [n, H, W] uint16, frame i seen by camera i of `cameras` (`tracking.Cameras`, n <= its count) ->
+        POSE_DTYPE[n].  Guesses as `predict_batch`."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.ndim != 3:
+            raise ValueError("frames must be [n, H, W]")
+        n, h, w = frames.shape
+        mg, rg, gm = _guesses(n, midp_guess, rot_guess, guess_mask)
+        out = np.zeros(n, dtype=POSE_DTYPE)
+        check(self._lib.dh_predict_batch_cameras(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), cameras._h, vp(mg),
+                                                 vp(rg), vp(gm), vp(out)))
+        return out
+
+    def predict_batch_cameras_device(self, frames_ptr: int, n: int, w: int, h: int, cameras, out_ptr: int,
+                                     midp_guess_ptr: int | None = None, rot_guess_ptr: int | None = None,
+                                     guess_mask_ptr: int | None = None, stream: int = 0) -> None:
+        """Device-resident twin of `predict_batch_cameras` (as `predict_batch_device`).  Asynchronous."""
+        check(self._lib.dh_predict_batch_cameras_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), cameras._h,
+                                                        vp(midp_guess_ptr), vp(rot_guess_ptr), vp(guess_mask_ptr), vp(out_ptr),
+                                                        _stream(stream)))
+
     @staticmethod
     def _payload_arrays(payloads):
         bufs = [np.frombuffer(b, dtype=np.uint8) for b in payloads]

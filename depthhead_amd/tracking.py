@@ -1,0 +1,125 @@
+"""Several cameras in one batch, and live head tracking on the device (include/depthhead_hip.h: dh_cameras, dh_tracker).
+
+* `Cameras(intrinsics, device)`: an immutable table of per-camera intrinsic matrices on one GPU.  Frame i of a camera batch
+  (`HoughPrediction.predict_batch_cameras`) is seen by camera i.
+* `HeadTracker(hp, cameras, w, h, prev_guess, sluggish)`: the reference's live loop (examples/live_prediction.rs:79-101) for
+  one frame per camera per step -- each camera's pose becomes that camera's next guess without leaving the device.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import POSE_DTYPE, check, vp
+
+TRACK_PREV_GUESS = 1   # DH_TRACK_PREV_GUESS: live_prediction --prevguess
+TRACK_SLUGGISH = 2     # DH_TRACK_SLUGGISH:   live_prediction --sluggish
+
+
+def _stream(stream: int):
+    return C.c_void_p(stream) if stream else None
+
+
+class Cameras:
+    """`intrinsics`: [n, 3, 3] (or [n, 9]) f32 row-major matrices, or a list of `IntrinsicMatrix`."""
+
+    def __init__(self, intrinsics, device: int = 0):
+        self._lib = _lib.load()
+        mats = [getattr(k, "mat", k) for k in intrinsics] if isinstance(intrinsics, (list, tuple)) else intrinsics
+        self.K = np.ascontiguousarray(np.asarray(mats, dtype=np.float32).reshape(-1, 9))
+        self.n = int(self.K.shape[0])
+        self.device = device
+        self._h = C.c_void_p()
+        check(self._lib.dh_cameras_create(vp(self.K), C.c_int(self.n), C.c_int(device), C.byref(self._h)))
+
+    def __len__(self) -> int:
+        return self.n
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.dh_cameras_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class HeadTracker:
+    """One frame per camera per step; the state (midpoint [n, 3] f32, rotation [n, 3] f64, guess mask [n] u8) stays on the
+    device.  Steps of one tracker must be stream-ordered.  The camera table must outlive the tracker."""
+
+    def __init__(self, hp, cameras: Cameras, w: int, h: int, prev_guess: bool = True, sluggish: bool = False):
+        self._lib = _lib.load()
+        self.hp, self.cameras, self.w, self.h = hp, cameras, int(w), int(h)
+        self.n = len(cameras)
+        self.flags = (TRACK_PREV_GUESS if prev_guess else 0) | (TRACK_SLUGGISH if sluggish else 0)
+        self._h = C.c_void_p()
+        check(self._lib.dh_tracker_create(cameras._h, C.c_uint32(self.flags), C.byref(self._h)))
+        hp.reserve(self.n, self.w, self.h)      # after this a device step allocates nothing (capturable)
+
+    def _present(self, present):
+        if present is None:
+            return None
+        p = np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
+        return p
+
+    def step(self, frames, present=None) -> np.ndarray:
+        """Host frames [n_cams, h, w] uint16 -> POSE_DTYPE[n_cams]; cameras with present[c] == 0 keep their state."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.shape != (self.n, self.h, self.w):
+            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
+        pr = self._present(present)
+        out = np.zeros(self.n, dtype=POSE_DTYPE)
+        check(self._lib.dh_tracker_step(self.hp._ph, self._h, vp(frames), C.c_int(self.w), C.c_int(self.h), vp(pr), vp(out)))
+        return out
+
+    def step_device(self, frames_ptr: int, out_ptr: int, present_ptr: int = 0, stream: int = 0) -> None:
+        """Device frames [n_cams][h][w] u16, poses [n_cams] dh_pose, present [n_cams] u8 or 0; asynchronous on `stream`."""
+        check(self._lib.dh_tracker_step_device(self.hp._ph, self._h, vp(frames_ptr), C.c_int(self.w), C.c_int(self.h),
+                                               vp(present_ptr or None), vp(out_ptr), _stream(stream)))
+
+    def capture(self, frames_ptr: int, out_ptr: int, present_ptr: int = 0) -> None:
+        """Capture one device step into the predictor's graph slot; every `hp.graph_launch()` is then one step."""
+        check(self._lib.dh_tracker_capture(self.hp._ph, self._h, vp(frames_ptr), C.c_int(self.w), C.c_int(self.h),
+                                           vp(present_ptr or None), vp(out_ptr)))
+
+    def reset(self, camera: int | None = None, stream: int = 0) -> None:
+        """The reference's initial state ([0, 0, 0], no rotation) for one camera or all; stream-ordered."""
+        check(self._lib.dh_tracker_reset(self._h, C.c_int(-1 if camera is None else int(camera)), _stream(stream)))
+
+    def state(self) -> dict:
+        """Synchronous copy of the state: midp [n, 3] f32, rot [n, 3] f64, mask [n] u8 (bit0 midpoint guess, bit1
+        rotation guess) and has_rot [n] bool."""
+        midp = np.zeros((self.n, 3), dtype=np.float32)
+        rot = np.zeros((self.n, 3), dtype=np.float64)
+        flags = np.zeros(self.n, dtype=np.uint8)
+        check(self._lib.dh_tracker_state(self._h, vp(midp), vp(rot), vp(flags)))
+        return {"midp": midp, "rot": rot, "mask": flags & 3, "has_rot": (flags & 4) != 0}
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.dh_tracker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -224,6 +224,47 @@ int dh_predictor_set_forking(dh_predictor *p, int chunks);
 /* Number of sliding-window positions for a frame size (prediction.rs:535-548, 684-686). */
 int dh_patch_grid(const dh_params *p, int w, int h, int *nx, int *ny);
 
+/* ---- several cameras in one batch; live head tracking (examples/live_prediction.rs) ----
+ * A dh_cameras table holds n intrinsic matrices on one device.  It is immutable once created and may be shared by predictors
+ * of that device.  In a camera batch, frame i is seen by camera i of the table: its inverse is the same dh_mat3_inv_f32 a
+ * single-K batch computes, so a table of n copies of K predicts exactly what dh_predict_batch(K) does. */
+typedef struct dh_cameras dh_cameras;
+int dh_cameras_create(const float *K /* [n][9] row-major */, int n, int device, dh_cameras **out);
+int dh_cameras_destroy(dh_cameras *c);
+/* frame i uses camera i; n <= the table's count; guesses / poses as dh_predict_batch(_device).  DH_EINVAL: the table lives
+ * on another device than the predictor, more frames than cameras, NULL arguments. */
+int dh_predict_batch_cameras(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                             const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out);
+int dh_predict_batch_cameras_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                    const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out,
+                                    void *stream);
+
+/* A tracker feeds each camera's pose back as that camera's next guess, on the device (live_prediction.rs:79-101):
+ *   DH_TRACK_PREV_GUESS  the stored midpoint is the next midpoint guess when its z > 500 mm, the stored rotation the next
+ *                        rotation guess once there is one (--prevguess; without it every step predicts without guesses);
+ *   DH_TRACK_SLUGGISH    the stored midpoint moves only when the new one is within an L1 distance of 100 mm of it, or when
+ *                        its z < 500 mm (--sluggish).
+ * The state -- midpoint [n][3] f32, rotation [n][3] f64, guess mask [n] u8 -- lives on the tracker's device and is what the
+ * next step's kernels read as their guesses.  A step predicts one frame per camera (frames [n_cams][h][w]) and then updates
+ * the cameras whose `present` byte is non-zero (all of them when present is NULL); absent cameras are predicted with their
+ * current guesses and keep their state.  One tracker's steps must be stream-ordered: a step reads the state the previous
+ * one wrote.  After dh_predictor_reserve(p, n_cams, w, h) the device step allocates nothing and does not synchronise. */
+#define DH_TRACK_PREV_GUESS 1u
+#define DH_TRACK_SLUGGISH 2u
+typedef struct dh_tracker dh_tracker;
+int dh_tracker_create(const dh_cameras *c, uint32_t flags, dh_tracker **out);   /* the table must outlive the tracker */
+int dh_tracker_destroy(dh_tracker *t);
+/* the reference's initial state, [0,0,0], no rotation, mask 0, for one camera or all (camera = -1); stream-ordered */
+int dh_tracker_reset(dh_tracker *t, int camera, void *stream);
+int dh_tracker_step(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out);
+int dh_tracker_step_device(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                           dh_pose *out, void *stream);
+/* synchronous copy-out, each pointer nullable: midp [n][3], rot [n][3], flags [n] = guess mask | 4 once a rotation is stored */
+int dh_tracker_state(dh_tracker *t, float *midp, double *rot, uint8_t *flags);
+/* capture one dh_tracker_step_device (device pointers) into the predictor's graph slot; replay with dh_graph_launch.  Each
+ * replay is one step.  Like a captured batch it is refused (DH_ESTATE) once the workspace has been reallocated. */
+int dh_tracker_capture(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
