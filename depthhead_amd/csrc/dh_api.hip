@@ -587,6 +587,11 @@ struct CamSel {
         for (int i = 0; i < n; ++i) if (!c->host[(size_t)c0 + i].pin) return false;
         return true;
     }
+    // k_vote's approximate cell quotient covers every camera of frames [0, n) (dh_vote_cell_fast_)
+    bool all_cell_fast(int n, int w, int h) const {
+        for (int i = 0; i < n; ++i) if (!dh_vote_cell_fast_(c->host[(size_t)c0 + i].k, w, h)) return false;
+        return true;
+    }
 };
 
 // How enqueue_range runs besides the product batch.
@@ -731,7 +736,8 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
     if (o.traverse_only) return DH_OK;
     {
         VoteArgs va{};
-        va.n_frames = n; va.w = w; va.h = h; va.cell_fast = p->knobs.vote_exact ? 0 : 1;
+        va.n_frames = n; va.w = w; va.h = h;
+        va.cell_fast = !p->knobs.vote_exact && (!cs.c || cs.all_cell_fast(n, w, h)) ? 1 : 0;   // (one K: dh_launch_vote decides)
         memcpy(va.k, K, sizeof va.k);
         va.cams = cs.dev(); va.cams_pin = cs.c && cs.all_pin(n) ? 1 : 0;
         va.f = p->dev; va.hits = ws.hits.get() + hoff; va.hit_box = ws.hit_box.get() + hoff; va.hit_rot = ws.hit_rot.get() + hoff;

@@ -443,6 +443,13 @@ int dh_blur_taps_(float sigma, std::vector<float> &k) {
     return DH_OK;
 }
 
+// ------------------------------------------------------------------ k_vote's approximate cell quotient
+bool dh_vote_cell_fast_(const float K[9], int w, int h) {
+    if (w <= 0 || h <= 0 || w % 20 != 0 || h % 20 != 0) return false;
+    // (products of a float and a small integer: exact in double; !(x <= b) also refuses NaN)
+    return std::fabs((double)K[2]) * 20.0 <= 100.0 * w && std::fabs((double)K[5]) * 20.0 <= 100.0 * h;
+}
+
 // ------------------------------------------------------------------ upload chunking
 int dh_chunk_plan_(int m, int stage_chunk, bool single, int cstart[DH_STAGE_EVENTS + 1]) {
     if (m <= 0) { cstart[0] = 0; return 0; }

@@ -160,6 +160,17 @@ void dh_build_kernel_r2_(float sigma, std::vector<float> &k, size_t padded);   /
 void dh_build_kernel_table_(float sigma, std::vector<float> &k);    // FullArray3D::build_kernel(20, sigma) (meanshift.rs:228-252), summation order
 int dh_blur_taps_(float sigma, std::vector<float> &k);               // imageproc gaussian_kernel_f32 (restated; parity unpinned)
 
+// k_vote's approximate guess-grid cell (vote_positions) may be used for frames of w x h seen through K: w and h are positive
+// multiples of 20, and the principal point lies within 5 frame widths / heights of the origin,
+//     |cx| * 20 <= 100 * w  and  |cy| * 20 <= 100 * h      (cx = K[2], cy = K[5]; evaluated exactly in double).
+// Why: only quotients q = T + C in [0, 20] can change a cell (outside, both sides clamp to cell 0 / 19), with C = cx * 20 / w
+// the constant term, so |T| <= 20 + |C|.  With e = 2^-24 and v_rcp_f32 within 1 ulp, the pinhole form
+// fma(nx * rcp(nz), kxs, cxs) lies within (6 |T| + 3 |C| + 3 |q|) e of the reference's rounded x2 * 20 / w, that is within
+// 9 (20 + |C|) e <= 6.5e-5 for |C| <= 100: less than the 1e-4 band around a border inside which the reference's expression
+// decides.  (The general form keeps the reference's r0 / r2 and errs by a few e of q alone; one rule covers both.)  NaN or
+// infinite cx / cy fail the test.
+bool dh_vote_cell_fast_(const float K[9], int w, int h);
+
 // ------------------------------------------------------------------ upload chunking of the host entry points
 #define DH_STAGE_EVENTS 16       // upload chunks in flight per slice
 // Chunk starts of a slice of m frames: cstart[0 .. nchunks], cstart[nchunks] = m.  `single` (parity taps on: they describe

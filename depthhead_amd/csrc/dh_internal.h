@@ -216,7 +216,7 @@ struct VoteArgs {
     uint32_t *rot_grid;     // [n][8000]
     const uint32_t *leaf_hits; // nullable [n][n_leaves]: rotation votes per leaf (k_emit); then the 20^3 grid is built per leaf, not per hit
     int stop;               // profiling knob (env DH_VOTE_STOP): 1 / 2 / 3 = return after the LDS set-up / the hit records / the leaf histogram
-    int cell_fast;          // w and h are multiples of 20: a vote's guess-grid cell may be taken from an approximate quotient (vote_positions)
+    int cell_fast;          // a vote's guess-grid cell may be taken from an approximate quotient (vote_positions): dh_vote_cell_fast_ holds
     float sx, sy;           // 20 / w, 20 / h
     float kxs, cxs, kys, cys; // pinhole intrinsics: fx * sx, cx * sx, fy * sy, cy * sy (k_vote's approximate cell quotient)
     const DhCam *cams;      // nullable [n_frames]: per-frame cameras (the CAM instance takes k and kxs .. cys from cams[frame])

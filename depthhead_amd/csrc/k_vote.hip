@@ -47,7 +47,9 @@ __device__ __forceinline__ void vote_positions(const VoteArgs &a, uint32_t *pos,
             // the host: v_rcp_f32 (1 ulp), three roundings and the two constants put it within 9.2e-6 of the real u for |u| <= 21
             // (|first term| <= 31), the reference's own four roundings move its quotient by < 7.4e-6 more, and outside [0, 20) both
             // sides clamp into cell 0 / 19 wherever they are.  Quotients within 1e-4 of an integer, and everything not finite
-            // (nz = 0, NaN), take the reference's expression and its two IEEE divisions -- 0.04 % of the votes.
+            // (nz = 0, NaN), take the reference's expression and its two IEEE divisions -- 0.04 % of the votes.  The bound needs
+            // the constant term cx * 20 / w to be small: a.cell_fast is set by the host only where dh_vote_cell_fast_ (dh_host.h,
+            // the exact inequality and its analysis) holds for the launch's K or for every camera of the launch.
             uint32_t idx;
             float ux, uy;
             if (PINNED) {
@@ -194,7 +196,8 @@ hipError_t dh_launch_vote(const VoteArgs &a, hipStream_t s) {
     const uint32_t slices = a.n_frames >= 128 ? VOTE_SLICES : std::min(128u, std::max((uint32_t)VOTE_SLICES, 1024u / (uint32_t)a.n_frames));
     const dim3 grid(slices, a.n_frames), block(VOTE_THREADS);
     VoteArgs b = a;
-    b.cell_fast = a.cell_fast && a.w % DH_GRID == 0 && a.h % DH_GRID == 0 && a.w > 0 && a.h > 0;
+    // (a camera table: enqueue_range has applied dh_vote_cell_fast_ to every camera of the launch; a.k is only a stand-in)
+    b.cell_fast = a.cell_fast && (a.cams || dh_vote_cell_fast_(a.k, a.w, a.h));
     b.sx = (float)DH_GRID / (float)a.w; b.sy = (float)DH_GRID / (float)a.h;
     b.kxs = a.k[0] * b.sx; b.cxs = a.k[2] * b.sx; b.kys = a.k[4] * b.sy; b.cys = a.k[5] * b.sy;   // (one f32 rounding each: see vote_positions)
 #define VOTE_LAUNCH(TAB_, PIN_)                                                                       \

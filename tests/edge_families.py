@@ -388,6 +388,166 @@ def vote_cells_at_grid_borders() -> Family:
     return Family(forest, synth.ModelParams(stepwidth=4), frames, K, reach=reach)
 
 
+# ---- k_vote's approximate cell quotient, emulated in numpy float32 (depthhead_amd/csrc/k_vote.hip, vote_positions)
+def window_points(K, model, frame):
+    """img_to_space (types.rs:432-445) of the centre of every foreground window of `frame` (the ones that vote), in the
+    reference's window order: float32 [n, 3]."""
+    h, w = frame.shape
+    box = (0, 0, model.subimage_width, model.subimage_height)
+    xy = np.array([(x, y) for x, y, ox, oy in pyref._windows(model, w, h) if pyref.average_value_in_rect(frame, ox, oy, box) > 0.0],
+                  dtype=np.int64).reshape(-1, 2)
+    x, y, z = xy[:, 0].astype(np.float32), xy[:, 1].astype(np.float32), frame[xy[:, 1], xy[:, 0]].astype(np.float32)
+    inv = pyref.mat3_inv(np.asarray(K, dtype=np.float32), np.float32)
+    r = []
+    for j in range(3):                                                  # meancov_estimation.rs:201-216, operation by operation
+        t = x * inv[j][0]
+        t = t + y * inv[j][1]
+        r.append(t + np.float32(1.0) * inv[j][2])
+    with np.errstate(all="ignore"):
+        c = z / r[2]
+        return np.stack([r[0] * c, r[1] * c, r[2] * c], axis=-1)
+
+
+def _fma_f32(a, b, c):
+    """fmaf(a, b, c) with one rounding: a * b of two floats is exact in float64; the float64 sum is rounded to odd (TwoSum
+    gives its error), which then rounds to the float32 of the exact a * b + c."""
+    p = a.astype(F64) * b.astype(F64)
+    s = p + F64(c)
+    bb = s - p
+    with np.errstate(invalid="ignore"):
+        err = (p - (s - bb)) + (F64(c) - bb)
+    inexact = np.isfinite(s) & (err != 0) & (s.view(np.int64) & 1 == 0)
+    s = np.where(inexact, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def vote_cells(K, w, h, p3, offs):
+    """Guess-grid cells of every (window, offset) position vote: (votes [n, m] bool, the reference's cells (prediction.rs:647-672),
+    [the cells vote_positions' PINNED fast path gives with v_rcp_f32 returning RN(1 / nz) - 1 ulp, RN, RN + 1 ulp]).  The fast
+    path is fma(nx * rcp(nz), kxs, cxs) with kxs .. cys rounded once in f32 from 20 / w; quotients within 1e-4 of an integer
+    fall back to the reference's expression, which is what the fast cells hold there."""
+    K = np.asarray(K, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        n = p3[:, None, :] - offs[None, :, :]
+        nx, ny, nz = n[..., 0], n[..., 1], n[..., 2]
+
+        def ref_axis(row, lim):
+            r = nx * K[row, 0]
+            r = r + ny * K[row, 1]
+            r = r + nz * K[row, 2]
+            r2 = nx * K[2, 0]
+            r2 = r2 + ny * K[2, 1]
+            r2 = r2 + nz * K[2, 2]
+            q = r / r2
+            q = np.where(q > 0, q, np.float32(0.0))
+            q = np.where(q < np.float32(lim - 1), q, np.float32(lim - 1))
+            return q.astype(np.int64) * 20 // lim
+        ref = ref_axis(1, h) * 20 + ref_axis(0, w)
+        sx, sy = np.float32(20.0) / np.float32(w), np.float32(20.0) / np.float32(h)
+        kxs, cxs, kys, cys = K[0, 0] * sx, K[0, 2] * sx, K[1, 1] * sy, K[1, 2] * sy
+        rn = np.float32(1.0) / nz
+        fast = []
+        for rc in (np.nextafter(rn, np.float32(-np.inf)), rn, np.nextafter(rn, np.float32(np.inf))):
+            ux, uy = _fma_f32(nx * rc, kxs, cxs), _fma_f32(ny * rc, kys, cys)
+            near = ~(np.abs(ux - np.rint(ux)) > np.float32(1e-4)) | ~(np.abs(uy - np.rint(uy)) > np.float32(1e-4))
+            cell = (np.minimum(np.maximum(uy, 0), 19.5).astype(np.int64) * 20 + np.minimum(np.maximum(ux, 0), 19.5).astype(np.int64))
+            fast.append(np.where(near, ref, cell))
+    return nz >= 0, ref, fast
+
+
+def _one_leaf_forest(offs):
+    rots = np.tile(np.array([[0.1, -0.2, 0.3]]), (2, 1))
+    return Forest(np.array([~0], dtype=np.int32), np.zeros(0, dtype=NODE_DTYPE), np.array([1.0]),
+                  np.array([0, len(offs)], dtype=np.uint32), np.array([0, len(rots)], dtype=np.uint32), offs, rots)
+
+
+def _pos_grid(votes, cells, valtoadd):
+    return np.bincount(cells[votes], minlength=400).astype(np.uint32) * np.uint32(valtoadd)
+
+
+def _one_leaf_offsets_ok(offs):
+    assert len(offs) >= 2 and np.isfinite(offs).all()
+    assert pyref.trace_of_cov(offs, np.float32) <= pyref.MAX_VARIANCE_OFFSET       # prediction.rs:641: the leaf votes
+
+
+def principal_point_beside_the_frame() -> Family:
+    """vote_cells_at_grid_borders with the principal point two frame widths left of and 2.5 heights below the frame (160 x 120,
+    cx = -2 w, cy = 2.5 h): the constant term cx * 20 / w of k_vote's approximate cell quotient is -40 and 50 cells, inside
+    the range its error analysis covers (dh_vote_cell_fast_), so the fast path stays on.  Votes ON, and 1e-6 .. 1e-2 px beside,
+    borders of the 20 x 20 guess grid; the emulated fast path agrees with the reference for every admissible reciprocal."""
+    w, h = 160, 120
+    K = synth.default_intrinsic(w, h)
+    K[0, 2], K[1, 2] = -2.0 * w, 2.5 * h
+    fx = float(K[0, 0])
+    assert fx == int(fx) and w % 20 == 0 and h % 20 == 0
+    frames = np.full((2, h, w), int(fx), dtype=np.uint16)
+    frames[1, :, : w // 2] = 0
+    eps = [0.0, 1e-6, -1e-6, 1e-5, -1e-5, 1e-4, -1e-4, 3e-4, -3e-4, 1e-3, -1e-3, 1e-2]
+    cw, ch = w / 20.0, h / 20.0
+    offs = np.array([[(40 % cw) + 4 * (j % 3) + e, (40 % ch) + 4 * (j % 2) - e, 0.0] for j, e in enumerate(eps)], dtype=np.float32)
+    _one_leaf_offsets_ok(offs)
+    model = synth.ModelParams(stepwidth=4)
+    p3 = window_points(K, model, frames[0])
+    votes, ref, fast = vote_cells(K, w, h, p3, offs)
+    for cells in fast:
+        assert np.array_equal(cells[votes], ref[votes])
+    # the votes' pixel positions x2 sit on and beside the cell borders
+    x2 = (p3[:, None, 0] - offs[None, :, 0]) * K[0, 0] / (p3[:, None, 2] - offs[None, :, 2]) + K[0, 2]
+    d = np.abs(x2 / cw - np.rint(x2 / cw)) * cw
+    assert (d < 1e-6).any() and ((d > 5e-7) & (d < 2e-2)).sum() > 100
+
+    def reach(results):
+        assert np.array_equal(results[0]["pos_grid"], _pos_grid(votes, ref, 1000 // len(offs)))
+        assert results[0]["pos_grid"].astype(np.int64).sum() > 0 and (results[1]["patch_flags"] == 0).any()
+    return Family(_one_leaf_forest(offs), model, frames, K, reach=reach)
+
+
+def principal_point_far_off_the_frame() -> Family:
+    """A principal point about 100 frame widths left of a 160 x 120 frame (cx = -15918.38..., found by search), where the
+    constant term of k_vote's approximate cell quotient is about -1990 cells and the quotient's rounding errors pass the
+    1e-4 border band.  Offsets (drawn to put votes within 6e-4 of a cell border, kept where the emulation mis-cells them)
+    send, under each of the three reciprocals within 1 ulp of 1 / nz, several votes of a flat frame to a different cell from
+    the reference's x2 * 20 / w.  The host keeps such a K off the fast path (dh_vote_cell_fast_)."""
+    w, h = 160, 120
+    K = synth.default_intrinsic(w, h)
+    K[0, 2] = np.float32(-15918.3837890625)
+    fx, z = float(K[0, 0]), int(K[0, 0])
+    cw = w / 20.0
+    model = synth.ModelParams(stepwidth=4)
+    frames = np.full((2, h, w), z, dtype=np.uint16)
+    frames[1, :, : w // 2] = 0
+    p3 = window_points(K, model, frames[0])
+    # candidates: window i's vote lands at x2 = (nx / nz) fx + cx = k * cw + e, |e| < 6e-4 cells, |ox| about <= 20 px
+    rs = np.random.RandomState(3)
+    m = 600
+    oz = rs.uniform(-0.1, 0.1, m).astype(np.float32)        # (nx moves by about cx * oz / fx)
+    xw = p3[rs.randint(0, len(p3), m), 0].astype(F64)
+    pix = xw * fx / z + float(K[0, 2])
+    u = np.round((pix - rs.uniform(-20, 20, m)) / cw) + rs.uniform(-6e-4, 6e-4, m)
+    ox = (xw - (u * cw - float(K[0, 2])) * (z - oz.astype(F64)) / fx).astype(np.float32)
+    cand = np.stack([ox, rs.uniform(-10, 10, m).astype(np.float32), oz], axis=-1)
+    votes, ref, fast = vote_cells(K, w, h, p3, cand)
+    keep = set()
+    for cells in fast:                                  # the 8 candidates that mis-cell most votes, per reciprocal
+        bad = ((cells != ref) & votes).sum(axis=0)
+        keep.update(int(j) for j in np.argsort(-bad, kind="stable")[:8] if bad[j] > 0)
+    offs = cand[sorted(keep)]
+    _one_leaf_offsets_ok(offs)
+    valtoadd = 1000 // len(offs)
+    grids = []
+    for f in frames:
+        votes, ref, fast = vote_cells(K, w, h, window_points(K, model, f), offs)
+        for cells in fast:
+            assert ((cells != ref) & votes).sum() >= 3, "the fast quotient mis-cells too few votes"
+        grids.append(_pos_grid(votes, ref, valtoadd))
+        assert all(not np.array_equal(_pos_grid(votes, cells, valtoadd), grids[-1]) for cells in fast)
+
+    def reach(results):
+        for r, g in zip(results, grids):             # pyref counts every vote in the reference's cell
+            assert np.array_equal(r["pos_grid"], g)
+    return Family(_one_leaf_forest(offs), model, frames, K, reach=reach)
+
+
 def nonfinite_rotations() -> Family:
     """Rotations of NaN, +-inf and 1e300 in voting leaves: the trace of their covariance is NaN or inf, so `<= 400` is false
     and the leaf casts no rotation vote (prediction.rs:600); its position votes still count."""
@@ -468,11 +628,33 @@ def meanshift_dead_end() -> Family:
     return Family(forest, model, frames, synth.default_intrinsic(w, h), None, rot, reach=reach)
 
 
+def is_pinhole(K) -> bool:
+    K = np.asarray(K, dtype=np.float32)
+    return bool(K[0, 1] == 0 and K[1, 0] == 0 and K[2, 0] == 0 and K[2, 1] == 0 and K[2, 2] == 1)
+
+
+def decoy_cameras(fam) -> np.ndarray:
+    """One decoy camera per frame of a family (float32 [n, 3, 3]) for the camera-table tests: pinhole variants of a pinhole K
+    with other fx, fy, cx and cy; perturbations of every entry of a dense K."""
+    out = []
+    for j in range(fam.frames.shape[0]):
+        D = np.asarray(fam.K, dtype=np.float32).copy()
+        s = 1.0 + 0.03 * (j + 1)
+        if is_pinhole(D):
+            D[0, 0] *= s; D[1, 1] /= s; D[0, 2] += 2.5 * (j + 1); D[1, 2] -= 1.5 * (j + 1)
+        else:
+            D *= np.float32(s)
+            D[0, 1] += 0.25; D[1, 0] -= 0.125; D[2, 0] += 1e-3 * (j + 1)
+        out.append(D)
+    return np.stack(out).astype(np.float32)
+
+
 FAMILIES = {f.__name__: f for f in (
     hand_forest, integer_thresholds, nonfinite_thresholds, blank_frames, no_window_frame, one_row_of_windows, guess_overrides,
     odd_patch_dense_intrinsic, window_means_at_the_gate, probabilities_outside_the_unit_interval, nonfinite_offset_votes,
     mixed_rectangles_on_reachable_differences, hundreds_of_equal_rotations, vote_cells_at_grid_borders, nonfinite_rotations,
-    zero_meanshift_iterations, underflowing_kernel, meanshift_dead_end)}
+    zero_meanshift_iterations, underflowing_kernel, meanshift_dead_end, principal_point_beside_the_frame,
+    principal_point_far_off_the_frame)}
 
 
 # ================================================================== sibling consumers: predict_mask, the 2-D Hough image

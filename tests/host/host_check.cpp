@@ -2,14 +2,16 @@
 // sanitizers: built by tests/test_host_sanitize.py with g++ -fsanitize=address,undefined and once more with
 // -fsanitize=thread.  Prints "host_check ok" and exits 0; any check that fails prints its line and exits 1.
 // Covers: forest validation (good / every refused kind), patch grids, tile selection across geometries (with the invariants
-// the kernels rely on), the per-batch counter block's layout, upload chunk plans, the run-length payload scanner / packer on
-// well-formed, redundant and malformed payloads (incl. every truncation point of a payload), the host BIWI parsers, knob
-// parsing, the exception guard, and dh_parallel_for_ / the thread-local error slots under concurrency.
+// the kernels rely on), the per-batch counter block's layout, upload chunk plans, where k_vote's approximate cell quotient
+// is allowed, the run-length payload scanner / packer on well-formed, redundant and malformed payloads (incl. every
+// truncation point of a payload), the host BIWI parsers, knob parsing, the exception guard, and dh_parallel_for_ / the
+// thread-local error slots under concurrency.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <stdexcept>
 #include <string>
@@ -261,6 +263,35 @@ static void test_chunk_plan() {
     CHECK(dh_chunk_plan_(40, 64, true, cs) == 1 && dh_chunk_plan_(40, 64, false, cs) == 2);
 }
 
+// ------------------------------------------------------------------ k_vote's approximate cell quotient: where the host allows it
+static void test_vote_cell_fast() {
+    auto K = [](float cx, float cy) { return std::vector<float>{575.8f, 0.f, cx, 0.f, 575.8f, cy, 0.f, 0.f, 1.f}; };
+    CHECK(dh_vote_cell_fast_(K(320.f, 240.f).data(), 640, 480));               // the benchmark's (synth.default_intrinsic)
+    CHECK(dh_vote_cell_fast_(K(-320.f, 300.f).data(), 160, 120));              // cx = -2 w, cy = 2.5 h
+    CHECK(dh_vote_cell_fast_(K(0.f, 0.f).data(), 20, 20));
+    // the frame: positive multiples of 20 only
+    for (int w : {0, -20, 150, 201, 19, 21, 630})
+        CHECK(!dh_vote_cell_fast_(K(0.f, 0.f).data(), w, 480) && !dh_vote_cell_fast_(K(0.f, 0.f).data(), 640, w));
+    // |cx| * 20 <= 100 w and |cy| * 20 <= 100 h, inclusive, on both signs: exactly 5 w / 5 h passes, the next float does not
+    for (int w : {20, 160, 640, 1920})
+        for (float sgn : {1.f, -1.f}) {
+            const float edge = sgn * 5.f * (float)w, past = std::nextafter(edge, sgn * INFINITY);
+            CHECK(dh_vote_cell_fast_(K(edge, 0.f).data(), w, 120) && !dh_vote_cell_fast_(K(past, 0.f).data(), w, 120));
+            CHECK(dh_vote_cell_fast_(K(0.f, edge).data(), 160, w) && !dh_vote_cell_fast_(K(0.f, past).data(), 160, w));
+            CHECK(dh_vote_cell_fast_(K(std::nextafter(edge, 0.f), 0.f).data(), w, 120));
+        }
+    CHECK(!dh_vote_cell_fast_(K(-15918.3837890625f, 60.f).data(), 160, 120));   // about 100 frame widths away
+    for (float bad : {NAN, INFINITY, -INFINITY}) {
+        CHECK(!dh_vote_cell_fast_(K(bad, 240.f).data(), 640, 480));
+        CHECK(!dh_vote_cell_fast_(K(320.f, bad).data(), 640, 480));
+    }
+    // the other entries of K play no part (the general form of the projection keeps the reference's quotient)
+    std::vector<float> dense = {22.0f, 11.4f, 12.11f, 2.1f, 4.1f, 2.11f, 1.3f, 3.1f, 19.0f};
+    CHECK(dh_vote_cell_fast_(dense.data(), 160, 120));
+    dense[0] = INFINITY; dense[8] = NAN;
+    CHECK(dh_vote_cell_fast_(dense.data(), 160, 120));
+}
+
 // ------------------------------------------------------------------ run-length coded payloads
 static void put32(std::vector<uint8_t> &b, uint32_t v) { for (int i = 0; i < 4; ++i) b.push_back((uint8_t)(v >> (8 * i))); }
 static std::vector<uint8_t> encode(const std::vector<uint16_t> &img, uint32_t W, uint32_t H, bool redundant) {
@@ -480,6 +511,7 @@ int main() {
     test_forest();
     test_geometry();
     test_chunk_plan();
+    test_vote_cell_fast();
     test_rle();
     test_biwi_text();
     test_tables_and_knobs();

@@ -35,6 +35,18 @@ def family_results(name):
     return _cache[name]
 
 
+def decoy_results(name):
+    """(decoy cameras, pyref results of frame i seen through decoy camera i) of a 3-D family (ef.decoy_cameras), once per session."""
+    key = ("decoy", name)
+    if key not in _cache:
+        fam = family_results(name)[0]
+        Ds = ef.decoy_cameras(fam)
+        with np.errstate(all="ignore"):
+            res = [pyref.predict(fam.forest, fam.model, f, Ds[i], *fam.guesses(i)) for i, f in enumerate(fam.frames)]
+        _cache[key] = (Ds, res)
+    return _cache[key]
+
+
 def aux_family_results(name):
     key = ("aux", name)
     if key not in _cache:
@@ -53,6 +65,20 @@ def test_pyref_against_the_oracle(oracle, name, mode):
     for i, f in enumerate(fam.frames):
         mg, rg = fam.guesses(i)
         r = oracle.predict(fam.forest, fam.model, f, fam.K, mg, rg, rect_mode=MODES[mode])
+        for k in KEYS:
+            assert np.array_equal(res[i][k], getattr(r, k)), (name, i, k, res[i][k], getattr(r, k))
+
+
+@pytest.mark.parametrize("name", list(ef.FAMILIES))
+def test_pyref_against_the_oracle_with_decoy_cameras(oracle, name):
+    """The decoy cameras that tests/test_gpu_camera_edges.py interleaves with every family's own K: pyref and the oracle agree
+    on every intermediate there too."""
+    fam = family_results(name)[0]
+    Ds, res = decoy_results(name)
+    assert ef.is_pinhole(Ds[0]) == ef.is_pinhole(fam.K) and not (Ds == fam.K).all(axis=(1, 2)).any()
+    for i, f in enumerate(fam.frames):
+        mg, rg = fam.guesses(i)
+        r = oracle.predict(fam.forest, fam.model, f, Ds[i], mg, rg)
         for k in KEYS:
             assert np.array_equal(res[i][k], getattr(r, k)), (name, i, k, res[i][k], getattr(r, k))
 

@@ -13,6 +13,7 @@ larger torch allocation between two guard bands:
 Outputs sit at skewed addresses (a mask at an odd byte, u16 images at 2 mod 4, poses at 8 mod 16), frames at 0 / 2 / 4 / 6
 bytes past an 8-byte boundary with widths of every residue mod 4, so that both the 8-byte-load and the narrow-load paths
 run.  Calls go to a non-default torch stream, each right behind an asynchronous upload of its frames on that stream.
+Camera-table batches and tracker steps are held to the same bands: their `present` bytes between non-zero and zero bands.
 """
 import os
 
@@ -511,3 +512,89 @@ def test_aux_device_calls_between_product_batches(hp_mod, oracle, torch_dev, aux
             _check_poses(out.result("poses"), ref, ("batch", i, "forked" if forked else "whole"))
             if forked:
                 hp.set_forking(0)
+
+
+# ------------------------------------------------------------------ (d) camera tables and tracker steps on device buffers
+@pytest.mark.parametrize("chunks", [1, 2, 3])
+def test_predict_batch_cameras_device_inside_guard_bands(hp_mod, oracle, torch_dev, pose_forest, chunks):
+    """dh_predict_batch_cameras_device, unforked and forked into 2 / 3 sub-batches: frames at 2 mod 4, guesses and the guess
+    mask between harmful bands, poses at 8 mod 16 on a non-default stream; every record written, the bands intact, frame i
+    the oracle's with camera i's K and its own guesses, byte-identical with zero bands around every input."""
+    from depthhead_amd.tracking import Cameras
+    from test_gpu_tracking import cameras_k
+    torch, dev = torch_dev
+    w, h, n = 202, 152, 50
+    model = synth.ModelParams(stepwidth=4)
+    Ks = cameras_k(w, h)
+    cam_of = (np.arange(n) * 3) % len(Ks)
+    frames = synth.biwi_batch(n, w, h, first=600)
+    base = np.zeros(n * PB, dtype=np.uint8)
+    for c in range(len(Ks)):
+        idx = np.flatnonzero(cam_of == c)
+        base.reshape(n, PB)[idx] = _pose_refs(oracle, pose_forest, model, frames[idx], Ks[c]).reshape(-1, PB)
+    mg, rg, gm = _guesses(base, n)
+    ref = np.zeros(n * PB, dtype=np.uint8)
+    for c in range(len(Ks)):
+        idx = np.flatnonzero(cam_of == c)
+        ref.reshape(n, PB)[idx] = _pose_refs(oracle, pose_forest, model, frames[idx], Ks[c], mg[idx], rg[idx], gm[idx]).reshape(-1, PB)
+    st = torch.cuda.Stream(device=dev)
+    out = OutBuf(torch_dev, n * PB, 8, 80 + chunks)
+    got = []
+    with hp_mod.HoughPrediction(pose_forest, model, device=0) as hp, Cameras(Ks[cam_of]) as cams:
+        hp.set_forking(chunks)
+        hp.reserve(n, w, h)
+        for harmful in (True, False):
+            fin = InBuf(torch_dev, frames.nbytes, 2, 13, _harm_u16 if harmful else None)
+            gb = GuessBufs(torch_dev, n, 30, harmful)
+            out.reset()
+            fin.upload(frames, st)
+            gb.upload(mg, rg, gm, st)
+            hp.predict_batch_cameras_device(fin.ptr, n, w, h, cams, out.ptr, gb.mg.ptr, gb.rg.ptr, gb.gm.ptr, stream=st.cuda_stream)
+            st.synchronize()
+            fin.released()
+            gb.released()
+            got.append(out.result("poses"))
+            _check_poses(got[-1], ref, (chunks, "harmful" if harmful else "zero", "bands"))
+    assert got[0].tobytes() == got[1].tobytes()
+
+
+def test_tracker_step_device_inside_guard_bands(hp_mod, oracle, torch_dev):
+    """dh_tracker_step_device on a non-default stream: the `present` bytes between bands of non-zero bytes (and of zero
+    bytes), frames between harmful bands, poses at 8 mod 16 between guard bands.  Every step's records equal the live-loop
+    restatement and the zero-band run byte for byte; the bands stay intact; the final tracker states are identical."""
+    from depthhead_amd.tracking import Cameras, HeadTracker
+    from test_gpu_tracking import RESET_AT, RESET_CAM, STEPS, live_loop_restatement, present_at, track_frames
+    torch, dev = torch_dev
+    forest = synth.fit_forest(6, 10, synth.FOREST_SEED_BASE + 9, n_frames=12, subset=1500)
+    model = synth.ModelParams(stepwidth=4)
+    Ks, frames = track_frames()
+    C, h, w = frames.shape[1], frames.shape[2], frames.shape[3]
+    ref_poses, _, _, _ = live_loop_restatement(oracle, forest, model, Ks, frames, True, False)
+    st = torch.cuda.Stream(device=dev)
+    runs = []
+    for harmful in (True, False):
+        out = OutBuf(torch_dev, C * PB, 8, 90)
+        fin = InBuf(torch_dev, frames[0].nbytes, 2, 17, _harm_u16 if harmful else None)
+        pin = InBuf(torch_dev, C, 1, 19, _harm_u8 if harmful else None)
+        steps = []
+        with hp_mod.HoughPrediction(forest, model, device=0) as hp, Cameras(Ks) as cams, \
+                HeadTracker(hp, cams, w, h, prev_guess=True, sluggish=False) as tr:
+            for t in range(STEPS):
+                if t == RESET_AT:
+                    tr.reset(RESET_CAM, stream=st.cuda_stream)
+                out.reset()
+                fin.upload(frames[t], st)
+                pin.upload(present_at(t, C), st)
+                tr.step_device(fin.ptr, out.ptr, pin.ptr, stream=st.cuda_stream)
+                st.synchronize()
+                fin.released()
+                pin.released()
+                got = out.result(f"poses of step {t}")
+                want = _poses_bytes(np.stack([m for m, _ in ref_poses[t]]), np.stack([r for _, r in ref_poses[t]]))
+                _check_poses(got, want, (t, "harmful" if harmful else "zero", "bands"))
+                steps.append(got)
+            runs.append((steps, tr.state()))
+    (a, sa), (b, sb) = runs
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
+    for k in ("midp", "rot", "mask", "has_rot"):
+        assert sa[k].tobytes() == sb[k].tobytes(), k

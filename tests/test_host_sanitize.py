@@ -7,6 +7,8 @@ import platform
 import shutil
 import subprocess
 
+import numpy as np
+
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,3 +54,41 @@ def test_host_translation_units_have_no_hip_in_them():
         txt = open(os.path.join(CSRC, fn)).read()
         for word in ("hip/hip_runtime", "hipMalloc", "hipStream", "hipError_t", "__global__", "__device__", "dh_internal.h"):
             assert word not in txt, (fn, word)
+
+
+_CELL_FAST_DRIVER = r"""
+#include <stdio.h>
+#include <stdlib.h>
+#include "dh_host.h"
+int main(int argc, char **argv) {          // w h k0 .. k8 -> 1 / 0
+    float K[9];
+    for (int i = 0; i < 9; ++i) K[i] = strtof(argv[3 + i], nullptr);
+    printf("%d\n", dh_vote_cell_fast_(K, atoi(argv[1]), atoi(argv[2])) ? 1 : 0);
+    return 0;
+}
+"""
+
+
+def test_vote_cell_fast_keeps_the_benchmark_intrinsics(tmp_path):
+    """dh_vote_cell_fast_ (dh_host.h) on the Python side's own matrices: the benchmark's K (synth.default_intrinsic(640, 480))
+    and the principal point two frame widths beside the frame keep k_vote's approximate cell quotient; the one about 100 frame
+    widths away, where the quotient is known to pick wrong cells (tests/edge_families.py), does not."""
+    import edge_families as ef
+    from depthhead_amd import synth
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    src, exe = tmp_path / "cell_fast.cpp", str(tmp_path / "cell_fast")
+    src.write_text(_CELL_FAST_DRIVER)
+    res = subprocess.run([gxx, "-std=c++17", "-O1", "-ffp-contract=off", "-pthread", f"-I{CSRC}", str(src), os.path.join(CSRC, "dh_host.cpp"),
+                          "-o", exe], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-3000:]
+
+    def fast(K, w, h):
+        args = [repr(float(v)) for v in np.asarray(K, dtype=np.float32).reshape(-1)]   # (repr of a float32 widened: exact)
+        return subprocess.run([exe, str(w), str(h), *args], capture_output=True, text=True, timeout=60).stdout.strip() == "1"
+    assert fast(synth.default_intrinsic(640, 480), 640, 480)
+    for name, expect in (("principal_point_beside_the_frame", True), ("principal_point_far_off_the_frame", False)):
+        fam = ef.FAMILIES[name]()
+        n, h, w = fam.frames.shape
+        assert fast(fam.K, w, h) == expect, name
