@@ -19,6 +19,11 @@ ERRORS = {-1: "DH_EINVAL", -2: "DH_EFOREST", -3: "DH_EHIP", -4: "DH_ENOMEM", -5:
 
 POSE_DTYPE = np.dtype([("mid_point", "<f4", (3,)), ("reserved", "<u4"), ("rotation", "<f8", (3,))], align=True)
 assert POSE_DTYPE.itemsize == 40
+# dh_support: vote support of a pose (head bounding box of the supporting windows' centres, counts, mass)
+SUPPORT_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4"), ("width", "<u4"), ("height", "<u4"), ("windows", "<u4"), ("hits", "<u4"),
+                          ("mass", "<u8"), ("total_mass", "<u8")], align=True)
+assert SUPPORT_DTYPE.itemsize == 40
+SUPPORT_RADIUS = 30   # DH_SUPPORT_RADIUS
 
 
 class ForestDesc(C.Structure):
@@ -53,6 +58,8 @@ EXPORTS = [
     "dh_cameras_create", "dh_cameras_destroy", "dh_predict_batch_cameras", "dh_predict_batch_cameras_device",
     "dh_tracker_create", "dh_tracker_destroy", "dh_tracker_reset", "dh_tracker_step", "dh_tracker_step_device",
     "dh_tracker_state", "dh_tracker_capture",
+    "dh_predict_batch_support", "dh_predict_batch_support_device", "dh_predict_batch_cameras_support",
+    "dh_predict_batch_cameras_support_device", "dh_tracker_step_support", "dh_tracker_step_support_device",
 ]
 
 

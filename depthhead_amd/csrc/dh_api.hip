@@ -180,6 +180,13 @@ struct Workspace {
     Buf<int32_t> dbg_votes;            // 16-byte vote records (debug_votes_)
     Buf<uint32_t> dbg_vcount;
     bool dbg_valid = false;
+    // vote support (k_support), allocated by the first support call of this workspace (support_reserve): nothing else reads them,
+    // so allocating them leaves every other buffer -- and a captured batch -- as it is
+    Buf<uint32_t> hit_win;             // [cap][hits_cap] window of every hit record (k_emit's SUP instance)
+    Buf<SupAcc> sup_acc;               // [cap] per-frame accumulators, zero between calls
+    Buf<uint32_t> sup_bits;            // [cap][sup_words] window bitmaps, zero between calls
+    uint32_t sup_words = 0;
+    Buf<dh_support> sup;               // [cap] host entry points: the support records of a slice on the device
 
     // frame f0's entries of the counter block (CounterLayout, dh_host.h)
     uint32_t *hit_count(int f0) const { return counters.get() + lay.hit_count + f0; }
@@ -217,6 +224,7 @@ struct dh_predictor {
     hipEvent_t ev_stage[DH_STAGE_EVENTS] = {};   // chunk k uploaded (recorded on an upload stream, waited for on own_stream)
     hipEvent_t ev_slice = nullptr;        // the kernels that read the staging buffers are done (recorded on own_stream)
     Buf<uint8_t, PINNED> pin_small;       // page-locked staging of a slice's small host arrays: poses out, guesses in (small_stage)
+    Buf<dh_support, PINNED> pin_sup;      // ... and support records out (download_support)
     // run-length coded input (dh_predict_batch_rle): pinned staging + device copies of payload blob and run table
     Buf<uint8_t, PINNED> pin_blob;
     Buf<uint2, PINNED> pin_runs;
@@ -602,6 +610,8 @@ struct EnqueueOpts {
     bool traverse_only = false;     // stop after k_traverse
     int chunk = 0;                  // forked sub-batch: its tile-flag tag and tile list
     bool zero_fold = false;         // k_boxsum zeroes the counters: no fill of their own
+    dh_support *support = nullptr;  // non-NULL: k_emit's SUP instance, then k_support after k_cluster (indexed like `out`)
+    uint32_t radius = 0;
 };
 
 // Enqueue the kernels (k_boxsum / k_pixflags, k_traverse, k_emit, k_vote, [k_region,] k_cluster) for frames [f0, f0 + n) of the batch on stream s.
@@ -726,6 +736,7 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
             ea.leaf_hits = leaf_hits;
             ea.gen = gen;
             ea.dbg_flags = ta.dbg_flags;
+            if (o.support) ea.hit_win = ws.hit_win.get() + hoff;
 #ifdef DH_PROFILING_KNOBS
             ea.stop = p->knobs.emit_stop;
 #endif
@@ -794,6 +805,17 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         }
         { Range r(o.profile, "dh:cluster"); HIP_TRY(dh_launch_cluster(ca, s)); }
     }
+    if (o.support) {
+        SupportArgs sa{};
+        sa.n_frames = n; sa.nx = g.nx; sa.step = (int)p->params.stepwidth;
+        sa.lw = (int)p->params.subimage_width / 2; sa.lh = (int)p->params.subimage_height / 2;
+        sa.radius = o.radius; sa.poses = out + f0;
+        sa.hits = ws.hits.get() + hoff; sa.hit_box = ws.hit_box.get() + hoff; sa.hit_win = ws.hit_win.get() + hoff;
+        sa.hit_count = hit_count; sa.hits_cap = ws.hits_cap; sa.off4 = p->dev.off4;
+        sa.acc = ws.sup_acc.get() + f0; sa.bits = ws.sup_bits.get() + (size_t)f0 * ws.sup_words; sa.bit_words = ws.sup_words;
+        sa.out = o.support + f0;
+        { Range r(o.profile, "dh:support"); HIP_TRY(dh_launch_support(sa, s)); }
+    }
     if (o.profile) { HIP_TRY(hipEventRecord(p->ev[3], s)); p->ev_valid = true; }
     return DH_OK;
 }
@@ -803,13 +825,42 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
 // stream, reusing the workspace.
 static int max_resident_frames(const dh_predictor *p) { return p->knobs.max_resident; }
 
+// Support records of a batch (the *_support entry points): one per frame, indexed like the poses.
+struct SupOut {
+    dh_support *rec = nullptr;
+    uint32_t radius = 0;
+};
+
+// The support scratch of the current workspace (Workspace::hit_win ..), allocated and zeroed on the first support call that
+// needs it; a no-op after that.  Nothing a captured batch points to is touched.
+static int support_reserve(dh_predictor *p) {
+    Workspace &ws = p->ws;
+    if (ws.sup) return DH_OK;           // (allocated last: its presence means the others are there and zeroed)
+    const size_t cap = (size_t)ws.cap_frames;
+    ws.sup_words = (uint32_t)((std::max(ws.geom.npatch, 1) + 31) / 32);
+    TRY(ws.hit_win.alloc(cap * ws.hits_cap));
+    TRY(ws.sup_acc.alloc(cap));
+    TRY(ws.sup_bits.alloc(cap * ws.sup_words));
+    TRY(ws.sup.alloc(cap));
+    if (hipMemsetAsync(ws.sup_acc.get(), 0, cap * sizeof(SupAcc), p->own_stream) != hipSuccess ||
+        hipMemsetAsync(ws.sup_bits.get(), 0, cap * ws.sup_words * sizeof(uint32_t), p->own_stream) != hipSuccess ||
+        hipStreamSynchronize(p->own_stream) != hipSuccess) {
+        ws.sup.reset();
+        return fail(DH_EHIP, "zero-fill of the support scratch");
+    }
+    return DH_OK;
+}
+
 // The device batch behind dh_predict_batch_device and the camera / tracker calls (arguments checked, device selected): one K
 // (cams.c == NULL) or frame i -> camera cams.c0 + i.  Slices and forked sub-batches offset the camera as they offset guesses.
+// With `sup`, every slice and sub-batch also reports its frames' vote support (k_support) into sup->rec, offset like `out`.
 static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const CamSel &cams,
-                        const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out, hipStream_t s) {
+                        const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out, hipStream_t s,
+                        const SupOut *sup = nullptr) {
     const int slice = p->debug ? n : std::min(n, max_resident_frames(p));   // the taps index the whole batch
     int rc = reserve(p, slice, w, h);
     if (rc) return rc;
+    if (sup) TRY(support_reserve(p));
     float kinv[9];
     if (cams.c) {                // (kernel-argument stand-ins: the CAM instances read the records)
         K = cams.c->host[cams.c0].k;
@@ -843,6 +894,7 @@ static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, i
         if (chunks <= 1) {
             EnqueueOpts o;
             o.profile = p->profiling; o.zero_fold = fold;
+            if (sup) { o.support = sup->rec + f0; o.radius = sup->radius; }
             TRY(enqueue_range(p, fr, 0, m, w, h, K, kinv, cams.at(f0), mg, rg, gm, out + f0, s, o));
         } else {
             HIP_TRY(hipEventRecord(p->ev_fork, s));
@@ -852,6 +904,7 @@ static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, i
                 if (c > 0) HIP_TRY(hipStreamWaitEvent(cs, p->ev_fork, 0));
                 EnqueueOpts o;
                 o.chunk = c;
+                if (sup) { o.support = sup->rec + f0; o.radius = sup->radius; }
                 TRY(enqueue_range(p, fr, c0, c1 - c0, w, h, K, kinv, cams.at(f0), mg, rg, gm, out + f0, cs, o));
                 if (c > 0) {
                     HIP_TRY(hipEventRecord(p->ev_join[c - 1], cs));
@@ -935,8 +988,16 @@ static int slice_setup(dh_predictor *p, int f0, int m, int w, int h, const Guess
 }
 // Chunk [c0, c0 + cm) of a staged slice -- frames, guesses and poses in the workspace -- on stream s; with a camera table
 // (`cams`: the slice's first frame) frame c0 + i reads camera cams.c0 + c0 + i.
-static int predict_staged(dh_predictor *p, int c0, int cm, int w, int h, const float K[9], const CamSel &cams, const Guesses &g, hipStream_t s) {
+// With `sup` (its records: the slice's, in Workspace::sup) chunk frame c0 + i reports into sup->rec[c0 + i].
+static int predict_staged(dh_predictor *p, int c0, int cm, int w, int h, const float K[9], const CamSel &cams, const Guesses &g, hipStream_t s,
+                          const SupOut *sup = nullptr) {
     const Workspace &ws = p->ws;
+    if (sup) {
+        const SupOut so{sup->rec + c0, sup->radius};
+        return batch_device(p, ws.frames.get() + (size_t)c0 * w * h, cm, w, h, cams.c ? nullptr : K, cams.c ? cams.at(c0) : CamSel{},
+                            g.midp ? ws.midp.get() + (size_t)c0 * 3 : nullptr, g.rot ? ws.rot.get() + (size_t)c0 * 3 : nullptr,
+                            g.mask ? ws.mask.get() + c0 : nullptr, ws.poses.get() + c0, s, &so);
+    }
     if (cams.c)
         return batch_device(p, ws.frames.get() + (size_t)c0 * w * h, cm, w, h, nullptr, cams.at(c0), g.midp ? ws.midp.get() + (size_t)c0 * 3 : nullptr,
                             g.rot ? ws.rot.get() + (size_t)c0 * 3 : nullptr, g.mask ? ws.mask.get() + c0 : nullptr, ws.poses.get() + c0, s);
@@ -950,16 +1011,26 @@ static int download_poses(dh_predictor *p, const SmallStage &st, int m, dh_pose 
     memcpy(out, st.poses, (size_t)m * sizeof(dh_pose));
     return DH_OK;
 }
+// support records of the slice: Workspace::sup -> pinned staging on s, wait, -> the caller's array (after download_poses)
+static int download_support(dh_predictor *p, int m, dh_support *out, hipStream_t s) {
+    TRY(p->pin_sup.grow((size_t)m));
+    HIP_TRY(hipMemcpyAsync(p->pin_sup.get(), p->ws.sup.get(), (size_t)m * sizeof(dh_support), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(out, p->pin_sup.get(), (size_t)m * sizeof(dh_support));
+    return DH_OK;
+}
 // The slice loop of the host batch paths: enqueue(f0, m, &st) sets slice [f0, f0 + m) up (slice_setup) and enqueues its
-// prediction on own_stream; its poses then come back in one copy.  With the taps on, the whole batch is one slice.
+// prediction on own_stream; its poses then come back in one copy (and with `sup`, its support records in a second one).  With
+// the taps on, the whole batch is one slice.
 template <typename F>
-static int host_slices(dh_predictor *p, int n, dh_pose *out, F enqueue) {
+static int host_slices(dh_predictor *p, int n, dh_pose *out, F enqueue, dh_support *sup = nullptr) {
     const int slice = p->debug ? n : std::min(n, max_resident_frames(p));
     for (int f0 = 0; f0 < n; f0 += slice) {
         const int m = std::min(slice, n - f0);
         SmallStage st;
         int rc = enqueue(f0, m, &st);
         if (rc == DH_OK) rc = download_poses(p, st, m, out + f0, p->own_stream);
+        if (rc == DH_OK && sup) rc = download_support(p, m, sup + f0, p->own_stream);
         if (rc) return rc;
     }
     return DH_OK;
@@ -968,21 +1039,26 @@ static int host_slices(dh_predictor *p, int n, dh_pose *out, F enqueue) {
 // Host entry point.  The frames cross PCIe in chunks on copy_stream while the kernels of the previous chunk run on
 // own_stream (the path is PCIe-bound: 614 KB per frame in, 40 bytes out), so a batch takes about its upload time plus
 // the kernels of the last chunk.  The poses of a slice come back in one copy.
+// With `sup` (the caller's host records, sup->rec[i] for frame i) every slice also reports its vote support.
 static int batch_host(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const CamSel &cams,
-                      const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
+                      const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out,
+                      const SupOut *sup = nullptr) {
     const Guesses g{midp_guess, rot_guess, guess_mask};
     hipStream_t s = p->own_stream, cs = p->copy_stream;
     const size_t fpx = (size_t)w * h;
     return host_slices(p, n, out, [&](int f0, int m, SmallStage *st) -> int {
         int rc = slice_setup(p, f0, m, w, h, g, st);
+        if (rc == DH_OK && sup) rc = support_reserve(p);
         if (rc) return rc;
+        const SupOut dsup{p->ws.sup.get(), sup ? sup->radius : 0u};     // the slice's records on the device
+        const SupOut *ds = sup ? &dsup : nullptr;
         // the parity taps describe ONE device batch: with them on, the slice is a single chunk
         int cstart[DH_STAGE_EVENTS + 1];
         const int nchunks = dh_chunk_plan_(m, p->knobs.stage_chunk, p->debug, cstart);
         if (nchunks == 1) {
             // latency path (single frames, small batches): one copy on the compute stream itself
             HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-            rc = predict_staged(p, 0, m, w, h, K, cams.at(f0), g, s);
+            rc = predict_staged(p, 0, m, w, h, K, cams.at(f0), g, s, ds);
             if (rc) { (void)hipStreamSynchronize(s); return rc; }
         } else {
             // Chunk k + 1 is uploaded on copy_stream while the kernels of chunk k run on own_stream.  From page-locked host
@@ -997,13 +1073,13 @@ static int batch_host(dh_predictor *p, const uint16_t *frames, int n, int w, int
                 HIP_TRY(hipMemcpyAsync(p->ws.frames.get() + (size_t)c0 * fpx, frames + (size_t)(f0 + c0) * fpx, (size_t)cm * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, cs));
                 HIP_TRY(hipEventRecord(p->ev_stage[k], cs));
                 HIP_TRY(hipStreamWaitEvent(s, p->ev_stage[k], 0));
-                rc = predict_staged(p, c0, cm, w, h, K, cams.at(f0), g, s);
+                rc = predict_staged(p, c0, cm, w, h, K, cams.at(f0), g, s, ds);
                 if (rc) { (void)hipStreamSynchronize(cs); (void)hipStreamSynchronize(s); return rc; }
             }
         }
         HIP_TRY(hipEventRecord(p->ev_slice, s));
         return DH_OK;
-    });
+    }, sup ? sup->rec : nullptr);
 }
 static int predict_batch_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
                                 const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
@@ -1284,10 +1360,11 @@ static int tracker_reset_(dh_tracker *t, int camera, void *stream) {
 }
 // Cameras [c0, c0 + m) of a step (device frames / poses / present of those cameras): their batch with the tracker's guesses, then
 // k_track over their poses, both on stream s.
+// With `sup`, the batch also reports the cameras' vote support; k_track does not read it.
 static int track_enqueue(dh_predictor *p, dh_tracker *t, int c0, int m, const uint16_t *frames, int w, int h, const uint8_t *present,
-                         dh_pose *out, hipStream_t s) {
+                         dh_pose *out, hipStream_t s, const SupOut *sup = nullptr) {
     TRY(batch_device(p, frames, m, w, h, nullptr, CamSel{t->cams, c0}, t->midp.get() + (size_t)c0 * 3, t->rot.get() + (size_t)c0 * 3,
-                     t->mask.get() + c0, out, s));
+                     t->mask.get() + c0, out, s, sup));
     TrackArgs a{};
     a.poses = out; a.present = present; a.n = m; a.flags = t->flags;
     a.midp = t->midp.get() + (size_t)c0 * 3; a.rot = t->rot.get() + (size_t)c0 * 3; a.mask = t->mask.get() + c0; a.has_rot = t->has_rot.get() + c0;
@@ -1305,25 +1382,33 @@ static int tracker_step_device_(dh_predictor *p, dh_tracker *t, const uint16_t *
     if (!guard.ok) return DH_EHIP;
     return track_enqueue(p, t, 0, t->n, frames, w, h, present, out, (hipStream_t)stream);
 }
-static int tracker_step_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out) {
-    TRY(tracker_args(p, t, frames, out, "dh_tracker_step"));
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
+// The host step behind dh_tracker_step and, with `sup` (host records), dh_tracker_step_support.
+static int tracker_step_host(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out,
+                             const SupOut *sup) {
     hipStream_t s = p->own_stream;
     const size_t fpx = (size_t)w * h;
     // resident slices of the host batch paths: cameras [f0, f0 + m) are staged, predicted and updated, their poses copied back
     return host_slices(p, t->n, out, [&](int f0, int m, SmallStage *st) -> int {
         TRY(slice_setup(p, f0, m, w, h, Guesses{nullptr, nullptr, nullptr}, st));
+        if (sup) TRY(support_reserve(p));
+        const SupOut dsup{p->ws.sup.get(), sup ? sup->radius : 0u};
         HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
         if (present) {
             memcpy(st->mask, present + f0, (size_t)m);       // (the slice's guess-mask staging: a tracker's guesses are on the device)
             HIP_TRY(hipMemcpyAsync(t->present.get() + f0, st->mask, (size_t)m, hipMemcpyHostToDevice, s));
         }
-        int rc = track_enqueue(p, t, f0, m, p->ws.frames.get(), w, h, present ? t->present.get() + f0 : nullptr, p->ws.poses.get(), s);
+        int rc = track_enqueue(p, t, f0, m, p->ws.frames.get(), w, h, present ? t->present.get() + f0 : nullptr, p->ws.poses.get(), s,
+                               sup ? &dsup : nullptr);
         if (rc) { (void)hipStreamSynchronize(s); return rc; }
         HIP_TRY(hipEventRecord(p->ev_slice, s));
         return DH_OK;
-    });
+    }, sup ? sup->rec : nullptr);
+}
+static int tracker_step_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out) {
+    TRY(tracker_args(p, t, frames, out, "dh_tracker_step"));
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    return tracker_step_host(p, t, frames, w, h, present, out, nullptr);
 }
 static int tracker_state_(dh_tracker *t, float *midp, double *rot, uint8_t *flags) {
     if (!t) return fail(DH_EINVAL, "dh_tracker_state: NULL tracker");
@@ -1362,6 +1447,82 @@ static int tracker_capture_(dh_predictor *p, dh_tracker *t, const uint16_t *fram
     p->graph = g;
     HIP_TRY(hipGraphInstantiate(&p->graph_exec, p->graph, nullptr, nullptr, 0));
     return DH_OK;
+}
+
+// ------------------------------------------------------------------ vote support
+// The *_support twins of the batch, camera and tracker calls: the same checks, the same batch with k_emit's SUP instance and
+// k_support appended, one dh_support per frame.  A radius that does not fit an int (a negative one passed) is refused first.
+static int support_args(uint32_t radius, const dh_support *support, const char *fn) {
+    if (radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u (a negative int?); expected 0 .. 2^31 - 1", fn, radius);
+    if (!support) return fail(DH_EINVAL, "%s: NULL support", fn);
+    return DH_OK;
+}
+static int predict_batch_support_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const float *midp_guess,
+                                  const double *rot_guess, const uint8_t *guess_mask, uint32_t radius, dh_pose *out, dh_support *support) {
+    TRY(support_args(radius, support, "dh_predict_batch_support"));
+    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch_support: NULL argument");
+    if (n == 0) return DH_OK;
+    if (n < 0) return fail(DH_EINVAL, "negative batch size");
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    const SupOut sup{support, radius};
+    return batch_host(p, frames, n, w, h, K, CamSel{}, midp_guess, rot_guess, guess_mask, out, &sup);
+}
+static int predict_batch_support_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
+                                         const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius,
+                                         dh_pose *out, dh_support *support, void *stream) {
+    TRY(support_args(radius, support, "dh_predict_batch_support_device"));
+    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch_support_device: NULL argument");
+    if (n == 0) return DH_OK;
+    if (n < 0) return fail(DH_EINVAL, "negative batch size");
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    const SupOut sup{support, radius};
+    return batch_device(p, frames, n, w, h, K, CamSel{}, midp_guess, rot_guess, guess_mask, out, (hipStream_t)stream, &sup);
+}
+static int predict_batch_cameras_support_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                          const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius,
+                                          dh_pose *out, dh_support *support) {
+    TRY(support_args(radius, support, "dh_predict_batch_cameras_support"));
+    if (!p || !frames || !c || !out) return fail(DH_EINVAL, "dh_predict_batch_cameras_support: NULL argument");
+    if (n < 0) return fail(DH_EINVAL, "negative batch size");
+    TRY(cameras_check(p, c, n, "dh_predict_batch_cameras_support"));
+    if (n == 0) return DH_OK;
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    const SupOut sup{support, radius};
+    return batch_host(p, frames, n, w, h, nullptr, CamSel{c, 0}, midp_guess, rot_guess, guess_mask, out, &sup);
+}
+static int predict_batch_cameras_support_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                                 const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
+                                                 uint32_t radius, dh_pose *out, dh_support *support, void *stream) {
+    TRY(support_args(radius, support, "dh_predict_batch_cameras_support_device"));
+    if (!p || !frames || !c || !out) return fail(DH_EINVAL, "dh_predict_batch_cameras_support_device: NULL argument");
+    if (n < 0) return fail(DH_EINVAL, "negative batch size");
+    TRY(cameras_check(p, c, n, "dh_predict_batch_cameras_support_device"));
+    if (n == 0) return DH_OK;
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    const SupOut sup{support, radius};
+    return batch_device(p, frames, n, w, h, nullptr, CamSel{c, 0}, midp_guess, rot_guess, guess_mask, out, (hipStream_t)stream, &sup);
+}
+static int tracker_step_support_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                 uint32_t radius, dh_pose *out, dh_support *support) {
+    TRY(support_args(radius, support, "dh_tracker_step_support"));
+    TRY(tracker_args(p, t, frames, out, "dh_tracker_step_support"));
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    const SupOut sup{support, radius};
+    return tracker_step_host(p, t, frames, w, h, present, out, &sup);
+}
+static int tracker_step_support_device_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                        uint32_t radius, dh_pose *out, dh_support *support, void *stream) {
+    TRY(support_args(radius, support, "dh_tracker_step_support_device"));
+    TRY(tracker_args(p, t, frames, out, "dh_tracker_step_support_device"));
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    const SupOut sup{support, radius};
+    return track_enqueue(p, t, 0, t->n, frames, w, h, present, out, (hipStream_t)stream, &sup);
 }
 
 // ------------------------------------------------------------------ predict_mask / 2-D Hough votes
@@ -1943,4 +2104,10 @@ DH_API(tracker_step, (dh_predictor *p, dh_tracker *t, const uint16_t *frames, in
 DH_API(tracker_step_device, (dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out, void *stream), (p, t, frames, w, h, present, out, stream))
 DH_API(tracker_state, (dh_tracker *t, float *midp, double *rot, uint8_t *flags), (t, midp, rot, flags))
 DH_API(tracker_capture, (dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out), (p, t, frames, w, h, present, out))
+DH_API(predict_batch_support, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius, dh_pose *out, dh_support *support), (p, frames, n, w, h, K, midp_guess, rot_guess, guess_mask, radius, out, support))
+DH_API(predict_batch_support_device, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius, dh_pose *out, dh_support *support, void *stream), (p, frames, n, w, h, K, midp_guess, rot_guess, guess_mask, radius, out, support, stream))
+DH_API(predict_batch_cameras_support, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius, dh_pose *out, dh_support *support), (p, frames, n, w, h, c, midp_guess, rot_guess, guess_mask, radius, out, support))
+DH_API(predict_batch_cameras_support_device, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius, dh_pose *out, dh_support *support, void *stream), (p, frames, n, w, h, c, midp_guess, rot_guess, guess_mask, radius, out, support, stream))
+DH_API(tracker_step_support, (dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, dh_pose *out, dh_support *support), (p, t, frames, w, h, present, radius, out, support))
+DH_API(tracker_step_support_device, (dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, dh_pose *out, dh_support *support, void *stream), (p, t, frames, w, h, present, radius, out, support, stream))
 #undef DH_API

@@ -162,6 +162,7 @@ struct EmitArgs {
     uint8_t  *dbg_flags;    // nullable [n][npatch]: bit 1 set for windows that pass the gate
     int stop;               // profiling knob (env DH_EMIT_STOP): 1 / 2 = return after the window lookup / after the gate
     const DhCam *cams;      // nullable [n_frames]: per-frame cameras (the CAM instance reads cams[frame].kinv, not kinv)
+    uint32_t *hit_win;      // non-NULL selects the SUP instance: [n_frames][hits_cap] window (patch index) of every hit record (k_support)
 };
 
 // k_boxsum: per frame the image of all rw x rh rectangle sums, out[y][x] = sum of the rectangle whose
@@ -279,6 +280,33 @@ struct VotesDumpArgs {
     uint32_t *count;
 };
 
+// k_support: per-frame accumulator of the support record.  Zero between calls: the frame's last
+// workgroup writes the record and clears it.  The minima are kept as their complements, so that 0 is every field's neutral value.
+struct __attribute__((aligned(16))) SupAcc {
+    uint32_t nxmin, nymin, xmax, ymax;   // ~min / max of the supporting windows' centre pixels
+    uint32_t windows, hits, done, pad;   // done: workgroups of the frame that have finished
+    uint64_t mass, total;
+};
+static_assert(sizeof(SupAcc) == 48, "SupAcc: three 16-byte rows");
+static_assert(sizeof(dh_support) == 40, "dh_support: include/depthhead_hip.h");
+
+struct SupportArgs {
+    int n_frames;
+    int nx, step, lw, lh;   // window grid: window gp has its centre at ((gp % nx) * step + lw, (gp / nx) * step + lh) (prediction.rs:544-552)
+    uint32_t radius;
+    const dh_pose  *poses;  // [n_frames] this launch's poses (k_cluster)
+    const HitRec   *hits;
+    const HitBox   *hit_box;
+    const uint32_t *hit_win;   // [n_frames][hits_cap] (k_emit's SUP instance)
+    const uint32_t *hit_count;
+    uint32_t  hits_cap;
+    const float4   *off4;   // DevForest::off4
+    SupAcc   *acc;          // [n_frames], zero on entry and on exit
+    uint32_t *bits;         // [n_frames][bit_words] window bitmap, zero on entry and on exit
+    uint32_t  bit_words;    // ceil(npatch / 32)
+    dh_support *out;        // [n_frames]
+};
+
 // Sibling consumers of the walk (prediction.rs:760-905): they read the per-(patch, tree) leaf ids
 // and the background flags that k_traverse writes when asked to.
 struct AuxArgs {
@@ -377,6 +405,7 @@ hipError_t dh_launch_emit(const EmitArgs &a, hipStream_t s);
 hipError_t dh_launch_vote(const VoteArgs &a, hipStream_t s);
 hipError_t dh_launch_cluster(const ClusterArgs &a, hipStream_t s);
 hipError_t dh_launch_region(const ClusterArgs &a, hipStream_t s);
+hipError_t dh_launch_support(const SupportArgs &a, hipStream_t s);
 hipError_t dh_launch_votes_dump(const VotesDumpArgs &a, hipStream_t s);
 hipError_t dh_launch_track(const TrackArgs &a, hipStream_t s);
 hipError_t dh_launch_boxsum(const BoxArgs &a, hipStream_t s);

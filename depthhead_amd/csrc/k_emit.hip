@@ -15,7 +15,9 @@
 // occupancy of this latency-bound kernel) in proportion to the forest: 62 VGPRs at EB = 8, 80 at 10, 122 at 16.
 // CAM: the batch has a camera table (EmitArgs::cams): the frame's inverse intrinsic comes from its record (an instance of its
 // own: the instances without a table keep their code and registers).
-template <int EB, int LS, bool CAM>      // LS: log2 of the window list's leaf entry size (dh_device.h: load_leaf)
+// SUP: the batch reports vote support (k_support): every hit record's window also goes to EmitArgs::hit_win (again an instance
+// of its own, so the plain instances keep their code).
+template <int EB, int LS, bool CAM, bool SUP>      // LS: log2 of the window list's leaf entry size (dh_device.h: load_leaf)
 __global__ void __launch_bounds__(EMIT_THREADS) k_emit(EmitArgs a) {
     const int frame = blockIdx.y, lane = threadIdx.x & (WAVE - 1);
     if (CAM) cam_kinv(a.kinv, a.cams + frame);
@@ -179,6 +181,7 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(EmitArgs a) {
         const uint32_t h = chunk + (uint32_t)lane;
         const int sw = __shfl(wi, src);
         const float p0 = __shfl(q0, src), p1 = __shfl(q1, src), p2 = __shfl(q2, src);
+        const uint32_t hw = SUP ? (uint32_t)__shfl((int)gp, src) : 0u;
         const uint32_t o = base + h;
         if (h < wave_total && o < a.hits_cap) {
             const uint32_t lid = load_leaf(wlf, ls, (size_t)tree * a.win_cap + sw);
@@ -193,6 +196,7 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(EmitArgs a) {
             // the rotation record is only read when there is no leaf histogram (k_vote, k_cluster) or by the vote-dump tap
             if (!a.leaf_hits || a.dbg_flags) *(uint4 *)(drot + o) = make_uint4(t2v.y, t2v.z, t2v.w, t3.x);    // rlo, rhi, rb, n_rot
             if (a.leaf_hits && !hist_here && (t1.w & LF_ROT)) atomicAdd(&a.leaf_hits[(size_t)frame * a.f.n_leaves + lid], 1u);
+            if (SUP) a.hit_win[(size_t)frame * a.hits_cap + o] = hw;
         }
     }
 }
@@ -202,15 +206,20 @@ hipError_t dh_launch_emit(const EmitArgs &a, hipStream_t s) {
     if (a.n_frames > 65535) return hipErrorInvalidConfiguration;
     const dim3 grid((a.npatch + EMIT_THREADS - 1) / EMIT_THREADS, a.n_frames), block(EMIT_THREADS);
     const uint32_t T = a.f.n_trees;
-#define EMIT_LAUNCH(EB_)                                                                       \
-    do {                                                                                       \
-        if (a.cams) {                                                                          \
-            if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1, true>), grid, block, 0, s, a);  \
-            else hipLaunchKernelGGL((k_emit<EB_, 2, true>), grid, block, 0, s, a);                 \
-        } else {                                                                               \
-            if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1, false>), grid, block, 0, s, a); \
-            else hipLaunchKernelGGL((k_emit<EB_, 2, false>), grid, block, 0, s, a);                \
-        }                                                                                      \
+#define EMIT_LAUNCH_S(EB_, SUP_)                                                                      \
+    do {                                                                                              \
+        if (a.cams) {                                                                                 \
+            if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1, true, SUP_>), grid, block, 0, s, a);   \
+            else hipLaunchKernelGGL((k_emit<EB_, 2, true, SUP_>), grid, block, 0, s, a);                  \
+        } else {                                                                                      \
+            if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1, false, SUP_>), grid, block, 0, s, a);  \
+            else hipLaunchKernelGGL((k_emit<EB_, 2, false, SUP_>), grid, block, 0, s, a);                 \
+        }                                                                                             \
+    } while (0)
+#define EMIT_LAUNCH(EB_)                                \
+    do {                                                \
+        if (a.hit_win) EMIT_LAUNCH_S(EB_, true);        \
+        else EMIT_LAUNCH_S(EB_, false);                 \
     } while (0)
     if (T <= 4) EMIT_LAUNCH(4);
     else if (T <= 8) EMIT_LAUNCH(8);
@@ -218,5 +227,6 @@ hipError_t dh_launch_emit(const EmitArgs &a, hipStream_t s) {
     else if (T <= 12) EMIT_LAUNCH(12);
     else EMIT_LAUNCH(16);
 #undef EMIT_LAUNCH
+#undef EMIT_LAUNCH_S
     return hipGetLastError();
 }

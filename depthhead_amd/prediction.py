@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import POSE_DTYPE, check, vp
+from ._lib import POSE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, check, vp
 from .forest import Forest
 from .synth import ModelParams
 
@@ -52,6 +52,11 @@ def _stream(stream: int):
     return C.c_void_p(stream) if stream else None
 
 
+def _radius(radius) -> C.c_uint32:
+    """The support radius as the C uint32_t: a negative one wraps and is refused by the library (DH_EINVAL)."""
+    return C.c_uint32(int(radius) & 0xFFFFFFFF)
+
+
 class IntrinsicMatrix:
     """Row-major 3x3 f32 camera matrix (src/types.rs:405)."""
 
@@ -66,10 +71,13 @@ class IntrinsicMatrix:
 
 @dataclass
 class PredictionResult:
-    """prediction.rs:259-267; `bounding_box` is always Rect(0,0,0,0) in the reference (:491)."""
+    """prediction.rs:259-267; `bounding_box` is always Rect(0,0,0,0) in the reference (:491).  With a support radius
+    (`predict_parameter_parallel(..., support_radius=r)`) it is the (x, y, width, height) of the supporting windows' centre
+    pixels and `support` holds the whole SUPPORT_DTYPE record (include/depthhead_hip.h: dh_support)."""
     mid_point: np.ndarray   # float32[3], mm
     rotation: np.ndarray    # float64[3], radians
     bounding_box: tuple = (0, 0, 0, 0)
+    support: np.void | None = None
 
 
 class HoughPrediction:
@@ -143,15 +151,23 @@ class HoughPrediction:
         check(self._lib.dh_predictor_sigma(self._ph, C.byref(out)))
         return float(out.value)
 
-    def predict_parameter_parallel(self, img, intrinsic: IntrinsicMatrix, midp_guess=None, rot_guess=None) -> PredictionResult:
-        """prediction.rs:397-409: one depth frame (H x W uint16) -> head position and rotation."""
+    def predict_parameter_parallel(self, img, intrinsic: IntrinsicMatrix, midp_guess=None, rot_guess=None,
+                                   support_radius: int | None = None) -> PredictionResult:
+        """prediction.rs:397-409: one depth frame (H x W uint16) -> head position and rotation.  With `support_radius` (cells =
+        mm; `SUPPORT_RADIUS` is the default of the support calls) the result also carries the pose's vote support: its
+        bounding box and the record (`predict_batch_support`)."""
         img = np.ascontiguousarray(img, dtype=np.uint16)
         if img.ndim != 2:
             raise ValueError("img must be a 2-D uint16 depth image")
         mg = None if midp_guess is None else np.asarray(midp_guess, dtype=np.float32).reshape(1, 3)
         rg = None if rot_guess is None else np.asarray(rot_guess, dtype=np.float64).reshape(1, 3)
-        poses = self.predict_batch(img[None], intrinsic, mg, rg)
-        return PredictionResult(poses["mid_point"][0].copy(), poses["rotation"][0].copy())
+        if support_radius is None:
+            poses = self.predict_batch(img[None], intrinsic, mg, rg)
+            return PredictionResult(poses["mid_point"][0].copy(), poses["rotation"][0].copy())
+        poses, sup = self.predict_batch_support(img[None], intrinsic, support_radius, mg, rg)
+        s = sup[0].copy()
+        return PredictionResult(poses["mid_point"][0].copy(), poses["rotation"][0].copy(),
+                                (int(s["x"]), int(s["y"]), int(s["width"]), int(s["height"])), s)
 
     # the serial twin returns identical results (prediction.rs:386 vs :407)
     predict_parameter = predict_parameter_parallel
@@ -190,6 +206,54 @@ class HoughPrediction:
         check(self._lib.dh_predict_batch_cameras_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), cameras._h,
                                                         vp(midp_guess_ptr), vp(rot_guess_ptr), vp(guess_mask_ptr), vp(out_ptr),
                                                         _stream(stream)))
+
+    # ---- vote support (include/depthhead_hip.h: dh_support) --------------------------------------
+    def predict_batch_support(self, frames, intrinsic: IntrinsicMatrix, radius: int = SUPPORT_RADIUS, midp_guess=None,
+                              rot_guess=None, guess_mask=None) -> tuple[np.ndarray, np.ndarray]:
+        """`predict_batch` that also reports each pose's vote support: -> (POSE_DTYPE[n], SUPPORT_DTYPE[n]).  The poses are
+        byte-identical to `predict_batch`'s."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.ndim != 3:
+            raise ValueError("frames must be [n, H, W]")
+        n, h, w = frames.shape
+        mg, rg, gm = _guesses(n, midp_guess, rot_guess, guess_mask)
+        out = np.zeros(n, dtype=POSE_DTYPE)
+        sup = np.zeros(n, dtype=SUPPORT_DTYPE)
+        check(self._lib.dh_predict_batch_support(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic), vp(mg),
+                                                 vp(rg), vp(gm), _radius(radius), vp(out), vp(sup)))
+        return out, sup
+
+    def predict_batch_support_device(self, frames_ptr: int, n: int, w: int, h: int, intrinsic: IntrinsicMatrix, out_ptr: int,
+                                     support_ptr: int, radius: int = SUPPORT_RADIUS, midp_guess_ptr: int | None = None,
+                                     rot_guess_ptr: int | None = None, guess_mask_ptr: int | None = None, stream: int = 0) -> None:
+        """Device-resident twin of `predict_batch_support`: support records [n] dh_support at `support_ptr`.  Asynchronous."""
+        check(self._lib.dh_predict_batch_support_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h),
+                                                        _kmat(intrinsic), vp(midp_guess_ptr), vp(rot_guess_ptr), vp(guess_mask_ptr),
+                                                        _radius(radius), vp(out_ptr), vp(support_ptr), _stream(stream)))
+
+    def predict_batch_cameras_support(self, frames, cameras, radius: int = SUPPORT_RADIUS, midp_guess=None, rot_guess=None,
+                                      guess_mask=None) -> tuple[np.ndarray, np.ndarray]:
+        """`predict_batch_cameras` with each pose's vote support: -> (POSE_DTYPE[n], SUPPORT_DTYPE[n])."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.ndim != 3:
+            raise ValueError("frames must be [n, H, W]")
+        n, h, w = frames.shape
+        mg, rg, gm = _guesses(n, midp_guess, rot_guess, guess_mask)
+        out = np.zeros(n, dtype=POSE_DTYPE)
+        sup = np.zeros(n, dtype=SUPPORT_DTYPE)
+        check(self._lib.dh_predict_batch_cameras_support(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), cameras._h,
+                                                         vp(mg), vp(rg), vp(gm), _radius(radius), vp(out), vp(sup)))
+        return out, sup
+
+    def predict_batch_cameras_support_device(self, frames_ptr: int, n: int, w: int, h: int, cameras, out_ptr: int,
+                                             support_ptr: int, radius: int = SUPPORT_RADIUS, midp_guess_ptr: int | None = None,
+                                             rot_guess_ptr: int | None = None, guess_mask_ptr: int | None = None,
+                                             stream: int = 0) -> None:
+        """Device-resident twin of `predict_batch_cameras_support`.  Asynchronous."""
+        check(self._lib.dh_predict_batch_cameras_support_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h),
+                                                                cameras._h, vp(midp_guess_ptr), vp(rot_guess_ptr),
+                                                                vp(guess_mask_ptr), _radius(radius), vp(out_ptr), vp(support_ptr),
+                                                                _stream(stream)))
 
     @staticmethod
     def _payload_arrays(payloads):

@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import POSE_DTYPE, check, vp
+from ._lib import POSE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, check, vp
+from .prediction import _radius
 
 TRACK_PREV_GUESS = 1   # DH_TRACK_PREV_GUESS: live_prediction --prevguess
 TRACK_SLUGGISH = 2     # DH_TRACK_SLUGGISH:   live_prediction --sluggish
@@ -88,6 +89,26 @@ class HeadTracker:
         """Device frames [n_cams][h][w] u16, poses [n_cams] dh_pose, present [n_cams] u8 or 0; asynchronous on `stream`."""
         check(self._lib.dh_tracker_step_device(self.hp._ph, self._h, vp(frames_ptr), C.c_int(self.w), C.c_int(self.h),
                                                vp(present_ptr or None), vp(out_ptr), _stream(stream)))
+
+    def step_support(self, frames, present=None, radius: int = SUPPORT_RADIUS) -> tuple[np.ndarray, np.ndarray]:
+        """`step` that also reports every camera's vote support (absent cameras included): -> (POSE_DTYPE[n_cams],
+        SUPPORT_DTYPE[n_cams]).  The state is updated exactly as by `step`."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.shape != (self.n, self.h, self.w):
+            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
+        pr = self._present(present)
+        out = np.zeros(self.n, dtype=POSE_DTYPE)
+        sup = np.zeros(self.n, dtype=SUPPORT_DTYPE)
+        check(self._lib.dh_tracker_step_support(self.hp._ph, self._h, vp(frames), C.c_int(self.w), C.c_int(self.h), vp(pr),
+                                                _radius(radius), vp(out), vp(sup)))
+        return out, sup
+
+    def step_support_device(self, frames_ptr: int, out_ptr: int, support_ptr: int, present_ptr: int = 0,
+                            radius: int = SUPPORT_RADIUS, stream: int = 0) -> None:
+        """Device-resident twin of `step_support`: support records [n_cams] dh_support at `support_ptr`.  Asynchronous."""
+        check(self._lib.dh_tracker_step_support_device(self.hp._ph, self._h, vp(frames_ptr), C.c_int(self.w), C.c_int(self.h),
+                                                       vp(present_ptr or None), _radius(radius), vp(out_ptr),
+                                                       vp(support_ptr), _stream(stream)))
 
     def capture(self, frames_ptr: int, out_ptr: int, present_ptr: int = 0) -> None:
         """Capture one device step into the predictor's graph slot; every `hp.graph_launch()` is then one step."""

@@ -89,7 +89,8 @@ typedef struct dh_params {
 } dh_params;
 
 /* `PredictionResult` (prediction.rs:259-267).  bounding_box is always Rect(0,0,0,0) there
- * (:491) and is not carried.  36 payload bytes; `reserved` fills the natural padding and is 0. */
+ * (:491) and is not carried here: the *_support calls report it in a dh_support record.  36 payload
+ * bytes; `reserved` fills the natural padding and is 0. */
 typedef struct dh_pose {
     float    mid_point[3]; /* mm, camera space, integer-valued          */
     uint32_t reserved;
@@ -264,6 +265,51 @@ int dh_tracker_state(dh_tracker *t, float *midp, double *rot, uint8_t *flags);
 /* capture one dh_tracker_step_device (device pointers) into the predictor's graph slot; replay with dh_graph_launch.  Each
  * replay is one step.  Like a captured batch it is refused (DH_ESTATE) once the workspace has been reallocated. */
 int dh_tracker_capture(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out);
+
+/* ---- vote support of each pose: head bounding box and confidence ----
+ * Not in the reference, which computes none of it.  For frame f with final midpoint cell m = (int)mid_point and a radius r
+ * (cells = mm), the frame's POSITION VOTES are exactly the votes the reference adds to its midpoint accumulator
+ * (prediction.rs:590-667): windows past the 0.7 gate, leaves with prob > 0 whose offsets pass the covariance gate, every
+ * offset o with p3 - o not negative in z, in cell c = (int)(p3 - o).  A vote SUPPORTS the pose when max_k |c_k - m_k| <= r
+ * (evaluated in 64 bits).  Per frame:
+ *   x, y, width, height  the Rect (types.rs:33-61) spanned by the CENTRE pixels (prediction.rs:544-552) of the windows with at
+ *                        least one supporting vote: x = min cx, width = max cx - min cx + 1.  All 0 when nothing supports,
+ *                        i.e. the reference's Rect(0,0,0,0).  The union of those windows' patch rectangles is this box
+ *                        grown by subimage_width / 2 and subimage_height / 2 on every side.
+ *   windows              distinct windows with at least one supporting vote
+ *   hits                 (window, tree) pairs with at least one supporting vote
+ *   mass                 sum of valtoadd over the supporting votes (exact, 64 bits)
+ *   total_mass           the same sum over all position votes of the frame; mass / total_mass is the pose's confidence
+ * Integer throughout: the record is bit-identical run to run.  The poses of these calls are byte-identical to those of the
+ * plain calls.  `support` has one record per frame (host memory for the host calls, device memory for the _device calls).
+ * radius: at most 2^31 - 1 (DH_EINVAL otherwise, e.g. a negative int passed).  The first support call of a workspace
+ * allocates its scratch (4 bytes per (window, tree) pair and frame); after that the _device calls allocate nothing and do
+ * not synchronise.  The plain entry points are unaffected: they launch exactly the kernels they launch without it. */
+#define DH_SUPPORT_RADIUS 30   /* chosen by measurement: DESIGN.md section 13 */
+typedef struct dh_support {
+    uint32_t x, y, width, height;   /* Rect of the supporting windows' centre pixels */
+    uint32_t windows;
+    uint32_t hits;
+    uint64_t mass;                  /* (byte offset 24: the record has no padding) */
+    uint64_t total_mass;
+} dh_support; /* 40 bytes */
+int dh_predict_batch_support(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
+                             const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius,
+                             dh_pose *out, dh_support *support);
+int dh_predict_batch_support_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
+                                    const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius,
+                                    dh_pose *out, dh_support *support, void *stream);
+int dh_predict_batch_cameras_support(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                     const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius,
+                                     dh_pose *out, dh_support *support);
+int dh_predict_batch_cameras_support_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                            const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
+                                            uint32_t radius, dh_pose *out, dh_support *support, void *stream);
+/* one record per camera, absent ones included; the tracker's state is updated exactly as by dh_tracker_step(_device) */
+int dh_tracker_step_support(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                            uint32_t radius, dh_pose *out, dh_support *support);
+int dh_tracker_step_support_device(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                   uint32_t radius, dh_pose *out, dh_support *support, void *stream);
 
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
