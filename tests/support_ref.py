@@ -1,7 +1,7 @@
 """CPU restatement of the vote-support record (include/depthhead_hip.h: dh_support).
 
-TEST INFRASTRUCTURE ONLY.  It starts from the oracle's taps of one frame (`pyoracle.predict(..., taps=True)`: leaf_idx,
-patch_flags, mid_point) and the forest's leaf tables, and replays the position votes of the reference
+TEST INFRASTRUCTURE ONLY.  It starts from the taps of one frame (leaf_idx, patch_flags, mid_point) and the forest's leaf
+tables, and replays the position votes of the reference
 (prediction.rs:544-667) with pyref's f32 `Intrinsic.img_to_space` and `trace_of_cov`:
 
 * windows past the 0.7 gate (patch_flags == 3), in the reference's loop order (window i at centre
@@ -10,6 +10,11 @@ patch_flags, mid_point) and the forest's leaf tables, and replays the position v
 * every offset o with p3 - o not negative in z; cell c = (as_i32(p3 - o)) (DH_ZSCALEFACTOR = 1).
 
 A vote supports the pose when max_k |c_k - m_k| <= r, m = as_i32(mid_point).
+
+The taps come from either restatement of the prediction: the C oracle's (`pyoracle.predict(..., taps=True)`, `support_ref`)
+or pyref's result dicts (`replay`), so that a misreading shared by the oracle and the kernels cannot stay green.
+`hit_boxes` restates k_forest's per-leaf offset box as k_emit turns it into each hit's HitBox, and `branches` sorts the hits
+into k_support's three cases.
 """
 from __future__ import annotations
 
@@ -26,6 +31,20 @@ class LeafTables:
     def __init__(self, forest):
         self.forest = forest
         self._gate = {}
+        self._box = {}
+
+    def box(self, leaf: int):
+        """(omin, omax) f32 [3] of a leaf's offsets, as k_forest.hip builds them: +-inf in every coordinate when some offset
+        is not finite or exceeds 3e38 in magnitude."""
+        if leaf not in self._box:
+            f = self.forest
+            offs = np.asarray(f.offsets[f.off_begin[leaf]:f.off_begin[leaf + 1]], dtype=np.float32).reshape(-1, 3)
+            if not (np.abs(offs) <= np.float32(3.0e38)).all():
+                lo, hi = np.full(3, -np.inf, np.float32), np.full(3, np.inf, np.float32)
+            else:
+                lo, hi = offs.min(axis=0), offs.max(axis=0)
+            self._box[leaf] = (lo, hi)
+        return self._box[leaf]
 
     def votes(self, leaf: int):
         """(valtoadd, offsets f32 [k, 3]) of a leaf that casts position votes, else None."""
@@ -50,30 +69,35 @@ def as_i32_vec(a: np.ndarray) -> np.ndarray:
     return np.trunc(out).astype(np.int64)
 
 
-def frame_votes(tables: LeafTables, model, img, K, leaf_idx, patch_flags):
-    """All position votes of one frame: (window index [k], tree [k], cell int64 [k, 3], value [k])."""
+def _voting_hits(tables: LeafTables, model, img, K, leaf_idx, patch_flags):
+    """(window, tree, leaf, p3 f32 [3], valtoadd, offsets) of every hit record with position votes, in the reference's order."""
     img = np.asarray(img, dtype=np.uint16)
     h, w = img.shape
     nx, _ = model.patch_grid(w, h)
     lw, lh, step = int(model.subimage_width) // 2, int(model.subimage_height) // 2, int(model.stepwidth)
     intr = pyref.Intrinsic(K)
-    wins, trees, cells, vals = [], [], [], []
     for wi in np.flatnonzero(np.asarray(patch_flags) == 3):
         cx, cy = lw + (wi % nx) * step, lh + (wi // nx) * step
-        p3 = np.array(intr.img_to_space([pyref.F32(cx), pyref.F32(cy)], pyref.F32(img[cy, cx])), dtype=np.float32)
+        with np.errstate(all="ignore"):
+            p3 = np.array(intr.img_to_space([pyref.F32(cx), pyref.F32(cy)], pyref.F32(img[cy, cx])), dtype=np.float32)
         for t, leaf in enumerate(leaf_idx[wi]):
             lv = tables.votes(int(leaf))
-            if lv is None:
-                continue
-            v, offs = lv
-            with np.errstate(over="ignore", invalid="ignore"):
-                d = p3[None, :] - offs                              # f32, prediction.rs:647
-            keep = ~(d[:, 2] < 0.0)                                  # :650 (NaN z is kept, as in the reference)
-            c = as_i32_vec(d[keep])
-            wins.append(np.full(len(c), wi, dtype=np.int64))
-            trees.append(np.full(len(c), t, dtype=np.int64))
-            cells.append(c)
-            vals.append(np.full(len(c), v, dtype=np.uint64))
+            if lv is not None:
+                yield int(wi), t, int(leaf), p3, lv[0], lv[1]
+
+
+def frame_votes(tables: LeafTables, model, img, K, leaf_idx, patch_flags):
+    """All position votes of one frame: (window index [k], tree [k], cell int64 [k, 3], value [k])."""
+    wins, trees, cells, vals = [], [], [], []
+    for wi, t, _, p3, v, offs in _voting_hits(tables, model, img, K, leaf_idx, patch_flags):
+        with np.errstate(over="ignore", invalid="ignore"):
+            d = p3[None, :] - offs                              # f32, prediction.rs:647
+        keep = ~(d[:, 2] < 0.0)                                  # :650 (NaN z is kept, as in the reference)
+        c = as_i32_vec(d[keep])
+        wins.append(np.full(len(c), wi, dtype=np.int64))
+        trees.append(np.full(len(c), t, dtype=np.int64))
+        cells.append(c)
+        vals.append(np.full(len(c), v, dtype=np.uint64))
     if not cells:
         e = np.zeros(0, dtype=np.int64)
         return e, e, np.zeros((0, 3), dtype=np.int64), np.zeros(0, dtype=np.uint64)
@@ -98,13 +122,47 @@ def support_from_votes(votes, mid_point, radius: int, model, w: int, h: int) -> 
     return rec
 
 
+def replay(tables: LeafTables, model, img, K, leaf_idx, patch_flags, mid_point, radii):
+    """The dh_support records (dicts) of one frame at each radius of `radii`, and its votes, from any source of taps."""
+    img = np.asarray(img, dtype=np.uint16)
+    h, w = img.shape
+    votes = frame_votes(tables, model, img, K, leaf_idx, patch_flags)
+    return [support_from_votes(votes, mid_point, r, model, w, h) for r in radii], votes
+
+
 def support_ref(oracle, tables: LeafTables, model, img, K, radius: int, midp_guess=None, rot_guess=None):
-    """(oracle result, dh_support record as a dict, the frame's votes) of one frame."""
+    """(oracle result, dh_support record as a dict, the frame's votes) of one frame, replayed from the oracle's taps."""
     img = np.asarray(img, dtype=np.uint16)
     res = oracle.predict(tables.forest, model, img, K, midp_guess, rot_guess, taps=True)
-    votes = frame_votes(tables, model, img, K, res.leaf_idx, res.patch_flags)
-    h, w = img.shape
-    return res, support_from_votes(votes, res.mid_point, radius, model, w, h), votes
+    (rec,), votes = replay(tables, model, img, K, res.leaf_idx, res.patch_flags, res.mid_point, [radius])
+    return res, rec, votes
+
+
+def hit_boxes(tables: LeafTables, model, img, K, leaf_idx, patch_flags):
+    """HitBox of every hit record with position votes (k_emit.hip): lo, hi int64 [k, 3] = as_i32(p3 - omax), as_i32(p3 - omin),
+    differences in f32, the box of a leaf with a non-finite offset unbounded (LeafTables.box)."""
+    lo, hi = [], []
+    for _, _, leaf, p3, _, _ in _voting_hits(tables, model, img, K, leaf_idx, patch_flags):
+        omin, omax = tables.box(leaf)
+        with np.errstate(over="ignore", invalid="ignore"):
+            lo.append(as_i32_vec(p3 - omax))
+            hi.append(as_i32_vec(p3 - omin))
+    if not lo:
+        return np.zeros((0, 3), np.int64), np.zeros((0, 3), np.int64)
+    return np.stack(lo), np.stack(hi)
+
+
+BRANCHES = ("skip", "walk_miss", "meets")
+
+
+def branches(boxes, mid_point, radius: int) -> dict:
+    """Hits per case of k_support: the box misses the cube m +- r with lo.z >= 1 (counted without a read), misses with
+    lo.z < 1 (offsets walked for total_mass), meets the cube (offsets walked for both sums)."""
+    lo, hi = boxes
+    m = as_i32_vec(np.asarray(mid_point, dtype=np.float32))
+    meets = np.all(lo <= m + int(radius), axis=1) & np.all(hi >= m - int(radius), axis=1)
+    return {"skip": int(np.sum(~meets & (lo[:, 2] >= 1))), "walk_miss": int(np.sum(~meets & (lo[:, 2] < 1))),
+            "meets": int(np.sum(meets))}
 
 
 def as_record(rec: dict, dtype) -> np.ndarray:
