@@ -1859,6 +1859,7 @@ static int trainer_add_frames_(dh_trainer *t, const uint16_t *frames, const uint
     if (!frames || !masks || !K || !pos3d || !rot_deg) return fail(DH_EINVAL, "dh_trainer_add_frames: NULL argument");
     TrainGeom g;
     TRY(dh_train_geom_(t->p, w, h, g));
+    TRY(dh_train_check_rotations_(rot_deg, n));
     if ((uint64_t)g.nx * g.ny > 0xffffffffull) return fail(DH_ESIZE, "too many windows per frame");
     DeviceGuard guard(t->device);
     if (!guard.ok) return DH_EHIP;

@@ -42,6 +42,13 @@ static inline int32_t rot_bin_host(double deg) {
     return (int32_t)((uint32_t)r + 60u);
 }
 
+bool dh_rot_vote_ok_(double deg) {
+    int32_t r = rot_bin_host(deg);
+    if (r >= DH_ROT_GRID_PARTS) r -= DH_ROT_GRID_PARTS;
+    else if (r < 0) r += DH_ROT_GRID_PARTS;
+    return r >= 0 && r < DH_ROT_GRID_PARTS;
+}
+
 int dh_forest_build_(const dh_forest_desc *d, dh_forest **out) {
     if (!d || !out) return dh_fail_(DH_EINVAL, "dh_forest_create: NULL argument");
     *out = nullptr;
@@ -122,12 +129,9 @@ int dh_forest_build_(const dh_forest_desc *d, dh_forest **out) {
         if (f->off_begin[L + 1] == f->off_begin[L]) return dh_fail_(DH_EFOREST, "leaf %u: prob > 0 but no offsets (reference divides by zero)", L);
         if (f->rot_begin[L + 1] == f->rot_begin[L]) return dh_fail_(DH_EFOREST, "leaf %u: prob > 0 but no rotations (reference unwraps None)", L);
         for (uint32_t i = f->rot_begin[L]; i < f->rot_begin[L + 1]; ++i)
-            for (int k = 0; k < 3; ++k) {
-                int32_t r = rot_bin_host(f->rotations[(size_t)i * 3 + k]);
-                if (r >= DH_ROT_GRID_PARTS) r -= DH_ROT_GRID_PARTS;
-                else if (r < 0) r += DH_ROT_GRID_PARTS;
-                if (r < 0 || r >= DH_ROT_GRID_PARTS) return dh_fail_(DH_EFOREST, "leaf %u: rotation bin outside [0,120) after one wrap (reference indexes out of bounds)", L);
-            }
+            for (int k = 0; k < 3; ++k)
+                if (!dh_rot_vote_ok_(f->rotations[(size_t)i * 3 + k]))
+                    return dh_fail_(DH_EFOREST, "leaf %u: rotation bin outside [0,120) after one wrap (reference indexes out of bounds)", L);
     }
     own.f = nullptr;
     *out = f;

@@ -51,6 +51,10 @@ struct dh_forest {
 };
 // Body of dh_forest_create: copies and validates (header comment of dh_forest_create lists what is refused).
 int dh_forest_build_(const dh_forest_desc *d, dh_forest **out);
+// A rotation vote (degrees) a forest can hold: its bin (deg * 120 / 360) as i32 + 60 lies in [0, 120) after one wrap
+// (prediction.rs:605-613), which takes -543 < deg < 540; NaN falls in bin 60.  dh_forest_build_ refuses a voting leaf
+// with any other rotation, so the trainer refuses such truth when frames are added (dh_train_check_rotations_).
+bool dh_rot_vote_ok_(double deg);
 
 // The offset votes once more as (x, y, z, 0) records, every leaf's run padded to a multiple of 4 records (64 bytes):
 // b4[l] = index of leaf l's first record, o4 = 4 floats per record (+ 4 records of slack).

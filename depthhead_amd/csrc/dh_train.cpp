@@ -40,6 +40,14 @@ int dh_train_geom_(const dh_train_params &p, int w, int h, TrainGeom &g) {
     return DH_OK;
 }
 
+int dh_train_check_rotations_(const float *rot_deg, int n) {
+    for (size_t i = 0; i < (size_t)n * 3; ++i)
+        if (!dh_rot_vote_ok_((double)rot_deg[i]))
+            return dh_fail_(DH_EINVAL, "frame %zu: rot_deg[%zu] = %g degrees is outside what a forest can hold (-543 < deg < 540 or NaN)",
+                            i / 3, i % 3, (double)rot_deg[i]);
+    return DH_OK;
+}
+
 int dh_train_chunk_frames_(int w, int h) {
     const size_t per = (size_t)w * h * 3 + (size_t)(w + 1) * (h + 1) * 4;   // frame + mask + summed-area table
     return (int)std::max<size_t>(1, std::min<size_t>(256, (256u << 20) / per));

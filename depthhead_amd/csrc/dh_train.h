@@ -59,6 +59,9 @@ struct TrainGeom {
     uint32_t bw = 0, bh = 0;                   // rectangle-sum image of a sample: (W - rw + 1) x (H - rh + 1), 0 x 0 for empty rectangles
 };
 int dh_train_geom_(const dh_train_params &p, int w, int h, TrainGeom &g);   // DH_ESIZE for frames smaller than the patch
+// Truth a forest can hold: every rot_deg of the n frames passes dh_rot_vote_ok_ (widened to f64, as the pool stores it);
+// otherwise DH_EINVAL before anything is uploaded (the fit's forest would fail dh_forest_build_ after all the work).
+int dh_train_check_rotations_(const float *rot_deg, int n);
 // Frames per upload chunk for frames of w x h (a chunk's frames, masks and summed-area tables stay below ~256 MB).
 int dh_train_chunk_frames_(int w, int h);
 

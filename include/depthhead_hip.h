@@ -361,7 +361,8 @@ int dh_trainer_destroy(dh_trainer *t);
 /* Sample extraction of learn (prediction.rs:145-215) for n frames (row-major u16 depth, u8 mask, index y*w+x); K: [n][9]
  * row-major intrinsics, pos3d [n][3] mm, rot_deg [n][3] degrees.  Frames are uploaded in chunks and windowed on the device;
  * only the kept samples stay resident.  The pool does not depend on how frames are split across calls.  Frames smaller
- * than the patch: DH_ESIZE. */
+ * than the patch: DH_ESIZE.  A rot_deg a forest cannot hold as a vote (+-inf, or outside -543 < deg < 540; NaN is held):
+ * DH_EINVAL, with nothing added.  Non-finite pos3d or offsets (e.g. a K whose third row gives r[2] = 0) are kept. */
 int dh_trainer_add_frames(dh_trainer *t, const uint16_t *frames, const uint8_t *masks, int n, int w, int h, const float *K,
                           const float *pos3d, const float *rot_deg);
 /* Grow n_trees trees on the device from the pool; *out is an ordinary forest (validated like dh_forest_create; child_one

@@ -2,6 +2,7 @@
 // geometry, chunk sizes, the keyed subset draws, early_stop / partition / comp_leaf_data bookkeeping and the assembly of
 // the forest) under the CPU sanitizers: built by tests/test_train_host.py with g++ -fsanitize=address,undefined and once
 // more with -fsanitize=thread (several growers on several threads).  Prints "train_check ok" and exits 0.
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -48,6 +49,19 @@ static void validation() {
     for (uint32_t x = 40; x < 203u - 41u; x += 7) nx++;
     CHECK(g.nx == nx);
     for (int w : {80, 320, 640, 4096}) CHECK(dh_train_chunk_frames_(w, w) >= 1 && dh_train_chunk_frames_(w, w) <= 256);
+    // the chunk boundaries the training families cross (tests/train_ref/train_families.py): 257 frames of 48 x 40 are
+    // chunks of 256 + 1, 32 frames of 1280 x 960 chunks of 31 + 1
+    CHECK(dh_train_chunk_frames_(48, 40) == 256);
+    CHECK(dh_train_chunk_frames_(640, 480) == 124);
+    CHECK(dh_train_chunk_frames_(1280, 960) == 31);
+    p = base(); p.subimage_width = 198; p.subimage_height = 331; CHECK(dh_train_validate_(&p) == DH_ESIZE);   // 65 538 pixels
+    // truth a forest can hold: rotation bins in [0, 120) after one wrap, -543 < deg < 540, NaN in bin 60
+    for (float d : {0.f, 539.75f, -542.75f, NAN}) CHECK(dh_rot_vote_ok_(d));
+    for (float d : {540.f, -543.f, INFINITY, -INFINITY, 1e30f}) CHECK(!dh_rot_vote_ok_(d));
+    const float rots[6] = {10.f, -20.f, NAN, 1.f, 2.f, 3.f};
+    CHECK(dh_train_check_rotations_(rots, 2) == DH_OK);
+    const float bad[6] = {10.f, -20.f, 30.f, 1.f, -INFINITY, 3.f};
+    CHECK(dh_train_check_rotations_(bad, 1) == DH_OK && dh_train_check_rotations_(bad, 2) == DH_EINVAL);
 }
 
 // A random pool and random device answers: the grower's bookkeeping must keep every sample, partition stably and

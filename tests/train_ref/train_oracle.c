@@ -385,12 +385,21 @@ int to_pool_set(size_t n, const uint8_t *lab, const float *off, const double *ro
  * subset draws, partitioned by the forest's own splits), regenerates the node's candidates and checks that
  *   - early_stop holds: a node the rules stop is a leaf, one they do not stop is split unless no candidate is valid;
  *   - a split is bitwise one of the node's valid candidates and its score is <= min + 1e-12 * max(1, |min|);
- *   - a leaf is bitwise comp_leaf_data (prob, offsets, rotations, order);
+ *   - a leaf is bitwise comp_leaf_data (prob, offsets, rotations, order; a NaN vote matches any NaN);
  * and accumulates the negative-det count over every valid candidate of every searched node (comparable with the
  * trainer's count when all trees are walked).  *gap = smallest best / second-best distinct score gap over split nodes;
  * visited[0..1] = split nodes / leaves reached.  Returns 0, or -1 with a message in msg. */
 #include <stdio.h>
 typedef struct { int32_t ref; uint32_t heap; uint32_t *set; size_t n; } VE;
+/* A leaf vote against its sample: bitwise, except that a NaN matches any NaN (NaN bit patterns are not part of the
+ * contract: the device and this oracle need not produce the same NaN from 0 / 0 or inf * 0). */
+static int same_vote(const float *o, const float *so, const double *r, const double *sr) {
+    for (int k = 0; k < 3; ++k) {
+        if (isnan(o[k]) ? !isnan(so[k]) : memcmp(&o[k], &so[k], 4) != 0) return 0;
+        if (isnan(r[k]) ? !isnan(sr[k]) : memcmp(&r[k], &sr[k], 8) != 0) return 0;
+    }
+    return 1;
+}
 int to_verify(const TOParams *p, const int32_t *roots, const TONode *nodes, uint32_t n_nodes, const double *prob, const uint32_t *ob,
               const uint32_t *rb, uint32_t n_leaves, const float *offs, const double *rots, uint32_t tree_begin, uint32_t tree_end,
               double *gap, uint64_t *neg_det, uint32_t *visited, char *msg, size_t msgn) {
@@ -452,7 +461,7 @@ int to_verify(const TOParams *p, const int32_t *roots, const TONode *nodes, uint
                 for (size_t i = 0; i < e.n && rc == 0; ++i) {
                     const uint32_t s = e.set[i];
                     if (!g_lab[s]) continue;
-                    if (memcmp(&offs[(size_t)(ob[L] + v) * 3], &g_off[(size_t)s * 3], 12) || memcmp(&rots[(size_t)(rb[L] + v) * 3], &g_rot[(size_t)s * 3], 24)) {
+                    if (!same_vote(&offs[(size_t)(ob[L] + v) * 3], &g_off[(size_t)s * 3], &rots[(size_t)(rb[L] + v) * 3], &g_rot[(size_t)s * 3])) {
                         rc = -1;
                         snprintf(msg, msgn, "tree %u heap %u: leaf %u vote %zu differs from its positive sample %u", t, e.heap, L, v, s);
                     }

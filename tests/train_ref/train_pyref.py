@@ -39,6 +39,7 @@ class Trainer:
         self.p = p
         self.frames = 0
         self.patches, self.lab, self.off, self.rot = [], [], [], []
+        self.where = []   # (frame index over every frame added, x, y) of each sample's window centre
 
     def add(self, frames, masks, K, pos3d, rot_deg):
         p = self.p
@@ -76,6 +77,7 @@ class Trainer:
                     self.lab.append(c)
                     self.off.append([float(o) for o in off])
                     self.rot.append(rot)
+                    self.where.append((self.frames + f, x, y))
         self.frames += n
 
     def fit(self):

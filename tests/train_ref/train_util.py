@@ -136,3 +136,47 @@ def oracle_verify(p, f: Forest, trees=None):
     if trees is None:
         assert visited[0] == f.n_nodes and visited[1] == f.n_leaves, (visited, f.n_nodes, f.n_leaves)
     return gap.value, neg.value, int(visited[0]), int(visited[1])
+
+
+def _votes_equal_nan(x: np.ndarray, y: np.ndarray) -> bool:
+    """Bitwise equal, except that a NaN matches any NaN at the same position."""
+    if x.shape != y.shape or x.dtype != y.dtype:
+        return False
+    nx, ny = np.isnan(x), np.isnan(y)
+    if not np.array_equal(nx, ny):
+        return False
+    u = np.uint32 if x.dtype == np.float32 else np.uint64
+    return np.array_equal(x.view(u)[~nx], y.view(u)[~ny])
+
+
+def forest_equal_nan(a: Forest, b: Forest) -> bool:
+    """forest_equal with NaN-tolerant votes: the structure (roots, nodes, leaf probabilities, vote ranges) byte for byte,
+    offsets and rotations bitwise except that NaN matches NaN (NaN bits are not part of the contract)."""
+    return (np.array_equal(a.roots, b.roots) and a.nodes.tobytes() == b.nodes.tobytes()
+            and a.leaf_prob.tobytes() == b.leaf_prob.tobytes() and np.array_equal(a.off_begin, b.off_begin)
+            and np.array_equal(a.rot_begin, b.rot_begin) and _votes_equal_nan(a.offsets, b.offsets)
+            and _votes_equal_nan(a.rotations, b.rotations))
+
+
+def raw_add_frames(tr, frames, masks, K, p3, rd) -> int:
+    """dh_trainer_add_frames on a training.Trainer with the arrays exactly as given (masks are not normalised to 0 / 1);
+    -> the return code."""
+    from depthhead_amd._lib import vp
+    n, h, w = frames.shape
+    arrs = (frames, masks, K, p3, rd)
+    for a, dt, shape in zip(arrs, (np.uint16, np.uint8, np.float32, np.float32, np.float32),
+                            ((n, h, w), (n, h, w), (n, 9), (n, 3), (n, 3))):
+        assert a.dtype == dt and a.shape == shape and a.flags.c_contiguous, (a.dtype, a.shape)
+    return tr._lib.dh_trainer_add_frames(tr._h, vp(frames), vp(masks), n, w, h, vp(K), vp(p3), vp(rd))
+
+
+def oracle_run(p, calls):
+    """Feed `calls` ((frames, masks, K, pos3d, rot_deg) each, masks as given) to a fresh oracle pool and fit it.
+    -> (pool sizes after each call, Forest, margin, neg_det); the oracle keeps the pool (for oracle_verify)."""
+    oracle().to_reset()
+    sizes = []
+    for ch in calls:
+        assert oracle_add(p, *ch) == 0
+        sizes.append(int(oracle().to_pool_size()))
+    f, margin, neg = oracle_fit(p)
+    return sizes, f, margin, neg
