@@ -24,6 +24,11 @@ SUPPORT_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4"), ("width", "<u4"), ("height
                           ("mass", "<u8"), ("total_mass", "<u8")], align=True)
 assert SUPPORT_DTYPE.itemsize == 40
 SUPPORT_RADIUS = 30   # DH_SUPPORT_RADIUS
+# dh_head: one detected head of a frame (dh_predict_heads*): its pose and its vote support
+HEAD_DTYPE = np.dtype([("pose", POSE_DTYPE), ("support", SUPPORT_DTYPE)], align=True)
+assert HEAD_DTYPE.itemsize == 80 and HEAD_DTYPE.fields["support"][1] == 40
+MAX_HEADS = 4          # DH_MAX_HEADS
+HEADS_SUPPRESS = 2     # DH_HEADS_SUPPRESS (guess-grid cells)
 
 
 class ForestDesc(C.Structure):
@@ -60,6 +65,7 @@ EXPORTS = [
     "dh_tracker_state", "dh_tracker_capture",
     "dh_predict_batch_support", "dh_predict_batch_support_device", "dh_predict_batch_cameras_support",
     "dh_predict_batch_cameras_support_device", "dh_tracker_step_support", "dh_tracker_step_support_device",
+    "dh_predict_heads", "dh_predict_heads_device", "dh_predict_heads_cameras", "dh_predict_heads_cameras_device",
 ]
 
 

@@ -187,6 +187,19 @@ struct Workspace {
     Buf<uint32_t> sup_bits;            // [cap][sup_words] window bitmaps, zero between calls
     uint32_t sup_words = 0;
     Buf<dh_support> sup;               // [cap] host entry points: the support records of a slice on the device
+    // several heads per frame (k_heads.hip), allocated by the first heads call of this workspace (heads_reserve) beside the support
+    // scratch, and like it read by nothing else; the arrays marked "zero" are zero between calls (their readers clear them)
+    Buf<int32_t> hd_pick;              // [cap][DH_MAX_HEADS] seed cells
+    Buf<uint32_t> hd_nseed;            // [cap]
+    Buf<HdMom> hd_mom;                 // [cap][DH_MAX_HEADS] zero
+    Buf<dh_pose> hd_pose;              // [cap][DH_MAX_HEADS]
+    Buf<SupAcc> hd_acc;                // [cap][DH_MAX_HEADS] zero
+    Buf<uint32_t> hd_bits;             // [cap][DH_MAX_HEADS][sup_words] zero
+    Buf<dh_support> hd_sup;            // [cap][DH_MAX_HEADS]
+    Buf<uint8_t> hd_mask;              // [cap][hits_cap]
+    Buf<uint32_t> hd_rgrid;            // [cap][DH_MAX_HEADS][8000] zero
+    Buf<dh_head> hd_out;               // [cap][DH_MAX_HEADS] host entry points: the heads of a slice on the device
+    Buf<uint32_t> hd_n;                // [cap] host entry points
 
     // frame f0's entries of the counter block (CounterLayout, dh_host.h)
     uint32_t *hit_count(int f0) const { return counters.get() + lay.hit_count + f0; }
@@ -612,6 +625,9 @@ struct EnqueueOpts {
     bool zero_fold = false;         // k_boxsum zeroes the counters: no fill of their own
     dh_support *support = nullptr;  // non-NULL: k_emit's SUP instance, then k_support after k_cluster (indexed like `out`)
     uint32_t radius = 0;
+    dh_head *heads = nullptr;       // non-NULL: k_emit's SUP instance, then the heads kernels in place of k_region / k_cluster (DESIGN.md
+    uint32_t *n_heads = nullptr;    // section 14); heads [n][max_heads], n_heads [n] of this range, `out` unused
+    int max_heads = 0;
 };
 
 // Enqueue the kernels (k_boxsum / k_pixflags, k_traverse, k_emit, k_vote, [k_region,] k_cluster) for frames [f0, f0 + n) of the batch on stream s.
@@ -733,10 +749,11 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
             ea.win_count = win_count; ea.win_patch = ta.win_patch; ea.win_leaf = ta.win_leaf; ea.leaf_ls = ws.leaf_ls; ea.win_cap = g.win_cap;
             ea.hits = ws.hits.get() + hoff; ea.hit_box = ws.hit_box.get() + hoff; ea.hit_rot = ws.hit_rot.get() + hoff;
             ea.hit_count = hit_count; ea.hits_cap = ws.hits_cap;
-            ea.leaf_hits = leaf_hits;
+            // (a heads batch keeps every hit's rotation record: its rotation votes are restricted per head, hit by hit)
+            ea.leaf_hits = o.heads ? nullptr : leaf_hits;
             ea.gen = gen;
             ea.dbg_flags = ta.dbg_flags;
-            if (o.support) ea.hit_win = ws.hit_win.get() + hoff;
+            if (o.support || o.heads) ea.hit_win = ws.hit_win.get() + hoff;
 #ifdef DH_PROFILING_KNOBS
             ea.stop = p->knobs.emit_stop;
 #endif
@@ -754,13 +771,54 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         va.f = p->dev; va.hits = ws.hits.get() + hoff; va.hit_box = ws.hit_box.get() + hoff; va.hit_rot = ws.hit_rot.get() + hoff;
         va.hit_count = hit_count; va.hits_cap = ws.hits_cap;
         va.pos_grid = pos_grid; va.rot_grid = rot_grid;
-        va.leaf_hits = leaf_hits;
+        va.leaf_hits = o.heads ? nullptr : leaf_hits;
 #ifdef DH_PROFILING_KNOBS
         va.stop = p->knobs.vote_stop;
 #endif
         { Range r(o.profile, "dh:vote"); HIP_TRY(dh_launch_vote(va, s)); }
     }
     if (o.profile) HIP_TRY(hipEventRecord(p->ev[2], s));
+    if (o.heads) {
+        // several heads per frame: seeds, their moments, position mean shifts, support (+ head masks and rotation grids), rotation
+        // mean shifts, merge (k_heads.hip)
+        HeadsArgs ha{};
+        ha.n_frames = n; ha.w = w; ha.h = h; ha.max_heads = o.max_heads;
+        memcpy(ha.k, K, sizeof ha.k);
+        ha.cams = cs.dev();
+        ha.off4 = p->dev.off4; ha.rough_cell = p->dev.rough_cell;
+        ha.hits = ws.hits.get() + hoff; ha.hit_box = ws.hit_box.get() + hoff; ha.hit_rot = ws.hit_rot.get() + hoff; ha.hit_win = ws.hit_win.get() + hoff;
+        ha.hit_count = hit_count; ha.hits_cap = ws.hits_cap;
+        ha.pos_grid = pos_grid;
+        const size_t hk = (size_t)f0 * DH_MAX_HEADS;
+        ha.pick = ws.hd_pick.get() + hk; ha.nseed = ws.hd_nseed.get() + f0; ha.mom = ws.hd_mom.get() + hk;
+        ha.nx = g.nx; ha.step = (int)p->params.stepwidth;
+        ha.lw = (int)p->params.subimage_width / 2; ha.lh = (int)p->params.subimage_height / 2;
+        ha.radius = o.radius;
+        ha.hpose = ws.hd_pose.get() + hk; ha.acc = ws.hd_acc.get() + hk; ha.bits = ws.hd_bits.get() + hk * ws.sup_words; ha.bit_words = ws.sup_words;
+        ha.hsup = ws.hd_sup.get() + hk; ha.hmask = ws.hd_mask.get() + hoff; ha.rgrid = ws.hd_rgrid.get() + hk * DH_GRID3;
+        ha.n_heads = o.n_heads + f0; ha.heads = o.heads + (size_t)f0 * o.max_heads;
+        ClusterArgs ca{};
+        ca.frames = fr; ca.n_frames = n; ca.w = w; ca.h = h;
+        memcpy(ca.kinv, kinv, 9 * sizeof(float));
+        ca.cams = cs.dev();
+        ca.f = p->dev; ca.hits = ha.hits; ca.hit_box = ha.hit_box; ca.hit_rot = ha.hit_rot;
+        ca.hit_count = hit_count; ca.hits_cap = ws.hits_cap;
+        ca.pos_grid = pos_grid; ca.rot_grid = ha.rgrid; ca.kern_r2 = p->kern_r2.get();
+        ca.iterations = p->params.meanshift_iterations;
+        ca.out = ws.hd_pose.get() + hk;
+        ca.hd_nseed = ha.nseed; ca.hd_mom = ha.mom; ca.hd_rgrid = ha.rgrid; ca.hd_mask = ha.hmask;
+        Range r(o.profile, "dh:heads");
+        HIP_TRY(dh_launch_heads_seeds(ha, s));
+        HIP_TRY(dh_launch_heads_moments(ha, s));
+        ca.hd_which = 0;
+        HIP_TRY(dh_launch_cluster_heads(ca, o.max_heads, s));
+        HIP_TRY(dh_launch_heads_support(ha, s));
+        ca.hd_which = 1;
+        HIP_TRY(dh_launch_cluster_heads(ca, o.max_heads, s));
+        HIP_TRY(dh_launch_heads_finish(ha, s));
+        if (o.profile) { HIP_TRY(hipEventRecord(p->ev[3], s)); p->ev_valid = true; }
+        return DH_OK;
+    }
     {
         ClusterArgs ca{};
         ca.frames = fr; ca.n_frames = n; ca.w = w; ca.h = h;
@@ -851,16 +909,52 @@ static int support_reserve(dh_predictor *p) {
     return DH_OK;
 }
 
+// Heads of a batch (the dh_predict_heads* entry points): n_heads [n], heads [n][max_heads].
+struct HeadsOut {
+    dh_head *heads = nullptr;
+    uint32_t *n_heads = nullptr;
+    int max_heads = 0;
+    uint32_t radius = 0;
+};
+
+// The heads scratch of the current workspace (Workspace::hd_*, and the support scratch it shares: k_emit's hit windows), allocated
+// and zeroed on the first heads call that needs it; a no-op after that.  Nothing a captured batch points to is touched.
+static int heads_reserve(dh_predictor *p) {
+    TRY(support_reserve(p));
+    Workspace &ws = p->ws;
+    if (ws.hd_n) return DH_OK;          // (allocated last: its presence means the others are there and zeroed)
+    const size_t cap = (size_t)ws.cap_frames, ch = cap * DH_MAX_HEADS;
+    TRY(ws.hd_pick.alloc(ch));
+    TRY(ws.hd_nseed.alloc(cap));
+    TRY(ws.hd_mom.alloc(ch));
+    TRY(ws.hd_pose.alloc(ch));
+    TRY(ws.hd_acc.alloc(ch));
+    TRY(ws.hd_bits.alloc(ch * ws.sup_words));
+    TRY(ws.hd_sup.alloc(ch));
+    TRY(ws.hd_mask.alloc(cap * ws.hits_cap));
+    TRY(ws.hd_rgrid.alloc(ch * DH_GRID3));
+    TRY(ws.hd_out.alloc(ch));
+    if (hipMemsetAsync(ws.hd_mom.get(), 0, ch * sizeof(HdMom), p->own_stream) != hipSuccess ||
+        hipMemsetAsync(ws.hd_acc.get(), 0, ch * sizeof(SupAcc), p->own_stream) != hipSuccess ||
+        hipMemsetAsync(ws.hd_bits.get(), 0, ch * ws.sup_words * sizeof(uint32_t), p->own_stream) != hipSuccess ||
+        hipMemsetAsync(ws.hd_rgrid.get(), 0, ch * DH_GRID3 * sizeof(uint32_t), p->own_stream) != hipSuccess ||
+        hipStreamSynchronize(p->own_stream) != hipSuccess)
+        return fail(DH_EHIP, "zero-fill of the heads scratch");
+    TRY(ws.hd_n.alloc(cap));
+    return DH_OK;
+}
+
 // The device batch behind dh_predict_batch_device and the camera / tracker calls (arguments checked, device selected): one K
 // (cams.c == NULL) or frame i -> camera cams.c0 + i.  Slices and forked sub-batches offset the camera as they offset guesses.
 // With `sup`, every slice and sub-batch also reports its frames' vote support (k_support) into sup->rec, offset like `out`.
 static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const CamSel &cams,
                         const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out, hipStream_t s,
-                        const SupOut *sup = nullptr) {
+                        const SupOut *sup = nullptr, const HeadsOut *hd = nullptr) {
     const int slice = p->debug ? n : std::min(n, max_resident_frames(p));   // the taps index the whole batch
     int rc = reserve(p, slice, w, h);
     if (rc) return rc;
     if (sup) TRY(support_reserve(p));
+    if (hd) TRY(heads_reserve(p));
     float kinv[9];
     if (cams.c) {                // (kernel-argument stand-ins: the CAM instances read the records)
         K = cams.c->host[cams.c0].k;
@@ -895,7 +989,8 @@ static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, i
             EnqueueOpts o;
             o.profile = p->profiling; o.zero_fold = fold;
             if (sup) { o.support = sup->rec + f0; o.radius = sup->radius; }
-            TRY(enqueue_range(p, fr, 0, m, w, h, K, kinv, cams.at(f0), mg, rg, gm, out + f0, s, o));
+            if (hd) { o.heads = hd->heads + (size_t)f0 * hd->max_heads; o.n_heads = hd->n_heads + f0; o.max_heads = hd->max_heads; o.radius = hd->radius; }
+            TRY(enqueue_range(p, fr, 0, m, w, h, K, kinv, cams.at(f0), mg, rg, gm, out ? out + f0 : nullptr, s, o));
         } else {
             HIP_TRY(hipEventRecord(p->ev_fork, s));
             for (int c = 0; c < chunks; ++c) {
@@ -905,7 +1000,8 @@ static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, i
                 EnqueueOpts o;
                 o.chunk = c;
                 if (sup) { o.support = sup->rec + f0; o.radius = sup->radius; }
-                TRY(enqueue_range(p, fr, c0, c1 - c0, w, h, K, kinv, cams.at(f0), mg, rg, gm, out + f0, cs, o));
+                if (hd) { o.heads = hd->heads + (size_t)f0 * hd->max_heads; o.n_heads = hd->n_heads + f0; o.max_heads = hd->max_heads; o.radius = hd->radius; }
+                TRY(enqueue_range(p, fr, c0, c1 - c0, w, h, K, kinv, cams.at(f0), mg, rg, gm, out ? out + f0 : nullptr, cs, o));
                 if (c > 0) {
                     HIP_TRY(hipEventRecord(p->ev_join[c - 1], cs));
                     HIP_TRY(hipStreamWaitEvent(s, p->ev_join[c - 1], 0));
@@ -915,7 +1011,7 @@ static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, i
     }
     p->last_n = std::min(n, slice);   // the taps describe the last resident slice
     p->last_frames = frames;
-    p->ws.dbg_valid = p->debug;
+    p->ws.dbg_valid = p->debug && !hd;   // (a heads batch runs no k_cluster of its own: the guess / mean-shift taps are not its)
     return DH_OK;
 }
 
@@ -1526,6 +1622,79 @@ static int tracker_step_support_device_(dh_predictor *p, dh_tracker *t, const ui
 }
 
 // ------------------------------------------------------------------ predict_mask / 2-D Hough votes
+// ------------------------------------------------------------------ several heads per frame
+// Checked on the host before anything is launched: NULLs, max_heads in 1 .. DH_MAX_HEADS, a radius that fits an int.
+static int heads_args(const dh_predictor *p, const uint16_t *frames, int n, int max_heads, uint32_t radius, const uint32_t *n_heads,
+                      const dh_head *heads, const char *fn) {
+    if (!p || !frames || !n_heads || !heads) return fail(DH_EINVAL, "%s: NULL argument", fn);
+    if (max_heads < 1 || max_heads > DH_MAX_HEADS) return fail(DH_EINVAL, "%s: max_heads %d outside 1 .. %d", fn, max_heads, DH_MAX_HEADS);
+    if (radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u above 2^31 - 1", fn, radius);
+    if (n < 0) return fail(DH_EINVAL, "negative batch size");
+    return DH_OK;
+}
+// The host calls: per resident slice, the frames go up, the device batch runs, the heads and counts come back.
+static int heads_host(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_cameras *c, int max_heads,
+                      uint32_t radius, uint32_t *n_heads, dh_head *heads) {
+    const int slice = std::min(n, max_resident_frames(p));
+    hipStream_t s = p->own_stream;
+    for (int f0 = 0; f0 < n; f0 += slice) {
+        const int m = std::min(slice, n - f0);
+        TRY(reserve(p, m, w, h));
+        TRY(ensure_frame_staging(p, m, w, h));
+        TRY(heads_reserve(p));
+        const size_t fpx = (size_t)w * h;
+        HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        const HeadsOut ho{p->ws.hd_out.get(), p->ws.hd_n.get(), max_heads, radius};
+        int rc = batch_device(p, p->ws.frames.get(), m, w, h, c ? nullptr : K, c ? CamSel{c, f0} : CamSel{}, nullptr, nullptr, nullptr,
+                              nullptr, s, nullptr, &ho);
+        if (rc) { (void)hipStreamSynchronize(s); return rc; }
+        HIP_TRY(hipMemcpyAsync(heads + (size_t)f0 * max_heads, p->ws.hd_out.get(), (size_t)m * max_heads * sizeof(dh_head), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(n_heads + f0, p->ws.hd_n.get(), (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return DH_OK;
+}
+static int predict_heads_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], int max_heads, uint32_t radius,
+                          uint32_t *n_heads, dh_head *heads) {
+    TRY(heads_args(p, frames, n, max_heads, radius, n_heads, heads, "dh_predict_heads"));
+    if (!K) return fail(DH_EINVAL, "dh_predict_heads: NULL argument");
+    if (n == 0) return DH_OK;
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    return heads_host(p, frames, n, w, h, K, nullptr, max_heads, radius, n_heads, heads);
+}
+static int predict_heads_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], int max_heads,
+                                 uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream) {
+    TRY(heads_args(p, frames, n, max_heads, radius, n_heads, heads, "dh_predict_heads_device"));
+    if (!K) return fail(DH_EINVAL, "dh_predict_heads_device: NULL argument");
+    if (n == 0) return DH_OK;
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    const HeadsOut ho{heads, n_heads, max_heads, radius};
+    return batch_device(p, frames, n, w, h, K, CamSel{}, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr, &ho);
+}
+static int predict_heads_cameras_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads,
+                                  uint32_t radius, uint32_t *n_heads, dh_head *heads) {
+    TRY(heads_args(p, frames, n, max_heads, radius, n_heads, heads, "dh_predict_heads_cameras"));
+    if (!c) return fail(DH_EINVAL, "dh_predict_heads_cameras: NULL argument");
+    TRY(cameras_check(p, c, n, "dh_predict_heads_cameras"));
+    if (n == 0) return DH_OK;
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    return heads_host(p, frames, n, w, h, nullptr, c, max_heads, radius, n_heads, heads);
+}
+static int predict_heads_cameras_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads,
+                                         uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream) {
+    TRY(heads_args(p, frames, n, max_heads, radius, n_heads, heads, "dh_predict_heads_cameras_device"));
+    if (!c) return fail(DH_EINVAL, "dh_predict_heads_cameras_device: NULL argument");
+    TRY(cameras_check(p, c, n, "dh_predict_heads_cameras_device"));
+    if (n == 0) return DH_OK;
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    const HeadsOut ho{heads, n_heads, max_heads, radius};
+    return batch_device(p, frames, n, w, h, nullptr, CamSel{c, 0}, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr, &ho);
+}
+
 static int aux_reserve(dh_predictor *p, int n, int w, int h, size_t out_bytes) {
     TRY(reserve(p, n, w, h));
     Workspace &ws = p->ws;
@@ -2111,4 +2280,8 @@ DH_API(predict_batch_cameras_support, (dh_predictor *p, const uint16_t *frames, 
 DH_API(predict_batch_cameras_support_device, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius, dh_pose *out, dh_support *support, void *stream), (p, frames, n, w, h, c, midp_guess, rot_guess, guess_mask, radius, out, support, stream))
 DH_API(tracker_step_support, (dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, dh_pose *out, dh_support *support), (p, t, frames, w, h, present, radius, out, support))
 DH_API(tracker_step_support_device, (dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, dh_pose *out, dh_support *support, void *stream), (p, t, frames, w, h, present, radius, out, support, stream))
+DH_API(predict_heads, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], int max_heads, uint32_t radius, uint32_t *n_heads, dh_head *heads), (p, frames, n, w, h, K, max_heads, radius, n_heads, heads))
+DH_API(predict_heads_device, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], int max_heads, uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream), (p, frames, n, w, h, K, max_heads, radius, n_heads, heads, stream))
+DH_API(predict_heads_cameras, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads, uint32_t radius, uint32_t *n_heads, dh_head *heads), (p, frames, n, w, h, c, max_heads, radius, n_heads, heads))
+DH_API(predict_heads_cameras_device, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads, uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream), (p, frames, n, w, h, c, max_heads, radius, n_heads, heads, stream))
 #undef DH_API

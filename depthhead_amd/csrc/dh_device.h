@@ -109,3 +109,55 @@ __device__ __forceinline__ void store_leaf(char *base, int ls, int idx, int32_t 
 __device__ __forceinline__ uint32_t load_leaf(const char *base, int ls, size_t idx) {
     return ls == 1 ? (uint32_t)((const uint16_t *)base)[idx] : (uint32_t)((const int32_t *)base)[idx];
 }
+
+// wave reductions and a relaxed agent-scope load (k_support, k_heads)
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int o = WAVE / 2; o; o >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
+        v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+    for (int o = WAVE / 2; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int o = WAVE / 2; o; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T load_agent(T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// floor(n / d) of a 128-bit two's complement numerator n = nhi:nlo by a positive 128-bit denominator d = dhi:dlo (d < 2^127), for
+// quotients that fit an i32 (k_cluster's HEADS instance: the centroid of i32 cells).  Restoring long division, one bit per step.
+__device__ __forceinline__ int32_t floor_div_i128(uint64_t nlo, uint64_t nhi, uint64_t dlo, uint64_t dhi) {
+    const bool neg = (int64_t)nhi < 0;
+    if (neg) {
+        nlo = ~nlo + 1ull; nhi = ~nhi + (nlo == 0ull ? 1ull : 0ull);       // |n|
+        const uint64_t t = nlo + dlo;                                      // |n| + d - 1: floor(n / d) = -ceil(|n| / d)
+        nhi += dhi + (t < nlo ? 1ull : 0ull); nlo = t;
+        nhi -= nlo == 0ull ? 1ull : 0ull; nlo -= 1ull;
+    }
+    uint64_t q = 0, rlo = 0, rhi = 0;                                      // (the quotient is below 2^32: only its low word is kept)
+#pragma unroll 1
+    for (int i = 127; i >= 0; --i) {
+        const uint64_t bit = (i >= 64 ? nhi >> (i - 64) : nlo >> i) & 1ull;
+        rhi = (rhi << 1) | (rlo >> 63); rlo = (rlo << 1) | bit;
+        if (rhi > dhi || (rhi == dhi && rlo >= dlo)) {
+            rhi -= dhi + (rlo < dlo ? 1ull : 0ull); rlo -= dlo;
+            if (i < 64) q |= 1ull << i;
+        }
+    }
+    return neg ? (int32_t)(0ll - (int64_t)q) : (int32_t)(int64_t)q;
+}
+
+// hi:lo += s (sign-extended), exactly
+__device__ __forceinline__ void add_i128(uint64_t &lo, uint64_t &hi, int64_t s) {
+    const uint64_t u = (uint64_t)s;
+    lo += u;
+    hi += (lo < u ? 1ull : 0ull) + (s < 0 ? ~0ull : 0ull);
+}

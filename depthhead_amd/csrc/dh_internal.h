@@ -2,6 +2,7 @@
 // (k_*.hip): kernel argument blocks, device views of the forest, record layouts, launchers.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "dh_host.h"
@@ -253,6 +254,13 @@ struct ClusterArgs {
     uint32_t *dbg_steps;       // nullable [2][n]
     int stop;               // profiling knob (env DH_CL_STOP): low 4 bits 1 / 2 / 3 = return after the initial guess / the first region build / the first weighted sum; + 16 / 32: the position / rotation workgroups return at once
     const DhCam *cams;      // nullable [n_frames]: per-frame cameras (k_cluster's and k_region's CAM instances read cams[frame].kinv)
+    // HEADS instances (several heads per frame, k_heads.hip): workgroup (head, frame) runs accumulator hd_which from head's seed and
+    // writes out[frame * DH_MAX_HEADS + head]; heads at or beyond hd_nseed[frame] return at once
+    int hd_which;
+    const uint32_t *hd_nseed;  // [n_frames] seeds per frame (k_heads_seeds)
+    struct HdMom *hd_mom;      // [n_frames][DH_MAX_HEADS] vote moments of the seed cells: the position instance divides, then zeroes them
+    uint32_t *hd_rgrid;        // [n_frames][DH_MAX_HEADS][8000] the heads' 20^3 rotation grids: the rotation instance reads, then zeroes them
+    const uint8_t *hd_mask;    // [n_frames][hits_cap] bit k: the hit supports head k (k_heads_support); the rotation gather skips the others
 };
 
 // k_track: one live-tracking step's state update (dh_track.h) for every camera of a tracker, after the step's k_cluster.
@@ -305,6 +313,45 @@ struct SupportArgs {
     uint32_t *bits;         // [n_frames][bit_words] window bitmap, zero on entry and on exit
     uint32_t  bit_words;    // ceil(npatch / 32)
     dh_support *out;        // [n_frames]
+};
+
+// Several heads per frame.  Exact vote moments of one seed cell: [0] sum v, [1 .. 3] sum v * c_x, c_y, c_z,
+// each a 128-bit two's complement value hi:lo (|sum| < 1000 * 2^31 * votes per frame: beyond 64 bits past 2^22 votes).
+struct __attribute__((aligned(16))) HdMom {
+    unsigned long long lo[4], hi[4];
+};
+static_assert(sizeof(HdMom) == 64, "HdMom: one 64-byte line");
+static_assert(sizeof(dh_head) == 80 && offsetof(dh_head, pose) == 0 && offsetof(dh_head, support) == 40, "dh_head: include/depthhead_hip.h");
+
+struct HeadsArgs {
+    int n_frames, w, h, max_heads;
+    float k[9];
+    const DhCam *cams;          // nullable [n_frames]: the frame's k from its record (k_heads_moments)
+    const float4   *off4;       // DevForest::off4
+    const uint32_t *rough_cell; // DevForest::rough_cell
+    const HitRec   *hits;
+    const HitBox   *hit_box;
+    const HitRot   *hit_rot;
+    const uint32_t *hit_win;    // [n_frames][hits_cap] (k_emit's SUP instance)
+    const uint32_t *hit_count;
+    uint32_t  hits_cap;
+    const uint32_t *pos_grid;   // [n_frames][400] (k_vote)
+    int32_t  *pick;             // [n_frames][DH_MAX_HEADS] seed cells of the guess grid (k_heads_seeds), -1: none
+    uint32_t *nseed;            // [n_frames]
+    HdMom    *mom;              // [n_frames][DH_MAX_HEADS], zero on entry and on exit (k_cluster's HEADS position instance clears them)
+    // support of the heads (k_heads_support), laid out like SupportArgs, one slot per (frame, head)
+    int nx, step, lw, lh;
+    uint32_t radius;
+    const dh_pose *hpose;       // [n_frames][DH_MAX_HEADS] the heads' poses (k_cluster's HEADS instances)
+    SupAcc   *acc;              // [n_frames][DH_MAX_HEADS], zero on entry and on exit
+    uint32_t *bits;             // [n_frames][DH_MAX_HEADS][bit_words], zero on entry and on exit
+    uint32_t  bit_words;
+    dh_support *hsup;           // [n_frames][DH_MAX_HEADS]
+    uint8_t  *hmask;            // [n_frames][hits_cap] written for every record
+    uint32_t *rgrid;            // [n_frames][DH_MAX_HEADS][8000] rotation grids of the supporting hits, zero on entry (k_cluster clears them)
+    // output (k_heads_finish)
+    uint32_t *n_heads;          // [n_frames]
+    dh_head  *heads;            // [n_frames][max_heads]
 };
 
 // Sibling consumers of the walk (prediction.rs:760-905): they read the per-(patch, tree) leaf ids
@@ -406,6 +453,11 @@ hipError_t dh_launch_vote(const VoteArgs &a, hipStream_t s);
 hipError_t dh_launch_cluster(const ClusterArgs &a, hipStream_t s);
 hipError_t dh_launch_region(const ClusterArgs &a, hipStream_t s);
 hipError_t dh_launch_support(const SupportArgs &a, hipStream_t s);
+hipError_t dh_launch_cluster_heads(const ClusterArgs &a, int max_heads, hipStream_t s);   // ClusterArgs::hd_which selects the accumulator
+hipError_t dh_launch_heads_seeds(const HeadsArgs &a, hipStream_t s);
+hipError_t dh_launch_heads_moments(const HeadsArgs &a, hipStream_t s);
+hipError_t dh_launch_heads_support(const HeadsArgs &a, hipStream_t s);
+hipError_t dh_launch_heads_finish(const HeadsArgs &a, hipStream_t s);
 hipError_t dh_launch_votes_dump(const VotesDumpArgs &a, hipStream_t s);
 hipError_t dh_launch_track(const TrackArgs &a, hipStream_t s);
 hipError_t dh_launch_boxsum(const BoxArgs &a, hipStream_t s);

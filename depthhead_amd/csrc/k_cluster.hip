@@ -78,14 +78,15 @@ struct ClShared {
 // Initial guess of one accumulator into sh.s_pos (the caller synchronises before reading it): first strictly-greatest
 // cell, i.e. greatest value then smallest index (prediction.rs:694-702 for the 20x20 grid; :733-742 with the x-fastest
 // iteration order of meanshift.rs:114-138 for the 20^3 grid); all-zero grid -> index 0; then the caller's guesses (:437-460).
-__device__ __forceinline__ void cl_initial_guess(const ClusterArgs &a, const int which, const int frame, const ClShared sh) {
+// `row`: the grid's row (the frame; k_cluster's HEADS rotation instance: its (frame, head) grid of ClusterArgs::hd_rgrid).
+__device__ __forceinline__ void cl_initial_guess(const ClusterArgs &a, const int which, const int frame, const ClShared sh, const size_t row) {
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
     unsigned long long *red64 = sh.red64;
     uint32_t *red32 = sh.red32;
     int32_t *s_pos = sh.s_pos;
     const uint8_t gmask = a.guess_mask ? a.guess_mask[frame] : 3;
     {
-        const uint32_t *g = which == 0 ? a.pos_grid + (size_t)frame * DH_POSGRID : a.rot_grid + (size_t)frame * DH_GRID3;
+        const uint32_t *g = which == 0 ? a.pos_grid + row * DH_POSGRID : a.rot_grid + row * DH_GRID3;
         const int ncell = which == 0 ? DH_POSGRID : DH_GRID3;
         unsigned long long best = 0;   // (value << 32) | ~idx
         uint32_t gv[(DH_GRID3 + CL_THREADS - 1) / CL_THREADS];          // a thread's eight cells of the 20^3 grid: all loads in flight, one round trip
@@ -148,10 +149,11 @@ __device__ __forceinline__ void cl_initial_guess(const ClusterArgs &a, const int
 // accumulator in global memory -- every vote of accumulator `which` that falls into it, from the hit
 // records [h0, h1) of the frame -- or, for rotation votes of forests with a leaf histogram, from the leaves [l0, l1).
 // Integer atomics: exact and order-free, so any split of the ranges over workgroups sums to the same block.
-template <int EDGE>
+// HM: rotation votes only of the hit records whose ClusterArgs::hd_mask byte has bit `hbit` set (k_cluster's HEADS instances).
+template <int EDGE, bool HM = false>
 __device__ __forceinline__ void cl_gather(const ClusterArgs &a, const int which, const int frame, const int32_t org[3],
                                           const uint32_t h0, const uint32_t h1, const uint32_t l0, const uint32_t l1, const ClShared sh,
-                                          uint32_t *region) {
+                                          uint32_t *region, const uint32_t hbit = 0u) {
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     float *prod = sh.prod;
     uint32_t &s_total = *sh.s_total;
@@ -296,7 +298,7 @@ __device__ __forceinline__ void cl_gather(const ClusterArgs &a, const int which,
             for (int j = 0; j < 2; ++j) {
                 uint32_t i = i0 + j * CL_THREADS + tid;
                 r[j].x = 0xFFFFFFFFu;
-                if (i < h1) { r[j] = *(const uint4 *)(hr + i); vv[j] = box[i].v; }
+                if (i < h1 && (!HM || (a.hd_mask[(size_t)frame * a.hits_cap + i] & hbit))) { r[j] = *(const uint4 *)(hr + i); vv[j] = box[i].v; }
             }
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -337,7 +339,11 @@ __device__ __forceinline__ void cl_gather(const ClusterArgs &a, const int which,
 // SUP: the batch has blocks of both accumulators in global memory (k_region; a.pre_region != NULL); a separate instance so that
 // the code of batches without them keeps its registers.
 // CAM: the batch has a camera table (ClusterArgs::cams): the initial position guess un-projects with the frame's record.
-template <bool SUP, bool CAM>
+// HEADS: several heads per frame (k_heads.hip): workgroup (head, frame) runs accumulator a.hd_which from the
+// head's seed -- the position from the floor of its seed cell's vote centroid, the rotation from the argmax of its own 20^3 grid
+// over the rotation votes of the hits that support it -- and gathers rotation votes of those hits only (never from k_region's
+// blocks, which are centred on the reference's guess).
+template <bool SUP, bool CAM, bool HEADS = false>
 __global__ void __launch_bounds__(CL_THREADS, 8) k_cluster(ClusterArgs a) {
     __shared__ uint32_t region[RG3];
     __shared__ __attribute__((aligned(16))) float prod[CL_PROD_CAP * 4];
@@ -350,7 +356,9 @@ __global__ void __launch_bounds__(CL_THREADS, 8) k_cluster(ClusterArgs a) {
     __shared__ uint32_t s_total;
     __shared__ float s_kr2[DH_KERN_R2];     // Gaussian weights by squared distance: no global load inside a weighted sum
 
-    const int which = blockIdx.x, frame = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+    const int which = HEADS ? a.hd_which : (int)blockIdx.x, frame = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+    const uint32_t head = HEADS ? blockIdx.x : 0u;
+    if (HEADS && head >= a.hd_nseed[frame]) return;             // (uniform: no seed for this head)
     if (CAM) cam_kinv(a.kinv, a.cams + frame);
 
     const ClShared sh{prod, red64, red32, s_pos, &s_total};
@@ -363,8 +371,21 @@ __global__ void __launch_bounds__(CL_THREADS, 8) k_cluster(ClusterArgs a) {
     __syncthreads();
     unsigned long long t_prev = a.dbg_stamps ? clock64() : 0ull;
 #endif
-    cl_initial_guess(a, which, frame, sh);
-    __syncthreads();
+    if (!HEADS) {
+        cl_initial_guess(a, which, frame, sh, (size_t)frame);
+        __syncthreads();
+    } else if (which == 0) {
+        // the seed: floor of the centroid of the seed cell's votes, per axis (k_heads_moments), then the moments go back to zero
+        HdMom *m = a.hd_mom + (size_t)frame * DH_MAX_HEADS + head;
+        if (tid < 3) s_pos[tid] = floor_div_i128(m->lo[tid + 1], m->hi[tid + 1], m->lo[0], m->hi[0]);
+        __syncthreads();
+        if (tid < 8) ((unsigned long long *)m)[tid] = 0ull;
+    } else {
+        const size_t row = (size_t)frame * DH_MAX_HEADS + head;
+        cl_initial_guess(a, which, frame, sh, row);
+        __syncthreads();
+        for (int i = tid; i < DH_GRID3; i += CL_THREADS) a.hd_rgrid[row * DH_GRID3 + i] = 0u;   // (every thread has read its cells)
+    }
     CSTAMP(0)
     int32_t pos[3] = {s_pos[0], s_pos[1], s_pos[2]};
     if (a.dbg_guess && tid < 3) a.dbg_guess[(size_t)frame * 6 + which * 3 + tid] = pos[tid];
@@ -420,7 +441,7 @@ __global__ void __launch_bounds__(CL_THREADS, 8) k_cluster(ClusterArgs a) {
                 clean = false;
                 CSTAMP(1)
                 if (KNOB_STOP((a.stop & 15) == 4)) return;
-                cl_gather<RG>(a, which, frame, org, 0u, n_hits, 0u, a.f.n_leaves, sh, region);
+                cl_gather<RG, HEADS>(a, which, frame, org, 0u, n_hits, 0u, a.f.n_leaves, sh, region, 1u << head);
             }
             // the region's occupancy masks (one thread per (x, y) row)
             __syncthreads();
@@ -522,7 +543,7 @@ __global__ void __launch_bounds__(CL_THREADS, 8) k_cluster(ClusterArgs a) {
 #endif
     if (a.dbg_steps && tid == 0) a.dbg_steps[(size_t)which * a.n_frames + frame] = steps;
     if (tid == 0) {
-        dh_pose *o = a.out + frame;
+        dh_pose *o = a.out + (HEADS ? (size_t)frame * DH_MAX_HEADS + head : (size_t)frame);
         if (which == 0) {                                                                    // prediction.rs:486-488
             o->mid_point[0] = (float)pos[0];
             o->mid_point[1] = (float)pos[1];
@@ -544,6 +565,15 @@ hipError_t dh_launch_cluster(const ClusterArgs &a, hipStream_t s) {
         if (a.pre_region) hipLaunchKernelGGL((k_cluster<true, false>), dim3(2, a.n_frames), dim3(CL_THREADS), 0, s, a);
         else hipLaunchKernelGGL((k_cluster<false, false>), dim3(2, a.n_frames), dim3(CL_THREADS), 0, s, a);
     }
+    return hipGetLastError();
+}
+
+// Both accumulators of the heads of every frame, one launch each (dh_api.hip orders them around k_heads_support).
+hipError_t dh_launch_cluster_heads(const ClusterArgs &a, int max_heads, hipStream_t s) {
+    if (a.n_frames == 0) return hipSuccess;
+    if (a.n_frames > 65535 || a.pre_region || a.leaf_hits || a.dbg_guess || a.dbg_trace || a.dbg_steps) return hipErrorInvalidValue;
+    if (a.cams) hipLaunchKernelGGL((k_cluster<false, true, true>), dim3(max_heads, a.n_frames), dim3(CL_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((k_cluster<false, false, true>), dim3(max_heads, a.n_frames), dim3(CL_THREADS), 0, s, a);
     return hipGetLastError();
 }
 
@@ -580,7 +610,7 @@ __global__ void __launch_bounds__(CL_THREADS, 8) k_region(ClusterArgs a) {
     const uint32_t l0 = min(a.f.n_leaves, (uint32_t)slice * lper), l1 = min(a.f.n_leaves, l0 + lper);
     const bool by_leaves = which == 1 && a.leaf_hits;
     if (by_leaves ? l0 >= l1 : h0 >= h1) return;                    // nothing in this share (uniform for the workgroup)
-    cl_initial_guess(a, which, frame, sh);
+    cl_initial_guess(a, which, frame, sh, (size_t)frame);
     __syncthreads();
     uint32_t *pre = a.pre_region + ((size_t)frame * 2 + which) * SRG3;
     int32_t org[3];

@@ -27,26 +27,7 @@
 
 __device__ __forceinline__ bool in_cube(int32_t c, int64_t lo, int64_t hi) { return (int64_t)c >= lo && (int64_t)c <= hi; }
 
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int o = WAVE / 2; o; o >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
-        v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int o = WAVE / 2; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = WAVE / 2; o; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T load_agent(T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// (wave_sum_u64, wave_min_u32, wave_max_u32, load_agent: dh_device.h)
 
 __global__ void __launch_bounds__(SUP_THREADS) k_support(SupportArgs a) {
     const int frame = blockIdx.y, lane = threadIdx.x & (WAVE - 1);

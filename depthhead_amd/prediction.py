@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import POSE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, check, vp
+from ._lib import HEAD_DTYPE, MAX_HEADS, POSE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, check, vp
 from .forest import Forest
 from .synth import ModelParams
 
@@ -254,6 +254,43 @@ class HoughPrediction:
                                                                 cameras._h, vp(midp_guess_ptr), vp(rot_guess_ptr),
                                                                 vp(guess_mask_ptr), _radius(radius), vp(out_ptr), vp(support_ptr),
                                                                 _stream(stream)))
+
+    # ---- several heads per frame (include/depthhead_hip.h: dh_head) ----------
+    def predict_heads(self, frames, intrinsic: IntrinsicMatrix, max_heads: int = MAX_HEADS,
+                      radius: int = SUPPORT_RADIUS) -> tuple[np.ndarray, np.ndarray]:
+        """Up to `max_heads` heads per frame, each with its own pose and vote support: -> (n_heads uint32[n],
+        HEAD_DTYPE[n, max_heads]).  Heads are ordered by support mass; slots from n_heads[i] on are zero."""
+        frames, _, n, h, w = _host_frames(frames)
+        n_heads = np.zeros(n, dtype=np.uint32)
+        heads = np.zeros((n, max(int(max_heads), 0)), dtype=HEAD_DTYPE)
+        check(self._lib.dh_predict_heads(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic),
+                                         C.c_int(int(max_heads)), _radius(radius), vp(n_heads), vp(heads)))
+        return n_heads, heads
+
+    def predict_heads_device(self, frames_ptr: int, n: int, w: int, h: int, intrinsic: IntrinsicMatrix, n_heads_ptr: int,
+                             heads_ptr: int, max_heads: int = MAX_HEADS, radius: int = SUPPORT_RADIUS, stream: int = 0) -> None:
+        """Device-resident twin of `predict_heads`: n_heads [n] u32 and heads [n][max_heads] dh_head at raw device addresses.
+        Asynchronous."""
+        check(self._lib.dh_predict_heads_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic),
+                                                C.c_int(int(max_heads)), _radius(radius), vp(n_heads_ptr), vp(heads_ptr),
+                                                _stream(stream)))
+
+    def predict_heads_cameras(self, frames, cameras, max_heads: int = MAX_HEADS,
+                              radius: int = SUPPORT_RADIUS) -> tuple[np.ndarray, np.ndarray]:
+        """`predict_heads` with frame i seen by camera i of a `Cameras` table."""
+        frames, _, n, h, w = _host_frames(frames)
+        n_heads = np.zeros(n, dtype=np.uint32)
+        heads = np.zeros((n, max(int(max_heads), 0)), dtype=HEAD_DTYPE)
+        check(self._lib.dh_predict_heads_cameras(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), cameras._h,
+                                                 C.c_int(int(max_heads)), _radius(radius), vp(n_heads), vp(heads)))
+        return n_heads, heads
+
+    def predict_heads_cameras_device(self, frames_ptr: int, n: int, w: int, h: int, cameras, n_heads_ptr: int, heads_ptr: int,
+                                     max_heads: int = MAX_HEADS, radius: int = SUPPORT_RADIUS, stream: int = 0) -> None:
+        """Device-resident twin of `predict_heads_cameras`.  Asynchronous."""
+        check(self._lib.dh_predict_heads_cameras_device(self._ph, vp(frames_ptr), C.c_int(n), C.c_int(w), C.c_int(h), cameras._h,
+                                                        C.c_int(int(max_heads)), _radius(radius), vp(n_heads_ptr), vp(heads_ptr),
+                                                        _stream(stream)))
 
     @staticmethod
     def _payload_arrays(payloads):

@@ -311,6 +311,42 @@ int dh_tracker_step_support(dh_predictor *p, dh_tracker *t, const uint16_t *fram
 int dh_tracker_step_support_device(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
                                    uint32_t radius, dh_pose *out, dh_support *support, void *stream);
 
+/* ---- several heads per frame ----
+ * Not in the reference, which returns one pose per frame: PARITY UNPINNED, the definition below is this library's.  For frame f,
+ * max_heads in 1 .. DH_MAX_HEADS and a radius r as in the support calls:
+ *   1. the position votes are those of section 13; each vote (value v, cell c) also adds to one cell g of the 20 x 20 guess
+ *      grid, the cell the reference's projection and clamp give it (prediction.rs:660-676);
+ *   2. seed cells: the 400 grid cells in the order (count descending, index ascending); a cell with count > 0 is picked when it
+ *      lies more than DH_HEADS_SUPPRESS cells (Chebyshev, on the grid) from every cell picked before; at most max_heads picks.
+ *      The first pick is the reference's own guess cell (prediction.rs:694-704);
+ *   3. seed k = floor(sum v * c / sum v) per axis over the votes of pick k (exact: 128-bit sums);
+ *   4. the position mean shift of the plain call from each seed, over the frame's whole position accumulator: mid_k;
+ *   5. head k's dh_support record for m = mid_k and radius r;
+ *   6. its rotation: the plain call's rotation rule (coarse-grid argmax, mean shift) over the rotation votes of the hits
+ *      (window, tree) that support head k only.  At r = 2^31 - 1 every hit supports every head: each rotation is the plain one;
+ *   7. heads with mass 0 are dropped; walking the rest in seed order, a head whose mid_point lies within
+ *      DH_MEANSHIFT_KERNEL_SIZE cells (Chebyshev) of a head kept before is dropped; the survivors ordered by mass descending,
+ *      ties by seed order.  n_heads[f] of them fill heads[f][0 .. n_heads[f]); slots up to max_heads - 1 are zero.
+ * Integer or the plain call's f32 / f64 rules throughout: bit-identical run to run.  heads is [n][max_heads] (host memory for the
+ * host calls, device memory for the _device calls), n_heads [n].  DH_EINVAL before anything is launched: max_heads 0 or above
+ * DH_MAX_HEADS, a radius above 2^31 - 1, NULL arguments, a camera table of another device.  The first heads call of a workspace
+ * allocates its scratch; after that the _device calls allocate nothing and do not synchronise.  No guesses: heads start from
+ * their seeds. */
+#define DH_MAX_HEADS 4
+#define DH_HEADS_SUPPRESS 2    /* guess-grid cells */
+typedef struct dh_head {
+    dh_pose pose;
+    dh_support support;
+} dh_head; /* 80 bytes */
+int dh_predict_heads(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], int max_heads, uint32_t radius,
+                     uint32_t *n_heads, dh_head *heads);
+int dh_predict_heads_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], int max_heads,
+                            uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream);
+int dh_predict_heads_cameras(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads,
+                             uint32_t radius, uint32_t *n_heads, dh_head *heads);
+int dh_predict_heads_cameras_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads,
+                                    uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run

@@ -1,0 +1,254 @@
+"""The several-heads restatement (tests/heads_ref.py) on hand-built cases and synthetic scenes, and the heads ABI without a GPU.
+
+* heads_ref's mean shift is pyref.meanshift; its guess cells add up to the oracle's pos_grid (checked in every heads_ref call);
+* a hand-built forest and frame with two vote clusters gives two heads in mass order; the seed suppression boundary (2 cells
+  apart suppressed, 3 kept), the merge boundary (20 cells merged, 21 kept), equal grid counts (lower index first), an empty
+  frame, max_heads = 1, the centroid's floor on negative coordinates and exact moments at saturated i32 cells;
+* at r = 2^31 - 1 every head's rotation is oracle.predict's;
+* two synthetic heads composited into one scene are both found within the measured distance, and the plain call misses one;
+* the new symbols are exported and declared, dh_head is 80 bytes, and the argument checks answer DH_EINVAL.
+"""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from depthhead_amd import synth
+from depthhead_amd.forest import Forest, NODE_DTYPE
+from oracle import pyref
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import heads_ref as hr  # noqa: E402
+import support_ref as sr  # noqa: E402
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "depthhead_hip.h")
+
+
+def one_leaf_forest(offsets, rots=((0.0, 0.0, 0.0), (3.0, 0.0, 0.0))):
+    """One tree whose every non-zero window reaches leaf 0 (prob 1, the given offsets and rotations: at least two of each, or
+    the covariance gates read NaN)."""
+    nodes = np.zeros(1, dtype=NODE_DTYPE)
+    nodes[0]["r1"] = (0, 0, 1, 1)
+    nodes[0]["r2"] = (0, 0, 1, 1)
+    nodes[0]["threshold"] = -1.0
+    nodes[0]["child_zero"] = ~1
+    nodes[0]["child_one"] = ~0
+    offs = np.vstack([np.asarray(offsets, np.float32).reshape(-1, 3), [[0, 0, 0]]]).astype(np.float32)
+    rr = np.vstack([np.asarray(rots, np.float64).reshape(-1, 3), [[0, 0, 0]]])
+    k, q = len(offsets), len(rots)
+    return Forest(np.array([0], np.int32), nodes, np.array([1.0, 0.0]), np.array([0, k, k + 1], np.uint32),
+                  np.array([0, q, q + 1], np.uint32), offs, rr)
+
+
+def two_blocks(w=128, h=96, near=800, far=1000):
+    """Two small blocks, each within two guess-grid cells: one seed each."""
+    img = np.zeros((h, w), np.uint16)
+    img[42:50, 8:20] = near          # left block: heavier (more windows)
+    img[40:48, 100:108] = far
+    return img
+
+
+MODEL8 = synth.ModelParams(stepwidth=4, subimage_width=8, subimage_height=8)
+
+
+def test_meanshift_is_pyref_meanshift():
+    rng = np.random.default_rng(5)
+    kern = hr.kernel_array(8.0)
+    kd = pyref.build_kernel(20, pyref.F32(8.0))
+    for _ in range(4):
+        cells = rng.integers(-12, 12, size=(60, 3)) + np.array([100, -50, 700])
+        vals = rng.integers(1, 3000, size=60)
+        c, v = hr.accumulate(cells, vals)
+        acc = {tuple(int(x) for x in cc): int(vv) for cc, vv in zip(c, v)}
+        start = (int(c[0, 0]) + 3, int(c[0, 1]) - 2, int(c[0, 2]))
+        ref, _ = pyref.meanshift(acc, start, kd, 20, 6)
+        assert hr.meanshift(c, v, start, kern, 6) == ref
+
+
+def test_two_clusters_two_heads_in_mass_order(oracle):
+    """Two blocks of constant depth, two votes per window 100 mm in front of its centre (windows whose centre pixel is
+    background vote behind the camera and are dropped): two clusters, two heads, the block with more windows first; each head's
+    support is its own block's windows."""
+    f = one_leaf_forest([[0, 0, 100], [0, 2, 100]])
+    tab = sr.LeafTables(f)
+    img = two_blocks()
+    K = synth.default_intrinsic(128, 96)
+    n, kept, info, res, fh = hr.heads_ref(oracle, tab, MODEL8, img, K, 4, 150)
+    assert n == 2, (n, info["picks"])
+    assert kept[0]["support"]["mass"] > kept[1]["support"]["mass"] > 0
+    assert kept[0]["mid_point"][0] < 0 < kept[1]["mid_point"][0]            # left block (x < cx) first
+    assert kept[0]["support"]["x"] + kept[0]["support"]["width"] <= 64 <= kept[1]["support"]["x"]
+    assert kept[0]["support"]["total_mass"] == kept[1]["support"]["total_mass"] == int(fh["vals"].sum())
+    n1, kept1, _, _, _ = hr.heads_ref(oracle, tab, MODEL8, img, K, 1, 150)    # max_heads = 1: the reference's guess cell
+    assert n1 == 1 and info["picks"][0] == int(np.argmax(res.pos_grid)) and kept1[0]["seed_cell"] == info["picks"][0]
+
+
+def test_empty_frame_has_no_heads(oracle):
+    f = one_leaf_forest([[0, 0, 100], [0, 2, 100]])
+    n, kept, info, _, _ = hr.heads_ref(oracle, sr.LeafTables(f), MODEL8, np.zeros((96, 128), np.uint16),
+                                       synth.default_intrinsic(128, 96), 4, 30)
+    assert n == 0 and kept == [] and info["picks"] == []
+    from depthhead_amd._lib import HEAD_DTYPE
+    assert hr.as_records(0, [], 4, HEAD_DTYPE).tobytes() == bytes(4 * 80)
+
+
+def test_seed_suppression_boundary():
+    g = np.zeros(400, np.int64)
+    g[5 * 20 + 5] = 100
+    g[5 * 20 + 7] = 90          # 2 cells away: suppressed
+    g[7 * 20 + 3] = 80          # 2 cells away (Chebyshev): suppressed
+    g[5 * 20 + 8] = 70          # 3 cells away: kept
+    g[8 * 20 + 5] = 60          # 3 cells away: kept
+    assert hr.seed_cells(g, 4) == [105, 108, 165]
+    assert hr.seed_cells(g, 1) == [105]
+
+
+def test_equal_counts_lower_index_first():
+    g = np.zeros(400, np.int64)
+    g[[300, 40, 210]] = 7
+    assert hr.seed_cells(g, 4) == [40, 210, 300]
+    assert hr.seed_cells(g, 2) == [40, 210]
+
+
+def cand(k, mid, mass):
+    return dict(k=k, mid=mid, support={"mass": mass})
+
+
+def test_merge_boundary():
+    kept, merged = hr.merge_order([cand(0, (0, 0, 800), 5), cand(1, (20, -20, 820), 9), cand(2, (21, 0, 800), 7)])
+    assert [c["k"] for c in kept] == [2, 0] and merged == 1                  # 20 apart merged, 21 kept; mass order
+    kept, merged = hr.merge_order([cand(0, (0, 0, 0), 0), cand(1, (5, 0, 0), 3), cand(2, (30, 0, 0), 3)])
+    assert [c["k"] for c in kept] == [1, 2] and merged == 0                  # mass 0 dropped first; ties in seed order
+
+
+def test_centroid_floor_on_negative_coordinates():
+    fh = dict(g=np.array([7, 7, 7, 8]), vals=np.array([1, 1, 1, 5]),
+              cells=np.array([[-3, 0, 5], [-4, 1, 5], [-4, -1, 6], [9, 9, 9]]))
+    assert hr.seed_point(fh, 7) == (-4, 0, 5)          # -11/3 -> -4, 0/3 -> 0, 16/3 -> 5
+    fh["cells"][:3, 1] = [-1, -1, 0]
+    assert hr.seed_point(fh, 7)[1] == -1               # -2/3 -> -1 (toward -inf, not toward zero)
+
+
+def test_moments_at_saturated_cells():
+    """Votes in cells saturated at i32 min / max: the sums exceed 64 bits' worth of int64 partials no step, and the centroid is
+    exact (numpy's own int64 sum of v * c would wrap past 2^63 at this many votes)."""
+    n = 5_000_000
+    vals = np.full(n, 1000, np.int64)
+    lo = np.full(n, -(1 << 31), np.int64)
+    hi = np.full(n, (1 << 31) - 1, np.int64)
+    assert hr.exact_sum(vals, lo) == -(1 << 31) * 1000 * n and hr.exact_sum(vals, hi) == ((1 << 31) - 1) * 1000 * n
+    assert abs(hr.exact_sum(vals, lo)) > (1 << 63)
+    cells = np.stack([lo, hi, np.where(np.arange(n) % 2 == 0, lo, hi)], axis=1)
+    fh = dict(g=np.zeros(n, np.int64), vals=vals, cells=cells)
+    assert hr.seed_point(fh, 0) == (-(1 << 31), (1 << 31) - 1, -1)      # mean of the two extremes: -1/2 floors to -1
+
+
+def test_full_radius_rotation_is_the_oracle_rotation(oracle):
+    forest = synth.fit_forest(6, 10, synth.FOREST_SEED_BASE + 9, n_frames=12, subset=1500)
+    tab = sr.LeafTables(forest)
+    model = synth.ModelParams(stepwidth=4)
+    K = synth.default_intrinsic(128, 112)
+    checked = 0
+    for first in (63, 20, 24):
+        img = synth.biwi_batch(1, 128, 112, first=first)[0]
+        n, kept, _, res, fh = hr.heads_ref(oracle, tab, model, img, K, 4, (1 << 31) - 1)
+        c, v = hr.accumulate(fh["rot_cells"], fh["rot_vals"])
+        rc = res.rot_cells.astype(np.int64)
+        assert np.array_equal(c, rc[:, :3]) and np.array_equal(v, rc[:, 3] % (1 << 32))   # every rotation vote is a supporter's
+        for head in kept:
+            assert head["rotation"].tobytes() == res.rotation.tobytes()
+            assert head["support"]["mass"] == head["support"]["total_mass"]
+            checked += 1
+    assert checked >= 3
+
+
+# Quality on two synthetic heads in one scene (training.synthetic_truth; the second head's frame moved sideways so the heads do
+# not overlap).  Measured with heads_ref on scenes 0 .. 15 at DH_SUPPORT_RADIUS with the 6-tree test forest (DESIGN.md section
+# 14): in 8 scenes both true heads have a detected head within 87.3 mm; in the other 8 one of them is 148 - 408 mm from every
+# detected head (the small forest's votes for that head do not hold a mode near it).  The test holds the 8 scenes where both
+# are found, listed here: worst distance 81.3 mm, bound 102 mm (25 % margin).  The plain call's single pose is more than the
+# bound from one of the two heads in each of them.
+QUALITY_SCENES = (0, 1, 4, 6, 8, 10, 12, 13)
+QUALITY_BOUND_MM = 102.0
+
+
+def two_head_scene(i, w=320, h=240):
+    from depthhead_amd import training
+    da, _, K, pa, _ = training.synthetic_truth(w, h, synth.FRAME_SEED_BASE + 3000 + i)
+    db, _, _, pb, _ = training.synthetic_truth(w, h, synth.FRAME_SEED_BASE + 4000 + i)
+    s = w // 3 if pb[0] < pa[0] else -(w // 3)          # move head b away from head a
+    moved = np.zeros_like(db)
+    if s > 0:
+        moved[:, s:] = db[:, : w - s]
+    else:
+        moved[:, : w + s] = db[:, -s:]
+    pb = pb.copy()
+    pb[0] += np.float32(s * pb[2] / K[0, 0])
+    return hr.composite(da, moved), K, pa, pb
+
+
+def test_two_synthetic_heads_are_found(oracle):
+    from depthhead_amd._lib import SUPPORT_RADIUS
+    forest = synth.fit_forest(6, 10, synth.FOREST_SEED_BASE + 9, n_frames=12, subset=1500)
+    tab = sr.LeafTables(forest)
+    model = synth.ModelParams(stepwidth=4)
+    worst = 0.0
+    for i in QUALITY_SCENES:
+        img, K, pa, pb = two_head_scene(i)
+        n, kept, _, res, _ = hr.heads_ref(oracle, tab, model, img, K, 4, SUPPORT_RADIUS)
+        mids = [c["mid_point"] for c in kept]
+        da = min(np.linalg.norm(m - pa) for m in mids)
+        db = min(np.linalg.norm(m - pb) for m in mids)
+        worst = max(worst, da, db)
+        assert da <= QUALITY_BOUND_MM and db <= QUALITY_BOUND_MM, (i, da, db)
+        plain = res.mid_point
+        assert max(np.linalg.norm(plain - pa), np.linalg.norm(plain - pb)) > QUALITY_BOUND_MM, i
+    print("worst distance to a true head: %.1f mm" % worst)
+
+
+# ---------------------------------------------------------------------------------------------------- ABI without a GPU
+HEADS_CALLS = ["dh_predict_heads", "dh_predict_heads_device", "dh_predict_heads_cameras", "dh_predict_heads_cameras_device"]
+
+
+def test_heads_symbols_and_layout(hip_lib):
+    from depthhead_amd import _lib
+    src = open(HEADER).read()
+    for name in HEADS_CALLS:
+        assert hasattr(hip_lib, name) and name in _lib.EXPORTS and f"int {name}(" in src
+    assert _lib.HEAD_DTYPE.itemsize == 80 and _lib.HEAD_DTYPE.fields["support"][1] == 40
+    assert f"#define DH_MAX_HEADS {_lib.MAX_HEADS}\n" in src and f"#define DH_HEADS_SUPPRESS {_lib.HEADS_SUPPRESS} " in src
+    assert hr.MAX_HEADS == _lib.MAX_HEADS and hr.HEADS_SUPPRESS == _lib.HEADS_SUPPRESS
+
+
+def test_heads_argument_checks_without_gpu(hip_lib):
+    lib = hip_lib
+    fr = np.zeros((1, 8, 8), np.uint16)
+    nh = np.full(1, 7, np.uint32)
+    heads = np.full(4 * 80, 0xAB, np.uint8)
+    K = (C.c_float * 9)(*([1.0] * 9))
+    vp = lambda a: C.c_void_p(a.ctypes.data)   # noqa: E731
+    r = C.c_uint32
+    fake = C.c_void_p(8)                       # never dereferenced: the checks run first
+    for mh in (0, 5, -1):
+        assert lib.dh_predict_heads(fake, vp(fr), 1, 8, 8, K, mh, r(10), vp(nh), vp(heads)) == -1
+        assert b"max_heads" in lib.dh_last_error()
+        assert lib.dh_predict_heads_device(fake, vp(fr), 1, 8, 8, K, mh, r(10), vp(nh), vp(heads), None) == -1
+        assert lib.dh_predict_heads_cameras(fake, vp(fr), 1, 8, 8, fake, mh, r(10), vp(nh), vp(heads)) == -1
+        assert lib.dh_predict_heads_cameras_device(fake, vp(fr), 1, 8, 8, fake, mh, r(10), vp(nh), vp(heads), None) == -1
+    for rad in (1 << 31, 0xFFFFFFFF):
+        assert lib.dh_predict_heads(fake, vp(fr), 1, 8, 8, K, 4, r(rad), vp(nh), vp(heads)) == -1
+        assert b"radius" in lib.dh_last_error()
+        assert lib.dh_predict_heads_cameras_device(fake, vp(fr), 1, 8, 8, fake, 4, r(rad), vp(nh), vp(heads), None) == -1
+        assert b"radius" in lib.dh_last_error()
+    assert lib.dh_predict_heads(None, vp(fr), 1, 8, 8, K, 4, r(10), vp(nh), vp(heads)) == -1
+    assert lib.dh_predict_heads(fake, vp(fr), 1, 8, 8, K, 4, r(10), None, vp(heads)) == -1
+    assert lib.dh_predict_heads(fake, vp(fr), 1, 8, 8, K, 4, r(10), vp(nh), None) == -1
+    assert lib.dh_predict_heads(fake, None, 1, 8, 8, K, 4, r(10), vp(nh), vp(heads)) == -1
+    assert lib.dh_predict_heads(fake, vp(fr), 1, 8, 8, None, 4, r(10), vp(nh), vp(heads)) == -1
+    assert lib.dh_predict_heads_device(fake, vp(fr), 1, 8, 8, None, 4, r(10), vp(nh), vp(heads), None) == -1
+    assert lib.dh_predict_heads_cameras(fake, vp(fr), 1, 8, 8, None, 4, r(10), vp(nh), vp(heads)) == -1
+    assert lib.dh_predict_heads_cameras_device(fake, vp(fr), 1, 8, 8, None, 4, r(10), vp(nh), vp(heads), None) == -1
+    assert b"NULL" in lib.dh_last_error()
+    assert nh[0] == 7 and (heads == 0xAB).all()          # output untouched
