@@ -236,8 +236,8 @@ struct dh_predictor {
     hipStream_t copy_stream = nullptr;    // host entry points: uploads run here, ahead of the kernels on own_stream
     hipEvent_t ev_stage[DH_STAGE_EVENTS] = {};   // chunk k uploaded (recorded on an upload stream, waited for on own_stream)
     hipEvent_t ev_slice = nullptr;        // the kernels that read the staging buffers are done (recorded on own_stream)
-    Buf<uint8_t, PINNED> pin_small;       // page-locked staging of a slice's small host arrays: poses out, guesses in (small_stage)
-    Buf<dh_support, PINNED> pin_sup;      // ... and support records out (download_support)
+    Buf<uint8_t, PINNED> pin_small;       // page-locked staging of a slice's small host arrays: guesses in (small_stage)
+    Buf<uint8_t, PINNED> pin_out;         // ... and its poses, support records and heads out (download)
     // run-length coded input (dh_predict_batch_rle): pinned staging + device copies of payload blob and run table
     Buf<uint8_t, PINNED> pin_blob;
     Buf<uint2, PINNED> pin_runs;
@@ -615,7 +615,38 @@ struct CamSel {
     }
 };
 
-// How enqueue_range runs besides the product batch.
+// One prediction: n frames of w x h seen through one K (cams.c == NULL) or frame i -> camera cams.c0 + i, per-frame guesses (each
+// optional), and what it writes: poses into `out`, with `support` also each pose's vote support, or with `heads` the heads of
+// every frame instead.  Its pointers are host or device ones, as the driver that runs it expects.  at(f) is the same request
+// from frame f on: slices, forked sub-batches and staged chunks all take theirs that way.
+enum ReqKind { POSES, SUPPORT, HEADS };     // the outputs an entry point promises (check_req)
+template <typename T>
+static T *off(T *ptr, size_t k) { return ptr ? ptr + k : nullptr; }
+struct BatchReq {
+    const uint16_t *frames = nullptr;
+    int n = 0, w = 0, h = 0;
+    const float *K = nullptr;
+    CamSel cams;
+    const float *midp = nullptr;       // guesses: [n][3], [n][3], [n] (bit0 midpoint, bit1 rotation)
+    const double *rot = nullptr;
+    const uint8_t *mask = nullptr;
+    dh_pose *out = nullptr;            // [n] (unused with heads)
+    ReqKind kind = POSES;
+    uint32_t radius = 0;               // support and heads
+    dh_support *support = nullptr;     // [n] non-NULL: k_emit's SUP instance, then k_support after k_cluster
+    dh_head *heads = nullptr;          // [n][max_heads] non-NULL: k_emit's SUP instance, then the heads kernels in place of
+    uint32_t *n_heads = nullptr;       // [n]              k_region / k_cluster
+    int max_heads = 0;
+    BatchReq at(int f) const {
+        BatchReq r = *this;
+        r.n = n - f; r.frames = off(frames, (size_t)f * w * h); r.cams = cams.at(f);
+        r.midp = off(midp, (size_t)f * 3); r.rot = off(rot, (size_t)f * 3); r.mask = off(mask, f);
+        r.out = off(out, f); r.support = off(support, f); r.heads = off(heads, (size_t)f * max_heads); r.n_heads = off(n_heads, f);
+        return r;
+    }
+};
+
+// How enqueue_range runs the kernels of a request.
 struct EnqueueOpts {
     bool profile = false;           // events and roctx ranges (dh_set_profiling)
     int32_t *leaf_out = nullptr;    // k_traverse's leaf ids and patch flags into these instead of the taps (mask / 2-D Hough)
@@ -623,25 +654,26 @@ struct EnqueueOpts {
     bool traverse_only = false;     // stop after k_traverse
     int chunk = 0;                  // forked sub-batch: its tile-flag tag and tile list
     bool zero_fold = false;         // k_boxsum zeroes the counters: no fill of their own
-    dh_support *support = nullptr;  // non-NULL: k_emit's SUP instance, then k_support after k_cluster (indexed like `out`)
-    uint32_t radius = 0;
-    dh_head *heads = nullptr;       // non-NULL: k_emit's SUP instance, then the heads kernels in place of k_region / k_cluster (DESIGN.md
-    uint32_t *n_heads = nullptr;    // section 14); heads [n][max_heads], n_heads [n] of this range, `out` unused
-    int max_heads = 0;
 };
 
-// Enqueue the kernels (k_boxsum / k_pixflags, k_traverse, k_emit, k_vote, [k_region,] k_cluster) for frames [f0, f0 + n) of the batch on stream s.
-// With a camera table (`cams`, camera of frame 0 of `frames`) frame f0 + i reads camera cams.c0 + f0 + i; K and kinv are unused.
-static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n, int w, int h, const float K[9],
-                         const float kinv[9], const CamSel &cams, const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
-                         dh_pose *out, hipStream_t s, const EnqueueOpts &o) {
+// Enqueue the kernels (k_boxsum / k_pixflags, k_traverse, k_emit, k_vote, then [k_region,] k_cluster [, k_support] or the heads
+// kernels) for frames [f0, f0 + n) of the resident slice sl on stream s: sl.at(f0) gives their inputs and outputs, f0 their place
+// in the workspace.
+static int enqueue_range(dh_predictor *p, const BatchReq &sl, int f0, int n, hipStream_t s, const EnqueueOpts &o) {
     const Workspace &ws = p->ws;
-    const CamSel cs = cams.at(f0);
+    const BatchReq q = sl.at(f0);
+    const CamSel &cs = q.cams;
+    const int w = sl.w, h = sl.h;
+    // one K, or the range's first camera: kernel-argument stand-ins there (the CAM instances read the records)
+    const float *K = cs.c ? cs.c->host[cs.c0].k : q.K;
+    float kinv[9];
+    if (cs.c) memcpy(kinv, cs.c->host[cs.c0].kinv, sizeof kinv);
+    else dh_mat3_inv_f32_(K, kinv);   // cached in a RefCell by the reference (types.rs:436-441)
     const Geom &g = ws.geom;
     uint32_t *gen = p->gen.get() + o.chunk;      // this kernel sequence's tile-flag tag
     uint32_t *hit_count = ws.hit_count(f0), *pos_grid = ws.pos_grid(f0), *rot_grid = ws.rot_grid(f0), *leaf_hits = ws.leaf_hits(f0);
     const size_t hoff = (size_t)f0 * ws.hits_cap;
-    const uint16_t *fr = frames + (size_t)f0 * w * h;
+    const uint16_t *fr = q.frames;
     char batch_name[48];
     snprintf(batch_name, sizeof batch_name, "dh:batch n=%d %dx%d", n, w, h);
     Range batch_range(o.profile, batch_name);
@@ -750,10 +782,10 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
             ea.hits = ws.hits.get() + hoff; ea.hit_box = ws.hit_box.get() + hoff; ea.hit_rot = ws.hit_rot.get() + hoff;
             ea.hit_count = hit_count; ea.hits_cap = ws.hits_cap;
             // (a heads batch keeps every hit's rotation record: its rotation votes are restricted per head, hit by hit)
-            ea.leaf_hits = o.heads ? nullptr : leaf_hits;
+            ea.leaf_hits = q.heads ? nullptr : leaf_hits;
             ea.gen = gen;
             ea.dbg_flags = ta.dbg_flags;
-            if (o.support || o.heads) ea.hit_win = ws.hit_win.get() + hoff;
+            if (q.support || q.heads) ea.hit_win = ws.hit_win.get() + hoff;
 #ifdef DH_PROFILING_KNOBS
             ea.stop = p->knobs.emit_stop;
 #endif
@@ -771,18 +803,18 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         va.f = p->dev; va.hits = ws.hits.get() + hoff; va.hit_box = ws.hit_box.get() + hoff; va.hit_rot = ws.hit_rot.get() + hoff;
         va.hit_count = hit_count; va.hits_cap = ws.hits_cap;
         va.pos_grid = pos_grid; va.rot_grid = rot_grid;
-        va.leaf_hits = o.heads ? nullptr : leaf_hits;
+        va.leaf_hits = q.heads ? nullptr : leaf_hits;
 #ifdef DH_PROFILING_KNOBS
         va.stop = p->knobs.vote_stop;
 #endif
         { Range r(o.profile, "dh:vote"); HIP_TRY(dh_launch_vote(va, s)); }
     }
     if (o.profile) HIP_TRY(hipEventRecord(p->ev[2], s));
-    if (o.heads) {
+    if (q.heads) {
         // several heads per frame: seeds, their moments, position mean shifts, support (+ head masks and rotation grids), rotation
         // mean shifts, merge (k_heads.hip)
         HeadsArgs ha{};
-        ha.n_frames = n; ha.w = w; ha.h = h; ha.max_heads = o.max_heads;
+        ha.n_frames = n; ha.w = w; ha.h = h; ha.max_heads = q.max_heads;
         memcpy(ha.k, K, sizeof ha.k);
         ha.cams = cs.dev();
         ha.off4 = p->dev.off4; ha.rough_cell = p->dev.rough_cell;
@@ -793,10 +825,10 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         ha.pick = ws.hd_pick.get() + hk; ha.nseed = ws.hd_nseed.get() + f0; ha.mom = ws.hd_mom.get() + hk;
         ha.nx = g.nx; ha.step = (int)p->params.stepwidth;
         ha.lw = (int)p->params.subimage_width / 2; ha.lh = (int)p->params.subimage_height / 2;
-        ha.radius = o.radius;
+        ha.radius = q.radius;
         ha.hpose = ws.hd_pose.get() + hk; ha.acc = ws.hd_acc.get() + hk; ha.bits = ws.hd_bits.get() + hk * ws.sup_words; ha.bit_words = ws.sup_words;
         ha.hsup = ws.hd_sup.get() + hk; ha.hmask = ws.hd_mask.get() + hoff; ha.rgrid = ws.hd_rgrid.get() + hk * DH_GRID3;
-        ha.n_heads = o.n_heads + f0; ha.heads = o.heads + (size_t)f0 * o.max_heads;
+        ha.n_heads = q.n_heads; ha.heads = q.heads;
         ClusterArgs ca{};
         ca.frames = fr; ca.n_frames = n; ca.w = w; ca.h = h;
         memcpy(ca.kinv, kinv, 9 * sizeof(float));
@@ -811,10 +843,10 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         HIP_TRY(dh_launch_heads_seeds(ha, s));
         HIP_TRY(dh_launch_heads_moments(ha, s));
         ca.hd_which = 0;
-        HIP_TRY(dh_launch_cluster_heads(ca, o.max_heads, s));
+        HIP_TRY(dh_launch_cluster_heads(ca, q.max_heads, s));
         HIP_TRY(dh_launch_heads_support(ha, s));
         ca.hd_which = 1;
-        HIP_TRY(dh_launch_cluster_heads(ca, o.max_heads, s));
+        HIP_TRY(dh_launch_cluster_heads(ca, q.max_heads, s));
         HIP_TRY(dh_launch_heads_finish(ha, s));
         if (o.profile) { HIP_TRY(hipEventRecord(p->ev[3], s)); p->ev_valid = true; }
         return DH_OK;
@@ -844,10 +876,8 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
             ca.dbg_stamps = cl_stamps;
         }
 #endif
-        ca.midp_guess = midp_guess ? midp_guess + (size_t)f0 * 3 : nullptr;
-        ca.rot_guess = rot_guess ? rot_guess + (size_t)f0 * 3 : nullptr;
-        ca.guess_mask = guess_mask ? guess_mask + f0 : nullptr;
-        ca.out = out + f0;
+        ca.midp_guess = q.midp; ca.rot_guess = q.rot; ca.guess_mask = q.mask;
+        ca.out = q.out;
         if (p->debug) { ca.dbg_guess = ws.dbg_guess.get(); ca.dbg_trace = ws.dbg_trace.get(); ca.dbg_steps = ws.dbg_steps.get(); }
         // few frames with many hit records each: the first region of every accumulator is gathered by several workgroups
         const int slices = std::min(16, 256 / std::max(n, 1));
@@ -863,15 +893,15 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
         }
         { Range r(o.profile, "dh:cluster"); HIP_TRY(dh_launch_cluster(ca, s)); }
     }
-    if (o.support) {
+    if (q.support) {
         SupportArgs sa{};
         sa.n_frames = n; sa.nx = g.nx; sa.step = (int)p->params.stepwidth;
         sa.lw = (int)p->params.subimage_width / 2; sa.lh = (int)p->params.subimage_height / 2;
-        sa.radius = o.radius; sa.poses = out + f0;
+        sa.radius = q.radius; sa.poses = q.out;
         sa.hits = ws.hits.get() + hoff; sa.hit_box = ws.hit_box.get() + hoff; sa.hit_win = ws.hit_win.get() + hoff;
         sa.hit_count = hit_count; sa.hits_cap = ws.hits_cap; sa.off4 = p->dev.off4;
         sa.acc = ws.sup_acc.get() + f0; sa.bits = ws.sup_bits.get() + (size_t)f0 * ws.sup_words; sa.bit_words = ws.sup_words;
-        sa.out = o.support + f0;
+        sa.out = q.support;
         { Range r(o.profile, "dh:support"); HIP_TRY(dh_launch_support(sa, s)); }
     }
     if (o.profile) { HIP_TRY(hipEventRecord(p->ev[3], s)); p->ev_valid = true; }
@@ -882,12 +912,6 @@ static int enqueue_range(dh_predictor *p, const uint16_t *frames, int f0, int n,
 // per frame: 9 MB per frame at BASELINE config 2).  Larger batches are walked in slices on the same
 // stream, reusing the workspace.
 static int max_resident_frames(const dh_predictor *p) { return p->knobs.max_resident; }
-
-// Support records of a batch (the *_support entry points): one per frame, indexed like the poses.
-struct SupOut {
-    dh_support *rec = nullptr;
-    uint32_t radius = 0;
-};
 
 // The support scratch of the current workspace (Workspace::hit_win ..), allocated and zeroed on the first support call that
 // needs it; a no-op after that.  Nothing a captured batch points to is touched.
@@ -908,14 +932,6 @@ static int support_reserve(dh_predictor *p) {
     }
     return DH_OK;
 }
-
-// Heads of a batch (the dh_predict_heads* entry points): n_heads [n], heads [n][max_heads].
-struct HeadsOut {
-    dh_head *heads = nullptr;
-    uint32_t *n_heads = nullptr;
-    int max_heads = 0;
-    uint32_t radius = 0;
-};
 
 // The heads scratch of the current workspace (Workspace::hd_*, and the support scratch it shares: k_emit's hit windows), allocated
 // and zeroed on the first heads call that needs it; a no-op after that.  Nothing a captured batch points to is touched.
@@ -944,30 +960,57 @@ static int heads_reserve(dh_predictor *p) {
     return DH_OK;
 }
 
-// The device batch behind dh_predict_batch_device and the camera / tracker calls (arguments checked, device selected): one K
-// (cams.c == NULL) or frame i -> camera cams.c0 + i.  Slices and forked sub-batches offset the camera as they offset guesses.
-// With `sup`, every slice and sub-batch also reports its frames' vote support (k_support) into sup->rec, offset like `out`.
-static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const CamSel &cams,
-                        const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out, hipStream_t s,
-                        const SupOut *sup = nullptr, const HeadsOut *hd = nullptr) {
-    const int slice = p->debug ? n : std::min(n, max_resident_frames(p));   // the taps index the whole batch
-    int rc = reserve(p, slice, w, h);
-    if (rc) return rc;
-    if (sup) TRY(support_reserve(p));
-    if (hd) TRY(heads_reserve(p));
-    float kinv[9];
-    if (cams.c) {                // (kernel-argument stand-ins: the CAM instances read the records)
-        K = cams.c->host[cams.c0].k;
-        memcpy(kinv, cams.c->host[cams.c0].kinv, sizeof kinv);
-    } else {
-        dh_mat3_inv_f32_(K, kinv);   // cached in a RefCell by the reference (types.rs:436-441)
-    }
+// ------------------------------------------------------------------ checking a request
+// shared checks of the camera calls: n frames against the table, the table on the predictor's device
+static int cameras_check(const dh_predictor *p, const dh_cameras *c, int n, const char *fn) {
+    if (c->device != p->device) return fail(DH_EINVAL, "%s: camera table on device %d, predictor on device %d", fn, c->device, p->device);
+    if (n > c->n) return fail(DH_EINVAL, "%s: %d frames, the camera table has %d cameras", fn, n, c->n);
+    return DH_OK;
+}
+
+// The checks of a request made by entry point fn, on the host before anything is launched.  An input with several faults
+// reports the first of them in this order:
+//   1. a radius (support, heads) above 2^31 - 1: a negative int passed
+//   2. max_heads (heads) outside 1 .. DH_MAX_HEADS
+//   3. NULL support records (support)
+//   4. any other NULL: the predictor, the input (`input`: the frames or the payloads), K or the camera table, the poses or
+//      the heads and their counts
+//   5. n < 0
+//   6. the camera table: on the predictor's device, a camera for every frame
+//   7. n == 0: nothing to run, DH_OK (run returns before selecting the device)
+static int check_req(const dh_predictor *p, const BatchReq &r, bool input, const char *fn) {
+    if (r.kind != POSES && r.radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u (a negative int?); expected 0 .. 2^31 - 1", fn, r.radius);
+    if (r.kind == HEADS && (r.max_heads < 1 || r.max_heads > DH_MAX_HEADS))
+        return fail(DH_EINVAL, "%s: max_heads %d outside 1 .. %d", fn, r.max_heads, DH_MAX_HEADS);
+    if (r.kind == SUPPORT && !r.support) return fail(DH_EINVAL, "%s: NULL support", fn);
+    if (!p || !input || (!r.K && !r.cams.c) || (r.kind == HEADS ? !r.heads || !r.n_heads : !r.out)) return fail(DH_EINVAL, "%s: NULL argument", fn);
+    if (r.n < 0) return fail(DH_EINVAL, "negative batch size");
+    if (r.cams.c) TRY(cameras_check(p, r.cams.c, r.n, fn));
+    return DH_OK;
+}
+
+// Every prediction entry point: its request checked (check_req), then driver() on the predictor's device.
+template <typename F>
+static int run(dh_predictor *p, const BatchReq &r, bool input, const char *fn, F driver) {
+    TRY(check_req(p, r, input, fn));
+    if (r.n == 0) return DH_OK;
+    DeviceGuard guard(p->device);
+    if (!guard.ok) return DH_EHIP;
+    return driver();
+}
+
+// ------------------------------------------------------------------ the batch drivers
+// The device batch every prediction runs (request checked, device selected): r's arrays are on the device, its kernels go to
+// stream s.  Frames beyond the resident limit run in slices; the slices and forked sub-batches each take their part of r.
+static int batch_device(dh_predictor *p, const BatchReq &r, hipStream_t s) {
+    const int n = r.n, slice = p->debug ? n : std::min(n, max_resident_frames(p));   // the taps index the whole batch
+    TRY(reserve(p, slice, r.w, r.h));
+    if (r.support) TRY(support_reserve(p));
+    if (r.heads) TRY(heads_reserve(p));
     for (int f0 = 0; f0 < n; f0 += slice) {
-        const int m = std::min(slice, n - f0);
-        const uint16_t *fr = frames + (size_t)f0 * w * h;
-        const float *mg = midp_guess ? midp_guess + (size_t)f0 * 3 : nullptr;
-        const double *rg = rot_guess ? rot_guess + (size_t)f0 * 3 : nullptr;
-        const uint8_t *gm = guess_mask ? guess_mask + f0 : nullptr;
+        BatchReq sl = r.at(f0);
+        sl.n = std::min(slice, n - f0);
+        const int m = sl.n;
         // Forked sub-batches: two halves of the slice on two streams let the latency-bound tail kernels of one half run
         // beside the head kernels of the other.  Measured on MI355X: it pays once each half still has >= 256 frames
         // (512 frames per call: 479 k -> 533 k frames/s with 2 chunks, 483 k with 4; 256 frames per call: no gain),
@@ -988,9 +1031,7 @@ static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, i
         if (chunks <= 1) {
             EnqueueOpts o;
             o.profile = p->profiling; o.zero_fold = fold;
-            if (sup) { o.support = sup->rec + f0; o.radius = sup->radius; }
-            if (hd) { o.heads = hd->heads + (size_t)f0 * hd->max_heads; o.n_heads = hd->n_heads + f0; o.max_heads = hd->max_heads; o.radius = hd->radius; }
-            TRY(enqueue_range(p, fr, 0, m, w, h, K, kinv, cams.at(f0), mg, rg, gm, out ? out + f0 : nullptr, s, o));
+            TRY(enqueue_range(p, sl, 0, m, s, o));
         } else {
             HIP_TRY(hipEventRecord(p->ev_fork, s));
             for (int c = 0; c < chunks; ++c) {
@@ -999,9 +1040,7 @@ static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, i
                 if (c > 0) HIP_TRY(hipStreamWaitEvent(cs, p->ev_fork, 0));
                 EnqueueOpts o;
                 o.chunk = c;
-                if (sup) { o.support = sup->rec + f0; o.radius = sup->radius; }
-                if (hd) { o.heads = hd->heads + (size_t)f0 * hd->max_heads; o.n_heads = hd->n_heads + f0; o.max_heads = hd->max_heads; o.radius = hd->radius; }
-                TRY(enqueue_range(p, fr, c0, c1 - c0, w, h, K, kinv, cams.at(f0), mg, rg, gm, out ? out + f0 : nullptr, cs, o));
+                TRY(enqueue_range(p, sl, c0, c1 - c0, cs, o));
                 if (c > 0) {
                     HIP_TRY(hipEventRecord(p->ev_join[c - 1], cs));
                     HIP_TRY(hipStreamWaitEvent(s, p->ev_join[c - 1], 0));
@@ -1010,20 +1049,9 @@ static int batch_device(dh_predictor *p, const uint16_t *frames, int n, int w, i
         }
     }
     p->last_n = std::min(n, slice);   // the taps describe the last resident slice
-    p->last_frames = frames;
-    p->ws.dbg_valid = p->debug && !hd;   // (a heads batch runs no k_cluster of its own: the guess / mean-shift taps are not its)
+    p->last_frames = r.frames;
+    p->ws.dbg_valid = p->debug && !r.heads;   // (a heads batch runs no k_cluster of its own: the guess / mean-shift taps are not its)
     return DH_OK;
-}
-
-static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
-                                       const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
-                                       dh_pose *out, void *stream_) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch_device: NULL argument");
-    if (n == 0) return DH_OK;
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    return batch_device(p, frames, n, w, h, K, CamSel{}, midp_guess, rot_guess, guess_mask, out, (hipStream_t)stream_);
 }
 
 // n frames of w x h in ws.frames
@@ -1040,121 +1068,113 @@ static int stage_frames(dh_predictor *p, const uint16_t *frames, int n, int w, i
     return DH_OK;
 }
 
-// The small host arrays of a slice (poses out; guesses and their mask in) cross PCIe through the predictor's OWN page-locked
-// staging block: the caller's arrays are ordinary pageable memory a few hundred bytes long, typically sharing their pages
-// with other allocations of other host threads, and handing such ranges to the runtime's pageable-copy path (pin the pages,
-// DMA, unpin -- per copy, beside other threads doing the same to neighbouring bytes) is both slower than a pinned copy and
-// the one place where concurrent predictors met inside the runtime.  Layout for m frames: poses | rot guesses | mid guesses | mask.
+// The small host arrays of a slice (guesses and their mask in; poses, support records and heads out: download) cross PCIe
+// through the predictor's OWN page-locked staging blocks: the caller's arrays are ordinary pageable memory a few hundred bytes
+// long, typically sharing their pages with other allocations of other host threads, and handing such ranges to the runtime's
+// pageable-copy path (pin the pages, DMA, unpin -- per copy, beside other threads doing the same to neighbouring bytes) is both
+// slower than a pinned copy and the one place where concurrent predictors met inside the runtime.  Layout for m frames of the
+// inbound block: rot guesses | mid guesses | mask.
 struct SmallStage {
-    dh_pose *poses; double *rot; float *midp; uint8_t *mask;
+    double *rot; float *midp; uint8_t *mask;
 };
 static int small_stage(dh_predictor *p, int m, SmallStage *st) {
-    const size_t need = (size_t)m * (sizeof(dh_pose) + 3 * sizeof(double) + 3 * sizeof(float) + 1) + 64;
+    const size_t need = (size_t)m * (3 * sizeof(double) + 3 * sizeof(float) + 1) + 64;
     TRY(p->pin_small.grow(need));      // (only between slices: both streams are idle)
-    st->poses = (dh_pose *)p->pin_small.get();
-    st->rot = (double *)(st->poses + m);
+    st->rot = (double *)p->pin_small.get();
     st->midp = (float *)(st->rot + (size_t)m * 3);
     st->mask = (uint8_t *)(st->midp + (size_t)m * 3);
     return DH_OK;
 }
-// Per-frame host guesses of a batch, each optional.
-struct Guesses {
-    const float *midp; const double *rot; const uint8_t *mask;
-};
-// Per-slice setup of the host batch paths: the workspace and frame staging for m frames of w x h, and the guesses of
-// frames [f0, f0 + m) through the pinned staging block into the workspace's device arrays on own_stream.
-static int slice_setup(dh_predictor *p, int f0, int m, int w, int h, const Guesses &g, SmallStage *st) {
-    TRY(reserve(p, m, w, h));
-    TRY(ensure_frame_staging(p, m, w, h));
-    TRY(small_stage(p, m, st));
-    hipStream_t s = p->own_stream;
-    if (g.midp) {
-        memcpy(st->midp, g.midp + (size_t)f0 * 3, (size_t)m * 3 * sizeof(float));
-        HIP_TRY(hipMemcpyAsync(p->ws.midp.get(), st->midp, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, s));
-    }
-    if (g.rot) {
-        memcpy(st->rot, g.rot + (size_t)f0 * 3, (size_t)m * 3 * sizeof(double));
-        HIP_TRY(hipMemcpyAsync(p->ws.rot.get(), st->rot, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    }
-    if (g.mask) {
-        memcpy(st->mask, g.mask + f0, (size_t)m);
-        HIP_TRY(hipMemcpyAsync(p->ws.mask.get(), st->mask, (size_t)m, hipMemcpyHostToDevice, s));
-    }
+// count elements of the workspace's src -> the outbound staging block on s, wait, -> the caller's dst
+template <typename T>
+static int download(dh_predictor *p, T *dst, const T *src, size_t count, hipStream_t s) {
+    TRY(p->pin_out.grow(count * sizeof(T)));
+    HIP_TRY(hipMemcpyAsync(p->pin_out.get(), src, count * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(dst, p->pin_out.get(), count * sizeof(T));
     return DH_OK;
 }
-// Chunk [c0, c0 + cm) of a staged slice -- frames, guesses and poses in the workspace -- on stream s; with a camera table
-// (`cams`: the slice's first frame) frame c0 + i reads camera cams.c0 + c0 + i.
-// With `sup` (its records: the slice's, in Workspace::sup) chunk frame c0 + i reports into sup->rec[c0 + i].
-static int predict_staged(dh_predictor *p, int c0, int cm, int w, int h, const float K[9], const CamSel &cams, const Guesses &g, hipStream_t s,
-                          const SupOut *sup = nullptr) {
+
+// Per-slice setup of the host entry points for slice sl (host arrays): the workspace, the output scratch sl asks for and the frame
+// staging for its sl.n frames of sl.w x sl.h, and its guesses through the pinned staging block into the workspace on own_stream.
+// *d is sl on those device buffers; its frames (ws.frames) are the caller's to fill.
+static int slice_setup(dh_predictor *p, const BatchReq &sl, BatchReq *d) {
+    const int m = sl.n;
+    TRY(reserve(p, m, sl.w, sl.h));
+    if (sl.support) TRY(support_reserve(p));
+    if (sl.heads) TRY(heads_reserve(p));
+    TRY(ensure_frame_staging(p, m, sl.w, sl.h));
+    SmallStage st;
+    TRY(small_stage(p, m, &st));
     const Workspace &ws = p->ws;
-    if (sup) {
-        const SupOut so{sup->rec + c0, sup->radius};
-        return batch_device(p, ws.frames.get() + (size_t)c0 * w * h, cm, w, h, cams.c ? nullptr : K, cams.c ? cams.at(c0) : CamSel{},
-                            g.midp ? ws.midp.get() + (size_t)c0 * 3 : nullptr, g.rot ? ws.rot.get() + (size_t)c0 * 3 : nullptr,
-                            g.mask ? ws.mask.get() + c0 : nullptr, ws.poses.get() + c0, s, &so);
+    hipStream_t s = p->own_stream;
+    *d = sl;
+    d->frames = ws.frames.get();
+    d->out = sl.out ? ws.poses.get() : nullptr;
+    d->support = sl.support ? ws.sup.get() : nullptr;
+    d->heads = sl.heads ? ws.hd_out.get() : nullptr;
+    d->n_heads = sl.heads ? ws.hd_n.get() : nullptr;
+    if (sl.midp) {
+        memcpy(st.midp, sl.midp, (size_t)m * 3 * sizeof(float));
+        HIP_TRY(hipMemcpyAsync(ws.midp.get(), st.midp, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, s));
+        d->midp = ws.midp.get();
     }
-    if (cams.c)
-        return batch_device(p, ws.frames.get() + (size_t)c0 * w * h, cm, w, h, nullptr, cams.at(c0), g.midp ? ws.midp.get() + (size_t)c0 * 3 : nullptr,
-                            g.rot ? ws.rot.get() + (size_t)c0 * 3 : nullptr, g.mask ? ws.mask.get() + c0 : nullptr, ws.poses.get() + c0, s);
-    return dh_predict_batch_device(p, ws.frames.get() + (size_t)c0 * w * h, cm, w, h, K, g.midp ? ws.midp.get() + (size_t)c0 * 3 : nullptr,
-                                   g.rot ? ws.rot.get() + (size_t)c0 * 3 : nullptr, g.mask ? ws.mask.get() + c0 : nullptr, ws.poses.get() + c0, s);
-}
-// poses of the slice: device -> staging on s, wait, -> the caller's array
-static int download_poses(dh_predictor *p, const SmallStage &st, int m, dh_pose *out, hipStream_t s) {
-    HIP_TRY(hipMemcpyAsync(st.poses, p->ws.poses.get(), (size_t)m * sizeof(dh_pose), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    memcpy(out, st.poses, (size_t)m * sizeof(dh_pose));
+    if (sl.rot) {
+        memcpy(st.rot, sl.rot, (size_t)m * 3 * sizeof(double));
+        HIP_TRY(hipMemcpyAsync(ws.rot.get(), st.rot, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        d->rot = ws.rot.get();
+    }
+    if (sl.mask) {
+        memcpy(st.mask, sl.mask, (size_t)m);
+        HIP_TRY(hipMemcpyAsync(ws.mask.get(), st.mask, (size_t)m, hipMemcpyHostToDevice, s));
+        d->mask = ws.mask.get();
+    }
     return DH_OK;
 }
-// support records of the slice: Workspace::sup -> pinned staging on s, wait, -> the caller's array (after download_poses)
-static int download_support(dh_predictor *p, int m, dh_support *out, hipStream_t s) {
-    TRY(p->pin_sup.grow((size_t)m));
-    HIP_TRY(hipMemcpyAsync(p->pin_sup.get(), p->ws.sup.get(), (size_t)m * sizeof(dh_support), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    memcpy(out, p->pin_sup.get(), (size_t)m * sizeof(dh_support));
-    return DH_OK;
+// Chunk [c0, c0 + cm) of a staged slice d (slice_setup) on stream s.
+static int predict_staged(dh_predictor *p, const BatchReq &d, int c0, int cm, hipStream_t s) {
+    BatchReq c = d.at(c0);
+    c.n = cm;
+    return batch_device(p, c, s);
 }
-// The slice loop of the host batch paths: enqueue(f0, m, &st) sets slice [f0, f0 + m) up (slice_setup) and enqueues its
-// prediction on own_stream; its poses then come back in one copy (and with `sup`, its support records in a second one).  With
-// the taps on, the whole batch is one slice.
+// The slice loop of the host entry points: enqueue(f0, sl) stages slice sl = r.at(f0) of the request (slice_setup) and enqueues
+// its prediction on own_stream; then each output r asks for -- poses, support records, heads and their counts -- comes back in
+// one copy.  With the taps on, the whole batch is one slice (heads keep their resident slices: their taps are not kept).
 template <typename F>
-static int host_slices(dh_predictor *p, int n, dh_pose *out, F enqueue, dh_support *sup = nullptr) {
-    const int slice = p->debug ? n : std::min(n, max_resident_frames(p));
+static int host_slices(dh_predictor *p, const BatchReq &r, F enqueue) {
+    const int n = r.n, slice = p->debug && !r.heads ? n : std::min(n, max_resident_frames(p));
+    const Workspace &ws = p->ws;
+    hipStream_t s = p->own_stream;
     for (int f0 = 0; f0 < n; f0 += slice) {
-        const int m = std::min(slice, n - f0);
-        SmallStage st;
-        int rc = enqueue(f0, m, &st);
-        if (rc == DH_OK) rc = download_poses(p, st, m, out + f0, p->own_stream);
-        if (rc == DH_OK && sup) rc = download_support(p, m, sup + f0, p->own_stream);
+        BatchReq sl = r.at(f0);
+        sl.n = std::min(slice, n - f0);
+        int rc = enqueue(f0, sl);
+        if (rc == DH_OK && sl.out) rc = download(p, sl.out, ws.poses.get(), sl.n, s);
+        if (rc == DH_OK && sl.support) rc = download(p, sl.support, ws.sup.get(), sl.n, s);
+        if (rc == DH_OK && sl.heads) rc = download(p, sl.heads, ws.hd_out.get(), (size_t)sl.n * sl.max_heads, s);
+        if (rc == DH_OK && sl.heads) rc = download(p, sl.n_heads, ws.hd_n.get(), sl.n, s);
         if (rc) return rc;
     }
     return DH_OK;
 }
 
-// Host entry point.  The frames cross PCIe in chunks on copy_stream while the kernels of the previous chunk run on
+// Host batch of frames.  The frames cross PCIe in chunks on copy_stream while the kernels of the previous chunk run on
 // own_stream (the path is PCIe-bound: 614 KB per frame in, 40 bytes out), so a batch takes about its upload time plus
-// the kernels of the last chunk.  The poses of a slice come back in one copy.
-// With `sup` (the caller's host records, sup->rec[i] for frame i) every slice also reports its vote support.
-static int batch_host(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const CamSel &cams,
-                      const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out,
-                      const SupOut *sup = nullptr) {
-    const Guesses g{midp_guess, rot_guess, guess_mask};
+// the kernels of the last chunk.  A heads batch uploads each slice in one copy.
+static int batch_host(dh_predictor *p, const BatchReq &r) {
     hipStream_t s = p->own_stream, cs = p->copy_stream;
-    const size_t fpx = (size_t)w * h;
-    return host_slices(p, n, out, [&](int f0, int m, SmallStage *st) -> int {
-        int rc = slice_setup(p, f0, m, w, h, g, st);
-        if (rc == DH_OK && sup) rc = support_reserve(p);
-        if (rc) return rc;
-        const SupOut dsup{p->ws.sup.get(), sup ? sup->radius : 0u};     // the slice's records on the device
-        const SupOut *ds = sup ? &dsup : nullptr;
+    const size_t fpx = (size_t)r.w * r.h;
+    return host_slices(p, r, [&](int, const BatchReq &sl) -> int {
+        BatchReq d;
+        TRY(slice_setup(p, sl, &d));
+        const int m = sl.n;
         // the parity taps describe ONE device batch: with them on, the slice is a single chunk
         int cstart[DH_STAGE_EVENTS + 1];
-        const int nchunks = dh_chunk_plan_(m, p->knobs.stage_chunk, p->debug, cstart);
+        const int nchunks = dh_chunk_plan_(m, p->knobs.stage_chunk, p->debug || sl.heads, cstart);
         if (nchunks == 1) {
             // latency path (single frames, small batches): one copy on the compute stream itself
-            HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-            rc = predict_staged(p, 0, m, w, h, K, cams.at(f0), g, s, ds);
+            HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), sl.frames, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+            int rc = predict_staged(p, d, 0, m, s);
             if (rc) { (void)hipStreamSynchronize(s); return rc; }
         } else {
             // Chunk k + 1 is uploaded on copy_stream while the kernels of chunk k run on own_stream.  From page-locked host
@@ -1166,25 +1186,28 @@ static int batch_host(dh_predictor *p, const uint16_t *frames, int n, int w, int
             HIP_TRY(hipStreamWaitEvent(cs, p->ev_slice, 0));          // the previous slice's kernels have read the staging buffer
             for (int k = 0; k < nchunks; ++k) {
                 const int c0 = cstart[k], cm = cstart[k + 1] - c0;
-                HIP_TRY(hipMemcpyAsync(p->ws.frames.get() + (size_t)c0 * fpx, frames + (size_t)(f0 + c0) * fpx, (size_t)cm * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, cs));
+                HIP_TRY(hipMemcpyAsync(p->ws.frames.get() + (size_t)c0 * fpx, sl.frames + (size_t)c0 * fpx, (size_t)cm * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, cs));
                 HIP_TRY(hipEventRecord(p->ev_stage[k], cs));
                 HIP_TRY(hipStreamWaitEvent(s, p->ev_stage[k], 0));
-                rc = predict_staged(p, c0, cm, w, h, K, cams.at(f0), g, s, ds);
+                int rc = predict_staged(p, d, c0, cm, s);
                 if (rc) { (void)hipStreamSynchronize(cs); (void)hipStreamSynchronize(s); return rc; }
             }
         }
         HIP_TRY(hipEventRecord(p->ev_slice, s));
         return DH_OK;
-    }, sup ? sup->rec : nullptr);
+    });
+}
+
+static int predict_batch_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
+                                 const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
+                                 dh_pose *out, void *stream_) {
+    const BatchReq r{frames, n, w, h, K, {}, midp_guess, rot_guess, guess_mask, out};
+    return run(p, r, frames != nullptr, "dh_predict_batch_device", [&] { return batch_device(p, r, (hipStream_t)stream_); });
 }
 static int predict_batch_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
-                                const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch: NULL argument");
-    if (n == 0) return DH_OK;
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    return batch_host(p, frames, n, w, h, K, CamSel{}, midp_guess, rot_guess, guess_mask, out);
+                          const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
+    const BatchReq r{frames, n, w, h, K, {}, midp_guess, rot_guess, guess_mask, out};
+    return run(p, r, frames != nullptr, "dh_predict_batch", [&] { return batch_host(p, r); });
 }
 
 // Page-locked host memory for frame buffers: uploads from it are asynchronous DMA at PCIe speed.
@@ -1269,35 +1292,36 @@ static int biwi_decode_depth_device_(dh_predictor *p, const uint8_t *const *bufs
     return DH_OK;
 }
 
-static int predict_batch_rle_(dh_predictor *p, const uint8_t *const *bufs, const size_t *lens, int n, const float K[9],
-                                    const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
-    if (!p || !bufs || !lens || !K || !out) return fail(DH_EINVAL, "dh_predict_batch_rle: NULL argument");
-    if (n == 0) return DH_OK;
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    const Guesses g{midp_guess, rot_guess, guess_mask};
+// The host batch of payloads: per resident slice the payloads are validated and packed, then decoded chunk by chunk into the
+// frame staging, each chunk predicted as it lands.  The frame size is the slice's decoded one.
+static int rle_host(dh_predictor *p, const BatchReq &r, const uint8_t *const *bufs, const size_t *lens) {
     hipStream_t s = p->own_stream;
-    return host_slices(p, n, out, [&](int f0, int m, SmallStage *st) -> int {
+    return host_slices(p, r, [&](int f0, BatchReq sl) -> int {
         HIP_TRY(hipStreamSynchronize(s));                         // pinned staging and device blob of the previous slice are free
         HIP_TRY(hipStreamSynchronize(p->copy_stream));
+        const int m = sl.n;
         RlePlan plan;
-        int rc = rle_prepare(p, bufs + f0, lens + f0, m, plan);   // validates: nothing launched on failure
-        if (rc) return rc;
+        TRY(rle_prepare(p, bufs + f0, lens + f0, m, plan));       // validates: nothing launched on failure
         const uint32_t W = plan.W, H = plan.H;
-        rc = slice_setup(p, f0, m, (int)W, (int)H, g, st);
-        if (rc) return rc;
+        sl.w = (int)W; sl.h = (int)H;
+        BatchReq d;
+        TRY(slice_setup(p, sl, &d));
         HIP_TRY(hipMemcpyAsync(p->dev_begin.get(), p->pin_begin.get(), ((size_t)m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         const int chunk = p->debug ? m : std::min(m, p->knobs.stage_chunk * 2);   // compressed chunks are small: twice the raw chunk
         int ci = 0;
         for (int c0 = 0; c0 < m; c0 += chunk, ++ci) {
             const int cm = std::min(chunk, m - c0);
-            rc = rle_upload_decode(p, plan.blob_off, c0, cm, ci, W, H, p->ws.frames.get() + (size_t)c0 * W * H, s);
-            if (rc == DH_OK) rc = predict_staged(p, c0, cm, (int)W, (int)H, K, CamSel{}, g, s);
+            int rc = rle_upload_decode(p, plan.blob_off, c0, cm, ci, W, H, p->ws.frames.get() + (size_t)c0 * W * H, s);
+            if (rc == DH_OK) rc = predict_staged(p, d, c0, cm, s);
             if (rc) { (void)hipStreamSynchronize(p->copy_stream); (void)hipStreamSynchronize(s); return rc; }
         }
         return DH_OK;
     });
+}
+static int predict_batch_rle_(dh_predictor *p, const uint8_t *const *bufs, const size_t *lens, int n, const float K[9],
+                              const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
+    const BatchReq r{nullptr, n, 0, 0, K, {}, midp_guess, rot_guess, guess_mask, out};     // (frames and their size: rle_host)
+    return run(p, r, bufs && lens, "dh_predict_batch_rle", [&] { return rle_host(p, r, bufs, lens); });
 }
 
 // ------------------------------------------------------------------ hipGraph capture of one batch
@@ -1312,20 +1336,18 @@ static int graph_destroy_(dh_predictor *p) {
     return DH_OK;
 }
 
-static int graph_capture_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
-                                const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_graph_capture: NULL argument");
-    if (n <= 0) return fail(DH_EINVAL, "batch size must be positive");
+// Captures driver() -- one device batch of r's size on own_stream -- into the predictor's graph slot, replacing what it held: no
+// taps or profiling, every allocation before the capture starts, refused by dh_graph_launch once the workspace is reallocated.
+template <typename F>
+static int capture(dh_predictor *p, const BatchReq &r, F driver) {
     if (p->debug || p->profiling) return fail(DH_ESTATE, "taps / profiling cannot be captured");
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    int rc = reserve(p, std::min(n, max_resident_frames(p)), w, h);   // every allocation happens before the capture starts
-    if (rc) return rc;
-    dh_graph_destroy(p);
+    TRY(reserve(p, std::min(r.n, max_resident_frames(p)), r.w, r.h));
+    drop_graph(p);
+    p->graph_stale = false;
     HIP_TRY(hipStreamSynchronize(p->own_stream));
     HIP_TRY(hipStreamBeginCapture(p->own_stream, hipStreamCaptureModeThreadLocal));
     p->capturing = true;
-    rc = dh_predict_batch_device(p, frames, n, w, h, K, midp_guess, rot_guess, guess_mask, out, p->own_stream);
+    const int rc = driver();
     p->capturing = false;
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(p->own_stream, &g);
@@ -1334,6 +1356,12 @@ static int graph_capture_(dh_predictor *p, const uint16_t *frames, int n, int w,
     p->graph = g;
     HIP_TRY(hipGraphInstantiate(&p->graph_exec, p->graph, nullptr, nullptr, 0));
     return DH_OK;
+}
+static int graph_capture_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
+                          const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
+    if (n == 0) return fail(DH_EINVAL, "dh_graph_capture: batch size must be positive");
+    const BatchReq r{frames, n, w, h, K, {}, midp_guess, rot_guess, guess_mask, out};
+    return run(p, r, frames != nullptr, "dh_graph_capture", [&] { return capture(p, r, [&] { return batch_device(p, r, p->own_stream); }); });
 }
 
 static int graph_launch_(dh_predictor *p, void *stream) {
@@ -1374,31 +1402,15 @@ static int cameras_destroy_(dh_cameras *c) {
     delete c;
     return DH_OK;
 }
-// shared checks of the camera calls: n frames against the table, the table on the predictor's device
-static int cameras_check(const dh_predictor *p, const dh_cameras *c, int n, const char *fn) {
-    if (c->device != p->device) return fail(DH_EINVAL, "%s: camera table on device %d, predictor on device %d", fn, c->device, p->device);
-    if (n > c->n) return fail(DH_EINVAL, "%s: %d frames, the camera table has %d cameras", fn, n, c->n);
-    return DH_OK;
-}
 static int predict_batch_cameras_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
                                          const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out, void *stream) {
-    if (!p || !frames || !c || !out) return fail(DH_EINVAL, "dh_predict_batch_cameras_device: NULL argument");
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    TRY(cameras_check(p, c, n, "dh_predict_batch_cameras_device"));
-    if (n == 0) return DH_OK;
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    return batch_device(p, frames, n, w, h, nullptr, CamSel{c, 0}, midp_guess, rot_guess, guess_mask, out, (hipStream_t)stream);
+    const BatchReq r{frames, n, w, h, nullptr, {c, 0}, midp_guess, rot_guess, guess_mask, out};
+    return run(p, r, frames != nullptr, "dh_predict_batch_cameras_device", [&] { return batch_device(p, r, (hipStream_t)stream); });
 }
 static int predict_batch_cameras_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
                                   const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out) {
-    if (!p || !frames || !c || !out) return fail(DH_EINVAL, "dh_predict_batch_cameras: NULL argument");
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    TRY(cameras_check(p, c, n, "dh_predict_batch_cameras"));
-    if (n == 0) return DH_OK;
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    return batch_host(p, frames, n, w, h, nullptr, CamSel{c, 0}, midp_guess, rot_guess, guess_mask, out);
+    const BatchReq r{frames, n, w, h, nullptr, {c, 0}, midp_guess, rot_guess, guess_mask, out};
+    return run(p, r, frames != nullptr, "dh_predict_batch_cameras", [&] { return batch_host(p, r); });
 }
 
 // A tracker's state is exactly the guess arrays of a camera batch (midp_guess, rot_guess, guess_mask): a step predicts with them
@@ -1454,57 +1466,53 @@ static int tracker_reset_(dh_tracker *t, int camera, void *stream) {
     HIP_TRY(hipMemsetAsync(t->has_rot.get() + c0, 0, m, s));
     return DH_OK;
 }
-// Cameras [c0, c0 + m) of a step (device frames / poses / present of those cameras): their batch with the tracker's guesses, then
-// k_track over their poses, both on stream s.
-// With `sup`, the batch also reports the cameras' vote support; k_track does not read it.
-static int track_enqueue(dh_predictor *p, dh_tracker *t, int c0, int m, const uint16_t *frames, int w, int h, const uint8_t *present,
-                         dh_pose *out, hipStream_t s, const SupOut *sup = nullptr) {
-    TRY(batch_device(p, frames, m, w, h, nullptr, CamSel{t->cams, c0}, t->midp.get() + (size_t)c0 * 3, t->rot.get() + (size_t)c0 * 3,
-                     t->mask.get() + c0, out, s, sup));
+// A step's request: every camera of the tracker (a NULL tracker leaves the camera table NULL: check_req refuses it), poses into
+// `out`; track_enqueue supplies the guesses.
+static BatchReq track_req(const dh_tracker *t, const uint16_t *frames, int w, int h, dh_pose *out) {
+    BatchReq r{frames, t ? t->n : 0, w, h, nullptr, {t ? t->cams : nullptr, 0}};
+    r.out = out;
+    return r;
+}
+// Cameras [c0, c0 + r.n) of a step (r on device buffers, c0 = r.cams.c0): their batch with the tracker's guesses, then k_track
+// over their poses, both on stream s.  k_track reads no support.
+static int track_enqueue(dh_predictor *p, dh_tracker *t, BatchReq r, const uint8_t *present, hipStream_t s) {
+    const size_t c0 = (size_t)r.cams.c0;
+    r.midp = t->midp.get() + c0 * 3; r.rot = t->rot.get() + c0 * 3; r.mask = t->mask.get() + c0;
+    TRY(batch_device(p, r, s));
     TrackArgs a{};
-    a.poses = out; a.present = present; a.n = m; a.flags = t->flags;
-    a.midp = t->midp.get() + (size_t)c0 * 3; a.rot = t->rot.get() + (size_t)c0 * 3; a.mask = t->mask.get() + c0; a.has_rot = t->has_rot.get() + c0;
-    { Range r(p->profiling, "dh:track"); HIP_TRY(dh_launch_track(a, s)); }
+    a.poses = r.out; a.present = present; a.n = r.n; a.flags = t->flags;
+    a.midp = t->midp.get() + c0 * 3; a.rot = t->rot.get() + c0 * 3; a.mask = t->mask.get() + c0; a.has_rot = t->has_rot.get() + c0;
+    { Range rg(p->profiling, "dh:track"); HIP_TRY(dh_launch_track(a, s)); }
     return DH_OK;
 }
-static int tracker_args(const dh_predictor *p, const dh_tracker *t, const uint16_t *frames, const dh_pose *out, const char *fn) {
-    if (!p || !t || !frames || !out) return fail(DH_EINVAL, "%s: NULL argument", fn);
-    return cameras_check(p, t->cams, t->n, fn);
-}
-static int tracker_step_device_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out,
-                                void *stream) {
-    TRY(tracker_args(p, t, frames, out, "dh_tracker_step_device"));
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    return track_enqueue(p, t, 0, t->n, frames, w, h, present, out, (hipStream_t)stream);
-}
-// The host step behind dh_tracker_step and, with `sup` (host records), dh_tracker_step_support.
-static int tracker_step_host(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out,
-                             const SupOut *sup) {
+// The host steps: resident slices of cameras [f0, f0 + m) are staged, predicted and updated, their outputs copied back.
+static int track_host(dh_predictor *p, dh_tracker *t, const BatchReq &r, const uint8_t *present) {
     hipStream_t s = p->own_stream;
-    const size_t fpx = (size_t)w * h;
-    // resident slices of the host batch paths: cameras [f0, f0 + m) are staged, predicted and updated, their poses copied back
-    return host_slices(p, t->n, out, [&](int f0, int m, SmallStage *st) -> int {
-        TRY(slice_setup(p, f0, m, w, h, Guesses{nullptr, nullptr, nullptr}, st));
-        if (sup) TRY(support_reserve(p));
-        const SupOut dsup{p->ws.sup.get(), sup ? sup->radius : 0u};
-        HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    return host_slices(p, r, [&](int f0, const BatchReq &sl) -> int {
+        BatchReq d;
+        TRY(slice_setup(p, sl, &d));
+        const int m = sl.n;
+        HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), sl.frames, (size_t)m * sl.w * sl.h * sizeof(uint16_t), hipMemcpyHostToDevice, s));
         if (present) {
-            memcpy(st->mask, present + f0, (size_t)m);       // (the slice's guess-mask staging: a tracker's guesses are on the device)
-            HIP_TRY(hipMemcpyAsync(t->present.get() + f0, st->mask, (size_t)m, hipMemcpyHostToDevice, s));
+            SmallStage st;
+            TRY(small_stage(p, m, &st));       // (the slice's guess-mask staging: a tracker's guesses are on the device)
+            memcpy(st.mask, present + f0, (size_t)m);
+            HIP_TRY(hipMemcpyAsync(t->present.get() + f0, st.mask, (size_t)m, hipMemcpyHostToDevice, s));
         }
-        int rc = track_enqueue(p, t, f0, m, p->ws.frames.get(), w, h, present ? t->present.get() + f0 : nullptr, p->ws.poses.get(), s,
-                               sup ? &dsup : nullptr);
+        int rc = track_enqueue(p, t, d, present ? t->present.get() + f0 : nullptr, s);
         if (rc) { (void)hipStreamSynchronize(s); return rc; }
         HIP_TRY(hipEventRecord(p->ev_slice, s));
         return DH_OK;
-    }, sup ? sup->rec : nullptr);
+    });
+}
+static int tracker_step_device_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out,
+                                void *stream) {
+    const BatchReq r = track_req(t, frames, w, h, out);
+    return run(p, r, frames != nullptr, "dh_tracker_step_device", [&] { return track_enqueue(p, t, r, present, (hipStream_t)stream); });
 }
 static int tracker_step_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out) {
-    TRY(tracker_args(p, t, frames, out, "dh_tracker_step"));
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    return tracker_step_host(p, t, frames, w, h, present, out, nullptr);
+    const BatchReq r = track_req(t, frames, w, h, out);
+    return run(p, r, frames != nullptr, "dh_tracker_step", [&] { return track_host(p, t, r, present); });
 }
 static int tracker_state_(dh_tracker *t, float *midp, double *rot, uint8_t *flags) {
     if (!t) return fail(DH_EINVAL, "dh_tracker_state: NULL tracker");
@@ -1522,179 +1530,79 @@ static int tracker_state_(dh_tracker *t, float *midp, double *rot, uint8_t *flag
     }
     return DH_OK;
 }
-// One device step captured into the predictor's graph slot (graph_capture_'s rules: no taps or profiling, every allocation before
-// the capture, refused by dh_graph_launch once the workspace is reallocated).
+// One device step captured into the predictor's graph slot (capture).
 static int tracker_capture_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out) {
-    TRY(tracker_args(p, t, frames, out, "dh_tracker_capture"));
-    if (p->debug || p->profiling) return fail(DH_ESTATE, "taps / profiling cannot be captured");
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    TRY(reserve(p, std::min(t->n, max_resident_frames(p)), w, h));
-    dh_graph_destroy(p);
-    HIP_TRY(hipStreamSynchronize(p->own_stream));
-    HIP_TRY(hipStreamBeginCapture(p->own_stream, hipStreamCaptureModeThreadLocal));
-    p->capturing = true;
-    int rc = track_enqueue(p, t, 0, t->n, frames, w, h, present, out, p->own_stream);
-    p->capturing = false;
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(p->own_stream, &g);
-    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-    if (e != hipSuccess) return fail(DH_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-    p->graph = g;
-    HIP_TRY(hipGraphInstantiate(&p->graph_exec, p->graph, nullptr, nullptr, 0));
-    return DH_OK;
+    const BatchReq r = track_req(t, frames, w, h, out);
+    return run(p, r, frames != nullptr, "dh_tracker_capture", [&] { return capture(p, r, [&] { return track_enqueue(p, t, r, present, p->own_stream); }); });
 }
 
 // ------------------------------------------------------------------ vote support
-// The *_support twins of the batch, camera and tracker calls: the same checks, the same batch with k_emit's SUP instance and
-// k_support appended, one dh_support per frame.  A radius that does not fit an int (a negative one passed) is refused first.
-static int support_args(uint32_t radius, const dh_support *support, const char *fn) {
-    if (radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u (a negative int?); expected 0 .. 2^31 - 1", fn, radius);
-    if (!support) return fail(DH_EINVAL, "%s: NULL support", fn);
-    return DH_OK;
-}
+// The *_support twins of the batch, camera and tracker calls: the same request with k_emit's SUP instance and k_support
+// appended, one dh_support per frame.
 static int predict_batch_support_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const float *midp_guess,
                                   const double *rot_guess, const uint8_t *guess_mask, uint32_t radius, dh_pose *out, dh_support *support) {
-    TRY(support_args(radius, support, "dh_predict_batch_support"));
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch_support: NULL argument");
-    if (n == 0) return DH_OK;
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    const SupOut sup{support, radius};
-    return batch_host(p, frames, n, w, h, K, CamSel{}, midp_guess, rot_guess, guess_mask, out, &sup);
+    const BatchReq r{frames, n, w, h, K, {}, midp_guess, rot_guess, guess_mask, out, SUPPORT, radius, support};
+    return run(p, r, frames != nullptr, "dh_predict_batch_support", [&] { return batch_host(p, r); });
 }
 static int predict_batch_support_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9],
                                          const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius,
                                          dh_pose *out, dh_support *support, void *stream) {
-    TRY(support_args(radius, support, "dh_predict_batch_support_device"));
-    if (!p || !frames || !K || !out) return fail(DH_EINVAL, "dh_predict_batch_support_device: NULL argument");
-    if (n == 0) return DH_OK;
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    const SupOut sup{support, radius};
-    return batch_device(p, frames, n, w, h, K, CamSel{}, midp_guess, rot_guess, guess_mask, out, (hipStream_t)stream, &sup);
+    const BatchReq r{frames, n, w, h, K, {}, midp_guess, rot_guess, guess_mask, out, SUPPORT, radius, support};
+    return run(p, r, frames != nullptr, "dh_predict_batch_support_device", [&] { return batch_device(p, r, (hipStream_t)stream); });
 }
 static int predict_batch_cameras_support_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
                                           const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, uint32_t radius,
                                           dh_pose *out, dh_support *support) {
-    TRY(support_args(radius, support, "dh_predict_batch_cameras_support"));
-    if (!p || !frames || !c || !out) return fail(DH_EINVAL, "dh_predict_batch_cameras_support: NULL argument");
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    TRY(cameras_check(p, c, n, "dh_predict_batch_cameras_support"));
-    if (n == 0) return DH_OK;
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    const SupOut sup{support, radius};
-    return batch_host(p, frames, n, w, h, nullptr, CamSel{c, 0}, midp_guess, rot_guess, guess_mask, out, &sup);
+    const BatchReq r{frames, n, w, h, nullptr, {c, 0}, midp_guess, rot_guess, guess_mask, out, SUPPORT, radius, support};
+    return run(p, r, frames != nullptr, "dh_predict_batch_cameras_support", [&] { return batch_host(p, r); });
 }
 static int predict_batch_cameras_support_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
                                                  const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask,
                                                  uint32_t radius, dh_pose *out, dh_support *support, void *stream) {
-    TRY(support_args(radius, support, "dh_predict_batch_cameras_support_device"));
-    if (!p || !frames || !c || !out) return fail(DH_EINVAL, "dh_predict_batch_cameras_support_device: NULL argument");
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    TRY(cameras_check(p, c, n, "dh_predict_batch_cameras_support_device"));
-    if (n == 0) return DH_OK;
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    const SupOut sup{support, radius};
-    return batch_device(p, frames, n, w, h, nullptr, CamSel{c, 0}, midp_guess, rot_guess, guess_mask, out, (hipStream_t)stream, &sup);
+    const BatchReq r{frames, n, w, h, nullptr, {c, 0}, midp_guess, rot_guess, guess_mask, out, SUPPORT, radius, support};
+    return run(p, r, frames != nullptr, "dh_predict_batch_cameras_support_device", [&] { return batch_device(p, r, (hipStream_t)stream); });
 }
 static int tracker_step_support_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
                                  uint32_t radius, dh_pose *out, dh_support *support) {
-    TRY(support_args(radius, support, "dh_tracker_step_support"));
-    TRY(tracker_args(p, t, frames, out, "dh_tracker_step_support"));
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    const SupOut sup{support, radius};
-    return tracker_step_host(p, t, frames, w, h, present, out, &sup);
+    BatchReq r = track_req(t, frames, w, h, out);
+    r.kind = SUPPORT; r.radius = radius; r.support = support;
+    return run(p, r, frames != nullptr, "dh_tracker_step_support", [&] { return track_host(p, t, r, present); });
 }
 static int tracker_step_support_device_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
                                         uint32_t radius, dh_pose *out, dh_support *support, void *stream) {
-    TRY(support_args(radius, support, "dh_tracker_step_support_device"));
-    TRY(tracker_args(p, t, frames, out, "dh_tracker_step_support_device"));
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    const SupOut sup{support, radius};
-    return track_enqueue(p, t, 0, t->n, frames, w, h, present, out, (hipStream_t)stream, &sup);
+    BatchReq r = track_req(t, frames, w, h, out);
+    r.kind = SUPPORT; r.radius = radius; r.support = support;
+    return run(p, r, frames != nullptr, "dh_tracker_step_support_device", [&] { return track_enqueue(p, t, r, present, (hipStream_t)stream); });
 }
 
-// ------------------------------------------------------------------ predict_mask / 2-D Hough votes (SURVEY 8f, N4)
 // ------------------------------------------------------------------ several heads per frame
-// Checked on the host before anything is launched: NULLs, max_heads in 1 .. DH_MAX_HEADS, a radius that fits an int.
-static int heads_args(const dh_predictor *p, const uint16_t *frames, int n, int max_heads, uint32_t radius, const uint32_t *n_heads,
-                      const dh_head *heads, const char *fn) {
-    if (!p || !frames || !n_heads || !heads) return fail(DH_EINVAL, "%s: NULL argument", fn);
-    if (max_heads < 1 || max_heads > DH_MAX_HEADS) return fail(DH_EINVAL, "%s: max_heads %d outside 1 .. %d", fn, max_heads, DH_MAX_HEADS);
-    if (radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u above 2^31 - 1", fn, radius);
-    if (n < 0) return fail(DH_EINVAL, "negative batch size");
-    return DH_OK;
-}
-// The host calls: per resident slice, the frames go up, the device batch runs, the heads and counts come back.
-static int heads_host(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_cameras *c, int max_heads,
-                      uint32_t radius, uint32_t *n_heads, dh_head *heads) {
-    const int slice = std::min(n, max_resident_frames(p));
-    hipStream_t s = p->own_stream;
-    for (int f0 = 0; f0 < n; f0 += slice) {
-        const int m = std::min(slice, n - f0);
-        TRY(reserve(p, m, w, h));
-        TRY(ensure_frame_staging(p, m, w, h));
-        TRY(heads_reserve(p));
-        const size_t fpx = (size_t)w * h;
-        HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), frames + (size_t)f0 * fpx, (size_t)m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        const HeadsOut ho{p->ws.hd_out.get(), p->ws.hd_n.get(), max_heads, radius};
-        int rc = batch_device(p, p->ws.frames.get(), m, w, h, c ? nullptr : K, c ? CamSel{c, f0} : CamSel{}, nullptr, nullptr, nullptr,
-                              nullptr, s, nullptr, &ho);
-        if (rc) { (void)hipStreamSynchronize(s); return rc; }
-        HIP_TRY(hipMemcpyAsync(heads + (size_t)f0 * max_heads, p->ws.hd_out.get(), (size_t)m * max_heads * sizeof(dh_head), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(n_heads + f0, p->ws.hd_n.get(), (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return DH_OK;
-}
+// n_heads [n] and heads [n][max_heads] in place of the poses.
 static int predict_heads_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], int max_heads, uint32_t radius,
                           uint32_t *n_heads, dh_head *heads) {
-    TRY(heads_args(p, frames, n, max_heads, radius, n_heads, heads, "dh_predict_heads"));
-    if (!K) return fail(DH_EINVAL, "dh_predict_heads: NULL argument");
-    if (n == 0) return DH_OK;
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    return heads_host(p, frames, n, w, h, K, nullptr, max_heads, radius, n_heads, heads);
+    BatchReq r{frames, n, w, h, K};
+    r.kind = HEADS; r.radius = radius; r.heads = heads; r.n_heads = n_heads; r.max_heads = max_heads;
+    return run(p, r, frames != nullptr, "dh_predict_heads", [&] { return batch_host(p, r); });
 }
 static int predict_heads_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], int max_heads,
                                  uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream) {
-    TRY(heads_args(p, frames, n, max_heads, radius, n_heads, heads, "dh_predict_heads_device"));
-    if (!K) return fail(DH_EINVAL, "dh_predict_heads_device: NULL argument");
-    if (n == 0) return DH_OK;
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    const HeadsOut ho{heads, n_heads, max_heads, radius};
-    return batch_device(p, frames, n, w, h, K, CamSel{}, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr, &ho);
+    BatchReq r{frames, n, w, h, K};
+    r.kind = HEADS; r.radius = radius; r.heads = heads; r.n_heads = n_heads; r.max_heads = max_heads;
+    return run(p, r, frames != nullptr, "dh_predict_heads_device", [&] { return batch_device(p, r, (hipStream_t)stream); });
 }
 static int predict_heads_cameras_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads,
                                   uint32_t radius, uint32_t *n_heads, dh_head *heads) {
-    TRY(heads_args(p, frames, n, max_heads, radius, n_heads, heads, "dh_predict_heads_cameras"));
-    if (!c) return fail(DH_EINVAL, "dh_predict_heads_cameras: NULL argument");
-    TRY(cameras_check(p, c, n, "dh_predict_heads_cameras"));
-    if (n == 0) return DH_OK;
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    return heads_host(p, frames, n, w, h, nullptr, c, max_heads, radius, n_heads, heads);
+    BatchReq r{frames, n, w, h, nullptr, {c, 0}};
+    r.kind = HEADS; r.radius = radius; r.heads = heads; r.n_heads = n_heads; r.max_heads = max_heads;
+    return run(p, r, frames != nullptr, "dh_predict_heads_cameras", [&] { return batch_host(p, r); });
 }
 static int predict_heads_cameras_device_(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads,
                                          uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream) {
-    TRY(heads_args(p, frames, n, max_heads, radius, n_heads, heads, "dh_predict_heads_cameras_device"));
-    if (!c) return fail(DH_EINVAL, "dh_predict_heads_cameras_device: NULL argument");
-    TRY(cameras_check(p, c, n, "dh_predict_heads_cameras_device"));
-    if (n == 0) return DH_OK;
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return DH_EHIP;
-    const HeadsOut ho{heads, n_heads, max_heads, radius};
-    return batch_device(p, frames, n, w, h, nullptr, CamSel{c, 0}, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr, &ho);
+    BatchReq r{frames, n, w, h, nullptr, {c, 0}};
+    r.kind = HEADS; r.radius = radius; r.heads = heads; r.n_heads = n_heads; r.max_heads = max_heads;
+    return run(p, r, frames != nullptr, "dh_predict_heads_cameras_device", [&] { return batch_device(p, r, (hipStream_t)stream); });
 }
 
+// ------------------------------------------------------------------ predict_mask / 2-D Hough votes (SURVEY 8f, N4)
 static int aux_reserve(dh_predictor *p, int n, int w, int h, size_t out_bytes) {
     TRY(reserve(p, n, w, h));
     Workspace &ws = p->ws;
@@ -1741,7 +1649,7 @@ static int aux_run(dh_predictor *p, unsigned req, const uint16_t *frames, int n,
     HIP_TRY(hipMemsetAsync(ws.aux_flags.get(), 0, (size_t)n * std::max(g.npatch, 1), s));
     EnqueueOpts o;
     o.leaf_out = ws.aux_leaf.get(); o.flags_out = ws.aux_flags.get(); o.traverse_only = true;
-    TRY(enqueue_range(p, frames, 0, n, w, h, K ? K : kid, kinv, CamSel{}, nullptr, nullptr, nullptr, ws.poses.get(), s, o));
+    TRY(enqueue_range(p, BatchReq{frames, n, w, h, K ? K : kid}, 0, n, s, o));
     AuxArgs a{};
     a.frames = frames; a.n_frames = n; a.w = w; a.h = h;
     a.step = (int)p->params.stepwidth; a.sw = (int)p->params.subimage_width; a.sh = (int)p->params.subimage_height;
@@ -1785,14 +1693,12 @@ static int aux_call(dh_predictor *p, const char *fn, unsigned req, const uint16_
         const int m = std::min(slice, n - f0);
         const size_t ob = (size_t)m * px * opx;
         uint8_t *dst = poses ? nullptr : (uint8_t *)out + f0 * px * opx;     // the caller's images of the slice
-        SmallStage st;
         rc = aux_reserve(p, m, w, h, host || poses ? ob : 0);    // (host twins and poses: the image goes to the scratch output)
         if (rc == DH_OK && host) rc = stage_frames(p, frames + f0 * px, m, w, h);
-        if (rc == DH_OK && host && poses) rc = small_stage(p, m, &st);
         if (rc == DH_OK)
             rc = aux_run(p, req, host ? p->ws.frames.get() : frames + f0 * px, m, w, h, K, host || poses ? p->ws.aux_out.get() : dst,
                          !poses ? nullptr : host ? p->ws.poses.get() : (dh_pose *)out + f0, s);
-        if (rc == DH_OK && host && poses) rc = download_poses(p, st, m, (dh_pose *)out + f0, s);
+        if (rc == DH_OK && host && poses) rc = download(p, (dh_pose *)out + f0, p->ws.poses.get(), m, s);
         if (rc) return rc;
         if (host && !poses) {
             HIP_TRY(hipMemcpyAsync(dst, p->ws.aux_out.get(), ob, hipMemcpyDeviceToHost, s));

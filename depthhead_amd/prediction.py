@@ -34,6 +34,15 @@ def _host_frames(img):
     return frames, single, n, h, w
 
 
+def _batch_frames(frames):
+    """A batch [n, H, W] -> (frames [n, H, W] uint16, n, h, w); anything else is a ValueError."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint16)
+    if frames.ndim != 3:
+        raise ValueError("frames must be [n, H, W]")
+    n, h, w = frames.shape
+    return frames, n, h, w
+
+
 def _kmat(intrinsic: "IntrinsicMatrix"):
     """The camera matrix as a C float[9]: passed as an argument, it lives until the call returns."""
     return (C.c_float * 9).from_buffer_copy(np.ascontiguousarray(intrinsic.mat, dtype=np.float32).reshape(9))
@@ -176,10 +185,7 @@ class HoughPrediction:
     def predict_batch(self, frames, intrinsic: IntrinsicMatrix, midp_guess=None, rot_guess=None, guess_mask=None) -> np.ndarray:
         """Host frames [n, H, W] uint16 -> POSE_DTYPE[n].  Guess arrays are [n, 3] or None;
         guess_mask [n] uint8 (bit0 mid, bit1 rot) marks which frames carry a guess."""
-        frames = np.ascontiguousarray(frames, dtype=np.uint16)
-        if frames.ndim != 3:
-            raise ValueError("frames must be [n, H, W]")
-        n, h, w = frames.shape
+        frames, n, h, w = _batch_frames(frames)
         mg, rg, gm = _guesses(n, midp_guess, rot_guess, guess_mask)
         out = np.zeros(n, dtype=POSE_DTYPE)
         check(self._lib.dh_predict_batch(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), _kmat(intrinsic), vp(mg),
@@ -189,10 +195,7 @@ class HoughPrediction:
     def predict_batch_cameras(self, frames, cameras, midp_guess=None, rot_guess=None, guess_mask=None) -> np.ndarray:
         """Host frames [n, H, W] uint16, frame i seen by camera i of `cameras` (`tracking.Cameras`, n <= its count) ->
         POSE_DTYPE[n].  Guesses as `predict_batch`."""
-        frames = np.ascontiguousarray(frames, dtype=np.uint16)
-        if frames.ndim != 3:
-            raise ValueError("frames must be [n, H, W]")
-        n, h, w = frames.shape
+        frames, n, h, w = _batch_frames(frames)
         mg, rg, gm = _guesses(n, midp_guess, rot_guess, guess_mask)
         out = np.zeros(n, dtype=POSE_DTYPE)
         check(self._lib.dh_predict_batch_cameras(self._ph, vp(frames), C.c_int(n), C.c_int(w), C.c_int(h), cameras._h, vp(mg),
@@ -212,10 +215,7 @@ class HoughPrediction:
                               rot_guess=None, guess_mask=None) -> tuple[np.ndarray, np.ndarray]:
         """`predict_batch` that also reports each pose's vote support: -> (POSE_DTYPE[n], SUPPORT_DTYPE[n]).  The poses are
         byte-identical to `predict_batch`'s."""
-        frames = np.ascontiguousarray(frames, dtype=np.uint16)
-        if frames.ndim != 3:
-            raise ValueError("frames must be [n, H, W]")
-        n, h, w = frames.shape
+        frames, n, h, w = _batch_frames(frames)
         mg, rg, gm = _guesses(n, midp_guess, rot_guess, guess_mask)
         out = np.zeros(n, dtype=POSE_DTYPE)
         sup = np.zeros(n, dtype=SUPPORT_DTYPE)
@@ -234,10 +234,7 @@ class HoughPrediction:
     def predict_batch_cameras_support(self, frames, cameras, radius: int = SUPPORT_RADIUS, midp_guess=None, rot_guess=None,
                                       guess_mask=None) -> tuple[np.ndarray, np.ndarray]:
         """`predict_batch_cameras` with each pose's vote support: -> (POSE_DTYPE[n], SUPPORT_DTYPE[n])."""
-        frames = np.ascontiguousarray(frames, dtype=np.uint16)
-        if frames.ndim != 3:
-            raise ValueError("frames must be [n, H, W]")
-        n, h, w = frames.shape
+        frames, n, h, w = _batch_frames(frames)
         mg, rg, gm = _guesses(n, midp_guess, rot_guess, guess_mask)
         out = np.zeros(n, dtype=POSE_DTYPE)
         sup = np.zeros(n, dtype=SUPPORT_DTYPE)
