@@ -29,6 +29,17 @@ HEAD_DTYPE = np.dtype([("pose", POSE_DTYPE), ("support", SUPPORT_DTYPE)], align=
 assert HEAD_DTYPE.itemsize == 80 and HEAD_DTYPE.fields["support"][1] == 40
 MAX_HEADS = 4          # DH_MAX_HEADS
 HEADS_SUPPRESS = 2     # DH_HEADS_SUPPRESS (guess-grid cells)
+# dh_head_track: one track slot of a multi-head tracker (dh_multi_tracker_*): id (0 = free), counters and its last head
+TRACK_DTYPE = np.dtype([("id", "<u4"), ("age", "<u4"), ("hits", "<u4"), ("misses", "<u4"), ("head", HEAD_DTYPE)], align=True)
+assert TRACK_DTYPE.itemsize == 96 and TRACK_DTYPE.fields["head"][1] == 16
+MAX_TRACKS = 8             # DH_MAX_TRACKS
+TRACK_GATE = 100           # DH_TRACK_GATE (cells = mm)
+TRACK_MAX_MISSES = 3       # DH_TRACK_MAX_MISSES
+
+
+class MultiTrackParams(C.Structure):
+    """dh_multi_track_params"""
+    _fields_ = [("max_heads", C.c_int32), ("radius", C.c_uint32), ("gate", C.c_uint32), ("max_misses", C.c_uint32)]
 
 
 class ForestDesc(C.Structure):
@@ -66,6 +77,8 @@ EXPORTS = [
     "dh_predict_batch_support", "dh_predict_batch_support_device", "dh_predict_batch_cameras_support",
     "dh_predict_batch_cameras_support_device", "dh_tracker_step_support", "dh_tracker_step_support_device",
     "dh_predict_heads", "dh_predict_heads_device", "dh_predict_heads_cameras", "dh_predict_heads_cameras_device",
+    "dh_multi_tracker_create", "dh_multi_tracker_destroy", "dh_multi_tracker_reset", "dh_multi_tracker_step",
+    "dh_multi_tracker_step_device", "dh_multi_tracker_state", "dh_multi_tracker_capture",
 ]
 
 

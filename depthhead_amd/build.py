@@ -17,8 +17,10 @@ LIB_KNOBS = os.path.join(HERE, "libdepthhead_hip_knobs.so")
 # host runtime, host-only logic (plain C++: also built with g++ under sanitizers by tests/test_host_sanitize.py), one
 # translation unit per kernel family
 SOURCES = ["dh_api.hip", "dh_host.cpp", "dh_biwi.cpp", "k_forest.hip", "k_prepare.hip", "k_traverse.hip", "k_emit.hip",
-           "k_vote.hip", "k_cluster.hip", "k_aux.hip", "dh_train.cpp", "k_train.hip", "k_track.hip", "k_support.hip", "k_heads.hip"]
-HEADERS = ["dh_internal.h", "dh_host.h", "dh_train.h", "dh_device.h", "dh_track.h", os.path.join("..", "..", "include", "depthhead_hip.h")]
+           "k_vote.hip", "k_cluster.hip", "k_aux.hip", "dh_train.cpp", "k_train.hip", "k_track.hip", "k_support.hip", "k_heads.hip",
+           "k_track_heads.hip"]
+HEADERS = ["dh_internal.h", "dh_host.h", "dh_train.h", "dh_device.h", "dh_track.h", "dh_track_heads.h",
+           os.path.join("..", "..", "include", "depthhead_hip.h")]
 
 # -ffp-contract=off: no FMA contraction on host or device -- every float expression keeps the
 # reference's separate multiply / add rounding (the kernels additionally use explicit *_rn

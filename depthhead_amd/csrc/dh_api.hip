@@ -1602,6 +1602,146 @@ static int predict_heads_cameras_device_(dh_predictor *p, const uint16_t *frames
     return run(p, r, frames != nullptr, "dh_predict_heads_cameras_device", [&] { return batch_device(p, r, (hipStream_t)stream); });
 }
 
+// ------------------------------------------------------------------ several heads per camera with identities
+// A multi-head tracker's state: DH_MAX_TRACKS track records and the next id per camera.  A step is a heads camera batch followed
+// by k_track_heads (dh_track_heads.h) over its heads.
+struct dh_multi_tracker {
+    const dh_cameras *cams = nullptr;
+    int n = 0;
+    dh_multi_track_params prm{};
+    Buf<dh_head_track> tracks;   // [n][DH_MAX_TRACKS]
+    Buf<uint32_t> next_id;       // [n]
+    Buf<uint8_t> present;        // [n] host steps: the caller's present bytes on the device
+    Buf<uint32_t> ids;           // [n][max_heads] host steps: the ids before their copy back
+};
+static int multi_params_check(const dh_multi_track_params *prm, const char *fn) {
+    if (prm->max_heads < 1 || prm->max_heads > DH_MAX_HEADS)
+        return fail(DH_EINVAL, "%s: max_heads %d outside 1 .. %d", fn, prm->max_heads, DH_MAX_HEADS);
+    if (prm->radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u (a negative int?); expected 0 .. 2^31 - 1", fn, prm->radius);
+    if (prm->gate > 0x7fffffffu) return fail(DH_EINVAL, "%s: gate %u (a negative int?); expected 0 .. 2^31 - 1", fn, prm->gate);
+    return DH_OK;
+}
+// tracks of cameras [c0, c0 + m) zeroed and their next ids 1, on stream s
+static int multi_tracker_clear(dh_multi_tracker *t, size_t c0, size_t m, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(t->tracks.get() + c0 * DH_MAX_TRACKS, 0, m * DH_MAX_TRACKS * sizeof(dh_head_track), s));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(t->next_id.get() + c0), 1, m, s));
+    return DH_OK;
+}
+static int multi_tracker_create_(const dh_cameras *c, const dh_multi_track_params *prm, dh_multi_tracker **out) {
+    if (!prm || !out) return fail(DH_EINVAL, "dh_multi_tracker_create: NULL argument");
+    *out = nullptr;
+    TRY(multi_params_check(prm, "dh_multi_tracker_create"));
+    if (!c) return fail(DH_EINVAL, "dh_multi_tracker_create: NULL camera table");
+    DeviceGuard guard(c->device);
+    if (!guard.ok) return DH_EHIP;
+    std::unique_ptr<dh_multi_tracker> t(new dh_multi_tracker);
+    t->cams = c; t->n = c->n; t->prm = *prm;
+    const size_t n = (size_t)c->n;
+    TRY(t->tracks.alloc(n * DH_MAX_TRACKS));
+    TRY(t->next_id.alloc(n));
+    TRY(t->present.alloc(n));
+    TRY(t->ids.alloc(n * (size_t)prm->max_heads));
+    TRY(multi_tracker_clear(t.get(), 0, n, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    *out = t.release();
+    return DH_OK;
+}
+static int multi_tracker_destroy_(dh_multi_tracker *t) {
+    if (!t) return DH_OK;
+    DeviceGuard guard(t->cams->device);
+    delete t;
+    return DH_OK;
+}
+static int multi_tracker_reset_(dh_multi_tracker *t, int camera, void *stream) {
+    if (!t) return fail(DH_EINVAL, "dh_multi_tracker_reset: NULL tracker");
+    if (camera < -1 || camera >= t->n) return fail(DH_EINVAL, "dh_multi_tracker_reset: camera %d of %d", camera, t->n);
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    const size_t c0 = camera < 0 ? 0 : (size_t)camera, m = camera < 0 ? (size_t)t->n : 1;
+    return multi_tracker_clear(t, c0, m, (hipStream_t)stream);
+}
+// A step's request: a heads camera batch of every camera of the tracker with its max_heads and radius.
+static BatchReq multi_track_req(const dh_multi_tracker *t, const uint16_t *frames, int w, int h, uint32_t *n_heads, dh_head *heads) {
+    BatchReq r{frames, t->n, w, h, nullptr, {t->cams, 0}};
+    r.kind = HEADS; r.radius = t->prm.radius; r.heads = heads; r.n_heads = n_heads; r.max_heads = t->prm.max_heads;
+    return r;
+}
+// Cameras [c0, c0 + r.n) of a step (r on device buffers, c0 = r.cams.c0): their heads batch, then k_track_heads over their heads,
+// both on stream s.  present, ids and tracks are the arrays of the whole camera table (present and tracks nullable).
+static int multi_track_enqueue(dh_predictor *p, dh_multi_tracker *t, const BatchReq &r, const uint8_t *present, uint32_t *ids,
+                               dh_head_track *tracks, hipStream_t s) {
+    const size_t c0 = (size_t)r.cams.c0;
+    TRY(batch_device(p, r, s));
+    TrackHeadsArgs a{};
+    a.heads = r.heads; a.n_heads = r.n_heads; a.present = off(present, c0);
+    a.state = t->tracks.get() + c0 * DH_MAX_TRACKS; a.next_id = t->next_id.get() + c0;
+    a.ids = ids + c0 * (size_t)r.max_heads; a.snapshot = off(tracks, c0 * DH_MAX_TRACKS);
+    a.n = r.n; a.max_heads = r.max_heads; a.gate = t->prm.gate; a.max_misses = t->prm.max_misses;
+    { Range rg(p->profiling, "dh:track_heads"); HIP_TRY(dh_launch_track_heads(a, s)); }
+    return DH_OK;
+}
+// The host steps: resident slices of cameras [f0, f0 + m) are staged, predicted and matched; their ids and track records come
+// back through the pinned staging block after the slice's kernels, its heads and their counts in host_slices' copy.
+static int multi_track_host(dh_predictor *p, dh_multi_tracker *t, const BatchReq &r, const uint8_t *present, uint32_t *ids,
+                            dh_head_track *tracks) {
+    hipStream_t s = p->own_stream;
+    const size_t mh = (size_t)r.max_heads;
+    return host_slices(p, r, [&](int f0, const BatchReq &sl) -> int {
+        BatchReq d;
+        TRY(slice_setup(p, sl, &d));
+        const int m = sl.n;
+        HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), sl.frames, (size_t)m * sl.w * sl.h * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        if (present) {
+            SmallStage st;
+            TRY(small_stage(p, m, &st));       // (the slice's guess-mask staging: the heads calls take no guesses)
+            memcpy(st.mask, present + f0, (size_t)m);
+            HIP_TRY(hipMemcpyAsync(t->present.get() + f0, st.mask, (size_t)m, hipMemcpyHostToDevice, s));
+        }
+        int rc = multi_track_enqueue(p, t, d, present ? t->present.get() : nullptr, t->ids.get(), nullptr, s);
+        if (rc) { (void)hipStreamSynchronize(s); return rc; }
+        HIP_TRY(hipEventRecord(p->ev_slice, s));
+        TRY(download(p, ids + (size_t)f0 * mh, t->ids.get() + (size_t)f0 * mh, (size_t)m * mh, s));
+        if (tracks) TRY(download(p, tracks + (size_t)f0 * DH_MAX_TRACKS, t->tracks.get() + (size_t)f0 * DH_MAX_TRACKS, (size_t)m * DH_MAX_TRACKS, s));
+        return DH_OK;
+    });
+}
+static int multi_tracker_step_device_(dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                      uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks, void *stream) {
+    if (!t || !ids) return fail(DH_EINVAL, "dh_multi_tracker_step_device: NULL argument");
+    const BatchReq r = multi_track_req(t, frames, w, h, n_heads, heads);
+    return run(p, r, frames != nullptr, "dh_multi_tracker_step_device",
+               [&] { return multi_track_enqueue(p, t, r, present, ids, tracks, (hipStream_t)stream); });
+}
+static int multi_tracker_step_(dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                               uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks) {
+    if (!t || !ids) return fail(DH_EINVAL, "dh_multi_tracker_step: NULL argument");
+    const BatchReq r = multi_track_req(t, frames, w, h, n_heads, heads);
+    return run(p, r, frames != nullptr, "dh_multi_tracker_step", [&] { return multi_track_host(p, t, r, present, ids, tracks); });
+}
+static int multi_tracker_state_(dh_multi_tracker *t, dh_head_track *tracks, uint32_t *next_id) {
+    if (!t) return fail(DH_EINVAL, "dh_multi_tracker_state: NULL tracker");
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    HIP_TRY(hipDeviceSynchronize());          // the steps may run on any stream of the device
+    const size_t n = (size_t)t->n;
+    if (tracks) HIP_TRY(hipMemcpy(tracks, t->tracks.get(), n * DH_MAX_TRACKS * sizeof(dh_head_track), hipMemcpyDeviceToHost));
+    if (next_id) HIP_TRY(hipMemcpy(next_id, t->next_id.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return DH_OK;
+}
+// One device step captured into the predictor's graph slot (capture).  capture() reserves the workspace but not the heads scratch:
+// both are made here first, so that nothing is allocated while the stream captures.
+static int multi_tracker_capture_(dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                  uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks) {
+    if (!t || !ids) return fail(DH_EINVAL, "dh_multi_tracker_capture: NULL argument");
+    const BatchReq r = multi_track_req(t, frames, w, h, n_heads, heads);
+    return run(p, r, frames != nullptr, "dh_multi_tracker_capture", [&] {
+        if (p->debug || p->profiling) return fail(DH_ESTATE, "taps / profiling cannot be captured");
+        TRY(reserve(p, std::min(r.n, max_resident_frames(p)), r.w, r.h));
+        TRY(heads_reserve(p));
+        return capture(p, r, [&] { return multi_track_enqueue(p, t, r, present, ids, tracks, p->own_stream); });
+    });
+}
+
 // ------------------------------------------------------------------ predict_mask / 2-D Hough votes
 static int aux_reserve(dh_predictor *p, int n, int w, int h, size_t out_bytes) {
     TRY(reserve(p, n, w, h));
@@ -2190,4 +2330,11 @@ DH_API(predict_heads, (dh_predictor *p, const uint16_t *frames, int n, int w, in
 DH_API(predict_heads_device, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const float K[9], int max_heads, uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream), (p, frames, n, w, h, K, max_heads, radius, n_heads, heads, stream))
 DH_API(predict_heads_cameras, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads, uint32_t radius, uint32_t *n_heads, dh_head *heads), (p, frames, n, w, h, c, max_heads, radius, n_heads, heads))
 DH_API(predict_heads_cameras_device, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads, uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream), (p, frames, n, w, h, c, max_heads, radius, n_heads, heads, stream))
+DH_API(multi_tracker_create, (const dh_cameras *c, const dh_multi_track_params *prm, dh_multi_tracker **out), (c, prm, out))
+DH_API(multi_tracker_destroy, (dh_multi_tracker *t), (t))
+DH_API(multi_tracker_reset, (dh_multi_tracker *t, int camera, void *stream), (t, camera, stream))
+DH_API(multi_tracker_step, (dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks), (p, t, frames, w, h, present, n_heads, heads, ids, tracks))
+DH_API(multi_tracker_step_device, (dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks, void *stream), (p, t, frames, w, h, present, n_heads, heads, ids, tracks, stream))
+DH_API(multi_tracker_state, (dh_multi_tracker *t, dh_head_track *tracks, uint32_t *next_id), (t, tracks, next_id))
+DH_API(multi_tracker_capture, (dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks), (p, t, frames, w, h, present, n_heads, heads, ids, tracks))
 #undef DH_API

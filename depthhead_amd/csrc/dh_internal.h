@@ -275,6 +275,19 @@ struct TrackArgs {
     uint32_t flags;         // DH_TRACK_*
 };
 
+// k_track_heads: one multi-head tracker step's matching (dh_track_heads.h) for cameras [0, n) of a step, after k_heads_finish.
+struct TrackHeadsArgs {
+    const dh_head *heads;     // [n][max_heads] the step's heads
+    const uint32_t *n_heads;  // [n]
+    const uint8_t *present;   // nullable [n]: only cameras whose byte is non-zero are matched
+    dh_head_track *state;     // [n][DH_MAX_TRACKS] the tracks
+    uint32_t *next_id;        // [n]
+    uint32_t *ids;            // [n][max_heads]
+    dh_head_track *snapshot;  // nullable [n][DH_MAX_TRACKS]: the tracks after the step
+    int n, max_heads;
+    uint32_t gate, max_misses;
+};
+
 struct VotesDumpArgs {
     int frame, which;
     DevForest f;
@@ -460,6 +473,7 @@ hipError_t dh_launch_heads_support(const HeadsArgs &a, hipStream_t s);
 hipError_t dh_launch_heads_finish(const HeadsArgs &a, hipStream_t s);
 hipError_t dh_launch_votes_dump(const VotesDumpArgs &a, hipStream_t s);
 hipError_t dh_launch_track(const TrackArgs &a, hipStream_t s);
+hipError_t dh_launch_track_heads(const TrackHeadsArgs &a, hipStream_t s);
 hipError_t dh_launch_boxsum(const BoxArgs &a, hipStream_t s);
 hipError_t dh_launch_pixflags(const PixFlagArgs &a, hipStream_t s);
 hipError_t dh_launch_top_build(const DevForest &f, const void *nodes_a, uint32_t n_amb, int top_levels, uint32_t *out, hipStream_t s);

@@ -4,6 +4,8 @@
   (`HoughPrediction.predict_batch_cameras`) is seen by camera i.
 * `HeadTracker(hp, cameras, w, h, prev_guess, sluggish)`: the reference's live loop (examples/live_prediction.rs:79-101) for
   one frame per camera per step -- each camera's pose becomes that camera's next guess without leaving the device.
+* `MultiHeadTracker(hp, cameras, w, h, max_heads, radius, gate, max_misses)`: up to MAX_HEADS heads per camera per step, each
+  with an id that lasts across steps, matched on the device (dh_multi_tracker).
 """
 from __future__ import annotations
 
@@ -12,7 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import POSE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, check, vp
+from ._lib import (HEAD_DTYPE, MAX_HEADS, MAX_TRACKS, POSE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, TRACK_DTYPE, TRACK_GATE,
+                   TRACK_MAX_MISSES, MultiTrackParams, check, vp)
 from .prediction import _radius
 
 TRACK_PREV_GUESS = 1   # DH_TRACK_PREV_GUESS: live_prediction --prevguess
@@ -131,6 +134,84 @@ class HeadTracker:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.dh_tracker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class MultiHeadTracker:
+    """Several heads per camera with identities that last across steps (include/depthhead_hip.h: dh_multi_tracker, DESIGN.md
+    section 15).  Each step runs the heads pipeline on one frame per camera and matches its heads to the camera's tracks on the
+    device: every head gets a u32 id, 0 for none.  The state (TRACK_DTYPE [n, MAX_TRACKS] and the next id [n]) stays on the
+    device.  Steps of one tracker must be stream-ordered.  The camera table must outlive the tracker."""
+
+    def __init__(self, hp, cameras: Cameras, w: int, h: int, max_heads: int = MAX_HEADS, radius: int = SUPPORT_RADIUS,
+                 gate: int = TRACK_GATE, max_misses: int = TRACK_MAX_MISSES):
+        self._lib = _lib.load()
+        self.hp, self.cameras, self.w, self.h = hp, cameras, int(w), int(h)
+        self.n = len(cameras)
+        self.max_heads = int(max_heads)
+        self.params = MultiTrackParams(self.max_heads, _radius(radius).value, _radius(gate).value,
+                                       int(max_misses) & 0xFFFFFFFF)
+        self._h = C.c_void_p()
+        check(self._lib.dh_multi_tracker_create(cameras._h, C.byref(self.params), C.byref(self._h)))
+        hp.reserve(self.n, self.w, self.h)
+
+    def step(self, frames, present=None, tracks: bool = True):
+        """Host frames [n_cams, h, w] uint16 -> (n_heads u32 [n_cams], HEAD_DTYPE [n_cams, max_heads], ids u32 [n_cams,
+        max_heads], TRACK_DTYPE [n_cams, MAX_TRACKS] after the step, or None with tracks=False).  Cameras with present[c] == 0
+        keep their tracks and get ids of zeros."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.shape != (self.n, self.h, self.w):
+            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
+        pr = None if present is None else np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
+        n_heads = np.zeros(self.n, dtype=np.uint32)
+        heads = np.zeros((self.n, self.max_heads), dtype=HEAD_DTYPE)
+        ids = np.zeros((self.n, self.max_heads), dtype=np.uint32)
+        tr = np.zeros((self.n, MAX_TRACKS), dtype=TRACK_DTYPE) if tracks else None
+        check(self._lib.dh_multi_tracker_step(self.hp._ph, self._h, vp(frames), C.c_int(self.w), C.c_int(self.h), vp(pr),
+                                              vp(n_heads), vp(heads), vp(ids), vp(tr)))
+        return n_heads, heads, ids, tr
+
+    def step_device(self, frames_ptr: int, n_heads_ptr: int, heads_ptr: int, ids_ptr: int, tracks_ptr: int = 0,
+                    present_ptr: int = 0, stream: int = 0) -> None:
+        """Device frames [n_cams][h][w] u16; n_heads [n_cams] u32, heads [n_cams][max_heads] dh_head, ids [n_cams][max_heads]
+        u32, tracks [n_cams][MAX_TRACKS] dh_head_track or 0, present [n_cams] u8 or 0.  Asynchronous on `stream`."""
+        check(self._lib.dh_multi_tracker_step_device(self.hp._ph, self._h, vp(frames_ptr), C.c_int(self.w), C.c_int(self.h),
+                                                     vp(present_ptr or None), vp(n_heads_ptr), vp(heads_ptr), vp(ids_ptr),
+                                                     vp(tracks_ptr or None), _stream(stream)))
+
+    def capture(self, frames_ptr: int, n_heads_ptr: int, heads_ptr: int, ids_ptr: int, tracks_ptr: int = 0,
+                present_ptr: int = 0) -> None:
+        """Capture one device step into the predictor's graph slot; every `hp.graph_launch()` is then one step."""
+        check(self._lib.dh_multi_tracker_capture(self.hp._ph, self._h, vp(frames_ptr), C.c_int(self.w), C.c_int(self.h),
+                                                 vp(present_ptr or None), vp(n_heads_ptr), vp(heads_ptr), vp(ids_ptr),
+                                                 vp(tracks_ptr or None)))
+
+    def reset(self, camera: int | None = None, stream: int = 0) -> None:
+        """Every slot of one camera or all free again, next id 1; stream-ordered."""
+        check(self._lib.dh_multi_tracker_reset(self._h, C.c_int(-1 if camera is None else int(camera)), _stream(stream)))
+
+    def state(self) -> tuple[np.ndarray, np.ndarray]:
+        """Synchronous copy of the state: (TRACK_DTYPE [n, MAX_TRACKS], next id u32 [n])."""
+        tr = np.zeros((self.n, MAX_TRACKS), dtype=TRACK_DTYPE)
+        nid = np.zeros(self.n, dtype=np.uint32)
+        check(self._lib.dh_multi_tracker_state(self._h, vp(tr), vp(nid)))
+        return tr, nid
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.dh_multi_tracker_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

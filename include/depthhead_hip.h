@@ -347,6 +347,63 @@ int dh_predict_heads_cameras(dh_predictor *p, const uint16_t *frames, int n, int
 int dh_predict_heads_cameras_device(dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, int max_heads,
                                     uint32_t radius, uint32_t *n_heads, dh_head *heads, void *stream);
 
+/* ---- several heads per camera with persistent identities ----
+ * Not in the reference: PARITY UNPINNED, the definition below is this library's.  A multi-head tracker keeps, per camera,
+ * DH_MAX_TRACKS track slots and next_id (1 when created or reset).  A step runs the heads calls above (max_heads and radius of
+ * the params) on one frame per camera and then, for each camera whose `present` byte is non-zero (all when present is NULL),
+ * with n = n_heads[c] and its heads:
+ *   1. the cell of every live track's (id != 0) head.pose.mid_point and of every head's mid_point: (int32_t) per axis as the
+ *      support calls convert it (NaN -> 0, saturating), widened to 64 bits;
+ *   2. d(t, j): the Chebyshev distance of the two cells, in 64 bits;
+ *   3. pairs with d <= gate are taken greedily in the order (d ascending, head j ascending, slot t ascending); a pair is
+ *      accepted when neither its track nor its head is taken yet;
+ *   4. a matched track takes the whole 80-byte head; hits and age + 1, misses = 0; ids[c][j] = its id;
+ *   5. an unmatched live track: age + 1, misses + 1; when misses > max_misses its slot is zeroed (freed);
+ *   6. unmatched heads in ascending j each take the lowest free slot: id = next_id, age = hits = 1, misses = 0, the head;
+ *      next_id + 1, wrapping from UINT32_MAX to 1 (0 is never an id); ids[c][j] = id.  With no free slot ids[c][j] = 0;
+ *   7. ids[c][j] = 0 for j >= n.
+ * age, hits and misses saturate at UINT32_MAX.  An absent camera keeps its state and gets ids of zeros; its heads are computed
+ * and written all the same.  Integer only: bit-identical run to run.  Ids are unique per camera until 2^32 - 1 births have
+ * happened since the last reset.  Defaults (choices, not measurements): gate 100 cells = mm admits 3 m/s at 30 Hz and is five
+ * times the 20-cell merge distance of the heads calls; 3 misses coast for 100 ms at 30 Hz.
+ * heads and ids are [n_cams][max_heads], n_heads [n_cams], tracks (nullable: the records of every camera after the step)
+ * [n_cams][DH_MAX_TRACKS]; host memory for the host calls, device memory for the _device and capture calls.  DH_EINVAL before
+ * anything is launched: NULL arguments, max_heads outside 1 .. DH_MAX_HEADS, radius or gate above 2^31 - 1, a camera out of
+ * range in reset, a camera table of another device.  One tracker's steps must be stream-ordered.  After
+ * dh_predictor_reserve(p, n_cams, w, h) and one heads call of that workspace the device step allocates nothing and does not
+ * synchronise; the capture call does both itself before it captures, and is refused (DH_ESTATE) like the other captures once
+ * the workspace has been reallocated. */
+#define DH_MAX_TRACKS 8
+#define DH_TRACK_GATE 100
+#define DH_TRACK_MAX_MISSES 3
+typedef struct dh_head_track {
+    uint32_t id;          /* 0 = free slot */
+    uint32_t age;         /* present steps since birth, saturating */
+    uint32_t hits;        /* steps matched (birth counts), saturating */
+    uint32_t misses;      /* consecutive present steps without a match */
+    dh_head head;         /* last matched head */
+} dh_head_track;          /* 96 bytes */
+typedef struct dh_multi_track_params {
+    int32_t max_heads;    /* 1 .. DH_MAX_HEADS, passed to the heads pipeline */
+    uint32_t radius;      /* support radius of the heads pipeline, 0 .. 2^31 - 1 */
+    uint32_t gate;        /* cells (= mm), 0 .. 2^31 - 1; default DH_TRACK_GATE */
+    uint32_t max_misses;  /* default DH_TRACK_MAX_MISSES */
+} dh_multi_track_params;  /* 16 bytes */
+typedef struct dh_multi_tracker dh_multi_tracker;
+int dh_multi_tracker_create(const dh_cameras *c, const dh_multi_track_params *prm, dh_multi_tracker **out);   /* the table must outlive it */
+int dh_multi_tracker_destroy(dh_multi_tracker *t);
+/* the created state (every slot free, next_id 1) for one camera or all (camera = -1); stream-ordered */
+int dh_multi_tracker_reset(dh_multi_tracker *t, int camera, void *stream);
+int dh_multi_tracker_step(dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                          uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks);
+int dh_multi_tracker_step_device(dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                 uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks, void *stream);
+/* synchronous copy-out, each pointer nullable: tracks [n_cams][DH_MAX_TRACKS], next_id [n_cams] */
+int dh_multi_tracker_state(dh_multi_tracker *t, dh_head_track *tracks, uint32_t *next_id);
+/* capture one dh_multi_tracker_step_device (device pointers) into the predictor's graph slot; each dh_graph_launch is one step */
+int dh_multi_tracker_capture(dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                             uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
