@@ -143,6 +143,31 @@ def vp(x):
     return C.c_void_p(int(x))
 
 
+class _Handle:
+    """Owner of library handles.  `close()` -- also at the end of a `with` block and at garbage collection, where what it
+    raises is swallowed -- destroys each handle of `_handles`, (attribute, destroy function) pairs, once and in that order."""
+    _handles: tuple = ()
+
+    def close(self):
+        for attr, destroy in self._handles:
+            h = getattr(self, attr, None)
+            if h and h.value:
+                getattr(self._lib, destroy)(h)
+                setattr(self, attr, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def pinned_empty(shape, dtype) -> np.ndarray:
     """A numpy array in page-locked host memory (dh_host_alloc): frame batches filled in place are uploaded by
     asynchronous DMA at PCIe speed.  The memory is released when the array (and every view of it) is gone."""

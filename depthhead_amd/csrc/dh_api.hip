@@ -960,6 +960,15 @@ static int heads_reserve(dh_predictor *p) {
     return DH_OK;
 }
 
+// Everything a request's kernels touch, for `frames` frames of its geometry: the workspace, then the support scratch or the heads
+// scratch when r asks for support records or heads.
+static int reserve_req(dh_predictor *p, const BatchReq &r, int frames) {
+    TRY(reserve(p, frames, r.w, r.h));
+    if (r.support) TRY(support_reserve(p));
+    if (r.heads) TRY(heads_reserve(p));
+    return DH_OK;
+}
+
 // ------------------------------------------------------------------ checking a request
 // shared checks of the camera calls: n frames against the table, the table on the predictor's device
 static int cameras_check(const dh_predictor *p, const dh_cameras *c, int n, const char *fn) {
@@ -1004,9 +1013,7 @@ static int run(dh_predictor *p, const BatchReq &r, bool input, const char *fn, F
 // stream s.  Frames beyond the resident limit run in slices; the slices and forked sub-batches each take their part of r.
 static int batch_device(dh_predictor *p, const BatchReq &r, hipStream_t s) {
     const int n = r.n, slice = p->debug ? n : std::min(n, max_resident_frames(p));   // the taps index the whole batch
-    TRY(reserve(p, slice, r.w, r.h));
-    if (r.support) TRY(support_reserve(p));
-    if (r.heads) TRY(heads_reserve(p));
+    TRY(reserve_req(p, r, slice));
     for (int f0 = 0; f0 < n; f0 += slice) {
         BatchReq sl = r.at(f0);
         sl.n = std::min(slice, n - f0);
@@ -1100,9 +1107,7 @@ static int download(dh_predictor *p, T *dst, const T *src, size_t count, hipStre
 // *d is sl on those device buffers; its frames (ws.frames) are the caller's to fill.
 static int slice_setup(dh_predictor *p, const BatchReq &sl, BatchReq *d) {
     const int m = sl.n;
-    TRY(reserve(p, m, sl.w, sl.h));
-    if (sl.support) TRY(support_reserve(p));
-    if (sl.heads) TRY(heads_reserve(p));
+    TRY(reserve_req(p, sl, m));
     TRY(ensure_frame_staging(p, m, sl.w, sl.h));
     SmallStage st;
     TRY(small_stage(p, m, &st));
@@ -1337,11 +1342,12 @@ static int graph_destroy_(dh_predictor *p) {
 }
 
 // Captures driver() -- one device batch of r's size on own_stream -- into the predictor's graph slot, replacing what it held: no
-// taps or profiling, every allocation before the capture starts, refused by dh_graph_launch once the workspace is reallocated.
+// taps or profiling, every allocation r asks for (reserve_req) before the capture starts, refused by dh_graph_launch once the
+// workspace is reallocated.
 template <typename F>
 static int capture(dh_predictor *p, const BatchReq &r, F driver) {
     if (p->debug || p->profiling) return fail(DH_ESTATE, "taps / profiling cannot be captured");
-    TRY(reserve(p, std::min(r.n, max_resident_frames(p)), r.w, r.h));
+    TRY(reserve_req(p, r, std::min(r.n, max_resident_frames(p))));
     drop_graph(p);
     p->graph_stale = false;
     HIP_TRY(hipStreamSynchronize(p->own_stream));
@@ -1413,80 +1419,63 @@ static int predict_batch_cameras_(dh_predictor *p, const uint16_t *frames, int n
     return run(p, r, frames != nullptr, "dh_predict_batch_cameras", [&] { return batch_host(p, r); });
 }
 
-// A tracker's state is exactly the guess arrays of a camera batch (midp_guess, rot_guess, guess_mask): a step predicts with them
-// and k_track then rewrites them from the step's poses (dh_track.h: live_prediction.rs:79-101).
-struct dh_tracker {
+// What both trackers share: the camera table they step, one frame per camera, and the device copy of a host step's present
+// bytes.  Create, destroy, reset and the prelude of state are written once for either tracker type T (below); T supplies
+// clear(c0, m, s), which puts the state of cameras [c0, c0 + m) back to its initial value on stream s.
+struct TrackerCore {
     const dh_cameras *cams = nullptr;
     int n = 0;
-    uint32_t flags = 0;
-    Buf<float> midp;         // [n][3]
-    Buf<double> rot;         // [n][3]
-    Buf<uint8_t> mask;       // [n] bit0 midpoint guess, bit1 rotation guess
-    Buf<uint8_t> has_rot;    // [n]
     Buf<uint8_t> present;    // [n] host steps: the caller's present bytes on the device
 };
-static int tracker_create_(const dh_cameras *c, uint32_t flags, dh_tracker **out) {
-    if (!c || !out) return fail(DH_EINVAL, "dh_tracker_create: NULL argument");
-    *out = nullptr;
-    if (flags & ~(DH_TRACK_PREV_GUESS | DH_TRACK_SLUGGISH)) return fail(DH_EINVAL, "dh_tracker_create: unknown flags 0x%x", flags);
+
+// A tracker of type T over camera table c (the caller has checked its own arguments): init(t, n) sets t's parameters and allocates
+// its state for n cameras, which clear() then sets for every camera before the call returns.
+template <typename T, typename F>
+static int create_tracker(const dh_cameras *c, T **out, F init) {
     DeviceGuard guard(c->device);
     if (!guard.ok) return DH_EHIP;
-    std::unique_ptr<dh_tracker> t(new dh_tracker);
-    t->cams = c; t->n = c->n; t->flags = flags;
+    std::unique_ptr<T> t(new T);
+    t->cams = c; t->n = c->n;
     const size_t n = (size_t)c->n;
-    TRY(t->midp.alloc(n * 3));
-    TRY(t->rot.alloc(n * 3));
-    TRY(t->mask.alloc(n));
-    TRY(t->has_rot.alloc(n));
+    TRY(init(*t, n));
     TRY(t->present.alloc(n));
-    HIP_TRY(hipMemset(t->midp.get(), 0, n * 3 * sizeof(float)));
-    HIP_TRY(hipMemset(t->rot.get(), 0, n * 3 * sizeof(double)));
-    HIP_TRY(hipMemset(t->mask.get(), 0, n));
-    HIP_TRY(hipMemset(t->has_rot.get(), 0, n));
+    TRY(t->clear(0, n, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
     *out = t.release();
     return DH_OK;
 }
-static int tracker_destroy_(dh_tracker *t) {
+template <typename T>
+static int destroy_tracker(T *t) {
     if (!t) return DH_OK;
     DeviceGuard guard(t->cams->device);
     delete t;
     return DH_OK;
 }
-static int tracker_reset_(dh_tracker *t, int camera, void *stream) {
-    if (!t) return fail(DH_EINVAL, "dh_tracker_reset: NULL tracker");
-    if (camera < -1 || camera >= t->n) return fail(DH_EINVAL, "dh_tracker_reset: camera %d of %d", camera, t->n);
+// One camera, or every camera for camera == -1, back to the initial state, ordered on `stream`; fn names the entry point.
+template <typename T>
+static int reset_tracker(T *t, int camera, void *stream, const char *fn) {
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", fn);
+    if (camera < -1 || camera >= t->n) return fail(DH_EINVAL, "%s: camera %d of %d", fn, camera, t->n);
     DeviceGuard guard(t->cams->device);
     if (!guard.ok) return DH_EHIP;
-    hipStream_t s = (hipStream_t)stream;
     const size_t c0 = camera < 0 ? 0 : (size_t)camera, m = camera < 0 ? (size_t)t->n : 1;
-    // live_prediction.rs:63-64: latest_midp = [0, 0, 0], latest_rot = None
-    HIP_TRY(hipMemsetAsync(t->midp.get() + c0 * 3, 0, m * 3 * sizeof(float), s));
-    HIP_TRY(hipMemsetAsync(t->rot.get() + c0 * 3, 0, m * 3 * sizeof(double), s));
-    HIP_TRY(hipMemsetAsync(t->mask.get() + c0, 0, m, s));
-    HIP_TRY(hipMemsetAsync(t->has_rot.get() + c0, 0, m, s));
-    return DH_OK;
+    return t->clear(c0, m, (hipStream_t)stream);
 }
-// A step's request: every camera of the tracker (a NULL tracker leaves the camera table NULL: check_req refuses it), poses into
-// `out`; track_enqueue supplies the guesses.
-static BatchReq track_req(const dh_tracker *t, const uint16_t *frames, int w, int h, dh_pose *out) {
-    BatchReq r{frames, t ? t->n : 0, w, h, nullptr, {t ? t->cams : nullptr, 0}};
-    r.out = out;
-    return r;
+// copy(n): the synchronous copies of a state call, once every step on the tracker's device is done; fn names the entry point.
+template <typename F>
+static int read_tracker(const TrackerCore *t, const char *fn, F copy) {
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", fn);
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    HIP_TRY(hipDeviceSynchronize());          // the steps may run on any stream of the device
+    return copy((size_t)t->n);
 }
-// Cameras [c0, c0 + r.n) of a step (r on device buffers, c0 = r.cams.c0): their batch with the tracker's guesses, then k_track
-// over their poses, both on stream s.  k_track reads no support.
-static int track_enqueue(dh_predictor *p, dh_tracker *t, BatchReq r, const uint8_t *present, hipStream_t s) {
-    const size_t c0 = (size_t)r.cams.c0;
-    r.midp = t->midp.get() + c0 * 3; r.rot = t->rot.get() + c0 * 3; r.mask = t->mask.get() + c0;
-    TRY(batch_device(p, r, s));
-    TrackArgs a{};
-    a.poses = r.out; a.present = present; a.n = r.n; a.flags = t->flags;
-    a.midp = t->midp.get() + c0 * 3; a.rot = t->rot.get() + c0 * 3; a.mask = t->mask.get() + c0; a.has_rot = t->has_rot.get() + c0;
-    { Range rg(p->profiling, "dh:track"); HIP_TRY(dh_launch_track(a, s)); }
-    return DH_OK;
-}
-// The host steps: resident slices of cameras [f0, f0 + m) are staged, predicted and updated, their outputs copied back.
-static int track_host(dh_predictor *p, dh_tracker *t, const BatchReq &r, const uint8_t *present) {
+
+// The host steps of tracker t: each resident slice of cameras [f0, f0 + m) stages its frames and its present bytes (into
+// t->present), then enqueue(d, present) runs the step on own_stream, d being the slice on device buffers and present the staged
+// bytes of the whole table or NULL.  after(f0, m) then copies back what the tracker reports beyond host_slices' own outputs.
+template <typename E, typename A>
+static int track_slices(dh_predictor *p, TrackerCore *t, const BatchReq &r, const uint8_t *present, E enqueue, A after) {
     hipStream_t s = p->own_stream;
     return host_slices(p, r, [&](int f0, const BatchReq &sl) -> int {
         BatchReq d;
@@ -1495,15 +1484,71 @@ static int track_host(dh_predictor *p, dh_tracker *t, const BatchReq &r, const u
         HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), sl.frames, (size_t)m * sl.w * sl.h * sizeof(uint16_t), hipMemcpyHostToDevice, s));
         if (present) {
             SmallStage st;
-            TRY(small_stage(p, m, &st));       // (the slice's guess-mask staging: a tracker's guesses are on the device)
+            TRY(small_stage(p, m, &st));       // (the slice's guess-mask staging: a tracker step takes no host guesses)
             memcpy(st.mask, present + f0, (size_t)m);
             HIP_TRY(hipMemcpyAsync(t->present.get() + f0, st.mask, (size_t)m, hipMemcpyHostToDevice, s));
         }
-        int rc = track_enqueue(p, t, d, present ? t->present.get() + f0 : nullptr, s);
+        int rc = enqueue(d, present ? t->present.get() : nullptr);
         if (rc) { (void)hipStreamSynchronize(s); return rc; }
         HIP_TRY(hipEventRecord(p->ev_slice, s));
-        return DH_OK;
+        return after(f0, m);
     });
+}
+
+// A tracker's state is exactly the guess arrays of a camera batch (midp_guess, rot_guess, guess_mask): a step predicts with them
+// and k_track then rewrites them from the step's poses (dh_track.h: live_prediction.rs:79-101).
+struct dh_tracker : TrackerCore {
+    uint32_t flags = 0;
+    Buf<float> midp;         // [n][3]
+    Buf<double> rot;         // [n][3]
+    Buf<uint8_t> mask;       // [n] bit0 midpoint guess, bit1 rotation guess
+    Buf<uint8_t> has_rot;    // [n]
+    // live_prediction.rs:63-64: latest_midp = [0, 0, 0], latest_rot = None
+    int clear(size_t c0, size_t m, hipStream_t s) {
+        HIP_TRY(hipMemsetAsync(midp.get() + c0 * 3, 0, m * 3 * sizeof(float), s));
+        HIP_TRY(hipMemsetAsync(rot.get() + c0 * 3, 0, m * 3 * sizeof(double), s));
+        HIP_TRY(hipMemsetAsync(mask.get() + c0, 0, m, s));
+        HIP_TRY(hipMemsetAsync(has_rot.get() + c0, 0, m, s));
+        return DH_OK;
+    }
+};
+static int tracker_create_(const dh_cameras *c, uint32_t flags, dh_tracker **out) {
+    if (!c || !out) return fail(DH_EINVAL, "dh_tracker_create: NULL argument");
+    *out = nullptr;
+    if (flags & ~(DH_TRACK_PREV_GUESS | DH_TRACK_SLUGGISH)) return fail(DH_EINVAL, "dh_tracker_create: unknown flags 0x%x", flags);
+    return create_tracker(c, out, [&](dh_tracker &t, size_t n) -> int {
+        t.flags = flags;
+        TRY(t.midp.alloc(n * 3));
+        TRY(t.rot.alloc(n * 3));
+        TRY(t.mask.alloc(n));
+        return t.has_rot.alloc(n);
+    });
+}
+static int tracker_destroy_(dh_tracker *t) { return destroy_tracker(t); }
+static int tracker_reset_(dh_tracker *t, int camera, void *stream) { return reset_tracker(t, camera, stream, "dh_tracker_reset"); }
+// A step's request: every camera of the tracker (a NULL tracker leaves the camera table NULL: check_req refuses it), poses into
+// `out`; track_enqueue supplies the guesses.
+static BatchReq track_req(const dh_tracker *t, const uint16_t *frames, int w, int h, dh_pose *out) {
+    BatchReq r{frames, t ? t->n : 0, w, h, nullptr, {t ? t->cams : nullptr, 0}};
+    r.out = out;
+    return r;
+}
+// Cameras [c0, c0 + r.n) of a step (r on device buffers, c0 = r.cams.c0): their batch with the tracker's guesses, then k_track
+// over their poses, both on stream s.  present is the array of the whole camera table (nullable).  k_track reads no support.
+static int track_enqueue(dh_predictor *p, dh_tracker *t, BatchReq r, const uint8_t *present, hipStream_t s) {
+    const size_t c0 = (size_t)r.cams.c0;
+    r.midp = t->midp.get() + c0 * 3; r.rot = t->rot.get() + c0 * 3; r.mask = t->mask.get() + c0;
+    TRY(batch_device(p, r, s));
+    TrackArgs a{};
+    a.poses = r.out; a.present = off(present, c0); a.n = r.n; a.flags = t->flags;
+    a.midp = t->midp.get() + c0 * 3; a.rot = t->rot.get() + c0 * 3; a.mask = t->mask.get() + c0; a.has_rot = t->has_rot.get() + c0;
+    { Range rg(p->profiling, "dh:track"); HIP_TRY(dh_launch_track(a, s)); }
+    return DH_OK;
+}
+// The host steps: k_track after each slice's batch, nothing copied back beyond the poses (and support records).
+static int track_host(dh_predictor *p, dh_tracker *t, const BatchReq &r, const uint8_t *present) {
+    return track_slices(p, t, r, present, [&](const BatchReq &d, const uint8_t *pr) { return track_enqueue(p, t, d, pr, p->own_stream); },
+                        [](int, int) { return DH_OK; });
 }
 static int tracker_step_device_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out,
                                 void *stream) {
@@ -1515,20 +1560,17 @@ static int tracker_step_(dh_predictor *p, dh_tracker *t, const uint16_t *frames,
     return run(p, r, frames != nullptr, "dh_tracker_step", [&] { return track_host(p, t, r, present); });
 }
 static int tracker_state_(dh_tracker *t, float *midp, double *rot, uint8_t *flags) {
-    if (!t) return fail(DH_EINVAL, "dh_tracker_state: NULL tracker");
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    HIP_TRY(hipDeviceSynchronize());          // the steps may run on any stream of the device
-    const size_t n = (size_t)t->n;
-    if (midp) HIP_TRY(hipMemcpy(midp, t->midp.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (rot) HIP_TRY(hipMemcpy(rot, t->rot.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (flags) {
-        std::vector<uint8_t> hr(n);
-        HIP_TRY(hipMemcpy(flags, t->mask.get(), n, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hr.data(), t->has_rot.get(), n, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i) flags[i] = (uint8_t)(flags[i] | (hr[i] ? 4u : 0u));
-    }
-    return DH_OK;
+    return read_tracker(t, "dh_tracker_state", [&](size_t n) -> int {
+        if (midp) HIP_TRY(hipMemcpy(midp, t->midp.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        if (rot) HIP_TRY(hipMemcpy(rot, t->rot.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+        if (flags) {
+            std::vector<uint8_t> hr(n);
+            HIP_TRY(hipMemcpy(flags, t->mask.get(), n, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(hr.data(), t->has_rot.get(), n, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; ++i) flags[i] = (uint8_t)(flags[i] | (hr[i] ? 4u : 0u));
+        }
+        return DH_OK;
+    });
 }
 // One device step captured into the predictor's graph slot (capture).
 static int tracker_capture_(dh_predictor *p, dh_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, dh_pose *out) {
@@ -1605,14 +1647,17 @@ static int predict_heads_cameras_device_(dh_predictor *p, const uint16_t *frames
 // ------------------------------------------------------------------ several heads per camera with identities
 // A multi-head tracker's state: DH_MAX_TRACKS track records and the next id per camera.  A step is a heads camera batch followed
 // by k_track_heads (dh_track_heads.h) over its heads.
-struct dh_multi_tracker {
-    const dh_cameras *cams = nullptr;
-    int n = 0;
+struct dh_multi_tracker : TrackerCore {
     dh_multi_track_params prm{};
     Buf<dh_head_track> tracks;   // [n][DH_MAX_TRACKS]
     Buf<uint32_t> next_id;       // [n]
-    Buf<uint8_t> present;        // [n] host steps: the caller's present bytes on the device
     Buf<uint32_t> ids;           // [n][max_heads] host steps: the ids before their copy back
+    // tracks zeroed, next ids 1
+    int clear(size_t c0, size_t m, hipStream_t s) {
+        HIP_TRY(hipMemsetAsync(tracks.get() + c0 * DH_MAX_TRACKS, 0, m * DH_MAX_TRACKS * sizeof(dh_head_track), s));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(next_id.get() + c0), 1, m, s));
+        return DH_OK;
+    }
 };
 static int multi_params_check(const dh_multi_track_params *prm, const char *fn) {
     if (prm->max_heads < 1 || prm->max_heads > DH_MAX_HEADS)
@@ -1621,45 +1666,20 @@ static int multi_params_check(const dh_multi_track_params *prm, const char *fn) 
     if (prm->gate > 0x7fffffffu) return fail(DH_EINVAL, "%s: gate %u (a negative int?); expected 0 .. 2^31 - 1", fn, prm->gate);
     return DH_OK;
 }
-// tracks of cameras [c0, c0 + m) zeroed and their next ids 1, on stream s
-static int multi_tracker_clear(dh_multi_tracker *t, size_t c0, size_t m, hipStream_t s) {
-    HIP_TRY(hipMemsetAsync(t->tracks.get() + c0 * DH_MAX_TRACKS, 0, m * DH_MAX_TRACKS * sizeof(dh_head_track), s));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(t->next_id.get() + c0), 1, m, s));
-    return DH_OK;
-}
 static int multi_tracker_create_(const dh_cameras *c, const dh_multi_track_params *prm, dh_multi_tracker **out) {
     if (!prm || !out) return fail(DH_EINVAL, "dh_multi_tracker_create: NULL argument");
     *out = nullptr;
     TRY(multi_params_check(prm, "dh_multi_tracker_create"));
     if (!c) return fail(DH_EINVAL, "dh_multi_tracker_create: NULL camera table");
-    DeviceGuard guard(c->device);
-    if (!guard.ok) return DH_EHIP;
-    std::unique_ptr<dh_multi_tracker> t(new dh_multi_tracker);
-    t->cams = c; t->n = c->n; t->prm = *prm;
-    const size_t n = (size_t)c->n;
-    TRY(t->tracks.alloc(n * DH_MAX_TRACKS));
-    TRY(t->next_id.alloc(n));
-    TRY(t->present.alloc(n));
-    TRY(t->ids.alloc(n * (size_t)prm->max_heads));
-    TRY(multi_tracker_clear(t.get(), 0, n, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-    *out = t.release();
-    return DH_OK;
+    return create_tracker(c, out, [&](dh_multi_tracker &t, size_t n) -> int {
+        t.prm = *prm;
+        TRY(t.tracks.alloc(n * DH_MAX_TRACKS));
+        TRY(t.next_id.alloc(n));
+        return t.ids.alloc(n * (size_t)prm->max_heads);
+    });
 }
-static int multi_tracker_destroy_(dh_multi_tracker *t) {
-    if (!t) return DH_OK;
-    DeviceGuard guard(t->cams->device);
-    delete t;
-    return DH_OK;
-}
-static int multi_tracker_reset_(dh_multi_tracker *t, int camera, void *stream) {
-    if (!t) return fail(DH_EINVAL, "dh_multi_tracker_reset: NULL tracker");
-    if (camera < -1 || camera >= t->n) return fail(DH_EINVAL, "dh_multi_tracker_reset: camera %d of %d", camera, t->n);
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    const size_t c0 = camera < 0 ? 0 : (size_t)camera, m = camera < 0 ? (size_t)t->n : 1;
-    return multi_tracker_clear(t, c0, m, (hipStream_t)stream);
-}
+static int multi_tracker_destroy_(dh_multi_tracker *t) { return destroy_tracker(t); }
+static int multi_tracker_reset_(dh_multi_tracker *t, int camera, void *stream) { return reset_tracker(t, camera, stream, "dh_multi_tracker_reset"); }
 // A step's request: a heads camera batch of every camera of the tracker with its max_heads and radius.
 static BatchReq multi_track_req(const dh_multi_tracker *t, const uint16_t *frames, int w, int h, uint32_t *n_heads, dh_head *heads) {
     BatchReq r{frames, t->n, w, h, nullptr, {t->cams, 0}};
@@ -1680,31 +1700,6 @@ static int multi_track_enqueue(dh_predictor *p, dh_multi_tracker *t, const Batch
     { Range rg(p->profiling, "dh:track_heads"); HIP_TRY(dh_launch_track_heads(a, s)); }
     return DH_OK;
 }
-// The host steps: resident slices of cameras [f0, f0 + m) are staged, predicted and matched; their ids and track records come
-// back through the pinned staging block after the slice's kernels, its heads and their counts in host_slices' copy.
-static int multi_track_host(dh_predictor *p, dh_multi_tracker *t, const BatchReq &r, const uint8_t *present, uint32_t *ids,
-                            dh_head_track *tracks) {
-    hipStream_t s = p->own_stream;
-    const size_t mh = (size_t)r.max_heads;
-    return host_slices(p, r, [&](int f0, const BatchReq &sl) -> int {
-        BatchReq d;
-        TRY(slice_setup(p, sl, &d));
-        const int m = sl.n;
-        HIP_TRY(hipMemcpyAsync(p->ws.frames.get(), sl.frames, (size_t)m * sl.w * sl.h * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        if (present) {
-            SmallStage st;
-            TRY(small_stage(p, m, &st));       // (the slice's guess-mask staging: the heads calls take no guesses)
-            memcpy(st.mask, present + f0, (size_t)m);
-            HIP_TRY(hipMemcpyAsync(t->present.get() + f0, st.mask, (size_t)m, hipMemcpyHostToDevice, s));
-        }
-        int rc = multi_track_enqueue(p, t, d, present ? t->present.get() : nullptr, t->ids.get(), nullptr, s);
-        if (rc) { (void)hipStreamSynchronize(s); return rc; }
-        HIP_TRY(hipEventRecord(p->ev_slice, s));
-        TRY(download(p, ids + (size_t)f0 * mh, t->ids.get() + (size_t)f0 * mh, (size_t)m * mh, s));
-        if (tracks) TRY(download(p, tracks + (size_t)f0 * DH_MAX_TRACKS, t->tracks.get() + (size_t)f0 * DH_MAX_TRACKS, (size_t)m * DH_MAX_TRACKS, s));
-        return DH_OK;
-    });
-}
 static int multi_tracker_step_device_(dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
                                       uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks, void *stream) {
     if (!t || !ids) return fail(DH_EINVAL, "dh_multi_tracker_step_device: NULL argument");
@@ -1716,30 +1711,33 @@ static int multi_tracker_step_(dh_predictor *p, dh_multi_tracker *t, const uint1
                                uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks) {
     if (!t || !ids) return fail(DH_EINVAL, "dh_multi_tracker_step: NULL argument");
     const BatchReq r = multi_track_req(t, frames, w, h, n_heads, heads);
-    return run(p, r, frames != nullptr, "dh_multi_tracker_step", [&] { return multi_track_host(p, t, r, present, ids, tracks); });
+    const size_t mh = (size_t)r.max_heads;
+    return run(p, r, frames != nullptr, "dh_multi_tracker_step", [&] {
+        hipStream_t s = p->own_stream;
+        auto enqueue = [&](const BatchReq &d, const uint8_t *pr) { return multi_track_enqueue(p, t, d, pr, t->ids.get(), nullptr, s); };
+        // the ids and track records of cameras [f0, f0 + m), after their kernels and before host_slices' copies of their heads
+        auto after = [&](int f0, int m) -> int {
+            TRY(download(p, ids + (size_t)f0 * mh, t->ids.get() + (size_t)f0 * mh, (size_t)m * mh, s));
+            if (tracks) TRY(download(p, tracks + (size_t)f0 * DH_MAX_TRACKS, t->tracks.get() + (size_t)f0 * DH_MAX_TRACKS, (size_t)m * DH_MAX_TRACKS, s));
+            return DH_OK;
+        };
+        return track_slices(p, t, r, present, enqueue, after);
+    });
 }
 static int multi_tracker_state_(dh_multi_tracker *t, dh_head_track *tracks, uint32_t *next_id) {
-    if (!t) return fail(DH_EINVAL, "dh_multi_tracker_state: NULL tracker");
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    HIP_TRY(hipDeviceSynchronize());          // the steps may run on any stream of the device
-    const size_t n = (size_t)t->n;
-    if (tracks) HIP_TRY(hipMemcpy(tracks, t->tracks.get(), n * DH_MAX_TRACKS * sizeof(dh_head_track), hipMemcpyDeviceToHost));
-    if (next_id) HIP_TRY(hipMemcpy(next_id, t->next_id.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return DH_OK;
+    return read_tracker(t, "dh_multi_tracker_state", [&](size_t n) -> int {
+        if (tracks) HIP_TRY(hipMemcpy(tracks, t->tracks.get(), n * DH_MAX_TRACKS * sizeof(dh_head_track), hipMemcpyDeviceToHost));
+        if (next_id) HIP_TRY(hipMemcpy(next_id, t->next_id.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
 }
-// One device step captured into the predictor's graph slot (capture).  capture() reserves the workspace but not the heads scratch:
-// both are made here first, so that nothing is allocated while the stream captures.
+// One device step captured into the predictor's graph slot (capture).
 static int multi_tracker_capture_(dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
                                   uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks) {
     if (!t || !ids) return fail(DH_EINVAL, "dh_multi_tracker_capture: NULL argument");
     const BatchReq r = multi_track_req(t, frames, w, h, n_heads, heads);
-    return run(p, r, frames != nullptr, "dh_multi_tracker_capture", [&] {
-        if (p->debug || p->profiling) return fail(DH_ESTATE, "taps / profiling cannot be captured");
-        TRY(reserve(p, std::min(r.n, max_resident_frames(p)), r.w, r.h));
-        TRY(heads_reserve(p));
-        return capture(p, r, [&] { return multi_track_enqueue(p, t, r, present, ids, tracks, p->own_stream); });
-    });
+    return run(p, r, frames != nullptr, "dh_multi_tracker_capture",
+               [&] { return capture(p, r, [&] { return multi_track_enqueue(p, t, r, present, ids, tracks, p->own_stream); }); });
 }
 
 // ------------------------------------------------------------------ predict_mask / 2-D Hough votes

@@ -89,9 +89,10 @@ class PredictionResult:
     support: np.void | None = None
 
 
-class HoughPrediction:
+class HoughPrediction(_lib._Handle):
     """GPU-resident predictor.  Like the reference type it is not thread-safe (`!Sync`,
     prediction.rs:253): use one instance per host thread / stream."""
+    _handles = (("_ph", "dh_predictor_destroy"), ("_fh", "dh_forest_destroy"))   # the predictor before its forest
 
     def __init__(self, forest: Forest, params: ModelParams | None = None, device: int = 0):
         self._lib = _lib.load()
@@ -117,26 +118,6 @@ class HoughPrediction:
     def _cparams(self) -> _lib.Params:
         p = self.params
         return _lib.Params(p.stepwidth, p.subimage_width, p.subimage_height, p.gaussian_sigma, p.meanshift_iterations)
-
-    def close(self):
-        if getattr(self, "_ph", None) and self._ph.value:
-            self._lib.dh_predictor_destroy(self._ph)
-            self._ph = C.c_void_p()
-        if getattr(self, "_fh", None) and self._fh.value:
-            self._lib.dh_forest_destroy(self._fh)
-            self._fh = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # ---- reference API -------------------------------------------------------------------
     @property

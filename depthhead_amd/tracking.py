@@ -16,18 +16,15 @@ import numpy as np
 from . import _lib
 from ._lib import (HEAD_DTYPE, MAX_HEADS, MAX_TRACKS, POSE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, TRACK_DTYPE, TRACK_GATE,
                    TRACK_MAX_MISSES, MultiTrackParams, check, vp)
-from .prediction import _radius
+from .prediction import _radius, _stream
 
 TRACK_PREV_GUESS = 1   # DH_TRACK_PREV_GUESS: live_prediction --prevguess
 TRACK_SLUGGISH = 2     # DH_TRACK_SLUGGISH:   live_prediction --sluggish
 
 
-def _stream(stream: int):
-    return C.c_void_p(stream) if stream else None
-
-
-class Cameras:
+class Cameras(_lib._Handle):
     """`intrinsics`: [n, 3, 3] (or [n, 9]) f32 row-major matrices, or a list of `IntrinsicMatrix`."""
+    _handles = (("_h", "dh_cameras_destroy"),)
 
     def __init__(self, intrinsics, device: int = 0):
         self._lib = _lib.load()
@@ -41,48 +38,40 @@ class Cameras:
     def __len__(self) -> int:
         return self.n
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.dh_cameras_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class _Tracker(_lib._Handle):
+    """What both trackers share: the predictor, the camera table, the frame size and the host step's argument checks."""
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class HeadTracker:
-    """One frame per camera per step; the state (midpoint [n, 3] f32, rotation [n, 3] f64, guess mask [n] u8) stays on the
-    device.  Steps of one tracker must be stream-ordered.  The camera table must outlive the tracker."""
-
-    def __init__(self, hp, cameras: Cameras, w: int, h: int, prev_guess: bool = True, sluggish: bool = False):
+    def __init__(self, hp, cameras: Cameras, w: int, h: int):
         self._lib = _lib.load()
         self.hp, self.cameras, self.w, self.h = hp, cameras, int(w), int(h)
         self.n = len(cameras)
+
+    def _frames(self, frames) -> np.ndarray:
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.shape != (self.n, self.h, self.w):
+            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
+        return frames
+
+    def _present(self, present):
+        return None if present is None else np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
+
+
+class HeadTracker(_Tracker):
+    """One frame per camera per step; the state (midpoint [n, 3] f32, rotation [n, 3] f64, guess mask [n] u8) stays on the
+    device.  Steps of one tracker must be stream-ordered.  The camera table must outlive the tracker."""
+    _handles = (("_h", "dh_tracker_destroy"),)
+
+    def __init__(self, hp, cameras: Cameras, w: int, h: int, prev_guess: bool = True, sluggish: bool = False):
+        super().__init__(hp, cameras, w, h)
         self.flags = (TRACK_PREV_GUESS if prev_guess else 0) | (TRACK_SLUGGISH if sluggish else 0)
         self._h = C.c_void_p()
         check(self._lib.dh_tracker_create(cameras._h, C.c_uint32(self.flags), C.byref(self._h)))
         hp.reserve(self.n, self.w, self.h)      # after this a device step allocates nothing (capturable)
 
-    def _present(self, present):
-        if present is None:
-            return None
-        p = np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
-        return p
-
     def step(self, frames, present=None) -> np.ndarray:
         """Host frames [n_cams, h, w] uint16 -> POSE_DTYPE[n_cams]; cameras with present[c] == 0 keep their state."""
-        frames = np.ascontiguousarray(frames, dtype=np.uint16)
-        if frames.shape != (self.n, self.h, self.w):
-            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
+        frames = self._frames(frames)
         pr = self._present(present)
         out = np.zeros(self.n, dtype=POSE_DTYPE)
         check(self._lib.dh_tracker_step(self.hp._ph, self._h, vp(frames), C.c_int(self.w), C.c_int(self.h), vp(pr), vp(out)))
@@ -96,9 +85,7 @@ class HeadTracker:
     def step_support(self, frames, present=None, radius: int = SUPPORT_RADIUS) -> tuple[np.ndarray, np.ndarray]:
         """`step` that also reports every camera's vote support (absent cameras included): -> (POSE_DTYPE[n_cams],
         SUPPORT_DTYPE[n_cams]).  The state is updated exactly as by `step`."""
-        frames = np.ascontiguousarray(frames, dtype=np.uint16)
-        if frames.shape != (self.n, self.h, self.w):
-            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
+        frames = self._frames(frames)
         pr = self._present(present)
         out = np.zeros(self.n, dtype=POSE_DTYPE)
         sup = np.zeros(self.n, dtype=SUPPORT_DTYPE)
@@ -131,35 +118,17 @@ class HeadTracker:
         check(self._lib.dh_tracker_state(self._h, vp(midp), vp(rot), vp(flags)))
         return {"midp": midp, "rot": rot, "mask": flags & 3, "has_rot": (flags & 4) != 0}
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.dh_tracker_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class MultiHeadTracker:
+class MultiHeadTracker(_Tracker):
     """Several heads per camera with identities that last across steps (include/depthhead_hip.h: dh_multi_tracker, DESIGN.md
     section 15).  Each step runs the heads pipeline on one frame per camera and matches its heads to the camera's tracks on the
     device: every head gets a u32 id, 0 for none.  The state (TRACK_DTYPE [n, MAX_TRACKS] and the next id [n]) stays on the
     device.  Steps of one tracker must be stream-ordered.  The camera table must outlive the tracker."""
+    _handles = (("_h", "dh_multi_tracker_destroy"),)
 
     def __init__(self, hp, cameras: Cameras, w: int, h: int, max_heads: int = MAX_HEADS, radius: int = SUPPORT_RADIUS,
                  gate: int = TRACK_GATE, max_misses: int = TRACK_MAX_MISSES):
-        self._lib = _lib.load()
-        self.hp, self.cameras, self.w, self.h = hp, cameras, int(w), int(h)
-        self.n = len(cameras)
+        super().__init__(hp, cameras, w, h)
         self.max_heads = int(max_heads)
         self.params = MultiTrackParams(self.max_heads, _radius(radius).value, _radius(gate).value,
                                        int(max_misses) & 0xFFFFFFFF)
@@ -171,10 +140,8 @@ class MultiHeadTracker:
         """Host frames [n_cams, h, w] uint16 -> (n_heads u32 [n_cams], HEAD_DTYPE [n_cams, max_heads], ids u32 [n_cams,
         max_heads], TRACK_DTYPE [n_cams, MAX_TRACKS] after the step, or None with tracks=False).  Cameras with present[c] == 0
         keep their tracks and get ids of zeros."""
-        frames = np.ascontiguousarray(frames, dtype=np.uint16)
-        if frames.shape != (self.n, self.h, self.w):
-            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
-        pr = None if present is None else np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
+        frames = self._frames(frames)
+        pr = self._present(present)
         n_heads = np.zeros(self.n, dtype=np.uint32)
         heads = np.zeros((self.n, self.max_heads), dtype=HEAD_DTYPE)
         ids = np.zeros((self.n, self.max_heads), dtype=np.uint32)
@@ -208,20 +175,3 @@ class MultiHeadTracker:
         nid = np.zeros(self.n, dtype=np.uint32)
         check(self._lib.dh_multi_tracker_state(self._h, vp(tr), vp(nid)))
         return tr, nid
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.dh_multi_tracker_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()

@@ -40,27 +40,14 @@ def export_forest(lib, handle) -> Forest:
     return Forest(roots, nodes, prob, ob, rb, offs, rots)
 
 
-class Trainer:
+class Trainer(_lib._Handle):
     """One dh_trainer: a sample pool on `device` fed by `add_frames`, fitted by `fit` (any number of times)."""
+    _handles = (("_h", "dh_trainer_destroy"),)
 
     def __init__(self, params: "_lib.TrainParams", device: int = 0):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         check(self._lib.dh_trainer_create(C.byref(params), int(device), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.dh_trainer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
     def add_frames(self, frames, masks, K, pos3d, rot_deg) -> None:
         """frames [n, H, W] u16, masks [n, H, W] (non-zero = head), K [n, 3, 3] or one [3, 3], pos3d / rot_deg [n, 3]."""
