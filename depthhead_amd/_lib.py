@@ -35,6 +35,23 @@ assert TRACK_DTYPE.itemsize == 96 and TRACK_DTYPE.fields["head"][1] == 16
 MAX_TRACKS = 8             # DH_MAX_TRACKS
 TRACK_GATE = 100           # DH_TRACK_GATE (cells = mm)
 TRACK_MAX_MISSES = 3       # DH_TRACK_MAX_MISSES
+# dh_rig_person / dh_rig_track: a person fused from the heads of a rig's cameras, and one track slot of a rig tracker
+RIG_PERSON_DTYPE = np.dtype([("views", "<u8"), ("mass", "<u8"), ("cell", "<i4", (3,)), ("n_views", "<u4"), ("world", "<f4", (3,)),
+                             ("id", "<u4"), ("best_cam", "<u4"), ("best_head", "<u4")], align=True)
+assert RIG_PERSON_DTYPE.itemsize == 56
+RIG_TRACK_DTYPE = np.dtype([("id", "<u4"), ("age", "<u4"), ("hits", "<u4"), ("misses", "<u4"), ("person", RIG_PERSON_DTYPE)],
+                           align=True)
+assert RIG_TRACK_DTYPE.itemsize == 72 and RIG_TRACK_DTYPE.fields["person"][1] == 16
+RIG_MAX_CAMERAS = 64       # DH_RIG_MAX_CAMERAS
+RIG_MAX_PERSONS = 16       # DH_RIG_MAX_PERSONS
+RIG_MAX_TRACKS = 16        # DH_RIG_MAX_TRACKS
+RIG_FUSE_GATE = 100        # DH_RIG_FUSE_GATE (cells = mm)
+
+
+class RigTrackParams(C.Structure):
+    """dh_rig_track_params"""
+    _fields_ = [("max_heads", C.c_int32), ("radius", C.c_uint32), ("fuse_gate", C.c_uint32), ("gate", C.c_uint32),
+                ("max_misses", C.c_uint32)]
 
 
 class MultiTrackParams(C.Structure):
@@ -79,6 +96,8 @@ EXPORTS = [
     "dh_predict_heads", "dh_predict_heads_device", "dh_predict_heads_cameras", "dh_predict_heads_cameras_device",
     "dh_multi_tracker_create", "dh_multi_tracker_destroy", "dh_multi_tracker_reset", "dh_multi_tracker_step",
     "dh_multi_tracker_step_device", "dh_multi_tracker_state", "dh_multi_tracker_capture",
+    "dh_rig_create", "dh_rig_destroy", "dh_rig_tracker_create", "dh_rig_tracker_destroy", "dh_rig_tracker_reset",
+    "dh_rig_tracker_step", "dh_rig_tracker_step_device", "dh_rig_tracker_state", "dh_rig_tracker_capture",
 ]
 
 

@@ -1429,9 +1429,10 @@ struct TrackerCore {
 };
 
 // A tracker of type T over camera table c (the caller has checked its own arguments): init(t, n) sets t's parameters and allocates
-// its state for n cameras, which clear() then sets for every camera before the call returns.
+// its state for n cameras, which clear() then sets for every camera before the call returns.  A tracker whose state is not per
+// camera (a rig tracker's is per rig) passes the number of its state units as `states`.
 template <typename T, typename F>
-static int create_tracker(const dh_cameras *c, T **out, F init) {
+static int create_tracker(const dh_cameras *c, T **out, F init, size_t states = 0) {
     DeviceGuard guard(c->device);
     if (!guard.ok) return DH_EHIP;
     std::unique_ptr<T> t(new T);
@@ -1439,7 +1440,7 @@ static int create_tracker(const dh_cameras *c, T **out, F init) {
     const size_t n = (size_t)c->n;
     TRY(init(*t, n));
     TRY(t->present.alloc(n));
-    TRY(t->clear(0, n, nullptr));
+    TRY(t->clear(0, states ? states : n, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     *out = t.release();
     return DH_OK;
@@ -1452,13 +1453,15 @@ static int destroy_tracker(T *t) {
     return DH_OK;
 }
 // One camera, or every camera for camera == -1, back to the initial state, ordered on `stream`; fn names the entry point.
+// `units` (default: the cameras) and `unit` say what the index counts when the state is not per camera.
 template <typename T>
-static int reset_tracker(T *t, int camera, void *stream, const char *fn) {
+static int reset_tracker(T *t, int camera, void *stream, const char *fn, int units = -1, const char *unit = "camera") {
     if (!t) return fail(DH_EINVAL, "%s: NULL tracker", fn);
-    if (camera < -1 || camera >= t->n) return fail(DH_EINVAL, "%s: camera %d of %d", fn, camera, t->n);
+    if (units < 0) units = t->n;
+    if (camera < -1 || camera >= units) return fail(DH_EINVAL, "%s: %s %d of %d", fn, unit, camera, units);
     DeviceGuard guard(t->cams->device);
     if (!guard.ok) return DH_EHIP;
-    const size_t c0 = camera < 0 ? 0 : (size_t)camera, m = camera < 0 ? (size_t)t->n : 1;
+    const size_t c0 = camera < 0 ? 0 : (size_t)camera, m = camera < 0 ? (size_t)units : 1;
     return t->clear(c0, m, (hipStream_t)stream);
 }
 // copy(n): the synchronous copies of a state call, once every step on the tracker's device is done; fn names the entry point.
@@ -1738,6 +1741,188 @@ static int multi_tracker_capture_(dh_predictor *p, dh_multi_tracker *t, const ui
     const BatchReq r = multi_track_req(t, frames, w, h, n_heads, heads);
     return run(p, r, frames != nullptr, "dh_multi_tracker_capture",
                [&] { return capture(p, r, [&] { return multi_track_enqueue(p, t, r, present, ids, tracks, p->own_stream); }); });
+}
+
+// ------------------------------------------------------------------ camera rigs
+// A rig table: the extrinsics of every camera of a camera table and the camera ranges of the rigs, on the table's device.
+struct dh_rig {
+    const dh_cameras *cams = nullptr;
+    int n_rigs = 0;
+    Buf<RigCam> dev;            // [cams->n]
+    Buf<int32_t> rig_begin;     // [n_rigs + 1]
+};
+static int rig_create_(const dh_cameras *c, const float *R, const float *t, const int32_t *rig_begin, int n_rigs, dh_rig **out) {
+    if (!out) return fail(DH_EINVAL, "dh_rig_create: NULL argument");
+    *out = nullptr;
+    if (!c || !R || !t || !rig_begin) return fail(DH_EINVAL, "dh_rig_create: NULL argument");
+    if (n_rigs < 1) return fail(DH_EINVAL, "dh_rig_create: n_rigs = %d, expected at least one rig", n_rigs);
+    if (rig_begin[0] != 0 || rig_begin[n_rigs] != c->n)
+        return fail(DH_EINVAL, "dh_rig_create: the rigs cover cameras %d .. %d, the camera table has 0 .. %d", rig_begin[0], rig_begin[n_rigs], c->n);
+    for (int g = 0; g < n_rigs; ++g) {
+        const int64_t m = (int64_t)rig_begin[g + 1] - rig_begin[g];
+        if (m < 1 || m > DH_RIG_MAX_CAMERAS)
+            return fail(DH_EINVAL, "dh_rig_create: rig %d has %lld cameras, expected 1 .. %d in ascending ranges", g, (long long)m, DH_RIG_MAX_CAMERAS);
+    }
+    std::vector<RigCam> host((size_t)c->n);
+    for (int i = 0; i < c->n; ++i) {
+        memcpy(host[(size_t)i].R, R + (size_t)i * 9, sizeof host[0].R);
+        memcpy(host[(size_t)i].t, t + (size_t)i * 3, sizeof host[0].t);
+        for (int q = 0; q < 12; ++q)
+            if (!std::isfinite(q < 9 ? host[(size_t)i].R[q] : host[(size_t)i].t[q - 9]))
+                return fail(DH_EINVAL, "dh_rig_create: camera %d has a non-finite entry in %s", i, q < 9 ? "R" : "t");
+    }
+    DeviceGuard guard(c->device);
+    if (!guard.ok) return DH_EHIP;
+    std::unique_ptr<dh_rig> r(new dh_rig);
+    r->cams = c; r->n_rigs = n_rigs;
+    TRY(r->dev.alloc((size_t)c->n));
+    TRY(r->rig_begin.alloc((size_t)n_rigs + 1));
+    HIP_TRY(hipMemcpy(r->dev.get(), host.data(), host.size() * sizeof(RigCam), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r->rig_begin.get(), rig_begin, ((size_t)n_rigs + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    *out = r.release();
+    return DH_OK;
+}
+static int rig_destroy_(dh_rig *r) {
+    if (!r) return DH_OK;
+    DeviceGuard guard(r->cams->device);
+    delete r;
+    return DH_OK;
+}
+
+// A rig tracker's state: DH_RIG_MAX_TRACKS track records and the next id per rig.  A step is a heads camera batch over the rig
+// table's cameras followed by k_rig_fuse (dh_rig.h) once over all rigs.  The host steps keep every slice's heads on the device
+// (heads, n_heads below) and fuse after the last slice, so that a resident limit smaller than a rig does not cut it in two.
+struct dh_rig_tracker : TrackerCore {
+    const dh_rig *rig = nullptr;
+    dh_rig_track_params prm{};
+    Buf<dh_rig_track> tracks;    // [n_rigs][DH_RIG_MAX_TRACKS]
+    Buf<uint32_t> next_id;       // [n_rigs]
+    // host steps: the whole table's heads for k_rig_fuse, and its outputs before their copy back
+    Buf<dh_head> heads;          // [n][max_heads]
+    Buf<uint32_t> n_heads;       // [n]
+    Buf<uint32_t> ids;           // [n][max_heads]
+    Buf<uint32_t> n_persons;     // [n_rigs]
+    Buf<dh_rig_person> persons;  // [n_rigs][DH_RIG_MAX_PERSONS]
+    // tracks zeroed, next ids 1, for rigs [g0, g0 + m)
+    int clear(size_t g0, size_t m, hipStream_t s) {
+        HIP_TRY(hipMemsetAsync(tracks.get() + g0 * DH_RIG_MAX_TRACKS, 0, m * DH_RIG_MAX_TRACKS * sizeof(dh_rig_track), s));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(next_id.get() + g0), 1, m, s));
+        return DH_OK;
+    }
+};
+static int rig_tracker_create_(const dh_rig *rig, const dh_rig_track_params *prm, dh_rig_tracker **out) {
+    const char *fn = "dh_rig_tracker_create";
+    if (!prm || !out) return fail(DH_EINVAL, "%s: NULL argument", fn);
+    *out = nullptr;
+    if (prm->max_heads < 1 || prm->max_heads > DH_MAX_HEADS) return fail(DH_EINVAL, "%s: max_heads %d outside 1 .. %d", fn, prm->max_heads, DH_MAX_HEADS);
+    if (prm->radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u (a negative int?); expected 0 .. 2^31 - 1", fn, prm->radius);
+    if (prm->fuse_gate > 0x7fffffffu) return fail(DH_EINVAL, "%s: fuse_gate %u (a negative int?); expected 0 .. 2^31 - 1", fn, prm->fuse_gate);
+    if (prm->gate > 0x7fffffffu) return fail(DH_EINVAL, "%s: gate %u (a negative int?); expected 0 .. 2^31 - 1", fn, prm->gate);
+    if (!rig) return fail(DH_EINVAL, "%s: NULL rig table", fn);
+    const size_t ng = (size_t)rig->n_rigs, mh = (size_t)prm->max_heads;
+    return create_tracker(rig->cams, out, [&](dh_rig_tracker &t, size_t n) -> int {
+        t.rig = rig; t.prm = *prm;
+        TRY(t.tracks.alloc(ng * DH_RIG_MAX_TRACKS));
+        TRY(t.next_id.alloc(ng));
+        TRY(t.heads.alloc(n * mh));
+        TRY(t.n_heads.alloc(n));
+        TRY(t.ids.alloc(n * mh));
+        TRY(t.n_persons.alloc(ng));
+        return t.persons.alloc(ng * DH_RIG_MAX_PERSONS);
+    }, ng);
+}
+static int rig_tracker_destroy_(dh_rig_tracker *t) { return destroy_tracker(t); }
+static int rig_tracker_reset_(dh_rig_tracker *t, int rig, void *stream) {
+    return reset_tracker(t, rig, stream, "dh_rig_tracker_reset", t ? t->rig->n_rigs : 0, "rig");
+}
+// A step's request: a heads camera batch of every camera of the rig table with the tracker's max_heads and radius.
+static BatchReq rig_track_req(const dh_rig_tracker *t, const uint16_t *frames, int w, int h, uint32_t *n_heads, dh_head *heads) {
+    BatchReq r{frames, t->n, w, h, nullptr, {t->cams, 0}};
+    r.kind = HEADS; r.radius = t->prm.radius; r.heads = heads; r.n_heads = n_heads; r.max_heads = t->prm.max_heads;
+    return r;
+}
+// k_rig_fuse over every rig on stream s: heads, n_heads, present (nullable) and ids are device arrays of the whole camera
+// table, n_persons, persons and tracks (nullable) of every rig.
+static int rig_fuse_enqueue(dh_predictor *p, dh_rig_tracker *t, const dh_head *heads, const uint32_t *n_heads, const uint8_t *present,
+                            uint32_t *ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, hipStream_t s) {
+    RigFuseArgs a{};
+    a.cams = t->rig->dev.get(); a.rig_begin = t->rig->rig_begin.get();
+    a.heads = heads; a.n_heads = n_heads; a.present = present;
+    a.state = t->tracks.get(); a.next_id = t->next_id.get();
+    a.ids = ids; a.n_persons = n_persons; a.persons = persons; a.snapshot = tracks;
+    a.n_rigs = t->rig->n_rigs; a.max_heads = t->prm.max_heads;
+    a.fuse_gate = t->prm.fuse_gate; a.gate = t->prm.gate; a.max_misses = t->prm.max_misses;
+    { Range rg(p->profiling, "dh:rig_fuse"); HIP_TRY(dh_launch_rig_fuse(a, s)); }
+    return DH_OK;
+}
+// The device step: the heads batch of the whole table (batch_device slices it when it exceeds the resident limit; the heads stay
+// in the caller's arrays), then k_rig_fuse, both on stream s.
+static int rig_track_enqueue(dh_predictor *p, dh_rig_tracker *t, const BatchReq &r, const uint8_t *present, uint32_t *ids,
+                             uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, hipStream_t s) {
+    TRY(batch_device(p, r, s));
+    return rig_fuse_enqueue(p, t, r.heads, r.n_heads, present, ids, n_persons, persons, tracks, s);
+}
+static int rig_args_check(const dh_predictor *p, const dh_rig_tracker *t, const void *ids, const void *n_persons, const void *persons, const char *fn) {
+    if (!t || !ids || !n_persons || !persons) return fail(DH_EINVAL, "%s: NULL argument", fn);
+    if (p && t->cams->device != p->device)
+        return fail(DH_EINVAL, "%s: rig table on device %d, predictor on device %d", fn, t->cams->device, p->device);
+    return DH_OK;
+}
+static int rig_tracker_step_device_(dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                    uint32_t *n_heads, dh_head *heads, uint32_t *ids, uint32_t *n_persons, dh_rig_person *persons,
+                                    dh_rig_track *tracks, void *stream) {
+    TRY(rig_args_check(p, t, ids, n_persons, persons, "dh_rig_tracker_step_device"));
+    const BatchReq r = rig_track_req(t, frames, w, h, n_heads, heads);
+    return run(p, r, frames != nullptr, "dh_rig_tracker_step_device",
+               [&] { return rig_track_enqueue(p, t, r, present, ids, n_persons, persons, tracks, (hipStream_t)stream); });
+}
+static int rig_tracker_step_(dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                             uint32_t *n_heads, dh_head *heads, uint32_t *ids, uint32_t *n_persons, dh_rig_person *persons,
+                             dh_rig_track *tracks) {
+    TRY(rig_args_check(p, t, ids, n_persons, persons, "dh_rig_tracker_step"));
+    const BatchReq r = rig_track_req(t, frames, w, h, n_heads, heads);
+    const size_t mh = (size_t)r.max_heads, ng = (size_t)t->rig->n_rigs;
+    return run(p, r, frames != nullptr, "dh_rig_tracker_step", [&] {
+        hipStream_t s = p->own_stream;
+        // a slice's heads pipeline, its heads kept in the tracker's arrays of the whole table
+        auto enqueue = [&](const BatchReq &d, const uint8_t *) -> int {
+            const size_t c0 = (size_t)d.cams.c0;
+            TRY(batch_device(p, d, s));
+            HIP_TRY(hipMemcpyAsync(t->heads.get() + c0 * mh, d.heads, (size_t)d.n * mh * sizeof(dh_head), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(t->n_heads.get() + c0, d.n_heads, (size_t)d.n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            return DH_OK;
+        };
+        // after the last slice: one k_rig_fuse over every rig, and its outputs back
+        auto after = [&](int f0, int m) -> int {
+            if (f0 + m < t->n) return DH_OK;
+            TRY(rig_fuse_enqueue(p, t, t->heads.get(), t->n_heads.get(), present ? t->present.get() : nullptr, t->ids.get(),
+                                 t->n_persons.get(), t->persons.get(), nullptr, s));
+            TRY(download(p, ids, t->ids.get(), (size_t)t->n * mh, s));
+            TRY(download(p, n_persons, t->n_persons.get(), ng, s));
+            TRY(download(p, persons, t->persons.get(), ng * DH_RIG_MAX_PERSONS, s));
+            if (tracks) TRY(download(p, tracks, t->tracks.get(), ng * DH_RIG_MAX_TRACKS, s));
+            return DH_OK;
+        };
+        return track_slices(p, t, r, present, enqueue, after);
+    });
+}
+static int rig_tracker_state_(dh_rig_tracker *t, dh_rig_track *tracks, uint32_t *next_id) {
+    return read_tracker(t, "dh_rig_tracker_state", [&](size_t) -> int {
+        const size_t ng = (size_t)t->rig->n_rigs;
+        if (tracks) HIP_TRY(hipMemcpy(tracks, t->tracks.get(), ng * DH_RIG_MAX_TRACKS * sizeof(dh_rig_track), hipMemcpyDeviceToHost));
+        if (next_id) HIP_TRY(hipMemcpy(next_id, t->next_id.get(), ng * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
+}
+// One device step captured into the predictor's graph slot (capture): the tracker's own buffers exist since its creation, so
+// the capture allocates nothing beyond what reserve_req covers.
+static int rig_tracker_capture_(dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                uint32_t *n_heads, dh_head *heads, uint32_t *ids, uint32_t *n_persons, dh_rig_person *persons,
+                                dh_rig_track *tracks) {
+    TRY(rig_args_check(p, t, ids, n_persons, persons, "dh_rig_tracker_capture"));
+    const BatchReq r = rig_track_req(t, frames, w, h, n_heads, heads);
+    return run(p, r, frames != nullptr, "dh_rig_tracker_capture",
+               [&] { return capture(p, r, [&] { return rig_track_enqueue(p, t, r, present, ids, n_persons, persons, tracks, p->own_stream); }); });
 }
 
 // ------------------------------------------------------------------ predict_mask / 2-D Hough votes
@@ -2335,4 +2520,13 @@ DH_API(multi_tracker_step, (dh_predictor *p, dh_multi_tracker *t, const uint16_t
 DH_API(multi_tracker_step_device, (dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks, void *stream), (p, t, frames, w, h, present, n_heads, heads, ids, tracks, stream))
 DH_API(multi_tracker_state, (dh_multi_tracker *t, dh_head_track *tracks, uint32_t *next_id), (t, tracks, next_id))
 DH_API(multi_tracker_capture, (dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks), (p, t, frames, w, h, present, n_heads, heads, ids, tracks))
+DH_API(rig_create, (const dh_cameras *c, const float *R, const float *t, const int32_t *rig_begin, int n_rigs, dh_rig **out), (c, R, t, rig_begin, n_rigs, out))
+DH_API(rig_destroy, (dh_rig *r), (r))
+DH_API(rig_tracker_create, (const dh_rig *r, const dh_rig_track_params *prm, dh_rig_tracker **out), (r, prm, out))
+DH_API(rig_tracker_destroy, (dh_rig_tracker *t), (t))
+DH_API(rig_tracker_reset, (dh_rig_tracker *t, int rig, void *stream), (t, rig, stream))
+DH_API(rig_tracker_step, (dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks), (p, t, frames, w, h, present, n_heads, heads, rig_ids, n_persons, persons, tracks))
+DH_API(rig_tracker_step_device, (dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, void *stream), (p, t, frames, w, h, present, n_heads, heads, rig_ids, n_persons, persons, tracks, stream))
+DH_API(rig_tracker_state, (dh_rig_tracker *t, dh_rig_track *tracks, uint32_t *next_id), (t, tracks, next_id))
+DH_API(rig_tracker_capture, (dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks), (p, t, frames, w, h, present, n_heads, heads, rig_ids, n_persons, persons, tracks))
 #undef DH_API

@@ -288,6 +288,25 @@ struct TrackHeadsArgs {
     uint32_t gate, max_misses;
 };
 
+// k_rig_fuse: one rig tracker step's fusion and matching (dh_rig.h) for every rig of a rig table, after k_heads_finish.
+struct RigCam { float R[9], t[3]; };   // a camera's extrinsics: world = R m + t
+static_assert(sizeof(RigCam) == 48, "RigCam: three 16-byte rows");
+struct RigFuseArgs {
+    const RigCam *cams;        // [n_cams]
+    const int32_t *rig_begin;  // [n_rigs + 1]
+    const dh_head *heads;      // [n_cams][max_heads] the step's heads
+    const uint32_t *n_heads;   // [n_cams]
+    const uint8_t *present;    // nullable [n_cams]
+    dh_rig_track *state;       // [n_rigs][DH_RIG_MAX_TRACKS] the tracks
+    uint32_t *next_id;         // [n_rigs]
+    uint32_t *ids;             // [n_cams][max_heads]
+    uint32_t *n_persons;       // [n_rigs]
+    dh_rig_person *persons;    // [n_rigs][DH_RIG_MAX_PERSONS]
+    dh_rig_track *snapshot;    // nullable [n_rigs][DH_RIG_MAX_TRACKS]: the tracks after the step
+    int n_rigs, max_heads;
+    uint32_t fuse_gate, gate, max_misses;
+};
+
 struct VotesDumpArgs {
     int frame, which;
     DevForest f;
@@ -474,6 +493,7 @@ hipError_t dh_launch_heads_finish(const HeadsArgs &a, hipStream_t s);
 hipError_t dh_launch_votes_dump(const VotesDumpArgs &a, hipStream_t s);
 hipError_t dh_launch_track(const TrackArgs &a, hipStream_t s);
 hipError_t dh_launch_track_heads(const TrackHeadsArgs &a, hipStream_t s);
+hipError_t dh_launch_rig_fuse(const RigFuseArgs &a, hipStream_t s);
 hipError_t dh_launch_boxsum(const BoxArgs &a, hipStream_t s);
 hipError_t dh_launch_pixflags(const PixFlagArgs &a, hipStream_t s);
 hipError_t dh_launch_top_build(const DevForest &f, const void *nodes_a, uint32_t n_amb, int top_levels, uint32_t *out, hipStream_t s);

@@ -404,6 +404,108 @@ int dh_multi_tracker_state(dh_multi_tracker *t, dh_head_track *tracks, uint32_t 
 int dh_multi_tracker_capture(dh_predictor *p, dh_multi_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
                              uint32_t *n_heads, dh_head *heads, uint32_t *ids, dh_head_track *tracks);
 
+/* ---- camera rigs: heads fused across cameras into tracks with rig-wide identities ----
+ * Not in the reference (one pose from one Kinect): PARITY UNPINNED, the definition below is this library's, and its constants
+ * are choices.  A RIG is a group of cameras that look at one space and share one world frame.  A rig table gives every camera c
+ * of a camera table its extrinsics: the camera-space point m is the world point R_c * m + t_c (R row-major, t in mm).  R is
+ * NOT required to be orthonormal: the library only applies it, it never inverts it.  Rig g owns the cameras
+ * rig_begin[g] .. rig_begin[g + 1] - 1; the ranges are ascending, cover 0 .. n exactly, and each holds 1 .. DH_RIG_MAX_CAMERAS
+ * cameras (the views of a person are a 64-bit mask).  The table is immutable, lives on the camera table's device, and the camera
+ * table must outlive it.  dh_rig_create answers DH_EINVAL before anything is allocated for: NULL arguments, n_rigs < 1, ranges
+ * that are not ascending or do not cover the table, an empty or too large rig, a non-finite entry of R or t.
+ *
+ * A rig tracker keeps, per rig, DH_RIG_MAX_TRACKS track slots and next_id (1 when created or reset).  A step runs the heads calls
+ * of section 14 (max_heads and radius of the params) on one frame per camera, exactly as dh_predict_heads_cameras(_device), and
+ * then, per rig, over the heads (c, j), j < min(n_heads[c], max_heads), of its PRESENT cameras (present[c] != 0; all when present
+ * is NULL):
+ *   0. world midpoint of head k with camera-space mid_point m: w_q = ((R[q][0] * m_0 + R[q][1] * m_1) + R[q][2] * m_2) + t_q in
+ *      f32, every product and sum rounded on its own, in exactly that order.  Its world cell: (int32_t) per axis as the support
+ *      calls convert (NaN -> 0, saturating), widened to 64 bits.  All distances are Chebyshev distances of cells in 64 bits;
+ *   1. ORDER the heads by (support.mass descending, camera c ascending, j ascending);
+ *   2. FUSE: walking the heads in that order, a head joins the first person (in order of creation) whose ANCHOR cell is within
+ *      fuse_gate (d <= fuse_gate) and that has no member from the same camera yet; otherwise it founds a new person, and its cell
+ *      is that person's anchor; when DH_RIG_MAX_PERSONS persons exist already it stays unassigned.  (Two heads of one camera
+ *      were told apart by section 14's merge rule and are never the same person.)
+ *   3. PERSON RECORD: cell = floor(sum of the members' world cells / members) per axis (exact in 64 bits, floor toward minus
+ *      infinity); views = bit (c - rig_begin[g]) for every member camera c; n_views; mass = the members' support.mass summed,
+ *      saturating at UINT64_MAX; best_cam / best_head = the anchor's (c, j), c being the index in the camera table (its heaviest
+ *      view: heads[c][j] carries the rotation in that camera's frame); world = the anchor's f32 world midpoint;
+ *   4. MATCH the persons against the rig's track slots as section 15 matches heads against a camera's: d(t, i) between the cell
+ *      of live track t's person record and person i's cell; pairs with d <= gate taken greedily in the order (d, person i, slot t)
+ *      ascending; a matched track takes the whole person record, hits and age + 1, misses = 0; an unmatched live track age + 1,
+ *      misses + 1, zeroed (freed) when misses > max_misses; unmatched persons in ascending i each take the lowest free slot with
+ *      id = next_id, age = hits = 1, misses = 0 (next_id + 1, wrapping from UINT32_MAX to 1: 0 is never an id), or get id 0 when
+ *      no slot is free.  age, hits, misses saturate at UINT32_MAX.  A person record's id is its track's id, in the persons output
+ *      and in the track record alike;
+ *   5. OUTPUTS: rig_ids[c][j] = the id of the person head (c, j) belongs to; 0 for unassigned heads, for j >= n, and for every
+ *      head of an absent camera.  n_persons[g], persons[g][DH_RIG_MAX_PERSONS] (unused records zero) and, when asked, the
+ *      snapshot tracks[g][DH_RIG_MAX_TRACKS] after the step.  n_heads and heads are written for every camera, absent ones
+ *      included, byte-identical to dh_predict_heads_cameras(_device) on the same frames;
+ *   6. a rig with NO present camera in a step keeps its whole state (no ageing; n_persons 0, ids 0); a rig with present cameras
+ *      but no head ages its tracks.  An absent camera contributes nothing.
+ * Integer apart from step 0's three products and three sums: bit-identical run to run, and to the sequential statement of the
+ * rule in depthhead_amd/csrc/dh_rig.h.  Defaults (choices): DH_RIG_FUSE_GATE 100 cells = mm -- the section 14 quality runs
+ * place a detected head within about 90 mm of the truth, so two views of one head can lie that far apart; gate DH_TRACK_GATE and max_misses
+ * DH_TRACK_MAX_MISSES as section 15.  DESIGN.md section 16 measures them on two parallel views of two-head scenes (ids held,
+ * fused cell within 54 mm of the truth); it does not measure the gate against two different people closer than 100 mm.
+ * heads and rig_ids are [n_cams][max_heads], n_heads [n_cams], n_persons [n_rigs], persons [n_rigs][DH_RIG_MAX_PERSONS], tracks
+ * (nullable) [n_rigs][DH_RIG_MAX_TRACKS]; host memory for the host calls, device memory for the _device and capture calls.
+ * DH_EINVAL before anything is launched: NULL arguments, max_heads outside 1 .. DH_MAX_HEADS, radius, fuse_gate or gate above
+ * 2^31 - 1, a rig out of range in reset, a rig table of another device than the predictor.  One tracker's steps must be
+ * stream-ordered.  After dh_predictor_reserve(p, n_cams, w, h) and one heads call of that workspace the device step allocates
+ * nothing and does not synchronise; the capture call does both itself before it captures.  The host step runs the heads
+ * pipeline in resident slices of cameras and fuses once, after the last slice, over the heads of the whole table: a rig is
+ * never cut in two. */
+#define DH_RIG_MAX_CAMERAS 64
+#define DH_RIG_MAX_PERSONS 16
+#define DH_RIG_MAX_TRACKS 16
+#define DH_RIG_FUSE_GATE 100
+typedef struct dh_rig_person {
+    uint64_t views;       /* bit k: camera rig_begin[g] + k sees this person */
+    uint64_t mass;        /* the members' support.mass summed, saturating */
+    int32_t cell[3];      /* floor of the mean of the members' world cells */
+    uint32_t n_views;
+    float world[3];       /* the anchor's world midpoint */
+    uint32_t id;          /* the person's track id; 0: no free slot */
+    uint32_t best_cam;    /* the anchor: camera (index in the camera table) and head of its heaviest view */
+    uint32_t best_head;
+} dh_rig_person;          /* 56 bytes, no padding */
+typedef struct dh_rig_track {
+    uint32_t id;          /* 0 = free slot */
+    uint32_t age;         /* steps of the rig (with a present camera) since birth, saturating */
+    uint32_t hits;        /* steps matched (birth counts), saturating */
+    uint32_t misses;      /* consecutive steps without a match */
+    dh_rig_person person; /* last matched person */
+} dh_rig_track;           /* 72 bytes, no padding */
+typedef struct dh_rig_track_params {
+    int32_t max_heads;    /* 1 .. DH_MAX_HEADS, passed to the heads pipeline */
+    uint32_t radius;      /* support radius of the heads pipeline, 0 .. 2^31 - 1 */
+    uint32_t fuse_gate;   /* cells (= mm), 0 .. 2^31 - 1; default DH_RIG_FUSE_GATE */
+    uint32_t gate;        /* cells (= mm), 0 .. 2^31 - 1; default DH_TRACK_GATE */
+    uint32_t max_misses;  /* default DH_TRACK_MAX_MISSES */
+} dh_rig_track_params;    /* 20 bytes */
+typedef struct dh_rig dh_rig;
+typedef struct dh_rig_tracker dh_rig_tracker;
+int dh_rig_create(const dh_cameras *c, const float *R /* [n][9] row-major */, const float *t /* [n][3] mm */,
+                  const int32_t *rig_begin /* [n_rigs + 1] */, int n_rigs, dh_rig **out);
+int dh_rig_destroy(dh_rig *r);
+int dh_rig_tracker_create(const dh_rig *r, const dh_rig_track_params *prm, dh_rig_tracker **out);   /* the rig table must outlive it */
+int dh_rig_tracker_destroy(dh_rig_tracker *t);
+/* the created state (every slot free, next_id 1) for one rig or all (rig = -1); stream-ordered */
+int dh_rig_tracker_reset(dh_rig_tracker *t, int rig, void *stream);
+int dh_rig_tracker_step(dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                        uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons,
+                        dh_rig_track *tracks);
+int dh_rig_tracker_step_device(dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                               uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons,
+                               dh_rig_track *tracks, void *stream);
+/* synchronous copy-out, each pointer nullable: tracks [n_rigs][DH_RIG_MAX_TRACKS], next_id [n_rigs] */
+int dh_rig_tracker_state(dh_rig_tracker *t, dh_rig_track *tracks, uint32_t *next_id);
+/* capture one dh_rig_tracker_step_device (device pointers) into the predictor's graph slot; each dh_graph_launch is one step */
+int dh_rig_tracker_capture(dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                           uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons,
+                           dh_rig_track *tracks);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
