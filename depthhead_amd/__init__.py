@@ -2,5 +2,6 @@
 `HoughPrediction::predict_parameter_parallel` path of Entscheider/depthhead)."""
 from .forest import Forest, NODE_DTYPE  # noqa: F401
 from .synth import ModelParams  # noqa: F401
+from .render import Mesh, Renderer, euler_to_matrix  # noqa: F401
 
-__all__ = ["Forest", "NODE_DTYPE", "ModelParams"]
+__all__ = ["Forest", "NODE_DTYPE", "ModelParams", "Mesh", "Renderer", "euler_to_matrix"]

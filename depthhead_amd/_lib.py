@@ -48,6 +48,20 @@ RIG_MAX_TRACKS = 16        # DH_RIG_MAX_TRACKS
 RIG_FUSE_GATE = 100        # DH_RIG_FUSE_GATE (cells = mm)
 
 
+# dh_render_instance: one posed mesh of a render call (dh_render_depth*)
+RENDER_INSTANCE_DTYPE = np.dtype([("frame", "<u4"), ("mesh", "<u4"), ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "<f4"),
+                                  ("flags", "<u4")], align=True)
+assert RENDER_INSTANCE_DTYPE.itemsize == 64
+RENDER_HEAD = 1            # DH_RENDER_HEAD
+RENDER_MAX_SIZE = 16384    # DH_RENDER_MAX_SIZE
+
+
+class RenderParams(C.Structure):
+    """dh_render_params"""
+    _fields_ = [("noise_amplitude", C.c_uint32), ("reserved0", C.c_uint32), ("hole_probability", C.c_double), ("seed", C.c_uint64),
+                ("reserved", C.c_uint64 * 2)]
+
+
 class RigTrackParams(C.Structure):
     """dh_rig_track_params"""
     _fields_ = [("max_heads", C.c_int32), ("radius", C.c_uint32), ("fuse_gate", C.c_uint32), ("gate", C.c_uint32),
@@ -98,6 +112,9 @@ EXPORTS = [
     "dh_multi_tracker_step_device", "dh_multi_tracker_state", "dh_multi_tracker_capture",
     "dh_rig_create", "dh_rig_destroy", "dh_rig_tracker_create", "dh_rig_tracker_destroy", "dh_rig_tracker_reset",
     "dh_rig_tracker_step", "dh_rig_tracker_step_device", "dh_rig_tracker_state", "dh_rig_tracker_capture",
+    "dh_mesh_create", "dh_mesh_destroy", "dh_mesh_info", "dh_renderer_create", "dh_renderer_destroy",
+    "dh_renderer_set_profiling", "dh_renderer_timing",
+    "dh_render_depth", "dh_render_depth_cameras", "dh_render_depth_device", "dh_render_depth_cameras_device",
 ]
 
 

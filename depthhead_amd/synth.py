@@ -354,3 +354,63 @@ def fit_forest(n_trees: int = 10, max_depth: int = 15, seed: int = FOREST_SEED_B
     offsets = np.concatenate(leaf_off).astype(np.float32) if n_votes.sum() else np.zeros((0, 3), dtype=np.float32)
     rotations = np.concatenate(leaf_rot).astype(np.float64) if n_votes.sum() else np.zeros((0, 3))
     return Forest(roots, nodes, np.array(leaf_prob), begin, begin.copy(), offsets, rotations)
+
+
+# ------------------------------------------------------------------ a procedural head mesh (rendered by depthhead_amd.render)
+def _icosphere(subdiv: int):
+    """Unit icosphere: (verts [nv, 3] f64, tris [nt, 3]); every subdivision splits a triangle into four."""
+    g = (1.0 + 5.0 ** 0.5) / 2.0
+    verts = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g),
+             (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    verts = [tuple(np.asarray(v, dtype=np.float64) / np.sqrt(1.0 + g * g)) for v in verts]
+    tris = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+            (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(subdiv):
+        cache: dict = {}
+
+        def mid(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in cache:
+                m = (np.asarray(verts[a]) + np.asarray(verts[b])) / 2.0
+                verts.append(tuple(m / np.sqrt((m * m).sum())))
+                cache[key] = len(verts) - 1
+            return cache[key]
+
+        nxt = []
+        for a, b, c in tris:
+            ab, bc, ca = mid(a, b), mid(b, c), mid(c, a)
+            nxt += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        tris = nxt
+    return np.asarray(verts, dtype=np.float64), np.asarray(tris, dtype=np.uint32)
+
+
+HEAD_SEMI_AXES = (75.0, 105.0, 95.0)   # mm: half width (x), half height (y, down), half depth (z, away from the camera)
+
+
+def head_mesh(subdiv: int = 3):
+    """A procedural head, (verts [nv, 3] f32 mm, tris [nt, 3] u32), centred on its origin in the camera frame (x right, y down,
+    z forward: the face looks along -z, toward the camera).  An icosphere stretched to an ellipsoid of HEAD_SEMI_AXES with two
+    radial bumps on the camera-facing side: a nose (about 26 mm, a little below the centre) and a chin (about 12 mm, further
+    down).  The bumps move every vertex along its own ray, so the mesh stays closed; they make the silhouette and the depth
+    profile change with yaw (the nose leaves the middle) and with pitch (nose and chin move up or down), which a sphere's do not.
+    subdiv 3: 642 vertices, 1280 triangles."""
+    u, tris = _icosphere(int(subdiv))
+
+    def bump(direction, height, width):
+        d = np.asarray(direction, dtype=np.float64)
+        d = d / np.sqrt((d * d).sum())
+        ang = np.arccos(np.clip(u @ d, -1.0, 1.0))
+        return height * np.exp(-(ang * ang) / (2.0 * width * width))
+
+    radial = 1.0 + bump((0.0, 0.12, -1.0), 0.28, 0.16) + bump((0.0, 0.85, -0.6), 0.12, 0.30)
+    verts = u * radial[:, None] * np.asarray(HEAD_SEMI_AXES)
+    return verts.astype(np.float32), tris
+
+
+def box_mesh(lo, hi):
+    """An axis-aligned box (8 vertices, 12 triangles) from corner `lo` to corner `hi`."""
+    (x0, y0, z0), (x1, y1, z1) = lo, hi
+    verts = np.array([(x, y, z) for z in (z0, z1) for y in (y0, y1) for x in (x0, x1)], dtype=np.float32)
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    tris = np.array([t for a, b, c, d in quads for t in ((a, b, c), (a, c, d))], dtype=np.uint32)
+    return verts, tris

@@ -192,3 +192,48 @@ def synthetic_data(n: int, w: int = 320, h: int = 240, first: int = 0):
     from . import synth
     for i in range(n):
         yield synthetic_truth(w, h, synth.FRAME_SEED_BASE + first + i)
+
+
+# ------------------------------------------------------------------ rendered subjects: a head whose rotation can be observed
+RENDER_SEED_BASE = 0x4EAD0000
+RENDER_BATCH = 64
+YAW, PITCH, ROLL = 1, 2, 0    # index of each angle in rot_deg: the viewer turns about y by rot[1], about x by rot[2], about z by rot[0]
+
+
+def rendered_pose(w: int, h: int, seed: int, yaw=(-40, 40), pitch=(-20, 20), roll=(-10, 10)):
+    """(pos3d [3] f32 mm, rot_deg [3] f32) of rendered frame `seed`: the head centre where `synth.head_truth` puts its sphere
+    (700 - 1200 mm, the middle half of the frame), the angles uniform in their ranges (degrees)."""
+    from . import synth
+    u = synth.SplitMix(seed).uniform(6)
+    K = synth.default_intrinsic(w, h)
+    z0 = 700.0 + 500.0 * u[0]
+    hx, hy = w * (0.25 + 0.5 * u[1]), h * (0.25 + 0.5 * u[2])
+    pos3d = np.array([(hx - K[0, 2]) * z0 / K[0, 0], (hy - K[1, 2]) * z0 / K[1, 1], z0], dtype=np.float32)
+    rot = np.zeros(3, dtype=np.float32)
+    for axis, rng, ui in ((YAW, yaw, u[3]), (PITCH, pitch, u[4]), (ROLL, roll, u[5])):
+        rot[axis] = rng[0] + (rng[1] - rng[0]) * ui
+    return pos3d, rot
+
+
+def rendered_data(n: int, w: int = 320, h: int = 240, first: int = 0, mesh=None, yaw=(-40, 40), pitch=(-20, 20), roll=(-10, 10),
+                  device: int = 0, noise: int = 2, holes: float = 0.02):
+    """`n` frames of a head mesh rendered on the GPU, as the (depth, mask, K, pos3d, rot_deg) tuples `synthetic_data` yields:
+    frame i (seed RENDER_SEED_BASE + first + i) holds the head (`mesh`: (verts, tris), default `synth.head_mesh()`) at
+    `rendered_pose`, turned by `render.euler_to_matrix(rot_deg)`, and a torso box that is not a head below it, its front 50 mm
+    behind the head centre; +-`noise` mm and `holes` as `synth.biwi_like`.  Rendered RENDER_BATCH frames at a time."""
+    from . import render, synth
+    verts, tris = synth.head_mesh() if mesh is None else mesh
+    K = synth.default_intrinsic(w, h)
+    with render.Mesh(verts, tris, device) as head, render.Mesh(*synth.box_mesh((-142.0, 85.0, 50.0), (142.0, 700.0, 250.0)), device) as torso, \
+            render.Renderer(device) as rd:
+        for b0 in range(0, n, RENDER_BATCH):
+            nb = min(RENDER_BATCH, n - b0)
+            poses = [rendered_pose(w, h, RENDER_SEED_BASE + first + b0 + i, yaw, pitch, roll) for i in range(nb)]
+            items = []
+            for i, (pos, rot) in enumerate(poses):
+                items.append((i, 0, render.euler_to_matrix(rot), pos, 1.0, True))
+                items.append((i, 1, np.eye(3, dtype=np.float32), pos, 1.0, False))
+            frames, masks = rd.render([head, torso], render.instances(items), nb, w, h, K, noise=noise, holes=holes,
+                                      seed=RENDER_SEED_BASE + first + b0)
+            for i, (pos, rot) in enumerate(poses):
+                yield frames[i], masks[i], K, pos, rot

@@ -506,6 +506,77 @@ int dh_rig_tracker_capture(dh_predictor *p, dh_rig_tracker *t, const uint16_t *f
                            uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons,
                            dh_rig_track *tracks);
 
+/* ---- rendering posed meshes to depth frames and head masks ----
+ * The reference draws its head model for display only (utils/src/headwin.rs); a renderer that produces the depth frame and head
+ * mask a Kinect would have recorded is not in it: PARITY UNPINNED, the definition below is this library's.  A batch is n frames of
+ * w x h and a list of instances; instance i draws mesh `mesh` into frame `frame` with vertex v carried to
+ *     p[j] = ((R[j][0] * sv0 + R[j][1] * sv1) + R[j][2] * sv2) + t[j],  sv = v * scale                       (f32, no contraction)
+ * and projected by the frame's intrinsic matrix as space_to_img_coord does (r = K p in the reference's mat-vec order, x = r0 / r2,
+ * y = r1 / r2), snapped to 1/16 pixel: s = floorf(x * 16.0f + 0.5f).  A triangle is dropped whole (never clipped) when a vertex
+ * has p.z < 1.0f, a snapped coordinate is not finite or lies outside +-2^20, or its area is zero; both windings are drawn.  A pixel
+ * is covered when its centre (16 x + 8, 16 y + 8) lies inside the triangle by int64 edge functions with a top-left fill rule
+ * (triangles sharing an edge cover every pixel along it exactly once).  Depth at a covered pixel, in f64 from the edge values e_i
+ * and iz_i = 1.0 / (double)p_i.z:  z = (double)(e0 + e1 + e2) / ((e0 * iz0 + e1 * iz1) + e2 * iz2),  d = (uint32)(z + 0.5) clamped to
+ * [1, 65535].  Every pixel keeps the smallest key (d << 1) | (head ? 0 : 1) over all triangles of its frame's instances (order-free;
+ * a head wins a depth tie): frames = d of that key or 0 where nothing was drawn, masks = 1 where the key is a head's, else 0.
+ * Sensor model, per pixel index k = (frame * h + y) * w + x with u(c) = the splitmix64 output number c (from 0) of the stream seeded
+ * with `seed`: a foreground pixel becomes clamp(d + (int)(u(2k) % (2a + 1)) - a, 1, 65535) with a = noise_amplitude, and then 0 (a
+ * hole) when (u(2k + 1) >> 11) < floor(hole_probability * 2^53).  Holes leave the mask as it is.  a = 0 and probability 0: no change.
+ * Bit-identical run to run and to tests/render_ref.py.
+ * A dh_mesh is immutable and lives on one device; a dh_renderer owns the triangle records, tile lists and (for the host calls)
+ * the output staging of one device, all growing on demand, and is NOT thread-safe.  instances, meshes, K and params are host
+ * memory in every call.  DH_EINVAL before anything is launched, with the outputs untouched: NULL renderer / frames (masks may be
+ * NULL: no mask is written), an instance naming a frame >= n or a mesh >= n_meshes, a mesh of another device, n < 1 or above
+ * 65535, w or h outside 1 .. DH_RENDER_MAX_SIZE, hole_probability outside [0, 1] (NaN included), noise_amplitude above 65535, a
+ * camera table of another device or whose length is not n.  The host calls are synchronous.  The _device calls take device
+ * output pointers and enqueue on `stream` (NULL = default stream); they wait on the host once, for the size of the tile lists,
+ * and their output is ordered before whatever is enqueued on that stream next (the _device prediction, tracker and rig calls). */
+#define DH_RENDER_HEAD 1u          /* dh_render_instance.flags bit 0: the instance is a head (mask 1, wins depth ties) */
+#define DH_RENDER_MAX_SIZE 16384   /* largest frame width or height */
+typedef struct dh_render_instance {
+    uint32_t frame;    /* 0 .. n - 1 */
+    uint32_t mesh;     /* index into the call's mesh list */
+    float    R[9];     /* row-major */
+    float    t[3];     /* mm */
+    float    scale;
+    uint32_t flags;    /* DH_RENDER_HEAD */
+} dh_render_instance;  /* 64 bytes, no padding */
+typedef struct dh_render_params {
+    uint32_t noise_amplitude;   /* a: integer noise in [-a, a]; 0 = none */
+    uint32_t reserved0;
+    double   hole_probability;  /* in [0, 1]; 0 = none */
+    uint64_t seed;
+    uint64_t reserved[2];       /* 0 */
+} dh_render_params;    /* 40 bytes */
+typedef struct dh_mesh dh_mesh;
+typedef struct dh_renderer dh_renderer;
+/* Copies nv vertices (x, y, z triples, mm) and nt triangles (index triples) to `device`.  DH_EINVAL: NULL arguments, nv or nt 0,
+ * an index >= nv, a non-finite vertex. */
+int dh_mesh_create(const float *verts, uint32_t nv, const uint32_t *tris, uint32_t nt, int device, dh_mesh **out);
+int dh_mesh_destroy(dh_mesh *m);
+/* each pointer nullable; bbox = min x, y, z then max x, y, z */
+int dh_mesh_info(const dh_mesh *m, uint32_t *nv, uint32_t *nt, float bbox[6]);
+int dh_renderer_create(int device, dh_renderer **out);
+int dh_renderer_destroy(dh_renderer *r);
+/* params NULL: no sensor model.  frames [n][h][w] u16, masks [n][h][w] u8 or NULL. */
+int dh_render_depth(dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances,
+                    uint32_t n_instances, int n, int w, int h, const float K[9], const dh_render_params *params, uint16_t *frames,
+                    uint8_t *masks);
+/* frame i is seen through camera i of the table, which must hold exactly n cameras */
+int dh_render_depth_cameras(dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances,
+                            uint32_t n_instances, int n, int w, int h, const dh_cameras *c, const dh_render_params *params,
+                            uint16_t *frames, uint8_t *masks);
+int dh_render_depth_device(dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances,
+                           uint32_t n_instances, int n, int w, int h, const float K[9], const dh_render_params *params,
+                           uint16_t *frames, uint8_t *masks, void *stream);
+int dh_render_depth_cameras_device(dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes,
+                                   const dh_render_instance *instances, uint32_t n_instances, int n, int w, int h, const dh_cameras *c,
+                                   const dh_render_params *params, uint16_t *frames, uint8_t *masks, void *stream);
+/* device time of the last render's kernels in ms (setup, offsets, fill, resolve), measured with events when `on` was set by
+ * dh_renderer_set_profiling before it; synchronises */
+int dh_renderer_set_profiling(dh_renderer *r, int on);
+int dh_renderer_timing(dh_renderer *r, float ms[4]);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
