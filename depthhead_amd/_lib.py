@@ -62,6 +62,20 @@ class RenderParams(C.Structure):
                 ("reserved", C.c_uint64 * 2)]
 
 
+# dh_fit_record: what one fitted instance reports (dh_fit_depth*)
+FIT_RECORD_DTYPE = np.dtype([("points", "<u4"), ("steps", "<u4"), ("status", "<u4"), ("reserved", "<u4"), ("sum_r2_fixed", "<i8")],
+                            align=True)
+assert FIT_RECORD_DTYPE.itemsize == 24
+FIT_MAX_POINTS = 32768     # DH_FIT_MAX_POINTS
+FIT_MAX_EXTENT = 4096      # DH_FIT_MAX_EXTENT (mm)
+
+
+class FitParams(C.Structure):
+    """dh_fit_params (`lam` is the header's `lambda`)"""
+    _fields_ = [("coarse_iterations", C.c_uint32), ("iterations", C.c_uint32), ("gate", C.c_double * 2), ("lam", C.c_double),
+                ("min_points", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
 class RigTrackParams(C.Structure):
     """dh_rig_track_params"""
     _fields_ = [("max_heads", C.c_int32), ("radius", C.c_uint32), ("fuse_gate", C.c_uint32), ("gate", C.c_uint32),
@@ -115,6 +129,8 @@ EXPORTS = [
     "dh_mesh_create", "dh_mesh_destroy", "dh_mesh_info", "dh_renderer_create", "dh_renderer_destroy",
     "dh_renderer_set_profiling", "dh_renderer_timing",
     "dh_render_depth", "dh_render_depth_cameras", "dh_render_depth_device", "dh_render_depth_cameras_device",
+    "dh_fit_model_create", "dh_fit_model_destroy", "dh_fit_model_info", "dh_fit_params_default", "dh_fitter_create",
+    "dh_fitter_destroy", "dh_fit_depth", "dh_fit_depth_cameras", "dh_fit_depth_device", "dh_fit_depth_cameras_device",
 ]
 
 

@@ -18,6 +18,7 @@
 
 #include "dh_internal.h"
 #include "dh_render.h"
+#include "dh_fit.h"
 
 // ------------------------------------------------------------------ errors
 #define fail dh_fail_          // (dh_host.cpp: one message slot per host thread)
@@ -2703,6 +2704,237 @@ static int render_depth_cameras_device_(dh_renderer *r, const dh_mesh *const *me
     return render_run(r, RenderReq{meshes, n_meshes, instances, n_instances, n, w, h, nullptr, c, true, params, frames, masks}, true, (hipStream_t)stream, "dh_render_depth_cameras_device");
 }
 
+// ------------------------------------------------------------------ fitting posed models to depth frames
+// A model: points and unit normals on one device, immutable.
+struct dh_fit_model {
+    int device = 0;
+    uint32_t n = 0;
+    double radius = 0.0;          // the largest |v|
+    Buf<float> pts, nrm;
+};
+static int fit_model_create_(const float *points, const float *normals, uint32_t n, int device, dh_fit_model **out) {
+    if (!out) return fail(DH_EINVAL, "dh_fit_model_create: NULL argument");
+    *out = nullptr;
+    if (!points || !normals) return fail(DH_EINVAL, "dh_fit_model_create: NULL argument");
+    if (n == 0 || n > DH_FIT_MAX_POINTS) return fail(DH_EINVAL, "dh_fit_model_create: %u points, expected 1 .. %u", n, DH_FIT_MAX_POINTS);
+    std::unique_ptr<dh_fit_model> m(new dh_fit_model);
+    m->device = device; m->n = n;
+    double r2 = 0.0;
+    for (uint32_t i = 0; i < n; ++i) {
+        double v2 = 0.0, m2 = 0.0;
+        for (int c = 0; c < 3; ++c) {
+            const float v = points[(size_t)i * 3 + c], nm = normals[(size_t)i * 3 + c];
+            if (!std::isfinite(v)) return fail(DH_EINVAL, "dh_fit_model_create: point %u is not finite", i);
+            if (!std::isfinite(nm)) return fail(DH_EINVAL, "dh_fit_model_create: normal %u is not finite", i);
+            v2 += (double)v * (double)v; m2 += (double)nm * (double)nm;
+        }
+        if (!(m2 >= 0.98 && m2 <= 1.02)) return fail(DH_EINVAL, "dh_fit_model_create: normal %u has squared length %g, expected 0.98 .. 1.02", i, m2);
+        r2 = std::max(r2, v2);
+    }
+    m->radius = sqrt(r2);
+    DeviceGuard guard(device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(m->pts.alloc((size_t)n * 3));
+    TRY(m->nrm.alloc((size_t)n * 3));
+    HIP_TRY(hipMemcpy(m->pts.get(), points, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->nrm.get(), normals, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    *out = m.release();
+    return DH_OK;
+}
+static int fit_model_destroy_(dh_fit_model *m) {
+    if (!m) return DH_OK;
+    DeviceGuard guard(m->device);
+    delete m;
+    return DH_OK;
+}
+static int fit_model_info_(const dh_fit_model *m, uint32_t *n, double *radius) {
+    if (!m) return fail(DH_EINVAL, "dh_fit_model_info: NULL model");
+    if (n) *n = m->n;
+    if (radius) *radius = m->radius;
+    return DH_OK;
+}
+static int fit_params_default_(dh_fit_params *p) {
+    if (!p) return fail(DH_EINVAL, "dh_fit_params_default: NULL argument");
+    memset(p, 0, sizeof *p);
+    p->coarse_iterations = 6; p->iterations = 14;
+    p->gate[0] = 120.0; p->gate[1] = 25.0;
+    p->lambda = 1e-3;
+    p->min_points = 16;
+    return DH_OK;
+}
+
+// A fitter: the call's tables (staged in page-locked memory, one upload per call) and, for the host calls, the frames and the
+// outputs on the device.  Everything grows on demand and is kept between calls.
+struct dh_fitter {
+    int device = 0;
+    hipStream_t s = nullptr;                 // the host calls' stream
+    hipEvent_t ev_up = nullptr;              // the last call's upload has left the staging buffer
+    hipEvent_t ev_done = nullptr;            // the last call's kernel is through with the tables
+    Buf<unsigned char, PINNED> stage;        // models | instances
+    Buf<unsigned char> tables;
+    Buf<uint16_t> frames;                    // host calls
+    Buf<dh_render_instance> out;
+    Buf<dh_fit_record> rec;
+    ~dh_fitter() {
+        if (ev_up) (void)hipEventDestroy(ev_up);
+        if (ev_done) (void)hipEventDestroy(ev_done);
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+// (the handle alone: the stream, the events and the buffers come with the first fit, after its arguments were checked)
+static int fitter_create_(int device, dh_fitter **out) {
+    if (!out) return fail(DH_EINVAL, "dh_fitter_create: NULL argument");
+    *out = nullptr;
+    if (device < 0) return fail(DH_EINVAL, "dh_fitter_create: device %d", device);
+    std::unique_ptr<dh_fitter> f(new dh_fitter);
+    f->device = device;
+    *out = f.release();
+    return DH_OK;
+}
+static int fitter_destroy_(dh_fitter *f) {
+    if (!f) return DH_OK;
+    if (f->s) {
+        DeviceGuard guard(f->device);
+        (void)hipDeviceSynchronize();
+        delete f;
+    } else delete f;
+    return DH_OK;
+}
+static int fitter_init(dh_fitter *f) {
+    if (f->s) return DH_OK;
+    TRY(hip_step(hipStreamCreateWithFlags(&f->s, hipStreamNonBlocking), "hipStreamCreate"));
+    TRY(hip_step(hipEventCreateWithFlags(&f->ev_up, hipEventDisableTiming), "hipEventCreate"));
+    TRY(hip_step(hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming), "hipEventCreate"));
+    return DH_OK;
+}
+
+// One fit call.  dev: frames / out / records are device pointers and `stream` the caller's; else host pointers.
+struct FitReq {
+    const uint16_t *frames; int n, w, h;
+    const float *K; const dh_cameras *cams; bool use_cams;
+    const dh_fit_model *const *models; uint32_t n_models;
+    const dh_render_instance *inst; uint32_t n_inst;
+    const dh_fit_params *prm;
+    dh_render_instance *out; dh_fit_record *rec;
+};
+static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, const char *who) {
+    // ---- refusals: all of them before anything is allocated or launched
+    if (!f) return fail(DH_EINVAL, "%s: NULL fitter", who);
+    if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!q.out || !q.rec) return fail(DH_EINVAL, "%s: NULL output", who);
+    if (q.n < 1 || q.n > 65535) return fail(DH_EINVAL, "%s: n = %d, expected 1 .. 65535 frames", who, q.n);
+    if (q.w < 1 || q.h < 1 || q.w > DH_RENDER_MAX_SIZE || q.h > DH_RENDER_MAX_SIZE)
+        return fail(DH_EINVAL, "%s: frame size %dx%d, expected 1 .. %d each way", who, q.w, q.h, DH_RENDER_MAX_SIZE);
+    if (q.use_cams) {
+        if (!q.cams) return fail(DH_EINVAL, "%s: NULL camera table", who);
+        if (q.cams->device != f->device) return fail(DH_EINVAL, "%s: the camera table lives on device %d, the fitter on %d", who, q.cams->device, f->device);
+        if (q.cams->n != q.n) return fail(DH_EINVAL, "%s: the camera table holds %d cameras, the batch %d frames", who, q.cams->n, q.n);
+    } else if (!q.K) return fail(DH_EINVAL, "%s: NULL K", who);
+    dh_fit_params prm;
+    (void)fit_params_default_(&prm);
+    if (q.prm) prm = *q.prm;
+    if ((uint64_t)prm.coarse_iterations + prm.iterations > 64)
+        return fail(DH_EINVAL, "%s: coarse_iterations %u + iterations %u above 64", who, prm.coarse_iterations, prm.iterations);
+    for (int g = 0; g < 2; ++g)
+        if (!(prm.gate[g] > 0.0 && prm.gate[g] <= 4096.0)) return fail(DH_EINVAL, "%s: gate[%d] = %g outside (0, 4096]", who, g, prm.gate[g]);
+    if (!(prm.lambda >= 0.0) || !std::isfinite(prm.lambda)) return fail(DH_EINVAL, "%s: lambda %g, expected a finite value >= 0", who, prm.lambda);
+    if (prm.min_points < 6) return fail(DH_EINVAL, "%s: min_points %u below 6", who, prm.min_points);
+    if (prm.reserved0 || prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
+    if (q.n_inst && !q.models) return fail(DH_EINVAL, "%s: NULL models", who);
+    if (q.n_inst > 0x7fffffffu) return fail(DH_EINVAL, "%s: too many instances", who);
+    for (uint32_t i = 0; i < q.n_inst; ++i) {
+        const dh_render_instance &in = q.inst[i];
+        if (in.frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, q.n);
+        if (in.mesh >= q.n_models) return fail(DH_EINVAL, "%s: instance %u names model %u of %u", who, i, in.mesh, q.n_models);
+        bool finite = std::isfinite(in.scale);
+        for (int c = 0; c < 9; ++c) finite = finite && std::isfinite(in.R[c]);
+        for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(in.t[c]);
+        if (!finite) return fail(DH_EINVAL, "%s: instance %u has a non-finite R, t or scale", who, i);
+        // R must be near a rotation: the magnitude bound of the int64 sums (dh_fit.h) rests on |R x| <= 1.03 |x|
+        for (int a = 0; a < 3; ++a)
+            for (int b = a; b < 3; ++b) {
+                const double g = ((double)in.R[3 * a] * (double)in.R[3 * b] + (double)in.R[3 * a + 1] * (double)in.R[3 * b + 1]) +
+                                 (double)in.R[3 * a + 2] * (double)in.R[3 * b + 2];
+                if (!(fabs(g - (a == b ? 1.0 : 0.0)) <= DH_FIT_R_TOLERANCE))
+                    return fail(DH_EINVAL, "%s: instance %u has an R that is not orthonormal: (R R^T)[%d][%d] = %g", who, i, a, b, g);
+            }
+        const dh_fit_model *m = q.models[in.mesh];
+        if (!m) return fail(DH_EINVAL, "%s: model %u is NULL", who, in.mesh);
+        if (m->device != f->device) return fail(DH_EINVAL, "%s: model %u lives on device %d, the fitter on %d", who, in.mesh, m->device, f->device);
+        const double extent = fabs((double)in.scale) * m->radius;
+        if (extent > DH_FIT_MAX_EXTENT) return fail(DH_EINVAL, "%s: instance %u spans %g mm from its origin (limit %g)", who, i, extent, DH_FIT_MAX_EXTENT);
+    }
+    if (q.n_inst == 0) return DH_OK;
+
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(fitter_init(f));
+    hipStream_t s = dev ? stream : f->s;
+    FitArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = q.n; a.w = q.w; a.h = q.h;
+    if (q.use_cams) a.cams = q.cams->dev.get();
+    else memcpy(a.k, q.K, sizeof a.k);
+    a.n_inst = q.n_inst;
+    a.coarse = prm.coarse_iterations; a.full = prm.iterations; a.min_points = prm.min_points;
+    a.gate[0] = prm.gate[0]; a.gate[1] = prm.gate[1];
+    a.lam1 = 1.0 + prm.lambda;
+    // ---- the call's tables: one staging buffer, one upload
+    const size_t o_inst = ((size_t)q.n_models * sizeof(FitModel) + 15) & ~(size_t)15;
+    const size_t bytes = o_inst + (size_t)q.n_inst * sizeof(dh_render_instance);
+    HIP_TRY(hipEventSynchronize(f->ev_up));          // (the staging buffer is free again; at once when nothing was recorded)
+    if (f->stage.cap() < bytes || f->tables.cap() < bytes) {
+        HIP_TRY(hipDeviceSynchronize());             // (an earlier call may still read the tables)
+        TRY(f->stage.grow(bytes));
+        TRY(f->tables.alloc(f->stage.cap()));
+    }
+    {
+        FitModel *mm = (FitModel *)f->stage.get();
+        for (uint32_t i = 0; i < q.n_models; ++i)    // (a model no instance names may be NULL: its row is never read)
+            mm[i] = q.models[i] && q.models[i]->device == f->device ? FitModel{q.models[i]->pts.get(), q.models[i]->nrm.get(), q.models[i]->n, 0}
+                                                                    : FitModel{nullptr, nullptr, 0, 0};
+        memcpy(f->stage.get() + o_inst, q.inst, (size_t)q.n_inst * sizeof(dh_render_instance));
+    }
+    a.models = (const FitModel *)f->tables.get();
+    a.inst = (const dh_render_instance *)(f->tables.get() + o_inst);
+    const size_t n_px = (size_t)q.n * q.w * q.h;
+    if (!dev) {
+        if (f->frames.cap() < n_px || f->out.cap() < q.n_inst) HIP_TRY(hipDeviceSynchronize());
+        TRY(f->frames.grow(n_px));
+        if (f->out.cap() < q.n_inst) { TRY(f->out.grow(q.n_inst)); TRY(f->rec.alloc(f->out.cap())); }
+        a.frames = f->frames.get(); a.out = f->out.get(); a.rec = f->rec.get();
+    } else { a.frames = q.frames; a.out = q.out; a.rec = q.rec; }
+    HIP_TRY(hipStreamWaitEvent(s, f->ev_done, 0));      // (a call on another stream may still be reading the tables)
+    HIP_TRY(hipMemcpyAsync(f->tables.get(), f->stage.get(), bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(f->ev_up, s));
+    if (!dev) HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    TRY(hip_step(dh_launch_fit(a, s), "k_fit"));
+    HIP_TRY(hipEventRecord(f->ev_done, s));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(q.out, a.out, (size_t)q.n_inst * sizeof(dh_render_instance), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)q.n_inst * sizeof(dh_fit_record), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return DH_OK;
+}
+static int fit_depth_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models, uint32_t n_models,
+                      const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records) {
+    return fit_run(f, FitReq{frames, n, w, h, K, nullptr, false, models, n_models, instances, n_instances, params, out, records}, false, nullptr, "dh_fit_depth");
+}
+static int fit_depth_cameras_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models,
+                              const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records) {
+    return fit_run(f, FitReq{frames, n, w, h, nullptr, c, true, models, n_models, instances, n_instances, params, out, records}, false, nullptr, "dh_fit_depth_cameras");
+}
+static int fit_depth_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models, uint32_t n_models,
+                             const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream) {
+    return fit_run(f, FitReq{frames, n, w, h, K, nullptr, false, models, n_models, instances, n_instances, params, out, records}, true, (hipStream_t)stream, "dh_fit_depth_device");
+}
+static int fit_depth_cameras_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models,
+                                     const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream) {
+    return fit_run(f, FitReq{frames, n, w, h, nullptr, c, true, models, n_models, instances, n_instances, params, out, records}, true, (hipStream_t)stream, "dh_fit_depth_cameras_device");
+}
+
 // ------------------------------------------------------------------ the C ABI
 // Every entry point of include/depthhead_hip.h runs its body (the *_ functions above) inside dh_guard_: the header promises
 // that nothing throws or aborts across the boundary, and the bodies allocate (std::vector, std::string, std::thread).
@@ -2800,4 +3032,14 @@ DH_API(render_depth, (dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_m
 DH_API(render_depth_cameras, (dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances, int n, int w, int h, const dh_cameras *c, const dh_render_params *params, uint16_t *frames, uint8_t *masks), (r, meshes, n_meshes, instances, n_instances, n, w, h, c, params, frames, masks))
 DH_API(render_depth_device, (dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances, int n, int w, int h, const float K[9], const dh_render_params *params, uint16_t *frames, uint8_t *masks, void *stream), (r, meshes, n_meshes, instances, n_instances, n, w, h, K, params, frames, masks, stream))
 DH_API(render_depth_cameras_device, (dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances, int n, int w, int h, const dh_cameras *c, const dh_render_params *params, uint16_t *frames, uint8_t *masks, void *stream), (r, meshes, n_meshes, instances, n_instances, n, w, h, c, params, frames, masks, stream))
+DH_API(fit_model_create, (const float *points, const float *normals, uint32_t n, int device, dh_fit_model **out), (points, normals, n, device, out))
+DH_API(fit_model_destroy, (dh_fit_model *m), (m))
+DH_API(fit_model_info, (const dh_fit_model *m, uint32_t *n, double *radius), (m, n, radius))
+DH_API(fit_params_default, (dh_fit_params *p), (p))
+DH_API(fitter_create, (int device, dh_fitter **out), (device, out))
+DH_API(fitter_destroy, (dh_fitter *f), (f))
+DH_API(fit_depth, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records), (f, frames, n, w, h, K, models, n_models, instances, n_instances, params, out, records))
+DH_API(fit_depth_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records), (f, frames, n, w, h, c, models, n_models, instances, n_instances, params, out, records))
+DH_API(fit_depth_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream), (f, frames, n, w, h, K, models, n_models, instances, n_instances, params, out, records, stream))
+DH_API(fit_depth_cameras_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream), (f, frames, n, w, h, c, models, n_models, instances, n_instances, params, out, records, stream))
 #undef DH_API

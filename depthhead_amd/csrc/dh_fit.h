@@ -1,0 +1,44 @@
+// dh_fit.h -- the fit's kernel argument block, table layouts and launcher (k_fit.hip), shared with the host runtime
+// (dh_api.hip).  Not part of the ABI.  The rule the kernel implements is stated in include/depthhead_hip.h (section "fitting
+// posed models to depth frames") and DESIGN.md section 18.
+#pragma once
+#include "dh_internal.h"
+
+static_assert(sizeof(dh_fit_params) == 56, "dh_fit_params: 56 bytes");
+static_assert(sizeof(dh_fit_record) == 24, "dh_fit_record: 24 bytes");
+
+#define DH_FIT_THREADS 256
+// Fixed point of the sums: S = 2^20.  Magnitude: an instance's R is refused unless |R R^T - I| <= DH_FIT_R_TOLERANCE per element,
+// so |R x| <= 1.03 |x|; normals have |m| <= 1.01: |nrm| <= 1.05, |J_a| <= 1.09 * 4096 (DH_FIT_MAX_EXTENT), and |r| <= 1.05 *
+// (|p| / p.z) * gate with gates up to 4096.  While |p| <= 2 p.z (a field of view below 120 degrees) one product stays below
+// 2^27; times 2^20, times 2^15 points (DH_FIT_MAX_POINTS): below 2^62 < 2^63.  The header says what holds outside that.
+#define DH_FIT_S 1048576.0
+#define DH_FIT_SUMS 29              // 21 A_ab (a <= b), 6 b_a, e and the count
+// Points and normals are staged in LDS (24 bytes a point) up to this many points: 24 KB, which leaves six workgroups to a CU's
+// 160 KB.  Larger models stream from global memory (L2-resident: every pass reads the same 24 n bytes).
+#define DH_FIT_LDS_POINTS 1024
+
+// One model of a fit call (device pointers of a dh_fit_model).
+struct FitModel {
+    const float *pts;         // [n][3]
+    const float *nrm;         // [n][3]
+    uint32_t n;
+    uint32_t pad;
+};
+
+struct FitArgs {
+    const uint16_t *frames;       // [n][h][w]
+    int n, w, h;
+    float k[9];                   // the one K of the batch (cams == NULL)
+    const DhCam *cams;            // nullable [n]: frame f sees cams[f].k
+    const FitModel *models;
+    const dh_render_instance *inst;
+    uint32_t n_inst;
+    uint32_t coarse, full, min_points;
+    double gate[2];
+    double lam1;                  // 1.0 + lambda (computed on the host: one f64 sum)
+    dh_render_instance *out;      // [n_inst]
+    dh_fit_record *rec;           // [n_inst]
+};
+
+hipError_t dh_launch_fit(const FitArgs &a, hipStream_t s);

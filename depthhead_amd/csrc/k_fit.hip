@@ -1,0 +1,268 @@
+// k_fit.hip -- posed point models fitted to depth frames: point-to-plane ICP with projective association (DESIGN.md section 18;
+// the rule is stated in include/depthhead_hip.h, section "fitting posed models to depth frames").  One kernel, k_fit: one
+// workgroup of 256 lanes per instance runs the whole schedule -- every pass, every step, the last pass -- inside one launch.
+//   pass   each lane strides over the model's points (staged in LDS up to DH_FIT_LDS_POINTS, else streamed), transforms,
+//          projects, gathers the depth pixel and adds the point's products to its int64 partial sums in registers; a coarse
+//          pass keeps only the 9 sums of the translation block, the last pass only e; the sums are reduced across the wave
+//          with 64-bit shuffles and one LDS atomic per wave and sum finishes them;
+//   step   after a barrier every lane solves the same system redundantly in f64 (deterministic, cheaper than a broadcast)
+//          and carries the pose (R, t: 12 doubles) in registers.
+// f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free: bit-identical
+// run to run and to tests/fit_ref.py.
+#include "dh_device.h"
+#include "dh_fit.h"
+
+#pragma clang fp contract(off)
+
+#define FIT_COARSE 0
+#define FIT_FULL 1
+#define FIT_LAST 2
+// the words of the reduction: A_ab at PAIR(a, b) (a <= b, row after row of the upper triangle), b_a, e, count
+#define FIT_PAIR(a, b) ((a) * 6 - (a) * ((a) - 1) / 2 + ((b) - (a)))
+#define FIT_B 21
+#define FIT_E 27
+#define FIT_COUNT 28
+static_assert(FIT_COUNT + 1 == DH_FIT_SUMS, "29 words");
+
+struct FitPose {
+    double R[9];
+    double t[3];
+};
+
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// One pass at `pose` with gate `gate`: the sums of MODE into s_sum (zeroed here; valid for every lane after the return).
+template <int MODE, bool STAGED>
+__device__ __forceinline__ void fit_pass(const FitArgs &a, const FitModel &m, const float *s_pts, const uint16_t *frame, const double K[9],
+                                         double scale, const FitPose &pose, double gate, unsigned long long *s_sum) {
+    constexpr int NJ = MODE == FIT_COARSE ? 3 : MODE == FIT_FULL ? 6 : 0;
+    constexpr int NA = NJ * (NJ + 1) / 2;
+    long long accA[NA > 0 ? NA : 1], accB[NJ > 0 ? NJ : 1];
+#pragma unroll
+    for (int k = 0; k < (NA > 0 ? NA : 1); ++k) accA[k] = 0;
+#pragma unroll
+    for (int k = 0; k < (NJ > 0 ? NJ : 1); ++k) accB[k] = 0;
+    long long e = 0, cnt = 0;
+    __syncthreads();                               // every lane has read the sums of the pass before
+    if (threadIdx.x < DH_FIT_SUMS) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    const double dw = (double)a.w, dh = (double)a.h;
+    for (uint32_t i = threadIdx.x; i < m.n; i += DH_FIT_THREADS) {
+        double v[3], nm[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            v[c] = (double)(STAGED ? s_pts[c * DH_FIT_LDS_POINTS + i] : m.pts[(size_t)i * 3 + c]);
+            nm[c] = (double)(STAGED ? s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] : m.nrm[(size_t)i * 3 + c]);
+        }
+        const double sv0 = v[0] * scale, sv1 = v[1] * scale, sv2 = v[2] * scale;
+        double p[3], n[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            p[j] = ((pose.R[3 * j] * sv0 + pose.R[3 * j + 1] * sv1) + pose.R[3 * j + 2] * sv2) + pose.t[j];
+            n[j] = (pose.R[3 * j] * nm[0] + pose.R[3 * j + 1] * nm[1]) + pose.R[3 * j + 2] * nm[2];
+        }
+        if (!(p[2] >= 1.0)) continue;
+        const double c = (n[0] * p[0] + n[1] * p[1]) + n[2] * p[2];
+        if (!(c < 0.0)) continue;
+        double r[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) r[j] = (p[0] * K[3 * j] + p[1] * K[3 * j + 1]) + p[2] * K[3 * j + 2];
+        const double x = r[0] / r[2], y = r[1] / r[2];
+        if (!(x >= 0.0 && x < dw && y >= 0.0 && y < dh)) continue;          // (NaN fails)
+        const int px = (int)x, py = (int)y;                                 // 0 <= px < w, 0 <= py < h
+        const uint32_t di = frame[(size_t)py * a.w + px];
+        if (di == 0) continue;
+        const double d = (double)di;
+        const double gap = d - p[2];
+        if (!((gap < 0.0 ? -gap : gap) <= gate)) continue;
+        const double res = c * (d / p[2] - 1.0);
+        if (MODE == FIT_LAST) e += (long long)((res * res) * DH_FIT_S);
+        else {
+            double J[6];
+            J[0] = n[0]; J[1] = n[1]; J[2] = n[2];
+            if (MODE == FIT_FULL) {
+                const double q0 = p[0] - pose.t[0], q1 = p[1] - pose.t[1], q2 = p[2] - pose.t[2];
+                J[3] = q1 * n[2] - q2 * n[1];
+                J[4] = q2 * n[0] - q0 * n[2];
+                J[5] = q0 * n[1] - q1 * n[0];
+            }
+            int k = 0;
+#pragma unroll
+            for (int ja = 0; ja < NJ; ++ja) {
+#pragma unroll
+                for (int jb = ja; jb < NJ; ++jb) accA[k++] += (long long)((J[ja] * J[jb]) * DH_FIT_S);
+                accB[ja] += (long long)((J[ja] * res) * DH_FIT_S);
+            }
+        }
+        cnt += 1;
+    }
+    const bool lead = (threadIdx.x & 63) == 0;
+    {
+        int k = 0;
+#pragma unroll
+        for (int ja = 0; ja < NJ; ++ja) {
+#pragma unroll
+            for (int jb = ja; jb < NJ; ++jb) {
+                const long long s = wave_sum(accA[k++]);
+                if (lead) atomicAdd(&s_sum[FIT_PAIR(ja, jb)], (unsigned long long)s);
+            }
+            const long long s = wave_sum(accB[ja]);
+            if (lead) atomicAdd(&s_sum[FIT_B + ja], (unsigned long long)s);
+        }
+    }
+    if (MODE == FIT_LAST) {
+        const long long s = wave_sum(e);
+        if (lead) atomicAdd(&s_sum[FIT_E], (unsigned long long)s);
+    }
+    {
+        const long long s = wave_sum(cnt);
+        if (lead) atomicAdd(&s_sum[FIT_COUNT], (unsigned long long)s);
+    }
+    __syncthreads();
+}
+
+// The step's system from the sums, damped, solved on its leading N x N block.  false: a pivot was not > 0.0.
+template <int N>
+__device__ __forceinline__ bool fit_solve(const unsigned long long *s_sum, double lam1, double x[6]) {
+    double A[N][N], b[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+        for (int j = i; j < N; ++j) {
+            const double v = (double)(long long)s_sum[FIT_PAIR(i, j)] / DH_FIT_S;
+            A[i][j] = v; A[j][i] = v;
+        }
+        A[i][i] = A[i][i] * lam1 + 1e-9;
+        b[i] = (double)(long long)s_sum[FIT_B + i] / DH_FIT_S;
+    }
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const double piv = A[k][k];
+        ok = ok && piv > 0.0;                      // (uniform over the workgroup: every lane holds the same numbers)
+#pragma unroll
+        for (int i = k + 1; i < N; ++i) {
+            const double f = A[i][k] / piv;
+#pragma unroll
+            for (int j = k + 1; j < N; ++j) A[i][j] = A[i][j] - f * A[k][j];
+            b[i] = b[i] - f * b[k];
+        }
+    }
+    if (!ok) return false;                         // (what was computed past a bad pivot is dropped)
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) {
+        double s = b[i];
+#pragma unroll
+        for (int j = i + 1; j < N; ++j) s = s - A[i][j] * x[j];
+        x[i] = s / A[i][i];
+    }
+    return true;
+}
+
+__device__ __forceinline__ bool fit_small(const double x[6], int n) {
+    bool small = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+        if (i < n) small = small && ((x[i] < 0.0 ? -x[i] : x[i]) < 1e-6);
+    return small;
+}
+
+// R = C R with C the Cayley rotation of a = w / 2 (the element order of the header)
+__device__ __forceinline__ void fit_cayley(double R[9], const double w[3]) {
+    const double a0 = w[0] / 2.0, a1 = w[1] / 2.0, a2 = w[2] / 2.0;
+    const double q = (a0 * a0 + a1 * a1) + a2 * a2;
+    const double s = 1.0 + q, d = 1.0 - q;
+    const double u0 = 2.0 * a0, u1 = 2.0 * a1, u2 = 2.0 * a2;
+    double C[9];
+    C[0] = (d + u0 * a0) / s;  C[1] = (u0 * a1 - u2) / s; C[2] = (u0 * a2 + u1) / s;
+    C[3] = (u1 * a0 + u2) / s; C[4] = (d + u1 * a1) / s;  C[5] = (u1 * a2 - u0) / s;
+    C[6] = (u2 * a0 - u1) / s; C[7] = (u2 * a1 + u0) / s; C[8] = (d + u2 * a2) / s;
+    double o[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = (C[3 * i] * R[j] + C[3 * i + 1] * R[3 + j]) + C[3 * i + 2] * R[6 + j];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = o[i];
+}
+
+template <bool STAGED>
+__device__ __forceinline__ void fit_run(const FitArgs &a, const dh_render_instance *in, const FitModel &m, const float *s_pts,
+                                        unsigned long long *s_sum) {
+    const uint32_t fr = in->frame;
+    const uint16_t *frame = a.frames + (size_t)fr * a.h * a.w;
+    double K[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) K[q] = (double)(a.cams ? a.cams[fr].k[q] : a.k[q]);
+    FitPose pose;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) pose.R[q] = (double)in->R[q];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) pose.t[q] = (double)in->t[q];
+    const double scale = (double)in->scale;
+    uint32_t steps = 0, status = DH_FIT_OK;
+    bool stop = false;
+    for (uint32_t it = 0; it < a.coarse; ++it) {
+        fit_pass<FIT_COARSE, STAGED>(a, m, s_pts, frame, K, scale, pose, a.gate[0], s_sum);
+        if ((uint32_t)s_sum[FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; stop = true; break; }
+        double x[6] = {0, 0, 0, 0, 0, 0};
+        if (!fit_solve<3>(s_sum, a.lam1, x)) { status = DH_FIT_SINGULAR; stop = true; break; }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
+        ++steps;
+        if (fit_small(x, 3)) break;
+    }
+    for (uint32_t it = 0; it < a.full && !stop; ++it) {
+        fit_pass<FIT_FULL, STAGED>(a, m, s_pts, frame, K, scale, pose, a.gate[1], s_sum);
+        if ((uint32_t)s_sum[FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; break; }
+        double x[6];
+        if (!fit_solve<6>(s_sum, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
+        fit_cayley(pose.R, x + 3);
+        ++steps;
+        if (fit_small(x, 6)) break;
+    }
+    fit_pass<FIT_LAST, STAGED>(a, m, s_pts, frame, K, scale, pose, a.gate[1], s_sum);
+    if (threadIdx.x == 0) {
+        dh_render_instance o = *in;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) o.R[q] = (float)pose.R[q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) o.t[q] = (float)pose.t[q];
+        a.out[blockIdx.x] = o;
+        dh_fit_record rec;
+        rec.points = (uint32_t)s_sum[FIT_COUNT];
+        rec.steps = steps;
+        rec.status = status;
+        rec.reserved = 0;
+        rec.sum_r2_fixed = (int64_t)s_sum[FIT_E];
+        a.rec[blockIdx.x] = rec;
+    }
+}
+
+__global__ __launch_bounds__(DH_FIT_THREADS) void k_fit(const FitArgs a) {
+    __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];
+    __shared__ unsigned long long s_sum[32];
+    const dh_render_instance *in = a.inst + blockIdx.x;
+    const FitModel m = a.models[in->mesh];
+    if (m.n <= DH_FIT_LDS_POINTS) {
+        for (uint32_t k = threadIdx.x; k < m.n * 3; k += DH_FIT_THREADS) {
+            const uint32_t i = k / 3, c = k - i * 3;
+            s_pts[c * DH_FIT_LDS_POINTS + i] = m.pts[k];
+            s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] = m.nrm[k];
+        }
+        fit_run<true>(a, in, m, s_pts, s_sum);      // (the first pass's barriers order the staging before its reads)
+    } else fit_run<false>(a, in, m, s_pts, s_sum);
+}
+
+// ------------------------------------------------------------------ launcher
+hipError_t dh_launch_fit(const FitArgs &a, hipStream_t s) {
+    if (a.n_inst == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fit, dim3(a.n_inst), dim3(DH_FIT_THREADS), 0, s, a);
+    return hipGetLastError();
+}

@@ -1,0 +1,146 @@
+"""Posed head models fitted to depth frames on the GPU: point-to-plane ICP with projective association,
+started from a rough pose per head (the forest's), so that position becomes accurate to millimetres and rotation to a few
+degrees.  All arithmetic of the fit runs in libdepthhead_hip.so (k_fit.hip); the rule is stated in include/depthhead_hip.h."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import FIT_RECORD_DTYPE, RENDER_INSTANCE_DTYPE, check, vp
+from .render import euler_to_matrix
+
+FIT_OK, FIT_FEW_POINTS, FIT_SINGULAR = 0, 1, 2      # dh_fit_record.status
+
+
+def vertex_normals(verts, tris) -> np.ndarray:
+    """Unit vertex normals [nv, 3] f32 of a triangle mesh: the face cross products (v_b - v_a) x (v_c - v_a) added to each of the
+    face's three vertices in triangle order, in f64, normalised and rounded to f32 once.  They point outward when the winding
+    is counter-clockwise seen from outside (synth.head_mesh's is); nothing is flipped by guessing.  A vertex no triangle with
+    area touches gets (0, 0, 0), which dh_fit_model_create refuses."""
+    v = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    t = np.asarray(tris, dtype=np.int64).reshape(-1, 3)
+    n = np.zeros_like(v)
+    for a, b, c in t:
+        f = np.cross(v[b] - v[a], v[c] - v[a])
+        n[a] += f
+        n[b] += f
+        n[c] += f
+    ln = np.sqrt((n * n).sum(axis=1))
+    return (n / np.where(ln > 0.0, ln, 1.0)[:, None]).astype(np.float32)
+
+
+def matrix_to_euler(R) -> np.ndarray:
+    """The three pose angles in DEGREES of a rotation matrix: the inverse of render.euler_to_matrix for |rot[1]| < 90."""
+    m = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    return np.degrees(np.array([np.arctan2(m[0, 1], m[0, 0]), np.arcsin(np.clip(m[0, 2], -1.0, 1.0)), np.arctan2(-m[1, 2], m[2, 2])]))
+
+
+def rms(record) -> float:
+    """Root mean square point-to-plane residual (mm) of a dh_fit_record; nan when no point was used."""
+    n = int(record["points"])
+    return float(np.sqrt(int(record["sum_r2_fixed"]) / 1048576.0 / n)) if n else float("nan")
+
+
+def instances_from_poses(poses_or_heads, scale: float = 1.0, frames=None, model: int = 0) -> np.ndarray:
+    """Start instances from dh_pose (POSE_DTYPE) or dh_head (HEAD_DTYPE) records: t = mid_point, R = euler_to_matrix of the
+    record's rotation (radians in the record).  Record i belongs to frame i unless `frames` names each one's."""
+    rec = np.asarray(poses_or_heads)
+    if rec.dtype.names and "pose" in rec.dtype.names:
+        rec = rec["pose"]
+    rec = rec.reshape(-1)
+    out = np.zeros(len(rec), dtype=RENDER_INSTANCE_DTYPE)
+    for i, p in enumerate(rec):
+        out[i] = (i if frames is None else int(frames[i]), model, euler_to_matrix(np.degrees(p["rotation"])).reshape(9),
+                  p["mid_point"], scale, 0)
+    return out
+
+
+class Model(_lib._Handle):
+    """One dh_fit_model: points [n, 3] (mm) and unit normals [n, 3] on `device`."""
+    _handles = (("_h", "dh_fit_model_destroy"),)
+
+    def __init__(self, points, normals, device: int = 0):
+        self._lib = _lib.load()
+        self.points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        self.normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if self.points.shape != self.normals.shape:
+            raise ValueError("as many normals as points are expected")
+        self.device = int(device)
+        self._h = C.c_void_p()
+        check(self._lib.dh_fit_model_create(vp(self.points), vp(self.normals), C.c_uint32(len(self.points)), self.device, C.byref(self._h)))
+
+    @classmethod
+    def from_mesh(cls, verts, tris, device: int = 0) -> "Model":
+        return cls(verts, vertex_normals(verts, tris), device=device)
+
+    def info(self):
+        """(n, radius = the largest |v|) as the library holds them."""
+        n, radius = C.c_uint32(), C.c_double()
+        check(self._lib.dh_fit_model_info(self._h, C.byref(n), C.byref(radius)))
+        return n.value, radius.value
+
+
+def fit_params(coarse_iterations=None, iterations=None, gate=None, lam=None, min_points=None) -> "_lib.FitParams":
+    """dh_fit_params_default with the given fields replaced."""
+    p = _lib.FitParams()
+    check(_lib.load().dh_fit_params_default(C.byref(p)))
+    if coarse_iterations is not None:
+        p.coarse_iterations = int(coarse_iterations)
+    if iterations is not None:
+        p.iterations = int(iterations)
+    if gate is not None:
+        p.gate[0], p.gate[1] = float(gate[0]), float(gate[1])
+    if lam is not None:
+        p.lam = float(lam)
+    if min_points is not None:
+        p.min_points = int(min_points)
+    return p
+
+
+class Fitter(_lib._Handle):
+    """One dh_fitter on `device`.  Not thread-safe."""
+    _handles = (("_h", "dh_fitter_destroy"),)
+
+    def __init__(self, device: int = 0):
+        self._lib = _lib.load()
+        self.device = int(device)
+        self._h = C.c_void_p()
+        check(self._lib.dh_fitter_create(self.device, C.byref(self._h)))
+
+    def fit(self, frames, models, instances, K_or_cameras, params=None, device_out: bool = False, stream=None):
+        """Refine `instances` (a RENDER_INSTANCE_DTYPE array of rough poses) of `models` against `frames`: [n, h, w] u16 as a
+        numpy array, or a torch tensor on the device with device_out=True.  Through one K ([3, 3] or an `IntrinsicMatrix`) or a
+        `tracking.Cameras` table of exactly n cameras.  Returns (instances, records) -- RENDER_INSTANCE_DTYPE and
+        FIT_RECORD_DTYPE arrays, or with device_out=True two uint8 torch tensors on the device holding them, ordered on `stream`
+        (default the current torch stream)."""
+        inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
+        models = list(models)
+        handles = (C.c_void_p * max(len(models), 1))(*[m._h.value for m in models])
+        n, h, w = (int(v) for v in frames.shape)
+        cams = getattr(K_or_cameras, "_h", None)
+        if cams is None:
+            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
+            kind, karg = "", vp(K)
+        else:
+            kind, karg = "_cameras", cams
+        prm = C.byref(params) if params is not None else None
+        ni = len(inst)
+        if not device_out:
+            fr = np.ascontiguousarray(frames, dtype=np.uint16)
+            out, rec = np.zeros(ni, RENDER_INSTANCE_DTYPE), np.zeros(ni, FIT_RECORD_DTYPE)
+            check(getattr(self._lib, "dh_fit_depth" + kind)(self._h, vp(fr), n, w, h, karg, handles, C.c_uint32(len(models)),
+                                                             vp(inst) if ni else None, C.c_uint32(ni), prm, vp(out), vp(rec)))
+            return out, rec
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
+            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
+        out = torch.empty(max(ni, 1) * RENDER_INSTANCE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        rec = torch.empty(max(ni, 1) * FIT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        check(getattr(self._lib, "dh_fit_depth" + kind + "_device")(self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, handles,
+                                                                      C.c_uint32(len(models)), vp(inst) if ni else None, C.c_uint32(ni), prm,
+                                                                      C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
+        return out[:ni * RENDER_INSTANCE_DTYPE.itemsize], rec[:ni * FIT_RECORD_DTYPE.itemsize]

@@ -577,6 +577,107 @@ int dh_render_depth_cameras_device(dh_renderer *r, const dh_mesh *const *meshes,
 int dh_renderer_set_profiling(dh_renderer *r, int on);
 int dh_renderer_timing(dh_renderer *r, float ms[4]);
 
+/* ---- fitting posed models to depth frames ----
+ * The step after a discriminative detector: the posed head model is fitted to the depth pixels (point-to-plane ICP with
+ * projective association) from a rough pose, the forest's.  Not in the reference: PARITY UNPINNED, the definition below is this
+ * library's.  The inverse of dh_render_depth*: frames and rough instances in, refined instances and one record each out.
+ * A model is n points v_i (mm) with unit normals m_i.  An instance is a dh_render_instance: `mesh` is the model index, R, t and
+ * scale widen to f64, `flags` is ignored.  Everything below is f64, evaluated left to right, every product, sum and quotient
+ * rounded on its own (no contraction), with + - * /, compares and casts only: no library function runs on the device.
+ * ONE PASS at pose (R, t) with gate g, for every point i of the model:
+ *     sv = v * scale;  p[j] = ((R[j][0] * sv0 + R[j][1] * sv1) + R[j][2] * sv2) + t[j];  nrm[j] = (R[j][0] * m0 + R[j][1] * m1) + R[j][2] * m2
+ *   skipped unless p.z >= 1.0;  c = (nrm0 * p0 + nrm1 * p1) + nrm2 * p2, skipped unless c < 0.0 (the point faces the camera);
+ *   projected by the frame's K widened to f64 as space_to_img_coord does: r[j] = (p0 * K[j][0] + p1 * K[j][1]) + p2 * K[j][2],
+ *   x = r0 / r2, y = r1 / r2, skipped unless 0.0 <= x < w and 0.0 <= y < h (NaN fails); the pixel is ((int)x, (int)y), the
+ *   renderer's pixel-centre convention;  d = (double)depth there, skipped when d == 0 or unless |d - p.z| <= g;
+ *     residual  r = c * (d / p.z - 1.0)      (the measured point on the model point's own ray, projected on the normal: no K^-1)
+ *     q = p - t;  J = (nrm0, nrm1, nrm2, q1 * nrm2 - q2 * nrm1, q2 * nrm0 - q0 * nrm2, q0 * nrm1 - q1 * nrm0)
+ *   and with S = 2^20 the int64 sums (truncating casts, so their order is free):  A_ab += (int64)((J_a * J_b) * S) for a <= b (21),
+ *   b_a += (int64)((J_a * r) * S) (6),  e += (int64)((r * r) * S),  count += 1.  Magnitudes: R is held to |R R^T - I| <=
+ *   DH_FIT_R_TOLERANCE per element, so |R x| <= 1.03 |x|; with |m| <= 1.01 that gives |nrm| <= 1.05, |q| <= 1.03 * 4096 and
+ *   |J_a| <= 1.09 * 4096, and |r| <= 1.05 * (|p| / p.z) * g.  For a camera that sees no point further than 60 degrees off its axis
+ *   (|p| <= 2 p.z: any field of view below 120 degrees) every product stays below 2^27; times 2^20, times 2^15 points: below
+ *   2^62.  A K that lets points through at a wider angle is not refused, but there the sums can leave int64 and the result is
+ *   unspecified (arithmetic only: nothing faults), and no longer pinned to the restatement, whose Python ints do not wrap.
+ * ONE STEP from the sums of a pass: count < min_points ends the fit with DH_FIT_FEW_POINTS.  A_ab = (double)sum / S (A symmetric),
+ *   b_a alike; A_aa = A_aa * (1.0 + lambda) + 1e-9; A x = b is solved on the leading n x n block (n = 3, the translation, in a coarse
+ *   step, else 6) by Gaussian elimination without pivoting in index order:  for k < n: piv = A[k][k]; for i in k+1 .. n-1:
+ *   f = A[i][k] / piv; A[i][j] = A[i][j] - f * A[k][j] for j in k+1 .. n-1; b[i] = b[i] - f * b[k];  then for i = n-1 .. 0:
+ *   s = b[i]; s = s - A[i][j] * x[j] for j in i+1 .. n-1; x[i] = s / A[i][i].  A pivot that is not > 0.0 (NaN included) ends the fit
+ *   with DH_FIT_SINGULAR and this step changes nothing.  Else t[j] = t[j] + x[j], and in a full step with a = x[3..5] / 2.0,
+ *   q = (a0 * a0 + a1 * a1) + a2 * a2, s = 1.0 + q, d = 1.0 - q, u_i = 2.0 * a_i the Cayley rotation (rational: no trigonometry)
+ *     C00 = (d + u0 * a0) / s   C01 = (u0 * a1 - u2) / s   C02 = (u0 * a2 + u1) / s
+ *     C10 = (u1 * a0 + u2) / s   C11 = (d + u1 * a1) / s   C12 = (u1 * a2 - u0) / s
+ *     C20 = (u2 * a0 - u1) / s   C21 = (u2 * a1 + u0) / s   C22 = (d + u2 * a2) / s
+ *   turns the model about its own origin:  R[i][j] = (C[i][0] * R[0][j] + C[i][1] * R[1][j]) + C[i][2] * R[2][j].
+ * SCHEDULE: coarse_iterations coarse steps at gate[0], then `iterations` full steps at gate[1].  A step after which every
+ *   |x_a| < 1e-6 ends its phase early (a coarse one goes on to the full steps, a full one ends the fit).  One last pass at gate[1]
+ *   at the final pose -- also after DH_FIT_FEW_POINTS and DH_FIT_SINGULAR -- gives the record's points (count) and sum_r2_fixed (e);
+ *   steps counts the steps that were applied.  The output instance is the input's with R and t rounded to f32 once (frame, mesh,
+ *   scale and flags copied through): it can be passed to dh_render_depth* as it is.  Bit-identical run to run and to tests/fit_ref.py.
+ * A dh_fit_model is immutable and lives on one device; a dh_fitter owns the call's tables and (for the host calls) the frame and
+ * output staging of one device, taken at the first fit and growing on demand, and is NOT thread-safe.  models, instances, K and
+ * params are host memory in every call; params NULL selects dh_fit_params_default.  DH_EINVAL before anything is launched, with
+ * the outputs untouched: NULL fitter / frames / out / records; n < 1 or above 65535; w or h outside 1 .. DH_RENDER_MAX_SIZE; NULL K,
+ * or a NULL camera table, one of another device or one whose length is not n; instances or models NULL with n_instances > 0; an
+ * instance naming a frame >= n or a model >= n_models; a NULL model or one of another device; a non-finite R, t or scale; an
+ * R with an element of R R^T (in f64) further than DH_FIT_R_TOLERANCE from the identity's (what the magnitude bound above rests
+ * on; a rotation rounded to f32 is within 1e-6); |scale| * (the model's largest |v|) above DH_FIT_MAX_EXTENT; coarse_iterations + iterations above 64; a gate
+ * outside (0, 4096] (NaN included); lambda not >= 0 or not finite; min_points below 6; a reserved word that is not 0.
+ * n_instances = 0 is no error and writes nothing.  The host calls are synchronous.  The _device calls take device frames and
+ * device outputs, enqueue on `stream` (NULL = default stream) and never wait on the host for anything the device computes --
+ * every pass and step of every instance runs inside one kernel launch -- and are ordered after whatever was enqueued on that stream before (a _device
+ * render or prediction) and before whatever follows. */
+#define DH_FIT_OK 0u
+#define DH_FIT_FEW_POINTS 1u       /* a pass associated fewer than min_points points */
+#define DH_FIT_SINGULAR 2u         /* a pivot of the normal equations was not > 0 */
+#define DH_FIT_MAX_POINTS 32768u   /* points of a model */
+#define DH_FIT_MAX_EXTENT 4096.0   /* mm: |scale| * largest |v| of an instance */
+#define DH_FIT_R_TOLERANCE 0.02    /* largest |(R R^T - I)[i][j]| of an instance */
+typedef struct dh_fit_params {
+    uint32_t coarse_iterations;   /* 6: translation-only steps at gate[0] */
+    uint32_t iterations;          /* 14: full steps at gate[1]; the two sum to at most 64 */
+    double   gate[2];             /* 120, 25 (mm): each in (0, 4096] */
+    double   lambda;              /* 1e-3: relative damping of the diagonal, >= 0 */
+    uint32_t min_points;          /* 16, at least 6 */
+    uint32_t reserved0;           /* 0 */
+    uint64_t reserved[2];         /* 0 */
+} dh_fit_params;       /* 56 bytes */
+typedef struct dh_fit_record {
+    uint32_t points;              /* points associated by the last pass */
+    uint32_t steps;               /* steps applied */
+    uint32_t status;              /* DH_FIT_* */
+    uint32_t reserved;            /* 0 */
+    int64_t  sum_r2_fixed;        /* e of the last pass: sum of (int64)(r * r * 2^20); rms = sqrt(e / 2^20 / points) */
+} dh_fit_record;       /* 24 bytes */
+typedef struct dh_fit_model dh_fit_model;
+typedef struct dh_fitter dh_fitter;
+/* Copies n points and their normals (x, y, z triples) to `device`.  DH_EINVAL: NULL arguments, n = 0 or above DH_FIT_MAX_POINTS,
+ * a non-finite value, a normal whose squared length (in f64) lies outside [0.98, 1.02]. */
+int dh_fit_model_create(const float *points, const float *normals, uint32_t n, int device, dh_fit_model **out);
+int dh_fit_model_destroy(dh_fit_model *m);
+/* each pointer nullable; radius = the largest |v| (f64) */
+int dh_fit_model_info(const dh_fit_model *m, uint32_t *n, double *radius);
+int dh_fit_params_default(dh_fit_params *p);
+int dh_fitter_create(int device, dh_fitter **out);
+int dh_fitter_destroy(dh_fitter *f);
+/* frames [n][h][w] u16; out [n_instances] and records [n_instances] */
+int dh_fit_depth(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models,
+                 uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params,
+                 dh_render_instance *out, dh_fit_record *records);
+/* frame i is seen through camera i of the table, which must hold exactly n cameras */
+int dh_fit_depth_cameras(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                         const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances,
+                         uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records);
+int dh_fit_depth_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9],
+                        const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances,
+                        uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records,
+                        void *stream);
+int dh_fit_depth_cameras_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances,
+                                uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records,
+                                void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
