@@ -23,7 +23,8 @@ INST, REC = _lib.RENDER_INSTANCE_DTYPE, _lib.FIT_RECORD_DTYPE
 @functools.lru_cache(maxsize=None)
 def host_models():
     """0: head_mesh(2), 162 points.  1: one point.  2: 257 points of head_mesh(3).  3: head_mesh(4), 2562 points, above the
-    LDS staging budget of 1024.  4: a plane of 81 points."""
+    LDS staging budget of 1024.  4: a plane of 81 points.  5 - 9: the first 255, 256, 1023, 1024 and 1025 points of head_mesh(4): either side of
+    the workgroup's 256 lanes and of the staging budget."""
     v2, _, n2 = fs.head(2)
     v3, _, n3 = fs.head(3)
     v4, _, n4 = fs.head(4)
@@ -32,7 +33,8 @@ def host_models():
     plane = np.stack([x.ravel(), y.ravel(), np.zeros(81)], axis=1).astype(np.float32)
     pn = np.tile(np.array([0, 0, -1], np.float32), (81, 1))
     front = int(np.argmin(v2[:, 2]))                  # a point that faces the camera at the identity pose
-    return ((v2, n2), (v2[front:front + 1].copy(), n2[front:front + 1].copy()), (v3[:257].copy(), n3[:257].copy()), (v4, n4), (plane, pn))
+    slices = tuple((v4[:k].copy(), n4[:k].copy()) for k in (255, 256, 1023, 1024, 1025))
+    return ((v2, n2), (v2[front:front + 1].copy(), n2[front:front + 1].copy()), (v3[:257].copy(), n3[:257].copy()), (v4, n4), (plane, pn)) + slices
 
 
 @pytest.fixture(scope="module")
@@ -168,10 +170,11 @@ def test_two_runs_are_byte_identical(gpu):
     same(a[1], five_frames_expected()[1], "record")
 
 
-@pytest.mark.parametrize("model,points", [(1, 1), (2, 257), (3, 2562)])
+@pytest.mark.parametrize("model,points", [(1, 1), (2, 257), (3, 2562), (5, 255), (6, 256), (7, 1023), (8, 1024), (9, 1025)])
 def test_model_sizes(gpu, model, points):
-    """One point (never enough: FEW_POINTS, but the last pass still counts it), 257 points (one more than the workgroup) and 2562
-    (streamed from global memory: above DH_FIT_LDS_POINTS)."""
+    """One point (never enough: FEW_POINTS, but the last pass still counts it), 255, 256 and 257 points (the workgroup's 256-lane
+    stride), 1023, 1024 and 1025 (the last model staged in LDS, m.n <= DH_FIT_LDS_POINTS, and the first streamed from global
+    memory) and 2562 (far above it)."""
     ms, _ = gpu
     assert ms[model].info()[0] == points == len(host_models()[model][0])
     w, h = 160, 120
