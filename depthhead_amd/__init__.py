@@ -3,6 +3,6 @@
 from .forest import Forest, NODE_DTYPE  # noqa: F401
 from .synth import ModelParams  # noqa: F401
 from .render import Mesh, Renderer, euler_to_matrix  # noqa: F401
-from .fit import Fitter, Model  # noqa: F401
+from .fit import Fitter, FitTracker, Model  # noqa: F401
 
-__all__ = ["Forest", "NODE_DTYPE", "ModelParams", "Mesh", "Renderer", "euler_to_matrix", "Fitter", "Model"]
+__all__ = ["Forest", "NODE_DTYPE", "ModelParams", "Mesh", "Renderer", "euler_to_matrix", "Fitter", "Model", "FitTracker"]

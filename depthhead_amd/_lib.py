@@ -76,6 +76,23 @@ class FitParams(C.Structure):
                 ("min_points", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 2)]
 
 
+# dh_fit_track_state / dh_fit_track_record: a fit tracker's per-camera state and what one step reports for a camera
+FIT_TRACK_STATE_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("t_prev", "<f4", (3,)), ("tracked", "<u4"),
+                                  ("have_prev", "<u4"), ("age", "<u4"), ("lost", "<u4")], align=True)
+assert FIT_TRACK_STATE_DTYPE.itemsize == 76
+FIT_TRACK_RECORD_DTYPE = np.dtype([("instance", RENDER_INSTANCE_DTYPE), ("fit", FIT_RECORD_DTYPE), ("status", "<u4"), ("age", "<u4"),
+                                   ("lost", "<u4"), ("reserved", "<u4")], align=True)
+assert FIT_TRACK_RECORD_DTYPE.itemsize == 104 and FIT_TRACK_RECORD_DTYPE.fields["fit"][1] == 64
+FIT_TRACK_ANGLES = 120     # DH_FIT_TRACK_ANGLES
+
+
+class FitTrackParams(C.Structure):
+    """dh_fit_track_params"""
+    _fields_ = [("iterations_tracked", C.c_uint32), ("keep_points", C.c_uint32), ("rms_max", C.c_double), ("max_jump", C.c_double),
+                ("conf_num", C.c_uint32), ("conf_den", C.c_uint32), ("min_windows", C.c_uint32), ("max_coast", C.c_uint32),
+                ("reserved", C.c_uint64 * 2)]
+
+
 class RigTrackParams(C.Structure):
     """dh_rig_track_params"""
     _fields_ = [("max_heads", C.c_int32), ("radius", C.c_uint32), ("fuse_gate", C.c_uint32), ("gate", C.c_uint32),
@@ -131,6 +148,9 @@ EXPORTS = [
     "dh_render_depth", "dh_render_depth_cameras", "dh_render_depth_device", "dh_render_depth_cameras_device",
     "dh_fit_model_create", "dh_fit_model_destroy", "dh_fit_model_info", "dh_fit_params_default", "dh_fitter_create",
     "dh_fitter_destroy", "dh_fit_depth", "dh_fit_depth_cameras", "dh_fit_depth_device", "dh_fit_depth_cameras_device",
+    "dh_fit_track_params_default", "dh_fit_tracker_angles", "dh_fit_tracker_create", "dh_fit_tracker_destroy", "dh_fit_tracker_reset",
+    "dh_fit_tracker_state", "dh_fit_tracker_step_poses", "dh_fit_tracker_step_poses_device", "dh_fit_tracker_step",
+    "dh_fit_tracker_step_device",
 ]
 
 

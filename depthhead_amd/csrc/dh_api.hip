@@ -2808,6 +2808,22 @@ static int fitter_init(dh_fitter *f) {
     return DH_OK;
 }
 
+// The refusals of a call's dh_fit_params (NULL: the defaults); *out is what the call runs with.
+static int fit_params_check(const dh_fit_params *in, dh_fit_params *out, const char *who) {
+    dh_fit_params prm;
+    (void)fit_params_default_(&prm);
+    if (in) prm = *in;
+    if ((uint64_t)prm.coarse_iterations + prm.iterations > 64)
+        return fail(DH_EINVAL, "%s: coarse_iterations %u + iterations %u above 64", who, prm.coarse_iterations, prm.iterations);
+    for (int g = 0; g < 2; ++g)
+        if (!(prm.gate[g] > 0.0 && prm.gate[g] <= 4096.0)) return fail(DH_EINVAL, "%s: gate[%d] = %g outside (0, 4096]", who, g, prm.gate[g]);
+    if (!(prm.lambda >= 0.0) || !std::isfinite(prm.lambda)) return fail(DH_EINVAL, "%s: lambda %g, expected a finite value >= 0", who, prm.lambda);
+    if (prm.min_points < 6) return fail(DH_EINVAL, "%s: min_points %u below 6", who, prm.min_points);
+    if (prm.reserved0 || prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    *out = prm;
+    return DH_OK;
+}
+
 // One fit call.  dev: frames / out / records are device pointers and `stream` the caller's; else host pointers.
 struct FitReq {
     const uint16_t *frames; int n, w, h;
@@ -2831,15 +2847,7 @@ static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, 
         if (q.cams->n != q.n) return fail(DH_EINVAL, "%s: the camera table holds %d cameras, the batch %d frames", who, q.cams->n, q.n);
     } else if (!q.K) return fail(DH_EINVAL, "%s: NULL K", who);
     dh_fit_params prm;
-    (void)fit_params_default_(&prm);
-    if (q.prm) prm = *q.prm;
-    if ((uint64_t)prm.coarse_iterations + prm.iterations > 64)
-        return fail(DH_EINVAL, "%s: coarse_iterations %u + iterations %u above 64", who, prm.coarse_iterations, prm.iterations);
-    for (int g = 0; g < 2; ++g)
-        if (!(prm.gate[g] > 0.0 && prm.gate[g] <= 4096.0)) return fail(DH_EINVAL, "%s: gate[%d] = %g outside (0, 4096]", who, g, prm.gate[g]);
-    if (!(prm.lambda >= 0.0) || !std::isfinite(prm.lambda)) return fail(DH_EINVAL, "%s: lambda %g, expected a finite value >= 0", who, prm.lambda);
-    if (prm.min_points < 6) return fail(DH_EINVAL, "%s: min_points %u below 6", who, prm.min_points);
-    if (prm.reserved0 || prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    TRY(fit_params_check(q.prm, &prm, who));
     if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
     if (q.n_inst && !q.models) return fail(DH_EINVAL, "%s: NULL models", who);
     if (q.n_inst > 0x7fffffffu) return fail(DH_EINVAL, "%s: too many instances", who);
@@ -2933,6 +2941,215 @@ static int fit_depth_device_(dh_fitter *f, const uint16_t *frames, int n, int w,
 static int fit_depth_cameras_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models,
                                      const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream) {
     return fit_run(f, FitReq{frames, n, w, h, nullptr, c, true, models, n_models, instances, n_instances, params, out, records}, true, (hipStream_t)stream, "dh_fit_depth_cameras_device");
+}
+
+// ------------------------------------------------------------------ carrying fitted poses across steps
+// The angle table of the header: computed once, by libm, and the only cosines and sines of the feature.
+struct FitTrackAngles {
+    double v[DH_FIT_TRACK_ANGLES][2];
+    FitTrackAngles() {
+        for (int i = 0; i < DH_FIT_TRACK_ANGLES; ++i) {
+            const double a = (double)(i - 60) / 60.0 * 3.14159;
+            v[i][0] = cos(a); v[i][1] = sin(a);
+        }
+    }
+};
+static const FitTrackAngles &fit_track_angles() {
+    static const FitTrackAngles tab;
+    return tab;
+}
+static int fit_tracker_angles_(double out[DH_FIT_TRACK_ANGLES][2]) {
+    if (!out) return fail(DH_EINVAL, "dh_fit_tracker_angles: NULL argument");
+    memcpy(out, fit_track_angles().v, sizeof fit_track_angles().v);
+    return DH_OK;
+}
+static int fit_track_params_default_(dh_fit_track_params *p) {
+    if (!p) return fail(DH_EINVAL, "dh_fit_track_params_default: NULL argument");
+    memset(p, 0, sizeof *p);
+    p->iterations_tracked = 6; p->keep_points = 30;
+    p->rms_max = 5.0; p->max_jump = 150.0;
+    p->conf_num = 1; p->conf_den = 50;
+    p->min_windows = 1; p->max_coast = 3;
+    return DH_OK;
+}
+
+// Every device buffer of a step is sized by the camera table and allocated at creation; the host forms stage through the
+// buffers of the second group on the tracker's own stream (the frames come with the first host step, for its frame size).
+struct dh_fit_tracker : TrackerCore {
+    const dh_fit_model *model = nullptr;
+    float scale = 1.0f;
+    uint32_t flags = 0;
+    dh_fit_track_params prm{};
+    int64_t rms_lim = 0;
+    double jump2 = 0.0;
+    Buf<dh_fit_track_state> state;       // [n]
+    Buf<double> angles;                  // [120][2]
+    Buf<FitModel> models;                // [1]
+    Buf<dh_render_instance> start, fit_out;
+    Buf<dh_fit_record> fit_rec;
+    Buf<uint32_t> sched, seed;
+    hipStream_t s = nullptr;             // host forms
+    Buf<uint16_t> frames;
+    Buf<dh_pose> poses;
+    Buf<dh_support> support;
+    Buf<dh_fit_track_record> records;
+    int clear(size_t c0, size_t m, hipStream_t st) {
+        HIP_TRY(hipMemsetAsync(state.get() + c0, 0, m * sizeof(dh_fit_track_state), st));
+        return DH_OK;
+    }
+    ~dh_fit_tracker() { if (s) (void)hipStreamDestroy(s); }
+};
+static int fit_tracker_create_(const dh_cameras *c, const dh_fit_model *m, float scale, uint32_t flags, const dh_fit_track_params *params,
+                               dh_fit_tracker **out) {
+    const char *who = "dh_fit_tracker_create";
+    if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
+    *out = nullptr;
+    dh_fit_track_params prm;
+    (void)fit_track_params_default_(&prm);
+    if (params) prm = *params;
+    if (flags & ~DH_FIT_TRACK_MOTION) return fail(DH_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    if (!std::isfinite(scale)) return fail(DH_EINVAL, "%s: scale is not finite", who);
+    if (prm.iterations_tracked > 64) return fail(DH_EINVAL, "%s: iterations_tracked %u above 64", who, prm.iterations_tracked);
+    if (!(prm.rms_max > 0.0 && prm.rms_max <= 4096.0)) return fail(DH_EINVAL, "%s: rms_max = %g outside (0, 4096]", who, prm.rms_max);
+    if (!(prm.max_jump > 0.0 && prm.max_jump <= 4096.0)) return fail(DH_EINVAL, "%s: max_jump = %g outside (0, 4096]", who, prm.max_jump);
+    if (prm.conf_den == 0 || prm.conf_num > prm.conf_den)
+        return fail(DH_EINVAL, "%s: confidence %u / %u, expected a fraction in [0, 1]", who, prm.conf_num, prm.conf_den);
+    if (prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    if (!c) return fail(DH_EINVAL, "%s: NULL camera table", who);
+    if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
+    if (m->device != c->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the camera table on %d", who, m->device, c->device);
+    const double extent = fabs((double)scale) * m->radius;
+    if (extent > DH_FIT_MAX_EXTENT) return fail(DH_EINVAL, "%s: the model spans %g mm from its origin (limit %g)", who, extent, DH_FIT_MAX_EXTENT);
+    return create_tracker(c, out, [&](dh_fit_tracker &t, size_t n) -> int {
+        t.model = m; t.scale = scale; t.flags = flags; t.prm = prm;
+        t.rms_lim = (int64_t)(prm.rms_max * prm.rms_max * 1048576.0);
+        t.jump2 = prm.max_jump * prm.max_jump;
+        TRY(t.state.alloc(n));
+        TRY(t.angles.alloc(DH_FIT_TRACK_ANGLES * 2));
+        TRY(t.models.alloc(1));
+        TRY(t.start.alloc(n)); TRY(t.fit_out.alloc(n)); TRY(t.fit_rec.alloc(n));
+        TRY(t.sched.alloc(n * 2)); TRY(t.seed.alloc(n));
+        TRY(t.poses.alloc(n)); TRY(t.support.alloc(n)); TRY(t.records.alloc(n));
+        const FitModel fm{m->pts.get(), m->nrm.get(), m->n, 0};
+        HIP_TRY(hipMemcpy(t.models.get(), &fm, sizeof fm, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(t.angles.get(), fit_track_angles().v, sizeof fit_track_angles().v, hipMemcpyHostToDevice));
+        return hip_step(hipStreamCreateWithFlags(&t.s, hipStreamNonBlocking), "hipStreamCreate");
+    });
+}
+static int fit_tracker_destroy_(dh_fit_tracker *t) {
+    if (t) {
+        DeviceGuard guard(t->cams->device);
+        (void)hipDeviceSynchronize();
+    }
+    return destroy_tracker(t);
+}
+static int fit_tracker_reset_(dh_fit_tracker *t, int camera, void *stream) { return reset_tracker(t, camera, stream, "dh_fit_tracker_reset"); }
+static int fit_tracker_state_(dh_fit_tracker *t, dh_fit_track_state *states) {
+    if (t && !states) return fail(DH_EINVAL, "dh_fit_tracker_state: NULL argument");
+    return read_tracker(t, "dh_fit_tracker_state", [&](size_t n) -> int {
+        HIP_TRY(hipMemcpy(states, t->state.get(), n * sizeof(dh_fit_track_state), hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
+}
+// The refusals of a step that are the tracker's own, before anything is launched.
+static int fit_track_check(const dh_fit_tracker *t, const void *frames, int w, int h, const void *poses, const void *support,
+                           const dh_fit_params *in, const void *records, dh_fit_params *prm, const char *who) {
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
+    if (!frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!poses || !support) return fail(DH_EINVAL, "%s: NULL poses or support", who);
+    if (!records) return fail(DH_EINVAL, "%s: NULL records", who);
+    if (w < 1 || h < 1 || w > DH_RENDER_MAX_SIZE || h > DH_RENDER_MAX_SIZE)
+        return fail(DH_EINVAL, "%s: frame size %dx%d, expected 1 .. %d each way", who, w, h, DH_RENDER_MAX_SIZE);
+    return fit_params_check(in, prm, who);
+}
+// Steps 0 - 6 for every camera, on device arrays and stream s (arguments checked, device selected): three launches.
+static int fit_track_enqueue(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
+                             const dh_support *support, const dh_fit_params &prm, dh_fit_track_record *records, hipStream_t s) {
+    FitTrackArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = t->n; a.flags = t->flags; a.scale = t->scale; a.prm = t->prm; a.rms_lim = t->rms_lim; a.jump2 = t->jump2;
+    a.coarse = prm.coarse_iterations; a.full = prm.iterations;
+    a.angles = t->angles.get(); a.present = present; a.poses = poses; a.support = support; a.state = t->state.get();
+    a.start = t->start.get(); a.sched = t->sched.get(); a.seed = t->seed.get();
+    a.fit_out = t->fit_out.get(); a.fit_rec = t->fit_rec.get(); a.records = records;
+    FitSchedArgs f;
+    memset(&f, 0, sizeof f);
+    f.f.frames = frames; f.f.n = t->n; f.f.w = w; f.f.h = h;
+    f.f.cams = t->cams->dev.get(); f.f.models = t->models.get(); f.f.inst = t->start.get(); f.f.n_inst = (uint32_t)t->n;
+    f.f.min_points = prm.min_points; f.f.gate[0] = prm.gate[0]; f.f.gate[1] = prm.gate[1]; f.f.lam1 = 1.0 + prm.lambda;
+    f.f.out = t->fit_out.get(); f.f.rec = t->fit_rec.get();
+    f.sched = t->sched.get(); f.seed = t->seed.get();
+    TRY(hip_step(dh_launch_fit_track_seed(a, s), "k_fit_track_seed"));
+    TRY(hip_step(dh_launch_fit_sched(f, s), "k_fit_sched"));
+    TRY(hip_step(dh_launch_fit_track_update(a, s), "k_fit_track_update"));
+    return DH_OK;
+}
+static int fit_tracker_step_poses_device_(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
+                                          const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records, void *stream) {
+    dh_fit_params prm;
+    TRY(fit_track_check(t, frames, w, h, poses, support, fit_params, records, &prm, "dh_fit_tracker_step_poses_device"));
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return fit_track_enqueue(t, frames, w, h, present, poses, support, prm, records, (hipStream_t)stream);
+}
+static int fit_tracker_step_device_(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
+                                    const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records,
+                                    void *stream) {
+    const char *who = "dh_fit_tracker_step_device";
+    dh_fit_params prm;
+    if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
+    TRY(fit_track_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
+    TRY(predict_batch_cameras_support_device_(p, frames, t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, poses_out, support_out, stream));
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return fit_track_enqueue(t, frames, w, h, present, poses_out, support_out, prm, records, (hipStream_t)stream);
+}
+// The host forms: everything staged through the tracker's buffers on its own stream; synchronous.  p NULL: the core step on
+// the caller's poses and support; else the prediction first, its poses and support copied back too.
+static int fit_track_host(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
+                          const dh_fit_params &prm, dh_pose *poses, dh_support *support, dh_fit_track_record *records) {
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    const size_t n = (size_t)t->n, n_px = n * w * h;
+    if (t->frames.cap() < n_px) TRY(t->frames.alloc(n_px));       // (host steps are synchronous: nothing reads the old buffer)
+    hipStream_t s = t->s;
+    HIP_TRY(hipMemcpyAsync(t->frames.get(), frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    if (present) HIP_TRY(hipMemcpyAsync(t->present.get(), present, n, hipMemcpyHostToDevice, s));
+    int rc;
+    if (p) rc = predict_batch_cameras_support_device_(p, t->frames.get(), t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, t->poses.get(),
+                                                      t->support.get(), s);
+    else {
+        HIP_TRY(hipMemcpyAsync(t->poses.get(), poses, n * sizeof(dh_pose), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(t->support.get(), support, n * sizeof(dh_support), hipMemcpyHostToDevice, s));
+        rc = DH_OK;
+    }
+    if (rc == DH_OK)
+        rc = fit_track_enqueue(t, t->frames.get(), w, h, present ? t->present.get() : nullptr, t->poses.get(), t->support.get(), prm,
+                               t->records.get(), s);
+    if (rc != DH_OK) { (void)hipStreamSynchronize(s); return rc; }
+    if (p) {
+        HIP_TRY(hipMemcpyAsync(poses, t->poses.get(), n * sizeof(dh_pose), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(support, t->support.get(), n * sizeof(dh_support), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipMemcpyAsync(records, t->records.get(), n * sizeof(dh_fit_track_record), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DH_OK;
+}
+static int fit_tracker_step_poses_(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
+                                   const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records) {
+    dh_fit_params prm;
+    TRY(fit_track_check(t, frames, w, h, poses, support, fit_params, records, &prm, "dh_fit_tracker_step_poses"));
+    return fit_track_host(nullptr, t, frames, w, h, present, 0, prm, const_cast<dh_pose *>(poses), const_cast<dh_support *>(support), records);
+}
+static int fit_tracker_step_(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
+                             const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records) {
+    const char *who = "dh_fit_tracker_step";
+    dh_fit_params prm;
+    if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
+    TRY(fit_track_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
+    if (radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u (a negative int?); expected 0 .. 2^31 - 1", who, radius);
+    if (t->cams->device != p->device) return fail(DH_EINVAL, "%s: camera table on device %d, predictor on device %d", who, t->cams->device, p->device);
+    return fit_track_host(p, t, frames, w, h, present, radius, prm, poses_out, support_out, records);
 }
 
 // ------------------------------------------------------------------ the C ABI
@@ -3042,4 +3259,14 @@ DH_API(fit_depth, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, co
 DH_API(fit_depth_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records), (f, frames, n, w, h, c, models, n_models, instances, n_instances, params, out, records))
 DH_API(fit_depth_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream), (f, frames, n, w, h, K, models, n_models, instances, n_instances, params, out, records, stream))
 DH_API(fit_depth_cameras_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream), (f, frames, n, w, h, c, models, n_models, instances, n_instances, params, out, records, stream))
+DH_API(fit_track_params_default, (dh_fit_track_params *p), (p))
+DH_API(fit_tracker_angles, (double out[DH_FIT_TRACK_ANGLES][2]), (out))
+DH_API(fit_tracker_create, (const dh_cameras *c, const dh_fit_model *m, float scale, uint32_t flags, const dh_fit_track_params *params, dh_fit_tracker **out), (c, m, scale, flags, params, out))
+DH_API(fit_tracker_destroy, (dh_fit_tracker *t), (t))
+DH_API(fit_tracker_reset, (dh_fit_tracker *t, int camera, void *stream), (t, camera, stream))
+DH_API(fit_tracker_state, (dh_fit_tracker *t, dh_fit_track_state *states), (t, states))
+DH_API(fit_tracker_step_poses, (dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records), (t, frames, w, h, present, poses, support, fit_params, records))
+DH_API(fit_tracker_step_poses_device, (dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records, void *stream), (t, frames, w, h, present, poses, support, fit_params, records, stream))
+DH_API(fit_tracker_step, (dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records), (p, t, frames, w, h, present, radius, fit_params, poses_out, support_out, records))
+DH_API(fit_tracker_step_device, (dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records, void *stream), (p, t, frames, w, h, present, radius, fit_params, poses_out, support_out, records, stream))
 #undef DH_API

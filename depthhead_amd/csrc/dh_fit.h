@@ -42,3 +42,47 @@ struct FitArgs {
 };
 
 hipError_t dh_launch_fit(const FitArgs &a, hipStream_t s);
+
+// ---- carrying fitted poses across steps (k_fit_track.hip and k_fit's per-instance-schedule instance)
+static_assert(sizeof(dh_fit_track_params) == 56, "dh_fit_track_params: 56 bytes");
+static_assert(sizeof(dh_fit_track_state) == 76, "dh_fit_track_state: 76 bytes");
+static_assert(sizeof(dh_fit_track_record) == 104, "dh_fit_track_record: 104 bytes");
+
+// What k_fit_track_seed decided for a camera: the start kind in the low byte, DH_FIT_SEED_VALID when the detection is valid.
+#define DH_FIT_SEED_NONE 0u
+#define DH_FIT_SEED_FOREST 1u
+#define DH_FIT_SEED_CARRIED 2u
+#define DH_FIT_SEED_ABSENT 3u
+#define DH_FIT_SEED_VALID 0x100u
+#define DH_FIT_TRACK_THREADS 64
+
+// k_fit_sched: k_fit with each instance's (coarse, full) read from `sched` and no work for an instance without a start.
+struct FitSchedArgs {
+    FitArgs f;                    // coarse and full unused
+    const uint32_t *sched;        // [n_inst][2]
+    const uint32_t *seed;         // [n_inst] DH_FIT_SEED_*
+};
+hipError_t dh_launch_fit_sched(const FitSchedArgs &a, hipStream_t s);
+
+struct FitTrackArgs {
+    int n;                        // cameras
+    uint32_t flags;               // DH_FIT_TRACK_*
+    float scale;
+    dh_fit_track_params prm;
+    int64_t rms_lim;              // (int64)(rms_max * rms_max * 2^20), cast on the host
+    double jump2;                 // max_jump * max_jump
+    uint32_t coarse, full;        // the forest start's schedule
+    const double *angles;         // [120][2] cos, sin
+    const uint8_t *present;       // nullable [n]
+    const dh_pose *poses;         // [n]
+    const dh_support *support;    // [n]
+    dh_fit_track_state *state;    // [n]
+    dh_render_instance *start;    // [n] seed -> fit, update
+    uint32_t *sched;              // [n][2]
+    uint32_t *seed;               // [n]
+    const dh_render_instance *fit_out;   // [n] fit -> update
+    const dh_fit_record *fit_rec;        // [n]
+    dh_fit_track_record *records;        // [n]
+};
+hipError_t dh_launch_fit_track_seed(const FitTrackArgs &a, hipStream_t s);
+hipError_t dh_launch_fit_track_update(const FitTrackArgs &a, hipStream_t s);

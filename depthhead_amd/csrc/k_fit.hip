@@ -260,9 +260,35 @@ __global__ __launch_bounds__(DH_FIT_THREADS) void k_fit(const FitArgs a) {
     } else fit_run<false>(a, in, m, s_pts, s_sum);
 }
 
+// The per-instance-schedule instance (dh_fit_tracker_step*): instance b runs (sched[b][0], sched[b][1]); a workgroup whose
+// instance has no start (uniform over the workgroup) leaves before the model is staged and writes nothing.
+__global__ __launch_bounds__(DH_FIT_THREADS) void k_fit_sched(const FitSchedArgs q) {
+    __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];
+    __shared__ unsigned long long s_sum[32];
+    const uint32_t kind = q.seed[blockIdx.x] & 0xffu;
+    if (kind != DH_FIT_SEED_FOREST && kind != DH_FIT_SEED_CARRIED) return;
+    FitArgs a = q.f;
+    a.coarse = q.sched[2 * blockIdx.x]; a.full = q.sched[2 * blockIdx.x + 1];
+    const dh_render_instance *in = a.inst + blockIdx.x;
+    const FitModel m = a.models[in->mesh];
+    if (m.n <= DH_FIT_LDS_POINTS) {
+        for (uint32_t k = threadIdx.x; k < m.n * 3; k += DH_FIT_THREADS) {
+            const uint32_t i = k / 3, c = k - i * 3;
+            s_pts[c * DH_FIT_LDS_POINTS + i] = m.pts[k];
+            s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] = m.nrm[k];
+        }
+        fit_run<true>(a, in, m, s_pts, s_sum);
+    } else fit_run<false>(a, in, m, s_pts, s_sum);
+}
+
 // ------------------------------------------------------------------ launcher
 hipError_t dh_launch_fit(const FitArgs &a, hipStream_t s) {
     if (a.n_inst == 0) return hipSuccess;
     hipLaunchKernelGGL(k_fit, dim3(a.n_inst), dim3(DH_FIT_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t dh_launch_fit_sched(const FitSchedArgs &a, hipStream_t s) {
+    if (a.f.n_inst == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fit_sched, dim3(a.f.n_inst), dim3(DH_FIT_THREADS), 0, s, a);
     return hipGetLastError();
 }

@@ -8,10 +8,15 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FIT_RECORD_DTYPE, RENDER_INSTANCE_DTYPE, check, vp
+from ._lib import (FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, POSE_DTYPE, RENDER_INSTANCE_DTYPE,
+                   SUPPORT_DTYPE, SUPPORT_RADIUS, check, vp)
 from .render import euler_to_matrix
 
 FIT_OK, FIT_FEW_POINTS, FIT_SINGULAR = 0, 1, 2      # dh_fit_record.status
+# dh_fit_track_record.status: the kind in the low byte, the reason bits of a rejected fit above it
+FIT_TRACK_NONE, FIT_TRACK_FITTED, FIT_TRACK_CARRIED, FIT_TRACK_REJECTED, FIT_TRACK_ABSENT = 0, 1, 2, 3, 4
+FIT_TRACK_BAD_STATUS, FIT_TRACK_BAD_POINTS, FIT_TRACK_BAD_RMS, FIT_TRACK_BAD_JUMP = 0x100, 0x200, 0x400, 0x800
+FIT_TRACK_MOTION = 1                                # DH_FIT_TRACK_MOTION
 
 
 def vertex_normals(verts, tris) -> np.ndarray:
@@ -144,3 +149,102 @@ class Fitter(_lib._Handle):
                                                                       C.c_uint32(len(models)), vp(inst) if ni else None, C.c_uint32(ni), prm,
                                                                       C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
         return out[:ni * RENDER_INSTANCE_DTYPE.itemsize], rec[:ni * FIT_RECORD_DTYPE.itemsize]
+
+
+def fit_track_params(iterations_tracked=None, keep_points=None, rms_max=None, max_jump=None, conf=None, min_windows=None,
+                     max_coast=None) -> "_lib.FitTrackParams":
+    """dh_fit_track_params_default with the given fields replaced; `conf` is (conf_num, conf_den)."""
+    p = _lib.FitTrackParams()
+    check(_lib.load().dh_fit_track_params_default(C.byref(p)))
+    for name, v in (("iterations_tracked", iterations_tracked), ("keep_points", keep_points), ("min_windows", min_windows),
+                    ("max_coast", max_coast)):
+        if v is not None:
+            setattr(p, name, int(v))
+    if rms_max is not None:
+        p.rms_max = float(rms_max)
+    if max_jump is not None:
+        p.max_jump = float(max_jump)
+    if conf is not None:
+        p.conf_num, p.conf_den = int(conf[0]), int(conf[1])
+    return p
+
+
+def angles() -> np.ndarray:
+    """The tracker's angle table [120, 2] f64: (cos, sin) of (i - 60) / 60 * 3.14159 as the library computed them."""
+    out = np.zeros((FIT_TRACK_ANGLES, 2), np.float64)
+    check(_lib.load().dh_fit_tracker_angles(vp(out)))
+    return out
+
+
+class FitTracker(_lib._Handle):
+    """One dh_fit_tracker: each camera of `cameras` (a `tracking.Cameras`) carries its fitted head pose from
+    step to step.  A step fits `model` to every present camera's frame -- from the carried pose, or from the forest's where
+    there is none -- and decides whether the fit is believed; a rejected fit sends the camera back to the forest.  The state
+    stays on the device.  Steps of one tracker must be stream-ordered; the camera table and the model must outlive it."""
+    _handles = (("_h", "dh_fit_tracker_destroy"),)
+
+    def __init__(self, cameras, model: Model, w: int, h: int, scale: float = 1.0, motion: bool = False, params=None):
+        self._lib = _lib.load()
+        self.cameras, self.model, self.w, self.h, self.n = cameras, model, int(w), int(h), len(cameras)
+        self.flags = FIT_TRACK_MOTION if motion else 0
+        self._h = C.c_void_p()
+        check(self._lib.dh_fit_tracker_create(cameras._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
+                                              C.byref(params) if params is not None else None, C.byref(self._h)))
+
+    def _frames(self, frames) -> np.ndarray:
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.shape != (self.n, self.h, self.w):
+            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
+        return frames
+
+    def _present(self, present):
+        return None if present is None else np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
+
+    def step_poses(self, frames, poses, support, present=None, fit_params=None) -> np.ndarray:
+        """The core step from the forest's POSE_DTYPE [n] and SUPPORT_DTYPE [n] of host frames [n, h, w] u16:
+        -> FIT_TRACK_RECORD_DTYPE [n]."""
+        frames, pr = self._frames(frames), self._present(present)
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(self.n)
+        support = np.ascontiguousarray(support, dtype=SUPPORT_DTYPE).reshape(self.n)
+        rec = np.zeros(self.n, FIT_TRACK_RECORD_DTYPE)
+        check(self._lib.dh_fit_tracker_step_poses(self._h, vp(frames), self.w, self.h, vp(pr), vp(poses), vp(support),
+                                                  C.byref(fit_params) if fit_params is not None else None, vp(rec)))
+        return rec
+
+    def step(self, hp, frames, present=None, radius: int = SUPPORT_RADIUS, fit_params=None):
+        """The whole step: `hp` (a HoughPrediction) predicts every camera's pose and support without guesses, then the core
+        step, on one stream.  -> (POSE_DTYPE [n], SUPPORT_DTYPE [n], FIT_TRACK_RECORD_DTYPE [n])."""
+        frames, pr = self._frames(frames), self._present(present)
+        poses, support = np.zeros(self.n, POSE_DTYPE), np.zeros(self.n, SUPPORT_DTYPE)
+        rec = np.zeros(self.n, FIT_TRACK_RECORD_DTYPE)
+        check(self._lib.dh_fit_tracker_step(hp._ph, self._h, vp(frames), self.w, self.h, vp(pr), C.c_uint32(int(radius) & 0xFFFFFFFF),
+                                            C.byref(fit_params) if fit_params is not None else None, vp(poses), vp(support), vp(rec)))
+        return poses, support, rec
+
+    def step_device(self, frames_ptr: int, poses_ptr: int, support_ptr: int, records_ptr: int, hp=None, present_ptr: int = 0,
+                    radius: int = SUPPORT_RADIUS, fit_params=None, stream: int = 0) -> None:
+        """Device frames [n][h][w] u16, poses [n] dh_pose, support [n] dh_support, records [n] dh_fit_track_record, present [n]
+        u8 or 0.  With `hp` the whole step (poses and support are outputs), without it the core step (they are inputs).
+        Asynchronous on `stream`; allocates nothing and never waits on the host."""
+        prm = C.byref(fit_params) if fit_params is not None else None
+        if hp is None:
+            check(self._lib.dh_fit_tracker_step_poses_device(self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None), vp(poses_ptr),
+                                                             vp(support_ptr), prm, vp(records_ptr), C.c_void_p(int(stream))))
+        else:
+            check(self._lib.dh_fit_tracker_step_device(hp._ph, self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
+                                                       C.c_uint32(int(radius) & 0xFFFFFFFF), prm, vp(poses_ptr), vp(support_ptr),
+                                                       vp(records_ptr), C.c_void_p(int(stream))))
+
+    def reset(self, camera: int | None = None, stream: int = 0) -> None:
+        """One camera or all back to the initial state (nothing tracked); stream-ordered."""
+        check(self._lib.dh_fit_tracker_reset(self._h, C.c_int(-1 if camera is None else int(camera)), C.c_void_p(int(stream))))
+
+    def state(self) -> np.ndarray:
+        """Synchronous copy of the state: FIT_TRACK_STATE_DTYPE [n]."""
+        st = np.zeros(self.n, FIT_TRACK_STATE_DTYPE)
+        check(self._lib.dh_fit_tracker_state(self._h, vp(st)))
+        return st
+
+    @staticmethod
+    def angles() -> np.ndarray:
+        return angles()

@@ -678,6 +678,115 @@ int dh_fit_depth_cameras_device(dh_fitter *f, const uint16_t *frames, int n, int
                                 uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records,
                                 void *stream);
 
+/* ---- carrying each camera's fitted pose across steps ----
+ * Detect once, follow with the model, fall back to the detector when the model loses the head: a dh_fit_tracker holds, per camera
+ * of a camera table, the last fitted instance, and each step fits every present camera's model to its frame from that instance
+ * (a short schedule without coarse steps) or, where there is none, from the forest's pose, and decides whether the fit is to be
+ * believed.  One head per camera.  Not in the reference: PARITY UNPINNED, the definition below is this library's.  f32 and f64
+ * expressions are evaluated left to right, every operation rounded on its own; only + - * /, compares and casts run on the
+ * device.  tests/fit_track_ref.py restates it; the GPU equals it byte for byte.
+ * STATE of camera c (dh_fit_track_state): R[9], t[3] of the last accepted instance (f32, exactly as the fit wrote them), t_prev[3]
+ *   the accepted t before that, tracked and have_prev (0 or 1), age (consecutive accepted steps) and lost (consecutive steps
+ *   without an accepted fit), both saturating at 2^32 - 1.  Created and reset to all zeros.
+ * ONE STEP of camera c from its depth frame, the forest's dh_pose and dh_support of that frame, and present[c] (NULL: all present):
+ * 0. ABSENT (present[c] == 0): R, t and t_prev stay; lost = lost + 1; have_prev = 0; when lost > max_coast: tracked = 0, age = 0.
+ *    The record: status DH_FIT_TRACK_ABSENT, instance and fit record zeros.  Nothing below runs.
+ * 1. DETECTION.  valid = total_mass > 0  and  mass * conf_den >= total_mass * conf_num (the exact 96-bit products)  and
+ *    windows >= min_windows.
+ * 2. START.  tracked: R = the state's R; t = the state's t, or with DH_FIT_TRACK_MOTION in the tracker's flags and have_prev,
+ *    t[j] = t[j] + (t[j] - t_prev[j]) in f32.  Schedule (0, iterations_tracked).
+ *    Else when valid: t = mid_point; for j = 0, 1, 2:  x = rotation[j] / 3.14159 * 60.0 + 60.5 (f64);  ri_j = 0 unless x >= 0.0 (NaN
+ *    too), 119 when x >= 119.0, else (int)x.  (c_j, s_j) = entry ri_j of the ANGLE TABLE: 120 pairs (cos a_i, sin a_i) of
+ *    a_i = (double)(i - 60) / 60.0 * 3.14159, computed once on the host by the C library's cos and sin and returned by
+ *    dh_fit_tracker_angles; no cosine or sine is evaluated anywhere else.  With, in f64 and row-major,
+ *      Z = [c0, s0, 0; -s0, c0, 0; 0, 0, 1]   (Rz(-a0): the sine negated, not evaluated again)
+ *      Y = [c1, 0, s1; 0, 1, 0; -s1, 0, c1]   X = [1, 0, 0; 0, c2, -s2; 0, s2, c2]
+ *    first M = Y Z, then R = X M, every element of a product as (A[i][0] * B[0][j] + A[i][1] * B[1][j]) + A[i][2] * B[2][j] with the
+ *    zeros and ones taking part as 0.0 and 1.0; R is rounded to f32 once: Rx(a2) Ry(a1) Rz(-a0), the convention of
+ *    render.euler_to_matrix.  Schedule (coarse_iterations, iterations) of the step's dh_fit_params.
+ *    Else there is NO START: lost = lost + 1, tracked = have_prev = age = 0, R, t, t_prev stay; the record: status
+ *    DH_FIT_TRACK_NONE, instance and fit record zeros; no fit work is done for the camera.
+ *    The start instance: frame c, mesh 0, R, t, the tracker's scale, flags 0.
+ * 3. FIT.  The rule of the section above, unchanged, on the start instance with the camera's K, the step's dh_fit_params (gates,
+ *    lambda, min_points) and the start's own schedule.
+ * 4. ACCEPTANCE.  Reason bits, the fit being accepted when none is set:
+ *    DH_FIT_TRACK_BAD_STATUS  status != DH_FIT_OK;      DH_FIT_TRACK_BAD_POINTS  points < keep_points;
+ *    DH_FIT_TRACK_BAD_RMS     sum_r2_fixed > (int64)(rms_max * rms_max * 1048576.0) * (int64)points   (the cast made once, on the host);
+ *    DH_FIT_TRACK_BAD_JUMP    the detection is valid and not ((dx * dx + dy * dy) + dz * dz <= max_jump * max_jump) with
+ *                             d = (double)t_fit - (double)mid_point, in f64 (a NaN rejects).
+ * 5. OUTCOME.  Accepted: t_prev = t; R, t = the fitted instance's; have_prev = the old tracked; tracked = 1; age = age + 1; lost = 0;
+ *    status DH_FIT_TRACK_CARRIED when the start was the carried one, else DH_FIT_TRACK_FITTED.  Not accepted: R, t, t_prev stay;
+ *    tracked = have_prev = age = 0; lost = lost + 1; status DH_FIT_TRACK_REJECTED | the reason bits; the next step starts from
+ *    the forest.
+ * 6. OUTPUT.  One dh_fit_track_record per camera: the fitted instance when accepted, else the start instance; the fit's record;
+ *    the status; age and lost after the step.
+ * dh_fit_tracker_create: the camera table and the model must outlive the tracker and live on one device.  Every device buffer
+ * is allocated there (the host forms' frame staging at the first host step, for its frame size): a _device step allocates nothing,
+ * launches k_fit_track_seed, the per-instance-schedule instance of k_fit and k_fit_track_update on `stream` and never waits on the
+ * host.  Steps of one tracker must be stream-ordered.  step_poses takes the forest's poses and support (host memory; _device:
+ * device memory); step first runs dh_predict_batch_cameras_support_device without guesses on the same stream and also returns
+ * its poses and support.  records [n_cams].  DH_EINVAL before anything is launched, with the outputs untouched:
+ * create: NULL cameras / model / out; unknown flags; a scale that is not finite or with |scale| * (the model's largest |v|) above
+ *   DH_FIT_MAX_EXTENT; a model on another device than the table; iterations_tracked above 64; rms_max or max_jump outside
+ *   (0, 4096] (NaN included); conf_den 0 or conf_num > conf_den; a reserved word that is not 0.
+ * step: NULL tracker / frames / poses / support / records (and predictor for the whole step); w or h outside 1 .. DH_RENDER_MAX_SIZE;
+ *   the fit's own refusals of dh_fit_params; for the whole step the predictor's own refusals (a radius above 2^31 - 1, another
+ *   device).  reset: NULL tracker, a camera outside -1 .. n - 1.  state, angles, params_default: NULL argument. */
+#define DH_FIT_TRACK_MOTION 1u          /* flags of dh_fit_tracker_create: constant-velocity start */
+#define DH_FIT_TRACK_NONE 0u            /* dh_fit_track_record.status, low byte */
+#define DH_FIT_TRACK_FITTED 1u
+#define DH_FIT_TRACK_CARRIED 2u
+#define DH_FIT_TRACK_REJECTED 3u
+#define DH_FIT_TRACK_ABSENT 4u
+#define DH_FIT_TRACK_BAD_STATUS 0x100u  /* reason bits, with DH_FIT_TRACK_REJECTED */
+#define DH_FIT_TRACK_BAD_POINTS 0x200u
+#define DH_FIT_TRACK_BAD_RMS 0x400u
+#define DH_FIT_TRACK_BAD_JUMP 0x800u
+#define DH_FIT_TRACK_ANGLES 120
+typedef struct dh_fit_track_params {
+    uint32_t iterations_tracked;  /* 6: full steps of a carried start, at most 64 */
+    uint32_t keep_points;         /* 30 */
+    double   rms_max;             /* 5.0 (mm), in (0, 4096] */
+    double   max_jump;            /* 150.0 (mm), in (0, 4096] */
+    uint32_t conf_num, conf_den;  /* 1 / 50: DESIGN.md section 13's confidence of a detected head at the default radius */
+    uint32_t min_windows;         /* 1 */
+    uint32_t max_coast;           /* 3 absent steps */
+    uint64_t reserved[2];         /* 0 */
+} dh_fit_track_params;  /* 56 bytes */
+typedef struct dh_fit_track_state {
+    float    R[9], t[3], t_prev[3];
+    uint32_t tracked, have_prev, age, lost;
+} dh_fit_track_state;   /* 76 bytes, no padding */
+typedef struct dh_fit_track_record {
+    dh_render_instance instance;
+    dh_fit_record      fit;
+    uint32_t status;              /* DH_FIT_TRACK_*: kind in the low byte, reason bits above it */
+    uint32_t age, lost;
+    uint32_t reserved;            /* 0 */
+} dh_fit_track_record;  /* 104 bytes, no padding */
+typedef struct dh_fit_tracker dh_fit_tracker;
+int dh_fit_track_params_default(dh_fit_track_params *p);
+/* the angle table (no tracker needed) */
+int dh_fit_tracker_angles(double out[DH_FIT_TRACK_ANGLES][2]);
+/* params NULL selects dh_fit_track_params_default */
+int dh_fit_tracker_create(const dh_cameras *c, const dh_fit_model *m, float scale, uint32_t flags, const dh_fit_track_params *params,
+                          dh_fit_tracker **out);
+int dh_fit_tracker_destroy(dh_fit_tracker *t);
+/* camera, or -1 for all, back to zeros; ordered on `stream` */
+int dh_fit_tracker_reset(dh_fit_tracker *t, int camera, void *stream);
+/* states [n_cams]; synchronises the device */
+int dh_fit_tracker_state(dh_fit_tracker *t, dh_fit_track_state *states);
+int dh_fit_tracker_step_poses(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
+                              const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records);
+int dh_fit_tracker_step_poses_device(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                     const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params,
+                                     dh_fit_track_record *records, void *stream);
+int dh_fit_tracker_step(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
+                        const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records);
+int dh_fit_tracker_step_device(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                               uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out,
+                               dh_fit_track_record *records, void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
