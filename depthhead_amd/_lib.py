@@ -93,6 +93,24 @@ class FitTrackParams(C.Structure):
                 ("reserved", C.c_uint64 * 2)]
 
 
+# dh_shape_record: what one shape step reports for a subject (dh_fit_shape*)
+SHAPE_RECORD_DTYPE = np.dtype([("delta", "<f8", (8,)), ("points", "<u4"), ("instances", "<u4"), ("status", "<u4"), ("reserved", "<u4"),
+                               ("sum_r2_fixed", "<i8")], align=True)
+assert SHAPE_RECORD_DTYPE.itemsize == 88
+SHAPE_MAX_FIELDS = 8       # DH_SHAPE_MAX_FIELDS
+SHAPE_MAX_SUBJECTS = 256   # DH_SHAPE_MAX_SUBJECTS
+SHAPE_SKIP = 0xFFFFFFFF    # DH_SHAPE_SKIP
+SHAPE_MAX_FIELD = 256      # DH_SHAPE_MAX_FIELD (mm)
+SHAPE_MAX_GATE = 256       # DH_SHAPE_MAX_GATE (mm)
+SHAPE_MAX_TERMS = 1 << 23  # DH_SHAPE_MAX_TERMS
+
+
+class ShapeParams(C.Structure):
+    """dh_shape_params (`lam` is the header's `lambda`)"""
+    _fields_ = [("gate", C.c_double), ("lam", C.c_double), ("min_points", C.c_uint32), ("reserved0", C.c_uint32),
+                ("reserved", C.c_uint64 * 2)]
+
+
 class RigTrackParams(C.Structure):
     """dh_rig_track_params"""
     _fields_ = [("max_heads", C.c_int32), ("radius", C.c_uint32), ("fuse_gate", C.c_uint32), ("gate", C.c_uint32),
@@ -151,6 +169,8 @@ EXPORTS = [
     "dh_fit_track_params_default", "dh_fit_tracker_angles", "dh_fit_tracker_create", "dh_fit_tracker_destroy", "dh_fit_tracker_reset",
     "dh_fit_tracker_state", "dh_fit_tracker_step_poses", "dh_fit_tracker_step_poses_device", "dh_fit_tracker_step",
     "dh_fit_tracker_step_device",
+    "dh_fit_basis_create", "dh_fit_basis_destroy", "dh_fit_basis_info", "dh_shape_params_default", "dh_fit_shape", "dh_fit_shape_cameras",
+    "dh_fit_shape_device", "dh_fit_shape_cameras_device",
 ]
 
 

@@ -2775,6 +2775,10 @@ struct dh_fitter {
     Buf<uint16_t> frames;                    // host calls
     Buf<dh_render_instance> out;
     Buf<dh_fit_record> rec;
+    Buf<unsigned long long> shape_sums;      // shape calls: [DH_SHAPE_MAX_SUBJECTS][DH_SHAPE_STRIDE], taken at the first one
+    Buf<dh_render_instance> shape_inst;      // host shape calls
+    Buf<uint32_t> shape_subj;
+    Buf<dh_shape_record> shape_rec;
     ~dh_fitter() {
         if (ev_up) (void)hipEventDestroy(ev_up);
         if (ev_done) (void)hipEventDestroy(ev_done);
@@ -2941,6 +2945,200 @@ static int fit_depth_device_(dh_fitter *f, const uint16_t *frames, int n, int w,
 static int fit_depth_cameras_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models,
                                      const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream) {
     return fit_run(f, FitReq{frames, n, w, h, nullptr, c, true, models, n_models, instances, n_instances, params, out, records}, true, (hipStream_t)stream, "dh_fit_depth_cameras_device");
+}
+
+// ------------------------------------------------------------------ adapting a model's shape to a subject
+// A basis: K displacement fields of a model of n points on one device, immutable, one plane per field and axis ([K][3][n]).
+struct dh_fit_basis {
+    int device = 0;
+    uint32_t n = 0, k = 0;
+    double largest = 0.0;         // the largest |B_k[i]|
+    Buf<float> planes;
+};
+static int fit_basis_create_(const float *fields, uint32_t n, uint32_t n_fields, int device, dh_fit_basis **out) {
+    if (!out) return fail(DH_EINVAL, "dh_fit_basis_create: NULL argument");
+    *out = nullptr;
+    if (!fields) return fail(DH_EINVAL, "dh_fit_basis_create: NULL argument");
+    if (n == 0 || n > DH_FIT_MAX_POINTS) return fail(DH_EINVAL, "dh_fit_basis_create: %u points, expected 1 .. %u", n, DH_FIT_MAX_POINTS);
+    if (n_fields == 0 || n_fields > DH_SHAPE_MAX_FIELDS)
+        return fail(DH_EINVAL, "dh_fit_basis_create: %u fields, expected 1 .. %u", n_fields, DH_SHAPE_MAX_FIELDS);
+    if (device < 0) return fail(DH_EINVAL, "dh_fit_basis_create: device %d", device);
+    std::unique_ptr<dh_fit_basis> b(new dh_fit_basis);
+    b->device = device; b->n = n; b->k = n_fields;
+    std::vector<float> planes((size_t)n_fields * 3 * n);
+    double l2 = 0.0;
+    for (uint32_t k = 0; k < n_fields; ++k)
+        for (uint32_t i = 0; i < n; ++i) {
+            double v2 = 0.0;
+            for (int c = 0; c < 3; ++c) {
+                const float v = fields[((size_t)k * n + i) * 3 + c];
+                if (!std::isfinite(v)) return fail(DH_EINVAL, "dh_fit_basis_create: field %u has a value at point %u that is not finite", k, i);
+                planes[((size_t)k * 3 + c) * n + i] = v;
+                v2 += (double)v * (double)v;
+            }
+            l2 = std::max(l2, v2);
+        }
+    b->largest = sqrt(l2);
+    DeviceGuard guard(device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(b->planes.alloc(planes.size()));
+    HIP_TRY(hipMemcpy(b->planes.get(), planes.data(), planes.size() * sizeof(float), hipMemcpyHostToDevice));
+    *out = b.release();
+    return DH_OK;
+}
+static int fit_basis_destroy_(dh_fit_basis *b) {
+    if (!b) return DH_OK;
+    DeviceGuard guard(b->device);
+    delete b;
+    return DH_OK;
+}
+static int fit_basis_info_(const dh_fit_basis *b, uint32_t *n, uint32_t *n_fields, double *largest) {
+    if (!b) return fail(DH_EINVAL, "dh_fit_basis_info: NULL basis");
+    if (n) *n = b->n;
+    if (n_fields) *n_fields = b->k;
+    if (largest) *largest = b->largest;
+    return DH_OK;
+}
+static int shape_params_default_(dh_shape_params *p) {
+    if (!p) return fail(DH_EINVAL, "dh_shape_params_default: NULL argument");
+    memset(p, 0, sizeof *p);
+    p->gate = 25.0;
+    p->lambda = 1e-3;
+    p->min_points = 64;
+    return DH_OK;
+}
+
+// One shape call.  dev: frames / instances / subjects / records are device pointers and `stream` the caller's; else host pointers.
+struct ShapeReq {
+    const uint16_t *frames; int n, w, h;
+    const float *K; const dh_cameras *cams; bool use_cams;
+    const dh_fit_model *model; const dh_fit_basis *basis;
+    const dh_render_instance *inst; uint32_t n_inst;
+    const uint32_t *subjects; uint32_t n_subjects;
+    const dh_shape_params *prm;
+    dh_shape_record *rec;
+};
+static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stream, const char *who) {
+    // ---- refusals: all of them before anything is allocated or launched
+    if (!f) return fail(DH_EINVAL, "%s: NULL fitter", who);
+    if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!q.rec) return fail(DH_EINVAL, "%s: NULL records", who);
+    if (!q.model) return fail(DH_EINVAL, "%s: NULL model", who);
+    if (!q.basis) return fail(DH_EINVAL, "%s: NULL basis", who);
+    if (q.n < 1 || q.n > 65535) return fail(DH_EINVAL, "%s: n = %d, expected 1 .. 65535 frames", who, q.n);
+    if (q.w < 1 || q.h < 1 || q.w > DH_RENDER_MAX_SIZE || q.h > DH_RENDER_MAX_SIZE)
+        return fail(DH_EINVAL, "%s: frame size %dx%d, expected 1 .. %d each way", who, q.w, q.h, DH_RENDER_MAX_SIZE);
+    if (q.use_cams) {
+        if (!q.cams) return fail(DH_EINVAL, "%s: NULL camera table", who);
+        if (q.cams->device != f->device) return fail(DH_EINVAL, "%s: the camera table lives on device %d, the fitter on %d", who, q.cams->device, f->device);
+        if (q.cams->n != q.n) return fail(DH_EINVAL, "%s: the camera table holds %d cameras, the batch %d frames", who, q.cams->n, q.n);
+    } else if (!q.K) return fail(DH_EINVAL, "%s: NULL K", who);
+    if (q.n_subjects < 1 || q.n_subjects > DH_SHAPE_MAX_SUBJECTS)
+        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u", who, q.n_subjects, DH_SHAPE_MAX_SUBJECTS);
+    dh_shape_params prm;
+    (void)shape_params_default_(&prm);
+    if (q.prm) prm = *q.prm;
+    if (!(prm.gate > 0.0 && prm.gate <= DH_SHAPE_MAX_GATE)) return fail(DH_EINVAL, "%s: gate = %g outside (0, %g]", who, prm.gate, DH_SHAPE_MAX_GATE);
+    if (!(prm.lambda >= 0.0) || !std::isfinite(prm.lambda)) return fail(DH_EINVAL, "%s: lambda %g, expected a finite value >= 0", who, prm.lambda);
+    if (prm.min_points < 1) return fail(DH_EINVAL, "%s: min_points 0 below 1", who);
+    if (prm.reserved0 || prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    const dh_fit_model *m = q.model;
+    const dh_fit_basis *b = q.basis;
+    if (m->device != f->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the fitter on %d", who, m->device, f->device);
+    if (b->device != f->device) return fail(DH_EINVAL, "%s: the basis lives on device %d, the fitter on %d", who, b->device, f->device);
+    if (b->n != m->n) return fail(DH_EINVAL, "%s: the basis is one of %u points, the model has %u", who, b->n, m->n);
+    if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
+    if (q.n_inst > DH_SHAPE_MAX_TERMS) return fail(DH_EINVAL, "%s: too many instances", who);
+    if (dev) {
+        if ((uint64_t)q.n_inst * m->n > DH_SHAPE_MAX_TERMS)
+            return fail(DH_EINVAL, "%s: %u instances of %u points exceed %u terms", who, q.n_inst, m->n, DH_SHAPE_MAX_TERMS);
+    } else {
+        std::vector<uint32_t> per(q.n_subjects, 0);
+        for (uint32_t i = 0; i < q.n_inst; ++i) {
+            const uint32_t sj = q.subjects ? q.subjects[i] : 0u;
+            if (sj == DH_SHAPE_SKIP) continue;
+            if (sj >= q.n_subjects) return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, q.n_subjects);
+            const dh_render_instance &in = q.inst[i];
+            if (in.frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, q.n);
+            bool finite = std::isfinite(in.scale);
+            for (int c = 0; c < 9; ++c) finite = finite && std::isfinite(in.R[c]);
+            for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(in.t[c]);
+            if (!finite) return fail(DH_EINVAL, "%s: instance %u has a non-finite R, t or scale", who, i);
+            for (int a = 0; a < 3; ++a)
+                for (int c = a; c < 3; ++c) {
+                    const double g = ((double)in.R[3 * a] * (double)in.R[3 * c] + (double)in.R[3 * a + 1] * (double)in.R[3 * c + 1]) +
+                                     (double)in.R[3 * a + 2] * (double)in.R[3 * c + 2];
+                    if (!(fabs(g - (a == c ? 1.0 : 0.0)) <= DH_FIT_R_TOLERANCE))
+                        return fail(DH_EINVAL, "%s: instance %u has an R that is not orthonormal: (R R^T)[%d][%d] = %g", who, i, a, c, g);
+                }
+            const double extent = fabs((double)in.scale) * m->radius;
+            if (extent > DH_FIT_MAX_EXTENT) return fail(DH_EINVAL, "%s: instance %u spans %g mm from its origin (limit %g)", who, i, extent, DH_FIT_MAX_EXTENT);
+            const double field = fabs((double)in.scale) * b->largest;
+            if (field > DH_SHAPE_MAX_FIELD) return fail(DH_EINVAL, "%s: instance %u scales the basis to %g mm (limit %g)", who, i, field, DH_SHAPE_MAX_FIELD);
+            if ((uint64_t)(++per[sj]) * m->n > DH_SHAPE_MAX_TERMS)
+                return fail(DH_EINVAL, "%s: subject %u has more than %u terms (instances times %u points)", who, sj, DH_SHAPE_MAX_TERMS, m->n);
+        }
+    }
+
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(fitter_init(f));
+    hipStream_t s = dev ? stream : f->s;
+    if (!f->shape_sums) TRY(f->shape_sums.alloc((size_t)DH_SHAPE_MAX_SUBJECTS * DH_SHAPE_STRIDE));
+    ShapeArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = q.n; a.w = q.w; a.h = q.h;
+    if (q.use_cams) a.cams = q.cams->dev.get();
+    else memcpy(a.k, q.K, sizeof a.k);
+    a.pts = m->pts.get(); a.nrm = m->nrm.get(); a.basis = b->planes.get();
+    a.np = m->n; a.nk = b->k;
+    a.radius = m->radius; a.largest = b->largest;
+    a.n_inst = q.n_inst; a.n_subjects = q.n_subjects;
+    a.min_points = prm.min_points;
+    a.gate = prm.gate;
+    a.lam1 = 1.0 + prm.lambda;
+    a.sums = f->shape_sums.get();
+    if (!dev) {
+        const size_t n_px = (size_t)q.n * q.w * q.h;
+        if (f->frames.cap() < n_px || f->shape_inst.cap() < q.n_inst || f->shape_rec.cap() < q.n_subjects) HIP_TRY(hipDeviceSynchronize());
+        TRY(f->frames.grow(n_px));
+        if (f->shape_inst.cap() < q.n_inst || !f->shape_inst) { TRY(f->shape_inst.grow(std::max<size_t>(q.n_inst, 1))); TRY(f->shape_subj.alloc(f->shape_inst.cap())); }
+        if (!f->shape_rec) TRY(f->shape_rec.alloc(DH_SHAPE_MAX_SUBJECTS));
+        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        if (q.n_inst) HIP_TRY(hipMemcpyAsync(f->shape_inst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_render_instance), hipMemcpyHostToDevice, s));
+        if (q.n_inst && q.subjects) HIP_TRY(hipMemcpyAsync(f->shape_subj.get(), q.subjects, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        a.frames = f->frames.get(); a.inst = f->shape_inst.get(); a.subjects = q.subjects ? f->shape_subj.get() : nullptr;
+        a.rec = f->shape_rec.get();
+    } else { a.frames = q.frames; a.inst = q.inst; a.subjects = q.subjects; a.rec = q.rec; }
+    // ---- the three stream-ordered operations
+    TRY(hip_step(dh_launch_shape_clear(a, s), "k_shape_clear"));
+    TRY(hip_step(dh_launch_shape_accumulate(a, s), "k_shape_accumulate"));
+    TRY(hip_step(dh_launch_shape_solve(a, s), "k_shape_solve"));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)q.n_subjects * sizeof(dh_shape_record), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return DH_OK;
+}
+static int fit_shape_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *model, const dh_fit_basis *basis,
+                      const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params,
+                      dh_shape_record *records) {
+    return shape_run(f, ShapeReq{frames, n, w, h, K, nullptr, false, model, basis, instances, n_instances, subjects, n_subjects, params, records}, false, nullptr, "dh_fit_shape");
+}
+static int fit_shape_cameras_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *model, const dh_fit_basis *basis,
+                              const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params,
+                              dh_shape_record *records) {
+    return shape_run(f, ShapeReq{frames, n, w, h, nullptr, c, true, model, basis, instances, n_instances, subjects, n_subjects, params, records}, false, nullptr, "dh_fit_shape_cameras");
+}
+static int fit_shape_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *model, const dh_fit_basis *basis,
+                             const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params,
+                             dh_shape_record *records, void *stream) {
+    return shape_run(f, ShapeReq{frames, n, w, h, K, nullptr, false, model, basis, instances, n_instances, subjects, n_subjects, params, records}, true, (hipStream_t)stream, "dh_fit_shape_device");
+}
+static int fit_shape_cameras_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *model, const dh_fit_basis *basis,
+                                     const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params,
+                                     dh_shape_record *records, void *stream) {
+    return shape_run(f, ShapeReq{frames, n, w, h, nullptr, c, true, model, basis, instances, n_instances, subjects, n_subjects, params, records}, true, (hipStream_t)stream, "dh_fit_shape_cameras_device");
 }
 
 // ------------------------------------------------------------------ carrying fitted poses across steps
@@ -3259,6 +3457,14 @@ DH_API(fit_depth, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, co
 DH_API(fit_depth_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records), (f, frames, n, w, h, c, models, n_models, instances, n_instances, params, out, records))
 DH_API(fit_depth_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream), (f, frames, n, w, h, K, models, n_models, instances, n_instances, params, out, records, stream))
 DH_API(fit_depth_cameras_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream), (f, frames, n, w, h, c, models, n_models, instances, n_instances, params, out, records, stream))
+DH_API(fit_basis_create, (const float *fields, uint32_t n, uint32_t n_fields, int device, dh_fit_basis **out), (fields, n, n_fields, device, out))
+DH_API(fit_basis_destroy, (dh_fit_basis *b), (b))
+DH_API(fit_basis_info, (const dh_fit_basis *b, uint32_t *n, uint32_t *n_fields, double *largest), (b, n, n_fields, largest))
+DH_API(shape_params_default, (dh_shape_params *p), (p))
+DH_API(fit_shape, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *model, const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records), (f, frames, n, w, h, K, model, basis, instances, n_instances, subjects, n_subjects, params, records))
+DH_API(fit_shape_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *model, const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records), (f, frames, n, w, h, c, model, basis, instances, n_instances, subjects, n_subjects, params, records))
+DH_API(fit_shape_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *model, const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n, w, h, K, model, basis, instances, n_instances, subjects, n_subjects, params, records, stream))
+DH_API(fit_shape_cameras_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *model, const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n, w, h, c, model, basis, instances, n_instances, subjects, n_subjects, params, records, stream))
 DH_API(fit_track_params_default, (dh_fit_track_params *p), (p))
 DH_API(fit_tracker_angles, (double out[DH_FIT_TRACK_ANGLES][2]), (out))
 DH_API(fit_tracker_create, (const dh_cameras *c, const dh_fit_model *m, float scale, uint32_t flags, const dh_fit_track_params *params, dh_fit_tracker **out), (c, m, scale, flags, params, out))

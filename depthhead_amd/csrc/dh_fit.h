@@ -86,3 +86,43 @@ struct FitTrackArgs {
 };
 hipError_t dh_launch_fit_track_seed(const FitTrackArgs &a, hipStream_t s);
 hipError_t dh_launch_fit_track_update(const FitTrackArgs &a, hipStream_t s);
+
+// ---- adapting a model's shape to a subject (k_fit_shape.hip)
+static_assert(sizeof(dh_shape_params) == 40, "dh_shape_params: 40 bytes");
+static_assert(sizeof(dh_shape_record) == 88, "dh_shape_record: 88 bytes");
+
+#define DH_SHAPE_THREADS 256
+// The sums of one subject, S = 2^20 as in the fit.  Magnitude: the gate g <= 256 (DH_SHAPE_MAX_GATE) and |scale| * max |B_k[i]| <=
+// 256 (DH_SHAPE_MAX_FIELD); with |R x| <= 1.03 |x| and |nrm| <= 1.05, |J_k| <= 1.05 * 1.03 * 256 < 277, and while |p| <= 2 p.z,
+// |r| <= 1.05 * 2 * 256 < 538: J J < 2^17, J r < 2^18, r r < 2^19.  Times 2^20, times 2^23 point-instances of one subject
+// (DH_SHAPE_MAX_TERMS): below 2^62 < 2^63.  The header says what holds outside that.
+// The words: A_kl at SHAPE_PAIR(k, l) (k <= l, rows of the 8 x 8 upper triangle whatever K is), b_k, e, count, used.
+#define DH_SHAPE_PAIR(k, l) ((k) * 8 - (k) * ((k) - 1) / 2 + ((l) - (k)))
+#define DH_SHAPE_B 36
+#define DH_SHAPE_E 44
+#define DH_SHAPE_COUNT 45
+#define DH_SHAPE_USED 46
+#define DH_SHAPE_SUMS 47
+#define DH_SHAPE_STRIDE 48          // words of a subject's row
+
+struct ShapeArgs {
+    const uint16_t *frames;       // [n][h][w]
+    int n, w, h;
+    float k[9];                   // the one K of the batch (cams == NULL)
+    const DhCam *cams;            // nullable [n]
+    const float *pts, *nrm;       // the model: [np][3] each
+    const float *basis;           // [nk][3][np]: one plane per field and axis, so a wave reads consecutive words
+    uint32_t np, nk;
+    double radius, largest;       // the model's largest |v|, the basis's largest |B_k[i]|
+    const dh_render_instance *inst;   // [n_inst]
+    const uint32_t *subjects;     // nullable [n_inst]
+    uint32_t n_inst, n_subjects;
+    uint32_t min_points;
+    double gate;
+    double lam1;                  // 1.0 + lambda (computed on the host: one f64 sum)
+    unsigned long long *sums;     // [n_subjects][DH_SHAPE_STRIDE], cleared on the stream (k_shape_clear) before the launch
+    dh_shape_record *rec;         // [n_subjects]
+};
+hipError_t dh_launch_shape_clear(const ShapeArgs &a, hipStream_t s);       // rows 0 .. n_subjects - 1 of a.sums
+hipError_t dh_launch_shape_accumulate(const ShapeArgs &a, hipStream_t s);
+hipError_t dh_launch_shape_solve(const ShapeArgs &a, hipStream_t s);

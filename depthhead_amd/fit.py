@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, POSE_DTYPE, RENDER_INSTANCE_DTYPE,
-                   SUPPORT_DTYPE, SUPPORT_RADIUS, check, vp)
+                   SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUPPORT_DTYPE, SUPPORT_RADIUS, check, vp)
 from .render import euler_to_matrix
 
 FIT_OK, FIT_FEW_POINTS, FIT_SINGULAR = 0, 1, 2      # dh_fit_record.status
@@ -17,6 +17,7 @@ FIT_OK, FIT_FEW_POINTS, FIT_SINGULAR = 0, 1, 2      # dh_fit_record.status
 FIT_TRACK_NONE, FIT_TRACK_FITTED, FIT_TRACK_CARRIED, FIT_TRACK_REJECTED, FIT_TRACK_ABSENT = 0, 1, 2, 3, 4
 FIT_TRACK_BAD_STATUS, FIT_TRACK_BAD_POINTS, FIT_TRACK_BAD_RMS, FIT_TRACK_BAD_JUMP = 0x100, 0x200, 0x400, 0x800
 FIT_TRACK_MOTION = 1                                # DH_FIT_TRACK_MOTION
+SHAPE_OK, SHAPE_FEW_POINTS, SHAPE_SINGULAR = 0, 1, 2  # dh_shape_record.status
 
 
 def vertex_normals(verts, tris) -> np.ndarray:
@@ -87,6 +88,56 @@ class Model(_lib._Handle):
         return n.value, radius.value
 
 
+class ShapeBasis(_lib._Handle):
+    """One dh_fit_basis: K displacement fields [K, n, 3] (mm) of a model of n points, on `device`."""
+    _handles = (("_h", "dh_fit_basis_destroy"),)
+
+    def __init__(self, fields, device: int = 0):
+        self._lib = _lib.load()
+        self.fields = np.ascontiguousarray(fields, dtype=np.float32)
+        if self.fields.ndim != 3 or self.fields.shape[2] != 3:
+            raise ValueError("fields [K, n, 3] are expected")
+        self.device = int(device)
+        self._h = C.c_void_p()
+        check(self._lib.dh_fit_basis_create(vp(self.fields), C.c_uint32(self.fields.shape[1]), C.c_uint32(self.fields.shape[0]), self.device,
+                                            C.byref(self._h)))
+
+    def __len__(self):
+        return self.fields.shape[0]
+
+    def info(self):
+        """(n, K, the largest |B_k[i]|) as the library holds them."""
+        n, k, largest = C.c_uint32(), C.c_uint32(), C.c_double()
+        check(self._lib.dh_fit_basis_info(self._h, C.byref(n), C.byref(k), C.byref(largest)))
+        return n.value, k.value, largest.value
+
+
+def shape_params(gate=None, lam=None, min_points=None) -> "_lib.ShapeParams":
+    """dh_shape_params_default with the given fields replaced."""
+    p = _lib.ShapeParams()
+    check(_lib.load().dh_shape_params_default(C.byref(p)))
+    if gate is not None:
+        p.gate = float(gate)
+    if lam is not None:
+        p.lam = float(lam)
+    if min_points is not None:
+        p.min_points = int(min_points)
+    return p
+
+
+def deform(verts, basis, coeffs) -> np.ndarray:
+    """The deformed vertices [n, 3] f32: v_i + sum_k c_k B_k[i] in f64, the fields added in index order, rounded to f32 once.
+    `basis` is a ShapeBasis or its fields [K, n, 3]."""
+    B = np.asarray(getattr(basis, "fields", basis), dtype=np.float32).astype(np.float64)
+    v = np.asarray(verts, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    c = np.asarray(coeffs, dtype=np.float64).reshape(-1)
+    if B.shape[1:] != v.shape or len(c) != len(B):
+        raise ValueError("basis [K, n, 3], verts [n, 3] and K coefficients are expected")
+    for k in range(len(B)):
+        v = v + c[k] * B[k]
+    return v.astype(np.float32)
+
+
 def fit_params(coarse_iterations=None, iterations=None, gate=None, lam=None, min_points=None) -> "_lib.FitParams":
     """dh_fit_params_default with the given fields replaced."""
     p = _lib.FitParams()
@@ -149,6 +200,70 @@ class Fitter(_lib._Handle):
                                                                       C.c_uint32(len(models)), vp(inst) if ni else None, C.c_uint32(ni), prm,
                                                                       C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
         return out[:ni * RENDER_INSTANCE_DTYPE.itemsize], rec[:ni * FIT_RECORD_DTYPE.itemsize]
+
+
+    def shape_step(self, frames, model, basis, instances, K_or_cameras, subjects=None, n_subjects: int = 1, params=None,
+                   device_out: bool = False, stream=None):
+        """One shape step of `model` and its `basis` over the fitted `instances` of `frames`, per subject:
+        subjects [n_instances] u32 (None: all subject 0; SHAPE_SKIP leaves an instance out).  Host form: numpy frames and
+        instances -> SHAPE_RECORD_DTYPE [n_subjects].  With device_out=True frames, instances and subjects are torch tensors on
+        the device (instances as the uint8 tensor Fitter.fit(device_out=True) returned, subjects int32 or None) and the records
+        come back as a uint8 torch tensor, ordered on `stream` (default the current torch stream) without a host wait."""
+        n, h, w = (int(v) for v in frames.shape)
+        cams = getattr(K_or_cameras, "_h", None)
+        if cams is None:
+            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
+            kind, karg = "", vp(K)
+        else:
+            kind, karg = "_cameras", cams
+        prm = C.byref(params) if params is not None else None
+        ns = int(n_subjects)
+        if not device_out:
+            fr = np.ascontiguousarray(frames, dtype=np.uint16)
+            inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
+            subj = None if subjects is None else np.ascontiguousarray(subjects, dtype=np.uint32).reshape(len(inst))
+            rec = np.zeros(max(ns, 0), SHAPE_RECORD_DTYPE)
+            check(getattr(self._lib, "dh_fit_shape" + kind)(self._h, vp(fr), n, w, h, karg, model._h, basis._h, vp(inst) if len(inst) else None,
+                                                             C.c_uint32(len(inst)), vp(subj), C.c_uint32(ns), prm, vp(rec)))
+            return rec
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
+            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
+        ni = instances.numel() * instances.element_size() // RENDER_INSTANCE_DTYPE.itemsize
+        if subjects is not None and (subjects.numel() != ni or subjects.element_size() != 4 or not subjects.is_contiguous()):
+            raise ValueError("device subjects: a contiguous 32-bit tensor with one word per instance is expected")
+        rec = torch.empty(max(ns, 1) * SHAPE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        check(getattr(self._lib, "dh_fit_shape" + kind + "_device")(self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, model._h, basis._h,
+                                                                      C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
+                                                                      C.c_void_p(subjects.data_ptr()) if subjects is not None else None,
+                                                                      C.c_uint32(ns), prm, C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
+        return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
+
+
+def adapt(fitter, frames, K_or_cameras, verts, tris, basis, starts, rounds: int = 6, fit_prm=None, shape_prm=None, coeffs=None):
+    """Adapt the shape coefficients of one subject's model to `frames` ([n, h, w] u16, numpy) by alternation, `rounds` times:
+    build the model from the current coefficients (deform, vertex_normals); fit every frame from its previous pose (the first
+    round from `starts`, RENDER_INSTANCE_DTYPE [m]); take one shape step over the fits that ended FIT_OK; add the increment
+    when the step ended SHAPE_OK.  Each round waits on the host: this happens once per subject, not once per frame.  `basis` is
+    the fields [K, n, 3] of the undeformed `verts`.  Returns (coefficients [K] f64, the last fitted instances, trace): trace[r]
+    holds the round's coefficients before the step, the fit records, the shape record and the increment."""
+    fields = np.ascontiguousarray(getattr(basis, "fields", basis), dtype=np.float32)
+    c = np.zeros(len(fields), np.float64) if coeffs is None else np.array(coeffs, dtype=np.float64)
+    inst = np.array(starts, dtype=RENDER_INSTANCE_DTYPE)
+    trace = []
+    with ShapeBasis(fields, device=fitter.device) as sb:
+        for _ in range(int(rounds)):
+            v = deform(verts, fields, c)
+            with Model(v, vertex_normals(v, tris), device=fitter.device) as model:
+                inst, rec = fitter.fit(frames, [model], inst, K_or_cameras, params=fit_prm)
+                subj = np.where(rec["status"] == FIT_OK, 0, SHAPE_SKIP).astype(np.uint32)
+                srec = fitter.shape_step(frames, model, sb, inst, K_or_cameras, subjects=subj, params=shape_prm)[0]
+            delta = srec["delta"][:len(c)].copy() if srec["status"] == SHAPE_OK else np.zeros(len(c))
+            trace.append({"coeffs": c.copy(), "fit": rec, "shape": srec, "delta": delta})
+            c = c + delta
+    return c, inst, trace
 
 
 def fit_track_params(iterations_tracked=None, keep_points=None, rms_max=None, max_jump=None, conf=None, min_windows=None,

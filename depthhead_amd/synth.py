@@ -407,6 +407,24 @@ def head_mesh(subdiv: int = 3):
     return verts.astype(np.float32), tris
 
 
+def head_basis(verts) -> np.ndarray:
+    """A shape basis [4, nv, 3] f32 for a head_mesh: the three per-axis stretch fields (x, 0, 0), (0, y, 0), (0, 0, z) -- so their
+    coefficients are relative stretches: coefficient 0.08 on the first widens the head by 8 % -- and the nose bump: every vertex
+    along its own ray, weighted by head_mesh's nose profile (a coefficient is the nose's relative growth)."""
+    v = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros((4,) + v.shape, np.float64)
+    for c in range(3):
+        out[c, :, c] = v[:, c]
+    u = v / np.asarray(HEAD_SEMI_AXES)
+    ln = np.sqrt((u * u).sum(axis=1))
+    u = u / np.where(ln > 0.0, ln, 1.0)[:, None]
+    d = np.array((0.0, 0.12, -1.0))
+    d = d / np.sqrt((d * d).sum())
+    ang = np.arccos(np.clip(u @ d, -1.0, 1.0))
+    out[3] = v * np.exp(-(ang * ang) / (2.0 * 0.16 * 0.16))[:, None]
+    return out.astype(np.float32)
+
+
 def box_mesh(lo, hi):
     """An axis-aligned box (8 vertices, 12 triangles) from corner `lo` to corner `hi`."""
     (x0, y0, z0), (x1, y1, z1) = lo, hi

@@ -787,6 +787,102 @@ int dh_fit_tracker_step_device(dh_predictor *p, dh_fit_tracker *t, const uint16_
                                uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out,
                                dh_fit_track_record *records, void *stream);
 
+/* ---- adapting a model's shape to a subject ----
+ * The fit above moves a rigid model; no subject has the generic head.  A dh_fit_basis adds a linear shape space to a model and one
+ * SHAPE STEP solves, per subject, for the increment of the shape coefficients that brings the model onto the frames it was already
+ * fitted to: one Gauss-Newton step over all fitted instances of the subject.  Not in the reference: PARITY UNPINNED, the
+ * definition below is this library's.  The arithmetic conventions are the fit's: f64, evaluated left to right, every product, sum
+ * and quotient rounded on its own, + - * /, compares and casts only, no library function on the device.
+ * BASIS: K displacement fields, 1 <= K <= DH_SHAPE_MAX_FIELDS, each n f32 triples B_k[i] in mm, for a model of n points; immutable,
+ *   on one device.  Deforming a model is the caller's step on the host: v_i + sum_k c_k B_k[i] in f64, rounded to f32 once, the
+ *   normals recomputed from the deformed mesh (fit.deform, fit.vertex_normals).  The device never evaluates coefficients: it solves
+ *   for an increment at the model it is given.
+ * ONE SHAPE STEP takes frames, one K or a camera table, ONE model and its basis, n_instances fitted instances (what dh_fit_depth*
+ *   wrote; `mesh` and `flags` are ignored), subjects[n_instances] (NULL: every instance belongs to subject 0; DH_SHAPE_SKIP: the
+ *   instance takes no part) and n_subjects <= DH_SHAPE_MAX_SUBJECTS.  For every instance that takes part and every point i of the
+ *   model, p, nrm, c, the five skip tests, the pixel, d and the residual r are those of ONE PASS of the section above at the
+ *   instance's (R, t), scale and frame, with gate g = params.gate.  For a point that passed, per field k < K:
+ *     sb = B_k[i] * scale;  w[j] = (R[j][0] * sb0 + R[j][1] * sb1) + R[j][2] * sb2;  J_k = (nrm0 * w0 + nrm1 * w1) + nrm2 * w2
+ *   and, into the sums of the instance's subject, with S = 2^20 and truncating casts (so their order is free):
+ *     A_kl += (int64)((J_k * J_l) * S) for k <= l,  b_k += (int64)((J_k * r) * S),  e += (int64)((r * r) * S),  count += 1;
+ *   used += 1 for every instance that passed at least one point.  Magnitudes: the gate lies in (0, DH_SHAPE_MAX_GATE] and
+ *   |scale| * (the basis's largest |B_k[i]|) <= DH_SHAPE_MAX_FIELD, so with the fit's |R x| <= 1.03 |x| and |nrm| <= 1.05,
+ *   |J_k| <= 1.05 * 1.03 * 256 < 2^9 and, while |p| <= 2 p.z, |r| <= 1.05 * 2 * 256 < 2^10: every product stays below 2^19;
+ *   times 2^20, a subject may sum 2^23 point-instances below 2^62.  A K that lets points through at a wider angle is not refused,
+ *   but there the sums can leave int64 and the result is unspecified (arithmetic only: nothing faults), and no longer pinned to the
+ *   restatement, whose Python ints do not wrap.
+ * SOLVE, per subject: count < min_points gives DH_SHAPE_FEW_POINTS and a zero increment (a subject without an instance: points 0).
+ *   Else A_kl = (double)sum / S (A symmetric), b_k alike; A_kk = A_kk * (1.0 + lambda) + 1e-9; A delta = b is solved on the K x K
+ *   block by the Gaussian elimination without pivoting and the back substitution of ONE STEP of the section above (n = K), in
+ *   that operation order.  A pivot that is not > 0.0 (NaN included) gives DH_SHAPE_SINGULAR and a zero increment.
+ * One dh_shape_record per subject: delta[k] for k < K and zeros beyond; points = count; instances = used; status; sum_r2_fixed = e,
+ *   the residual BEFORE the step (rms = sqrt(e / 2^20 / points)).  Bit-identical run to run and to tests/shape_ref.py.
+ * The calls run on a dh_fitter, which owns the sums buffer and (for the host calls) the staging, taken at the first shape call
+ * and growing on demand; the shape calls of one fitter must be stream-ordered with one another.  The host calls take host frames,
+ * instances, subjects and records and are synchronous.  The _device calls take device frames, instances, subjects and records,
+ * enqueue exactly three stream-ordered operations on `stream` (NULL = default stream) -- k_shape_clear (the subjects' sums back to zero),
+ * k_shape_accumulate, k_shape_solve -- and never wait on the host: they chain after dh_fit_depth*_device.  K and params are host memory in every call;
+ * params NULL selects dh_shape_params_default.
+ * DH_EINVAL before anything is launched, with the outputs untouched: NULL fitter / frames / records / model / basis; n < 1 or above
+ * 65535; w or h outside 1 .. DH_RENDER_MAX_SIZE; NULL K, or a NULL camera table, one of another device or one whose length is not
+ * n; n_subjects outside 1 .. DH_SHAPE_MAX_SUBJECTS; a gate outside (0, DH_SHAPE_MAX_GATE] (NaN included); lambda not >= 0 or not
+ * finite; min_points 0; a reserved word that is not 0; a model or basis of another device than the fitter; a basis whose n is not
+ * the model's; instances NULL with n_instances > 0; n_instances above 2^23.  The host calls also refuse, per instance that takes
+ * part: a frame >= n; a subject >= n_subjects that is not DH_SHAPE_SKIP; a non-finite R, t or scale; an R outside
+ * DH_FIT_R_TOLERANCE; |scale| * (the model's largest |v|) above DH_FIT_MAX_EXTENT; |scale| * (the basis's largest |B_k[i]|) above
+ * DH_SHAPE_MAX_FIELD; and a subject whose instances times n exceed DH_SHAPE_MAX_TERMS.  The _device calls cannot read the
+ * instances: they refuse n_instances * n above DH_SHAPE_MAX_TERMS, and the device skips (as DH_SHAPE_SKIP) every instance one of
+ * the per-instance refusals names, a NaN failing each test, so no input leads out of a buffer or out of the magnitude bound.
+ * n_instances = 0 is no error: every record is DH_SHAPE_FEW_POINTS with points 0. */
+#define DH_SHAPE_OK 0u
+#define DH_SHAPE_FEW_POINTS 1u         /* the subject's instances associated fewer than min_points points */
+#define DH_SHAPE_SINGULAR 2u           /* a pivot of the normal equations was not > 0 */
+#define DH_SHAPE_MAX_FIELDS 8u         /* fields of a basis */
+#define DH_SHAPE_MAX_SUBJECTS 256u     /* subjects of a call */
+#define DH_SHAPE_SKIP 0xFFFFFFFFu      /* subjects[i]: instance i takes no part */
+#define DH_SHAPE_MAX_FIELD 256.0       /* mm: |scale| * largest |B_k[i]| */
+#define DH_SHAPE_MAX_GATE 256.0        /* mm */
+#define DH_SHAPE_MAX_TERMS 8388608u    /* 2^23: points times instances of one subject */
+typedef struct dh_shape_params {
+    double   gate;                /* 25 (mm), in (0, DH_SHAPE_MAX_GATE] */
+    double   lambda;              /* 1e-3: relative damping of the diagonal, >= 0 */
+    uint32_t min_points;          /* 64, at least 1 */
+    uint32_t reserved0;           /* 0 */
+    uint64_t reserved[2];         /* 0 */
+} dh_shape_params;     /* 40 bytes */
+typedef struct dh_shape_record {
+    double   delta[8];            /* the increment of coefficient k; 0 for k >= K and when status is not DH_SHAPE_OK */
+    uint32_t points;              /* count */
+    uint32_t instances;           /* used */
+    uint32_t status;              /* DH_SHAPE_* */
+    uint32_t reserved;            /* 0 */
+    int64_t  sum_r2_fixed;        /* e: the residual before the step */
+} dh_shape_record;     /* 88 bytes, no padding */
+typedef struct dh_fit_basis dh_fit_basis;
+/* Copies n_fields fields of n triples each (fields[k][i][3], mm) to `device`.  DH_EINVAL: NULL arguments, n = 0 or above
+ * DH_FIT_MAX_POINTS, n_fields outside 1 .. DH_SHAPE_MAX_FIELDS, a non-finite value. */
+int dh_fit_basis_create(const float *fields, uint32_t n, uint32_t n_fields, int device, dh_fit_basis **out);
+int dh_fit_basis_destroy(dh_fit_basis *b);
+/* each pointer nullable; largest = the largest |B_k[i]| (f64) */
+int dh_fit_basis_info(const dh_fit_basis *b, uint32_t *n, uint32_t *n_fields, double *largest);
+int dh_shape_params_default(dh_shape_params *p);
+/* frames [n][h][w] u16; instances [n_instances]; subjects [n_instances] or NULL; records [n_subjects] */
+int dh_fit_shape(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *model,
+                 const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects,
+                 uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records);
+/* frame i is seen through camera i of the table, which must hold exactly n cameras */
+int dh_fit_shape_cameras(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *model,
+                         const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances,
+                         const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records);
+int dh_fit_shape_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *model,
+                        const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances,
+                        const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records,
+                        void *stream);
+int dh_fit_shape_cameras_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                const dh_fit_model *model, const dh_fit_basis *basis, const dh_render_instance *instances,
+                                uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params,
+                                dh_shape_record *records, void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
