@@ -2493,54 +2493,110 @@ static int mesh_info_(const dh_mesh *m, uint32_t *nv, uint32_t *nt, float bbox[6
     return DH_OK;
 }
 
-// A renderer: the call's tables (staged in page-locked memory, one upload per call), the triangle records, the tile counters and
-// lists, and the device frames of the host calls.  Everything grows on demand and is kept between calls.
-struct dh_renderer {
-    int device = 0;
+// The refusals that a render, fit or shape call begins with: the frame count, the frame size (a fit tracker's step has that half
+// alone) and the batch's camera table or K.  `owner` ("renderer" / "fitter") is who runs the call, on `device`.
+static int check_frame_size(int w, int h, const char *who) {
+    if (w < 1 || h < 1 || w > DH_RENDER_MAX_SIZE || h > DH_RENDER_MAX_SIZE)
+        return fail(DH_EINVAL, "%s: frame size %dx%d, expected 1 .. %d each way", who, w, h, DH_RENDER_MAX_SIZE);
+    return DH_OK;
+}
+static int check_frames(int n, int w, int h, const float *K, const dh_cameras *cams, bool use_cams, int device, const char *owner, const char *who) {
+    if (n < 1 || n > 65535) return fail(DH_EINVAL, "%s: n = %d, expected 1 .. 65535 frames", who, n);
+    TRY(check_frame_size(w, h, who));
+    if (use_cams) {
+        if (!cams) return fail(DH_EINVAL, "%s: NULL camera table", who);
+        if (cams->device != device) return fail(DH_EINVAL, "%s: the camera table lives on device %d, the %s on %d", who, cams->device, owner, device);
+        if (cams->n != n) return fail(DH_EINVAL, "%s: the camera table holds %d cameras, the batch %d frames", who, cams->n, n);
+    } else if (!K) return fail(DH_EINVAL, "%s: NULL K", who);
+    return DH_OK;
+}
+
+// The tables of a call (a renderer's or a fitter's): filled in page-locked memory, one upload per call, and the stream of the
+// owner's host calls.  The stream and the events come with init(), at the owner's first call, after its arguments were checked.
+struct CallTables {
     hipStream_t s = nullptr;                 // the host calls' stream
     hipEvent_t ev_up = nullptr;              // the last call's upload has left the staging buffer
-    hipEvent_t ev_done = nullptr;            // the last call's kernels are through with the renderer's memory
+    hipEvent_t ev_done = nullptr;            // the last call's kernels are through with the owner's memory
+    Buf<unsigned char, PINNED> stage;
+    Buf<unsigned char> dev;
+    ~CallTables() {
+        if (ev_up) (void)hipEventDestroy(ev_up);
+        if (ev_done) (void)hipEventDestroy(ev_done);
+        if (s) (void)hipStreamDestroy(s);
+    }
+    int init() {
+        if (s) return DH_OK;
+        TRY(hip_step(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate"));
+        TRY(hip_step(hipEventCreateWithFlags(&ev_up, hipEventDisableTiming), "hipEventCreate"));
+        TRY(hip_step(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming), "hipEventCreate"));
+        return DH_OK;
+    }
+    // `bytes` of staging, free to be filled
+    int reserve(size_t bytes) {
+        HIP_TRY(hipEventSynchronize(ev_up));         // (the staging buffer is free again; at once when nothing was recorded)
+        if (stage.cap() < bytes || dev.cap() < bytes) {
+            HIP_TRY(hipDeviceSynchronize());         // (an earlier call may still read the tables)
+            TRY(stage.grow(bytes));
+            TRY(dev.alloc(stage.cap()));
+        }
+        return DH_OK;
+    }
+    int upload(size_t bytes, hipStream_t st) {
+        HIP_TRY(hipStreamWaitEvent(st, ev_done, 0)); // (a call on another stream may still be using the tables and what they name)
+        HIP_TRY(hipMemcpyAsync(dev.get(), stage.get(), bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(ev_up, st));
+        return DH_OK;
+    }
+    int done(hipStream_t st) {
+        HIP_TRY(hipEventRecord(ev_done, st));
+        return DH_OK;
+    }
+};
+// The handle alone (dh_renderer, dh_fitter), and its end: a handle whose tables were set up has work that may still run.
+template <typename T>
+static int create_owner(int device, T **out, const char *who) {
+    if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
+    *out = nullptr;
+    if (device < 0) return fail(DH_EINVAL, "%s: device %d", who, device);
+    std::unique_ptr<T> o(new T);
+    o->device = device;
+    *out = o.release();
+    return DH_OK;
+}
+template <typename T>
+static int destroy_owner(T *o) {
+    if (!o) return DH_OK;
+    if (o->tab.s) {
+        DeviceGuard guard(o->device);
+        (void)hipDeviceSynchronize();
+        delete o;
+    } else delete o;
+    return DH_OK;
+}
+
+// A renderer: the call's tables, the triangle records, the tile counters and lists, and the device frames of the host calls.
+// Everything grows on demand and is kept between calls.
+struct dh_renderer {
+    int device = 0;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     bool profiling = false, timed = false;
-    Buf<unsigned char, PINNED> stage;        // tri_begin | meshes | instances
-    Buf<unsigned char> tables;
     Buf<unsigned long long, PINNED> total_h; // [2]
     Buf<unsigned long long> total;           // [2]
     Buf<RenderTri> tri;
     Buf<uint32_t> tile_cnt, tile_cur, list;
     Buf<uint16_t> frames;                    // host calls
     Buf<uint8_t> masks;
+    CallTables tab;                          // tri_begin | meshes | instances (last: its stream and events go before any buffer)
     ~dh_renderer() {
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-        if (ev_up) (void)hipEventDestroy(ev_up);
-        if (ev_done) (void)hipEventDestroy(ev_done);
-        if (s) (void)hipStreamDestroy(s);
     }
 };
-static int renderer_destroy_(dh_renderer *r) {
-    if (!r) return DH_OK;
-    if (r->s) {
-        DeviceGuard guard(r->device);
-        (void)hipDeviceSynchronize();
-        delete r;
-    } else delete r;
-    return DH_OK;
-}
-// (the handle alone: the stream, the events and the first buffers come with the first render, after its arguments were checked)
-static int renderer_create_(int device, dh_renderer **out) {
-    if (!out) return fail(DH_EINVAL, "dh_renderer_create: NULL argument");
-    *out = nullptr;
-    if (device < 0) return fail(DH_EINVAL, "dh_renderer_create: device %d", device);
-    std::unique_ptr<dh_renderer> r(new dh_renderer);
-    r->device = device;
-    *out = r.release();
-    return DH_OK;
-}
+static int renderer_destroy_(dh_renderer *r) { return destroy_owner(r); }
+static int renderer_create_(int device, dh_renderer **out) { return create_owner(device, out, "dh_renderer_create"); }
+// (the first buffers too come with the first render)
 static int renderer_init(dh_renderer *r) {
-    if (r->s) return DH_OK;
-    TRY(hip_step(hipStreamCreateWithFlags(&r->s, hipStreamNonBlocking), "hipStreamCreate"));
-    TRY(hip_step(hipEventCreateWithFlags(&r->ev_up, hipEventDisableTiming), "hipEventCreate"));
-    TRY(hip_step(hipEventCreateWithFlags(&r->ev_done, hipEventDisableTiming), "hipEventCreate"));
+    if (r->tab.s) return DH_OK;
+    TRY(r->tab.init());
     for (auto &e : r->ev) TRY(hip_step(hipEventCreate(&e), "hipEventCreate"));
     TRY(r->total.alloc(2));
     TRY(r->total_h.alloc(2));
@@ -2574,14 +2630,7 @@ static int render_run(dh_renderer *r, const RenderReq &q, bool dev_out, hipStrea
     // ---- refusals: all of them before anything is allocated or launched
     if (!r) return fail(DH_EINVAL, "%s: NULL renderer", who);
     if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
-    if (q.n < 1 || q.n > 65535) return fail(DH_EINVAL, "%s: n = %d, expected 1 .. 65535 frames", who, q.n);
-    if (q.w < 1 || q.h < 1 || q.w > DH_RENDER_MAX_SIZE || q.h > DH_RENDER_MAX_SIZE)
-        return fail(DH_EINVAL, "%s: frame size %dx%d, expected 1 .. %d each way", who, q.w, q.h, DH_RENDER_MAX_SIZE);
-    if (q.use_cams) {
-        if (!q.cams) return fail(DH_EINVAL, "%s: NULL camera table", who);
-        if (q.cams->device != r->device) return fail(DH_EINVAL, "%s: the camera table lives on device %d, the renderer on %d", who, q.cams->device, r->device);
-        if (q.cams->n != q.n) return fail(DH_EINVAL, "%s: the camera table holds %d cameras, the batch %d frames", who, q.cams->n, q.n);
-    } else if (!q.K) return fail(DH_EINVAL, "%s: NULL K", who);
+    TRY(check_frames(q.n, q.w, q.h, q.K, q.cams, q.use_cams, r->device, "renderer", who));
     if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
     if (q.n_inst && !q.meshes) return fail(DH_EINVAL, "%s: NULL meshes", who);
     if (q.n_inst > 0x7fffffffu) return fail(DH_EINVAL, "%s: too many instances", who);
@@ -2613,7 +2662,7 @@ static int render_run(dh_renderer *r, const RenderReq &q, bool dev_out, hipStrea
     DeviceGuard guard(r->device);
     if (!guard.ok) return DH_EHIP;
     TRY(renderer_init(r));
-    hipStream_t s = dev_out ? stream : r->s;
+    hipStream_t s = dev_out ? stream : r->tab.s;
     RenderArgs a;
     memset(&a, 0, sizeof a);
     a.n = q.n; a.w = q.w; a.h = q.h;
@@ -2628,24 +2677,19 @@ static int render_run(dh_renderer *r, const RenderReq &q, bool dev_out, hipStrea
     const size_t o_mesh = (((size_t)q.n_inst + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
     const size_t o_inst = o_mesh + (((size_t)q.n_meshes * sizeof(RenderMesh) + 15) & ~(size_t)15);
     const size_t bytes = o_inst + (size_t)q.n_inst * sizeof(dh_render_instance);
-    HIP_TRY(hipEventSynchronize(r->ev_up));          // (the staging buffer is free again; at once when nothing was recorded)
-    if (r->stage.cap() < bytes || r->tables.cap() < bytes) {
-        HIP_TRY(hipDeviceSynchronize());             // (an earlier call may still read the tables)
-        TRY(r->stage.grow(bytes));
-        TRY(r->tables.alloc(r->stage.cap()));
-    }
+    TRY(r->tab.reserve(bytes));
     {
-        uint32_t *tb = (uint32_t *)r->stage.get();
-        RenderMesh *mm = (RenderMesh *)(r->stage.get() + o_mesh);
+        uint32_t *tb = (uint32_t *)r->tab.stage.get();
+        RenderMesh *mm = (RenderMesh *)(r->tab.stage.get() + o_mesh);
         uint32_t acc = 0;
         for (uint32_t i = 0; i < q.n_inst; ++i) { tb[i] = acc; acc += q.meshes[q.inst[i].mesh]->nt; }
         tb[q.n_inst] = acc;
         for (uint32_t i = 0; i < q.n_meshes && q.n_inst; ++i) mm[i] = RenderMesh{q.meshes[i]->verts.get(), q.meshes[i]->tris.get(), q.meshes[i]->nv, q.meshes[i]->nt};
-        if (q.n_inst) memcpy(r->stage.get() + o_inst, q.inst, (size_t)q.n_inst * sizeof(dh_render_instance));
+        if (q.n_inst) memcpy(r->tab.stage.get() + o_inst, q.inst, (size_t)q.n_inst * sizeof(dh_render_instance));
     }
-    a.tri_begin = (const uint32_t *)r->tables.get();
-    a.meshes = (const RenderMesh *)(r->tables.get() + o_mesh);
-    a.inst = (const dh_render_instance *)(r->tables.get() + o_inst);
+    a.tri_begin = (const uint32_t *)r->tab.dev.get();
+    a.meshes = (const RenderMesh *)(r->tab.dev.get() + o_mesh);
+    a.inst = (const dh_render_instance *)(r->tab.dev.get() + o_inst);
     // ---- renderer-owned memory (growing waits for whatever still uses the old)
     if (r->tri.cap() < n_tri || r->tile_cnt.cap() < n_tiles) HIP_TRY(hipDeviceSynchronize());
     TRY(r->tri.grow((size_t)n_tri));
@@ -2658,9 +2702,7 @@ static int render_run(dh_renderer *r, const RenderReq &q, bool dev_out, hipStrea
     a.tri = r->tri.get(); a.tile_cnt = r->tile_cnt.get(); a.tile_cur = r->tile_cur.get(); a.total = r->total.get();
     const bool prof = r->profiling;
     Range range(prof, "dh:render");
-    HIP_TRY(hipStreamWaitEvent(s, r->ev_done, 0));      // (a call on another stream may still be using the records and lists)
-    HIP_TRY(hipMemcpyAsync(r->tables.get(), r->stage.get(), bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(r->ev_up, s));
+    TRY(r->tab.upload(bytes, s));                       // (waits for a call on another stream that still uses the records and lists)
     HIP_TRY(hipMemsetAsync(a.tile_cnt, 0, n_tiles * sizeof(uint32_t), s));
     HIP_TRY(hipMemsetAsync(a.total, 0, 2 * sizeof(unsigned long long), s));
     if (prof) HIP_TRY(hipEventRecord(r->ev[0], s));
@@ -2679,7 +2721,7 @@ static int render_run(dh_renderer *r, const RenderReq &q, bool dev_out, hipStrea
     if (prof) HIP_TRY(hipEventRecord(r->ev[3], s));
     TRY(hip_step(dh_launch_render_resolve(a, s), "k_render_resolve"));
     if (prof) { HIP_TRY(hipEventRecord(r->ev[4], s)); r->timed = true; }
-    HIP_TRY(hipEventRecord(r->ev_done, s));
+    TRY(r->tab.done(s));
     if (!dev_out) {
         HIP_TRY(hipMemcpyAsync(q.frames, a.frames, n_px * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
         if (q.masks) HIP_TRY(hipMemcpyAsync(q.masks, a.masks, n_px, hipMemcpyDeviceToHost, s));
@@ -2763,15 +2805,10 @@ static int fit_params_default_(dh_fit_params *p) {
     return DH_OK;
 }
 
-// A fitter: the call's tables (staged in page-locked memory, one upload per call) and, for the host calls, the frames and the
-// outputs on the device.  Everything grows on demand and is kept between calls.
+// A fitter: the call's tables and, for the host calls, the frames and the outputs on the device.  Everything grows on demand and
+// is kept between calls.
 struct dh_fitter {
     int device = 0;
-    hipStream_t s = nullptr;                 // the host calls' stream
-    hipEvent_t ev_up = nullptr;              // the last call's upload has left the staging buffer
-    hipEvent_t ev_done = nullptr;            // the last call's kernel is through with the tables
-    Buf<unsigned char, PINNED> stage;        // models | instances
-    Buf<unsigned char> tables;
     Buf<uint16_t> frames;                    // host calls
     Buf<dh_render_instance> out;
     Buf<dh_fit_record> rec;
@@ -2779,38 +2816,10 @@ struct dh_fitter {
     Buf<dh_render_instance> shape_inst;      // host shape calls
     Buf<uint32_t> shape_subj;
     Buf<dh_shape_record> shape_rec;
-    ~dh_fitter() {
-        if (ev_up) (void)hipEventDestroy(ev_up);
-        if (ev_done) (void)hipEventDestroy(ev_done);
-        if (s) (void)hipStreamDestroy(s);
-    }
+    CallTables tab;                          // models | instances (last: its stream and events go before any buffer)
 };
-// (the handle alone: the stream, the events and the buffers come with the first fit, after its arguments were checked)
-static int fitter_create_(int device, dh_fitter **out) {
-    if (!out) return fail(DH_EINVAL, "dh_fitter_create: NULL argument");
-    *out = nullptr;
-    if (device < 0) return fail(DH_EINVAL, "dh_fitter_create: device %d", device);
-    std::unique_ptr<dh_fitter> f(new dh_fitter);
-    f->device = device;
-    *out = f.release();
-    return DH_OK;
-}
-static int fitter_destroy_(dh_fitter *f) {
-    if (!f) return DH_OK;
-    if (f->s) {
-        DeviceGuard guard(f->device);
-        (void)hipDeviceSynchronize();
-        delete f;
-    } else delete f;
-    return DH_OK;
-}
-static int fitter_init(dh_fitter *f) {
-    if (f->s) return DH_OK;
-    TRY(hip_step(hipStreamCreateWithFlags(&f->s, hipStreamNonBlocking), "hipStreamCreate"));
-    TRY(hip_step(hipEventCreateWithFlags(&f->ev_up, hipEventDisableTiming), "hipEventCreate"));
-    TRY(hip_step(hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming), "hipEventCreate"));
-    return DH_OK;
-}
+static int fitter_create_(int device, dh_fitter **out) { return create_owner(device, out, "dh_fitter_create"); }
+static int fitter_destroy_(dh_fitter *f) { return destroy_owner(f); }
 
 // The refusals of a call's dh_fit_params (NULL: the defaults); *out is what the call runs with.
 static int fit_params_check(const dh_fit_params *in, dh_fit_params *out, const char *who) {
@@ -2827,6 +2836,25 @@ static int fit_params_check(const dh_fit_params *in, dh_fit_params *out, const c
     *out = prm;
     return DH_OK;
 }
+// The half of a FitArgs that the (checked) params fill.
+static void fit_args_params(FitArgs &a, const dh_fit_params &prm) {
+    a.coarse = prm.coarse_iterations; a.full = prm.iterations; a.min_points = prm.min_points;
+    a.gate[0] = prm.gate[0]; a.gate[1] = prm.gate[1];
+    a.lam1 = 1.0 + prm.lambda;
+}
+// What dh_fit_instance_fault found in instance i, as the refusal of a fit or shape call; DH_OK where it found nothing.
+static int instance_refusal(const FitInstanceFault &fault, const dh_render_instance &in, uint32_t i, double radius, double largest, const char *who) {
+    switch (fault.why) {
+    case DH_FIT_INST_OK: return DH_OK;
+    case DH_FIT_INST_NOT_FINITE: return fail(DH_EINVAL, "%s: instance %u has a non-finite R, t or scale", who, i);
+    case DH_FIT_INST_NOT_ORTHONORMAL:
+        return fail(DH_EINVAL, "%s: instance %u has an R that is not orthonormal: (R R^T)[%d][%d] = %g", who, i, fault.a, fault.b, fault.g);
+    case DH_FIT_INST_EXTENT:
+        return fail(DH_EINVAL, "%s: instance %u spans %g mm from its origin (limit %g)", who, i, fabs((double)in.scale) * radius, DH_FIT_MAX_EXTENT);
+    default:
+        return fail(DH_EINVAL, "%s: instance %u scales the basis to %g mm (limit %g)", who, i, fabs((double)in.scale) * largest, DH_SHAPE_MAX_FIELD);
+    }
+}
 
 // One fit call.  dev: frames / out / records are device pointers and `stream` the caller's; else host pointers.
 struct FitReq {
@@ -2842,14 +2870,7 @@ static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, 
     if (!f) return fail(DH_EINVAL, "%s: NULL fitter", who);
     if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
     if (!q.out || !q.rec) return fail(DH_EINVAL, "%s: NULL output", who);
-    if (q.n < 1 || q.n > 65535) return fail(DH_EINVAL, "%s: n = %d, expected 1 .. 65535 frames", who, q.n);
-    if (q.w < 1 || q.h < 1 || q.w > DH_RENDER_MAX_SIZE || q.h > DH_RENDER_MAX_SIZE)
-        return fail(DH_EINVAL, "%s: frame size %dx%d, expected 1 .. %d each way", who, q.w, q.h, DH_RENDER_MAX_SIZE);
-    if (q.use_cams) {
-        if (!q.cams) return fail(DH_EINVAL, "%s: NULL camera table", who);
-        if (q.cams->device != f->device) return fail(DH_EINVAL, "%s: the camera table lives on device %d, the fitter on %d", who, q.cams->device, f->device);
-        if (q.cams->n != q.n) return fail(DH_EINVAL, "%s: the camera table holds %d cameras, the batch %d frames", who, q.cams->n, q.n);
-    } else if (!q.K) return fail(DH_EINVAL, "%s: NULL K", who);
+    TRY(check_frames(q.n, q.w, q.h, q.K, q.cams, q.use_cams, f->device, "fitter", who));
     dh_fit_params prm;
     TRY(fit_params_check(q.prm, &prm, who));
     if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
@@ -2859,57 +2880,40 @@ static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, 
         const dh_render_instance &in = q.inst[i];
         if (in.frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, q.n);
         if (in.mesh >= q.n_models) return fail(DH_EINVAL, "%s: instance %u names model %u of %u", who, i, in.mesh, q.n_models);
-        bool finite = std::isfinite(in.scale);
-        for (int c = 0; c < 9; ++c) finite = finite && std::isfinite(in.R[c]);
-        for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(in.t[c]);
-        if (!finite) return fail(DH_EINVAL, "%s: instance %u has a non-finite R, t or scale", who, i);
-        // R must be near a rotation: the magnitude bound of the int64 sums (dh_fit.h) rests on |R x| <= 1.03 |x|
-        for (int a = 0; a < 3; ++a)
-            for (int b = a; b < 3; ++b) {
-                const double g = ((double)in.R[3 * a] * (double)in.R[3 * b] + (double)in.R[3 * a + 1] * (double)in.R[3 * b + 1]) +
-                                 (double)in.R[3 * a + 2] * (double)in.R[3 * b + 2];
-                if (!(fabs(g - (a == b ? 1.0 : 0.0)) <= DH_FIT_R_TOLERANCE))
-                    return fail(DH_EINVAL, "%s: instance %u has an R that is not orthonormal: (R R^T)[%d][%d] = %g", who, i, a, b, g);
-            }
         const dh_fit_model *m = q.models[in.mesh];
+        const double radius = m ? m->radius : 0.0;   // (the refusals of the model itself stand between those of R and of the extent)
+        const FitInstanceFault fault = dh_fit_instance_fault(in, radius, 0.0);
+        if (fault.why != DH_FIT_INST_OK && fault.why < DH_FIT_INST_EXTENT) return instance_refusal(fault, in, i, radius, 0.0, who);
         if (!m) return fail(DH_EINVAL, "%s: model %u is NULL", who, in.mesh);
         if (m->device != f->device) return fail(DH_EINVAL, "%s: model %u lives on device %d, the fitter on %d", who, in.mesh, m->device, f->device);
-        const double extent = fabs((double)in.scale) * m->radius;
-        if (extent > DH_FIT_MAX_EXTENT) return fail(DH_EINVAL, "%s: instance %u spans %g mm from its origin (limit %g)", who, i, extent, DH_FIT_MAX_EXTENT);
+        if (fault.why != DH_FIT_INST_OK) return instance_refusal(fault, in, i, radius, 0.0, who);
     }
     if (q.n_inst == 0) return DH_OK;
 
     DeviceGuard guard(f->device);
     if (!guard.ok) return DH_EHIP;
-    TRY(fitter_init(f));
-    hipStream_t s = dev ? stream : f->s;
+    TRY(f->tab.init());
+    hipStream_t s = dev ? stream : f->tab.s;
     FitArgs a;
     memset(&a, 0, sizeof a);
     a.n = q.n; a.w = q.w; a.h = q.h;
     if (q.use_cams) a.cams = q.cams->dev.get();
     else memcpy(a.k, q.K, sizeof a.k);
     a.n_inst = q.n_inst;
-    a.coarse = prm.coarse_iterations; a.full = prm.iterations; a.min_points = prm.min_points;
-    a.gate[0] = prm.gate[0]; a.gate[1] = prm.gate[1];
-    a.lam1 = 1.0 + prm.lambda;
+    fit_args_params(a, prm);
     // ---- the call's tables: one staging buffer, one upload
     const size_t o_inst = ((size_t)q.n_models * sizeof(FitModel) + 15) & ~(size_t)15;
     const size_t bytes = o_inst + (size_t)q.n_inst * sizeof(dh_render_instance);
-    HIP_TRY(hipEventSynchronize(f->ev_up));          // (the staging buffer is free again; at once when nothing was recorded)
-    if (f->stage.cap() < bytes || f->tables.cap() < bytes) {
-        HIP_TRY(hipDeviceSynchronize());             // (an earlier call may still read the tables)
-        TRY(f->stage.grow(bytes));
-        TRY(f->tables.alloc(f->stage.cap()));
-    }
+    TRY(f->tab.reserve(bytes));
     {
-        FitModel *mm = (FitModel *)f->stage.get();
+        FitModel *mm = (FitModel *)f->tab.stage.get();
         for (uint32_t i = 0; i < q.n_models; ++i)    // (a model no instance names may be NULL: its row is never read)
             mm[i] = q.models[i] && q.models[i]->device == f->device ? FitModel{q.models[i]->pts.get(), q.models[i]->nrm.get(), q.models[i]->n, 0}
                                                                     : FitModel{nullptr, nullptr, 0, 0};
-        memcpy(f->stage.get() + o_inst, q.inst, (size_t)q.n_inst * sizeof(dh_render_instance));
+        memcpy(f->tab.stage.get() + o_inst, q.inst, (size_t)q.n_inst * sizeof(dh_render_instance));
     }
-    a.models = (const FitModel *)f->tables.get();
-    a.inst = (const dh_render_instance *)(f->tables.get() + o_inst);
+    a.models = (const FitModel *)f->tab.dev.get();
+    a.inst = (const dh_render_instance *)(f->tab.dev.get() + o_inst);
     const size_t n_px = (size_t)q.n * q.w * q.h;
     if (!dev) {
         if (f->frames.cap() < n_px || f->out.cap() < q.n_inst) HIP_TRY(hipDeviceSynchronize());
@@ -2917,12 +2921,10 @@ static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, 
         if (f->out.cap() < q.n_inst) { TRY(f->out.grow(q.n_inst)); TRY(f->rec.alloc(f->out.cap())); }
         a.frames = f->frames.get(); a.out = f->out.get(); a.rec = f->rec.get();
     } else { a.frames = q.frames; a.out = q.out; a.rec = q.rec; }
-    HIP_TRY(hipStreamWaitEvent(s, f->ev_done, 0));      // (a call on another stream may still be reading the tables)
-    HIP_TRY(hipMemcpyAsync(f->tables.get(), f->stage.get(), bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(f->ev_up, s));
+    TRY(f->tab.upload(bytes, s));
     if (!dev) HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
     TRY(hip_step(dh_launch_fit(a, s), "k_fit"));
-    HIP_TRY(hipEventRecord(f->ev_done, s));
+    TRY(f->tab.done(s));
     if (!dev) {
         HIP_TRY(hipMemcpyAsync(q.out, a.out, (size_t)q.n_inst * sizeof(dh_render_instance), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)q.n_inst * sizeof(dh_fit_record), hipMemcpyDeviceToHost, s));
@@ -3025,14 +3027,7 @@ static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stre
     if (!q.rec) return fail(DH_EINVAL, "%s: NULL records", who);
     if (!q.model) return fail(DH_EINVAL, "%s: NULL model", who);
     if (!q.basis) return fail(DH_EINVAL, "%s: NULL basis", who);
-    if (q.n < 1 || q.n > 65535) return fail(DH_EINVAL, "%s: n = %d, expected 1 .. 65535 frames", who, q.n);
-    if (q.w < 1 || q.h < 1 || q.w > DH_RENDER_MAX_SIZE || q.h > DH_RENDER_MAX_SIZE)
-        return fail(DH_EINVAL, "%s: frame size %dx%d, expected 1 .. %d each way", who, q.w, q.h, DH_RENDER_MAX_SIZE);
-    if (q.use_cams) {
-        if (!q.cams) return fail(DH_EINVAL, "%s: NULL camera table", who);
-        if (q.cams->device != f->device) return fail(DH_EINVAL, "%s: the camera table lives on device %d, the fitter on %d", who, q.cams->device, f->device);
-        if (q.cams->n != q.n) return fail(DH_EINVAL, "%s: the camera table holds %d cameras, the batch %d frames", who, q.cams->n, q.n);
-    } else if (!q.K) return fail(DH_EINVAL, "%s: NULL K", who);
+    TRY(check_frames(q.n, q.w, q.h, q.K, q.cams, q.use_cams, f->device, "fitter", who));
     if (q.n_subjects < 1 || q.n_subjects > DH_SHAPE_MAX_SUBJECTS)
         return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u", who, q.n_subjects, DH_SHAPE_MAX_SUBJECTS);
     dh_shape_params prm;
@@ -3060,21 +3055,7 @@ static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stre
             if (sj >= q.n_subjects) return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, q.n_subjects);
             const dh_render_instance &in = q.inst[i];
             if (in.frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, q.n);
-            bool finite = std::isfinite(in.scale);
-            for (int c = 0; c < 9; ++c) finite = finite && std::isfinite(in.R[c]);
-            for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(in.t[c]);
-            if (!finite) return fail(DH_EINVAL, "%s: instance %u has a non-finite R, t or scale", who, i);
-            for (int a = 0; a < 3; ++a)
-                for (int c = a; c < 3; ++c) {
-                    const double g = ((double)in.R[3 * a] * (double)in.R[3 * c] + (double)in.R[3 * a + 1] * (double)in.R[3 * c + 1]) +
-                                     (double)in.R[3 * a + 2] * (double)in.R[3 * c + 2];
-                    if (!(fabs(g - (a == c ? 1.0 : 0.0)) <= DH_FIT_R_TOLERANCE))
-                        return fail(DH_EINVAL, "%s: instance %u has an R that is not orthonormal: (R R^T)[%d][%d] = %g", who, i, a, c, g);
-                }
-            const double extent = fabs((double)in.scale) * m->radius;
-            if (extent > DH_FIT_MAX_EXTENT) return fail(DH_EINVAL, "%s: instance %u spans %g mm from its origin (limit %g)", who, i, extent, DH_FIT_MAX_EXTENT);
-            const double field = fabs((double)in.scale) * b->largest;
-            if (field > DH_SHAPE_MAX_FIELD) return fail(DH_EINVAL, "%s: instance %u scales the basis to %g mm (limit %g)", who, i, field, DH_SHAPE_MAX_FIELD);
+            TRY(instance_refusal(dh_fit_instance_fault(in, m->radius, b->largest), in, i, m->radius, b->largest, who));
             if ((uint64_t)(++per[sj]) * m->n > DH_SHAPE_MAX_TERMS)
                 return fail(DH_EINVAL, "%s: subject %u has more than %u terms (instances times %u points)", who, sj, DH_SHAPE_MAX_TERMS, m->n);
         }
@@ -3082,8 +3063,8 @@ static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stre
 
     DeviceGuard guard(f->device);
     if (!guard.ok) return DH_EHIP;
-    TRY(fitter_init(f));
-    hipStream_t s = dev ? stream : f->s;
+    TRY(f->tab.init());
+    hipStream_t s = dev ? stream : f->tab.s;
     if (!f->shape_sums) TRY(f->shape_sums.alloc((size_t)DH_SHAPE_MAX_SUBJECTS * DH_SHAPE_STRIDE));
     ShapeArgs a;
     memset(&a, 0, sizeof a);
@@ -3256,8 +3237,7 @@ static int fit_track_check(const dh_fit_tracker *t, const void *frames, int w, i
     if (!frames) return fail(DH_EINVAL, "%s: NULL frames", who);
     if (!poses || !support) return fail(DH_EINVAL, "%s: NULL poses or support", who);
     if (!records) return fail(DH_EINVAL, "%s: NULL records", who);
-    if (w < 1 || h < 1 || w > DH_RENDER_MAX_SIZE || h > DH_RENDER_MAX_SIZE)
-        return fail(DH_EINVAL, "%s: frame size %dx%d, expected 1 .. %d each way", who, w, h, DH_RENDER_MAX_SIZE);
+    TRY(check_frame_size(w, h, who));
     return fit_params_check(in, prm, who);
 }
 // Steps 0 - 6 for every camera, on device arrays and stream s (arguments checked, device selected): three launches.
@@ -3274,7 +3254,7 @@ static int fit_track_enqueue(dh_fit_tracker *t, const uint16_t *frames, int w, i
     memset(&f, 0, sizeof f);
     f.f.frames = frames; f.f.n = t->n; f.f.w = w; f.f.h = h;
     f.f.cams = t->cams->dev.get(); f.f.models = t->models.get(); f.f.inst = t->start.get(); f.f.n_inst = (uint32_t)t->n;
-    f.f.min_points = prm.min_points; f.f.gate[0] = prm.gate[0]; f.f.gate[1] = prm.gate[1]; f.f.lam1 = 1.0 + prm.lambda;
+    fit_args_params(f.f, prm);                             // (k_fit_sched reads coarse and full per instance from sched)
     f.f.out = t->fit_out.get(); f.f.rec = t->fit_rec.get();
     f.sched = t->sched.get(); f.seed = t->seed.get();
     TRY(hip_step(dh_launch_fit_track_seed(a, s), "k_fit_track_seed"));

@@ -1,6 +1,8 @@
-// dh_fit.h -- the fit's kernel argument block, table layouts and launcher (k_fit.hip), shared with the host runtime
-// (dh_api.hip).  Not part of the ABI.  The rule the kernel implements is stated in include/depthhead_hip.h (section "fitting
-// posed models to depth frames") and DESIGN.md section 18.
+// dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip) share with the host runtime
+// (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, and the one test of whether an instance
+// may be fitted (dh_fit_instance_fault: the host's refusals and the shape kernel's skips).  The device arithmetic the kernels
+// share among themselves is in dh_fit_device.h.  Not part of the ABI.  The rules are stated in include/depthhead_hip.h (sections
+// "fitting posed models to depth frames" and after) and DESIGN.md sections 18 - 20.
 #pragma once
 #include "dh_internal.h"
 
@@ -14,6 +16,8 @@ static_assert(sizeof(dh_fit_record) == 24, "dh_fit_record: 24 bytes");
 // 2^27; times 2^20, times 2^15 points (DH_FIT_MAX_POINTS): below 2^62 < 2^63.  The header says what holds outside that.
 #define DH_FIT_S 1048576.0
 #define DH_FIT_SUMS 29              // 21 A_ab (a <= b), 6 b_a, e and the count
+// Where A_ab (a <= b) lies among sums laid out row after row as the upper triangle of a W x W matrix (the fit: 6, the shape step: 8)
+#define DH_FIT_PAIR(W, a, b) ((a) * (W) - (a) * ((a) - 1) / 2 + ((b) - (a)))
 // Points and normals are staged in LDS (24 bytes a point) up to this many points: 24 KB, which leaves six workgroups to a CU's
 // 160 KB.  Larger models stream from global memory (L2-resident: every pass reads the same 24 n bytes).
 #define DH_FIT_LDS_POINTS 1024
@@ -42,6 +46,40 @@ struct FitArgs {
 };
 
 hipError_t dh_launch_fit(const FitArgs &a, hipStream_t s);
+
+// Why an instance may not be fitted: the per-instance refusals of the header in their order, stated once for the host loops
+// (which turn the answer into their messages) and the shape kernel (which skips).  The magnitude bounds of the int64 sums, here
+// and at DH_SHAPE_*, rest on it.  radius: the model's largest |v|; largest: the basis's largest |B_k[i]| (0.0 where there is none).
+// (fit_run relies on the order of these values: it reports what comes before EXTENT, then the model's own refusals, then the rest)
+enum { DH_FIT_INST_OK = 0, DH_FIT_INST_NOT_FINITE, DH_FIT_INST_NOT_ORTHONORMAL, DH_FIT_INST_EXTENT, DH_FIT_INST_FIELD };
+struct FitInstanceFault {
+    int why;                      // DH_FIT_INST_*
+    int a, b;                     // NOT_ORTHONORMAL: the first element of R R^T (row after row, a <= b) out of tolerance
+    double g;                     //   and its value
+};
+__host__ __device__ inline FitInstanceFault dh_fit_instance_fault(const dh_render_instance &in, double radius, double largest) {
+    // Every test is made, none branches.  The tests run from the LAST refusal of the header's order to the FIRST and each
+    // failure overwrites the answer, so what is left at the end is the first failure in the header's order -- for R, the
+    // first (a, b) row after row, which the host message prints.
+    FitInstanceFault f{DH_FIT_INST_OK, 0, 0, 0.0};
+    const double sc = (double)in.scale;
+    const double as = sc < 0.0 ? -sc : sc;
+    if (!(as * largest <= DH_SHAPE_MAX_FIELD)) f.why = DH_FIT_INST_FIELD;
+    if (!(as * radius <= DH_FIT_MAX_EXTENT)) f.why = DH_FIT_INST_EXTENT;
+    // R must be near a rotation: |R x| <= 1.03 |x|
+    for (int a = 2; a >= 0; --a)
+        for (int b = 2; b >= a; --b) {
+            const double g = ((double)in.R[3 * a] * (double)in.R[3 * b] + (double)in.R[3 * a + 1] * (double)in.R[3 * b + 1]) +
+                             (double)in.R[3 * a + 2] * (double)in.R[3 * b + 2];
+            const double d = g - (a == b ? 1.0 : 0.0);
+            if (!((d < 0.0 ? -d : d) <= DH_FIT_R_TOLERANCE)) f = FitInstanceFault{DH_FIT_INST_NOT_ORTHONORMAL, a, b, g};
+        }
+    bool finite = sc - sc == 0.0;     // (x - x is 0.0 for a finite x alone)
+    for (int q = 0; q < 9; ++q) { const double r = (double)in.R[q]; finite = finite && r - r == 0.0; }
+    for (int q = 0; q < 3; ++q) { const double t = (double)in.t[q]; finite = finite && t - t == 0.0; }
+    if (!finite) f = FitInstanceFault{DH_FIT_INST_NOT_FINITE, 0, 0, 0.0};
+    return f;
+}
 
 // ---- carrying fitted poses across steps (k_fit_track.hip and k_fit's per-instance-schedule instance)
 static_assert(sizeof(dh_fit_track_params) == 56, "dh_fit_track_params: 56 bytes");
@@ -96,8 +134,7 @@ static_assert(sizeof(dh_shape_record) == 88, "dh_shape_record: 88 bytes");
 // 256 (DH_SHAPE_MAX_FIELD); with |R x| <= 1.03 |x| and |nrm| <= 1.05, |J_k| <= 1.05 * 1.03 * 256 < 277, and while |p| <= 2 p.z,
 // |r| <= 1.05 * 2 * 256 < 538: J J < 2^17, J r < 2^18, r r < 2^19.  Times 2^20, times 2^23 point-instances of one subject
 // (DH_SHAPE_MAX_TERMS): below 2^62 < 2^63.  The header says what holds outside that.
-// The words: A_kl at SHAPE_PAIR(k, l) (k <= l, rows of the 8 x 8 upper triangle whatever K is), b_k, e, count, used.
-#define DH_SHAPE_PAIR(k, l) ((k) * 8 - (k) * ((k) - 1) / 2 + ((l) - (k)))
+// The words: A_kl at DH_FIT_PAIR(8, k, l) (k <= l, rows of the 8 x 8 upper triangle whatever K is), b_k, e, count, used.
 #define DH_SHAPE_B 36
 #define DH_SHAPE_E 44
 #define DH_SHAPE_COUNT 45

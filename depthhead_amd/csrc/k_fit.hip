@@ -1,24 +1,24 @@
 // k_fit.hip -- posed point models fitted to depth frames: point-to-plane ICP with projective association (DESIGN.md section 18;
-// the rule is stated in include/depthhead_hip.h, section "fitting posed models to depth frames").  One kernel, k_fit: one
-// workgroup of 256 lanes per instance runs the whole schedule -- every pass, every step, the last pass -- inside one launch.
-//   pass   each lane strides over the model's points (staged in LDS up to DH_FIT_LDS_POINTS, else streamed), transforms,
-//          projects, gathers the depth pixel and adds the point's products to its int64 partial sums in registers; a coarse
-//          pass keeps only the 9 sums of the translation block, the last pass only e; the sums are reduced across the wave
-//          with 64-bit shuffles and one LDS atomic per wave and sum finishes them;
-//   step   after a barrier every lane solves the same system redundantly in f64 (deterministic, cheaper than a broadcast)
-//          and carries the pose (R, t: 12 doubles) in registers.
+// the rule is stated in include/depthhead_hip.h, section "fitting posed models to depth frames").  One kernel body, FIT_BLOCK,
+// in two instances (k_fit, and k_fit_sched with a schedule per instance): one workgroup of 256 lanes per instance runs the whole
+// schedule -- every pass, every step, the last pass -- inside one launch.
+//   pass   each lane strides over the model's points (staged in LDS up to DH_FIT_LDS_POINTS, else streamed), finds each point's
+//          correspondence (DH_FIT_CORRESPOND, dh_fit_device.h: transform, project, gather the depth pixel, gate, residual) and
+//          adds the point's products to its int64 partial sums in registers; a coarse pass keeps only the 9 sums of the
+//          translation block, the last pass only e; the sums are reduced across the wave with shuffles and one LDS atomic per
+//          wave and sum finishes them;
+//   step   after a barrier every lane solves the same system redundantly in f64 (fit_solve_tri, dh_fit_device.h: deterministic,
+//          cheaper than a broadcast) and carries the pose (R, t: 12 doubles) in registers.
 // f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free: bit-identical
 // run to run and to tests/fit_ref.py.
-#include "dh_device.h"
-#include "dh_fit.h"
+#include "dh_fit_device.h"
 
 #pragma clang fp contract(off)
 
 #define FIT_COARSE 0
 #define FIT_FULL 1
 #define FIT_LAST 2
-// the words of the reduction: A_ab at PAIR(a, b) (a <= b, row after row of the upper triangle), b_a, e, count
-#define FIT_PAIR(a, b) ((a) * 6 - (a) * ((a) - 1) / 2 + ((b) - (a)))
+// the words of the reduction: A_ab at DH_FIT_PAIR(6, a, b) (a <= b, row after row of the upper triangle), b_a, e, count
 #define FIT_B 21
 #define FIT_E 27
 #define FIT_COUNT 28
@@ -28,12 +28,6 @@ struct FitPose {
     double R[9];
     double t[3];
 };
-
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // One pass at `pose` with gate `gate`: the sums of MODE into s_sum (zeroed here; valid for every lane after the return).
 template <int MODE, bool STAGED>
@@ -58,28 +52,7 @@ __device__ __forceinline__ void fit_pass(const FitArgs &a, const FitModel &m, co
             v[c] = (double)(STAGED ? s_pts[c * DH_FIT_LDS_POINTS + i] : m.pts[(size_t)i * 3 + c]);
             nm[c] = (double)(STAGED ? s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] : m.nrm[(size_t)i * 3 + c]);
         }
-        const double sv0 = v[0] * scale, sv1 = v[1] * scale, sv2 = v[2] * scale;
-        double p[3], n[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            p[j] = ((pose.R[3 * j] * sv0 + pose.R[3 * j + 1] * sv1) + pose.R[3 * j + 2] * sv2) + pose.t[j];
-            n[j] = (pose.R[3 * j] * nm[0] + pose.R[3 * j + 1] * nm[1]) + pose.R[3 * j + 2] * nm[2];
-        }
-        if (!(p[2] >= 1.0)) continue;
-        const double c = (n[0] * p[0] + n[1] * p[1]) + n[2] * p[2];
-        if (!(c < 0.0)) continue;
-        double r[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) r[j] = (p[0] * K[3 * j] + p[1] * K[3 * j + 1]) + p[2] * K[3 * j + 2];
-        const double x = r[0] / r[2], y = r[1] / r[2];
-        if (!(x >= 0.0 && x < dw && y >= 0.0 && y < dh)) continue;          // (NaN fails)
-        const int px = (int)x, py = (int)y;                                 // 0 <= px < w, 0 <= py < h
-        const uint32_t di = frame[(size_t)py * a.w + px];
-        if (di == 0) continue;
-        const double d = (double)di;
-        const double gap = d - p[2];
-        if (!((gap < 0.0 ? -gap : gap) <= gate)) continue;
-        const double res = c * (d / p[2] - 1.0);
+        DH_FIT_CORRESPOND(v, nm, scale, pose.R, pose.t, K, frame, a.w, dw, dh, gate);
         if (MODE == FIT_LAST) e += (long long)((res * res) * DH_FIT_S);
         else {
             double J[6];
@@ -107,60 +80,22 @@ __device__ __forceinline__ void fit_pass(const FitArgs &a, const FitModel &m, co
         for (int ja = 0; ja < NJ; ++ja) {
 #pragma unroll
             for (int jb = ja; jb < NJ; ++jb) {
-                const long long s = wave_sum(accA[k++]);
-                if (lead) atomicAdd(&s_sum[FIT_PAIR(ja, jb)], (unsigned long long)s);
+                const unsigned long long s = wave_sum_u64((uint64_t)accA[k++]);
+                if (lead) atomicAdd(&s_sum[DH_FIT_PAIR(6, ja, jb)], s);
             }
-            const long long s = wave_sum(accB[ja]);
-            if (lead) atomicAdd(&s_sum[FIT_B + ja], (unsigned long long)s);
+            const unsigned long long s = wave_sum_u64((uint64_t)accB[ja]);
+            if (lead) atomicAdd(&s_sum[FIT_B + ja], s);
         }
     }
     if (MODE == FIT_LAST) {
-        const long long s = wave_sum(e);
-        if (lead) atomicAdd(&s_sum[FIT_E], (unsigned long long)s);
+        const unsigned long long s = wave_sum_u64((uint64_t)e);
+        if (lead) atomicAdd(&s_sum[FIT_E], s);
     }
     {
-        const long long s = wave_sum(cnt);
-        if (lead) atomicAdd(&s_sum[FIT_COUNT], (unsigned long long)s);
+        const unsigned long long s = wave_sum_u64((uint64_t)cnt);
+        if (lead) atomicAdd(&s_sum[FIT_COUNT], s);
     }
     __syncthreads();
-}
-
-// The step's system from the sums, damped, solved on its leading N x N block.  false: a pivot was not > 0.0.
-template <int N>
-__device__ __forceinline__ bool fit_solve(const unsigned long long *s_sum, double lam1, double x[6]) {
-    double A[N][N], b[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-#pragma unroll
-        for (int j = i; j < N; ++j) {
-            const double v = (double)(long long)s_sum[FIT_PAIR(i, j)] / DH_FIT_S;
-            A[i][j] = v; A[j][i] = v;
-        }
-        A[i][i] = A[i][i] * lam1 + 1e-9;
-        b[i] = (double)(long long)s_sum[FIT_B + i] / DH_FIT_S;
-    }
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const double piv = A[k][k];
-        ok = ok && piv > 0.0;                      // (uniform over the workgroup: every lane holds the same numbers)
-#pragma unroll
-        for (int i = k + 1; i < N; ++i) {
-            const double f = A[i][k] / piv;
-#pragma unroll
-            for (int j = k + 1; j < N; ++j) A[i][j] = A[i][j] - f * A[k][j];
-            b[i] = b[i] - f * b[k];
-        }
-    }
-    if (!ok) return false;                         // (what was computed past a bad pivot is dropped)
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-        double s = b[i];
-#pragma unroll
-        for (int j = i + 1; j < N; ++j) s = s - A[i][j] * x[j];
-        x[i] = s / A[i][i];
-    }
-    return true;
 }
 
 __device__ __forceinline__ bool fit_small(const double x[6], int n) {
@@ -210,7 +145,7 @@ __device__ __forceinline__ void fit_run(const FitArgs &a, const dh_render_instan
         fit_pass<FIT_COARSE, STAGED>(a, m, s_pts, frame, K, scale, pose, a.gate[0], s_sum);
         if ((uint32_t)s_sum[FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; stop = true; break; }
         double x[6] = {0, 0, 0, 0, 0, 0};
-        if (!fit_solve<3>(s_sum, a.lam1, x)) { status = DH_FIT_SINGULAR; stop = true; break; }
+        if (!fit_solve_tri<3, 6>(s_sum, FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; stop = true; break; }
 #pragma unroll
         for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
         ++steps;
@@ -220,7 +155,7 @@ __device__ __forceinline__ void fit_run(const FitArgs &a, const dh_render_instan
         fit_pass<FIT_FULL, STAGED>(a, m, s_pts, frame, K, scale, pose, a.gate[1], s_sum);
         if ((uint32_t)s_sum[FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; break; }
         double x[6];
-        if (!fit_solve<6>(s_sum, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
+        if (!fit_solve_tri<6, 6>(s_sum, FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
 #pragma unroll
         for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
         fit_cayley(pose.R, x + 3);
@@ -245,40 +180,33 @@ __device__ __forceinline__ void fit_run(const FitArgs &a, const dh_render_instan
     }
 }
 
-__global__ __launch_bounds__(DH_FIT_THREADS) void k_fit(const FitArgs a) {
-    __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];
-    __shared__ unsigned long long s_sum[32];
-    const dh_render_instance *in = a.inst + blockIdx.x;
-    const FitModel m = a.models[in->mesh];
-    if (m.n <= DH_FIT_LDS_POINTS) {
-        for (uint32_t k = threadIdx.x; k < m.n * 3; k += DH_FIT_THREADS) {
-            const uint32_t i = k / 3, c = k - i * 3;
-            s_pts[c * DH_FIT_LDS_POINTS + i] = m.pts[k];
-            s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] = m.nrm[k];
-        }
-        fit_run<true>(a, in, m, s_pts, s_sum);      // (the first pass's barriers order the staging before its reads)
-    } else fit_run<false>(a, in, m, s_pts, s_sum);
-}
+// One instance's whole fit, the body of both kernels: the model staged into LDS where it fits, then the schedule of `a` (the
+// first pass's barriers order the staging before its reads).  A macro: both kernels compile from the very tokens, and the
+// __shared__ arrays are each kernel's own.
+#define FIT_BLOCK(a)                                                                                                           \
+    __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];                                                                             \
+    __shared__ unsigned long long s_sum[32];                                                                                   \
+    const dh_render_instance *in = (a).inst + blockIdx.x;                                                                      \
+    const FitModel m = (a).models[in->mesh];                                                                                   \
+    if (m.n <= DH_FIT_LDS_POINTS) {                                                                                            \
+        for (uint32_t k = threadIdx.x; k < m.n * 3; k += DH_FIT_THREADS) {                                                     \
+            const uint32_t i = k / 3, c = k - i * 3;                                                                           \
+            s_pts[c * DH_FIT_LDS_POINTS + i] = m.pts[k];                                                                       \
+            s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] = m.nrm[k];                                                                 \
+        }                                                                                                                      \
+        fit_run<true>(a, in, m, s_pts, s_sum);                                                                                 \
+    } else fit_run<false>(a, in, m, s_pts, s_sum)
+
+__global__ __launch_bounds__(DH_FIT_THREADS) void k_fit(const FitArgs a) { FIT_BLOCK(a); }
 
 // The per-instance-schedule instance (dh_fit_tracker_step*): instance b runs (sched[b][0], sched[b][1]); a workgroup whose
 // instance has no start (uniform over the workgroup) leaves before the model is staged and writes nothing.
 __global__ __launch_bounds__(DH_FIT_THREADS) void k_fit_sched(const FitSchedArgs q) {
-    __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];
-    __shared__ unsigned long long s_sum[32];
     const uint32_t kind = q.seed[blockIdx.x] & 0xffu;
     if (kind != DH_FIT_SEED_FOREST && kind != DH_FIT_SEED_CARRIED) return;
     FitArgs a = q.f;
     a.coarse = q.sched[2 * blockIdx.x]; a.full = q.sched[2 * blockIdx.x + 1];
-    const dh_render_instance *in = a.inst + blockIdx.x;
-    const FitModel m = a.models[in->mesh];
-    if (m.n <= DH_FIT_LDS_POINTS) {
-        for (uint32_t k = threadIdx.x; k < m.n * 3; k += DH_FIT_THREADS) {
-            const uint32_t i = k / 3, c = k - i * 3;
-            s_pts[c * DH_FIT_LDS_POINTS + i] = m.pts[k];
-            s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] = m.nrm[k];
-        }
-        fit_run<true>(a, in, m, s_pts, s_sum);
-    } else fit_run<false>(a, in, m, s_pts, s_sum);
+    FIT_BLOCK(a);
 }
 
 // ------------------------------------------------------------------ launcher

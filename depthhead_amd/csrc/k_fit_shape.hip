@@ -1,50 +1,25 @@
 // k_fit_shape.hip -- one Gauss-Newton step of a model's shape coefficients over the fitted instances of each subject (DESIGN.md
 // section 20; the rule is stated in include/depthhead_hip.h, section "adapting a model's shape to a subject").  Three kernels:
 //   k_shape_accumulate  one workgroup of 256 lanes per instance; an instance that takes no part leaves at once.  Lanes stride
-//          over the model's points: the fit's one pass (transform, project, gather the depth pixel, gate, residual), then the
-//          point's K shape derivatives and its products into int64 partial sums in registers.  A single pass reads every model
-//          and basis value once, so nothing is staged in LDS; the basis lies one plane per field and axis, so a wave reads
-//          consecutive words.  The sums are reduced across the wave with 64-bit shuffles, across the four waves through LDS,
-//          and one 64-bit global atomic add per sum and workgroup lands them in the subject's row.
+//          over the model's points: the fit's correspondence (DH_FIT_CORRESPOND, dh_fit_device.h: the statement fit_pass
+//          expands too), then the point's K shape derivatives and its products into int64 partial sums in registers.  A single
+//          pass reads every model and basis value once, so nothing is staged in LDS; the basis lies one plane per field and
+//          axis, so a wave reads consecutive words.  The sums are reduced across the wave with shuffles, across the four waves
+//          through LDS, and one 64-bit global atomic add per sum and workgroup lands them in the subject's row.
 //   k_shape_clear       zeroes the rows of the call's subjects, before the accumulation on the same stream.
-//   k_shape_solve       one lane per subject: damping, elimination, back substitution, the record.
+//   k_shape_solve       one lane per subject: the fit's solve (fit_solve_tri, dh_fit_device.h) on the subject's row, the record.
 // K is a template argument (1 .. 8): every array is indexed at compile time and stays in registers.
 // f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free: bit-identical
 // run to run and to tests/shape_ref.py.
-#include "dh_device.h"
-#include "dh_fit.h"
+#include "dh_fit_device.h"
 
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ long long shape_wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // Whether instance `in` takes part: the header's per-instance refusals, decided on the device (a NaN fails each test).
 __device__ __forceinline__ bool shape_takes_part(const ShapeArgs &a, const dh_render_instance *in, uint32_t subject) {
     if (subject >= a.n_subjects) return false;                       // DH_SHAPE_SKIP among them
     if (in->frame >= (uint32_t)a.n) return false;
-    const double sc = (double)in->scale;
-    const double as = sc < 0.0 ? -sc : sc;
-    if (!(as * a.radius <= DH_FIT_MAX_EXTENT) || !(as * a.largest <= DH_SHAPE_MAX_FIELD)) return false;
-    bool ok = true;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const double t = (double)in->t[q];
-        ok = ok && (t - t == 0.0);                                   // finite
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = i; j < 3; ++j) {
-            const double g = ((double)in->R[3 * i] * (double)in->R[3 * j] + (double)in->R[3 * i + 1] * (double)in->R[3 * j + 1]) +
-                             (double)in->R[3 * i + 2] * (double)in->R[3 * j + 2];
-            const double d = g - (i == j ? 1.0 : 0.0);
-            ok = ok && ((d < 0.0 ? -d : d) <= DH_FIT_R_TOLERANCE);
-        }
-    return ok;
+    return dh_fit_instance_fault(*in, a.radius, a.largest).why == DH_FIT_INST_OK;
 }
 
 template <int NK>
@@ -78,28 +53,7 @@ __global__ __launch_bounds__(DH_SHAPE_THREADS) void k_shape_accumulate(const Sha
             v[c] = (double)a.pts[(size_t)i * 3 + c];
             nm[c] = (double)a.nrm[(size_t)i * 3 + c];
         }
-        const double sv0 = v[0] * scale, sv1 = v[1] * scale, sv2 = v[2] * scale;
-        double p[3], n[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            p[j] = ((R[3 * j] * sv0 + R[3 * j + 1] * sv1) + R[3 * j + 2] * sv2) + t[j];
-            n[j] = (R[3 * j] * nm[0] + R[3 * j + 1] * nm[1]) + R[3 * j + 2] * nm[2];
-        }
-        if (!(p[2] >= 1.0)) continue;
-        const double c = (n[0] * p[0] + n[1] * p[1]) + n[2] * p[2];
-        if (!(c < 0.0)) continue;
-        double r[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) r[j] = (p[0] * K[3 * j] + p[1] * K[3 * j + 1]) + p[2] * K[3 * j + 2];
-        const double x = r[0] / r[2], y = r[1] / r[2];
-        if (!(x >= 0.0 && x < dw && y >= 0.0 && y < dh)) continue;          // (NaN fails)
-        const int px = (int)x, py = (int)y;                                 // 0 <= px < w, 0 <= py < h
-        const uint32_t di = frame[(size_t)py * a.w + px];
-        if (di == 0) continue;
-        const double d = (double)di;
-        const double gap = d - p[2];
-        if (!((gap < 0.0 ? -gap : gap) <= gate)) continue;
-        const double res = c * (d / p[2] - 1.0);
+        DH_FIT_CORRESPOND(v, nm, scale, R, t, K, frame, a.w, dw, dh, gate);
         double J[NK];
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
@@ -129,13 +83,13 @@ __global__ __launch_bounds__(DH_SHAPE_THREADS) void k_shape_accumulate(const Sha
         for (int k = 0; k < NK; ++k) {
 #pragma unroll
             for (int l = k; l < NK; ++l) {
-                const long long s = shape_wave_sum(accA[q++]);
-                if (lead) s_part[wave][DH_SHAPE_PAIR(k, l)] = s;
+                const long long s = (long long)wave_sum_u64((uint64_t)accA[q++]);
+                if (lead) s_part[wave][DH_FIT_PAIR(8, k, l)] = s;
             }
-            const long long s = shape_wave_sum(accB[k]);
+            const long long s = (long long)wave_sum_u64((uint64_t)accB[k]);
             if (lead) s_part[wave][DH_SHAPE_B + k] = s;
         }
-        const long long se = shape_wave_sum(e), sc = shape_wave_sum(cnt);
+        const long long se = (long long)wave_sum_u64((uint64_t)e), sc = (long long)wave_sum_u64((uint64_t)cnt);
         if (lead) { s_part[wave][DH_SHAPE_E] = se; s_part[wave][DH_SHAPE_COUNT] = sc; }
     }
     __syncthreads();
@@ -179,44 +133,7 @@ __global__ __launch_bounds__(64) void k_shape_solve(const ShapeArgs a) {
     rec.sum_r2_fixed = (int64_t)row[DH_SHAPE_E];
     rec.status = DH_SHAPE_OK;
     if (count < (long long)a.min_points) rec.status = DH_SHAPE_FEW_POINTS;
-    else {
-        double A[NK][NK], b[NK], x[NK];
-#pragma unroll
-        for (int i = 0; i < NK; ++i) {
-#pragma unroll
-            for (int j = i; j < NK; ++j) {
-                const double v = (double)(long long)row[DH_SHAPE_PAIR(i, j)] / DH_FIT_S;
-                A[i][j] = v; A[j][i] = v;
-            }
-            A[i][i] = A[i][i] * a.lam1 + 1e-9;
-            b[i] = (double)(long long)row[DH_SHAPE_B + i] / DH_FIT_S;
-        }
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const double piv = A[k][k];
-            ok = ok && piv > 0.0;
-#pragma unroll
-            for (int i = k + 1; i < NK; ++i) {
-                const double f = A[i][k] / piv;
-#pragma unroll
-                for (int j = k + 1; j < NK; ++j) A[i][j] = A[i][j] - f * A[k][j];
-                b[i] = b[i] - f * b[k];
-            }
-        }
-        if (!ok) rec.status = DH_SHAPE_SINGULAR;                      // (what was computed past a bad pivot is dropped)
-        else {
-#pragma unroll
-            for (int i = NK - 1; i >= 0; --i) {
-                double s = b[i];
-#pragma unroll
-                for (int j = i + 1; j < NK; ++j) s = s - A[i][j] * x[j];
-                x[i] = s / A[i][i];
-            }
-#pragma unroll
-            for (int k = 0; k < NK; ++k) rec.delta[k] = x[k];
-        }
-    }
+    else if (!fit_solve_tri<NK, 8>(row, DH_SHAPE_B, a.lam1, rec.delta)) rec.status = DH_SHAPE_SINGULAR;
     a.rec[sj] = rec;
 }
 

@@ -2,9 +2,9 @@
 record and every byte of the state after every step -- no tolerance.  Three cameras (one with a matrix that is no pinhole)
 over six steps of tests/fit_track_scenes.py's moving head, with a head gone and back, an absent camera and invalid
 detections; the whole step behind a synth forest, whose device poses and support are fed to the restatement; 96x96 frames
-with models of 1 and 257 points; every start kind in one launch; the host calls against their _device twins on a side stream;
-outputs between guard bands through skewed pointers; reset of one camera and of all; two runs of one sequence; one step
-captured in a graph; the refusals that need a tracker."""
+with models of 1, 257 and 1025 points (the last streamed, not staged in LDS); every start kind in one launch; the host calls
+against their _device twins on a side stream; outputs between guard bands through skewed pointers; reset of one camera and of
+all; two runs of one sequence; one step captured in a graph; the refusals that need a tracker."""
 import ctypes as C
 import functools
 
@@ -59,6 +59,9 @@ def model_points(kind):
     if kind == "one":
         front = int(np.argmin(v2[:, 2]))
         return v2[front:front + 1].copy(), n2[front:front + 1].copy()
+    if kind == "1025":                                                # the first model past the fit's LDS staging budget of 1024
+        v4, _, n4 = fs.head(4)
+        return v4[:1025].copy(), n4[:1025].copy()
     v3, _, n3 = fs.head(3)
     return v3[:257].copy(), n3[:257].copy()
 
@@ -158,7 +161,7 @@ def test_whole_step_behind_a_synth_forest(gpu, radius, conf):
     assert all(s[2] == ft.ABSENT for s in seen[2:4])
 
 
-@pytest.mark.parametrize("kind,points", [("one", 1), ("257", 257)])
+@pytest.mark.parametrize("kind,points", [("one", 1), ("257", 257), ("1025", 1025)])
 def test_96x96_one_camera(gpu, kind, points):
     _, _, angles = gpu
     frames, K, pos, Rs, poses = sc.sequence(96, 96, 8010, steps=3)
