@@ -105,6 +105,16 @@ SHAPE_MAX_GATE = 256       # DH_SHAPE_MAX_GATE (mm)
 SHAPE_MAX_TERMS = 1 << 23  # DH_SHAPE_MAX_TERMS
 
 
+# dh_view_instance / dh_view_fit_record: one world-posed model seen by several cameras, and what its fit reports (dh_fit_depth_views*)
+VIEW_INSTANCE_DTYPE = np.dtype([("first_cam", "<u4"), ("model", "<u4"), ("views", "<u8"), ("R", "<f4", (9,)), ("t", "<f4", (3,)),
+                                ("scale", "<f4"), ("flags", "<u4")], align=True)
+assert VIEW_INSTANCE_DTYPE.itemsize == 72
+VIEW_FIT_RECORD_DTYPE = np.dtype([("points", "<u4"), ("steps", "<u4"), ("status", "<u4"), ("reserved", "<u4"), ("sum_r2_fixed", "<i8"),
+                                  ("views_used", "<u8")], align=True)
+assert VIEW_FIT_RECORD_DTYPE.itemsize == 32
+FIT_VIEW_TOLERANCE = 0.001  # DH_FIT_VIEW_TOLERANCE
+
+
 class ShapeParams(C.Structure):
     """dh_shape_params (`lam` is the header's `lambda`)"""
     _fields_ = [("gate", C.c_double), ("lam", C.c_double), ("min_points", C.c_uint32), ("reserved0", C.c_uint32),
@@ -171,6 +181,7 @@ EXPORTS = [
     "dh_fit_tracker_step_device",
     "dh_fit_basis_create", "dh_fit_basis_destroy", "dh_fit_basis_info", "dh_shape_params_default", "dh_fit_shape", "dh_fit_shape_cameras",
     "dh_fit_shape_device", "dh_fit_shape_cameras_device",
+    "dh_fit_views_create", "dh_fit_views_destroy", "dh_fit_views_info", "dh_fit_depth_views", "dh_fit_depth_views_device",
 ]
 
 

@@ -2816,6 +2816,9 @@ struct dh_fitter {
     Buf<dh_render_instance> shape_inst;      // host shape calls
     Buf<uint32_t> shape_subj;
     Buf<dh_shape_record> shape_rec;
+    Buf<dh_view_instance> view_out;          // host multi-view calls
+    Buf<dh_view_fit_record> view_rec;
+    std::vector<unsigned char> view_cmp;     // a captured multi-view call's tables, to be compared with the staged ones
     CallTables tab;                          // models | instances (last: its stream and events go before any buffer)
 };
 static int fitter_create_(int device, dh_fitter **out) { return create_owner(device, out, "dh_fitter_create"); }
@@ -2947,6 +2950,174 @@ static int fit_depth_device_(dh_fitter *f, const uint16_t *frames, int n, int w,
 static int fit_depth_cameras_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models,
                                      const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream) {
     return fit_run(f, FitReq{frames, n, w, h, nullptr, c, true, models, n_models, instances, n_instances, params, out, records}, true, (hipStream_t)stream, "dh_fit_depth_cameras_device");
+}
+
+// ------------------------------------------------------------------ fitting one model to several views
+// A view table: one world-to-camera transform per camera of a camera table, on that table's device, immutable.
+struct dh_fit_views {
+    int device = 0;
+    int n = 0;
+    const dh_cameras *cams = nullptr;        // the table it is bound to (which outlives it)
+    Buf<FitView> dev;
+};
+static int fit_views_create_(const dh_cameras *c, const float *V, const float *u, dh_fit_views **out) {
+    if (!out) return fail(DH_EINVAL, "dh_fit_views_create: NULL argument");
+    *out = nullptr;
+    if (!c || !V || !u) return fail(DH_EINVAL, "dh_fit_views_create: NULL argument");
+    std::vector<FitView> host((size_t)c->n);
+    for (int i = 0; i < c->n; ++i) {
+        FitView &v = host[(size_t)i];
+        memcpy(v.V, V + (size_t)i * 9, sizeof v.V);
+        memcpy(v.u, u + (size_t)i * 3, sizeof v.u);
+        for (int q = 0; q < 9; ++q) if (!std::isfinite(v.V[q])) return fail(DH_EINVAL, "dh_fit_views_create: view %d has a non-finite V or u", i);
+        for (int q = 0; q < 3; ++q) if (!std::isfinite(v.u[q])) return fail(DH_EINVAL, "dh_fit_views_create: view %d has a non-finite V or u", i);
+        for (int a = 0; a < 3; ++a)
+            for (int b = a; b < 3; ++b) {
+                const double g = ((double)v.V[3 * a] * (double)v.V[3 * b] + (double)v.V[3 * a + 1] * (double)v.V[3 * b + 1]) +
+                                 (double)v.V[3 * a + 2] * (double)v.V[3 * b + 2];
+                if (!(fabs(g - (a == b ? 1.0 : 0.0)) <= DH_FIT_VIEW_TOLERANCE))
+                    return fail(DH_EINVAL, "dh_fit_views_create: view %d has a V that is not orthonormal: (V V^T)[%d][%d] = %g", i, a, b, g);
+            }
+    }
+    std::unique_ptr<dh_fit_views> v(new dh_fit_views);
+    v->device = c->device; v->n = c->n; v->cams = c;
+    DeviceGuard guard(c->device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(v->dev.alloc(host.size()));
+    HIP_TRY(hipMemcpy(v->dev.get(), host.data(), host.size() * sizeof(FitView), hipMemcpyHostToDevice));
+    *out = v.release();
+    return DH_OK;
+}
+static int fit_views_destroy_(dh_fit_views *v) {
+    if (!v) return DH_OK;
+    DeviceGuard guard(v->device);
+    delete v;
+    return DH_OK;
+}
+static int fit_views_info_(const dh_fit_views *v, int *n, int *device) {
+    if (!v) return fail(DH_EINVAL, "dh_fit_views_info: NULL view table");
+    if (n) *n = v->n;
+    if (device) *device = v->device;
+    return DH_OK;
+}
+
+// One multi-view fit call.  dev: frames / out / records are device pointers and `stream` the caller's; else host pointers.
+struct FitViewsReq {
+    const uint16_t *frames; int w, h;
+    const dh_fit_views *views;
+    const dh_fit_model *const *models; uint32_t n_models;
+    const dh_view_instance *inst; uint32_t n_inst;
+    const dh_fit_params *prm;
+    dh_view_instance *out; dh_view_fit_record *rec;
+};
+static int fit_views_run(dh_fitter *f, const FitViewsReq &q, bool dev, hipStream_t stream, const char *who) {
+    // ---- refusals: all of them before anything is allocated or launched
+    if (!f) return fail(DH_EINVAL, "%s: NULL fitter", who);
+    if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!q.out || !q.rec) return fail(DH_EINVAL, "%s: NULL output", who);
+    if (!q.views) return fail(DH_EINVAL, "%s: NULL view table", who);
+    if (q.views->device != f->device) return fail(DH_EINVAL, "%s: the view table lives on device %d, the fitter on %d", who, q.views->device, f->device);
+    const int n = q.views->n;
+    TRY(check_frames(n, q.w, q.h, nullptr, q.views->cams, true, f->device, "fitter", who));
+    dh_fit_params prm;
+    TRY(fit_params_check(q.prm, &prm, who));
+    if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
+    if (q.n_inst && !q.models) return fail(DH_EINVAL, "%s: NULL models", who);
+    if (q.n_inst > 0x7fffffffu) return fail(DH_EINVAL, "%s: too many instances", who);
+    for (uint32_t i = 0; i < q.n_inst; ++i) {
+        const dh_view_instance &in = q.inst[i];
+        if (in.views == 0) return fail(DH_EINVAL, "%s: instance %u is seen by no view", who, i);
+        const uint64_t last = (uint64_t)in.first_cam + (63u - (unsigned)__builtin_clzll(in.views));
+        if (last >= (uint64_t)n) return fail(DH_EINVAL, "%s: instance %u names camera %llu of %d", who, i, (unsigned long long)last, n);
+        if (in.model >= q.n_models) return fail(DH_EINVAL, "%s: instance %u names model %u of %u", who, i, in.model, q.n_models);
+        dh_render_instance world;                    // the world pose, as dh_fit_instance_fault reads an instance
+        memset(&world, 0, sizeof world);
+        memcpy(world.R, in.R, sizeof world.R); memcpy(world.t, in.t, sizeof world.t);
+        world.scale = in.scale;
+        const dh_fit_model *m = q.models[in.model];
+        const double radius = m ? m->radius : 0.0;   // (the refusals of the model itself stand between those of R and of the extent)
+        const FitInstanceFault fault = dh_fit_instance_fault(world, radius, 0.0);
+        if (fault.why != DH_FIT_INST_OK && fault.why < DH_FIT_INST_EXTENT) return instance_refusal(fault, world, i, radius, 0.0, who);
+        if (!m) return fail(DH_EINVAL, "%s: model %u is NULL", who, in.model);
+        if (m->device != f->device) return fail(DH_EINVAL, "%s: model %u lives on device %d, the fitter on %d", who, in.model, m->device, f->device);
+        if (fault.why != DH_FIT_INST_OK) return instance_refusal(fault, world, i, radius, 0.0, who);
+        const uint64_t terms = (uint64_t)__builtin_popcountll(in.views) * m->n;
+        if (terms > DH_FIT_MAX_POINTS)
+            return fail(DH_EINVAL, "%s: instance %u sums %llu terms (%d views of %u points), above %u", who, i, (unsigned long long)terms,
+                        __builtin_popcountll(in.views), m->n, DH_FIT_MAX_POINTS);
+    }
+    if (q.n_inst == 0) return DH_OK;
+
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(f->tab.init());
+    hipStream_t s = dev ? stream : f->tab.s;
+    // A stream that is being captured takes the kernel alone, and nothing else is asked of the runtime while it captures: the
+    // tables must be the ones the fitter's last call uploaded (an eager call with the same models and instances), else DH_ESTATE.
+    bool capturing = false;
+    if (dev) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing(s, &cs));
+        capturing = cs != hipStreamCaptureStatusNone;
+    }
+    FitViewsArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = n; a.w = q.w; a.h = q.h;
+    a.cams = q.views->cams->dev.get();
+    a.views = q.views->dev.get();
+    a.n_inst = q.n_inst;
+    a.coarse = prm.coarse_iterations; a.full = prm.iterations; a.min_points = prm.min_points;
+    a.gate[0] = prm.gate[0]; a.gate[1] = prm.gate[1];
+    a.lam1 = 1.0 + prm.lambda;
+    // ---- the call's tables: one staging buffer, one upload
+    const size_t o_inst = ((size_t)q.n_models * sizeof(FitModel) + 15) & ~(size_t)15;
+    const size_t bytes = o_inst + (size_t)q.n_inst * sizeof(dh_view_instance);
+    auto fill = [&](unsigned char *dst) {            // every one of `bytes` bytes is written
+        FitModel *mm = (FitModel *)dst;
+        for (uint32_t i = 0; i < q.n_models; ++i)    // (a model no instance names may be NULL: its row is never read)
+            mm[i] = q.models[i] && q.models[i]->device == f->device ? FitModel{q.models[i]->pts.get(), q.models[i]->nrm.get(), q.models[i]->n, 0}
+                                                                    : FitModel{nullptr, nullptr, 0, 0};
+        memset(dst + (size_t)q.n_models * sizeof(FitModel), 0, o_inst - (size_t)q.n_models * sizeof(FitModel));
+        memcpy(dst + o_inst, q.inst, (size_t)q.n_inst * sizeof(dh_view_instance));
+    };
+    if (capturing) {
+        f->view_cmp.resize(bytes);                   // (the only path that builds the tables beside the staging buffer)
+        fill(f->view_cmp.data());
+        if (f->tab.stage.cap() < bytes || memcmp(f->tab.stage.get(), f->view_cmp.data(), bytes) != 0)
+            return fail(DH_ESTATE, "%s: the stream is being captured and the fitter's tables are not those of this call (run the call once before the capture)", who);
+    } else {
+        TRY(f->tab.reserve(bytes));
+        fill(f->tab.stage.get());
+    }
+    a.models = (const FitModel *)f->tab.dev.get();
+    a.inst = (const dh_view_instance *)(f->tab.dev.get() + o_inst);
+    const size_t n_px = (size_t)n * q.w * q.h;
+    if (!dev) {
+        if (f->frames.cap() < n_px || f->view_out.cap() < q.n_inst) HIP_TRY(hipDeviceSynchronize());
+        TRY(f->frames.grow(n_px));
+        if (f->view_out.cap() < q.n_inst) { TRY(f->view_out.grow(q.n_inst)); TRY(f->view_rec.alloc(f->view_out.cap())); }
+        a.frames = f->frames.get(); a.out = f->view_out.get(); a.rec = f->view_rec.get();
+    } else { a.frames = q.frames; a.out = q.out; a.rec = q.rec; }
+    if (capturing) return hip_step(dh_launch_fit_views(a, s), "k_fit_views");
+    TRY(f->tab.upload(bytes, s));
+    if (!dev) HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    TRY(hip_step(dh_launch_fit_views(a, s), "k_fit_views"));
+    TRY(f->tab.done(s));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(q.out, a.out, (size_t)q.n_inst * sizeof(dh_view_instance), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)q.n_inst * sizeof(dh_view_fit_record), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return DH_OK;
+}
+static int fit_depth_views_(dh_fitter *f, const uint16_t *frames, int w, int h, const dh_fit_views *views, const dh_fit_model *const *models, uint32_t n_models,
+                            const dh_view_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_view_instance *out, dh_view_fit_record *records) {
+    return fit_views_run(f, FitViewsReq{frames, w, h, views, models, n_models, instances, n_instances, params, out, records}, false, nullptr, "dh_fit_depth_views");
+}
+static int fit_depth_views_device_(dh_fitter *f, const uint16_t *frames, int w, int h, const dh_fit_views *views, const dh_fit_model *const *models, uint32_t n_models,
+                                   const dh_view_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_view_instance *out, dh_view_fit_record *records,
+                                   void *stream) {
+    return fit_views_run(f, FitViewsReq{frames, w, h, views, models, n_models, instances, n_instances, params, out, records}, true, (hipStream_t)stream, "dh_fit_depth_views_device");
 }
 
 // ------------------------------------------------------------------ adapting a model's shape to a subject
@@ -3437,6 +3608,11 @@ DH_API(fit_depth, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, co
 DH_API(fit_depth_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records), (f, frames, n, w, h, c, models, n_models, instances, n_instances, params, out, records))
 DH_API(fit_depth_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream), (f, frames, n, w, h, K, models, n_models, instances, n_instances, params, out, records, stream))
 DH_API(fit_depth_cameras_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream), (f, frames, n, w, h, c, models, n_models, instances, n_instances, params, out, records, stream))
+DH_API(fit_views_create, (const dh_cameras *c, const float *V, const float *u, dh_fit_views **out), (c, V, u, out))
+DH_API(fit_views_destroy, (dh_fit_views *v), (v))
+DH_API(fit_views_info, (const dh_fit_views *v, int *n, int *device), (v, n, device))
+DH_API(fit_depth_views, (dh_fitter *f, const uint16_t *frames, int w, int h, const dh_fit_views *views, const dh_fit_model *const *models, uint32_t n_models, const dh_view_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_view_instance *out, dh_view_fit_record *records), (f, frames, w, h, views, models, n_models, instances, n_instances, params, out, records))
+DH_API(fit_depth_views_device, (dh_fitter *f, const uint16_t *frames, int w, int h, const dh_fit_views *views, const dh_fit_model *const *models, uint32_t n_models, const dh_view_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_view_instance *out, dh_view_fit_record *records, void *stream), (f, frames, w, h, views, models, n_models, instances, n_instances, params, out, records, stream))
 DH_API(fit_basis_create, (const float *fields, uint32_t n, uint32_t n_fields, int device, dh_fit_basis **out), (fields, n, n_fields, device, out))
 DH_API(fit_basis_destroy, (dh_fit_basis *b), (b))
 DH_API(fit_basis_info, (const dh_fit_basis *b, uint32_t *n, uint32_t *n_fields, double *largest), (b, n, n_fields, largest))

@@ -163,3 +163,41 @@ struct ShapeArgs {
 hipError_t dh_launch_shape_clear(const ShapeArgs &a, hipStream_t s);       // rows 0 .. n_subjects - 1 of a.sums
 hipError_t dh_launch_shape_accumulate(const ShapeArgs &a, hipStream_t s);
 hipError_t dh_launch_shape_solve(const ShapeArgs &a, hipStream_t s);
+
+// ---- fitting one model to several views (k_fit_views.hip)
+static_assert(sizeof(dh_view_instance) == 72, "dh_view_instance: 72 bytes");
+static_assert(sizeof(dh_view_fit_record) == 32, "dh_view_fit_record: 32 bytes");
+// DH_FIT_VIEW_TOLERANCE (the header: 0.001) and the magnitudes of the sums.  G = V V^T is symmetric and |G - I| <= e per element
+// gives ||G - I||_2 <= 3 e (a row's absolute sum), so |V y|^2 = y^T V^T V y <= (1 + 3 e) |y|^2 (V^T V has G's eigenvalues), and
+// the same for V^T.  With e_R = DH_FIT_R_TOLERANCE = 0.02: |R_w x| <= sqrt(1.06) |x| < 1.0296 |x| (the fit's 1.03); with e_V =
+// 0.001: |V y| <= sqrt(1.003) |y| < 1.0015 |y|.  The composite R_v = V R_w (its nine elements rounded in f64: 1e-15 relative)
+// therefore has |R_v x| <= 1.0296 * 1.0015 |x| < 1.032 |x|: THE ONE CONSTANT THAT CHANGES is 1.03 -> 1.032.  What the fit derives
+// from it still holds with its own constants: |nrm| <= 1.032 * 1.01 < 1.043 <= 1.05; |q| = |R_v sv| <= 1.032 * 4096; |m| <= |q| |nrm|
+// <= 1.032 * 1.043 * 4096 < 1.077 * 4096; the world row J = (V^T nrm, V^T m) has |J_a| <= 1.0015 * 1.077 * 4096 < 1.079 * 4096 <=
+// 1.09 * 4096; and |r| <= 1.05 * (|p| / p.z) * gate per camera as before.  So while |p| <= 2 p.z in every view, J J <= (1.09 *
+// 4096)^2 < 2^24.3, J r <= 1.09 * 4096 * 1.05 * 2 * 4096 < 2^25.2 and r r <= (1.05 * 2 * 4096)^2 < 2^26.2: every product below
+// 2^27, times 2^20, times at most DH_FIT_MAX_POINTS = 2^15 (view, point) terms of an instance (refused above that): below 2^62.
+// A tolerance of 0.02 for V as well would give 1.0296^2 = 1.06 |x| and 1.06 * 1.01 = 1.071 > 1.05 for |nrm|: hence a small one.
+static_assert(DH_FIT_VIEW_TOLERANCE <= 0.001, "the magnitude argument above is made for a tolerance of at most 0.001");
+
+// One camera of a dh_fit_views table: camera-space point = V x + u for a world point x.
+struct FitView {
+    float V[9];                   // row-major
+    float u[3];                   // mm
+};
+
+struct FitViewsArgs {
+    const uint16_t *frames;       // [n][h][w]: frame c is camera c's
+    int n, w, h;
+    const DhCam *cams;            // [n]
+    const FitView *views;         // [n]
+    const FitModel *models;
+    const dh_view_instance *inst;
+    uint32_t n_inst;
+    uint32_t coarse, full, min_points;
+    double gate[2];
+    double lam1;                  // 1.0 + lambda (computed on the host: one f64 sum)
+    dh_view_instance *out;        // [n_inst]
+    dh_view_fit_record *rec;      // [n_inst]
+};
+hipError_t dh_launch_fit_views(const FitViewsArgs &a, hipStream_t s);

@@ -1,0 +1,242 @@
+// k_fit_views.hip -- one posed model fitted to the depth frames of several cameras at once (the rule is
+// stated in include/depthhead_hip.h, section "fitting one model to several views").  k_fit's structure with one loop more: one
+// workgroup of 256 lanes per instance runs the whole schedule -- every pass, every step, the last pass -- inside one launch, and
+// a pass walks the instance's views (outer loop, uniform over the workgroup) and for each view the model's points (inner loop).
+//   view   every lane composes the view's camera pose (R_v, t_v) = (V R_w, V t_w + u) from the world pose it carries, once per
+//          view and pass; the composite, V and K are the same in every lane and are moved to scalar registers (uni), so the
+//          point loop holds no more vector registers than k_fit's;
+//   point  DH_FIT_CORRESPOND as it stands at (scale, R_v, t_v, K_c, frame c); the row of a point that passed is turned back
+//          into the world frame, J = (V^T n, V^T m), and its products go to the lane's int64 partial sums, which run on over
+//          the views; one wave reduction and one LDS atomic per wave and sum finish a pass, as in k_fit;
+//   step   every lane solves the same system redundantly in f64 (fit_solve_tri) and carries the world pose in registers.
+// f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free: bit-identical
+// run to run and to tests/view_fit_ref.py.  With one view, V = I and u = 0 every sum equals k_fit's.
+#include "dh_fit_device.h"
+
+#pragma clang fp contract(off)
+
+#define FV_COARSE 0
+#define FV_FULL 1
+#define FV_LAST 2
+// the words of the reduction: k_fit's 29 (A_ab at DH_FIT_PAIR(6, a, b), b_a, e, count) and the mask of the views that were used
+#define FV_B 21
+#define FV_E 27
+#define FV_COUNT 28
+#define FV_USED 29
+static_assert(FV_COUNT + 1 == DH_FIT_SUMS, "29 words and the mask");
+
+struct FitViewsPose {
+    double R[9];
+    double t[3];
+};
+
+// A value that every lane of the workgroup holds alike, moved to scalar registers.
+__device__ __forceinline__ double uni(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// One pass at the world pose `pose` with gate `gate` over the views of `mask` (bit k: camera first_cam + k): the sums of MODE
+// into s_sum (zeroed here; valid for every lane after the return).
+template <int MODE, bool STAGED>
+__device__ __forceinline__ void fit_views_pass(const FitViewsArgs &a, const FitModel &m, const float *s_pts, uint32_t first_cam, uint64_t mask,
+                                               double scale, const FitViewsPose &pose, double gate, unsigned long long *s_sum) {
+    constexpr int NJ = MODE == FV_COARSE ? 3 : MODE == FV_FULL ? 6 : 0;
+    constexpr int NA = NJ * (NJ + 1) / 2;
+    long long accA[NA > 0 ? NA : 1], accB[NJ > 0 ? NJ : 1];
+#pragma unroll
+    for (int k = 0; k < (NA > 0 ? NA : 1); ++k) accA[k] = 0;
+#pragma unroll
+    for (int k = 0; k < (NJ > 0 ? NJ : 1); ++k) accB[k] = 0;
+    long long e = 0, cnt = 0;
+    uint64_t used = 0;                             // (uniform over the wave)
+    __syncthreads();                               // every lane has read the sums of the pass before
+    if (threadIdx.x < 32) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    const double dw = (double)a.w, dh = (double)a.h;
+    for (uint64_t rest = mask; rest; rest &= rest - 1) {
+        const uint32_t bit = (uint32_t)__builtin_ctzll(rest);
+        const uint32_t cam = first_cam + bit;      // < a.n: the host refused the call otherwise
+        const uint16_t *frame = a.frames + (size_t)cam * a.h * a.w;
+        const FitView *vw = a.views + cam;
+        double V[9], K[9], Rv[9], tv[3];
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            V[q] = uni((double)vw->V[q]);
+            K[q] = uni((double)a.cams[cam].k[q]);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                Rv[3 * i + j] = uni((V[3 * i] * pose.R[j] + V[3 * i + 1] * pose.R[3 + j]) + V[3 * i + 2] * pose.R[6 + j]);
+            tv[i] = uni(((V[3 * i] * pose.t[0] + V[3 * i + 1] * pose.t[1]) + V[3 * i + 2] * pose.t[2]) + (double)vw->u[i]);
+        }
+        const long long before = cnt;
+        for (uint32_t i = threadIdx.x; i < m.n; i += DH_FIT_THREADS) {
+            double v[3], nm[3];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                v[ax] = (double)(STAGED ? s_pts[ax * DH_FIT_LDS_POINTS + i] : m.pts[(size_t)i * 3 + ax]);
+                nm[ax] = (double)(STAGED ? s_pts[(3 + ax) * DH_FIT_LDS_POINTS + i] : m.nrm[(size_t)i * 3 + ax]);
+            }
+            DH_FIT_CORRESPOND(v, nm, scale, Rv, tv, K, frame, a.w, dw, dh, gate);
+            if (MODE == FV_LAST) e += (long long)((res * res) * DH_FIT_S);
+            else {
+                double J[6];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) J[j] = (V[j] * n[0] + V[3 + j] * n[1]) + V[6 + j] * n[2];
+                if (MODE == FV_FULL) {
+                    const double q0 = p[0] - tv[0], q1 = p[1] - tv[1], q2 = p[2] - tv[2];
+                    const double m0 = q1 * n[2] - q2 * n[1];
+                    const double m1 = q2 * n[0] - q0 * n[2];
+                    const double m2 = q0 * n[1] - q1 * n[0];
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) J[3 + j] = (V[j] * m0 + V[3 + j] * m1) + V[6 + j] * m2;
+                }
+                int k = 0;
+#pragma unroll
+                for (int ja = 0; ja < NJ; ++ja) {
+#pragma unroll
+                    for (int jb = ja; jb < NJ; ++jb) accA[k++] += (long long)((J[ja] * J[jb]) * DH_FIT_S);
+                    accB[ja] += (long long)((J[ja] * res) * DH_FIT_S);
+                }
+            }
+            cnt += 1;
+        }
+        if (MODE == FV_LAST && __ballot(cnt != before) != 0) used |= 1ull << bit;
+    }
+    const bool lead = (threadIdx.x & 63) == 0;
+    {
+        int k = 0;
+#pragma unroll
+        for (int ja = 0; ja < NJ; ++ja) {
+#pragma unroll
+            for (int jb = ja; jb < NJ; ++jb) {
+                const unsigned long long s = wave_sum_u64((uint64_t)accA[k++]);
+                if (lead) atomicAdd(&s_sum[DH_FIT_PAIR(6, ja, jb)], s);
+            }
+            const unsigned long long s = wave_sum_u64((uint64_t)accB[ja]);
+            if (lead) atomicAdd(&s_sum[FV_B + ja], s);
+        }
+    }
+    if (MODE == FV_LAST) {
+        const unsigned long long s = wave_sum_u64((uint64_t)e);
+        if (lead) {
+            atomicAdd(&s_sum[FV_E], s);
+            atomicOr(&s_sum[FV_USED], (unsigned long long)used);
+        }
+    }
+    {
+        const unsigned long long s = wave_sum_u64((uint64_t)cnt);
+        if (lead) atomicAdd(&s_sum[FV_COUNT], s);
+    }
+    __syncthreads();
+}
+
+// (fit_small and fit_cayley of k_fit.hip, which keeps them to itself: the step's early exit and R = C R in the header's order)
+__device__ __forceinline__ bool fit_views_small(const double x[6], int n) {
+    bool small = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+        if (i < n) small = small && ((x[i] < 0.0 ? -x[i] : x[i]) < 1e-6);
+    return small;
+}
+__device__ __forceinline__ void fit_views_cayley(double R[9], const double w[3]) {
+    const double a0 = w[0] / 2.0, a1 = w[1] / 2.0, a2 = w[2] / 2.0;
+    const double q = (a0 * a0 + a1 * a1) + a2 * a2;
+    const double s = 1.0 + q, d = 1.0 - q;
+    const double u0 = 2.0 * a0, u1 = 2.0 * a1, u2 = 2.0 * a2;
+    double C[9];
+    C[0] = (d + u0 * a0) / s;  C[1] = (u0 * a1 - u2) / s; C[2] = (u0 * a2 + u1) / s;
+    C[3] = (u1 * a0 + u2) / s; C[4] = (d + u1 * a1) / s;  C[5] = (u1 * a2 - u0) / s;
+    C[6] = (u2 * a0 - u1) / s; C[7] = (u2 * a1 + u0) / s; C[8] = (d + u2 * a2) / s;
+    double o[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = (C[3 * i] * R[j] + C[3 * i + 1] * R[3 + j]) + C[3 * i + 2] * R[6 + j];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = o[i];
+}
+
+template <bool STAGED>
+__device__ __forceinline__ void fit_views_run(const FitViewsArgs &a, const dh_view_instance *in, const FitModel &m, const float *s_pts,
+                                              unsigned long long *s_sum) {
+    const uint32_t first_cam = in->first_cam;
+    const uint64_t views = in->views;
+    const uint64_t mask = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(views >> 32)) << 32) |
+                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)views);
+    FitViewsPose pose;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) pose.R[q] = (double)in->R[q];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) pose.t[q] = (double)in->t[q];
+    const double scale = (double)in->scale;
+    uint32_t steps = 0, status = DH_FIT_OK;
+    bool stop = false;
+    for (uint32_t it = 0; it < a.coarse; ++it) {
+        fit_views_pass<FV_COARSE, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[0], s_sum);
+        if ((uint32_t)s_sum[FV_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; stop = true; break; }
+        double x[6] = {0, 0, 0, 0, 0, 0};
+        if (!fit_solve_tri<3, 6>(s_sum, FV_B, a.lam1, x)) { status = DH_FIT_SINGULAR; stop = true; break; }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
+        ++steps;
+        if (fit_views_small(x, 3)) break;
+    }
+    for (uint32_t it = 0; it < a.full && !stop; ++it) {
+        fit_views_pass<FV_FULL, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[1], s_sum);
+        if ((uint32_t)s_sum[FV_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; break; }
+        double x[6];
+        if (!fit_solve_tri<6, 6>(s_sum, FV_B, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
+        fit_views_cayley(pose.R, x + 3);
+        ++steps;
+        if (fit_views_small(x, 6)) break;
+    }
+    fit_views_pass<FV_LAST, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[1], s_sum);
+    if (threadIdx.x == 0) {
+        dh_view_instance o = *in;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) o.R[q] = (float)pose.R[q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) o.t[q] = (float)pose.t[q];
+        a.out[blockIdx.x] = o;
+        dh_view_fit_record rec;
+        rec.points = (uint32_t)s_sum[FV_COUNT];
+        rec.steps = steps;
+        rec.status = status;
+        rec.reserved = 0;
+        rec.sum_r2_fixed = (int64_t)s_sum[FV_E];
+        rec.views_used = (uint64_t)s_sum[FV_USED];
+        a.rec[blockIdx.x] = rec;
+    }
+}
+
+// One instance's whole fit: the model staged into LDS where it fits (the first pass's barriers order the staging before its
+// reads), then the schedule of `a` over the instance's views.
+__global__ __launch_bounds__(DH_FIT_THREADS) void k_fit_views(const FitViewsArgs a) {
+    __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];
+    __shared__ unsigned long long s_sum[32];
+    const dh_view_instance *in = a.inst + blockIdx.x;
+    const FitModel m = a.models[in->model];
+    if (m.n <= DH_FIT_LDS_POINTS) {
+        for (uint32_t k = threadIdx.x; k < m.n * 3; k += DH_FIT_THREADS) {
+            const uint32_t i = k / 3, c = k - i * 3;
+            s_pts[c * DH_FIT_LDS_POINTS + i] = m.pts[k];
+            s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] = m.nrm[k];
+        }
+        fit_views_run<true>(a, in, m, s_pts, s_sum);
+    } else fit_views_run<false>(a, in, m, s_pts, s_sum);
+}
+
+// ------------------------------------------------------------------ launcher
+hipError_t dh_launch_fit_views(const FitViewsArgs &a, hipStream_t s) {
+    if (a.n_inst == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fit_views, dim3(a.n_inst), dim3(DH_FIT_THREADS), 0, s, a);
+    return hipGetLastError();
+}

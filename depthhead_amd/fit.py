@@ -8,8 +8,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, POSE_DTYPE, RENDER_INSTANCE_DTYPE,
-                   SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUPPORT_DTYPE, SUPPORT_RADIUS, check, vp)
+from ._lib import (FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, FIT_VIEW_TOLERANCE, POSE_DTYPE,
+                   RENDER_INSTANCE_DTYPE, SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUPPORT_DTYPE, SUPPORT_RADIUS, VIEW_FIT_RECORD_DTYPE,
+                   VIEW_INSTANCE_DTYPE, check, vp)
 from .render import euler_to_matrix
 
 FIT_OK, FIT_FEW_POINTS, FIT_SINGULAR = 0, 1, 2      # dh_fit_record.status
@@ -86,6 +87,65 @@ class Model(_lib._Handle):
         n, radius = C.c_uint32(), C.c_double()
         check(self._lib.dh_fit_model_info(self._h, C.byref(n), C.byref(radius)))
         return n.value, radius.value
+
+
+def views_from_rig(R, t):
+    """The world-to-camera transforms (V [n, 3, 3] f32, u [n, 3] f32) of a rig's camera-to-world extrinsics R [n, 3, 3] (or
+    [n, 9]) and t [n, 3], as `tracking.Rig` takes them: V = R^T, u = -(R^T t), in f64, rounded to f32 once.  ValueError when an
+    R is not within DH_FIT_VIEW_TOLERANCE of a rotation (an element of R R^T off the identity's, or a determinant below 0)."""
+    R = np.asarray(R, dtype=np.float64).reshape(-1, 3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(-1, 3)
+    if len(R) != len(t):
+        raise ValueError("as many translations as rotations are expected")
+    for c, r in enumerate(R):
+        if not np.isfinite(r).all() or not (np.abs(r @ r.T - np.eye(3)) <= FIT_VIEW_TOLERANCE).all() or np.linalg.det(r) < 0.0:
+            raise ValueError(f"camera {c}: R is not a rotation")
+    V = np.transpose(R, (0, 2, 1))
+    u = -np.einsum("nij,nj->ni", V, t)
+    return np.ascontiguousarray(V, dtype=np.float32), np.ascontiguousarray(u, dtype=np.float32)
+
+
+class Views(_lib._Handle):
+    """One dh_fit_views: the world-to-camera transform (V [n, 3, 3], u [n, 3] mm) of every camera of
+    `cameras` (a `tracking.Cameras`, which must outlive it), on that table's device: camera point = V x + u."""
+    _handles = (("_h", "dh_fit_views_destroy"),)
+
+    def __init__(self, cameras, V, u):
+        self._lib = _lib.load()
+        self.cameras = cameras
+        self.V = np.ascontiguousarray(V, dtype=np.float32).reshape(-1, 3, 3)
+        self.u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 3)
+        if len(self.V) != len(cameras) or len(self.u) != len(cameras):
+            raise ValueError("one V and one u per camera of the table are expected")
+        self._h = C.c_void_p()
+        check(self._lib.dh_fit_views_create(cameras._h, vp(self.V), vp(self.u), C.byref(self._h)))
+
+    def __len__(self):
+        return len(self.V)
+
+    def info(self):
+        """(n cameras, device) as the library holds them."""
+        n, device = C.c_int(), C.c_int()
+        check(self._lib.dh_fit_views_info(self._h, C.byref(n), C.byref(device)))
+        return n.value, device.value
+
+
+def view_instances_from_persons(persons, heads, rig_R, rig_t, rig_begin, scale: float = 1.0, model: int = 0) -> np.ndarray:
+    """Start instances (VIEW_INSTANCE_DTYPE) of a multi-view fit from one rig's persons, as `tracking.RigTracker.step` reports
+    them: `persons` the RIG_PERSON_DTYPE records of rig g, `heads` the step's HEAD_DTYPE [cameras, max_heads], rig_R / rig_t the
+    extrinsics of all cameras and `rig_begin` the rig's first camera.  t is the person's `world`; R is rig_R[best_cam] times the
+    best head's rotation, composed by tracking.world_rotation (best_cam indexes the whole camera table); views come from the
+    person record and first_cam is `rig_begin` (rig_t is taken so that the call reads as the rig's; `world` already is in the
+    world frame).  A host helper outside the bit-exact contract, as instances_from_poses is."""
+    from .tracking import world_rotation
+    persons = np.asarray(persons).reshape(-1)
+    rig_R = np.asarray(rig_R, dtype=np.float64).reshape(-1, 3, 3)
+    out = np.zeros(len(persons), dtype=VIEW_INSTANCE_DTYPE)
+    for i, p in enumerate(persons):
+        cam = int(p["best_cam"])
+        R = world_rotation(rig_R[cam], heads[cam][int(p["best_head"])]["pose"]["rotation"])
+        out[i] = (int(rig_begin), model, int(p["views"]), R.astype(np.float32).reshape(9), p["world"], scale, 0)
+    return out
 
 
 class ShapeBasis(_lib._Handle):
@@ -201,6 +261,38 @@ class Fitter(_lib._Handle):
                                                                       C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
         return out[:ni * RENDER_INSTANCE_DTYPE.itemsize], rec[:ni * FIT_RECORD_DTYPE.itemsize]
 
+
+    def fit_views(self, frames, models, instances, views, params=None, device_out: bool = False, stream=None):
+        """Fit each of `instances` (VIEW_INSTANCE_DTYPE: one world pose and the mask of the cameras that see it) against the
+        frames of all its views at once.  frames [n, h, w] u16, frame c seen through camera c of `views`
+        (a `Views` of n cameras): a numpy array, or a torch tensor on the device with device_out=True.  Returns (instances,
+        records) -- VIEW_INSTANCE_DTYPE and VIEW_FIT_RECORD_DTYPE arrays, or with device_out=True two uint8 torch tensors on the
+        device holding them, ordered on `stream` (default the current torch stream)."""
+        inst = np.ascontiguousarray(instances, dtype=VIEW_INSTANCE_DTYPE)
+        models = list(models)
+        handles = (C.c_void_p * max(len(models), 1))(*[m._h.value for m in models])
+        n, h, w = (int(v) for v in frames.shape)
+        if n != len(views):
+            raise ValueError(f"{n} frames for a view table of {len(views)} cameras")
+        prm = C.byref(params) if params is not None else None
+        ni = len(inst)
+        if not device_out:
+            fr = np.ascontiguousarray(frames, dtype=np.uint16)
+            out, rec = np.zeros(ni, VIEW_INSTANCE_DTYPE), np.zeros(ni, VIEW_FIT_RECORD_DTYPE)
+            check(self._lib.dh_fit_depth_views(self._h, vp(fr), w, h, views._h, handles, C.c_uint32(len(models)), vp(inst) if ni else None,
+                                               C.c_uint32(ni), prm, vp(out), vp(rec)))
+            return out, rec
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
+            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
+        out = torch.empty(max(ni, 1) * VIEW_INSTANCE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        rec = torch.empty(max(ni, 1) * VIEW_FIT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        check(self._lib.dh_fit_depth_views_device(self._h, C.c_void_p(frames.data_ptr()), w, h, views._h, handles, C.c_uint32(len(models)),
+                                                  vp(inst) if ni else None, C.c_uint32(ni), prm, C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
+        return out[:ni * VIEW_INSTANCE_DTYPE.itemsize], rec[:ni * VIEW_FIT_RECORD_DTYPE.itemsize]
 
     def shape_step(self, frames, model, basis, instances, K_or_cameras, subjects=None, n_subjects: int = 1, params=None,
                    device_out: bool = False, stream=None):
