@@ -115,6 +115,22 @@ assert VIEW_FIT_RECORD_DTYPE.itemsize == 32
 FIT_VIEW_TOLERANCE = 0.001  # DH_FIT_VIEW_TOLERANCE
 
 
+# dh_rig_fit_state / dh_rig_fit_record: one entry of a rig fit tracker's per-rig state, and what one step reports for a slot
+RIG_FIT_STATE_DTYPE = np.dtype([("id", "<u4"), ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("t_prev", "<f4", (3,)), ("views_used", "<u8"),
+                                ("tracked", "<u4"), ("have_prev", "<u4"), ("age", "<u4"), ("lost", "<u4")], align=True)
+assert RIG_FIT_STATE_DTYPE.itemsize == 88 and RIG_FIT_STATE_DTYPE.fields["views_used"][1] == 64
+RIG_FIT_RECORD_DTYPE = np.dtype([("instance", VIEW_INSTANCE_DTYPE), ("fit", VIEW_FIT_RECORD_DTYPE), ("id", "<u4"), ("status", "<u4"),
+                                 ("age", "<u4"), ("lost", "<u4"), ("person", "<u4"), ("reserved", "<u4")], align=True)
+assert RIG_FIT_RECORD_DTYPE.itemsize == 128 and RIG_FIT_RECORD_DTYPE.fields["fit"][1] == 72
+RIG_FIT_NO_PERSON = 0xFFFFFFFF   # dh_rig_fit_record.person of an unseen entry
+
+
+class RigFitTrackParams(C.Structure):
+    """dh_rig_fit_track_params"""
+    _fields_ = [("iterations_tracked", C.c_uint32), ("keep_points", C.c_uint32), ("rms_max", C.c_double), ("max_jump", C.c_double),
+                ("max_coast", C.c_uint32), ("max_misses", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
 class ShapeParams(C.Structure):
     """dh_shape_params (`lam` is the header's `lambda`)"""
     _fields_ = [("gate", C.c_double), ("lam", C.c_double), ("min_points", C.c_uint32), ("reserved0", C.c_uint32),
@@ -182,6 +198,9 @@ EXPORTS = [
     "dh_fit_basis_create", "dh_fit_basis_destroy", "dh_fit_basis_info", "dh_shape_params_default", "dh_fit_shape", "dh_fit_shape_cameras",
     "dh_fit_shape_device", "dh_fit_shape_cameras_device",
     "dh_fit_views_create", "dh_fit_views_destroy", "dh_fit_views_info", "dh_fit_depth_views", "dh_fit_depth_views_device",
+    "dh_rig_fit_track_params_default", "dh_rig_fit_tracker_create", "dh_rig_fit_tracker_destroy", "dh_rig_fit_tracker_reset",
+    "dh_rig_fit_tracker_state", "dh_rig_fit_tracker_step_persons", "dh_rig_fit_tracker_step_persons_device", "dh_rig_fit_tracker_step",
+    "dh_rig_fit_tracker_step_device",
 ]
 
 

@@ -2,9 +2,10 @@
 // (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, and the one test of whether an instance
 // may be fitted (dh_fit_instance_fault: the host's refusals and the shape kernel's skips).  The device arithmetic the kernels
 // share among themselves is in dh_fit_device.h.  Not part of the ABI.  The rules are stated in include/depthhead_hip.h (sections
-// "fitting posed models to depth frames" and after) and DESIGN.md sections 18 - 20.
+// "fitting posed models to depth frames" and after) and DESIGN.md sections 18 - 22.
 #pragma once
 #include "dh_internal.h"
+#include "dh_rig_fit.h"
 
 static_assert(sizeof(dh_fit_params) == 56, "dh_fit_params: 56 bytes");
 static_assert(sizeof(dh_fit_record) == 24, "dh_fit_record: 24 bytes");
@@ -201,3 +202,52 @@ struct FitViewsArgs {
     dh_view_fit_record *rec;      // [n_inst]
 };
 hipError_t dh_launch_fit_views(const FitViewsArgs &a, hipStream_t s);
+
+// ---- carrying each rig person's fitted world pose across steps (k_rig_fit_track.hip and k_fit_views' per-instance-schedule
+// instance).  The bind of a step is stated in dh_rig_fit.h.
+// What k_rig_fit_seed decided for a slot: the start kind in the low byte, and what the slot is.
+#define DH_RIG_FIT_SEED_NONE 0u       // unused slot: a record of zeros
+#define DH_RIG_FIT_SEED_DETECTED 1u
+#define DH_RIG_FIT_SEED_CARRIED 2u
+#define DH_RIG_FIT_SEED_COAST 3u      // a tracked entry none of whose views is present
+#define DH_RIG_FIT_SEED_ABSENT 4u     // the rig has no present camera: the state is kept
+#define DH_RIG_FIT_SEED_IS_SEEN 0x100u    // who[slot] is the slot's person
+#define DH_RIG_FIT_SEED_IS_ENTRY 0x200u   // the slot is an entry of the state (else an unbound person)
+#define DH_RIG_FIT_THREADS 64
+
+// k_fit_views_sched: k_fit_views with each instance's (coarse, full) read from `sched` and no work for a slot without a start.
+struct FitViewsSchedArgs {
+    FitViewsArgs f;               // coarse and full unused
+    const uint32_t *sched;        // [n_inst][2]
+    const uint32_t *seed;         // [n_inst] DH_RIG_FIT_SEED_*
+    uint32_t group;               // slots of a group (a rig's DH_RIG_MAX_TRACKS); n_inst is a multiple of it
+};
+hipError_t dh_launch_fit_views_sched(const FitViewsSchedArgs &a, hipStream_t s);
+
+struct RigFitArgs {
+    int n_rigs, n_cams, max_heads;
+    uint32_t flags;               // DH_FIT_TRACK_*
+    float scale;
+    dh_rig_fit_track_params prm;
+    int64_t rms_lim;              // (int64)(rms_max * rms_max * 2^20), cast on the host
+    double jump2;                 // max_jump * max_jump
+    uint32_t coarse, full;        // the detected start's schedule
+    const double *angles;         // [120][2] cos, sin
+    const int32_t *rig_begin;     // [n_rigs + 1]
+    const FitView *views;         // [n_cams]
+    const uint8_t *present;       // nullable [n_cams]
+    const uint32_t *n_heads;      // [n_cams]
+    const dh_head *heads;         // [n_cams][max_heads]
+    const uint32_t *n_persons;    // [n_rigs]
+    const dh_rig_person *persons; // [n_rigs][DH_RIG_MAX_PERSONS]
+    dh_rig_fit_state *state;      // [n_rigs][DH_RIG_MAX_TRACKS]
+    dh_view_instance *start;      // [n_rigs][DH_RIG_MAX_TRACKS] seed -> fit, update
+    uint32_t *sched;              // [slots][2]
+    uint32_t *seed;               // [slots]
+    uint32_t *who;                // [slots] the slot's person or DH_RIG_FIT_NO_PERSON
+    const dh_view_instance *fit_out;     // [slots] fit -> update
+    const dh_view_fit_record *fit_rec;   // [slots]
+    dh_rig_fit_record *records;          // [slots]
+};
+hipError_t dh_launch_rig_fit_seed(const RigFitArgs &a, hipStream_t s);
+hipError_t dh_launch_rig_fit_update(const RigFitArgs &a, hipStream_t s);

@@ -10,7 +10,8 @@
 //          the views; one wave reduction and one LDS atomic per wave and sum finish a pass, as in k_fit;
 //   step   every lane solves the same system redundantly in f64 (fit_solve_tri) and carries the world pose in registers.
 // f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free: bit-identical
-// run to run and to tests/view_fit_ref.py.  With one view, V = I and u = 0 every sum equals k_fit's.
+// run to run and to tests/view_fit_ref.py.  With one view, V = I and u = 0 every sum equals k_fit's.  One kernel body,
+// FIT_VIEWS_BLOCK, in two instances: k_fit_views, and k_fit_views_sched with a schedule per instance.
 #include "dh_fit_device.h"
 
 #pragma clang fp contract(off)
@@ -163,8 +164,8 @@ __device__ __forceinline__ void fit_views_cayley(double R[9], const double w[3])
 }
 
 template <bool STAGED>
-__device__ __forceinline__ void fit_views_run(const FitViewsArgs &a, const dh_view_instance *in, const FitModel &m, const float *s_pts,
-                                              unsigned long long *s_sum) {
+__device__ __forceinline__ void fit_views_run(const FitViewsArgs &a, uint32_t b, const dh_view_instance *in, const FitModel &m,
+                                              const float *s_pts, unsigned long long *s_sum) {
     const uint32_t first_cam = in->first_cam;
     const uint64_t views = in->views;
     const uint64_t mask = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(views >> 32)) << 32) |
@@ -205,7 +206,7 @@ __device__ __forceinline__ void fit_views_run(const FitViewsArgs &a, const dh_vi
         for (int q = 0; q < 9; ++q) o.R[q] = (float)pose.R[q];
 #pragma unroll
         for (int q = 0; q < 3; ++q) o.t[q] = (float)pose.t[q];
-        a.out[blockIdx.x] = o;
+        a.out[b] = o;
         dh_view_fit_record rec;
         rec.points = (uint32_t)s_sum[FV_COUNT];
         rec.steps = steps;
@@ -213,30 +214,53 @@ __device__ __forceinline__ void fit_views_run(const FitViewsArgs &a, const dh_vi
         rec.reserved = 0;
         rec.sum_r2_fixed = (int64_t)s_sum[FV_E];
         rec.views_used = (uint64_t)s_sum[FV_USED];
-        a.rec[blockIdx.x] = rec;
+        a.rec[b] = rec;
     }
 }
 
-// One instance's whole fit: the model staged into LDS where it fits (the first pass's barriers order the staging before its
-// reads), then the schedule of `a` over the instance's views.
-__global__ __launch_bounds__(DH_FIT_THREADS) void k_fit_views(const FitViewsArgs a) {
-    __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];
-    __shared__ unsigned long long s_sum[32];
-    const dh_view_instance *in = a.inst + blockIdx.x;
-    const FitModel m = a.models[in->model];
-    if (m.n <= DH_FIT_LDS_POINTS) {
-        for (uint32_t k = threadIdx.x; k < m.n * 3; k += DH_FIT_THREADS) {
-            const uint32_t i = k / 3, c = k - i * 3;
-            s_pts[c * DH_FIT_LDS_POINTS + i] = m.pts[k];
-            s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] = m.nrm[k];
-        }
-        fit_views_run<true>(a, in, m, s_pts, s_sum);
-    } else fit_views_run<false>(a, in, m, s_pts, s_sum);
+// One instance's whole fit, the body of both kernels: the model staged into LDS where it fits (the first pass's barriers order
+// the staging before its reads), then the schedule of `a` over the instance's views.  A macro, as FIT_BLOCK is in k_fit.hip: both
+// kernels compile from the very tokens, and the __shared__ arrays are each kernel's own.  b: the instance of this workgroup.
+#define FIT_VIEWS_BLOCK(a, b)                                                                                                    \
+    __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];                                                                             \
+    __shared__ unsigned long long s_sum[32];                                                                                   \
+    const dh_view_instance *in = (a).inst + (b);                                                                              \
+    const FitModel m = (a).models[in->model];                                                                                  \
+    if (m.n <= DH_FIT_LDS_POINTS) {                                                                                            \
+        for (uint32_t k = threadIdx.x; k < m.n * 3; k += DH_FIT_THREADS) {                                                     \
+            const uint32_t i = k / 3, c = k - i * 3;                                                                           \
+            s_pts[c * DH_FIT_LDS_POINTS + i] = m.pts[k];                                                                       \
+            s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] = m.nrm[k];                                                                 \
+        }                                                                                                                      \
+        fit_views_run<true>(a, b, in, m, s_pts, s_sum);                                                                        \
+    } else fit_views_run<false>(a, b, in, m, s_pts, s_sum)
+
+__global__ __launch_bounds__(DH_FIT_THREADS) void k_fit_views(const FitViewsArgs a) { FIT_VIEWS_BLOCK(a, blockIdx.x); }
+
+// The per-instance-schedule instance (dh_rig_fit_tracker_step*): slot b runs (sched[b][0], sched[b][1]); a workgroup whose slot
+// has no start (uniform over the workgroup: one word read by every lane) leaves before the model is staged and writes nothing.
+// The slots come in groups of `group` (a rig's) of which the first ones are the busy ones, and workgroups are dealt to the
+// XCDs round-robin by blockIdx: workgroup w takes slot (w mod G) * group + w / G of the G = n_inst / group groups, so that
+// the first slots of all groups are consecutive workgroups and spread over the XCDs (w -> slot w put them all on one XCD
+// when `group` is a multiple of the XCD count, and the step took as long as twenty steps).  n_inst is a multiple of group.
+__global__ __launch_bounds__(DH_FIT_THREADS) void k_fit_views_sched(const FitViewsSchedArgs q) {
+    const uint32_t groups = q.f.n_inst / q.group;
+    const uint32_t b = (blockIdx.x % groups) * q.group + blockIdx.x / groups;      // < n_inst: blockIdx.x / groups < group
+    const uint32_t kind = q.seed[b] & 0xffu;
+    if (kind != DH_RIG_FIT_SEED_DETECTED && kind != DH_RIG_FIT_SEED_CARRIED) return;
+    FitViewsArgs a = q.f;
+    a.coarse = q.sched[2 * b]; a.full = q.sched[2 * b + 1];
+    FIT_VIEWS_BLOCK(a, b);
 }
 
 // ------------------------------------------------------------------ launcher
 hipError_t dh_launch_fit_views(const FitViewsArgs &a, hipStream_t s) {
     if (a.n_inst == 0) return hipSuccess;
     hipLaunchKernelGGL(k_fit_views, dim3(a.n_inst), dim3(DH_FIT_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t dh_launch_fit_views_sched(const FitViewsSchedArgs &a, hipStream_t s) {
+    if (a.f.n_inst == 0 || a.group == 0 || a.f.n_inst % a.group != 0) return a.f.n_inst == 0 ? hipSuccess : hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_fit_views_sched, dim3(a.f.n_inst), dim3(DH_FIT_THREADS), 0, s, a);
     return hipGetLastError();
 }

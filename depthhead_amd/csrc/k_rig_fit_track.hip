@@ -1,0 +1,202 @@
+// k_rig_fit_track.hip -- each rig person's fitted world pose carried across steps (the rule is stated in
+// include/depthhead_hip.h, section "carrying each rig person's fitted world pose across steps").  Two small kernels around
+// k_fit_views' per-instance-schedule instance (k_fit_views.hip), over the DH_RIG_MAX_TRACKS slots of every rig:
+//   k_rig_fit_seed    steps 0 - 2, one workgroup of 64 lanes per rig: the rig's entries and persons are copied to LDS, lane 0
+//                     binds persons to entries (dh_rig_fit_bind, dh_rig_fit.h: sequential, 16 x 16 at most), then one lane
+//                     per slot composes the slot's start instance, its schedule and its kind;
+//   k_rig_fit_update  steps 4 - 6, one lane per slot: acceptance, the entry's state and the slot's record.
+// f32 and f64 with + - * /, compares and casts only, every operation rounded on its own; the cosines and sines come from the
+// host's 120-entry table (section 19's).  Bit-identical to tests/rig_fit_track_ref.py.
+#include "dh_device.h"
+#include "dh_fit.h"
+
+#pragma clang fp contract(off)
+
+static_assert(DH_RIG_MAX_TRACKS <= DH_RIG_FIT_THREADS, "one lane per slot of a rig");
+static_assert(sizeof(dh_rig_fit_state) % 4 == 0 && sizeof(dh_rig_person) % 4 == 0, "copied to LDS word by word");
+
+__device__ __forceinline__ uint32_t rf_sat_inc(uint32_t v) { return v == 0xffffffffu ? v : v + 1u; }
+
+// o = A B, each element as (A[i][0] * B[0][j] + A[i][1] * B[1][j]) + A[i][2] * B[2][j]
+__device__ __forceinline__ void rf_mat3_mul(const double A[9], const double B[9], double o[9]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+
+__global__ __launch_bounds__(DH_RIG_FIT_THREADS) void k_rig_fit_seed(const RigFitArgs a) {
+    __shared__ dh_rig_fit_state s_st[DH_RIG_MAX_TRACKS];
+    __shared__ dh_rig_person s_p[DH_RIG_MAX_PERSONS];
+    __shared__ uint32_t s_role[DH_RIG_MAX_TRACKS], s_who[DH_RIG_MAX_TRACKS];
+    const int g = blockIdx.x, lane = threadIdx.x;                  // g < n_rigs: the grid is n_rigs
+    const int c0 = a.rig_begin[g], nc = a.rig_begin[g + 1] - c0;   // 1 .. DH_RIG_MAX_CAMERAS cameras (dh_rig_create)
+    // pm: one present camera per lane (nc <= 64 = the lanes of the one wave)
+    const bool here = lane < nc && (!a.present || a.present[c0 + lane] != 0);
+    const uint64_t pm = __ballot(here);
+    const size_t slot = (size_t)g * DH_RIG_MAX_TRACKS + lane;
+    if (pm == 0) {                                                 // (uniform) step 0: the state is kept
+        if (lane < DH_RIG_MAX_TRACKS) {
+            a.seed[slot] = DH_RIG_FIT_SEED_ABSENT;
+            a.who[slot] = DH_RIG_FIT_NO_PERSON;
+            a.sched[2 * slot] = 0; a.sched[2 * slot + 1] = 0;
+        }
+        return;
+    }
+    dh_rig_fit_state *gst = a.state + (size_t)g * DH_RIG_MAX_TRACKS;
+    {
+        const uint32_t *src = (const uint32_t *)gst;
+        uint32_t *dst = (uint32_t *)s_st;
+        for (uint32_t k = lane; k < sizeof(s_st) / 4; k += DH_RIG_FIT_THREADS) dst[k] = src[k];
+        src = (const uint32_t *)(a.persons + (size_t)g * DH_RIG_MAX_PERSONS);
+        dst = (uint32_t *)s_p;
+        for (uint32_t k = lane; k < sizeof(s_p) / 4; k += DH_RIG_FIT_THREADS) dst[k] = src[k];
+    }
+    __syncthreads();
+    if (lane == 0) dh_rig_fit_bind(s_st, s_p, a.n_persons[g], a.n_heads, a.n_cams, a.max_heads, s_role, s_who);
+    __syncthreads();
+    if (lane >= DH_RIG_MAX_TRACKS) return;
+    const uint32_t role = s_role[lane], pi = s_who[lane];
+    const dh_rig_fit_state st = s_st[lane];
+    dh_view_instance in;
+    in.first_cam = (uint32_t)c0; in.model = 0; in.views = 0; in.scale = a.scale; in.flags = 0;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) in.R[q] = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) in.t[q] = 0.0f;
+    uint32_t kind = DH_RIG_FIT_SEED_NONE, coarse = 0, full = 0;
+    if (role != DH_RIG_FIT_UNUSED) {
+        const bool seen = pi != DH_RIG_FIT_NO_PERSON;
+        const bool entry = role != DH_RIG_FIT_UNBOUND;
+        if (entry && st.tracked) {
+            in.views = (st.views_used | (seen ? s_p[pi].views : 0ull)) & pm;
+            if (in.views == 0) kind = DH_RIG_FIT_SEED_COAST;
+            else {
+                kind = DH_RIG_FIT_SEED_CARRIED;
+                full = a.prm.iterations_tracked;
+#pragma unroll
+                for (int q = 0; q < 9; ++q) in.R[q] = st.R[q];
+                const bool motion = (a.flags & DH_FIT_TRACK_MOTION) && st.have_prev;
+#pragma unroll
+                for (int q = 0; q < 3; ++q) in.t[q] = motion ? st.t[q] + (st.t[q] - st.t_prev[q]) : st.t[q];
+            }
+        } else {                                                   // detected: the slot has a person (the bind freed the rest)
+            const dh_rig_person &p = s_p[pi];
+            kind = DH_RIG_FIT_SEED_DETECTED;
+            coarse = a.coarse; full = a.full;
+            in.views = p.views & pm;
+            // best_cam < n_cams and best_head < max_heads: the bind ignores every other person
+            const dh_pose &po = a.heads[(size_t)p.best_cam * a.max_heads + p.best_head].pose;
+            double cs[3], sn[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double x = po.rotation[j] / 3.14159 * 60.0 + 60.5;
+                const int ri = !(x >= 0.0) ? 0 : x >= 119.0 ? 119 : (int)x;
+                cs[j] = a.angles[2 * ri]; sn[j] = a.angles[2 * ri + 1];
+            }
+            const double Z[9] = {cs[0], sn[0], 0.0, -sn[0], cs[0], 0.0, 0.0, 0.0, 1.0};
+            const double Y[9] = {cs[1], 0.0, sn[1], 0.0, 1.0, 0.0, -sn[1], 0.0, cs[1]};
+            const double X[9] = {1.0, 0.0, 0.0, 0.0, cs[2], -sn[2], 0.0, sn[2], cs[2]};
+            double M[9], R[9], Rh[9], V[9];
+            rf_mat3_mul(Y, Z, M);
+            rf_mat3_mul(X, M, R);
+#pragma unroll
+            for (int q = 0; q < 9; ++q) {
+                Rh[q] = (double)(float)R[q];
+                V[q] = (double)a.views[p.best_cam].V[q];
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) in.R[3 * i + j] = (float)((V[i] * Rh[j] + V[3 + i] * Rh[3 + j]) + V[6 + i] * Rh[6 + j]);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) in.t[q] = p.world[q];
+        }
+        if (seen) kind |= DH_RIG_FIT_SEED_IS_SEEN;
+        if (entry) kind |= DH_RIG_FIT_SEED_IS_ENTRY;
+    }
+    gst[lane] = st;                                                // what the bind made of the entry
+    a.start[slot] = in;
+    a.sched[2 * slot] = coarse; a.sched[2 * slot + 1] = full;
+    a.seed[slot] = kind;
+    a.who[slot] = pi;
+}
+
+__global__ __launch_bounds__(DH_RIG_FIT_THREADS) void k_rig_fit_update(const RigFitArgs a) {
+    const int slot = blockIdx.x * DH_RIG_FIT_THREADS + threadIdx.x;
+    if (slot >= a.n_rigs * DH_RIG_MAX_TRACKS) return;
+    const int g = slot / DH_RIG_MAX_TRACKS;
+    const uint32_t seed = a.seed[slot], kind = seed & 0xffu, pi = a.who[slot];
+    const bool seen = (seed & DH_RIG_FIT_SEED_IS_SEEN) != 0, entry = (seed & DH_RIG_FIT_SEED_IS_ENTRY) != 0;
+    dh_rig_fit_record rec;
+    memset(&rec, 0, sizeof rec);
+    if (kind == DH_RIG_FIT_SEED_NONE || kind == DH_RIG_FIT_SEED_ABSENT) {
+        if (kind == DH_RIG_FIT_SEED_ABSENT) rec.status = DH_FIT_TRACK_ABSENT;
+        a.records[slot] = rec;
+        return;
+    }
+    dh_rig_fit_state st;
+    memset(&st, 0, sizeof st);
+    if (entry) st = a.state[slot];
+    bool free_it = false;
+    rec.person = pi;
+    if (kind == DH_RIG_FIT_SEED_COAST) {
+        st.lost = rf_sat_inc(st.lost);
+        st.have_prev = 0;
+        free_it = st.lost > a.prm.max_coast;
+        rec.status = DH_FIT_TRACK_ABSENT;
+    } else {
+        const dh_view_instance fit = a.fit_out[slot];
+        const dh_view_fit_record fr = a.fit_rec[slot];
+        uint32_t why = 0;
+        if (fr.status != DH_FIT_OK) why |= DH_FIT_TRACK_BAD_STATUS;
+        if (fr.points < a.prm.keep_points) why |= DH_FIT_TRACK_BAD_POINTS;
+        if (fr.sum_r2_fixed > a.rms_lim * (long long)fr.points) why |= DH_FIT_TRACK_BAD_RMS;
+        if (seen) {
+            const dh_rig_person &p = a.persons[(size_t)g * DH_RIG_MAX_PERSONS + pi];   // pi < DH_RIG_MAX_PERSONS: the bind's
+            const double dx = (double)fit.t[0] - (double)p.world[0], dy = (double)fit.t[1] - (double)p.world[1],
+                         dz = (double)fit.t[2] - (double)p.world[2];
+            if (!((dx * dx + dy * dy) + dz * dz <= a.jump2)) why |= DH_FIT_TRACK_BAD_JUMP;
+        }
+        rec.fit = fr;
+        if (why == 0) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) { st.t_prev[q] = st.t[q]; st.t[q] = fit.t[q]; }
+#pragma unroll
+            for (int q = 0; q < 9; ++q) st.R[q] = fit.R[q];
+            st.views_used = fr.views_used;
+            st.have_prev = st.tracked;
+            st.tracked = 1;
+            st.age = rf_sat_inc(st.age);
+            st.lost = 0;
+            rec.instance = fit;
+            rec.status = kind == DH_RIG_FIT_SEED_CARRIED ? DH_FIT_TRACK_CARRIED : DH_FIT_TRACK_FITTED;
+        } else {
+            st.tracked = 0; st.have_prev = 0; st.age = 0;
+            st.lost = rf_sat_inc(st.lost);
+            rec.instance = a.start[slot];
+            rec.status = DH_FIT_TRACK_REJECTED | why;
+            free_it = !seen;
+        }
+    }
+    rec.id = entry ? st.id : a.persons[(size_t)g * DH_RIG_MAX_PERSONS + pi].id;   // (an unbound person is always seen)
+    rec.age = st.age; rec.lost = st.lost;
+    if (entry) {
+        if (free_it) memset(&st, 0, sizeof st);
+        a.state[slot] = st;
+    }
+    a.records[slot] = rec;
+}
+
+// ------------------------------------------------------------------ launchers
+hipError_t dh_launch_rig_fit_seed(const RigFitArgs &a, hipStream_t s) {
+    if (a.n_rigs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rig_fit_seed, dim3(a.n_rigs), dim3(DH_RIG_FIT_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t dh_launch_rig_fit_update(const RigFitArgs &a, hipStream_t s) {
+    if (a.n_rigs <= 0) return hipSuccess;
+    const int slots = a.n_rigs * DH_RIG_MAX_TRACKS;
+    hipLaunchKernelGGL(k_rig_fit_update, dim3((slots + DH_RIG_FIT_THREADS - 1) / DH_RIG_FIT_THREADS), dim3(DH_RIG_FIT_THREADS), 0, s, a);
+    return hipGetLastError();
+}

@@ -8,8 +8,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, FIT_VIEW_TOLERANCE, POSE_DTYPE,
-                   RENDER_INSTANCE_DTYPE, SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUPPORT_DTYPE, SUPPORT_RADIUS, VIEW_FIT_RECORD_DTYPE,
+from ._lib import (FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, FIT_VIEW_TOLERANCE, HEAD_DTYPE,
+                   MAX_HEADS, POSE_DTYPE, RIG_FIT_RECORD_DTYPE, RIG_FIT_STATE_DTYPE, RIG_MAX_PERSONS, RIG_MAX_TRACKS, RIG_PERSON_DTYPE,
+                   RIG_TRACK_DTYPE, RENDER_INSTANCE_DTYPE, SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUPPORT_DTYPE, SUPPORT_RADIUS, VIEW_FIT_RECORD_DTYPE,
                    VIEW_INSTANCE_DTYPE, check, vp)
 from .render import euler_to_matrix
 
@@ -455,3 +456,108 @@ class FitTracker(_lib._Handle):
     @staticmethod
     def angles() -> np.ndarray:
         return angles()
+
+
+def rig_fit_track_params(iterations_tracked=None, keep_points=None, rms_max=None, max_jump=None, max_coast=None,
+                         max_misses=None) -> "_lib.RigFitTrackParams":
+    """dh_rig_fit_track_params_default with the given fields replaced; `max_misses` is the rig tracker's, which the ids come from."""
+    p = _lib.RigFitTrackParams()
+    check(_lib.load().dh_rig_fit_track_params_default(C.byref(p)))
+    for name, v in (("iterations_tracked", iterations_tracked), ("keep_points", keep_points), ("max_coast", max_coast),
+                    ("max_misses", max_misses)):
+        if v is not None:
+            setattr(p, name, int(v))
+    if rms_max is not None:
+        p.rms_max = float(rms_max)
+    if max_jump is not None:
+        p.max_jump = float(max_jump)
+    return p
+
+
+class RigFitTracker(_lib._Handle):
+    """One dh_rig_fit_tracker: every person of every rig of `rig` (a `tracking.Rig`) keeps one fitted pose in
+    the world frame under the id a `tracking.RigTracker` gave it.  A step refits `model` against all the views (`views`, a `Views`
+    of the rig's camera table, consistent with the rig: `views_from_rig`) from the carried pose, or from the person record where
+    there is none, and decides whether the fit is believed.  The state stays on the device.  Steps of one tracker must be
+    stream-ordered; the tables and the model must outlive it."""
+    _handles = (("_h", "dh_rig_fit_tracker_destroy"),)
+
+    def __init__(self, rig, views: Views, model: Model, w: int, h: int, scale: float = 1.0, motion: bool = False, params=None):
+        self._lib = _lib.load()
+        self.rig, self.views, self.model, self.w, self.h = rig, views, model, int(w), int(h)
+        self.n, self.n_rigs = rig.n, rig.n_rigs
+        self.flags = FIT_TRACK_MOTION if motion else 0
+        self._h = C.c_void_p()
+        check(self._lib.dh_rig_fit_tracker_create(rig._h, views._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
+                                                  C.byref(params) if params is not None else None, C.byref(self._h)))
+
+    def _frames(self, frames) -> np.ndarray:
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.shape != (self.n, self.h, self.w):
+            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
+        return frames
+
+    def _present(self, present):
+        return None if present is None else np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
+
+    def step_persons(self, frames, n_heads, heads, n_persons, persons, present=None, fit_params=None) -> np.ndarray:
+        """The core step from the outputs of a rig tracker step -- n_heads u32 [n_cams], HEAD_DTYPE [n_cams, max_heads], n_persons
+        u32 [n_rigs], RIG_PERSON_DTYPE [n_rigs, RIG_MAX_PERSONS] -- and host frames [n_cams, h, w] u16:
+        -> RIG_FIT_RECORD_DTYPE [n_rigs, RIG_MAX_TRACKS]."""
+        frames, pr = self._frames(frames), self._present(present)
+        heads = np.ascontiguousarray(heads, dtype=HEAD_DTYPE)
+        if heads.ndim != 2 or heads.shape[0] != self.n:
+            raise ValueError(f"heads must be [{self.n}, max_heads]")
+        n_heads = np.ascontiguousarray(n_heads, dtype=np.uint32).reshape(self.n)
+        n_persons = np.ascontiguousarray(n_persons, dtype=np.uint32).reshape(self.n_rigs)
+        persons = np.ascontiguousarray(persons, dtype=RIG_PERSON_DTYPE).reshape(self.n_rigs, RIG_MAX_PERSONS)
+        rec = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_FIT_RECORD_DTYPE)
+        check(self._lib.dh_rig_fit_tracker_step_persons(self._h, vp(frames), self.w, self.h, vp(pr), C.c_int(heads.shape[1]), vp(n_heads),
+                                                        vp(heads), vp(n_persons), vp(persons),
+                                                        C.byref(fit_params) if fit_params is not None else None, vp(rec)))
+        return rec
+
+    def step(self, rig_tracker, frames, present=None, tracks: bool = True, fit_params=None):
+        """The whole step: `rig_tracker` (a `tracking.RigTracker` of the same rig table) steps on the frames, then the core
+        step, on one stream.  -> (what RigTracker.step returns: n_heads, heads, rig_ids, n_persons, persons, tracks or None;
+        RIG_FIT_RECORD_DTYPE [n_rigs, RIG_MAX_TRACKS])."""
+        frames, pr = self._frames(frames), self._present(present)
+        mh = rig_tracker.max_heads
+        n_heads, heads = np.zeros(self.n, np.uint32), np.zeros((self.n, mh), HEAD_DTYPE)
+        ids = np.zeros((self.n, mh), np.uint32)
+        n_persons, persons = np.zeros(self.n_rigs, np.uint32), np.zeros((self.n_rigs, RIG_MAX_PERSONS), RIG_PERSON_DTYPE)
+        tr = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_TRACK_DTYPE) if tracks else None
+        rec = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_FIT_RECORD_DTYPE)
+        check(self._lib.dh_rig_fit_tracker_step(rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames), self.w, self.h, vp(pr),
+                                                C.byref(fit_params) if fit_params is not None else None, vp(n_heads), vp(heads), vp(ids),
+                                                vp(n_persons), vp(persons), vp(tr), vp(rec)))
+        return (n_heads, heads, ids, n_persons, persons, tr), rec
+
+    def step_device(self, frames_ptr: int, n_heads_ptr: int, heads_ptr: int, n_persons_ptr: int, persons_ptr: int, records_ptr: int,
+                    max_heads: int = MAX_HEADS, rig_tracker=None, ids_ptr: int = 0, tracks_ptr: int = 0, present_ptr: int = 0,
+                    fit_params=None, stream: int = 0) -> None:
+        """Device frames [n_cams][h][w] u16, n_heads [n_cams] u32, heads [n_cams][max_heads] dh_head, n_persons [n_rigs] u32,
+        persons [n_rigs][RIG_MAX_PERSONS] dh_rig_person, records [n_rigs][RIG_MAX_TRACKS] dh_rig_fit_record, present [n_cams] u8
+        or 0.  With `rig_tracker` the whole step (heads and persons are outputs, as are rig_ids [n_cams][max_heads] u32 and, unless
+        0, tracks; max_heads is the rig tracker's), without it the core step (they are inputs).  Asynchronous on `stream`;
+        allocates nothing and never waits on the host."""
+        prm = C.byref(fit_params) if fit_params is not None else None
+        if rig_tracker is None:
+            check(self._lib.dh_rig_fit_tracker_step_persons_device(self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
+                                                                   C.c_int(int(max_heads)), vp(n_heads_ptr), vp(heads_ptr), vp(n_persons_ptr),
+                                                                   vp(persons_ptr), prm, vp(records_ptr), C.c_void_p(int(stream))))
+        else:
+            check(self._lib.dh_rig_fit_tracker_step_device(rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames_ptr), self.w, self.h,
+                                                           vp(present_ptr or None), prm, vp(n_heads_ptr), vp(heads_ptr), vp(ids_ptr or None),
+                                                           vp(n_persons_ptr), vp(persons_ptr), vp(tracks_ptr or None), vp(records_ptr),
+                                                           C.c_void_p(int(stream))))
+
+    def reset(self, rig: int | None = None, stream: int = 0) -> None:
+        """One rig or all back to the initial state (every entry free); stream-ordered."""
+        check(self._lib.dh_rig_fit_tracker_reset(self._h, C.c_int(-1 if rig is None else int(rig)), C.c_void_p(int(stream))))
+
+    def state(self) -> np.ndarray:
+        """Synchronous copy of the state: RIG_FIT_STATE_DTYPE [n_rigs, RIG_MAX_TRACKS]."""
+        st = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_FIT_STATE_DTYPE)
+        check(self._lib.dh_rig_fit_tracker_state(self._h, vp(st)))
+        return st

@@ -975,6 +975,131 @@ int dh_fit_depth_views_device(dh_fitter *f, const uint16_t *frames, int w, int h
                               uint32_t n_instances, const dh_fit_params *params, dh_view_instance *out,
                               dh_view_fit_record *records, void *stream);
 
+/* ---- carrying each rig person's fitted world pose across steps ----
+ * The composition of the three sections above: every person of every rig keeps ONE fitted pose in the WORLD frame under the
+ * rig-wide id the rig tracker (section 16) gave it.  Each step refits that pose against all the views that see the person,
+ * from where it was and with a short schedule (section 19's idea, section 21's fit), and falls back to the rig tracker's person
+ * record -- the forest's detection -- when the model loses the head.  A dh_rig_fit_tracker is bound to a rig table, a view table
+ * of the SAME camera table and one model.  Not in the reference: PARITY UNPINNED, the definition below is this library's.  f32
+ * and f64 expressions are evaluated left to right, every operation rounded on its own; only + - * /, compares and casts run on
+ * the device.  tests/rig_fit_track_ref.py restates it; the GPU equals it byte for byte.
+ * The view table alone gives the rotation of a detected start (V_b^T below), so the device inverts nothing.  That the persons'
+ * `world` came from a rig table CONSISTENT with the view table (V_c = R_c^T, u_c = -(R_c^T t_c): fit.views_from_rig) is the
+ * caller's contract; the library checks only that both tables are bound to one dh_cameras handle.
+ * STATE of rig g: DH_RIG_MAX_TRACKS entries (dh_rig_fit_state): id (0 = free; a free entry is all zeros), R[9], t[3] of the last
+ *   accepted fit in the world frame (f32, exactly as the fit wrote them), t_prev[3] the accepted t before that, views_used of
+ *   the last accepted fit, tracked and have_prev (0 or 1), age (consecutive accepted steps) and lost (consecutive steps without
+ *   an accepted fit), both saturating at 2^32 - 1.  Created and reset to all zeros.
+ * ONE STEP of rig g with cameras c0 = rig_begin[g] .. rig_begin[g + 1] - 1, from one frame per camera, present (NULL: all
+ * present) and the outputs of a rig tracker step -- n_heads [n_cams], heads [n_cams][max_heads], n_persons [n_rigs], persons
+ * [n_rigs][DH_RIG_MAX_PERSONS].  pm = the mask of the bits k with camera c0 + k present.
+ * 0. pm == 0: the whole state of the rig is kept; every record of the rig is zero but for status = DH_FIT_TRACK_ABSENT.
+ *    Nothing below runs.
+ * 1. BIND.  The persons i < min(n_persons[g], DH_RIG_MAX_PERSONS) are walked in ascending i.  A person whose best_cam is no
+ *    camera of the table or whose best_head >= min(n_heads[best_cam], max_heads) names no head and is ignored altogether.
+ *    A person with id != 0 takes the lowest entry that holds its id, unless an earlier person of this step took that entry;
+ *    when no entry holds the id it takes the lowest free entry, which becomes zeros with that id.  A person with id 0, one whose
+ *    id an earlier person of the step bound, and one that finds no free entry is UNBOUND: it is fitted from its detection
+ *    and reported, and nothing of it is carried.  An entry with id != 0 that no person took is UNSEEN; an unseen entry that is
+ *    not tracked is freed (zeroed) here and has no record.  Then the unbound persons, in ascending i, each take the lowest
+ *    RECORD SLOT s whose entry is free after all this; an unbound person for which none is left is dropped.  So a slot s of the
+ *    rig is an entry (seen or unseen), an unbound person, or unused.
+ * 2. START of a slot.
+ *    CARRIED (an entry that is tracked): R = the state's R; t = the state's t, or with DH_FIT_TRACK_MOTION in the tracker's flags
+ *      and have_prev, t[j] = t[j] + (t[j] - t_prev[j]) in f32; views = (views_used | the person's views when seen) & pm; schedule
+ *      (0, iterations_tracked).  When that mask is empty the entry COASTS instead: lost = lost + 1, have_prev = 0, and when
+ *      lost > max_coast the entry is freed (zeroed); its record: id, status DH_FIT_TRACK_ABSENT, age and lost (as they were
+ *      before the zeroing), the person index, instance and fit record zeros.  No fit work is done for it.
+ *    DETECTED (a seen entry that is not tracked, or an unbound person): t = the person's world; with b = best_cam, V = V_b of the
+ *      view table widened to f64 and Rh = the rotation section 19 builds from heads[b][best_head].pose.rotation -- the angle
+ *      table, M = Y Z, Rh = X M, rounded to f32 as there, and widened to f64 again --
+ *        R[i][j] = (V[0][i] * Rh[0][j] + V[1][i] * Rh[1][j]) + V[2][i] * Rh[2][j]        (V_b^T Rh), rounded to f32 once;
+ *      views = the person's views & pm; schedule (coarse_iterations, iterations) of the step's dh_fit_params.
+ *    The start is a dh_view_instance: first_cam c0, model 0, views, R, t, the tracker's scale, flags 0.
+ * 3. FIT.  The rule of the section above, unchanged, on the start with the step's dh_fit_params (gates, lambda, min_points) and
+ *    the start's own schedule (an empty mask included: every sum is zero then).
+ * 4. ACCEPTANCE.  Section 19's reason bits on the dh_view_fit_record: DH_FIT_TRACK_BAD_STATUS  status != DH_FIT_OK;
+ *    DH_FIT_TRACK_BAD_POINTS  points (over all views) < keep_points;  DH_FIT_TRACK_BAD_RMS  sum_r2_fixed > (int64)(rms_max * rms_max
+ *    * 1048576.0) * (int64)points (the cast made once, on the host);  DH_FIT_TRACK_BAD_JUMP  the slot is seen and not ((dx * dx + dy *
+ *    dy) + dz * dz <= max_jump * max_jump) with d = (double)t_fit - (double)world of its person, in f64 (a NaN rejects).
+ * 5. OUTCOME.  Accepted: t_prev = t; R, t = the fitted instance's; views_used = the record's; have_prev = the old tracked;
+ *    tracked = 1; age = age + 1; lost = 0 (an unseen entry too: it is followed as long as the model holds it); status
+ *    DH_FIT_TRACK_CARRIED when the start was the carried one, else DH_FIT_TRACK_FITTED.  Not accepted: R, t, t_prev, views_used
+ *    stay; tracked = have_prev = age = 0; lost = lost + 1; status DH_FIT_TRACK_REJECTED | the reason bits; a SEEN entry stays bound
+ *    (its id is kept and the next step starts from the detection), an UNSEEN entry is freed (zeroed) after its record is
+ *    written.  An unbound person runs the same from an entry of zeros, which is then dropped.
+ * 6. OUTPUT.  records[g][s], one dh_rig_fit_record per slot: id (the entry's; the person's for an unbound person); the fitted
+ *    instance when accepted, else the start; the fit's record; the status; age and lost after the step (before a zeroing);
+ *    person = the index i of the slot's person in persons[g], or 0xffffffff when unseen.  Unused slots are zeros.
+ * An entry lives only while the rig tracker still carries its id: the rig tracker drops an id after max_misses unmatched steps,
+ * and an id that came back would be a new person.  So max_coast MUST NOT EXCEED the max_misses the ids come from:
+ * dh_rig_fit_track_params carries that max_misses (default DH_TRACK_MAX_MISSES; pass the rig tracker's), create refuses a
+ * max_coast above it, and the whole step refuses a rig tracker whose max_misses is below the tracker's max_coast.
+ * dh_rig_fit_tracker_create: the tables and the model must outlive the tracker.  Every device buffer is allocated there (the
+ * host forms' frame staging at the first host step, for its frame size): a _device step allocates nothing, uploads nothing but
+ * kernel arguments, launches k_rig_fit_seed, the per-instance-schedule instance of k_fit_views and k_rig_fit_update on `stream`
+ * and never waits on the host.  Steps of one tracker must be stream-ordered.  step_persons is the core step (host memory;
+ * _device: device memory) with max_heads the row length of `heads`; step runs dh_rig_tracker_step_device of `rt` and then the
+ * core step on one stream and also returns the rig step's outputs (rig_ids [n_cams][max_heads], tracks nullable).  records
+ * [n_rigs][DH_RIG_MAX_TRACKS].  DH_EINVAL before anything is launched or allocated, with the outputs untouched:
+ * create: NULL out / rig / views / model; unknown flags; a scale that is not finite; iterations_tracked above 64; rms_max or
+ *   max_jump outside (0, 4096] (NaN included); max_coast above max_misses; a reserved word that is not 0; a view table bound to
+ *   another dh_cameras handle than the rig table; a model on another device than the tables; |scale| * (the model's largest |v|)
+ *   above DH_FIT_MAX_EXTENT; (cameras of the largest rig) * (the model's points) above DH_FIT_MAX_POINTS -- the device cannot
+ *   refuse an instance at run time, so the bound of section 21's sums (2^62) is secured here.
+ * step: NULL tracker / frames / n_heads / heads / n_persons / persons / records (and predictor, rig tracker, rig_ids for the
+ *   whole step); w or h outside 1 .. DH_RENDER_MAX_SIZE; max_heads outside 1 .. DH_MAX_HEADS; the fit's own refusals of
+ *   dh_fit_params; for the whole step a rig tracker of another rig table, one whose max_misses is below max_coast, and the rig
+ *   step's own refusals.  reset: NULL tracker, a rig outside -1 .. n_rigs - 1.  state, params_default: NULL argument. */
+typedef struct dh_rig_fit_track_params {
+    uint32_t iterations_tracked;  /* 6: full steps of a carried start, at most 64 */
+    uint32_t keep_points;         /* 30, counted over all views */
+    double   rms_max;             /* 5.0 (mm), in (0, 4096] */
+    double   max_jump;            /* 150.0 (mm), in (0, 4096] */
+    uint32_t max_coast;           /* 3 steps without a present view; at most max_misses */
+    uint32_t max_misses;          /* DH_TRACK_MAX_MISSES: the max_misses of the rig tracker the ids come from */
+    uint64_t reserved[2];         /* 0 */
+} dh_rig_fit_track_params;  /* 48 bytes */
+typedef struct dh_rig_fit_state {
+    uint32_t id;                  /* 0 = free entry */
+    float    R[9], t[3], t_prev[3];
+    uint64_t views_used;          /* of the last accepted fit */
+    uint32_t tracked, have_prev, age, lost;
+} dh_rig_fit_state;     /* 88 bytes, no padding */
+typedef struct dh_rig_fit_record {
+    dh_view_instance   instance;
+    dh_view_fit_record fit;
+    uint32_t id;
+    uint32_t status;              /* DH_FIT_TRACK_*: kind in the low byte, reason bits above it */
+    uint32_t age, lost;
+    uint32_t person;              /* index into persons[g]; 0xffffffff: unseen */
+    uint32_t reserved;            /* 0 */
+} dh_rig_fit_record;    /* 128 bytes, no padding */
+typedef struct dh_rig_fit_tracker dh_rig_fit_tracker;
+int dh_rig_fit_track_params_default(dh_rig_fit_track_params *p);
+/* params NULL selects dh_rig_fit_track_params_default */
+int dh_rig_fit_tracker_create(const dh_rig *rig, const dh_fit_views *views, const dh_fit_model *model, float scale, uint32_t flags,
+                              const dh_rig_fit_track_params *params, dh_rig_fit_tracker **out);
+int dh_rig_fit_tracker_destroy(dh_rig_fit_tracker *t);
+/* rig, or -1 for all, back to zeros; ordered on `stream` */
+int dh_rig_fit_tracker_reset(dh_rig_fit_tracker *t, int rig, void *stream);
+/* states [n_rigs][DH_RIG_MAX_TRACKS]; synchronises the device */
+int dh_rig_fit_tracker_state(dh_rig_fit_tracker *t, dh_rig_fit_state *states);
+int dh_rig_fit_tracker_step_persons(dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
+                                    const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons,
+                                    const dh_fit_params *fit_params, dh_rig_fit_record *records);
+int dh_rig_fit_tracker_step_persons_device(dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
+                                           const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons,
+                                           const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_fit_record *records,
+                                           void *stream);
+int dh_rig_fit_tracker_step(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
+                            const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids,
+                            uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records);
+int dh_rig_fit_tracker_step_device(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
+                                   const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads,
+                                   uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks,
+                                   dh_rig_fit_record *records, void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
