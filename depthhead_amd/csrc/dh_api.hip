@@ -2841,24 +2841,52 @@ static int fit_params_check(const dh_fit_params *in, dh_fit_params *out, const c
     *out = prm;
     return DH_OK;
 }
-// The half of a FitArgs that the (checked) params fill.
-static void fit_args_params(FitArgs &a, const dh_fit_params &prm) {
+// The half of a FitArgs or FitViewsArgs that the (checked) params fill.
+template <typename A>
+static void fit_args_params(A &a, const dh_fit_params &prm) {
     a.coarse = prm.coarse_iterations; a.full = prm.iterations; a.min_points = prm.min_points;
     a.gate[0] = prm.gate[0]; a.gate[1] = prm.gate[1];
     a.lam1 = 1.0 + prm.lambda;
 }
 // What dh_fit_instance_fault found in instance i, as the refusal of a fit or shape call; DH_OK where it found nothing.
-static int instance_refusal(const FitInstanceFault &fault, const dh_render_instance &in, uint32_t i, double radius, double largest, const char *who) {
+static int instance_refusal(const FitInstanceFault &fault, float scale, uint32_t i, double radius, double largest, const char *who) {
     switch (fault.why) {
     case DH_FIT_INST_OK: return DH_OK;
     case DH_FIT_INST_NOT_FINITE: return fail(DH_EINVAL, "%s: instance %u has a non-finite R, t or scale", who, i);
     case DH_FIT_INST_NOT_ORTHONORMAL:
         return fail(DH_EINVAL, "%s: instance %u has an R that is not orthonormal: (R R^T)[%d][%d] = %g", who, i, fault.a, fault.b, fault.g);
     case DH_FIT_INST_EXTENT:
-        return fail(DH_EINVAL, "%s: instance %u spans %g mm from its origin (limit %g)", who, i, fabs((double)in.scale) * radius, DH_FIT_MAX_EXTENT);
+        return fail(DH_EINVAL, "%s: instance %u spans %g mm from its origin (limit %g)", who, i, fabs((double)scale) * radius, DH_FIT_MAX_EXTENT);
     default:
-        return fail(DH_EINVAL, "%s: instance %u scales the basis to %g mm (limit %g)", who, i, fabs((double)in.scale) * largest, DH_SHAPE_MAX_FIELD);
+        return fail(DH_EINVAL, "%s: instance %u scales the basis to %g mm (limit %g)", who, i, fabs((double)scale) * largest, DH_SHAPE_MAX_FIELD);
     }
+}
+// The refusals of instance i (a dh_render_instance, or a dh_view_instance with its world pose) of a fit call that rest on its
+// model m, the call's models[model], in the header's order: what dh_fit_instance_fault finds before the extent, then the model's
+// own refusals (NULL, another device than the fitter's), then the rest of the fault.
+template <typename Instance>
+static int instance_model_refusal(const Instance &in, uint32_t i, const dh_fit_model *m, uint32_t model, int device, const char *who) {
+    const double radius = m ? m->radius : 0.0;
+    const FitInstanceFault fault = dh_fit_instance_fault(in, radius, 0.0);
+    if (fault.why != DH_FIT_INST_OK && fault.why < DH_FIT_INST_EXTENT) return instance_refusal(fault, in.scale, i, radius, 0.0, who);
+    if (!m) return fail(DH_EINVAL, "%s: model %u is NULL", who, model);
+    if (m->device != device) return fail(DH_EINVAL, "%s: model %u lives on device %d, the fitter on %d", who, model, m->device, device);
+    return instance_refusal(fault, in.scale, i, radius, 0.0, who);
+}
+// A fit call's tables, models | instances, as one run of bytes: where the instances begin, and the fill of all
+// fit_tables_offset(n_models) + n_inst * sizeof(Instance) bytes at dst -- every byte is written, so two fills of the same call
+// compare equal (the capture path of the multi-view fit).
+static size_t fit_tables_offset(uint32_t n_models) { return ((size_t)n_models * sizeof(FitModel) + 15) & ~(size_t)15; }
+template <typename Instance>
+static void fit_tables_fill(unsigned char *dst, const dh_fit_model *const *models, uint32_t n_models, const Instance *inst, uint32_t n_inst,
+                            int device) {
+    const size_t o_inst = fit_tables_offset(n_models);
+    FitModel *mm = (FitModel *)dst;
+    for (uint32_t i = 0; i < n_models; ++i)          // (a model no instance names may be NULL: its row is never read)
+        mm[i] = models[i] && models[i]->device == device ? FitModel{models[i]->pts.get(), models[i]->nrm.get(), models[i]->n, 0}
+                                                         : FitModel{nullptr, nullptr, 0, 0};
+    memset(dst + (size_t)n_models * sizeof(FitModel), 0, o_inst - (size_t)n_models * sizeof(FitModel));
+    memcpy(dst + o_inst, inst, (size_t)n_inst * sizeof(Instance));
 }
 
 // One fit call.  dev: frames / out / records are device pointers and `stream` the caller's; else host pointers.
@@ -2885,13 +2913,7 @@ static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, 
         const dh_render_instance &in = q.inst[i];
         if (in.frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, q.n);
         if (in.mesh >= q.n_models) return fail(DH_EINVAL, "%s: instance %u names model %u of %u", who, i, in.mesh, q.n_models);
-        const dh_fit_model *m = q.models[in.mesh];
-        const double radius = m ? m->radius : 0.0;   // (the refusals of the model itself stand between those of R and of the extent)
-        const FitInstanceFault fault = dh_fit_instance_fault(in, radius, 0.0);
-        if (fault.why != DH_FIT_INST_OK && fault.why < DH_FIT_INST_EXTENT) return instance_refusal(fault, in, i, radius, 0.0, who);
-        if (!m) return fail(DH_EINVAL, "%s: model %u is NULL", who, in.mesh);
-        if (m->device != f->device) return fail(DH_EINVAL, "%s: model %u lives on device %d, the fitter on %d", who, in.mesh, m->device, f->device);
-        if (fault.why != DH_FIT_INST_OK) return instance_refusal(fault, in, i, radius, 0.0, who);
+        TRY(instance_model_refusal(in, i, q.models[in.mesh], in.mesh, f->device, who));
     }
     if (q.n_inst == 0) return DH_OK;
 
@@ -2907,16 +2929,10 @@ static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, 
     a.n_inst = q.n_inst;
     fit_args_params(a, prm);
     // ---- the call's tables: one staging buffer, one upload
-    const size_t o_inst = ((size_t)q.n_models * sizeof(FitModel) + 15) & ~(size_t)15;
+    const size_t o_inst = fit_tables_offset(q.n_models);
     const size_t bytes = o_inst + (size_t)q.n_inst * sizeof(dh_render_instance);
     TRY(f->tab.reserve(bytes));
-    {
-        FitModel *mm = (FitModel *)f->tab.stage.get();
-        for (uint32_t i = 0; i < q.n_models; ++i)    // (a model no instance names may be NULL: its row is never read)
-            mm[i] = q.models[i] && q.models[i]->device == f->device ? FitModel{q.models[i]->pts.get(), q.models[i]->nrm.get(), q.models[i]->n, 0}
-                                                                    : FitModel{nullptr, nullptr, 0, 0};
-        memcpy(f->tab.stage.get() + o_inst, q.inst, (size_t)q.n_inst * sizeof(dh_render_instance));
-    }
+    fit_tables_fill(f->tab.stage.get(), q.models, q.n_models, q.inst, q.n_inst, f->device);
     a.models = (const FitModel *)f->tab.dev.get();
     a.inst = (const dh_render_instance *)(f->tab.dev.get() + o_inst);
     const size_t n_px = (size_t)q.n * q.w * q.h;
@@ -3032,17 +3048,8 @@ static int fit_views_run(dh_fitter *f, const FitViewsReq &q, bool dev, hipStream
         const uint64_t last = (uint64_t)in.first_cam + (63u - (unsigned)__builtin_clzll(in.views));
         if (last >= (uint64_t)n) return fail(DH_EINVAL, "%s: instance %u names camera %llu of %d", who, i, (unsigned long long)last, n);
         if (in.model >= q.n_models) return fail(DH_EINVAL, "%s: instance %u names model %u of %u", who, i, in.model, q.n_models);
-        dh_render_instance world;                    // the world pose, as dh_fit_instance_fault reads an instance
-        memset(&world, 0, sizeof world);
-        memcpy(world.R, in.R, sizeof world.R); memcpy(world.t, in.t, sizeof world.t);
-        world.scale = in.scale;
         const dh_fit_model *m = q.models[in.model];
-        const double radius = m ? m->radius : 0.0;   // (the refusals of the model itself stand between those of R and of the extent)
-        const FitInstanceFault fault = dh_fit_instance_fault(world, radius, 0.0);
-        if (fault.why != DH_FIT_INST_OK && fault.why < DH_FIT_INST_EXTENT) return instance_refusal(fault, world, i, radius, 0.0, who);
-        if (!m) return fail(DH_EINVAL, "%s: model %u is NULL", who, in.model);
-        if (m->device != f->device) return fail(DH_EINVAL, "%s: model %u lives on device %d, the fitter on %d", who, in.model, m->device, f->device);
-        if (fault.why != DH_FIT_INST_OK) return instance_refusal(fault, world, i, radius, 0.0, who);
+        TRY(instance_model_refusal(in, i, m, in.model, f->device, who));
         const uint64_t terms = (uint64_t)__builtin_popcountll(in.views) * m->n;
         if (terms > DH_FIT_MAX_POINTS)
             return fail(DH_EINVAL, "%s: instance %u sums %llu terms (%d views of %u points), above %u", who, i, (unsigned long long)terms,
@@ -3068,20 +3075,11 @@ static int fit_views_run(dh_fitter *f, const FitViewsReq &q, bool dev, hipStream
     a.cams = q.views->cams->dev.get();
     a.views = q.views->dev.get();
     a.n_inst = q.n_inst;
-    a.coarse = prm.coarse_iterations; a.full = prm.iterations; a.min_points = prm.min_points;
-    a.gate[0] = prm.gate[0]; a.gate[1] = prm.gate[1];
-    a.lam1 = 1.0 + prm.lambda;
+    fit_args_params(a, prm);
     // ---- the call's tables: one staging buffer, one upload
-    const size_t o_inst = ((size_t)q.n_models * sizeof(FitModel) + 15) & ~(size_t)15;
+    const size_t o_inst = fit_tables_offset(q.n_models);
     const size_t bytes = o_inst + (size_t)q.n_inst * sizeof(dh_view_instance);
-    auto fill = [&](unsigned char *dst) {            // every one of `bytes` bytes is written
-        FitModel *mm = (FitModel *)dst;
-        for (uint32_t i = 0; i < q.n_models; ++i)    // (a model no instance names may be NULL: its row is never read)
-            mm[i] = q.models[i] && q.models[i]->device == f->device ? FitModel{q.models[i]->pts.get(), q.models[i]->nrm.get(), q.models[i]->n, 0}
-                                                                    : FitModel{nullptr, nullptr, 0, 0};
-        memset(dst + (size_t)q.n_models * sizeof(FitModel), 0, o_inst - (size_t)q.n_models * sizeof(FitModel));
-        memcpy(dst + o_inst, q.inst, (size_t)q.n_inst * sizeof(dh_view_instance));
-    };
+    auto fill = [&](unsigned char *dst) { fit_tables_fill(dst, q.models, q.n_models, q.inst, q.n_inst, f->device); };
     if (capturing) {
         f->view_cmp.resize(bytes);                   // (the only path that builds the tables beside the staging buffer)
         fill(f->view_cmp.data());
@@ -3228,7 +3226,7 @@ static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stre
             if (sj >= q.n_subjects) return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, q.n_subjects);
             const dh_render_instance &in = q.inst[i];
             if (in.frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, q.n);
-            TRY(instance_refusal(dh_fit_instance_fault(in, m->radius, b->largest), in, i, m->radius, b->largest, who));
+            TRY(instance_refusal(dh_fit_instance_fault(in, m->radius, b->largest), in.scale, i, m->radius, b->largest, who));
             if ((uint64_t)(++per[sj]) * m->n > DH_SHAPE_MAX_TERMS)
                 return fail(DH_EINVAL, "%s: subject %u has more than %u terms (instances times %u points)", who, sj, DH_SHAPE_MAX_TERMS, m->n);
         }
@@ -3325,31 +3323,96 @@ static int fit_track_params_default_(dh_fit_track_params *p) {
     return DH_OK;
 }
 
-// Every device buffer of a step is sized by the camera table and allocated at creation; the host forms stage through the
-// buffers of the second group on the tracker's own stream (the frames come with the first host step, for its frame size).
-struct dh_fit_tracker : TrackerCore {
+// What the camera's fit tracker (below) and the rig's (section 22) share: the model and what the acceptance rule reads, the
+// tables every step reads, and for the host forms the tracker's own stream and the frames staged on it (they come with the first
+// host step, for its frame size).  A tracker T adds its params (T::prm), its state, the buffers between its three launches and
+// the staging buffers of its host forms (T::records among them); every device buffer of a step is allocated at creation.
+struct FitTrackerCore : TrackerCore {
     const dh_fit_model *model = nullptr;
     float scale = 1.0f;
     uint32_t flags = 0;
-    dh_fit_track_params prm{};
     int64_t rms_lim = 0;
     double jump2 = 0.0;
-    Buf<dh_fit_track_state> state;       // [n]
     Buf<double> angles;                  // [120][2]
     Buf<FitModel> models;                // [1]
-    Buf<dh_render_instance> start, fit_out;
-    Buf<dh_fit_record> fit_rec;
-    Buf<uint32_t> sched, seed;
+    Buf<uint32_t> sched, seed;           // [units][2], [units]: a unit is what one workgroup of the fit takes (a camera, a slot)
     hipStream_t s = nullptr;             // host forms
     Buf<uint16_t> frames;
-    Buf<dh_pose> poses;
+    ~FitTrackerCore() { if (s) (void)hipStreamDestroy(s); }
+    // The tail of a tracker's allocation: what the params come to, the shared tables for `units` units, and the stream.
+    int init_fit(const dh_fit_model *m, float scale_, uint32_t flags_, double rms_max, double max_jump, size_t units) {
+        model = m; scale = scale_; flags = flags_;
+        rms_lim = (int64_t)(rms_max * rms_max * 1048576.0);
+        jump2 = max_jump * max_jump;
+        TRY(angles.alloc(DH_FIT_TRACK_ANGLES * 2));
+        TRY(models.alloc(1));
+        TRY(sched.alloc(units * 2)); TRY(seed.alloc(units));
+        const FitModel fm{m->pts.get(), m->nrm.get(), m->n, 0};
+        HIP_TRY(hipMemcpy(models.get(), &fm, sizeof fm, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(angles.get(), fit_track_angles().v, sizeof fit_track_angles().v, hipMemcpyHostToDevice));
+        return hip_step(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
+    }
+};
+// The refusals of a fit tracker's creation in the header's order.  P: dh_fit_track_params or dh_rig_fit_track_params; own() gives
+// the refusals of the fields that only P has, tables() those of the tables and of the model beside them (NULL, device).
+template <typename P, typename Own, typename Tables>
+static int fit_tracker_create_check(const P &prm, float scale, uint32_t flags, const dh_fit_model *m, Own own, Tables tables, const char *who) {
+    if (flags & ~DH_FIT_TRACK_MOTION) return fail(DH_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    if (!std::isfinite(scale)) return fail(DH_EINVAL, "%s: scale is not finite", who);
+    if (prm.iterations_tracked > 64) return fail(DH_EINVAL, "%s: iterations_tracked %u above 64", who, prm.iterations_tracked);
+    if (!(prm.rms_max > 0.0 && prm.rms_max <= 4096.0)) return fail(DH_EINVAL, "%s: rms_max = %g outside (0, 4096]", who, prm.rms_max);
+    if (!(prm.max_jump > 0.0 && prm.max_jump <= 4096.0)) return fail(DH_EINVAL, "%s: max_jump = %g outside (0, 4096]", who, prm.max_jump);
+    TRY(own());
+    if (prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    TRY(tables());
+    if (!m) return fail(DH_EINVAL, "%s: NULL model", who);     // (tables() refuses it in its place: m is never read unchecked)
+    const double extent = fabs((double)scale) * m->radius;
+    if (extent > DH_FIT_MAX_EXTENT) return fail(DH_EINVAL, "%s: the model spans %g mm from its origin (limit %g)", who, extent, DH_FIT_MAX_EXTENT);
+    return DH_OK;
+}
+// (a step may still run on any stream of the device)
+template <typename T>
+static int destroy_fit_tracker(T *t) {
+    if (t) {
+        DeviceGuard guard(t->cams->device);
+        (void)hipDeviceSynchronize();
+    }
+    return destroy_tracker(t);
+}
+// The host form of a step of fit tracker t, synchronous on its own stream: the frames and the present bytes are staged,
+// upload(s) stages the caller's other inputs, step(frames, present, s) enqueues the step on the staged arrays (present: the
+// staged bytes or NULL), download(s) copies back what the step reports beside its records, and the n_rec records follow.
+template <typename T, typename Up, typename Step, typename Down, typename Rec>
+static int fit_tracker_host(T *t, const uint16_t *frames, int w, int h, const uint8_t *present, Up upload, Step step, Down download, Rec *records,
+                            size_t n_rec) {
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    const size_t n = (size_t)t->n, n_px = n * w * h;
+    if (t->frames.cap() < n_px) TRY(t->frames.alloc(n_px));       // (host steps are synchronous: nothing reads the old buffer)
+    hipStream_t s = t->s;
+    HIP_TRY(hipMemcpyAsync(t->frames.get(), frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    if (present) HIP_TRY(hipMemcpyAsync(t->present.get(), present, n, hipMemcpyHostToDevice, s));
+    TRY(upload(s));
+    const int rc = step(t->frames.get(), present ? t->present.get() : nullptr, s);
+    if (rc != DH_OK) { (void)hipStreamSynchronize(s); return rc; }
+    TRY(download(s));
+    HIP_TRY(hipMemcpyAsync(records, t->records.get(), n_rec * sizeof(Rec), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DH_OK;
+}
+
+struct dh_fit_tracker : FitTrackerCore {
+    dh_fit_track_params prm{};
+    Buf<dh_fit_track_state> state;       // [n]
+    Buf<dh_render_instance> start, fit_out;
+    Buf<dh_fit_record> fit_rec;
+    Buf<dh_pose> poses;                  // host forms
     Buf<dh_support> support;
     Buf<dh_fit_track_record> records;
     int clear(size_t c0, size_t m, hipStream_t st) {
         HIP_TRY(hipMemsetAsync(state.get() + c0, 0, m * sizeof(dh_fit_track_state), st));
         return DH_OK;
     }
-    ~dh_fit_tracker() { if (s) (void)hipStreamDestroy(s); }
 };
 static int fit_tracker_create_(const dh_cameras *c, const dh_fit_model *m, float scale, uint32_t flags, const dh_fit_track_params *params,
                                dh_fit_tracker **out) {
@@ -3359,42 +3422,25 @@ static int fit_tracker_create_(const dh_cameras *c, const dh_fit_model *m, float
     dh_fit_track_params prm;
     (void)fit_track_params_default_(&prm);
     if (params) prm = *params;
-    if (flags & ~DH_FIT_TRACK_MOTION) return fail(DH_EINVAL, "%s: unknown flags 0x%x", who, flags);
-    if (!std::isfinite(scale)) return fail(DH_EINVAL, "%s: scale is not finite", who);
-    if (prm.iterations_tracked > 64) return fail(DH_EINVAL, "%s: iterations_tracked %u above 64", who, prm.iterations_tracked);
-    if (!(prm.rms_max > 0.0 && prm.rms_max <= 4096.0)) return fail(DH_EINVAL, "%s: rms_max = %g outside (0, 4096]", who, prm.rms_max);
-    if (!(prm.max_jump > 0.0 && prm.max_jump <= 4096.0)) return fail(DH_EINVAL, "%s: max_jump = %g outside (0, 4096]", who, prm.max_jump);
-    if (prm.conf_den == 0 || prm.conf_num > prm.conf_den)
-        return fail(DH_EINVAL, "%s: confidence %u / %u, expected a fraction in [0, 1]", who, prm.conf_num, prm.conf_den);
-    if (prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
-    if (!c) return fail(DH_EINVAL, "%s: NULL camera table", who);
-    if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
-    if (m->device != c->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the camera table on %d", who, m->device, c->device);
-    const double extent = fabs((double)scale) * m->radius;
-    if (extent > DH_FIT_MAX_EXTENT) return fail(DH_EINVAL, "%s: the model spans %g mm from its origin (limit %g)", who, extent, DH_FIT_MAX_EXTENT);
+    TRY(fit_tracker_create_check(prm, scale, flags, m, [&]() -> int {
+        if (prm.conf_den == 0 || prm.conf_num > prm.conf_den)
+            return fail(DH_EINVAL, "%s: confidence %u / %u, expected a fraction in [0, 1]", who, prm.conf_num, prm.conf_den);
+        return DH_OK;
+    }, [&]() -> int {
+        if (!c) return fail(DH_EINVAL, "%s: NULL camera table", who);
+        if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
+        if (m->device != c->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the camera table on %d", who, m->device, c->device);
+        return DH_OK;
+    }, who));
     return create_tracker(c, out, [&](dh_fit_tracker &t, size_t n) -> int {
-        t.model = m; t.scale = scale; t.flags = flags; t.prm = prm;
-        t.rms_lim = (int64_t)(prm.rms_max * prm.rms_max * 1048576.0);
-        t.jump2 = prm.max_jump * prm.max_jump;
+        t.prm = prm;
         TRY(t.state.alloc(n));
-        TRY(t.angles.alloc(DH_FIT_TRACK_ANGLES * 2));
-        TRY(t.models.alloc(1));
         TRY(t.start.alloc(n)); TRY(t.fit_out.alloc(n)); TRY(t.fit_rec.alloc(n));
-        TRY(t.sched.alloc(n * 2)); TRY(t.seed.alloc(n));
         TRY(t.poses.alloc(n)); TRY(t.support.alloc(n)); TRY(t.records.alloc(n));
-        const FitModel fm{m->pts.get(), m->nrm.get(), m->n, 0};
-        HIP_TRY(hipMemcpy(t.models.get(), &fm, sizeof fm, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(t.angles.get(), fit_track_angles().v, sizeof fit_track_angles().v, hipMemcpyHostToDevice));
-        return hip_step(hipStreamCreateWithFlags(&t.s, hipStreamNonBlocking), "hipStreamCreate");
+        return t.init_fit(m, scale, flags, prm.rms_max, prm.max_jump, n);
     });
 }
-static int fit_tracker_destroy_(dh_fit_tracker *t) {
-    if (t) {
-        DeviceGuard guard(t->cams->device);
-        (void)hipDeviceSynchronize();
-    }
-    return destroy_tracker(t);
-}
+static int fit_tracker_destroy_(dh_fit_tracker *t) { return destroy_fit_tracker(t); }
 static int fit_tracker_reset_(dh_fit_tracker *t, int camera, void *stream) { return reset_tracker(t, camera, stream, "dh_fit_tracker_reset"); }
 static int fit_tracker_state_(dh_fit_tracker *t, dh_fit_track_state *states) {
     if (t && !states) return fail(DH_EINVAL, "dh_fit_tracker_state: NULL argument");
@@ -3459,32 +3505,22 @@ static int fit_tracker_step_device_(dh_predictor *p, dh_fit_tracker *t, const ui
 // the caller's poses and support; else the prediction first, its poses and support copied back too.
 static int fit_track_host(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
                           const dh_fit_params &prm, dh_pose *poses, dh_support *support, dh_fit_track_record *records) {
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    const size_t n = (size_t)t->n, n_px = n * w * h;
-    if (t->frames.cap() < n_px) TRY(t->frames.alloc(n_px));       // (host steps are synchronous: nothing reads the old buffer)
-    hipStream_t s = t->s;
-    HIP_TRY(hipMemcpyAsync(t->frames.get(), frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-    if (present) HIP_TRY(hipMemcpyAsync(t->present.get(), present, n, hipMemcpyHostToDevice, s));
-    int rc;
-    if (p) rc = predict_batch_cameras_support_device_(p, t->frames.get(), t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, t->poses.get(),
-                                                      t->support.get(), s);
-    else {
+    const size_t n = (size_t)t->n;
+    return fit_tracker_host(t, frames, w, h, present, [&](hipStream_t s) -> int {
+        if (p) return DH_OK;
         HIP_TRY(hipMemcpyAsync(t->poses.get(), poses, n * sizeof(dh_pose), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(t->support.get(), support, n * sizeof(dh_support), hipMemcpyHostToDevice, s));
-        rc = DH_OK;
-    }
-    if (rc == DH_OK)
-        rc = fit_track_enqueue(t, t->frames.get(), w, h, present ? t->present.get() : nullptr, t->poses.get(), t->support.get(), prm,
-                               t->records.get(), s);
-    if (rc != DH_OK) { (void)hipStreamSynchronize(s); return rc; }
-    if (p) {
+        return DH_OK;
+    }, [&](const uint16_t *fr, const uint8_t *pr, hipStream_t s) -> int {
+        if (p) TRY(predict_batch_cameras_support_device_(p, fr, t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, t->poses.get(),
+                                                         t->support.get(), s));
+        return fit_track_enqueue(t, fr, w, h, pr, t->poses.get(), t->support.get(), prm, t->records.get(), s);
+    }, [&](hipStream_t s) -> int {
+        if (!p) return DH_OK;
         HIP_TRY(hipMemcpyAsync(poses, t->poses.get(), n * sizeof(dh_pose), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(support, t->support.get(), n * sizeof(dh_support), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipMemcpyAsync(records, t->records.get(), n * sizeof(dh_fit_track_record), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return DH_OK;
+        return DH_OK;
+    }, records, n);
 }
 static int fit_tracker_step_poses_(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
                                    const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records) {
@@ -3513,27 +3549,17 @@ static int rig_fit_track_params_default_(dh_rig_fit_track_params *p) {
     return DH_OK;
 }
 
-// The state is per rig (DH_RIG_MAX_TRACKS entries each); every device buffer of a step is sized by the rig table and allocated
-// at creation; the host forms stage through the buffers of the second group on the tracker's own stream (the frames come with
-// the first host step, for its frame size).
-struct dh_rig_fit_tracker : TrackerCore {
+// A FitTrackerCore (section 19) whose state is per rig (DH_RIG_MAX_TRACKS entries each) and whose units are the slots; every
+// device buffer of a step is sized by the rig table and allocated at creation.
+struct dh_rig_fit_tracker : FitTrackerCore {
     const dh_rig *rig = nullptr;
     const dh_fit_views *views = nullptr;
-    const dh_fit_model *model = nullptr;
-    float scale = 1.0f;
-    uint32_t flags = 0;
     dh_rig_fit_track_params prm{};
-    int64_t rms_lim = 0;
-    double jump2 = 0.0;
     Buf<dh_rig_fit_state> state;         // [n_rigs][DH_RIG_MAX_TRACKS]
-    Buf<double> angles;                  // [120][2]
-    Buf<FitModel> models;                // [1]
     Buf<dh_view_instance> start, fit_out;    // [slots]
     Buf<dh_view_fit_record> fit_rec;
-    Buf<uint32_t> sched, seed, who;
-    hipStream_t s = nullptr;             // host forms
-    Buf<uint16_t> frames;
-    Buf<dh_head> heads;                  // [n][DH_MAX_HEADS]
+    Buf<uint32_t> who;
+    Buf<dh_head> heads;                  // host forms: [n][DH_MAX_HEADS]
     Buf<uint32_t> n_heads, ids, n_persons;
     Buf<dh_rig_person> persons;          // [n_rigs][DH_RIG_MAX_PERSONS]
     Buf<dh_rig_track> tracks;            // [n_rigs][DH_RIG_MAX_TRACKS]
@@ -3542,7 +3568,6 @@ struct dh_rig_fit_tracker : TrackerCore {
         HIP_TRY(hipMemsetAsync(state.get() + g0 * DH_RIG_MAX_TRACKS, 0, m * DH_RIG_MAX_TRACKS * sizeof(dh_rig_fit_state), st));
         return DH_OK;
     }
-    ~dh_rig_fit_tracker() { if (s) (void)hipStreamDestroy(s); }
 };
 static int rig_fit_tracker_create_(const dh_rig *rig, const dh_fit_views *views, const dh_fit_model *m, float scale, uint32_t flags,
                                    const dh_rig_fit_track_params *params, dh_rig_fit_tracker **out) {
@@ -3552,52 +3577,36 @@ static int rig_fit_tracker_create_(const dh_rig *rig, const dh_fit_views *views,
     dh_rig_fit_track_params prm;
     (void)rig_fit_track_params_default_(&prm);
     if (params) prm = *params;
-    if (flags & ~DH_FIT_TRACK_MOTION) return fail(DH_EINVAL, "%s: unknown flags 0x%x", who, flags);
-    if (!std::isfinite(scale)) return fail(DH_EINVAL, "%s: scale is not finite", who);
-    if (prm.iterations_tracked > 64) return fail(DH_EINVAL, "%s: iterations_tracked %u above 64", who, prm.iterations_tracked);
-    if (!(prm.rms_max > 0.0 && prm.rms_max <= 4096.0)) return fail(DH_EINVAL, "%s: rms_max = %g outside (0, 4096]", who, prm.rms_max);
-    if (!(prm.max_jump > 0.0 && prm.max_jump <= 4096.0)) return fail(DH_EINVAL, "%s: max_jump = %g outside (0, 4096]", who, prm.max_jump);
-    if (prm.max_coast > prm.max_misses)
-        return fail(DH_EINVAL, "%s: max_coast %u above the max_misses %u the ids come from", who, prm.max_coast, prm.max_misses);
-    if (prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
-    if (!rig) return fail(DH_EINVAL, "%s: NULL rig table", who);
-    if (!views) return fail(DH_EINVAL, "%s: NULL view table", who);
-    if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
-    if (views->cams != rig->cams) return fail(DH_EINVAL, "%s: the rig table and the view table are bound to different camera tables", who);
-    if (m->device != rig->cams->device)
-        return fail(DH_EINVAL, "%s: the model lives on device %d, the tables on %d", who, m->device, rig->cams->device);
-    const double extent = fabs((double)scale) * m->radius;
-    if (extent > DH_FIT_MAX_EXTENT) return fail(DH_EINVAL, "%s: the model spans %g mm from its origin (limit %g)", who, extent, DH_FIT_MAX_EXTENT);
+    TRY(fit_tracker_create_check(prm, scale, flags, m, [&]() -> int {
+        if (prm.max_coast > prm.max_misses)
+            return fail(DH_EINVAL, "%s: max_coast %u above the max_misses %u the ids come from", who, prm.max_coast, prm.max_misses);
+        return DH_OK;
+    }, [&]() -> int {
+        if (!rig) return fail(DH_EINVAL, "%s: NULL rig table", who);
+        if (!views) return fail(DH_EINVAL, "%s: NULL view table", who);
+        if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
+        if (views->cams != rig->cams) return fail(DH_EINVAL, "%s: the rig table and the view table are bound to different camera tables", who);
+        if (m->device != rig->cams->device)
+            return fail(DH_EINVAL, "%s: the model lives on device %d, the tables on %d", who, m->device, rig->cams->device);
+        return DH_OK;
+    }, who));
     const int64_t largest = rig->largest;
     if ((uint64_t)largest * m->n > DH_FIT_MAX_POINTS)
         return fail(DH_EINVAL, "%s: a rig of %lld cameras sums %llu terms of a %u-point model, above %u", who, (long long)largest,
                     (unsigned long long)((uint64_t)largest * m->n), m->n, DH_FIT_MAX_POINTS);
     const size_t ng = (size_t)rig->n_rigs, slots = ng * DH_RIG_MAX_TRACKS;
     return create_tracker(rig->cams, out, [&](dh_rig_fit_tracker &t, size_t n) -> int {
-        t.rig = rig; t.views = views; t.model = m; t.scale = scale; t.flags = flags; t.prm = prm;
-        t.rms_lim = (int64_t)(prm.rms_max * prm.rms_max * 1048576.0);
-        t.jump2 = prm.max_jump * prm.max_jump;
+        t.rig = rig; t.views = views; t.prm = prm;
         TRY(t.state.alloc(slots));
-        TRY(t.angles.alloc(DH_FIT_TRACK_ANGLES * 2));
-        TRY(t.models.alloc(1));
         TRY(t.start.alloc(slots)); TRY(t.fit_out.alloc(slots)); TRY(t.fit_rec.alloc(slots));
-        TRY(t.sched.alloc(slots * 2)); TRY(t.seed.alloc(slots)); TRY(t.who.alloc(slots));
+        TRY(t.who.alloc(slots));
         TRY(t.heads.alloc(n * DH_MAX_HEADS)); TRY(t.n_heads.alloc(n)); TRY(t.ids.alloc(n * DH_MAX_HEADS));
         TRY(t.n_persons.alloc(ng)); TRY(t.persons.alloc(ng * DH_RIG_MAX_PERSONS)); TRY(t.tracks.alloc(ng * DH_RIG_MAX_TRACKS));
         TRY(t.records.alloc(slots));
-        const FitModel fm{m->pts.get(), m->nrm.get(), m->n, 0};
-        HIP_TRY(hipMemcpy(t.models.get(), &fm, sizeof fm, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(t.angles.get(), fit_track_angles().v, sizeof fit_track_angles().v, hipMemcpyHostToDevice));
-        return hip_step(hipStreamCreateWithFlags(&t.s, hipStreamNonBlocking), "hipStreamCreate");
+        return t.init_fit(m, scale, flags, prm.rms_max, prm.max_jump, slots);
     }, ng);
 }
-static int rig_fit_tracker_destroy_(dh_rig_fit_tracker *t) {
-    if (t) {
-        DeviceGuard guard(t->cams->device);
-        (void)hipDeviceSynchronize();
-    }
-    return destroy_tracker(t);
-}
+static int rig_fit_tracker_destroy_(dh_rig_fit_tracker *t) { return destroy_fit_tracker(t); }
 static int rig_fit_tracker_reset_(dh_rig_fit_tracker *t, int rig, void *stream) {
     return reset_tracker(t, rig, stream, "dh_rig_fit_tracker_reset", t ? t->rig->n_rigs : 0, "rig");
 }
@@ -3640,8 +3649,8 @@ static int rig_fit_enqueue(dh_rig_fit_tracker *t, const uint16_t *frames, int w,
     f.f.frames = frames; f.f.n = t->n; f.f.w = w; f.f.h = h;
     f.f.cams = t->cams->dev.get(); f.f.views = t->views->dev.get(); f.f.models = t->models.get();
     f.f.inst = t->start.get(); f.f.n_inst = (uint32_t)(a.n_rigs * DH_RIG_MAX_TRACKS);
-    f.f.min_points = prm.min_points; f.f.gate[0] = prm.gate[0]; f.f.gate[1] = prm.gate[1]; f.f.lam1 = 1.0 + prm.lambda;
-    f.f.out = t->fit_out.get(); f.f.rec = t->fit_rec.get();      // (k_fit_views_sched reads coarse and full per slot from sched)
+    fit_args_params(f.f, prm);                                   // (k_fit_views_sched reads coarse and full per slot from sched)
+    f.f.out = t->fit_out.get(); f.f.rec = t->fit_rec.get();
     f.sched = t->sched.get(); f.seed = t->seed.get(); f.group = DH_RIG_MAX_TRACKS;
     TRY(hip_step(dh_launch_rig_fit_seed(a, s), "k_rig_fit_seed"));
     TRY(hip_step(dh_launch_fit_views_sched(f, s), "k_fit_views_sched"));
@@ -3690,39 +3699,29 @@ static int rig_fit_tracker_step_device_(dh_predictor *p, dh_rig_fit_tracker *t, 
 static int rig_fit_host(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present,
                         int max_heads, const dh_fit_params &prm, uint32_t *n_heads, dh_head *heads, uint32_t *ids, uint32_t *n_persons,
                         dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records) {
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    const size_t n = (size_t)t->n, n_px = n * w * h, ng = (size_t)t->rig->n_rigs, mh = (size_t)max_heads;
-    if (t->frames.cap() < n_px) TRY(t->frames.alloc(n_px));       // (host steps are synchronous: nothing reads the old buffer)
-    hipStream_t s = t->s;
-    HIP_TRY(hipMemcpyAsync(t->frames.get(), frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-    if (present) HIP_TRY(hipMemcpyAsync(t->present.get(), present, n, hipMemcpyHostToDevice, s));
-    const uint8_t *pr = present ? t->present.get() : nullptr;
-    int rc;
-    if (p) rc = rig_tracker_step_device_(p, rt, t->frames.get(), w, h, pr, t->n_heads.get(), t->heads.get(), t->ids.get(), t->n_persons.get(),
-                                         t->persons.get(), tracks ? t->tracks.get() : nullptr, s);
-    else {
+    const size_t n = (size_t)t->n, ng = (size_t)t->rig->n_rigs, mh = (size_t)max_heads;
+    return fit_tracker_host(t, frames, w, h, present, [&](hipStream_t s) -> int {
+        if (p) return DH_OK;
         HIP_TRY(hipMemcpyAsync(t->n_heads.get(), n_heads, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(t->heads.get(), heads, n * mh * sizeof(dh_head), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(t->n_persons.get(), n_persons, ng * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(t->persons.get(), persons, ng * DH_RIG_MAX_PERSONS * sizeof(dh_rig_person), hipMemcpyHostToDevice, s));
-        rc = DH_OK;
-    }
-    if (rc == DH_OK)
-        rc = rig_fit_enqueue(t, t->frames.get(), w, h, pr, max_heads, t->n_heads.get(), t->heads.get(), t->n_persons.get(), t->persons.get(), prm,
-                             t->records.get(), s);
-    if (rc != DH_OK) { (void)hipStreamSynchronize(s); return rc; }
-    if (p) {
+        return DH_OK;
+    }, [&](const uint16_t *fr, const uint8_t *pr, hipStream_t s) -> int {
+        if (p) TRY(rig_tracker_step_device_(p, rt, fr, w, h, pr, t->n_heads.get(), t->heads.get(), t->ids.get(), t->n_persons.get(),
+                                            t->persons.get(), tracks ? t->tracks.get() : nullptr, s));
+        return rig_fit_enqueue(t, fr, w, h, pr, max_heads, t->n_heads.get(), t->heads.get(), t->n_persons.get(), t->persons.get(), prm,
+                               t->records.get(), s);
+    }, [&](hipStream_t s) -> int {
+        if (!p) return DH_OK;
         HIP_TRY(hipMemcpyAsync(n_heads, t->n_heads.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(heads, t->heads.get(), n * mh * sizeof(dh_head), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(ids, t->ids.get(), n * mh * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(n_persons, t->n_persons.get(), ng * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(persons, t->persons.get(), ng * DH_RIG_MAX_PERSONS * sizeof(dh_rig_person), hipMemcpyDeviceToHost, s));
         if (tracks) HIP_TRY(hipMemcpyAsync(tracks, t->tracks.get(), ng * DH_RIG_MAX_TRACKS * sizeof(dh_rig_track), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipMemcpyAsync(records, t->records.get(), ng * DH_RIG_MAX_TRACKS * sizeof(dh_rig_fit_record), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return DH_OK;
+        return DH_OK;
+    }, records, ng * DH_RIG_MAX_TRACKS);
 }
 static int rig_fit_tracker_step_persons_(dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
                                          const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons,

@@ -1,8 +1,9 @@
-// dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip) share with the host runtime
-// (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, and the one test of whether an instance
-// may be fitted (dh_fit_instance_fault: the host's refusals and the shape kernel's skips).  The device arithmetic the kernels
-// share among themselves is in dh_fit_device.h.  Not part of the ABI.  The rules are stated in include/depthhead_hip.h (sections
-// "fitting posed models to depth frames" and after) and DESIGN.md sections 18 - 22.
+// dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip)
+// share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
+// words of both trackers, and the one test of whether an instance may be fitted (dh_fit_instance_fault: the host's refusals and
+// the shape kernel's skips).  The device arithmetic the kernels share among themselves is in dh_fit_device.h.  Not part of the
+// ABI.  The rules are stated in include/depthhead_hip.h (sections "fitting posed models to depth frames" and after) and
+// DESIGN.md sections 18 - 22.
 #pragma once
 #include "dh_internal.h"
 #include "dh_rig_fit.h"
@@ -17,6 +18,13 @@ static_assert(sizeof(dh_fit_record) == 24, "dh_fit_record: 24 bytes");
 // 2^27; times 2^20, times 2^15 points (DH_FIT_MAX_POINTS): below 2^62 < 2^63.  The header says what holds outside that.
 #define DH_FIT_S 1048576.0
 #define DH_FIT_SUMS 29              // 21 A_ab (a <= b), 6 b_a, e and the count
+// The words of the reduction: A_ab at DH_FIT_PAIR(6, a, b) (a <= b, row after row of the upper triangle), then b_a, e and the
+// count; the multi-view fit keeps the mask of the views that were used in the word after them.
+#define DH_FIT_B 21
+#define DH_FIT_E 27
+#define DH_FIT_COUNT 28
+#define DH_FIT_USED 29
+static_assert(DH_FIT_COUNT + 1 == DH_FIT_SUMS && DH_FIT_USED < 32, "29 words and the mask, in the 32 words of a kernel's s_sum");
 // Where A_ab (a <= b) lies among sums laid out row after row as the upper triangle of a W x W matrix (the fit: 6, the shape step: 8)
 #define DH_FIT_PAIR(W, a, b) ((a) * (W) - (a) * ((a) - 1) / 2 + ((b) - (a)))
 // Points and normals are staged in LDS (24 bytes a point) up to this many points: 24 KB, which leaves six workgroups to a CU's
@@ -51,14 +59,17 @@ hipError_t dh_launch_fit(const FitArgs &a, hipStream_t s);
 // Why an instance may not be fitted: the per-instance refusals of the header in their order, stated once for the host loops
 // (which turn the answer into their messages) and the shape kernel (which skips).  The magnitude bounds of the int64 sums, here
 // and at DH_SHAPE_*, rest on it.  radius: the model's largest |v|; largest: the basis's largest |B_k[i]| (0.0 where there is none).
-// (fit_run relies on the order of these values: it reports what comes before EXTENT, then the model's own refusals, then the rest)
+// (instance_model_refusal, dh_api.hip, relies on the order of these values: it reports what comes before EXTENT, then the model's
+// own refusals, then the rest)
 enum { DH_FIT_INST_OK = 0, DH_FIT_INST_NOT_FINITE, DH_FIT_INST_NOT_ORTHONORMAL, DH_FIT_INST_EXTENT, DH_FIT_INST_FIELD };
 struct FitInstanceFault {
     int why;                      // DH_FIT_INST_*
     int a, b;                     // NOT_ORTHONORMAL: the first element of R R^T (row after row, a <= b) out of tolerance
     double g;                     //   and its value
 };
-__host__ __device__ inline FitInstanceFault dh_fit_instance_fault(const dh_render_instance &in, double radius, double largest) {
+// Instance: dh_render_instance or dh_view_instance (whose R and t are the world pose); R, t and scale are what is read.
+template <typename Instance>
+__host__ __device__ inline FitInstanceFault dh_fit_instance_fault(const Instance &in, double radius, double largest) {
     // Every test is made, none branches.  The tests run from the LAST refusal of the header's order to the FIRST and each
     // failure overwrites the answer, so what is left at the end is the first failure in the header's order -- for R, the
     // first (a, b) row after row, which the host message prints.
@@ -87,13 +98,20 @@ static_assert(sizeof(dh_fit_track_params) == 56, "dh_fit_track_params: 56 bytes"
 static_assert(sizeof(dh_fit_track_state) == 76, "dh_fit_track_state: 76 bytes");
 static_assert(sizeof(dh_fit_track_record) == 104, "dh_fit_track_record: 104 bytes");
 
-// What k_fit_track_seed decided for a camera: the start kind in the low byte, DH_FIT_SEED_VALID when the detection is valid.
-#define DH_FIT_SEED_NONE 0u
-#define DH_FIT_SEED_FOREST 1u
-#define DH_FIT_SEED_CARRIED 2u
-#define DH_FIT_SEED_ABSENT 3u
-#define DH_FIT_SEED_VALID 0x100u
+// What a tracker's seed kernel (k_fit_track_seed for a camera, k_rig_fit_seed for a slot of a rig) decided: the start kind in
+// the low byte, one numbering for both trackers, and above it the flags that are each tracker's own.
+#define DH_FIT_SEED_NONE 0u           // nothing to fit and nothing tracked (the rig tracker: an unused slot, a record of zeros)
+#define DH_FIT_SEED_DETECTED 1u       // a start from the forest's detection
+#define DH_FIT_SEED_CARRIED 2u        // a start from the state
+#define DH_FIT_SEED_ABSENT 3u         // the camera is absent / the rig has no present camera
+#define DH_FIT_SEED_COAST 4u          // (the rig tracker) a tracked entry none of whose views is present
+#define DH_FIT_SEED_VALID 0x100u      // (the camera tracker) the detection is valid
 #define DH_FIT_TRACK_THREADS 64
+// Whether the seed word gives the instance no start: the *_sched kernels then do no work for it.
+__host__ __device__ inline bool dh_fit_seed_no_start(uint32_t seed) {
+    const uint32_t kind = seed & 0xffu;
+    return kind != DH_FIT_SEED_DETECTED && kind != DH_FIT_SEED_CARRIED;
+}
 
 // k_fit_sched: k_fit with each instance's (coarse, full) read from `sched` and no work for an instance without a start.
 struct FitSchedArgs {
@@ -205,12 +223,7 @@ hipError_t dh_launch_fit_views(const FitViewsArgs &a, hipStream_t s);
 
 // ---- carrying each rig person's fitted world pose across steps (k_rig_fit_track.hip and k_fit_views' per-instance-schedule
 // instance).  The bind of a step is stated in dh_rig_fit.h.
-// What k_rig_fit_seed decided for a slot: the start kind in the low byte, and what the slot is.
-#define DH_RIG_FIT_SEED_NONE 0u       // unused slot: a record of zeros
-#define DH_RIG_FIT_SEED_DETECTED 1u
-#define DH_RIG_FIT_SEED_CARRIED 2u
-#define DH_RIG_FIT_SEED_COAST 3u      // a tracked entry none of whose views is present
-#define DH_RIG_FIT_SEED_ABSENT 4u     // the rig has no present camera: the state is kept
+// What k_rig_fit_seed decided for a slot: a DH_FIT_SEED_* kind in the low byte (ABSENT: the state is kept), and what the slot is.
 #define DH_RIG_FIT_SEED_IS_SEEN 0x100u    // who[slot] is the slot's person
 #define DH_RIG_FIT_SEED_IS_ENTRY 0x200u   // the slot is an entry of the state (else an unbound person)
 #define DH_RIG_FIT_THREADS 64
@@ -219,7 +232,7 @@ hipError_t dh_launch_fit_views(const FitViewsArgs &a, hipStream_t s);
 struct FitViewsSchedArgs {
     FitViewsArgs f;               // coarse and full unused
     const uint32_t *sched;        // [n_inst][2]
-    const uint32_t *seed;         // [n_inst] DH_RIG_FIT_SEED_*
+    const uint32_t *seed;         // [n_inst] DH_FIT_SEED_* | DH_RIG_FIT_SEED_*
     uint32_t group;               // slots of a group (a rig's DH_RIG_MAX_TRACKS); n_inst is a multiple of it
 };
 hipError_t dh_launch_fit_views_sched(const FitViewsSchedArgs &a, hipStream_t s);

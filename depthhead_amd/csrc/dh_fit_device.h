@@ -1,7 +1,11 @@
-// dh_fit_device.h -- the device arithmetic that the fit (k_fit.hip, with its per-instance-schedule instance) and the shape step
-// (k_fit_shape.hip) must agree on bit for bit, each stated once: the per-point correspondence and the damped solve.  f64 with
-// + - * /, compares and casts only; every operation is rounded on its own, so the expression trees below are the contract
-// (tests/fit_ref.py and tests/shape_ref.py restate them).  Not part of the ABI.
+// dh_fit_device.h -- the device arithmetic that the fit family's kernels must agree on bit for bit, each piece stated once:
+//   the per-point correspondence and the damped solve     k_fit.hip, k_fit_views.hip, k_fit_shape.hip
+//   the pose, the modes of a pass, the step's helpers      k_fit.hip, k_fit_views.hip (each with its *_sched instance)
+//   the trackers' rule: table rotation, carried start,
+//   acceptance, jump test and the state updates            k_fit_track.hip, k_rig_fit_track.hip
+// f64 (the trackers: f32 too) with + - * /, compares and casts only; every operation is rounded on its own, so the expression
+// trees below are the contract (tests/fit_ref.py, shape_ref.py, view_fit_ref.py, fit_track_ref.py and rig_fit_track_ref.py
+// restate them).  Not part of the ABI.
 #pragma once
 #include "dh_device.h"
 #include "dh_fit.h"
@@ -76,4 +80,117 @@ __device__ __forceinline__ bool fit_solve_tri(const unsigned long long *sums, in
         x[i] = s / A[i][i];
     }
     return true;
+}
+
+// ---- the fit's pose, pass modes and step helpers (k_fit.hip and k_fit_views.hip; DESIGN.md sections 18 and 21)
+#define FIT_COARSE 0
+#define FIT_FULL 1
+#define FIT_LAST 2
+// The pose a fit carries in registers (the multi-view fit: the world pose).
+struct FitPose {
+    double R[9];
+    double t[3];
+};
+
+// The step's early exit: every one of the first n elements of x is below 1e-6 in magnitude.
+__device__ __forceinline__ bool fit_small(const double x[6], int n) {
+    bool small = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+        if (i < n) small = small && ((x[i] < 0.0 ? -x[i] : x[i]) < 1e-6);
+    return small;
+}
+
+// R = C R with C the Cayley rotation of a = w / 2 (the element order of the header)
+__device__ __forceinline__ void fit_cayley(double R[9], const double w[3]) {
+    const double a0 = w[0] / 2.0, a1 = w[1] / 2.0, a2 = w[2] / 2.0;
+    const double q = (a0 * a0 + a1 * a1) + a2 * a2;
+    const double s = 1.0 + q, d = 1.0 - q;
+    const double u0 = 2.0 * a0, u1 = 2.0 * a1, u2 = 2.0 * a2;
+    double C[9];
+    C[0] = (d + u0 * a0) / s;  C[1] = (u0 * a1 - u2) / s; C[2] = (u0 * a2 + u1) / s;
+    C[3] = (u1 * a0 + u2) / s; C[4] = (d + u1 * a1) / s;  C[5] = (u1 * a2 - u0) / s;
+    C[6] = (u2 * a0 - u1) / s; C[7] = (u2 * a1 + u0) / s; C[8] = (d + u2 * a2) / s;
+    double o[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = (C[3 * i] * R[j] + C[3 * i + 1] * R[3 + j]) + C[3 * i + 2] * R[6 + j];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = o[i];
+}
+
+// ---- the trackers' rule (k_fit_track.hip: one lane per camera; k_rig_fit_track.hip: one lane per slot of a rig; DESIGN.md
+// sections 19 and 22).  State: dh_fit_track_state or dh_rig_fit_state; Instance: dh_render_instance or dh_view_instance.
+__device__ __forceinline__ uint32_t fit_sat_inc(uint32_t v) { return v == 0xffffffffu ? v : v + 1u; }
+
+// o = A B, each element as (A[i][0] * B[0][j] + A[i][1] * B[1][j]) + A[i][2] * B[2][j]
+__device__ __forceinline__ void fit_mat3_mul(const double A[9], const double B[9], double o[9]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+
+// The forest's rotation as a matrix: each of the three angles picks its cosine and sine from the 120-entry table `angles`
+// ([120][2]: cos, sin), and R = X (Y Z) in f64.  The caller casts it.
+__device__ __forceinline__ void fit_track_rotation(const double rotation[3], const double *angles, double R[9]) {
+    double cs[3], sn[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double x = rotation[j] / 3.14159 * 60.0 + 60.5;
+        const int ri = !(x >= 0.0) ? 0 : x >= 119.0 ? 119 : (int)x;
+        cs[j] = angles[2 * ri]; sn[j] = angles[2 * ri + 1];
+    }
+    const double Z[9] = {cs[0], sn[0], 0.0, -sn[0], cs[0], 0.0, 0.0, 0.0, 1.0};
+    const double Y[9] = {cs[1], 0.0, sn[1], 0.0, 1.0, 0.0, -sn[1], 0.0, cs[1]};
+    const double X[9] = {1.0, 0.0, 0.0, 0.0, cs[2], -sn[2], 0.0, sn[2], cs[2]};
+    double M[9];
+    fit_mat3_mul(Y, Z, M);
+    fit_mat3_mul(X, M, R);
+}
+
+// The carried start: the state's R, and its t moved on at constant velocity where the tracker's flags ask for it and the state
+// has a step before its last.
+template <typename State, typename Instance>
+__device__ __forceinline__ void fit_track_carried_start(const State &st, uint32_t flags, Instance &in) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) in.R[q] = st.R[q];
+    const bool motion = (flags & DH_FIT_TRACK_MOTION) && st.have_prev;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) in.t[q] = motion ? st.t[q] + (st.t[q] - st.t_prev[q]) : st.t[q];
+}
+
+// Why a fit is not accepted, from its record alone (DH_FIT_TRACK_BAD_STATUS | BAD_POINTS | BAD_RMS; 0: nothing).
+// Record: dh_fit_record or dh_view_fit_record.
+template <typename Record>
+__device__ __forceinline__ uint32_t fit_track_why(const Record &fr, uint32_t keep_points, int64_t rms_lim) {
+    uint32_t why = 0;
+    if (fr.status != DH_FIT_OK) why |= DH_FIT_TRACK_BAD_STATUS;
+    if (fr.points < keep_points) why |= DH_FIT_TRACK_BAD_POINTS;
+    if (fr.sum_r2_fixed > rms_lim * (long long)fr.points) why |= DH_FIT_TRACK_BAD_RMS;
+    return why;
+}
+
+// DH_FIT_TRACK_BAD_JUMP where the fitted midpoint lies further than sqrt(jump2) from the detection's (NaN fails), else 0.
+__device__ __forceinline__ uint32_t fit_track_jump(const float fitted[3], const float detected[3], double jump2) {
+    const double dx = (double)fitted[0] - (double)detected[0], dy = (double)fitted[1] - (double)detected[1],
+                 dz = (double)fitted[2] - (double)detected[2];
+    return !((dx * dx + dy * dy) + dz * dz <= jump2) ? DH_FIT_TRACK_BAD_JUMP : 0u;
+}
+
+// The state after an accepted fit (a macro, as DH_FIT_CORRESPOND is), and after a rejected one.
+#define DH_FIT_TRACK_ACCEPT(st, fit)                                                                                           \
+    do {                                                                                                                       \
+        _Pragma("unroll") for (int q = 0; q < 3; ++q) { (st).t_prev[q] = (st).t[q]; (st).t[q] = (fit).t[q]; }                  \
+        _Pragma("unroll") for (int q = 0; q < 9; ++q) (st).R[q] = (fit).R[q];                                                  \
+        (st).have_prev = (st).tracked;                                                                                         \
+        (st).tracked = 1;                                                                                                      \
+        (st).age = fit_sat_inc((st).age);                                                                                      \
+        (st).lost = 0;                                                                                                         \
+    } while (0)
+template <typename State>
+__device__ __forceinline__ void fit_track_reject(State &st) {
+    st.tracked = 0; st.have_prev = 0; st.age = 0;
+    st.lost = fit_sat_inc(st.lost);
 }

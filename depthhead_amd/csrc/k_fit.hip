@@ -1,5 +1,5 @@
 // k_fit.hip -- posed point models fitted to depth frames: point-to-plane ICP with projective association (DESIGN.md section 18;
-// the rule is stated in include/depthhead_hip.h, section "fitting posed models to depth frames").  One kernel body, FIT_BLOCK,
+// the rule is stated in include/depthhead_hip.h, section "fitting posed models to depth frames").  One kernel body, DH_FIT_BLOCK,
 // in two instances (k_fit, and k_fit_sched with a schedule per instance): one workgroup of 256 lanes per instance runs the whole
 // schedule -- every pass, every step, the last pass -- inside one launch.
 //   pass   each lane strides over the model's points (staged in LDS up to DH_FIT_LDS_POINTS, else streamed), finds each point's
@@ -10,24 +10,11 @@
 //   step   after a barrier every lane solves the same system redundantly in f64 (fit_solve_tri, dh_fit_device.h: deterministic,
 //          cheaper than a broadcast) and carries the pose (R, t: 12 doubles) in registers.
 // f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free: bit-identical
-// run to run and to tests/fit_ref.py.
+// run to run and to tests/fit_ref.py.  The pose (FitPose), the modes of a pass and the step's helpers (fit_small, fit_cayley) are
+// dh_fit_device.h's, which k_fit_views.hip shares; the offsets of the sums are dh_fit.h's.
 #include "dh_fit_device.h"
 
 #pragma clang fp contract(off)
-
-#define FIT_COARSE 0
-#define FIT_FULL 1
-#define FIT_LAST 2
-// the words of the reduction: A_ab at DH_FIT_PAIR(6, a, b) (a <= b, row after row of the upper triangle), b_a, e, count
-#define FIT_B 21
-#define FIT_E 27
-#define FIT_COUNT 28
-static_assert(FIT_COUNT + 1 == DH_FIT_SUMS, "29 words");
-
-struct FitPose {
-    double R[9];
-    double t[3];
-};
 
 // One pass at `pose` with gate `gate`: the sums of MODE into s_sum (zeroed here; valid for every lane after the return).
 template <int MODE, bool STAGED>
@@ -84,45 +71,18 @@ __device__ __forceinline__ void fit_pass(const FitArgs &a, const FitModel &m, co
                 if (lead) atomicAdd(&s_sum[DH_FIT_PAIR(6, ja, jb)], s);
             }
             const unsigned long long s = wave_sum_u64((uint64_t)accB[ja]);
-            if (lead) atomicAdd(&s_sum[FIT_B + ja], s);
+            if (lead) atomicAdd(&s_sum[DH_FIT_B + ja], s);
         }
     }
     if (MODE == FIT_LAST) {
         const unsigned long long s = wave_sum_u64((uint64_t)e);
-        if (lead) atomicAdd(&s_sum[FIT_E], s);
+        if (lead) atomicAdd(&s_sum[DH_FIT_E], s);
     }
     {
         const unsigned long long s = wave_sum_u64((uint64_t)cnt);
-        if (lead) atomicAdd(&s_sum[FIT_COUNT], s);
+        if (lead) atomicAdd(&s_sum[DH_FIT_COUNT], s);
     }
     __syncthreads();
-}
-
-__device__ __forceinline__ bool fit_small(const double x[6], int n) {
-    bool small = true;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-        if (i < n) small = small && ((x[i] < 0.0 ? -x[i] : x[i]) < 1e-6);
-    return small;
-}
-
-// R = C R with C the Cayley rotation of a = w / 2 (the element order of the header)
-__device__ __forceinline__ void fit_cayley(double R[9], const double w[3]) {
-    const double a0 = w[0] / 2.0, a1 = w[1] / 2.0, a2 = w[2] / 2.0;
-    const double q = (a0 * a0 + a1 * a1) + a2 * a2;
-    const double s = 1.0 + q, d = 1.0 - q;
-    const double u0 = 2.0 * a0, u1 = 2.0 * a1, u2 = 2.0 * a2;
-    double C[9];
-    C[0] = (d + u0 * a0) / s;  C[1] = (u0 * a1 - u2) / s; C[2] = (u0 * a2 + u1) / s;
-    C[3] = (u1 * a0 + u2) / s; C[4] = (d + u1 * a1) / s;  C[5] = (u1 * a2 - u0) / s;
-    C[6] = (u2 * a0 - u1) / s; C[7] = (u2 * a1 + u0) / s; C[8] = (d + u2 * a2) / s;
-    double o[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[3 * i + j] = (C[3 * i] * R[j] + C[3 * i + 1] * R[3 + j]) + C[3 * i + 2] * R[6 + j];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = o[i];
 }
 
 template <bool STAGED>
@@ -143,9 +103,9 @@ __device__ __forceinline__ void fit_run(const FitArgs &a, const dh_render_instan
     bool stop = false;
     for (uint32_t it = 0; it < a.coarse; ++it) {
         fit_pass<FIT_COARSE, STAGED>(a, m, s_pts, frame, K, scale, pose, a.gate[0], s_sum);
-        if ((uint32_t)s_sum[FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; stop = true; break; }
+        if ((uint32_t)s_sum[DH_FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; stop = true; break; }
         double x[6] = {0, 0, 0, 0, 0, 0};
-        if (!fit_solve_tri<3, 6>(s_sum, FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; stop = true; break; }
+        if (!fit_solve_tri<3, 6>(s_sum, DH_FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; stop = true; break; }
 #pragma unroll
         for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
         ++steps;
@@ -153,9 +113,9 @@ __device__ __forceinline__ void fit_run(const FitArgs &a, const dh_render_instan
     }
     for (uint32_t it = 0; it < a.full && !stop; ++it) {
         fit_pass<FIT_FULL, STAGED>(a, m, s_pts, frame, K, scale, pose, a.gate[1], s_sum);
-        if ((uint32_t)s_sum[FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; break; }
+        if ((uint32_t)s_sum[DH_FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; break; }
         double x[6];
-        if (!fit_solve_tri<6, 6>(s_sum, FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
+        if (!fit_solve_tri<6, 6>(s_sum, DH_FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
 #pragma unroll
         for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
         fit_cayley(pose.R, x + 3);
@@ -171,11 +131,11 @@ __device__ __forceinline__ void fit_run(const FitArgs &a, const dh_render_instan
         for (int q = 0; q < 3; ++q) o.t[q] = (float)pose.t[q];
         a.out[blockIdx.x] = o;
         dh_fit_record rec;
-        rec.points = (uint32_t)s_sum[FIT_COUNT];
+        rec.points = (uint32_t)s_sum[DH_FIT_COUNT];
         rec.steps = steps;
         rec.status = status;
         rec.reserved = 0;
-        rec.sum_r2_fixed = (int64_t)s_sum[FIT_E];
+        rec.sum_r2_fixed = (int64_t)s_sum[DH_FIT_E];
         a.rec[blockIdx.x] = rec;
     }
 }
@@ -183,7 +143,7 @@ __device__ __forceinline__ void fit_run(const FitArgs &a, const dh_render_instan
 // One instance's whole fit, the body of both kernels: the model staged into LDS where it fits, then the schedule of `a` (the
 // first pass's barriers order the staging before its reads).  A macro: both kernels compile from the very tokens, and the
 // __shared__ arrays are each kernel's own.
-#define FIT_BLOCK(a)                                                                                                           \
+#define DH_FIT_BLOCK(a)                                                                                                           \
     __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];                                                                             \
     __shared__ unsigned long long s_sum[32];                                                                                   \
     const dh_render_instance *in = (a).inst + blockIdx.x;                                                                      \
@@ -197,16 +157,15 @@ __device__ __forceinline__ void fit_run(const FitArgs &a, const dh_render_instan
         fit_run<true>(a, in, m, s_pts, s_sum);                                                                                 \
     } else fit_run<false>(a, in, m, s_pts, s_sum)
 
-__global__ __launch_bounds__(DH_FIT_THREADS) void k_fit(const FitArgs a) { FIT_BLOCK(a); }
+__global__ __launch_bounds__(DH_FIT_THREADS) void k_fit(const FitArgs a) { DH_FIT_BLOCK(a); }
 
 // The per-instance-schedule instance (dh_fit_tracker_step*): instance b runs (sched[b][0], sched[b][1]); a workgroup whose
 // instance has no start (uniform over the workgroup) leaves before the model is staged and writes nothing.
 __global__ __launch_bounds__(DH_FIT_THREADS) void k_fit_sched(const FitSchedArgs q) {
-    const uint32_t kind = q.seed[blockIdx.x] & 0xffu;
-    if (kind != DH_FIT_SEED_FOREST && kind != DH_FIT_SEED_CARRIED) return;
+    if (dh_fit_seed_no_start(q.seed[blockIdx.x])) return;
     FitArgs a = q.f;
     a.coarse = q.sched[2 * blockIdx.x]; a.full = q.sched[2 * blockIdx.x + 1];
-    FIT_BLOCK(a);
+    DH_FIT_BLOCK(a);
 }
 
 // ------------------------------------------------------------------ launcher

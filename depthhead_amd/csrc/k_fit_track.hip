@@ -4,21 +4,11 @@
 //   k_fit_track_seed    steps 0 - 2: absent / detection valid / the start instance, its schedule and its kind;
 //   k_fit_track_update  steps 4 - 6: acceptance, the camera's state and its record.
 // f32 and f64 with + - * /, compares and casts only, every operation rounded on its own; the cosines and sines come from the
-// host's 120-entry table.  Bit-identical to tests/fit_track_ref.py.
-#include "dh_device.h"
-#include "dh_fit.h"
+// host's 120-entry table.  Bit-identical to tests/fit_track_ref.py.  The rule's pieces that the rig tracker (k_rig_fit_track.hip)
+// applies too -- the table rotation, the carried start, acceptance, the jump test and the state updates -- are dh_fit_device.h's.
+#include "dh_fit_device.h"
 
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ uint32_t sat_inc(uint32_t v) { return v == 0xffffffffu ? v : v + 1u; }
-
-// o = A B, each element as (A[i][0] * B[0][j] + A[i][1] * B[1][j]) + A[i][2] * B[2][j]
-__device__ __forceinline__ void mat3_mul(const double A[9], const double B[9], double o[9]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
 
 __global__ __launch_bounds__(DH_FIT_TRACK_THREADS) void k_fit_track_seed(const FitTrackArgs a) {
     const int c = blockIdx.x * DH_FIT_TRACK_THREADS + threadIdx.x;
@@ -42,28 +32,13 @@ __global__ __launch_bounds__(DH_FIT_TRACK_THREADS) void k_fit_track_seed(const F
         if (st.tracked) {
             kind = DH_FIT_SEED_CARRIED;
             full = a.prm.iterations_tracked;
-#pragma unroll
-            for (int q = 0; q < 9; ++q) in.R[q] = st.R[q];
-            const bool motion = (a.flags & DH_FIT_TRACK_MOTION) && st.have_prev;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) in.t[q] = motion ? st.t[q] + (st.t[q] - st.t_prev[q]) : st.t[q];
+            fit_track_carried_start(st, a.flags, in);
         } else if (valid) {
-            kind = DH_FIT_SEED_FOREST;
+            kind = DH_FIT_SEED_DETECTED;
             coarse = a.coarse; full = a.full;
             const dh_pose po = a.poses[c];
-            double cs[3], sn[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const double x = po.rotation[j] / 3.14159 * 60.0 + 60.5;
-                const int ri = !(x >= 0.0) ? 0 : x >= 119.0 ? 119 : (int)x;
-                cs[j] = a.angles[2 * ri]; sn[j] = a.angles[2 * ri + 1];
-            }
-            const double Z[9] = {cs[0], sn[0], 0.0, -sn[0], cs[0], 0.0, 0.0, 0.0, 1.0};
-            const double Y[9] = {cs[1], 0.0, sn[1], 0.0, 1.0, 0.0, -sn[1], 0.0, cs[1]};
-            const double X[9] = {1.0, 0.0, 0.0, 0.0, cs[2], -sn[2], 0.0, sn[2], cs[2]};
-            double M[9], R[9];
-            mat3_mul(Y, Z, M);
-            mat3_mul(X, M, R);
+            double R[9];
+            fit_track_rotation(po.rotation, a.angles, R);
 #pragma unroll
             for (int q = 0; q < 9; ++q) in.R[q] = (float)R[q];
 #pragma unroll
@@ -90,7 +65,7 @@ __global__ __launch_bounds__(DH_FIT_TRACK_THREADS) void k_fit_track_update(const
 #pragma unroll
         for (int q = 0; q < 3; ++q) rec.instance.t[q] = 0.0f;
         rec.fit.points = 0; rec.fit.steps = 0; rec.fit.status = 0; rec.fit.reserved = 0; rec.fit.sum_r2_fixed = 0;
-        st.lost = sat_inc(st.lost);
+        st.lost = fit_sat_inc(st.lost);
         st.have_prev = 0;
         if (kind == DH_FIT_SEED_ABSENT) {
             if (st.lost > a.prm.max_coast) { st.tracked = 0; st.age = 0; }
@@ -102,31 +77,15 @@ __global__ __launch_bounds__(DH_FIT_TRACK_THREADS) void k_fit_track_update(const
     } else {
         const dh_render_instance fit = a.fit_out[c];
         const dh_fit_record fr = a.fit_rec[c];
-        uint32_t why = 0;
-        if (fr.status != DH_FIT_OK) why |= DH_FIT_TRACK_BAD_STATUS;
-        if (fr.points < a.prm.keep_points) why |= DH_FIT_TRACK_BAD_POINTS;
-        if (fr.sum_r2_fixed > a.rms_lim * (long long)fr.points) why |= DH_FIT_TRACK_BAD_RMS;
-        if (seed & DH_FIT_SEED_VALID) {
-            const dh_pose po = a.poses[c];
-            const double dx = (double)fit.t[0] - (double)po.mid_point[0], dy = (double)fit.t[1] - (double)po.mid_point[1],
-                         dz = (double)fit.t[2] - (double)po.mid_point[2];
-            if (!((dx * dx + dy * dy) + dz * dz <= a.jump2)) why |= DH_FIT_TRACK_BAD_JUMP;
-        }
+        uint32_t why = fit_track_why(fr, a.prm.keep_points, a.rms_lim);
+        if (seed & DH_FIT_SEED_VALID) why |= fit_track_jump(fit.t, a.poses[c].mid_point, a.jump2);
         rec.fit = fr;
         if (why == 0) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) { st.t_prev[q] = st.t[q]; st.t[q] = fit.t[q]; }
-#pragma unroll
-            for (int q = 0; q < 9; ++q) st.R[q] = fit.R[q];
-            st.have_prev = st.tracked;
-            st.tracked = 1;
-            st.age = sat_inc(st.age);
-            st.lost = 0;
+            DH_FIT_TRACK_ACCEPT(st, fit);
             rec.instance = fit;
             rec.status = kind == DH_FIT_SEED_CARRIED ? DH_FIT_TRACK_CARRIED : DH_FIT_TRACK_FITTED;
         } else {
-            st.tracked = 0; st.have_prev = 0; st.age = 0;
-            st.lost = sat_inc(st.lost);
+            fit_track_reject(st);
             rec.instance = a.start[c];
             rec.status = DH_FIT_TRACK_REJECTED | why;
         }

@@ -12,24 +12,10 @@
 // f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free: bit-identical
 // run to run and to tests/view_fit_ref.py.  With one view, V = I and u = 0 every sum equals k_fit's.  One kernel body,
 // FIT_VIEWS_BLOCK, in two instances: k_fit_views, and k_fit_views_sched with a schedule per instance.
+// The pose (FitPose), the modes of a pass and the step's helpers (fit_small, fit_cayley) are k_fit's very ones, in dh_fit_device.h.
 #include "dh_fit_device.h"
 
 #pragma clang fp contract(off)
-
-#define FV_COARSE 0
-#define FV_FULL 1
-#define FV_LAST 2
-// the words of the reduction: k_fit's 29 (A_ab at DH_FIT_PAIR(6, a, b), b_a, e, count) and the mask of the views that were used
-#define FV_B 21
-#define FV_E 27
-#define FV_COUNT 28
-#define FV_USED 29
-static_assert(FV_COUNT + 1 == DH_FIT_SUMS, "29 words and the mask");
-
-struct FitViewsPose {
-    double R[9];
-    double t[3];
-};
 
 // A value that every lane of the workgroup holds alike, moved to scalar registers.
 __device__ __forceinline__ double uni(double v) {
@@ -43,8 +29,8 @@ __device__ __forceinline__ double uni(double v) {
 // into s_sum (zeroed here; valid for every lane after the return).
 template <int MODE, bool STAGED>
 __device__ __forceinline__ void fit_views_pass(const FitViewsArgs &a, const FitModel &m, const float *s_pts, uint32_t first_cam, uint64_t mask,
-                                               double scale, const FitViewsPose &pose, double gate, unsigned long long *s_sum) {
-    constexpr int NJ = MODE == FV_COARSE ? 3 : MODE == FV_FULL ? 6 : 0;
+                                               double scale, const FitPose &pose, double gate, unsigned long long *s_sum) {
+    constexpr int NJ = MODE == FIT_COARSE ? 3 : MODE == FIT_FULL ? 6 : 0;
     constexpr int NA = NJ * (NJ + 1) / 2;
     long long accA[NA > 0 ? NA : 1], accB[NJ > 0 ? NJ : 1];
 #pragma unroll
@@ -84,12 +70,12 @@ __device__ __forceinline__ void fit_views_pass(const FitViewsArgs &a, const FitM
                 nm[ax] = (double)(STAGED ? s_pts[(3 + ax) * DH_FIT_LDS_POINTS + i] : m.nrm[(size_t)i * 3 + ax]);
             }
             DH_FIT_CORRESPOND(v, nm, scale, Rv, tv, K, frame, a.w, dw, dh, gate);
-            if (MODE == FV_LAST) e += (long long)((res * res) * DH_FIT_S);
+            if (MODE == FIT_LAST) e += (long long)((res * res) * DH_FIT_S);
             else {
                 double J[6];
 #pragma unroll
                 for (int j = 0; j < 3; ++j) J[j] = (V[j] * n[0] + V[3 + j] * n[1]) + V[6 + j] * n[2];
-                if (MODE == FV_FULL) {
+                if (MODE == FIT_FULL) {
                     const double q0 = p[0] - tv[0], q1 = p[1] - tv[1], q2 = p[2] - tv[2];
                     const double m0 = q1 * n[2] - q2 * n[1];
                     const double m1 = q2 * n[0] - q0 * n[2];
@@ -107,7 +93,7 @@ __device__ __forceinline__ void fit_views_pass(const FitViewsArgs &a, const FitM
             }
             cnt += 1;
         }
-        if (MODE == FV_LAST && __ballot(cnt != before) != 0) used |= 1ull << bit;
+        if (MODE == FIT_LAST && __ballot(cnt != before) != 0) used |= 1ull << bit;
     }
     const bool lead = (threadIdx.x & 63) == 0;
     {
@@ -120,47 +106,21 @@ __device__ __forceinline__ void fit_views_pass(const FitViewsArgs &a, const FitM
                 if (lead) atomicAdd(&s_sum[DH_FIT_PAIR(6, ja, jb)], s);
             }
             const unsigned long long s = wave_sum_u64((uint64_t)accB[ja]);
-            if (lead) atomicAdd(&s_sum[FV_B + ja], s);
+            if (lead) atomicAdd(&s_sum[DH_FIT_B + ja], s);
         }
     }
-    if (MODE == FV_LAST) {
+    if (MODE == FIT_LAST) {
         const unsigned long long s = wave_sum_u64((uint64_t)e);
         if (lead) {
-            atomicAdd(&s_sum[FV_E], s);
-            atomicOr(&s_sum[FV_USED], (unsigned long long)used);
+            atomicAdd(&s_sum[DH_FIT_E], s);
+            atomicOr(&s_sum[DH_FIT_USED], (unsigned long long)used);
         }
     }
     {
         const unsigned long long s = wave_sum_u64((uint64_t)cnt);
-        if (lead) atomicAdd(&s_sum[FV_COUNT], s);
+        if (lead) atomicAdd(&s_sum[DH_FIT_COUNT], s);
     }
     __syncthreads();
-}
-
-// (fit_small and fit_cayley of k_fit.hip, which keeps them to itself: the step's early exit and R = C R in the header's order)
-__device__ __forceinline__ bool fit_views_small(const double x[6], int n) {
-    bool small = true;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-        if (i < n) small = small && ((x[i] < 0.0 ? -x[i] : x[i]) < 1e-6);
-    return small;
-}
-__device__ __forceinline__ void fit_views_cayley(double R[9], const double w[3]) {
-    const double a0 = w[0] / 2.0, a1 = w[1] / 2.0, a2 = w[2] / 2.0;
-    const double q = (a0 * a0 + a1 * a1) + a2 * a2;
-    const double s = 1.0 + q, d = 1.0 - q;
-    const double u0 = 2.0 * a0, u1 = 2.0 * a1, u2 = 2.0 * a2;
-    double C[9];
-    C[0] = (d + u0 * a0) / s;  C[1] = (u0 * a1 - u2) / s; C[2] = (u0 * a2 + u1) / s;
-    C[3] = (u1 * a0 + u2) / s; C[4] = (d + u1 * a1) / s;  C[5] = (u1 * a2 - u0) / s;
-    C[6] = (u2 * a0 - u1) / s; C[7] = (u2 * a1 + u0) / s; C[8] = (d + u2 * a2) / s;
-    double o[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[3 * i + j] = (C[3 * i] * R[j] + C[3 * i + 1] * R[3 + j]) + C[3 * i + 2] * R[6 + j];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = o[i];
 }
 
 template <bool STAGED>
@@ -170,7 +130,7 @@ __device__ __forceinline__ void fit_views_run(const FitViewsArgs &a, uint32_t b,
     const uint64_t views = in->views;
     const uint64_t mask = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(views >> 32)) << 32) |
                           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)views);
-    FitViewsPose pose;
+    FitPose pose;
 #pragma unroll
     for (int q = 0; q < 9; ++q) pose.R[q] = (double)in->R[q];
 #pragma unroll
@@ -179,27 +139,27 @@ __device__ __forceinline__ void fit_views_run(const FitViewsArgs &a, uint32_t b,
     uint32_t steps = 0, status = DH_FIT_OK;
     bool stop = false;
     for (uint32_t it = 0; it < a.coarse; ++it) {
-        fit_views_pass<FV_COARSE, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[0], s_sum);
-        if ((uint32_t)s_sum[FV_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; stop = true; break; }
+        fit_views_pass<FIT_COARSE, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[0], s_sum);
+        if ((uint32_t)s_sum[DH_FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; stop = true; break; }
         double x[6] = {0, 0, 0, 0, 0, 0};
-        if (!fit_solve_tri<3, 6>(s_sum, FV_B, a.lam1, x)) { status = DH_FIT_SINGULAR; stop = true; break; }
+        if (!fit_solve_tri<3, 6>(s_sum, DH_FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; stop = true; break; }
 #pragma unroll
         for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
         ++steps;
-        if (fit_views_small(x, 3)) break;
+        if (fit_small(x, 3)) break;
     }
     for (uint32_t it = 0; it < a.full && !stop; ++it) {
-        fit_views_pass<FV_FULL, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[1], s_sum);
-        if ((uint32_t)s_sum[FV_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; break; }
+        fit_views_pass<FIT_FULL, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[1], s_sum);
+        if ((uint32_t)s_sum[DH_FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; break; }
         double x[6];
-        if (!fit_solve_tri<6, 6>(s_sum, FV_B, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
+        if (!fit_solve_tri<6, 6>(s_sum, DH_FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
 #pragma unroll
         for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
-        fit_views_cayley(pose.R, x + 3);
+        fit_cayley(pose.R, x + 3);
         ++steps;
-        if (fit_views_small(x, 6)) break;
+        if (fit_small(x, 6)) break;
     }
-    fit_views_pass<FV_LAST, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[1], s_sum);
+    fit_views_pass<FIT_LAST, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[1], s_sum);
     if (threadIdx.x == 0) {
         dh_view_instance o = *in;
 #pragma unroll
@@ -208,12 +168,12 @@ __device__ __forceinline__ void fit_views_run(const FitViewsArgs &a, uint32_t b,
         for (int q = 0; q < 3; ++q) o.t[q] = (float)pose.t[q];
         a.out[b] = o;
         dh_view_fit_record rec;
-        rec.points = (uint32_t)s_sum[FV_COUNT];
+        rec.points = (uint32_t)s_sum[DH_FIT_COUNT];
         rec.steps = steps;
         rec.status = status;
         rec.reserved = 0;
-        rec.sum_r2_fixed = (int64_t)s_sum[FV_E];
-        rec.views_used = (uint64_t)s_sum[FV_USED];
+        rec.sum_r2_fixed = (int64_t)s_sum[DH_FIT_E];
+        rec.views_used = (uint64_t)s_sum[DH_FIT_USED];
         a.rec[b] = rec;
     }
 }
@@ -246,8 +206,7 @@ __global__ __launch_bounds__(DH_FIT_THREADS) void k_fit_views(const FitViewsArgs
 __global__ __launch_bounds__(DH_FIT_THREADS) void k_fit_views_sched(const FitViewsSchedArgs q) {
     const uint32_t groups = q.f.n_inst / q.group;
     const uint32_t b = (blockIdx.x % groups) * q.group + blockIdx.x / groups;      // < n_inst: blockIdx.x / groups < group
-    const uint32_t kind = q.seed[b] & 0xffu;
-    if (kind != DH_RIG_FIT_SEED_DETECTED && kind != DH_RIG_FIT_SEED_CARRIED) return;
+    if (dh_fit_seed_no_start(q.seed[b])) return;
     FitViewsArgs a = q.f;
     a.coarse = q.sched[2 * b]; a.full = q.sched[2 * b + 1];
     FIT_VIEWS_BLOCK(a, b);

@@ -6,24 +6,15 @@
 //                     per slot composes the slot's start instance, its schedule and its kind;
 //   k_rig_fit_update  steps 4 - 6, one lane per slot: acceptance, the entry's state and the slot's record.
 // f32 and f64 with + - * /, compares and casts only, every operation rounded on its own; the cosines and sines come from the
-// host's 120-entry table (section 19's).  Bit-identical to tests/rig_fit_track_ref.py.
-#include "dh_device.h"
-#include "dh_fit.h"
+// host's 120-entry table (section 19's).  Bit-identical to tests/rig_fit_track_ref.py.  The pieces of the rule that are the
+// camera tracker's (k_fit_track.hip) -- the table rotation, the carried start, acceptance, the jump test and the state updates --
+// are dh_fit_device.h's; what is here is the bind, the views and the slots.
+#include "dh_fit_device.h"
 
 #pragma clang fp contract(off)
 
 static_assert(DH_RIG_MAX_TRACKS <= DH_RIG_FIT_THREADS, "one lane per slot of a rig");
 static_assert(sizeof(dh_rig_fit_state) % 4 == 0 && sizeof(dh_rig_person) % 4 == 0, "copied to LDS word by word");
-
-__device__ __forceinline__ uint32_t rf_sat_inc(uint32_t v) { return v == 0xffffffffu ? v : v + 1u; }
-
-// o = A B, each element as (A[i][0] * B[0][j] + A[i][1] * B[1][j]) + A[i][2] * B[2][j]
-__device__ __forceinline__ void rf_mat3_mul(const double A[9], const double B[9], double o[9]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
 
 __global__ __launch_bounds__(DH_RIG_FIT_THREADS) void k_rig_fit_seed(const RigFitArgs a) {
     __shared__ dh_rig_fit_state s_st[DH_RIG_MAX_TRACKS];
@@ -37,7 +28,7 @@ __global__ __launch_bounds__(DH_RIG_FIT_THREADS) void k_rig_fit_seed(const RigFi
     const size_t slot = (size_t)g * DH_RIG_MAX_TRACKS + lane;
     if (pm == 0) {                                                 // (uniform) step 0: the state is kept
         if (lane < DH_RIG_MAX_TRACKS) {
-            a.seed[slot] = DH_RIG_FIT_SEED_ABSENT;
+            a.seed[slot] = DH_FIT_SEED_ABSENT;
             a.who[slot] = DH_RIG_FIT_NO_PERSON;
             a.sched[2 * slot] = 0; a.sched[2 * slot + 1] = 0;
         }
@@ -64,42 +55,27 @@ __global__ __launch_bounds__(DH_RIG_FIT_THREADS) void k_rig_fit_seed(const RigFi
     for (int q = 0; q < 9; ++q) in.R[q] = 0.0f;
 #pragma unroll
     for (int q = 0; q < 3; ++q) in.t[q] = 0.0f;
-    uint32_t kind = DH_RIG_FIT_SEED_NONE, coarse = 0, full = 0;
+    uint32_t kind = DH_FIT_SEED_NONE, coarse = 0, full = 0;
     if (role != DH_RIG_FIT_UNUSED) {
         const bool seen = pi != DH_RIG_FIT_NO_PERSON;
         const bool entry = role != DH_RIG_FIT_UNBOUND;
         if (entry && st.tracked) {
             in.views = (st.views_used | (seen ? s_p[pi].views : 0ull)) & pm;
-            if (in.views == 0) kind = DH_RIG_FIT_SEED_COAST;
+            if (in.views == 0) kind = DH_FIT_SEED_COAST;
             else {
-                kind = DH_RIG_FIT_SEED_CARRIED;
+                kind = DH_FIT_SEED_CARRIED;
                 full = a.prm.iterations_tracked;
-#pragma unroll
-                for (int q = 0; q < 9; ++q) in.R[q] = st.R[q];
-                const bool motion = (a.flags & DH_FIT_TRACK_MOTION) && st.have_prev;
-#pragma unroll
-                for (int q = 0; q < 3; ++q) in.t[q] = motion ? st.t[q] + (st.t[q] - st.t_prev[q]) : st.t[q];
+                fit_track_carried_start(st, a.flags, in);
             }
         } else {                                                   // detected: the slot has a person (the bind freed the rest)
             const dh_rig_person &p = s_p[pi];
-            kind = DH_RIG_FIT_SEED_DETECTED;
+            kind = DH_FIT_SEED_DETECTED;
             coarse = a.coarse; full = a.full;
             in.views = p.views & pm;
             // best_cam < n_cams and best_head < max_heads: the bind ignores every other person
             const dh_pose &po = a.heads[(size_t)p.best_cam * a.max_heads + p.best_head].pose;
-            double cs[3], sn[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const double x = po.rotation[j] / 3.14159 * 60.0 + 60.5;
-                const int ri = !(x >= 0.0) ? 0 : x >= 119.0 ? 119 : (int)x;
-                cs[j] = a.angles[2 * ri]; sn[j] = a.angles[2 * ri + 1];
-            }
-            const double Z[9] = {cs[0], sn[0], 0.0, -sn[0], cs[0], 0.0, 0.0, 0.0, 1.0};
-            const double Y[9] = {cs[1], 0.0, sn[1], 0.0, 1.0, 0.0, -sn[1], 0.0, cs[1]};
-            const double X[9] = {1.0, 0.0, 0.0, 0.0, cs[2], -sn[2], 0.0, sn[2], cs[2]};
-            double M[9], R[9], Rh[9], V[9];
-            rf_mat3_mul(Y, Z, M);
-            rf_mat3_mul(X, M, R);
+            double R[9], Rh[9], V[9];
+            fit_track_rotation(po.rotation, a.angles, R);
 #pragma unroll
             for (int q = 0; q < 9; ++q) {
                 Rh[q] = (double)(float)R[q];
@@ -130,8 +106,8 @@ __global__ __launch_bounds__(DH_RIG_FIT_THREADS) void k_rig_fit_update(const Rig
     const bool seen = (seed & DH_RIG_FIT_SEED_IS_SEEN) != 0, entry = (seed & DH_RIG_FIT_SEED_IS_ENTRY) != 0;
     dh_rig_fit_record rec;
     memset(&rec, 0, sizeof rec);
-    if (kind == DH_RIG_FIT_SEED_NONE || kind == DH_RIG_FIT_SEED_ABSENT) {
-        if (kind == DH_RIG_FIT_SEED_ABSENT) rec.status = DH_FIT_TRACK_ABSENT;
+    if (kind == DH_FIT_SEED_NONE || kind == DH_FIT_SEED_ABSENT) {
+        if (kind == DH_FIT_SEED_ABSENT) rec.status = DH_FIT_TRACK_ABSENT;
         a.records[slot] = rec;
         return;
     }
@@ -140,40 +116,25 @@ __global__ __launch_bounds__(DH_RIG_FIT_THREADS) void k_rig_fit_update(const Rig
     if (entry) st = a.state[slot];
     bool free_it = false;
     rec.person = pi;
-    if (kind == DH_RIG_FIT_SEED_COAST) {
-        st.lost = rf_sat_inc(st.lost);
+    if (kind == DH_FIT_SEED_COAST) {
+        st.lost = fit_sat_inc(st.lost);
         st.have_prev = 0;
         free_it = st.lost > a.prm.max_coast;
         rec.status = DH_FIT_TRACK_ABSENT;
     } else {
         const dh_view_instance fit = a.fit_out[slot];
         const dh_view_fit_record fr = a.fit_rec[slot];
-        uint32_t why = 0;
-        if (fr.status != DH_FIT_OK) why |= DH_FIT_TRACK_BAD_STATUS;
-        if (fr.points < a.prm.keep_points) why |= DH_FIT_TRACK_BAD_POINTS;
-        if (fr.sum_r2_fixed > a.rms_lim * (long long)fr.points) why |= DH_FIT_TRACK_BAD_RMS;
-        if (seen) {
-            const dh_rig_person &p = a.persons[(size_t)g * DH_RIG_MAX_PERSONS + pi];   // pi < DH_RIG_MAX_PERSONS: the bind's
-            const double dx = (double)fit.t[0] - (double)p.world[0], dy = (double)fit.t[1] - (double)p.world[1],
-                         dz = (double)fit.t[2] - (double)p.world[2];
-            if (!((dx * dx + dy * dy) + dz * dz <= a.jump2)) why |= DH_FIT_TRACK_BAD_JUMP;
-        }
+        uint32_t why = fit_track_why(fr, a.prm.keep_points, a.rms_lim);
+        // pi < DH_RIG_MAX_PERSONS: the bind's
+        if (seen) why |= fit_track_jump(fit.t, a.persons[(size_t)g * DH_RIG_MAX_PERSONS + pi].world, a.jump2);
         rec.fit = fr;
         if (why == 0) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) { st.t_prev[q] = st.t[q]; st.t[q] = fit.t[q]; }
-#pragma unroll
-            for (int q = 0; q < 9; ++q) st.R[q] = fit.R[q];
+            DH_FIT_TRACK_ACCEPT(st, fit);
             st.views_used = fr.views_used;
-            st.have_prev = st.tracked;
-            st.tracked = 1;
-            st.age = rf_sat_inc(st.age);
-            st.lost = 0;
             rec.instance = fit;
-            rec.status = kind == DH_RIG_FIT_SEED_CARRIED ? DH_FIT_TRACK_CARRIED : DH_FIT_TRACK_FITTED;
+            rec.status = kind == DH_FIT_SEED_CARRIED ? DH_FIT_TRACK_CARRIED : DH_FIT_TRACK_FITTED;
         } else {
-            st.tracked = 0; st.have_prev = 0; st.age = 0;
-            st.lost = rf_sat_inc(st.lost);
+            fit_track_reject(st);
             rec.instance = a.start[slot];
             rec.status = DH_FIT_TRACK_REJECTED | why;
             free_it = !seen;

@@ -384,7 +384,20 @@ def angles() -> np.ndarray:
     return out
 
 
-class FitTracker(_lib._Handle):
+class _StepInputs:
+    """What the host steps of both fit trackers make of their frames and present bytes (self.n cameras of self.h x self.w)."""
+
+    def _frames(self, frames) -> np.ndarray:
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.shape != (self.n, self.h, self.w):
+            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
+        return frames
+
+    def _present(self, present):
+        return None if present is None else np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
+
+
+class FitTracker(_StepInputs, _lib._Handle):
     """One dh_fit_tracker: each camera of `cameras` (a `tracking.Cameras`) carries its fitted head pose from
     step to step.  A step fits `model` to every present camera's frame -- from the carried pose, or from the forest's where
     there is none -- and decides whether the fit is believed; a rejected fit sends the camera back to the forest.  The state
@@ -398,15 +411,6 @@ class FitTracker(_lib._Handle):
         self._h = C.c_void_p()
         check(self._lib.dh_fit_tracker_create(cameras._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
                                               C.byref(params) if params is not None else None, C.byref(self._h)))
-
-    def _frames(self, frames) -> np.ndarray:
-        frames = np.ascontiguousarray(frames, dtype=np.uint16)
-        if frames.shape != (self.n, self.h, self.w):
-            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
-        return frames
-
-    def _present(self, present):
-        return None if present is None else np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
 
     def step_poses(self, frames, poses, support, present=None, fit_params=None) -> np.ndarray:
         """The core step from the forest's POSE_DTYPE [n] and SUPPORT_DTYPE [n] of host frames [n, h, w] u16:
@@ -474,7 +478,7 @@ def rig_fit_track_params(iterations_tracked=None, keep_points=None, rms_max=None
     return p
 
 
-class RigFitTracker(_lib._Handle):
+class RigFitTracker(_StepInputs, _lib._Handle):
     """One dh_rig_fit_tracker: every person of every rig of `rig` (a `tracking.Rig`) keeps one fitted pose in
     the world frame under the id a `tracking.RigTracker` gave it.  A step refits `model` against all the views (`views`, a `Views`
     of the rig's camera table, consistent with the rig: `views_from_rig`) from the carried pose, or from the person record where
@@ -490,15 +494,6 @@ class RigFitTracker(_lib._Handle):
         self._h = C.c_void_p()
         check(self._lib.dh_rig_fit_tracker_create(rig._h, views._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
                                                   C.byref(params) if params is not None else None, C.byref(self._h)))
-
-    def _frames(self, frames) -> np.ndarray:
-        frames = np.ascontiguousarray(frames, dtype=np.uint16)
-        if frames.shape != (self.n, self.h, self.w):
-            raise ValueError(f"frames must be [{self.n}, {self.h}, {self.w}]")
-        return frames
-
-    def _present(self, present):
-        return None if present is None else np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
 
     def step_persons(self, frames, n_heads, heads, n_persons, persons, present=None, fit_params=None) -> np.ndarray:
         """The core step from the outputs of a rig tracker step -- n_heads u32 [n_cams], HEAD_DTYPE [n_cams, max_heads], n_persons
