@@ -196,7 +196,7 @@ EXPORTS = [
     "dh_fit_tracker_state", "dh_fit_tracker_step_poses", "dh_fit_tracker_step_poses_device", "dh_fit_tracker_step",
     "dh_fit_tracker_step_device",
     "dh_fit_basis_create", "dh_fit_basis_destroy", "dh_fit_basis_info", "dh_shape_params_default", "dh_fit_shape", "dh_fit_shape_cameras",
-    "dh_fit_shape_device", "dh_fit_shape_cameras_device",
+    "dh_fit_shape_device", "dh_fit_shape_cameras_device", "dh_fit_shape_views", "dh_fit_shape_views_device",
     "dh_fit_views_create", "dh_fit_views_destroy", "dh_fit_views_info", "dh_fit_depth_views", "dh_fit_depth_views_device",
     "dh_rig_fit_track_params_default", "dh_rig_fit_tracker_create", "dh_rig_fit_tracker_destroy", "dh_rig_fit_tracker_reset",
     "dh_rig_fit_tracker_state", "dh_rig_fit_tracker_step_persons", "dh_rig_fit_tracker_step_persons_device", "dh_rig_fit_tracker_step",

@@ -2818,6 +2818,8 @@ struct dh_fitter {
     Buf<dh_render_instance> shape_inst;      // host shape calls
     Buf<uint32_t> shape_subj;
     Buf<dh_shape_record> shape_rec;
+    Buf<dh_view_instance> shape_vinst;       // host multi-view shape calls
+    Buf<uint32_t> shape_vsubj, shape_vsets;
     Buf<dh_view_instance> view_out;          // host multi-view calls
     Buf<dh_view_fit_record> view_rec;
     std::vector<unsigned char> view_cmp;     // a captured multi-view call's tables, to be compared with the staged ones
@@ -3181,6 +3183,48 @@ static int shape_params_default_(dh_shape_params *p) {
     return DH_OK;
 }
 
+// The refusals every shape call (single-view or multi-view) begins with, around those of its frames: the pointers, then the
+// subject count, the params (NULL: the defaults; *out is what the call runs with), the model and the basis, the instances.
+static int shape_check_pointers(const dh_fitter *f, const void *frames, const void *rec, const dh_fit_model *m, const dh_fit_basis *b, const char *who) {
+    if (!f) return fail(DH_EINVAL, "%s: NULL fitter", who);
+    if (!frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!rec) return fail(DH_EINVAL, "%s: NULL records", who);
+    if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
+    if (!b) return fail(DH_EINVAL, "%s: NULL basis", who);
+    return DH_OK;
+}
+static int shape_check_call(const dh_fitter *f, const dh_fit_model *m, const dh_fit_basis *b, uint32_t n_subjects, const dh_shape_params *in,
+                            dh_shape_params *out, const void *inst, uint32_t n_inst, const char *who) {
+    if (n_subjects < 1 || n_subjects > DH_SHAPE_MAX_SUBJECTS)
+        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u", who, n_subjects, DH_SHAPE_MAX_SUBJECTS);
+    dh_shape_params prm;
+    (void)shape_params_default_(&prm);
+    if (in) prm = *in;
+    if (!(prm.gate > 0.0 && prm.gate <= DH_SHAPE_MAX_GATE)) return fail(DH_EINVAL, "%s: gate = %g outside (0, %g]", who, prm.gate, DH_SHAPE_MAX_GATE);
+    if (!(prm.lambda >= 0.0) || !std::isfinite(prm.lambda)) return fail(DH_EINVAL, "%s: lambda %g, expected a finite value >= 0", who, prm.lambda);
+    if (prm.min_points < 1) return fail(DH_EINVAL, "%s: min_points 0 below 1", who);
+    if (prm.reserved0 || prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    if (m->device != f->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the fitter on %d", who, m->device, f->device);
+    if (b->device != f->device) return fail(DH_EINVAL, "%s: the basis lives on device %d, the fitter on %d", who, b->device, f->device);
+    if (b->n != m->n) return fail(DH_EINVAL, "%s: the basis is one of %u points, the model has %u", who, b->n, m->n);
+    if (n_inst && !inst) return fail(DH_EINVAL, "%s: NULL instances", who);
+    if (n_inst > DH_SHAPE_MAX_TERMS) return fail(DH_EINVAL, "%s: too many instances", who);
+    *out = prm;
+    return DH_OK;
+}
+// The half of a ShapeArgs that the model, the basis, the subjects and the (checked) params fill.
+static void shape_args_common(ShapeArgs &a, dh_fitter *f, const dh_fit_model *m, const dh_fit_basis *b, uint32_t n_inst, uint32_t n_subjects,
+                              const dh_shape_params &prm) {
+    a.pts = m->pts.get(); a.nrm = m->nrm.get(); a.basis = b->planes.get();
+    a.np = m->n; a.nk = b->k;
+    a.radius = m->radius; a.largest = b->largest;
+    a.n_inst = n_inst; a.n_subjects = n_subjects;
+    a.min_points = prm.min_points;
+    a.gate = prm.gate;
+    a.lam1 = 1.0 + prm.lambda;
+    a.sums = f->shape_sums.get();
+}
+
 // One shape call.  dev: frames / instances / subjects / records are device pointers and `stream` the caller's; else host pointers.
 struct ShapeReq {
     const uint16_t *frames; int n, w, h;
@@ -3193,28 +3237,12 @@ struct ShapeReq {
 };
 static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stream, const char *who) {
     // ---- refusals: all of them before anything is allocated or launched
-    if (!f) return fail(DH_EINVAL, "%s: NULL fitter", who);
-    if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
-    if (!q.rec) return fail(DH_EINVAL, "%s: NULL records", who);
-    if (!q.model) return fail(DH_EINVAL, "%s: NULL model", who);
-    if (!q.basis) return fail(DH_EINVAL, "%s: NULL basis", who);
+    TRY(shape_check_pointers(f, q.frames, q.rec, q.model, q.basis, who));
     TRY(check_frames(q.n, q.w, q.h, q.K, q.cams, q.use_cams, f->device, "fitter", who));
-    if (q.n_subjects < 1 || q.n_subjects > DH_SHAPE_MAX_SUBJECTS)
-        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u", who, q.n_subjects, DH_SHAPE_MAX_SUBJECTS);
     dh_shape_params prm;
-    (void)shape_params_default_(&prm);
-    if (q.prm) prm = *q.prm;
-    if (!(prm.gate > 0.0 && prm.gate <= DH_SHAPE_MAX_GATE)) return fail(DH_EINVAL, "%s: gate = %g outside (0, %g]", who, prm.gate, DH_SHAPE_MAX_GATE);
-    if (!(prm.lambda >= 0.0) || !std::isfinite(prm.lambda)) return fail(DH_EINVAL, "%s: lambda %g, expected a finite value >= 0", who, prm.lambda);
-    if (prm.min_points < 1) return fail(DH_EINVAL, "%s: min_points 0 below 1", who);
-    if (prm.reserved0 || prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    TRY(shape_check_call(f, q.model, q.basis, q.n_subjects, q.prm, &prm, q.inst, q.n_inst, who));
     const dh_fit_model *m = q.model;
     const dh_fit_basis *b = q.basis;
-    if (m->device != f->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the fitter on %d", who, m->device, f->device);
-    if (b->device != f->device) return fail(DH_EINVAL, "%s: the basis lives on device %d, the fitter on %d", who, b->device, f->device);
-    if (b->n != m->n) return fail(DH_EINVAL, "%s: the basis is one of %u points, the model has %u", who, b->n, m->n);
-    if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
-    if (q.n_inst > DH_SHAPE_MAX_TERMS) return fail(DH_EINVAL, "%s: too many instances", who);
     if (dev) {
         if ((uint64_t)q.n_inst * m->n > DH_SHAPE_MAX_TERMS)
             return fail(DH_EINVAL, "%s: %u instances of %u points exceed %u terms", who, q.n_inst, m->n, DH_SHAPE_MAX_TERMS);
@@ -3242,14 +3270,7 @@ static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stre
     a.n = q.n; a.w = q.w; a.h = q.h;
     if (q.use_cams) a.cams = q.cams->dev.get();
     else memcpy(a.k, q.K, sizeof a.k);
-    a.pts = m->pts.get(); a.nrm = m->nrm.get(); a.basis = b->planes.get();
-    a.np = m->n; a.nk = b->k;
-    a.radius = m->radius; a.largest = b->largest;
-    a.n_inst = q.n_inst; a.n_subjects = q.n_subjects;
-    a.min_points = prm.min_points;
-    a.gate = prm.gate;
-    a.lam1 = 1.0 + prm.lambda;
-    a.sums = f->shape_sums.get();
+    shape_args_common(a, f, m, b, q.n_inst, q.n_subjects, prm);
     if (!dev) {
         const size_t n_px = (size_t)q.n * q.w * q.h;
         if (f->frames.cap() < n_px || f->shape_inst.cap() < q.n_inst || f->shape_rec.cap() < q.n_subjects) HIP_TRY(hipDeviceSynchronize());
@@ -3291,6 +3312,110 @@ static int fit_shape_cameras_device_(dh_fitter *f, const uint16_t *frames, int n
                                      const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params,
                                      dh_shape_record *records, void *stream) {
     return shape_run(f, ShapeReq{frames, n, w, h, nullptr, c, true, model, basis, instances, n_instances, subjects, n_subjects, params, records}, true, (hipStream_t)stream, "dh_fit_shape_cameras_device");
+}
+
+// ------------------------------------------------------------------ adapting a model's shape across views
+// One multi-view shape call.  dev: frames / instances / sets / subjects / records are device pointers and `stream` the caller's.
+struct ShapeViewsReq {
+    const uint16_t *frames; uint32_t n_sets; int w, h;
+    const dh_fit_views *views;
+    const dh_fit_model *model; const dh_fit_basis *basis;
+    const dh_view_instance *inst; uint32_t n_inst;
+    const uint32_t *sets; const uint32_t *subjects; uint32_t n_subjects;
+    const dh_shape_params *prm;
+    dh_shape_record *rec;
+};
+static int shape_views_run(dh_fitter *f, const ShapeViewsReq &q, bool dev, hipStream_t stream, const char *who) {
+    // ---- refusals: all of them before anything is allocated or launched
+    TRY(shape_check_pointers(f, q.frames, q.rec, q.model, q.basis, who));
+    if (!q.views) return fail(DH_EINVAL, "%s: NULL view table", who);
+    if (q.views->device != f->device) return fail(DH_EINVAL, "%s: the view table lives on device %d, the fitter on %d", who, q.views->device, f->device);
+    const int n = q.views->n;
+    if (q.n_sets < 1 || (uint64_t)q.n_sets * (uint64_t)n > 65535)
+        return fail(DH_EINVAL, "%s: n_sets = %u of %d cameras, expected 1 .. 65535 frames", who, q.n_sets, n);
+    TRY(check_frames(n, q.w, q.h, nullptr, q.views->cams, true, f->device, "fitter", who));
+    dh_shape_params prm;
+    TRY(shape_check_call(f, q.model, q.basis, q.n_subjects, q.prm, &prm, q.inst, q.n_inst, who));
+    const dh_fit_model *m = q.model;
+    const dh_fit_basis *b = q.basis;
+    const uint32_t ranks = (uint32_t)std::min(64, n);
+    if (dev) {
+        if ((uint64_t)q.n_inst * ranks * m->n > DH_SHAPE_MAX_TERMS)
+            return fail(DH_EINVAL, "%s: %u instances of %u views of %u points exceed %u terms", who, q.n_inst, ranks, m->n, DH_SHAPE_MAX_TERMS);
+    } else {
+        std::vector<uint64_t> per(q.n_subjects, 0);
+        for (uint32_t i = 0; i < q.n_inst; ++i) {
+            const dh_view_instance &in = q.inst[i];
+            const uint32_t sj = q.subjects ? q.subjects[i] : 0u, set = q.sets ? q.sets[i] : 0u;
+            const ShapeViewsSkip sk = dh_shape_views_skip(in, set, sj, (uint32_t)n, q.n_sets, q.n_subjects, m->radius, b->largest);
+            switch (sk.why) {
+            case DH_SHAPE_VIEWS_OK: break;
+            case DH_SHAPE_VIEWS_SKIPPED: continue;
+            case DH_SHAPE_VIEWS_NO_VIEW: return fail(DH_EINVAL, "%s: instance %u is seen by no view", who, i);
+            case DH_SHAPE_VIEWS_CAMERA: return fail(DH_EINVAL, "%s: instance %u names camera %llu of %d", who, i, (unsigned long long)sk.last, n);
+            case DH_SHAPE_VIEWS_SET: return fail(DH_EINVAL, "%s: instance %u names set %u of %u", who, i, set, q.n_sets);
+            case DH_SHAPE_VIEWS_SUBJECT: return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, q.n_subjects);
+            default: return instance_refusal(sk.fault, in.scale, i, m->radius, b->largest, who);
+            }
+            per[sj] += (uint64_t)__builtin_popcountll(in.views) * m->n;
+            if (per[sj] > DH_SHAPE_MAX_TERMS)
+                return fail(DH_EINVAL, "%s: subject %u has more than %u terms (views times %u points)", who, sj, DH_SHAPE_MAX_TERMS, m->n);
+        }
+    }
+
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(f->tab.init());
+    hipStream_t s = dev ? stream : f->tab.s;
+    if (!f->shape_sums) TRY(f->shape_sums.alloc((size_t)DH_SHAPE_MAX_SUBJECTS * DH_SHAPE_STRIDE));
+    ShapeViewsArgs v;
+    memset(&v, 0, sizeof v);
+    ShapeArgs &a = v.s;
+    a.n = n; a.w = q.w; a.h = q.h;
+    a.cams = q.views->cams->dev.get();
+    shape_args_common(a, f, m, b, q.n_inst, q.n_subjects, prm);
+    v.views = q.views->dev.get();
+    v.n_sets = q.n_sets; v.ranks = ranks;
+    if (!dev) {
+        const size_t n_px = (size_t)q.n_sets * n * q.w * q.h;
+        if (f->frames.cap() < n_px || f->shape_vinst.cap() < q.n_inst || !f->shape_vinst || !f->shape_rec) HIP_TRY(hipDeviceSynchronize());
+        TRY(f->frames.grow(n_px));
+        if (f->shape_vinst.cap() < q.n_inst || !f->shape_vinst) {
+            TRY(f->shape_vinst.grow(std::max<size_t>(q.n_inst, 1)));
+            TRY(f->shape_vsubj.alloc(f->shape_vinst.cap()));
+            TRY(f->shape_vsets.alloc(f->shape_vinst.cap()));
+        }
+        if (!f->shape_rec) TRY(f->shape_rec.alloc(DH_SHAPE_MAX_SUBJECTS));
+        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        if (q.n_inst) HIP_TRY(hipMemcpyAsync(f->shape_vinst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_view_instance), hipMemcpyHostToDevice, s));
+        if (q.n_inst && q.subjects) HIP_TRY(hipMemcpyAsync(f->shape_vsubj.get(), q.subjects, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (q.n_inst && q.sets) HIP_TRY(hipMemcpyAsync(f->shape_vsets.get(), q.sets, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        a.frames = f->frames.get(); v.inst = f->shape_vinst.get();
+        a.subjects = q.subjects ? f->shape_vsubj.get() : nullptr;
+        v.sets = q.sets ? f->shape_vsets.get() : nullptr;
+        a.rec = f->shape_rec.get();
+    } else { a.frames = q.frames; v.inst = q.inst; a.subjects = q.subjects; v.sets = q.sets; a.rec = q.rec; }
+    // ---- the three stream-ordered operations
+    TRY(hip_step(dh_launch_shape_clear(a, s), "k_shape_clear"));
+    TRY(hip_step(dh_launch_shape_accumulate_views(v, s), "k_shape_accumulate_views"));
+    TRY(hip_step(dh_launch_shape_solve(a, s), "k_shape_solve"));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)q.n_subjects * sizeof(dh_shape_record), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return DH_OK;
+}
+static int fit_shape_views_(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model,
+                            const dh_fit_basis *basis, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets,
+                            const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records) {
+    return shape_views_run(f, ShapeViewsReq{frames, n_sets, w, h, views, model, basis, instances, n_instances, sets, subjects, n_subjects, params, records},
+                           false, nullptr, "dh_fit_shape_views");
+}
+static int fit_shape_views_device_(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model,
+                                   const dh_fit_basis *basis, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets,
+                                   const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records, void *stream) {
+    return shape_views_run(f, ShapeViewsReq{frames, n_sets, w, h, views, model, basis, instances, n_instances, sets, subjects, n_subjects, params, records},
+                           true, (hipStream_t)stream, "dh_fit_shape_views_device");
 }
 
 // ------------------------------------------------------------------ carrying fitted poses across steps
@@ -3861,6 +3986,8 @@ DH_API(fit_shape, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, co
 DH_API(fit_shape_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *model, const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records), (f, frames, n, w, h, c, model, basis, instances, n_instances, subjects, n_subjects, params, records))
 DH_API(fit_shape_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *model, const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n, w, h, K, model, basis, instances, n_instances, subjects, n_subjects, params, records, stream))
 DH_API(fit_shape_cameras_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *model, const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n, w, h, c, model, basis, instances, n_instances, subjects, n_subjects, params, records, stream))
+DH_API(fit_shape_views, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model, const dh_fit_basis *basis, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records), (f, frames, n_sets, w, h, views, model, basis, instances, n_instances, sets, subjects, n_subjects, params, records))
+DH_API(fit_shape_views_device, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model, const dh_fit_basis *basis, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n_sets, w, h, views, model, basis, instances, n_instances, sets, subjects, n_subjects, params, records, stream))
 DH_API(fit_track_params_default, (dh_fit_track_params *p), (p))
 DH_API(fit_tracker_angles, (double out[DH_FIT_TRACK_ANGLES][2]), (out))
 DH_API(fit_tracker_create, (const dh_cameras *c, const dh_fit_model *m, float scale, uint32_t flags, const dh_fit_track_params *params, dh_fit_tracker **out), (c, m, scale, flags, params, out))

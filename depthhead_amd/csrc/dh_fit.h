@@ -1,9 +1,9 @@
-// dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip)
-// share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
+// dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip,
+// k_fit_shape_views.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
 // words of both trackers, and the one test of whether an instance may be fitted (dh_fit_instance_fault: the host's refusals and
 // the shape kernel's skips).  The device arithmetic the kernels share among themselves is in dh_fit_device.h.  Not part of the
 // ABI.  The rules are stated in include/depthhead_hip.h (sections "fitting posed models to depth frames" and after) and
-// DESIGN.md sections 18 - 22.
+// DESIGN.md sections 18 - 23.
 #pragma once
 #include "dh_internal.h"
 #include "dh_rig_fit.h"
@@ -220,6 +220,64 @@ struct FitViewsArgs {
     dh_view_fit_record *rec;      // [n_inst]
 };
 hipError_t dh_launch_fit_views(const FitViewsArgs &a, hipStream_t s);
+
+// ---- adapting a model's shape across views (k_fit_shape_views.hip)
+// Magnitudes.  A view's terms are section 20's with the composite R_v = V R_w for R, and the section above gives |R_v x| <=
+// 1.032 |x| for a view table within DH_FIT_VIEW_TOLERANCE and an R_w within DH_FIT_R_TOLERANCE: THE ONE CONSTANT THAT CHANGES
+// is again 1.03 -> 1.032.  |nrm| <= 1.032 * 1.01 < 1.043 <= 1.05 as there, so |J_k| <= 1.05 * 1.032 * 256 < 278 < 2^9 and, while
+// |p| <= 2 p.z in every view, |r| <= 1.05 * 2 * 256 < 538 < 2^10: J J < 2^17, J r < 2^18, r r < 2^19 as in section 20, every
+// product below 2^19.  Times 2^20, times DH_SHAPE_MAX_TERMS = 2^23 terms of one subject -- which now counts its (view, point)
+// pairs: the host form adds popcount(views) * points per instance, the _device form bounds the call by n_instances *
+// min(64, n) * points -- below 2^62 < 2^63.
+
+// The r-th set bit of `mask`, counted from bit 0 (r = 0: the lowest); 64 where the mask has r set bits or fewer.  Six halvings:
+// the answer lies in the low half of the window when that half holds more than r set bits, else in the high half with r
+// lowered by the low half's count.
+__host__ __device__ inline uint32_t dh_shape_view_bit(uint64_t mask, uint32_t r) {
+    uint32_t pos = 0;
+    for (uint32_t width = 32; width; width >>= 1) {
+        const uint32_t low = (uint32_t)__builtin_popcountll(mask & ((1ull << width) - 1ull));
+        if (r >= low) { r -= low; mask >>= width; pos += width; }
+    }
+    return (mask & 1ull) != 0 && r == 0 ? pos : 64u;
+}
+
+// Why an instance of a multi-view shape step takes no part: DH_SHAPE_SKIP first (no refusal: the caller asked for it), then the
+// per-instance refusals of the header in their order.  Stated once for the host loop (which turns the answer into its messages)
+// and k_shape_accumulate_views (which skips the instance as a whole).  n: the view table's cameras; a NaN fails each test.
+// An instance that passes names only cameras < n and a set < n_sets: no index formed from it leads out of a buffer.
+enum { DH_SHAPE_VIEWS_OK = 0, DH_SHAPE_VIEWS_SKIPPED, DH_SHAPE_VIEWS_NO_VIEW, DH_SHAPE_VIEWS_CAMERA, DH_SHAPE_VIEWS_SET, DH_SHAPE_VIEWS_SUBJECT,
+       DH_SHAPE_VIEWS_FAULT };
+struct ShapeViewsSkip {
+    int why;                      // DH_SHAPE_VIEWS_*
+    uint64_t last;                // CAMERA: the camera the highest set bit names
+    FitInstanceFault fault;       // FAULT: what dh_fit_instance_fault found
+};
+__host__ __device__ inline ShapeViewsSkip dh_shape_views_skip(const dh_view_instance &in, uint32_t set, uint32_t subject, uint32_t n, uint32_t n_sets,
+                                                              uint32_t n_subjects, double radius, double largest) {
+    ShapeViewsSkip s{DH_SHAPE_VIEWS_OK, 0, FitInstanceFault{DH_FIT_INST_OK, 0, 0, 0.0}};
+    if (subject == DH_SHAPE_SKIP) { s.why = DH_SHAPE_VIEWS_SKIPPED; return s; }
+    if (in.views == 0) { s.why = DH_SHAPE_VIEWS_NO_VIEW; return s; }
+    s.last = (uint64_t)in.first_cam + (63u - (uint32_t)__builtin_clzll(in.views));
+    if (s.last >= (uint64_t)n) { s.why = DH_SHAPE_VIEWS_CAMERA; return s; }
+    if (set >= n_sets) { s.why = DH_SHAPE_VIEWS_SET; return s; }
+    if (subject >= n_subjects) { s.why = DH_SHAPE_VIEWS_SUBJECT; return s; }
+    s.fault = dh_fit_instance_fault(in, radius, largest);
+    if (s.fault.why != DH_FIT_INST_OK) s.why = DH_SHAPE_VIEWS_FAULT;
+    return s;
+}
+
+// k_shape_accumulate_views: one workgroup per (instance, view) pair of a grid of n_inst * ranks.  The clear and the solve of the
+// call are section 20's, launched with `s`.
+struct ShapeViewsArgs {
+    ShapeArgs s;                  // frames [n_sets][n][h][w]; n: the view table's cameras; cams [n]; inst and k unused
+    const FitView *views;         // [n]
+    const dh_view_instance *inst; // [n_inst]
+    const uint32_t *sets;         // nullable [n_inst]
+    uint32_t n_sets;
+    uint32_t ranks;               // min(64, n): the views an instance can have
+};
+hipError_t dh_launch_shape_accumulate_views(const ShapeViewsArgs &a, hipStream_t s);
 
 // ---- carrying each rig person's fitted world pose across steps (k_rig_fit_track.hip and k_fit_views' per-instance-schedule
 // instance).  The bind of a step is stated in dh_rig_fit.h.

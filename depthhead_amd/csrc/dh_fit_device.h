@@ -1,11 +1,12 @@
 // dh_fit_device.h -- the device arithmetic that the fit family's kernels must agree on bit for bit, each piece stated once:
-//   the per-point correspondence and the damped solve     k_fit.hip, k_fit_views.hip, k_fit_shape.hip
+//   the per-point correspondence and the damped solve     k_fit.hip, k_fit_views.hip, k_fit_shape.hip, k_fit_shape_views.hip
+//   the shape step's point loop and reduction              k_fit_shape.hip, k_fit_shape_views.hip
 //   the pose, the modes of a pass, the step's helpers      k_fit.hip, k_fit_views.hip (each with its *_sched instance)
 //   the trackers' rule: table rotation, carried start,
 //   acceptance, jump test and the state updates            k_fit_track.hip, k_rig_fit_track.hip
 // f64 (the trackers: f32 too) with + - * /, compares and casts only; every operation is rounded on its own, so the expression
-// trees below are the contract (tests/fit_ref.py, shape_ref.py, view_fit_ref.py, fit_track_ref.py and rig_fit_track_ref.py
-// restate them).  Not part of the ABI.
+// trees below are the contract (tests/fit_ref.py, shape_ref.py, view_fit_ref.py, fit_track_ref.py and rig_fit_track_ref.py and
+// shape_views_ref.py restate them).  Not part of the ABI.
 #pragma once
 #include "dh_device.h"
 #include "dh_fit.h"
@@ -81,6 +82,98 @@ __device__ __forceinline__ bool fit_solve_tri(const unsigned long long *sums, in
     }
     return true;
 }
+
+// A value that every lane of the workgroup holds alike, moved to scalar registers.
+__device__ __forceinline__ double uni(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// ---- the shape step's accumulation (k_fit_shape.hip and k_fit_shape_views.hip; DESIGN.md sections 20 and 23)
+// What one workgroup of DH_SHAPE_THREADS lanes adds to the row of `subject`: the tail of both accumulate kernels, a macro as
+// DH_FIT_CORRESPOND is, so that both compile from the very tokens.  a: the ShapeArgs; NK: the fields, a compile-time constant;
+// frame, K[9], R[9], t[3], scale: the depth frame and the camera pose the points are posed by (doubles, uniform over the
+// workgroup; the multi-view step passes the composite of a view); s_part: the kernel's own __shared__ long long
+// [DH_SHAPE_THREADS / 64][DH_SHAPE_STRIDE].  Lanes stride over the model's points: the correspondence, then sb, w and J_k in the
+// header's operation order and the products into int64 partial sums in registers.  The sums are reduced across the wave with
+// shuffles, across the four waves through LDS, and one 64-bit global atomic add per word and workgroup lands them in the row;
+// `used` grows by one where the workgroup passed a point.  It returns from the kernel: nothing may follow the expansion.
+// It is a run of statements expanded in the kernel's outermost scope and it claims names there: besides what
+// DH_FIT_CORRESPOND declares in the loop body it declares NA, dw, dh, gate, accA, accB, e, cnt, np, wave, lead, word, row,
+// mine and s, and in inner scopes i, v, nm, J, q, k, l, c, se, sc, base and wv.  The kernel can use none of these names for
+// anything the expansion has to see (its arguments are evaluated inside it), so the kernels call their argument block `a`
+// (or bind `a` to the ShapeArgs inside it) and their own locals by other names.
+#define DH_SHAPE_BLOCK(a, NK, frame, K, R, t, scale, subject, s_part)                                                          \
+    constexpr int NA = (NK) * ((NK) + 1) / 2;                                                                                  \
+    const double dw = (double)(a).w, dh = (double)(a).h, gate = (a).gate;                                                      \
+    long long accA[NA], accB[NK], e = 0, cnt = 0;                                                                              \
+    _Pragma("unroll") for (int k = 0; k < NA; ++k) accA[k] = 0;                                                                \
+    _Pragma("unroll") for (int k = 0; k < (NK); ++k) accB[k] = 0;                                                              \
+    const size_t np = (a).np;                                                                                                  \
+    for (uint32_t i = threadIdx.x; i < (a).np; i += DH_SHAPE_THREADS) {                                                        \
+        double v[3], nm[3];                                                                                                    \
+        _Pragma("unroll") for (int c = 0; c < 3; ++c) {                                                                        \
+            v[c] = (double)(a).pts[(size_t)i * 3 + c];                                                                         \
+            nm[c] = (double)(a).nrm[(size_t)i * 3 + c];                                                                        \
+        }                                                                                                                      \
+        DH_FIT_CORRESPOND(v, nm, scale, R, t, K, frame, (a).w, dw, dh, gate);                                                  \
+        double J[NK];                                                                                                          \
+        _Pragma("unroll") for (int k = 0; k < (NK); ++k) {                                                                     \
+            const float *plane = (a).basis + (size_t)k * 3 * np + i;                                                           \
+            const double sb0 = (double)plane[0] * (scale), sb1 = (double)plane[np] * (scale), sb2 = (double)plane[2 * np] * (scale); \
+            const double w0 = ((R)[0] * sb0 + (R)[1] * sb1) + (R)[2] * sb2;                                                    \
+            const double w1 = ((R)[3] * sb0 + (R)[4] * sb1) + (R)[5] * sb2;                                                    \
+            const double w2 = ((R)[6] * sb0 + (R)[7] * sb1) + (R)[8] * sb2;                                                    \
+            J[k] = (n[0] * w0 + n[1] * w1) + n[2] * w2;                                                                        \
+        }                                                                                                                      \
+        int q = 0;                                                                                                             \
+        _Pragma("unroll") for (int k = 0; k < (NK); ++k) {                                                                     \
+            _Pragma("unroll") for (int l = k; l < (NK); ++l) accA[q++] += (long long)((J[k] * J[l]) * DH_FIT_S);               \
+            accB[k] += (long long)((J[k] * res) * DH_FIT_S);                                                                   \
+        }                                                                                                                      \
+        e += (long long)((res * res) * DH_FIT_S);                                                                              \
+        cnt += 1;                                                                                                              \
+    }                                                                                                                          \
+    /* ---- across the wave in registers, across the waves in LDS, then one global atomic per sum */                          \
+    const int wave = threadIdx.x >> 6;                                                                                         \
+    const bool lead = (threadIdx.x & 63) == 0;                                                                                 \
+    {                                                                                                                          \
+        int q = 0;                                                                                                             \
+        _Pragma("unroll") for (int k = 0; k < (NK); ++k) {                                                                     \
+            _Pragma("unroll") for (int l = k; l < (NK); ++l) {                                                                 \
+                const long long s = (long long)wave_sum_u64((uint64_t)accA[q++]);                                              \
+                if (lead) (s_part)[wave][DH_FIT_PAIR(8, k, l)] = s;                                                            \
+            }                                                                                                                  \
+            const long long s = (long long)wave_sum_u64((uint64_t)accB[k]);                                                    \
+            if (lead) (s_part)[wave][DH_SHAPE_B + k] = s;                                                                      \
+        }                                                                                                                      \
+        const long long se = (long long)wave_sum_u64((uint64_t)e), sc = (long long)wave_sum_u64((uint64_t)cnt);                \
+        if (lead) { (s_part)[wave][DH_SHAPE_E] = se; (s_part)[wave][DH_SHAPE_COUNT] = sc; }                                    \
+    }                                                                                                                          \
+    __syncthreads();                                                                                                           \
+    const int word = threadIdx.x;                                                                                              \
+    if (word > DH_SHAPE_USED) return;                                                                                          \
+    unsigned long long *row = (a).sums + (size_t)(subject) * DH_SHAPE_STRIDE;                                                  \
+    if (word == DH_SHAPE_USED) {                                                                                               \
+        long long c = 0;                                                                                                       \
+        _Pragma("unroll") for (int wv = 0; wv < DH_SHAPE_THREADS / 64; ++wv) c += (s_part)[wv][DH_SHAPE_COUNT];                \
+        if (c > 0) atomicAdd(&row[DH_SHAPE_USED], 1ull);                                                                       \
+        return;                                                                                                                \
+    }                                                                                                                          \
+    /* a word of A that this K does not use was never written: the words of an NK x NK block are those with l < NK */          \
+    bool mine = word >= DH_SHAPE_E;                                                                                            \
+    if (word >= DH_SHAPE_B && word < DH_SHAPE_E) mine = word - DH_SHAPE_B < (NK);                                              \
+    if (word < DH_SHAPE_B) {                                                                                                   \
+        int k = 0, base = 0;                                                                                                   \
+        while (word >= base + (8 - k)) { base += 8 - k; ++k; } /* row k of the 8 x 8 upper triangle starts at `base` */        \
+        mine = k < (NK) && k + (word - base) < (NK);                                                                           \
+    }                                                                                                                          \
+    if (!mine) return;                                                                                                         \
+    long long s = 0;                                                                                                           \
+    _Pragma("unroll") for (int wv = 0; wv < DH_SHAPE_THREADS / 64; ++wv) s += (s_part)[wv][word];                              \
+    atomicAdd(&row[word], (unsigned long long)s)
 
 // ---- the fit's pose, pass modes and step helpers (k_fit.hip and k_fit_views.hip; DESIGN.md sections 18 and 21)
 #define FIT_COARSE 0

@@ -5,7 +5,9 @@
 //          expands too), then the point's K shape derivatives and its products into int64 partial sums in registers.  A single
 //          pass reads every model and basis value once, so nothing is staged in LDS; the basis lies one plane per field and
 //          axis, so a wave reads consecutive words.  The sums are reduced across the wave with shuffles, across the four waves
-//          through LDS, and one 64-bit global atomic add per sum and workgroup lands them in the subject's row.
+//          through LDS, and one 64-bit global atomic add per sum and workgroup lands them in the subject's row.  The loop
+//          and the reduction are DH_SHAPE_BLOCK (dh_fit_device.h), which k_shape_accumulate_views (k_fit_shape_views.hip)
+//          expands too; the clear and the solve below serve both.
 //   k_shape_clear       zeroes the rows of the call's subjects, before the accumulation on the same stream.
 //   k_shape_solve       one lane per subject: the fit's solve (fit_solve_tri, dh_fit_device.h) on the subject's row, the record.
 // K is a template argument (1 .. 8): every array is indexed at compile time and stays in registers.
@@ -24,7 +26,6 @@ __device__ __forceinline__ bool shape_takes_part(const ShapeArgs &a, const dh_re
 
 template <int NK>
 __global__ __launch_bounds__(DH_SHAPE_THREADS) void k_shape_accumulate(const ShapeArgs a) {
-    constexpr int NA = NK * (NK + 1) / 2;
     __shared__ long long s_part[DH_SHAPE_THREADS / 64][DH_SHAPE_STRIDE];
     const dh_render_instance *in = a.inst + blockIdx.x;
     const uint32_t subject = a.subjects ? a.subjects[blockIdx.x] : 0u;
@@ -39,83 +40,7 @@ __global__ __launch_bounds__(DH_SHAPE_THREADS) void k_shape_accumulate(const Sha
 #pragma unroll
     for (int q = 0; q < 3; ++q) t[q] = (double)in->t[q];
     const double scale = (double)in->scale;
-    const double dw = (double)a.w, dh = (double)a.h, gate = a.gate;
-    long long accA[NA], accB[NK], e = 0, cnt = 0;
-#pragma unroll
-    for (int k = 0; k < NA; ++k) accA[k] = 0;
-#pragma unroll
-    for (int k = 0; k < NK; ++k) accB[k] = 0;
-    const size_t np = a.np;
-    for (uint32_t i = threadIdx.x; i < a.np; i += DH_SHAPE_THREADS) {
-        double v[3], nm[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            v[c] = (double)a.pts[(size_t)i * 3 + c];
-            nm[c] = (double)a.nrm[(size_t)i * 3 + c];
-        }
-        DH_FIT_CORRESPOND(v, nm, scale, R, t, K, frame, a.w, dw, dh, gate);
-        double J[NK];
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const float *plane = a.basis + (size_t)k * 3 * np + i;
-            const double sb0 = (double)plane[0] * scale, sb1 = (double)plane[np] * scale, sb2 = (double)plane[2 * np] * scale;
-            const double w0 = (R[0] * sb0 + R[1] * sb1) + R[2] * sb2;
-            const double w1 = (R[3] * sb0 + R[4] * sb1) + R[5] * sb2;
-            const double w2 = (R[6] * sb0 + R[7] * sb1) + R[8] * sb2;
-            J[k] = (n[0] * w0 + n[1] * w1) + n[2] * w2;
-        }
-        int q = 0;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-#pragma unroll
-            for (int l = k; l < NK; ++l) accA[q++] += (long long)((J[k] * J[l]) * DH_FIT_S);
-            accB[k] += (long long)((J[k] * res) * DH_FIT_S);
-        }
-        e += (long long)((res * res) * DH_FIT_S);
-        cnt += 1;
-    }
-    // ---- across the wave in registers, across the waves in LDS, then one global atomic per sum
-    const int wave = threadIdx.x >> 6;
-    const bool lead = (threadIdx.x & 63) == 0;
-    {
-        int q = 0;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-#pragma unroll
-            for (int l = k; l < NK; ++l) {
-                const long long s = (long long)wave_sum_u64((uint64_t)accA[q++]);
-                if (lead) s_part[wave][DH_FIT_PAIR(8, k, l)] = s;
-            }
-            const long long s = (long long)wave_sum_u64((uint64_t)accB[k]);
-            if (lead) s_part[wave][DH_SHAPE_B + k] = s;
-        }
-        const long long se = (long long)wave_sum_u64((uint64_t)e), sc = (long long)wave_sum_u64((uint64_t)cnt);
-        if (lead) { s_part[wave][DH_SHAPE_E] = se; s_part[wave][DH_SHAPE_COUNT] = sc; }
-    }
-    __syncthreads();
-    const int word = threadIdx.x;
-    if (word > DH_SHAPE_USED) return;
-    unsigned long long *row = a.sums + (size_t)subject * DH_SHAPE_STRIDE;
-    if (word == DH_SHAPE_USED) {
-        long long c = 0;
-#pragma unroll
-        for (int wv = 0; wv < DH_SHAPE_THREADS / 64; ++wv) c += s_part[wv][DH_SHAPE_COUNT];
-        if (c > 0) atomicAdd(&row[DH_SHAPE_USED], 1ull);
-        return;
-    }
-    // a word of A that this K does not use was never written: the words of an NK x NK block are those with l < NK
-    bool mine = word >= DH_SHAPE_E;
-    if (word >= DH_SHAPE_B && word < DH_SHAPE_E) mine = word - DH_SHAPE_B < NK;
-    if (word < DH_SHAPE_B) {
-        int k = 0, base = 0;
-        while (word >= base + (8 - k)) { base += 8 - k; ++k; }          // row k of the 8 x 8 upper triangle starts at `base`
-        mine = k < NK && k + (word - base) < NK;
-    }
-    if (!mine) return;
-    long long s = 0;
-#pragma unroll
-    for (int wv = 0; wv < DH_SHAPE_THREADS / 64; ++wv) s += s_part[wv][word];
-    atomicAdd(&row[word], (unsigned long long)s);
+    DH_SHAPE_BLOCK(a, NK, frame, K, R, t, scale, subject, s_part);
 }
 
 template <int NK>

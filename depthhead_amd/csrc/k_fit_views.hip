@@ -12,18 +12,11 @@
 // f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free: bit-identical
 // run to run and to tests/view_fit_ref.py.  With one view, V = I and u = 0 every sum equals k_fit's.  One kernel body,
 // FIT_VIEWS_BLOCK, in two instances: k_fit_views, and k_fit_views_sched with a schedule per instance.
-// The pose (FitPose), the modes of a pass and the step's helpers (fit_small, fit_cayley) are k_fit's very ones, in dh_fit_device.h.
+// The pose (FitPose), the modes of a pass and the step's helpers (fit_small, fit_cayley) are k_fit's very ones, in dh_fit_device.h;
+// uni() is there too (k_shape_accumulate_views moves its composite to scalar registers with it).
 #include "dh_fit_device.h"
 
 #pragma clang fp contract(off)
-
-// A value that every lane of the workgroup holds alike, moved to scalar registers.
-__device__ __forceinline__ double uni(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 // One pass at the world pose `pose` with gate `gate` over the views of `mask` (bit k: camera first_cam + k): the sums of MODE
 // into s_sum (zeroed here; valid for every lane after the return).

@@ -334,6 +334,48 @@ class Fitter(_lib._Handle):
                                                                       C.c_uint32(ns), prm, C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
         return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
 
+    def shape_step_views(self, frames, views, model, basis, instances, sets=None, subjects=None, n_subjects: int = 1, params=None,
+                         device_out: bool = False, stream=None):
+        """One multi-view shape step of `model` and its `basis` over the world-posed `instances`
+        (VIEW_INSTANCE_DTYPE, what fit_views returned) of frames [n_sets, n, h, w] u16 -- frame [s, c] is camera c of `views` (a
+        `Views` of n cameras) at set s -- per subject: sets [n_instances] u32 (None: all in set 0), subjects [n_instances] u32
+        (None: all subject 0; SHAPE_SKIP leaves an instance out).  The record's `instances` counts (instance, view) pairs.  Host
+        form: numpy arrays -> SHAPE_RECORD_DTYPE [n_subjects].  With device_out=True frames, instances, sets and subjects are
+        torch tensors on the device (instances as the uint8 tensor Fitter.fit_views(device_out=True) returned, sets and subjects
+        int32 or None) and the records come back as a uint8 torch tensor, ordered on `stream` (default the current torch stream)
+        without a host wait."""
+        n_sets, n, h, w = (int(v) for v in frames.shape)
+        if n != len(views):
+            raise ValueError(f"{n} frames a set for a view table of {len(views)} cameras")
+        prm = C.byref(params) if params is not None else None
+        ns = int(n_subjects)
+        if not device_out:
+            fr = np.ascontiguousarray(frames, dtype=np.uint16)
+            inst = np.ascontiguousarray(instances, dtype=VIEW_INSTANCE_DTYPE)
+            st = None if sets is None else np.ascontiguousarray(sets, dtype=np.uint32).reshape(len(inst))
+            subj = None if subjects is None else np.ascontiguousarray(subjects, dtype=np.uint32).reshape(len(inst))
+            rec = np.zeros(max(ns, 0), SHAPE_RECORD_DTYPE)
+            check(self._lib.dh_fit_shape_views(self._h, vp(fr), C.c_uint32(n_sets), w, h, views._h, model._h, basis._h,
+                                               vp(inst) if len(inst) else None, C.c_uint32(len(inst)), vp(st), vp(subj), C.c_uint32(ns), prm,
+                                               vp(rec)))
+            return rec
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
+            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
+        ni = instances.numel() * instances.element_size() // VIEW_INSTANCE_DTYPE.itemsize
+        for name, words in (("sets", sets), ("subjects", subjects)):
+            if words is not None and (words.numel() != ni or words.element_size() != 4 or not words.is_contiguous()):
+                raise ValueError(f"device {name}: a contiguous 32-bit tensor with one word per instance is expected")
+        rec = torch.empty(max(ns, 1) * SHAPE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        check(self._lib.dh_fit_shape_views_device(self._h, C.c_void_p(frames.data_ptr()), C.c_uint32(n_sets), w, h, views._h, model._h, basis._h,
+                                                  C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
+                                                  C.c_void_p(sets.data_ptr()) if sets is not None else None,
+                                                  C.c_void_p(subjects.data_ptr()) if subjects is not None else None, C.c_uint32(ns), prm,
+                                                  C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
+        return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
+
 
 def adapt(fitter, frames, K_or_cameras, verts, tris, basis, starts, rounds: int = 6, fit_prm=None, shape_prm=None, coeffs=None):
     """Adapt the shape coefficients of one subject's model to `frames` ([n, h, w] u16, numpy) by alternation, `rounds` times:
@@ -353,6 +395,36 @@ def adapt(fitter, frames, K_or_cameras, verts, tris, basis, starts, rounds: int 
                 inst, rec = fitter.fit(frames, [model], inst, K_or_cameras, params=fit_prm)
                 subj = np.where(rec["status"] == FIT_OK, 0, SHAPE_SKIP).astype(np.uint32)
                 srec = fitter.shape_step(frames, model, sb, inst, K_or_cameras, subjects=subj, params=shape_prm)[0]
+            delta = srec["delta"][:len(c)].copy() if srec["status"] == SHAPE_OK else np.zeros(len(c))
+            trace.append({"coeffs": c.copy(), "fit": rec, "shape": srec, "delta": delta})
+            c = c + delta
+    return c, inst, trace
+
+def adapt_views(fitter, frames, views, verts, tris, basis, starts, sets=None, rounds: int = 6, fit_prm=None, shape_prm=None, coeffs=None):
+    """`adapt` over the views of a rig: frames [n_sets, n, h, w] u16 (numpy), `views` a `Views` of n
+    cameras, `starts` VIEW_INSTANCE_DTYPE [m] world poses and sets [m] the set each belongs to (None: set 0).  A round builds
+    the model from the current coefficients, fits every instance from its previous pose with Fitter.fit_views (one call per
+    set, over the instances of that set), takes ONE multi-view shape step over the fits that ended FIT_OK and adds the
+    increment when the step ended SHAPE_OK.  Returns what `adapt` returns: (coefficients [K] f64, the last fitted instances,
+    trace); trace[r]["fit"] holds VIEW_FIT_RECORD_DTYPE records in the order of `starts`."""
+    fields = np.ascontiguousarray(getattr(basis, "fields", basis), dtype=np.float32)
+    c = np.zeros(len(fields), np.float64) if coeffs is None else np.array(coeffs, dtype=np.float64)
+    inst = np.array(starts, dtype=VIEW_INSTANCE_DTYPE)
+    st = np.zeros(len(inst), np.uint32) if sets is None else np.ascontiguousarray(sets, dtype=np.uint32).reshape(len(inst))
+    trace = []
+    with ShapeBasis(fields, device=fitter.device) as sb:
+        for _ in range(int(rounds)):
+            v = deform(verts, fields, c)
+            with Model(v, vertex_normals(v, tris), device=fitter.device) as model:
+                rec = np.zeros(len(inst), VIEW_FIT_RECORD_DTYPE)
+                for s in np.unique(st):
+                    of = np.flatnonzero(st == s)
+                    one = inst[of].copy()
+                    one["model"] = 0
+                    out, rec[of] = fitter.fit_views(frames[int(s)], [model], one, views, params=fit_prm)
+                    inst["R"][of], inst["t"][of] = out["R"], out["t"]
+                subj = np.where(rec["status"] == FIT_OK, 0, SHAPE_SKIP).astype(np.uint32)
+                srec = fitter.shape_step_views(frames, views, model, sb, inst, sets=st, subjects=subj, params=shape_prm)[0]
             delta = srec["delta"][:len(c)].copy() if srec["status"] == SHAPE_OK else np.zeros(len(c))
             trace.append({"coeffs": c.copy(), "fit": rec, "shape": srec, "delta": delta})
             c = c + delta

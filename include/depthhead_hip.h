@@ -853,7 +853,7 @@ typedef struct dh_shape_params {
 typedef struct dh_shape_record {
     double   delta[8];            /* the increment of coefficient k; 0 for k >= K and when status is not DH_SHAPE_OK */
     uint32_t points;              /* count */
-    uint32_t instances;           /* used */
+    uint32_t instances;           /* used (dh_fit_shape_views*: the (instance, view) pairs that passed a point) */
     uint32_t status;              /* DH_SHAPE_* */
     uint32_t reserved;            /* 0 */
     int64_t  sum_r2_fixed;        /* e: the residual before the step */
@@ -974,6 +974,55 @@ int dh_fit_depth_views_device(dh_fitter *f, const uint16_t *frames, int w, int h
                               const dh_fit_model *const *models, uint32_t n_models, const dh_view_instance *instances,
                               uint32_t n_instances, const dh_fit_params *params, dh_view_instance *out,
                               dh_view_fit_record *records, void *stream);
+
+/* ---- adapting a model's shape across views ----
+ * The shape step of section 20 knows one camera and a camera-frame pose per instance; the multi-view fit of section 21 writes ONE
+ * world pose per instance and the mask of the cameras that see it.  A MULTI-VIEW SHAPE STEP takes those instances as they are and
+ * sums, per subject, section 20's normal equations over every (instance, view, point): a shape coefficient is a scalar, the same
+ * in every frame, so a view contributes its terms with the composite camera pose of section 21 in place of (R, t) and nothing
+ * else changes.  Not in the reference: PARITY UNPINNED, the definition below is this library's.  The arithmetic conventions are
+ * the fit's: f64, evaluated left to right, every product, sum and quotient rounded on its own, + - * /, compares and casts only.
+ * ONE MULTI-VIEW SHAPE STEP takes frames [n_sets][n][h][w] u16, where n is the view table's cameras and a SET is one moment of
+ *   the rig: frame s * n + c is camera c at set s; a dh_fit_views table (and through it the camera table); ONE model and its
+ *   basis; n_instances dh_view_instance (what dh_fit_depth_views* wrote; `model` and `flags` are ignored, as section 20 ignores
+ *   `mesh`); sets[n_instances] (NULL: every instance is in set 0); subjects[n_instances] (NULL: subject 0; DH_SHAPE_SKIP: the
+ *   instance takes no part); n_subjects and dh_shape_params.  For every instance that takes part and every set bit k of `views`,
+ *   with c = first_cam + k, V = V_c, u = u_c:
+ *     the composite (R_v, t_v) is formed once, exactly as section 21 writes it (R_v = V R_w, t_v = V t_w + u, in its element
+ *     order); every point of the model runs ONE PASS of section 18 unchanged at (scale, R_v, t_v), camera c's K, frame
+ *     sets[i] * n + c and gate g = params.gate; and a point that passed adds section 20's terms with R_v for R, in section 20's
+ *     operation order (sb, w, J_k), into its subject's sums: A_kl, b_k, e, count, with S = 2^20 and truncating casts.
+ *   used += 1 for every (instance, view) PAIR that passed at least one point: THE RECORD'S `instances` FIELD COUNTS PAIRS HERE,
+ *   not instances (with one view per instance it is section 20's count).
+ *   Magnitudes: with section 21's |R_v x| <= 1.032 |x|, |J_k| <= 1.05 * 1.032 * 256 < 2^9 and section 20's product bounds stand;
+ *   DH_SHAPE_MAX_TERMS = 2^23 counts the (view, point) pairs of a subject.  Outside |p| <= 2 p.z the words of section 20 hold.
+ * SOLVE, the statuses and dh_shape_record are section 20's, unchanged.  With one view, V = I, u = 0 and n_sets = 1 every sum and
+ *   every record byte equals dh_fit_shape_cameras on the same pose.  Bit-identical run to run and to tests/shape_views_ref.py.
+ * The calls run on a dh_fitter and reuse its sums buffer, so ALL shape calls of one fitter, of this section and of section 20, must
+ * be stream-ordered with one another.  dh_fit_shape_views takes host frames, instances, sets, subjects and records and is
+ * synchronous.  dh_fit_shape_views_device takes device frames, instances, sets, subjects and records, enqueues exactly three
+ * kernels on `stream` (NULL = default stream) -- k_shape_clear, k_shape_accumulate_views (one workgroup per (instance, view) pair),
+ * k_shape_solve -- allocates nothing after the fitter's first shape call and never waits on the host: it chains after
+ * dh_fit_depth_views_device, whose `out` is its `instances`.  params is host memory in both; NULL selects dh_shape_params_default.
+ * DH_EINVAL before anything is launched, with the outputs untouched: section 20's refusals for the fitter, frames, records, model,
+ * basis, params, n_subjects, w and h and the instance count; a NULL view table or one of another device than the fitter; n_sets of
+ * 0, or n_sets * n above 65535.  The host call also refuses, per instance that takes part (its subject is not DH_SHAPE_SKIP), in
+ * this order: views == 0; a set bit naming a camera >= n; a set >= n_sets; a subject >= n_subjects; what section 20 refuses of R,
+ * t and scale, the field limit included; and a subject whose (instance, view) pairs times the model's points exceed
+ * DH_SHAPE_MAX_TERMS.  The _device call cannot read the instances: it refuses n_instances * min(64, n) * (the model's points)
+ * above DH_SHAPE_MAX_TERMS, and the device skips, AS A WHOLE, every instance one of the per-instance refusals names, a NaN failing
+ * each test, so no input leads out of a buffer or out of the magnitude bound.  n_instances = 0 is no error: every record is
+ * DH_SHAPE_FEW_POINTS with points 0. */
+/* frames [n_sets][n][h][w] u16 with n the view table's cameras; instances, sets (or NULL) and subjects (or NULL) [n_instances];
+ * records [n_subjects] */
+int dh_fit_shape_views(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views,
+                       const dh_fit_model *model, const dh_fit_basis *basis, const dh_view_instance *instances,
+                       uint32_t n_instances, const uint32_t *sets, const uint32_t *subjects, uint32_t n_subjects,
+                       const dh_shape_params *params, dh_shape_record *records);
+int dh_fit_shape_views_device(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views,
+                              const dh_fit_model *model, const dh_fit_basis *basis, const dh_view_instance *instances,
+                              uint32_t n_instances, const uint32_t *sets, const uint32_t *subjects, uint32_t n_subjects,
+                              const dh_shape_params *params, dh_shape_record *records, void *stream);
 
 /* ---- carrying each rig person's fitted world pose across steps ----
  * The composition of the three sections above: every person of every rig keeps ONE fitted pose in the WORLD frame under the
