@@ -137,6 +137,21 @@ class ShapeParams(C.Structure):
                 ("reserved", C.c_uint64 * 2)]
 
 
+# dh_calib_record: what one calibration step reports for a camera (dh_fit_calibrate_views*)
+CALIB_RECORD_DTYPE = np.dtype([("V", "<f4", (9,)), ("u", "<f4", (3,)), ("points", "<u4"), ("pairs", "<u4"), ("status", "<u4"),
+                               ("reserved", "<u4"), ("sum_r2_fixed", "<i8"), ("delta", "<f8", (6,))], align=True)
+assert CALIB_RECORD_DTYPE.itemsize == 120
+CALIB_SKIP = 0xFFFFFFFF    # DH_CALIB_SKIP
+CALIB_ARM_UNIT = 64        # DH_CALIB_ARM_UNIT (mm)
+CALIB_MAX_ARM = 2048       # DH_CALIB_MAX_ARM (mm)
+
+
+class CalibParams(C.Structure):
+    """dh_calib_params (`lam` is the header's `lambda`)"""
+    _fields_ = [("gate", C.c_double), ("lam", C.c_double), ("pivot", C.c_double * 3), ("min_points", C.c_uint32),
+                ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
 class RigTrackParams(C.Structure):
     """dh_rig_track_params"""
     _fields_ = [("max_heads", C.c_int32), ("radius", C.c_uint32), ("fuse_gate", C.c_uint32), ("gate", C.c_uint32),
@@ -197,6 +212,7 @@ EXPORTS = [
     "dh_fit_tracker_step_device",
     "dh_fit_basis_create", "dh_fit_basis_destroy", "dh_fit_basis_info", "dh_shape_params_default", "dh_fit_shape", "dh_fit_shape_cameras",
     "dh_fit_shape_device", "dh_fit_shape_cameras_device", "dh_fit_shape_views", "dh_fit_shape_views_device",
+    "dh_calib_params_default", "dh_fit_calibrate_views", "dh_fit_calibrate_views_device",
     "dh_fit_views_create", "dh_fit_views_destroy", "dh_fit_views_info", "dh_fit_depth_views", "dh_fit_depth_views_device",
     "dh_rig_fit_track_params_default", "dh_rig_fit_tracker_create", "dh_rig_fit_tracker_destroy", "dh_rig_fit_tracker_reset",
     "dh_rig_fit_tracker_state", "dh_rig_fit_tracker_step_persons", "dh_rig_fit_tracker_step_persons_device", "dh_rig_fit_tracker_step",

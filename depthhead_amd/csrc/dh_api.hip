@@ -2820,6 +2820,9 @@ struct dh_fitter {
     Buf<dh_shape_record> shape_rec;
     Buf<dh_view_instance> shape_vinst;       // host multi-view shape calls
     Buf<uint32_t> shape_vsubj, shape_vsets;
+    Buf<unsigned long long> calib_sums;      // calibration calls: [cameras][DH_CALIB_STRIDE], taken at the first one of a table size
+    Buf<uint8_t> calib_hold;                 // host calibration calls (instances, sets and take: the shape_v* staging)
+    Buf<dh_calib_record> calib_rec;
     Buf<dh_view_instance> view_out;          // host multi-view calls
     Buf<dh_view_fit_record> view_rec;
     std::vector<unsigned char> view_cmp;     // a captured multi-view call's tables, to be compared with the staged ones
@@ -3418,6 +3421,138 @@ static int fit_shape_views_device_(dh_fitter *f, const uint16_t *frames, uint32_
                            true, (hipStream_t)stream, "dh_fit_shape_views_device");
 }
 
+// ------------------------------------------------------------------ calibrating a view table
+static int calib_params_default_(dh_calib_params *p) {
+    if (!p) return fail(DH_EINVAL, "dh_calib_params_default: NULL argument");
+    memset(p, 0, sizeof *p);
+    p->gate = 25.0;
+    p->lambda = 1e-3;
+    p->min_points = 64;
+    return DH_OK;
+}
+// One calibration call.  dev: frames / instances / sets / take / hold / records are device pointers and `stream` the caller's.
+struct CalibReq {
+    const uint16_t *frames; uint32_t n_sets; int w, h;
+    const dh_fit_views *views;
+    const dh_fit_model *model;
+    const dh_view_instance *inst; uint32_t n_inst;
+    const uint32_t *sets; const uint32_t *take; const uint8_t *hold;
+    const dh_calib_params *prm;
+    dh_calib_record *rec;
+};
+static int calib_run(dh_fitter *f, const CalibReq &q, bool dev, hipStream_t stream, const char *who) {
+    // ---- refusals: all of them before anything is allocated or launched
+    if (!f) return fail(DH_EINVAL, "%s: NULL fitter", who);
+    if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!q.rec) return fail(DH_EINVAL, "%s: NULL records", who);
+    if (!q.model) return fail(DH_EINVAL, "%s: NULL model", who);
+    if (!q.views) return fail(DH_EINVAL, "%s: NULL view table", who);
+    if (q.views->device != f->device) return fail(DH_EINVAL, "%s: the view table lives on device %d, the fitter on %d", who, q.views->device, f->device);
+    const int n = q.views->n;
+    if (q.n_sets < 1 || (uint64_t)q.n_sets * (uint64_t)n > 65535)
+        return fail(DH_EINVAL, "%s: n_sets = %u of %d cameras, expected 1 .. 65535 frames", who, q.n_sets, n);
+    TRY(check_frames(n, q.w, q.h, nullptr, q.views->cams, true, f->device, "fitter", who));
+    dh_calib_params prm;
+    (void)calib_params_default_(&prm);
+    if (q.prm) prm = *q.prm;
+    if (!(prm.gate > 0.0 && prm.gate <= DH_SHAPE_MAX_GATE)) return fail(DH_EINVAL, "%s: gate = %g outside (0, %g]", who, prm.gate, DH_SHAPE_MAX_GATE);
+    if (!(prm.lambda >= 0.0) || !std::isfinite(prm.lambda)) return fail(DH_EINVAL, "%s: lambda %g, expected a finite value >= 0", who, prm.lambda);
+    if (prm.min_points < 1) return fail(DH_EINVAL, "%s: min_points 0 below 1", who);
+    for (int j = 0; j < 3; ++j)
+        if (!std::isfinite(prm.pivot[j])) return fail(DH_EINVAL, "%s: pivot[%d] is not finite", who, j);
+    if (prm.reserved0 || prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    const dh_fit_model *m = q.model;
+    if (m->device != f->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the fitter on %d", who, m->device, f->device);
+    if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
+    if (q.n_inst > DH_SHAPE_MAX_TERMS) return fail(DH_EINVAL, "%s: too many instances", who);
+    if (dev) {
+        if ((uint64_t)q.n_inst * m->n > DH_SHAPE_MAX_TERMS)
+            return fail(DH_EINVAL, "%s: %u instances of %u points exceed %u terms", who, q.n_inst, m->n, DH_SHAPE_MAX_TERMS);
+    } else {
+        std::vector<uint64_t> per((size_t)n, 0);
+        for (uint32_t i = 0; i < q.n_inst; ++i) {
+            const dh_view_instance &in = q.inst[i];
+            const uint32_t tk = q.take ? q.take[i] : 0u, set = q.sets ? q.sets[i] : 0u;
+            const ShapeViewsSkip sk = dh_calib_skip(in, set, tk, (uint32_t)n, q.n_sets, m->radius);
+            switch (sk.why) {
+            case DH_SHAPE_VIEWS_OK: break;
+            case DH_SHAPE_VIEWS_SKIPPED: continue;
+            case DH_SHAPE_VIEWS_NO_VIEW: return fail(DH_EINVAL, "%s: instance %u is seen by no view", who, i);
+            case DH_SHAPE_VIEWS_CAMERA: return fail(DH_EINVAL, "%s: instance %u names camera %llu of %d", who, i, (unsigned long long)sk.last, n);
+            case DH_SHAPE_VIEWS_SET: return fail(DH_EINVAL, "%s: instance %u names set %u of %u", who, i, set, q.n_sets);
+            default: return instance_refusal(sk.fault, in.scale, i, m->radius, 0.0, who);
+            }
+            for (uint32_t k = 0; k < 64; ++k) {
+                if (!((in.views >> k) & 1ull)) continue;
+                const uint32_t c = in.first_cam + k;
+                if (q.hold && q.hold[c] != 0) continue;                   // (a pair beyond the arm counts: only the device forms it)
+                per[c] += m->n;
+                if (per[c] > DH_SHAPE_MAX_TERMS)
+                    return fail(DH_EINVAL, "%s: camera %u has more than %u terms (pairs times %u points)", who, c, DH_SHAPE_MAX_TERMS, m->n);
+            }
+        }
+    }
+
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(f->tab.init());
+    hipStream_t s = dev ? stream : f->tab.s;
+    const size_t words = (size_t)n * DH_CALIB_STRIDE;
+    if (f->calib_sums.cap() < words) { HIP_TRY(hipDeviceSynchronize()); TRY(f->calib_sums.grow(words)); }
+    CalibArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = n; a.w = q.w; a.h = q.h;
+    a.cams = q.views->cams->dev.get();
+    a.views = q.views->dev.get();
+    a.pts = m->pts.get(); a.nrm = m->nrm.get(); a.np = m->n; a.radius = m->radius;
+    a.n_inst = q.n_inst; a.n_sets = q.n_sets; a.ranks = (uint32_t)std::min(64, n);
+    a.min_points = prm.min_points; a.gate = prm.gate; a.lam1 = 1.0 + prm.lambda;
+    for (int j = 0; j < 3; ++j) a.pivot[j] = prm.pivot[j];
+    a.sums = f->calib_sums.get();
+    if (!dev) {
+        const size_t n_px = (size_t)q.n_sets * n * q.w * q.h;
+        if (f->frames.cap() < n_px || f->shape_vinst.cap() < q.n_inst || !f->shape_vinst || f->calib_hold.cap() < (size_t)n) HIP_TRY(hipDeviceSynchronize());
+        TRY(f->frames.grow(n_px));
+        if (f->shape_vinst.cap() < q.n_inst || !f->shape_vinst) {
+            TRY(f->shape_vinst.grow(std::max<size_t>(q.n_inst, 1)));
+            TRY(f->shape_vsubj.alloc(f->shape_vinst.cap()));
+            TRY(f->shape_vsets.alloc(f->shape_vinst.cap()));
+        }
+        if (f->calib_hold.cap() < (size_t)n) { TRY(f->calib_hold.grow((size_t)n)); TRY(f->calib_rec.grow((size_t)n)); }
+        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        if (q.n_inst) HIP_TRY(hipMemcpyAsync(f->shape_vinst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_view_instance), hipMemcpyHostToDevice, s));
+        if (q.n_inst && q.take) HIP_TRY(hipMemcpyAsync(f->shape_vsubj.get(), q.take, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (q.n_inst && q.sets) HIP_TRY(hipMemcpyAsync(f->shape_vsets.get(), q.sets, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (q.hold) HIP_TRY(hipMemcpyAsync(f->calib_hold.get(), q.hold, (size_t)n, hipMemcpyHostToDevice, s));
+        a.frames = f->frames.get(); a.inst = f->shape_vinst.get();
+        a.take = q.take ? f->shape_vsubj.get() : nullptr;
+        a.sets = q.sets ? f->shape_vsets.get() : nullptr;
+        a.hold = q.hold ? f->calib_hold.get() : nullptr;
+        a.rec = f->calib_rec.get();
+    } else { a.frames = q.frames; a.inst = q.inst; a.take = q.take; a.sets = q.sets; a.hold = q.hold; a.rec = q.rec; }
+    // ---- the three stream-ordered operations
+    TRY(hip_step(dh_launch_calib_clear(a, s), "k_calib_clear"));
+    TRY(hip_step(dh_launch_calib_accumulate(a, s), "k_calib_accumulate"));
+    TRY(hip_step(dh_launch_calib_solve(a, s), "k_calib_solve"));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)n * sizeof(dh_calib_record), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return DH_OK;
+}
+static int fit_calibrate_views_(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model,
+                                const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *take, const uint8_t *hold,
+                                const dh_calib_params *params, dh_calib_record *records) {
+    return calib_run(f, CalibReq{frames, n_sets, w, h, views, model, instances, n_instances, sets, take, hold, params, records}, false, nullptr,
+                     "dh_fit_calibrate_views");
+}
+static int fit_calibrate_views_device_(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model,
+                                       const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *take, const uint8_t *hold,
+                                       const dh_calib_params *params, dh_calib_record *records, void *stream) {
+    return calib_run(f, CalibReq{frames, n_sets, w, h, views, model, instances, n_instances, sets, take, hold, params, records}, true, (hipStream_t)stream,
+                     "dh_fit_calibrate_views_device");
+}
+
 // ------------------------------------------------------------------ carrying fitted poses across steps
 // The angle table of the header: computed once, by libm, and the only cosines and sines of the feature.
 struct FitTrackAngles {
@@ -3988,6 +4123,9 @@ DH_API(fit_shape_device, (dh_fitter *f, const uint16_t *frames, int n, int w, in
 DH_API(fit_shape_cameras_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *model, const dh_fit_basis *basis, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n, w, h, c, model, basis, instances, n_instances, subjects, n_subjects, params, records, stream))
 DH_API(fit_shape_views, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model, const dh_fit_basis *basis, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records), (f, frames, n_sets, w, h, views, model, basis, instances, n_instances, sets, subjects, n_subjects, params, records))
 DH_API(fit_shape_views_device, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model, const dh_fit_basis *basis, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n_sets, w, h, views, model, basis, instances, n_instances, sets, subjects, n_subjects, params, records, stream))
+DH_API(calib_params_default, (dh_calib_params *p), (p))
+DH_API(fit_calibrate_views, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *take, const uint8_t *hold, const dh_calib_params *params, dh_calib_record *records), (f, frames, n_sets, w, h, views, model, instances, n_instances, sets, take, hold, params, records))
+DH_API(fit_calibrate_views_device, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *take, const uint8_t *hold, const dh_calib_params *params, dh_calib_record *records, void *stream), (f, frames, n_sets, w, h, views, model, instances, n_instances, sets, take, hold, params, records, stream))
 DH_API(fit_track_params_default, (dh_fit_track_params *p), (p))
 DH_API(fit_tracker_angles, (double out[DH_FIT_TRACK_ANGLES][2]), (out))
 DH_API(fit_tracker_create, (const dh_cameras *c, const dh_fit_model *m, float scale, uint32_t flags, const dh_fit_track_params *params, dh_fit_tracker **out), (c, m, scale, flags, params, out))

@@ -1,9 +1,9 @@
 // dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip,
-// k_fit_shape_views.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
+// k_fit_shape_views.hip, k_calib_views.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
 // words of both trackers, and the one test of whether an instance may be fitted (dh_fit_instance_fault: the host's refusals and
 // the shape kernel's skips).  The device arithmetic the kernels share among themselves is in dh_fit_device.h.  Not part of the
 // ABI.  The rules are stated in include/depthhead_hip.h (sections "fitting posed models to depth frames" and after) and
-// DESIGN.md sections 18 - 23.
+// DESIGN.md sections 18 - 24.
 #pragma once
 #include "dh_internal.h"
 #include "dh_rig_fit.h"
@@ -278,6 +278,86 @@ struct ShapeViewsArgs {
     uint32_t ranks;               // min(64, n): the views an instance can have
 };
 hipError_t dh_launch_shape_accumulate_views(const ShapeViewsArgs &a, hipStream_t s);
+
+// ---- calibrating a view table (k_calib_views.hip)
+static_assert(sizeof(dh_calib_params) == 64, "dh_calib_params: 64 bytes");
+static_assert(sizeof(dh_calib_record) == 120, "dh_calib_record: 120 bytes");
+static_assert(DH_CALIB_SKIP == DH_SHAPE_SKIP, "take[i] is handed to dh_shape_views_skip as the subject");
+// Magnitudes.  A pair's point pass is section 21's at the composite (R_v, t_v), so |p - t_v| = |R_v sv| <= 1.032 * 4096 < 4228 and
+// |nrm| <= 1.05 as derived above.  A pair takes part only while |t_v[i] - g_c[i]| <= DH_CALIB_MAX_ARM = 2048 per component, so
+// |t_v - g_c| <= 2048 sqrt(3) < 3548 and |q| = |p - g_c| <= 4228 + 3548 < 7776.  The cross product has |m| <= |q| |nrm| <= 1.05 *
+// 7776 < 8165, and the rotation columns are m / DH_CALIB_ARM_UNIT: |J_3..5| < 8165 / 64 < 127.6 < 2^7; |J_0..2| <= 1.05.  The
+// gate lies in (0, DH_SHAPE_MAX_GATE = 256], so while |p| <= 2 p.z, |r| <= 1.05 * 2 * 256 < 538.  Products: J J < 127.6^2 <
+// 16282 < 2^14, J r < 127.6 * 538 < 68649 < 2^16.1, r r < 538^2 < 2^18.2: every one below section 20's 2^19.  Times 2^20, times
+// DH_SHAPE_MAX_TERMS = 2^23 terms of one CAMERA -- the host form adds the model's points per pair that takes part, the _device
+// form bounds the call by n_instances * points (an instance gives a camera at most one pair) -- below 2^62 < 2^63.  Without
+// the arm unit |J_3..5| would reach 2^13 and J J 2^26: 2^23 terms would not fit.  Without the arm limit |q| is unbounded.
+static_assert(DH_CALIB_ARM_UNIT == 64.0 && DH_CALIB_MAX_ARM == 2048.0 && DH_SHAPE_MAX_GATE <= 256.0, "the magnitude argument above");
+#define DH_CALIB_THREADS 256
+#define DH_CALIB_STRIDE 32            // words of a camera's row: the fit's 29 at their offsets, the pair count at DH_FIT_USED
+
+// Why an (instance, view) pair of a calibration step takes no part, stated once for the host loop (which turns the whole-
+// instance answers into its messages and counts the pairs that are left) and k_calib_accumulate (which skips).  The whole
+// instance first: DH_CALIB_SKIP, then the per-instance refusals of the header in their order -- dh_shape_views_skip's with
+// `take` for the subject, one subject and no basis (largest 0.0: the field test passes whenever the scale is finite).
+__host__ __device__ inline ShapeViewsSkip dh_calib_skip(const dh_view_instance &in, uint32_t set, uint32_t take, uint32_t n, uint32_t n_sets, double radius) {
+    return dh_shape_views_skip(in, set, take == DH_CALIB_SKIP ? DH_SHAPE_SKIP : 0u, n, n_sets, 1u, radius, 0.0);
+}
+// Then the pair, of an instance that passed: the composite camera pose of the view (section 21's expressions), the camera's
+// pivot g_c, and whether the pair is left out -- the camera is held, or a component of t_v - g_c exceeds DH_CALIB_MAX_ARM (a NaN
+// fails).  Neither is a refusal.
+enum { DH_CALIB_PAIR_OK = 0, DH_CALIB_PAIR_HELD, DH_CALIB_PAIR_ARM };
+struct CalibPair {
+    int why;                      // DH_CALIB_PAIR_*
+    double R[9], t[3];            // (R_v, t_v)
+    double g[3];                  // g_c
+};
+// g_c alone (the solve needs it for a camera no pair names)
+__host__ __device__ inline void dh_calib_pivot(const FitView &vw, const double o[3], double g[3]) {
+    for (int i = 0; i < 3; ++i)
+        g[i] = (((double)vw.V[3 * i] * o[0] + (double)vw.V[3 * i + 1] * o[1]) + (double)vw.V[3 * i + 2] * o[2]) + (double)vw.u[i];
+}
+__host__ __device__ inline CalibPair dh_calib_pair(const dh_view_instance &in, const FitView &vw, const double o[3], bool held) {
+    CalibPair c;
+    c.why = DH_CALIB_PAIR_OK;
+    for (int i = 0; i < 3; ++i) {
+        const double v0 = (double)vw.V[3 * i], v1 = (double)vw.V[3 * i + 1], v2 = (double)vw.V[3 * i + 2];
+        for (int j = 0; j < 3; ++j) c.R[3 * i + j] = (v0 * (double)in.R[j] + v1 * (double)in.R[3 + j]) + v2 * (double)in.R[6 + j];
+        c.t[i] = ((v0 * (double)in.t[0] + v1 * (double)in.t[1]) + v2 * (double)in.t[2]) + (double)vw.u[i];
+    }
+    dh_calib_pivot(vw, o, c.g);
+    for (int i = 2; i >= 0; --i) {
+        const double arm = c.t[i] - c.g[i];
+        if (!((arm < 0.0 ? -arm : arm) <= DH_CALIB_MAX_ARM)) c.why = DH_CALIB_PAIR_ARM;
+    }
+    if (held) c.why = DH_CALIB_PAIR_HELD;
+    return c;
+}
+
+struct CalibArgs {
+    const uint16_t *frames;       // [n_sets][n][h][w]
+    int n, w, h;                  // n: the view table's cameras
+    const DhCam *cams;            // [n]
+    const FitView *views;         // [n]
+    const float *pts, *nrm;       // the model: [np][3] each
+    uint32_t np;
+    double radius;                // the model's largest |v|
+    const dh_view_instance *inst; // [n_inst]
+    const uint32_t *sets;         // nullable [n_inst]
+    const uint32_t *take;         // nullable [n_inst]
+    const uint8_t *hold;          // nullable [n]
+    uint32_t n_inst, n_sets;
+    uint32_t ranks;               // min(64, n): the views an instance can have
+    uint32_t min_points;
+    double gate;
+    double lam1;                  // 1.0 + lambda (computed on the host: one f64 sum)
+    double pivot[3];              // o
+    unsigned long long *sums;     // [n][DH_CALIB_STRIDE], cleared on the stream (k_calib_clear) before the accumulation
+    dh_calib_record *rec;         // [n]
+};
+hipError_t dh_launch_calib_clear(const CalibArgs &a, hipStream_t s);       // rows 0 .. n - 1 of a.sums
+hipError_t dh_launch_calib_accumulate(const CalibArgs &a, hipStream_t s);  // one workgroup per (instance, view) pair: n_inst * ranks
+hipError_t dh_launch_calib_solve(const CalibArgs &a, hipStream_t s);       // one lane per camera
 
 // ---- carrying each rig person's fitted world pose across steps (k_rig_fit_track.hip and k_fit_views' per-instance-schedule
 // instance).  The bind of a step is stated in dh_rig_fit.h.

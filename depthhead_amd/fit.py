@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, FIT_VIEW_TOLERANCE, HEAD_DTYPE,
+from ._lib import (CALIB_RECORD_DTYPE, CALIB_SKIP, FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, FIT_VIEW_TOLERANCE, HEAD_DTYPE,
                    MAX_HEADS, POSE_DTYPE, RIG_FIT_RECORD_DTYPE, RIG_FIT_STATE_DTYPE, RIG_MAX_PERSONS, RIG_MAX_TRACKS, RIG_PERSON_DTYPE,
                    RIG_TRACK_DTYPE, RENDER_INSTANCE_DTYPE, SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUPPORT_DTYPE, SUPPORT_RADIUS, VIEW_FIT_RECORD_DTYPE,
                    VIEW_INSTANCE_DTYPE, check, vp)
@@ -20,6 +20,7 @@ FIT_TRACK_NONE, FIT_TRACK_FITTED, FIT_TRACK_CARRIED, FIT_TRACK_REJECTED, FIT_TRA
 FIT_TRACK_BAD_STATUS, FIT_TRACK_BAD_POINTS, FIT_TRACK_BAD_RMS, FIT_TRACK_BAD_JUMP = 0x100, 0x200, 0x400, 0x800
 FIT_TRACK_MOTION = 1                                # DH_FIT_TRACK_MOTION
 SHAPE_OK, SHAPE_FEW_POINTS, SHAPE_SINGULAR = 0, 1, 2  # dh_shape_record.status
+CALIB_OK, CALIB_FEW_POINTS, CALIB_SINGULAR, CALIB_NOT_ORTHONORMAL, CALIB_HELD = 0, 1, 2, 3, 4  # dh_calib_record.status
 
 
 def vertex_normals(verts, tris) -> np.ndarray:
@@ -184,6 +185,37 @@ def shape_params(gate=None, lam=None, min_points=None) -> "_lib.ShapeParams":
     if min_points is not None:
         p.min_points = int(min_points)
     return p
+
+
+def calib_params(gate=None, lam=None, min_points=None, pivot=None) -> "_lib.CalibParams":
+    """dh_calib_params_default with the given fields replaced."""
+    p = _lib.CalibParams()
+    check(_lib.load().dh_calib_params_default(C.byref(p)))
+    if gate is not None:
+        p.gate = float(gate)
+    if lam is not None:
+        p.lam = float(lam)
+    if min_points is not None:
+        p.min_points = int(min_points)
+    if pivot is not None:
+        p.pivot[0], p.pivot[1], p.pivot[2] = (float(v) for v in pivot)
+    return p
+
+
+def views_from_records(cameras, views_V, views_u, records) -> "Views":
+    """The next view table after a calibration step: a new `Views` of `cameras` that takes V and u from
+    every record whose status is CALIB_OK and keeps the old entry (views_V [n, 3, 3], views_u [n, 3]) elsewhere.  A
+    dh_fit_views is immutable, so each round makes a new table on the host; the old one may be closed once nothing is bound to
+    it."""
+    V = np.array(views_V, dtype=np.float32).reshape(-1, 3, 3)
+    u = np.array(views_u, dtype=np.float32).reshape(-1, 3)
+    rec = np.asarray(records).reshape(-1)
+    if len(rec) != len(V) or len(u) != len(V):
+        raise ValueError("one record, one V and one u per camera are expected")
+    ok = rec["status"] == CALIB_OK
+    V[ok] = rec["V"][ok].reshape(-1, 3, 3)
+    u[ok] = rec["u"][ok]
+    return Views(cameras, V, u)
 
 
 def deform(verts, basis, coeffs) -> np.ndarray:
@@ -377,6 +409,51 @@ class Fitter(_lib._Handle):
         return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
 
 
+    def calibrate_step(self, frames, views, model, instances, sets=None, take=None, hold=None, params=None, device_out: bool = False,
+                       stream=None):
+        """One calibration step of the cameras of `views` (a `Views` of n cameras) over the world-posed
+        `instances` (VIEW_INSTANCE_DTYPE, what fit_views returned) of frames [n_sets, n, h, w] u16, with `model` held: sets
+        [n_instances] u32 (None: all in set 0), take [n_instances] u32 (None: all take part; CALIB_SKIP leaves an instance out),
+        hold [n] u8 (None: none; non-zero: the camera is held and gets no update).  Host form: numpy arrays -> CALIB_RECORD_DTYPE
+        [n], one record per camera.  With device_out=True frames, instances, sets, take and hold are torch tensors on the device
+        (instances as the uint8 tensor Fitter.fit_views(device_out=True) returned, sets and take int32 or None, hold uint8 or
+        None) and the records come back as a uint8 torch tensor, ordered on `stream` (default the current torch stream) without
+        a host wait."""
+        n_sets, n, h, w = (int(v) for v in frames.shape)
+        if n != len(views):
+            raise ValueError(f"{n} frames a set for a view table of {len(views)} cameras")
+        prm = C.byref(params) if params is not None else None
+        if not device_out:
+            fr = np.ascontiguousarray(frames, dtype=np.uint16)
+            inst = np.ascontiguousarray(instances, dtype=VIEW_INSTANCE_DTYPE)
+            st = None if sets is None else np.ascontiguousarray(sets, dtype=np.uint32).reshape(len(inst))
+            tk = None if take is None else np.ascontiguousarray(take, dtype=np.uint32).reshape(len(inst))
+            hd = None if hold is None else np.ascontiguousarray(hold, dtype=np.uint8).reshape(n)
+            rec = np.zeros(n, CALIB_RECORD_DTYPE)
+            check(self._lib.dh_fit_calibrate_views(self._h, vp(fr), C.c_uint32(n_sets), w, h, views._h, model._h,
+                                                   vp(inst) if len(inst) else None, C.c_uint32(len(inst)), vp(st), vp(tk), vp(hd), prm, vp(rec)))
+            return rec
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
+            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
+        ni = instances.numel() * instances.element_size() // VIEW_INSTANCE_DTYPE.itemsize
+        for name, words in (("sets", sets), ("take", take)):
+            if words is not None and (words.numel() != ni or words.element_size() != 4 or not words.is_contiguous()):
+                raise ValueError(f"device {name}: a contiguous 32-bit tensor with one word per instance is expected")
+        if hold is not None and (hold.numel() != n or hold.element_size() != 1 or not hold.is_contiguous()):
+            raise ValueError("device hold: a contiguous 8-bit tensor with one byte per camera is expected")
+        rec = torch.empty(n * CALIB_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        check(self._lib.dh_fit_calibrate_views_device(self._h, C.c_void_p(frames.data_ptr()), C.c_uint32(n_sets), w, h, views._h, model._h,
+                                                      C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
+                                                      C.c_void_p(sets.data_ptr()) if sets is not None else None,
+                                                      C.c_void_p(take.data_ptr()) if take is not None else None,
+                                                      C.c_void_p(hold.data_ptr()) if hold is not None else None, prm,
+                                                      C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
+        return rec
+
+
 def adapt(fitter, frames, K_or_cameras, verts, tris, basis, starts, rounds: int = 6, fit_prm=None, shape_prm=None, coeffs=None):
     """Adapt the shape coefficients of one subject's model to `frames` ([n, h, w] u16, numpy) by alternation, `rounds` times:
     build the model from the current coefficients (deform, vertex_normals); fit every frame from its previous pose (the first
@@ -429,6 +506,80 @@ def adapt_views(fitter, frames, views, verts, tris, basis, starts, sets=None, ro
             trace.append({"coeffs": c.copy(), "fit": rec, "shape": srec, "delta": delta})
             c = c + delta
     return c, inst, trace
+
+
+def calibrate_views(fitter, frames, cameras, V, u, model, starts, sets=None, hold=None, steps: int = 8, wide_steps: int = 3,
+                    gates=(60.0, 25.0), rounds: int = 3, joint_steps: int = 2, fit_prm=None, refit_prm=None, lam=None, min_points=None):
+    """Calibrate the extrinsics (V [n, 3, 3], u [n, 3]) of the cameras of `cameras` from frames [n_sets, n, h, w] u16 (numpy) of
+    one head model moved through the volume.  `starts` are VIEW_INSTANCE_DTYPE [m] rough world poses
+    whose `views` name every camera that sees the instance, sets [m] the set of each (None: set 0), hold [n] marks the gauge
+    cameras, whose entries are trusted and stay as they are: at least one is needed.  Three stages:
+      1. every instance is fitted against the HELD cameras among its views only (fit_prm);
+      2. `steps` calibration steps with the pivot at the mean fitted position, the first `wide_steps` at gates[0], the others
+         at gates[1], over the fits that ended FIT_OK, a new table after each;
+      3. `rounds` times: every instance is refitted against ALL its views from its last pose (refit_prm, default no coarse and
+         6 full steps), then `joint_steps` calibration steps at gates[1].
+    Each step waits on the host: this happens once per rig, not once per frame.  Returns (V, u, the last instances, trace):
+    trace is a list of {"stage", "records" (CALIB_RECORD_DTYPE [n]), "fit" (the VIEW_FIT_RECORD_DTYPE [m] records the step's
+    poses came from)}."""
+    V = np.array(V, dtype=np.float32).reshape(-1, 3, 3)
+    u = np.array(u, dtype=np.float32).reshape(-1, 3)
+    n = len(V)
+    inst = np.array(starts, dtype=VIEW_INSTANCE_DTYPE)
+    st = np.zeros(len(inst), np.uint32) if sets is None else np.ascontiguousarray(sets, dtype=np.uint32).reshape(len(inst))
+    hd = np.zeros(n, np.uint8) if hold is None else (np.asarray(hold).reshape(n) != 0).astype(np.uint8)
+    if refit_prm is None:
+        refit_prm = fit_params(coarse_iterations=0, iterations=6)
+    all_views = inst["views"].copy()
+    held_mask = np.zeros(len(inst), np.uint64)
+    for i, s in enumerate(inst):
+        m = 0
+        for k in range(64):
+            c = int(s["first_cam"]) + k
+            if (int(s["views"]) >> k) & 1 and c < n and hd[c]:
+                m |= 1 << k
+        held_mask[i] = m
+    trace = []
+
+    def fit_all(table, masks, prm):
+        rec = np.zeros(len(inst), VIEW_FIT_RECORD_DTYPE)
+        rec["status"] = FIT_FEW_POINTS
+        for s in np.unique(st):
+            of = np.flatnonzero((st == s) & (masks != 0))
+            if not len(of):
+                continue
+            one = inst[of].copy()
+            one["model"], one["views"] = 0, masks[of]
+            out, rec[of] = fitter.fit_views(frames[int(s)], [model], one, table, params=prm)
+            inst["R"][of], inst["t"][of] = out["R"], out["t"]
+        return rec
+
+    def calib(table, rec, gate, stage):
+        nonlocal V, u
+        ok = rec["status"] == FIT_OK
+        pivot = inst["t"][ok].astype(np.float64).mean(axis=0) if ok.any() else np.zeros(3)
+        take = np.where(ok, 0, CALIB_SKIP).astype(np.uint32)
+        crec = fitter.calibrate_step(frames, table, model, inst, sets=st, take=take, hold=hd,
+                                     params=calib_params(gate=gate, lam=lam, min_points=min_points, pivot=pivot))
+        trace.append({"stage": stage, "records": crec, "fit": rec})
+        nxt = views_from_records(cameras, V, u, crec)
+        V, u = nxt.V, nxt.u
+        table.close()
+        return nxt
+
+    table = Views(cameras, V, u)
+    try:
+        rec = fit_all(table, held_mask, fit_prm)
+        inst["views"] = all_views
+        for k in range(int(steps)):
+            table = calib(table, rec, gates[0] if k < int(wide_steps) else gates[1], "held")
+        for r in range(int(rounds)):
+            rec = fit_all(table, all_views, refit_prm)
+            for _ in range(int(joint_steps)):
+                table = calib(table, rec, gates[1], f"joint {r}")
+    finally:
+        table.close()
+    return V, u, inst, trace
 
 
 def fit_track_params(iterations_tracked=None, keep_points=None, rms_max=None, max_jump=None, conf=None, min_windows=None,

@@ -1024,6 +1024,104 @@ int dh_fit_shape_views_device(dh_fitter *f, const uint16_t *frames, uint32_t n_s
                               uint32_t n_instances, const uint32_t *sets, const uint32_t *subjects, uint32_t n_subjects,
                               const dh_shape_params *params, dh_shape_record *records, void *stream);
 
+/* ---- calibrating a view table ----
+ * Every multi-view section above takes the view table on faith.  A CALIBRATION STEP reads the same residual once more with the
+ * fitted world poses and the model HELD and each camera MOVED: one Gauss-Newton step per camera over all the (instance, point)
+ * pairs that camera sees, for a small rigid motion of the camera.  Not in the reference: PARITY UNPINNED, the definition below is
+ * this library's.  The arithmetic conventions are the fit's: f64, evaluated left to right, every product, sum and quotient
+ * rounded on its own (no contraction), + - * /, compares and casts only, no library function on the device.
+ * ONE CALIBRATION STEP takes frames [n_sets][n][h][w] u16 (section 23's layout: frame s * n + c is camera c at set s), a
+ *   dh_fit_views table of n cameras, ONE model, n_instances dh_view_instance (what dh_fit_depth_views* wrote; `model` and `flags`
+ *   are ignored), sets[n_instances] (NULL: set 0), take[n_instances] (NULL: all take part; DH_CALIB_SKIP: the instance takes no
+ *   part; any other value: it does), hold[n] bytes (NULL: none; non-zero: camera c is HELD, a gauge camera that gets no update)
+ *   and dh_calib_params.  It writes one dh_calib_record per CAMERA.
+ * PIVOT: params.pivot is one world point o (mm).  Camera c's pivot is its image, formed as section 21 forms t_v:
+ *     g_c[i] = ((V[i][0] * o0 + V[i][1] * o1) + V[i][2] * o2) + u[i]
+ *   The camera is turned about g_c, not about its own origin: with o among the heads a rotation moves the model points little,
+ *   so rotation and translation decouple and the lever arms stay short (Magnitudes).
+ * ACCUMULATION, for every instance that takes part and every set bit k of `views` with c = first_cam + k not held: the
+ *   composite (R_v, t_v) is formed exactly as section 21 writes it.  The pair takes no part unless |t_v[i] - g_c[i]| <=
+ *   DH_CALIB_MAX_ARM for i = 0, 1, 2 (a NaN fails).  Every point of the model runs ONE PASS of section 18 unchanged at (scale,
+ *   R_v, t_v), camera c's K, frame sets[i] * n + c and gate g = params.gate.  A point that passed adds to CAMERA c's sums the
+ *   fit's full row with the pivot in place of the translation:
+ *     q = p - g_c;   m = (q1 * nrm2 - q2 * nrm1,  q2 * nrm0 - q0 * nrm2,  q0 * nrm1 - q1 * nrm0)
+ *     J = (nrm0, nrm1, nrm2, m0 / DH_CALIB_ARM_UNIT, m1 / DH_CALIB_ARM_UNIT, m2 / DH_CALIB_ARM_UNIT)       (64: the division is exact)
+ *   A_ab += (int64)((J_a * J_b) * S) for a <= b (21),  b_a += (int64)((J_a * r) * S) (6),  e += (int64)((r * r) * S),  count += 1,
+ *   with S = 2^20 and truncating casts, so their order is free.  pairs += 1 for every (instance, view) pair that passed a point.
+ *   Moving the camera by (d, w) about g_c moves a camera-space point p to C (p - g_c) + g_c + d: J is the derivative of the
+ *   residual with respect to d and to 64 w.
+ *   Magnitudes: |q| <= |p - t_v| + |t_v - g_c| <= 1.032 * 4096 + 2048 sqrt(3) < 7775, so |J_3..5| <= 1.05 * 7775 / 64 < 128 and
+ *   |J_0..2| <= 1.05; the gate lies in (0, DH_SHAPE_MAX_GATE], so |r| < 538 while |p| <= 2 p.z: J J < 2^14, J r < 2^16.1,
+ *   r r < 2^18.2, every product below section 20's 2^19; times 2^20, a camera may sum DH_SHAPE_MAX_TERMS = 2^23 (instance, point)
+ *   terms below 2^62.  Outside |p| <= 2 p.z the words of section 18 hold (unspecified, nothing faults).
+ * SOLVE, per camera: a held camera gets DH_CALIB_HELD.  Else count < min_points gives DH_CALIB_FEW_POINTS.  Else A_ab = (double)sum
+ *   / S (A symmetric), b_a alike, A_aa = A_aa * (1.0 + lambda) + 1e-9, and A x = b is solved on the 6 x 6 block by section 18's
+ *   elimination and back substitution; a pivot that is not > 0.0 gives DH_CALIB_SINGULAR.  Else d = x[0..2], w[j] = x[3 + j] /
+ *   DH_CALIB_ARM_UNIT, C is section 18's Cayley rotation of w (a = w / 2.0 and the nine quotients written there), and
+ *     V'[i][j] = (C[i][0] * V[0][j] + C[i][1] * V[1][j]) + C[i][2] * V[2][j]
+ *     s = u - g_c;   u'[i] = (((C[i][0] * s0 + C[i][1] * s1) + C[i][2] * s2) + g_c[i]) + d[i]
+ *   both rounded to f32 once.  If an element of V' V'^T (of the ROUNDED V', in f64, formed as R R^T is in section 18) is further
+ *   than DH_FIT_VIEW_TOLERANCE from the identity's (NaN included) the status is DH_CALIB_NOT_ORTHONORMAL, else DH_CALIB_OK.
+ * RECORD: V, u = the updated entry when the status is DH_CALIB_OK, otherwise the table's own entry bit for bit; points = count;
+ *   pairs; status; sum_r2_fixed = e, the residual BEFORE the step; delta = (d, w), zeros unless DH_CALIB_OK.  The view table is
+ *   immutable: the caller builds the next one on the host from the records (fit.views_from_records).  Bit-identical run to run
+ *   and to tests/calib_ref.py.
+ * The calls run on a dh_fitter, which owns the sums ([n] rows of 32 words, taken at the first call of a given table size) and,
+ * for the host call, the staging; the calibration calls of one fitter must be stream-ordered with one another and with its
+ * shape calls.  dh_fit_calibrate_views takes host frames, instances, sets, take, hold and records and is synchronous.
+ * dh_fit_calibrate_views_device takes device pointers for those, enqueues exactly three kernels on `stream` (NULL = default
+ * stream) -- k_calib_clear, k_calib_accumulate (one workgroup per (instance, view) pair), k_calib_solve -- and never waits on
+ * the host: it chains after dh_fit_depth_views_device, whose `out` is its `instances`.  params is host memory in both forms;
+ * NULL selects dh_calib_params_default.
+ * DH_EINVAL before anything is launched, with the outputs untouched: NULL fitter / frames / records / model; a model of another
+ * device than the fitter; a NULL view table or one of another device; n_sets of 0, or n_sets * n above 65535; w or h outside
+ * 1 .. DH_RENDER_MAX_SIZE; a gate outside (0, DH_SHAPE_MAX_GATE] (NaN included); lambda not >= 0 or not finite; min_points 0; a
+ * non-finite pivot; a reserved word that is not 0; instances NULL with n_instances > 0; n_instances above 2^23.  The host call
+ * also refuses, per instance that takes part, in this order: views == 0; a set bit naming a camera >= n; a set >= n_sets; a
+ * non-finite R, t or scale; an R outside DH_FIT_R_TOLERANCE; |scale| * (the model's largest |v|) above DH_FIT_MAX_EXTENT; and a
+ * camera that is not held whose pairs times the model's points exceed DH_SHAPE_MAX_TERMS (every pair of an instance that takes
+ * part counts here, one beyond the arm too: only the device forms t_v).  A pair beyond DH_CALIB_MAX_ARM is SKIPPED in both
+ * forms, not refused (the caller cannot know it before the fit), and is not counted in the record's `pairs`.  The _device call cannot read
+ * the instances: it refuses n_instances * (the model's points) above DH_SHAPE_MAX_TERMS, and the device skips, AS A WHOLE, every
+ * instance one of the per-instance refusals names, a NaN failing each test, so no input leads out of a buffer or out of the
+ * magnitude bound.  n_instances = 0 is no error: every camera that is not held reports DH_CALIB_FEW_POINTS. */
+#define DH_CALIB_OK 0u
+#define DH_CALIB_FEW_POINTS 1u         /* the camera's pairs associated fewer than min_points points */
+#define DH_CALIB_SINGULAR 2u           /* a pivot of the normal equations was not > 0 */
+#define DH_CALIB_NOT_ORTHONORMAL 3u    /* the updated V, rounded to f32, is outside DH_FIT_VIEW_TOLERANCE */
+#define DH_CALIB_HELD 4u               /* hold[c] was set */
+#define DH_CALIB_SKIP 0xFFFFFFFFu      /* take[i]: instance i takes no part */
+#define DH_CALIB_ARM_UNIT 64.0         /* mm: the unit of the rotation columns (a power of two) */
+#define DH_CALIB_MAX_ARM 2048.0        /* mm: largest |t_v[i] - g_c[i]| of a pair that takes part */
+typedef struct dh_calib_params {
+    double   gate;                /* 25 (mm), in (0, DH_SHAPE_MAX_GATE] */
+    double   lambda;              /* 1e-3: relative damping of the diagonal, >= 0 */
+    double   pivot[3];            /* 0, 0, 0 (mm): the world point o the cameras are turned about */
+    uint32_t min_points;          /* 64, at least 1 */
+    uint32_t reserved0;           /* 0 */
+    uint64_t reserved[2];         /* 0 */
+} dh_calib_params;     /* 64 bytes */
+typedef struct dh_calib_record {
+    float    V[9], u[3];          /* the updated entry when status is DH_CALIB_OK; otherwise the table's own, bit for bit */
+    uint32_t points;              /* count */
+    uint32_t pairs;               /* the (instance, view) pairs that passed a point */
+    uint32_t status;              /* DH_CALIB_* */
+    uint32_t reserved;            /* 0 */
+    int64_t  sum_r2_fixed;        /* e: the residual before the step */
+    double   delta[6];            /* d (mm) and w (radians to first order); 0 unless status is DH_CALIB_OK */
+} dh_calib_record;     /* 120 bytes, no padding */
+int dh_calib_params_default(dh_calib_params *p);
+/* frames [n_sets][n][h][w] u16 with n the view table's cameras; instances, sets (or NULL) and take (or NULL) [n_instances];
+ * hold (or NULL) [n] bytes; records [n] */
+int dh_fit_calibrate_views(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views,
+                           const dh_fit_model *model, const dh_view_instance *instances, uint32_t n_instances,
+                           const uint32_t *sets, const uint32_t *take, const uint8_t *hold, const dh_calib_params *params,
+                           dh_calib_record *records);
+int dh_fit_calibrate_views_device(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views,
+                                  const dh_fit_model *model, const dh_view_instance *instances, uint32_t n_instances,
+                                  const uint32_t *sets, const uint32_t *take, const uint8_t *hold, const dh_calib_params *params,
+                                  dh_calib_record *records, void *stream);
+
 /* ---- carrying each rig person's fitted world pose across steps ----
  * The composition of the three sections above: every person of every rig keeps ONE fitted pose in the WORLD frame under the
  * rig-wide id the rig tracker (section 16) gave it.  Each step refits that pose against all the views that see the person,
