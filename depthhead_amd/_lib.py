@@ -103,6 +103,12 @@ SHAPE_SKIP = 0xFFFFFFFF    # DH_SHAPE_SKIP
 SHAPE_MAX_FIELD = 256      # DH_SHAPE_MAX_FIELD (mm)
 SHAPE_MAX_GATE = 256       # DH_SHAPE_MAX_GATE (mm)
 SHAPE_MAX_TERMS = 1 << 23  # DH_SHAPE_MAX_TERMS
+# dh_subject_state: one subject of a dh_fit_subjects (its coefficients, counters, flags)
+SUBJECT_STATE_DTYPE = np.dtype([("coeffs", "<f8", (8,)), ("applied", "<u4"), ("rejected", "<u4"), ("flags", "<u4"), ("zero_normals", "<u4")],
+                               align=True)
+assert SUBJECT_STATE_DTYPE.itemsize == 80
+SUBJECTS_MAX_TRIS = 131072  # DH_SUBJECTS_MAX_TRIS
+SUBJECT_CLAMPED, SUBJECT_NONFINITE = 1, 2   # DH_SUBJECT_*
 
 
 # dh_view_instance / dh_view_fit_record: one world-posed model seen by several cameras, and what its fit reports (dh_fit_depth_views*)
@@ -217,6 +223,10 @@ EXPORTS = [
     "dh_rig_fit_track_params_default", "dh_rig_fit_tracker_create", "dh_rig_fit_tracker_destroy", "dh_rig_fit_tracker_reset",
     "dh_rig_fit_tracker_state", "dh_rig_fit_tracker_step_persons", "dh_rig_fit_tracker_step_persons_device", "dh_rig_fit_tracker_step",
     "dh_rig_fit_tracker_step_device",
+    "dh_fit_subjects_create", "dh_fit_subjects_destroy", "dh_fit_subjects_info", "dh_fit_subjects_model", "dh_fit_subjects_set_coeffs",
+    "dh_fit_subjects_state", "dh_fit_subjects_read", "dh_fit_subjects_update", "dh_fit_subjects_update_device", "dh_fit_shape_subjects", "dh_fit_shape_subjects_cameras",
+    "dh_fit_shape_subjects_device", "dh_fit_shape_subjects_cameras_device", "dh_fit_depth_carried_device",
+    "dh_fit_depth_cameras_carried_device",
 ]
 
 

@@ -2818,6 +2818,7 @@ struct dh_fitter {
     Buf<dh_render_instance> shape_inst;      // host shape calls
     Buf<uint32_t> shape_subj;
     Buf<dh_shape_record> shape_rec;
+    Buf<dh_fit_record> shape_fit_rec;        // host shape calls over a subject set: the instances' fit records
     Buf<dh_view_instance> shape_vinst;       // host multi-view shape calls
     Buf<uint32_t> shape_vsubj, shape_vsets;
     Buf<unsigned long long> calib_sums;      // calibration calls: [cameras][DH_CALIB_STRIDE], taken at the first one of a table size
@@ -2902,6 +2903,7 @@ struct FitReq {
     const dh_render_instance *inst; uint32_t n_inst;
     const dh_fit_params *prm;
     dh_render_instance *out; dh_fit_record *rec;
+    const dh_render_instance *carried = nullptr;     // (device forms) nullable [n_inst] on the device: the R and t to start from
 };
 static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, const char *who) {
     // ---- refusals: all of them before anything is allocated or launched
@@ -2949,6 +2951,7 @@ static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, 
     } else { a.frames = q.frames; a.out = q.out; a.rec = q.rec; }
     TRY(f->tab.upload(bytes, s));
     if (!dev) HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    if (q.carried) TRY(hip_step(dh_launch_fit_carry((dh_render_instance *)(f->tab.dev.get() + o_inst), q.carried, q.n_inst, s), "k_fit_carry"));
     TRY(hip_step(dh_launch_fit(a, s), "k_fit"));
     TRY(f->tab.done(s));
     if (!dev) {
@@ -2973,6 +2976,21 @@ static int fit_depth_device_(dh_fitter *f, const uint16_t *frames, int n, int w,
 static int fit_depth_cameras_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models,
                                      const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream) {
     return fit_run(f, FitReq{frames, n, w, h, nullptr, c, true, models, n_models, instances, n_instances, params, out, records}, true, (hipStream_t)stream, "dh_fit_depth_cameras_device");
+}
+// The device forms whose instances start from the device output of an earlier fit.
+static int fit_depth_carried_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models, uint32_t n_models,
+                                     const dh_render_instance *instances, uint32_t n_instances, const dh_render_instance *carried, const dh_fit_params *params,
+                                     dh_render_instance *out, dh_fit_record *records, void *stream) {
+    const char *who = "dh_fit_depth_carried_device";
+    if (n_instances && !carried) return fail(DH_EINVAL, "%s: NULL carried instances", who);
+    return fit_run(f, FitReq{frames, n, w, h, K, nullptr, false, models, n_models, instances, n_instances, params, out, records, carried}, true, (hipStream_t)stream, who);
+}
+static int fit_depth_cameras_carried_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models,
+                                             uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_render_instance *carried,
+                                             const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream) {
+    const char *who = "dh_fit_depth_cameras_carried_device";
+    if (n_instances && !carried) return fail(DH_EINVAL, "%s: NULL carried instances", who);
+    return fit_run(f, FitReq{frames, n, w, h, nullptr, c, true, models, n_models, instances, n_instances, params, out, records, carried}, true, (hipStream_t)stream, who);
 }
 
 // ------------------------------------------------------------------ fitting one model to several views
@@ -3133,6 +3151,9 @@ struct dh_fit_basis {
     double largest = 0.0;         // the largest |B_k[i]|
     Buf<float> planes;
 };
+// (tests/test_abi_fit_shape.py and tests/test_abi_subjects.py hand a zeroed block of 256 bytes where a refusal only needs a basis
+// that is not NULL: a basis of 0 points on device 0 whose memory is never touched)
+static_assert(sizeof(dh_fit_basis) <= 256, "the ABI tests' stand-in for a basis is 256 zero bytes");
 static int fit_basis_create_(const float *fields, uint32_t n, uint32_t n_fields, int device, dh_fit_basis **out) {
     if (!out) return fail(DH_EINVAL, "dh_fit_basis_create: NULL argument");
     *out = nullptr;
@@ -3186,6 +3207,187 @@ static int shape_params_default_(dh_shape_params *p) {
     return DH_OK;
 }
 
+// ---- a shape per subject
+// A set: S deformable models of one base mesh on one device.  The models are ordinary dh_fit_models that the set owns; their
+// radius is the set's bound.
+struct dh_fit_subjects {
+    int device = 0;
+    uint32_t n = 0, n_tris = 0, n_subjects = 0;
+    double max_coeff = 0.0, radius = 0.0;    // radius: the bound on |v'| (dh_subjects_radius_bound)
+    const dh_fit_basis *basis = nullptr;     // borrowed: it outlives the set
+    Buf<float> base;
+    Buf<uint32_t> tris, corner_begin, corners;
+    Buf<dh_subject_state> state;
+    Buf<SubjectModel> table;                 // [S] the models' pointers
+    Buf<dh_shape_record> rec;                // the host update's records
+    std::vector<std::unique_ptr<dh_fit_model>> models;
+    hipStream_t s = nullptr;                 // the host calls' stream
+    ~dh_fit_subjects() { if (s) (void)hipStreamDestroy(s); }
+};
+static SubjectsArgs subjects_args(const dh_fit_subjects *set, const dh_shape_record *rec, uint32_t first, uint32_t count) {
+    SubjectsArgs a;
+    memset(&a, 0, sizeof a);
+    a.base = set->base.get(); a.basis = set->basis->planes.get();
+    a.tris = set->tris.get(); a.corner_begin = set->corner_begin.get(); a.corners = set->corners.get();
+    a.models = set->table.get(); a.state = set->state.get(); a.rec = rec;
+    a.n = set->n; a.nk = set->basis->k;
+    a.first = first; a.count = count;
+    a.max_coeff = set->max_coeff;
+    return a;
+}
+static int fit_subjects_create_(const float *verts, uint32_t n, const uint32_t *tris, uint32_t n_tris, const dh_fit_basis *basis, uint32_t n_subjects,
+                                double max_coeff, int device, dh_fit_subjects **out) {
+    const char *who = "dh_fit_subjects_create";
+    if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
+    *out = nullptr;
+    if (!verts || !tris || !basis) return fail(DH_EINVAL, "%s: NULL argument", who);
+    if (n == 0 || n > DH_FIT_MAX_POINTS) return fail(DH_EINVAL, "%s: %u points, expected 1 .. %u", who, n, DH_FIT_MAX_POINTS);
+    if (n_tris == 0 || n_tris > DH_SUBJECTS_MAX_TRIS) return fail(DH_EINVAL, "%s: %u triangles, expected 1 .. %u", who, n_tris, DH_SUBJECTS_MAX_TRIS);
+    if (n_subjects < 1 || n_subjects > DH_SHAPE_MAX_SUBJECTS)
+        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u", who, n_subjects, DH_SHAPE_MAX_SUBJECTS);
+    if (!(max_coeff > 0.0) || !std::isfinite(max_coeff)) return fail(DH_EINVAL, "%s: max_coeff %g, expected a finite value > 0", who, max_coeff);
+    if (device < 0) return fail(DH_EINVAL, "%s: device %d", who, device);
+    double r2 = 0.0;
+    for (uint32_t i = 0; i < n; ++i) {
+        double v2 = 0.0;
+        for (int c = 0; c < 3; ++c) {
+            const float v = verts[(size_t)i * 3 + c];
+            if (!std::isfinite(v)) return fail(DH_EINVAL, "%s: vertex %u is not finite", who, i);
+            v2 += (double)v * (double)v;
+        }
+        r2 = std::max(r2, v2);
+    }
+    std::vector<uint32_t> begin((size_t)n + 1), corners((size_t)n_tris * 3);
+    uint32_t bad = 0;
+    if (!dh_subjects_corner_lists(tris, n_tris, n, begin.data(), corners.data(), &bad))
+        return fail(DH_EINVAL, "%s: triangle %u names a vertex that is not below %u", who, bad, n);
+    const uint32_t flat = dh_subjects_first_zero_normal(verts, tris, begin.data(), corners.data(), n);
+    if (flat < n) return fail(DH_EINVAL, "%s: vertex %u of the base mesh has a zero normal", who, flat);
+    if (basis->n != n) return fail(DH_EINVAL, "%s: the basis is one of %u points, the mesh has %u", who, basis->n, n);
+    if (basis->device != device) return fail(DH_EINVAL, "%s: the basis lives on device %d, the set on %d", who, basis->device, device);
+
+    std::unique_ptr<dh_fit_subjects> set(new dh_fit_subjects);
+    set->device = device; set->n = n; set->n_tris = n_tris; set->n_subjects = n_subjects;
+    set->max_coeff = max_coeff; set->basis = basis;
+    set->radius = dh_subjects_radius_bound(sqrt(r2), basis->k, max_coeff, basis->largest);
+    DeviceGuard guard(device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(set->base.alloc((size_t)n * 3));
+    TRY(set->tris.alloc((size_t)n_tris * 3));
+    TRY(set->corner_begin.alloc(begin.size()));
+    TRY(set->corners.alloc(corners.size()));
+    TRY(set->state.alloc(n_subjects));
+    TRY(set->table.alloc(n_subjects));
+    TRY(set->rec.alloc(n_subjects));
+    std::vector<SubjectModel> table(n_subjects);
+    for (uint32_t sj = 0; sj < n_subjects; ++sj) {
+        std::unique_ptr<dh_fit_model> m(new dh_fit_model);
+        m->device = device; m->n = n; m->radius = set->radius;
+        TRY(m->pts.alloc((size_t)n * 3));
+        TRY(m->nrm.alloc((size_t)n * 3));
+        table[sj] = SubjectModel{m->pts.get(), m->nrm.get()};
+        set->models.push_back(std::move(m));
+    }
+    TRY(hip_step(hipStreamCreateWithFlags(&set->s, hipStreamNonBlocking), "hipStreamCreate"));
+    HIP_TRY(hipMemcpy(set->base.get(), verts, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(set->tris.get(), tris, (size_t)n_tris * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(set->corner_begin.get(), begin.data(), begin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(set->corners.get(), corners.data(), corners.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(set->table.get(), table.data(), table.size() * sizeof(SubjectModel), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(set->state.get(), 0, (size_t)n_subjects * sizeof(dh_subject_state)));
+    // every model evaluated at its zero coefficients
+    TRY(hip_step(dh_launch_subjects_update(subjects_args(set.get(), nullptr, 0, n_subjects), set->s), "k_subjects"));
+    HIP_TRY(hipStreamSynchronize(set->s));
+    *out = set.release();
+    return DH_OK;
+}
+static int fit_subjects_destroy_(dh_fit_subjects *s) {
+    if (!s) return DH_OK;
+    DeviceGuard guard(s->device);
+    delete s;
+    return DH_OK;
+}
+static int fit_subjects_info_(const dh_fit_subjects *s, uint32_t *n, uint32_t *n_tris, uint32_t *n_fields, uint32_t *n_subjects, double *radius, int *device) {
+    if (!s) return fail(DH_EINVAL, "dh_fit_subjects_info: NULL subject set");
+    if (n) *n = s->n;
+    if (n_tris) *n_tris = s->n_tris;
+    if (n_fields) *n_fields = s->basis->k;
+    if (n_subjects) *n_subjects = s->n_subjects;
+    if (radius) *radius = s->radius;
+    if (device) *device = s->device;
+    return DH_OK;
+}
+static int fit_subjects_model_(const dh_fit_subjects *s, uint32_t subject, const dh_fit_model **model) {
+    if (!s || !model) return fail(DH_EINVAL, "dh_fit_subjects_model: NULL argument");
+    if (subject >= s->n_subjects) return fail(DH_EINVAL, "dh_fit_subjects_model: subject %u of %u", subject, s->n_subjects);
+    *model = s->models[subject].get();
+    return DH_OK;
+}
+static int fit_subjects_set_coeffs_(dh_fit_subjects *s, uint32_t first, uint32_t count, const double *coeffs) {
+    const char *who = "dh_fit_subjects_set_coeffs";
+    if (!s) return fail(DH_EINVAL, "%s: NULL subject set", who);
+    if (!coeffs) return fail(DH_EINVAL, "%s: NULL coefficients", who);
+    if ((uint64_t)first + count > s->n_subjects) return fail(DH_EINVAL, "%s: subjects %u .. %llu of %u", who, first, (unsigned long long)first + count, s->n_subjects);
+    const uint32_t nk = s->basis->k;
+    for (uint32_t i = 0; i < count; ++i)
+        for (uint32_t k = 0; k < nk; ++k) {
+            const double c = coeffs[(size_t)i * 8 + k];
+            if (!(fabs(c) <= s->max_coeff)) return fail(DH_EINVAL, "%s: coefficient %u of subject %u is %g, outside +-%g", who, k, first + i, c, s->max_coeff);
+        }
+    if (count == 0) return DH_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return DH_EHIP;
+    std::vector<dh_subject_state> st(count);
+    HIP_TRY(hipMemcpyAsync(st.data(), s->state.get() + first, (size_t)count * sizeof(dh_subject_state), hipMemcpyDeviceToHost, s->s));
+    HIP_TRY(hipStreamSynchronize(s->s));
+    for (uint32_t i = 0; i < count; ++i) {
+        for (uint32_t k = 0; k < 8; ++k) st[i].coeffs[k] = k < nk ? coeffs[(size_t)i * 8 + k] : 0.0;
+        st[i].flags = 0;
+    }
+    HIP_TRY(hipMemcpyAsync(s->state.get() + first, st.data(), (size_t)count * sizeof(dh_subject_state), hipMemcpyHostToDevice, s->s));
+    TRY(hip_step(dh_launch_subjects_update(subjects_args(s, nullptr, first, count), s->s), "k_subjects"));
+    HIP_TRY(hipStreamSynchronize(s->s));
+    return DH_OK;
+}
+static int fit_subjects_state_(dh_fit_subjects *s, dh_subject_state *state) {
+    if (!s) return fail(DH_EINVAL, "dh_fit_subjects_state: NULL subject set");
+    if (!state) return fail(DH_EINVAL, "dh_fit_subjects_state: NULL state");
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return DH_EHIP;
+    HIP_TRY(hipMemcpyAsync(state, s->state.get(), (size_t)s->n_subjects * sizeof(dh_subject_state), hipMemcpyDeviceToHost, s->s));
+    HIP_TRY(hipStreamSynchronize(s->s));
+    return DH_OK;
+}
+static int fit_subjects_read_(dh_fit_subjects *s, uint32_t subject, float *points, float *normals) {
+    if (!s) return fail(DH_EINVAL, "dh_fit_subjects_read: NULL subject set");
+    if (subject >= s->n_subjects) return fail(DH_EINVAL, "dh_fit_subjects_read: subject %u of %u", subject, s->n_subjects);
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return DH_EHIP;
+    const dh_fit_model *m = s->models[subject].get();
+    const size_t bytes = (size_t)s->n * 3 * sizeof(float);
+    if (points) HIP_TRY(hipMemcpyAsync(points, m->pts.get(), bytes, hipMemcpyDeviceToHost, s->s));
+    if (normals) HIP_TRY(hipMemcpyAsync(normals, m->nrm.get(), bytes, hipMemcpyDeviceToHost, s->s));
+    HIP_TRY(hipStreamSynchronize(s->s));
+    return DH_OK;
+}
+static int fit_subjects_update_(dh_fit_subjects *s, const dh_shape_record *records) {
+    if (!s) return fail(DH_EINVAL, "dh_fit_subjects_update: NULL subject set");
+    if (!records) return fail(DH_EINVAL, "dh_fit_subjects_update: NULL records");
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return DH_EHIP;
+    HIP_TRY(hipMemcpyAsync(s->rec.get(), records, (size_t)s->n_subjects * sizeof(dh_shape_record), hipMemcpyHostToDevice, s->s));
+    TRY(hip_step(dh_launch_subjects_update(subjects_args(s, s->rec.get(), 0, s->n_subjects), s->s), "k_subjects"));
+    HIP_TRY(hipStreamSynchronize(s->s));
+    return DH_OK;
+}
+static int fit_subjects_update_device_(dh_fit_subjects *s, const dh_shape_record *records, void *stream) {
+    if (!s) return fail(DH_EINVAL, "dh_fit_subjects_update_device: NULL subject set");
+    if (!records) return fail(DH_EINVAL, "dh_fit_subjects_update_device: NULL records");
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return DH_EHIP;
+    return hip_step(dh_launch_subjects_update(subjects_args(s, records, 0, s->n_subjects), (hipStream_t)stream), "k_subjects");
+}
+
 // The refusals every shape call (single-view or multi-view) begins with, around those of its frames: the pointers, then the
 // subject count, the params (NULL: the defaults; *out is what the call runs with), the model and the basis, the instances.
 static int shape_check_pointers(const dh_fitter *f, const void *frames, const void *rec, const dh_fit_model *m, const dh_fit_basis *b, const char *who) {
@@ -3237,15 +3439,25 @@ struct ShapeReq {
     const uint32_t *subjects; uint32_t n_subjects;
     const dh_shape_params *prm;
     dh_shape_record *rec;
+    // the step over a subject set: `set` in place of model and basis, and the instances' fit records
+    bool use_set = false;
+    const dh_fit_subjects *set = nullptr;
+    const dh_fit_record *fit_rec = nullptr;
 };
 static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stream, const char *who) {
     // ---- refusals: all of them before anything is allocated or launched
-    TRY(shape_check_pointers(f, q.frames, q.rec, q.model, q.basis, who));
+    if (q.use_set && f && q.frames && q.rec && !q.set) return fail(DH_EINVAL, "%s: NULL subject set", who);
+    // (a set's models all have the set's bound for their radius: the first stands for them in the checks)
+    const dh_fit_model *m = q.use_set ? (q.set ? q.set->models[0].get() : nullptr) : q.model;
+    const dh_fit_basis *b = q.use_set ? (q.set ? q.set->basis : nullptr) : q.basis;
+    TRY(shape_check_pointers(f, q.frames, q.rec, m, b, who));
     TRY(check_frames(q.n, q.w, q.h, q.K, q.cams, q.use_cams, f->device, "fitter", who));
+    if (q.use_set && q.set->device != f->device)
+        return fail(DH_EINVAL, "%s: the subject set lives on device %d, the fitter on %d", who, q.set->device, f->device);
+    if (q.use_set && q.n_subjects > q.set->n_subjects)
+        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u, the set's", who, q.n_subjects, q.set->n_subjects);
     dh_shape_params prm;
-    TRY(shape_check_call(f, q.model, q.basis, q.n_subjects, q.prm, &prm, q.inst, q.n_inst, who));
-    const dh_fit_model *m = q.model;
-    const dh_fit_basis *b = q.basis;
+    TRY(shape_check_call(f, m, b, q.n_subjects, q.prm, &prm, q.inst, q.n_inst, who));
     if (dev) {
         if ((uint64_t)q.n_inst * m->n > DH_SHAPE_MAX_TERMS)
             return fail(DH_EINVAL, "%s: %u instances of %u points exceed %u terms", who, q.n_inst, m->n, DH_SHAPE_MAX_TERMS);
@@ -3254,6 +3466,7 @@ static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stre
         for (uint32_t i = 0; i < q.n_inst; ++i) {
             const uint32_t sj = q.subjects ? q.subjects[i] : 0u;
             if (sj == DH_SHAPE_SKIP) continue;
+            if (q.fit_rec && q.fit_rec[i].status != DH_FIT_OK) continue;
             if (sj >= q.n_subjects) return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, q.n_subjects);
             const dh_render_instance &in = q.inst[i];
             if (in.frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, q.n);
@@ -3280,15 +3493,25 @@ static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stre
         TRY(f->frames.grow(n_px));
         if (f->shape_inst.cap() < q.n_inst || !f->shape_inst) { TRY(f->shape_inst.grow(std::max<size_t>(q.n_inst, 1))); TRY(f->shape_subj.alloc(f->shape_inst.cap())); }
         if (!f->shape_rec) TRY(f->shape_rec.alloc(DH_SHAPE_MAX_SUBJECTS));
+        if (q.fit_rec && f->shape_fit_rec.cap() < f->shape_inst.cap()) {
+            HIP_TRY(hipDeviceSynchronize());
+            TRY(f->shape_fit_rec.alloc(f->shape_inst.cap()));
+        }
         HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
         if (q.n_inst) HIP_TRY(hipMemcpyAsync(f->shape_inst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_render_instance), hipMemcpyHostToDevice, s));
         if (q.n_inst && q.subjects) HIP_TRY(hipMemcpyAsync(f->shape_subj.get(), q.subjects, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         a.frames = f->frames.get(); a.inst = f->shape_inst.get(); a.subjects = q.subjects ? f->shape_subj.get() : nullptr;
         a.rec = f->shape_rec.get();
     } else { a.frames = q.frames; a.inst = q.inst; a.subjects = q.subjects; a.rec = q.rec; }
+    const dh_fit_record *fit_rec = q.fit_rec;
+    if (!dev && q.fit_rec && q.n_inst) {
+        HIP_TRY(hipMemcpyAsync(f->shape_fit_rec.get(), q.fit_rec, (size_t)q.n_inst * sizeof(dh_fit_record), hipMemcpyHostToDevice, s));
+        fit_rec = f->shape_fit_rec.get();
+    }
     // ---- the three stream-ordered operations
     TRY(hip_step(dh_launch_shape_clear(a, s), "k_shape_clear"));
-    TRY(hip_step(dh_launch_shape_accumulate(a, s), "k_shape_accumulate"));
+    if (q.use_set) TRY(hip_step(dh_launch_shape_accumulate_subjects(ShapeSubjectsArgs{a, q.set->table.get(), fit_rec}, s), "k_shape_accumulate_subjects"));
+    else TRY(hip_step(dh_launch_shape_accumulate(a, s), "k_shape_accumulate"));
     TRY(hip_step(dh_launch_shape_solve(a, s), "k_shape_solve"));
     if (!dev) {
         HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)q.n_subjects * sizeof(dh_shape_record), hipMemcpyDeviceToHost, s));
@@ -3315,6 +3538,37 @@ static int fit_shape_cameras_device_(dh_fitter *f, const uint16_t *frames, int n
                                      const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params,
                                      dh_shape_record *records, void *stream) {
     return shape_run(f, ShapeReq{frames, n, w, h, nullptr, c, true, model, basis, instances, n_instances, subjects, n_subjects, params, records}, true, (hipStream_t)stream, "dh_fit_shape_cameras_device");
+}
+
+// The same step over a subject set.
+static ShapeReq shape_subjects_req(const uint16_t *frames, int n, int w, int h, const float *K, const dh_cameras *c, bool use_cams, const dh_fit_subjects *set,
+                                   const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                                   const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records) {
+    return ShapeReq{frames, n, w, h, K, c, use_cams, nullptr, nullptr, instances, n_instances, subjects, n_subjects, params, records, true, set, fit_records};
+}
+static int fit_shape_subjects_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set,
+                               const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                               const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records) {
+    return shape_run(f, shape_subjects_req(frames, n, w, h, K, nullptr, false, set, instances, n_instances, subjects, n_subjects, fit_records, params, records),
+                     false, nullptr, "dh_fit_shape_subjects");
+}
+static int fit_shape_subjects_cameras_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_subjects *set,
+                                       const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                                       const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records) {
+    return shape_run(f, shape_subjects_req(frames, n, w, h, nullptr, c, true, set, instances, n_instances, subjects, n_subjects, fit_records, params, records),
+                     false, nullptr, "dh_fit_shape_subjects_cameras");
+}
+static int fit_shape_subjects_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set,
+                                      const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                                      const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records, void *stream) {
+    return shape_run(f, shape_subjects_req(frames, n, w, h, K, nullptr, false, set, instances, n_instances, subjects, n_subjects, fit_records, params, records),
+                     true, (hipStream_t)stream, "dh_fit_shape_subjects_device");
+}
+static int fit_shape_subjects_cameras_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_subjects *set,
+                                              const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                                              const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records, void *stream) {
+    return shape_run(f, shape_subjects_req(frames, n, w, h, nullptr, c, true, set, instances, n_instances, subjects, n_subjects, fit_records, params, records),
+                     true, (hipStream_t)stream, "dh_fit_shape_subjects_cameras_device");
 }
 
 // ------------------------------------------------------------------ adapting a model's shape across views
@@ -4125,6 +4379,21 @@ DH_API(fit_shape_views, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, 
 DH_API(fit_shape_views_device, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model, const dh_fit_basis *basis, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n_sets, w, h, views, model, basis, instances, n_instances, sets, subjects, n_subjects, params, records, stream))
 DH_API(calib_params_default, (dh_calib_params *p), (p))
 DH_API(fit_calibrate_views, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *take, const uint8_t *hold, const dh_calib_params *params, dh_calib_record *records), (f, frames, n_sets, w, h, views, model, instances, n_instances, sets, take, hold, params, records))
+DH_API(fit_depth_carried_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_render_instance *carried, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream), (f, frames, n, w, h, K, models, n_models, instances, n_instances, carried, params, out, records, stream))
+DH_API(fit_depth_cameras_carried_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances, uint32_t n_instances, const dh_render_instance *carried, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records, void *stream), (f, frames, n, w, h, c, models, n_models, instances, n_instances, carried, params, out, records, stream))
+DH_API(fit_subjects_create, (const float *verts, uint32_t n, const uint32_t *tris, uint32_t n_tris, const dh_fit_basis *basis, uint32_t n_subjects, double max_coeff, int device, dh_fit_subjects **out), (verts, n, tris, n_tris, basis, n_subjects, max_coeff, device, out))
+DH_API(fit_subjects_destroy, (dh_fit_subjects *s), (s))
+DH_API(fit_subjects_info, (const dh_fit_subjects *s, uint32_t *n, uint32_t *n_tris, uint32_t *n_fields, uint32_t *n_subjects, double *radius, int *device), (s, n, n_tris, n_fields, n_subjects, radius, device))
+DH_API(fit_subjects_model, (const dh_fit_subjects *s, uint32_t subject, const dh_fit_model **model), (s, subject, model))
+DH_API(fit_subjects_set_coeffs, (dh_fit_subjects *s, uint32_t first, uint32_t count, const double *coeffs), (s, first, count, coeffs))
+DH_API(fit_subjects_state, (dh_fit_subjects *s, dh_subject_state *state), (s, state))
+DH_API(fit_subjects_read, (dh_fit_subjects *s, uint32_t subject, float *points, float *normals), (s, subject, points, normals))
+DH_API(fit_subjects_update, (dh_fit_subjects *s, const dh_shape_record *records), (s, records))
+DH_API(fit_subjects_update_device, (dh_fit_subjects *s, const dh_shape_record *records, void *stream), (s, records, stream))
+DH_API(fit_shape_subjects, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records), (f, frames, n, w, h, K, set, instances, n_instances, subjects, n_subjects, fit_records, params, records))
+DH_API(fit_shape_subjects_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records), (f, frames, n, w, h, c, set, instances, n_instances, subjects, n_subjects, fit_records, params, records))
+DH_API(fit_shape_subjects_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n, w, h, K, set, instances, n_instances, subjects, n_subjects, fit_records, params, records, stream))
+DH_API(fit_shape_subjects_cameras_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n, w, h, c, set, instances, n_instances, subjects, n_subjects, fit_records, params, records, stream))
 DH_API(fit_calibrate_views_device, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *take, const uint8_t *hold, const dh_calib_params *params, dh_calib_record *records, void *stream), (f, frames, n_sets, w, h, views, model, instances, n_instances, sets, take, hold, params, records, stream))
 DH_API(fit_track_params_default, (dh_fit_track_params *p), (p))
 DH_API(fit_tracker_angles, (double out[DH_FIT_TRACK_ANGLES][2]), (out))

@@ -1,9 +1,9 @@
 // dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip,
-// k_fit_shape_views.hip, k_calib_views.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
+// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
 // words of both trackers, and the one test of whether an instance may be fitted (dh_fit_instance_fault: the host's refusals and
 // the shape kernel's skips).  The device arithmetic the kernels share among themselves is in dh_fit_device.h.  Not part of the
 // ABI.  The rules are stated in include/depthhead_hip.h (sections "fitting posed models to depth frames" and after) and
-// DESIGN.md sections 18 - 24.
+// DESIGN.md sections 18 - 25.
 #pragma once
 #include "dh_internal.h"
 #include "dh_rig_fit.h"
@@ -402,3 +402,92 @@ struct RigFitArgs {
 };
 hipError_t dh_launch_rig_fit_seed(const RigFitArgs &a, hipStream_t s);
 hipError_t dh_launch_rig_fit_update(const RigFitArgs &a, hipStream_t s);
+
+// ---- a shape per subject (k_subjects.hip)
+static_assert(sizeof(dh_subject_state) == 80, "dh_subject_state: 80 bytes");
+// Magnitudes.  A model of a set is v'_i = fl32(v_i + sum_k c_k B_k[i]) with |c_k| <= max_coeff (the clamp of the update and the
+// refusal of dh_fit_subjects_set_coeffs: no other path writes a coefficient), so |v'_i| <= |v_i| + K max_coeff max |B_k[i]| <= the
+// set's bound radius(base) + K * max_coeff * largest, up to the roundings: the K f64 products and sums (K * 2^-52 relative) and
+// the one rounding to f32 (2^-24 relative per component).  Together below 1.2e-7 relative, which the fit's constant absorbs:
+// section 21 derives |R x| <= 1.0296 |x| and the argument is made with 1.03, a margin of 3.9e-4.  The extent test of
+// dh_fit_instance_fault with the BOUND for the radius therefore gives |scale| |v'| <= 4096 (1 + 1.2e-7) for every coefficient the
+// device can reach, and sections 18 - 24 hold for a model of a set as they stand.
+// The normals.  The points are f32 widened, so a difference of two is 0 or at least 2^-149 in magnitude, a product of two
+// differences 0 or at least 2^-298 (and at most 2^258), and a face product and any sum of them 0 or a multiple of 2^-350: a
+// component of the summed normal is exactly 0.0 or at least 2^-350, and at most 3 * 131072 * 2^259 < 2^278.  q = (n0 n0 + n1 n1)
+// + n2 n2 is then exactly 0.0 or in [2^-700, 2^558]: never subnormal, never infinite, its relative error below 2^-51.  With a
+// correctly rounded square root |n / ln| <= 1 + 2^-50 before the rounding to f32: a normal of a set has |nrm| <= 1 + 1e-7 <= 1.01,
+// which is what dh_fit_model_create demands of a caller's, or it is (0, 0, 0): such a point has c = 0.0, fails `c < 0.0` and
+// never reaches a sum.
+
+// The set's bound on |v'| (f64, computed once at creation): radius(base) + (K * max_coeff) * largest.
+inline double dh_subjects_radius_bound(double base_radius, uint32_t n_fields, double max_coeff, double largest) {
+    return base_radius + ((double)n_fields * max_coeff) * largest;
+}
+// Each vertex's incident corners in ascending (triangle, corner) order: begin [n + 1] and corners [3 n_tris], corner t * 3 + c
+// being corner c of triangle t.  A counting sort, so a vertex's run is ascending by construction.  false: an index >= n, and
+// *bad_tri names the first triangle that holds one.
+inline bool dh_subjects_corner_lists(const uint32_t *tris, uint32_t n_tris, uint32_t n, uint32_t *begin, uint32_t *corners, uint32_t *bad_tri) {
+    for (uint32_t i = 0; i <= n; ++i) begin[i] = 0;
+    for (uint32_t t = 0; t < n_tris; ++t)
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t v = tris[(size_t)t * 3 + c];
+            if (v >= n) { if (bad_tri) *bad_tri = t; return false; }
+            ++begin[v + 1];
+        }
+    for (uint32_t i = 0; i < n; ++i) begin[i + 1] += begin[i];
+    for (uint32_t q = 0; q < 3 * n_tris; ++q) corners[begin[tris[q]]++] = q;     // ascending q: each run fills from its front,
+    for (uint32_t i = n; i > 0; --i) begin[i] = begin[i - 1];                    // which leaves begin[v] at the run's end:
+    begin[0] = 0;                                                                // the next vertex's beginning
+    return true;
+}
+// The first vertex of the mesh pts [n][3] whose summed normal has length 0 (k_subjects_normals' arithmetic on the host: the gather
+// over the corner list, q, one square root), or n where there is none.  What dh_fit_subjects_create refuses a base mesh by.
+inline uint32_t dh_subjects_first_zero_normal(const float *pts, const uint32_t *tris, const uint32_t *begin, const uint32_t *corners, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        double s[3] = {0.0, 0.0, 0.0};
+        for (uint32_t j = begin[i]; j < begin[i + 1]; ++j) {
+            const uint32_t *tri = tris + (size_t)(corners[j] / 3u) * 3;
+            const float *pa = pts + (size_t)tri[0] * 3, *pb = pts + (size_t)tri[1] * 3, *pc = pts + (size_t)tri[2] * 3;
+            double u[3], w[3];
+            for (int c = 0; c < 3; ++c) { u[c] = (double)pb[c] - (double)pa[c]; w[c] = (double)pc[c] - (double)pa[c]; }
+            s[0] = s[0] + (u[1] * w[2] - u[2] * w[1]);
+            s[1] = s[1] + (u[2] * w[0] - u[0] * w[2]);
+            s[2] = s[2] + (u[0] * w[1] - u[1] * w[0]);
+        }
+        const double q = (s[0] * s[0] + s[1] * s[1]) + s[2] * s[2];
+        if (!(__builtin_sqrt(q) > 0.0)) return i;
+    }
+    return n;
+}
+
+// One model of a set as the update kernels write it.
+struct SubjectModel {
+    float *pts;                   // [n][3]
+    float *nrm;                   // [n][3]
+};
+struct SubjectsArgs {
+    const float *base;            // [n][3] the base mesh
+    const float *basis;           // [nk][3][n]
+    const uint32_t *tris;         // [n_tris][3]
+    const uint32_t *corner_begin; // [n + 1]
+    const uint32_t *corners;      // [3 n_tris]
+    const SubjectModel *models;   // [S]
+    dh_subject_state *state;      // [S]
+    const dh_shape_record *rec;   // nullable [S]: NULL evaluates the coefficients as they are
+    uint32_t n, nk;
+    uint32_t first, count;        // the subjects that are applied and evaluated
+    double max_coeff;
+};
+hipError_t dh_launch_subjects_update(const SubjectsArgs &a, hipStream_t s);       // k_subjects_apply, _points, _normals
+
+// k_shape_accumulate_subjects: section 20's accumulation with the model of each instance's subject.
+struct ShapeSubjectsArgs {
+    ShapeArgs s;                  // pts and nrm unused; radius: the set's bound
+    const SubjectModel *models;   // [S] (n_subjects <= S)
+    const dh_fit_record *fit_rec; // nullable [n_inst]: an instance whose fit did not end DH_FIT_OK takes no part
+};
+hipError_t dh_launch_shape_accumulate_subjects(const ShapeSubjectsArgs &a, hipStream_t s);
+// k_fit_carry: the R and t of a fit call's uploaded instances replaced by those of `carried` (device, [n_inst]) where they are
+// finite and within DH_FIT_R_TOLERANCE of a rotation.
+hipError_t dh_launch_fit_carry(dh_render_instance *inst, const dh_render_instance *carried, uint32_t n_inst, hipStream_t s);

@@ -1,6 +1,6 @@
 // dh_fit_device.h -- the device arithmetic that the fit family's kernels must agree on bit for bit, each piece stated once:
 //   the per-point correspondence and the damped solve     k_fit.hip, k_fit_views.hip, k_fit_shape.hip, k_fit_shape_views.hip
-//   the shape step's point loop and reduction              k_fit_shape.hip, k_fit_shape_views.hip
+//   the shape step's point loop and reduction              k_fit_shape.hip, k_fit_shape_views.hip, k_subjects.hip
 //   the pose, the modes of a pass, the step's helpers      k_fit.hip, k_fit_views.hip (each with its *_sched instance)
 //   the trackers' rule: table rotation, carried start,
 //   acceptance, jump test and the state updates            k_fit_track.hip, k_rig_fit_track.hip
@@ -91,7 +91,14 @@ __device__ __forceinline__ double uni(double v) {
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-// ---- the shape step's accumulation (k_fit_shape.hip and k_fit_shape_views.hip; DESIGN.md sections 20 and 23)
+// ---- the shape step's accumulation (k_fit_shape.hip, k_fit_shape_views.hip and k_subjects.hip; DESIGN.md sections 20, 23 and 25)
+// Whether instance `in` of a single-view step (k_shape_accumulate, k_shape_accumulate_subjects) takes part: the header's per-instance refusals, decided on the device (a NaN fails each test).
+__device__ __forceinline__ bool shape_takes_part(const ShapeArgs &a, const dh_render_instance *in, uint32_t subject) {
+    if (subject >= a.n_subjects) return false;                       // DH_SHAPE_SKIP among them
+    if (in->frame >= (uint32_t)a.n) return false;
+    return dh_fit_instance_fault(*in, a.radius, a.largest).why == DH_FIT_INST_OK;
+}
+
 // What one workgroup of DH_SHAPE_THREADS lanes adds to the row of `subject`: the tail of both accumulate kernels, a macro as
 // DH_FIT_CORRESPOND is, so that both compile from the very tokens.  a: the ShapeArgs; NK: the fields, a compile-time constant;
 // frame, K[9], R[9], t[3], scale: the depth frame and the camera pose the points are posed by (doubles, uniform over the

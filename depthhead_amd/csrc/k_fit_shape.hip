@@ -17,13 +17,6 @@
 
 #pragma clang fp contract(off)
 
-// Whether instance `in` takes part: the header's per-instance refusals, decided on the device (a NaN fails each test).
-__device__ __forceinline__ bool shape_takes_part(const ShapeArgs &a, const dh_render_instance *in, uint32_t subject) {
-    if (subject >= a.n_subjects) return false;                       // DH_SHAPE_SKIP among them
-    if (in->frame >= (uint32_t)a.n) return false;
-    return dh_fit_instance_fault(*in, a.radius, a.largest).why == DH_FIT_INST_OK;
-}
-
 template <int NK>
 __global__ __launch_bounds__(DH_SHAPE_THREADS) void k_shape_accumulate(const ShapeArgs a) {
     __shared__ long long s_part[DH_SHAPE_THREADS / 64][DH_SHAPE_STRIDE];

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from ._lib import (CALIB_RECORD_DTYPE, CALIB_SKIP, FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, FIT_VIEW_TOLERANCE, HEAD_DTYPE,
                    MAX_HEADS, POSE_DTYPE, RIG_FIT_RECORD_DTYPE, RIG_FIT_STATE_DTYPE, RIG_MAX_PERSONS, RIG_MAX_TRACKS, RIG_PERSON_DTYPE,
-                   RIG_TRACK_DTYPE, RENDER_INSTANCE_DTYPE, SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUPPORT_DTYPE, SUPPORT_RADIUS, VIEW_FIT_RECORD_DTYPE,
+                   RIG_TRACK_DTYPE, RENDER_INSTANCE_DTYPE, SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUBJECT_STATE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, VIEW_FIT_RECORD_DTYPE,
                    VIEW_INSTANCE_DTYPE, check, vp)
 from .render import euler_to_matrix
 
@@ -21,6 +21,7 @@ FIT_TRACK_BAD_STATUS, FIT_TRACK_BAD_POINTS, FIT_TRACK_BAD_RMS, FIT_TRACK_BAD_JUM
 FIT_TRACK_MOTION = 1                                # DH_FIT_TRACK_MOTION
 SHAPE_OK, SHAPE_FEW_POINTS, SHAPE_SINGULAR = 0, 1, 2  # dh_shape_record.status
 CALIB_OK, CALIB_FEW_POINTS, CALIB_SINGULAR, CALIB_NOT_ORTHONORMAL, CALIB_HELD = 0, 1, 2, 3, 4  # dh_calib_record.status
+SUBJECT_CLAMPED, SUBJECT_NONFINITE = 1, 2            # dh_subject_state.flags
 
 
 def vertex_normals(verts, tris) -> np.ndarray:
@@ -258,12 +259,14 @@ class Fitter(_lib._Handle):
         self._h = C.c_void_p()
         check(self._lib.dh_fitter_create(self.device, C.byref(self._h)))
 
-    def fit(self, frames, models, instances, K_or_cameras, params=None, device_out: bool = False, stream=None):
+    def fit(self, frames, models, instances, K_or_cameras, params=None, device_out: bool = False, stream=None, carried=None):
         """Refine `instances` (a RENDER_INSTANCE_DTYPE array of rough poses) of `models` against `frames`: [n, h, w] u16 as a
         numpy array, or a torch tensor on the device with device_out=True.  Through one K ([3, 3] or an `IntrinsicMatrix`) or a
         `tracking.Cameras` table of exactly n cameras.  Returns (instances, records) -- RENDER_INSTANCE_DTYPE and
         FIT_RECORD_DTYPE arrays, or with device_out=True two uint8 torch tensors on the device holding them, ordered on `stream`
-        (default the current torch stream)."""
+        (default the current torch stream).  `carried` (device_out=True only): the uint8 tensor an earlier fit(device_out=True)
+        returned for the same instances, whose R and t the fit starts from in place of those of `instances` (DESIGN.md section
+        25)."""
         inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
         models = list(models)
         handles = (C.c_void_p * max(len(models), 1))(*[m._h.value for m in models])
@@ -289,6 +292,13 @@ class Fitter(_lib._Handle):
         out = torch.empty(max(ni, 1) * RENDER_INSTANCE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         rec = torch.empty(max(ni, 1) * FIT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        if carried is not None:
+            if carried.numel() * carried.element_size() != ni * RENDER_INSTANCE_DTYPE.itemsize or not carried.is_contiguous() or carried.device != dev:
+                raise ValueError("carried: the contiguous device tensor of an earlier fit of as many instances is expected")
+            check(getattr(self._lib, "dh_fit_depth" + kind + "_carried_device")(
+                self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, handles, C.c_uint32(len(models)), vp(inst) if ni else None, C.c_uint32(ni),
+                C.c_void_p(carried.data_ptr()) if ni else None, prm, C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
+            return out[:ni * RENDER_INSTANCE_DTYPE.itemsize], rec[:ni * FIT_RECORD_DTYPE.itemsize]
         check(getattr(self._lib, "dh_fit_depth" + kind + "_device")(self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, handles,
                                                                       C.c_uint32(len(models)), vp(inst) if ni else None, C.c_uint32(ni), prm,
                                                                       C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
@@ -364,6 +374,49 @@ class Fitter(_lib._Handle):
                                                                       C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
                                                                       C.c_void_p(subjects.data_ptr()) if subjects is not None else None,
                                                                       C.c_uint32(ns), prm, C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
+        return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
+
+    def shape_step_subjects(self, frames, subjects_set, instances, K_or_cameras, subjects=None, n_subjects=None, fit_records=None, params=None,
+                            device_out: bool = False, stream=None):
+        """`shape_step` over a `Subjects` set: instance i is taken at the model of subject subjects[i] (None:
+        subject 0), and where `fit_records` (FIT_RECORD_DTYPE [n_instances], what `fit` returned with the instances) is given,
+        an instance whose fit did not end FIT_OK takes no part.  n_subjects defaults to the set's.  Host form: numpy arrays ->
+        SHAPE_RECORD_DTYPE [n_subjects].  With device_out=True frames, instances, subjects and fit_records are torch tensors on
+        the device (instances and fit_records as the uint8 tensors Fitter.fit(device_out=True) returned, subjects int32 or None)
+        and the records come back as a uint8 torch tensor, ordered on `stream` without a host wait."""
+        n, h, w = (int(v) for v in frames.shape)
+        cams = getattr(K_or_cameras, "_h", None)
+        if cams is None:
+            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
+            kind, karg = "", vp(K)
+        else:
+            kind, karg = "_cameras", cams
+        prm = C.byref(params) if params is not None else None
+        ns = len(subjects_set) if n_subjects is None else int(n_subjects)
+        if not device_out:
+            fr = np.ascontiguousarray(frames, dtype=np.uint16)
+            inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
+            subj = None if subjects is None else np.ascontiguousarray(subjects, dtype=np.uint32).reshape(len(inst))
+            frec = None if fit_records is None else np.ascontiguousarray(fit_records, dtype=FIT_RECORD_DTYPE).reshape(len(inst))
+            rec = np.zeros(max(ns, 0), SHAPE_RECORD_DTYPE)
+            check(getattr(self._lib, "dh_fit_shape_subjects" + kind)(self._h, vp(fr), n, w, h, karg, subjects_set._h, vp(inst) if len(inst) else None,
+                                                                      C.c_uint32(len(inst)), vp(subj), C.c_uint32(ns), vp(frec), prm, vp(rec)))
+            return rec
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
+            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
+        ni = instances.numel() * instances.element_size() // RENDER_INSTANCE_DTYPE.itemsize
+        if subjects is not None and (subjects.numel() != ni or subjects.element_size() != 4 or not subjects.is_contiguous()):
+            raise ValueError("device subjects: a contiguous 32-bit tensor with one word per instance is expected")
+        if fit_records is not None and (fit_records.numel() * fit_records.element_size() != ni * FIT_RECORD_DTYPE.itemsize or not fit_records.is_contiguous()):
+            raise ValueError("device fit_records: the contiguous tensor of one dh_fit_record per instance is expected")
+        rec = torch.empty(max(ns, 1) * SHAPE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        check(getattr(self._lib, "dh_fit_shape_subjects" + kind + "_device")(
+            self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, subjects_set._h, C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
+            C.c_void_p(subjects.data_ptr()) if subjects is not None else None, C.c_uint32(ns),
+            C.c_void_p(fit_records.data_ptr()) if fit_records is not None else None, prm, C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
         return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
 
     def shape_step_views(self, frames, views, model, basis, instances, sets=None, subjects=None, n_subjects: int = 1, params=None,
@@ -476,6 +529,118 @@ def adapt(fitter, frames, K_or_cameras, verts, tris, basis, starts, rounds: int 
             trace.append({"coeffs": c.copy(), "fit": rec, "shape": srec, "delta": delta})
             c = c + delta
     return c, inst, trace
+
+class _SetModel:
+    """One model of a `Subjects` set: what Fitter's calls and the trackers read of a `Model` (its handle), borrowed -- the set owns it."""
+
+    def __init__(self, lib, handle, device):
+        self._lib, self._h, self.device = lib, handle, device
+
+    def info(self):
+        """(n, radius): the radius is the set's bound on every model it can hold."""
+        n, radius = C.c_uint32(), C.c_double()
+        check(self._lib.dh_fit_model_info(self._h, C.byref(n), C.byref(radius)))
+        return n.value, radius.value
+
+
+class Subjects(_lib._Handle):
+    """One dh_fit_subjects: `n_subjects` deformable models of the mesh (verts [n, 3], tris [m, 3]) on
+    `device`, each with its own coefficients of `basis` (a `ShapeBasis` of n points, which must outlive the set), every
+    coefficient kept within +-max_coeff.  `models[s]` is subject s's model for any call that takes a `Model`; its contents
+    follow the subject's coefficients with every `update`."""
+    _handles = (("_h", "dh_fit_subjects_destroy"),)
+
+    def __init__(self, verts, tris, basis, n_subjects: int, max_coeff: float = 0.5, device: int = 0):
+        self._lib = _lib.load()
+        self.verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        self.tris = np.ascontiguousarray(tris, dtype=np.uint32).reshape(-1, 3)
+        self.basis, self.device, self.n_subjects, self.max_coeff = basis, int(device), int(n_subjects), float(max_coeff)
+        self._h = C.c_void_p()
+        check(self._lib.dh_fit_subjects_create(vp(self.verts), C.c_uint32(len(self.verts)), vp(self.tris), C.c_uint32(len(self.tris)), basis._h,
+                                               C.c_uint32(self.n_subjects), C.c_double(self.max_coeff), self.device, C.byref(self._h)))
+        self.models = []
+        for s in range(self.n_subjects):
+            h = C.c_void_p()
+            check(self._lib.dh_fit_subjects_model(self._h, C.c_uint32(s), C.byref(h)))
+            self.models.append(_SetModel(self._lib, h, self.device))
+
+    def __len__(self):
+        return self.n_subjects
+
+    def close(self):
+        self.models = []
+        super().close()
+
+    def info(self):
+        """(n, n_tris, K, S, the radius bound, device) as the library holds them."""
+        n, nt, k, s, radius, device = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_double(), C.c_int()
+        check(self._lib.dh_fit_subjects_info(self._h, C.byref(n), C.byref(nt), C.byref(k), C.byref(s), C.byref(radius), C.byref(device)))
+        return n.value, nt.value, k.value, s.value, radius.value, device.value
+
+    def state(self) -> np.ndarray:
+        """Synchronous copy of the subjects' states: SUBJECT_STATE_DTYPE [S]."""
+        st = np.zeros(self.n_subjects, SUBJECT_STATE_DTYPE)
+        check(self._lib.dh_fit_subjects_state(self._h, vp(st)))
+        return st
+
+    def read(self, subject: int):
+        """Synchronous copy of subject `subject`'s model as it stands: (points [n, 3] f32, normals [n, 3] f32)."""
+        pts, nrm = np.zeros_like(self.verts), np.zeros_like(self.verts)
+        check(self._lib.dh_fit_subjects_read(self._h, C.c_uint32(int(subject)), vp(pts), vp(nrm)))
+        return pts, nrm
+
+    def set_coeffs(self, coeffs, first: int = 0) -> None:
+        """Set the coefficients of subjects first .. first + len(coeffs) - 1 (coeffs [count, K] or [count, 8]) and evaluate their
+        models; synchronous."""
+        c = np.asarray(coeffs, dtype=np.float64)
+        c = c.reshape(-1, c.shape[-1])
+        full = np.zeros((len(c), 8), np.float64)
+        full[:, :c.shape[1]] = c
+        check(self._lib.dh_fit_subjects_set_coeffs(self._h, C.c_uint32(int(first)), C.c_uint32(len(full)), vp(full)))
+
+    def update(self, records, device: bool = False, stream=None) -> None:
+        """Apply one shape record per subject (SHAPE_RECORD_DTYPE [S], what shape_step_subjects returned) and evaluate every
+        model.  Host form: a numpy array, synchronous.  device=True: the uint8 torch tensor of shape_step_subjects(device_out=True),
+        three kernels on `stream` (default the current torch stream), no host wait."""
+        if not device:
+            rec = np.ascontiguousarray(records, dtype=SHAPE_RECORD_DTYPE).reshape(self.n_subjects)
+            check(self._lib.dh_fit_subjects_update(self._h, vp(rec)))
+            return
+        import torch
+        if records.numel() * records.element_size() != self.n_subjects * SHAPE_RECORD_DTYPE.itemsize or not records.is_contiguous():
+            raise ValueError("device records: the contiguous tensor of one dh_shape_record per subject is expected")
+        s = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream if stream is None else int(stream)
+        check(self._lib.dh_fit_subjects_update_device(self._h, C.c_void_p(records.data_ptr()), C.c_void_p(s)))
+
+
+def adapt_subjects(fitter, frames, K_or_cameras, subjects, starts, subject_of, rounds: int = 6, fit_prm=None, shape_prm=None):
+    """`adapt` for all the subjects of a `Subjects` set at once, on the device.  frames [n, h, w] u16
+    (numpy) go to the device once; `starts` are RENDER_INSTANCE_DTYPE [m] rough poses and subject_of [m] names each one's
+    subject.  Every round is one fit of all instances -- instance i against models[subject_of[i]], from `starts` in the first
+    round and from the previous round's fitted poses after it (`carried`) -- one shape step over the set with the fit's records
+    as the filter, and one update of the set, all enqueued on the current torch stream: the host reads nothing inside the loop
+    and once at the end.  The set's coefficients are adapted in place, from where they stand.  Returns (state
+    SUBJECT_STATE_DTYPE [S], the last fitted instances, the FIT_RECORD_DTYPE and SHAPE_RECORD_DTYPE records of the last round)."""
+    import torch
+    dev = torch.device("cuda", fitter.device)
+    inst = np.array(starts, dtype=RENDER_INSTANCE_DTYPE)
+    who = np.ascontiguousarray(subject_of, dtype=np.uint32).reshape(len(inst))
+    inst["mesh"] = who
+    host = np.ascontiguousarray(frames, dtype=np.uint16)
+    d_frames = torch.from_numpy((host if host.flags.writeable else host.copy()).view(np.int16)).to(dev)
+    d_who = torch.from_numpy(who.view(np.int32)).to(dev)
+    d_inst = d_frec = d_srec = None
+    for _ in range(int(rounds)):
+        d_inst, d_frec = fitter.fit(d_frames, subjects.models, inst, K_or_cameras, params=fit_prm, device_out=True, carried=d_inst)
+        d_srec = fitter.shape_step_subjects(d_frames, subjects, d_inst, K_or_cameras, subjects=d_who, fit_records=d_frec, params=shape_prm,
+                                            device_out=True)
+        subjects.update(d_srec, device=True)
+    torch.cuda.current_stream(dev).synchronize()
+    if d_inst is None:
+        return subjects.state(), inst, (np.zeros(len(inst), FIT_RECORD_DTYPE), np.zeros(len(subjects), SHAPE_RECORD_DTYPE))
+    out = d_inst.cpu().numpy().view(RENDER_INSTANCE_DTYPE).copy()
+    return subjects.state(), out, (d_frec.cpu().numpy().view(FIT_RECORD_DTYPE).copy(), d_srec.cpu().numpy().view(SHAPE_RECORD_DTYPE).copy())
+
 
 def adapt_views(fitter, frames, views, verts, tris, basis, starts, sets=None, rounds: int = 6, fit_prm=None, shape_prm=None, coeffs=None):
     """`adapt` over the views of a rig: frames [n_sets, n, h, w] u16 (numpy), `views` a `Views` of n

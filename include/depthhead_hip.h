@@ -1247,6 +1247,123 @@ int dh_rig_fit_tracker_step_device(dh_predictor *p, dh_rig_fit_tracker *t, dh_ri
                                    uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks,
                                    dh_rig_fit_record *records, void *stream);
 
+/* ---- a shape per subject ----
+ * The shape steps of sections 20 and 23 solve for an increment of the coefficients at the one model they are given; deforming the
+ * model was the caller's step on the host.  A dh_fit_subjects keeps S deformable models of one base mesh ON THE DEVICE, one per
+ * subject, evaluates each subject's coefficients into its model there, and the shape step over a set reads every instance at its
+ * own subject's model: many subjects adapt at once and a whole alternation (fit, shape step, update) is stream-ordered with no
+ * host wait.  Not in the reference: PARITY UNPINNED, the definition below is this library's.  Arithmetic: f64 with + - * /, ONE
+ * square root (correctly rounded, as IEEE 754 demands), compares and casts; every operation rounded on its own.
+ * THE SET owns the base vertices v[n] (f32 triples), the triangles, each vertex's list of incident corners in ascending (triangle,
+ *   corner) order (built once on the host), one dh_subject_state per subject and S models.  The basis (section 20) is borrowed and
+ *   must outlive the set; K is its field count.  Every subject starts with all coefficients 0 and its model evaluated at them.
+ * THE MODELS: dh_fit_subjects_model hands out subject s's model as an ordinary dh_fit_model that every call taking one accepts
+ *   unchanged (dh_fit_depth*, dh_fit_depth_views*, the trackers, dh_fit_shape*, dh_fit_calibrate_views*).  It is owned by the set
+ *   (never pass it to dh_fit_model_destroy), valid until the set is destroyed, and its contents change, stream-ordered, with each
+ *   update: a call that reads it must be stream-ordered with the updates around it.  Its radius (dh_fit_model_info) is the SET'S
+ *   BOUND, computed once in f64:  bound = radius(base) + (K * max_coeff) * (the basis's largest |B_k[i]|),
+ *   radius(base) being the largest |v| as dh_fit_model_create computes it.  No coefficient the device can reach leaves
+ *   [-max_coeff, max_coeff], so |v'| <= bound for every model the set ever holds, and the existing per-instance refusal
+ *   |scale| * radius > DH_FIT_MAX_EXTENT keeps the magnitude arguments of sections 18 - 24 closed without the host knowing the
+ *   coefficients.
+ * THE UPDATE of subject s by its record r = records[s] (a dh_shape_record, what a shape step wrote):
+ *   APPLY.  r.status != DH_SHAPE_OK: nothing is applied.  Else, if a delta[k], k < K, is not finite: rejected += 1, flags |=
+ *     DH_SUBJECT_NONFINITE and nothing else changes.  Else for every k < K:  c_k = c_k + delta[k], then c_k > max_coeff becomes
+ *     max_coeff and c_k < -max_coeff becomes -max_coeff, flags |= DH_SUBJECT_CLAMPED where either moved it; applied += 1.  The
+ *     counters saturate at 2^32 - 1; the flags stay set until dh_fit_subjects_set_coeffs.
+ *   POINTS, always from the BASE, never from the previous model, so nothing drifts:  x = (f64)v_i;  for k ascending
+ *     x[j] = x[j] + c_k * (f64)B_k[i][j];  v'_i = (f32)x, rounded once (what fit.deform computes).
+ *   NORMALS, from the f32 v' widened again (what fit.vertex_normals computes).  Per triangle (a, b, c):  u = v'_b - v'_a,
+ *     w = v'_c - v'_a,  f = (u1 * w2 - u2 * w1,  u2 * w0 - u0 * w2,  u0 * w1 - u1 * w0).  Per vertex: m = +0.0, then m = m + f for
+ *     every incident corner in (triangle, corner) order -- a triangle that names the vertex twice adds its f twice.  Then
+ *     q = (m0 * m0 + m1 * m1) + m2 * m2,  ln = sqrt(q),  nrm = (f32)(m / (ln > 0 ? ln : 1)).  A vertex with ln = 0 keeps a zero
+ *     normal: the fit never associates it (c < 0.0 fails), so nothing leaves the magnitude bound; zero_normals counts such
+ *     vertices at the last evaluation.  Floating-point sums depend on their order, so the sum is a gather over the corner list in
+ *     list order: no floating-point atomic anywhere.
+ *   Every update evaluates ALL subjects, applied or not.
+ * THE SHAPE STEP OVER A SET is ONE SHAPE STEP of section 20 with two changes: instance i is evaluated at the model of its subject
+ *   subjects[i] (NULL: subject 0), and where fit_records is given, instance i takes no part unless fit_records[i].status is
+ *   DH_FIT_OK (as if its subject were DH_SHAPE_SKIP) -- so the outputs of dh_fit_depth*_device chain straight in.  Sums, solve and
+ *   records are section 20's, n_subjects <= S records; the per-instance refusals are section 20's with the set's bound for the
+ *   model's radius, and so is the term limit.
+ * CARRIED STARTS.  The instances of dh_fit_depth*_device are host memory, so a fit could not start from what an earlier fit left on
+ *   the device.  dh_fit_depth_carried_device and its camera twin are dh_fit_depth_device and dh_fit_depth_cameras_device with one
+ *   more argument, carried[n_instances] ON THE DEVICE (what an earlier dh_fit_depth*_device wrote to its `out`; it may be that very
+ *   buffer of this call): after the upload of the call's tables one more kernel, k_fit_carry, gives instance i the R and t of
+ *   carried[i] where all twelve are finite and R R^T is within DH_FIT_R_TOLERANCE of the identity (the tests of section 18, so its
+ *   magnitude bound holds for whatever the buffer contains), and leaves the uploaded R and t elsewhere.  frame, mesh, scale and
+ *   flags are always the host instance's, and every refusal of dh_fit_depth_device is made on the host instances as they are
+ *   given.  DH_EINVAL in addition: carried NULL with n_instances > 0.
+ * dh_fit_subjects_create -- DH_EINVAL before anything is allocated or launched, *out NULL, in this order: NULL out; NULL verts, tris or
+ *   basis; n = 0 or above DH_FIT_MAX_POINTS; n_tris outside 1 .. DH_SUBJECTS_MAX_TRIS; n_subjects outside 1 ..
+ *   DH_SHAPE_MAX_SUBJECTS; max_coeff not > 0 or not finite; device < 0; a vertex that is not finite; a triangle index >= n; a base
+ *   mesh one of whose vertex normals is zero (as dh_fit_model_create refuses a zero normal); a basis of another n; a basis on
+ *   another device.
+ * dh_fit_subjects_set_coeffs (host, synchronous) sets the coefficients of subjects first .. first + count - 1 from coeffs[count][8]
+ *   (f64; those of k >= K are ignored and kept 0), clears their flags, keeps their counters and evaluates those subjects.
+ *   DH_EINVAL, nothing changed: NULL set or coeffs; first + count above S; a coefficient k < K that is not finite or whose magnitude
+ *   exceeds max_coeff.
+ * dh_fit_subjects_update (host records[S], synchronous) and dh_fit_subjects_update_device (device records[S]; exactly three kernels
+ *   on `stream`, NULL = default stream -- k_subjects_apply, k_subjects_points, k_subjects_normals -- no host wait, no allocation) run
+ *   THE UPDATE.  DH_EINVAL: NULL set or records.  dh_fit_subjects_state (host, synchronous; DH_EINVAL: NULL set or state) copies the S states out and
+ *   dh_fit_subjects_read (host, synchronous; DH_EINVAL: NULL set, subject >= S) one subject's points and normals.  The host calls
+ *   run on a stream of the set's own and wait for it alone: the caller orders them against device calls that use the models.
+ * dh_fit_shape_subjects* -- DH_EINVAL as dh_fit_shape* and in its order, with a NULL subject set in place of the NULL model and basis,
+ *   then, after the frames' refusals, a set that lives on another device than the fitter, and n_subjects outside 1 .. S.  The host forms skip an instance whose fit record is not DH_FIT_OK before any
+ *   per-instance refusal.  The _device forms enqueue exactly three kernels on `stream`: k_shape_clear,
+ *   k_shape_accumulate_subjects, k_shape_solve.  Bit-identical run to run and to tests/subjects_ref.py. */
+#define DH_SUBJECTS_MAX_TRIS 131072u   /* triangles of a set's mesh */
+#define DH_SUBJECT_CLAMPED 1u          /* dh_subject_state.flags: a coefficient was moved back to +-max_coeff */
+#define DH_SUBJECT_NONFINITE 2u        /*   an increment that was not finite was rejected */
+typedef struct dh_subject_state {
+    double   coeffs[8];           /* offset 0:  c_k; 0 for k >= K */
+    uint32_t applied;             /* offset 64: increments added */
+    uint32_t rejected;            /* offset 68: increments rejected as not finite */
+    uint32_t flags;               /* offset 72: DH_SUBJECT_* */
+    uint32_t zero_normals;        /* offset 76: vertices whose normal was zero at the last evaluation */
+} dh_subject_state;    /* 80 bytes, no padding */
+typedef struct dh_fit_subjects dh_fit_subjects;
+/* verts [n][3] f32 (mm), tris [n_tris][3] u32, basis of n points */
+int dh_fit_subjects_create(const float *verts, uint32_t n, const uint32_t *tris, uint32_t n_tris, const dh_fit_basis *basis,
+                           uint32_t n_subjects, double max_coeff, int device, dh_fit_subjects **out);
+int dh_fit_subjects_destroy(dh_fit_subjects *s);
+/* each pointer nullable; radius = the set's bound */
+int dh_fit_subjects_info(const dh_fit_subjects *s, uint32_t *n, uint32_t *n_tris, uint32_t *n_fields, uint32_t *n_subjects,
+                         double *radius, int *device);
+/* *model: subject `subject`'s model, borrowed from the set.  DH_EINVAL: NULL set or model, subject >= S. */
+int dh_fit_subjects_model(const dh_fit_subjects *s, uint32_t subject, const dh_fit_model **model);
+int dh_fit_subjects_set_coeffs(dh_fit_subjects *s, uint32_t first, uint32_t count, const double *coeffs);
+int dh_fit_subjects_state(dh_fit_subjects *s, dh_subject_state *state);
+/* subject `subject`'s model as it stands: points [n][3] and normals [n][3] f32, each nullable */
+int dh_fit_subjects_read(dh_fit_subjects *s, uint32_t subject, float *points, float *normals);
+int dh_fit_subjects_update(dh_fit_subjects *s, const dh_shape_record *records);
+int dh_fit_subjects_update_device(dh_fit_subjects *s, const dh_shape_record *records, void *stream);
+/* as dh_fit_depth_device / dh_fit_depth_cameras_device; carried [n_instances] on the device */
+int dh_fit_depth_carried_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9],
+                                const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances,
+                                uint32_t n_instances, const dh_render_instance *carried, const dh_fit_params *params,
+                                dh_render_instance *out, dh_fit_record *records, void *stream);
+int dh_fit_depth_cameras_carried_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                        const dh_fit_model *const *models, uint32_t n_models, const dh_render_instance *instances,
+                                        uint32_t n_instances, const dh_render_instance *carried, const dh_fit_params *params,
+                                        dh_render_instance *out, dh_fit_record *records, void *stream);
+/* frames [n][h][w] u16; instances [n_instances]; subjects [n_instances] or NULL; fit_records [n_instances] or NULL; records [n_subjects] */
+int dh_fit_shape_subjects(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set,
+                          const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                          const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records);
+int dh_fit_shape_subjects_cameras(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                  const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances,
+                                  const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records,
+                                  const dh_shape_params *params, dh_shape_record *records);
+int dh_fit_shape_subjects_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set,
+                                 const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects,
+                                 uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params,
+                                 dh_shape_record *records, void *stream);
+int dh_fit_shape_subjects_cameras_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                         const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances,
+                                         const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records,
+                                         const dh_shape_params *params, dh_shape_record *records, void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
