@@ -153,8 +153,12 @@ struct Workspace {
     Buf<uint32_t> box;                 // [cap][box_rows][m][box_plane] rectangle-sum images (uniform path)
     Buf<unsigned long long> box_mask;  // [cap][ceil(box_rows / 32)][box_parts] which lanes wrote non-zero sums last time (BoxArgs::blk_mask)
     int blk_shift = 5;                 // log2 height of k_boxsum's mask blocks in this workspace (BoxArgs::blk_shift)
-    Buf<uint32_t> tile_list;           // [DH_MAX_CHUNKS][8][ceil(cap / 8) * tiles] + [DH_MAX_CHUNKS][8] counts behind it (k_tile_list)
+    Buf<uint32_t> tile_list;           // [DH_MAX_CHUNKS] x ([8][ceil(cap / 8) * tiles] uint2 entries + [8] counts behind them) (k_tile_list, k_tile_shift)
     size_t tile_list_stride = 0;       // entries per x
+    TileShifts shifts;                 // the shifts of the tile grid a frame of this workspace chooses from (dh_tile_shifts_)
+    Buf<uint32_t> tile_shift;          // [cap] sx | sy << 16 chosen for each frame of the last batch (k_tile_shift; zero otherwise)
+    int list_chunks = 0;               // kernel sequences of the last batch that ran with tile lists (debug_tile_shifts_)
+    uint32_t *list_ptr(int chunk) const { return tile_list.get() + (size_t)chunk * 8 * (2 * tile_list_stride + 1); }
     Buf<uint32_t> win_patch;           // [cap][win_cap] window list: position in the window grid
     Buf<uint8_t> win_leaf;             // [cap][T][win_cap] window list: leaf per tree (u16 entries for forests of <= 65 535 leaves, else i32)
     int leaf_ls = 2;                   // log2 of its entry size
@@ -527,7 +531,13 @@ static int reserve(dh_predictor *p, int n, int w, int h) {
     TRY(ws.win_leaf.alloc(((size_t)cap * std::max(g.win_cap, 1) * p->n_trees) << ws.leaf_ls));
     if (!p->knobs.no_tile_list && g.npatch > 0) {
         ws.tile_list_stride = (size_t)((cap + 7) / 8) * g.tiles_x * g.tiles_y;
-        if (ws.tile_list_stride < ((size_t)1 << 31)) TRY(ws.tile_list.alloc((size_t)DH_MAX_CHUNKS * 8 * (ws.tile_list_stride + 1)));
+        if (ws.tile_list_stride < ((size_t)1 << 30)) TRY(ws.tile_list.alloc((size_t)DH_MAX_CHUNKS * 8 * (2 * ws.tile_list_stride + 1)));
+    }
+    TRY(dh_tile_shifts_(g, (int)p->params.stepwidth, ws.blk_shift, p->knobs, &ws.shifts));
+    if (!ws.tile_list) ws.shifts.on = false;
+    if (ws.shifts.on) {
+        TRY(ws.tile_shift.alloc(cap));
+        if (hipMemsetAsync(ws.tile_shift.get(), 0, (size_t)cap * sizeof(uint32_t), p->own_stream) != hipSuccess) return fail(DH_EHIP, "hipMemset(tile_shift)");
     }
     if (g.uniform) {
         const size_t words = (size_t)cap * g.box_rows * ((size_t)g.box_plane << g.swz_log2);
@@ -683,6 +693,14 @@ static int enqueue_range(dh_predictor *p, const BatchReq &sl, int f0, int n, hip
     uint32_t *box = g.uniform ? ws.box.get() + (size_t)f0 * g.box_rows * ((size_t)g.box_plane << g.swz_log2) : nullptr;
     // tile flags: one byte per tile, frames packed back to back (the slice always starts at the frame the memset covered)
     uint8_t *tile_flags = ws.tile_flags(f0);
+    // product mode: the flagged tiles as compact lists, so that the workgroups of empty tiles sit at the end of k_traverse's grid
+    // (with the taps on, every tile position keeps its workgroup: those of empty tiles write the taps' "background")
+    // (the list moves the empty tiles' workgroups behind the flagged ones; a batch whose tiles all fit the chip's 512 workgroup
+    // slots at once gains nothing from that and saves the dispatch: 3 us of a single frame's 96)
+    const bool use_list = ws.tile_list && g.npatch > 0 && !o.leaf_out && !o.flags_out && !p->debug && (long)n * g.tiles_x * g.tiles_y > 512;
+    if (use_list) p->ws.list_chunks = std::max(p->ws.list_chunks, o.chunk + 1);
+    uint2 *tl_list = use_list ? (uint2 *)ws.list_ptr(o.chunk) : nullptr;
+    uint32_t *tl_count = use_list ? ws.list_ptr(o.chunk) + 16 * ws.tile_list_stride : nullptr;
     if (g.npatch > 0 && g.uniform) {
         BoxArgs ba{};
         ba.frames = fr; ba.zeros = p->zeros.get(); ba.n_frames = n; ba.w = w; ba.h = h; ba.rw = p->f_rw; ba.rh = p->f_rh;
@@ -717,6 +735,7 @@ static int enqueue_range(dh_predictor *p, const BatchReq &sl, int f0, int n, hip
         ba.blk_shift = ws.blk_shift;
         ba.mask_blocks = (g.box_rows + (1 << ws.blk_shift) - 1) >> ws.blk_shift;
         ba.blk_mask = ws.box_mask ? ws.box_mask.get() + (size_t)f0 * ba.mask_blocks * g.box_parts : nullptr;
+        if (use_list && ws.shifts.on) ba.list_count = tl_count;     // k_tile_shift appends to the lists
         ba.blocks_per_frame = (ba.parts * ba.bands + 3) / 4;
         { Range r(o.profile, "dh:boxsum"); HIP_TRY(dh_launch_boxsum(ba, s)); }
     }
@@ -729,13 +748,21 @@ static int enqueue_range(dh_predictor *p, const BatchReq &sl, int f0, int n, hip
         fa.tfh = (g.py - 1) * (int)p->params.stepwidth + (int)p->params.subimage_height;
         { Range r(o.profile, "dh:pixflags"); HIP_TRY(dh_launch_pixflags(fa, s)); }
     }
-    // product mode: the flagged tiles as compact lists, so that the workgroups of empty tiles sit at the end of k_traverse's grid
-    // (with the taps on, every tile position keeps its workgroup: those of empty tiles write the taps' "background")
-    // (the list moves the empty tiles' workgroups behind the flagged ones; a batch whose tiles all fit the chip's 512 workgroup
-    // slots at once gains nothing from that and saves the dispatch: 3 us of a single frame's 96)
-    const bool use_list = ws.tile_list && g.npatch > 0 && !o.leaf_out && !o.flags_out && !p->debug && (long)n * g.tiles_x * g.tiles_y > 512;
-    uint32_t *tl_list = use_list ? ws.tile_list.get() + (size_t)o.chunk * 8 * (ws.tile_list_stride + 1) : nullptr;
-    uint32_t *tl_count = use_list ? tl_list + 8 * ws.tile_list_stride : nullptr;
+    // (a workspace whose frames choose the shift of their tile grid: k_tile_shift counts the flagged tiles of every allowed shift on
+    // k_boxsum's masks and writes the lists of the best one; k_boxsum's flags then serve the other paths only)
+    if (use_list && ws.shifts.on) {
+        TileShiftArgs sa{};
+        sa.n_frames = n; sa.blk_shift = ws.blk_shift; sa.mask_blocks = (g.box_rows + (1 << ws.blk_shift) - 1) >> ws.blk_shift; sa.parts = g.box_parts;
+        sa.blk_mask = ws.box_mask.get() + (size_t)f0 * sa.mask_blocks * g.box_parts;
+        sa.ow4 = g.box_ow / 4; sa.nc = g.box_parts * sa.ow4;
+        sa.tiles_x = g.tiles_x; sa.tiles_y = g.tiles_y; sa.step = (int)p->params.stepwidth;
+        sa.tpx = g.px * sa.step; sa.tpy = g.py * sa.step;
+        sa.tbw = (g.px - 1) * sa.step + (int)p->params.subimage_width - p->f_rw + 1;
+        sa.tbh = (g.py - 1) * sa.step + (int)p->params.subimage_height - p->f_rh + 1;
+        sa.sx0 = ws.shifts.sx0; sa.sy0 = ws.shifts.sy0; sa.gx = ws.shifts.gx; sa.nsx = ws.shifts.nsx; sa.nsy = ws.shifts.nsy;
+        sa.list = tl_list; sa.count = tl_count; sa.stride = (uint32_t)ws.tile_list_stride; sa.shift_out = ws.tile_shift.get() + f0;
+        Range r(o.profile, "dh:tile_list"); HIP_TRY(dh_launch_tile_shift(sa, s));
+    } else
     if (use_list) { Range r(o.profile, "dh:tile_list"); HIP_TRY(dh_launch_tile_list(tile_flags, gen, n, g.tiles_x * g.tiles_y, tl_list, tl_count, (uint32_t)ws.tile_list_stride, s)); }
     if (o.profile) HIP_TRY(hipEventRecord(p->ev[4], s));
     if (g.npatch > 0) {
@@ -1020,6 +1047,7 @@ static int batch_device(dh_predictor *p, const BatchReq &r, hipStream_t s) {
         BatchReq sl = r.at(f0);
         sl.n = std::min(slice, n - f0);
         const int m = sl.n;
+        p->ws.list_chunks = 0;
         // Forked sub-batches: two halves of the slice on two streams let the latency-bound tail kernels of one half run
         // beside the head kernels of the other.  Measured on MI355X: it pays once each half still has >= 256 frames
         // (512 frames per call: 479 k -> 533 k frames/s with 2 chunks, 483 k with 4; 256 frames per call: no gain),
@@ -1998,6 +2026,7 @@ static int aux_run(dh_predictor *p, unsigned req, const uint16_t *frames, int n,
         if (req & AUX_POSES) HIP_TRY(dh_launch_argmax2d(hough, frames, n, w, h, kinv, poses2d, s));
     }
     p->last_n = 0;   // the pose taps do not refer to this run
+    p->ws.list_chunks = 0;
     return DH_OK;
 }
 
@@ -2143,6 +2172,27 @@ static int debug_geometry_(dh_predictor *p, int32_t out[10]) {
     const int32_t v[10] = {(g.uniform ? 1 : 0) | (walk_tab ? 1 << 8 : 0) | (walk_tab ? g.top_levels << 16 : 0), g.px, g.py, g.tiles_x, g.tiles_y, g.swz_log2, g.swz_q, g.ss_row, p->f_rw, p->f_rh};
     memcpy(out, v, sizeof v);
     return DH_OK;
+}
+// Like the other taps this describes the last resident slice of the last batch (batch_device starts every slice with list_chunks = 0;
+// a replayed graph rewrites the lists of the batch it captured; the mask / 2-D Hough calls run without lists and clear last_n).
+// The tile lists of that slice: shifts[f] = {sx, sy} of frame f's tile grid in windows (zeros where no frame chooses: TileShifts),
+// counts[x] = flagged tiles in the list of the frames = x mod 8 (summed over forked sub-batches, each of which counts from its own first frame).
+static int debug_tile_shifts_(dh_predictor *p, int32_t *shifts, uint32_t counts[8]) {
+    return with_taps(p, false, [&]() -> int {
+        const Workspace &ws = p->ws;
+        if (!shifts || !counts) return fail(DH_EINVAL, "NULL output");
+        if (ws.list_chunks == 0) return fail(DH_ESTATE, "the last batch ran without tile lists");
+        std::vector<uint32_t> sh((size_t)p->last_n, 0u);
+        if (ws.tile_shift) HIP_TRY(hipMemcpy(sh.data(), ws.tile_shift.get(), sh.size() * 4, hipMemcpyDeviceToHost));
+        for (int f = 0; f < p->last_n; ++f) { shifts[2 * f] = (int32_t)(sh[f] & 0xffffu); shifts[2 * f + 1] = (int32_t)(sh[f] >> 16); }
+        for (int x = 0; x < 8; ++x) counts[x] = 0;
+        for (int c = 0; c < ws.list_chunks; ++c) {
+            uint32_t cc[8];
+            HIP_TRY(hipMemcpy(cc, ws.list_ptr(c) + 16 * ws.tile_list_stride, sizeof cc, hipMemcpyDeviceToHost));
+            for (int x = 0; x < 8; ++x) counts[x] += cc[x];
+        }
+        return DH_OK;
+    });
 }
 static int debug_guesses_(dh_predictor *p, int32_t *out) {
     return with_taps(p, true, [&]() -> int {
@@ -4295,6 +4345,7 @@ DH_API(debug_patch_flags, (dh_predictor *p, uint8_t *out, size_t cap), (p, out, 
 DH_API(debug_grids, (dh_predictor *p, uint32_t *pos_grid, uint32_t *rot_grid), (p, pos_grid, rot_grid))
 DH_API(debug_hit_counts, (dh_predictor *p, uint32_t *out), (p, out))
 DH_API(debug_geometry, (dh_predictor *p, int32_t out[10]), (p, out))
+DH_API(debug_tile_shifts, (dh_predictor *p, int32_t *shifts, uint32_t counts[8]), (p, shifts, counts))
 DH_API(debug_guesses, (dh_predictor *p, int32_t *out), (p, out))
 DH_API(debug_meanshift, (dh_predictor *p, int which, int32_t *trace, uint32_t *steps), (p, which, trace, steps))
 DH_API(debug_votes, (dh_predictor *p, int frame, int which, int32_t *out, size_t cap, size_t *count), (p, frame, which, out, cap, count))

@@ -200,6 +200,12 @@ Knobs dh_read_knobs_() {
     k.vote_exact = getenv("DH_VOTE_EXACT") != nullptr;
     k.no_tile_list = getenv("DH_NO_TILE_LIST") != nullptr;
     k.no_zero_fold = getenv("DH_NO_ZERO_FOLD") != nullptr;
+    if (const char *e = getenv("DH_TILE_SHIFT")) {
+        char tail = 0;
+        if (strcmp(e, "off") == 0) k.tile_shift_mode = 1;
+        else if (sscanf(e, "%d,%d%c", &k.tile_shift_x, &k.tile_shift_y, &tail) == 2 && k.tile_shift_x >= 0 && k.tile_shift_y >= 0) k.tile_shift_mode = 2;
+        else k.tile_shift_mode = 3;
+    }
     if (const char *e = getenv("DH_TOP_LEVELS")) k.top_levels = std::max(0, std::min(8, atoi(e)));
     k.stage_chunk = std::max(1, geti("DH_STAGE_CHUNK", 64));
     k.host_threads = std::max(1, std::min(64, geti("DH_HOST_THREADS", (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())))));
@@ -356,6 +362,32 @@ int dh_choose_tile_(const TileQuery &p, Geom &g) {
         g.box_oh = ((g.box_rows + g.box_bands - 1) / g.box_bands + 31) & ~31;     // whole 32-row blocks per band (BoxArgs::blk_mask)
         g.box_bands = (g.box_rows + g.box_oh - 1) / g.box_oh;
     }
+    return DH_OK;
+}
+
+int dh_tile_shifts_(const Geom &g, int step, int blk_shift, const Knobs &k, TileShifts *out) {
+    TileShifts t;
+    if (k.tile_shift_mode == 3) return dh_fail_(DH_EINVAL, "DH_TILE_SHIFT: expected \"off\" or \"sx,sy\" (windows, >= 0)");
+    *out = t;
+    if (k.tile_shift_mode == 1 || !g.uniform || g.npatch <= 0 || k.box_dense || k.no_tile_list || step <= 0) return DH_OK;
+    const int slack_x = g.tiles_x * g.px - g.nx, slack_y = g.tiles_y * g.py - g.ny;
+    // a shift of s windows moves a tile's first region column by s * step / m words of its plane: whole 16-byte pieces
+    const int m4 = 4 << g.swz_log2;
+    int a = step, b = m4;
+    while (b) { const int r = a % b; a = b; b = r; }
+    t.gx = m4 / a;
+    if (k.tile_shift_mode == 2) {
+        t.sx0 = std::min(k.tile_shift_x, slack_x) / t.gx * t.gx; t.sy0 = std::min(k.tile_shift_y, slack_y);
+    } else {
+        t.nsx = slack_x / t.gx + 1; t.nsy = slack_y + 1;
+        if (t.nsx * t.nsy == 1) return DH_OK;
+    }
+    const int mask_blocks = (g.box_rows + (1 << blk_shift) - 1) >> blk_shift;
+    const bool fits = dh_tile_shift_lds_words(mask_blocks, g.box_parts, g.box_parts * (g.box_ow / 4), t.nsx * t.nsy) <= DH_TILE_SHIFT_LDS_WORDS;
+    if (!fits && k.tile_shift_mode == 2)
+        return dh_fail_(DH_EINVAL, "DH_TILE_SHIFT=%d,%d: frames of %dx%d are too large for the shifted tile lists", k.tile_shift_x, k.tile_shift_y, g.w, g.h);
+    t.on = fits;
+    *out = t;
     return DH_OK;
 }
 

@@ -93,6 +93,8 @@ struct Knobs {
     int top_levels = -1;              // DH_TOP_LEVELS: tree levels walked from the LDS copy of the tree tops (-1 = auto, 0 = none)
     bool no_zero_fold = false;        // DH_NO_ZERO_FOLD: the per-batch counters get a fill dispatch of their own instead of being cleared by k_boxsum
     bool no_tile_list = false;        // DH_NO_TILE_LIST: k_traverse launches a workgroup per tile position, empty ones included
+    int tile_shift_mode = 0;          // DH_TILE_SHIFT: 0 = every frame chooses its tile grid's shift (k_tile_shift), 1 = "off", 2 = "sx,sy" forced for
+    int tile_shift_x = 0, tile_shift_y = 0;   // every frame (clamped to the allowed shifts), 3 = anything else (refused when a workspace is sized)
     bool vote_exact = false;          // DH_VOTE_EXACT: k_vote takes the two IEEE divisions for every vote
     bool no_absorb = false;           // DH_NO_ABSORB: uniform path walks the guarded node table
     bool no_general_int = false;      // DH_NO_GENERAL_INT: general path with the f64 divisions on every visit
@@ -136,6 +138,22 @@ struct TileQuery {
 // Tile of PX x PY window positions per workgroup for g.{w, h, nx, ny, uniform}: fills the rest of g.  Returns DH_OK,
 // a negative DH_E* (message set), or 1 = "no tile fits the uniform layout: retry on the general path".
 int dh_choose_tile_(const TileQuery &q, Geom &g);
+// The shifts of the tile grid a frame may choose from (k_tile_shift): sx = sx0 + gx * i for i < nsx, sy = sy0 + j for j < nsy, in
+// windows.  They stay within the grid's slack (tiles_x * px - nx, tiles_y * py - ny), so the tile count and every buffer stay as
+// they are, and sx moves in the steps gx that keep a tile's first region column where the unshifted grid has it modulo 16 bytes of
+// its plane (k_traverse's direct-to-LDS copy; the tile chooser picks px % 4 == 0 for the same reason).  `on` is false -- the fixed
+// grid and k_boxsum's flags -- off the uniform path, without the sparse-store masks or the tile lists, under DH_TILE_SHIFT=off,
+// when the slack allows the one shift (0, 0) only, or when the occupancy table of a frame would not fit k_tile_shift's LDS.
+struct TileShifts {
+    bool on = false;
+    int gx = 1, nsx = 1, nsy = 1, sx0 = 0, sy0 = 0;
+};
+#define DH_TILE_SHIFT_LDS_WORDS 12288      // 48 KB
+static inline size_t dh_tile_shift_lds_words(int mask_blocks, int parts, int nc, int n_shifts) {
+    return (size_t)2 * mask_blocks * parts + (size_t)(mask_blocks + 1) * (nc + 1) + (size_t)n_shifts + 8;   // keep in step with k_tile_shift
+}
+// Returns DH_OK or DH_EINVAL (message set): a malformed DH_TILE_SHIFT, or a forced shift this geometry cannot run.
+int dh_tile_shifts_(const Geom &g, int step, int blk_shift, const Knobs &k, TileShifts *out);
 static const int kBoxSpan = 256, kBoxMaxRect = 96;   // image columns one k_boxsum wave spans; largest rectangle edge it serves
 // Bands a frame is cut into by the LDS-ring k_boxsum for a batch of n frames: band height `*oh` (whole mask blocks of `blk` rows)
 // and the number of bands.  A workgroup is 4 waves = 4 (part, band) units and the chip holds `wg_slots` of them (3 per CU: the

@@ -114,7 +114,8 @@ struct TraverseArgs {
     int swz_log2, swz_q;    // uniform path: LDS slot of region cell (y, x) = y * ss_row + (x & (m - 1)) * swz_q + (x >> swz_log2), m = 1 << swz_log2
     const uint32_t *box;    // uniform path: [n_frames][box_rows][m planes][box_plane] box-sum images written by k_boxsum
     int box_plane, box_rows;
-    const uint32_t *tile_list;       // nullable: [8][tile_list_stride] the flagged (frame group << 16 | tile) pairs per x = frame mod 8 (k_tile_list)
+    const uint2 *tile_list;          // nullable: [8][tile_list_stride] per x = frame mod 8 the flagged tiles, .x = frame group << 16 | tile,
+                                     // .y = the frame's grid shift sx | sy << 16 in windows (k_tile_list, k_tile_shift)
     const uint32_t *tile_list_count; // [8]
     uint32_t tile_list_stride;
     const uint32_t *gen;       // the batch's tile-flag tag (BoxArgs::gen)
@@ -179,6 +180,7 @@ struct BoxArgs {
     uint8_t *tile_flags;    // [n_frames][tiles_x * tiles_y] k_traverse tiles with a non-zero sum in their region: set to the batch's TAG (*gen)
     const uint32_t *gen;    // the batch's tile-flag tag, 1 .. 255 (k_emit moves it on): a flag holding any other value is clear -- or a stale,
                             // harmless false positive (the flags are conservative) -- so the flags never need a fill
+    uint32_t *list_count;   // nullable: [8] the tile lists' lengths, cleared here for k_tile_shift, which appends to them
     uint32_t *zero_ptr;     // nullable: the per-batch counters [0, zero_lo) and [zero_hi, zero_end) (words), zeroed by this kernel's waves
     uint32_t zero_lo, zero_hi, zero_end;   // instead of by a fill of their own (the tile flags sit in [zero_lo, zero_hi))
     int tiles_x, tiles_y;   // k_traverse's tiling: tile (tx, ty) reads columns [tx * tpx, tx * tpx + tbw), rows [ty * tpy, ty * tpy + tbh)
@@ -193,6 +195,26 @@ struct BoxArgs {
     unsigned long long *blk_mask;
     int mask_blocks;        // ceil(rows / block height)
     int blk_shift;          // log2 of the mask blocks' height: 5 (32 rows); 3 on single-frame workspaces, whose bands are 8 rows
+};
+
+// k_tile_shift: per frame, the shift of the tile grid that leaves the fewest flagged tiles, and the tile lists of that grid.
+// Tile (tx, ty) of a grid shifted by (sx, sy) windows covers window columns [max(0, tx px - sx), min(nx, (tx + 1) px - sx)) and rows
+// likewise; sx = sx0 + gx i (i < nsx) and sy = sy0 + j (j < nsy) stay within the slack tiles_x px - nx, tiles_y py - ny of the
+// grid, so every tile exists under every shift and no buffer changes size.  The occupancy it counts on is k_boxsum's sparse-store
+// masks (BoxArgs::blk_mask) of this batch: 4-column groups x mask blocks of rows that hold a non-zero rectangle sum.  A tile is
+// flagged when such a group meets its (unclipped) region -- at shift (0, 0) exactly the tiles k_boxsum flags.
+struct TileShiftArgs {
+    const unsigned long long *blk_mask;   // [n_frames][mask_blocks][parts]
+    int n_frames, mask_blocks, blk_shift, parts;
+    int ow4, nc;            // 4-column groups per part (BoxArgs::ow / 4) and per row (parts * ow4)
+    int tiles_x, tiles_y;
+    int tpx, tpy, tbw, tbh; // as BoxArgs: an unshifted tile's region is columns [tx * tpx, tx * tpx + tbw), rows [ty * tpy, ty * tpy + tbh)
+    int step;               // pixels per window of shift
+    int sx0, sy0, gx, nsx, nsy;
+    uint2 *list;            // TraverseArgs::tile_list; a frame's entries are appended in one piece (the lengths start at zero: BoxArgs::list_count)
+    uint32_t *count;        // [8]
+    uint32_t stride;
+    uint32_t *shift_out;    // [n_frames] sx | sy << 16
 };
 
 // k_pixflags: tile flags of the general path (non-zero pixel under the tile's footprint).
@@ -479,7 +501,8 @@ hipError_t dh_launch_nodes_compact(const DevForest &f, int ss, int swz_log2, int
                                    uint32_t *amb_list, uint32_t n_amb, hipStream_t s);
 #define DH_AMB_CAP 4096      // ambiguous nodes the walk table can hold (more: the guarded node table is walked)
 hipError_t dh_launch_traverse(const TraverseArgs &a, size_t lds_bytes, hipStream_t s);
-hipError_t dh_launch_tile_list(const uint8_t *flags, const uint32_t *gen, int n_frames, int tiles, uint32_t *list, uint32_t *count, uint32_t stride, hipStream_t s);
+hipError_t dh_launch_tile_list(const uint8_t *flags, const uint32_t *gen, int n_frames, int tiles, uint2 *list, uint32_t *count, uint32_t stride, hipStream_t s);
+hipError_t dh_launch_tile_shift(const TileShiftArgs &a, hipStream_t s);
 hipError_t dh_launch_emit(const EmitArgs &a, hipStream_t s);
 hipError_t dh_launch_vote(const VoteArgs &a, hipStream_t s);
 hipError_t dh_launch_cluster(const ClusterArgs &a, hipStream_t s);

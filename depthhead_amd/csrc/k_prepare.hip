@@ -1,4 +1,4 @@
-// k_prepare.hip -- per batch, ahead of the walks: rectangle-sum images and tile flags (k_boxsum, k_pixflags), tile lists (k_tile_list), zero-fill (k_zero)
+// k_prepare.hip -- per batch, ahead of the walks: rectangle-sum images and tile flags (k_boxsum, k_pixflags), tile lists (k_tile_list, k_tile_shift), zero-fill (k_zero)
 //
 // One of the kernel translation units of libdepthhead_hip.so (hand-written HIP for gfx950: wave64, 160 KB LDS/CU;
 // no MFMA anywhere -- there is no dense contraction on this path).  Overview of the pipeline: dh_api.hip.
@@ -145,6 +145,7 @@ __global__ void __launch_bounds__(BOXW_THREADS) k_boxsum(BoxArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t pex_s[BOXW_WAVES][BOX_SPAN + BOX_MAXR + 8];
     extern __shared__ __attribute__((aligned(16))) uint32_t box_dyn[];       // RING: [BOXW_WAVES][rh - 1][64] packed rows
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
+    if (a.list_count && (blockIdx.x | blockIdx.y | blockIdx.z) == 0 && threadIdx.x < 8) a.list_count[threadIdx.x] = 0u;
     if (a.zero_ptr) {
         // the batch's other counters (hit counters, guess grids, window counts, leaf histogram): this is the first kernel of the
         // batch and none of them is touched before the next one, so every wave of the grid clears a share -- no fill dispatch
@@ -237,7 +238,8 @@ hipError_t dh_launch_pixflags(const PixFlagArgs &a, hipStream_t s) {
 // k-th entry; the workgroups beyond a list's end -- the flagged-empty tiles, four in seven on the bench frames -- then sit at the
 // END of the grid, where they leave at once instead of each holding a workgroup slot (79 KB of LDS) for the 1-2 us it takes a
 // workgroup to start, read its flag and go, in the middle of the real work.
-__global__ void __launch_bounds__(1024) k_tile_list(const uint8_t *flags, const uint32_t *gen, int n_frames, int tiles, uint32_t *list, uint32_t *count, uint32_t stride) {
+// (The grid of these lists is the unshifted one: .y = 0.  k_tile_shift writes the lists of the batches whose frames choose a shift.)
+__global__ void __launch_bounds__(1024) k_tile_list(const uint8_t *flags, const uint32_t *gen, int n_frames, int tiles, uint2 *list, uint32_t *count, uint32_t stride) {
     __shared__ uint32_t wsum[16];
     const uint8_t tag = (uint8_t)*gen;
     const int x = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid >> 6;
@@ -253,16 +255,115 @@ __global__ void __launch_bounds__(1024) k_tile_list(const uint8_t *flags, const 
         __syncthreads();
         uint32_t off = 0, tot = 0;
         for (int i = 0; i < 16; ++i) { const uint32_t c = wsum[i]; off += i < wv ? c : 0u; tot += c; }
-        if (on) list[(size_t)x * stride + base + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (z << 16) | t;
+        if (on) list[(size_t)x * stride + base + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = make_uint2((z << 16) | t, 0u);
         base += tot;
         __syncthreads();
     }
     if (tid == 0) count[x] = base;
 }
 
-hipError_t dh_launch_tile_list(const uint8_t *flags, const uint32_t *gen, int n_frames, int tiles, uint32_t *list, uint32_t *count, uint32_t stride, hipStream_t s) {
+hipError_t dh_launch_tile_list(const uint8_t *flags, const uint32_t *gen, int n_frames, int tiles, uint2 *list, uint32_t *count, uint32_t stride, hipStream_t s) {
     if (n_frames == 0 || tiles == 0) return hipSuccess;
     hipLaunchKernelGGL(k_tile_list, dim3(8), dim3(1024), 0, s, flags, gen, n_frames, tiles, list, count, stride);
+    return hipGetLastError();
+}
+
+// ================================================================== k_tile_shift
+// Where a head sits relative to a tile grid fixed at window (0, 0) is arbitrary, and a flagged tile costs k_traverse the same
+// whether it is full or nearly empty.  The grid has slack (tiles_x * px - nx window columns, tiles_y * py - ny rows): one
+// workgroup per frame counts, for every allowed shift of the grid (TileShiftArgs), the tiles that would be flagged, takes the
+// shift with the fewest (ties: smallest sy, then smallest sx) and appends the flagged tiles of that grid to the frame's list.
+//
+// The occupancy is k_boxsum's mask of this batch, bit (block b, group c) = "a non-zero rectangle sum with its origin in rows
+// [b B, (b + 1) B) and columns [4 c, 4 c + 4)".  S[b][c] = number of set bits in blocks < b and groups < c (a summed-area table
+// in LDS: the row prefixes are popcounts of the mask words, the columns are added up by one thread each), so "does the region of
+// a tile meet a set bit" is four reads.  Lists are appended per frame with one atomic on the list's length: their order varies
+// from run to run, what k_traverse writes for a (frame, tile) does not depend on it.
+#define TSH_THREADS 256
+__global__ void __launch_bounds__(TSH_THREADS) k_tile_shift(TileShiftArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t tsh[];
+    const int frame = (int)blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid >> 6;
+    const int NB = a.mask_blocks, NC = a.nc, W1 = NC + 1, tiles = a.tiles_x * a.tiles_y, n_shifts = a.nsx * a.nsy;
+    unsigned long long *mk = (unsigned long long *)tsh;      // [NB][parts] the frame's mask words
+    uint32_t *S = tsh + 2 * NB * a.parts;                    // [NB + 1][W1]
+    uint32_t *cnt = S + (NB + 1) * W1;                       // [n_shifts] flagged tiles per shift
+    uint32_t *misc = cnt + n_shifts;                         // [0] best count << 16 | shift, [1] first list entry, [4 ..] per-wave counts
+    const unsigned long long valid = a.ow4 >= 64 ? ~0ull : (1ull << a.ow4) - 1ull;
+    const unsigned long long *bm = a.blk_mask + (size_t)frame * NB * a.parts;
+    for (int i = tid; i < NB * a.parts; i += TSH_THREADS) mk[i] = bm[i] & valid;
+    for (int i = tid; i < W1; i += TSH_THREADS) S[i] = 0u;
+    for (int i = tid; i < n_shifts; i += TSH_THREADS) cnt[i] = 0u;
+    if (tid == 0) misc[0] = 0xffffffffu;
+    __syncthreads();
+    {
+        const float r_w1 = 1.0f / (float)W1, r_ow4 = 1.0f / (float)a.ow4;
+        for (int i = tid; i < NB * W1; i += TSH_THREADS) {
+            const int b = div_small(i, W1, r_w1), c = i - b * W1;              // bits of block b in the groups < c
+            const int part = div_small(c, a.ow4, r_ow4), l = c - part * a.ow4;
+            uint32_t h = 0;
+            for (int p2 = 0; p2 < part; ++p2) h += (uint32_t)__popcll(mk[b * a.parts + p2]);
+            if (part < a.parts) h += (uint32_t)__popcll(mk[b * a.parts + part] & ((1ull << l) - 1ull));
+            S[(b + 1) * W1 + c] = h;
+        }
+    }
+    __syncthreads();
+    for (int c = tid; c < W1; c += TSH_THREADS) {
+        uint32_t run = 0;
+        for (int b = 1; b <= NB; ++b) { run += S[b * W1 + c]; S[b * W1 + c] = run; }
+    }
+    __syncthreads();
+    const float r_tx = 1.0f / (float)a.tiles_x;
+    // the rule of k_boxsum's flags: the region [X, X + tbw) x [Y, Y + tbh) of the tile meets the columns of a set group and the rows of its block
+    auto flagged = [&](int t, int sx, int sy) -> bool {
+        const int ty = div_small(t, a.tiles_x, r_tx), tx = t - ty * a.tiles_x;
+        const int X = tx * a.tpx - sx * a.step, Y = ty * a.tpy - sy * a.step;
+        const int c0 = max(X, 0) >> 2, c1 = min((X + a.tbw - 1) >> 2, NC - 1);
+        const int b0 = max(Y, 0) >> a.blk_shift, b1 = min((Y + a.tbh - 1) >> a.blk_shift, NB - 1);
+        if (c1 < c0 || b1 < b0) return false;
+        return S[(b1 + 1) * W1 + c1 + 1] - S[b0 * W1 + c1 + 1] - S[(b1 + 1) * W1 + c0] + S[b0 * W1 + c0] != 0u;
+    };
+    {
+        const float r_tiles = 1.0f / (float)tiles, r_nsx = 1.0f / (float)a.nsx;
+        for (int i = tid; i < n_shifts * tiles; i += TSH_THREADS) {
+            const int sh = div_small(i, tiles, r_tiles), t = i - sh * tiles;
+            const int isy = div_small(sh, a.nsx, r_nsx), isx = sh - isy * a.nsx;
+            if (flagged(t, a.sx0 + isx * a.gx, a.sy0 + isy)) atomicAdd(&cnt[sh], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n_shifts; i += TSH_THREADS) atomicMin(&misc[0], (cnt[i] << 16) | (uint32_t)i);   // shifts are numbered sy-major
+    __syncthreads();
+    const uint32_t best = misc[0] & 0xffffu, total = misc[0] >> 16;
+    const int bsy = (int)best / a.nsx, bsx = (int)best - bsy * a.nsx;
+    const int sx = a.sx0 + bsx * a.gx, sy = a.sy0 + bsy;
+    const uint32_t x = (uint32_t)frame & 7u, z = (uint32_t)frame >> 3;
+    if (tid == 0) {
+        a.shift_out[frame] = (uint32_t)sx | ((uint32_t)sy << 16);
+        misc[1] = total ? atomicAdd(&a.count[x], total) : 0u;
+    }
+    uint32_t base = 0;
+    for (int t0 = 0; t0 < tiles; t0 += TSH_THREADS) {
+        const int t = t0 + tid;
+        const bool on = t < tiles && flagged(t, sx, sy);
+        const unsigned long long bal = __ballot(on);
+        if (lane == 0) misc[4 + wv] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = 0, tot = 0;
+        for (int i = 0; i < TSH_THREADS / WAVE; ++i) { const uint32_t c = misc[4 + i]; off += i < wv ? c : 0u; tot += c; }
+        // (base + off + rank < total <= the frame's tiles, and a list holds every tile of its frames: an entry stays inside its list
+        // as long as the lengths started at zero -- checked all the same, the list is the one thing here written through a shared index)
+        const uint32_t slot = misc[1] + base + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (on && slot < a.stride) a.list[(size_t)x * a.stride + slot] = make_uint2((z << 16) | (uint32_t)t, (uint32_t)sx | ((uint32_t)sy << 16));
+        base += tot;
+        __syncthreads();
+    }
+}
+
+hipError_t dh_launch_tile_shift(const TileShiftArgs &a, hipStream_t s) {
+    if (a.n_frames == 0 || a.tiles_x * a.tiles_y == 0) return hipSuccess;
+    const size_t words = dh_tile_shift_lds_words(a.mask_blocks, a.parts, a.nc, a.nsx * a.nsy);
+    if (words > DH_TILE_SHIFT_LDS_WORDS || a.nsx * a.nsy > 65535 || a.tiles_x * a.tiles_y > 65535) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(k_tile_shift, dim3(a.n_frames), dim3(TSH_THREADS), words * sizeof(uint32_t), s, a);
     return hipGetLastError();
 }
 

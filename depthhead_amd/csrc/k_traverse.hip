@@ -527,19 +527,26 @@ __global__ void __launch_bounds__(TRAV_THREADS, TRAV_THREADS / 128) k_traverse(T
     // XCDs round-robin -- is x + 8 * (tile + tiles * z), so no division is needed to decode it.
     int frame = (int)blockIdx.z * 8 + (int)blockIdx.x;
     int tile = (int)blockIdx.y;
+    int sx = 0, sy = 0;     // the frame's grid shift in windows (k_tile_shift): wave-uniform, like everything derived from it
     if (a.tile_list) {
-        // (k_tile_list) this workgroup takes the k-th flagged tile of the frames = x mod 8; both loads at once
+        // (k_tile_list, k_tile_shift) this workgroup takes the k-th flagged tile of the frames = x mod 8 and with it the shift of
+        // that frame's tile grid; both loads at once
         const uint32_t k = blockIdx.y + gridDim.y * blockIdx.z;
-        const uint32_t e = a.tile_list[(size_t)blockIdx.x * a.tile_list_stride + k], cnt = a.tile_list_count[blockIdx.x];
+        const uint2 e = a.tile_list[(size_t)blockIdx.x * a.tile_list_stride + k];
+        const uint32_t cnt = a.tile_list_count[blockIdx.x];
         if (k >= cnt) return;
-        frame = (int)(e >> 16) * 8 + (int)blockIdx.x; tile = (int)(e & 0xffffu);
+        frame = (int)(e.x >> 16) * 8 + (int)blockIdx.x; tile = (int)(e.x & 0xffffu);
+        sx = (int)(e.y & 0xffffu); sy = (int)(e.y >> 16);
     }
     if (frame >= a.n_frames || KNOB_STOP(a.stop_phase == 9)) return;
     const int ty = div_small(tile, a.tiles_x, 1.0f / (float)a.tiles_x), tx = tile - ty * a.tiles_x;
-    const int cx = min(a.px, a.nx - tx * a.px), cy = min(a.py, a.ny - ty * a.py);
+    // the tile's windows: columns [wx0, wx0 + cx), rows [wy0, wy0 + cy) of the frame's window grid -- a shifted grid cuts tiles at the
+    // left and top edge as well as at the right and bottom
+    const int wx0 = max(0, tx * a.px - sx), wy0 = max(0, ty * a.py - sy);
+    const int cx = min(a.nx, (tx + 1) * a.px - sx) - wx0, cy = min(a.ny, (ty + 1) * a.py - sy) - wy0;
     const float r_cx = 1.0f / (float)cx;
     const int npt = cx * cy;
-    const int fx0 = tx * a.px * a.step, fy0 = ty * a.py * a.step;   // footprint origin (pixels)
+    const int fx0 = wx0 * a.step, fy0 = wy0 * a.step;   // footprint origin (pixels)
     const int fw = (cx - 1) * a.step + a.sw, fh = (cy - 1) * a.step + a.sh;
     const int ss = a.ss_row;
 
@@ -618,7 +625,7 @@ __global__ void __launch_bounds__(TRAV_THREADS, TRAV_THREADS / 128) k_traverse(T
         // cover every window): all of its windows are background (prediction.rs:567-576)
         if (a.dbg_flags)
             for (int p = tid; p < npt; p += TRAV_THREADS) {
-                int gp = (ty * a.py + p / cx) * a.nx + tx * a.px + p % cx;
+                int gp = (wy0 + p / cx) * a.nx + wx0 + p % cx;
                 size_t o = (size_t)frame * a.nx * a.ny + gp;
                 a.dbg_flags[o] = 0;
                 if (a.dbg_leaf)
@@ -662,7 +669,7 @@ __global__ void __launch_bounds__(TRAV_THREADS, TRAV_THREADS / 128) k_traverse(T
             sum = sat[(oy + a.sh) * ss + ox + a.sw] - sat[oy * ss + ox + a.sw] - sat[(oy + a.sh) * ss + ox] + sat[oy * ss + ox];
         }
         const bool nonbg = sum != 0;   // (sum as f64)/(count as f64) > 0.0  <=>  sum > 0
-        const int gp = (ty * a.py + pyi) * a.nx + tx * a.px + pxi;     // position in the frame's window grid
+        const int gp = (wy0 + pyi) * a.nx + wx0 + pxi;     // position in the frame's window grid
         // slot = running count of active windows: one LDS atomic per wave, ranks from the ballot
         const unsigned long long bal = __ballot(nonbg);
         uint32_t wave_base = 0;

@@ -431,6 +431,13 @@ class HoughPrediction(_lib._Handle):
         geo.update(uniform=path & 1, walk_table=(path >> 8) & 1, top_levels=path >> 16)
         return geo
 
+    def debug_tile_shifts(self, n: int) -> tuple[np.ndarray, np.ndarray]:
+        """Of the last batch (n frames, run with tile lists): each frame's tile-grid shift [n, 2] (sx, sy) in windows, and the tiles walked
+        per list of the frames = x mod 8 [8]."""
+        shifts, counts = np.zeros((n, 2), dtype=np.int32), np.zeros(8, dtype=np.uint32)
+        check(self._lib.dh_debug_tile_shifts(self._ph, vp(shifts), vp(counts)))
+        return shifts, counts
+
     def debug_hit_counts(self, n: int) -> np.ndarray:
         out = np.zeros(n, dtype=np.uint32)
         check(self._lib.dh_debug_hit_counts(self._ph, vp(out)))

@@ -1462,6 +1462,12 @@ int dh_debug_hit_counts(dh_predictor *p, uint32_t *out);
  * nodes with an ambiguity band); bits 16..: tree levels walked from LDS), tile px, py, tiles_x, tiles_y, column de-interleave log2,
  * plane stride q, LDS row stride, rectangle w, rectangle h. */
 int dh_debug_geometry(dh_predictor *p, int32_t out[10]);
+/* The tile lists of the last batch -- of its last resident slice, as for every tap, when DH_MAX_RESIDENT_FRAMES cut it into slices
+ * (large batches in product mode; DH_ESTATE when it ran without them).  Each frame of such a batch
+ * chooses the shift of its tile grid -- within the grid's slack over the window grid -- that leaves the fewest tiles to walk:
+ * shifts [n][2] = {sx, sy} in windows per frame (zeros where the geometry or DH_TILE_SHIFT=off leaves the one shift (0, 0);
+ * DH_TILE_SHIFT=sx,sy forces one shift), counts [8] = tiles walked for the frames = x mod 8.  Waits for the batch; debug only. */
+int dh_debug_tile_shifts(dh_predictor *p, int32_t *shifts, uint32_t counts[8]);
 
 #ifdef __cplusplus
 }
