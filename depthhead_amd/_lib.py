@@ -109,6 +109,22 @@ SUBJECT_STATE_DTYPE = np.dtype([("coeffs", "<f8", (8,)), ("applied", "<u4"), ("r
 assert SUBJECT_STATE_DTYPE.itemsize == 80
 SUBJECTS_MAX_TRIS = 131072  # DH_SUBJECTS_MAX_TRIS
 SUBJECT_CLAMPED, SUBJECT_NONFINITE = 1, 2   # DH_SUBJECT_*
+# dh_surface_record: what one surface step reports for a subject (dh_fit_surface_subjects*)
+SURFACE_RECORD_DTYPE = np.dtype([("status", "<u4"), ("points", "<u4"), ("instances", "<u4"), ("observed", "<u4"), ("clamped", "<u4"),
+                                 ("rejected", "<u4"), ("sum_r2_fixed", "<i8"), ("max_abs", "<f8")], align=True)
+assert SURFACE_RECORD_DTYPE.itemsize == 40
+SURFACE_OK, SURFACE_FEW_POINTS = 0, 1       # DH_SURFACE_*
+SURFACE_MAX_OFFSET = 64        # DH_SURFACE_MAX_OFFSET (mm)
+SURFACE_MAX_SCALE = 64         # DH_SURFACE_MAX_SCALE
+SURFACE_MAX_CELLS = 1 << 22    # DH_SURFACE_MAX_CELLS
+SURFACE_MAX_ITERATIONS = 256   # DH_SURFACE_MAX_ITERATIONS
+SURFACE_LDS_POINTS = 10112     # the solve keeps its two buffers in LDS up to this many vertices (dh_fit.h)
+
+
+class SurfaceParams(C.Structure):
+    """dh_surface_params"""
+    _fields_ = [("gate", C.c_double), ("min_cos2", C.c_double), ("mu", C.c_double), ("eps", C.c_double), ("min_count", C.c_uint32),
+                ("min_points", C.c_uint32), ("iterations", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 2)]
 
 
 # dh_view_instance / dh_view_fit_record: one world-posed model seen by several cameras, and what its fit reports (dh_fit_depth_views*)
@@ -227,6 +243,8 @@ EXPORTS = [
     "dh_fit_subjects_state", "dh_fit_subjects_read", "dh_fit_subjects_update", "dh_fit_subjects_update_device", "dh_fit_shape_subjects", "dh_fit_shape_subjects_cameras",
     "dh_fit_shape_subjects_device", "dh_fit_shape_subjects_cameras_device", "dh_fit_depth_carried_device",
     "dh_fit_depth_cameras_carried_device",
+    "dh_fit_subjects_create_surface", "dh_fit_subjects_set_offsets", "dh_fit_subjects_read_offsets", "dh_fit_surface_params_default",
+    "dh_fit_surface_subjects", "dh_fit_surface_subjects_cameras", "dh_fit_surface_subjects_device", "dh_fit_surface_subjects_cameras_device",
 ]
 
 

@@ -3271,6 +3271,15 @@ struct dh_fit_subjects {
     Buf<SubjectModel> table;                 // [S] the models' pointers
     Buf<dh_shape_record> rec;                // the host update's records
     std::vector<std::unique_ptr<dh_fit_model>> models;
+    // a surface set: everything below is allocated at creation, nothing later
+    bool surface = false;
+    double max_offset = 0.0;
+    Buf<float> nb;                           // [n][3] the base normals
+    Buf<uint32_t> nbr_begin, nbr;            // each vertex's neighbour list
+    Buf<double> offsets;                     // [S][n]
+    Buf<unsigned long long> rows, tally;     // the step's sums: [S][n][DH_SURFACE_ROW] and [S][DH_SURFACE_TALLY]
+    Buf<double> scratch;                     // [S][2][n]
+    Buf<dh_surface_record> srec;             // [S] the host step's records
     hipStream_t s = nullptr;                 // the host calls' stream
     ~dh_fit_subjects() { if (s) (void)hipStreamDestroy(s); }
 };
@@ -3285,9 +3294,15 @@ static SubjectsArgs subjects_args(const dh_fit_subjects *set, const dh_shape_rec
     a.max_coeff = set->max_coeff;
     return a;
 }
-static int fit_subjects_create_(const float *verts, uint32_t n, const uint32_t *tris, uint32_t n_tris, const dh_fit_basis *basis, uint32_t n_subjects,
-                                double max_coeff, int device, dh_fit_subjects **out) {
-    const char *who = "dh_fit_subjects_create";
+// One evaluation of subjects first .. first + count - 1 (apply where rec is given, points, normals): a surface set's points
+// carry its offsets.
+static hipError_t subjects_evaluate(const dh_fit_subjects *set, const dh_shape_record *rec, uint32_t first, uint32_t count, hipStream_t s) {
+    const SubjectsArgs a = subjects_args(set, rec, first, count);
+    if (!set->surface) return dh_launch_subjects_update(a, s);
+    return dh_launch_subjects_update_surface(SurfacePointsArgs{a, set->nb.get(), set->offsets.get()}, true, s);
+}
+static int subjects_create(const float *verts, uint32_t n, const uint32_t *tris, uint32_t n_tris, const dh_fit_basis *basis, uint32_t n_subjects,
+                           double max_coeff, bool surface, double max_offset, int device, dh_fit_subjects **out, const char *who) {
     if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
     *out = nullptr;
     if (!verts || !tris || !basis) return fail(DH_EINVAL, "%s: NULL argument", who);
@@ -3315,11 +3330,24 @@ static int fit_subjects_create_(const float *verts, uint32_t n, const uint32_t *
     if (flat < n) return fail(DH_EINVAL, "%s: vertex %u of the base mesh has a zero normal", who, flat);
     if (basis->n != n) return fail(DH_EINVAL, "%s: the basis is one of %u points, the mesh has %u", who, basis->n, n);
     if (basis->device != device) return fail(DH_EINVAL, "%s: the basis lives on device %d, the set on %d", who, basis->device, device);
+    std::vector<uint32_t> nbr_begin, nbr;
+    if (surface) {
+        if (!(max_offset > 0.0 && max_offset <= DH_SURFACE_MAX_OFFSET))
+            return fail(DH_EINVAL, "%s: max_offset %g outside (0, %g]", who, max_offset, DH_SURFACE_MAX_OFFSET);
+        if ((uint64_t)n_subjects * n > DH_SURFACE_MAX_CELLS)
+            return fail(DH_EINVAL, "%s: %u subjects of %u vertices exceed %u cells", who, n_subjects, n, DH_SURFACE_MAX_CELLS);
+        std::vector<uint32_t> work((size_t)n_tris * 6);
+        nbr_begin.resize((size_t)n + 1); nbr.resize((size_t)n_tris * 6);
+        (void)dh_subjects_neighbour_lists(tris, n_tris, n, nbr_begin.data(), nbr.data(), work.data(), nullptr);   // (the indices were checked above)
+        nbr.resize(std::max<size_t>(nbr_begin[n], 1));
+    }
 
     std::unique_ptr<dh_fit_subjects> set(new dh_fit_subjects);
     set->device = device; set->n = n; set->n_tris = n_tris; set->n_subjects = n_subjects;
     set->max_coeff = max_coeff; set->basis = basis;
-    set->radius = dh_subjects_radius_bound(sqrt(r2), basis->k, max_coeff, basis->largest);
+    set->surface = surface; set->max_offset = surface ? max_offset : 0.0;
+    set->radius = surface ? dh_surface_radius_bound(sqrt(r2), basis->k, max_coeff, basis->largest, max_offset)
+                          : dh_subjects_radius_bound(sqrt(r2), basis->k, max_coeff, basis->largest);
     DeviceGuard guard(device);
     if (!guard.ok) return DH_EHIP;
     TRY(set->base.alloc((size_t)n * 3));
@@ -3345,10 +3373,70 @@ static int fit_subjects_create_(const float *verts, uint32_t n, const uint32_t *
     HIP_TRY(hipMemcpy(set->corners.get(), corners.data(), corners.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(set->table.get(), table.data(), table.size() * sizeof(SubjectModel), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(set->state.get(), 0, (size_t)n_subjects * sizeof(dh_subject_state)));
-    // every model evaluated at its zero coefficients
-    TRY(hip_step(dh_launch_subjects_update(subjects_args(set.get(), nullptr, 0, n_subjects), set->s), "k_subjects"));
+    if (surface) {
+        const size_t cells = (size_t)n_subjects * n;
+        TRY(set->nb.alloc((size_t)n * 3));
+        TRY(set->nbr_begin.alloc(nbr_begin.size()));
+        TRY(set->nbr.alloc(nbr.size()));
+        TRY(set->offsets.alloc(cells));
+        TRY(set->rows.alloc(cells * DH_SURFACE_ROW));
+        TRY(set->tally.alloc((size_t)n_subjects * DH_SURFACE_TALLY));
+        TRY(set->scratch.alloc(cells * 2));
+        TRY(set->srec.alloc(n_subjects));
+        TRY(hip_step(dh_surface_solve_prepare(n), "k_surface_solve: dynamic LDS"));
+        HIP_TRY(hipMemcpy(set->nbr_begin.get(), nbr_begin.data(), nbr_begin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(set->nbr.get(), nbr.data(), nbr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(set->offsets.get(), 0, cells * sizeof(double)));
+        HIP_TRY(hipMemset(set->rows.get(), 0, cells * DH_SURFACE_ROW * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(set->tally.get(), 0, (size_t)n_subjects * DH_SURFACE_TALLY * sizeof(unsigned long long)));
+        HIP_TRY(hipDeviceSynchronize());
+        // the base normals: section 25's normals of subject 0's model at its zero coefficients, which is the base mesh
+        TRY(hip_step(dh_launch_subjects_update(subjects_args(set.get(), nullptr, 0, 1), set->s), "k_subjects"));
+        HIP_TRY(hipMemcpyAsync(set->nb.get(), table[0].nrm, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, set->s));
+    }
+    // every model evaluated at its zero coefficients (and zero offsets)
+    TRY(hip_step(subjects_evaluate(set.get(), nullptr, 0, n_subjects, set->s), "k_subjects"));
     HIP_TRY(hipStreamSynchronize(set->s));
     *out = set.release();
+    return DH_OK;
+}
+static int fit_subjects_create_(const float *verts, uint32_t n, const uint32_t *tris, uint32_t n_tris, const dh_fit_basis *basis, uint32_t n_subjects,
+                                double max_coeff, int device, dh_fit_subjects **out) {
+    return subjects_create(verts, n, tris, n_tris, basis, n_subjects, max_coeff, false, 0.0, device, out, "dh_fit_subjects_create");
+}
+static int fit_subjects_create_surface_(const float *verts, uint32_t n, const uint32_t *tris, uint32_t n_tris, const dh_fit_basis *basis, uint32_t n_subjects,
+                                        double max_coeff, double max_offset, int device, dh_fit_subjects **out) {
+    return subjects_create(verts, n, tris, n_tris, basis, n_subjects, max_coeff, true, max_offset, device, out, "dh_fit_subjects_create_surface");
+}
+// The offsets of one subject of a surface set.
+static int fit_subjects_set_offsets_(dh_fit_subjects *s, uint32_t subject, const double *offsets) {
+    const char *who = "dh_fit_subjects_set_offsets";
+    if (!s) return fail(DH_EINVAL, "%s: NULL subject set", who);
+    if (!offsets) return fail(DH_EINVAL, "%s: NULL offsets", who);
+    if (!s->surface) return fail(DH_EINVAL, "%s: the set holds no offsets (dh_fit_subjects_create_surface makes one that does)", who);
+    if (subject >= s->n_subjects) return fail(DH_EINVAL, "%s: subject %u of %u", who, subject, s->n_subjects);
+    for (uint32_t i = 0; i < s->n; ++i)
+        if (!(fabs(offsets[i]) <= s->max_offset)) return fail(DH_EINVAL, "%s: offset %u is %g, outside +-%g", who, i, offsets[i], s->max_offset);
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return DH_EHIP;
+    HIP_TRY(hipMemcpyAsync(s->offsets.get() + (size_t)subject * s->n, offsets, (size_t)s->n * sizeof(double), hipMemcpyHostToDevice, s->s));
+    TRY(hip_step(subjects_evaluate(s, nullptr, subject, 1, s->s), "k_subjects"));
+    HIP_TRY(hipStreamSynchronize(s->s));
+    return DH_OK;
+}
+static int fit_subjects_read_offsets_(dh_fit_subjects *s, uint32_t subject, double *offsets, uint32_t *counts) {
+    const char *who = "dh_fit_subjects_read_offsets";
+    if (!s) return fail(DH_EINVAL, "%s: NULL subject set", who);
+    if (!s->surface) return fail(DH_EINVAL, "%s: the set holds no offsets (dh_fit_subjects_create_surface makes one that does)", who);
+    if (subject >= s->n_subjects) return fail(DH_EINVAL, "%s: subject %u of %u", who, subject, s->n_subjects);
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return DH_EHIP;
+    std::vector<unsigned long long> rows(counts ? (size_t)s->n * DH_SURFACE_ROW : 0);
+    if (offsets) HIP_TRY(hipMemcpyAsync(offsets, s->offsets.get() + (size_t)subject * s->n, (size_t)s->n * sizeof(double), hipMemcpyDeviceToHost, s->s));
+    if (counts) HIP_TRY(hipMemcpyAsync(rows.data(), s->rows.get() + (size_t)subject * s->n * DH_SURFACE_ROW, rows.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->s));
+    HIP_TRY(hipStreamSynchronize(s->s));
+    if (counts)
+        for (uint32_t i = 0; i < s->n; ++i) counts[i] = (uint32_t)std::min<unsigned long long>(rows[(size_t)i * DH_SURFACE_ROW + DH_SURFACE_CNT], 0xffffffffull);
     return DH_OK;
 }
 static int fit_subjects_destroy_(dh_fit_subjects *s) {
@@ -3395,7 +3483,7 @@ static int fit_subjects_set_coeffs_(dh_fit_subjects *s, uint32_t first, uint32_t
         st[i].flags = 0;
     }
     HIP_TRY(hipMemcpyAsync(s->state.get() + first, st.data(), (size_t)count * sizeof(dh_subject_state), hipMemcpyHostToDevice, s->s));
-    TRY(hip_step(dh_launch_subjects_update(subjects_args(s, nullptr, first, count), s->s), "k_subjects"));
+    TRY(hip_step(subjects_evaluate(s, nullptr, first, count, s->s), "k_subjects"));
     HIP_TRY(hipStreamSynchronize(s->s));
     return DH_OK;
 }
@@ -3426,7 +3514,7 @@ static int fit_subjects_update_(dh_fit_subjects *s, const dh_shape_record *recor
     DeviceGuard guard(s->device);
     if (!guard.ok) return DH_EHIP;
     HIP_TRY(hipMemcpyAsync(s->rec.get(), records, (size_t)s->n_subjects * sizeof(dh_shape_record), hipMemcpyHostToDevice, s->s));
-    TRY(hip_step(dh_launch_subjects_update(subjects_args(s, s->rec.get(), 0, s->n_subjects), s->s), "k_subjects"));
+    TRY(hip_step(subjects_evaluate(s, s->rec.get(), 0, s->n_subjects, s->s), "k_subjects"));
     HIP_TRY(hipStreamSynchronize(s->s));
     return DH_OK;
 }
@@ -3435,7 +3523,7 @@ static int fit_subjects_update_device_(dh_fit_subjects *s, const dh_shape_record
     if (!records) return fail(DH_EINVAL, "dh_fit_subjects_update_device: NULL records");
     DeviceGuard guard(s->device);
     if (!guard.ok) return DH_EHIP;
-    return hip_step(dh_launch_subjects_update(subjects_args(s, records, 0, s->n_subjects), (hipStream_t)stream), "k_subjects");
+    return hip_step(subjects_evaluate(s, records, 0, s->n_subjects, (hipStream_t)stream), "k_subjects");
 }
 
 // The refusals every shape call (single-view or multi-view) begins with, around those of its frames: the pointers, then the
@@ -3619,6 +3707,150 @@ static int fit_shape_subjects_cameras_device_(dh_fitter *f, const uint16_t *fram
                                               const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records, void *stream) {
     return shape_run(f, shape_subjects_req(frames, n, w, h, nullptr, c, true, set, instances, n_instances, subjects, n_subjects, fit_records, params, records),
                      true, (hipStream_t)stream, "dh_fit_shape_subjects_cameras_device");
+}
+
+// ---- the surface step over a surface set
+static int fit_surface_params_default_(dh_surface_params *p) {
+    if (!p) return fail(DH_EINVAL, "dh_fit_surface_params_default: NULL argument");
+    memset(p, 0, sizeof *p);
+    p->gate = 25.0; p->min_cos2 = 0.25; p->mu = 0.5; p->eps = 0.05;
+    p->min_count = 2; p->min_points = 64; p->iterations = 32;
+    return DH_OK;
+}
+// One surface call.  dev: frames / instances / subjects / fit records / records are device pointers and `stream` the caller's.
+struct SurfaceReq {
+    const uint16_t *frames; int n, w, h;
+    const float *K; const dh_cameras *cams; bool use_cams;
+    dh_fit_subjects *set;
+    const dh_render_instance *inst; uint32_t n_inst;
+    const uint32_t *subjects; uint32_t n_subjects;
+    const dh_fit_record *fit_rec;
+    const dh_surface_params *prm;
+    dh_surface_record *rec;
+};
+static int surface_run(dh_fitter *f, const SurfaceReq &q, bool dev, hipStream_t stream, const char *who) {
+    // ---- refusals: all of them before anything is allocated or launched
+    if (!f) return fail(DH_EINVAL, "%s: NULL fitter", who);
+    if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!q.rec) return fail(DH_EINVAL, "%s: NULL records", who);
+    if (!q.set) return fail(DH_EINVAL, "%s: NULL subject set", who);
+    TRY(check_frames(q.n, q.w, q.h, q.K, q.cams, q.use_cams, f->device, "fitter", who));
+    dh_fit_subjects *set = q.set;
+    if (set->device != f->device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the fitter on %d", who, set->device, f->device);
+    if (!set->surface) return fail(DH_EINVAL, "%s: the set holds no offsets (dh_fit_subjects_create_surface makes one that does)", who);
+    if (q.n_subjects < 1 || q.n_subjects > set->n_subjects)
+        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u, the set's", who, q.n_subjects, set->n_subjects);
+    dh_surface_params prm;
+    (void)fit_surface_params_default_(&prm);
+    if (q.prm) prm = *q.prm;
+    if (!std::isfinite(prm.gate) || !std::isfinite(prm.min_cos2) || !std::isfinite(prm.mu) || !std::isfinite(prm.eps))
+        return fail(DH_EINVAL, "%s: gate %g, min_cos2 %g, mu %g, eps %g: a value is not finite", who, prm.gate, prm.min_cos2, prm.mu, prm.eps);
+    if (!(prm.gate > 0.0 && prm.gate <= DH_SHAPE_MAX_GATE)) return fail(DH_EINVAL, "%s: gate = %g outside (0, %g]", who, prm.gate, DH_SHAPE_MAX_GATE);
+    if (!(prm.min_cos2 >= 0.0 && prm.min_cos2 <= 1.0)) return fail(DH_EINVAL, "%s: min_cos2 = %g outside [0, 1]", who, prm.min_cos2);
+    if (!(prm.mu >= 0.0)) return fail(DH_EINVAL, "%s: mu = %g below 0", who, prm.mu);
+    if (!(prm.eps > 0.0)) return fail(DH_EINVAL, "%s: eps = %g, expected a value > 0", who, prm.eps);
+    if (prm.min_count < 1) return fail(DH_EINVAL, "%s: min_count 0 below 1", who);
+    if (prm.min_points < 1) return fail(DH_EINVAL, "%s: min_points 0 below 1", who);
+    if (prm.iterations > DH_SURFACE_MAX_ITERATIONS) return fail(DH_EINVAL, "%s: iterations = %u above %u", who, prm.iterations, DH_SURFACE_MAX_ITERATIONS);
+    if (prm.reserved0 || prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
+    if (q.n_inst > DH_SHAPE_MAX_TERMS) return fail(DH_EINVAL, "%s: too many instances", who);
+    const double largest = set->basis->largest;
+    if (dev) {
+        if ((uint64_t)q.n_inst * set->n > DH_SHAPE_MAX_TERMS)
+            return fail(DH_EINVAL, "%s: %u instances of %u points exceed %u terms", who, q.n_inst, set->n, DH_SHAPE_MAX_TERMS);
+    } else {
+        std::vector<uint32_t> per(q.n_subjects, 0);
+        for (uint32_t i = 0; i < q.n_inst; ++i) {
+            const uint32_t sj = q.subjects ? q.subjects[i] : 0u;
+            if (sj == DH_SHAPE_SKIP) continue;
+            if (q.fit_rec && q.fit_rec[i].status != DH_FIT_OK) continue;
+            if (sj >= q.n_subjects) return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, q.n_subjects);
+            const dh_render_instance &in = q.inst[i];
+            if (in.frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, q.n);
+            TRY(instance_refusal(dh_fit_instance_fault(in, set->radius, largest), in.scale, i, set->radius, largest, who));
+            if (!(fabs((double)in.scale) <= DH_SURFACE_MAX_SCALE))
+                return fail(DH_EINVAL, "%s: instance %u has |scale| = %g above %g", who, i, fabs((double)in.scale), DH_SURFACE_MAX_SCALE);
+            if ((uint64_t)(++per[sj]) * set->n > DH_SHAPE_MAX_TERMS)
+                return fail(DH_EINVAL, "%s: subject %u has more than %u terms (instances times %u points)", who, sj, DH_SHAPE_MAX_TERMS, set->n);
+        }
+    }
+
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(f->tab.init());
+    hipStream_t s = dev ? stream : f->tab.s;
+    SurfaceArgs g;
+    memset(&g, 0, sizeof g);
+    ShapeArgs &a = g.s;
+    a.n = q.n; a.w = q.w; a.h = q.h;
+    if (q.use_cams) a.cams = q.cams->dev.get();
+    else memcpy(a.k, q.K, sizeof a.k);
+    a.np = set->n; a.nk = set->basis->k;
+    a.radius = set->radius; a.largest = largest;
+    a.n_inst = q.n_inst; a.n_subjects = q.n_subjects;
+    a.min_points = prm.min_points; a.gate = prm.gate;
+    g.models = set->table.get();
+    g.nb = set->nb.get(); g.nbr_begin = set->nbr_begin.get(); g.nbr = set->nbr.get();
+    g.offsets = set->offsets.get(); g.rows = set->rows.get(); g.tally = set->tally.get(); g.scratch = set->scratch.get();
+    g.state = set->state.get();
+    g.min_cos2 = prm.min_cos2; g.mu = prm.mu; g.eps = prm.eps; g.max_offset = set->max_offset;
+    g.min_count = prm.min_count; g.iterations = prm.iterations;
+    g.fit_rec = q.fit_rec;
+    if (!dev) {
+        const size_t n_px = (size_t)q.n * q.w * q.h;
+        if (f->frames.cap() < n_px || f->shape_inst.cap() < q.n_inst) HIP_TRY(hipDeviceSynchronize());
+        TRY(f->frames.grow(n_px));
+        if (f->shape_inst.cap() < q.n_inst || !f->shape_inst) { TRY(f->shape_inst.grow(std::max<size_t>(q.n_inst, 1))); TRY(f->shape_subj.alloc(f->shape_inst.cap())); }
+        if (q.fit_rec && f->shape_fit_rec.cap() < f->shape_inst.cap()) {
+            HIP_TRY(hipDeviceSynchronize());
+            TRY(f->shape_fit_rec.alloc(f->shape_inst.cap()));
+        }
+        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        if (q.n_inst) HIP_TRY(hipMemcpyAsync(f->shape_inst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_render_instance), hipMemcpyHostToDevice, s));
+        if (q.n_inst && q.subjects) HIP_TRY(hipMemcpyAsync(f->shape_subj.get(), q.subjects, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (q.n_inst && q.fit_rec) {
+            HIP_TRY(hipMemcpyAsync(f->shape_fit_rec.get(), q.fit_rec, (size_t)q.n_inst * sizeof(dh_fit_record), hipMemcpyHostToDevice, s));
+            g.fit_rec = f->shape_fit_rec.get();
+        }
+        a.frames = f->frames.get(); a.inst = f->shape_inst.get(); a.subjects = q.subjects ? f->shape_subj.get() : nullptr;
+        g.rec = set->srec.get();
+    } else { a.frames = q.frames; a.inst = q.inst; a.subjects = q.subjects; g.rec = q.rec; }
+    // ---- the five stream-ordered operations
+    TRY(hip_step(dh_launch_surface_clear(g, s), "k_surface_clear"));
+    TRY(hip_step(dh_launch_surface_accumulate(g, s), "k_surface_accumulate"));
+    TRY(hip_step(dh_launch_surface_solve(g, s), "k_surface_solve"));
+    TRY(hip_step(dh_launch_subjects_update_surface(SurfacePointsArgs{subjects_args(set, nullptr, 0, q.n_subjects), set->nb.get(), set->offsets.get()}, false, s),
+                 "k_subjects_points_surface"));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(q.rec, g.rec, (size_t)q.n_subjects * sizeof(dh_surface_record), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return DH_OK;
+}
+static int fit_surface_subjects_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], dh_fit_subjects *set,
+                                 const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                                 const dh_fit_record *fit_records, const dh_surface_params *params, dh_surface_record *records) {
+    return surface_run(f, SurfaceReq{frames, n, w, h, K, nullptr, false, set, instances, n_instances, subjects, n_subjects, fit_records, params, records},
+                       false, nullptr, "dh_fit_surface_subjects");
+}
+static int fit_surface_subjects_cameras_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, dh_fit_subjects *set,
+                                         const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                                         const dh_fit_record *fit_records, const dh_surface_params *params, dh_surface_record *records) {
+    return surface_run(f, SurfaceReq{frames, n, w, h, nullptr, c, true, set, instances, n_instances, subjects, n_subjects, fit_records, params, records},
+                       false, nullptr, "dh_fit_surface_subjects_cameras");
+}
+static int fit_surface_subjects_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], dh_fit_subjects *set,
+                                        const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                                        const dh_fit_record *fit_records, const dh_surface_params *params, dh_surface_record *records, void *stream) {
+    return surface_run(f, SurfaceReq{frames, n, w, h, K, nullptr, false, set, instances, n_instances, subjects, n_subjects, fit_records, params, records},
+                       true, (hipStream_t)stream, "dh_fit_surface_subjects_device");
+}
+static int fit_surface_subjects_cameras_device_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, dh_fit_subjects *set,
+                                                const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                                                const dh_fit_record *fit_records, const dh_surface_params *params, dh_surface_record *records, void *stream) {
+    return surface_run(f, SurfaceReq{frames, n, w, h, nullptr, c, true, set, instances, n_instances, subjects, n_subjects, fit_records, params, records},
+                       true, (hipStream_t)stream, "dh_fit_surface_subjects_cameras_device");
 }
 
 // ------------------------------------------------------------------ adapting a model's shape across views
@@ -4441,6 +4673,14 @@ DH_API(fit_subjects_state, (dh_fit_subjects *s, dh_subject_state *state), (s, st
 DH_API(fit_subjects_read, (dh_fit_subjects *s, uint32_t subject, float *points, float *normals), (s, subject, points, normals))
 DH_API(fit_subjects_update, (dh_fit_subjects *s, const dh_shape_record *records), (s, records))
 DH_API(fit_subjects_update_device, (dh_fit_subjects *s, const dh_shape_record *records, void *stream), (s, records, stream))
+DH_API(fit_subjects_create_surface, (const float *verts, uint32_t n, const uint32_t *tris, uint32_t n_tris, const dh_fit_basis *basis, uint32_t n_subjects, double max_coeff, double max_offset, int device, dh_fit_subjects **out), (verts, n, tris, n_tris, basis, n_subjects, max_coeff, max_offset, device, out))
+DH_API(fit_subjects_set_offsets, (dh_fit_subjects *s, uint32_t subject, const double *offsets), (s, subject, offsets))
+DH_API(fit_subjects_read_offsets, (dh_fit_subjects *s, uint32_t subject, double *offsets, uint32_t *counts), (s, subject, offsets, counts))
+DH_API(fit_surface_params_default, (dh_surface_params *p), (p))
+DH_API(fit_surface_subjects, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_surface_params *params, dh_surface_record *records), (f, frames, n, w, h, K, set, instances, n_instances, subjects, n_subjects, fit_records, params, records))
+DH_API(fit_surface_subjects_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_surface_params *params, dh_surface_record *records), (f, frames, n, w, h, c, set, instances, n_instances, subjects, n_subjects, fit_records, params, records))
+DH_API(fit_surface_subjects_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_surface_params *params, dh_surface_record *records, void *stream), (f, frames, n, w, h, K, set, instances, n_instances, subjects, n_subjects, fit_records, params, records, stream))
+DH_API(fit_surface_subjects_cameras_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_surface_params *params, dh_surface_record *records, void *stream), (f, frames, n, w, h, c, set, instances, n_instances, subjects, n_subjects, fit_records, params, records, stream))
 DH_API(fit_shape_subjects, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records), (f, frames, n, w, h, K, set, instances, n_instances, subjects, n_subjects, fit_records, params, records))
 DH_API(fit_shape_subjects_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records), (f, frames, n, w, h, c, set, instances, n_instances, subjects, n_subjects, fit_records, params, records))
 DH_API(fit_shape_subjects_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n, w, h, K, set, instances, n_instances, subjects, n_subjects, fit_records, params, records, stream))

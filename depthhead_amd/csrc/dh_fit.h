@@ -1,5 +1,5 @@
 // dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip,
-// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
+// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
 // words of both trackers, and the one test of whether an instance may be fitted (dh_fit_instance_fault: the host's refusals and
 // the shape kernel's skips).  The device arithmetic the kernels share among themselves is in dh_fit_device.h.  Not part of the
 // ABI.  The rules are stated in include/depthhead_hip.h (sections "fitting posed models to depth frames" and after) and
@@ -404,6 +404,7 @@ hipError_t dh_launch_rig_fit_seed(const RigFitArgs &a, hipStream_t s);
 hipError_t dh_launch_rig_fit_update(const RigFitArgs &a, hipStream_t s);
 
 // ---- a shape per subject (k_subjects.hip)
+#define DH_SUBJECTS_THREADS 256         // the points and normals kernels of a set (k_subjects.hip, k_surface.hip): one lane per vertex
 static_assert(sizeof(dh_subject_state) == 80, "dh_subject_state: 80 bytes");
 // Magnitudes.  A model of a set is v'_i = fl32(v_i + sum_k c_k B_k[i]) with |c_k| <= max_coeff (the clamp of the update and the
 // refusal of dh_fit_subjects_set_coeffs: no other path writes a coefficient), so |v'_i| <= |v_i| + K max_coeff max |B_k[i]| <= the
@@ -491,3 +492,113 @@ hipError_t dh_launch_shape_accumulate_subjects(const ShapeSubjectsArgs &a, hipSt
 // k_fit_carry: the R and t of a fit call's uploaded instances replaced by those of `carried` (device, [n_inst]) where they are
 // finite and within DH_FIT_R_TOLERANCE of a rotation.
 hipError_t dh_launch_fit_carry(dh_render_instance *inst, const dh_render_instance *carried, uint32_t n_inst, hipStream_t s);
+
+// ---- a surface per subject (k_surface.hip)
+static_assert(sizeof(dh_surface_params) == 64, "dh_surface_params: 64 bytes");
+static_assert(sizeof(dh_surface_record) == 40, "dh_surface_record: 40 bytes");
+// Magnitudes.  A model of a surface set is v'_i = fl32((v_i + sum_k c_k B_k[i]) + o_i nb_i) with |o_i| <= max_offset (the clamp of
+// the solve and the refusal of dh_fit_subjects_set_offsets: no other path writes an offset) and |nb_i| <= 1 + 1e-7 <= 1.01 (the
+// base normals are normals of section 25), so |v'_i| <= section 25's bound + 1.01 max_offset, up to three more f64 roundings
+// (3 * 2^-52 relative) that the same margin absorbs: the extent test with this bound keeps sections 18 - 25 closed.
+// The sums of a vertex, S = 2^20.  sb = nb * scale has |sb| <= 1.01 |scale|, w = R sb has |w| <= 1.03 * 1.01 |scale|, and with
+// |nrm| <= 1.05, |J| <= 1.05 * 1.0403 |scale| < 1.1 |scale|.  |scale| is not bounded by the extent test alone (a small model may
+// carry a large scale), so an instance takes part only while |scale| <= DH_SURFACE_MAX_SCALE = 64: |J| < 70.4.  The gate lies in
+// (0, 256], so while |p| <= 2 p.z, |res| < 538 (section 20).  J J < 4957 < 2^12.3, J res < 37876 < 2^15.3; times 2^20, times the
+// instances that can add to ONE vertex's words -- one term per instance, and a call has at most DH_SHAPE_MAX_TERMS = 2^23
+// instances -- below 2^58.3 < 2^63.  The subject's e is section 20's word: res res < 2^18.2, times 2^20, times at most 2^23
+// (instance, point) terms of one subject (the host forms count them per subject, the _device forms bound the call by
+// n_instances * n): below 2^61.2.  cnt, points and instances count terms: below 2^23.
+static_assert(DH_SURFACE_MAX_SCALE <= 64.0 && DH_SHAPE_MAX_GATE <= 256.0 && DH_SHAPE_MAX_TERMS <= 8388608u, "the magnitude argument above");
+#define DH_SURFACE_NB_BOUND 1.01
+#define DH_SURFACE_THREADS 256          // accumulate: one workgroup per instance
+#define DH_SURFACE_SOLVE_THREADS 512    // solve: one workgroup per subject
+// The words of a vertex's row, and of a subject's tally.  The solve reuses words A and B of a row for the two values of the
+// vertex that no sweep changes (the numerator's constant part and the denominator), as f64 bit patterns: the sums are spent by then.
+#define DH_SURFACE_A 0
+#define DH_SURFACE_B 1
+#define DH_SURFACE_CNT 2
+#define DH_SURFACE_ROW 3
+#define DH_SURFACE_E 0
+#define DH_SURFACE_POINTS 1
+#define DH_SURFACE_USED 2
+#define DH_SURFACE_TALLY 4
+// The solve keeps u and u' in LDS while two f64 arrays of n fit beside its 2 KB of counters in the 160 KB a workgroup may have on
+// gfx950: 16 n <= 163840 - 2048.  Above that they lie in the set's scratch.
+#define DH_SURFACE_LDS_POINTS 10112u
+static_assert(16u * DH_SURFACE_LDS_POINTS + 2048u <= 163840u, "two f64 arrays and the counters in 160 KB");
+
+// The set's bound on |v'| with offsets: section 25's bound + max_offset * 1.01.
+inline double dh_surface_radius_bound(double base_radius, uint32_t n_fields, double max_coeff, double largest, double max_offset) {
+    return dh_subjects_radius_bound(base_radius, n_fields, max_coeff, largest) + max_offset * DH_SURFACE_NB_BOUND;
+}
+// Each vertex's neighbours -- the unique vertices other than itself that share an edge of a triangle with it -- ascending, in CSR
+// form: begin [n + 1] and list [begin[n]], at most 6 n_tris entries (`list` must hold that many).  Every triangle gives each of
+// its corners the other two; a vertex's run is sorted and its duplicates and the vertex itself are dropped.  false: an index >= n,
+// *bad_tri names the first triangle that holds one.  `work` is scratch of 6 n_tris words.
+inline bool dh_subjects_neighbour_lists(const uint32_t *tris, uint32_t n_tris, uint32_t n, uint32_t *begin, uint32_t *list, uint32_t *work,
+                                        uint32_t *bad_tri) {
+    for (uint32_t i = 0; i <= n; ++i) begin[i] = 0;
+    for (uint32_t t = 0; t < n_tris; ++t)
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t v = tris[(size_t)t * 3 + c];
+            if (v >= n) { if (bad_tri) *bad_tri = t; return false; }
+            begin[v + 1] += 2;
+        }
+    for (uint32_t i = 0; i < n; ++i) begin[i + 1] += begin[i];
+    for (uint32_t t = 0; t < n_tris; ++t)                                          // work: every vertex's raw run, begin[v] moving to its end
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t v = tris[(size_t)t * 3 + c];
+            work[begin[v]++] = tris[(size_t)t * 3 + (c + 1) % 3];
+            work[begin[v]++] = tris[(size_t)t * 3 + (c + 2) % 3];
+        }
+    uint32_t out = 0, from = 0;
+    for (uint32_t v = 0; v < n; ++v) {
+        const uint32_t to = begin[v];                                              // the raw run is work[from .. to)
+        for (uint32_t a = from + 1; a < to; ++a) {                                 // insertion sort: runs are short
+            const uint32_t x = work[a];
+            uint32_t b = a;
+            for (; b > from && work[b - 1] > x; --b) work[b] = work[b - 1];
+            work[b] = x;
+        }
+        begin[v] = out;
+        for (uint32_t a = from; a < to; ++a)
+            if (work[a] != v && (a == from || work[a] != work[a - 1])) list[out++] = work[a];
+        from = to;
+    }
+    begin[n] = out;
+    return true;
+}
+
+// k_subjects_points_surface: k_subjects_points' tree, then the offset along the base normal.
+struct SurfacePointsArgs {
+    SubjectsArgs a;
+    const float *nb;              // [n][3] the base normals
+    const double *offsets;        // [S][n]
+};
+struct SurfaceArgs {
+    ShapeArgs s;                  // pts, nrm, basis, nk, lam1, sums and rec unused; np: the set's n; radius: the set's bound
+    const SubjectModel *models;   // [S] (n_subjects <= S)
+    const dh_fit_record *fit_rec; // nullable [n_inst]
+    const float *nb;              // [n][3]
+    const uint32_t *nbr_begin;    // [n + 1]
+    const uint32_t *nbr;          // [nbr_begin[n]]
+    double *offsets;              // [S][n]
+    unsigned long long *rows;     // [S][n][DH_SURFACE_ROW]
+    unsigned long long *tally;    // [S][DH_SURFACE_TALLY]
+    double *scratch;              // [S][2][n]: u and u' of a model above DH_SURFACE_LDS_POINTS
+    dh_subject_state *state;      // [S]: zero_normals back to 0 for the normals pass
+    dh_surface_record *rec;       // [n_subjects]
+    double min_cos2, mu, eps, max_offset;
+    uint32_t min_count, iterations;
+};
+hipError_t dh_launch_surface_clear(const SurfaceArgs &a, hipStream_t s);       // the rows and tallies of subjects 0 .. n_subjects - 1
+hipError_t dh_launch_surface_accumulate(const SurfaceArgs &a, hipStream_t s);  // one workgroup per instance
+hipError_t dh_launch_surface_solve(const SurfaceArgs &a, hipStream_t s);       // one workgroup per subject
+// Once per set, at its creation on the set's device: lets k_surface_solve take the dynamic LDS a model of n vertices needs, so that
+// a step is its five launches and no other runtime call.
+hipError_t dh_surface_solve_prepare(uint32_t n);
+// k_subjects_apply where rec is given, then k_subjects_points_surface and k_subjects_normals, for subjects a.a.first .. + a.a.count - 1
+hipError_t dh_launch_subjects_update_surface(const SurfacePointsArgs &a, bool apply, hipStream_t s);
+// (k_subjects.hip) its kernels one by one, for the evaluation of a surface set
+hipError_t dh_launch_subjects_apply(const SubjectsArgs &a, hipStream_t s);
+hipError_t dh_launch_subjects_normals(const SubjectsArgs &a, hipStream_t s);

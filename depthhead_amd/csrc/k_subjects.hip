@@ -23,8 +23,6 @@
 
 #pragma clang fp contract(off)
 
-#define DH_SUBJECTS_THREADS 256
-
 __global__ __launch_bounds__(64) void k_subjects_apply(const SubjectsArgs a) {
     const uint32_t sj = a.first + blockIdx.x * 64 + threadIdx.x;
     if (sj >= a.first + a.count) return;
@@ -145,6 +143,18 @@ hipError_t dh_launch_subjects_update(const SubjectsArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_subjects_apply, dim3((a.count + 63) / 64), dim3(64), 0, s, a);
     const dim3 grid((a.n + DH_SUBJECTS_THREADS - 1) / DH_SUBJECTS_THREADS, a.count);
     hipLaunchKernelGGL(k_subjects_points, grid, dim3(DH_SUBJECTS_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k_subjects_normals, grid, dim3(DH_SUBJECTS_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+// The same kernels one by one: a surface set (k_surface.hip) evaluates its points with a kernel of its own between them.
+hipError_t dh_launch_subjects_apply(const SubjectsArgs &a, hipStream_t s) {
+    if (a.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_subjects_apply, dim3((a.count + 63) / 64), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t dh_launch_subjects_normals(const SubjectsArgs &a, hipStream_t s) {
+    if (a.count == 0) return hipSuccess;
+    const dim3 grid((a.n + DH_SUBJECTS_THREADS - 1) / DH_SUBJECTS_THREADS, a.count);
     hipLaunchKernelGGL(k_subjects_normals, grid, dim3(DH_SUBJECTS_THREADS), 0, s, a);
     return hipGetLastError();
 }

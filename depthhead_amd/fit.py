@@ -10,7 +10,8 @@ import numpy as np
 from . import _lib
 from ._lib import (CALIB_RECORD_DTYPE, CALIB_SKIP, FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, FIT_VIEW_TOLERANCE, HEAD_DTYPE,
                    MAX_HEADS, POSE_DTYPE, RIG_FIT_RECORD_DTYPE, RIG_FIT_STATE_DTYPE, RIG_MAX_PERSONS, RIG_MAX_TRACKS, RIG_PERSON_DTYPE,
-                   RIG_TRACK_DTYPE, RENDER_INSTANCE_DTYPE, SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUBJECT_STATE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, VIEW_FIT_RECORD_DTYPE,
+                   RIG_TRACK_DTYPE, RENDER_INSTANCE_DTYPE, SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUBJECT_STATE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, SURFACE_RECORD_DTYPE,
+                   VIEW_FIT_RECORD_DTYPE,
                    VIEW_INSTANCE_DTYPE, check, vp)
 from .render import euler_to_matrix
 
@@ -22,6 +23,7 @@ FIT_TRACK_MOTION = 1                                # DH_FIT_TRACK_MOTION
 SHAPE_OK, SHAPE_FEW_POINTS, SHAPE_SINGULAR = 0, 1, 2  # dh_shape_record.status
 CALIB_OK, CALIB_FEW_POINTS, CALIB_SINGULAR, CALIB_NOT_ORTHONORMAL, CALIB_HELD = 0, 1, 2, 3, 4  # dh_calib_record.status
 SUBJECT_CLAMPED, SUBJECT_NONFINITE = 1, 2            # dh_subject_state.flags
+SURFACE_OK, SURFACE_FEW_POINTS = 0, 1                # dh_surface_record.status
 
 
 def vertex_normals(verts, tris) -> np.ndarray:
@@ -185,6 +187,17 @@ def shape_params(gate=None, lam=None, min_points=None) -> "_lib.ShapeParams":
         p.lam = float(lam)
     if min_points is not None:
         p.min_points = int(min_points)
+    return p
+
+
+def surface_params(gate=None, min_cos2=None, mu=None, eps=None, min_count=None, min_points=None, iterations=None) -> "_lib.SurfaceParams":
+    """dh_fit_surface_params_default with the given fields replaced."""
+    p = _lib.SurfaceParams()
+    check(_lib.load().dh_fit_surface_params_default(C.byref(p)))
+    for name, value, cast in (("gate", gate, float), ("min_cos2", min_cos2, float), ("mu", mu, float), ("eps", eps, float),
+                              ("min_count", min_count, int), ("min_points", min_points, int), ("iterations", iterations, int)):
+        if value is not None:
+            setattr(p, name, cast(value))
     return p
 
 
@@ -419,6 +432,48 @@ class Fitter(_lib._Handle):
             C.c_void_p(fit_records.data_ptr()) if fit_records is not None else None, prm, C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
         return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
 
+    def surface_step_subjects(self, frames, subjects_set, instances, K_or_cameras, subjects=None, n_subjects=None, fit_records=None, params=None,
+                              device_out: bool = False, stream=None):
+        """One surface step over a `Subjects` set made with max_offset: every offset of subjects
+        0 .. n_subjects - 1 re-estimated from the fitted `instances`, and their models evaluated.  The arguments are
+        `shape_step_subjects`'s.  Host form: numpy arrays -> SURFACE_RECORD_DTYPE [n_subjects].  With device_out=True frames,
+        instances, subjects and fit_records are torch tensors on the device and the records come back as a uint8 torch tensor:
+        five kernels ordered on `stream`, no host wait."""
+        n, h, w = (int(v) for v in frames.shape)
+        cams = getattr(K_or_cameras, "_h", None)
+        if cams is None:
+            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
+            kind, karg = "", vp(K)
+        else:
+            kind, karg = "_cameras", cams
+        prm = C.byref(params) if params is not None else None
+        ns = len(subjects_set) if n_subjects is None else int(n_subjects)
+        if not device_out:
+            fr = np.ascontiguousarray(frames, dtype=np.uint16)
+            inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
+            subj = None if subjects is None else np.ascontiguousarray(subjects, dtype=np.uint32).reshape(len(inst))
+            frec = None if fit_records is None else np.ascontiguousarray(fit_records, dtype=FIT_RECORD_DTYPE).reshape(len(inst))
+            rec = np.zeros(max(ns, 0), SURFACE_RECORD_DTYPE)
+            check(getattr(self._lib, "dh_fit_surface_subjects" + kind)(self._h, vp(fr), n, w, h, karg, subjects_set._h, vp(inst) if len(inst) else None,
+                                                                        C.c_uint32(len(inst)), vp(subj), C.c_uint32(ns), vp(frec), prm, vp(rec)))
+            return rec
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
+            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
+        ni = instances.numel() * instances.element_size() // RENDER_INSTANCE_DTYPE.itemsize
+        if subjects is not None and (subjects.numel() != ni or subjects.element_size() != 4 or not subjects.is_contiguous()):
+            raise ValueError("device subjects: a contiguous 32-bit tensor with one word per instance is expected")
+        if fit_records is not None and (fit_records.numel() * fit_records.element_size() != ni * FIT_RECORD_DTYPE.itemsize or not fit_records.is_contiguous()):
+            raise ValueError("device fit_records: the contiguous tensor of one dh_fit_record per instance is expected")
+        rec = torch.empty(max(ns, 1) * SURFACE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        check(getattr(self._lib, "dh_fit_surface_subjects" + kind + "_device")(
+            self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, subjects_set._h, C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
+            C.c_void_p(subjects.data_ptr()) if subjects is not None else None, C.c_uint32(ns),
+            C.c_void_p(fit_records.data_ptr()) if fit_records is not None else None, prm, C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
+        return rec[:ns * SURFACE_RECORD_DTYPE.itemsize]
+
     def shape_step_views(self, frames, views, model, basis, instances, sets=None, subjects=None, n_subjects: int = 1, params=None,
                          device_out: bool = False, stream=None):
         """One multi-view shape step of `model` and its `basis` over the world-posed `instances`
@@ -550,14 +605,22 @@ class Subjects(_lib._Handle):
     follow the subject's coefficients with every `update`."""
     _handles = (("_h", "dh_fit_subjects_destroy"),)
 
-    def __init__(self, verts, tris, basis, n_subjects: int, max_coeff: float = 0.5, device: int = 0):
+    def __init__(self, verts, tris, basis, n_subjects: int, max_coeff: float = 0.5, device: int = 0, max_offset=None):
+        """max_offset (mm; None: none): a SURFACE set, which also holds one offset per (subject, vertex)
+        along the base mesh's vertex normal, each kept within +-max_offset, for `Fitter.surface_step_subjects`."""
         self._lib = _lib.load()
         self.verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
         self.tris = np.ascontiguousarray(tris, dtype=np.uint32).reshape(-1, 3)
         self.basis, self.device, self.n_subjects, self.max_coeff = basis, int(device), int(n_subjects), float(max_coeff)
+        self.max_offset = None if max_offset is None else float(max_offset)
         self._h = C.c_void_p()
-        check(self._lib.dh_fit_subjects_create(vp(self.verts), C.c_uint32(len(self.verts)), vp(self.tris), C.c_uint32(len(self.tris)), basis._h,
-                                               C.c_uint32(self.n_subjects), C.c_double(self.max_coeff), self.device, C.byref(self._h)))
+        if self.max_offset is None:
+            check(self._lib.dh_fit_subjects_create(vp(self.verts), C.c_uint32(len(self.verts)), vp(self.tris), C.c_uint32(len(self.tris)), basis._h,
+                                                   C.c_uint32(self.n_subjects), C.c_double(self.max_coeff), self.device, C.byref(self._h)))
+        else:
+            check(self._lib.dh_fit_subjects_create_surface(vp(self.verts), C.c_uint32(len(self.verts)), vp(self.tris), C.c_uint32(len(self.tris)),
+                                                           basis._h, C.c_uint32(self.n_subjects), C.c_double(self.max_coeff),
+                                                           C.c_double(self.max_offset), self.device, C.byref(self._h)))
         self.models = []
         for s in range(self.n_subjects):
             h = C.c_void_p()
@@ -597,6 +660,20 @@ class Subjects(_lib._Handle):
         full = np.zeros((len(c), 8), np.float64)
         full[:, :c.shape[1]] = c
         check(self._lib.dh_fit_subjects_set_coeffs(self._h, C.c_uint32(int(first)), C.c_uint32(len(full)), vp(full)))
+
+    def offsets(self, subject: int, counts: bool = False):
+        """Synchronous copy of subject `subject`'s offsets [n] f64 (a surface set); with counts=True (offsets, counts [n] u32): how
+        often the last surface step saw each vertex."""
+        o, c = np.zeros(len(self.verts), np.float64), np.zeros(len(self.verts), np.uint32)
+        check(self._lib.dh_fit_subjects_read_offsets(self._h, C.c_uint32(int(subject)), vp(o), vp(c) if counts else None))
+        return (o, c) if counts else o
+
+    def set_offsets(self, subject: int, offsets) -> None:
+        """Set subject `subject`'s offsets [n] (mm, each within +-max_offset) and evaluate its model; synchronous."""
+        o = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+        if len(o) != len(self.verts):
+            raise ValueError("one offset per vertex is expected")
+        check(self._lib.dh_fit_subjects_set_offsets(self._h, C.c_uint32(int(subject)), vp(o)))
 
     def update(self, records, device: bool = False, stream=None) -> None:
         """Apply one shape record per subject (SHAPE_RECORD_DTYPE [S], what shape_step_subjects returned) and evaluate every
@@ -640,6 +717,38 @@ def adapt_subjects(fitter, frames, K_or_cameras, subjects, starts, subject_of, r
         return subjects.state(), inst, (np.zeros(len(inst), FIT_RECORD_DTYPE), np.zeros(len(subjects), SHAPE_RECORD_DTYPE))
     out = d_inst.cpu().numpy().view(RENDER_INSTANCE_DTYPE).copy()
     return subjects.state(), out, (d_frec.cpu().numpy().view(FIT_RECORD_DTYPE).copy(), d_srec.cpu().numpy().view(SHAPE_RECORD_DTYPE).copy())
+
+
+def refine_subjects(fitter, frames, K_or_cameras, subjects, starts, subject_of, rounds: int = 6, shape_rounds: int = 0, fit_prm=None,
+                    shape_prm=None, surface_prm=None):
+    """Refine every subject of a surface `Subjects` set per vertex, on the device.  frames [n, h, w] u16
+    (numpy) go to the device once; `starts` and subject_of are `adapt_subjects`'s.  Every round is one fit of all instances from
+    the previous round's poses (`carried`); in the first `shape_rounds` rounds one shape step over the set and its update; then
+    one surface step -- all enqueued on the current torch stream, nothing read inside the loop and once at the end.  Offsets
+    and coefficients are refined in place, from where they stand.  Returns (state SUBJECT_STATE_DTYPE [S], the last fitted
+    instances, the FIT_RECORD_DTYPE and SURFACE_RECORD_DTYPE records of the last round)."""
+    import torch
+    dev = torch.device("cuda", fitter.device)
+    inst = np.array(starts, dtype=RENDER_INSTANCE_DTYPE)
+    who = np.ascontiguousarray(subject_of, dtype=np.uint32).reshape(len(inst))
+    inst["mesh"] = who
+    host = np.ascontiguousarray(frames, dtype=np.uint16)
+    d_frames = torch.from_numpy((host if host.flags.writeable else host.copy()).view(np.int16)).to(dev)
+    d_who = torch.from_numpy(who.view(np.int32)).to(dev)
+    d_inst = d_frec = d_urec = None
+    for r in range(int(rounds)):
+        d_inst, d_frec = fitter.fit(d_frames, subjects.models, inst, K_or_cameras, params=fit_prm, device_out=True, carried=d_inst)
+        if r < int(shape_rounds):
+            d_srec = fitter.shape_step_subjects(d_frames, subjects, d_inst, K_or_cameras, subjects=d_who, fit_records=d_frec, params=shape_prm,
+                                                device_out=True)
+            subjects.update(d_srec, device=True)
+        d_urec = fitter.surface_step_subjects(d_frames, subjects, d_inst, K_or_cameras, subjects=d_who, fit_records=d_frec, params=surface_prm,
+                                              device_out=True)
+    torch.cuda.current_stream(dev).synchronize()
+    if d_inst is None:
+        return subjects.state(), inst, (np.zeros(len(inst), FIT_RECORD_DTYPE), np.zeros(len(subjects), SURFACE_RECORD_DTYPE))
+    out = d_inst.cpu().numpy().view(RENDER_INSTANCE_DTYPE).copy()
+    return subjects.state(), out, (d_frec.cpu().numpy().view(FIT_RECORD_DTYPE).copy(), d_urec.cpu().numpy().view(SURFACE_RECORD_DTYPE).copy())
 
 
 def adapt_views(fitter, frames, views, verts, tris, basis, starts, sets=None, rounds: int = 6, fit_prm=None, shape_prm=None, coeffs=None):

@@ -1364,6 +1364,122 @@ int dh_fit_shape_subjects_cameras_device(dh_fitter *f, const uint16_t *frames, i
                                          const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records,
                                          const dh_shape_params *params, dh_shape_record *records, void *stream);
 
+/* ---- a surface per subject ----
+ * A basis of at most 8 fields cannot express a cheekbone, a brow or a jaw: whatever it does not span stays in the fit's residual.
+ * A SURFACE SET is a dh_fit_subjects that holds, besides section 25's coefficients, one scalar offset o[s][i] (mm, f64) per subject
+ * and vertex ALONG THE BASE MESH'S VERTEX NORMAL, and the SURFACE STEP re-estimates all offsets of all subjects from fitted frames
+ * on the device.  Not in the reference: PARITY UNPINNED, the definition below is this library's.  Arithmetic: f64 with + - * /,
+ * compares and casts; every operation rounded on its own; the sums are int64 (their order is free); no floating-point atomic.
+ * THE SET.  dh_fit_subjects_create_surface is dh_fit_subjects_create with one more argument, max_offset.  Besides what section 25
+ *   holds, the set holds (all allocated at creation, nothing later): the base normals nb_i -- THE NORMALS of section 25 of the base
+ *   vertices themselves (what fit.vertex_normals computes), as f32; each vertex's NEIGHBOUR LIST -- the unique vertices j != i
+ *   that share an edge of a triangle with i, ascending; deg_i is its length; the offsets, all +0.0 at first; the step's sums, three
+ *   u64 words per (subject, vertex), and four per subject (three used); two f64 per (subject, vertex) of scratch; one dh_surface_record per
+ *   subject.  A set made by dh_fit_subjects_create is unchanged in every respect and every surface call refuses it.
+ *   The set's bound grows:  bound = (radius(base) + (K * max_coeff) * largest) + max_offset * 1.01, 1.01 bounding |nb| (section 25
+ *   derives |nrm| <= 1 + 1e-7).  No offset the device can reach leaves [-max_offset, max_offset], so the argument of section 25
+ *   holds with this bound.
+ * POINTS of a surface set, always from the base:  section 25's POINTS tree x (the fields for k ascending), then
+ *   x[j] = x[j] + o_i * (f64)nb_i[j] for j = 0, 1, 2;  v'_i = (f32)x, rounded once.  NORMALS are section 25's, from v'.
+ *   dh_fit_subjects_update, _update_device and _set_coeffs on a surface set evaluate the points so (k_subjects_points_surface in
+ *   place of k_subjects_points; ordinary sets run the kernel they ran).
+ * THE SURFACE STEP, over frames, K or cameras, instances, subjects[], n_subjects and fit_records exactly as dh_fit_shape_subjects*
+ *   takes them; an instance takes part by that call's rule (its subject < n_subjects, its fit record DH_FIT_OK where records are
+ *   given, none of the per-instance refusals) and, in addition, only while |scale| <= DH_SURFACE_MAX_SCALE.
+ *   ACCUMULATE.  For every instance that takes part and every point i of its subject's model: p, nrm, c, the pixel, d and
+ *     res = c * (d / p.z - 1) are the fit's one pass (section 18) at the instance's pose with gate `gate`; the point is kept only
+ *     if it passes that and  c * c >= min_cos2 * ((p0 * p0 + p1 * p1) + p2 * p2)  (a grazing point carries a bad normal).  Then
+ *     sb = (f64)nb_i * scale (per component),  w_r = (R[r][0] * sb0 + R[r][1] * sb1) + R[r][2] * sb2,
+ *     J = (nrm0 * w0 + nrm1 * w1) + nrm2 * w2,  and with S = 2^20:
+ *       a[s][i] += (int64)((J * J) * S);   b[s][i] += (int64)((J * res) * S);   cnt[s][i] += 1;
+ *     and per subject  e += (int64)((res * res) * S), points += 1, and instances += 1 for every instance that kept a point.
+ *     The sign is section 20's: a positive solution moves the model point along its normal toward the measurement.
+ *     Magnitudes: |nb| <= 1.01, |R x| <= 1.03 |x| and |nrm| <= 1.05 give |J| <= 1.05 * 1.03 * 1.01 |scale| < 1.1 |scale| <= 70.4;
+ *     the gate lies in (0, DH_SHAPE_MAX_GATE], so |res| < 538 while |p| <= 2 p.z (section 20): J J < 2^12.3, J res < 2^15.3, times
+ *     2^20, times at most DH_SHAPE_MAX_TERMS = 2^23 instances into one vertex's words: below 2^59; e is section 20's word with its
+ *     limit of 2^23 (instance, point) terms of one subject.  Outside |p| <= 2 p.z the words of section 20 hold.
+ *   SOLVE, per subject s < n_subjects.  points < min_points: DH_SURFACE_FEW_POINTS, the offsets stay as they were.  Otherwise, per
+ *     vertex:  A_i = (f64)(int64)a_i / S and B_i = (f64)(int64)b_i / S where cnt_i >= min_count, both +0.0 elsewhere;
+ *     u = o; then exactly `iterations` JACOBI sweeps, every u' from the u of the sweep before:
+ *       u'_i = ((A_i * o_i + B_i) + mu * s_i) / ((A_i + mu * (f64)deg_i) + eps),   s_i = +0.0, then s_i = s_i + u_j for every j of
+ *       i's neighbour list in list order.
+ *     It descends  sum_i A_i (u_i - o_i - B_i / A_i)^2 + mu * sum_edges (u_i - u_j)^2 + eps * sum_i u_i^2:  a vertex never seen is
+ *     filled from its neighbours and decays to 0; the denominator is positive since eps > 0.  After the sweeps, per vertex: a u_i
+ *     that is not finite keeps o_i and is counted (rejected); else u_i > max_offset becomes max_offset, u_i < -max_offset becomes
+ *     -max_offset, each counted (clamped); o_i = u_i.  With iterations = 0, u = o.
+ *   One dh_surface_record per subject: status; points; instances; observed = the vertices with cnt_i >= min_count; clamped;
+ *     rejected; sum_r2_fixed = e; max_abs = the largest |o_i| of the subject after the step.  With DH_SURFACE_FEW_POINTS observed,
+ *     clamped and rejected are 0 and max_abs is that of the offsets as they stand.
+ *   Then POINTS and NORMALS of subjects 0 .. n_subjects - 1 (zero_normals counted anew): the models are current when the call
+ *   returns (host forms) or when the stream reaches the end of the call (_device forms).
+ * dh_fit_subjects_create_surface -- DH_EINVAL as dh_fit_subjects_create and in its order, then: max_offset not finite or outside
+ *   (0, DH_SURFACE_MAX_OFFSET]; n_subjects * n above DH_SURFACE_MAX_CELLS (the sums are 24 bytes a cell: 100 MB at the limit).
+ * dh_fit_subjects_set_offsets (host, synchronous) sets subject `subject`'s offsets from offsets[n] (f64) and evaluates that subject.
+ *   DH_EINVAL, nothing changed: NULL set or offsets; a set without offsets; subject >= S; a value that is not finite or whose
+ *   magnitude exceeds max_offset.  dh_fit_subjects_read_offsets (host, synchronous) copies out subject `subject`'s offsets [n] f64
+ *   and the last step's cnt_i as counts [n] u32 (saturated; what the words hold: 0 after creation, stale for a subject the last
+ *   step did not name), each nullable.  DH_EINVAL: NULL set; a set without offsets; subject >= S.
+ * dh_fit_surface_subjects* -- DH_EINVAL, before anything is launched and with nothing written, in this order: NULL fitter, frames,
+ *   records, subject set; the frames' refusals of dh_fit_shape*; a set on another device than the fitter; a set without offsets;
+ *   n_subjects outside 1 .. S; a non-finite gate, min_cos2, mu or eps; a gate outside (0, DH_SHAPE_MAX_GATE]; min_cos2 outside
+ *   [0, 1]; mu < 0; eps not > 0; min_count 0; min_points 0; iterations above DH_SURFACE_MAX_ITERATIONS; a reserved word that is not
+ *   0; NULL instances with n_instances > 0; n_instances above DH_SHAPE_MAX_TERMS.  The host forms then refuse, per instance that
+ *   takes part, what dh_fit_shape_subjects refuses (with the set's bound), then |scale| above DH_SURFACE_MAX_SCALE, then a subject
+ *   whose instances times n exceed DH_SHAPE_MAX_TERMS.  The _device forms cannot read the instances: they refuse n_instances * n
+ *   above DH_SHAPE_MAX_TERMS and the device skips every instance one of the per-instance refusals names.  n_instances = 0 is no
+ *   error: every record is DH_SURFACE_FEW_POINTS.  params is host memory in both forms; NULL selects
+ *   dh_fit_surface_params_default.  The _device forms enqueue exactly five kernels on `stream` (NULL = default stream), no host
+ *   wait, no allocation: k_surface_clear, k_surface_accumulate, k_surface_solve, k_subjects_points_surface, k_subjects_normals.
+ *   A set serves one surface step at a time (the sums are the set's).  Bit-identical run to run and to tests/surface_ref.py. */
+#define DH_SURFACE_OK 0u
+#define DH_SURFACE_FEW_POINTS 1u         /* the subject's instances kept fewer than min_points points */
+#define DH_SURFACE_MAX_OFFSET 64.0       /* mm: the largest max_offset of a set */
+#define DH_SURFACE_MAX_SCALE 64.0        /* |scale| of an instance of a surface step */
+#define DH_SURFACE_MAX_CELLS 4194304u    /* 2^22: subjects times vertices of a surface set */
+#define DH_SURFACE_MAX_ITERATIONS 256u   /* Jacobi sweeps of a step */
+typedef struct dh_surface_params {
+    double   gate;                /* 25 (mm), in (0, DH_SHAPE_MAX_GATE] */
+    double   min_cos2;            /* 0.25: the squared cosine between normal and ray below which a point is dropped, in [0, 1] */
+    double   mu;                  /* 0.5: weight of the edge term, >= 0 */
+    double   eps;                 /* 0.05: weight of the offsets themselves, > 0 */
+    uint32_t min_count;           /* 2: a vertex seen fewer times has no data term */
+    uint32_t min_points;          /* 64: fewer kept points of a subject give DH_SURFACE_FEW_POINTS */
+    uint32_t iterations;          /* 32: Jacobi sweeps, at most DH_SURFACE_MAX_ITERATIONS */
+    uint32_t reserved0;           /* 0 */
+    uint64_t reserved[2];         /* 0 */
+} dh_surface_params;   /* 64 bytes */
+typedef struct dh_surface_record {
+    uint32_t status;              /* offset 0:  DH_SURFACE_* */
+    uint32_t points;              /* offset 4:  kept points of the subject's instances */
+    uint32_t instances;           /* offset 8:  instances that kept a point */
+    uint32_t observed;            /* offset 12: vertices with cnt >= min_count */
+    uint32_t clamped;             /* offset 16: offsets moved back to +-max_offset */
+    uint32_t rejected;            /* offset 20: solutions that were not finite */
+    int64_t  sum_r2_fixed;        /* offset 24: e */
+    double   max_abs;             /* offset 32: the largest |o_i| after the step */
+} dh_surface_record;   /* 40 bytes, no padding */
+int dh_fit_subjects_create_surface(const float *verts, uint32_t n, const uint32_t *tris, uint32_t n_tris, const dh_fit_basis *basis,
+                                   uint32_t n_subjects, double max_coeff, double max_offset, int device, dh_fit_subjects **out);
+int dh_fit_subjects_set_offsets(dh_fit_subjects *s, uint32_t subject, const double *offsets);
+int dh_fit_subjects_read_offsets(dh_fit_subjects *s, uint32_t subject, double *offsets, uint32_t *counts);
+int dh_fit_surface_params_default(dh_surface_params *p);
+/* frames [n][h][w] u16; instances [n_instances]; subjects [n_instances] or NULL; fit_records [n_instances] or NULL; records [n_subjects] */
+int dh_fit_surface_subjects(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], dh_fit_subjects *set,
+                            const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
+                            const dh_fit_record *fit_records, const dh_surface_params *params, dh_surface_record *records);
+int dh_fit_surface_subjects_cameras(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                    dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances,
+                                    const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records,
+                                    const dh_surface_params *params, dh_surface_record *records);
+int dh_fit_surface_subjects_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], dh_fit_subjects *set,
+                                   const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects,
+                                   uint32_t n_subjects, const dh_fit_record *fit_records, const dh_surface_params *params,
+                                   dh_surface_record *records, void *stream);
+int dh_fit_surface_subjects_cameras_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                           dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances,
+                                           const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records,
+                                           const dh_surface_params *params, dh_surface_record *records, void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
