@@ -127,6 +127,22 @@ class SurfaceParams(C.Structure):
                 ("min_points", C.c_uint32), ("iterations", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 2)]
 
 
+# dh_ident_record: what identification reports for one fitted instance (dh_fit_identify_subjects*)
+IDENT_RECORD_DTYPE = np.dtype([("status", "<u4"), ("best", "<u4"), ("second", "<u4"), ("eligible", "<u4"), ("points_best", "<u4"),
+                               ("points_second", "<u4"), ("sum_r2_best", "<i8"), ("sum_r2_second", "<i8")], align=True)
+assert IDENT_RECORD_DTYPE.itemsize == 40
+IDENT_OK, IDENT_SKIPPED, IDENT_NO_CANDIDATE, IDENT_FAR, IDENT_AMBIGUOUS = 0, 1, 2, 3, 4   # DH_IDENT_*
+IDENT_UNKNOWN = 0xFFFFFFFF         # DH_IDENT_UNKNOWN (== DH_SHAPE_SKIP)
+IDENT_MAX_PAIRS = 1 << 22          # DH_IDENT_MAX_PAIRS
+IDENT_DEFAULT_MAX_RMS = 1.68       # DH_IDENT_DEFAULT_MAX_RMS (mm)
+
+
+class IdentParams(C.Structure):
+    """dh_ident_params (`lam` is the header's `lambda`)"""
+    _fields_ = [("iterations", C.c_uint32), ("min_points", C.c_uint32), ("gate", C.c_double), ("lam", C.c_double), ("max_rms", C.c_double),
+                ("min_ratio", C.c_double), ("reserved", C.c_uint64 * 3)]
+
+
 # dh_view_instance / dh_view_fit_record: one world-posed model seen by several cameras, and what its fit reports (dh_fit_depth_views*)
 VIEW_INSTANCE_DTYPE = np.dtype([("first_cam", "<u4"), ("model", "<u4"), ("views", "<u8"), ("R", "<f4", (9,)), ("t", "<f4", (3,)),
                                 ("scale", "<f4"), ("flags", "<u4")], align=True)
@@ -245,6 +261,8 @@ EXPORTS = [
     "dh_fit_depth_cameras_carried_device",
     "dh_fit_subjects_create_surface", "dh_fit_subjects_set_offsets", "dh_fit_subjects_read_offsets", "dh_fit_surface_params_default",
     "dh_fit_surface_subjects", "dh_fit_surface_subjects_cameras", "dh_fit_surface_subjects_device", "dh_fit_surface_subjects_cameras_device",
+    "dh_fit_ident_params_default", "dh_fit_identify_subjects", "dh_fit_identify_subjects_cameras", "dh_fit_identify_subjects_device",
+    "dh_fit_identify_subjects_cameras_device",
 ]
 
 

@@ -1,9 +1,9 @@
 // dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip,
-// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
+// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip, k_ident.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
 // words of both trackers, and the one test of whether an instance may be fitted (dh_fit_instance_fault: the host's refusals and
 // the shape kernel's skips).  The device arithmetic the kernels share among themselves is in dh_fit_device.h.  Not part of the
 // ABI.  The rules are stated in include/depthhead_hip.h (sections "fitting posed models to depth frames" and after) and
-// DESIGN.md sections 18 - 25.
+// DESIGN.md sections 18 - 27.
 #pragma once
 #include "dh_internal.h"
 #include "dh_rig_fit.h"
@@ -602,3 +602,68 @@ hipError_t dh_launch_subjects_update_surface(const SurfacePointsArgs &a, bool ap
 // (k_subjects.hip) its kernels one by one, for the evaluation of a surface set
 hipError_t dh_launch_subjects_apply(const SubjectsArgs &a, hipStream_t s);
 hipError_t dh_launch_subjects_normals(const SubjectsArgs &a, hipStream_t s);
+
+// ---- identifying the subject of a fitted head (k_ident.hip)
+static_assert(sizeof(dh_ident_params) == 64, "dh_ident_params: 64 bytes");
+static_assert(sizeof(dh_ident_record) == 40, "dh_ident_record: 40 bytes");
+static_assert(DH_IDENT_UNKNOWN == DH_SHAPE_SKIP, "subjects_out is handed to a shape or surface step as its subjects");
+// Magnitudes.  A pair's passes are section 18's at a model of the set, and the instance takes part only while |scale| * (the
+// set's bound) <= DH_FIT_MAX_EXTENT: sections 25 and 26 show that this keeps section 18's argument closed for every model the
+// set can hold.  The 29 words are the fit's as they stand.
+#define DH_IDENT_THREADS 64             // k_ident_decide: one wave per instance
+
+// The mean square of a score: two correctly rounded divisions.  points > 0.
+__host__ __device__ inline double dh_ident_mean(int64_t sum_r2_fixed, uint32_t points) {
+    return ((double)sum_r2_fixed / DH_FIT_S) / (double)points;
+}
+// Whether (m_a, a) precedes (m_b, b): the smaller mean square, a tie to the lower index.  (a NaN precedes nothing and nothing
+// precedes it; an eligible m is finite)
+__host__ __device__ inline bool dh_ident_precedes(double m_a, uint32_t a, double m_b, uint32_t b) {
+    return m_a < m_b || (m_a == m_b && a < b);
+}
+// The status of an instance that takes part, from |E|, the best and second mean squares and the limits (max_ms = max_rms *
+// max_rms, formed on the host); m_second is read only where eligible > 1.
+__host__ __device__ inline uint32_t dh_ident_status(uint32_t eligible, double m_best, double m_second, double max_ms, double min_ratio) {
+    if (eligible == 0) return DH_IDENT_NO_CANDIDATE;
+    if (!(m_best <= max_ms)) return DH_IDENT_FAR;
+    if (eligible > 1 && !(m_second >= min_ratio * m_best)) return DH_IDENT_AMBIGUOUS;
+    return DH_IDENT_OK;
+}
+// The best and the second of the candidates seen so far: (+inf, DH_IDENT_UNKNOWN) where there is none, which every eligible
+// candidate precedes.  add: one more candidate; merge: the picks of two disjoint sets of candidates (the decide wave's shuffle
+// reduction).  Both keep best before second under dh_ident_precedes.
+struct IdentPick {
+    double m_best, m_second;
+    uint32_t best, second;
+};
+__host__ __device__ inline IdentPick dh_ident_pick_none() {
+    return IdentPick{__builtin_huge_val(), __builtin_huge_val(), DH_IDENT_UNKNOWN, DH_IDENT_UNKNOWN};
+}
+__host__ __device__ inline void dh_ident_pick_add(IdentPick &p, double m, uint32_t s) {
+    if (dh_ident_precedes(m, s, p.m_best, p.best)) { p.m_second = p.m_best; p.second = p.best; p.m_best = m; p.best = s; }
+    else if (dh_ident_precedes(m, s, p.m_second, p.second)) { p.m_second = m; p.second = s; }
+}
+__host__ __device__ inline void dh_ident_pick_merge(IdentPick &p, const IdentPick &o) {
+    if (dh_ident_precedes(o.m_best, o.best, p.m_best, p.best)) {          // the other's best wins: the second is the better of my best and its second
+        if (dh_ident_precedes(o.m_second, o.second, p.m_best, p.best)) { p.m_second = o.m_second; p.second = o.second; }
+        else { p.m_second = p.m_best; p.second = p.best; }
+        p.m_best = o.m_best; p.best = o.best;
+    } else if (dh_ident_precedes(o.m_best, o.best, p.m_second, p.second)) { p.m_second = o.m_best; p.second = o.best; }
+}
+
+struct IdentArgs {
+    FitArgs f;                    // frames, n, w, h, k, cams, inst, n_inst; coarse 0, full = iterations, both gates = gate, lam1, min_points; models, out and rec unused
+    const SubjectModel *models;   // [S] (n_subjects <= S)
+    uint32_t np, n_subjects;      // the set's points; the candidates' range
+    double radius, largest;       // the set's bound, the basis's largest |B_k[i]|
+    const uint8_t *enrolled;      // nullable [n_subjects]
+    const dh_fit_record *fit_rec; // nullable [n_inst]
+    dh_fit_record *score;         // [n_inst][n_subjects]: the caller's `scores` or the fitter's scratch
+    float *pose;                  // [n_inst][n_subjects][12]: R then t of each pair's refit (the fitter's scratch)
+    double max_ms, min_ratio;     // max_rms * max_rms (one f64 product on the host), min_ratio
+    uint32_t *subjects_out;       // [n_inst]
+    dh_ident_record *rec;         // [n_inst]
+    dh_render_instance *poses_out;// nullable [n_inst]
+};
+hipError_t dh_launch_ident_score(const IdentArgs &a, hipStream_t s);       // one workgroup per pair, the subject the fast index
+hipError_t dh_launch_ident_decide(const IdentArgs &a, hipStream_t s);      // one wave per instance

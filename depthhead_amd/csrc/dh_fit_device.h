@@ -2,6 +2,7 @@
 //   the per-point correspondence and the damped solve     k_fit.hip, k_fit_views.hip, k_fit_shape.hip, k_fit_shape_views.hip
 //   the shape step's point loop and reduction              k_fit_shape.hip, k_fit_shape_views.hip, k_subjects.hip
 //   the pose, the modes of a pass, the step's helpers      k_fit.hip, k_fit_views.hip (each with its *_sched instance)
+//   the single-view pass                                   k_fit.hip, k_ident.hip
 //   the trackers' rule: table rotation, carried start,
 //   acceptance, jump test and the state updates            k_fit_track.hip, k_rig_fit_track.hip
 // f64 (the trackers: f32 too) with + - * /, compares and casts only; every operation is rounded on its own, so the expression
@@ -218,6 +219,76 @@ __device__ __forceinline__ void fit_cayley(double R[9], const double w[3]) {
         for (int j = 0; j < 3; ++j) o[3 * i + j] = (C[3 * i] * R[j] + C[3 * i + 1] * R[3 + j]) + C[3 * i + 2] * R[6 + j];
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = o[i];
+}
+
+// ---- the single-view fit's pass (k_fit.hip and k_ident.hip; DESIGN.md sections 18 and 27)
+// One pass at `pose` with gate `gate`: the sums of MODE into s_sum (zeroed here; valid for every lane after the return).
+template <int MODE, bool STAGED>
+__device__ __forceinline__ void fit_pass(const FitArgs &a, const FitModel &m, const float *s_pts, const uint16_t *frame, const double K[9],
+                                         double scale, const FitPose &pose, double gate, unsigned long long *s_sum) {
+    constexpr int NJ = MODE == FIT_COARSE ? 3 : MODE == FIT_FULL ? 6 : 0;
+    constexpr int NA = NJ * (NJ + 1) / 2;
+    long long accA[NA > 0 ? NA : 1], accB[NJ > 0 ? NJ : 1];
+#pragma unroll
+    for (int k = 0; k < (NA > 0 ? NA : 1); ++k) accA[k] = 0;
+#pragma unroll
+    for (int k = 0; k < (NJ > 0 ? NJ : 1); ++k) accB[k] = 0;
+    long long e = 0, cnt = 0;
+    __syncthreads();                               // every lane has read the sums of the pass before
+    if (threadIdx.x < DH_FIT_SUMS) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    const double dw = (double)a.w, dh = (double)a.h;
+    for (uint32_t i = threadIdx.x; i < m.n; i += DH_FIT_THREADS) {
+        double v[3], nm[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            v[c] = (double)(STAGED ? s_pts[c * DH_FIT_LDS_POINTS + i] : m.pts[(size_t)i * 3 + c]);
+            nm[c] = (double)(STAGED ? s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] : m.nrm[(size_t)i * 3 + c]);
+        }
+        DH_FIT_CORRESPOND(v, nm, scale, pose.R, pose.t, K, frame, a.w, dw, dh, gate);
+        if (MODE == FIT_LAST) e += (long long)((res * res) * DH_FIT_S);
+        else {
+            double J[6];
+            J[0] = n[0]; J[1] = n[1]; J[2] = n[2];
+            if (MODE == FIT_FULL) {
+                const double q0 = p[0] - pose.t[0], q1 = p[1] - pose.t[1], q2 = p[2] - pose.t[2];
+                J[3] = q1 * n[2] - q2 * n[1];
+                J[4] = q2 * n[0] - q0 * n[2];
+                J[5] = q0 * n[1] - q1 * n[0];
+            }
+            int k = 0;
+#pragma unroll
+            for (int ja = 0; ja < NJ; ++ja) {
+#pragma unroll
+                for (int jb = ja; jb < NJ; ++jb) accA[k++] += (long long)((J[ja] * J[jb]) * DH_FIT_S);
+                accB[ja] += (long long)((J[ja] * res) * DH_FIT_S);
+            }
+        }
+        cnt += 1;
+    }
+    const bool lead = (threadIdx.x & 63) == 0;
+    {
+        int k = 0;
+#pragma unroll
+        for (int ja = 0; ja < NJ; ++ja) {
+#pragma unroll
+            for (int jb = ja; jb < NJ; ++jb) {
+                const unsigned long long s = wave_sum_u64((uint64_t)accA[k++]);
+                if (lead) atomicAdd(&s_sum[DH_FIT_PAIR(6, ja, jb)], s);
+            }
+            const unsigned long long s = wave_sum_u64((uint64_t)accB[ja]);
+            if (lead) atomicAdd(&s_sum[DH_FIT_B + ja], s);
+        }
+    }
+    if (MODE == FIT_LAST) {
+        const unsigned long long s = wave_sum_u64((uint64_t)e);
+        if (lead) atomicAdd(&s_sum[DH_FIT_E], s);
+    }
+    {
+        const unsigned long long s = wave_sum_u64((uint64_t)cnt);
+        if (lead) atomicAdd(&s_sum[DH_FIT_COUNT], s);
+    }
+    __syncthreads();
 }
 
 // ---- the trackers' rule (k_fit_track.hip: one lane per camera; k_rig_fit_track.hip: one lane per slot of a rig; DESIGN.md

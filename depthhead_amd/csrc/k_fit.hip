@@ -11,79 +11,11 @@
 //          cheaper than a broadcast) and carries the pose (R, t: 12 doubles) in registers.
 // f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free: bit-identical
 // run to run and to tests/fit_ref.py.  The pose (FitPose), the modes of a pass and the step's helpers (fit_small, fit_cayley) are
-// dh_fit_device.h's, which k_fit_views.hip shares; the offsets of the sums are dh_fit.h's.
+// dh_fit_device.h's, which k_fit_views.hip shares; so is the pass itself (fit_pass), which k_ident.hip shares; the offsets of the
+// sums are dh_fit.h's.
 #include "dh_fit_device.h"
 
 #pragma clang fp contract(off)
-
-// One pass at `pose` with gate `gate`: the sums of MODE into s_sum (zeroed here; valid for every lane after the return).
-template <int MODE, bool STAGED>
-__device__ __forceinline__ void fit_pass(const FitArgs &a, const FitModel &m, const float *s_pts, const uint16_t *frame, const double K[9],
-                                         double scale, const FitPose &pose, double gate, unsigned long long *s_sum) {
-    constexpr int NJ = MODE == FIT_COARSE ? 3 : MODE == FIT_FULL ? 6 : 0;
-    constexpr int NA = NJ * (NJ + 1) / 2;
-    long long accA[NA > 0 ? NA : 1], accB[NJ > 0 ? NJ : 1];
-#pragma unroll
-    for (int k = 0; k < (NA > 0 ? NA : 1); ++k) accA[k] = 0;
-#pragma unroll
-    for (int k = 0; k < (NJ > 0 ? NJ : 1); ++k) accB[k] = 0;
-    long long e = 0, cnt = 0;
-    __syncthreads();                               // every lane has read the sums of the pass before
-    if (threadIdx.x < DH_FIT_SUMS) s_sum[threadIdx.x] = 0;
-    __syncthreads();
-    const double dw = (double)a.w, dh = (double)a.h;
-    for (uint32_t i = threadIdx.x; i < m.n; i += DH_FIT_THREADS) {
-        double v[3], nm[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            v[c] = (double)(STAGED ? s_pts[c * DH_FIT_LDS_POINTS + i] : m.pts[(size_t)i * 3 + c]);
-            nm[c] = (double)(STAGED ? s_pts[(3 + c) * DH_FIT_LDS_POINTS + i] : m.nrm[(size_t)i * 3 + c]);
-        }
-        DH_FIT_CORRESPOND(v, nm, scale, pose.R, pose.t, K, frame, a.w, dw, dh, gate);
-        if (MODE == FIT_LAST) e += (long long)((res * res) * DH_FIT_S);
-        else {
-            double J[6];
-            J[0] = n[0]; J[1] = n[1]; J[2] = n[2];
-            if (MODE == FIT_FULL) {
-                const double q0 = p[0] - pose.t[0], q1 = p[1] - pose.t[1], q2 = p[2] - pose.t[2];
-                J[3] = q1 * n[2] - q2 * n[1];
-                J[4] = q2 * n[0] - q0 * n[2];
-                J[5] = q0 * n[1] - q1 * n[0];
-            }
-            int k = 0;
-#pragma unroll
-            for (int ja = 0; ja < NJ; ++ja) {
-#pragma unroll
-                for (int jb = ja; jb < NJ; ++jb) accA[k++] += (long long)((J[ja] * J[jb]) * DH_FIT_S);
-                accB[ja] += (long long)((J[ja] * res) * DH_FIT_S);
-            }
-        }
-        cnt += 1;
-    }
-    const bool lead = (threadIdx.x & 63) == 0;
-    {
-        int k = 0;
-#pragma unroll
-        for (int ja = 0; ja < NJ; ++ja) {
-#pragma unroll
-            for (int jb = ja; jb < NJ; ++jb) {
-                const unsigned long long s = wave_sum_u64((uint64_t)accA[k++]);
-                if (lead) atomicAdd(&s_sum[DH_FIT_PAIR(6, ja, jb)], s);
-            }
-            const unsigned long long s = wave_sum_u64((uint64_t)accB[ja]);
-            if (lead) atomicAdd(&s_sum[DH_FIT_B + ja], s);
-        }
-    }
-    if (MODE == FIT_LAST) {
-        const unsigned long long s = wave_sum_u64((uint64_t)e);
-        if (lead) atomicAdd(&s_sum[DH_FIT_E], s);
-    }
-    {
-        const unsigned long long s = wave_sum_u64((uint64_t)cnt);
-        if (lead) atomicAdd(&s_sum[DH_FIT_COUNT], s);
-    }
-    __syncthreads();
-}
 
 template <bool STAGED>
 __device__ __forceinline__ void fit_run(const FitArgs &a, const dh_render_instance *in, const FitModel &m, const float *s_pts,

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (CALIB_RECORD_DTYPE, CALIB_SKIP, FIT_RECORD_DTYPE, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, FIT_VIEW_TOLERANCE, HEAD_DTYPE,
+from ._lib import (CALIB_RECORD_DTYPE, CALIB_SKIP, FIT_RECORD_DTYPE, IDENT_RECORD_DTYPE, IDENT_UNKNOWN, FIT_TRACK_ANGLES, FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE, FIT_VIEW_TOLERANCE, HEAD_DTYPE,
                    MAX_HEADS, POSE_DTYPE, RIG_FIT_RECORD_DTYPE, RIG_FIT_STATE_DTYPE, RIG_MAX_PERSONS, RIG_MAX_TRACKS, RIG_PERSON_DTYPE,
                    RIG_TRACK_DTYPE, RENDER_INSTANCE_DTYPE, SHAPE_RECORD_DTYPE, SHAPE_SKIP, SUBJECT_STATE_DTYPE, SUPPORT_DTYPE, SUPPORT_RADIUS, SURFACE_RECORD_DTYPE,
                    VIEW_FIT_RECORD_DTYPE,
@@ -24,6 +24,7 @@ SHAPE_OK, SHAPE_FEW_POINTS, SHAPE_SINGULAR = 0, 1, 2  # dh_shape_record.status
 CALIB_OK, CALIB_FEW_POINTS, CALIB_SINGULAR, CALIB_NOT_ORTHONORMAL, CALIB_HELD = 0, 1, 2, 3, 4  # dh_calib_record.status
 SUBJECT_CLAMPED, SUBJECT_NONFINITE = 1, 2            # dh_subject_state.flags
 SURFACE_OK, SURFACE_FEW_POINTS = 0, 1                # dh_surface_record.status
+IDENT_OK, IDENT_SKIPPED, IDENT_NO_CANDIDATE, IDENT_FAR, IDENT_AMBIGUOUS = 0, 1, 2, 3, 4   # dh_ident_record.status
 
 
 def vertex_normals(verts, tris) -> np.ndarray:
@@ -196,6 +197,17 @@ def surface_params(gate=None, min_cos2=None, mu=None, eps=None, min_count=None, 
     check(_lib.load().dh_fit_surface_params_default(C.byref(p)))
     for name, value, cast in (("gate", gate, float), ("min_cos2", min_cos2, float), ("mu", mu, float), ("eps", eps, float),
                               ("min_count", min_count, int), ("min_points", min_points, int), ("iterations", iterations, int)):
+        if value is not None:
+            setattr(p, name, cast(value))
+    return p
+
+
+def ident_params(iterations=None, min_points=None, gate=None, lam=None, max_rms=None, min_ratio=None) -> "_lib.IdentParams":
+    """dh_fit_ident_params_default with the given fields replaced."""
+    p = _lib.IdentParams()
+    check(_lib.load().dh_fit_ident_params_default(C.byref(p)))
+    for name, value, cast in (("iterations", iterations, int), ("min_points", min_points, int), ("gate", gate, float), ("lam", lam, float),
+                              ("max_rms", max_rms, float), ("min_ratio", min_ratio, float)):
         if value is not None:
             setattr(p, name, cast(value))
     return p
@@ -474,6 +486,60 @@ class Fitter(_lib._Handle):
             C.c_void_p(fit_records.data_ptr()) if fit_records is not None else None, prm, C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
         return rec[:ns * SURFACE_RECORD_DTYPE.itemsize]
 
+    def identify_subjects(self, frames, subjects_set, instances, K_or_cameras, n_subjects=None, enrolled=None, fit_records=None, params=None,
+                          scores: bool = False, device_out: bool = False, stream=None):
+        """Which enrolled subject of a `Subjects` set each fitted instance is: every instance that takes
+        part is refitted with the model of every candidate -- the subjects s < n_subjects (default the set's) with enrolled[s] != 0
+        (None: all) -- and the candidate with the smallest mean squared residual wins, unless it exceeds params.max_rms (IDENT_FAR)
+        or the second is within params.min_ratio of it (IDENT_AMBIGUOUS).  `fit_records` (what `fit` returned with the instances)
+        leaves out an instance whose fit did not end FIT_OK.  Returns (subjects u32 [n_instances] -- IDENT_UNKNOWN, which is
+        SHAPE_SKIP, where the status is not IDENT_OK --, IDENT_RECORD_DTYPE records, the instances with the best candidate's
+        refitted pose) and, with scores=True, every pair's FIT_RECORD_DTYPE [n_instances, n_subjects] after them.  Host form: numpy
+        arrays.  With device_out=True frames, instances, enrolled (uint8) and fit_records are torch tensors on the device and the
+        results come back as torch tensors (subjects int32, the others uint8): two kernels ordered on `stream`, no host wait."""
+        n, h, w = (int(v) for v in frames.shape)
+        cams = getattr(K_or_cameras, "_h", None)
+        if cams is None:
+            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
+            kind, karg = "", vp(K)
+        else:
+            kind, karg = "_cameras", cams
+        prm = C.byref(params) if params is not None else None
+        ns = len(subjects_set) if n_subjects is None else int(n_subjects)
+        if not device_out:
+            fr = np.ascontiguousarray(frames, dtype=np.uint16)
+            inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
+            ni = len(inst)
+            enr = None if enrolled is None else np.ascontiguousarray(np.asarray(enrolled) != 0, dtype=np.uint8).reshape(max(ns, 0))
+            frec = None if fit_records is None else np.ascontiguousarray(fit_records, dtype=FIT_RECORD_DTYPE).reshape(ni)
+            sub, rec = np.full(ni, IDENT_UNKNOWN, np.uint32), np.zeros(ni, IDENT_RECORD_DTYPE)
+            poses, sc = np.zeros(ni, RENDER_INSTANCE_DTYPE), np.zeros((ni, max(ns, 0)), FIT_RECORD_DTYPE)
+            check(getattr(self._lib, "dh_fit_identify_subjects" + kind)(self._h, vp(fr), n, w, h, karg, subjects_set._h, vp(inst) if ni else None,
+                                                                         C.c_uint32(ni), vp(enr), C.c_uint32(ns), vp(frec), prm, vp(sub), vp(rec),
+                                                                         vp(poses), vp(sc) if scores else None))
+            return (sub, rec, poses, sc) if scores else (sub, rec, poses)
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
+            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
+        ni = instances.numel() * instances.element_size() // RENDER_INSTANCE_DTYPE.itemsize
+        if enrolled is not None and (enrolled.numel() != ns or enrolled.element_size() != 1 or not enrolled.is_contiguous()):
+            raise ValueError("device enrolled: a contiguous 8-bit tensor with one byte per subject is expected")
+        if fit_records is not None and (fit_records.numel() * fit_records.element_size() != ni * FIT_RECORD_DTYPE.itemsize or not fit_records.is_contiguous()):
+            raise ValueError("device fit_records: the contiguous tensor of one dh_fit_record per instance is expected")
+        sub = torch.empty(max(ni, 1), dtype=torch.int32, device=dev)
+        rec = torch.empty(max(ni, 1) * IDENT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        poses = torch.empty(max(ni, 1) * RENDER_INSTANCE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        sc = torch.empty(max(ni * ns, 1) * FIT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev) if scores else None
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        check(getattr(self._lib, "dh_fit_identify_subjects" + kind + "_device")(
+            self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, subjects_set._h, C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
+            C.c_void_p(enrolled.data_ptr()) if enrolled is not None else None, C.c_uint32(ns),
+            C.c_void_p(fit_records.data_ptr()) if fit_records is not None else None, prm, C.c_void_p(sub.data_ptr()), C.c_void_p(rec.data_ptr()),
+            C.c_void_p(poses.data_ptr()), C.c_void_p(sc.data_ptr()) if scores else None, C.c_void_p(s)))
+        out = (sub[:ni], rec[:ni * IDENT_RECORD_DTYPE.itemsize], poses[:ni * RENDER_INSTANCE_DTYPE.itemsize])
+        return out + (sc[:ni * ns * FIT_RECORD_DTYPE.itemsize],) if scores else out
+
     def shape_step_views(self, frames, views, model, basis, instances, sets=None, subjects=None, n_subjects: int = 1, params=None,
                          device_out: bool = False, stream=None):
         """One multi-view shape step of `model` and its `basis` over the world-posed `instances`
@@ -749,6 +815,32 @@ def refine_subjects(fitter, frames, K_or_cameras, subjects, starts, subject_of, 
         return subjects.state(), inst, (np.zeros(len(inst), FIT_RECORD_DTYPE), np.zeros(len(subjects), SURFACE_RECORD_DTYPE))
     out = d_inst.cpu().numpy().view(RENDER_INSTANCE_DTYPE).copy()
     return subjects.state(), out, (d_frec.cpu().numpy().view(FIT_RECORD_DTYPE).copy(), d_urec.cpu().numpy().view(SURFACE_RECORD_DTYPE).copy())
+
+
+def recognise_subjects(fitter, frames, K_or_cameras, subjects, starts, model, enrolled=None, fit_prm=None, ident_prm=None):
+    """Say who each rough head of `frames` is, on the device.  frames [n, h, w] u16 (numpy) go to the device
+    once; `starts` are RENDER_INSTANCE_DTYPE [m] rough poses.  Every start is fitted with `model` (the generic head: a `Model`)
+    under fit_prm, then `Fitter.identify_subjects` runs from those poses and records against the candidates of `subjects` (a
+    `Subjects` set; enrolled [S] marks them, None: all) under ident_prm -- all enqueued on the current torch stream, nothing read
+    in between and once at the end.  Returns (subjects u32 [m] with IDENT_UNKNOWN for an unknown head, IDENT_RECORD_DTYPE [m], the
+    instances at the best candidate's refitted pose, the generic fit's FIT_RECORD_DTYPE [m])."""
+    import torch
+    dev = torch.device("cuda", fitter.device)
+    inst = np.array(starts, dtype=RENDER_INSTANCE_DTYPE)
+    inst["mesh"] = 0
+    if len(inst) == 0:
+        return np.zeros(0, np.uint32), np.zeros(0, IDENT_RECORD_DTYPE), inst, np.zeros(0, FIT_RECORD_DTYPE)
+    host = np.ascontiguousarray(frames, dtype=np.uint16)
+    d_frames = torch.from_numpy((host if host.flags.writeable else host.copy()).view(np.int16)).to(dev)
+    d_enr = None
+    if enrolled is not None:
+        d_enr = torch.from_numpy(np.ascontiguousarray(np.asarray(enrolled) != 0, dtype=np.uint8).reshape(len(subjects))).to(dev)
+    d_inst, d_frec = fitter.fit(d_frames, [model], inst, K_or_cameras, params=fit_prm, device_out=True)
+    d_sub, d_rec, d_poses = fitter.identify_subjects(d_frames, subjects, d_inst, K_or_cameras, enrolled=d_enr, fit_records=d_frec, params=ident_prm,
+                                                     device_out=True)
+    torch.cuda.current_stream(dev).synchronize()
+    return (d_sub.cpu().numpy().view(np.uint32).copy(), d_rec.cpu().numpy().view(IDENT_RECORD_DTYPE).copy(),
+            d_poses.cpu().numpy().view(RENDER_INSTANCE_DTYPE).copy(), d_frec.cpu().numpy().view(FIT_RECORD_DTYPE).copy())
 
 
 def adapt_views(fitter, frames, views, verts, tris, basis, starts, sets=None, rounds: int = 6, fit_prm=None, shape_prm=None, coeffs=None):

@@ -1480,6 +1480,109 @@ int dh_fit_surface_subjects_cameras_device(dh_fitter *f, const uint16_t *frames,
                                            const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records,
                                            const dh_surface_params *params, dh_surface_record *records, void *stream);
 
+/* ---- identifying the subject of a fitted head ----
+ * Sections 25 and 26 keep a gallery on the device, but every call that uses it must be TOLD who is in each frame.  This call
+ * answers that: given fitted heads and a set, it says for each head which enrolled subject it is, or that it is none of them.
+ * Not in the reference: PARITY UNPINNED, the definition below is this library's.  Arithmetic: f64 with + - * /, compares and
+ * casts; every operation rounded on its own; the sums are int64 (their order is free); no floating-point atomic.
+ * INPUTS: frames with one K or a camera table; a subject set (ordinary or surface) and n_subjects <= S; enrolled[n_subjects], u8,
+ *   nullable: subject s is a CANDIDATE where enrolled is NULL or enrolled[s] != 0 (a fresh set's unenrolled subjects all hold the
+ *   generic head and would tie, hence the mask); n_instances fitted instances -- what dh_fit_depth* wrote; `mesh` and `flags` are
+ *   ignored; fit_records[n_instances], nullable; a dh_ident_params (NULL: dh_fit_ident_params_default).
+ * TAKING PART.  Instance i takes part by the rule of dh_fit_shape_subjects*: its frame is below n; fit_records[i].status is
+ *   DH_FIT_OK where records are given; none of the per-instance refusals of section 18 and 20 applies, with the set's bound for
+ *   the model's radius and the basis's largest |B_k[i]|.
+ * THE SCORE of pair (i, s), for every instance i that takes part and every candidate s, is section 18's fit of subject s's model
+ *   AS THE SET HOLDS IT NOW at frame instances[i].frame, started at the instance's (R, t) with its scale, on the schedule
+ *   coarse_iterations = 0, `iterations` full steps at gate `gate` with `lambda`, and `min_points` for the fit's own min_points:
+ *   a pass that associates fewer points ends it DH_FIT_FEW_POINTS, a pivot that is not > 0 DH_FIT_SINGULAR, a step with every
+ *   |x_a| < 1e-6 ends it early, all as in section 18; then the last pass at `gate`.  The score is that fit's dh_fit_record
+ *   (points, steps, status, sum_r2_fixed) and its refitted pose, R and t rounded to f32 once.  With iterations = 0 it is one pass
+ *   at the given pose.  The sums are the fit's 29 words and their magnitude argument holds as it stands: the set's bound in the
+ *   extent test keeps it closed for every model the set can hold (sections 25 and 26).
+ * THE DECISION for instance i.  E, the ELIGIBLE candidates, are those whose score has status DH_FIT_OK and points >= min_points.
+ *   For s in E:  m_s = ((f64)sum_r2_fixed / 2^20) / (f64)points  -- two correctly rounded divisions; finite, since min_points >= 6.
+ *   (m_a, a) PRECEDES (m_b, b) when m_a < m_b, or m_a == m_b and a < b: a tie goes to the lower index.  best is the s in E
+ *   that precedes all others, second the same over E without best.  The status is the first of these that applies:
+ *     DH_IDENT_SKIPPED       the instance takes no part;
+ *     DH_IDENT_NO_CANDIDATE  E is empty;
+ *     DH_IDENT_FAR           not  m_best <= max_rms * max_rms  (the product formed once, on the host, in f64);
+ *     DH_IDENT_AMBIGUOUS     a second exists and not  m_second >= min_ratio * m_best;
+ *     DH_IDENT_OK            otherwise.
+ * OUTPUTS per instance.  subjects_out[i] = best where the status is DH_IDENT_OK, else DH_IDENT_UNKNOWN -- which IS DH_SHAPE_SKIP,
+ *   so the array can be handed to a shape or surface step as `subjects` unchanged and unknown heads take no part.  records[i], a
+ *   dh_ident_record: best and second are reported whatever the status is (DH_IDENT_UNKNOWN where there is none, with points and
+ *   sum_r2_fixed 0).  poses_out[i], nullable: the input instance with R and t replaced by the best pair's refitted pose where E is
+ *   not empty, else the input copied through.  scores, nullable, [n_instances][n_subjects] dh_fit_record: every pair's score;
+ *   a pair that did not run (its subject no candidate, its instance taking no part) holds zeros.
+ * dh_fit_identify_subjects* -- argument order as dh_fit_surface_subjects*.  The host forms are synchronous and take host frames,
+ *   instances, enrolled, fit_records and outputs.  The _device forms take all of these on the device (params stays host memory),
+ *   enqueue exactly two kernels on `stream` (NULL = default stream) -- k_ident_score, one workgroup per (instance, subject) pair,
+ *   and k_ident_decide, one wave per instance -- with no host wait, ordered after whatever the stream held (a _device fit, a
+ *   _device update of the set).  The pair scratch -- one score and one pose per pair -- is the fitter's: taken at the first call,
+ *   it grows as the fitter's other tables do (growing waits for the device; a call that fits allocates nothing).
+ *   DH_EINVAL, before anything is launched and with nothing written, in this order: NULL fitter, frames, subjects_out, records,
+ *   subject set; the frames' refusals of dh_fit_shape*; a set on another device than the fitter; n_subjects outside 1 .. S; a NaN
+ *   in gate, lambda, max_rms or min_ratio; iterations above 64; a gate outside (0, 4096]; lambda negative or infinite; min_points
+ *   below 6; max_rms not > 0 (+inf is allowed and disables the limit); min_ratio below 1; a reserved word that is not 0; NULL
+ *   instances with n_instances > 0; n_instances * n_subjects above DH_IDENT_MAX_PAIRS.  The host forms then refuse, per instance
+ *   whose fit record is DH_FIT_OK (or all, without records), what dh_fit_shape_subjects refuses: a frame >= n, then the
+ *   per-instance refusals with the set's bound.  The _device forms cannot read the instances: the device skips every instance one
+ *   of these names (DH_IDENT_SKIPPED).  n_instances = 0 is no error and writes nothing.
+ *   Bit-identical run to run and to tests/ident_ref.py.
+ * THE DEFAULT max_rms is measured (tests/test_ident_ref.py): three subjects enrolled from 8 frames each, 4
+ *   held-out frames of each and of a stranger identified.  The largest best mean square of the 12 known probes was 2.2557 mm^2,
+ *   the smallest of the 4 stranger probes 3.5547 mm^2; the default is the square root of their geometric mean, rounded to 1.68. */
+#define DH_IDENT_OK 0u
+#define DH_IDENT_SKIPPED 1u              /* the instance takes no part */
+#define DH_IDENT_NO_CANDIDATE 2u         /* no candidate's score is eligible */
+#define DH_IDENT_FAR 3u                  /* the best mean square exceeds max_rms^2: none of the candidates */
+#define DH_IDENT_AMBIGUOUS 4u            /* the second is within min_ratio of the best */
+#define DH_IDENT_UNKNOWN 0xFFFFFFFFu     /* subjects_out[i], best, second: no subject (== DH_SHAPE_SKIP) */
+#define DH_IDENT_MAX_PAIRS 4194304u      /* 2^22: instances times subjects of a call */
+#define DH_IDENT_DEFAULT_MAX_RMS 1.68    /* mm: sqrt(sqrt(2.2557 * 3.5547)) = 1.6828 (the measurement above) */
+typedef struct dh_ident_params {
+    uint32_t iterations;          /* offset 0:  4: full steps of a pair's refit, at most 64 */
+    uint32_t min_points;          /* offset 4:  64: of the refit and of eligibility, at least 6 */
+    double   gate;                /* offset 8:  25 (mm), in (0, 4096] */
+    double   lambda;              /* offset 16: 1e-3 */
+    double   max_rms;             /* offset 24: DH_IDENT_DEFAULT_MAX_RMS (mm), > 0; +inf disables the limit */
+    double   min_ratio;           /* offset 32: 1.0, which disables the test; >= 1 */
+    uint64_t reserved[3];         /* offset 40: 0 */
+} dh_ident_params;     /* 64 bytes */
+typedef struct dh_ident_record {
+    uint32_t status;              /* offset 0:  DH_IDENT_* */
+    uint32_t best;                /* offset 4:  the best eligible candidate, or DH_IDENT_UNKNOWN */
+    uint32_t second;              /* offset 8:  the second, or DH_IDENT_UNKNOWN */
+    uint32_t eligible;            /* offset 12: |E| */
+    uint32_t points_best;         /* offset 16: points of the best's score */
+    uint32_t points_second;       /* offset 20 */
+    int64_t  sum_r2_best;         /* offset 24: sum_r2_fixed of the best's score */
+    int64_t  sum_r2_second;       /* offset 32 */
+} dh_ident_record;     /* 40 bytes, no padding */
+int dh_fit_ident_params_default(dh_ident_params *p);
+/* frames [n][h][w] u16; enrolled [n_subjects] u8 or NULL; instances [n_instances]; fit_records [n_instances] or NULL; subjects_out
+ * [n_instances] u32; records [n_instances]; poses_out [n_instances] or NULL; scores [n_instances][n_subjects] or NULL */
+int dh_fit_identify_subjects(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set,
+                             const dh_render_instance *instances, uint32_t n_instances, const uint8_t *enrolled, uint32_t n_subjects,
+                             const dh_fit_record *fit_records, const dh_ident_params *params, uint32_t *subjects_out,
+                             dh_ident_record *records, dh_render_instance *poses_out, dh_fit_record *scores);
+int dh_fit_identify_subjects_cameras(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                     const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances,
+                                     const uint8_t *enrolled, uint32_t n_subjects, const dh_fit_record *fit_records,
+                                     const dh_ident_params *params, uint32_t *subjects_out, dh_ident_record *records,
+                                     dh_render_instance *poses_out, dh_fit_record *scores);
+int dh_fit_identify_subjects_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set,
+                                    const dh_render_instance *instances, uint32_t n_instances, const uint8_t *enrolled,
+                                    uint32_t n_subjects, const dh_fit_record *fit_records, const dh_ident_params *params,
+                                    uint32_t *subjects_out, dh_ident_record *records, dh_render_instance *poses_out,
+                                    dh_fit_record *scores, void *stream);
+int dh_fit_identify_subjects_cameras_device(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c,
+                                            const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances,
+                                            const uint8_t *enrolled, uint32_t n_subjects, const dh_fit_record *fit_records,
+                                            const dh_ident_params *params, uint32_t *subjects_out, dh_ident_record *records,
+                                            dh_render_instance *poses_out, dh_fit_record *scores, void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
