@@ -119,7 +119,10 @@ def frame_hits(tables: sr.LeafTables, model, img, K, leaf_idx, patch_flags):
         wins.append(np.full(len(c), wi, np.int64)); trees.append(np.full(len(c), t, np.int64))
         cells.append(c); vals.append(np.full(len(c), v, np.int64)); gcell.append(guess_cells(d, K, w, h))
         vhit.append(np.full(len(c), hi, np.int64))
-        r = _rot_cells(tables.forest, leaf)
+        rot = tables.__dict__.setdefault("_rot", {})         # per leaf, like LeafTables' own tables
+        if leaf not in rot:
+            rot[leaf] = _rot_cells(tables.forest, leaf)
+        r = rot[leaf]
         if r is not None:
             rc.append(r); rv.append(np.full(len(r), v, np.int64)); rhit.append(np.full(len(r), hi, np.int64))
     cat = lambda xs, shape: np.concatenate(xs) if xs else np.zeros(shape, np.int64)   # noqa: E731

@@ -2,7 +2,7 @@
 // sanitizers: built by tests/test_host_sanitize.py with g++ -fsanitize=address,undefined and once more with
 // -fsanitize=thread.  Prints "host_check ok" and exits 0; any check that fails prints its line and exits 1.
 // Covers: forest validation (good / every refused kind), patch grids, tile selection across geometries (with the invariants
-// the kernels rely on), the per-batch counter block's layout, upload chunk plans, where k_vote's approximate cell quotient
+// the kernels rely on), the shifts a frame's tile grid may take (dh_tile_shifts_), the per-batch counter block's layout, upload chunk plans, where k_vote's approximate cell quotient
 // is allowed, the run-length payload scanner / packer on well-formed, redundant and malformed payloads (incl. every
 // truncation point of a payload), the host BIWI parsers, knob parsing, the exception guard, and dh_parallel_for_ / the
 // thread-local error slots under concurrency.
@@ -480,6 +480,75 @@ static void test_tables_and_knobs() {
     CHECK(kn.max_resident == 512 && kn.stage_chunk == 64 && kn.top_levels == -1 && !kn.no_absorb);
 }
 
+// dh_tile_shifts_: the shifts a frame's tile grid may take.  Geometries come from dh_choose_tile_ with a forced tile, as a
+// workspace builds them; the expected values are worked out from the rule's prose (dh_host.h), not from its code.
+static Geom shift_geom(int w, int h, int step, int tx, int ty, bool uniform = true) {
+    TileQuery q;
+    q.params = dh_params{(uint32_t)step, 80, 80, 8.0f, 20}; q.f_rw = q.f_rh = 24; q.n_trees = 6; q.absorb_ok = uniform; q.tile_x = tx; q.tile_y = ty;
+    Geom g;
+    g.w = w; g.h = h; g.uniform = uniform;
+    CHECK(dh_patch_grid_(q.params, w, h, &g.nx, &g.ny) == DH_OK);
+    g.npatch = g.nx * g.ny;
+    CHECK(dh_choose_tile_(q, g) == DH_OK && g.px == tx && g.py == ty);
+    return g;
+}
+static void test_tile_shifts() {
+    // gx: 4 for every stride but 16 (2) and 32 (1); 13 x 8 windows in tiles of 6 x 3 leave a slack of 5 columns and 1 row
+    for (int step : {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 16, 24, 32}) {
+        const Geom g = shift_geom(80 + 13 * step, 80 + 8 * step, step, 6, 3);
+        CHECK(g.nx == 13 && g.ny == 8 && g.tiles_x == 3 && g.tiles_y == 3);
+        const int gx = step == 16 ? 2 : step == 32 ? 1 : 4;
+        TileShifts t;
+        CHECK(dh_tile_shifts_(g, step, 3, Knobs(), &t) == DH_OK);
+        CHECK(t.on && t.gx == gx && t.nsx == 5 / gx + 1 && t.nsy == 2 && t.sx0 == 0 && t.sy0 == 0);
+        // a forced shift: clamped to the slack, sx rounded down to a multiple of gx, the one shift of every frame
+        Knobs k; k.tile_shift_mode = 2; k.tile_shift_x = 100; k.tile_shift_y = 100;
+        CHECK(dh_tile_shifts_(g, step, 3, k, &t) == DH_OK && t.on && t.gx == gx && t.nsx == 1 && t.nsy == 1 && t.sx0 == 5 / gx * gx && t.sy0 == 1);
+        k.tile_shift_x = 3; k.tile_shift_y = 0;
+        CHECK(dh_tile_shifts_(g, step, 3, k, &t) == DH_OK && t.on && t.sx0 == 3 / gx * gx && t.sy0 == 0);
+    }
+    // 324 x 244 at stride 4 in tiles of 12 x 8: 61 x 41 windows, slack 11 and 7
+    const Geom g = shift_geom(324, 244, 4, 12, 8);
+    TileShifts t;
+    CHECK(dh_tile_shifts_(g, 4, 3, Knobs(), &t) == DH_OK && t.on && t.gx == 4 && t.nsx == 3 && t.nsy == 8);
+    {
+        Knobs k; k.tile_shift_mode = 2; k.tile_shift_x = 6; k.tile_shift_y = 3;
+        CHECK(dh_tile_shifts_(g, 4, 3, k, &t) == DH_OK && t.on && t.sx0 == 4 && t.sy0 == 3 && t.nsx * t.nsy == 1);
+        k.tile_shift_x = 11; k.tile_shift_y = 7;
+        CHECK(dh_tile_shifts_(g, 4, 5, k, &t) == DH_OK && t.on && t.sx0 == 8 && t.sy0 == 7);
+    }
+    // the paths without a choice: "off", the general path, dense box sums, no tile lists -- and a malformed value
+    { Knobs k; k.tile_shift_mode = 1; t.on = true; CHECK(dh_tile_shifts_(g, 4, 3, k, &t) == DH_OK && !t.on && t.nsx * t.nsy == 1 && t.sx0 == 0 && t.sy0 == 0); }
+    { Knobs k; k.box_dense = true; t.on = true; CHECK(dh_tile_shifts_(g, 4, 3, k, &t) == DH_OK && !t.on); }
+    { Knobs k; k.no_tile_list = true; t.on = true; CHECK(dh_tile_shifts_(g, 4, 3, k, &t) == DH_OK && !t.on); }
+    { const Geom gg = shift_geom(324, 244, 4, 12, 8, false); t.on = true; CHECK(dh_tile_shifts_(gg, 4, 3, Knobs(), &t) == DH_OK && !t.on); }
+    { Knobs k; k.tile_shift_mode = 3; CHECK(dh_tile_shifts_(g, 4, 3, k, &t) == DH_EINVAL && strstr(dh_err_get_(), "DH_TILE_SHIFT")); }
+    // whole tiles, no slack: the one shift (0, 0)
+    { const Geom g0 = shift_geom(320, 240, 4, 12, 8); t.on = true; CHECK(g0.nx == 60 && g0.ny == 40 && dh_tile_shifts_(g0, 4, 3, Knobs(), &t) == DH_OK && !t.on && t.nsx * t.nsy == 1); }
+    // the LDS limit: 800 x 600 is 4 parts of 49 groups and 577 rows.  16-row blocks: 2 * 37 * 4 + 38 * 197 + 12 + 8 = 7 802 words, inside
+    // the 12 288; 8-row blocks: 2 * 73 * 4 + 74 * 197 + 12 + 8 = 15 182, outside -- the fixed grid, and a forced shift is refused
+    {
+        const Geom gl = shift_geom(800, 600, 4, 16, 6);
+        CHECK(gl.nx == 180 && gl.ny == 130 && gl.box_parts == 4 && gl.box_ow == 196 && gl.box_rows == 577);
+        CHECK(dh_tile_shift_lds_words(37, 4, 196, 12) == 7802 && dh_tile_shift_lds_words(73, 4, 196, 12) == 15182 && DH_TILE_SHIFT_LDS_WORDS == 12288);
+        CHECK(dh_tile_shift_lds_words(60, 1, 198, 21) == 12288 && dh_tile_shift_lds_words(60, 1, 198, 22) == 12289);
+        CHECK(dh_tile_shifts_(gl, 4, 4, Knobs(), &t) == DH_OK && t.on && t.gx == 4 && t.nsx == 4 && t.nsy == 3);
+        t.on = true;
+        CHECK(dh_tile_shifts_(gl, 4, 3, Knobs(), &t) == DH_OK && !t.on);
+        Knobs k; k.tile_shift_mode = 2; k.tile_shift_x = 4; k.tile_shift_y = 1;
+        CHECK(dh_tile_shifts_(gl, 4, 4, k, &t) == DH_OK && t.on && t.sx0 == 4 && t.sy0 == 1);
+        CHECK(dh_tile_shifts_(gl, 4, 3, k, &t) == DH_EINVAL && strstr(dh_err_get_(), "800x600") && strstr(dh_err_get_(), "DH_TILE_SHIFT=4,1"));
+    }
+    // DH_TILE_SHIFT as the environment gives it
+    setenv("DH_TILE_SHIFT", "off", 1);
+    CHECK(dh_read_knobs_().tile_shift_mode == 1);
+    setenv("DH_TILE_SHIFT", "8,7", 1);
+    { const Knobs k = dh_read_knobs_(); CHECK(k.tile_shift_mode == 2 && k.tile_shift_x == 8 && k.tile_shift_y == 7); }
+    for (const char *bad : {"on", "4", "-4,0", "4,1,2"}) { setenv("DH_TILE_SHIFT", bad, 1); CHECK(dh_read_knobs_().tile_shift_mode == 3); }
+    unsetenv("DH_TILE_SHIFT");
+    CHECK(dh_read_knobs_().tile_shift_mode == 0);
+}
+
 static void test_guard_and_threads() {
     CHECK(dh_guard_("x", []() -> int { throw std::bad_alloc(); }) == DH_ENOMEM && strstr(dh_err_get_(), "out of host memory"));
     CHECK(dh_guard_("x", []() -> int { throw std::runtime_error("boom"); }) == DH_EINVAL && strstr(dh_err_get_(), "boom"));
@@ -516,6 +585,7 @@ int main() {
     test_biwi_text();
     test_tables_and_knobs();
     test_counter_layout();
+    test_tile_shifts();
     test_guard_and_threads();
     if (g_fail) { fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     printf("host_check ok\n");

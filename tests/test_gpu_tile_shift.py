@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import tile_shift_ref as tsr
 from depthhead_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -96,51 +97,26 @@ def off(hp_mod, forest, frames):
     return _run(hp_mod, forest, frames, DH_TILE_SHIFT="off")
 
 
-# ------------------------------------------------------------------ the choice, restated
+# ------------------------------------------------------------------ the choice, restated (tests/tile_shift_ref.py, at this geometry)
+def _geo(w=W, h=H):
+    return tsr.Geometry(w, h, STEP, (80, 80), (RW, RH), (PX, PY))
+
+
 def _occupancy(frame, block):
-    """Pixel-resolution image of k_boxsum's masks: True over the 4 columns x `block` rows of every group that holds a rectangle
-    origin with a non-zero sum.  (Origins right of w - rw are left out: their clipped rectangles lie inside that of column w - rw,
-    and no tile's region holds one of them without it.)"""
-    h, w = frame.shape
-    sat = np.zeros((h + 1, w + 1), np.int64)
-    sat[1:, 1:] = np.cumsum(np.cumsum(frame > 0, axis=0), axis=1)
-    nz = (sat[RH:, RW:] - sat[:-RH, RW:] - sat[RH:, :-RW] + sat[:-RH, :-RW]) > 0       # [h - rh + 1][w - rw + 1]
-    rows, cols = nz.shape
-    occ = np.zeros((-(-rows // block) * block, -(-cols // 4) * 4), bool)
-    occ[:rows, :cols] = nz
-    g = occ.reshape(occ.shape[0] // block, block, occ.shape[1] // 4, 4).any(axis=(1, 3))
-    return np.repeat(np.repeat(g, block, axis=0), 4, axis=1)
+    return tsr.occupancy(frame, block, (RW, RH))
 
 
 def _tiles(occ, sx, sy, tiles_x, tiles_y):
-    """Tiles of the grid shifted by (sx, sy) windows whose region of rectangle origins meets the occupancy."""
-    n = 0
-    for ty in range(tiles_y):
-        for tx in range(tiles_x):
-            x, y = (tx * PX - sx) * STEP, (ty * PY - sy) * STEP
-            n += bool(occ[max(y, 0):y + TBH, max(x, 0):x + TBW].any())
-    return n
+    geo = _geo()
+    assert (geo.tiles_x, geo.tiles_y) == (tiles_x, tiles_y)
+    return tsr.tiles(occ, geo, sx, sy)
 
 
 def _choice(frames, block, w=W, h=H):
-    """Per frame: tiles at shift (0, 0), the chosen shift (fewest tiles, ties to the smallest (sy, sx)) and its tiles."""
-    nx, ny = MODEL.patch_grid(w, h)
-    tiles_x, tiles_y = -(-nx // PX), -(-ny // PY)
-    shifts = [(sx, sy) for sy in range(tiles_y * PY - ny + 1) for sx in range(0, tiles_x * PX - nx + 1, 4)]
-    res = []
-    for fr in frames:
-        occ = _occupancy(fr, block)
-        counts = [_tiles(occ, sx, sy, tiles_x, tiles_y) for sx, sy in shifts]
-        best = min(range(len(shifts)), key=lambda i: (counts[i], shifts[i][1], shifts[i][0]))
-        res.append((counts[0], shifts[best], counts[best]))
-    return res, shifts
+    return tsr.choice(frames, _geo(w, h), block)
 
 
-def _per_list(per_frame):
-    out = np.zeros(8, np.int64)
-    for i, c in enumerate(per_frame):
-        out[i % 8] += c
-    return out
+_per_list = tsr.per_list
 
 
 # ------------------------------------------------------------------ poses
