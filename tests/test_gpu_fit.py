@@ -4,7 +4,9 @@ whose width is no multiple of 8 with models across every edge, twelve instances 
 heads), models of 1, 257 and 2562 points (the workgroup's stride edge and the streaming path past the LDS budget), schedules
 without coarse or without any steps, both early exits on a head scene, the FEW_POINTS and SINGULAR exits, a camera table with a matrix that is no pinhole, the
 device twins chained after a device render on one stream, a fitter reused with a smaller, a larger and the smaller batch
-again, and two runs of the same call."""
+again, and two runs of the same call.  The scenes here are rendered with seeded noise and random poses, so no point lands ON a
+compare of the correspondence; tests/test_gpu_fit_edges.py holds this and every other entry point of the fit family to points
+placed on each compare and one step to either side of it (tests/fit_edges.py)."""
 import functools
 
 import numpy as np
