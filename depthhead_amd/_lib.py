@@ -135,6 +135,7 @@ IDENT_OK, IDENT_SKIPPED, IDENT_NO_CANDIDATE, IDENT_FAR, IDENT_AMBIGUOUS = 0, 1, 
 IDENT_UNKNOWN = 0xFFFFFFFF         # DH_IDENT_UNKNOWN (== DH_SHAPE_SKIP)
 IDENT_MAX_PAIRS = 1 << 22          # DH_IDENT_MAX_PAIRS
 IDENT_DEFAULT_MAX_RMS = 1.68       # DH_IDENT_DEFAULT_MAX_RMS (mm)
+IDENT_VIEWS_DEFAULT_MAX_RMS = 2.58  # DH_IDENT_VIEWS_DEFAULT_MAX_RMS (mm)
 
 
 class IdentParams(C.Structure):
@@ -263,6 +264,7 @@ EXPORTS = [
     "dh_fit_surface_subjects", "dh_fit_surface_subjects_cameras", "dh_fit_surface_subjects_device", "dh_fit_surface_subjects_cameras_device",
     "dh_fit_ident_params_default", "dh_fit_identify_subjects", "dh_fit_identify_subjects_cameras", "dh_fit_identify_subjects_device",
     "dh_fit_identify_subjects_cameras_device",
+    "dh_fit_ident_views_params_default", "dh_fit_identify_subjects_views", "dh_fit_identify_subjects_views_device",
 ]
 
 

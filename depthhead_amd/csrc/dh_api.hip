@@ -2882,6 +2882,9 @@ struct dh_fitter {
     Buf<uint32_t> ident_sub;
     Buf<dh_ident_record> ident_rec;
     Buf<dh_render_instance> ident_poses;
+    Buf<dh_view_fit_record> ident_vscore;    // multi-view identify calls: one 32-byte score per pair (the poses: ident_pose)
+    Buf<dh_view_fit_record> ident_vfit_rec;  // host multi-view identify calls (frames, instances, sets: the shape_v* staging;
+    Buf<dh_view_instance> ident_vposes;      //   enrolled, subjects and records: the ident_* staging)
     std::vector<unsigned char> view_cmp;     // a captured multi-view call's tables, to be compared with the staged ones
     CallTables tab;                          // models | instances (last: its stream and events go before any buffer)
 };
@@ -3868,6 +3871,25 @@ static int fit_ident_params_default_(dh_ident_params *p) {
     p->max_rms = DH_IDENT_DEFAULT_MAX_RMS; p->min_ratio = 1.0;
     return DH_OK;
 }
+// The refusals of an identify call's dh_ident_params in the header's order (NULL: the defaults with `default_max_rms`, section
+// 27's or section 28's); *out is what the call runs with.
+static int ident_params_check(const dh_ident_params *in, double default_max_rms, dh_ident_params *out, const char *who) {
+    dh_ident_params prm;
+    (void)fit_ident_params_default_(&prm);
+    prm.max_rms = default_max_rms;
+    if (in) prm = *in;
+    if (std::isnan(prm.gate) || std::isnan(prm.lambda) || std::isnan(prm.max_rms) || std::isnan(prm.min_ratio))
+        return fail(DH_EINVAL, "%s: gate %g, lambda %g, max_rms %g, min_ratio %g: a value is NaN", who, prm.gate, prm.lambda, prm.max_rms, prm.min_ratio);
+    if (prm.iterations > 64) return fail(DH_EINVAL, "%s: iterations = %u above 64", who, prm.iterations);
+    if (!(prm.gate > 0.0 && prm.gate <= 4096.0)) return fail(DH_EINVAL, "%s: gate = %g outside (0, 4096]", who, prm.gate);
+    if (!(prm.lambda >= 0.0) || !std::isfinite(prm.lambda)) return fail(DH_EINVAL, "%s: lambda %g, expected a finite value >= 0", who, prm.lambda);
+    if (prm.min_points < 6) return fail(DH_EINVAL, "%s: min_points %u below 6", who, prm.min_points);
+    if (!(prm.max_rms > 0.0)) return fail(DH_EINVAL, "%s: max_rms = %g, expected a value > 0", who, prm.max_rms);
+    if (!(prm.min_ratio >= 1.0)) return fail(DH_EINVAL, "%s: min_ratio = %g below 1", who, prm.min_ratio);
+    if (prm.reserved[0] || prm.reserved[1] || prm.reserved[2]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    *out = prm;
+    return DH_OK;
+}
 // One identify call.  dev: frames / instances / enrolled / fit records / every output are device pointers and `stream` the caller's.
 struct IdentReq {
     const uint16_t *frames; int n, w, h;
@@ -3892,17 +3914,7 @@ static int ident_run(dh_fitter *f, const IdentReq &q, bool dev, hipStream_t stre
     if (q.n_subjects < 1 || q.n_subjects > set->n_subjects)
         return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u, the set's", who, q.n_subjects, set->n_subjects);
     dh_ident_params prm;
-    (void)fit_ident_params_default_(&prm);
-    if (q.prm) prm = *q.prm;
-    if (std::isnan(prm.gate) || std::isnan(prm.lambda) || std::isnan(prm.max_rms) || std::isnan(prm.min_ratio))
-        return fail(DH_EINVAL, "%s: gate %g, lambda %g, max_rms %g, min_ratio %g: a value is NaN", who, prm.gate, prm.lambda, prm.max_rms, prm.min_ratio);
-    if (prm.iterations > 64) return fail(DH_EINVAL, "%s: iterations = %u above 64", who, prm.iterations);
-    if (!(prm.gate > 0.0 && prm.gate <= 4096.0)) return fail(DH_EINVAL, "%s: gate = %g outside (0, 4096]", who, prm.gate);
-    if (!(prm.lambda >= 0.0) || !std::isfinite(prm.lambda)) return fail(DH_EINVAL, "%s: lambda %g, expected a finite value >= 0", who, prm.lambda);
-    if (prm.min_points < 6) return fail(DH_EINVAL, "%s: min_points %u below 6", who, prm.min_points);
-    if (!(prm.max_rms > 0.0)) return fail(DH_EINVAL, "%s: max_rms = %g, expected a value > 0", who, prm.max_rms);
-    if (!(prm.min_ratio >= 1.0)) return fail(DH_EINVAL, "%s: min_ratio = %g below 1", who, prm.min_ratio);
-    if (prm.reserved[0] || prm.reserved[1] || prm.reserved[2]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    TRY(ident_params_check(q.prm, DH_IDENT_DEFAULT_MAX_RMS, &prm, who));
     if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
     const uint64_t pairs = (uint64_t)q.n_inst * q.n_subjects;
     if (pairs > DH_IDENT_MAX_PAIRS)
@@ -4014,6 +4026,163 @@ static int fit_identify_subjects_cameras_device_(dh_fitter *f, const uint16_t *f
                                                  dh_render_instance *poses_out, dh_fit_record *scores, void *stream) {
     return ident_run(f, IdentReq{frames, n, w, h, nullptr, c, true, set, instances, n_instances, enrolled, n_subjects, fit_records, params, subjects_out, records, poses_out, scores},
                      true, (hipStream_t)stream, "dh_fit_identify_subjects_cameras_device");
+}
+
+// ---- identifying enrolled subjects across the views of a rig
+static int fit_ident_views_params_default_(dh_ident_params *p) {
+    if (!p) return fail(DH_EINVAL, "dh_fit_ident_views_params_default: NULL argument");
+    (void)fit_ident_params_default_(p);
+    p->max_rms = DH_IDENT_VIEWS_DEFAULT_MAX_RMS;
+    return DH_OK;
+}
+// One multi-view identify call.  dev: frames / instances / sets / enrolled / fit records / every output are device pointers and
+// `stream` the caller's.
+struct IdentViewsReq {
+    const uint16_t *frames; uint32_t n_sets; int w, h;
+    const dh_fit_views *views;
+    const dh_fit_subjects *set;
+    const dh_view_instance *inst; uint32_t n_inst;
+    const uint32_t *sets; const uint8_t *enrolled; uint32_t n_subjects;
+    const dh_view_fit_record *fit_rec;
+    const dh_ident_params *prm;
+    uint32_t *subjects_out; dh_ident_record *rec; dh_view_instance *poses_out; dh_view_fit_record *scores;
+};
+static int ident_views_run(dh_fitter *f, const IdentViewsReq &q, bool dev, hipStream_t stream, const char *who) {
+    // ---- refusals: all of them before anything is allocated or launched
+    if (!f) return fail(DH_EINVAL, "%s: NULL fitter", who);
+    if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!q.subjects_out) return fail(DH_EINVAL, "%s: NULL subjects_out", who);
+    if (!q.rec) return fail(DH_EINVAL, "%s: NULL records", who);
+    if (!q.set) return fail(DH_EINVAL, "%s: NULL subject set", who);
+    if (!q.views) return fail(DH_EINVAL, "%s: NULL view table", who);
+    if (q.views->device != f->device) return fail(DH_EINVAL, "%s: the view table lives on device %d, the fitter on %d", who, q.views->device, f->device);
+    const int n = q.views->n;
+    if (q.n_sets < 1 || (uint64_t)q.n_sets * (uint64_t)n > 65535)
+        return fail(DH_EINVAL, "%s: n_sets = %u of %d cameras, expected 1 .. 65535 frames", who, q.n_sets, n);
+    TRY(check_frames(n, q.w, q.h, nullptr, q.views->cams, true, f->device, "fitter", who));
+    const dh_fit_subjects *set = q.set;
+    if (set->device != f->device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the fitter on %d", who, set->device, f->device);
+    if (q.n_subjects < 1 || q.n_subjects > set->n_subjects)
+        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u, the set's", who, q.n_subjects, set->n_subjects);
+    dh_ident_params prm;
+    TRY(ident_params_check(q.prm, DH_IDENT_VIEWS_DEFAULT_MAX_RMS, &prm, who));
+    if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
+    const uint64_t pairs = (uint64_t)q.n_inst * q.n_subjects;
+    if (pairs > DH_IDENT_MAX_PAIRS)
+        return fail(DH_EINVAL, "%s: %u instances times %u subjects exceed %u pairs", who, q.n_inst, q.n_subjects, DH_IDENT_MAX_PAIRS);
+    if (q.n_inst == 0) return DH_OK;
+    const double largest = set->basis->largest;
+    if (!dev)
+        for (uint32_t i = 0; i < q.n_inst; ++i) {
+            const dh_view_instance &in = q.inst[i];
+            const uint32_t st = q.sets ? q.sets[i] : 0u;
+            const IdentViewsPart part = dh_ident_views_part(in, st, q.fit_rec ? q.fit_rec + i : nullptr, (uint32_t)n, q.n_sets, set->n, set->radius, largest);
+            switch (part.why) {
+            case DH_IDENT_VIEWS_OK: case DH_IDENT_VIEWS_RECORD: break;
+            case DH_IDENT_VIEWS_WHERE:
+                if (part.skip.why == DH_SHAPE_VIEWS_NO_VIEW) return fail(DH_EINVAL, "%s: instance %u is seen by no view", who, i);
+                if (part.skip.why == DH_SHAPE_VIEWS_CAMERA)
+                    return fail(DH_EINVAL, "%s: instance %u names camera %llu of %d", who, i, (unsigned long long)part.skip.last, n);
+                return fail(DH_EINVAL, "%s: instance %u names set %u of %u", who, i, st, q.n_sets);
+            case DH_IDENT_VIEWS_FAULT: return instance_refusal(part.skip.fault, in.scale, i, set->radius, largest, who);
+            default:
+                return fail(DH_EINVAL, "%s: instance %u sums %llu terms (%d views of %u points), above %u", who, i, (unsigned long long)part.terms,
+                            __builtin_popcountll(in.views), set->n, DH_FIT_MAX_POINTS);
+            }
+        }
+
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return DH_EHIP;
+    TRY(f->tab.init());
+    hipStream_t s = dev ? stream : f->tab.s;
+    IdentViewsArgs g;
+    memset(&g, 0, sizeof g);
+    FitViewsArgs &a = g.f;
+    a.n = n; a.w = q.w; a.h = q.h;
+    a.cams = q.views->cams->dev.get();
+    a.views = q.views->dev.get();
+    a.n_inst = q.n_inst;
+    a.coarse = 0; a.full = prm.iterations; a.min_points = prm.min_points;
+    a.gate[0] = prm.gate; a.gate[1] = prm.gate;
+    a.lam1 = 1.0 + prm.lambda;
+    g.models = set->table.get();
+    g.np = set->n; g.n_subjects = q.n_subjects;
+    g.radius = set->radius; g.largest = largest;
+    g.n_sets = q.n_sets;
+    g.max_ms = prm.max_rms * prm.max_rms; g.min_ratio = prm.min_ratio;
+    // ---- the pair scratch: the fitter's, grown on demand (growing waits for the device, as the other tables do); the poses are
+    // section 27's buffer, which is why all identify calls of a fitter must be stream-ordered with one another
+    const bool own_scores = !dev || !q.scores;
+    if ((own_scores && f->ident_vscore.cap() < pairs) || f->ident_pose.cap() < pairs * 12) {
+        HIP_TRY(hipDeviceSynchronize());
+        if (own_scores) TRY(f->ident_vscore.grow((size_t)pairs));
+        TRY(f->ident_pose.grow((size_t)pairs * 12));
+    }
+    g.pose = f->ident_pose.get();
+    if (!dev) {
+        const size_t n_px = (size_t)q.n_sets * n * q.w * q.h;
+        if (f->frames.cap() < n_px || f->shape_vinst.cap() < q.n_inst || !f->shape_vinst || f->ident_sub.cap() < q.n_inst || !f->ident_vposes ||
+            f->ident_vposes.cap() < q.n_inst || !f->ident_enrolled)
+            HIP_TRY(hipDeviceSynchronize());
+        TRY(f->frames.grow(n_px));
+        if (f->shape_vinst.cap() < q.n_inst || !f->shape_vinst) {
+            TRY(f->shape_vinst.grow(q.n_inst));
+            TRY(f->shape_vsubj.alloc(f->shape_vinst.cap()));
+            TRY(f->shape_vsets.alloc(f->shape_vinst.cap()));
+        }
+        if (f->ident_sub.cap() < q.n_inst) {
+            TRY(f->ident_sub.grow(q.n_inst));
+            TRY(f->ident_rec.alloc(f->ident_sub.cap()));
+            TRY(f->ident_poses.alloc(f->ident_sub.cap()));
+        }
+        if (f->ident_vposes.cap() < q.n_inst || !f->ident_vposes) {
+            TRY(f->ident_vposes.grow(q.n_inst));
+            TRY(f->ident_vfit_rec.alloc(f->ident_vposes.cap()));
+        }
+        if (!f->ident_enrolled) TRY(f->ident_enrolled.alloc(DH_SHAPE_MAX_SUBJECTS));
+        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(f->shape_vinst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_view_instance), hipMemcpyHostToDevice, s));
+        if (q.sets) HIP_TRY(hipMemcpyAsync(f->shape_vsets.get(), q.sets, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (q.enrolled) HIP_TRY(hipMemcpyAsync(f->ident_enrolled.get(), q.enrolled, q.n_subjects, hipMemcpyHostToDevice, s));
+        if (q.fit_rec) HIP_TRY(hipMemcpyAsync(f->ident_vfit_rec.get(), q.fit_rec, (size_t)q.n_inst * sizeof(dh_view_fit_record), hipMemcpyHostToDevice, s));
+        a.frames = f->frames.get(); a.inst = f->shape_vinst.get();
+        g.sets = q.sets ? f->shape_vsets.get() : nullptr;
+        g.enrolled = q.enrolled ? f->ident_enrolled.get() : nullptr;
+        g.fit_rec = q.fit_rec ? f->ident_vfit_rec.get() : nullptr;
+        g.score = f->ident_vscore.get();
+        g.subjects_out = f->ident_sub.get(); g.rec = f->ident_rec.get();
+        g.poses_out = q.poses_out ? f->ident_vposes.get() : nullptr;
+    } else {
+        a.frames = q.frames; a.inst = q.inst;
+        g.sets = q.sets; g.enrolled = q.enrolled; g.fit_rec = q.fit_rec;
+        g.score = q.scores ? q.scores : f->ident_vscore.get();
+        g.subjects_out = q.subjects_out; g.rec = q.rec; g.poses_out = q.poses_out;
+    }
+    // ---- the two stream-ordered operations
+    TRY(hip_step(dh_launch_ident_views_score(g, s), "k_ident_views_score"));
+    TRY(hip_step(dh_launch_ident_views_decide(g, s), "k_ident_views_decide"));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(q.subjects_out, g.subjects_out, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(q.rec, g.rec, (size_t)q.n_inst * sizeof(dh_ident_record), hipMemcpyDeviceToHost, s));
+        if (q.poses_out) HIP_TRY(hipMemcpyAsync(q.poses_out, g.poses_out, (size_t)q.n_inst * sizeof(dh_view_instance), hipMemcpyDeviceToHost, s));
+        if (q.scores) HIP_TRY(hipMemcpyAsync(q.scores, g.score, (size_t)pairs * sizeof(dh_view_fit_record), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return DH_OK;
+}
+static int fit_identify_subjects_views_(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_subjects *set,
+                                        const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint8_t *enrolled, uint32_t n_subjects,
+                                        const dh_view_fit_record *fit_records, const dh_ident_params *params, uint32_t *subjects_out, dh_ident_record *records,
+                                        dh_view_instance *poses_out, dh_view_fit_record *scores) {
+    return ident_views_run(f, IdentViewsReq{frames, n_sets, w, h, views, set, instances, n_instances, sets, enrolled, n_subjects, fit_records, params, subjects_out, records, poses_out, scores},
+                           false, nullptr, "dh_fit_identify_subjects_views");
+}
+static int fit_identify_subjects_views_device_(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_subjects *set,
+                                               const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint8_t *enrolled, uint32_t n_subjects,
+                                               const dh_view_fit_record *fit_records, const dh_ident_params *params, uint32_t *subjects_out, dh_ident_record *records,
+                                               dh_view_instance *poses_out, dh_view_fit_record *scores, void *stream) {
+    return ident_views_run(f, IdentViewsReq{frames, n_sets, w, h, views, set, instances, n_instances, sets, enrolled, n_subjects, fit_records, params, subjects_out, records, poses_out, scores},
+                           true, (hipStream_t)stream, "dh_fit_identify_subjects_views_device");
 }
 
 // ------------------------------------------------------------------ adapting a model's shape across views
@@ -4849,6 +5018,9 @@ DH_API(fit_identify_subjects, (dh_fitter *f, const uint16_t *frames, int n, int 
 DH_API(fit_identify_subjects_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint8_t *enrolled, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_ident_params *params, uint32_t *subjects_out, dh_ident_record *records, dh_render_instance *poses_out, dh_fit_record *scores), (f, frames, n, w, h, c, set, instances, n_instances, enrolled, n_subjects, fit_records, params, subjects_out, records, poses_out, scores))
 DH_API(fit_identify_subjects_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint8_t *enrolled, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_ident_params *params, uint32_t *subjects_out, dh_ident_record *records, dh_render_instance *poses_out, dh_fit_record *scores, void *stream), (f, frames, n, w, h, K, set, instances, n_instances, enrolled, n_subjects, fit_records, params, subjects_out, records, poses_out, scores, stream))
 DH_API(fit_identify_subjects_cameras_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint8_t *enrolled, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_ident_params *params, uint32_t *subjects_out, dh_ident_record *records, dh_render_instance *poses_out, dh_fit_record *scores, void *stream), (f, frames, n, w, h, c, set, instances, n_instances, enrolled, n_subjects, fit_records, params, subjects_out, records, poses_out, scores, stream))
+DH_API(fit_ident_views_params_default, (dh_ident_params *p), (p))
+DH_API(fit_identify_subjects_views, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_subjects *set, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint8_t *enrolled, uint32_t n_subjects, const dh_view_fit_record *fit_records, const dh_ident_params *params, uint32_t *subjects_out, dh_ident_record *records, dh_view_instance *poses_out, dh_view_fit_record *scores), (f, frames, n_sets, w, h, views, set, instances, n_instances, sets, enrolled, n_subjects, fit_records, params, subjects_out, records, poses_out, scores))
+DH_API(fit_identify_subjects_views_device, (dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_subjects *set, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint8_t *enrolled, uint32_t n_subjects, const dh_view_fit_record *fit_records, const dh_ident_params *params, uint32_t *subjects_out, dh_ident_record *records, dh_view_instance *poses_out, dh_view_fit_record *scores, void *stream), (f, frames, n_sets, w, h, views, set, instances, n_instances, sets, enrolled, n_subjects, fit_records, params, subjects_out, records, poses_out, scores, stream))
 DH_API(fit_shape_subjects, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records), (f, frames, n, w, h, K, set, instances, n_instances, subjects, n_subjects, fit_records, params, records))
 DH_API(fit_shape_subjects_cameras, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records), (f, frames, n, w, h, c, set, instances, n_instances, subjects, n_subjects, fit_records, params, records))
 DH_API(fit_shape_subjects_device, (dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set, const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_fit_record *fit_records, const dh_shape_params *params, dh_shape_record *records, void *stream), (f, frames, n, w, h, K, set, instances, n_instances, subjects, n_subjects, fit_records, params, records, stream))

@@ -1,9 +1,9 @@
 // dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip,
-// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip, k_ident.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
+// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip, k_ident.hip, k_ident_views.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
 // words of both trackers, and the one test of whether an instance may be fitted (dh_fit_instance_fault: the host's refusals and
 // the shape kernel's skips).  The device arithmetic the kernels share among themselves is in dh_fit_device.h.  Not part of the
 // ABI.  The rules are stated in include/depthhead_hip.h (sections "fitting posed models to depth frames" and after) and
-// DESIGN.md sections 18 - 27.
+// DESIGN.md sections 18 - 28.
 #pragma once
 #include "dh_internal.h"
 #include "dh_rig_fit.h"
@@ -667,3 +667,50 @@ struct IdentArgs {
 };
 hipError_t dh_launch_ident_score(const IdentArgs &a, hipStream_t s);       // one workgroup per pair, the subject the fast index
 hipError_t dh_launch_ident_decide(const IdentArgs &a, hipStream_t s);      // one wave per instance
+
+// ---- identifying enrolled subjects across the views of a rig (k_ident_views.hip)
+// Magnitudes.  A pair's passes are section 21's at a model of the set: the extent test with the set's bound keeps |scale| |v'| <=
+// 4096 for every model the set can hold (sections 25 and 26), the view table is within DH_FIT_VIEW_TOLERANCE by construction, and
+// an instance takes part only while popcount(views) * (the set's points) <= DH_FIT_MAX_POINTS: section 21's 2^62 stands.  The
+// decision reads scores and is section 27's functions above as they are.
+
+// Why an instance of a multi-view identification takes no part, the header's six tests in their order, stated once for the
+// host loop (which refuses what is no SKIP of the fit record) and for both kernels (which skip the instance as a whole).  Tests
+// 1 - 3 and 5 are dh_shape_views_skip's with subject 0 of 1: it makes 5 after 3, and the fit record's test is put between them
+// here.  fit_rec: the instance's own record, or NULL; np: the set's points; a NaN fails each test.  An instance that passes names
+// only cameras < n and a set < n_sets, and sums at most DH_FIT_MAX_POINTS (view, point) terms.
+enum { DH_IDENT_VIEWS_OK = 0, DH_IDENT_VIEWS_WHERE, DH_IDENT_VIEWS_RECORD, DH_IDENT_VIEWS_FAULT, DH_IDENT_VIEWS_TERMS };
+struct IdentViewsPart {
+    int why;                      // DH_IDENT_VIEWS_*
+    ShapeViewsSkip skip;          // WHERE (no view, a camera >= n, a set >= n_sets) and FAULT: what dh_shape_views_skip found
+    uint64_t terms;               // TERMS: popcount(views) * np
+};
+__host__ __device__ inline IdentViewsPart dh_ident_views_part(const dh_view_instance &in, uint32_t set, const dh_view_fit_record *fit_rec, uint32_t n,
+                                                              uint32_t n_sets, uint32_t np, double radius, double largest) {
+    IdentViewsPart p{DH_IDENT_VIEWS_OK, dh_shape_views_skip(in, set, 0u, n, n_sets, 1u, radius, largest), 0};
+    p.terms = (uint64_t)__builtin_popcountll(in.views) * np;
+    if (p.skip.why != DH_SHAPE_VIEWS_OK && p.skip.why != DH_SHAPE_VIEWS_FAULT) p.why = DH_IDENT_VIEWS_WHERE;
+    else if (fit_rec && fit_rec->status != DH_FIT_OK) p.why = DH_IDENT_VIEWS_RECORD;
+    else if (p.skip.why == DH_SHAPE_VIEWS_FAULT) p.why = DH_IDENT_VIEWS_FAULT;
+    else if (p.terms > DH_FIT_MAX_POINTS) p.why = DH_IDENT_VIEWS_TERMS;
+    return p;
+}
+
+struct IdentViewsArgs {
+    FitViewsArgs f;               // frames [n_sets][n][h][w], n, w, h, cams, views, inst, n_inst; coarse 0, full = iterations, both gates = gate, lam1, min_points; models, out and rec unused
+    const SubjectModel *models;   // [S] (n_subjects <= S)
+    uint32_t np, n_subjects;      // the set's points; the candidates' range
+    double radius, largest;       // the set's bound, the basis's largest |B_k[i]|
+    const uint32_t *sets;         // nullable [n_inst]
+    uint32_t n_sets;
+    const uint8_t *enrolled;      // nullable [n_subjects]
+    const dh_view_fit_record *fit_rec;   // nullable [n_inst]
+    dh_view_fit_record *score;    // [n_inst][n_subjects]: the caller's `scores` or the fitter's scratch
+    float *pose;                  // [n_inst][n_subjects][12]: R then t of each pair's refit (the fitter's scratch, section 27's)
+    double max_ms, min_ratio;     // max_rms * max_rms (one f64 product on the host), min_ratio
+    uint32_t *subjects_out;       // [n_inst]
+    dh_ident_record *rec;         // [n_inst]
+    dh_view_instance *poses_out;  // nullable [n_inst]
+};
+hipError_t dh_launch_ident_views_score(const IdentViewsArgs &a, hipStream_t s);    // one workgroup per pair, the subject the fast index
+hipError_t dh_launch_ident_views_decide(const IdentViewsArgs &a, hipStream_t s);   // one wave per instance

@@ -3,6 +3,7 @@
 //   the shape step's point loop and reduction              k_fit_shape.hip, k_fit_shape_views.hip, k_subjects.hip
 //   the pose, the modes of a pass, the step's helpers      k_fit.hip, k_fit_views.hip (each with its *_sched instance)
 //   the single-view pass                                   k_fit.hip, k_ident.hip
+//   the multi-view pass                                    k_fit_views.hip, k_ident_views.hip
 //   the trackers' rule: table rotation, carried start,
 //   acceptance, jump test and the state updates            k_fit_track.hip, k_rig_fit_track.hip
 // f64 (the trackers: f32 too) with + - * /, compares and casts only; every operation is rounded on its own, so the expression
@@ -89,6 +90,13 @@ __device__ __forceinline__ double uni(double v) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// A double from lane (this lane ^ o) of the wave (the decide kernels of k_ident.hip and k_ident_views.hip merge their picks with it).
+__device__ __forceinline__ double shfl_xor_f64(double v, int o) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)b, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(b >> 32), o);
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
@@ -283,6 +291,105 @@ __device__ __forceinline__ void fit_pass(const FitArgs &a, const FitModel &m, co
     if (MODE == FIT_LAST) {
         const unsigned long long s = wave_sum_u64((uint64_t)e);
         if (lead) atomicAdd(&s_sum[DH_FIT_E], s);
+    }
+    {
+        const unsigned long long s = wave_sum_u64((uint64_t)cnt);
+        if (lead) atomicAdd(&s_sum[DH_FIT_COUNT], s);
+    }
+    __syncthreads();
+}
+
+// ---- the multi-view fit's pass (k_fit_views.hip and k_ident_views.hip; DESIGN.md sections 21 and 28)
+// One pass at the world pose `pose` with gate `gate` over the views of `mask` (bit k: camera first_cam + k): the sums of MODE
+// into s_sum (zeroed here; valid for every lane after the return).
+template <int MODE, bool STAGED>
+__device__ __forceinline__ void fit_views_pass(const FitViewsArgs &a, const FitModel &m, const float *s_pts, uint32_t first_cam, uint64_t mask,
+                                               double scale, const FitPose &pose, double gate, unsigned long long *s_sum) {
+    constexpr int NJ = MODE == FIT_COARSE ? 3 : MODE == FIT_FULL ? 6 : 0;
+    constexpr int NA = NJ * (NJ + 1) / 2;
+    long long accA[NA > 0 ? NA : 1], accB[NJ > 0 ? NJ : 1];
+#pragma unroll
+    for (int k = 0; k < (NA > 0 ? NA : 1); ++k) accA[k] = 0;
+#pragma unroll
+    for (int k = 0; k < (NJ > 0 ? NJ : 1); ++k) accB[k] = 0;
+    long long e = 0, cnt = 0;
+    uint64_t used = 0;                             // (uniform over the wave)
+    __syncthreads();                               // every lane has read the sums of the pass before
+    if (threadIdx.x < 32) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    const double dw = (double)a.w, dh = (double)a.h;
+    for (uint64_t rest = mask; rest; rest &= rest - 1) {
+        const uint32_t bit = (uint32_t)__builtin_ctzll(rest);
+        const uint32_t cam = first_cam + bit;      // < a.n: the host refused the call otherwise
+        const uint16_t *frame = a.frames + (size_t)cam * a.h * a.w;
+        const FitView *vw = a.views + cam;
+        double V[9], K[9], Rv[9], tv[3];
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            V[q] = uni((double)vw->V[q]);
+            K[q] = uni((double)a.cams[cam].k[q]);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                Rv[3 * i + j] = uni((V[3 * i] * pose.R[j] + V[3 * i + 1] * pose.R[3 + j]) + V[3 * i + 2] * pose.R[6 + j]);
+            tv[i] = uni(((V[3 * i] * pose.t[0] + V[3 * i + 1] * pose.t[1]) + V[3 * i + 2] * pose.t[2]) + (double)vw->u[i]);
+        }
+        const long long before = cnt;
+        for (uint32_t i = threadIdx.x; i < m.n; i += DH_FIT_THREADS) {
+            double v[3], nm[3];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                v[ax] = (double)(STAGED ? s_pts[ax * DH_FIT_LDS_POINTS + i] : m.pts[(size_t)i * 3 + ax]);
+                nm[ax] = (double)(STAGED ? s_pts[(3 + ax) * DH_FIT_LDS_POINTS + i] : m.nrm[(size_t)i * 3 + ax]);
+            }
+            DH_FIT_CORRESPOND(v, nm, scale, Rv, tv, K, frame, a.w, dw, dh, gate);
+            if (MODE == FIT_LAST) e += (long long)((res * res) * DH_FIT_S);
+            else {
+                double J[6];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) J[j] = (V[j] * n[0] + V[3 + j] * n[1]) + V[6 + j] * n[2];
+                if (MODE == FIT_FULL) {
+                    const double q0 = p[0] - tv[0], q1 = p[1] - tv[1], q2 = p[2] - tv[2];
+                    const double m0 = q1 * n[2] - q2 * n[1];
+                    const double m1 = q2 * n[0] - q0 * n[2];
+                    const double m2 = q0 * n[1] - q1 * n[0];
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) J[3 + j] = (V[j] * m0 + V[3 + j] * m1) + V[6 + j] * m2;
+                }
+                int k = 0;
+#pragma unroll
+                for (int ja = 0; ja < NJ; ++ja) {
+#pragma unroll
+                    for (int jb = ja; jb < NJ; ++jb) accA[k++] += (long long)((J[ja] * J[jb]) * DH_FIT_S);
+                    accB[ja] += (long long)((J[ja] * res) * DH_FIT_S);
+                }
+            }
+            cnt += 1;
+        }
+        if (MODE == FIT_LAST && __ballot(cnt != before) != 0) used |= 1ull << bit;
+    }
+    const bool lead = (threadIdx.x & 63) == 0;
+    {
+        int k = 0;
+#pragma unroll
+        for (int ja = 0; ja < NJ; ++ja) {
+#pragma unroll
+            for (int jb = ja; jb < NJ; ++jb) {
+                const unsigned long long s = wave_sum_u64((uint64_t)accA[k++]);
+                if (lead) atomicAdd(&s_sum[DH_FIT_PAIR(6, ja, jb)], s);
+            }
+            const unsigned long long s = wave_sum_u64((uint64_t)accB[ja]);
+            if (lead) atomicAdd(&s_sum[DH_FIT_B + ja], s);
+        }
+    }
+    if (MODE == FIT_LAST) {
+        const unsigned long long s = wave_sum_u64((uint64_t)e);
+        if (lead) {
+            atomicAdd(&s_sum[DH_FIT_E], s);
+            atomicOr(&s_sum[DH_FIT_USED], (unsigned long long)used);
+        }
     }
     {
         const unsigned long long s = wave_sum_u64((uint64_t)cnt);

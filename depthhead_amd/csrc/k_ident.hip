@@ -95,12 +95,8 @@ __global__ __launch_bounds__(DH_FIT_THREADS) void k_ident_score(const IdentArgs 
     } else ident_run<false>(q, in, m, s_pts, s_sum, pair);
 }
 
-__device__ __forceinline__ double shfl_xor_f64(double v, int o) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)b, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(b >> 32), o);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
+// (k_ident_views_decide, k_ident_views.hip, is this kernel over rows of dh_view_fit_record with a dh_view_instance pose: the strided
+// picks, the shuffle reduction and lane 0's record are the same statements there, and a change to either belongs in both)
 __global__ __launch_bounds__(DH_IDENT_THREADS) void k_ident_decide(const IdentArgs q) {
     const uint32_t i = blockIdx.x;
     const dh_render_instance *in = q.f.inst + i;

@@ -213,6 +213,17 @@ def ident_params(iterations=None, min_points=None, gate=None, lam=None, max_rms=
     return p
 
 
+def ident_views_params(iterations=None, min_points=None, gate=None, lam=None, max_rms=None, min_ratio=None) -> "_lib.IdentParams":
+    """dh_fit_ident_views_params_default -- the multi-view call's own measured max_rms -- with the given fields replaced."""
+    p = _lib.IdentParams()
+    check(_lib.load().dh_fit_ident_views_params_default(C.byref(p)))
+    for name, value, cast in (("iterations", iterations, int), ("min_points", min_points, int), ("gate", gate, float), ("lam", lam, float),
+                              ("max_rms", max_rms, float), ("min_ratio", min_ratio, float)):
+        if value is not None:
+            setattr(p, name, cast(value))
+    return p
+
+
 def calib_params(gate=None, lam=None, min_points=None, pivot=None) -> "_lib.CalibParams":
     """dh_calib_params_default with the given fields replaced."""
     p = _lib.CalibParams()
@@ -582,6 +593,61 @@ class Fitter(_lib._Handle):
                                                   C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
         return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
 
+    def identify_subjects_views(self, frames, views, subjects_set, instances, sets=None, n_subjects=None, enrolled=None, fit_records=None,
+                                params=None, scores: bool = False, device_out: bool = False, stream=None):
+        """Which enrolled subject of a `Subjects` set each world-posed instance is, decided from all the cameras that see it
+        (DESIGN.md section 28): `identify_subjects` with the multi-view fit for the score.  frames [n_sets, n, h, w] u16 -- frame
+        [s, c] is camera c of `views` (a `Views` of n cameras) at set s; instances VIEW_INSTANCE_DTYPE (what fit_views returned),
+        sets [n_instances] u32 (None: all in set 0), fit_records VIEW_FIT_RECORD_DTYPE (what fit_views returned with them).
+        params None selects the multi-view defaults (`ident_views_params`).  Returns (subjects u32 [n_instances], IDENT_RECORD_DTYPE
+        records, the instances with the best candidate's refitted world pose) and, with scores=True, every pair's
+        VIEW_FIT_RECORD_DTYPE [n_instances, n_subjects] after them.  Host form: numpy arrays.  With device_out=True frames,
+        instances, sets (int32), enrolled (uint8) and fit_records are torch tensors on the device and the results come back as torch
+        tensors (subjects int32, the others uint8): two kernels ordered on `stream`, no host wait.  All identify calls of one
+        fitter must be ordered on one stream."""
+        n_sets, n, h, w = (int(v) for v in frames.shape)
+        if n != len(views):
+            raise ValueError(f"{n} frames a set for a view table of {len(views)} cameras")
+        prm = C.byref(params) if params is not None else None
+        ns = len(subjects_set) if n_subjects is None else int(n_subjects)
+        if not device_out:
+            fr = np.ascontiguousarray(frames, dtype=np.uint16)
+            inst = np.ascontiguousarray(instances, dtype=VIEW_INSTANCE_DTYPE)
+            ni = len(inst)
+            st = None if sets is None else np.ascontiguousarray(sets, dtype=np.uint32).reshape(ni)
+            enr = None if enrolled is None else np.ascontiguousarray(np.asarray(enrolled) != 0, dtype=np.uint8).reshape(max(ns, 0))
+            frec = None if fit_records is None else np.ascontiguousarray(fit_records, dtype=VIEW_FIT_RECORD_DTYPE).reshape(ni)
+            sub, rec = np.full(ni, IDENT_UNKNOWN, np.uint32), np.zeros(ni, IDENT_RECORD_DTYPE)
+            poses, sc = np.zeros(ni, VIEW_INSTANCE_DTYPE), np.zeros((ni, max(ns, 0)), VIEW_FIT_RECORD_DTYPE)
+            check(self._lib.dh_fit_identify_subjects_views(self._h, vp(fr), C.c_uint32(n_sets), w, h, views._h, subjects_set._h,
+                                                           vp(inst) if ni else None, C.c_uint32(ni), vp(st), vp(enr), C.c_uint32(ns), vp(frec), prm,
+                                                           vp(sub), vp(rec), vp(poses), vp(sc) if scores else None))
+            return (sub, rec, poses, sc) if scores else (sub, rec, poses)
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
+            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
+        ni = instances.numel() * instances.element_size() // VIEW_INSTANCE_DTYPE.itemsize
+        if sets is not None and (sets.numel() != ni or sets.element_size() != 4 or not sets.is_contiguous()):
+            raise ValueError("device sets: a contiguous 32-bit tensor with one word per instance is expected")
+        if enrolled is not None and (enrolled.numel() != ns or enrolled.element_size() != 1 or not enrolled.is_contiguous()):
+            raise ValueError("device enrolled: a contiguous 8-bit tensor with one byte per subject is expected")
+        if fit_records is not None and (fit_records.numel() * fit_records.element_size() != ni * VIEW_FIT_RECORD_DTYPE.itemsize
+                                        or not fit_records.is_contiguous()):
+            raise ValueError("device fit_records: the contiguous tensor of one dh_view_fit_record per instance is expected")
+        sub = torch.empty(max(ni, 1), dtype=torch.int32, device=dev)
+        rec = torch.empty(max(ni, 1) * IDENT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        poses = torch.empty(max(ni, 1) * VIEW_INSTANCE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        sc = torch.empty(max(ni * ns, 1) * VIEW_FIT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev) if scores else None
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        check(self._lib.dh_fit_identify_subjects_views_device(
+            self._h, C.c_void_p(frames.data_ptr()), C.c_uint32(n_sets), w, h, views._h, subjects_set._h,
+            C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni), C.c_void_p(sets.data_ptr()) if sets is not None else None,
+            C.c_void_p(enrolled.data_ptr()) if enrolled is not None else None, C.c_uint32(ns),
+            C.c_void_p(fit_records.data_ptr()) if fit_records is not None else None, prm, C.c_void_p(sub.data_ptr()), C.c_void_p(rec.data_ptr()),
+            C.c_void_p(poses.data_ptr()), C.c_void_p(sc.data_ptr()) if scores else None, C.c_void_p(s)))
+        out = (sub[:ni], rec[:ni * IDENT_RECORD_DTYPE.itemsize], poses[:ni * VIEW_INSTANCE_DTYPE.itemsize])
+        return out + (sc[:ni * ns * VIEW_FIT_RECORD_DTYPE.itemsize],) if scores else out
 
     def calibrate_step(self, frames, views, model, instances, sets=None, take=None, hold=None, params=None, device_out: bool = False,
                        stream=None):
@@ -841,6 +907,33 @@ def recognise_subjects(fitter, frames, K_or_cameras, subjects, starts, model, en
     torch.cuda.current_stream(dev).synchronize()
     return (d_sub.cpu().numpy().view(np.uint32).copy(), d_rec.cpu().numpy().view(IDENT_RECORD_DTYPE).copy(),
             d_poses.cpu().numpy().view(RENDER_INSTANCE_DTYPE).copy(), d_frec.cpu().numpy().view(FIT_RECORD_DTYPE).copy())
+
+
+def recognise_subjects_views(fitter, frames, views, subjects, starts, model, enrolled=None, fit_prm=None, ident_prm=None):
+    """`recognise_subjects` for one moment of a rig.  frames [n, h, w] u16 (numpy), camera c's frame at index
+    c, go to the device once; `starts` are VIEW_INSTANCE_DTYPE [m] rough world poses with their view masks.  Every start is fitted
+    with `model` (the generic head: a `Model`) over its views by `Fitter.fit_views` under fit_prm, then
+    `Fitter.identify_subjects_views` runs from those instances and records with n_sets = 1 against the candidates of `subjects`
+    under ident_prm -- all enqueued on the current torch stream, nothing read in between and once at the end.  Returns (subjects u32
+    [m] with IDENT_UNKNOWN for an unknown head, IDENT_RECORD_DTYPE [m], the instances at the best candidate's refitted world pose,
+    the generic fit's VIEW_FIT_RECORD_DTYPE [m])."""
+    import torch
+    dev = torch.device("cuda", fitter.device)
+    inst = np.array(starts, dtype=VIEW_INSTANCE_DTYPE)
+    inst["model"] = 0
+    if len(inst) == 0:
+        return np.zeros(0, np.uint32), np.zeros(0, IDENT_RECORD_DTYPE), inst, np.zeros(0, VIEW_FIT_RECORD_DTYPE)
+    host = np.ascontiguousarray(frames, dtype=np.uint16)
+    d_frames = torch.from_numpy((host if host.flags.writeable else host.copy()).view(np.int16)).to(dev)
+    d_enr = None
+    if enrolled is not None:
+        d_enr = torch.from_numpy(np.ascontiguousarray(np.asarray(enrolled) != 0, dtype=np.uint8).reshape(len(subjects))).to(dev)
+    d_inst, d_frec = fitter.fit_views(d_frames, [model], inst, views, params=fit_prm, device_out=True)
+    d_sub, d_rec, d_poses = fitter.identify_subjects_views(d_frames.reshape(1, *d_frames.shape), views, subjects, d_inst, enrolled=d_enr,
+                                                           fit_records=d_frec, params=ident_prm, device_out=True)
+    torch.cuda.current_stream(dev).synchronize()
+    return (d_sub.cpu().numpy().view(np.uint32).copy(), d_rec.cpu().numpy().view(IDENT_RECORD_DTYPE).copy(),
+            d_poses.cpu().numpy().view(VIEW_INSTANCE_DTYPE).copy(), d_frec.cpu().numpy().view(VIEW_FIT_RECORD_DTYPE).copy())
 
 
 def adapt_views(fitter, frames, views, verts, tris, basis, starts, sets=None, rounds: int = 6, fit_prm=None, shape_prm=None, coeffs=None):

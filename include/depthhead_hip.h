@@ -1583,6 +1583,82 @@ int dh_fit_identify_subjects_cameras_device(dh_fitter *f, const uint16_t *frames
                                             const dh_ident_params *params, uint32_t *subjects_out, dh_ident_record *records,
                                             dh_render_instance *poses_out, dh_fit_record *scores, void *stream);
 
+/* ---- identifying enrolled subjects across the views of a rig ----
+ * The call above asks the gallery about a head seen through ONE camera.  A rig's fit (section 21) ends in one WORLD pose per person
+ * and the mask of the cameras that see it; this call asks the gallery about such a person from ALL those cameras at once: one score
+ * per (person, candidate), its sums taken over every (view, point) pair.  Not in the reference: PARITY UNPINNED, the definition
+ * below is this library's.  The arithmetic conventions are the fit's: f64 with + - * /, compares and casts; every operation rounded
+ * on its own; the sums are int64 (their order is free); no floating-point atomic; no library function on the device.
+ * INPUTS: frames [n_sets][n][h][w] u16 with n the view table's cameras -- frame s * n + c is camera c at set s, as in
+ *   dh_fit_shape_views*; a dh_fit_views table and through it the camera table; a subject set (ordinary or surface); n_instances
+ *   dh_view_instance -- what dh_fit_depth_views* wrote; `model` and `flags` are ignored; sets[n_instances] (NULL: every instance is
+ *   in set 0); enrolled[n_subjects], u8, nullable (NULL: every subject is a candidate), and n_subjects <= S, as in the section
+ *   above; fit_records[n_instances] of dh_view_fit_record, nullable; a dh_ident_params (NULL: dh_fit_ident_views_params_default).
+ * TAKING PART.  Instance i takes part when every one of these tests passes, in this order, a NaN failing each:
+ *     1. views != 0;
+ *     2. the highest set bit of views names a camera first_cam + k < n;
+ *     3. its set is < n_sets;
+ *     4. where fit records are given, fit_records[i].status is DH_FIT_OK;
+ *     5. none of the refusals of section 18 and 20 for R, t and scale applies, with the set's bound for the model's radius and the
+ *        basis's largest |B_k[i]|;
+ *     6. popcount(views) * (the set's points) <= DH_FIT_MAX_POINTS, which keeps section 21's bound of 2^62 on the sums.
+ *   (1 - 3 and 5 are the tests of dh_fit_shape_views* for one subject.)
+ * THE SCORE of pair (i, s), for every instance i that takes part and every candidate s, is section 21's fit of subject s's model AS
+ *   THE SET HOLDS IT NOW, started at the instance's world (R, t) with its scale, over the views of its mask, in the frames of its
+ *   set (frame sets[i] * n + c for camera c), on the schedule coarse_iterations = 0, `iterations` full steps at gate `gate` with
+ *   `lambda`, and `min_points` for the fit's own min_points -- DH_FIT_FEW_POINTS, DH_FIT_SINGULAR and the early exit as in section 21 --
+ *   then the last pass at `gate`.  The score is that fit's dh_view_fit_record (points, steps, status, sum_r2_fixed, views_used) and
+ *   its refitted world pose, R and t rounded to f32 once.  With iterations = 0 it is one pass at the given pose.
+ * THE DECISION is the section above's, unchanged, over the scores' points, status and sum_r2_fixed: the eligible candidates, the
+ *   mean square m_s (two divisions), the order with its tie to the lower index, DH_IDENT_SKIPPED / NO_CANDIDATE / FAR / AMBIGUOUS /
+ *   OK, and DH_IDENT_UNKNOWN == DH_SHAPE_SKIP.  All candidates of an instance share one view mask, so points counts the same (view,
+ *   point) pairs for each and the means are comparable; m_s is a mean over all the views.
+ * OUTPUTS per instance.  subjects_out[i] and records[i] (a dh_ident_record) as in the section above.  poses_out[i], nullable, a
+ *   dh_view_instance: the input with R and t replaced by the best pair's refitted world pose where there is a best, else the input
+ *   copied through.  scores, nullable, [n_instances][n_subjects] dh_view_fit_record: every pair's score; a pair that did not run
+ *   holds zeros.
+ * IDENTITY WITH THE SINGLE-VIEW CALL.  With one view, V = I, u = 0 and n_sets = 1 every subject, every record byte and every
+ *   refitted pose equals dh_fit_identify_subjects_cameras on the same pose, and every score equals the single-view score in its
+ *   first 24 bytes (section 21 shows that every sum is then section 18's).
+ * dh_fit_identify_subjects_views takes host frames, instances, sets, enrolled, fit_records and outputs and is synchronous.
+ *   dh_fit_identify_subjects_views_device takes all of these on the device (params stays host memory), enqueues exactly two
+ *   kernels on `stream` (NULL = default stream) -- k_ident_views_score, one workgroup per (instance, subject) pair, and
+ *   k_ident_views_decide, one wave per instance -- and never waits on the host: it chains after dh_fit_depth_views_device, whose
+ *   `out` and `records` are its `instances` and `fit_records`.  The pair scratch is the fitter's and grows as the section above's
+ *   does (growing waits for the device; a call that fits allocates nothing); the poses share that section's buffer, so ALL IDENTIFY
+ *   CALLS OF ONE FITTER, of this section and the one above, MUST BE STREAM-ORDERED WITH ONE ANOTHER.
+ *   DH_EINVAL, before anything is launched and with nothing written, in this order: NULL fitter, frames, subjects_out, records,
+ *   subject set; a NULL view table or one of another device than the fitter; n_sets of 0 or n_sets * n above 65535; w or h outside
+ *   1 .. DH_RENDER_MAX_SIZE; a set on another device than the fitter; n_subjects outside 1 .. S; the params' refusals of the section
+ *   above, in its order; NULL instances with n_instances > 0; n_instances * n_subjects above DH_IDENT_MAX_PAIRS.  The host form then
+ *   refuses, per instance, each of the tests of TAKING PART in their order -- except that an instance which passes tests 1 - 3 and
+ *   whose fit record is not DH_FIT_OK is no error: it is DH_IDENT_SKIPPED.  The _device form cannot read the instances: the device
+ *   skips, AS A WHOLE, every instance that fails a test (DH_IDENT_SKIPPED), so no input leads out of a buffer or out of the
+ *   magnitude bound.  n_instances = 0 is no error and writes nothing.
+ *   Bit-identical run to run and to tests/ident_views_ref.py.
+ * THE DEFAULT max_rms of this call is measured on its own (tests/test_ident_views_ref.py): section 27's 1.68
+ *   was measured on single 320x240 views and does not carry over to a rig of 160x120 cameras.  Three subjects enrolled from the
+ *   middle camera's frames of 4 sets each; 4 further sets of each and of a stranger fitted and identified over three views.  The
+ *   largest best mean square of the 12 known probes was 4.0152 mm^2, the smallest of the 4 stranger probes 10.9989 mm^2; the
+ *   default is the square root of their geometric mean, rounded to 2.58. */
+#define DH_IDENT_VIEWS_DEFAULT_MAX_RMS 2.58   /* mm: sqrt(sqrt(4.0152 * 10.9989)) = 2.5779 (the measurement above) */
+/* dh_fit_ident_params_default with max_rms = DH_IDENT_VIEWS_DEFAULT_MAX_RMS */
+int dh_fit_ident_views_params_default(dh_ident_params *p);
+/* frames [n_sets][n][h][w] u16 with n the view table's cameras; instances and sets (or NULL) [n_instances]; enrolled [n_subjects] u8
+ * or NULL; fit_records [n_instances] or NULL; subjects_out [n_instances] u32; records [n_instances]; poses_out [n_instances] or
+ * NULL; scores [n_instances][n_subjects] or NULL */
+int dh_fit_identify_subjects_views(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views,
+                                   const dh_fit_subjects *set, const dh_view_instance *instances, uint32_t n_instances,
+                                   const uint32_t *sets, const uint8_t *enrolled, uint32_t n_subjects,
+                                   const dh_view_fit_record *fit_records, const dh_ident_params *params, uint32_t *subjects_out,
+                                   dh_ident_record *records, dh_view_instance *poses_out, dh_view_fit_record *scores);
+int dh_fit_identify_subjects_views_device(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views,
+                                          const dh_fit_subjects *set, const dh_view_instance *instances, uint32_t n_instances,
+                                          const uint32_t *sets, const uint8_t *enrolled, uint32_t n_subjects,
+                                          const dh_view_fit_record *fit_records, const dh_ident_params *params, uint32_t *subjects_out,
+                                          dh_ident_record *records, dh_view_instance *poses_out, dh_view_fit_record *scores,
+                                          void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
