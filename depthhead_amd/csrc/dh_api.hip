@@ -2857,39 +2857,79 @@ static int fit_params_default_(dh_fit_params *p) {
     return DH_OK;
 }
 
-// A fitter: the call's tables and, for the host calls, the frames and the outputs on the device.  Everything grows on demand and
-// is kept between calls.
+// A fitter: the call's tables, the kernels' scratch (both forms of a call use it) and one arena that holds the device copy of a
+// host call's arguments, which CallArgs slices anew for every call.  Everything grows on demand and is
+// kept between calls.
 struct dh_fitter {
     int device = 0;
-    Buf<uint16_t> frames;                    // host calls
-    Buf<dh_render_instance> out;
-    Buf<dh_fit_record> rec;
+    Buf<unsigned char> arena;                // host calls: every array the call passes or returns, one 256-byte aligned slice each
     Buf<unsigned long long> shape_sums;      // shape calls: [DH_SHAPE_MAX_SUBJECTS][DH_SHAPE_STRIDE], taken at the first one
-    Buf<dh_render_instance> shape_inst;      // host shape calls
-    Buf<uint32_t> shape_subj;
-    Buf<dh_shape_record> shape_rec;
-    Buf<dh_fit_record> shape_fit_rec;        // host shape calls over a subject set: the instances' fit records
-    Buf<dh_view_instance> shape_vinst;       // host multi-view shape calls
-    Buf<uint32_t> shape_vsubj, shape_vsets;
     Buf<unsigned long long> calib_sums;      // calibration calls: [cameras][DH_CALIB_STRIDE], taken at the first one of a table size
-    Buf<uint8_t> calib_hold;                 // host calibration calls (instances, sets and take: the shape_v* staging)
-    Buf<dh_calib_record> calib_rec;
-    Buf<dh_view_instance> view_out;          // host multi-view calls
-    Buf<dh_view_fit_record> view_rec;
     Buf<dh_fit_record> ident_score;          // identify calls: one score and one pose (R, t: 12 floats) per (instance, subject) pair
     Buf<float> ident_pose;
-    Buf<uint8_t> ident_enrolled;             // host identify calls (frames, instances and fit records: the shape staging)
-    Buf<uint32_t> ident_sub;
-    Buf<dh_ident_record> ident_rec;
-    Buf<dh_render_instance> ident_poses;
     Buf<dh_view_fit_record> ident_vscore;    // multi-view identify calls: one 32-byte score per pair (the poses: ident_pose)
-    Buf<dh_view_fit_record> ident_vfit_rec;  // host multi-view identify calls (frames, instances, sets: the shape_v* staging;
-    Buf<dh_view_instance> ident_vposes;      //   enrolled, subjects and records: the ident_* staging)
     std::vector<unsigned char> view_cmp;     // a captured multi-view call's tables, to be compared with the staged ones
     CallTables tab;                          // models | instances (last: its stream and events go before any buffer)
 };
 static int fitter_create_(int device, dh_fitter **out) { return create_owner(device, out, "dh_fitter_create"); }
 static int fitter_destroy_(dh_fitter *f) { return destroy_owner(f); }
+
+// The array arguments of one call of the fit family, bound the same way by every *_run and in both forms.  The call declares each
+// array once -- in(): one the kernels read, out(): one they write -- naming the field of the kernels' arguments that is to point
+// at it; a declaration allocates nothing.  commit() then fills every field: in the _device form with the caller's own pointers,
+// and nothing is asked of the runtime (a stream that is being captured stays untouched); in the host form with slices of the
+// fitter's arena, each aligned to 256 bytes as an allocation of its own would be; the arena grows at most once, before any slice
+// exists, and the inputs follow on the stream in the order they were declared.  A NULL array binds NULL.  finish() ends a host call: the outputs the caller asked for come back in the order they
+// were declared and the stream is waited for.
+class CallArgs {
+    struct Arg {
+        void *field;              // the pointer to fill
+        const void *src;          // in(): the caller's array
+        void *dst, *at;           // out(): the caller's array, and where the output lives on the device when that is not it
+        size_t bytes;
+    };
+    dh_fitter *f_;
+    bool dev_;
+    hipStream_t s_;
+    Arg arg_[12];                 // (the longest call, the multi-view identify, declares nine)
+    int n_ = 0;
+    static size_t slice(size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; }
+  public:
+    CallArgs(dh_fitter *f, bool dev, hipStream_t s) : f_(f), dev_(dev), s_(s) {}
+    template <typename T>
+    void in(const T **field, const T *src, size_t count) { arg_[n_++] = Arg{field, src, nullptr, nullptr, count * sizeof(T)}; }
+    // `at`: scratch of the fitter's or the set's that a host call's output is read back from, and a _device call's output goes to
+    // when the caller passes NULL
+    template <typename T>
+    void out(T **field, T *dst, size_t count, T *at = nullptr) { arg_[n_++] = Arg{field, nullptr, dst, at, count * sizeof(T)}; }
+    int commit() {
+        size_t total = 0;
+        for (int i = 0; i < n_ && !dev_; ++i)
+            if (!arg_[i].at && (arg_[i].src || arg_[i].dst)) total += slice(arg_[i].bytes);
+        if (f_->arena.cap() < total) {
+            HIP_TRY(hipDeviceSynchronize());         // (an earlier call may still use the old arena)
+            TRY(f_->arena.grow(total));
+        }
+        unsigned char *next = f_->arena.get();
+        for (int i = 0; i < n_; ++i) {
+            Arg &a = arg_[i];
+            void *p = a.at;
+            if (dev_) p = a.src ? const_cast<void *>(a.src) : a.dst ? a.dst : a.at;
+            else if (!a.at && (a.src || a.dst)) { p = next; next += slice(a.bytes); }
+            memcpy(a.field, &p, sizeof p);           // (every field is a pointer to an object type)
+            a.at = p;
+            if (!dev_ && a.src && a.bytes) HIP_TRY(hipMemcpyAsync(p, a.src, a.bytes, hipMemcpyHostToDevice, s_));
+        }
+        return DH_OK;
+    }
+    int finish() {
+        if (dev_) return DH_OK;
+        for (int i = 0; i < n_; ++i)
+            if (arg_[i].dst && arg_[i].bytes) HIP_TRY(hipMemcpyAsync(arg_[i].dst, arg_[i].at, arg_[i].bytes, hipMemcpyDeviceToHost, s_));
+        HIP_TRY(hipStreamSynchronize(s_));
+        return DH_OK;
+    }
+};
 
 // The refusals of a call's dh_fit_params (NULL: the defaults); *out is what the call runs with.
 static int fit_params_check(const dh_fit_params *in, dh_fit_params *out, const char *who) {
@@ -2912,6 +2952,13 @@ static void fit_args_params(A &a, const dh_fit_params &prm) {
     a.coarse = prm.coarse_iterations; a.full = prm.iterations; a.min_points = prm.min_points;
     a.gate[0] = prm.gate[0]; a.gate[1] = prm.gate[1];
     a.lam1 = 1.0 + prm.lambda;
+}
+// The half of a FitArgs or ShapeArgs that the (checked) frames fill: their count and size, and K or the camera table.
+template <typename A>
+static void args_frames(A &a, int n, int w, int h, const float *K, const dh_cameras *cams, bool use_cams) {
+    a.n = n; a.w = w; a.h = h;
+    if (use_cams) a.cams = cams->dev.get();
+    else memcpy(a.k, K, sizeof a.k);
 }
 // What dh_fit_instance_fault found in instance i, as the refusal of a fit or shape call; DH_OK where it found nothing.
 static int instance_refusal(const FitInstanceFault &fault, float scale, uint32_t i, double radius, double largest, const char *who) {
@@ -2989,9 +3036,7 @@ static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, 
     hipStream_t s = dev ? stream : f->tab.s;
     FitArgs a;
     memset(&a, 0, sizeof a);
-    a.n = q.n; a.w = q.w; a.h = q.h;
-    if (q.use_cams) a.cams = q.cams->dev.get();
-    else memcpy(a.k, q.K, sizeof a.k);
+    args_frames(a, q.n, q.w, q.h, q.K, q.cams, q.use_cams);
     a.n_inst = q.n_inst;
     fit_args_params(a, prm);
     // ---- the call's tables: one staging buffer, one upload
@@ -3001,24 +3046,16 @@ static int fit_run(dh_fitter *f, const FitReq &q, bool dev, hipStream_t stream, 
     fit_tables_fill(f->tab.stage.get(), q.models, q.n_models, q.inst, q.n_inst, f->device);
     a.models = (const FitModel *)f->tab.dev.get();
     a.inst = (const dh_render_instance *)(f->tab.dev.get() + o_inst);
-    const size_t n_px = (size_t)q.n * q.w * q.h;
-    if (!dev) {
-        if (f->frames.cap() < n_px || f->out.cap() < q.n_inst) HIP_TRY(hipDeviceSynchronize());
-        TRY(f->frames.grow(n_px));
-        if (f->out.cap() < q.n_inst) { TRY(f->out.grow(q.n_inst)); TRY(f->rec.alloc(f->out.cap())); }
-        a.frames = f->frames.get(); a.out = f->out.get(); a.rec = f->rec.get();
-    } else { a.frames = q.frames; a.out = q.out; a.rec = q.rec; }
+    CallArgs args(f, dev, s);
+    args.in(&a.frames, q.frames, (size_t)q.n * q.w * q.h);
+    args.out(&a.out, q.out, q.n_inst);
+    args.out(&a.rec, q.rec, q.n_inst);
     TRY(f->tab.upload(bytes, s));
-    if (!dev) HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    TRY(args.commit());
     if (q.carried) TRY(hip_step(dh_launch_fit_carry((dh_render_instance *)(f->tab.dev.get() + o_inst), q.carried, q.n_inst, s), "k_fit_carry"));
     TRY(hip_step(dh_launch_fit(a, s), "k_fit"));
     TRY(f->tab.done(s));
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(q.out, a.out, (size_t)q.n_inst * sizeof(dh_render_instance), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)q.n_inst * sizeof(dh_fit_record), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return DH_OK;
+    return args.finish();
 }
 static int fit_depth_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *const *models, uint32_t n_models,
                       const dh_render_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_render_instance *out, dh_fit_record *records) {
@@ -3101,6 +3138,17 @@ static int fit_views_info_(const dh_fit_views *v, int *n, int *device) {
     return DH_OK;
 }
 
+// The refusals of a multi-view call's view table and of what rests on it: the table, n_sets (NULL: the call takes one set of
+// frames and has no such argument) and the frames of its cameras; *n: how many those are.
+static int check_views(const dh_fitter *f, const dh_fit_views *views, const uint32_t *n_sets, int w, int h, int *n, const char *who) {
+    if (!views) return fail(DH_EINVAL, "%s: NULL view table", who);
+    if (views->device != f->device) return fail(DH_EINVAL, "%s: the view table lives on device %d, the fitter on %d", who, views->device, f->device);
+    *n = views->n;
+    if (n_sets && (*n_sets < 1 || (uint64_t)*n_sets * (uint64_t)*n > 65535))
+        return fail(DH_EINVAL, "%s: n_sets = %u of %d cameras, expected 1 .. 65535 frames", who, *n_sets, *n);
+    return check_frames(*n, w, h, nullptr, views->cams, true, f->device, "fitter", who);
+}
+
 // One multi-view fit call.  dev: frames / out / records are device pointers and `stream` the caller's; else host pointers.
 struct FitViewsReq {
     const uint16_t *frames; int w, h;
@@ -3115,10 +3163,8 @@ static int fit_views_run(dh_fitter *f, const FitViewsReq &q, bool dev, hipStream
     if (!f) return fail(DH_EINVAL, "%s: NULL fitter", who);
     if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
     if (!q.out || !q.rec) return fail(DH_EINVAL, "%s: NULL output", who);
-    if (!q.views) return fail(DH_EINVAL, "%s: NULL view table", who);
-    if (q.views->device != f->device) return fail(DH_EINVAL, "%s: the view table lives on device %d, the fitter on %d", who, q.views->device, f->device);
-    const int n = q.views->n;
-    TRY(check_frames(n, q.w, q.h, nullptr, q.views->cams, true, f->device, "fitter", who));
+    int n = 0;
+    TRY(check_views(f, q.views, nullptr, q.w, q.h, &n, who));
     dh_fit_params prm;
     TRY(fit_params_check(q.prm, &prm, who));
     if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
@@ -3173,24 +3219,16 @@ static int fit_views_run(dh_fitter *f, const FitViewsReq &q, bool dev, hipStream
     }
     a.models = (const FitModel *)f->tab.dev.get();
     a.inst = (const dh_view_instance *)(f->tab.dev.get() + o_inst);
-    const size_t n_px = (size_t)n * q.w * q.h;
-    if (!dev) {
-        if (f->frames.cap() < n_px || f->view_out.cap() < q.n_inst) HIP_TRY(hipDeviceSynchronize());
-        TRY(f->frames.grow(n_px));
-        if (f->view_out.cap() < q.n_inst) { TRY(f->view_out.grow(q.n_inst)); TRY(f->view_rec.alloc(f->view_out.cap())); }
-        a.frames = f->frames.get(); a.out = f->view_out.get(); a.rec = f->view_rec.get();
-    } else { a.frames = q.frames; a.out = q.out; a.rec = q.rec; }
-    if (capturing) return hip_step(dh_launch_fit_views(a, s), "k_fit_views");
-    TRY(f->tab.upload(bytes, s));
-    if (!dev) HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    CallArgs args(f, dev, s);
+    args.in(&a.frames, q.frames, (size_t)n * q.w * q.h);
+    args.out(&a.out, q.out, q.n_inst);
+    args.out(&a.rec, q.rec, q.n_inst);
+    if (!capturing) TRY(f->tab.upload(bytes, s));
+    TRY(args.commit());                              // (a capture is of a _device call: its pointers are the caller's)
     TRY(hip_step(dh_launch_fit_views(a, s), "k_fit_views"));
+    if (capturing) return DH_OK;
     TRY(f->tab.done(s));
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(q.out, a.out, (size_t)q.n_inst * sizeof(dh_view_instance), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)q.n_inst * sizeof(dh_view_fit_record), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return DH_OK;
+    return args.finish();
 }
 static int fit_depth_views_(dh_fitter *f, const uint16_t *frames, int w, int h, const dh_fit_views *views, const dh_fit_model *const *models, uint32_t n_models,
                             const dh_view_instance *instances, uint32_t n_instances, const dh_fit_params *params, dh_view_instance *out, dh_view_fit_record *records) {
@@ -3576,6 +3614,42 @@ static void shape_args_common(ShapeArgs &a, dh_fitter *f, const dh_fit_model *m,
     a.lam1 = 1.0 + prm.lambda;
     a.sums = f->shape_sums.get();
 }
+// The refusals of a single-view shape or surface step that rest on its instances.  The _device form knows their number alone; the
+// host form goes through those that take part, in the header's order, and counts each subject's terms.  max_scale > 0: the
+// surface step's bound on |scale|.
+static int shape_check_terms(bool dev, const dh_render_instance *inst, uint32_t n_inst, const uint32_t *subjects, uint32_t n_subjects,
+                             const dh_fit_record *fit_rec, int n, uint32_t np, double radius, double largest, double max_scale, const char *who) {
+    if (dev) {
+        if ((uint64_t)n_inst * np > DH_SHAPE_MAX_TERMS)
+            return fail(DH_EINVAL, "%s: %u instances of %u points exceed %u terms", who, n_inst, np, DH_SHAPE_MAX_TERMS);
+        return DH_OK;
+    }
+    std::vector<uint32_t> per(n_subjects, 0);
+    for (uint32_t i = 0; i < n_inst; ++i) {
+        const uint32_t sj = subjects ? subjects[i] : 0u;
+        if (sj == DH_SHAPE_SKIP) continue;
+        if (fit_rec && fit_rec[i].status != DH_FIT_OK) continue;
+        if (sj >= n_subjects) return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, n_subjects);
+        const dh_render_instance &in = inst[i];
+        if (in.frame >= (uint32_t)n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, n);
+        TRY(instance_refusal(dh_fit_instance_fault(in, radius, largest), in.scale, i, radius, largest, who));
+        if (max_scale > 0.0 && !(fabs((double)in.scale) <= max_scale))
+            return fail(DH_EINVAL, "%s: instance %u has |scale| = %g above %g", who, i, fabs((double)in.scale), max_scale);
+        if ((uint64_t)(++per[sj]) * np > DH_SHAPE_MAX_TERMS)
+            return fail(DH_EINVAL, "%s: subject %u has more than %u terms (instances times %u points)", who, sj, DH_SHAPE_MAX_TERMS, np);
+    }
+    return DH_OK;
+}
+
+// The refusals of the subject set of a surface or identify call (the shape step over a set has its own: it names n_subjects = 0
+// with the plain step's words, after the params): the set's device, that it holds offsets where the call needs them, n_subjects.
+static int check_subjects(const dh_fitter *f, const dh_fit_subjects *set, uint32_t n_subjects, bool surface, const char *who) {
+    if (set->device != f->device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the fitter on %d", who, set->device, f->device);
+    if (surface && !set->surface) return fail(DH_EINVAL, "%s: the set holds no offsets (dh_fit_subjects_create_surface makes one that does)", who);
+    if (n_subjects < 1 || n_subjects > set->n_subjects)
+        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u, the set's", who, n_subjects, set->n_subjects);
+    return DH_OK;
+}
 
 // One shape call.  dev: frames / instances / subjects / records are device pointers and `stream` the caller's; else host pointers.
 struct ShapeReq {
@@ -3605,23 +3679,7 @@ static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stre
         return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u, the set's", who, q.n_subjects, q.set->n_subjects);
     dh_shape_params prm;
     TRY(shape_check_call(f, m, b, q.n_subjects, q.prm, &prm, q.inst, q.n_inst, who));
-    if (dev) {
-        if ((uint64_t)q.n_inst * m->n > DH_SHAPE_MAX_TERMS)
-            return fail(DH_EINVAL, "%s: %u instances of %u points exceed %u terms", who, q.n_inst, m->n, DH_SHAPE_MAX_TERMS);
-    } else {
-        std::vector<uint32_t> per(q.n_subjects, 0);
-        for (uint32_t i = 0; i < q.n_inst; ++i) {
-            const uint32_t sj = q.subjects ? q.subjects[i] : 0u;
-            if (sj == DH_SHAPE_SKIP) continue;
-            if (q.fit_rec && q.fit_rec[i].status != DH_FIT_OK) continue;
-            if (sj >= q.n_subjects) return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, q.n_subjects);
-            const dh_render_instance &in = q.inst[i];
-            if (in.frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, q.n);
-            TRY(instance_refusal(dh_fit_instance_fault(in, m->radius, b->largest), in.scale, i, m->radius, b->largest, who));
-            if ((uint64_t)(++per[sj]) * m->n > DH_SHAPE_MAX_TERMS)
-                return fail(DH_EINVAL, "%s: subject %u has more than %u terms (instances times %u points)", who, sj, DH_SHAPE_MAX_TERMS, m->n);
-        }
-    }
+    TRY(shape_check_terms(dev, q.inst, q.n_inst, q.subjects, q.n_subjects, q.fit_rec, q.n, m->n, m->radius, b->largest, 0.0, who));
 
     DeviceGuard guard(f->device);
     if (!guard.ok) return DH_EHIP;
@@ -3630,41 +3688,22 @@ static int shape_run(dh_fitter *f, const ShapeReq &q, bool dev, hipStream_t stre
     if (!f->shape_sums) TRY(f->shape_sums.alloc((size_t)DH_SHAPE_MAX_SUBJECTS * DH_SHAPE_STRIDE));
     ShapeArgs a;
     memset(&a, 0, sizeof a);
-    a.n = q.n; a.w = q.w; a.h = q.h;
-    if (q.use_cams) a.cams = q.cams->dev.get();
-    else memcpy(a.k, q.K, sizeof a.k);
+    args_frames(a, q.n, q.w, q.h, q.K, q.cams, q.use_cams);
     shape_args_common(a, f, m, b, q.n_inst, q.n_subjects, prm);
-    if (!dev) {
-        const size_t n_px = (size_t)q.n * q.w * q.h;
-        if (f->frames.cap() < n_px || f->shape_inst.cap() < q.n_inst || f->shape_rec.cap() < q.n_subjects) HIP_TRY(hipDeviceSynchronize());
-        TRY(f->frames.grow(n_px));
-        if (f->shape_inst.cap() < q.n_inst || !f->shape_inst) { TRY(f->shape_inst.grow(std::max<size_t>(q.n_inst, 1))); TRY(f->shape_subj.alloc(f->shape_inst.cap())); }
-        if (!f->shape_rec) TRY(f->shape_rec.alloc(DH_SHAPE_MAX_SUBJECTS));
-        if (q.fit_rec && f->shape_fit_rec.cap() < f->shape_inst.cap()) {
-            HIP_TRY(hipDeviceSynchronize());
-            TRY(f->shape_fit_rec.alloc(f->shape_inst.cap()));
-        }
-        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        if (q.n_inst) HIP_TRY(hipMemcpyAsync(f->shape_inst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_render_instance), hipMemcpyHostToDevice, s));
-        if (q.n_inst && q.subjects) HIP_TRY(hipMemcpyAsync(f->shape_subj.get(), q.subjects, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        a.frames = f->frames.get(); a.inst = f->shape_inst.get(); a.subjects = q.subjects ? f->shape_subj.get() : nullptr;
-        a.rec = f->shape_rec.get();
-    } else { a.frames = q.frames; a.inst = q.inst; a.subjects = q.subjects; a.rec = q.rec; }
-    const dh_fit_record *fit_rec = q.fit_rec;
-    if (!dev && q.fit_rec && q.n_inst) {
-        HIP_TRY(hipMemcpyAsync(f->shape_fit_rec.get(), q.fit_rec, (size_t)q.n_inst * sizeof(dh_fit_record), hipMemcpyHostToDevice, s));
-        fit_rec = f->shape_fit_rec.get();
-    }
+    const dh_fit_record *fit_rec = nullptr;
+    CallArgs args(f, dev, s);
+    args.in(&a.frames, q.frames, (size_t)q.n * q.w * q.h);
+    args.in(&a.inst, q.inst, q.n_inst);
+    args.in(&a.subjects, q.subjects, q.n_inst);
+    args.in(&fit_rec, q.fit_rec, q.n_inst);
+    args.out(&a.rec, q.rec, q.n_subjects);
+    TRY(args.commit());
     // ---- the three stream-ordered operations
     TRY(hip_step(dh_launch_shape_clear(a, s), "k_shape_clear"));
     if (q.use_set) TRY(hip_step(dh_launch_shape_accumulate_subjects(ShapeSubjectsArgs{a, q.set->table.get(), fit_rec}, s), "k_shape_accumulate_subjects"));
     else TRY(hip_step(dh_launch_shape_accumulate(a, s), "k_shape_accumulate"));
     TRY(hip_step(dh_launch_shape_solve(a, s), "k_shape_solve"));
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)q.n_subjects * sizeof(dh_shape_record), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return DH_OK;
+    return args.finish();
 }
 static int fit_shape_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_model *model, const dh_fit_basis *basis,
                       const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects, const dh_shape_params *params,
@@ -3745,10 +3784,7 @@ static int surface_run(dh_fitter *f, const SurfaceReq &q, bool dev, hipStream_t 
     if (!q.set) return fail(DH_EINVAL, "%s: NULL subject set", who);
     TRY(check_frames(q.n, q.w, q.h, q.K, q.cams, q.use_cams, f->device, "fitter", who));
     dh_fit_subjects *set = q.set;
-    if (set->device != f->device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the fitter on %d", who, set->device, f->device);
-    if (!set->surface) return fail(DH_EINVAL, "%s: the set holds no offsets (dh_fit_subjects_create_surface makes one that does)", who);
-    if (q.n_subjects < 1 || q.n_subjects > set->n_subjects)
-        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u, the set's", who, q.n_subjects, set->n_subjects);
+    TRY(check_subjects(f, set, q.n_subjects, true, who));
     dh_surface_params prm;
     (void)fit_surface_params_default_(&prm);
     if (q.prm) prm = *q.prm;
@@ -3765,25 +3801,7 @@ static int surface_run(dh_fitter *f, const SurfaceReq &q, bool dev, hipStream_t 
     if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
     if (q.n_inst > DH_SHAPE_MAX_TERMS) return fail(DH_EINVAL, "%s: too many instances", who);
     const double largest = set->basis->largest;
-    if (dev) {
-        if ((uint64_t)q.n_inst * set->n > DH_SHAPE_MAX_TERMS)
-            return fail(DH_EINVAL, "%s: %u instances of %u points exceed %u terms", who, q.n_inst, set->n, DH_SHAPE_MAX_TERMS);
-    } else {
-        std::vector<uint32_t> per(q.n_subjects, 0);
-        for (uint32_t i = 0; i < q.n_inst; ++i) {
-            const uint32_t sj = q.subjects ? q.subjects[i] : 0u;
-            if (sj == DH_SHAPE_SKIP) continue;
-            if (q.fit_rec && q.fit_rec[i].status != DH_FIT_OK) continue;
-            if (sj >= q.n_subjects) return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, q.n_subjects);
-            const dh_render_instance &in = q.inst[i];
-            if (in.frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, in.frame, q.n);
-            TRY(instance_refusal(dh_fit_instance_fault(in, set->radius, largest), in.scale, i, set->radius, largest, who));
-            if (!(fabs((double)in.scale) <= DH_SURFACE_MAX_SCALE))
-                return fail(DH_EINVAL, "%s: instance %u has |scale| = %g above %g", who, i, fabs((double)in.scale), DH_SURFACE_MAX_SCALE);
-            if ((uint64_t)(++per[sj]) * set->n > DH_SHAPE_MAX_TERMS)
-                return fail(DH_EINVAL, "%s: subject %u has more than %u terms (instances times %u points)", who, sj, DH_SHAPE_MAX_TERMS, set->n);
-        }
-    }
+    TRY(shape_check_terms(dev, q.inst, q.n_inst, q.subjects, q.n_subjects, q.fit_rec, q.n, set->n, set->radius, largest, DH_SURFACE_MAX_SCALE, who));
 
     DeviceGuard guard(f->device);
     if (!guard.ok) return DH_EHIP;
@@ -3792,9 +3810,7 @@ static int surface_run(dh_fitter *f, const SurfaceReq &q, bool dev, hipStream_t 
     SurfaceArgs g;
     memset(&g, 0, sizeof g);
     ShapeArgs &a = g.s;
-    a.n = q.n; a.w = q.w; a.h = q.h;
-    if (q.use_cams) a.cams = q.cams->dev.get();
-    else memcpy(a.k, q.K, sizeof a.k);
+    args_frames(a, q.n, q.w, q.h, q.K, q.cams, q.use_cams);
     a.np = set->n; a.nk = set->basis->k;
     a.radius = set->radius; a.largest = largest;
     a.n_inst = q.n_inst; a.n_subjects = q.n_subjects;
@@ -3805,37 +3821,20 @@ static int surface_run(dh_fitter *f, const SurfaceReq &q, bool dev, hipStream_t 
     g.state = set->state.get();
     g.min_cos2 = prm.min_cos2; g.mu = prm.mu; g.eps = prm.eps; g.max_offset = set->max_offset;
     g.min_count = prm.min_count; g.iterations = prm.iterations;
-    g.fit_rec = q.fit_rec;
-    if (!dev) {
-        const size_t n_px = (size_t)q.n * q.w * q.h;
-        if (f->frames.cap() < n_px || f->shape_inst.cap() < q.n_inst) HIP_TRY(hipDeviceSynchronize());
-        TRY(f->frames.grow(n_px));
-        if (f->shape_inst.cap() < q.n_inst || !f->shape_inst) { TRY(f->shape_inst.grow(std::max<size_t>(q.n_inst, 1))); TRY(f->shape_subj.alloc(f->shape_inst.cap())); }
-        if (q.fit_rec && f->shape_fit_rec.cap() < f->shape_inst.cap()) {
-            HIP_TRY(hipDeviceSynchronize());
-            TRY(f->shape_fit_rec.alloc(f->shape_inst.cap()));
-        }
-        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        if (q.n_inst) HIP_TRY(hipMemcpyAsync(f->shape_inst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_render_instance), hipMemcpyHostToDevice, s));
-        if (q.n_inst && q.subjects) HIP_TRY(hipMemcpyAsync(f->shape_subj.get(), q.subjects, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (q.n_inst && q.fit_rec) {
-            HIP_TRY(hipMemcpyAsync(f->shape_fit_rec.get(), q.fit_rec, (size_t)q.n_inst * sizeof(dh_fit_record), hipMemcpyHostToDevice, s));
-            g.fit_rec = f->shape_fit_rec.get();
-        }
-        a.frames = f->frames.get(); a.inst = f->shape_inst.get(); a.subjects = q.subjects ? f->shape_subj.get() : nullptr;
-        g.rec = set->srec.get();
-    } else { a.frames = q.frames; a.inst = q.inst; a.subjects = q.subjects; g.rec = q.rec; }
+    CallArgs args(f, dev, s);
+    args.in(&a.frames, q.frames, (size_t)q.n * q.w * q.h);
+    args.in(&a.inst, q.inst, q.n_inst);
+    args.in(&a.subjects, q.subjects, q.n_inst);
+    args.in(&g.fit_rec, q.fit_rec, q.n_inst);
+    args.out(&g.rec, q.rec, q.n_subjects, set->srec.get());   // (a surface set allocates nothing after its creation)
+    TRY(args.commit());
     // ---- the five stream-ordered operations
     TRY(hip_step(dh_launch_surface_clear(g, s), "k_surface_clear"));
     TRY(hip_step(dh_launch_surface_accumulate(g, s), "k_surface_accumulate"));
     TRY(hip_step(dh_launch_surface_solve(g, s), "k_surface_solve"));
     TRY(hip_step(dh_launch_subjects_update_surface(SurfacePointsArgs{subjects_args(set, nullptr, 0, q.n_subjects), set->nb.get(), set->offsets.get()}, false, s),
                  "k_subjects_points_surface"));
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(q.rec, g.rec, (size_t)q.n_subjects * sizeof(dh_surface_record), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return DH_OK;
+    return args.finish();
 }
 static int fit_surface_subjects_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], dh_fit_subjects *set,
                                  const dh_render_instance *instances, uint32_t n_instances, const uint32_t *subjects, uint32_t n_subjects,
@@ -3890,6 +3889,17 @@ static int ident_params_check(const dh_ident_params *in, double default_max_rms,
     *out = prm;
     return DH_OK;
 }
+// The half of an IdentArgs or IdentViewsArgs that the set, the subject count and the (checked) params fill.
+template <typename G>
+static void ident_args_common(G &g, const dh_fit_subjects *set, uint32_t n_subjects, const dh_ident_params &prm) {
+    g.f.coarse = 0; g.f.full = prm.iterations; g.f.min_points = prm.min_points;
+    g.f.gate[0] = prm.gate; g.f.gate[1] = prm.gate;
+    g.f.lam1 = 1.0 + prm.lambda;
+    g.models = set->table.get();
+    g.np = set->n; g.n_subjects = n_subjects;
+    g.radius = set->radius; g.largest = set->basis->largest;
+    g.max_ms = prm.max_rms * prm.max_rms; g.min_ratio = prm.min_ratio;
+}
 // One identify call.  dev: frames / instances / enrolled / fit records / every output are device pointers and `stream` the caller's.
 struct IdentReq {
     const uint16_t *frames; int n, w, h;
@@ -3910,9 +3920,7 @@ static int ident_run(dh_fitter *f, const IdentReq &q, bool dev, hipStream_t stre
     if (!q.set) return fail(DH_EINVAL, "%s: NULL subject set", who);
     TRY(check_frames(q.n, q.w, q.h, q.K, q.cams, q.use_cams, f->device, "fitter", who));
     const dh_fit_subjects *set = q.set;
-    if (set->device != f->device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the fitter on %d", who, set->device, f->device);
-    if (q.n_subjects < 1 || q.n_subjects > set->n_subjects)
-        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u, the set's", who, q.n_subjects, set->n_subjects);
+    TRY(check_subjects(f, set, q.n_subjects, false, who));
     dh_ident_params prm;
     TRY(ident_params_check(q.prm, DH_IDENT_DEFAULT_MAX_RMS, &prm, who));
     if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
@@ -3936,17 +3944,9 @@ static int ident_run(dh_fitter *f, const IdentReq &q, bool dev, hipStream_t stre
     IdentArgs g;
     memset(&g, 0, sizeof g);
     FitArgs &a = g.f;
-    a.n = q.n; a.w = q.w; a.h = q.h;
-    if (q.use_cams) a.cams = q.cams->dev.get();
-    else memcpy(a.k, q.K, sizeof a.k);
+    args_frames(a, q.n, q.w, q.h, q.K, q.cams, q.use_cams);
     a.n_inst = q.n_inst;
-    a.coarse = 0; a.full = prm.iterations; a.min_points = prm.min_points;
-    a.gate[0] = prm.gate; a.gate[1] = prm.gate;
-    a.lam1 = 1.0 + prm.lambda;
-    g.models = set->table.get();
-    g.np = set->n; g.n_subjects = q.n_subjects;
-    g.radius = set->radius; g.largest = largest;
-    g.max_ms = prm.max_rms * prm.max_rms; g.min_ratio = prm.min_ratio;
+    ident_args_common(g, set, q.n_subjects, prm);
     // ---- the pair scratch: the fitter's, grown on demand (growing waits for the device, as the other tables do)
     const bool own_scores = !dev || !q.scores;
     if ((own_scores && f->ident_score.cap() < pairs) || f->ident_pose.cap() < pairs * 12) {
@@ -3955,49 +3955,20 @@ static int ident_run(dh_fitter *f, const IdentReq &q, bool dev, hipStream_t stre
         TRY(f->ident_pose.grow((size_t)pairs * 12));
     }
     g.pose = f->ident_pose.get();
-    if (!dev) {
-        const size_t n_px = (size_t)q.n * q.w * q.h;
-        if (f->frames.cap() < n_px || f->shape_inst.cap() < q.n_inst || f->ident_sub.cap() < q.n_inst || f->ident_enrolled.cap() < q.n_subjects)
-            HIP_TRY(hipDeviceSynchronize());
-        TRY(f->frames.grow(n_px));
-        if (f->shape_inst.cap() < q.n_inst || !f->shape_inst) { TRY(f->shape_inst.grow(std::max<size_t>(q.n_inst, 1))); TRY(f->shape_subj.alloc(f->shape_inst.cap())); }
-        if (q.fit_rec && f->shape_fit_rec.cap() < f->shape_inst.cap()) {
-            HIP_TRY(hipDeviceSynchronize());
-            TRY(f->shape_fit_rec.alloc(f->shape_inst.cap()));
-        }
-        if (f->ident_sub.cap() < q.n_inst) {
-            TRY(f->ident_sub.grow(q.n_inst));
-            TRY(f->ident_rec.alloc(f->ident_sub.cap()));
-            TRY(f->ident_poses.alloc(f->ident_sub.cap()));
-        }
-        if (!f->ident_enrolled) TRY(f->ident_enrolled.alloc(DH_SHAPE_MAX_SUBJECTS));
-        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(f->shape_inst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_render_instance), hipMemcpyHostToDevice, s));
-        if (q.enrolled) HIP_TRY(hipMemcpyAsync(f->ident_enrolled.get(), q.enrolled, q.n_subjects, hipMemcpyHostToDevice, s));
-        if (q.fit_rec) HIP_TRY(hipMemcpyAsync(f->shape_fit_rec.get(), q.fit_rec, (size_t)q.n_inst * sizeof(dh_fit_record), hipMemcpyHostToDevice, s));
-        a.frames = f->frames.get(); a.inst = f->shape_inst.get();
-        g.enrolled = q.enrolled ? f->ident_enrolled.get() : nullptr;
-        g.fit_rec = q.fit_rec ? f->shape_fit_rec.get() : nullptr;
-        g.score = f->ident_score.get();
-        g.subjects_out = f->ident_sub.get(); g.rec = f->ident_rec.get();
-        g.poses_out = q.poses_out ? f->ident_poses.get() : nullptr;
-    } else {
-        a.frames = q.frames; a.inst = q.inst;
-        g.enrolled = q.enrolled; g.fit_rec = q.fit_rec;
-        g.score = q.scores ? q.scores : f->ident_score.get();
-        g.subjects_out = q.subjects_out; g.rec = q.rec; g.poses_out = q.poses_out;
-    }
+    CallArgs args(f, dev, s);
+    args.in(&a.frames, q.frames, (size_t)q.n * q.w * q.h);
+    args.in(&a.inst, q.inst, q.n_inst);
+    args.in(&g.enrolled, q.enrolled, q.n_subjects);
+    args.in(&g.fit_rec, q.fit_rec, q.n_inst);
+    args.out(&g.subjects_out, q.subjects_out, q.n_inst);
+    args.out(&g.rec, q.rec, q.n_inst);
+    args.out(&g.poses_out, q.poses_out, q.n_inst);
+    args.out(&g.score, q.scores, (size_t)pairs, f->ident_score.get());
+    TRY(args.commit());
     // ---- the two stream-ordered operations
     TRY(hip_step(dh_launch_ident_score(g, s), "k_ident_score"));
     TRY(hip_step(dh_launch_ident_decide(g, s), "k_ident_decide"));
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(q.subjects_out, g.subjects_out, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(q.rec, g.rec, (size_t)q.n_inst * sizeof(dh_ident_record), hipMemcpyDeviceToHost, s));
-        if (q.poses_out) HIP_TRY(hipMemcpyAsync(q.poses_out, g.poses_out, (size_t)q.n_inst * sizeof(dh_render_instance), hipMemcpyDeviceToHost, s));
-        if (q.scores) HIP_TRY(hipMemcpyAsync(q.scores, g.score, (size_t)pairs * sizeof(dh_fit_record), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return DH_OK;
+    return args.finish();
 }
 static int fit_identify_subjects_(dh_fitter *f, const uint16_t *frames, int n, int w, int h, const float K[9], const dh_fit_subjects *set,
                                   const dh_render_instance *instances, uint32_t n_instances, const uint8_t *enrolled, uint32_t n_subjects,
@@ -4035,6 +4006,19 @@ static int fit_ident_views_params_default_(dh_ident_params *p) {
     p->max_rms = DH_IDENT_VIEWS_DEFAULT_MAX_RMS;
     return DH_OK;
 }
+// What dh_shape_views_skip or dh_calib_skip found in instance i of a host multi-view call, as the call's refusal; DH_OK where the
+// instance takes part or is left out.
+static int views_skip_refusal(const ShapeViewsSkip &sk, const dh_view_instance &in, uint32_t i, int n, uint32_t set, uint32_t n_sets, uint32_t sj,
+                              uint32_t n_subjects, double radius, double largest, const char *who) {
+    switch (sk.why) {
+    case DH_SHAPE_VIEWS_OK: case DH_SHAPE_VIEWS_SKIPPED: return DH_OK;
+    case DH_SHAPE_VIEWS_NO_VIEW: return fail(DH_EINVAL, "%s: instance %u is seen by no view", who, i);
+    case DH_SHAPE_VIEWS_CAMERA: return fail(DH_EINVAL, "%s: instance %u names camera %llu of %d", who, i, (unsigned long long)sk.last, n);
+    case DH_SHAPE_VIEWS_SET: return fail(DH_EINVAL, "%s: instance %u names set %u of %u", who, i, set, n_sets);
+    case DH_SHAPE_VIEWS_SUBJECT: return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, n_subjects);
+    default: return instance_refusal(sk.fault, in.scale, i, radius, largest, who);
+    }
+}
 // One multi-view identify call.  dev: frames / instances / sets / enrolled / fit records / every output are device pointers and
 // `stream` the caller's.
 struct IdentViewsReq {
@@ -4054,16 +4038,10 @@ static int ident_views_run(dh_fitter *f, const IdentViewsReq &q, bool dev, hipSt
     if (!q.subjects_out) return fail(DH_EINVAL, "%s: NULL subjects_out", who);
     if (!q.rec) return fail(DH_EINVAL, "%s: NULL records", who);
     if (!q.set) return fail(DH_EINVAL, "%s: NULL subject set", who);
-    if (!q.views) return fail(DH_EINVAL, "%s: NULL view table", who);
-    if (q.views->device != f->device) return fail(DH_EINVAL, "%s: the view table lives on device %d, the fitter on %d", who, q.views->device, f->device);
-    const int n = q.views->n;
-    if (q.n_sets < 1 || (uint64_t)q.n_sets * (uint64_t)n > 65535)
-        return fail(DH_EINVAL, "%s: n_sets = %u of %d cameras, expected 1 .. 65535 frames", who, q.n_sets, n);
-    TRY(check_frames(n, q.w, q.h, nullptr, q.views->cams, true, f->device, "fitter", who));
+    int n = 0;
+    TRY(check_views(f, q.views, &q.n_sets, q.w, q.h, &n, who));
     const dh_fit_subjects *set = q.set;
-    if (set->device != f->device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the fitter on %d", who, set->device, f->device);
-    if (q.n_subjects < 1 || q.n_subjects > set->n_subjects)
-        return fail(DH_EINVAL, "%s: n_subjects = %u, expected 1 .. %u, the set's", who, q.n_subjects, set->n_subjects);
+    TRY(check_subjects(f, set, q.n_subjects, false, who));
     dh_ident_params prm;
     TRY(ident_params_check(q.prm, DH_IDENT_VIEWS_DEFAULT_MAX_RMS, &prm, who));
     if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
@@ -4079,12 +4057,8 @@ static int ident_views_run(dh_fitter *f, const IdentViewsReq &q, bool dev, hipSt
             const IdentViewsPart part = dh_ident_views_part(in, st, q.fit_rec ? q.fit_rec + i : nullptr, (uint32_t)n, q.n_sets, set->n, set->radius, largest);
             switch (part.why) {
             case DH_IDENT_VIEWS_OK: case DH_IDENT_VIEWS_RECORD: break;
-            case DH_IDENT_VIEWS_WHERE:
-                if (part.skip.why == DH_SHAPE_VIEWS_NO_VIEW) return fail(DH_EINVAL, "%s: instance %u is seen by no view", who, i);
-                if (part.skip.why == DH_SHAPE_VIEWS_CAMERA)
-                    return fail(DH_EINVAL, "%s: instance %u names camera %llu of %d", who, i, (unsigned long long)part.skip.last, n);
-                return fail(DH_EINVAL, "%s: instance %u names set %u of %u", who, i, st, q.n_sets);
-            case DH_IDENT_VIEWS_FAULT: return instance_refusal(part.skip.fault, in.scale, i, set->radius, largest, who);
+            case DH_IDENT_VIEWS_WHERE: case DH_IDENT_VIEWS_FAULT:      // (the view, the camera or the set; R, t or scale)
+                return views_skip_refusal(part.skip, in, i, n, st, q.n_sets, 0u, 1u, set->radius, largest, who);
             default:
                 return fail(DH_EINVAL, "%s: instance %u sums %llu terms (%d views of %u points), above %u", who, i, (unsigned long long)part.terms,
                             __builtin_popcountll(in.views), set->n, DH_FIT_MAX_POINTS);
@@ -4102,14 +4076,8 @@ static int ident_views_run(dh_fitter *f, const IdentViewsReq &q, bool dev, hipSt
     a.cams = q.views->cams->dev.get();
     a.views = q.views->dev.get();
     a.n_inst = q.n_inst;
-    a.coarse = 0; a.full = prm.iterations; a.min_points = prm.min_points;
-    a.gate[0] = prm.gate; a.gate[1] = prm.gate;
-    a.lam1 = 1.0 + prm.lambda;
-    g.models = set->table.get();
-    g.np = set->n; g.n_subjects = q.n_subjects;
-    g.radius = set->radius; g.largest = largest;
+    ident_args_common(g, set, q.n_subjects, prm);
     g.n_sets = q.n_sets;
-    g.max_ms = prm.max_rms * prm.max_rms; g.min_ratio = prm.min_ratio;
     // ---- the pair scratch: the fitter's, grown on demand (growing waits for the device, as the other tables do); the poses are
     // section 27's buffer, which is why all identify calls of a fitter must be stream-ordered with one another
     const bool own_scores = !dev || !q.scores;
@@ -4119,56 +4087,21 @@ static int ident_views_run(dh_fitter *f, const IdentViewsReq &q, bool dev, hipSt
         TRY(f->ident_pose.grow((size_t)pairs * 12));
     }
     g.pose = f->ident_pose.get();
-    if (!dev) {
-        const size_t n_px = (size_t)q.n_sets * n * q.w * q.h;
-        if (f->frames.cap() < n_px || f->shape_vinst.cap() < q.n_inst || !f->shape_vinst || f->ident_sub.cap() < q.n_inst || !f->ident_vposes ||
-            f->ident_vposes.cap() < q.n_inst || !f->ident_enrolled)
-            HIP_TRY(hipDeviceSynchronize());
-        TRY(f->frames.grow(n_px));
-        if (f->shape_vinst.cap() < q.n_inst || !f->shape_vinst) {
-            TRY(f->shape_vinst.grow(q.n_inst));
-            TRY(f->shape_vsubj.alloc(f->shape_vinst.cap()));
-            TRY(f->shape_vsets.alloc(f->shape_vinst.cap()));
-        }
-        if (f->ident_sub.cap() < q.n_inst) {
-            TRY(f->ident_sub.grow(q.n_inst));
-            TRY(f->ident_rec.alloc(f->ident_sub.cap()));
-            TRY(f->ident_poses.alloc(f->ident_sub.cap()));
-        }
-        if (f->ident_vposes.cap() < q.n_inst || !f->ident_vposes) {
-            TRY(f->ident_vposes.grow(q.n_inst));
-            TRY(f->ident_vfit_rec.alloc(f->ident_vposes.cap()));
-        }
-        if (!f->ident_enrolled) TRY(f->ident_enrolled.alloc(DH_SHAPE_MAX_SUBJECTS));
-        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(f->shape_vinst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_view_instance), hipMemcpyHostToDevice, s));
-        if (q.sets) HIP_TRY(hipMemcpyAsync(f->shape_vsets.get(), q.sets, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (q.enrolled) HIP_TRY(hipMemcpyAsync(f->ident_enrolled.get(), q.enrolled, q.n_subjects, hipMemcpyHostToDevice, s));
-        if (q.fit_rec) HIP_TRY(hipMemcpyAsync(f->ident_vfit_rec.get(), q.fit_rec, (size_t)q.n_inst * sizeof(dh_view_fit_record), hipMemcpyHostToDevice, s));
-        a.frames = f->frames.get(); a.inst = f->shape_vinst.get();
-        g.sets = q.sets ? f->shape_vsets.get() : nullptr;
-        g.enrolled = q.enrolled ? f->ident_enrolled.get() : nullptr;
-        g.fit_rec = q.fit_rec ? f->ident_vfit_rec.get() : nullptr;
-        g.score = f->ident_vscore.get();
-        g.subjects_out = f->ident_sub.get(); g.rec = f->ident_rec.get();
-        g.poses_out = q.poses_out ? f->ident_vposes.get() : nullptr;
-    } else {
-        a.frames = q.frames; a.inst = q.inst;
-        g.sets = q.sets; g.enrolled = q.enrolled; g.fit_rec = q.fit_rec;
-        g.score = q.scores ? q.scores : f->ident_vscore.get();
-        g.subjects_out = q.subjects_out; g.rec = q.rec; g.poses_out = q.poses_out;
-    }
+    CallArgs args(f, dev, s);
+    args.in(&a.frames, q.frames, (size_t)q.n_sets * n * q.w * q.h);
+    args.in(&a.inst, q.inst, q.n_inst);
+    args.in(&g.sets, q.sets, q.n_inst);
+    args.in(&g.enrolled, q.enrolled, q.n_subjects);
+    args.in(&g.fit_rec, q.fit_rec, q.n_inst);
+    args.out(&g.subjects_out, q.subjects_out, q.n_inst);
+    args.out(&g.rec, q.rec, q.n_inst);
+    args.out(&g.poses_out, q.poses_out, q.n_inst);
+    args.out(&g.score, q.scores, (size_t)pairs, f->ident_vscore.get());
+    TRY(args.commit());
     // ---- the two stream-ordered operations
     TRY(hip_step(dh_launch_ident_views_score(g, s), "k_ident_views_score"));
     TRY(hip_step(dh_launch_ident_views_decide(g, s), "k_ident_views_decide"));
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(q.subjects_out, g.subjects_out, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(q.rec, g.rec, (size_t)q.n_inst * sizeof(dh_ident_record), hipMemcpyDeviceToHost, s));
-        if (q.poses_out) HIP_TRY(hipMemcpyAsync(q.poses_out, g.poses_out, (size_t)q.n_inst * sizeof(dh_view_instance), hipMemcpyDeviceToHost, s));
-        if (q.scores) HIP_TRY(hipMemcpyAsync(q.scores, g.score, (size_t)pairs * sizeof(dh_view_fit_record), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return DH_OK;
+    return args.finish();
 }
 static int fit_identify_subjects_views_(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_subjects *set,
                                         const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint8_t *enrolled, uint32_t n_subjects,
@@ -4199,12 +4132,8 @@ struct ShapeViewsReq {
 static int shape_views_run(dh_fitter *f, const ShapeViewsReq &q, bool dev, hipStream_t stream, const char *who) {
     // ---- refusals: all of them before anything is allocated or launched
     TRY(shape_check_pointers(f, q.frames, q.rec, q.model, q.basis, who));
-    if (!q.views) return fail(DH_EINVAL, "%s: NULL view table", who);
-    if (q.views->device != f->device) return fail(DH_EINVAL, "%s: the view table lives on device %d, the fitter on %d", who, q.views->device, f->device);
-    const int n = q.views->n;
-    if (q.n_sets < 1 || (uint64_t)q.n_sets * (uint64_t)n > 65535)
-        return fail(DH_EINVAL, "%s: n_sets = %u of %d cameras, expected 1 .. 65535 frames", who, q.n_sets, n);
-    TRY(check_frames(n, q.w, q.h, nullptr, q.views->cams, true, f->device, "fitter", who));
+    int n = 0;
+    TRY(check_views(f, q.views, &q.n_sets, q.w, q.h, &n, who));
     dh_shape_params prm;
     TRY(shape_check_call(f, q.model, q.basis, q.n_subjects, q.prm, &prm, q.inst, q.n_inst, who));
     const dh_fit_model *m = q.model;
@@ -4219,15 +4148,8 @@ static int shape_views_run(dh_fitter *f, const ShapeViewsReq &q, bool dev, hipSt
             const dh_view_instance &in = q.inst[i];
             const uint32_t sj = q.subjects ? q.subjects[i] : 0u, set = q.sets ? q.sets[i] : 0u;
             const ShapeViewsSkip sk = dh_shape_views_skip(in, set, sj, (uint32_t)n, q.n_sets, q.n_subjects, m->radius, b->largest);
-            switch (sk.why) {
-            case DH_SHAPE_VIEWS_OK: break;
-            case DH_SHAPE_VIEWS_SKIPPED: continue;
-            case DH_SHAPE_VIEWS_NO_VIEW: return fail(DH_EINVAL, "%s: instance %u is seen by no view", who, i);
-            case DH_SHAPE_VIEWS_CAMERA: return fail(DH_EINVAL, "%s: instance %u names camera %llu of %d", who, i, (unsigned long long)sk.last, n);
-            case DH_SHAPE_VIEWS_SET: return fail(DH_EINVAL, "%s: instance %u names set %u of %u", who, i, set, q.n_sets);
-            case DH_SHAPE_VIEWS_SUBJECT: return fail(DH_EINVAL, "%s: instance %u names subject %u of %u", who, i, sj, q.n_subjects);
-            default: return instance_refusal(sk.fault, in.scale, i, m->radius, b->largest, who);
-            }
+            TRY(views_skip_refusal(sk, in, i, n, set, q.n_sets, sj, q.n_subjects, m->radius, b->largest, who));
+            if (sk.why == DH_SHAPE_VIEWS_SKIPPED) continue;
             per[sj] += (uint64_t)__builtin_popcountll(in.views) * m->n;
             if (per[sj] > DH_SHAPE_MAX_TERMS)
                 return fail(DH_EINVAL, "%s: subject %u has more than %u terms (views times %u points)", who, sj, DH_SHAPE_MAX_TERMS, m->n);
@@ -4247,34 +4169,18 @@ static int shape_views_run(dh_fitter *f, const ShapeViewsReq &q, bool dev, hipSt
     shape_args_common(a, f, m, b, q.n_inst, q.n_subjects, prm);
     v.views = q.views->dev.get();
     v.n_sets = q.n_sets; v.ranks = ranks;
-    if (!dev) {
-        const size_t n_px = (size_t)q.n_sets * n * q.w * q.h;
-        if (f->frames.cap() < n_px || f->shape_vinst.cap() < q.n_inst || !f->shape_vinst || !f->shape_rec) HIP_TRY(hipDeviceSynchronize());
-        TRY(f->frames.grow(n_px));
-        if (f->shape_vinst.cap() < q.n_inst || !f->shape_vinst) {
-            TRY(f->shape_vinst.grow(std::max<size_t>(q.n_inst, 1)));
-            TRY(f->shape_vsubj.alloc(f->shape_vinst.cap()));
-            TRY(f->shape_vsets.alloc(f->shape_vinst.cap()));
-        }
-        if (!f->shape_rec) TRY(f->shape_rec.alloc(DH_SHAPE_MAX_SUBJECTS));
-        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        if (q.n_inst) HIP_TRY(hipMemcpyAsync(f->shape_vinst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_view_instance), hipMemcpyHostToDevice, s));
-        if (q.n_inst && q.subjects) HIP_TRY(hipMemcpyAsync(f->shape_vsubj.get(), q.subjects, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (q.n_inst && q.sets) HIP_TRY(hipMemcpyAsync(f->shape_vsets.get(), q.sets, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        a.frames = f->frames.get(); v.inst = f->shape_vinst.get();
-        a.subjects = q.subjects ? f->shape_vsubj.get() : nullptr;
-        v.sets = q.sets ? f->shape_vsets.get() : nullptr;
-        a.rec = f->shape_rec.get();
-    } else { a.frames = q.frames; v.inst = q.inst; a.subjects = q.subjects; v.sets = q.sets; a.rec = q.rec; }
+    CallArgs args(f, dev, s);
+    args.in(&a.frames, q.frames, (size_t)q.n_sets * n * q.w * q.h);
+    args.in(&v.inst, q.inst, q.n_inst);
+    args.in(&a.subjects, q.subjects, q.n_inst);
+    args.in(&v.sets, q.sets, q.n_inst);
+    args.out(&a.rec, q.rec, q.n_subjects);
+    TRY(args.commit());
     // ---- the three stream-ordered operations
     TRY(hip_step(dh_launch_shape_clear(a, s), "k_shape_clear"));
     TRY(hip_step(dh_launch_shape_accumulate_views(v, s), "k_shape_accumulate_views"));
     TRY(hip_step(dh_launch_shape_solve(a, s), "k_shape_solve"));
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)q.n_subjects * sizeof(dh_shape_record), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return DH_OK;
+    return args.finish();
 }
 static int fit_shape_views_(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model,
                             const dh_fit_basis *basis, const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets,
@@ -4314,12 +4220,8 @@ static int calib_run(dh_fitter *f, const CalibReq &q, bool dev, hipStream_t stre
     if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
     if (!q.rec) return fail(DH_EINVAL, "%s: NULL records", who);
     if (!q.model) return fail(DH_EINVAL, "%s: NULL model", who);
-    if (!q.views) return fail(DH_EINVAL, "%s: NULL view table", who);
-    if (q.views->device != f->device) return fail(DH_EINVAL, "%s: the view table lives on device %d, the fitter on %d", who, q.views->device, f->device);
-    const int n = q.views->n;
-    if (q.n_sets < 1 || (uint64_t)q.n_sets * (uint64_t)n > 65535)
-        return fail(DH_EINVAL, "%s: n_sets = %u of %d cameras, expected 1 .. 65535 frames", who, q.n_sets, n);
-    TRY(check_frames(n, q.w, q.h, nullptr, q.views->cams, true, f->device, "fitter", who));
+    int n = 0;
+    TRY(check_views(f, q.views, &q.n_sets, q.w, q.h, &n, who));
     dh_calib_params prm;
     (void)calib_params_default_(&prm);
     if (q.prm) prm = *q.prm;
@@ -4342,14 +4244,8 @@ static int calib_run(dh_fitter *f, const CalibReq &q, bool dev, hipStream_t stre
             const dh_view_instance &in = q.inst[i];
             const uint32_t tk = q.take ? q.take[i] : 0u, set = q.sets ? q.sets[i] : 0u;
             const ShapeViewsSkip sk = dh_calib_skip(in, set, tk, (uint32_t)n, q.n_sets, m->radius);
-            switch (sk.why) {
-            case DH_SHAPE_VIEWS_OK: break;
-            case DH_SHAPE_VIEWS_SKIPPED: continue;
-            case DH_SHAPE_VIEWS_NO_VIEW: return fail(DH_EINVAL, "%s: instance %u is seen by no view", who, i);
-            case DH_SHAPE_VIEWS_CAMERA: return fail(DH_EINVAL, "%s: instance %u names camera %llu of %d", who, i, (unsigned long long)sk.last, n);
-            case DH_SHAPE_VIEWS_SET: return fail(DH_EINVAL, "%s: instance %u names set %u of %u", who, i, set, q.n_sets);
-            default: return instance_refusal(sk.fault, in.scale, i, m->radius, 0.0, who);
-            }
+            TRY(views_skip_refusal(sk, in, i, n, set, q.n_sets, 0u, 1u, m->radius, 0.0, who));
+            if (sk.why == DH_SHAPE_VIEWS_SKIPPED) continue;
             for (uint32_t k = 0; k < 64; ++k) {
                 if (!((in.views >> k) & 1ull)) continue;
                 const uint32_t c = in.first_cam + k;
@@ -4377,36 +4273,19 @@ static int calib_run(dh_fitter *f, const CalibReq &q, bool dev, hipStream_t stre
     a.min_points = prm.min_points; a.gate = prm.gate; a.lam1 = 1.0 + prm.lambda;
     for (int j = 0; j < 3; ++j) a.pivot[j] = prm.pivot[j];
     a.sums = f->calib_sums.get();
-    if (!dev) {
-        const size_t n_px = (size_t)q.n_sets * n * q.w * q.h;
-        if (f->frames.cap() < n_px || f->shape_vinst.cap() < q.n_inst || !f->shape_vinst || f->calib_hold.cap() < (size_t)n) HIP_TRY(hipDeviceSynchronize());
-        TRY(f->frames.grow(n_px));
-        if (f->shape_vinst.cap() < q.n_inst || !f->shape_vinst) {
-            TRY(f->shape_vinst.grow(std::max<size_t>(q.n_inst, 1)));
-            TRY(f->shape_vsubj.alloc(f->shape_vinst.cap()));
-            TRY(f->shape_vsets.alloc(f->shape_vinst.cap()));
-        }
-        if (f->calib_hold.cap() < (size_t)n) { TRY(f->calib_hold.grow((size_t)n)); TRY(f->calib_rec.grow((size_t)n)); }
-        HIP_TRY(hipMemcpyAsync(f->frames.get(), q.frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        if (q.n_inst) HIP_TRY(hipMemcpyAsync(f->shape_vinst.get(), q.inst, (size_t)q.n_inst * sizeof(dh_view_instance), hipMemcpyHostToDevice, s));
-        if (q.n_inst && q.take) HIP_TRY(hipMemcpyAsync(f->shape_vsubj.get(), q.take, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (q.n_inst && q.sets) HIP_TRY(hipMemcpyAsync(f->shape_vsets.get(), q.sets, (size_t)q.n_inst * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (q.hold) HIP_TRY(hipMemcpyAsync(f->calib_hold.get(), q.hold, (size_t)n, hipMemcpyHostToDevice, s));
-        a.frames = f->frames.get(); a.inst = f->shape_vinst.get();
-        a.take = q.take ? f->shape_vsubj.get() : nullptr;
-        a.sets = q.sets ? f->shape_vsets.get() : nullptr;
-        a.hold = q.hold ? f->calib_hold.get() : nullptr;
-        a.rec = f->calib_rec.get();
-    } else { a.frames = q.frames; a.inst = q.inst; a.take = q.take; a.sets = q.sets; a.hold = q.hold; a.rec = q.rec; }
+    CallArgs args(f, dev, s);
+    args.in(&a.frames, q.frames, (size_t)q.n_sets * n * q.w * q.h);
+    args.in(&a.inst, q.inst, q.n_inst);
+    args.in(&a.take, q.take, q.n_inst);
+    args.in(&a.sets, q.sets, q.n_inst);
+    args.in(&a.hold, q.hold, (size_t)n);
+    args.out(&a.rec, q.rec, (size_t)n);
+    TRY(args.commit());
     // ---- the three stream-ordered operations
     TRY(hip_step(dh_launch_calib_clear(a, s), "k_calib_clear"));
     TRY(hip_step(dh_launch_calib_accumulate(a, s), "k_calib_accumulate"));
     TRY(hip_step(dh_launch_calib_solve(a, s), "k_calib_solve"));
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(q.rec, a.rec, (size_t)n * sizeof(dh_calib_record), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return DH_OK;
+    return args.finish();
 }
 static int fit_calibrate_views_(dh_fitter *f, const uint16_t *frames, uint32_t n_sets, int w, int h, const dh_fit_views *views, const dh_fit_model *model,
                                 const dh_view_instance *instances, uint32_t n_instances, const uint32_t *sets, const uint32_t *take, const uint8_t *hold,
