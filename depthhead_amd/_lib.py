@@ -329,6 +329,35 @@ def vp(x):
     return C.c_void_p(int(x))
 
 
+def ref(struct):
+    """byref(struct), or None for None: a params argument that may be absent."""
+    return None if struct is None else C.byref(struct)
+
+
+def intrinsics(K_or_cameras):
+    """(suffix of the call's name, its argument) for one K ([3, 3] or an `IntrinsicMatrix`) or a `tracking.Cameras` table."""
+    cams = getattr(K_or_cameras, "_h", None)
+    if cams is not None:
+        return "_cameras", cams
+    return "", held(np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9))
+
+
+def stream_of(device, stream=None) -> int:
+    """The stream handle a _device form is ordered on: `stream`, or for None the current torch stream of `device` (an ordinal
+    or a torch.device)."""
+    if stream is not None:
+        return int(stream)
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def held(array: np.ndarray):
+    """void* from a numpy array that carries the array, which so lives as long as the pointer does: for an array made on the way."""
+    p = C.c_void_p(array.ctypes.data)
+    p.array = array
+    return p
+
+
 class _Handle:
     """Owner of library handles.  `close()` -- also at the end of a `with` block and at garbage collection, where what it
     raises is swallowed -- destroys each handle of `_handles`, (attribute, destroy function) pairs, once and in that order."""

@@ -4,6 +4,7 @@ degrees.  All arithmetic of the fit runs in libdepthhead_hip.so (k_fit.hip); the
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -178,65 +179,50 @@ class ShapeBasis(_lib._Handle):
         return n.value, k.value, largest.value
 
 
+def _params(struct, default: str, **fields):
+    """A `struct` as the library's `default` function fills it, with every field given (not None) replaced: cast by the field's
+    own ctypes type -- doubles with float, integers with int, an array element by element (as many values as it has elements)."""
+    p = struct()
+    check(getattr(_lib.load(), default)(C.byref(p)))
+    types = dict(struct._fields_)
+    for name, value in fields.items():
+        if value is None:
+            continue
+        t = types[name]
+        if issubclass(t, C.Array):
+            cast = float if t._type_ is C.c_double else int
+            getattr(p, name)[:] = [cast(v) for v in value]
+        else:
+            setattr(p, name, float(value) if t is C.c_double else int(value))
+    return p
+
+
 def shape_params(gate=None, lam=None, min_points=None) -> "_lib.ShapeParams":
     """dh_shape_params_default with the given fields replaced."""
-    p = _lib.ShapeParams()
-    check(_lib.load().dh_shape_params_default(C.byref(p)))
-    if gate is not None:
-        p.gate = float(gate)
-    if lam is not None:
-        p.lam = float(lam)
-    if min_points is not None:
-        p.min_points = int(min_points)
-    return p
+    return _params(_lib.ShapeParams, "dh_shape_params_default", gate=gate, lam=lam, min_points=min_points)
 
 
 def surface_params(gate=None, min_cos2=None, mu=None, eps=None, min_count=None, min_points=None, iterations=None) -> "_lib.SurfaceParams":
     """dh_fit_surface_params_default with the given fields replaced."""
-    p = _lib.SurfaceParams()
-    check(_lib.load().dh_fit_surface_params_default(C.byref(p)))
-    for name, value, cast in (("gate", gate, float), ("min_cos2", min_cos2, float), ("mu", mu, float), ("eps", eps, float),
-                              ("min_count", min_count, int), ("min_points", min_points, int), ("iterations", iterations, int)):
-        if value is not None:
-            setattr(p, name, cast(value))
-    return p
+    return _params(_lib.SurfaceParams, "dh_fit_surface_params_default", gate=gate, min_cos2=min_cos2, mu=mu, eps=eps, min_count=min_count,
+                   min_points=min_points, iterations=iterations)
 
 
 def ident_params(iterations=None, min_points=None, gate=None, lam=None, max_rms=None, min_ratio=None) -> "_lib.IdentParams":
     """dh_fit_ident_params_default with the given fields replaced."""
-    p = _lib.IdentParams()
-    check(_lib.load().dh_fit_ident_params_default(C.byref(p)))
-    for name, value, cast in (("iterations", iterations, int), ("min_points", min_points, int), ("gate", gate, float), ("lam", lam, float),
-                              ("max_rms", max_rms, float), ("min_ratio", min_ratio, float)):
-        if value is not None:
-            setattr(p, name, cast(value))
-    return p
+    return _params(_lib.IdentParams, "dh_fit_ident_params_default", iterations=iterations, min_points=min_points, gate=gate, lam=lam, max_rms=max_rms,
+                   min_ratio=min_ratio)
 
 
 def ident_views_params(iterations=None, min_points=None, gate=None, lam=None, max_rms=None, min_ratio=None) -> "_lib.IdentParams":
     """dh_fit_ident_views_params_default -- the multi-view call's own measured max_rms -- with the given fields replaced."""
-    p = _lib.IdentParams()
-    check(_lib.load().dh_fit_ident_views_params_default(C.byref(p)))
-    for name, value, cast in (("iterations", iterations, int), ("min_points", min_points, int), ("gate", gate, float), ("lam", lam, float),
-                              ("max_rms", max_rms, float), ("min_ratio", min_ratio, float)):
-        if value is not None:
-            setattr(p, name, cast(value))
-    return p
+    return _params(_lib.IdentParams, "dh_fit_ident_views_params_default", iterations=iterations, min_points=min_points, gate=gate, lam=lam,
+                   max_rms=max_rms, min_ratio=min_ratio)
 
 
 def calib_params(gate=None, lam=None, min_points=None, pivot=None) -> "_lib.CalibParams":
     """dh_calib_params_default with the given fields replaced."""
-    p = _lib.CalibParams()
-    check(_lib.load().dh_calib_params_default(C.byref(p)))
-    if gate is not None:
-        p.gate = float(gate)
-    if lam is not None:
-        p.lam = float(lam)
-    if min_points is not None:
-        p.min_points = int(min_points)
-    if pivot is not None:
-        p.pivot[0], p.pivot[1], p.pivot[2] = (float(v) for v in pivot)
-    return p
+    return _params(_lib.CalibParams, "dh_calib_params_default", gate=gate, lam=lam, min_points=min_points, pivot=pivot)
 
 
 def views_from_records(cameras, views_V, views_u, records) -> "Views":
@@ -270,19 +256,116 @@ def deform(verts, basis, coeffs) -> np.ndarray:
 
 def fit_params(coarse_iterations=None, iterations=None, gate=None, lam=None, min_points=None) -> "_lib.FitParams":
     """dh_fit_params_default with the given fields replaced."""
-    p = _lib.FitParams()
-    check(_lib.load().dh_fit_params_default(C.byref(p)))
-    if coarse_iterations is not None:
-        p.coarse_iterations = int(coarse_iterations)
-    if iterations is not None:
-        p.iterations = int(iterations)
-    if gate is not None:
-        p.gate[0], p.gate[1] = float(gate[0]), float(gate[1])
-    if lam is not None:
-        p.lam = float(lam)
-    if min_points is not None:
-        p.min_points = int(min_points)
-    return p
+    return _params(_lib.FitParams, "dh_fit_params_default", coarse_iterations=coarse_iterations, iterations=iterations, gate=gate, lam=lam,
+                   min_points=min_points)
+
+
+_RECORD_NAMES = {FIT_RECORD_DTYPE: "dh_fit_record", VIEW_FIT_RECORD_DTYPE: "dh_view_fit_record"}
+
+
+def check_tensor(t, device, name, dtype=None, count=None, per="instance"):
+    """ValueError, in the words of argument `name`, unless the torch tensor `t` can go to a _device form as a device address:
+    it lies on `device` (a torch.device), is contiguous and, where `count` is given, is `count` items of `dtype` long -- in
+    elements of the dtype's own size for a plain dtype (the frames, the word and the byte arrays), of any size for a record
+    dtype.  `per` is what the message says there is one item of.  Needs no fitter and no GPU."""
+    dtype = None if dtype is None else np.dtype(dtype)
+    plain = dtype is not None and dtype.names is None
+    if (t.device == device and t.is_contiguous() and (not plain or t.element_size() == dtype.itemsize)
+            and (count is None or t.numel() * t.element_size() == count * dtype.itemsize)):
+        return
+    if name == "frames":
+        raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
+    if name == "instances":
+        raise ValueError("device instances: a contiguous tensor on the fitter's device is expected")
+    if name == "carried":
+        raise ValueError("carried: the contiguous device tensor of an earlier fit of as many instances is expected")
+    if plain:
+        raise ValueError(f"device {name}: a contiguous {8 * dtype.itemsize}-bit tensor with one {'word' if dtype.itemsize == 4 else 'byte'} "
+                         f"per {per} is expected")
+    raise ValueError(f"device {name}: the contiguous tensor of one {_RECORD_NAMES[dtype]} per {per} is expected")
+
+
+_U8, _U16, _U32 = np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.uint32)
+_DEVICES = {}       # ordinal -> (torch, torch.device("cuda", ordinal)), filled by the first _device form of a fitter on it
+
+
+class _Call:
+    """The arguments of one call of a Fitter, bound for its host form or its _device form.  The method
+    writes the C call once, `call(name, argument, ...)` in the header's order after the fitter's handle, and gets each array
+    argument from one of the methods below; Python evaluates them from left to right, so every refusal comes in the header's
+    order and before the first output is allocated.  Host form: numpy arrays in and out, each input kept alive by its
+    pointer.  _device form: torch tensors on the fitter's device, checked by `check_tensor`, and the stream as the last
+    argument.  After `instances`, `ni` is their count."""
+    dev, ni, infix = None, 0, ""
+
+    def __init__(self, fitter, device_out: bool, stream):
+        self.fitter, self.stream, self.outs = fitter, stream, []
+        if device_out:
+            if fitter.device not in _DEVICES:
+                import torch
+                _DEVICES[fitter.device] = torch, torch.device("cuda", fitter.device)
+            self.torch, self.dev = _DEVICES[fitter.device]
+
+    def frames(self, frames):
+        if self.dev is None:
+            return _lib.held(np.ascontiguousarray(frames, dtype=_U16))
+        check_tensor(frames, self.dev, "frames", _U16)
+        return C.c_void_p(frames.data_ptr())
+
+    def instances(self, instances, dtype, host: bool = False):
+        """The instances, NULL when there are none; host=True: a numpy array in both forms."""
+        if self.dev is None or host:
+            inst = np.ascontiguousarray(instances, dtype=dtype)
+            self.ni = len(inst)
+            return _lib.held(inst) if self.ni else None
+        check_tensor(instances, self.dev, "instances")
+        self.ni = instances.numel() * instances.element_size() // dtype.itemsize
+        return C.c_void_p(instances.data_ptr()) if self.ni else None
+
+    def inp(self, name, array, dtype, count, per="instance", nonzero: bool = False):
+        """A nullable input of `count` items of `dtype`, one per `per`: None binds NULL.  nonzero=True: bytes that the host form
+        normalises with != 0."""
+        if array is None:
+            return None
+        if self.dev is None:
+            return _lib.held(np.ascontiguousarray(np.asarray(array) != 0 if nonzero else array, dtype=dtype).reshape(max(count, 0)))
+        check_tensor(array, self.dev, name, dtype, count, per)
+        return C.c_void_p(array.data_ptr())
+
+    def carried(self, carried, dtype):
+        """The instances an earlier fit left on the device, to be spliced into the list with `*`: an argument of the _device
+        form alone, and only when given -- the call's name then gets `_carried`."""
+        if carried is None or self.dev is None:
+            return ()
+        check_tensor(carried, self.dev, "carried", dtype, self.ni)
+        self.infix = "_carried"
+        return (C.c_void_p(carried.data_ptr()) if self.ni else None,)
+
+    def out(self, dtype, *shape, fill=0, give: bool = True, spare: int = 1):
+        """An output of `shape` items of `dtype`; give=False: NULL, and the call returns nothing for it.  Host form: a numpy
+        array of `fill`.  _device form: a flat torch tensor -- int32 for words, else the records' bytes as uint8 -- of at least
+        `spare` items, cut to the items asked for (no empty allocation: its address would be NULL)."""
+        if not give:
+            return None
+        if self.dev is None:
+            shape = tuple([max(s, 0) for s in shape])
+            self.outs.append(np.full(shape, fill, dtype) if fill else np.zeros(shape, dtype))
+            return vp(self.outs[-1])
+        count = math.prod(shape)
+        size, kind = (1, self.torch.int32) if dtype.names is None else (dtype.itemsize, self.torch.uint8)
+        t = self.torch.empty(max(count, spare) * size, dtype=kind, device=self.dev)
+        self.outs.append(t if count >= spare else t[:count * size])     # (cut only where the spare item was allocated)
+        return C.c_void_p(t.data_ptr())
+
+    def call(self, name, *args):
+        """Call `name` -- `name` + `_device` with the stream appended in that form -- and return the outputs in the order they
+        were declared: one as itself, several as a tuple."""
+        f = self.fitter
+        if self.dev is None:
+            check(getattr(f._lib, name)(f._h, *args))
+        else:
+            check(getattr(f._lib, name + self.infix + "_device")(f._h, *args, C.c_void_p(_lib.stream_of(self.dev, self.stream))))
+        return self.outs[0] if len(self.outs) == 1 else tuple(self.outs)
 
 
 class Fitter(_lib._Handle):
@@ -303,43 +386,14 @@ class Fitter(_lib._Handle):
         (default the current torch stream).  `carried` (device_out=True only): the uint8 tensor an earlier fit(device_out=True)
         returned for the same instances, whose R and t the fit starts from in place of those of `instances` (DESIGN.md section
         25)."""
-        inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
         models = list(models)
         handles = (C.c_void_p * max(len(models), 1))(*[m._h.value for m in models])
         n, h, w = (int(v) for v in frames.shape)
-        cams = getattr(K_or_cameras, "_h", None)
-        if cams is None:
-            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
-            kind, karg = "", vp(K)
-        else:
-            kind, karg = "_cameras", cams
-        prm = C.byref(params) if params is not None else None
-        ni = len(inst)
-        if not device_out:
-            fr = np.ascontiguousarray(frames, dtype=np.uint16)
-            out, rec = np.zeros(ni, RENDER_INSTANCE_DTYPE), np.zeros(ni, FIT_RECORD_DTYPE)
-            check(getattr(self._lib, "dh_fit_depth" + kind)(self._h, vp(fr), n, w, h, karg, handles, C.c_uint32(len(models)),
-                                                             vp(inst) if ni else None, C.c_uint32(ni), prm, vp(out), vp(rec)))
-            return out, rec
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
-            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
-        out = torch.empty(max(ni, 1) * RENDER_INSTANCE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        rec = torch.empty(max(ni, 1) * FIT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
-        if carried is not None:
-            if carried.numel() * carried.element_size() != ni * RENDER_INSTANCE_DTYPE.itemsize or not carried.is_contiguous() or carried.device != dev:
-                raise ValueError("carried: the contiguous device tensor of an earlier fit of as many instances is expected")
-            check(getattr(self._lib, "dh_fit_depth" + kind + "_carried_device")(
-                self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, handles, C.c_uint32(len(models)), vp(inst) if ni else None, C.c_uint32(ni),
-                C.c_void_p(carried.data_ptr()) if ni else None, prm, C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
-            return out[:ni * RENDER_INSTANCE_DTYPE.itemsize], rec[:ni * FIT_RECORD_DTYPE.itemsize]
-        check(getattr(self._lib, "dh_fit_depth" + kind + "_device")(self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, handles,
-                                                                      C.c_uint32(len(models)), vp(inst) if ni else None, C.c_uint32(ni), prm,
-                                                                      C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
-        return out[:ni * RENDER_INSTANCE_DTYPE.itemsize], rec[:ni * FIT_RECORD_DTYPE.itemsize]
-
+        kind, karg = _lib.intrinsics(K_or_cameras)
+        b = _Call(self, device_out, stream)
+        return b.call("dh_fit_depth" + kind, b.frames(frames), n, w, h, karg, handles, C.c_uint32(len(models)),
+                      b.instances(instances, RENDER_INSTANCE_DTYPE, host=True), C.c_uint32(b.ni), *b.carried(carried, RENDER_INSTANCE_DTYPE),
+                      _lib.ref(params), b.out(RENDER_INSTANCE_DTYPE, b.ni), b.out(FIT_RECORD_DTYPE, b.ni))
 
     def fit_views(self, frames, models, instances, views, params=None, device_out: bool = False, stream=None):
         """Fit each of `instances` (VIEW_INSTANCE_DTYPE: one world pose and the mask of the cameras that see it) against the
@@ -347,31 +401,15 @@ class Fitter(_lib._Handle):
         (a `Views` of n cameras): a numpy array, or a torch tensor on the device with device_out=True.  Returns (instances,
         records) -- VIEW_INSTANCE_DTYPE and VIEW_FIT_RECORD_DTYPE arrays, or with device_out=True two uint8 torch tensors on the
         device holding them, ordered on `stream` (default the current torch stream)."""
-        inst = np.ascontiguousarray(instances, dtype=VIEW_INSTANCE_DTYPE)
         models = list(models)
         handles = (C.c_void_p * max(len(models), 1))(*[m._h.value for m in models])
         n, h, w = (int(v) for v in frames.shape)
         if n != len(views):
             raise ValueError(f"{n} frames for a view table of {len(views)} cameras")
-        prm = C.byref(params) if params is not None else None
-        ni = len(inst)
-        if not device_out:
-            fr = np.ascontiguousarray(frames, dtype=np.uint16)
-            out, rec = np.zeros(ni, VIEW_INSTANCE_DTYPE), np.zeros(ni, VIEW_FIT_RECORD_DTYPE)
-            check(self._lib.dh_fit_depth_views(self._h, vp(fr), w, h, views._h, handles, C.c_uint32(len(models)), vp(inst) if ni else None,
-                                               C.c_uint32(ni), prm, vp(out), vp(rec)))
-            return out, rec
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
-            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
-        out = torch.empty(max(ni, 1) * VIEW_INSTANCE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        rec = torch.empty(max(ni, 1) * VIEW_FIT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
-        check(self._lib.dh_fit_depth_views_device(self._h, C.c_void_p(frames.data_ptr()), w, h, views._h, handles, C.c_uint32(len(models)),
-                                                  vp(inst) if ni else None, C.c_uint32(ni), prm, C.c_void_p(out.data_ptr()),
-                                                  C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
-        return out[:ni * VIEW_INSTANCE_DTYPE.itemsize], rec[:ni * VIEW_FIT_RECORD_DTYPE.itemsize]
+        b = _Call(self, device_out, stream)
+        return b.call("dh_fit_depth_views", b.frames(frames), w, h, views._h, handles, C.c_uint32(len(models)),
+                      b.instances(instances, VIEW_INSTANCE_DTYPE, host=True), C.c_uint32(b.ni), _lib.ref(params),
+                      b.out(VIEW_INSTANCE_DTYPE, b.ni), b.out(VIEW_FIT_RECORD_DTYPE, b.ni))
 
     def shape_step(self, frames, model, basis, instances, K_or_cameras, subjects=None, n_subjects: int = 1, params=None,
                    device_out: bool = False, stream=None):
@@ -381,36 +419,12 @@ class Fitter(_lib._Handle):
         the device (instances as the uint8 tensor Fitter.fit(device_out=True) returned, subjects int32 or None) and the records
         come back as a uint8 torch tensor, ordered on `stream` (default the current torch stream) without a host wait."""
         n, h, w = (int(v) for v in frames.shape)
-        cams = getattr(K_or_cameras, "_h", None)
-        if cams is None:
-            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
-            kind, karg = "", vp(K)
-        else:
-            kind, karg = "_cameras", cams
-        prm = C.byref(params) if params is not None else None
+        kind, karg = _lib.intrinsics(K_or_cameras)
         ns = int(n_subjects)
-        if not device_out:
-            fr = np.ascontiguousarray(frames, dtype=np.uint16)
-            inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
-            subj = None if subjects is None else np.ascontiguousarray(subjects, dtype=np.uint32).reshape(len(inst))
-            rec = np.zeros(max(ns, 0), SHAPE_RECORD_DTYPE)
-            check(getattr(self._lib, "dh_fit_shape" + kind)(self._h, vp(fr), n, w, h, karg, model._h, basis._h, vp(inst) if len(inst) else None,
-                                                             C.c_uint32(len(inst)), vp(subj), C.c_uint32(ns), prm, vp(rec)))
-            return rec
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
-            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
-        ni = instances.numel() * instances.element_size() // RENDER_INSTANCE_DTYPE.itemsize
-        if subjects is not None and (subjects.numel() != ni or subjects.element_size() != 4 or not subjects.is_contiguous()):
-            raise ValueError("device subjects: a contiguous 32-bit tensor with one word per instance is expected")
-        rec = torch.empty(max(ns, 1) * SHAPE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
-        check(getattr(self._lib, "dh_fit_shape" + kind + "_device")(self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, model._h, basis._h,
-                                                                      C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
-                                                                      C.c_void_p(subjects.data_ptr()) if subjects is not None else None,
-                                                                      C.c_uint32(ns), prm, C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
-        return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
+        b = _Call(self, device_out, stream)
+        return b.call("dh_fit_shape" + kind, b.frames(frames), n, w, h, karg, model._h, basis._h, b.instances(instances, RENDER_INSTANCE_DTYPE),
+                      C.c_uint32(b.ni), b.inp("subjects", subjects, _U32, b.ni), C.c_uint32(ns), _lib.ref(params),
+                      b.out(SHAPE_RECORD_DTYPE, ns))
 
     def shape_step_subjects(self, frames, subjects_set, instances, K_or_cameras, subjects=None, n_subjects=None, fit_records=None, params=None,
                             device_out: bool = False, stream=None):
@@ -420,40 +434,8 @@ class Fitter(_lib._Handle):
         SHAPE_RECORD_DTYPE [n_subjects].  With device_out=True frames, instances, subjects and fit_records are torch tensors on
         the device (instances and fit_records as the uint8 tensors Fitter.fit(device_out=True) returned, subjects int32 or None)
         and the records come back as a uint8 torch tensor, ordered on `stream` without a host wait."""
-        n, h, w = (int(v) for v in frames.shape)
-        cams = getattr(K_or_cameras, "_h", None)
-        if cams is None:
-            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
-            kind, karg = "", vp(K)
-        else:
-            kind, karg = "_cameras", cams
-        prm = C.byref(params) if params is not None else None
-        ns = len(subjects_set) if n_subjects is None else int(n_subjects)
-        if not device_out:
-            fr = np.ascontiguousarray(frames, dtype=np.uint16)
-            inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
-            subj = None if subjects is None else np.ascontiguousarray(subjects, dtype=np.uint32).reshape(len(inst))
-            frec = None if fit_records is None else np.ascontiguousarray(fit_records, dtype=FIT_RECORD_DTYPE).reshape(len(inst))
-            rec = np.zeros(max(ns, 0), SHAPE_RECORD_DTYPE)
-            check(getattr(self._lib, "dh_fit_shape_subjects" + kind)(self._h, vp(fr), n, w, h, karg, subjects_set._h, vp(inst) if len(inst) else None,
-                                                                      C.c_uint32(len(inst)), vp(subj), C.c_uint32(ns), vp(frec), prm, vp(rec)))
-            return rec
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
-            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
-        ni = instances.numel() * instances.element_size() // RENDER_INSTANCE_DTYPE.itemsize
-        if subjects is not None and (subjects.numel() != ni or subjects.element_size() != 4 or not subjects.is_contiguous()):
-            raise ValueError("device subjects: a contiguous 32-bit tensor with one word per instance is expected")
-        if fit_records is not None and (fit_records.numel() * fit_records.element_size() != ni * FIT_RECORD_DTYPE.itemsize or not fit_records.is_contiguous()):
-            raise ValueError("device fit_records: the contiguous tensor of one dh_fit_record per instance is expected")
-        rec = torch.empty(max(ns, 1) * SHAPE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
-        check(getattr(self._lib, "dh_fit_shape_subjects" + kind + "_device")(
-            self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, subjects_set._h, C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
-            C.c_void_p(subjects.data_ptr()) if subjects is not None else None, C.c_uint32(ns),
-            C.c_void_p(fit_records.data_ptr()) if fit_records is not None else None, prm, C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
-        return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
+        return self._step_subjects("dh_fit_shape_subjects", SHAPE_RECORD_DTYPE, frames, subjects_set, instances, K_or_cameras, subjects, n_subjects,
+                                   fit_records, params, device_out, stream)
 
     def surface_step_subjects(self, frames, subjects_set, instances, K_or_cameras, subjects=None, n_subjects=None, fit_records=None, params=None,
                               device_out: bool = False, stream=None):
@@ -462,40 +444,19 @@ class Fitter(_lib._Handle):
         `shape_step_subjects`'s.  Host form: numpy arrays -> SURFACE_RECORD_DTYPE [n_subjects].  With device_out=True frames,
         instances, subjects and fit_records are torch tensors on the device and the records come back as a uint8 torch tensor:
         five kernels ordered on `stream`, no host wait."""
+        return self._step_subjects("dh_fit_surface_subjects", SURFACE_RECORD_DTYPE, frames, subjects_set, instances, K_or_cameras, subjects,
+                                   n_subjects, fit_records, params, device_out, stream)
+
+    def _step_subjects(self, name, record, frames, subjects_set, instances, K_or_cameras, subjects, n_subjects, fit_records, params, device_out,
+                       stream):
+        """The shape step and the surface step over a subject set: one argument list, two calls and record types."""
         n, h, w = (int(v) for v in frames.shape)
-        cams = getattr(K_or_cameras, "_h", None)
-        if cams is None:
-            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
-            kind, karg = "", vp(K)
-        else:
-            kind, karg = "_cameras", cams
-        prm = C.byref(params) if params is not None else None
+        kind, karg = _lib.intrinsics(K_or_cameras)
         ns = len(subjects_set) if n_subjects is None else int(n_subjects)
-        if not device_out:
-            fr = np.ascontiguousarray(frames, dtype=np.uint16)
-            inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
-            subj = None if subjects is None else np.ascontiguousarray(subjects, dtype=np.uint32).reshape(len(inst))
-            frec = None if fit_records is None else np.ascontiguousarray(fit_records, dtype=FIT_RECORD_DTYPE).reshape(len(inst))
-            rec = np.zeros(max(ns, 0), SURFACE_RECORD_DTYPE)
-            check(getattr(self._lib, "dh_fit_surface_subjects" + kind)(self._h, vp(fr), n, w, h, karg, subjects_set._h, vp(inst) if len(inst) else None,
-                                                                        C.c_uint32(len(inst)), vp(subj), C.c_uint32(ns), vp(frec), prm, vp(rec)))
-            return rec
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
-            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
-        ni = instances.numel() * instances.element_size() // RENDER_INSTANCE_DTYPE.itemsize
-        if subjects is not None and (subjects.numel() != ni or subjects.element_size() != 4 or not subjects.is_contiguous()):
-            raise ValueError("device subjects: a contiguous 32-bit tensor with one word per instance is expected")
-        if fit_records is not None and (fit_records.numel() * fit_records.element_size() != ni * FIT_RECORD_DTYPE.itemsize or not fit_records.is_contiguous()):
-            raise ValueError("device fit_records: the contiguous tensor of one dh_fit_record per instance is expected")
-        rec = torch.empty(max(ns, 1) * SURFACE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
-        check(getattr(self._lib, "dh_fit_surface_subjects" + kind + "_device")(
-            self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, subjects_set._h, C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
-            C.c_void_p(subjects.data_ptr()) if subjects is not None else None, C.c_uint32(ns),
-            C.c_void_p(fit_records.data_ptr()) if fit_records is not None else None, prm, C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
-        return rec[:ns * SURFACE_RECORD_DTYPE.itemsize]
+        b = _Call(self, device_out, stream)
+        return b.call(name + kind, b.frames(frames), n, w, h, karg, subjects_set._h, b.instances(instances, RENDER_INSTANCE_DTYPE), C.c_uint32(b.ni),
+                      b.inp("subjects", subjects, _U32, b.ni), C.c_uint32(ns), b.inp("fit_records", fit_records, FIT_RECORD_DTYPE, b.ni),
+                      _lib.ref(params), b.out(record, ns))
 
     def identify_subjects(self, frames, subjects_set, instances, K_or_cameras, n_subjects=None, enrolled=None, fit_records=None, params=None,
                           scores: bool = False, device_out: bool = False, stream=None):
@@ -509,47 +470,13 @@ class Fitter(_lib._Handle):
         arrays.  With device_out=True frames, instances, enrolled (uint8) and fit_records are torch tensors on the device and the
         results come back as torch tensors (subjects int32, the others uint8): two kernels ordered on `stream`, no host wait."""
         n, h, w = (int(v) for v in frames.shape)
-        cams = getattr(K_or_cameras, "_h", None)
-        if cams is None:
-            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
-            kind, karg = "", vp(K)
-        else:
-            kind, karg = "_cameras", cams
-        prm = C.byref(params) if params is not None else None
+        kind, karg = _lib.intrinsics(K_or_cameras)
         ns = len(subjects_set) if n_subjects is None else int(n_subjects)
-        if not device_out:
-            fr = np.ascontiguousarray(frames, dtype=np.uint16)
-            inst = np.ascontiguousarray(instances, dtype=RENDER_INSTANCE_DTYPE)
-            ni = len(inst)
-            enr = None if enrolled is None else np.ascontiguousarray(np.asarray(enrolled) != 0, dtype=np.uint8).reshape(max(ns, 0))
-            frec = None if fit_records is None else np.ascontiguousarray(fit_records, dtype=FIT_RECORD_DTYPE).reshape(ni)
-            sub, rec = np.full(ni, IDENT_UNKNOWN, np.uint32), np.zeros(ni, IDENT_RECORD_DTYPE)
-            poses, sc = np.zeros(ni, RENDER_INSTANCE_DTYPE), np.zeros((ni, max(ns, 0)), FIT_RECORD_DTYPE)
-            check(getattr(self._lib, "dh_fit_identify_subjects" + kind)(self._h, vp(fr), n, w, h, karg, subjects_set._h, vp(inst) if ni else None,
-                                                                         C.c_uint32(ni), vp(enr), C.c_uint32(ns), vp(frec), prm, vp(sub), vp(rec),
-                                                                         vp(poses), vp(sc) if scores else None))
-            return (sub, rec, poses, sc) if scores else (sub, rec, poses)
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
-            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
-        ni = instances.numel() * instances.element_size() // RENDER_INSTANCE_DTYPE.itemsize
-        if enrolled is not None and (enrolled.numel() != ns or enrolled.element_size() != 1 or not enrolled.is_contiguous()):
-            raise ValueError("device enrolled: a contiguous 8-bit tensor with one byte per subject is expected")
-        if fit_records is not None and (fit_records.numel() * fit_records.element_size() != ni * FIT_RECORD_DTYPE.itemsize or not fit_records.is_contiguous()):
-            raise ValueError("device fit_records: the contiguous tensor of one dh_fit_record per instance is expected")
-        sub = torch.empty(max(ni, 1), dtype=torch.int32, device=dev)
-        rec = torch.empty(max(ni, 1) * IDENT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        poses = torch.empty(max(ni, 1) * RENDER_INSTANCE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        sc = torch.empty(max(ni * ns, 1) * FIT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev) if scores else None
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
-        check(getattr(self._lib, "dh_fit_identify_subjects" + kind + "_device")(
-            self._h, C.c_void_p(frames.data_ptr()), n, w, h, karg, subjects_set._h, C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
-            C.c_void_p(enrolled.data_ptr()) if enrolled is not None else None, C.c_uint32(ns),
-            C.c_void_p(fit_records.data_ptr()) if fit_records is not None else None, prm, C.c_void_p(sub.data_ptr()), C.c_void_p(rec.data_ptr()),
-            C.c_void_p(poses.data_ptr()), C.c_void_p(sc.data_ptr()) if scores else None, C.c_void_p(s)))
-        out = (sub[:ni], rec[:ni * IDENT_RECORD_DTYPE.itemsize], poses[:ni * RENDER_INSTANCE_DTYPE.itemsize])
-        return out + (sc[:ni * ns * FIT_RECORD_DTYPE.itemsize],) if scores else out
+        b = _Call(self, device_out, stream)
+        return b.call("dh_fit_identify_subjects" + kind, b.frames(frames), n, w, h, karg, subjects_set._h, b.instances(instances, RENDER_INSTANCE_DTYPE),
+                      C.c_uint32(b.ni), b.inp("enrolled", enrolled, _U8, ns, per="subject", nonzero=True), C.c_uint32(ns),
+                      b.inp("fit_records", fit_records, FIT_RECORD_DTYPE, b.ni), _lib.ref(params), b.out(_U32, b.ni, fill=IDENT_UNKNOWN),
+                      b.out(IDENT_RECORD_DTYPE, b.ni), b.out(RENDER_INSTANCE_DTYPE, b.ni), b.out(FIT_RECORD_DTYPE, b.ni, ns, give=scores))
 
     def shape_step_views(self, frames, views, model, basis, instances, sets=None, subjects=None, n_subjects: int = 1, params=None,
                          device_out: bool = False, stream=None):
@@ -564,34 +491,11 @@ class Fitter(_lib._Handle):
         n_sets, n, h, w = (int(v) for v in frames.shape)
         if n != len(views):
             raise ValueError(f"{n} frames a set for a view table of {len(views)} cameras")
-        prm = C.byref(params) if params is not None else None
         ns = int(n_subjects)
-        if not device_out:
-            fr = np.ascontiguousarray(frames, dtype=np.uint16)
-            inst = np.ascontiguousarray(instances, dtype=VIEW_INSTANCE_DTYPE)
-            st = None if sets is None else np.ascontiguousarray(sets, dtype=np.uint32).reshape(len(inst))
-            subj = None if subjects is None else np.ascontiguousarray(subjects, dtype=np.uint32).reshape(len(inst))
-            rec = np.zeros(max(ns, 0), SHAPE_RECORD_DTYPE)
-            check(self._lib.dh_fit_shape_views(self._h, vp(fr), C.c_uint32(n_sets), w, h, views._h, model._h, basis._h,
-                                               vp(inst) if len(inst) else None, C.c_uint32(len(inst)), vp(st), vp(subj), C.c_uint32(ns), prm,
-                                               vp(rec)))
-            return rec
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
-            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
-        ni = instances.numel() * instances.element_size() // VIEW_INSTANCE_DTYPE.itemsize
-        for name, words in (("sets", sets), ("subjects", subjects)):
-            if words is not None and (words.numel() != ni or words.element_size() != 4 or not words.is_contiguous()):
-                raise ValueError(f"device {name}: a contiguous 32-bit tensor with one word per instance is expected")
-        rec = torch.empty(max(ns, 1) * SHAPE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
-        check(self._lib.dh_fit_shape_views_device(self._h, C.c_void_p(frames.data_ptr()), C.c_uint32(n_sets), w, h, views._h, model._h, basis._h,
-                                                  C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
-                                                  C.c_void_p(sets.data_ptr()) if sets is not None else None,
-                                                  C.c_void_p(subjects.data_ptr()) if subjects is not None else None, C.c_uint32(ns), prm,
-                                                  C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
-        return rec[:ns * SHAPE_RECORD_DTYPE.itemsize]
+        b = _Call(self, device_out, stream)
+        return b.call("dh_fit_shape_views", b.frames(frames), C.c_uint32(n_sets), w, h, views._h, model._h, basis._h,
+                      b.instances(instances, VIEW_INSTANCE_DTYPE), C.c_uint32(b.ni), b.inp("sets", sets, _U32, b.ni),
+                      b.inp("subjects", subjects, _U32, b.ni), C.c_uint32(ns), _lib.ref(params), b.out(SHAPE_RECORD_DTYPE, ns))
 
     def identify_subjects_views(self, frames, views, subjects_set, instances, sets=None, n_subjects=None, enrolled=None, fit_records=None,
                                 params=None, scores: bool = False, device_out: bool = False, stream=None):
@@ -608,46 +512,13 @@ class Fitter(_lib._Handle):
         n_sets, n, h, w = (int(v) for v in frames.shape)
         if n != len(views):
             raise ValueError(f"{n} frames a set for a view table of {len(views)} cameras")
-        prm = C.byref(params) if params is not None else None
         ns = len(subjects_set) if n_subjects is None else int(n_subjects)
-        if not device_out:
-            fr = np.ascontiguousarray(frames, dtype=np.uint16)
-            inst = np.ascontiguousarray(instances, dtype=VIEW_INSTANCE_DTYPE)
-            ni = len(inst)
-            st = None if sets is None else np.ascontiguousarray(sets, dtype=np.uint32).reshape(ni)
-            enr = None if enrolled is None else np.ascontiguousarray(np.asarray(enrolled) != 0, dtype=np.uint8).reshape(max(ns, 0))
-            frec = None if fit_records is None else np.ascontiguousarray(fit_records, dtype=VIEW_FIT_RECORD_DTYPE).reshape(ni)
-            sub, rec = np.full(ni, IDENT_UNKNOWN, np.uint32), np.zeros(ni, IDENT_RECORD_DTYPE)
-            poses, sc = np.zeros(ni, VIEW_INSTANCE_DTYPE), np.zeros((ni, max(ns, 0)), VIEW_FIT_RECORD_DTYPE)
-            check(self._lib.dh_fit_identify_subjects_views(self._h, vp(fr), C.c_uint32(n_sets), w, h, views._h, subjects_set._h,
-                                                           vp(inst) if ni else None, C.c_uint32(ni), vp(st), vp(enr), C.c_uint32(ns), vp(frec), prm,
-                                                           vp(sub), vp(rec), vp(poses), vp(sc) if scores else None))
-            return (sub, rec, poses, sc) if scores else (sub, rec, poses)
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
-            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
-        ni = instances.numel() * instances.element_size() // VIEW_INSTANCE_DTYPE.itemsize
-        if sets is not None and (sets.numel() != ni or sets.element_size() != 4 or not sets.is_contiguous()):
-            raise ValueError("device sets: a contiguous 32-bit tensor with one word per instance is expected")
-        if enrolled is not None and (enrolled.numel() != ns or enrolled.element_size() != 1 or not enrolled.is_contiguous()):
-            raise ValueError("device enrolled: a contiguous 8-bit tensor with one byte per subject is expected")
-        if fit_records is not None and (fit_records.numel() * fit_records.element_size() != ni * VIEW_FIT_RECORD_DTYPE.itemsize
-                                        or not fit_records.is_contiguous()):
-            raise ValueError("device fit_records: the contiguous tensor of one dh_view_fit_record per instance is expected")
-        sub = torch.empty(max(ni, 1), dtype=torch.int32, device=dev)
-        rec = torch.empty(max(ni, 1) * IDENT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        poses = torch.empty(max(ni, 1) * VIEW_INSTANCE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        sc = torch.empty(max(ni * ns, 1) * VIEW_FIT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev) if scores else None
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
-        check(self._lib.dh_fit_identify_subjects_views_device(
-            self._h, C.c_void_p(frames.data_ptr()), C.c_uint32(n_sets), w, h, views._h, subjects_set._h,
-            C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni), C.c_void_p(sets.data_ptr()) if sets is not None else None,
-            C.c_void_p(enrolled.data_ptr()) if enrolled is not None else None, C.c_uint32(ns),
-            C.c_void_p(fit_records.data_ptr()) if fit_records is not None else None, prm, C.c_void_p(sub.data_ptr()), C.c_void_p(rec.data_ptr()),
-            C.c_void_p(poses.data_ptr()), C.c_void_p(sc.data_ptr()) if scores else None, C.c_void_p(s)))
-        out = (sub[:ni], rec[:ni * IDENT_RECORD_DTYPE.itemsize], poses[:ni * VIEW_INSTANCE_DTYPE.itemsize])
-        return out + (sc[:ni * ns * VIEW_FIT_RECORD_DTYPE.itemsize],) if scores else out
+        b = _Call(self, device_out, stream)
+        return b.call("dh_fit_identify_subjects_views", b.frames(frames), C.c_uint32(n_sets), w, h, views._h, subjects_set._h,
+                      b.instances(instances, VIEW_INSTANCE_DTYPE), C.c_uint32(b.ni), b.inp("sets", sets, _U32, b.ni),
+                      b.inp("enrolled", enrolled, _U8, ns, per="subject", nonzero=True), C.c_uint32(ns),
+                      b.inp("fit_records", fit_records, VIEW_FIT_RECORD_DTYPE, b.ni), _lib.ref(params), b.out(_U32, b.ni, fill=IDENT_UNKNOWN),
+                      b.out(IDENT_RECORD_DTYPE, b.ni), b.out(VIEW_INSTANCE_DTYPE, b.ni), b.out(VIEW_FIT_RECORD_DTYPE, b.ni, ns, give=scores))
 
     def calibrate_step(self, frames, views, model, instances, sets=None, take=None, hold=None, params=None, device_out: bool = False,
                        stream=None):
@@ -662,36 +533,11 @@ class Fitter(_lib._Handle):
         n_sets, n, h, w = (int(v) for v in frames.shape)
         if n != len(views):
             raise ValueError(f"{n} frames a set for a view table of {len(views)} cameras")
-        prm = C.byref(params) if params is not None else None
-        if not device_out:
-            fr = np.ascontiguousarray(frames, dtype=np.uint16)
-            inst = np.ascontiguousarray(instances, dtype=VIEW_INSTANCE_DTYPE)
-            st = None if sets is None else np.ascontiguousarray(sets, dtype=np.uint32).reshape(len(inst))
-            tk = None if take is None else np.ascontiguousarray(take, dtype=np.uint32).reshape(len(inst))
-            hd = None if hold is None else np.ascontiguousarray(hold, dtype=np.uint8).reshape(n)
-            rec = np.zeros(n, CALIB_RECORD_DTYPE)
-            check(self._lib.dh_fit_calibrate_views(self._h, vp(fr), C.c_uint32(n_sets), w, h, views._h, model._h,
-                                                   vp(inst) if len(inst) else None, C.c_uint32(len(inst)), vp(st), vp(tk), vp(hd), prm, vp(rec)))
-            return rec
-        import torch
-        dev = torch.device("cuda", self.device)
-        if not frames.is_contiguous() or frames.element_size() != 2 or frames.device != dev:
-            raise ValueError("device frames: a contiguous 16-bit tensor on the fitter's device is expected")
-        ni = instances.numel() * instances.element_size() // VIEW_INSTANCE_DTYPE.itemsize
-        for name, words in (("sets", sets), ("take", take)):
-            if words is not None and (words.numel() != ni or words.element_size() != 4 or not words.is_contiguous()):
-                raise ValueError(f"device {name}: a contiguous 32-bit tensor with one word per instance is expected")
-        if hold is not None and (hold.numel() != n or hold.element_size() != 1 or not hold.is_contiguous()):
-            raise ValueError("device hold: a contiguous 8-bit tensor with one byte per camera is expected")
-        rec = torch.empty(n * CALIB_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
-        check(self._lib.dh_fit_calibrate_views_device(self._h, C.c_void_p(frames.data_ptr()), C.c_uint32(n_sets), w, h, views._h, model._h,
-                                                      C.c_void_p(instances.data_ptr()) if ni else None, C.c_uint32(ni),
-                                                      C.c_void_p(sets.data_ptr()) if sets is not None else None,
-                                                      C.c_void_p(take.data_ptr()) if take is not None else None,
-                                                      C.c_void_p(hold.data_ptr()) if hold is not None else None, prm,
-                                                      C.c_void_p(rec.data_ptr()), C.c_void_p(s)))
-        return rec
+        b = _Call(self, device_out, stream)
+        return b.call("dh_fit_calibrate_views", b.frames(frames), C.c_uint32(n_sets), w, h, views._h, model._h,
+                      b.instances(instances, VIEW_INSTANCE_DTYPE), C.c_uint32(b.ni), b.inp("sets", sets, _U32, b.ni),
+                      b.inp("take", take, _U32, b.ni), b.inp("hold", hold, _U8, n, per="camera"), _lib.ref(params),
+                      b.out(CALIB_RECORD_DTYPE, n, spare=0))
 
 
 def adapt(fitter, frames, K_or_cameras, verts, tris, basis, starts, rounds: int = 6, fit_prm=None, shape_prm=None, coeffs=None):
@@ -815,11 +661,9 @@ class Subjects(_lib._Handle):
             rec = np.ascontiguousarray(records, dtype=SHAPE_RECORD_DTYPE).reshape(self.n_subjects)
             check(self._lib.dh_fit_subjects_update(self._h, vp(rec)))
             return
-        import torch
         if records.numel() * records.element_size() != self.n_subjects * SHAPE_RECORD_DTYPE.itemsize or not records.is_contiguous():
             raise ValueError("device records: the contiguous tensor of one dh_shape_record per subject is expected")
-        s = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream if stream is None else int(stream)
-        check(self._lib.dh_fit_subjects_update_device(self._h, C.c_void_p(records.data_ptr()), C.c_void_p(s)))
+        check(self._lib.dh_fit_subjects_update_device(self._h, C.c_void_p(records.data_ptr()), C.c_void_p(_lib.stream_of(self.device, stream))))
 
 
 def adapt_subjects(fitter, frames, K_or_cameras, subjects, starts, subject_of, rounds: int = 6, fit_prm=None, shape_prm=None):
@@ -1044,16 +888,8 @@ def calibrate_views(fitter, frames, cameras, V, u, model, starts, sets=None, hol
 def fit_track_params(iterations_tracked=None, keep_points=None, rms_max=None, max_jump=None, conf=None, min_windows=None,
                      max_coast=None) -> "_lib.FitTrackParams":
     """dh_fit_track_params_default with the given fields replaced; `conf` is (conf_num, conf_den)."""
-    p = _lib.FitTrackParams()
-    check(_lib.load().dh_fit_track_params_default(C.byref(p)))
-    for name, v in (("iterations_tracked", iterations_tracked), ("keep_points", keep_points), ("min_windows", min_windows),
-                    ("max_coast", max_coast)):
-        if v is not None:
-            setattr(p, name, int(v))
-    if rms_max is not None:
-        p.rms_max = float(rms_max)
-    if max_jump is not None:
-        p.max_jump = float(max_jump)
+    p = _params(_lib.FitTrackParams, "dh_fit_track_params_default", iterations_tracked=iterations_tracked, keep_points=keep_points, rms_max=rms_max,
+                max_jump=max_jump, min_windows=min_windows, max_coast=max_coast)
     if conf is not None:
         p.conf_num, p.conf_den = int(conf[0]), int(conf[1])
     return p
@@ -1092,7 +928,7 @@ class FitTracker(_StepInputs, _lib._Handle):
         self.flags = FIT_TRACK_MOTION if motion else 0
         self._h = C.c_void_p()
         check(self._lib.dh_fit_tracker_create(cameras._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
-                                              C.byref(params) if params is not None else None, C.byref(self._h)))
+                                              _lib.ref(params), C.byref(self._h)))
 
     def step_poses(self, frames, poses, support, present=None, fit_params=None) -> np.ndarray:
         """The core step from the forest's POSE_DTYPE [n] and SUPPORT_DTYPE [n] of host frames [n, h, w] u16:
@@ -1102,7 +938,7 @@ class FitTracker(_StepInputs, _lib._Handle):
         support = np.ascontiguousarray(support, dtype=SUPPORT_DTYPE).reshape(self.n)
         rec = np.zeros(self.n, FIT_TRACK_RECORD_DTYPE)
         check(self._lib.dh_fit_tracker_step_poses(self._h, vp(frames), self.w, self.h, vp(pr), vp(poses), vp(support),
-                                                  C.byref(fit_params) if fit_params is not None else None, vp(rec)))
+                                                  _lib.ref(fit_params), vp(rec)))
         return rec
 
     def step(self, hp, frames, present=None, radius: int = SUPPORT_RADIUS, fit_params=None):
@@ -1112,7 +948,7 @@ class FitTracker(_StepInputs, _lib._Handle):
         poses, support = np.zeros(self.n, POSE_DTYPE), np.zeros(self.n, SUPPORT_DTYPE)
         rec = np.zeros(self.n, FIT_TRACK_RECORD_DTYPE)
         check(self._lib.dh_fit_tracker_step(hp._ph, self._h, vp(frames), self.w, self.h, vp(pr), C.c_uint32(int(radius) & 0xFFFFFFFF),
-                                            C.byref(fit_params) if fit_params is not None else None, vp(poses), vp(support), vp(rec)))
+                                            _lib.ref(fit_params), vp(poses), vp(support), vp(rec)))
         return poses, support, rec
 
     def step_device(self, frames_ptr: int, poses_ptr: int, support_ptr: int, records_ptr: int, hp=None, present_ptr: int = 0,
@@ -1120,7 +956,7 @@ class FitTracker(_StepInputs, _lib._Handle):
         """Device frames [n][h][w] u16, poses [n] dh_pose, support [n] dh_support, records [n] dh_fit_track_record, present [n]
         u8 or 0.  With `hp` the whole step (poses and support are outputs), without it the core step (they are inputs).
         Asynchronous on `stream`; allocates nothing and never waits on the host."""
-        prm = C.byref(fit_params) if fit_params is not None else None
+        prm = _lib.ref(fit_params)
         if hp is None:
             check(self._lib.dh_fit_tracker_step_poses_device(self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None), vp(poses_ptr),
                                                              vp(support_ptr), prm, vp(records_ptr), C.c_void_p(int(stream))))
@@ -1147,17 +983,8 @@ class FitTracker(_StepInputs, _lib._Handle):
 def rig_fit_track_params(iterations_tracked=None, keep_points=None, rms_max=None, max_jump=None, max_coast=None,
                          max_misses=None) -> "_lib.RigFitTrackParams":
     """dh_rig_fit_track_params_default with the given fields replaced; `max_misses` is the rig tracker's, which the ids come from."""
-    p = _lib.RigFitTrackParams()
-    check(_lib.load().dh_rig_fit_track_params_default(C.byref(p)))
-    for name, v in (("iterations_tracked", iterations_tracked), ("keep_points", keep_points), ("max_coast", max_coast),
-                    ("max_misses", max_misses)):
-        if v is not None:
-            setattr(p, name, int(v))
-    if rms_max is not None:
-        p.rms_max = float(rms_max)
-    if max_jump is not None:
-        p.max_jump = float(max_jump)
-    return p
+    return _params(_lib.RigFitTrackParams, "dh_rig_fit_track_params_default", iterations_tracked=iterations_tracked, keep_points=keep_points,
+                   rms_max=rms_max, max_jump=max_jump, max_coast=max_coast, max_misses=max_misses)
 
 
 class RigFitTracker(_StepInputs, _lib._Handle):
@@ -1175,7 +1002,7 @@ class RigFitTracker(_StepInputs, _lib._Handle):
         self.flags = FIT_TRACK_MOTION if motion else 0
         self._h = C.c_void_p()
         check(self._lib.dh_rig_fit_tracker_create(rig._h, views._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
-                                                  C.byref(params) if params is not None else None, C.byref(self._h)))
+                                                  _lib.ref(params), C.byref(self._h)))
 
     def step_persons(self, frames, n_heads, heads, n_persons, persons, present=None, fit_params=None) -> np.ndarray:
         """The core step from the outputs of a rig tracker step -- n_heads u32 [n_cams], HEAD_DTYPE [n_cams, max_heads], n_persons
@@ -1191,7 +1018,7 @@ class RigFitTracker(_StepInputs, _lib._Handle):
         rec = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_FIT_RECORD_DTYPE)
         check(self._lib.dh_rig_fit_tracker_step_persons(self._h, vp(frames), self.w, self.h, vp(pr), C.c_int(heads.shape[1]), vp(n_heads),
                                                         vp(heads), vp(n_persons), vp(persons),
-                                                        C.byref(fit_params) if fit_params is not None else None, vp(rec)))
+                                                        _lib.ref(fit_params), vp(rec)))
         return rec
 
     def step(self, rig_tracker, frames, present=None, tracks: bool = True, fit_params=None):
@@ -1206,7 +1033,7 @@ class RigFitTracker(_StepInputs, _lib._Handle):
         tr = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_TRACK_DTYPE) if tracks else None
         rec = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_FIT_RECORD_DTYPE)
         check(self._lib.dh_rig_fit_tracker_step(rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames), self.w, self.h, vp(pr),
-                                                C.byref(fit_params) if fit_params is not None else None, vp(n_heads), vp(heads), vp(ids),
+                                                _lib.ref(fit_params), vp(n_heads), vp(heads), vp(ids),
                                                 vp(n_persons), vp(persons), vp(tr), vp(rec)))
         return (n_heads, heads, ids, n_persons, persons, tr), rec
 
@@ -1218,7 +1045,7 @@ class RigFitTracker(_StepInputs, _lib._Handle):
         or 0.  With `rig_tracker` the whole step (heads and persons are outputs, as are rig_ids [n_cams][max_heads] u32 and, unless
         0, tracks; max_heads is the rig tracker's), without it the core step (they are inputs).  Asynchronous on `stream`;
         allocates nothing and never waits on the host."""
-        prm = C.byref(fit_params) if fit_params is not None else None
+        prm = _lib.ref(fit_params)
         if rig_tracker is None:
             check(self._lib.dh_rig_fit_tracker_step_persons_device(self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
                                                                    C.c_int(int(max_heads)), vp(n_heads_ptr), vp(heads_ptr), vp(n_persons_ptr),

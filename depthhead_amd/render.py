@@ -121,12 +121,7 @@ class Renderer(_lib._Handle):
         meshes = list(meshes)
         handles = (C.c_void_p * max(len(meshes), 1))(*[m._h.value for m in meshes])
         prm = _lib.RenderParams(int(noise), 0, float(holes), int(seed) & 0xFFFFFFFFFFFFFFFF, (C.c_uint64 * 2)(0, 0))
-        cams = getattr(K_or_cameras, "_h", None)
-        if cams is None:
-            K = np.ascontiguousarray(getattr(K_or_cameras, "mat", K_or_cameras), dtype=np.float32).reshape(9)
-            kind, karg = "", vp(K)
-        else:
-            kind, karg = "_cameras", cams
+        kind, karg = _lib.intrinsics(K_or_cameras)
         n, w, h = int(n), int(w), int(h)
         head = (self._h, handles, C.c_uint32(len(meshes)), vp(inst) if len(inst) else None, C.c_uint32(len(inst)), n, w, h, karg,
                 C.byref(prm))
@@ -143,9 +138,9 @@ class Renderer(_lib._Handle):
         if hasattr(torch, "uint16"):
             frames = frames.view(torch.uint16)
         mk = torch.empty(shape, dtype=torch.uint8, device=dev) if masks else None
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
         check(getattr(self._lib, "dh_render_depth" + kind + "_device")(*head, C.c_void_p(frames.data_ptr()),
-                                                                         C.c_void_p(mk.data_ptr()) if masks else None, C.c_void_p(s)))
+                                                                         C.c_void_p(mk.data_ptr()) if masks else None,
+                                                                         C.c_void_p(_lib.stream_of(self.device, stream))))
         return frames, mk
 
     def set_profiling(self, on: bool) -> None:

@@ -6,7 +6,9 @@ host staging grows in mid-sequence (one cropped frame first, two sets of three f
 call again at the end), every nullable input is an array in one call and None in its neighbour of the same kind (an array that
 changes the answer when it is read), and no size ends on a natural boundary (159 x 119 frames, 3 subjects, 5 and 7 instances).
 The scene is ident_views_scenes' gallery of the 162-vertex head seen by three 160x120 cameras; its middle camera serves the
-single-view kinds."""
+single-view kinds.  Before the last call the sequence runs the forms of the Python API that no other test drives (DESIGN.md section
+18c): the shape step and the shape step over a set through a camera table, and a fit through one from carried poses, each against
+its host form."""
 import contextlib
 import functools
 import time
@@ -54,7 +56,7 @@ def opened():
         got.set_coeffs(st.state["coeffs"][:, :len(B)])
         cams = stack.enter_context(Cameras(Ks))
         yield dict(basis=basis, set=got, views=stack.enter_context(fit.Views(cams, V, u)), model=stack.enter_context(fit.Model(st.pts[1], st.nrm[1])),
-                   coeffs=st.state["coeffs"][:, :len(B)])
+                   coeffs=st.state["coeffs"][:, :len(B)], twice=stack.enter_context(Cameras(np.stack([Ks[CAM], Ks[CAM]]))))
 
 
 @pytest.fixture(scope="module")
@@ -79,13 +81,20 @@ def d32(words):
 
 
 def run(f, g, kind, a, device=False):
-    """One call of `kind` with the arguments `a` on fitter f, in the host form or the _device form: the tuple of its outputs."""
+    """One call of `kind` with the arguments `a` on fitter f, in the host form or the _device form: the tuple of its outputs.  The
+    single-view kinds see through the middle camera's K or, with a["cameras"], through a table that holds it once per frame; with
+    a["carried"] the _device fit gets the instances as an earlier fit's tensor and, as its instances, the same 50 mm away: it equals
+    the host form only if it starts from the carried poses."""
     fr_ = d16(a["frames"]) if device else np.ascontiguousarray(a["frames"])
     words = d32 if device else (lambda x: x)
     rows = d8 if device else (lambda x: x)
-    K = scene()[4][CAM]
+    K = g["twice"] if a.get("cameras") else scene()[4][CAM]
     kw = dict(device_out=True) if device else {}
-    if kind == "fit":
+    if kind == "fit" and device and a.get("carried"):
+        away = a["inst"].copy()
+        away["t"] += np.float32(50.0)
+        out = f.fit(fr_, [g["model"]], away, K, carried=d8(a["inst"]), **kw)
+    elif kind == "fit":
         out = f.fit(fr_, [g["model"]], a["inst"], K, **kw)
     elif kind == "fit_views":
         out = f.fit_views(fr_, [g["model"]], a["inst"], g["views"], **kw)
@@ -154,6 +163,10 @@ def sequence():
         ("shape_views", dict(frames=rig2, inst=world[:5], n_subjects=1), False),
         ("calib", dict(frames=rig2, inst=world[:5], sets=sets[:5], take=take, hold=np.array([0, 1, 0], np.uint8)), True),
         ("calib", dict(frames=rig2, inst=world[:5]), False),
+        # the forms of the Python API that no other test runs: the _cameras twins of the shape steps, and of a carried fit, on the device
+        ("shape", dict(frames=two, inst=single[:5], subjects=subj, n_subjects=3, cameras=True), True),
+        ("shape_set", dict(frames=two, inst=single[:5], subjects=subj, n_subjects=3, fit_records=bad, cameras=True), True),
+        ("fit", dict(frames=two, inst=single[:5], cameras=True, carried=True), True),
         ("fit", dict(frames=one, inst=first), False),
     ]
 
