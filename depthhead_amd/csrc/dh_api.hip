@@ -4,61 +4,12 @@
 //
 // Sits where HoughPrediction::predict_parameter_generic sits in the reference
 // (src/hough/prediction.rs:421-493); the unit of work is a batch of frames.
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <atomic>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
-
-#include "dh_internal.h"
+//
+// This unit holds the predictor and the families that drive it or are still to be cut out; the trainer
+// and the renderer have units of their own (dh_api_train.hip, dh_api_render.hip) and share with this one what dh_runtime.h holds.
+#include "dh_runtime.h"
 #include "dh_render.h"
 #include "dh_fit.h"
-
-// ------------------------------------------------------------------ errors
-#define fail dh_fail_          // (dh_host.cpp: one message slot per host thread)
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? DH_ENOMEM : DH_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-#define TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)      // a DH_* call's failure returns at once
-// a failed HIP call as DH_EHIP, the message naming the step
-static int hip_step(hipError_t e, const char *what) { return e == hipSuccess ? DH_OK : fail(DH_EHIP, "%s: %s", what, hipGetErrorString(e)); }
-
-// ------------------------------------------------------------------ roctx ranges (tracing)
-// With profiling on (dh_set_profiling) every kernel launch of a batch sits inside a named roctx range on the host thread --
-// "dh:boxsum", "dh:traverse", "dh:emit", "dh:vote", "dh:cluster", and "dh:batch n=..." around them -- which rocprofv3
-// --marker-trace shows beside the kernel trace.  The marker library is looked up at run time (librocprofiler-sdk-roctx.so,
-// else libroctx64.so): the product library has no link-time dependency on a profiler, and without one the ranges are no-ops.
-#include <dlfcn.h>
-namespace {
-struct Roctx {
-    int (*push)(const char *) = nullptr;
-    int (*pop)() = nullptr;
-    Roctx() {
-        for (const char *name : {"librocprofiler-sdk-roctx.so.1", "librocprofiler-sdk-roctx.so", "libroctx64.so.4", "libroctx64.so"}) {
-            if (void *h = dlopen(name, RTLD_LAZY | RTLD_GLOBAL)) {
-                push = (int (*)(const char *))dlsym(h, "roctxRangePushA");
-                pop = (int (*)())dlsym(h, "roctxRangePop");
-                if (push && pop) return;
-                push = nullptr; pop = nullptr;
-            }
-        }
-    }
-};
-const Roctx &roctx() { static const Roctx r; return r; }      // (thread-safe initialisation; only ever touched with profiling on)
-struct Range {
-    bool on;
-    Range(bool enabled, const char *name) : on(enabled && roctx().push) { if (on) roctx().push(name); }
-    ~Range() { if (on) roctx().pop(); }
-};
-}   // namespace
 
 extern "C" const char *dh_last_error(void) { return dh_err_get_(); }
 extern "C" int dh_version(void) { return DH_VERSION; }
@@ -85,57 +36,6 @@ static int patch_grid_(const dh_params *p, int w, int h, int *nx, int *ny) {
     if (!p || !nx || !ny) return fail(DH_EINVAL, "dh_patch_grid: NULL argument");
     return dh_patch_grid_(*p, w, h, nx, ny);
 }
-
-// Entry points run on the predictor's device and leave the caller's current device as they found it.  A guard that cannot
-// select the device has set the error message: its owner returns DH_EHIP.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-        else prev = -1;
-        if (!ok) (void)fail(DH_EHIP, "cannot select device %d", dev);
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// ------------------------------------------------------------------ owned memory
-// One device (hipMalloc) or page-locked host (hipHostMalloc) allocation of cap() elements of T.  Move-only: the memory goes
-// with reset(), the next alloc(), an assignment and the destructor.  Every buffer of a predictor is one of these.
-enum Mem { DEVICE, PINNED };
-template <typename T, Mem M = DEVICE>
-class Buf {
-    T *ptr_ = nullptr;
-    size_t cap_ = 0;
-  public:
-    Buf() = default;
-    Buf(Buf &&o) noexcept : ptr_(o.ptr_), cap_(o.cap_) { o.ptr_ = nullptr; o.cap_ = 0; }
-    Buf &operator=(Buf &&o) noexcept {
-        if (this != &o) { reset(); ptr_ = o.ptr_; cap_ = o.cap_; o.ptr_ = nullptr; o.cap_ = 0; }
-        return *this;
-    }
-    ~Buf() { reset(); }
-    T *get() const { return ptr_; }
-    size_t cap() const { return cap_; }
-    explicit operator bool() const { return ptr_ != nullptr; }
-    void reset() {
-        if (ptr_) (void)(M == PINNED ? hipHostFree(ptr_) : hipFree(ptr_));
-        ptr_ = nullptr; cap_ = 0;
-    }
-    // The old memory is freed first.  At least one element is allocated: an empty buffer still has an address.
-    int alloc(size_t count) {
-        reset();
-        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-        void *q = nullptr;
-        hipError_t e = M == PINNED ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
-        if (e != hipSuccess) return fail(DH_ENOMEM, "%s(%zu bytes): %s", M == PINNED ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
-        ptr_ = (T *)q; cap_ = count;
-        return DH_OK;
-    }
-    // Staging that only ever grows: a quarter and 4 096 elements of headroom over `need`, the old contents dropped.
-    int grow(size_t need) { return need <= cap_ ? DH_OK : alloc(need + need / 4 + 4096); }
-};
 
 // ------------------------------------------------------------------ predictor
 #define DH_MAX_CHUNKS 8
@@ -598,16 +498,6 @@ static int predictor_reserve_(dh_predictor *p, int n, int w, int h) {
     if (!guard.ok) return DH_EHIP;
     return reserve(p, n, w, h);
 }
-
-// ------------------------------------------------------------------ camera tables (dh_cameras)
-// One record per camera on one device (DhCam), built once on the host: kinv by the same dh_mat3_inv_f32_ a single-K batch
-// uses, and the pinhole bit by the test dh_launch_vote applies to a single K.
-struct dh_cameras {
-    int device = 0;
-    int n = 0;
-    Buf<DhCam> dev;
-    std::vector<DhCam> host;     // the same records (kernel-argument stand-ins, the PIN decision of a launch)
-};
 
 // Which intrinsics a batch's frames see: one K for the whole batch (no table), or frame i -> camera c0 + i of a table.
 struct CamSel {
@@ -2233,569 +2123,6 @@ static int debug_votes_(dh_predictor *p, int frame, int which, int32_t *out, siz
         if (ncopy && out) HIP_TRY(hipMemcpy(out, ws.dbg_votes.get(), ncopy * 16, hipMemcpyDeviceToHost));
         return DH_OK;
     });
-}
-
-// ------------------------------------------------------------------ trainer (HoughLearning, prediction.rs:103-234)
-// The pool of samples lives on the device (rectangle-sum images, labels, truth) with a host copy of the truth, which the
-// host half of tree growing (dh_train.cpp) reads.  Calls are synchronous on the trainer's own stream.
-struct dh_trainer {
-    int device = 0;
-    dh_train_params p{};
-    TrainGeom g;                       // rectangle size and sample image size (frame-independent)
-    hipStream_t s = nullptr;
-    uint64_t frames = 0;
-    size_t pool = 0, cap = 0;
-    Buf<uint32_t> box;                 // [cap][bh][bw]
-    Buf<uint8_t> lab;
-    Buf<float> off;
-    Buf<double> rot;
-    std::vector<uint8_t> h_lab;
-    std::vector<float> h_off;
-    std::vector<double> h_rot;
-    uint64_t neg_det = 0;
-    std::vector<TrainLevelStat> stats;   // of the last fit
-};
-
-static int trainer_destroy_(dh_trainer *t) {
-    if (!t) return DH_OK;
-    DeviceGuard guard(t->device);
-    if (t->s) (void)hipStreamDestroy(t->s);
-    delete t;
-    return DH_OK;
-}
-
-static int trainer_create_(const dh_train_params *prm, int device, dh_trainer **out) {
-    if (!out) return fail(DH_EINVAL, "dh_trainer_create: NULL argument");
-    *out = nullptr;
-    TRY(dh_train_validate_(prm));
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(DH_EINVAL, "device %d out of range (%d visible)", device, ndev);
-    DeviceGuard guard(device);
-    if (!guard.ok) return DH_EHIP;
-    std::unique_ptr<dh_trainer> t(new dh_trainer);
-    t->device = device;
-    t->p = *prm;
-    TRY(dh_train_geom_(t->p, (int)prm->subimage_width, (int)prm->subimage_height, t->g));
-    TRY(hip_step(hipStreamCreateWithFlags(&t->s, hipStreamNonBlocking), "hipStreamCreate"));
-    *out = t.release();
-    return DH_OK;
-}
-
-// Capacity for `need` samples; the resident ones are kept.
-template <typename T>
-static int train_grow(Buf<T> &b, size_t old_elems, size_t new_elems, hipStream_t s) {
-    Buf<T> nb;
-    TRY(nb.alloc(new_elems));
-    if (old_elems) HIP_TRY(hipMemcpyAsync(nb.get(), b.get(), old_elems * sizeof(T), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    b = std::move(nb);
-    return DH_OK;
-}
-static int trainer_reserve(dh_trainer *t, size_t need) {
-    if (need <= t->cap) return DH_OK;
-    const size_t cap = std::max(need, t->cap * 2 + 1024), st = (size_t)t->g.bw * t->g.bh;
-    TRY(train_grow(t->box, t->pool * st, cap * st, t->s));
-    TRY(train_grow(t->lab, t->pool, cap, t->s));
-    TRY(train_grow(t->off, t->pool * 3, cap * 3, t->s));
-    TRY(train_grow(t->rot, t->pool * 3, cap * 3, t->s));
-    t->cap = cap;
-    return DH_OK;
-}
-
-static int trainer_add_frames_(dh_trainer *t, const uint16_t *frames, const uint8_t *masks, int n, int w, int h, const float *K,
-                               const float *pos3d, const float *rot_deg) {
-    if (!t) return fail(DH_EINVAL, "dh_trainer_add_frames: NULL trainer");
-    if (n < 0) return fail(DH_EINVAL, "negative frame count");
-    if (n == 0) return DH_OK;
-    if (!frames || !masks || !K || !pos3d || !rot_deg) return fail(DH_EINVAL, "dh_trainer_add_frames: NULL argument");
-    TrainGeom g;
-    TRY(dh_train_geom_(t->p, w, h, g));
-    TRY(dh_train_check_rotations_(rot_deg, n));
-    if ((uint64_t)g.nx * g.ny > 0xffffffffull) return fail(DH_ESIZE, "too many windows per frame");
-    DeviceGuard guard(t->device);
-    if (!guard.ok) return DH_EHIP;
-    const int chunk = std::min(n, dh_train_chunk_frames_(w, h));
-    const size_t px = (size_t)w * h, spx = (size_t)(w + 1) * (h + 1);
-    Buf<uint16_t> d_frames;
-    Buf<uint8_t> d_masks;
-    Buf<uint32_t> d_sat, d_sel, d_cnt;
-    Buf<float> d_kinv, d_pos, d_rot;
-    Buf<uint4> d_list;
-    TRY(d_frames.alloc(chunk * px));
-    TRY(d_masks.alloc(chunk * px));
-    TRY(d_sat.alloc(chunk * spx));
-    TRY(d_sel.alloc((size_t)chunk * 2 * DH_TRAIN_KEEP));
-    TRY(d_cnt.alloc((size_t)chunk * 2));
-    TRY(d_kinv.alloc((size_t)chunk * 9));
-    TRY(d_pos.alloc((size_t)chunk * 3));
-    TRY(d_rot.alloc((size_t)chunk * 3));
-    TRY(d_list.alloc((size_t)chunk * 2 * DH_TRAIN_KEEP));
-    std::vector<float> kinv((size_t)chunk * 9);
-    std::vector<uint32_t> sel((size_t)chunk * 2 * DH_TRAIN_KEEP), cnt((size_t)chunk * 2);
-    std::vector<uint4> list;
-    for (int c0 = 0; c0 < n; c0 += chunk) {
-        const int m = std::min(chunk, n - c0);
-        for (int i = 0; i < m; ++i) dh_mat3_inv_f32_(K + (size_t)(c0 + i) * 9, &kinv[(size_t)i * 9]);   // IntrinsicMatrix::inv (types.rs:436-441)
-        HIP_TRY(hipMemcpyAsync(d_frames.get(), frames + c0 * px, m * px * 2, hipMemcpyHostToDevice, t->s));
-        HIP_TRY(hipMemcpyAsync(d_masks.get(), masks + c0 * px, m * px, hipMemcpyHostToDevice, t->s));
-        HIP_TRY(hipMemcpyAsync(d_kinv.get(), kinv.data(), (size_t)m * 36, hipMemcpyHostToDevice, t->s));
-        HIP_TRY(hipMemcpyAsync(d_pos.get(), pos3d + (size_t)c0 * 3, (size_t)m * 12, hipMemcpyHostToDevice, t->s));
-        HIP_TRY(hipMemcpyAsync(d_rot.get(), rot_deg + (size_t)c0 * 3, (size_t)m * 12, hipMemcpyHostToDevice, t->s));
-        TrainWinArgs wa{};
-        wa.frames = d_frames.get(); wa.masks = d_masks.get(); wa.sat = d_sat.get();
-        wa.n = m; wa.w = w; wa.h = h;
-        wa.W = t->p.subimage_width; wa.H = t->p.subimage_height; wa.step = t->p.stepwidth;
-        wa.lw = g.lw; wa.lh = g.lh; wa.nx = g.nx; wa.ny = g.ny;
-        wa.seed = t->p.seed; wa.frame0 = t->frames;
-        wa.sel = d_sel.get(); wa.cnt = d_cnt.get();
-        TRY(hip_step(dh_launch_train_windows(wa, t->s), "k_train_select"));
-        HIP_TRY(hipMemcpyAsync(sel.data(), d_sel.get(), sel.size() * 4, hipMemcpyDeviceToHost, t->s));
-        HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt.get(), cnt.size() * 4, hipMemcpyDeviceToHost, t->s));
-        HIP_TRY(hipStreamSynchronize(t->s));
-        // pool order: frame after frame, each frame's negatives before its positives (prediction.rs:212-215)
-        list.clear();
-        for (int i = 0; i < m; ++i) {
-            const uint32_t k = cnt[(size_t)i * 2] + cnt[(size_t)i * 2 + 1];
-            for (uint32_t j = 0; j < k; ++j)
-                list.push_back(make_uint4((uint32_t)i, sel[(size_t)i * 2 * DH_TRAIN_KEEP + j], (uint32_t)(t->pool + list.size()), 0u));
-        }
-        TRY(trainer_reserve(t, t->pool + list.size()));
-        if (!list.empty()) {
-            HIP_TRY(hipMemcpyAsync(d_list.get(), list.data(), list.size() * sizeof(uint4), hipMemcpyHostToDevice, t->s));
-            TrainExtractArgs ea{};
-            ea.frames = d_frames.get(); ea.masks = d_masks.get(); ea.sat = d_sat.get();
-            ea.w = w; ea.h = h;
-            ea.W = wa.W; ea.H = wa.H; ea.step = wa.step; ea.lw = g.lw; ea.lh = g.lh; ea.nx = g.nx;
-            ea.rw = g.rw; ea.rh = g.rh; ea.bw = g.bw; ea.bh = g.bh;
-            ea.list = d_list.get(); ea.n_list = (uint32_t)list.size();
-            ea.kinv = d_kinv.get(); ea.pos3d = d_pos.get(); ea.rot_deg = d_rot.get();
-            ea.box = t->box.get(); ea.lab = t->lab.get(); ea.off = t->off.get(); ea.rot = t->rot.get();
-            TRY(hip_step(dh_launch_train_extract(ea, t->s), "k_train_extract"));
-            const size_t k = list.size(), b = t->pool;
-            t->h_lab.resize(b + k);
-            t->h_off.resize((b + k) * 3);
-            t->h_rot.resize((b + k) * 3);
-            HIP_TRY(hipMemcpyAsync(t->h_lab.data() + b, t->lab.get() + b, k, hipMemcpyDeviceToHost, t->s));
-            HIP_TRY(hipMemcpyAsync(t->h_off.data() + b * 3, t->off.get() + b * 3, k * 12, hipMemcpyDeviceToHost, t->s));
-            HIP_TRY(hipMemcpyAsync(t->h_rot.data() + b * 3, t->rot.get() + b * 3, k * 24, hipMemcpyDeviceToHost, t->s));
-            HIP_TRY(hipStreamSynchronize(t->s));
-            t->pool += k;
-        }
-        t->frames += (uint64_t)m;
-    }
-    return DH_OK;
-}
-
-// stamm's tree growing, breadth-first over every tree at once (PARITY UNPINNED): per level the host
-// applies early_stop, the device scores every (node, candidate) pair and picks each node's best split and the samples'
-// sides, the host partitions stably and records leaves.
-static int trainer_fit_(dh_trainer *t, dh_forest **out) {
-    if (!t || !out) return fail(DH_EINVAL, "dh_trainer_fit: NULL argument");
-    *out = nullptr;
-    if (t->pool == 0) return fail(DH_ESTATE, "dh_trainer_fit: no samples (add frames with a non-background window first)");
-    if ((uint64_t)t->p.n_trees * t->p.subset_per_tree > 0xffffffffull) return fail(DH_ESIZE, "n_trees * subset_per_tree above 2^32");
-    DeviceGuard guard(t->device);
-    if (!guard.ok) return DH_EHIP;
-    TrainGrower gr(t->p, t->h_lab.data(), t->h_off.data(), t->h_rot.data(), t->pool);
-    std::vector<uint32_t> idx, nidx;
-    std::vector<TrainNode> level, split, next;
-    std::vector<TrainBest> best;
-    std::vector<uint8_t> side;
-    gr.roots(idx, level);
-    Buf<uint32_t> d_idx;
-    Buf<TrainNode> d_nodes;
-    Buf<double> d_score;
-    Buf<TrainBest> d_best;
-    Buf<uint8_t> d_side;
-    Buf<unsigned long long> d_neg;
-    TRY(d_neg.alloc(1));
-    HIP_TRY(hipMemsetAsync(d_neg.get(), 0, 8, t->s));
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Ev { hipEvent_t *e; ~Ev() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_own{ev};
-    for (auto &e : ev) TRY(hip_step(hipEventCreate(&e), "hipEventCreate"));
-    const uint32_t F = t->p.features_per_node;
-    std::vector<float> ms;
-    uint32_t depth = 0;
-    for (;; ++depth) {
-        gr.stop_rules(depth, idx, level, split);
-        if (split.empty()) break;
-        const size_t m = split.size();
-        TRY(d_idx.grow(idx.size()));
-        TRY(d_nodes.grow(m));
-        TRY(d_score.grow(m * F));
-        TRY(d_best.grow(m));
-        TRY(d_side.grow(idx.size()));
-        HIP_TRY(hipMemcpyAsync(d_idx.get(), idx.data(), idx.size() * 4, hipMemcpyHostToDevice, t->s));
-        HIP_TRY(hipMemcpyAsync(d_nodes.get(), split.data(), m * sizeof(TrainNode), hipMemcpyHostToDevice, t->s));
-        TrainLevelArgs la{};
-        la.box = t->box.get(); la.stride = (size_t)t->g.bw * t->g.bh; la.bw = t->g.bw;
-        la.area = (double)t->g.rw * (double)t->g.rh;
-        la.lab = t->lab.get(); la.off = t->off.get(); la.rot = t->rot.get();
-        la.idx = d_idx.get(); la.nodes = d_nodes.get();
-        la.n_nodes = (uint32_t)m; la.F = F; la.cblocks = (F + 255) / 256;
-        la.seed = t->p.seed;
-        la.W = t->p.subimage_width; la.H = t->p.subimage_height; la.rw = t->g.rw; la.rh = t->g.rh;
-        la.scale = t->p.subrect_feature_scale;
-        la.wdepth = 1.0 - exp(-((double)depth / t->p.steepness));       // (1 - e^(-rel!(depth, steepness))), houghforest.rs:289-292
-        la.score = d_score.get(); la.best = d_best.get(); la.side = d_side.get(); la.neg_det = d_neg.get();
-        HIP_TRY(hipEventRecord(ev[0], t->s));
-        TRY(hip_step(dh_launch_train_level(la, t->s), "k_train_score"));
-        HIP_TRY(hipEventRecord(ev[1], t->s));
-        best.resize(m);
-        side.resize(idx.size());
-        HIP_TRY(hipMemcpyAsync(best.data(), d_best.get(), m * sizeof(TrainBest), hipMemcpyDeviceToHost, t->s));
-        HIP_TRY(hipMemcpyAsync(side.data(), d_side.get(), idx.size(), hipMemcpyDeviceToHost, t->s));
-        HIP_TRY(hipStreamSynchronize(t->s));
-        float e_ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&e_ms, ev[0], ev[1]));
-        ms.push_back(e_ms);
-        gr.apply(idx, split, best.data(), side.data(), nidx, next);
-        idx.swap(nidx);
-        level.swap(next);
-        if (level.empty()) break;
-    }
-    unsigned long long neg = 0;
-    HIP_TRY(hipMemcpyAsync(&neg, d_neg.get(), 8, hipMemcpyDeviceToHost, t->s));
-    HIP_TRY(hipStreamSynchronize(t->s));
-    TRY(gr.assemble(out));
-    t->neg_det = neg;
-    t->stats = gr.stats;
-    for (size_t i = 0; i < ms.size() && i < t->stats.size(); ++i) t->stats[i].ms = ms[i];
-    return DH_OK;
-}
-
-static int trainer_stats_(const dh_trainer *t, dh_train_stats *out, uint32_t *nodes, uint32_t *leaves, float *level_ms, uint32_t cap) {
-    if (!t || !out) return fail(DH_EINVAL, "dh_trainer_stats: NULL argument");
-    *out = dh_train_stats{};
-    out->frames = t->frames;
-    out->pool_size = t->pool;
-    for (uint8_t l : t->h_lab) out->pool_positives += l;
-    out->neg_det = t->neg_det;
-    out->levels = (uint32_t)t->stats.size();
-    for (uint32_t i = 0; i < cap; ++i) {
-        const bool have = i < t->stats.size();
-        if (nodes) nodes[i] = have ? t->stats[i].nodes : 0;
-        if (leaves) leaves[i] = have ? t->stats[i].leaves : 0;
-        if (level_ms) level_ms[i] = have ? t->stats[i].ms : 0.f;
-    }
-    return DH_OK;
-}
-
-static int forest_export_(const dh_forest *f, int32_t *roots, dh_node *nodes, double *leaf_prob, uint32_t *off_begin, uint32_t *rot_begin,
-                          float *offsets, double *rotations, uint32_t *n_off, uint32_t *n_rot) {
-    if (!f) return fail(DH_EINVAL, "dh_forest_export: NULL forest");
-    if (n_off) *n_off = (uint32_t)(f->offsets.size() / 3);
-    if (n_rot) *n_rot = (uint32_t)(f->rotations.size() / 3);
-    if (roots) std::copy(f->roots.begin(), f->roots.end(), roots);
-    if (nodes) std::copy(f->nodes.begin(), f->nodes.end(), nodes);
-    if (leaf_prob) std::copy(f->leaf_prob.begin(), f->leaf_prob.end(), leaf_prob);
-    if (off_begin) std::copy(f->off_begin.begin(), f->off_begin.end(), off_begin);
-    if (rot_begin) std::copy(f->rot_begin.begin(), f->rot_begin.end(), rot_begin);
-    if (offsets) std::copy(f->offsets.begin(), f->offsets.end(), offsets);
-    if (rotations) std::copy(f->rotations.begin(), f->rotations.end(), rotations);
-    return DH_OK;
-}
-
-// ------------------------------------------------------------------ rendering posed meshes
-// A mesh: vertices and index triples on one device, immutable.
-struct dh_mesh {
-    int device = 0;
-    uint32_t nv = 0, nt = 0;
-    float bbox[6] = {0, 0, 0, 0, 0, 0};
-    Buf<float> verts;
-    Buf<uint32_t> tris;
-};
-static int mesh_create_(const float *verts, uint32_t nv, const uint32_t *tris, uint32_t nt, int device, dh_mesh **out) {
-    if (!out) return fail(DH_EINVAL, "dh_mesh_create: NULL argument");
-    *out = nullptr;
-    if (!verts || !tris) return fail(DH_EINVAL, "dh_mesh_create: NULL argument");
-    if (nv == 0 || nt == 0) return fail(DH_EINVAL, "dh_mesh_create: %u vertices and %u triangles, expected at least one of each", nv, nt);
-    if (nt > 0x7fffffffu / 3 || nv > 0x7fffffffu / 3) return fail(DH_EINVAL, "dh_mesh_create: mesh too large");
-    std::unique_ptr<dh_mesh> m(new dh_mesh);
-    m->device = device; m->nv = nv; m->nt = nt;
-    for (int q = 0; q < 3; ++q) { m->bbox[q] = INFINITY; m->bbox[3 + q] = -INFINITY; }
-    for (size_t i = 0; i < (size_t)nv * 3; ++i) {
-        if (!std::isfinite(verts[i])) return fail(DH_EINVAL, "dh_mesh_create: vertex %zu is not finite", i / 3);
-        m->bbox[i % 3] = std::min(m->bbox[i % 3], verts[i]);
-        m->bbox[3 + i % 3] = std::max(m->bbox[3 + i % 3], verts[i]);
-    }
-    for (size_t i = 0; i < (size_t)nt * 3; ++i)
-        if (tris[i] >= nv) return fail(DH_EINVAL, "dh_mesh_create: triangle %zu names vertex %u of %u", i / 3, tris[i], nv);
-    DeviceGuard guard(device);
-    if (!guard.ok) return DH_EHIP;
-    TRY(m->verts.alloc((size_t)nv * 3));
-    TRY(m->tris.alloc((size_t)nt * 3));
-    HIP_TRY(hipMemcpy(m->verts.get(), verts, (size_t)nv * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->tris.get(), tris, (size_t)nt * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
-    *out = m.release();
-    return DH_OK;
-}
-static int mesh_destroy_(dh_mesh *m) {
-    if (!m) return DH_OK;
-    DeviceGuard guard(m->device);
-    delete m;
-    return DH_OK;
-}
-static int mesh_info_(const dh_mesh *m, uint32_t *nv, uint32_t *nt, float bbox[6]) {
-    if (!m) return fail(DH_EINVAL, "dh_mesh_info: NULL mesh");
-    if (nv) *nv = m->nv;
-    if (nt) *nt = m->nt;
-    if (bbox) memcpy(bbox, m->bbox, sizeof m->bbox);
-    return DH_OK;
-}
-
-// The refusals that a render, fit or shape call begins with: the frame count, the frame size (a fit tracker's step has that half
-// alone) and the batch's camera table or K.  `owner` ("renderer" / "fitter") is who runs the call, on `device`.
-static int check_frame_size(int w, int h, const char *who) {
-    if (w < 1 || h < 1 || w > DH_RENDER_MAX_SIZE || h > DH_RENDER_MAX_SIZE)
-        return fail(DH_EINVAL, "%s: frame size %dx%d, expected 1 .. %d each way", who, w, h, DH_RENDER_MAX_SIZE);
-    return DH_OK;
-}
-static int check_frames(int n, int w, int h, const float *K, const dh_cameras *cams, bool use_cams, int device, const char *owner, const char *who) {
-    if (n < 1 || n > 65535) return fail(DH_EINVAL, "%s: n = %d, expected 1 .. 65535 frames", who, n);
-    TRY(check_frame_size(w, h, who));
-    if (use_cams) {
-        if (!cams) return fail(DH_EINVAL, "%s: NULL camera table", who);
-        if (cams->device != device) return fail(DH_EINVAL, "%s: the camera table lives on device %d, the %s on %d", who, cams->device, owner, device);
-        if (cams->n != n) return fail(DH_EINVAL, "%s: the camera table holds %d cameras, the batch %d frames", who, cams->n, n);
-    } else if (!K) return fail(DH_EINVAL, "%s: NULL K", who);
-    return DH_OK;
-}
-
-// The tables of a call (a renderer's or a fitter's): filled in page-locked memory, one upload per call, and the stream of the
-// owner's host calls.  The stream and the events come with init(), at the owner's first call, after its arguments were checked.
-struct CallTables {
-    hipStream_t s = nullptr;                 // the host calls' stream
-    hipEvent_t ev_up = nullptr;              // the last call's upload has left the staging buffer
-    hipEvent_t ev_done = nullptr;            // the last call's kernels are through with the owner's memory
-    Buf<unsigned char, PINNED> stage;
-    Buf<unsigned char> dev;
-    ~CallTables() {
-        if (ev_up) (void)hipEventDestroy(ev_up);
-        if (ev_done) (void)hipEventDestroy(ev_done);
-        if (s) (void)hipStreamDestroy(s);
-    }
-    int init() {
-        if (s) return DH_OK;
-        TRY(hip_step(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate"));
-        TRY(hip_step(hipEventCreateWithFlags(&ev_up, hipEventDisableTiming), "hipEventCreate"));
-        TRY(hip_step(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming), "hipEventCreate"));
-        return DH_OK;
-    }
-    // `bytes` of staging, free to be filled
-    int reserve(size_t bytes) {
-        HIP_TRY(hipEventSynchronize(ev_up));         // (the staging buffer is free again; at once when nothing was recorded)
-        if (stage.cap() < bytes || dev.cap() < bytes) {
-            HIP_TRY(hipDeviceSynchronize());         // (an earlier call may still read the tables)
-            TRY(stage.grow(bytes));
-            TRY(dev.alloc(stage.cap()));
-        }
-        return DH_OK;
-    }
-    int upload(size_t bytes, hipStream_t st) {
-        HIP_TRY(hipStreamWaitEvent(st, ev_done, 0)); // (a call on another stream may still be using the tables and what they name)
-        HIP_TRY(hipMemcpyAsync(dev.get(), stage.get(), bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(ev_up, st));
-        return DH_OK;
-    }
-    int done(hipStream_t st) {
-        HIP_TRY(hipEventRecord(ev_done, st));
-        return DH_OK;
-    }
-};
-// The handle alone (dh_renderer, dh_fitter), and its end: a handle whose tables were set up has work that may still run.
-template <typename T>
-static int create_owner(int device, T **out, const char *who) {
-    if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
-    *out = nullptr;
-    if (device < 0) return fail(DH_EINVAL, "%s: device %d", who, device);
-    std::unique_ptr<T> o(new T);
-    o->device = device;
-    *out = o.release();
-    return DH_OK;
-}
-template <typename T>
-static int destroy_owner(T *o) {
-    if (!o) return DH_OK;
-    if (o->tab.s) {
-        DeviceGuard guard(o->device);
-        (void)hipDeviceSynchronize();
-        delete o;
-    } else delete o;
-    return DH_OK;
-}
-
-// A renderer: the call's tables, the triangle records, the tile counters and lists, and the device frames of the host calls.
-// Everything grows on demand and is kept between calls.
-struct dh_renderer {
-    int device = 0;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool profiling = false, timed = false;
-    Buf<unsigned long long, PINNED> total_h; // [2]
-    Buf<unsigned long long> total;           // [2]
-    Buf<RenderTri> tri;
-    Buf<uint32_t> tile_cnt, tile_cur, list;
-    Buf<uint16_t> frames;                    // host calls
-    Buf<uint8_t> masks;
-    CallTables tab;                          // tri_begin | meshes | instances (last: its stream and events go before any buffer)
-    ~dh_renderer() {
-        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-    }
-};
-static int renderer_destroy_(dh_renderer *r) { return destroy_owner(r); }
-static int renderer_create_(int device, dh_renderer **out) { return create_owner(device, out, "dh_renderer_create"); }
-// (the first buffers too come with the first render)
-static int renderer_init(dh_renderer *r) {
-    if (r->tab.s) return DH_OK;
-    TRY(r->tab.init());
-    for (auto &e : r->ev) TRY(hip_step(hipEventCreate(&e), "hipEventCreate"));
-    TRY(r->total.alloc(2));
-    TRY(r->total_h.alloc(2));
-    return DH_OK;
-}
-static int renderer_set_profiling_(dh_renderer *r, int on) {
-    if (!r) return fail(DH_EINVAL, "dh_renderer_set_profiling: NULL renderer");
-    r->profiling = on != 0;
-    return DH_OK;
-}
-static int renderer_timing_(dh_renderer *r, float ms[4]) {
-    if (!r || !ms) return fail(DH_EINVAL, "dh_renderer_timing: NULL argument");
-    if (!r->timed) return fail(DH_ESTATE, "dh_renderer_timing: no render has run with profiling on");
-    DeviceGuard guard(r->device);
-    if (!guard.ok) return DH_EHIP;
-    HIP_TRY(hipEventSynchronize(r->ev[4]));
-    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], r->ev[i], r->ev[i + 1]));
-    return DH_OK;
-}
-
-// One render call.  dev_out: frames / masks are device pointers and `stream` the caller's; else host pointers.
-struct RenderReq {
-    const dh_mesh *const *meshes; uint32_t n_meshes;
-    const dh_render_instance *inst; uint32_t n_inst;
-    int n, w, h;
-    const float *K; const dh_cameras *cams; bool use_cams;
-    const dh_render_params *prm;
-    uint16_t *frames; uint8_t *masks;
-};
-static int render_run(dh_renderer *r, const RenderReq &q, bool dev_out, hipStream_t stream, const char *who) {
-    // ---- refusals: all of them before anything is allocated or launched
-    if (!r) return fail(DH_EINVAL, "%s: NULL renderer", who);
-    if (!q.frames) return fail(DH_EINVAL, "%s: NULL frames", who);
-    TRY(check_frames(q.n, q.w, q.h, q.K, q.cams, q.use_cams, r->device, "renderer", who));
-    if (q.n_inst && !q.inst) return fail(DH_EINVAL, "%s: NULL instances", who);
-    if (q.n_inst && !q.meshes) return fail(DH_EINVAL, "%s: NULL meshes", who);
-    if (q.n_inst > 0x7fffffffu) return fail(DH_EINVAL, "%s: too many instances", who);
-    uint32_t noise = 0;
-    unsigned long long hole_thr = 0, seed = 0;
-    if (q.prm) {
-        const double p = q.prm->hole_probability;
-        if (!(p >= 0.0 && p <= 1.0)) return fail(DH_EINVAL, "%s: hole_probability %g outside [0, 1]", who, p);
-        if (q.prm->noise_amplitude > 65535u) return fail(DH_EINVAL, "%s: noise_amplitude %u above 65535", who, q.prm->noise_amplitude);
-        noise = q.prm->noise_amplitude; seed = q.prm->seed;
-        hole_thr = (unsigned long long)floor(p * 9007199254740992.0);
-    }
-    for (uint32_t i = 0; i < q.n_inst; ++i) {
-        if (q.inst[i].frame >= (uint32_t)q.n) return fail(DH_EINVAL, "%s: instance %u names frame %u of %d", who, i, q.inst[i].frame, q.n);
-        if (q.inst[i].mesh >= q.n_meshes) return fail(DH_EINVAL, "%s: instance %u names mesh %u of %u", who, i, q.inst[i].mesh, q.n_meshes);
-    }
-    for (uint32_t i = 0; i < q.n_meshes && q.n_inst; ++i) {
-        if (!q.meshes[i]) return fail(DH_EINVAL, "%s: mesh %u is NULL", who, i);
-        if (q.meshes[i]->device != r->device) return fail(DH_EINVAL, "%s: mesh %u lives on device %d, the renderer on %d", who, i, q.meshes[i]->device, r->device);
-    }
-    uint64_t n_tri = 0;
-    uint32_t max_nt = 0;
-    for (uint32_t i = 0; i < q.n_inst; ++i) {
-        n_tri += q.meshes[q.inst[i].mesh]->nt;
-        max_nt = std::max(max_nt, q.meshes[q.inst[i].mesh]->nt);
-    }
-    if (n_tri > 0x7fffffffull) return fail(DH_ESIZE, "%s: %llu triangles in one call (limit 2^31 - 1)", who, (unsigned long long)n_tri);
-
-    DeviceGuard guard(r->device);
-    if (!guard.ok) return DH_EHIP;
-    TRY(renderer_init(r));
-    hipStream_t s = dev_out ? stream : r->tab.s;
-    RenderArgs a;
-    memset(&a, 0, sizeof a);
-    a.n = q.n; a.w = q.w; a.h = q.h;
-    a.tiles_x = (q.w + DH_RT_W - 1) / DH_RT_W; a.tiles_y = (q.h + DH_RT_H - 1) / DH_RT_H;
-    const size_t n_tiles = (size_t)q.n * a.tiles_x * a.tiles_y, n_px = (size_t)q.n * q.w * q.h;
-    if (n_tiles > 0x7fffffffull) return fail(DH_ESIZE, "%s: %zu screen tiles in one call (limit 2^31 - 1)", who, n_tiles);
-    a.n_inst = q.n_inst; a.max_nt = max_nt; a.n_tri = (uint32_t)n_tri;
-    if (q.use_cams) a.cams = q.cams->dev.get();
-    else memcpy(a.k, q.K, sizeof a.k);
-    a.noise = noise; a.hole_thr = hole_thr; a.seed = seed;
-    // ---- the call's tables: one staging buffer, one upload
-    const size_t o_mesh = (((size_t)q.n_inst + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
-    const size_t o_inst = o_mesh + (((size_t)q.n_meshes * sizeof(RenderMesh) + 15) & ~(size_t)15);
-    const size_t bytes = o_inst + (size_t)q.n_inst * sizeof(dh_render_instance);
-    TRY(r->tab.reserve(bytes));
-    {
-        uint32_t *tb = (uint32_t *)r->tab.stage.get();
-        RenderMesh *mm = (RenderMesh *)(r->tab.stage.get() + o_mesh);
-        uint32_t acc = 0;
-        for (uint32_t i = 0; i < q.n_inst; ++i) { tb[i] = acc; acc += q.meshes[q.inst[i].mesh]->nt; }
-        tb[q.n_inst] = acc;
-        for (uint32_t i = 0; i < q.n_meshes && q.n_inst; ++i) mm[i] = RenderMesh{q.meshes[i]->verts.get(), q.meshes[i]->tris.get(), q.meshes[i]->nv, q.meshes[i]->nt};
-        if (q.n_inst) memcpy(r->tab.stage.get() + o_inst, q.inst, (size_t)q.n_inst * sizeof(dh_render_instance));
-    }
-    a.tri_begin = (const uint32_t *)r->tab.dev.get();
-    a.meshes = (const RenderMesh *)(r->tab.dev.get() + o_mesh);
-    a.inst = (const dh_render_instance *)(r->tab.dev.get() + o_inst);
-    // ---- renderer-owned memory (growing waits for whatever still uses the old)
-    if (r->tri.cap() < n_tri || r->tile_cnt.cap() < n_tiles) HIP_TRY(hipDeviceSynchronize());
-    TRY(r->tri.grow((size_t)n_tri));
-    if (r->tile_cnt.cap() < n_tiles) { TRY(r->tile_cnt.grow(n_tiles)); TRY(r->tile_cur.alloc(r->tile_cnt.cap())); }
-    if (!dev_out) {
-        if (r->frames.cap() < n_px) { HIP_TRY(hipDeviceSynchronize()); TRY(r->frames.grow(n_px)); TRY(r->masks.alloc(r->frames.cap())); }
-        a.frames = r->frames.get(); a.masks = q.masks ? r->masks.get() : nullptr;
-    } else { a.frames = q.frames; a.masks = q.masks; }
-    a.vec = q.w % 8 == 0 && (uintptr_t)a.frames % 16 == 0 && (uintptr_t)a.masks % 8 == 0 ? 1 : 0;
-    a.tri = r->tri.get(); a.tile_cnt = r->tile_cnt.get(); a.tile_cur = r->tile_cur.get(); a.total = r->total.get();
-    const bool prof = r->profiling;
-    Range range(prof, "dh:render");
-    TRY(r->tab.upload(bytes, s));                       // (waits for a call on another stream that still uses the records and lists)
-    HIP_TRY(hipMemsetAsync(a.tile_cnt, 0, n_tiles * sizeof(uint32_t), s));
-    HIP_TRY(hipMemsetAsync(a.total, 0, 2 * sizeof(unsigned long long), s));
-    if (prof) HIP_TRY(hipEventRecord(r->ev[0], s));
-    TRY(hip_step(dh_launch_render_setup(a, s), "k_render_setup"));
-    if (prof) HIP_TRY(hipEventRecord(r->ev[1], s));
-    // the size of the tile lists: the one point where the host waits
-    HIP_TRY(hipMemcpyAsync(r->total_h.get(), a.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const unsigned long long refs = r->total_h.get()[0];
-    if (refs > 0xffffffffull) return fail(DH_ESIZE, "%s: the tile lists need %llu entries (limit 2^32 - 1)", who, refs);
-    TRY(r->list.grow((size_t)refs));
-    a.list = r->list.get(); a.list_cap = r->list.cap();
-    TRY(hip_step(dh_launch_render_offsets(a, s), "k_render_offsets"));
-    if (prof) HIP_TRY(hipEventRecord(r->ev[2], s));
-    TRY(hip_step(dh_launch_render_fill(a, s), "k_render_fill"));
-    if (prof) HIP_TRY(hipEventRecord(r->ev[3], s));
-    TRY(hip_step(dh_launch_render_resolve(a, s), "k_render_resolve"));
-    if (prof) { HIP_TRY(hipEventRecord(r->ev[4], s)); r->timed = true; }
-    TRY(r->tab.done(s));
-    if (!dev_out) {
-        HIP_TRY(hipMemcpyAsync(q.frames, a.frames, n_px * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
-        if (q.masks) HIP_TRY(hipMemcpyAsync(q.masks, a.masks, n_px, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return DH_OK;
-}
-static int render_depth_(dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances,
-                         int n, int w, int h, const float K[9], const dh_render_params *params, uint16_t *frames, uint8_t *masks) {
-    return render_run(r, RenderReq{meshes, n_meshes, instances, n_instances, n, w, h, K, nullptr, false, params, frames, masks}, false, nullptr, "dh_render_depth");
-}
-static int render_depth_cameras_(dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances,
-                                 int n, int w, int h, const dh_cameras *c, const dh_render_params *params, uint16_t *frames, uint8_t *masks) {
-    return render_run(r, RenderReq{meshes, n_meshes, instances, n_instances, n, w, h, nullptr, c, true, params, frames, masks}, false, nullptr, "dh_render_depth_cameras");
-}
-static int render_depth_device_(dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances,
-                                int n, int w, int h, const float K[9], const dh_render_params *params, uint16_t *frames, uint8_t *masks, void *stream) {
-    return render_run(r, RenderReq{meshes, n_meshes, instances, n_instances, n, w, h, K, nullptr, false, params, frames, masks}, true, (hipStream_t)stream, "dh_render_depth_device");
-}
-static int render_depth_cameras_device_(dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances,
-                                        int n, int w, int h, const dh_cameras *c, const dh_render_params *params, uint16_t *frames, uint8_t *masks, void *stream) {
-    return render_run(r, RenderReq{meshes, n_meshes, instances, n_instances, n, w, h, nullptr, c, true, params, frames, masks}, true, (hipStream_t)stream, "dh_render_depth_cameras_device");
 }
 
 // ------------------------------------------------------------------ fitting posed models to depth frames
@@ -4748,11 +4075,7 @@ static int rig_fit_tracker_step_(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_
     return rig_fit_host(p, t, rt, frames, w, h, present, rt->prm.max_heads, prm, n_heads, heads, ids, n_persons, persons, tracks, records);
 }
 
-// ------------------------------------------------------------------ the C ABI
-// Every entry point of include/depthhead_hip.h runs its body (the *_ functions above) inside dh_guard_: the header promises
-// that nothing throws or aborts across the boundary, and the bodies allocate (std::vector, std::string, std::thread).
-#define DH_API(name, params, args) \
-    extern "C" int dh_##name params { return dh_guard_("dh_" #name, [&]() -> int { return name##_ args; }); }
+// ------------------------------------------------------------------ the C ABI (DH_API: dh_runtime.h)
 DH_API(forest_create, (const dh_forest_desc *d, dh_forest **out), (d, out))
 DH_API(forest_destroy, (dh_forest *f), (f))
 DH_API(forest_info, (const dh_forest *f, uint32_t *n_trees, uint32_t *n_nodes, uint32_t *n_leaves, uint32_t *max_depth), (f, n_trees, n_nodes, n_leaves, max_depth))
@@ -4792,12 +4115,6 @@ DH_API(debug_tile_shifts, (dh_predictor *p, int32_t *shifts, uint32_t counts[8])
 DH_API(debug_guesses, (dh_predictor *p, int32_t *out), (p, out))
 DH_API(debug_meanshift, (dh_predictor *p, int which, int32_t *trace, uint32_t *steps), (p, which, trace, steps))
 DH_API(debug_votes, (dh_predictor *p, int frame, int which, int32_t *out, size_t cap, size_t *count), (p, frame, which, out, cap, count))
-DH_API(trainer_create, (const dh_train_params *p, int device, dh_trainer **out), (p, device, out))
-DH_API(trainer_destroy, (dh_trainer *t), (t))
-DH_API(trainer_add_frames, (dh_trainer *t, const uint16_t *frames, const uint8_t *masks, int n, int w, int h, const float *K, const float *pos3d, const float *rot_deg), (t, frames, masks, n, w, h, K, pos3d, rot_deg))
-DH_API(trainer_fit, (dh_trainer *t, dh_forest **out), (t, out))
-DH_API(trainer_stats, (const dh_trainer *t, dh_train_stats *out, uint32_t *nodes_per_level, uint32_t *leaves_per_level, float *level_ms, uint32_t cap_levels), (t, out, nodes_per_level, leaves_per_level, level_ms, cap_levels))
-DH_API(forest_export, (const dh_forest *f, int32_t *roots, dh_node *nodes, double *leaf_prob, uint32_t *off_begin, uint32_t *rot_begin, float *offsets, double *rotations, uint32_t *n_off, uint32_t *n_rot), (f, roots, nodes, leaf_prob, off_begin, rot_begin, offsets, rotations, n_off, n_rot))
 DH_API(cameras_create, (const float *K, int n, int device, dh_cameras **out), (K, n, device, out))
 DH_API(cameras_destroy, (dh_cameras *c), (c))
 DH_API(predict_batch_cameras, (dh_predictor *p, const uint16_t *frames, int n, int w, int h, const dh_cameras *c, const float *midp_guess, const double *rot_guess, const uint8_t *guess_mask, dh_pose *out), (p, frames, n, w, h, c, midp_guess, rot_guess, guess_mask, out))
@@ -4835,17 +4152,6 @@ DH_API(rig_tracker_step, (dh_predictor *p, dh_rig_tracker *t, const uint16_t *fr
 DH_API(rig_tracker_step_device, (dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, void *stream), (p, t, frames, w, h, present, n_heads, heads, rig_ids, n_persons, persons, tracks, stream))
 DH_API(rig_tracker_state, (dh_rig_tracker *t, dh_rig_track *tracks, uint32_t *next_id), (t, tracks, next_id))
 DH_API(rig_tracker_capture, (dh_predictor *p, dh_rig_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks), (p, t, frames, w, h, present, n_heads, heads, rig_ids, n_persons, persons, tracks))
-DH_API(mesh_create, (const float *verts, uint32_t nv, const uint32_t *tris, uint32_t nt, int device, dh_mesh **out), (verts, nv, tris, nt, device, out))
-DH_API(mesh_destroy, (dh_mesh *m), (m))
-DH_API(mesh_info, (const dh_mesh *m, uint32_t *nv, uint32_t *nt, float bbox[6]), (m, nv, nt, bbox))
-DH_API(renderer_create, (int device, dh_renderer **out), (device, out))
-DH_API(renderer_destroy, (dh_renderer *r), (r))
-DH_API(renderer_set_profiling, (dh_renderer *r, int on), (r, on))
-DH_API(renderer_timing, (dh_renderer *r, float ms[4]), (r, ms))
-DH_API(render_depth, (dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances, int n, int w, int h, const float K[9], const dh_render_params *params, uint16_t *frames, uint8_t *masks), (r, meshes, n_meshes, instances, n_instances, n, w, h, K, params, frames, masks))
-DH_API(render_depth_cameras, (dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances, int n, int w, int h, const dh_cameras *c, const dh_render_params *params, uint16_t *frames, uint8_t *masks), (r, meshes, n_meshes, instances, n_instances, n, w, h, c, params, frames, masks))
-DH_API(render_depth_device, (dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances, int n, int w, int h, const float K[9], const dh_render_params *params, uint16_t *frames, uint8_t *masks, void *stream), (r, meshes, n_meshes, instances, n_instances, n, w, h, K, params, frames, masks, stream))
-DH_API(render_depth_cameras_device, (dh_renderer *r, const dh_mesh *const *meshes, uint32_t n_meshes, const dh_render_instance *instances, uint32_t n_instances, int n, int w, int h, const dh_cameras *c, const dh_render_params *params, uint16_t *frames, uint8_t *masks, void *stream), (r, meshes, n_meshes, instances, n_instances, n, w, h, c, params, frames, masks, stream))
 DH_API(fit_model_create, (const float *points, const float *normals, uint32_t n, int device, dh_fit_model **out), (points, normals, n, device, out))
 DH_API(fit_model_destroy, (dh_fit_model *m), (m))
 DH_API(fit_model_info, (const dh_fit_model *m, uint32_t *n, double *radius), (m, n, radius))
@@ -4924,4 +4230,3 @@ DH_API(rig_fit_tracker_step_persons, (dh_rig_fit_tracker *t, const uint16_t *fra
 DH_API(rig_fit_tracker_step_persons_device, (dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_fit_record *records, void *stream), (t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, fit_params, records, stream))
 DH_API(rig_fit_tracker_step, (dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records), (p, t, rt, frames, w, h, present, fit_params, n_heads, heads, rig_ids, n_persons, persons, tracks, records))
 DH_API(rig_fit_tracker_step_device, (dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records, void *stream), (p, t, rt, frames, w, h, present, fit_params, n_heads, heads, rig_ids, n_persons, persons, tracks, records, stream))
-#undef DH_API

@@ -4,7 +4,7 @@
 //
 // No HIP type or call appears here: dh_host.cpp and dh_biwi.cpp build with plain g++ as well as with hipcc, which is
 // what puts them under AddressSanitizer / UBSan / ThreadSanitizer on the CPU (tests/host/, tests/test_host_sanitize.py;
-// GPU sanitizers are unavailable on the pool).  dh_api.hip is the only caller in the product library.  Not part of the ABI.
+// GPU sanitizers are unavailable on the pool).  The runtime units (dh_api*.hip) are the only callers in the product library.  Not part of the ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// dh_internal.h -- structures shared by the host runtime (dh_api.hip) and the gfx950 kernels
+// dh_internal.h -- structures shared by the host runtime (dh_api*.hip) and the gfx950 kernels
 // (k_*.hip): kernel argument blocks, device views of the forest, record layouts, launchers.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // dh_render.h -- the renderer's kernel argument block, record layouts and launchers (k_render.hip), shared with the host
-// runtime (dh_api.hip).  Not part of the ABI.  The rule the kernels implement is stated in include/depthhead_hip.h (section
+// runtime (dh_api_render.hip).  Not part of the ABI.  The rule the kernels implement is stated in include/depthhead_hip.h (section
 // "rendering posed meshes") and DESIGN.md section 17.
 #pragma once
 #include "dh_internal.h"

@@ -1,7 +1,7 @@
 // dh_train.h -- the host-only half of the trainer behind dh_trainer_* (include/depthhead_hip.h): parameter validation,
 // the keyed random draws, the window grid, the upload chunk plan, and the level-by-level bookkeeping of tree growing
 // (early_stop, comp_leaf_data, stable partitions, assembly of the forest in CSR form).  The device half (window pass,
-// rectangle-sum images, split search) is k_train.hip; dh_api.hip sequences the two.
+// rectangle-sum images, split search) is k_train.hip; dh_api_train.hip sequences the two.
 //
 // Like dh_host.h, no HIP call appears in dh_train.cpp: it builds with plain g++ under AddressSanitizer / UBSan /
 // ThreadSanitizer (tests/host/train_check.cpp).  The draws below are also compiled for the device (DH_HD).

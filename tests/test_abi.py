@@ -10,6 +10,7 @@ import pytest
 
 from depthhead_amd import synth, _lib
 from depthhead_amd.forest import Forest, NODE_DTYPE
+import runtime_units
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "depthhead_hip.h")
 
@@ -233,16 +234,17 @@ def test_cpp_example_compiles_and_links(tmp_path):
 
 def test_every_entry_point_runs_inside_the_exception_guard():
     """include/depthhead_hip.h: "never throws or aborts across the boundary".  Every `extern "C" int dh_*` definition of the
-    library is either generated by the DH_API macro (dh_api.hip: body inside dh_guard_) or calls dh_guard_ itself (dh_biwi.cpp);
-    the only unguarded definitions are the two that cannot throw (dh_version, dh_last_error)."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    csrc = os.path.join(root, "depthhead_amd", "csrc")
-    api = open(os.path.join(csrc, "dh_api.hip")).read()
-    guarded = set("dh_" + m for m in re.findall(r"^DH_API\((\w+),", api, flags=re.M))
-    assert "dh_guard_(" in api[api.index("#define DH_API"):api.index("#define DH_API") + 300]
-    raw = set(re.findall(r'extern "C" (?:int|const char \*)\s*(dh_\w+)\(', api))
-    assert raw <= {"dh_version", "dh_last_error"}, raw
-    biwi = open(os.path.join(csrc, "dh_biwi.cpp")).read()
+    library is either generated by the DH_API macro (dh_runtime.h: body inside dh_guard_) or calls dh_guard_ itself (dh_biwi.cpp);
+    the only unguarded definitions, in every unit of the runtime, are the two that cannot throw (dh_version, dh_last_error)."""
+    assert "dh_api.hip" in runtime_units.UNITS and "dh_runtime.h" in runtime_units.HEADERS
+    guarded = runtime_units.guarded()
+    macros = runtime_units.api_macros()
+    assert set(macros) == {"DH_API"}, macros
+    assert 'extern "C" int dh_##name' in macros["DH_API"] and "dh_guard_(" in macros["DH_API"]
+    for name, src in {**runtime_units.units(), **runtime_units.headers()}.items():
+        raw = runtime_units.raw_definitions(src)
+        assert raw <= {"dh_version", "dh_last_error"}, (name, raw)
+    biwi = runtime_units.read("dh_biwi.cpp")
     for name, body in re.findall(r'extern "C" int (dh_\w+)\([^)]*\) \{(.*?)\n\}', biwi, flags=re.S):
         assert "dh_guard_(" in body, name
         guarded.add(name)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from depthhead_amd import _lib
+import runtime_units
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_fit_ident_params_default", "dh_fit_identify_subjects", "dh_fit_identify_subjects_cameras", "dh_fit_identify_subjects_device",
@@ -63,7 +64,7 @@ def test_header_and_exports_are_equal():
     declared = set(re.findall(r"^(?:int|const char \*)\s*(dh_\w+)\(", text, re.M))
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     assert len(_lib.EXPORTS) == len(set(_lib.EXPORTS))
-    api = open(os.path.join(ROOT, "depthhead_amd", "csrc", "dh_api.hip")).read()
+    api = runtime_units.text()
     for n in NEW:
         assert f"DH_API({n[3:]}," in api, n                                         # through the guard, as every export
 

@@ -12,6 +12,7 @@ import re
 import numpy as np
 
 from depthhead_amd import _lib
+import runtime_units
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_fit_ident_views_params_default", "dh_fit_identify_subjects_views", "dh_fit_identify_subjects_views_device"]
@@ -39,7 +40,7 @@ def test_header_and_exports_are_equal():
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     assert len(_lib.EXPORTS) == len(set(_lib.EXPORTS))
     assert "identifying enrolled subjects across the views of a rig" in text and "MUST BE STREAM-ORDERED" in text
-    api = open(os.path.join(ROOT, "depthhead_amd", "csrc", "dh_api.hip")).read()
+    api = runtime_units.text()
     for n in NEW:
         assert f"DH_API({n[3:]}," in api, n                                         # through the guard, as every export
 
