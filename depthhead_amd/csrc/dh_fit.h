@@ -1,5 +1,5 @@
 // dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip,
-// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip, k_ident.hip, k_ident_views.hip) share with the host runtime (dh_api.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
+// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip, k_ident.hip, k_ident_views.hip) share with the host runtime (dh_api_fit.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
 // words of both trackers, and the one test of whether an instance may be fitted (dh_fit_instance_fault: the host's refusals and
 // the shape kernel's skips).  The device arithmetic the kernels share among themselves is in dh_fit_device.h.  Not part of the
 // ABI.  The rules are stated in include/depthhead_hip.h (sections "fitting posed models to depth frames" and after) and
@@ -59,7 +59,7 @@ hipError_t dh_launch_fit(const FitArgs &a, hipStream_t s);
 // Why an instance may not be fitted: the per-instance refusals of the header in their order, stated once for the host loops
 // (which turn the answer into their messages) and the shape kernel (which skips).  The magnitude bounds of the int64 sums, here
 // and at DH_SHAPE_*, rest on it.  radius: the model's largest |v|; largest: the basis's largest |B_k[i]| (0.0 where there is none).
-// (instance_model_refusal, dh_api.hip, relies on the order of these values: it reports what comes before EXTENT, then the model's
+// (instance_model_refusal, dh_api_fit.hip, relies on the order of these values: it reports what comes before EXTENT, then the model's
 // own refusals, then the rest)
 enum { DH_FIT_INST_OK = 0, DH_FIT_INST_NOT_FINITE, DH_FIT_INST_NOT_ORTHONORMAL, DH_FIT_INST_EXTENT, DH_FIT_INST_FIELD };
 struct FitInstanceFault {

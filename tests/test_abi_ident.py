@@ -109,7 +109,7 @@ def test_the_defaults(hip_lib):
 
 
 def stand_in_set(n_subjects=3, device=0):
-    """256 bytes that read as a dh_fit_subjects of 642 points and n_subjects subjects on `device` with no memory (dh_api.hip: int
+    """256 bytes that read as a dh_fit_subjects of 642 points and n_subjects subjects on `device` with no memory (dh_api_fit.hip: int
     device; uint32 n, n_tris, n_subjects; ...) -- for the refusals that come before the set's models and basis are read."""
     block = np.zeros(256, np.uint8)
     block[0:4].view(np.int32)[:] = device

@@ -1,7 +1,7 @@
 """The multi-view identification entry points without a GPU: exported and declared, the argument lists of the
 two forms, the two defaults, and every refusal that is decided before a device is touched, in the header's order with every later
 one provoked as well, answering DH_EINVAL with a message that names the call and leaving the four outputs untouched.  Handles live
-on a device, so the calls get blocks that read as one (dh_api.hip): a view table of two words and a pointer to its camera table
+on a device, so the calls get blocks that read as one (dh_api_fit.hip): a view table of two words and a pointer to its camera table
 (device, n), and a subject set (device; n, n_tris, n_subjects; max_coeff, radius; its basis: device; n, k; largest) whose device
 memory is never touched -- every refusal made here comes before the set's models are read.  What needs a real set and a real rig
 is in tests/test_gpu_ident_views.py."""

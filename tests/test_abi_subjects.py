@@ -89,7 +89,7 @@ TETRA_T = np.array([(0, 2, 1), (0, 1, 3), (0, 3, 2), (1, 2, 3)], np.uint32)
 
 def test_create_refusals_in_their_order(hip_lib):
     lib, vp = hip_lib, _lib.vp
-    # a basis handle that is not NULL: 0 points on device 0.  (dh_api.hip pins sizeof(dh_fit_basis) <= 256 with a static_assert, so
+    # a basis handle that is not NULL: 0 points on device 0.  (dh_api_fit.hip pins sizeof(dh_fit_basis) <= 256 with a static_assert, so
     # the library never reads past this block; its device memory is never touched before the call has ended)
     zeros = np.zeros(256, np.uint8)
 

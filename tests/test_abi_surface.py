@@ -104,7 +104,7 @@ TETRA_T = np.array([(0, 2, 1), (0, 1, 3), (0, 3, 2), (1, 2, 3)], np.uint32)
 
 
 def stand_in_basis(n, k=1):
-    """256 bytes that read as a dh_fit_basis of n points and k fields on device 0 with largest 0 and no memory (dh_api.hip: int
+    """256 bytes that read as a dh_fit_basis of n points and k fields on device 0 with largest 0 and no memory (dh_api_fit.hip: int
     device; uint32 n, k; double largest; the buffer) -- for refusals that come after the basis's own."""
     block = np.zeros(256, np.uint8)
     block[4:12].view(np.uint32)[:] = (n, k)
