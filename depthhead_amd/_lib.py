@@ -229,7 +229,7 @@ EXPORTS = [
     "dh_biwi_decode_depth", "dh_biwi_parse_cal", "dh_biwi_parse_pose",
     "dh_graph_capture", "dh_graph_launch", "dh_graph_destroy",
     "dh_set_profiling", "dh_get_timing", "dh_debug_enable", "dh_debug_leaf_indices", "dh_debug_patch_flags",
-    "dh_debug_grids", "dh_debug_guesses", "dh_debug_votes", "dh_debug_meanshift", "dh_debug_hit_counts", "dh_debug_geometry", "dh_debug_tile_shifts",
+    "dh_debug_grids", "dh_debug_guesses", "dh_debug_votes", "dh_debug_meanshift", "dh_debug_hit_counts", "dh_debug_geometry", "dh_debug_tile_shifts", "dh_debug_window_totals",
     "dh_trainer_create", "dh_trainer_destroy", "dh_trainer_add_frames", "dh_trainer_fit", "dh_trainer_stats", "dh_forest_export",
     "dh_cameras_create", "dh_cameras_destroy", "dh_predict_batch_cameras", "dh_predict_batch_cameras_device",
     "dh_tracker_create", "dh_tracker_destroy", "dh_tracker_reset", "dh_tracker_step", "dh_tracker_step_device",

@@ -59,6 +59,7 @@ struct Workspace {
     size_t tile_list_stride = 0;       // entries per x
     TileShifts shifts;                 // the shifts of the tile grid a frame of this workspace chooses from (dh_tile_shifts_)
     Buf<uint32_t> tile_shift;          // [cap] sx | sy << 16 chosen for each frame of the last batch (k_tile_shift; zero otherwise)
+    bool last_gated = false;           // the last batch's tiles gated their own windows (dh_tile_gate_; debug_window_totals_)
     int list_chunks = 0;               // kernel sequences of the last batch that ran with tile lists (debug_tile_shifts_)
     uint32_t *list_ptr(int chunk) const { return tile_list.get() + (size_t)chunk * 8 * (2 * tile_list_stride + 1); }
     Buf<uint32_t> win_patch;           // [cap][win_cap] window list: position in the window grid
@@ -115,6 +116,7 @@ struct Workspace {
     uint32_t *rot_grid(int f0) const { return counters.get() + lay.rot_grid + (size_t)f0 * DH_GRID3; }
     uint8_t *tile_flags(int f0) const { return (uint8_t *)(counters.get() + lay.tile_flags) + (size_t)f0 * lay.tiles; }
     uint32_t *win_count(int f0) const { return counters.get() + lay.win_count + (size_t)f0 * lay.tiles; }
+    uint32_t *win_total(int f0) const { return counters.get() + lay.win_count + f0; }   // (gated batches only: CounterLayout, dh_host.h)
     uint32_t *leaf_hits(int f0) const { return lay.leaves ? counters.get() + lay.leaf_hits + (size_t)f0 * lay.leaves : nullptr; }
 };
 
@@ -675,7 +677,7 @@ static int enqueue_range(dh_predictor *p, const BatchReq &sl, int f0, int n, hip
             else {
                 unsigned long long hst[8];
                 HIP_TRY(hipMemcpy(hst, stamps, 64, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[k_traverse cycles/phase summed over the workgroups that reach it] region=%llu gate=%llu walks=%llu\n", hst[0], hst[1], hst[2]);
+                fprintf(stderr, "[k_traverse cycles/phase summed over the workgroups that reach it] region=%llu gate=%llu walks=%llu gated tail=%llu\n", hst[0], hst[1], hst[2], hst[3]);
                 HIP_TRY(hipMemset(stamps, 0, 64));
             }
             ta.dbg_stamps = stamps;
@@ -685,6 +687,10 @@ static int enqueue_range(dh_predictor *p, const BatchReq &sl, int f0, int n, hip
         const int tiles = g.tiles_x * g.tiles_y;
         uint32_t *win_count = ws.win_count(f0);
         ta.win_count = win_count; ta.win_cap = g.win_cap;
+        // the tiles gate their own windows wherever the rule allows (dh_host.h); a launch that stops here feeds the taps' arrays
+        const bool gate = !o.traverse_only && !o.leaf_out && !o.flags_out && dh_tile_gate_(g, p->ws.cap_frames, p->absorb_ok, p->n_trees, p->debug, p->knobs);
+        if (gate) { ta.tile_gate = 1; ta.win_total = ws.win_total(f0); }
+        if (!o.traverse_only) p->ws.last_gated = gate;
         ta.win_patch = ws.win_patch.get() + (size_t)f0 * g.win_cap; ta.win_leaf = ws.win_leaf.get() + (((size_t)f0 * g.win_cap * p->n_trees) << ws.leaf_ls); ta.leaf_ls = ws.leaf_ls;
         ta.dbg_leaf = o.leaf_out ? o.leaf_out : p->debug ? ws.dbg_leaf.get() + (size_t)f0 * g.npatch * p->n_trees : nullptr;
         ta.dbg_flags = o.flags_out ? o.flags_out : p->debug ? ws.dbg_flags.get() + (size_t)f0 * g.npatch : nullptr;
@@ -699,6 +705,7 @@ static int enqueue_range(dh_predictor *p, const BatchReq &sl, int f0, int n, hip
             memcpy(ea.kinv, kinv, 9 * sizeof(float));
             ea.cams = cs.dev();
             ea.f = p->dev;
+            ea.win_total = ta.win_total; ea.pre_gated = ta.tile_gate;
             ea.win_count = win_count; ea.win_patch = ta.win_patch; ea.win_leaf = ta.win_leaf; ea.leaf_ls = ws.leaf_ls; ea.win_cap = g.win_cap;
             ea.hits = ws.hits.get() + hoff; ea.hit_box = ws.hit_box.get() + hoff; ea.hit_rot = ws.hit_rot.get() + hoff;
             ea.hit_count = hit_count; ea.hits_cap = ws.hits_cap;
@@ -2056,12 +2063,36 @@ static int debug_hit_counts_(dh_predictor *p, uint32_t *out) {
         return DH_OK;
     });
 }
+// The windows of every frame of the last batch that passed the probability gate (prediction.rs:582-584).  A batch whose tiles gated
+// their own windows counted them (win_total: the lengths of its lists); for any other the frames' lists, still in the workspace, are
+// gated once more here.
+static int debug_window_totals_(dh_predictor *p, uint32_t *out) {
+    return with_taps(p, false, [&]() -> int {
+        if (!out) return fail(DH_EINVAL, "NULL output");
+        const Workspace &ws = p->ws;
+        const Geom &g = ws.geom;
+        const size_t bytes = (size_t)p->last_n * 4;
+        if (g.npatch <= 0) { memset(out, 0, bytes); return DH_OK; }
+        if (ws.last_gated) { HIP_TRY(hipMemcpy(out, ws.win_total(0), bytes, hipMemcpyDeviceToHost)); return DH_OK; }
+        Buf<uint32_t> tot;
+        TRY(tot.alloc(p->last_n));
+        HIP_TRY(hipMemset(tot.get(), 0, bytes));
+        EmitArgs ea{};
+        ea.n_frames = p->last_n; ea.px = g.px; ea.py = g.py; ea.tiles = g.tiles_x * g.tiles_y; ea.f = p->dev;
+        ea.win_count = ws.win_count(0); ea.win_leaf = ws.win_leaf.get(); ea.leaf_ls = ws.leaf_ls; ea.win_cap = g.win_cap;
+        HIP_TRY(dh_launch_window_totals(ea, tot.get(), nullptr));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(out, tot.get(), bytes, hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
+}
 static int debug_geometry_(dh_predictor *p, int32_t out[10]) {
     if (!p || !out) return fail(DH_EINVAL, "NULL argument");
     if (p->ws.cap_frames == 0) return fail(DH_ESTATE, "no workspace yet (dh_predictor_reserve or a batch)");
     const Geom &g = p->ws.geom;
     const bool walk_tab = g.uniform && p->absorb_ok;
-    const int32_t v[10] = {(g.uniform ? 1 : 0) | (walk_tab ? 1 << 8 : 0) | (walk_tab ? g.top_levels << 16 : 0), g.px, g.py, g.tiles_x, g.tiles_y, g.swz_log2, g.swz_q, g.ss_row, p->f_rw, p->f_rh};
+    const bool tile_gate = dh_tile_gate_(g, p->ws.cap_frames, p->absorb_ok, p->n_trees, p->debug, p->knobs);
+    const int32_t v[10] = {(g.uniform ? 1 : 0) | (walk_tab ? 1 << 8 : 0) | (tile_gate ? 1 << 9 : 0) | (walk_tab ? g.top_levels << 16 : 0), g.px, g.py, g.tiles_x, g.tiles_y, g.swz_log2, g.swz_q, g.ss_row, p->f_rw, p->f_rh};
     memcpy(out, v, sizeof v);
     return DH_OK;
 }
@@ -2611,6 +2642,7 @@ DH_API(debug_patch_flags, (dh_predictor *p, uint8_t *out, size_t cap), (p, out, 
 DH_API(debug_grids, (dh_predictor *p, uint32_t *pos_grid, uint32_t *rot_grid), (p, pos_grid, rot_grid))
 DH_API(debug_hit_counts, (dh_predictor *p, uint32_t *out), (p, out))
 DH_API(debug_geometry, (dh_predictor *p, int32_t out[10]), (p, out))
+DH_API(debug_window_totals, (dh_predictor *p, uint32_t *out), (p, out))
 DH_API(debug_tile_shifts, (dh_predictor *p, int32_t *shifts, uint32_t counts[8]), (p, shifts, counts))
 DH_API(debug_guesses, (dh_predictor *p, int32_t *out), (p, out))
 DH_API(debug_meanshift, (dh_predictor *p, int which, int32_t *trace, uint32_t *steps), (p, which, trace, steps))

@@ -197,6 +197,7 @@ Knobs dh_read_knobs_() {
     k.region_min_hits = std::max(0, geti("DH_REGION_MIN_HITS", 0));
     k.no_general_int = getenv("DH_NO_GENERAL_INT") != nullptr;
     k.no_absorb = getenv("DH_NO_ABSORB") != nullptr;
+    k.no_tile_gate = getenv("DH_NO_TILE_GATE") != nullptr;
     k.vote_exact = getenv("DH_VOTE_EXACT") != nullptr;
     k.no_tile_list = getenv("DH_NO_TILE_LIST") != nullptr;
     k.no_zero_fold = getenv("DH_NO_ZERO_FOLD") != nullptr;
@@ -389,6 +390,12 @@ int dh_tile_shifts_(const Geom &g, int step, int blk_shift, const Knobs &k, Tile
     t.on = fits;
     *out = t;
     return DH_OK;
+}
+
+bool dh_tile_gate_(const Geom &g, int cap_frames, bool absorb_ok, uint32_t n_trees, bool taps, const Knobs &k) {
+    if (!g.uniform || !absorb_ok || g.npatch <= 0 || cap_frames <= 1 || taps || k.no_tile_gate) return false;
+    const size_t items = (size_t)g.px * g.py * n_trees;
+    return items <= 4096 && items * 8 <= (size_t)4 * g.ss_max;
 }
 
 // ------------------------------------------------------------------ per-batch counter block

@@ -97,6 +97,7 @@ struct Knobs {
     int tile_shift_x = 0, tile_shift_y = 0;   // every frame (clamped to the allowed shifts), 3 = anything else (refused when a workspace is sized)
     bool vote_exact = false;          // DH_VOTE_EXACT: k_vote takes the two IEEE divisions for every vote
     bool no_absorb = false;           // DH_NO_ABSORB: uniform path walks the guarded node table
+    bool no_tile_gate = false;        // DH_NO_TILE_GATE: k_traverse lists every active window and k_emit runs the probability gate (dh_tile_gate_)
     bool no_general_int = false;      // DH_NO_GENERAL_INT: general path with the f64 divisions on every visit
     int stage_chunk = 64;             // DH_STAGE_CHUNK: frames per upload chunk of the host entry points
     int host_threads = 8;             // DH_HOST_THREADS: host threads that validate / pack run-length coded payloads
@@ -160,6 +161,18 @@ static const int kBoxSpan = 256, kBoxMaxRect = 96;   // image columns one k_boxs
 // ring's LDS); a wave marches its band + rh - 1 rows.  Picks the band count with the smallest (march) x (rounds of workgroups).
 int dh_box_bands_(int n, int parts, int rows, int blk, int rh, int wg_slots, int *oh);
 
+// Whether k_traverse's tiles run the probability gate themselves and list only the windows that pass it (its gated tail; k_emit then
+// takes its pre-gated instances).  All of: the uniform path with the walk table; every tile walks in ONE lock-step pass,
+// px * py * T <= 4096 (with several passes the region is still read when the first leaves are known); the f64 leaf probability the
+// tail parks per (window, tree) fits the tile's dead region, px * py * T * 8 <= 4 * ss_max; the workspace holds more than one frame (a
+// single-frame workspace serves latency: a frame alone waits for the chain of its kernels, and the tail's two global round trips --
+// probability gather, returning atomic -- lengthen k_traverse's by more than k_emit's look-up gives back: 79.6 -> 86 us per frame at
+// 640 x 480, stride 4, profiles/r05_tile_gate.md); the taps are off
+// (they describe the ungated list); DH_NO_TILE_GATE is unset.  A launch that stops after k_traverse (mask / 2-D Hough: its leaves go
+// to the taps' arrays) keeps the ungated path whatever this says.  No request kind needs ungated windows: poses, support and heads
+// all start from k_emit's hit records.
+bool dh_tile_gate_(const Geom &g, int cap_frames, bool absorb_ok, uint32_t n_trees, bool taps, const Knobs &k);
+
 // ------------------------------------------------------------------ per-batch counter block
 #define DH_GRID3 8000          // 20^3
 #define DH_POSGRID 400         // 20^2
@@ -167,6 +180,9 @@ int dh_box_bands_(int n, int parts, int rows, int blk, int rh, int wg_slots, int
 // region: hit counts [cap] | position grids [cap][20^2] | rotation grids [cap][20^3] | tile flags [cap * flag_words] |
 // window counts [cap][tiles] | leaf histogram [cap][leaves] (absent: leaves = 0).  The tile flags are one byte per tile and
 // frame f's start at byte f * tiles of their region (flag_words * 4 >= tiles).
+// A batch whose tiles gate their own windows (dh_tile_gate_) neither writes nor reads the per-tile window counts: the FIRST cap
+// words of that region are then win_total[cap], the gated windows per frame (tiles >= 1 wherever a frame has windows) -- inside the
+// range every path clears per batch (k_boxsum's folded fill, the fill of its own, before forked sub-batches, in a replayed graph).
 struct CounterLayout {
     size_t tiles = 0, leaves = 0;      // tile-flag bytes and window counts per frame; histogram words per frame
     size_t hit_count = 0, pos_grid = 0, rot_grid = 0, tile_flags = 0, win_count = 0, leaf_hits = 0;   // first word of each region

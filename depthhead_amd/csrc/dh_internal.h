@@ -128,7 +128,7 @@ struct TraverseArgs {
     int top_levels;
     const void *nodes_g;    // general path: NodeG[n_nodes] with integer split bounds (patches up to 255 x 255), else NULL
     unsigned long long *dbg_stamps; // profiling: [8] summed cycles per phase (region build, gate, walks) over all workgroups (env DH_TRAV_STAMPS)
-    int stop_phase;         // profiling knob (env DH_TRAV_STOP): 0 = run everything, 9 / 1 / 3 = return at entry / after the region build / after the gate
+    int stop_phase;         // profiling knob (env DH_TRAV_STOP): 0 = run everything, 9 / 1 / 3 / 4 = return at entry / after the region build / after the gate / after the walks (before the gated tail)
     DevForest f;
     // window list (read by k_emit): tile t owns slots [t * px * py, t * px * py + win_count[frame][t])
     uint32_t *win_count;    // [n_frames][tiles] active windows per tile (zeroed per batch by the host)
@@ -136,6 +136,11 @@ struct TraverseArgs {
     void     *win_leaf;     // [n_frames][T][win_cap] leaf reached in every tree: u16 entries when leaf_ls == 1 (forests of <= 65 535 leaves), else i32
     int       leaf_ls;      // log2 of the entry size of win_leaf (1 or 2)
     int       win_cap;      // tiles * px * py
+    // the pre-gated list (tile_gate != 0, dh_tile_gate_; the <true, true, true> instance): a tile runs the probability gate itself
+    // and appends only the windows that pass it, so the frame's list is slots [0, win_total[frame]) in no defined order and
+    // win_count is neither written nor read
+    uint32_t *win_total;    // [n_frames] gated windows per frame (zeroed per batch with the other counters: CounterLayout)
+    int       tile_gate;
     int32_t  *dbg_leaf;     // nullable [n][npatch][T]
     uint8_t  *dbg_flags;    // nullable [n][npatch]
 };
@@ -154,6 +159,8 @@ struct EmitArgs {
     const void     *win_leaf;   // see TraverseArgs
     int       leaf_ls;
     int       win_cap;
+    const uint32_t *win_total;  // with pre_gated (the PG instances): [n_frames] length of each frame's list, see TraverseArgs
+    int       pre_gated;
     HitRec   *hits;
     HitBox   *hit_box;
     HitRot   *hit_rot;
@@ -504,6 +511,7 @@ hipError_t dh_launch_traverse(const TraverseArgs &a, size_t lds_bytes, hipStream
 hipError_t dh_launch_tile_list(const uint8_t *flags, const uint32_t *gen, int n_frames, int tiles, uint2 *list, uint32_t *count, uint32_t stride, hipStream_t s);
 hipError_t dh_launch_tile_shift(const TileShiftArgs &a, hipStream_t s);
 hipError_t dh_launch_emit(const EmitArgs &a, hipStream_t s);
+hipError_t dh_launch_window_totals(const EmitArgs &a, uint32_t *out, hipStream_t s);   // debug: out[frame] += windows of an UNGATED list that pass the gate
 hipError_t dh_launch_vote(const VoteArgs &a, hipStream_t s);
 hipError_t dh_launch_cluster(const ClusterArgs &a, hipStream_t s);
 hipError_t dh_launch_region(const ClusterArgs &a, hipStream_t s);

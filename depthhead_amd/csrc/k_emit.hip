@@ -17,7 +17,9 @@
 // own: the instances without a table keep their code and registers).
 // SUP: the batch reports vote support (k_support): every hit record's window also goes to EmitArgs::hit_win (again an instance
 // of its own, so the plain instances keep their code).
-template <int EB, int LS, bool CAM, bool SUP>      // LS: log2 of the window list's leaf entry size (dh_device.h: load_leaf)
+// PG: the list is pre-gated (k_traverse's gated tail, EmitArgs::pre_gated): thread i of the frame takes slot i of its list and is live
+// iff i < win_total[frame] -- no per-tile counts, no scan, no search, no probability sum; every listed window has passed the gate.
+template <int EB, int LS, bool CAM, bool SUP, bool PG>      // LS: log2 of the window list's leaf entry size (dh_device.h: load_leaf)
 __global__ void __launch_bounds__(EMIT_THREADS) k_emit(EmitArgs a) {
     const int frame = blockIdx.y, lane = threadIdx.x & (WAVE - 1);
     if (CAM) cam_kinv(a.kinv, a.cams + frame);
@@ -32,6 +34,9 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(EmitArgs a) {
     const uint32_t idx = (uint32_t)blockIdx.x * EMIT_THREADS + threadIdx.x;
     uint32_t before = 0;                 // active windows in the tiles of earlier steps
     int tile = -1, slot = 0;
+    if (PG) {
+        if (idx < min(a.win_total[frame], (uint32_t)a.win_cap)) { tile = 0; slot = (int)idx; }      // (one wave-uniform load)
+    } else
     for (int t0 = 0; t0 < a.tiles; t0 += WAVE) {
         const uint32_t c = t0 + lane < a.tiles ? counts[t0 + lane] : 0u;
         const uint32_t inc = wave_incl_scan(c);
@@ -85,15 +90,15 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(EmitArgs a) {
 #pragma unroll
             for (int k = 0; k < EB; ++k)
                 if (t0 + k < T) {
-                    prob = __dadd_rn(prob, pr[k]);                                   // tree order, f64 (prediction.rs:582-584)
+                    if (!PG) prob = __dadd_rn(prob, pr[k]);                          // tree order, f64 (prediction.rs:582-584)
                     if ((lf[k] & LF_PROB) && (lf[k] & (LF_ROT | LF_OFF))) {
                         cnt++; voting |= 1ull << ((t0 + k) & 63);
                         if (lf[k] & LF_ROT) rotv |= 1u << k;                          // (only read when T <= EB)
                     }
                 }
         }
-        prob = __ddiv_rn(prob, (double)T);
-        gated = prob > DH_PROB_GATE;
+        if (!PG) prob = __ddiv_rn(prob, (double)T);
+        gated = PG ? true : prob > DH_PROB_GATE;
         if (!gated) { cnt = 0; voting = 0; rotv = 0; }
         if (gated && a.dbg_flags) a.dbg_flags[(size_t)frame * a.npatch + gp] = 3;
     }
@@ -201,20 +206,48 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit(EmitArgs a) {
     }
 }
 
+// dh_debug_window_totals for a batch that ran the gate in k_emit: one workgroup per frame goes over the frame's ungated list and
+// gates every window once more, with the operations above (debug only: nothing on the prediction path launches it).
+__global__ void __launch_bounds__(EMIT_THREADS) k_window_totals(EmitArgs a, uint32_t *out) {
+    const int frame = blockIdx.x, T = (int)a.f.n_trees, pp = a.px * a.py;
+    const char *wl = (const char *)a.win_leaf + (((size_t)frame * a.win_cap * T) << a.leaf_ls);
+    uint32_t n = 0;
+    for (int tile = 0; tile < a.tiles; ++tile) {
+        const uint32_t c = min(a.win_count[(size_t)frame * a.tiles + tile], (uint32_t)pp);
+        for (uint32_t slot = threadIdx.x; slot < c; slot += EMIT_THREADS) {
+            const size_t w = (size_t)tile * pp + slot;
+            double prob = 0.0;
+            for (int t = 0; t < T; ++t) prob = __dadd_rn(prob, a.f.leaf_prob[load_leaf(wl, a.leaf_ls, (size_t)t * a.win_cap + w)]);
+            if (__ddiv_rn(prob, (double)T) > DH_PROB_GATE) ++n;
+        }
+    }
+    if (n) atomicAdd(&out[frame], n);
+}
+hipError_t dh_launch_window_totals(const EmitArgs &a, uint32_t *out, hipStream_t s) {
+    if (a.n_frames == 0 || a.tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_window_totals, dim3(a.n_frames), dim3(EMIT_THREADS), 0, s, a, out);
+    return hipGetLastError();
+}
+
 hipError_t dh_launch_emit(const EmitArgs &a, hipStream_t s) {
     if (a.n_frames == 0 || a.tiles == 0 || a.npatch == 0) return hipSuccess;
-    if (a.n_frames > 65535) return hipErrorInvalidConfiguration;
+    if (a.n_frames > 65535 || (a.pre_gated && !a.win_total)) return hipErrorInvalidConfiguration;
     const dim3 grid((a.npatch + EMIT_THREADS - 1) / EMIT_THREADS, a.n_frames), block(EMIT_THREADS);
     const uint32_t T = a.f.n_trees;
-#define EMIT_LAUNCH_S(EB_, SUP_)                                                                      \
-    do {                                                                                              \
-        if (a.cams) {                                                                                 \
-            if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1, true, SUP_>), grid, block, 0, s, a);   \
-            else hipLaunchKernelGGL((k_emit<EB_, 2, true, SUP_>), grid, block, 0, s, a);                  \
-        } else {                                                                                      \
-            if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1, false, SUP_>), grid, block, 0, s, a);  \
-            else hipLaunchKernelGGL((k_emit<EB_, 2, false, SUP_>), grid, block, 0, s, a);                 \
-        }                                                                                             \
+#define EMIT_LAUNCH_P(EB_, SUP_, PG_)                                                                      \
+    do {                                                                                                   \
+        if (a.cams) {                                                                                      \
+            if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1, true, SUP_, PG_>), grid, block, 0, s, a);   \
+            else hipLaunchKernelGGL((k_emit<EB_, 2, true, SUP_, PG_>), grid, block, 0, s, a);                  \
+        } else {                                                                                           \
+            if (a.leaf_ls == 1) hipLaunchKernelGGL((k_emit<EB_, 1, false, SUP_, PG_>), grid, block, 0, s, a);  \
+            else hipLaunchKernelGGL((k_emit<EB_, 2, false, SUP_, PG_>), grid, block, 0, s, a);                 \
+        }                                                                                                  \
+    } while (0)
+#define EMIT_LAUNCH_S(EB_, SUP_)                        \
+    do {                                                \
+        if (a.pre_gated) EMIT_LAUNCH_P(EB_, SUP_, true); \
+        else EMIT_LAUNCH_P(EB_, SUP_, false);           \
     } while (0)
 #define EMIT_LAUNCH(EB_)                                \
     do {                                                \
@@ -228,5 +261,6 @@ hipError_t dh_launch_emit(const EmitArgs &a, hipStream_t s) {
     else EMIT_LAUNCH(16);
 #undef EMIT_LAUNCH
 #undef EMIT_LAUNCH_S
+#undef EMIT_LAUNCH_P
     return hipGetLastError();
 }

@@ -331,9 +331,12 @@ __device__ __forceinline__ void walk_uniform(const TraverseArgs &a, const uint32
 //  * the loop is wave-uniform (no per-walk exec masks): two half-word byte offsets -> two LDS reads, subtract, compare, select;
 //  * a walk that lands in the ambiguity band of a node leaves the loop with that node's code, is decided by the reference's
 //    f64 arithmetic and re-enters (rare; the layout is described at k_nodes_compact).
-template <int W>
+//  * GATE (the gated tail of k_traverse, phase 5): the tile's walks are one pass, and instead of storing its leaves a lane keeps
+//    them (gl) with their f64 probabilities (gpr: one more gather per chain, from the dense table DevForest::leaf_prob) for the tail.
+template <int W, bool GATE>
 __device__ __forceinline__ void walk_absorb(const TraverseArgs &a, const uint32_t *sat, const uint32_t *top, char *wleaf, int32_t *dleaf,
-                                            const uint32_t *active, const uint32_t *agp, int n_active, int total, int cx, int ss, int T) {
+                                            const uint32_t *active, const uint32_t *agp, int n_active, int total, int cx, int ss, int T,
+                                            uint32_t (&gl)[TRAV_WMAX], double (&gpr)[TRAV_WMAX]) {
     const int tid = threadIdx.x;
     const char *tab = (const char *)a.nodes_a;
     const uint32_t lb = a.walk_lb;                   // byte offset of the entry finished walks re-read; leaf l = lb + 16 l
@@ -416,13 +419,21 @@ __device__ __forceinline__ void walk_absorb(const TraverseArgs &a, const uint32_
                 }
             if (__ballot(again) == 0ull) break;
         }
+        if (GATE) {
+            // (an item past the tile's last one stands on entry lb = leaf 0: its gather is harmless and the tail never parks it)
 #pragma unroll
-        for (int i = 0; i < W; ++i)
-            if (k0 + i * TRAV_THREADS < total) {
-                const int32_t leaf = (int32_t)((cur[i] - lb) >> 4);
-                store_leaf(wleaf, a.leaf_ls, dst[i], leaf);
-                if (dleaf) dleaf[ddst[i]] = leaf;
-            }
+            for (int i = 0; i < W; ++i) gl[i] = (cur[i] - lb) >> 4;
+#pragma unroll
+            for (int i = 0; i < W; ++i) gpr[i] = a.f.leaf_prob[gl[i]];
+        } else {
+#pragma unroll
+            for (int i = 0; i < W; ++i)
+                if (k0 + i * TRAV_THREADS < total) {
+                    const int32_t leaf = (int32_t)((cur[i] - lb) >> 4);
+                    store_leaf(wleaf, a.leaf_ls, dst[i], leaf);
+                    if (dleaf) dleaf[ddst[i]] = leaf;
+                }
+        }
     }
 }
 
@@ -515,7 +526,9 @@ __device__ __forceinline__ void walk_general_int(const TraverseArgs &a, const ui
 #define STAMP(k)
 #endif
 
-template <bool UNI, bool GI>
+// GATE (an instance of its own beside the walk-table one, UNI && GI; the other three keep their code, registers and list layout):
+// the tile gates its own windows (phase 5) and lists only the ones that vote.
+template <bool UNI, bool GI, bool GATE = false>
 __global__ void __launch_bounds__(TRAV_THREADS, TRAV_THREADS / 128) k_traverse(TraverseArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
@@ -690,10 +703,11 @@ __global__ void __launch_bounds__(TRAV_THREADS, TRAV_THREADS / 128) k_traverse(T
     if (KNOB_STOP(a.stop_phase == 3)) return;
     STAMP(1)
     const int n_active = (int)misc[0];
-    if (tid == 0) a.win_count[(size_t)frame * (a.tiles_x * a.tiles_y) + tile] = (uint32_t)n_active;   // zero for skipped tiles (host memset)
+    // (the gated tail keeps no per-tile counts and no tile segments: its windows go to the frame's list by win_total)
+    if (!GATE && tid == 0) a.win_count[(size_t)frame * (a.tiles_x * a.tiles_y) + tile] = (uint32_t)n_active;   // zero for skipped tiles (host memset)
     if (n_active == 0) return;     // nothing to walk (debug taps were written above)
     // the window list's positions: stored after the barrier so that nothing waits for the stores
-    if (tid < n_active) wpatch[tid] = agp[tid];
+    if (!GATE && tid < n_active) wpatch[tid] = agp[tid];
 
     // ---- phase 3: root->leaf walks.  Work item k = (tree k / n_active, active slot k % n_active),
     // lane = k mod 1024: the lanes of a wave walk the SAME tree for NEIGHBOURING windows (4 px apart),
@@ -708,6 +722,10 @@ __global__ void __launch_bounds__(TRAV_THREADS, TRAV_THREADS / 128) k_traverse(T
     const int total = n_active * T;
     char *wleaf = (char *)a.win_leaf + (((size_t)frame * a.win_cap * T + wbase) << a.leaf_ls);   // [tree][win_cap] per frame
     int32_t *dleaf = a.dbg_leaf ? a.dbg_leaf + (size_t)frame * a.nx * a.ny * T : nullptr;
+    uint32_t gl[TRAV_WMAX];        // (GATE) leaf and leaf probability of this lane's items tid, tid + TRAV_THREADS, ...
+    double gpr[TRAV_WMAX];
+#pragma unroll
+    for (int i = 0; i < TRAV_WMAX; ++i) { gl[i] = 0; gpr[i] = 0.0; }
     if (UNI) {
         // W walks per lane, advanced in lock step: their node fetches and box-sum reads are
         // independent, so each lane keeps W dependent-load chains in flight.  W = walks per lane
@@ -718,17 +736,17 @@ __global__ void __launch_bounds__(TRAV_THREADS, TRAV_THREADS / 128) k_traverse(T
         const int all_passes = (total - wave_first + TRAV_THREADS - 1) / TRAV_THREADS;
         const int per_lane = all_passes > TRAV_WMAX ? (total + TRAV_THREADS - 1) / TRAV_THREADS : all_passes;
         if (GI) {                   // (uniform path: the second template flag selects the absorbing-leaf walk table)
-            if (per_lane <= 1) walk_absorb<1>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T);
-            else if (per_lane == 2) walk_absorb<2>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T);
-            else if (per_lane == 3) walk_absorb<3>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T);
+            if (per_lane <= 1) walk_absorb<1, GATE>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T, gl, gpr);
+            else if (per_lane == 2) walk_absorb<2, GATE>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T, gl, gpr);
+            else if (per_lane == 3) walk_absorb<3, GATE>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T, gl, gpr);
 #if TRAV_WMAX >= 8
-            else if (per_lane == 4) walk_absorb<4>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T);
-            else if (per_lane == 5) walk_absorb<5>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T);
-            else if (per_lane == 6) walk_absorb<6>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T);
-            else if (per_lane == 7) walk_absorb<7>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T);
-            else walk_absorb<8>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T);
+            else if (per_lane == 4) walk_absorb<4, GATE>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T, gl, gpr);
+            else if (per_lane == 5) walk_absorb<5, GATE>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T, gl, gpr);
+            else if (per_lane == 6) walk_absorb<6, GATE>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T, gl, gpr);
+            else if (per_lane == 7) walk_absorb<7, GATE>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T, gl, gpr);
+            else walk_absorb<8, GATE>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T, gl, gpr);
 #else
-            else walk_absorb<4>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T);
+            else walk_absorb<4, GATE>(a, sat, top, wleaf, dleaf, active, agp, n_active, total, cx, ss, T, gl, gpr);
 #endif
         } else
         if (per_lane <= 1) walk_uniform<1>(a, sat, wleaf, dleaf, active, agp, n_active, total, cx, ss, T);
@@ -766,6 +784,60 @@ __global__ void __launch_bounds__(TRAV_THREADS, TRAV_THREADS / 128) k_traverse(T
     }
 
     STAMP(2)
+
+    // ---- phase 5 (GATE): the probability gate of prediction.rs:582-584, here instead of in k_emit, so that only the windows that
+    // pass it -- 25 of a frame's thousands of active ones on the bench workload -- are listed. The host selects this instance only where a tile's walks are ONE
+    // pass (px * py * T <= TRAV_WMAX * TRAV_THREADS: every lane holds all of its items now) and one f64 per item fits the region.
+    // The leaves stay in their lanes' registers: only the probabilities cross lanes.
+    if (GATE) {
+        if (KNOB_STOP(a.stop_phase == 4)) return;
+        __syncthreads();                                   // the region is dead once every wave has left its walks
+        double *pprob = (double *)sat;                     // [tree][slot] = item k: consecutive lanes, consecutive words
+#pragma unroll
+        for (int i = 0; i < TRAV_WMAX; ++i) {
+            const int k = tid + i * TRAV_THREADS;
+            if (k < total) pprob[k] = gpr[i];
+        }
+        __syncthreads();
+        // thread s < n_active gates the window of slot s and leaves its place in the frame's list, or "none", in active[s] (the
+        // walks are over: nothing reads the window of a slot any more)
+        if (__builtin_amdgcn_readfirstlane(tid & ~(WAVE - 1)) < n_active) {      // (wave-uniform: the other waves have no window)
+            bool gated = false;
+            if (tid < n_active) {
+                // the very operations of k_emit on the very same f64 values, in tree order: bit-identical by construction
+                double prob = 0.0;
+                for (int t = 0; t < T; ++t) prob = __dadd_rn(prob, pprob[t * n_active + tid]);
+                prob = __ddiv_rn(prob, (double)T);
+                gated = prob > DH_PROB_GATE;
+            }
+            const unsigned long long bal = __ballot(gated);
+            uint32_t lslot = 0xffffffffu;
+            if (bal) {                                     // a wave without a gated window issues no atomic and no store
+                uint32_t wave_base = 0;
+                if (lane == 0) wave_base = atomicAdd(&a.win_total[frame], (uint32_t)__popcll(bal));
+                wave_base = __shfl(wave_base, 0);
+                // place in the frame's list (in no defined order: it depends on scheduling).  It cannot overflow: a frame's gated
+                // windows are distinct window positions, so base + rank < npatch <= win_cap; the stores are clamped all the same.
+                if (gated) lslot = wave_base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+                if (lslot < (uint32_t)a.win_cap) a.win_patch[(size_t)frame * a.win_cap + lslot] = agp[tid];
+            }
+            if (tid < n_active) active[tid] = lslot;
+        }
+        __syncthreads();
+        // every lane stores the leaves of its own items: consecutive lanes hold one tree's neighbouring slots, whose places ascend
+        char *fl = (char *)a.win_leaf + (((size_t)frame * a.win_cap * T) << a.leaf_ls);   // [tree][win_cap] per frame
+        const float r_act = 1.0f / (float)n_active;
+#pragma unroll
+        for (int i = 0; i < TRAV_WMAX; ++i) {
+            const int k = tid + i * TRAV_THREADS;
+            if (k < total) {
+                const int t = div_small(k, n_active, r_act);
+                const uint32_t lslot = active[k - t * n_active];
+                if (lslot < (uint32_t)a.win_cap) store_leaf(fl, a.leaf_ls, t * a.win_cap + (int)lslot, (int32_t)gl[i]);
+            }
+        }
+        STAMP(3)
+    }
 }
 
 // Raise the dynamic-LDS limit of the walk kernel: a per-DEVICE attribute, set once per device and process (not allowed during
@@ -780,6 +852,7 @@ hipError_t dh_kernels_init(int device) {
     if (tracked && (done[device >> 6].load(std::memory_order_acquire) >> (device & 63)) & 1ull) return hipSuccess;
     hipError_t e = hipFuncSetAttribute((const void *)k_traverse<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_traverse<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_traverse<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_traverse<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_traverse<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = dh_region_init();
@@ -793,7 +866,9 @@ hipError_t dh_launch_traverse(const TraverseArgs &a, size_t lds_bytes, hipStream
     if (tiles == 0 || fb == 0) return hipSuccess;
     if (tiles > 65535 || fb > 65535) return hipErrorInvalidConfiguration;
     const dim3 grid((unsigned)std::min(8, a.n_frames), tiles, fb);      // (fewer than 8 frames: no workgroups for the frames that are not there)
-    if (a.uniform && a.nodes_a) hipLaunchKernelGGL((k_traverse<true, true>), grid, dim3(TRAV_THREADS), lds_bytes, s, a);
+    if (a.tile_gate && !(a.uniform && a.nodes_a && a.win_total)) return hipErrorInvalidValue;   // (dh_tile_gate_: the walk-table path only)
+    if (a.tile_gate) hipLaunchKernelGGL((k_traverse<true, true, true>), grid, dim3(TRAV_THREADS), lds_bytes, s, a);
+    else if (a.uniform && a.nodes_a) hipLaunchKernelGGL((k_traverse<true, true>), grid, dim3(TRAV_THREADS), lds_bytes, s, a);
     else if (a.uniform) hipLaunchKernelGGL((k_traverse<true, false>), grid, dim3(TRAV_THREADS), lds_bytes, s, a);
     else if (a.nodes_g) hipLaunchKernelGGL((k_traverse<false, true>), grid, dim3(TRAV_THREADS), lds_bytes, s, a);
     else hipLaunchKernelGGL((k_traverse<false, false>), grid, dim3(TRAV_THREADS), lds_bytes, s, a);

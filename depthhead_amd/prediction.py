@@ -428,7 +428,7 @@ class HoughPrediction(_lib._Handle):
         keys = ("uniform", "px", "py", "tiles_x", "tiles_y", "swz_log2", "swz_q", "ss_row", "rw", "rh")
         geo = dict(zip(keys, (int(x) for x in out)))
         path = geo["uniform"]
-        geo.update(uniform=path & 1, walk_table=(path >> 8) & 1, top_levels=path >> 16)
+        geo.update(uniform=path & 1, walk_table=(path >> 8) & 1, tile_gate=bool((path >> 9) & 1), top_levels=path >> 16)
         return geo
 
     def debug_tile_shifts(self, n: int) -> tuple[np.ndarray, np.ndarray]:
@@ -441,6 +441,12 @@ class HoughPrediction(_lib._Handle):
     def debug_hit_counts(self, n: int) -> np.ndarray:
         out = np.zeros(n, dtype=np.uint32)
         check(self._lib.dh_debug_hit_counts(self._ph, vp(out)))
+        return out
+
+    def debug_window_totals(self, n: int) -> np.ndarray:
+        """Of the last batch (n frames): per frame, the windows that passed the probability gate."""
+        out = np.zeros(n, dtype=np.uint32)
+        check(self._lib.dh_debug_window_totals(self._ph, vp(out)))
         return out
 
     def debug_votes(self, frame: int, which: int, cap: int = 1 << 22) -> np.ndarray:

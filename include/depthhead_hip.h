@@ -1754,7 +1754,8 @@ int dh_debug_meanshift(dh_predictor *p, int which, int32_t *trace, uint32_t *ste
 int dh_debug_hit_counts(dh_predictor *p, uint32_t *out);
 /* Tiling the runtime chose for the current workspace (tests construct edge cases from it):
  * out[0..9] = path (bit 0: uniform-rectangle path; bit 8: its walks use the walk table (always, unless the forest has more than 4096
- * nodes with an ambiguity band); bits 16..: tree levels walked from LDS), tile px, py, tiles_x, tiles_y, column de-interleave log2,
+ * nodes with an ambiguity band); bit 9: the tiles of a batch run the probability gate themselves and list only the windows that pass
+ * it (not with the taps on, nor under DH_NO_TILE_GATE); bits 16..: tree levels walked from LDS), tile px, py, tiles_x, tiles_y, column de-interleave log2,
  * plane stride q, LDS row stride, rectangle w, rectangle h. */
 int dh_debug_geometry(dh_predictor *p, int32_t out[10]);
 /* The tile lists of the last batch -- of its last resident slice, as for every tap, when DH_MAX_RESIDENT_FRAMES cut it into slices
@@ -1763,6 +1764,9 @@ int dh_debug_geometry(dh_predictor *p, int32_t out[10]);
  * shifts [n][2] = {sx, sy} in windows per frame (zeros where the geometry or DH_TILE_SHIFT=off leaves the one shift (0, 0);
  * DH_TILE_SHIFT=sx,sy forces one shift), counts [8] = tiles walked for the frames = x mod 8.  Waits for the batch; debug only. */
 int dh_debug_tile_shifts(dh_predictor *p, int32_t *shifts, uint32_t counts[8]);
+/* [n]: per frame of the last batch, the windows that passed the probability gate (prediction.rs:582-584) -- patch flag 3 of
+ * dh_debug_patch_flags, without the taps.  Waits for the batch; debug only. */
+int dh_debug_window_totals(dh_predictor *p, uint32_t *out);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ for l in sys.stdin:
     if l.startswith(chr(123)): d=json.loads(l); print('$1', d['kernels_ms'])
 "; }
 run full
-for v in 9 1 3; do DH_TRAV_STOP=$v run "DH_TRAV_STOP=$v"; done
+for v in 9 1 3 4; do DH_TRAV_STOP=$v run "DH_TRAV_STOP=$v"; done      # (4: before the gated tail; DH_NO_TILE_GATE=1 gives the ungated pair)
 for v in 1 2; do DH_EMIT_STOP=$v run "DH_EMIT_STOP=$v"; done
 for v in 1 2 3; do DH_VOTE_STOP=$v run "DH_VOTE_STOP=$v"; done
 for v in 1 2 3; do DH_CL_STOP=$v run "DH_CL_STOP=$v"; done
