@@ -562,275 +562,275 @@ struct EnqueueOpts {
     bool zero_fold = false;         // k_boxsum zeroes the counters: no fill of their own
 };
 
-// Enqueue the kernels (k_boxsum / k_pixflags, k_traverse, k_emit, k_vote, then [k_region,] k_cluster [, k_support] or the heads
-// kernels) for frames [f0, f0 + n) of the resident slice sl on stream s: sl.at(f0) gives their inputs and outputs, f0 their place
-// in the workspace.
-static int enqueue_range(dh_predictor *p, const BatchReq &sl, int f0, int n, hipStream_t s, const EnqueueOpts &o) {
-    const Workspace &ws = p->ws;
-    const BatchReq q = sl.at(f0);
-    const CamSel &cs = q.cams;
-    const int w = sl.w, h = sl.h;
-    // one K, or the range's first camera: kernel-argument stand-ins there (the CAM instances read the records)
-    const float *K = cs.c ? cs.c->host[cs.c0].k : q.K;
-    float kinv[9];
-    if (cs.c) memcpy(kinv, cs.c->host[cs.c0].kinv, sizeof kinv);
-    else dh_mat3_inv_f32_(K, kinv);   // cached in a RefCell by the reference (types.rs:436-441)
-    const Geom &g = ws.geom;
+// What the stages of enqueue_range share: frames [f0, f0 + n) of a resident slice, their place in the workspace, and what is
+// decided once for the whole kernel sequence.  enqueue_range gives the first six (and kinv); the rest follows from them.  Every
+// stage takes it by const reference.
+struct Launch {
+    dh_predictor *p;
+    const BatchReq q;                  // the range's request, sl.at(f0): inputs and outputs from its first frame on
+    const int f0, n; const hipStream_t s; const EnqueueOpts &o;
+    float kinv[9];                     // inverse of K (below)
+    const Workspace &ws = p->ws; const Geom &g = ws.geom;
+    const int w = q.w, h = q.h; const DhCam *cams = q.cams.dev();
+    const float *K = q.cams.c ? q.cams.c->host[q.cams.c0].k : q.K;   // one K, or the range's first camera: kernel-argument stand-ins there (the CAM instances read the records, `cams`)
     uint32_t *gen = p->gen.get() + o.chunk;      // this kernel sequence's tile-flag tag
+    // the range's entries of the counter block (its window counts: set_windows); the tile flags are one byte per tile, frames packed back to back
     uint32_t *hit_count = ws.hit_count(f0), *pos_grid = ws.pos_grid(f0), *rot_grid = ws.rot_grid(f0), *leaf_hits = ws.leaf_hits(f0);
-    const size_t hoff = (size_t)f0 * ws.hits_cap;
-    const uint16_t *fr = q.frames;
-    char batch_name[48];
-    snprintf(batch_name, sizeof batch_name, "dh:batch n=%d %dx%d", n, w, h);
-    Range batch_range(o.profile, batch_name);
-    if (o.profile) HIP_TRY(hipEventRecord(p->ev[0], s));
-    uint32_t *box = g.uniform ? ws.box.get() + (size_t)f0 * g.box_rows * ((size_t)g.box_plane << g.swz_log2) : nullptr;
-    // tile flags: one byte per tile, frames packed back to back (the slice always starts at the frame the memset covered)
     uint8_t *tile_flags = ws.tile_flags(f0);
-    // product mode: the flagged tiles as compact lists, so that the workgroups of empty tiles sit at the end of k_traverse's grid
-    // (with the taps on, every tile position keeps its workgroup: those of empty tiles write the taps' "background")
-    // (the list moves the empty tiles' workgroups behind the flagged ones; a batch whose tiles all fit the chip's 512 workgroup
-    // slots at once gains nothing from that and saves the dispatch: 3 us of a single frame's 96)
-    const bool use_list = ws.tile_list && g.npatch > 0 && !o.leaf_out && !o.flags_out && !p->debug && (long)n * g.tiles_x * g.tiles_y > 512;
-    if (use_list) p->ws.list_chunks = std::max(p->ws.list_chunks, o.chunk + 1);
+    size_t hoff = (size_t)f0 * ws.hits_cap;      // the range's first hit record
+    // uniform path: its rectangle-sum images, how k_boxsum cuts them, its sparse-store masks
+    uint32_t *box = g.uniform ? ws.box.get() + (size_t)f0 * g.box_rows * ((size_t)g.box_plane << g.swz_log2) : nullptr;
+    BoxPlan bp = g.uniform ? dh_box_plan_(n, g, p->f_rh, ws.blk_shift, p->knobs) : BoxPlan();
+    unsigned long long *blk_mask = ws.box_mask ? ws.box_mask.get() + (size_t)f0 * bp.mask_blocks * g.box_parts : nullptr;
+    int step = (int)p->params.stepwidth, lw = (int)p->params.subimage_width / 2, lh = (int)p->params.subimage_height / 2;   // the window grid's stride, half a window
+    // an unshifted tile on the image its flags come from: pitch, and the footprint of its windows -- in pixels, on the uniform path
+    // less rw - 1, rh - 1 (the rectangle-sum image holds one cell per rectangle origin)
+    int tpx = g.px * step, tpy = g.py * step;
+    int tw = (g.px - 1) * step + (int)p->params.subimage_width - (g.uniform ? p->f_rw - 1 : 0);
+    int th = (g.py - 1) * step + (int)p->params.subimage_height - (g.uniform ? p->f_rh - 1 : 0);
+    bool use_list = dh_use_tile_list_((bool)ws.tile_list, g.npatch, o.leaf_out || o.flags_out || p->debug, n, g.tiles_x * g.tiles_y);   // product mode: the flagged tiles as compact lists
     uint2 *tl_list = use_list ? (uint2 *)ws.list_ptr(o.chunk) : nullptr;
     uint32_t *tl_count = use_list ? ws.list_ptr(o.chunk) + 16 * ws.tile_list_stride : nullptr;
-    if (g.npatch > 0 && g.uniform) {
-        BoxArgs ba{};
-        ba.frames = fr; ba.zeros = p->zeros.get(); ba.n_frames = n; ba.w = w; ba.h = h; ba.rw = p->f_rw; ba.rh = p->f_rh;
-        ba.tile_flags = tile_flags; ba.tiles_x = g.tiles_x; ba.tiles_y = g.tiles_y; ba.gen = gen;
-        if (o.zero_fold) { ba.zero_ptr = ws.counters.get(); ba.zero_lo = (uint32_t)ws.lay.zero_lo; ba.zero_hi = (uint32_t)ws.lay.zero_hi; ba.zero_end = (uint32_t)ws.lay.zero_words; }
-        ba.tpx = g.px * (int)p->params.stepwidth; ba.tpy = g.py * (int)p->params.stepwidth;
-        ba.tbw = (g.px - 1) * (int)p->params.stepwidth + (int)p->params.subimage_width - p->f_rw + 1;
-        ba.tbh = (g.py - 1) * (int)p->params.stepwidth + (int)p->params.subimage_height - p->f_rh + 1;
-        ba.out = box; ba.plane = g.box_plane; ba.rows = g.box_rows; ba.lg = g.swz_log2;
-        ba.ow = g.box_ow; ba.oh = g.box_oh; ba.parts = g.box_parts; ba.bands = g.box_bands;
-        // LDS-ring instance (each pixel read once): 4 waves x (rh - 1) packed rows per workgroup, so about
-        // 12 waves fit a CU; the bands are made as tall as keeps the whole launch resident at once
-        const bool ring_on = !p->knobs.box_no_ring;
-        if (ring_on && p->f_rh >= 2 && p->f_rh - 1 <= 28) {      // 4 x 28 x 512 B + the prefix rows < 64 KB
-            // (a single-frame workspace: 8-row bands and mask blocks -- a wave's march of band + rh - 1 rows IS the kernel's
-            // duration there: 31 instead of 55 rows at rh = 24; one 320 x 240 frame 86 -> 79 us with 16-row bands, 76 with 8)
-            const int blk = 1 << ws.blk_shift;
-            int oh = 0;
-            // workgroups the chip holds at once: per CU what the ring's LDS leaves room for (53 KB at rh = 24: three), at most the six
-            // that 76 VGPRs allow; 256 CUs
-            const size_t lds_wg = (size_t)4 * (p->f_rh - 1) * 64 * 8 + (size_t)4 * (256 + 96 + 8) * 4;
-            const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(6, ((size_t)160 * 1024) / lds_wg));
-            int bands = dh_box_bands_(n, g.box_parts, g.box_rows, blk, p->f_rh, wg_per_cu * 256, &oh);
-            if (p->knobs.box_bands > 0) {                     // DH_BOX_BANDS: experiments
-                bands = std::min(p->knobs.box_bands, std::max(1, (g.box_rows + blk - 1) / blk));
-                oh = ((g.box_rows + bands - 1) / bands + blk - 1) & ~(blk - 1);
-            }
-            ba.oh = oh;                                       // whole mask blocks per band (BoxArgs::blk_mask)
-            ba.bands = (g.box_rows + ba.oh - 1) / ba.oh;
-            ba.ring = 1;
-        }
-        ba.blk_shift = ws.blk_shift;
-        ba.mask_blocks = (g.box_rows + (1 << ws.blk_shift) - 1) >> ws.blk_shift;
-        ba.blk_mask = ws.box_mask ? ws.box_mask.get() + (size_t)f0 * ba.mask_blocks * g.box_parts : nullptr;
-        if (use_list && ws.shifts.on) ba.list_count = tl_count;     // k_tile_shift appends to the lists
-        ba.blocks_per_frame = (ba.parts * ba.bands + 3) / 4;
-        { Range r(o.profile, "dh:boxsum"); HIP_TRY(dh_launch_boxsum(ba, s)); }
+    uint8_t *dbg_flags = o.flags_out ? o.flags_out : p->debug ? ws.dbg_flags.get() + (size_t)f0 * g.npatch : nullptr;   // k_traverse's and k_emit's patch flags: the caller's array, else the taps'
+};
+
+// The hit records of the frames from f0 on, for every argument block that reads or writes them.
+template <typename A>
+static void set_hits(A &a, const Workspace &ws, int f0) {
+    const size_t hoff = (size_t)f0 * ws.hits_cap;
+    a.hits = ws.hits.get() + hoff; a.hit_box = ws.hit_box.get() + hoff; a.hit_rot = ws.hit_rot.get() + hoff;
+    a.hit_count = ws.hit_count(f0); a.hits_cap = ws.hits_cap;
+}
+// The window lists of the frames from f0 on: k_traverse writes them, k_emit and k_window_totals read them.
+template <typename A>
+static void set_windows(A &a, const Workspace &ws, int f0, uint32_t n_trees) {
+    a.win_count = ws.win_count(f0); a.win_cap = ws.geom.win_cap; a.leaf_ls = ws.leaf_ls;
+    a.win_patch = ws.win_patch.get() + (size_t)f0 * a.win_cap; a.win_leaf = ws.win_leaf.get() + (((size_t)f0 * a.win_cap * n_trees) << ws.leaf_ls);
+}
+#ifdef DH_PROFILING_KNOBS
+// A kernel's cycle stamps (`words` of them, at most 16): allocated on first use; from then on every launch first prints, through
+// `print`, what the last one summed.  Cleared either way.
+template <typename Print>
+static int next_stamps(Buf<unsigned long long> &buf, size_t words, unsigned long long **out, Print print) {
+    if (!buf) TRY(buf.alloc(words));
+    else {
+        unsigned long long hst[16];
+        HIP_TRY(hipMemcpy(hst, buf.get(), words * 8, hipMemcpyDeviceToHost));
+        print(hst);
     }
-    if (g.npatch > 0 && !g.uniform) {
+    HIP_TRY(hipMemset(buf.get(), 0, words * 8));
+    *out = buf.get();
+    return DH_OK;
+}
+#endif
+
+// Tile flags: k_boxsum with the rectangle-sum images (uniform path), else k_pixflags.
+static int enqueue_flags(const Launch &L) {
+    const Workspace &ws = L.ws; const Geom &g = L.g;
+    if (!g.uniform) {
         PixFlagArgs fa{};
-        fa.frames = fr; fa.n_frames = n; fa.w = w; fa.h = h; fa.tile_flags = tile_flags; fa.gen = gen;
-        fa.tiles_x = g.tiles_x; fa.tiles_y = g.tiles_y;
-        fa.tpx = g.px * (int)p->params.stepwidth; fa.tpy = g.py * (int)p->params.stepwidth;
-        fa.tfw = (g.px - 1) * (int)p->params.stepwidth + (int)p->params.subimage_width;
-        fa.tfh = (g.py - 1) * (int)p->params.stepwidth + (int)p->params.subimage_height;
-        { Range r(o.profile, "dh:pixflags"); HIP_TRY(dh_launch_pixflags(fa, s)); }
-    }
-    // (a workspace whose frames choose the shift of their tile grid: k_tile_shift counts the flagged tiles of every allowed shift on
-    // k_boxsum's masks and writes the lists of the best one; k_boxsum's flags then serve the other paths only)
-    if (use_list && ws.shifts.on) {
-        TileShiftArgs sa{};
-        sa.n_frames = n; sa.blk_shift = ws.blk_shift; sa.mask_blocks = (g.box_rows + (1 << ws.blk_shift) - 1) >> ws.blk_shift; sa.parts = g.box_parts;
-        sa.blk_mask = ws.box_mask.get() + (size_t)f0 * sa.mask_blocks * g.box_parts;
-        sa.ow4 = g.box_ow / 4; sa.nc = g.box_parts * sa.ow4;
-        sa.tiles_x = g.tiles_x; sa.tiles_y = g.tiles_y; sa.step = (int)p->params.stepwidth;
-        sa.tpx = g.px * sa.step; sa.tpy = g.py * sa.step;
-        sa.tbw = (g.px - 1) * sa.step + (int)p->params.subimage_width - p->f_rw + 1;
-        sa.tbh = (g.py - 1) * sa.step + (int)p->params.subimage_height - p->f_rh + 1;
-        sa.sx0 = ws.shifts.sx0; sa.sy0 = ws.shifts.sy0; sa.gx = ws.shifts.gx; sa.nsx = ws.shifts.nsx; sa.nsy = ws.shifts.nsy;
-        sa.list = tl_list; sa.count = tl_count; sa.stride = (uint32_t)ws.tile_list_stride; sa.shift_out = ws.tile_shift.get() + f0;
-        Range r(o.profile, "dh:tile_list"); HIP_TRY(dh_launch_tile_shift(sa, s));
-    } else
-    if (use_list) { Range r(o.profile, "dh:tile_list"); HIP_TRY(dh_launch_tile_list(tile_flags, gen, n, g.tiles_x * g.tiles_y, tl_list, tl_count, (uint32_t)ws.tile_list_stride, s)); }
-    if (o.profile) HIP_TRY(hipEventRecord(p->ev[4], s));
-    if (g.npatch > 0) {
-        TraverseArgs ta{};
-        ta.frames = fr; ta.n_frames = n; ta.w = w; ta.h = h;
-        ta.step = (int)p->params.stepwidth; ta.sw = (int)p->params.subimage_width; ta.sh = (int)p->params.subimage_height;
-        ta.nx = g.nx; ta.ny = g.ny; ta.px = g.px; ta.py = g.py; ta.tiles_x = g.tiles_x; ta.tiles_y = g.tiles_y;
-        ta.ss_max = g.ss_max; ta.ss_row = g.ss_row; ta.swz_log2 = g.swz_log2; ta.swz_q = g.swz_q;
-        ta.uniform = g.uniform ? 1 : 0; ta.rw = p->f_rw; ta.rh = p->f_rh; ta.area = (uint32_t)(p->f_rw * p->f_rh);
-        ta.nodes_u = p->nodes_u.get(); ta.nodes_a = p->absorb_ok ? p->nodes_a.get() : nullptr; ta.walk_lb = (p->n_nodes + p->n_amb) << 4; ta.amb_list = p->amb_list.get(); ta.top_tab = p->top_tab.get(); ta.top_levels = g.top_levels; ta.nodes_g = p->knobs.no_general_int ? nullptr : p->nodes_g.get();
-        ta.box = box; ta.box_plane = g.box_plane; ta.box_rows = g.box_rows;
-        ta.tile_flags = tile_flags; ta.gen = gen;
-#ifdef DH_PROFILING_KNOBS
-        ta.stop_phase = p->knobs.trav_stop;
-        if (p->knobs.trav_stamps) {
-            unsigned long long *stamps = p->trav_stamps.get();
-            if (!stamps) { TRY(p->trav_stamps.alloc(8)); stamps = p->trav_stamps.get(); HIP_TRY(hipMemset(stamps, 0, 64)); }
-            else {
-                unsigned long long hst[8];
-                HIP_TRY(hipMemcpy(hst, stamps, 64, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[k_traverse cycles/phase summed over the workgroups that reach it] region=%llu gate=%llu walks=%llu gated tail=%llu\n", hst[0], hst[1], hst[2], hst[3]);
-                HIP_TRY(hipMemset(stamps, 0, 64));
-            }
-            ta.dbg_stamps = stamps;
-        }
-#endif
-        ta.f = p->dev;
-        const int tiles = g.tiles_x * g.tiles_y;
-        uint32_t *win_count = ws.win_count(f0);
-        ta.win_count = win_count; ta.win_cap = g.win_cap;
-        // the tiles gate their own windows wherever the rule allows (dh_host.h); a launch that stops here feeds the taps' arrays
-        const bool gate = !o.traverse_only && !o.leaf_out && !o.flags_out && dh_tile_gate_(g, p->ws.cap_frames, p->absorb_ok, p->n_trees, p->debug, p->knobs);
-        if (gate) { ta.tile_gate = 1; ta.win_total = ws.win_total(f0); }
-        if (!o.traverse_only) p->ws.last_gated = gate;
-        ta.win_patch = ws.win_patch.get() + (size_t)f0 * g.win_cap; ta.win_leaf = ws.win_leaf.get() + (((size_t)f0 * g.win_cap * p->n_trees) << ws.leaf_ls); ta.leaf_ls = ws.leaf_ls;
-        ta.dbg_leaf = o.leaf_out ? o.leaf_out : p->debug ? ws.dbg_leaf.get() + (size_t)f0 * g.npatch * p->n_trees : nullptr;
-        ta.dbg_flags = o.flags_out ? o.flags_out : p->debug ? ws.dbg_flags.get() + (size_t)f0 * g.npatch : nullptr;
-        if (use_list) { ta.tile_list = tl_list; ta.tile_list_count = tl_count; ta.tile_list_stride = (uint32_t)ws.tile_list_stride; }
-        { Range r(o.profile, "dh:traverse"); HIP_TRY(dh_launch_traverse(ta, g.lds, s)); }
-        if (o.profile) HIP_TRY(hipEventRecord(p->ev[5], s));
-        if (!o.traverse_only) {
-            EmitArgs ea{};
-            ea.frames = fr; ea.n_frames = n; ea.w = w; ea.h = h;
-            ea.step = ta.step; ea.lw = ta.sw / 2; ea.lh = ta.sh / 2; ea.nx = g.nx; ea.npatch = g.npatch;
-            ea.px = g.px; ea.py = g.py; ea.tiles = tiles;
-            memcpy(ea.kinv, kinv, 9 * sizeof(float));
-            ea.cams = cs.dev();
-            ea.f = p->dev;
-            ea.win_total = ta.win_total; ea.pre_gated = ta.tile_gate;
-            ea.win_count = win_count; ea.win_patch = ta.win_patch; ea.win_leaf = ta.win_leaf; ea.leaf_ls = ws.leaf_ls; ea.win_cap = g.win_cap;
-            ea.hits = ws.hits.get() + hoff; ea.hit_box = ws.hit_box.get() + hoff; ea.hit_rot = ws.hit_rot.get() + hoff;
-            ea.hit_count = hit_count; ea.hits_cap = ws.hits_cap;
-            // (a heads batch keeps every hit's rotation record: its rotation votes are restricted per head, hit by hit)
-            ea.leaf_hits = q.heads ? nullptr : leaf_hits;
-            ea.gen = gen;
-            ea.dbg_flags = ta.dbg_flags;
-            if (q.support || q.heads) ea.hit_win = ws.hit_win.get() + hoff;
-#ifdef DH_PROFILING_KNOBS
-            ea.stop = p->knobs.emit_stop;
-#endif
-            { Range r(o.profile, "dh:emit"); HIP_TRY(dh_launch_emit(ea, s)); }
-        }
-    } else if (o.profile) HIP_TRY(hipEventRecord(p->ev[5], s));
-    if (o.profile) HIP_TRY(hipEventRecord(p->ev[1], s));
-    if (o.traverse_only) return DH_OK;
-    {
-        VoteArgs va{};
-        va.n_frames = n; va.w = w; va.h = h;
-        va.cell_fast = !p->knobs.vote_exact && (!cs.c || cs.all_cell_fast(n, w, h)) ? 1 : 0;   // (one K: dh_launch_vote decides)
-        memcpy(va.k, K, sizeof va.k);
-        va.cams = cs.dev(); va.cams_pin = cs.c && cs.all_pin(n) ? 1 : 0;
-        va.f = p->dev; va.hits = ws.hits.get() + hoff; va.hit_box = ws.hit_box.get() + hoff; va.hit_rot = ws.hit_rot.get() + hoff;
-        va.hit_count = hit_count; va.hits_cap = ws.hits_cap;
-        va.pos_grid = pos_grid; va.rot_grid = rot_grid;
-        va.leaf_hits = q.heads ? nullptr : leaf_hits;
-#ifdef DH_PROFILING_KNOBS
-        va.stop = p->knobs.vote_stop;
-#endif
-        { Range r(o.profile, "dh:vote"); HIP_TRY(dh_launch_vote(va, s)); }
-    }
-    if (o.profile) HIP_TRY(hipEventRecord(p->ev[2], s));
-    if (q.heads) {
-        // several heads per frame: seeds, their moments, position mean shifts, support (+ head masks and rotation grids), rotation
-        // mean shifts, merge (k_heads.hip)
-        HeadsArgs ha{};
-        ha.n_frames = n; ha.w = w; ha.h = h; ha.max_heads = q.max_heads;
-        memcpy(ha.k, K, sizeof ha.k);
-        ha.cams = cs.dev();
-        ha.off4 = p->dev.off4; ha.rough_cell = p->dev.rough_cell;
-        ha.hits = ws.hits.get() + hoff; ha.hit_box = ws.hit_box.get() + hoff; ha.hit_rot = ws.hit_rot.get() + hoff; ha.hit_win = ws.hit_win.get() + hoff;
-        ha.hit_count = hit_count; ha.hits_cap = ws.hits_cap;
-        ha.pos_grid = pos_grid;
-        const size_t hk = (size_t)f0 * DH_MAX_HEADS;
-        ha.pick = ws.hd_pick.get() + hk; ha.nseed = ws.hd_nseed.get() + f0; ha.mom = ws.hd_mom.get() + hk;
-        ha.nx = g.nx; ha.step = (int)p->params.stepwidth;
-        ha.lw = (int)p->params.subimage_width / 2; ha.lh = (int)p->params.subimage_height / 2;
-        ha.radius = q.radius;
-        ha.hpose = ws.hd_pose.get() + hk; ha.acc = ws.hd_acc.get() + hk; ha.bits = ws.hd_bits.get() + hk * ws.sup_words; ha.bit_words = ws.sup_words;
-        ha.hsup = ws.hd_sup.get() + hk; ha.hmask = ws.hd_mask.get() + hoff; ha.rgrid = ws.hd_rgrid.get() + hk * DH_GRID3;
-        ha.n_heads = q.n_heads; ha.heads = q.heads;
-        ClusterArgs ca{};
-        ca.frames = fr; ca.n_frames = n; ca.w = w; ca.h = h;
-        memcpy(ca.kinv, kinv, 9 * sizeof(float));
-        ca.cams = cs.dev();
-        ca.f = p->dev; ca.hits = ha.hits; ca.hit_box = ha.hit_box; ca.hit_rot = ha.hit_rot;
-        ca.hit_count = hit_count; ca.hits_cap = ws.hits_cap;
-        ca.pos_grid = pos_grid; ca.rot_grid = ha.rgrid; ca.kern_r2 = p->kern_r2.get();
-        ca.iterations = p->params.meanshift_iterations;
-        ca.out = ws.hd_pose.get() + hk;
-        ca.hd_nseed = ha.nseed; ca.hd_mom = ha.mom; ca.hd_rgrid = ha.rgrid; ca.hd_mask = ha.hmask;
-        Range r(o.profile, "dh:heads");
-        HIP_TRY(dh_launch_heads_seeds(ha, s));
-        HIP_TRY(dh_launch_heads_moments(ha, s));
-        ca.hd_which = 0;
-        HIP_TRY(dh_launch_cluster_heads(ca, q.max_heads, s));
-        HIP_TRY(dh_launch_heads_support(ha, s));
-        ca.hd_which = 1;
-        HIP_TRY(dh_launch_cluster_heads(ca, q.max_heads, s));
-        HIP_TRY(dh_launch_heads_finish(ha, s));
-        if (o.profile) { HIP_TRY(hipEventRecord(p->ev[3], s)); p->ev_valid = true; }
+        fa.frames = L.q.frames; fa.n_frames = L.n; fa.w = L.w; fa.h = L.h; fa.tile_flags = L.tile_flags; fa.gen = L.gen;
+        fa.tiles_x = g.tiles_x; fa.tiles_y = g.tiles_y; fa.tpx = L.tpx; fa.tpy = L.tpy; fa.tfw = L.tw; fa.tfh = L.th;
+        { Range r(L.o.profile, "dh:pixflags"); HIP_TRY(dh_launch_pixflags(fa, L.s)); }
         return DH_OK;
     }
-    {
-        ClusterArgs ca{};
-        ca.frames = fr; ca.n_frames = n; ca.w = w; ca.h = h;
-        memcpy(ca.kinv, kinv, 9 * sizeof(float));
-        ca.cams = cs.dev();
-        ca.f = p->dev; ca.hits = ws.hits.get() + hoff; ca.hit_box = ws.hit_box.get() + hoff; ca.hit_rot = ws.hit_rot.get() + hoff;
-        ca.hit_count = hit_count; ca.hits_cap = ws.hits_cap;
-        ca.leaf_hits = leaf_hits;
-        ca.pos_grid = pos_grid; ca.rot_grid = rot_grid; ca.kern_r2 = p->kern_r2.get();
-        ca.iterations = p->params.meanshift_iterations;
+    BoxArgs ba{};
+    ba.frames = L.q.frames; ba.zeros = L.p->zeros.get(); ba.n_frames = L.n; ba.w = L.w; ba.h = L.h; ba.rw = L.p->f_rw; ba.rh = L.p->f_rh;
+    ba.tile_flags = L.tile_flags; ba.tiles_x = g.tiles_x; ba.tiles_y = g.tiles_y; ba.gen = L.gen; ba.tpx = L.tpx; ba.tpy = L.tpy; ba.tbw = L.tw; ba.tbh = L.th;
+    if (L.o.zero_fold) { ba.zero_ptr = ws.counters.get(); ba.zero_lo = (uint32_t)ws.lay.zero_lo; ba.zero_hi = (uint32_t)ws.lay.zero_hi; ba.zero_end = (uint32_t)ws.lay.zero_words; }
+    ba.out = L.box; ba.plane = g.box_plane; ba.rows = g.box_rows; ba.lg = g.swz_log2; ba.ow = g.box_ow; ba.parts = g.box_parts;
+    ba.ring = L.bp.ring; ba.oh = L.bp.oh; ba.bands = L.bp.bands; ba.blocks_per_frame = L.bp.blocks_per_frame;
+    ba.blk_shift = ws.blk_shift; ba.mask_blocks = L.bp.mask_blocks; ba.blk_mask = L.blk_mask;
+    if (L.use_list && ws.shifts.on) ba.list_count = L.tl_count;     // k_tile_shift appends to the lists
+    { Range r(L.o.profile, "dh:boxsum"); HIP_TRY(dh_launch_boxsum(ba, L.s)); }
+    return DH_OK;
+}
+// The tile lists of a launch that uses them.  A workspace whose frames choose the shift of their tile grid: k_tile_shift counts the
+// flagged tiles of every allowed shift on k_boxsum's masks and writes the lists of the best one (k_boxsum's flags then serve the
+// other paths only); else k_tile_list compacts the flags.
+static int enqueue_tile_list(const Launch &L) {
+    const Workspace &ws = L.ws; const Geom &g = L.g;
+    Range r(L.o.profile, "dh:tile_list");
+    if (!ws.shifts.on) { HIP_TRY(dh_launch_tile_list(L.tile_flags, L.gen, L.n, g.tiles_x * g.tiles_y, L.tl_list, L.tl_count, (uint32_t)ws.tile_list_stride, L.s)); return DH_OK; }
+    TileShiftArgs sa{};
+    sa.n_frames = L.n; sa.blk_shift = ws.blk_shift; sa.mask_blocks = L.bp.mask_blocks; sa.parts = g.box_parts; sa.blk_mask = L.blk_mask; sa.ow4 = g.box_ow / 4; sa.nc = g.box_parts * sa.ow4;
+    sa.tiles_x = g.tiles_x; sa.tiles_y = g.tiles_y; sa.step = L.step; sa.tpx = L.tpx; sa.tpy = L.tpy; sa.tbw = L.tw; sa.tbh = L.th;
+    sa.sx0 = ws.shifts.sx0; sa.sy0 = ws.shifts.sy0; sa.gx = ws.shifts.gx; sa.nsx = ws.shifts.nsx; sa.nsy = ws.shifts.nsy;
+    sa.list = L.tl_list; sa.count = L.tl_count; sa.stride = (uint32_t)ws.tile_list_stride; sa.shift_out = ws.tile_shift.get() + L.f0;
+    HIP_TRY(dh_launch_tile_shift(sa, L.s));
+    return DH_OK;
+}
+// k_traverse.  *gated: its tiles gate their own windows, and k_emit takes the pre-gated lists (enqueue_emit).
+static int enqueue_traverse(const Launch &L, bool *gated) {
+    dh_predictor *p = L.p;
+    const Workspace &ws = L.ws; const Geom &g = L.g;
+    TraverseArgs ta{};
+    ta.frames = L.q.frames; ta.n_frames = L.n; ta.w = L.w; ta.h = L.h;
+    ta.step = L.step; ta.sw = (int)p->params.subimage_width; ta.sh = (int)p->params.subimage_height;
+    ta.nx = g.nx; ta.ny = g.ny; ta.px = g.px; ta.py = g.py; ta.tiles_x = g.tiles_x; ta.tiles_y = g.tiles_y;
+    ta.ss_max = g.ss_max; ta.ss_row = g.ss_row; ta.swz_log2 = g.swz_log2; ta.swz_q = g.swz_q;
+    ta.uniform = g.uniform ? 1 : 0; ta.rw = p->f_rw; ta.rh = p->f_rh; ta.area = (uint32_t)(p->f_rw * p->f_rh);
+    ta.nodes_u = p->nodes_u.get(); ta.nodes_a = p->absorb_ok ? p->nodes_a.get() : nullptr; ta.walk_lb = (p->n_nodes + p->n_amb) << 4; ta.amb_list = p->amb_list.get();
+    ta.top_tab = p->top_tab.get(); ta.top_levels = g.top_levels; ta.nodes_g = p->knobs.no_general_int ? nullptr : p->nodes_g.get();
+    ta.box = L.box; ta.box_plane = g.box_plane; ta.box_rows = g.box_rows; ta.tile_flags = L.tile_flags; ta.gen = L.gen;
 #ifdef DH_PROFILING_KNOBS
-        ca.stop = p->knobs.cl_stop;
-        if (p->knobs.cl_stamps) {
-            unsigned long long *cl_stamps = p->cl_stamps.get();
-            if (!cl_stamps) { TRY(p->cl_stamps.alloc(16)); cl_stamps = p->cl_stamps.get(); HIP_TRY(hipMemset(cl_stamps, 0, 128)); }
-            else {
-                unsigned long long hst[16];
-                HIP_TRY(hipMemcpy(hst, cl_stamps, 128, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[k_cluster rotation workgroups, cycles summed] guess=%llu zero=%llu gather=%llu | sums: count sweep=%llu (4)=%llu scan+park=%llu (6)=%llu chain=%llu update=%llu | sums=%llu workgroups=%llu\n",
-                        hst[0], hst[1], hst[2], hst[3], hst[4], hst[5], hst[6], hst[7], hst[8], hst[14], hst[15]);
-                HIP_TRY(hipMemset(cl_stamps, 0, 128));
-            }
-            ca.dbg_stamps = cl_stamps;
-        }
+    ta.stop_phase = p->knobs.trav_stop;
+    if (p->knobs.trav_stamps)
+        TRY(next_stamps(p->trav_stamps, 8, &ta.dbg_stamps, [](const unsigned long long *hst) {
+            fprintf(stderr, "[k_traverse cycles/phase summed over the workgroups that reach it] region=%llu gate=%llu walks=%llu gated tail=%llu\n", hst[0], hst[1], hst[2], hst[3]);
+        }));
 #endif
-        ca.midp_guess = q.midp; ca.rot_guess = q.rot; ca.guess_mask = q.mask;
-        ca.out = q.out;
-        if (p->debug) { ca.dbg_guess = ws.dbg_guess.get(); ca.dbg_trace = ws.dbg_trace.get(); ca.dbg_steps = ws.dbg_steps.get(); }
-        // few frames with many hit records each: the first region of every accumulator is gathered by several workgroups
-        const int slices = std::min(16, 256 / std::max(n, 1));
-        if (ws.pre_region && slices >= 2 && f0 + n <= ws.pre_cap && ca.iterations > 0) {
-            ca.pre_region = ws.pre_region.get() + (size_t)f0 * 2 * DH_SUPER_CELLS;
-            ca.pre_slices = slices;
-            ca.pre_min_hits = ws.pre_min_hits;
-            // (a kernel node inside a captured graph, like the counters' fill)
-            const size_t pre_bytes = (size_t)n * 2 * DH_SUPER_CELLS * sizeof(uint32_t);
-            if (p->capturing) HIP_TRY(dh_launch_zero(ca.pre_region, pre_bytes, s));
-            else HIP_TRY(hipMemsetAsync(ca.pre_region, 0, pre_bytes, s));
-            { Range r(o.profile, "dh:region"); HIP_TRY(dh_launch_region(ca, s)); }
-        }
-        { Range r(o.profile, "dh:cluster"); HIP_TRY(dh_launch_cluster(ca, s)); }
+    ta.f = p->dev; set_windows(ta, ws, L.f0, p->n_trees);
+    // the tiles gate their own windows wherever the rule allows (dh_host.h); a launch that stops here feeds the taps' arrays
+    *gated = !L.o.traverse_only && !L.o.leaf_out && !L.o.flags_out && dh_tile_gate_(g, ws.cap_frames, p->absorb_ok, p->n_trees, p->debug, p->knobs);
+    if (*gated) { ta.tile_gate = 1; ta.win_total = ws.win_total(L.f0); }
+    if (!L.o.traverse_only) p->ws.last_gated = *gated;
+    ta.dbg_flags = L.dbg_flags; ta.dbg_leaf = L.o.leaf_out ? L.o.leaf_out : p->debug ? ws.dbg_leaf.get() + (size_t)L.f0 * g.npatch * p->n_trees : nullptr;
+    if (L.use_list) { ta.tile_list = L.tl_list; ta.tile_list_count = L.tl_count; ta.tile_list_stride = (uint32_t)ws.tile_list_stride; }
+    { Range r(L.o.profile, "dh:traverse"); HIP_TRY(dh_launch_traverse(ta, g.lds, L.s)); }
+    return DH_OK;
+}
+// k_emit on the window lists enqueue_traverse left: pre-gated ones where its tiles gated.
+static int enqueue_emit(const Launch &L, bool gated) {
+    const Geom &g = L.g;
+    EmitArgs ea{};
+    ea.frames = L.q.frames; ea.n_frames = L.n; ea.w = L.w; ea.h = L.h;
+    ea.step = L.step; ea.lw = L.lw; ea.lh = L.lh; ea.nx = g.nx; ea.npatch = g.npatch; ea.px = g.px; ea.py = g.py; ea.tiles = g.tiles_x * g.tiles_y;
+    memcpy(ea.kinv, L.kinv, sizeof ea.kinv);
+    ea.cams = L.cams; ea.f = L.p->dev; set_windows(ea, L.ws, L.f0, L.p->n_trees);
+    if (gated) { ea.pre_gated = 1; ea.win_total = L.ws.win_total(L.f0); }
+    set_hits(ea, L.ws, L.f0);
+    // (a heads batch keeps every hit's rotation record: its rotation votes are restricted per head, hit by hit)
+    ea.leaf_hits = L.q.heads ? nullptr : L.leaf_hits;
+    ea.gen = L.gen; ea.dbg_flags = L.dbg_flags;
+    if (L.q.support || L.q.heads) ea.hit_win = L.ws.hit_win.get() + L.hoff;
+#ifdef DH_PROFILING_KNOBS
+    ea.stop = L.p->knobs.emit_stop;
+#endif
+    { Range r(L.o.profile, "dh:emit"); HIP_TRY(dh_launch_emit(ea, L.s)); }
+    return DH_OK;
+}
+static int enqueue_vote(const Launch &L) {
+    const CamSel &cs = L.q.cams;
+    VoteArgs va{};
+    va.n_frames = L.n; va.w = L.w; va.h = L.h;
+    va.cell_fast = !L.p->knobs.vote_exact && (!cs.c || cs.all_cell_fast(L.n, L.w, L.h)) ? 1 : 0;   // (one K: dh_launch_vote decides)
+    memcpy(va.k, L.K, sizeof va.k);
+    va.cams = L.cams; va.cams_pin = cs.c && cs.all_pin(L.n) ? 1 : 0; va.f = L.p->dev;
+    set_hits(va, L.ws, L.f0);
+    va.pos_grid = L.pos_grid; va.rot_grid = L.rot_grid; va.leaf_hits = L.q.heads ? nullptr : L.leaf_hits;
+#ifdef DH_PROFILING_KNOBS
+    va.stop = L.p->knobs.vote_stop;
+#endif
+    { Range r(L.o.profile, "dh:vote"); HIP_TRY(dh_launch_vote(va, L.s)); }
+    return DH_OK;
+}
+// What k_cluster's pose instances and its HEADS instances take alike; the rotation grid, the leaf histogram and the outputs differ.
+static ClusterArgs cluster_args(const Launch &L) {
+    ClusterArgs ca{};
+    ca.frames = L.q.frames; ca.n_frames = L.n; ca.w = L.w; ca.h = L.h;
+    memcpy(ca.kinv, L.kinv, sizeof ca.kinv);
+    ca.cams = L.cams; ca.f = L.p->dev; set_hits(ca, L.ws, L.f0);
+    ca.pos_grid = L.pos_grid; ca.kern_r2 = L.p->kern_r2.get(); ca.iterations = L.p->params.meanshift_iterations;
+    return ca;
+}
+// [k_region,] k_cluster: one pose per frame.
+static int enqueue_cluster(const Launch &L) {
+    dh_predictor *p = L.p; const Workspace &ws = L.ws;
+    ClusterArgs ca = cluster_args(L);
+    ca.leaf_hits = L.leaf_hits; ca.rot_grid = L.rot_grid;
+#ifdef DH_PROFILING_KNOBS
+    ca.stop = p->knobs.cl_stop;
+    if (p->knobs.cl_stamps)
+        TRY(next_stamps(p->cl_stamps, 16, &ca.dbg_stamps, [](const unsigned long long *hst) {
+            fprintf(stderr, "[k_cluster rotation workgroups, cycles summed] guess=%llu zero=%llu gather=%llu | sums: count sweep=%llu (4)=%llu scan+park=%llu (6)=%llu chain=%llu update=%llu | sums=%llu workgroups=%llu\n",
+                    hst[0], hst[1], hst[2], hst[3], hst[4], hst[5], hst[6], hst[7], hst[8], hst[14], hst[15]);
+        }));
+#endif
+    ca.midp_guess = L.q.midp; ca.rot_guess = L.q.rot; ca.guess_mask = L.q.mask; ca.out = L.q.out;
+    if (p->debug) { ca.dbg_guess = ws.dbg_guess.get(); ca.dbg_trace = ws.dbg_trace.get(); ca.dbg_steps = ws.dbg_steps.get(); }
+    // few frames with many hit records each: the first region of every accumulator is gathered by several workgroups
+    const int slices = std::min(16, 256 / std::max(L.n, 1));
+    if (ws.pre_region && slices >= 2 && L.f0 + L.n <= ws.pre_cap && ca.iterations > 0) {
+        ca.pre_region = ws.pre_region.get() + (size_t)L.f0 * 2 * DH_SUPER_CELLS; ca.pre_slices = slices; ca.pre_min_hits = ws.pre_min_hits;
+        // (a kernel node inside a captured graph, like the counters' fill)
+        const size_t pre_bytes = (size_t)L.n * 2 * DH_SUPER_CELLS * sizeof(uint32_t);
+        if (p->capturing) HIP_TRY(dh_launch_zero(ca.pre_region, pre_bytes, L.s));
+        else HIP_TRY(hipMemsetAsync(ca.pre_region, 0, pre_bytes, L.s));
+        { Range r(L.o.profile, "dh:region"); HIP_TRY(dh_launch_region(ca, L.s)); }
     }
-    if (q.support) {
-        SupportArgs sa{};
-        sa.n_frames = n; sa.nx = g.nx; sa.step = (int)p->params.stepwidth;
-        sa.lw = (int)p->params.subimage_width / 2; sa.lh = (int)p->params.subimage_height / 2;
-        sa.radius = q.radius; sa.poses = q.out;
-        sa.hits = ws.hits.get() + hoff; sa.hit_box = ws.hit_box.get() + hoff; sa.hit_win = ws.hit_win.get() + hoff;
-        sa.hit_count = hit_count; sa.hits_cap = ws.hits_cap; sa.off4 = p->dev.off4;
-        sa.acc = ws.sup_acc.get() + f0; sa.bits = ws.sup_bits.get() + (size_t)f0 * ws.sup_words; sa.bit_words = ws.sup_words;
-        sa.out = q.support;
-        { Range r(o.profile, "dh:support"); HIP_TRY(dh_launch_support(sa, s)); }
+    { Range r(L.o.profile, "dh:cluster"); HIP_TRY(dh_launch_cluster(ca, L.s)); }
+    return DH_OK;
+}
+// Several heads per frame: seeds, their moments, position mean shifts, support (+ head masks and rotation grids), rotation mean
+// shifts, merge (k_heads.hip), in place of k_region / k_cluster.
+static int enqueue_heads(const Launch &L) {
+    const Workspace &ws = L.ws; const BatchReq &q = L.q;
+    HeadsArgs ha{};
+    ha.n_frames = L.n; ha.w = L.w; ha.h = L.h; ha.max_heads = q.max_heads;
+    memcpy(ha.k, L.K, sizeof ha.k);
+    ha.cams = L.cams; ha.off4 = L.p->dev.off4; ha.rough_cell = L.p->dev.rough_cell;
+    set_hits(ha, ws, L.f0);
+    ha.hit_win = ws.hit_win.get() + L.hoff; ha.pos_grid = L.pos_grid;
+    const size_t hk = (size_t)L.f0 * DH_MAX_HEADS;
+    ha.pick = ws.hd_pick.get() + hk; ha.nseed = ws.hd_nseed.get() + L.f0; ha.mom = ws.hd_mom.get() + hk;
+    ha.nx = L.g.nx; ha.step = L.step; ha.lw = L.lw; ha.lh = L.lh; ha.radius = q.radius; ha.n_heads = q.n_heads; ha.heads = q.heads;
+    ha.hpose = ws.hd_pose.get() + hk; ha.acc = ws.hd_acc.get() + hk; ha.bits = ws.hd_bits.get() + hk * ws.sup_words; ha.bit_words = ws.sup_words;
+    ha.hsup = ws.hd_sup.get() + hk; ha.hmask = ws.hd_mask.get() + L.hoff; ha.rgrid = ws.hd_rgrid.get() + hk * DH_GRID3;
+    ClusterArgs ca = cluster_args(L);
+    ca.rot_grid = ha.rgrid; ca.out = ws.hd_pose.get() + hk; ca.hd_nseed = ha.nseed; ca.hd_mom = ha.mom; ca.hd_rgrid = ha.rgrid; ca.hd_mask = ha.hmask;
+    Range r(L.o.profile, "dh:heads");
+    HIP_TRY(dh_launch_heads_seeds(ha, L.s));
+    HIP_TRY(dh_launch_heads_moments(ha, L.s));
+    ca.hd_which = 0;
+    HIP_TRY(dh_launch_cluster_heads(ca, q.max_heads, L.s));
+    HIP_TRY(dh_launch_heads_support(ha, L.s));
+    ca.hd_which = 1;
+    HIP_TRY(dh_launch_cluster_heads(ca, q.max_heads, L.s));
+    HIP_TRY(dh_launch_heads_finish(ha, L.s));
+    return DH_OK;
+}
+// k_support: each pose's vote support, after k_cluster.
+static int enqueue_support(const Launch &L) {
+    const Workspace &ws = L.ws;
+    SupportArgs sa{};
+    sa.n_frames = L.n; sa.nx = L.g.nx; sa.step = L.step; sa.lw = L.lw; sa.lh = L.lh;
+    sa.radius = L.q.radius; sa.poses = L.q.out; sa.out = L.q.support;
+    sa.hits = ws.hits.get() + L.hoff; sa.hit_box = ws.hit_box.get() + L.hoff; sa.hit_win = ws.hit_win.get() + L.hoff;
+    sa.hit_count = L.hit_count; sa.hits_cap = ws.hits_cap; sa.off4 = L.p->dev.off4;
+    sa.acc = ws.sup_acc.get() + L.f0; sa.bits = ws.sup_bits.get() + (size_t)L.f0 * ws.sup_words; sa.bit_words = ws.sup_words;
+    { Range r(L.o.profile, "dh:support"); HIP_TRY(dh_launch_support(sa, L.s)); }
+    return DH_OK;
+}
+
+// Enqueue the kernels (k_boxsum / k_pixflags, k_traverse, k_emit, k_vote, then [k_region,] k_cluster [, k_support] or the heads
+// kernels) for frames [f0, f0 + n) of the resident slice sl on stream s: sl.at(f0) gives their inputs and outputs, f0 their place
+// in the workspace.  This is the sequence and the profiling events; each stage above fills its own argument blocks.
+static int enqueue_range(dh_predictor *p, const BatchReq &sl, int f0, int n, hipStream_t s, const EnqueueOpts &o) {
+    Launch L{p, sl.at(f0), f0, n, s, o};
+    if (L.q.cams.c) memcpy(L.kinv, L.q.cams.c->host[L.q.cams.c0].kinv, sizeof L.kinv);
+    else dh_mat3_inv_f32_(L.K, L.kinv);   // cached in a RefCell by the reference (types.rs:436-441)
+    if (L.use_list) p->ws.list_chunks = std::max(p->ws.list_chunks, o.chunk + 1);
+    const bool windows = L.g.npatch > 0;
+    char batch_name[48];
+    snprintf(batch_name, sizeof batch_name, "dh:batch n=%d %dx%d", n, L.w, L.h);
+    Range batch_range(o.profile, batch_name);
+    if (o.profile) HIP_TRY(hipEventRecord(p->ev[0], s));
+    if (windows) TRY(enqueue_flags(L));
+    if (L.use_list) TRY(enqueue_tile_list(L));
+    if (o.profile) HIP_TRY(hipEventRecord(p->ev[4], s));
+    bool gated = false;
+    if (windows) TRY(enqueue_traverse(L, &gated));
+    if (o.profile) HIP_TRY(hipEventRecord(p->ev[5], s));
+    if (windows && !o.traverse_only) TRY(enqueue_emit(L, gated));
+    if (o.profile) HIP_TRY(hipEventRecord(p->ev[1], s));
+    if (o.traverse_only) return DH_OK;
+    TRY(enqueue_vote(L));
+    if (o.profile) HIP_TRY(hipEventRecord(p->ev[2], s));
+    if (L.q.heads) TRY(enqueue_heads(L));
+    else {
+        TRY(enqueue_cluster(L));
+        if (L.q.support) TRY(enqueue_support(L));
     }
     if (o.profile) { HIP_TRY(hipEventRecord(p->ev[3], s)); p->ev_valid = true; }
     return DH_OK;
@@ -2079,7 +2079,7 @@ static int debug_window_totals_(dh_predictor *p, uint32_t *out) {
         HIP_TRY(hipMemset(tot.get(), 0, bytes));
         EmitArgs ea{};
         ea.n_frames = p->last_n; ea.px = g.px; ea.py = g.py; ea.tiles = g.tiles_x * g.tiles_y; ea.f = p->dev;
-        ea.win_count = ws.win_count(0); ea.win_leaf = ws.win_leaf.get(); ea.leaf_ls = ws.leaf_ls; ea.win_cap = g.win_cap;
+        set_windows(ea, ws, 0, p->n_trees);
         HIP_TRY(dh_launch_window_totals(ea, tot.get(), nullptr));
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(out, tot.get(), bytes, hipMemcpyDeviceToHost));
@@ -2145,7 +2145,7 @@ static int debug_votes_(dh_predictor *p, int frame, int which, int32_t *out, siz
         if (cap * 4 > ws.dbg_votes.cap()) TRY(ws.dbg_votes.alloc(cap * 4));
         HIP_TRY(hipMemset(ws.dbg_vcount.get(), 0, 4));
         VotesDumpArgs a{};
-        a.frame = frame; a.which = which; a.f = p->dev; a.hits = ws.hits.get(); a.hit_box = ws.hit_box.get(); a.hit_rot = ws.hit_rot.get(); a.hit_count = ws.hit_count(0); a.hits_cap = ws.hits_cap;
+        a.frame = frame; a.which = which; a.f = p->dev; set_hits(a, ws, 0);
         a.out = ws.dbg_votes.get(); a.cap = (uint32_t)cap; a.count = ws.dbg_vcount.get();
         HIP_TRY(dh_launch_votes_dump(a, nullptr));
         HIP_TRY(hipDeviceSynchronize());

@@ -383,7 +383,7 @@ int dh_tile_shifts_(const Geom &g, int step, int blk_shift, const Knobs &k, Tile
         t.nsx = slack_x / t.gx + 1; t.nsy = slack_y + 1;
         if (t.nsx * t.nsy == 1) return DH_OK;
     }
-    const int mask_blocks = (g.box_rows + (1 << blk_shift) - 1) >> blk_shift;
+    const int mask_blocks = dh_mask_blocks_(g.box_rows, blk_shift);
     const bool fits = dh_tile_shift_lds_words(mask_blocks, g.box_parts, g.box_parts * (g.box_ow / 4), t.nsx * t.nsy) <= DH_TILE_SHIFT_LDS_WORDS;
     if (!fits && k.tile_shift_mode == 2)
         return dh_fail_(DH_EINVAL, "DH_TILE_SHIFT=%d,%d: frames of %dx%d are too large for the shifted tile lists", k.tile_shift_x, k.tile_shift_y, g.w, g.h);
@@ -438,6 +438,26 @@ int dh_box_bands_(int n, int parts, int rows, int blk, int rh, int wg_slots, int
     }
     if (oh_out) *oh_out = best_oh;
     return best_bands;
+}
+
+BoxPlan dh_box_plan_(int n, const Geom &g, int rh, int blk_shift, const Knobs &k) {
+    BoxPlan b;
+    b.oh = g.box_oh; b.bands = g.box_bands;
+    b.mask_blocks = dh_mask_blocks_(g.box_rows, blk_shift);
+    if (!k.box_no_ring && rh >= 2 && rh <= 29) {
+        const int blk = 1 << blk_shift;
+        const size_t lds_wg = (size_t)4 * (rh - 1) * 512 + (size_t)4 * (256 + 96 + 8) * 4;
+        const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(6, ((size_t)160 * 1024) / lds_wg));
+        dh_box_bands_(n, g.box_parts, g.box_rows, blk, rh, wg_per_cu * 256, &b.oh);
+        if (k.box_bands > 0) {                            // DH_BOX_BANDS: experiments
+            const int bands = std::min(k.box_bands, std::max(1, b.mask_blocks));
+            b.oh = ((g.box_rows + bands - 1) / bands + blk - 1) & ~(blk - 1);
+        }
+        b.bands = (g.box_rows + b.oh - 1) / b.oh;         // whole mask blocks per band (BoxArgs::blk_mask)
+        b.ring = 1;
+    }
+    b.blocks_per_frame = (g.box_parts * b.bands + 3) / 4;
+    return b;
 }
 
 void dh_mat3_inv_f32_(const float m[9], float o[9]) {

@@ -160,6 +160,27 @@ static const int kBoxSpan = 256, kBoxMaxRect = 96;   // image columns one k_boxs
 // and the number of bands.  A workgroup is 4 waves = 4 (part, band) units and the chip holds `wg_slots` of them (3 per CU: the
 // ring's LDS); a wave marches its band + rh - 1 rows.  Picks the band count with the smallest (march) x (rounds of workgroups).
 int dh_box_bands_(int n, int parts, int rows, int blk, int rh, int wg_slots, int *oh);
+// Mask blocks (of 1 << blk_shift rows) that cover `rows` rows: BoxArgs::mask_blocks, TileShiftArgs::mask_blocks.
+static inline int dh_mask_blocks_(int rows, int blk_shift) { return (rows + (1 << blk_shift) - 1) >> blk_shift; }
+// How k_boxsum runs a batch of n frames of g with rectangles rh rows high, in a workspace whose mask blocks are 1 << blk_shift rows.
+// ring: the LDS-ring instance (each pixel read once) wherever its ring fits, 2 <= rh <= 29: a workgroup's 4 waves keep rh - 1 packed
+// rows of 512 B each, 4 x 28 x 512 B + the prefix rows < 64 KB.  Its bands (oh rows each, whole mask blocks) come from dh_box_bands_
+// for the workgroups the chip holds at once: per CU what the ring's LDS, 4 (rh - 1) 512 + 4 (256 + 96 + 8) 4 bytes per workgroup,
+// leaves of 160 KB (52 864 B at rh = 24: three), at most the six that 76 VGPRs allow; 256 CUs.  (With few frames the band is short --
+// a wave's march of band + rh - 1 rows IS the kernel's duration there: a single-frame workspace has 8-row blocks, 31 instead of 55
+// rows at rh = 24; one 320 x 240 frame 86 -> 79 us with 16-row bands, 76 with 8.)  DH_BOX_BANDS (experiments) replaces the band
+// count, clamped to one mask block per band at least.  Without the ring (other rh, DH_BOX_NO_RING) the geometry's own bands,
+// g.box_oh x g.box_bands.  blocks_per_frame = ceil(parts * bands / 4) workgroups.  (Hidden: the library's dynamic symbols stay as they were.)
+struct BoxPlan { int ring = 0, oh = 0, bands = 0, mask_blocks = 0, blocks_per_frame = 0; };
+__attribute__((visibility("hidden"))) BoxPlan dh_box_plan_(int n, const Geom &g, int rh, int blk_shift, const Knobs &k);
+// Whether a launch of n frames of `tiles` tiles each hands k_traverse the flagged tiles as compact lists (k_tile_list /
+// k_tile_shift), which moves the workgroups of empty tiles behind the flagged ones.  Not with a requested leaf or flag output or the
+// taps on (outputs_or_taps): there every tile position keeps its workgroup, those of empty tiles write the "background".  Not for a
+// launch whose tiles all fit the chip's 512 workgroup slots at once, n * tiles <= 512: it gains nothing from the order and saves
+// the dispatch, 3 us of a single frame's 96.  Not without lists in the workspace (DH_NO_TILE_LIST) or without windows.
+static inline bool dh_use_tile_list_(bool has_lists, int npatch, bool outputs_or_taps, int n, int tiles) {
+    return has_lists && npatch > 0 && !outputs_or_taps && (long)n * tiles > 512;
+}
 
 // Whether k_traverse's tiles run the probability gate themselves and list only the windows that pass it (its gated tail; k_emit then
 // takes its pre-gated instances).  All of: the uniform path with the walk table; every tile walks in ONE lock-step pass,

@@ -2,7 +2,7 @@
 // sanitizers: built by tests/test_host_sanitize.py with g++ -fsanitize=address,undefined and once more with
 // -fsanitize=thread.  Prints "host_check ok" and exits 0; any check that fails prints its line and exits 1.
 // Covers: forest validation (good / every refused kind), patch grids, tile selection across geometries (with the invariants
-// the kernels rely on), the shifts a frame's tile grid may take (dh_tile_shifts_), the per-batch counter block's layout, upload chunk plans, where k_vote's approximate cell quotient
+// the kernels rely on), the shifts a frame's tile grid may take (dh_tile_shifts_), k_boxsum's launch plan and the tile-list rule (dh_box_plan_, dh_use_tile_list_), the per-batch counter block's layout, upload chunk plans, where k_vote's approximate cell quotient
 // is allowed, the run-length payload scanner / packer on well-formed, redundant and malformed payloads (incl. every
 // truncation point of a payload), the host BIWI parsers, knob parsing, the exception guard, and dh_parallel_for_ / the
 // thread-local error slots under concurrency.
@@ -549,6 +549,68 @@ static void test_tile_shifts() {
     CHECK(dh_read_knobs_().tile_shift_mode == 0);
 }
 
+// dh_box_plan_ and dh_use_tile_list_: the launch rules of k_boxsum and of the tile lists.  The expected values are worked out from the
+// rules' prose (dh_host.h; the cost of a band count: dh_box_bands_ in dh_host.cpp), not from their code.
+// Frames of 640 x 480 with 24-row rectangles have 457 rows in 3 parts.  In 32-row blocks the cuts into whole blocks are
+//     bands x rows    1 x 480   2 x 256   3 x 160   4 x 128   5 x 96   8 x 64   15 x 32
+//     workgroups        1         2         3         3         4        6        12      per frame: ceil(3 bands / 4)
+// and a cut costs (rows + (rh - 1) / 2) x rounds, rounds = 1 while the n frames' workgroups fit the chip's slots, else
+// r + (ceil(r) - r) / 2 for r = workgroups / slots.
+static Geom box_geom(int parts, int rows) {
+    Geom g;
+    g.uniform = true; g.box_parts = parts; g.box_rows = rows; g.box_oh = 64; g.box_bands = (rows + 63) / 64;   // (64-row bands: DH_BOX_BAND's default)
+    return g;
+}
+static bool plan_is(const BoxPlan &b, int ring, int oh, int bands, int mask_blocks, int blocks_per_frame) {
+    return b.ring == ring && b.oh == oh && b.bands == bands && b.mask_blocks == mask_blocks && b.blocks_per_frame == blocks_per_frame;
+}
+static void test_launch_rules() {
+    const Geom g = box_geom(3, 457);
+    const Knobs k0;
+    // rh = 24: 4 x 23 x 512 + 4 x 360 x 4 = 47 104 + 5 760 = 52 864 B of LDS per workgroup, floor(163 840 / 52 864) = 3 per CU, 768 slots
+    // (what the dh_box_bands_ literals pass).  256 frames: 491.5, 267.5, 171.5, 139.5 (768 workgroups, one round), 107.5 x 1.67,
+    // 75.5 x 2, 43.5 x 4 -- four bands of 128 rows, 15 mask blocks, 3 workgroups per frame
+    CHECK(plan_is(dh_box_plan_(256, g, 24, 5, k0), 1, 128, 4, 15, 3));
+    // rh = 2: 2 048 + 5 760 = 7 808 B would allow 20 per CU; the cap of six gives 1 536 slots.  256 frames: .., 96.5, 64.5 (1 536
+    // workgroups, one round), 32.5 x 2 = 65 -- eight bands of 64.  (Uncapped, 5 120 slots would take the 15 bands; five per CU, 1 280
+    // slots, 5 x 96; three per CU 4 x 128.)
+    CHECK(plan_is(dh_box_plan_(256, g, 2, 5, k0), 1, 64, 8, 15, 6));
+    // rh = 29, the last ring size: 57 344 + 5 760 = 63 104 B, 2 per CU, 512 slots.  256 frames, (rows + 14) x rounds: 494, 270,
+    // 174 x 1.75, 142 x 1.75 = 248.5, 110 x 2 = 220, 78 x 3 = 234, 46 x 6 -- five bands of 96 (one or three per CU would take 4 x 128)
+    CHECK(plan_is(dh_box_plan_(256, g, 29, 5, k0), 1, 96, 5, 15, 4));
+    // no ring beyond those sizes or under DH_BOX_NO_RING: the geometry's own bands (8 x 64: 6 workgroups per frame), DH_BOX_BANDS ignored
+    CHECK(plan_is(dh_box_plan_(256, g, 30, 5, k0), 0, 64, 8, 15, 6));
+    CHECK(plan_is(dh_box_plan_(256, g, 1, 5, k0), 0, 64, 8, 15, 6));
+    { Knobs k; k.box_no_ring = true; CHECK(plan_is(dh_box_plan_(256, g, 24, 5, k), 0, 64, 8, 15, 6)); }
+    { Knobs k; k.box_bands = 3; CHECK(plan_is(dh_box_plan_(256, g, 30, 5, k), 0, 64, 8, 15, 6)); }
+    // DH_BOX_BANDS: the band count asked for, at most one per mask block, then whole blocks per band -- 7 bands would be 66 rows
+    // each, 96 in whole blocks, which makes 5; 99 is clamped to the 15 blocks
+    { Knobs k; k.box_bands = 1; CHECK(plan_is(dh_box_plan_(256, g, 24, 5, k), 1, 480, 1, 15, 1)); }
+    { Knobs k; k.box_bands = 3; CHECK(plan_is(dh_box_plan_(256, g, 24, 5, k), 1, 160, 3, 15, 3)); }
+    { Knobs k; k.box_bands = 7; CHECK(plan_is(dh_box_plan_(256, g, 24, 5, k), 1, 96, 5, 15, 4)); }
+    { Knobs k; k.box_bands = 99; CHECK(plan_is(dh_box_plan_(256, g, 24, 5, k), 1, 32, 15, 15, 12)); }
+    // a single-frame workspace (8-row blocks): one 320 x 240 frame takes the shortest bands, 28 of 8 rows over 217 rows
+    CHECK(plan_is(dh_box_plan_(1, box_geom(1, 217), 24, 3, k0), 1, 8, 28, 28, 7));
+    // whole mask blocks cover every row exactly once, whatever the batch: bands of whole blocks, the last one started, none beyond it
+    for (int n : {1, 2, 7, 64, 100, 256, 300, 512, 4096})
+        for (int rows : {1, 5, 31, 32, 33, 217, 457, 1000})
+            for (int sh : {3, 4, 5})
+                for (int parts : {1, 3, 5})
+                    for (int rh : {2, 24, 29, 30}) {
+                        const int blk = 1 << sh;
+                        const BoxPlan b = dh_box_plan_(n, box_geom(parts, rows), rh, sh, k0);
+                        CHECK(b.ring == (rh <= 29) && b.mask_blocks == dh_mask_blocks_(rows, sh) && (long)b.mask_blocks * blk >= rows && (long)(b.mask_blocks - 1) * blk < rows);
+                        CHECK(b.bands >= 1 && b.oh >= blk && b.oh % blk == 0 && (long)b.bands * b.oh >= rows && (long)(b.bands - 1) * b.oh < rows);
+                        CHECK(b.blocks_per_frame * 4 >= parts * b.bands && (b.blocks_per_frame - 1) * 4 < parts * b.bands);
+                    }
+    // tile lists: the bench grid of 7 x 6 tiles fits the 512 workgroup slots with 12 frames (504) and not with 13 (546); exactly 512 still fits
+    CHECK(!dh_use_tile_list_(true, 2400, false, 12, 42) && dh_use_tile_list_(true, 2400, false, 13, 42));
+    CHECK(!dh_use_tile_list_(true, 2400, false, 64, 8) && dh_use_tile_list_(true, 2400, false, 57, 9));
+    CHECK(!dh_use_tile_list_(true, 2400, true, 13, 42) && !dh_use_tile_list_(true, 2400, true, 4096, 42));     // a leaf or flag output, the taps
+    CHECK(!dh_use_tile_list_(true, 0, false, 4096, 42) && !dh_use_tile_list_(false, 2400, false, 4096, 42));   // no windows; no lists in the workspace
+    CHECK(dh_use_tile_list_(true, 1, false, 1 << 20, 1 << 12));                                                // (the product is taken in 64 bits)
+}
+
 static void test_guard_and_threads() {
     CHECK(dh_guard_("x", []() -> int { throw std::bad_alloc(); }) == DH_ENOMEM && strstr(dh_err_get_(), "out of host memory"));
     CHECK(dh_guard_("x", []() -> int { throw std::runtime_error("boom"); }) == DH_EINVAL && strstr(dh_err_get_(), "boom"));
@@ -586,6 +648,7 @@ int main() {
     test_tables_and_knobs();
     test_counter_layout();
     test_tile_shifts();
+    test_launch_rules();
     test_guard_and_threads();
     if (g_fail) { fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     printf("host_check ok\n");
