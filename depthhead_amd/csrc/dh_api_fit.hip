@@ -1,7 +1,7 @@
 // dh_api_fit.hip -- the fit family's runtime: models, view tables, bases and subject sets, the fitter and every call it runs (fit,
 // multi-view fit, shape, surface, identify, calibration) in its host and _device forms.  Kernels: k_fit.hip, k_fit_views.hip,
 // k_fit_shape.hip, k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip, k_ident.hip, k_ident_views.hip.  Shares
-// dh_runtime.h with every runtime unit and dh_runtime_fit.h with the fit trackers in dh_api.hip.
+// dh_runtime.h with every runtime unit and dh_runtime_fit.h with the fit trackers in dh_api_fit_track.hip.
 #include <math.h>
 #include <string.h>
 

@@ -1,0 +1,483 @@
+// dh_api_fit_track.hip -- the fit trackers' runtime: what both share (the angle table, FitTrackerCore, the creation check, the
+// host form of a step), the camera fit tracker and the rig fit tracker (section 22) in their host and
+// _device forms.  Kernels: k_fit_track.hip, k_rig_fit_track.hip, and the _sched launches of k_fit.hip and k_fit_views.hip.  Shares
+// dh_runtime.h with every runtime unit, dh_runtime_fit.h with the fit family (dh_api_fit.hip), and dh_runtime_track.h with the
+// trackers in dh_api.hip, which also defines the three functions of that header a whole step calls.
+#include <math.h>
+#include <string.h>
+
+#include "dh_runtime.h"
+#include "dh_fit.h"
+#include "dh_runtime_fit.h"
+#include "dh_runtime_track.h"
+
+// ------------------------------------------------------------------ carrying fitted poses across steps
+// The angle table of the header: computed once, by libm, and the only cosines and sines of the feature.
+struct FitTrackAngles {
+    double v[DH_FIT_TRACK_ANGLES][2];
+    FitTrackAngles() {
+        for (int i = 0; i < DH_FIT_TRACK_ANGLES; ++i) {
+            const double a = (double)(i - 60) / 60.0 * 3.14159;
+            v[i][0] = cos(a); v[i][1] = sin(a);
+        }
+    }
+};
+static const FitTrackAngles &fit_track_angles() {
+    static const FitTrackAngles tab;
+    return tab;
+}
+static int fit_tracker_angles_(double out[DH_FIT_TRACK_ANGLES][2]) {
+    if (!out) return fail(DH_EINVAL, "dh_fit_tracker_angles: NULL argument");
+    memcpy(out, fit_track_angles().v, sizeof fit_track_angles().v);
+    return DH_OK;
+}
+static int fit_track_params_default_(dh_fit_track_params *p) {
+    if (!p) return fail(DH_EINVAL, "dh_fit_track_params_default: NULL argument");
+    memset(p, 0, sizeof *p);
+    p->iterations_tracked = 6; p->keep_points = 30;
+    p->rms_max = 5.0; p->max_jump = 150.0;
+    p->conf_num = 1; p->conf_den = 50;
+    p->min_windows = 1; p->max_coast = 3;
+    return DH_OK;
+}
+
+// What the camera's fit tracker (below) and the rig's (section 22) share: the model and what the acceptance rule reads, the
+// tables every step reads, and for the host forms the tracker's own stream and the frames staged on it (they come with the first
+// host step, for its frame size).  A tracker T adds its params (T::prm), its state, the buffers between its three launches and
+// the staging buffers of its host forms (T::records among them); every device buffer of a step is allocated at creation.
+struct FitTrackerCore : TrackerCore {
+    const dh_fit_model *model = nullptr;
+    float scale = 1.0f;
+    uint32_t flags = 0;
+    int64_t rms_lim = 0;
+    double jump2 = 0.0;
+    Buf<double> angles;                  // [120][2]
+    Buf<FitModel> models;                // [1]
+    Buf<uint32_t> sched, seed;           // [units][2], [units]: a unit is what one workgroup of the fit takes (a camera, a slot)
+    hipStream_t s = nullptr;             // host forms
+    Buf<uint16_t> frames;
+    ~FitTrackerCore() { if (s) (void)hipStreamDestroy(s); }
+    // The tail of a tracker's allocation: what the params come to, the shared tables for `units` units, and the stream.
+    int init_fit(const dh_fit_model *m, float scale_, uint32_t flags_, double rms_max, double max_jump, size_t units) {
+        model = m; scale = scale_; flags = flags_;
+        rms_lim = (int64_t)(rms_max * rms_max * 1048576.0);
+        jump2 = max_jump * max_jump;
+        TRY(angles.alloc(DH_FIT_TRACK_ANGLES * 2));
+        TRY(models.alloc(1));
+        TRY(sched.alloc(units * 2)); TRY(seed.alloc(units));
+        const FitModel fm{m->pts.get(), m->nrm.get(), m->n, 0};
+        HIP_TRY(hipMemcpy(models.get(), &fm, sizeof fm, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(angles.get(), fit_track_angles().v, sizeof fit_track_angles().v, hipMemcpyHostToDevice));
+        return hip_step(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
+    }
+};
+// The refusals of a fit tracker's creation in the header's order.  P: dh_fit_track_params or dh_rig_fit_track_params; own() gives
+// the refusals of the fields that only P has, tables() those of the tables and of the model beside them (NULL, device).
+template <typename P, typename Own, typename Tables>
+static int fit_tracker_create_check(const P &prm, float scale, uint32_t flags, const dh_fit_model *m, Own own, Tables tables, const char *who) {
+    if (flags & ~DH_FIT_TRACK_MOTION) return fail(DH_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    if (!std::isfinite(scale)) return fail(DH_EINVAL, "%s: scale is not finite", who);
+    if (prm.iterations_tracked > 64) return fail(DH_EINVAL, "%s: iterations_tracked %u above 64", who, prm.iterations_tracked);
+    if (!(prm.rms_max > 0.0 && prm.rms_max <= 4096.0)) return fail(DH_EINVAL, "%s: rms_max = %g outside (0, 4096]", who, prm.rms_max);
+    if (!(prm.max_jump > 0.0 && prm.max_jump <= 4096.0)) return fail(DH_EINVAL, "%s: max_jump = %g outside (0, 4096]", who, prm.max_jump);
+    TRY(own());
+    if (prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
+    TRY(tables());
+    if (!m) return fail(DH_EINVAL, "%s: NULL model", who);     // (tables() refuses it in its place: m is never read unchecked)
+    const double extent = fabs((double)scale) * m->radius;
+    if (extent > DH_FIT_MAX_EXTENT) return fail(DH_EINVAL, "%s: the model spans %g mm from its origin (limit %g)", who, extent, DH_FIT_MAX_EXTENT);
+    return DH_OK;
+}
+// (a step may still run on any stream of the device)
+template <typename T>
+static int destroy_fit_tracker(T *t) {
+    if (t) {
+        DeviceGuard guard(t->cams->device);
+        (void)hipDeviceSynchronize();
+    }
+    return destroy_tracker(t);
+}
+// The host form of a step of fit tracker t, synchronous on its own stream: the frames and the present bytes are staged,
+// upload(s) stages the caller's other inputs, step(frames, present, s) enqueues the step on the staged arrays (present: the
+// staged bytes or NULL), download(s) copies back what the step reports beside its records, and the n_rec records follow.
+template <typename T, typename Up, typename Step, typename Down, typename Rec>
+static int fit_tracker_host(T *t, const uint16_t *frames, int w, int h, const uint8_t *present, Up upload, Step step, Down download, Rec *records,
+                            size_t n_rec) {
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    const size_t n = (size_t)t->n, n_px = n * w * h;
+    if (t->frames.cap() < n_px) TRY(t->frames.alloc(n_px));       // (host steps are synchronous: nothing reads the old buffer)
+    hipStream_t s = t->s;
+    HIP_TRY(hipMemcpyAsync(t->frames.get(), frames, n_px * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    if (present) HIP_TRY(hipMemcpyAsync(t->present.get(), present, n, hipMemcpyHostToDevice, s));
+    TRY(upload(s));
+    const int rc = step(t->frames.get(), present ? t->present.get() : nullptr, s);
+    if (rc != DH_OK) { (void)hipStreamSynchronize(s); return rc; }
+    TRY(download(s));
+    HIP_TRY(hipMemcpyAsync(records, t->records.get(), n_rec * sizeof(Rec), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DH_OK;
+}
+
+struct dh_fit_tracker : FitTrackerCore {
+    dh_fit_track_params prm{};
+    Buf<dh_fit_track_state> state;       // [n]
+    Buf<dh_render_instance> start, fit_out;
+    Buf<dh_fit_record> fit_rec;
+    Buf<dh_pose> poses;                  // host forms
+    Buf<dh_support> support;
+    Buf<dh_fit_track_record> records;
+    int clear(size_t c0, size_t m, hipStream_t st) {
+        HIP_TRY(hipMemsetAsync(state.get() + c0, 0, m * sizeof(dh_fit_track_state), st));
+        return DH_OK;
+    }
+};
+static int fit_tracker_create_(const dh_cameras *c, const dh_fit_model *m, float scale, uint32_t flags, const dh_fit_track_params *params,
+                               dh_fit_tracker **out) {
+    const char *who = "dh_fit_tracker_create";
+    if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
+    *out = nullptr;
+    dh_fit_track_params prm;
+    (void)fit_track_params_default_(&prm);
+    if (params) prm = *params;
+    TRY(fit_tracker_create_check(prm, scale, flags, m, [&]() -> int {
+        if (prm.conf_den == 0 || prm.conf_num > prm.conf_den)
+            return fail(DH_EINVAL, "%s: confidence %u / %u, expected a fraction in [0, 1]", who, prm.conf_num, prm.conf_den);
+        return DH_OK;
+    }, [&]() -> int {
+        if (!c) return fail(DH_EINVAL, "%s: NULL camera table", who);
+        if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
+        if (m->device != c->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the camera table on %d", who, m->device, c->device);
+        return DH_OK;
+    }, who));
+    return create_tracker(c, out, [&](dh_fit_tracker &t, size_t n) -> int {
+        t.prm = prm;
+        TRY(t.state.alloc(n));
+        TRY(t.start.alloc(n)); TRY(t.fit_out.alloc(n)); TRY(t.fit_rec.alloc(n));
+        TRY(t.poses.alloc(n)); TRY(t.support.alloc(n)); TRY(t.records.alloc(n));
+        return t.init_fit(m, scale, flags, prm.rms_max, prm.max_jump, n);
+    });
+}
+static int fit_tracker_destroy_(dh_fit_tracker *t) { return destroy_fit_tracker(t); }
+static int fit_tracker_reset_(dh_fit_tracker *t, int camera, void *stream) { return reset_tracker(t, camera, stream, "dh_fit_tracker_reset"); }
+static int fit_tracker_state_(dh_fit_tracker *t, dh_fit_track_state *states) {
+    if (t && !states) return fail(DH_EINVAL, "dh_fit_tracker_state: NULL argument");
+    return read_tracker(t, "dh_fit_tracker_state", [&](size_t n) -> int {
+        HIP_TRY(hipMemcpy(states, t->state.get(), n * sizeof(dh_fit_track_state), hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
+}
+// The refusals of a step that are the tracker's own, before anything is launched.
+static int fit_track_check(const dh_fit_tracker *t, const void *frames, int w, int h, const void *poses, const void *support,
+                           const dh_fit_params *in, const void *records, dh_fit_params *prm, const char *who) {
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
+    if (!frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!poses || !support) return fail(DH_EINVAL, "%s: NULL poses or support", who);
+    if (!records) return fail(DH_EINVAL, "%s: NULL records", who);
+    TRY(check_frame_size(w, h, who));
+    return fit_params_check(in, prm, who);
+}
+// Steps 0 - 6 for every camera, on device arrays and stream s (arguments checked, device selected): three launches.
+static int fit_track_enqueue(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
+                             const dh_support *support, const dh_fit_params &prm, dh_fit_track_record *records, hipStream_t s) {
+    FitTrackArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = t->n; a.flags = t->flags; a.scale = t->scale; a.prm = t->prm; a.rms_lim = t->rms_lim; a.jump2 = t->jump2;
+    a.coarse = prm.coarse_iterations; a.full = prm.iterations;
+    a.angles = t->angles.get(); a.present = present; a.poses = poses; a.support = support; a.state = t->state.get();
+    a.start = t->start.get(); a.sched = t->sched.get(); a.seed = t->seed.get();
+    a.fit_out = t->fit_out.get(); a.fit_rec = t->fit_rec.get(); a.records = records;
+    FitSchedArgs f;
+    memset(&f, 0, sizeof f);
+    f.f.frames = frames; f.f.n = t->n; f.f.w = w; f.f.h = h;
+    f.f.cams = t->cams->dev.get(); f.f.models = t->models.get(); f.f.inst = t->start.get(); f.f.n_inst = (uint32_t)t->n;
+    fit_args_params(f.f, prm);                             // (k_fit_sched reads coarse and full per instance from sched)
+    f.f.out = t->fit_out.get(); f.f.rec = t->fit_rec.get();
+    f.sched = t->sched.get(); f.seed = t->seed.get();
+    TRY(hip_step(dh_launch_fit_track_seed(a, s), "k_fit_track_seed"));
+    TRY(hip_step(dh_launch_fit_sched(f, s), "k_fit_sched"));
+    TRY(hip_step(dh_launch_fit_track_update(a, s), "k_fit_track_update"));
+    return DH_OK;
+}
+static int fit_tracker_step_poses_device_(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
+                                          const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records, void *stream) {
+    dh_fit_params prm;
+    TRY(fit_track_check(t, frames, w, h, poses, support, fit_params, records, &prm, "dh_fit_tracker_step_poses_device"));
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return fit_track_enqueue(t, frames, w, h, present, poses, support, prm, records, (hipStream_t)stream);
+}
+static int fit_tracker_step_device_(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
+                                    const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records,
+                                    void *stream) {
+    const char *who = "dh_fit_tracker_step_device";
+    dh_fit_params prm;
+    if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
+    TRY(fit_track_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
+    TRY(dh_predict_batch_cameras_support_device_(p, frames, t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, poses_out, support_out, stream));
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return fit_track_enqueue(t, frames, w, h, present, poses_out, support_out, prm, records, (hipStream_t)stream);
+}
+// The host forms: everything staged through the tracker's buffers on its own stream; synchronous.  p NULL: the core step on
+// the caller's poses and support; else the prediction first, its poses and support copied back too.
+static int fit_track_host(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
+                          const dh_fit_params &prm, dh_pose *poses, dh_support *support, dh_fit_track_record *records) {
+    const size_t n = (size_t)t->n;
+    return fit_tracker_host(t, frames, w, h, present, [&](hipStream_t s) -> int {
+        if (p) return DH_OK;
+        HIP_TRY(hipMemcpyAsync(t->poses.get(), poses, n * sizeof(dh_pose), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(t->support.get(), support, n * sizeof(dh_support), hipMemcpyHostToDevice, s));
+        return DH_OK;
+    }, [&](const uint16_t *fr, const uint8_t *pr, hipStream_t s) -> int {
+        if (p) TRY(dh_predict_batch_cameras_support_device_(p, fr, t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, t->poses.get(),
+                                                         t->support.get(), s));
+        return fit_track_enqueue(t, fr, w, h, pr, t->poses.get(), t->support.get(), prm, t->records.get(), s);
+    }, [&](hipStream_t s) -> int {
+        if (!p) return DH_OK;
+        HIP_TRY(hipMemcpyAsync(poses, t->poses.get(), n * sizeof(dh_pose), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(support, t->support.get(), n * sizeof(dh_support), hipMemcpyDeviceToHost, s));
+        return DH_OK;
+    }, records, n);
+}
+static int fit_tracker_step_poses_(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
+                                   const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records) {
+    dh_fit_params prm;
+    TRY(fit_track_check(t, frames, w, h, poses, support, fit_params, records, &prm, "dh_fit_tracker_step_poses"));
+    return fit_track_host(nullptr, t, frames, w, h, present, 0, prm, const_cast<dh_pose *>(poses), const_cast<dh_support *>(support), records);
+}
+static int fit_tracker_step_(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
+                             const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records) {
+    const char *who = "dh_fit_tracker_step";
+    dh_fit_params prm;
+    if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
+    TRY(fit_track_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
+    if (radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u (a negative int?); expected 0 .. 2^31 - 1", who, radius);
+    if (t->cams->device != dh_predictor_device_(p))
+        return fail(DH_EINVAL, "%s: camera table on device %d, predictor on device %d", who, t->cams->device, dh_predictor_device_(p));
+    return fit_track_host(p, t, frames, w, h, present, radius, prm, poses_out, support_out, records);
+}
+
+// ------------------------------------------------------------------ carrying each rig person's fitted world pose
+static int rig_fit_track_params_default_(dh_rig_fit_track_params *p) {
+    if (!p) return fail(DH_EINVAL, "dh_rig_fit_track_params_default: NULL argument");
+    memset(p, 0, sizeof *p);
+    p->iterations_tracked = 6; p->keep_points = 30;
+    p->rms_max = 5.0; p->max_jump = 150.0;
+    p->max_coast = 3; p->max_misses = DH_TRACK_MAX_MISSES;
+    return DH_OK;
+}
+
+// A FitTrackerCore (section 19) whose state is per rig (DH_RIG_MAX_TRACKS entries each) and whose units are the slots; every
+// device buffer of a step is sized by the rig table and allocated at creation.
+struct dh_rig_fit_tracker : FitTrackerCore {
+    const dh_rig *rig = nullptr;
+    const dh_fit_views *views = nullptr;
+    dh_rig_fit_track_params prm{};
+    Buf<dh_rig_fit_state> state;         // [n_rigs][DH_RIG_MAX_TRACKS]
+    Buf<dh_view_instance> start, fit_out;    // [slots]
+    Buf<dh_view_fit_record> fit_rec;
+    Buf<uint32_t> who;
+    Buf<dh_head> heads;                  // host forms: [n][DH_MAX_HEADS]
+    Buf<uint32_t> n_heads, ids, n_persons;
+    Buf<dh_rig_person> persons;          // [n_rigs][DH_RIG_MAX_PERSONS]
+    Buf<dh_rig_track> tracks;            // [n_rigs][DH_RIG_MAX_TRACKS]
+    Buf<dh_rig_fit_record> records;      // [slots]
+    int clear(size_t g0, size_t m, hipStream_t st) {
+        HIP_TRY(hipMemsetAsync(state.get() + g0 * DH_RIG_MAX_TRACKS, 0, m * DH_RIG_MAX_TRACKS * sizeof(dh_rig_fit_state), st));
+        return DH_OK;
+    }
+};
+static int rig_fit_tracker_create_(const dh_rig *rig, const dh_fit_views *views, const dh_fit_model *m, float scale, uint32_t flags,
+                                   const dh_rig_fit_track_params *params, dh_rig_fit_tracker **out) {
+    const char *who = "dh_rig_fit_tracker_create";
+    if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
+    *out = nullptr;
+    dh_rig_fit_track_params prm;
+    (void)rig_fit_track_params_default_(&prm);
+    if (params) prm = *params;
+    TRY(fit_tracker_create_check(prm, scale, flags, m, [&]() -> int {
+        if (prm.max_coast > prm.max_misses)
+            return fail(DH_EINVAL, "%s: max_coast %u above the max_misses %u the ids come from", who, prm.max_coast, prm.max_misses);
+        return DH_OK;
+    }, [&]() -> int {
+        if (!rig) return fail(DH_EINVAL, "%s: NULL rig table", who);
+        if (!views) return fail(DH_EINVAL, "%s: NULL view table", who);
+        if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
+        if (views->cams != rig->cams) return fail(DH_EINVAL, "%s: the rig table and the view table are bound to different camera tables", who);
+        if (m->device != rig->cams->device)
+            return fail(DH_EINVAL, "%s: the model lives on device %d, the tables on %d", who, m->device, rig->cams->device);
+        return DH_OK;
+    }, who));
+    const int64_t largest = rig->largest;
+    if ((uint64_t)largest * m->n > DH_FIT_MAX_POINTS)
+        return fail(DH_EINVAL, "%s: a rig of %lld cameras sums %llu terms of a %u-point model, above %u", who, (long long)largest,
+                    (unsigned long long)((uint64_t)largest * m->n), m->n, DH_FIT_MAX_POINTS);
+    const size_t ng = (size_t)rig->n_rigs, slots = ng * DH_RIG_MAX_TRACKS;
+    return create_tracker(rig->cams, out, [&](dh_rig_fit_tracker &t, size_t n) -> int {
+        t.rig = rig; t.views = views; t.prm = prm;
+        TRY(t.state.alloc(slots));
+        TRY(t.start.alloc(slots)); TRY(t.fit_out.alloc(slots)); TRY(t.fit_rec.alloc(slots));
+        TRY(t.who.alloc(slots));
+        TRY(t.heads.alloc(n * DH_MAX_HEADS)); TRY(t.n_heads.alloc(n)); TRY(t.ids.alloc(n * DH_MAX_HEADS));
+        TRY(t.n_persons.alloc(ng)); TRY(t.persons.alloc(ng * DH_RIG_MAX_PERSONS)); TRY(t.tracks.alloc(ng * DH_RIG_MAX_TRACKS));
+        TRY(t.records.alloc(slots));
+        return t.init_fit(m, scale, flags, prm.rms_max, prm.max_jump, slots);
+    }, ng);
+}
+static int rig_fit_tracker_destroy_(dh_rig_fit_tracker *t) { return destroy_fit_tracker(t); }
+static int rig_fit_tracker_reset_(dh_rig_fit_tracker *t, int rig, void *stream) {
+    return reset_tracker(t, rig, stream, "dh_rig_fit_tracker_reset", t ? t->rig->n_rigs : 0, "rig");
+}
+static int rig_fit_tracker_state_(dh_rig_fit_tracker *t, dh_rig_fit_state *states) {
+    if (t && !states) return fail(DH_EINVAL, "dh_rig_fit_tracker_state: NULL argument");
+    return read_tracker(t, "dh_rig_fit_tracker_state", [&](size_t) -> int {
+        HIP_TRY(hipMemcpy(states, t->state.get(), (size_t)t->rig->n_rigs * DH_RIG_MAX_TRACKS * sizeof(dh_rig_fit_state), hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
+}
+// The refusals of a step that are the tracker's own, before anything is launched.
+static int rig_fit_check(const dh_rig_fit_tracker *t, const void *frames, int w, int h, int max_heads, const void *n_heads, const void *heads,
+                         const void *n_persons, const void *persons, const dh_fit_params *in, const void *records, dh_fit_params *prm,
+                         const char *who) {
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
+    if (!frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!n_heads || !heads) return fail(DH_EINVAL, "%s: NULL heads", who);
+    if (!n_persons || !persons) return fail(DH_EINVAL, "%s: NULL persons", who);
+    if (!records) return fail(DH_EINVAL, "%s: NULL records", who);
+    TRY(check_frame_size(w, h, who));
+    if (max_heads < 1 || max_heads > DH_MAX_HEADS) return fail(DH_EINVAL, "%s: max_heads %d outside 1 .. %d", who, max_heads, DH_MAX_HEADS);
+    return fit_params_check(in, prm, who);
+}
+// Steps 0 - 6 for every rig, on device arrays and stream s (arguments checked, device selected): three launches, and nothing
+// uploaded but their arguments.
+static int rig_fit_enqueue(dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
+                           const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons,
+                           const dh_fit_params &prm, dh_rig_fit_record *records, hipStream_t s) {
+    RigFitArgs a;
+    memset(&a, 0, sizeof a);
+    a.n_rigs = t->rig->n_rigs; a.n_cams = t->n; a.max_heads = max_heads;
+    a.flags = t->flags; a.scale = t->scale; a.prm = t->prm; a.rms_lim = t->rms_lim; a.jump2 = t->jump2;
+    a.coarse = prm.coarse_iterations; a.full = prm.iterations;
+    a.angles = t->angles.get(); a.rig_begin = t->rig->rig_begin.get(); a.views = t->views->dev.get();
+    a.present = present; a.n_heads = n_heads; a.heads = heads; a.n_persons = n_persons; a.persons = persons;
+    a.state = t->state.get(); a.start = t->start.get(); a.sched = t->sched.get(); a.seed = t->seed.get(); a.who = t->who.get();
+    a.fit_out = t->fit_out.get(); a.fit_rec = t->fit_rec.get(); a.records = records;
+    FitViewsSchedArgs f;
+    memset(&f, 0, sizeof f);
+    f.f.frames = frames; f.f.n = t->n; f.f.w = w; f.f.h = h;
+    f.f.cams = t->cams->dev.get(); f.f.views = t->views->dev.get(); f.f.models = t->models.get();
+    f.f.inst = t->start.get(); f.f.n_inst = (uint32_t)(a.n_rigs * DH_RIG_MAX_TRACKS);
+    fit_args_params(f.f, prm);                                   // (k_fit_views_sched reads coarse and full per slot from sched)
+    f.f.out = t->fit_out.get(); f.f.rec = t->fit_rec.get();
+    f.sched = t->sched.get(); f.seed = t->seed.get(); f.group = DH_RIG_MAX_TRACKS;
+    TRY(hip_step(dh_launch_rig_fit_seed(a, s), "k_rig_fit_seed"));
+    TRY(hip_step(dh_launch_fit_views_sched(f, s), "k_fit_views_sched"));
+    TRY(hip_step(dh_launch_rig_fit_update(a, s), "k_rig_fit_update"));
+    return DH_OK;
+}
+static int rig_fit_tracker_step_persons_device_(dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
+                                                const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons,
+                                                const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_fit_record *records,
+                                                void *stream) {
+    dh_fit_params prm;
+    TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm, "dh_rig_fit_tracker_step_persons_device"));
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return rig_fit_enqueue(t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, prm, records, (hipStream_t)stream);
+}
+// The refusals of the whole step beyond the core step's: the rig tracker must step the tracker's own rig table and must not
+// drop an id sooner than the tracker stops coasting on it.
+static int rig_fit_step_check(const dh_predictor *p, const dh_rig_fit_tracker *t, const dh_rig_tracker *rt, const void *frames, int w, int h,
+                              const void *n_heads, const void *heads, const void *ids, const void *n_persons, const void *persons,
+                              const dh_fit_params *in, const void *records, dh_fit_params *prm, const char *who) {
+    if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
+    if (!rt) return fail(DH_EINVAL, "%s: NULL rig tracker", who);
+    TRY(rig_fit_check(t, frames, w, h, rt->prm.max_heads, n_heads, heads, n_persons, persons, in, records, prm, who));
+    if (!ids) return fail(DH_EINVAL, "%s: NULL rig_ids", who);
+    if (rt->rig != t->rig) return fail(DH_EINVAL, "%s: the rig tracker steps another rig table than the fit tracker's", who);
+    if (rt->prm.max_misses < t->prm.max_coast)
+        return fail(DH_EINVAL, "%s: the rig tracker's max_misses %u is below the fit tracker's max_coast %u", who, rt->prm.max_misses, t->prm.max_coast);
+    return DH_OK;
+}
+static int rig_fit_tracker_step_device_(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
+                                        const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *ids,
+                                        uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records,
+                                        void *stream) {
+    const char *who = "dh_rig_fit_tracker_step_device";
+    dh_fit_params prm;
+    TRY(rig_fit_step_check(p, t, rt, frames, w, h, n_heads, heads, ids, n_persons, persons, fit_params, records, &prm, who));
+    TRY(dh_rig_tracker_step_device_(p, rt, frames, w, h, present, n_heads, heads, ids, n_persons, persons, tracks, stream));
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return rig_fit_enqueue(t, frames, w, h, present, rt->prm.max_heads, n_heads, heads, n_persons, persons, prm, records, (hipStream_t)stream);
+}
+// The host forms: everything staged through the tracker's buffers on its own stream; synchronous.  p NULL: the core step on
+// the caller's heads and persons; else the rig step first (its device form, on the staged frames), its outputs copied back too.
+static int rig_fit_host(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present,
+                        int max_heads, const dh_fit_params &prm, uint32_t *n_heads, dh_head *heads, uint32_t *ids, uint32_t *n_persons,
+                        dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records) {
+    const size_t n = (size_t)t->n, ng = (size_t)t->rig->n_rigs, mh = (size_t)max_heads;
+    return fit_tracker_host(t, frames, w, h, present, [&](hipStream_t s) -> int {
+        if (p) return DH_OK;
+        HIP_TRY(hipMemcpyAsync(t->n_heads.get(), n_heads, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(t->heads.get(), heads, n * mh * sizeof(dh_head), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(t->n_persons.get(), n_persons, ng * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(t->persons.get(), persons, ng * DH_RIG_MAX_PERSONS * sizeof(dh_rig_person), hipMemcpyHostToDevice, s));
+        return DH_OK;
+    }, [&](const uint16_t *fr, const uint8_t *pr, hipStream_t s) -> int {
+        if (p) TRY(dh_rig_tracker_step_device_(p, rt, fr, w, h, pr, t->n_heads.get(), t->heads.get(), t->ids.get(), t->n_persons.get(),
+                                            t->persons.get(), tracks ? t->tracks.get() : nullptr, s));
+        return rig_fit_enqueue(t, fr, w, h, pr, max_heads, t->n_heads.get(), t->heads.get(), t->n_persons.get(), t->persons.get(), prm,
+                               t->records.get(), s);
+    }, [&](hipStream_t s) -> int {
+        if (!p) return DH_OK;
+        HIP_TRY(hipMemcpyAsync(n_heads, t->n_heads.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(heads, t->heads.get(), n * mh * sizeof(dh_head), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ids, t->ids.get(), n * mh * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(n_persons, t->n_persons.get(), ng * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(persons, t->persons.get(), ng * DH_RIG_MAX_PERSONS * sizeof(dh_rig_person), hipMemcpyDeviceToHost, s));
+        if (tracks) HIP_TRY(hipMemcpyAsync(tracks, t->tracks.get(), ng * DH_RIG_MAX_TRACKS * sizeof(dh_rig_track), hipMemcpyDeviceToHost, s));
+        return DH_OK;
+    }, records, ng * DH_RIG_MAX_TRACKS);
+}
+static int rig_fit_tracker_step_persons_(dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
+                                         const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons,
+                                         const dh_fit_params *fit_params, dh_rig_fit_record *records) {
+    dh_fit_params prm;
+    TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm, "dh_rig_fit_tracker_step_persons"));
+    return rig_fit_host(nullptr, t, nullptr, frames, w, h, present, max_heads, prm, const_cast<uint32_t *>(n_heads), const_cast<dh_head *>(heads),
+                        nullptr, const_cast<uint32_t *>(n_persons), const_cast<dh_rig_person *>(persons), nullptr, records);
+}
+static int rig_fit_tracker_step_(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
+                                 const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *ids,
+                                 uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records) {
+    const char *who = "dh_rig_fit_tracker_step";
+    dh_fit_params prm;
+    TRY(rig_fit_step_check(p, t, rt, frames, w, h, n_heads, heads, ids, n_persons, persons, fit_params, records, &prm, who));
+    if (t->cams->device != dh_predictor_device_(p))
+        return fail(DH_EINVAL, "%s: rig table on device %d, predictor on device %d", who, t->cams->device, dh_predictor_device_(p));
+    return rig_fit_host(p, t, rt, frames, w, h, present, rt->prm.max_heads, prm, n_heads, heads, ids, n_persons, persons, tracks, records);
+}
+
+// ------------------------------------------------------------------ the C ABI (DH_API: dh_runtime.h)
+DH_API(fit_track_params_default, (dh_fit_track_params *p), (p))
+DH_API(fit_tracker_angles, (double out[DH_FIT_TRACK_ANGLES][2]), (out))
+DH_API(fit_tracker_create, (const dh_cameras *c, const dh_fit_model *m, float scale, uint32_t flags, const dh_fit_track_params *params, dh_fit_tracker **out), (c, m, scale, flags, params, out))
+DH_API(fit_tracker_destroy, (dh_fit_tracker *t), (t))
+DH_API(fit_tracker_reset, (dh_fit_tracker *t, int camera, void *stream), (t, camera, stream))
+DH_API(fit_tracker_state, (dh_fit_tracker *t, dh_fit_track_state *states), (t, states))
+DH_API(fit_tracker_step_poses, (dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records), (t, frames, w, h, present, poses, support, fit_params, records))
+DH_API(fit_tracker_step_poses_device, (dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records, void *stream), (t, frames, w, h, present, poses, support, fit_params, records, stream))
+DH_API(fit_tracker_step, (dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records), (p, t, frames, w, h, present, radius, fit_params, poses_out, support_out, records))
+DH_API(fit_tracker_step_device, (dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records, void *stream), (p, t, frames, w, h, present, radius, fit_params, poses_out, support_out, records, stream))
+DH_API(rig_fit_track_params_default, (dh_rig_fit_track_params *p), (p))
+DH_API(rig_fit_tracker_create, (const dh_rig *rig, const dh_fit_views *views, const dh_fit_model *model, float scale, uint32_t flags, const dh_rig_fit_track_params *params, dh_rig_fit_tracker **out), (rig, views, model, scale, flags, params, out))
+DH_API(rig_fit_tracker_destroy, (dh_rig_fit_tracker *t), (t))
+DH_API(rig_fit_tracker_reset, (dh_rig_fit_tracker *t, int rig, void *stream), (t, rig, stream))
+DH_API(rig_fit_tracker_state, (dh_rig_fit_tracker *t, dh_rig_fit_state *states), (t, states))
+DH_API(rig_fit_tracker_step_persons, (dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_fit_record *records), (t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, fit_params, records))
+DH_API(rig_fit_tracker_step_persons_device, (dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_fit_record *records, void *stream), (t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, fit_params, records, stream))
+DH_API(rig_fit_tracker_step, (dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records), (p, t, rt, frames, w, h, present, fit_params, n_heads, heads, rig_ids, n_persons, persons, tracks, records))
+DH_API(rig_fit_tracker_step_device, (dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records, void *stream), (p, t, rt, frames, w, h, present, fit_params, n_heads, heads, rig_ids, n_persons, persons, tracks, records, stream))

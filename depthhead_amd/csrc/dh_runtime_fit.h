@@ -1,4 +1,4 @@
-// dh_runtime_fit.h -- what the fit family's unit (dh_api_fit.hip) and the fit trackers (still in dh_api.hip) both use: the model
+// dh_runtime_fit.h -- what the fit family's unit (dh_api_fit.hip) and the fit trackers' (dh_api_fit_track.hip) both use: the model
 // and view-table handles, and the check and the argument half of a call's dh_fit_params.  Everything is static, as in dh_runtime.h.
 // Not part of the ABI; only those two units include it.
 #pragma once

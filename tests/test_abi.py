@@ -236,7 +236,8 @@ def test_every_entry_point_runs_inside_the_exception_guard():
     """include/depthhead_hip.h: "never throws or aborts across the boundary".  Every `extern "C" int dh_*` definition of the
     library is either generated by the DH_API macro (dh_runtime.h: body inside dh_guard_) or calls dh_guard_ itself (dh_biwi.cpp);
     the only unguarded definitions, in every unit of the runtime, are the two that cannot throw (dh_version, dh_last_error)."""
-    assert {"dh_api.hip", "dh_api_fit.hip"} <= set(runtime_units.UNITS) and {"dh_runtime.h", "dh_runtime_fit.h"} <= set(runtime_units.HEADERS)
+    assert {"dh_api.hip", "dh_api_fit.hip", "dh_api_fit_track.hip"} <= set(runtime_units.UNITS)
+    assert {"dh_runtime.h", "dh_runtime_fit.h", "dh_runtime_track.h"} <= set(runtime_units.HEADERS)
     guarded = runtime_units.guarded()
     macros = runtime_units.api_macros()
     assert set(macros) == {"DH_API"}, macros
