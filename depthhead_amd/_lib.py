@@ -144,6 +144,20 @@ class IdentParams(C.Structure):
                 ("min_ratio", C.c_double), ("reserved", C.c_uint64 * 3)]
 
 
+# dh_subject_track_state / dh_subject_track_record: a subject fit tracker's per-camera state and what one step reports for a camera
+SUBJECT_TRACK_STATE_DTYPE = np.dtype([("fit", FIT_TRACK_STATE_DTYPE), ("subject", "<u4"), ("wait", "<u4"), ("tries", "<u4"),
+                                      ("bound_age", "<u4")], align=True)
+assert SUBJECT_TRACK_STATE_DTYPE.itemsize == 92
+SUBJECT_TRACK_RECORD_DTYPE = np.dtype([("track", FIT_TRACK_RECORD_DTYPE), ("ident", IDENT_RECORD_DTYPE), ("subject", "<u4"), ("model", "<u4"),
+                                       ("identified", "<u4"), ("tries", "<u4")], align=True)
+assert SUBJECT_TRACK_RECORD_DTYPE.itemsize == 160 and SUBJECT_TRACK_RECORD_DTYPE.fields["ident"][1] == 104
+
+
+class SubjectTrackParams(C.Structure):
+    """dh_subject_track_params"""
+    _fields_ = [("retry", C.c_uint32), ("max_tries", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
 # dh_view_instance / dh_view_fit_record: one world-posed model seen by several cameras, and what its fit reports (dh_fit_depth_views*)
 VIEW_INSTANCE_DTYPE = np.dtype([("first_cam", "<u4"), ("model", "<u4"), ("views", "<u8"), ("R", "<f4", (9,)), ("t", "<f4", (3,)),
                                 ("scale", "<f4"), ("flags", "<u4")], align=True)
@@ -265,6 +279,10 @@ EXPORTS = [
     "dh_fit_ident_params_default", "dh_fit_identify_subjects", "dh_fit_identify_subjects_cameras", "dh_fit_identify_subjects_device",
     "dh_fit_identify_subjects_cameras_device",
     "dh_fit_ident_views_params_default", "dh_fit_identify_subjects_views", "dh_fit_identify_subjects_views_device",
+    "dh_subject_track_params_default", "dh_subject_fit_tracker_create", "dh_subject_fit_tracker_destroy", "dh_subject_fit_tracker_reset",
+    "dh_subject_fit_tracker_state", "dh_subject_fit_tracker_info", "dh_subject_fit_tracker_set_enrolled", "dh_subject_fit_tracker_bind",
+    "dh_subject_fit_tracker_step_poses", "dh_subject_fit_tracker_step_poses_device", "dh_subject_fit_tracker_step",
+    "dh_subject_fit_tracker_step_device",
 ]
 
 

@@ -1060,6 +1060,15 @@ static int ident_params_check(const dh_ident_params *in, double default_max_rms,
     *out = prm;
     return DH_OK;
 }
+// (dh_runtime_fit.h: what the subject fit tracker's creation reads of a set and checks of its dh_ident_params)
+void dh_fit_subjects_view_(const dh_fit_subjects *set, SubjectsView *v, FitModel *models) {
+    *v = SubjectsView{set->device, set->n, set->n_subjects, set->radius, set->basis->largest, set->table.get()};
+    if (models)
+        for (uint32_t s = 0; s < set->n_subjects; ++s) models[s] = FitModel{set->models[s]->pts.get(), set->models[s]->nrm.get(), set->n, 0};
+}
+int dh_ident_params_check_(const dh_ident_params *in, dh_ident_params *out, const char *who) {
+    return ident_params_check(in, DH_IDENT_DEFAULT_MAX_RMS, out, who);
+}
 // The half of an IdentArgs or IdentViewsArgs that the set, the subject count and the (checked) params fill.
 template <typename G>
 static void ident_args_common(G &g, const dh_fit_subjects *set, uint32_t n_subjects, const dh_ident_params &prm) {

@@ -1,6 +1,7 @@
 // dh_api_fit_track.hip -- the fit trackers' runtime: what both share (the angle table, FitTrackerCore, the creation check, the
-// host form of a step), the camera fit tracker and the rig fit tracker (section 22) in their host and
-// _device forms.  Kernels: k_fit_track.hip, k_rig_fit_track.hip, and the _sched launches of k_fit.hip and k_fit_views.hip.  Shares
+// host form of a step), the camera fit tracker, the rig fit tracker (section 22) and the subject fit tracker
+// (section 29) in their host and _device forms.  Kernels: k_fit_track.hip, k_rig_fit_track.hip, k_subject_track.hip, and the _sched
+// launches of k_fit.hip and k_fit_views.hip.  Shares
 // dh_runtime.h with every runtime unit, dh_runtime_fit.h with the fit family (dh_api_fit.hip), and dh_runtime_track.h with the
 // trackers in dh_api.hip, which also defines the three functions of that header a whole step calls.
 #include <math.h>
@@ -461,6 +462,254 @@ static int rig_fit_tracker_step_(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_
     return rig_fit_host(p, t, rt, frames, w, h, present, rt->prm.max_heads, prm, n_heads, heads, ids, n_persons, persons, tracks, records);
 }
 
+// ------------------------------------------------------------------ following each tracked head with its own subject's model
+static int subject_track_params_default_(dh_subject_track_params *p) {
+    if (!p) return fail(DH_EINVAL, "dh_subject_track_params_default: NULL argument");
+    memset(p, 0, sizeof *p);
+    p->retry = 4; p->max_tries = 4;
+    return DH_OK;
+}
+
+// A FitTrackerCore whose model table holds the set's S models and the generic one at index S (core.model: the generic one), whose
+// state carries each camera's binding, and which owns what an identification needs: the mask, the list and the pair scratch.
+struct dh_subject_fit_tracker : FitTrackerCore {
+    const dh_fit_subjects *set = nullptr;
+    SubjectsView sv{};
+    dh_fit_track_params prm{};
+    dh_ident_params iprm{};
+    dh_subject_track_params sprm{};
+    uint32_t grid = 0;                   // workgroups of k_subject_track_score
+    Buf<dh_subject_track_state> state;   // [n]
+    Buf<dh_render_instance> start, fit_out;
+    Buf<dh_fit_record> fit_rec;
+    Buf<uint8_t> enrolled;               // [S]: ones for "all"
+    Buf<uint32_t> want, n_want, wants;   // [n], [1], [n]
+    Buf<dh_fit_record> score;            // [n][S]
+    Buf<float> pose;                     // [n][S][12]
+    Buf<dh_pose> poses;                  // host forms
+    Buf<dh_support> support;
+    Buf<dh_subject_track_record> records;
+    // zeros, and DH_IDENT_UNKNOWN (every byte 0xFF) in the subject word of each state
+    int clear(size_t c0, size_t m, hipStream_t st) {
+        HIP_TRY(hipMemsetAsync(state.get() + c0, 0, m * sizeof(dh_subject_track_state), st));
+        HIP_TRY(hipMemset2DAsync(&state.get()[c0].subject, sizeof(dh_subject_track_state), 0xFF, sizeof(uint32_t), m, st));
+        return DH_OK;
+    }
+    // the mask on the device, ordered on st; the caller's memory is free when this returns
+    int put_enrolled(const uint8_t *mask, hipStream_t st) {
+        if (!mask) { HIP_TRY(hipMemsetAsync(enrolled.get(), 1, sv.n_subjects, st)); return DH_OK; }
+        HIP_TRY(hipMemcpyAsync(enrolled.get(), mask, sv.n_subjects, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return DH_OK;
+    }
+};
+static int subject_fit_tracker_create_(const dh_cameras *c, const dh_fit_subjects *set, const dh_fit_model *m, float scale, uint32_t flags,
+                                       const dh_fit_track_params *track_params, const dh_ident_params *ident_params,
+                                       const dh_subject_track_params *params, const uint8_t *enrolled, dh_subject_fit_tracker **out) {
+    const char *who = "dh_subject_fit_tracker_create";
+    if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
+    *out = nullptr;
+    dh_fit_track_params prm;
+    (void)fit_track_params_default_(&prm);
+    if (track_params) prm = *track_params;
+    dh_subject_track_params sprm;
+    (void)subject_track_params_default_(&sprm);
+    if (params) sprm = *params;
+    dh_ident_params iprm;
+    SubjectsView sv{};
+    TRY(fit_tracker_create_check(prm, scale, flags, m, [&]() -> int {
+        if (prm.conf_den == 0 || prm.conf_num > prm.conf_den)
+            return fail(DH_EINVAL, "%s: confidence %u / %u, expected a fraction in [0, 1]", who, prm.conf_num, prm.conf_den);
+        return DH_OK;
+    }, [&]() -> int {
+        if (!c) return fail(DH_EINVAL, "%s: NULL camera table", who);
+        if (!set) return fail(DH_EINVAL, "%s: NULL subject set", who);
+        if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
+        TRY(dh_ident_params_check_(ident_params, &iprm, who));
+        if (sprm.reserved[0] || sprm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the dh_subject_track_params is not 0", who);
+        dh_fit_subjects_view_(set, &sv, nullptr);
+        if (sv.device != c->device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the camera table on %d", who, sv.device, c->device);
+        if (m->device != c->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the camera table on %d", who, m->device, c->device);
+        if (m->n != sv.n) return fail(DH_EINVAL, "%s: the generic model has %u points, a model of the set %u", who, m->n, sv.n);
+        const double extent = fabs((double)scale) * sv.radius;
+        if (extent > DH_FIT_MAX_EXTENT)
+            return fail(DH_EINVAL, "%s: a model of the set may span %g mm from its origin (limit %g)", who, extent, DH_FIT_MAX_EXTENT);
+        return DH_OK;
+    }, who));
+    const uint64_t pairs = (uint64_t)c->n * sv.n_subjects;
+    if (pairs > DH_IDENT_MAX_PAIRS)
+        return fail(DH_EINVAL, "%s: %d cameras times %u subjects exceed %u pairs", who, c->n, sv.n_subjects, DH_IDENT_MAX_PAIRS);
+    return create_tracker(c, out, [&](dh_subject_fit_tracker &t, size_t n) -> int {
+        const uint32_t S = sv.n_subjects;
+        t.set = set; t.sv = sv; t.prm = prm; t.iprm = iprm; t.sprm = sprm;
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, c->device));
+        t.grid = (uint32_t)std::min<uint64_t>(pairs, 2ull * (uint64_t)std::max(prop.multiProcessorCount, 1));
+        TRY(t.state.alloc(n));
+        TRY(t.start.alloc(n)); TRY(t.fit_out.alloc(n)); TRY(t.fit_rec.alloc(n));
+        TRY(t.enrolled.alloc(S)); TRY(t.want.alloc(n)); TRY(t.n_want.alloc(1)); TRY(t.wants.alloc(n));
+        TRY(t.score.alloc((size_t)pairs)); TRY(t.pose.alloc((size_t)pairs * 12));
+        TRY(t.poses.alloc(n)); TRY(t.support.alloc(n)); TRY(t.records.alloc(n));
+        TRY(t.init_fit(m, scale, flags, prm.rms_max, prm.max_jump, n));
+        // the table of S + 1 models in place of the core's one
+        std::vector<FitModel> table((size_t)S + 1);
+        dh_fit_subjects_view_(set, &t.sv, table.data());
+        table[S] = FitModel{m->pts.get(), m->nrm.get(), m->n, 0};
+        TRY(t.models.alloc((size_t)S + 1));
+        HIP_TRY(hipMemcpy(t.models.get(), table.data(), table.size() * sizeof(FitModel), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(t.n_want.get(), 0, sizeof(uint32_t)));
+        HIP_TRY(hipMemset(t.wants.get(), 0, n * sizeof(uint32_t)));
+        return t.put_enrolled(enrolled, nullptr);
+    });
+}
+static int subject_fit_tracker_destroy_(dh_subject_fit_tracker *t) { return destroy_fit_tracker(t); }
+static int subject_fit_tracker_reset_(dh_subject_fit_tracker *t, int camera, void *stream) {
+    return reset_tracker(t, camera, stream, "dh_subject_fit_tracker_reset");
+}
+static int subject_fit_tracker_state_(dh_subject_fit_tracker *t, dh_subject_track_state *states) {
+    if (t && !states) return fail(DH_EINVAL, "dh_subject_fit_tracker_state: NULL argument");
+    return read_tracker(t, "dh_subject_fit_tracker_state", [&](size_t n) -> int {
+        HIP_TRY(hipMemcpy(states, t->state.get(), n * sizeof(dh_subject_track_state), hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
+}
+static int subject_fit_tracker_info_(const dh_subject_fit_tracker *t, int *n_cams, uint32_t *n_subjects, uint32_t *score_workgroups) {
+    if (!t) return fail(DH_EINVAL, "dh_subject_fit_tracker_info: NULL tracker");
+    if (n_cams) *n_cams = t->n;
+    if (n_subjects) *n_subjects = t->sv.n_subjects;
+    if (score_workgroups) *score_workgroups = t->grid;
+    return DH_OK;
+}
+static int subject_fit_tracker_set_enrolled_(dh_subject_fit_tracker *t, const uint8_t *enrolled, void *stream) {
+    if (!t) return fail(DH_EINVAL, "dh_subject_fit_tracker_set_enrolled: NULL tracker");
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return t->put_enrolled(enrolled, (hipStream_t)stream);
+}
+static int subject_fit_tracker_bind_(dh_subject_fit_tracker *t, int camera, uint32_t subject, void *stream) {
+    const char *who = "dh_subject_fit_tracker_bind";
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
+    if (camera < 0 || camera >= t->n) return fail(DH_EINVAL, "%s: camera %d of %d", who, camera, t->n);
+    if (subject >= t->sv.n_subjects && subject != DH_IDENT_UNKNOWN)
+        return fail(DH_EINVAL, "%s: subject %u of %u (DH_IDENT_UNKNOWN unbinds)", who, subject, t->sv.n_subjects);
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    dh_subject_track_state *st = t->state.get() + camera;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&st->subject, (int)subject, 1, (hipStream_t)stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&st->wait, 0, 3, (hipStream_t)stream));      // wait, tries, bound_age
+    return DH_OK;
+}
+// The refusals of a step that are the tracker's own: section 19's.
+static int subject_track_check(const dh_subject_fit_tracker *t, const void *frames, int w, int h, const void *poses, const void *support,
+                               const dh_fit_params *in, const void *records, dh_fit_params *prm, const char *who) {
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
+    if (!frames) return fail(DH_EINVAL, "%s: NULL frames", who);
+    if (!poses || !support) return fail(DH_EINVAL, "%s: NULL poses or support", who);
+    if (!records) return fail(DH_EINVAL, "%s: NULL records", who);
+    TRY(check_frame_size(w, h, who));
+    return fit_params_check(in, prm, who);
+}
+// One step of every camera on device arrays and stream s (arguments checked, device selected): five launches, a linear chain.
+static int subject_track_enqueue(dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
+                                 const dh_support *support, const dh_fit_params &prm, dh_subject_track_record *records, hipStream_t s) {
+    SubjectTrackArgs g;
+    memset(&g, 0, sizeof g);
+    FitTrackArgs &a = g.a;
+    a.n = t->n; a.flags = t->flags; a.scale = t->scale; a.prm = t->prm; a.rms_lim = t->rms_lim; a.jump2 = t->jump2;
+    a.coarse = prm.coarse_iterations; a.full = prm.iterations;
+    a.angles = t->angles.get(); a.present = present; a.poses = poses; a.support = support;
+    a.start = t->start.get(); a.sched = t->sched.get(); a.seed = t->seed.get();
+    a.fit_out = t->fit_out.get(); a.fit_rec = t->fit_rec.get();
+    FitSchedArgs f;
+    memset(&f, 0, sizeof f);
+    f.f.frames = frames; f.f.n = t->n; f.f.w = w; f.f.h = h;
+    f.f.cams = t->cams->dev.get(); f.f.models = t->models.get(); f.f.inst = t->start.get(); f.f.n_inst = (uint32_t)t->n;
+    fit_args_params(f.f, prm);                             // (k_fit_sched reads coarse and full per instance from sched)
+    f.f.out = t->fit_out.get(); f.f.rec = t->fit_rec.get();
+    f.sched = t->sched.get(); f.seed = t->seed.get();
+    IdentArgs &q = g.q;
+    q.f.frames = frames; q.f.n = t->n; q.f.w = w; q.f.h = h;
+    q.f.cams = t->cams->dev.get(); q.f.inst = t->fit_out.get(); q.f.n_inst = (uint32_t)t->n;
+    q.f.coarse = 0; q.f.full = t->iprm.iterations; q.f.min_points = t->iprm.min_points;
+    q.f.gate[0] = t->iprm.gate; q.f.gate[1] = t->iprm.gate;
+    q.f.lam1 = 1.0 + t->iprm.lambda;
+    q.models = t->sv.table; q.np = t->sv.n; q.n_subjects = t->sv.n_subjects;
+    q.radius = t->sv.radius; q.largest = t->sv.largest;
+    q.enrolled = t->enrolled.get(); q.fit_rec = t->fit_rec.get();
+    q.score = t->score.get(); q.pose = t->pose.get();
+    q.max_ms = t->iprm.max_rms * t->iprm.max_rms; q.min_ratio = t->iprm.min_ratio;
+    g.state = t->state.get(); g.records = records;
+    g.retry = t->sprm.retry; g.max_tries = t->sprm.max_tries;
+    g.want = t->want.get(); g.n_want = t->n_want.get(); g.wants = t->wants.get();
+    g.grid = t->grid;
+    TRY(hip_step(dh_launch_subject_track_seed(g, s), "k_subject_track_seed"));
+    TRY(hip_step(dh_launch_fit_sched(f, s), "k_fit_sched"));
+    TRY(hip_step(dh_launch_subject_track_update(g, s), "k_subject_track_update"));
+    TRY(hip_step(dh_launch_subject_track_score(g, s), "k_subject_track_score"));
+    TRY(hip_step(dh_launch_subject_track_bind(g, s), "k_subject_track_bind"));
+    return DH_OK;
+}
+static int subject_fit_tracker_step_poses_device_(dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                                  const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params,
+                                                  dh_subject_track_record *records, void *stream) {
+    dh_fit_params prm;
+    TRY(subject_track_check(t, frames, w, h, poses, support, fit_params, records, &prm, "dh_subject_fit_tracker_step_poses_device"));
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return subject_track_enqueue(t, frames, w, h, present, poses, support, prm, records, (hipStream_t)stream);
+}
+static int subject_fit_tracker_step_device_(dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                            uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out,
+                                            dh_subject_track_record *records, void *stream) {
+    const char *who = "dh_subject_fit_tracker_step_device";
+    dh_fit_params prm;
+    if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
+    TRY(subject_track_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
+    TRY(dh_predict_batch_cameras_support_device_(p, frames, t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, poses_out, support_out, stream));
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return subject_track_enqueue(t, frames, w, h, present, poses_out, support_out, prm, records, (hipStream_t)stream);
+}
+// The host forms, as the camera fit tracker's: p NULL: the core step on the caller's poses and support; else the prediction first.
+static int subject_track_host(dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                              uint32_t radius, const dh_fit_params &prm, dh_pose *poses, dh_support *support, dh_subject_track_record *records) {
+    const size_t n = (size_t)t->n;
+    return fit_tracker_host(t, frames, w, h, present, [&](hipStream_t s) -> int {
+        if (p) return DH_OK;
+        HIP_TRY(hipMemcpyAsync(t->poses.get(), poses, n * sizeof(dh_pose), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(t->support.get(), support, n * sizeof(dh_support), hipMemcpyHostToDevice, s));
+        return DH_OK;
+    }, [&](const uint16_t *fr, const uint8_t *pr, hipStream_t s) -> int {
+        if (p) TRY(dh_predict_batch_cameras_support_device_(p, fr, t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, t->poses.get(),
+                                                         t->support.get(), s));
+        return subject_track_enqueue(t, fr, w, h, pr, t->poses.get(), t->support.get(), prm, t->records.get(), s);
+    }, [&](hipStream_t s) -> int {
+        if (!p) return DH_OK;
+        HIP_TRY(hipMemcpyAsync(poses, t->poses.get(), n * sizeof(dh_pose), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(support, t->support.get(), n * sizeof(dh_support), hipMemcpyDeviceToHost, s));
+        return DH_OK;
+    }, records, n);
+}
+static int subject_fit_tracker_step_poses_(dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                           const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params,
+                                           dh_subject_track_record *records) {
+    dh_fit_params prm;
+    TRY(subject_track_check(t, frames, w, h, poses, support, fit_params, records, &prm, "dh_subject_fit_tracker_step_poses"));
+    return subject_track_host(nullptr, t, frames, w, h, present, 0, prm, const_cast<dh_pose *>(poses), const_cast<dh_support *>(support), records);
+}
+static int subject_fit_tracker_step_(dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                     uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out,
+                                     dh_subject_track_record *records) {
+    const char *who = "dh_subject_fit_tracker_step";
+    dh_fit_params prm;
+    if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
+    TRY(subject_track_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
+    if (radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u (a negative int?); expected 0 .. 2^31 - 1", who, radius);
+    if (t->cams->device != dh_predictor_device_(p))
+        return fail(DH_EINVAL, "%s: camera table on device %d, predictor on device %d", who, t->cams->device, dh_predictor_device_(p));
+    return subject_track_host(p, t, frames, w, h, present, radius, prm, poses_out, support_out, records);
+}
+
 // ------------------------------------------------------------------ the C ABI (DH_API: dh_runtime.h)
 DH_API(fit_track_params_default, (dh_fit_track_params *p), (p))
 DH_API(fit_tracker_angles, (double out[DH_FIT_TRACK_ANGLES][2]), (out))
@@ -481,3 +730,15 @@ DH_API(rig_fit_tracker_step_persons, (dh_rig_fit_tracker *t, const uint16_t *fra
 DH_API(rig_fit_tracker_step_persons_device, (dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_fit_record *records, void *stream), (t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, fit_params, records, stream))
 DH_API(rig_fit_tracker_step, (dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records), (p, t, rt, frames, w, h, present, fit_params, n_heads, heads, rig_ids, n_persons, persons, tracks, records))
 DH_API(rig_fit_tracker_step_device, (dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records, void *stream), (p, t, rt, frames, w, h, present, fit_params, n_heads, heads, rig_ids, n_persons, persons, tracks, records, stream))
+DH_API(subject_track_params_default, (dh_subject_track_params *p), (p))
+DH_API(subject_fit_tracker_create, (const dh_cameras *c, const dh_fit_subjects *set, const dh_fit_model *generic, float scale, uint32_t flags, const dh_fit_track_params *track_params, const dh_ident_params *ident_params, const dh_subject_track_params *params, const uint8_t *enrolled, dh_subject_fit_tracker **out), (c, set, generic, scale, flags, track_params, ident_params, params, enrolled, out))
+DH_API(subject_fit_tracker_destroy, (dh_subject_fit_tracker *t), (t))
+DH_API(subject_fit_tracker_reset, (dh_subject_fit_tracker *t, int camera, void *stream), (t, camera, stream))
+DH_API(subject_fit_tracker_state, (dh_subject_fit_tracker *t, dh_subject_track_state *states), (t, states))
+DH_API(subject_fit_tracker_info, (const dh_subject_fit_tracker *t, int *n_cams, uint32_t *n_subjects, uint32_t *score_workgroups), (t, n_cams, n_subjects, score_workgroups))
+DH_API(subject_fit_tracker_set_enrolled, (dh_subject_fit_tracker *t, const uint8_t *enrolled, void *stream), (t, enrolled, stream))
+DH_API(subject_fit_tracker_bind, (dh_subject_fit_tracker *t, int camera, uint32_t subject, void *stream), (t, camera, subject, stream))
+DH_API(subject_fit_tracker_step_poses, (dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params, dh_subject_track_record *records), (t, frames, w, h, present, poses, support, fit_params, records))
+DH_API(subject_fit_tracker_step_poses_device, (dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params, dh_subject_track_record *records, void *stream), (t, frames, w, h, present, poses, support, fit_params, records, stream))
+DH_API(subject_fit_tracker_step, (dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_subject_track_record *records), (p, t, frames, w, h, present, radius, fit_params, poses_out, support_out, records))
+DH_API(subject_fit_tracker_step_device, (dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_subject_track_record *records, void *stream), (p, t, frames, w, h, present, radius, fit_params, poses_out, support_out, records, stream))

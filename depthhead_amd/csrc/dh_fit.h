@@ -1,9 +1,9 @@
 // dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip,
-// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip, k_ident.hip, k_ident_views.hip) share with the host runtime (dh_api_fit.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
+// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip, k_ident.hip, k_ident_views.hip, k_subject_track.hip) share with the host runtime (dh_api_fit.hip, dh_api_fit_track.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
 // words of both trackers, and the one test of whether an instance may be fitted (dh_fit_instance_fault: the host's refusals and
 // the shape kernel's skips).  The device arithmetic the kernels share among themselves is in dh_fit_device.h.  Not part of the
 // ABI.  The rules are stated in include/depthhead_hip.h (sections "fitting posed models to depth frames" and after) and
-// DESIGN.md sections 18 - 28.
+// DESIGN.md sections 18 - 29.
 #pragma once
 #include "dh_internal.h"
 #include "dh_rig_fit.h"
@@ -714,3 +714,30 @@ struct IdentViewsArgs {
 };
 hipError_t dh_launch_ident_views_score(const IdentViewsArgs &a, hipStream_t s);    // one workgroup per pair, the subject the fast index
 hipError_t dh_launch_ident_views_decide(const IdentViewsArgs &a, hipStream_t s);   // one wave per instance
+
+// ---- following each tracked head with its own subject's model (k_subject_track.hip)
+static_assert(sizeof(dh_subject_track_params) == 24, "dh_subject_track_params: 24 bytes");
+static_assert(sizeof(dh_subject_track_state) == 92, "dh_subject_track_state: 92 bytes");
+static_assert(sizeof(dh_subject_track_record) == 160, "dh_subject_track_record: 160 bytes");
+// Magnitudes.  The step's fit is section 18's over a table whose entries are the set's models and the generic one: creation
+// refuses a scale whose product with the set's bound or with the generic radius exceeds DH_FIT_MAX_EXTENT, so every start
+// instance passes the extent test for whichever entry it names.  A wanted pair is section 27's as it stands.
+
+// One step's four launches beside k_fit_sched share one block: section 19's (its state and records unused: the state here is
+// 92 bytes a camera, the record 160), section 27's (inst and fit_rec: the step's fitted instances and their records, n_inst the
+// cameras; score and pose: the tracker's scratch of cameras * S pairs; subjects_out, rec and poses_out unused) and the tracker's own.
+struct SubjectTrackArgs {
+    FitTrackArgs a;
+    IdentArgs q;                  // q.enrolled is never NULL here: the tracker holds a mask of ones for "all"
+    dh_subject_track_state *state;       // [n]
+    dh_subject_track_record *records;    // [n]
+    uint32_t retry, max_tries;
+    uint32_t *want;               // [n] the cameras that want identification, in no particular order
+    uint32_t *n_want;             // [1] how many: cleared by the seed kernel, grown by the update kernel
+    uint32_t *wants;              // [n] 0 or 1 per camera: what the list holds, indexed by camera
+    uint32_t grid;                // workgroups of the score kernel, fixed at creation
+};
+hipError_t dh_launch_subject_track_seed(const SubjectTrackArgs &g, hipStream_t s);     // one lane per camera
+hipError_t dh_launch_subject_track_update(const SubjectTrackArgs &g, hipStream_t s);   // one lane per camera
+hipError_t dh_launch_subject_track_score(const SubjectTrackArgs &g, hipStream_t s);    // g.grid workgroups over the list's pairs
+hipError_t dh_launch_subject_track_bind(const SubjectTrackArgs &g, hipStream_t s);     // one wave per camera

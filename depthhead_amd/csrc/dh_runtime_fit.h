@@ -53,3 +53,17 @@ struct dh_fit_views {
     const dh_cameras *cams = nullptr;        // the table it is bound to (which outlives it)
     Buf<FitView> dev;
 };
+
+// What the subject fit tracker (dh_api_fit_track.hip) reads of a subject set and of an identify call's
+// params, defined in dh_api_fit.hip beside the set and the check they belong to (dh_host.h's names for internal symbols).
+struct dh_fit_subjects;
+struct SubjectsView {
+    int device;
+    uint32_t n, n_subjects;       // the points of a model, S
+    double radius, largest;       // the set's bound on |v'|, the basis's largest |B_k[i]|
+    const SubjectModel *table;    // device, [S]: what the identify kernels read
+};
+// *v, and where `models` is given (host, [S]) each model's device pointers as an entry of a fit's model table.
+void dh_fit_subjects_view_(const dh_fit_subjects *set, SubjectsView *v, FitModel *models);
+// ident_params_check with section 27's default max_rms.
+int dh_ident_params_check_(const dh_ident_params *in, dh_ident_params *out, const char *who);

@@ -17,58 +17,7 @@
 
 #pragma clang fp contract(off)
 
-// Whether instance `in` (number i) takes part: the rule of dh_fit_shape_subjects* without a subject (a NaN fails each test).
-__device__ __forceinline__ bool ident_takes_part(const IdentArgs &q, const dh_render_instance *in, uint32_t i) {
-    if (in->frame >= (uint32_t)q.f.n) return false;
-    if (q.fit_rec && q.fit_rec[i].status != DH_FIT_OK) return false;
-    return dh_fit_instance_fault(*in, q.radius, q.largest).why == DH_FIT_INST_OK;
-}
-
-// One pair's refit: the full steps of k_fit's schedule (no coarse ones), then the last pass; the score and the pose written by lane 0.
-template <bool STAGED>
-__device__ __forceinline__ void ident_run(const IdentArgs &q, const dh_render_instance *in, const FitModel &m, const float *s_pts,
-                                          unsigned long long *s_sum, size_t pair) {
-    const FitArgs &a = q.f;
-    const uint32_t fr = in->frame;
-    const uint16_t *frame = a.frames + (size_t)fr * a.h * a.w;
-    double K[9];
-#pragma unroll
-    for (int c = 0; c < 9; ++c) K[c] = (double)(a.cams ? a.cams[fr].k[c] : a.k[c]);
-    FitPose pose;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) pose.R[c] = (double)in->R[c];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) pose.t[c] = (double)in->t[c];
-    const double scale = (double)in->scale;
-    uint32_t steps = 0, status = DH_FIT_OK;
-    for (uint32_t it = 0; it < a.full; ++it) {
-        fit_pass<FIT_FULL, STAGED>(a, m, s_pts, frame, K, scale, pose, a.gate[1], s_sum);
-        if ((uint32_t)s_sum[DH_FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; break; }
-        double x[6];
-        if (!fit_solve_tri<6, 6>(s_sum, DH_FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
-        fit_cayley(pose.R, x + 3);
-        ++steps;
-        if (fit_small(x, 6)) break;
-    }
-    fit_pass<FIT_LAST, STAGED>(a, m, s_pts, frame, K, scale, pose, a.gate[1], s_sum);
-    if (threadIdx.x == 0) {
-        dh_fit_record rec;
-        rec.points = (uint32_t)s_sum[DH_FIT_COUNT];
-        rec.steps = steps;
-        rec.status = status;
-        rec.reserved = 0;
-        rec.sum_r2_fixed = (int64_t)s_sum[DH_FIT_E];
-        q.score[pair] = rec;
-        float *o = q.pose + pair * 12;
-#pragma unroll
-        for (int c = 0; c < 9; ++c) o[c] = (float)pose.R[c];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[9 + c] = (float)pose.t[c];
-    }
-}
-
+// (ident_takes_part and ident_run, one pair's refit, are dh_fit_device.h's: k_subject_track.hip runs them over its compact list)
 __global__ __launch_bounds__(DH_FIT_THREADS) void k_ident_score(const IdentArgs q) {
     __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];
     __shared__ unsigned long long s_sum[32];

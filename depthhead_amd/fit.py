@@ -1065,3 +1065,91 @@ class RigFitTracker(_StepInputs, _lib._Handle):
         st = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_FIT_STATE_DTYPE)
         check(self._lib.dh_rig_fit_tracker_state(self._h, vp(st)))
         return st
+
+
+def subject_track_params(retry=None, max_tries=None) -> "_lib.SubjectTrackParams":
+    """dh_subject_track_params_default with the given fields replaced."""
+    return _params(_lib.SubjectTrackParams, "dh_subject_track_params_default", retry=retry, max_tries=max_tries)
+
+
+class SubjectFitTracker(_StepInputs, _lib._Handle):
+    """One dh_subject_fit_tracker: a `FitTracker` bound to a `Subjects` set.  A track that starts is
+    followed with `model` (the generic head), identified against the set's enrolled subjects on the device, and from the next
+    step on followed with its own subject's model as the set holds it.  `enrolled` [S] (None: all) says which subjects are
+    candidates.  The state stays on the device; a step never waits on the host.  Steps, resets, binds and mask changes of one
+    tracker must be stream-ordered with one another and with the set's updates; the camera table, the set and the model must
+    outlive it."""
+    _handles = (("_h", "dh_subject_fit_tracker_destroy"),)
+
+    def __init__(self, cameras, subjects: Subjects, model: Model, w: int, h: int, scale: float = 1.0, motion: bool = False, params=None,
+                 ident_params=None, subject_params=None, enrolled=None):
+        self._lib = _lib.load()
+        self.cameras, self.subjects, self.model, self.w, self.h, self.n = cameras, subjects, model, int(w), int(h), len(cameras)
+        self.flags = FIT_TRACK_MOTION if motion else 0
+        self._h = C.c_void_p()
+        check(self._lib.dh_subject_fit_tracker_create(cameras._h, subjects._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
+                                                      _lib.ref(params), _lib.ref(ident_params), _lib.ref(subject_params),
+                                                      vp(self._mask(enrolled)), C.byref(self._h)))
+
+    def _mask(self, enrolled):
+        return None if enrolled is None else np.ascontiguousarray(enrolled, dtype=np.uint8).reshape(len(self.subjects))
+
+    def step_poses(self, frames, poses, support, present=None, fit_params=None) -> np.ndarray:
+        """The core step from the forest's POSE_DTYPE [n] and SUPPORT_DTYPE [n] of host frames [n, h, w] u16:
+        -> SUBJECT_TRACK_RECORD_DTYPE [n]."""
+        frames, pr = self._frames(frames), self._present(present)
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(self.n)
+        support = np.ascontiguousarray(support, dtype=SUPPORT_DTYPE).reshape(self.n)
+        rec = np.zeros(self.n, _lib.SUBJECT_TRACK_RECORD_DTYPE)
+        check(self._lib.dh_subject_fit_tracker_step_poses(self._h, vp(frames), self.w, self.h, vp(pr), vp(poses), vp(support),
+                                                          _lib.ref(fit_params), vp(rec)))
+        return rec
+
+    def step(self, hp, frames, present=None, radius: int = SUPPORT_RADIUS, fit_params=None):
+        """The whole step: `hp` (a HoughPrediction) predicts every camera's pose and support without guesses, then the core
+        step, on one stream.  -> (POSE_DTYPE [n], SUPPORT_DTYPE [n], SUBJECT_TRACK_RECORD_DTYPE [n])."""
+        frames, pr = self._frames(frames), self._present(present)
+        poses, support = np.zeros(self.n, POSE_DTYPE), np.zeros(self.n, SUPPORT_DTYPE)
+        rec = np.zeros(self.n, _lib.SUBJECT_TRACK_RECORD_DTYPE)
+        check(self._lib.dh_subject_fit_tracker_step(hp._ph, self._h, vp(frames), self.w, self.h, vp(pr), C.c_uint32(int(radius) & 0xFFFFFFFF),
+                                                    _lib.ref(fit_params), vp(poses), vp(support), vp(rec)))
+        return poses, support, rec
+
+    def step_device(self, frames_ptr: int, poses_ptr: int, support_ptr: int, records_ptr: int, hp=None, present_ptr: int = 0,
+                    radius: int = SUPPORT_RADIUS, fit_params=None, stream: int = 0) -> None:
+        """`FitTracker.step_device` with records [n] of dh_subject_track_record: five launches on `stream`, no allocation and no
+        host wait."""
+        prm = _lib.ref(fit_params)
+        if hp is None:
+            check(self._lib.dh_subject_fit_tracker_step_poses_device(self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
+                                                                     vp(poses_ptr), vp(support_ptr), prm, vp(records_ptr),
+                                                                     C.c_void_p(int(stream))))
+        else:
+            check(self._lib.dh_subject_fit_tracker_step_device(hp._ph, self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
+                                                               C.c_uint32(int(radius) & 0xFFFFFFFF), prm, vp(poses_ptr), vp(support_ptr),
+                                                               vp(records_ptr), C.c_void_p(int(stream))))
+
+    def reset(self, camera: int | None = None, stream: int = 0) -> None:
+        """One camera or all back to the initial state (nothing tracked, nobody bound); stream-ordered."""
+        check(self._lib.dh_subject_fit_tracker_reset(self._h, C.c_int(-1 if camera is None else int(camera)), C.c_void_p(int(stream))))
+
+    def state(self) -> np.ndarray:
+        """Synchronous copy of the state: SUBJECT_TRACK_STATE_DTYPE [n]."""
+        st = np.zeros(self.n, _lib.SUBJECT_TRACK_STATE_DTYPE)
+        check(self._lib.dh_subject_fit_tracker_state(self._h, vp(st)))
+        return st
+
+    def info(self):
+        """(cameras, S, the workgroups of the score kernel's grid)."""
+        n, s, g = C.c_int(), C.c_uint32(), C.c_uint32()
+        check(self._lib.dh_subject_fit_tracker_info(self._h, C.byref(n), C.byref(s), C.byref(g)))
+        return n.value, s.value, g.value
+
+    def bind(self, camera: int, subject: int | None, stream: int = 0) -> None:
+        """The caller's own binding of `camera` to `subject`; None unbinds.  Stream-ordered."""
+        check(self._lib.dh_subject_fit_tracker_bind(self._h, C.c_int(int(camera)), C.c_uint32(IDENT_UNKNOWN if subject is None else int(subject)),
+                                                    C.c_void_p(int(stream))))
+
+    def set_enrolled(self, enrolled, stream: int = 0) -> None:
+        """Replace the candidates' mask ([S], None: all); stream-ordered."""
+        check(self._lib.dh_subject_fit_tracker_set_enrolled(self._h, vp(self._mask(enrolled)), C.c_void_p(int(stream))))

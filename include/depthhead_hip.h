@@ -1659,6 +1659,117 @@ int dh_fit_identify_subjects_views_device(dh_fitter *f, const uint16_t *frames, 
                                           dh_ident_record *records, dh_view_instance *poses_out, dh_view_fit_record *scores,
                                           void *stream);
 
+/* ---- following each tracked head with its own subject's model ----
+ * The fit tracker of section 19 follows every head with ONE model, the generic head; sections 25 - 27 keep a gallery of per-person
+ * models on the device and can say whose a fitted head is.  A dh_subject_fit_tracker joins them: a track that starts is followed
+ * with the generic model, identified against the gallery on the device, and from the next step on followed with its own subject's
+ * model -- with no host wait and no allocation in a step.  Not in the reference: PARITY UNPINNED, the definition below is this
+ * library's.  The arithmetic conventions are those of sections 19 and 27: f32 and f64 with + - * /, compares and casts, every
+ * operation rounded on its own; int64 sums whose order is free; no sine, cosine or floating-point atomic on the device (the
+ * angle table is section 19's).  tests/subject_track_ref.py restates it; the GPU equals it byte for byte.
+ * CREATION: a camera table; a subject set of S subjects (ordinary or surface); a GENERIC dh_fit_model of the set's point count
+ *   (its points need not be the set's base mesh); scale and flags (DH_FIT_TRACK_MOTION) as in section 19; a dh_fit_track_params
+ *   (NULL: section 19's defaults), a dh_ident_params (NULL: dh_fit_ident_params_default) and a dh_subject_track_params (NULL:
+ *   dh_subject_track_params_default); enrolled[S], u8, host memory, NULL meaning every subject is a candidate.  The tracker builds a
+ *   device table of S + 1 models: entries 0 .. S - 1 name the set's models, whose buffers dh_fit_subjects_update* and the set_*
+ *   calls rewrite in place -- an update of the set enqueued on the stream of the steps is seen by the next step --, entry S is the
+ *   generic model.  The camera table, the set and the generic model must outlive the tracker.
+ * STATE of camera c (dh_subject_track_state, 92 bytes): section 19's dh_fit_track_state, then `subject` (the bound subject < S, or
+ *   DH_IDENT_UNKNOWN while unbound -- the library writes no other value), `wait` (accepted steps to pass before the next try),
+ *   `tries` (identifications of this track that did not bind) and `bound_age` (accepted steps since the binding), the last two
+ *   saturating at 2^32 - 1.  Created and reset to zeros with subject = DH_IDENT_UNKNOWN.
+ * ONE STEP of camera c, from the inputs of section 19's step:
+ * 1. Section 19's steps 0 - 6 on the first 76 bytes of the state, unchanged but for the start instance's `mesh`: the state's subject
+ *    where it is < S (the camera is BOUND), else S.  The fit is section 18's over the table of S + 1 models: a bound camera is
+ *    fitted with its subject's model as the set holds it now, an unbound one with the generic model.
+ * 2. BINDING LIFECYCLE, on the state step 1 left.  tracked == 0 (the fit was rejected, there was no start, or an absent camera
+ *    coasted past max_coast): subject = DH_IDENT_UNKNOWN, wait = tries = bound_age = 0.  Else, when this step's fit was ACCEPTED:
+ *    a bound camera has bound_age = bound_age + 1; an unbound camera WANTS IDENTIFICATION when wait == 0 and (max_tries == 0 or
+ *    tries < max_tries), and otherwise, when wait > 0, has wait = wait - 1.  Else (an absent camera within max_coast) nothing
+ *    changes: the binding is kept.
+ * 3. IDENTIFICATION of a camera that wants it is section 27's rule exactly: the one instance is this step's accepted fitted
+ *    instance (frame c, fit record DH_FIT_OK), the frames and the camera table are the step's, the candidates the tracker's
+ *    enrolled subjects among all S, the parameters the tracker's dh_ident_params; TAKING PART, THE SCORE of every (camera,
+ *    candidate) pair and THE DECISION as stated there, with the set's models as they are at this point of the stream.  Status
+ *    DH_IDENT_OK: subject = best, bound_age = 0 (two cameras may bind one subject).  Any other status: tries = tries + 1, wait =
+ *    retry.  R and t of the state stay those of the accepted fit: the refitted pose of the best pair is not taken.
+ * 4. OUTPUT.  One dh_subject_track_record per camera: `track`, section 19's record of step 1 (its instance names the mesh the
+ *    fit used); `ident`, the identification's dh_ident_record, or where none ran all zeros with status DH_IDENT_SKIPPED; `subject`,
+ *    the state's after the step; `model`, the subject whose model this step's fit used, DH_IDENT_UNKNOWN for the generic model
+ *    or where no fit ran; `identified`, 1 where an identification ran, else 0; `tries` after the step.
+ * A binding takes effect at the NEXT step's start.  dh_subject_fit_tracker_bind is the caller's own binding of one camera:
+ *   subject < S binds it (wait = tries = bound_age = 0), DH_IDENT_UNKNOWN unbinds it (the same, and the track may be identified
+ *   again); ordered on `stream`.  Rule 2 holds for it as for any binding: a camera that is not tracked keeps a caller's binding
+ *   only through a step whose fit is accepted.  dh_subject_fit_tracker_set_enrolled replaces the mask (NULL: all candidates),
+ *   ordered on `stream`; it returns once the mask has left the caller's memory.  Bindings made under an earlier mask stay.
+ * A _device step allocates nothing, never waits on the host and is five launches on `stream`, a linear chain:
+ *   k_subject_track_seed, the per-instance-schedule instance of k_fit, k_subject_track_update (which appends the cameras that
+ *   want identification to a device list), k_subject_track_score -- a grid fixed at creation of min(n_cams * S, 2 * the device's
+ *   compute units) workgroups that loop over the list's (camera, subject) pairs, so a step in which nobody wants identification
+ *   costs a launch of workgroups that leave at once, not n_cams * S of them -- and k_subject_track_bind.  The pair scratch
+ *   (n_cams * S scores and poses) is the tracker's own, allocated at creation.  Steps, resets, binds and mask changes of one
+ *   tracker must be stream-ordered with one another and with the updates of its set.  The step functions take the arguments
+ *   of dh_fit_tracker_step* with records [n_cams] of dh_subject_track_record.
+ * DH_EINVAL before anything is launched, with the outputs untouched.  create, in this order: NULL out; unknown flags; a scale that
+ *   is not finite; iterations_tracked above 64; rms_max or max_jump outside (0, 4096] (NaN included); conf_den 0 or conf_num >
+ *   conf_den; a reserved word of the dh_fit_track_params that is not 0; NULL cameras, set or generic model; the dh_ident_params'
+ *   refusals of section 27 in its order; a reserved word of the dh_subject_track_params that is not 0; a set or a generic model
+ *   on another device than the camera table; a generic model whose point count is not the set's; |scale| * (the set's bound)
+ *   above DH_FIT_MAX_EXTENT; |scale| * (the generic model's largest |v|) above DH_FIT_MAX_EXTENT; n_cams * S above
+ *   DH_IDENT_MAX_PAIRS.  step: section 19's step refusals.  reset: NULL tracker, a camera outside -1 .. n - 1.  bind: NULL tracker, a
+ *   camera outside 0 .. n - 1, a subject that is neither < S nor DH_IDENT_UNKNOWN.  set_enrolled, state, info, params_default: NULL
+ *   tracker / argument (info's outputs are each nullable).
+ * THE DEFAULTS.  retry = 4 and max_tries = 4 (tests/test_subject_track_ref.py: the runs that chose them);
+ *   max_rms NULL-selected is section 27's DH_IDENT_DEFAULT_MAX_RMS. */
+typedef struct dh_subject_track_params {
+    uint32_t retry;               /* 4: accepted steps an unbound track waits after an identification that did not bind */
+    uint32_t max_tries;           /* 4: identifications of one track that may fail before it stays generic; 0: no limit */
+    uint64_t reserved[2];         /* 0 */
+} dh_subject_track_params;  /* 24 bytes */
+typedef struct dh_subject_track_state {
+    dh_fit_track_state fit;       /* offset 0 */
+    uint32_t subject;             /* offset 76: < S, or DH_IDENT_UNKNOWN */
+    uint32_t wait;                /* offset 80 */
+    uint32_t tries;               /* offset 84 */
+    uint32_t bound_age;           /* offset 88 */
+} dh_subject_track_state;   /* 92 bytes, no padding */
+typedef struct dh_subject_track_record {
+    dh_fit_track_record track;    /* offset 0 */
+    dh_ident_record     ident;    /* offset 104 */
+    uint32_t subject;             /* offset 144: the state's after the step */
+    uint32_t model;               /* offset 148: whose model the step's fit used, or DH_IDENT_UNKNOWN */
+    uint32_t identified;          /* offset 152: 0 or 1 */
+    uint32_t tries;               /* offset 156 */
+} dh_subject_track_record;  /* 160 bytes, no padding */
+typedef struct dh_subject_fit_tracker dh_subject_fit_tracker;
+int dh_subject_track_params_default(dh_subject_track_params *p);
+/* track_params, ident_params, params, enrolled: each NULL selects its default (enrolled: all S subjects) */
+int dh_subject_fit_tracker_create(const dh_cameras *c, const dh_fit_subjects *set, const dh_fit_model *generic, float scale, uint32_t flags,
+                                  const dh_fit_track_params *track_params, const dh_ident_params *ident_params,
+                                  const dh_subject_track_params *params, const uint8_t *enrolled, dh_subject_fit_tracker **out);
+int dh_subject_fit_tracker_destroy(dh_subject_fit_tracker *t);
+/* camera, or -1 for all, back to the initial state; ordered on `stream` */
+int dh_subject_fit_tracker_reset(dh_subject_fit_tracker *t, int camera, void *stream);
+/* states [n_cams]; synchronises the device */
+int dh_subject_fit_tracker_state(dh_subject_fit_tracker *t, dh_subject_track_state *states);
+/* the cameras, S, and the workgroups of k_subject_track_score; each output nullable */
+int dh_subject_fit_tracker_info(const dh_subject_fit_tracker *t, int *n_cams, uint32_t *n_subjects, uint32_t *score_workgroups);
+/* enrolled [S] u8, host memory, or NULL for all */
+int dh_subject_fit_tracker_set_enrolled(dh_subject_fit_tracker *t, const uint8_t *enrolled, void *stream);
+int dh_subject_fit_tracker_bind(dh_subject_fit_tracker *t, int camera, uint32_t subject, void *stream);
+int dh_subject_fit_tracker_step_poses(dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                      const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params,
+                                      dh_subject_track_record *records);
+int dh_subject_fit_tracker_step_poses_device(dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                             const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params,
+                                             dh_subject_track_record *records, void *stream);
+int dh_subject_fit_tracker_step(dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out,
+                                dh_subject_track_record *records);
+int dh_subject_fit_tracker_step_device(dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h,
+                                       const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out,
+                                       dh_support *support_out, dh_subject_track_record *records, void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
