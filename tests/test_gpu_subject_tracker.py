@@ -6,7 +6,6 @@ streamed model; galleries of 1, 63, 64 and 65; nobody enrolled; every bound and 
 on the stream between two steps; the identification half against dh_fit_identify_subjects_cameras_device; the host calls against
 their _device twins on a side stream between guard bands; resets; two runs of one sequence; one step captured in a graph; the
 refusals that need a tracker; and the test the feature exists for: a bound camera is fitted with its subject's model."""
-import contextlib
 import ctypes as C
 import functools
 
@@ -20,6 +19,7 @@ import ident_ref as ir
 import subject_track_ref as stf
 import subject_track_scenes as sts
 from depthhead_amd import _lib, fit, tracking
+from subject_track_gpu import IDENT, TRACK, both, gpu_set, guarded, pair, same, to_dev, untouched
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +27,6 @@ W, H, STEPS = 160, 120, 6
 REC, STATE, POSE, SUP = _lib.SUBJECT_TRACK_RECORD_DTYPE, _lib.SUBJECT_TRACK_STATE_DTYPE, _lib.POSE_DTYPE, _lib.SUPPORT_DTYPE
 UNKNOWN = stf.UNKNOWN
 EINVAL = -1
-# The splatted scenes are coarser than a rendered frame (tests/test_subject_track_ref.py): the identification's limit lies between a
-# known head's best mean square and the stranger's, and the tracker accepts the generic head's fit of the stranger.
-IDENT = dict(min_points=16, max_rms=3.8)
-TRACK = dict(rms_max=8.0)
 
 
 def k_keys():
@@ -62,55 +58,8 @@ def angles():
     return fit.angles()
 
 
-@contextlib.contextmanager
-def gpu_set(name, n_subjects, surface=False):
-    """(the set on the GPU, its restated twin) of ident_scenes' gallery `name`, in one state."""
-    v, t, B, st = sts.restated_set(name, n_subjects, surface)
-    with fit.ShapeBasis(B) as basis, fit.Subjects(v, t, basis, n_subjects, max_offset=16.0 if surface else None) as got:
-        got.set_coeffs(st.state["coeffs"][:, :len(B)])
-        if surface:
-            for s in range(n_subjects):
-                got.set_offsets(s, st.offsets[s])
-        for s in (0, n_subjects - 1):
-            pts, nrm = got.read(s)
-            assert pts.tobytes() == st.pts[s].tobytes() and nrm.tobytes() == st.nrm[s].tobytes()
-        yield got, st
-
-
-@contextlib.contextmanager
-def pair(angles, name, n_subjects, Ks, w, h, enrolled=None, sub=None, track=None, ident=None, surface=False, flags=0, trackers=1):
-    """(trackers on the GPU, the restated tracker, the GPU set, the restated set) over one gallery and camera table."""
-    track, ident = dict(TRACK if track is None else track), dict(IDENT if ident is None else ident)
-    with contextlib.ExitStack() as stack:
-        got, st = stack.enter_context(gpu_set(name, n_subjects, surface))
-        cams = stack.enter_context(tracking.Cameras(Ks))
-        model = stack.enter_context(fit.Model(*sts.generic(name)))
-        trs = [stack.enter_context(fit.SubjectFitTracker(cams, got, model, w, h, motion=bool(flags), params=fit.fit_track_params(**track),
-                                                         ident_params=fit.ident_params(**ident),
-                                                         subject_params=None if sub is None else fit.subject_track_params(**sub), enrolled=enrolled))
-               for _ in range(trackers)]
-        ref = stf.Tracker(Ks, st, sts.generic(name), angles, flags=flags, prm=ft.params(**track), ident_prm=ir.params(**ident),
-                          sub_prm=None if sub is None else stf.params(**sub), enrolled=enrolled)
-        yield trs if trackers > 1 else trs[0], ref, got, st, cams, model
-
-
-def same(got, want, what):
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert len(got) == len(want) and got.dtype.itemsize == want.dtype.itemsize, what
-    for i in range(len(want)):
-        assert got[i].tobytes() == want[i].tobytes(), (what, i, got[i], want[i])
-
-
 def kinds(rec):
     return (np.asarray(rec["track"]["status"]) & 0xFF).tolist()
-
-
-def both(tr, ref, frames, poses, sup, present=None, what="step"):
-    got = tr.step_poses(frames, poses, sup, present)
-    want = ref.step(frames, poses, sup, present)
-    same(got, want, f"records of {what}")
-    same(tr.state(), ref.state, f"state after {what}")
-    return got
 
 
 def run_both(tr, ref, frames, poses, sup, present=None, steps=None):
@@ -233,11 +182,6 @@ def test_every_bound_and_unbound_start_kind_in_one_launch(angles):
     assert rec["subject"].tolist() == [0, UNKNOWN, 1, 2, UNKNOWN]
 
 
-def to_dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
 def test_the_set_updated_on_the_stream_between_two_steps(angles):
     """dh_fit_subjects_update_device between two _device steps on one stream: the second step's fit is the restatement's at the
     updated model (the tracker's table names the set's buffers, which the update rewrites in place)."""
@@ -294,18 +238,6 @@ def test_the_identification_half_equals_the_existing_call(angles):
                 else:
                     assert irec[c]["status"] == ir.SKIPPED == rec["ident"][c]["status"]
         assert seen >= 3
-
-
-def guarded(nbytes, skew):
-    """A device buffer of 4 KB guard bands around `nbytes` at a skewed start: (tensor, pointer, offset)."""
-    import torch
-    buf = torch.full((4096 + skew + nbytes + 4096,), 0xA5, dtype=torch.uint8, device="cuda")
-    return buf, buf.data_ptr() + 4096 + skew, 4096 + skew
-
-
-def untouched(buf, off, nbytes):
-    host = buf.cpu().numpy()
-    return (host[:off] == 0xA5).all() and (host[off + nbytes:] == 0xA5).all()
 
 
 @functools.lru_cache(maxsize=None)
