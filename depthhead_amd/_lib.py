@@ -178,6 +178,15 @@ assert RIG_FIT_RECORD_DTYPE.itemsize == 128 and RIG_FIT_RECORD_DTYPE.fields["fit
 RIG_FIT_NO_PERSON = 0xFFFFFFFF   # dh_rig_fit_record.person of an unseen entry
 
 
+# dh_rig_subject_state / dh_rig_subject_record: an entry of a rig subject fit tracker's state, and what one step reports for a slot
+RIG_SUBJECT_STATE_DTYPE = np.dtype([("fit", RIG_FIT_STATE_DTYPE), ("subject", "<u4"), ("wait", "<u4"), ("tries", "<u4"), ("bound_age", "<u4")],
+                                   align=True)
+assert RIG_SUBJECT_STATE_DTYPE.itemsize == 104
+RIG_SUBJECT_RECORD_DTYPE = np.dtype([("track", RIG_FIT_RECORD_DTYPE), ("ident", IDENT_RECORD_DTYPE), ("subject", "<u4"), ("model", "<u4"),
+                                     ("identified", "<u4"), ("tries", "<u4")], align=True)
+assert RIG_SUBJECT_RECORD_DTYPE.itemsize == 184 and RIG_SUBJECT_RECORD_DTYPE.fields["ident"][1] == 128
+
+
 class RigFitTrackParams(C.Structure):
     """dh_rig_fit_track_params"""
     _fields_ = [("iterations_tracked", C.c_uint32), ("keep_points", C.c_uint32), ("rms_max", C.c_double), ("max_jump", C.c_double),
@@ -283,6 +292,10 @@ EXPORTS = [
     "dh_subject_fit_tracker_state", "dh_subject_fit_tracker_info", "dh_subject_fit_tracker_set_enrolled", "dh_subject_fit_tracker_bind",
     "dh_subject_fit_tracker_step_poses", "dh_subject_fit_tracker_step_poses_device", "dh_subject_fit_tracker_step",
     "dh_subject_fit_tracker_step_device",
+    "dh_rig_subject_fit_tracker_create", "dh_rig_subject_fit_tracker_destroy", "dh_rig_subject_fit_tracker_reset",
+    "dh_rig_subject_fit_tracker_state", "dh_rig_subject_fit_tracker_info", "dh_rig_subject_fit_tracker_set_enrolled",
+    "dh_rig_subject_fit_tracker_bind", "dh_rig_subject_fit_tracker_step_persons", "dh_rig_subject_fit_tracker_step_persons_device",
+    "dh_rig_subject_fit_tracker_step", "dh_rig_subject_fit_tracker_step_device",
 ]
 
 

@@ -20,7 +20,7 @@ SOURCES = ["dh_api.hip", "dh_api_train.hip", "dh_api_render.hip", "dh_api_fit.hi
            "k_vote.hip", "k_cluster.hip", "k_aux.hip", "dh_train.cpp", "k_train.hip", "k_track.hip", "k_support.hip", "k_heads.hip",
            "k_track_heads.hip", "k_rig.hip", "k_render.hip", "k_fit.hip", "k_fit_track.hip", "k_fit_shape.hip", "k_fit_views.hip",
            "k_rig_fit_track.hip", "k_fit_shape_views.hip", "k_calib_views.hip", "k_subjects.hip", "k_surface.hip", "k_ident.hip",
-           "k_ident_views.hip", "k_subject_track.hip"]
+           "k_ident_views.hip", "k_subject_track.hip", "k_rig_subject_track.hip"]
 HEADERS = ["dh_internal.h", "dh_host.h", "dh_train.h", "dh_device.h", "dh_track.h", "dh_track_heads.h", "dh_rig.h", "dh_render.h", "dh_fit.h",
            "dh_fit_device.h", "dh_rig_fit.h", "dh_runtime.h", "dh_runtime_fit.h", "dh_runtime_track.h",
            os.path.join("..", "..", "include", "depthhead_hip.h")]

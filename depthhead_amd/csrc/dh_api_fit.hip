@@ -1069,6 +1069,9 @@ void dh_fit_subjects_view_(const dh_fit_subjects *set, SubjectsView *v, FitModel
 int dh_ident_params_check_(const dh_ident_params *in, dh_ident_params *out, const char *who) {
     return ident_params_check(in, DH_IDENT_DEFAULT_MAX_RMS, out, who);
 }
+int dh_ident_views_params_check_(const dh_ident_params *in, dh_ident_params *out, const char *who) {
+    return ident_params_check(in, DH_IDENT_VIEWS_DEFAULT_MAX_RMS, out, who);
+}
 // The half of an IdentArgs or IdentViewsArgs that the set, the subject count and the (checked) params fill.
 template <typename G>
 static void ident_args_common(G &g, const dh_fit_subjects *set, uint32_t n_subjects, const dh_ident_params &prm) {

@@ -1,7 +1,7 @@
 // dh_api_fit_track.hip -- the fit trackers' runtime: what both share (the angle table, FitTrackerCore, the creation check, the
-// host form of a step), the camera fit tracker, the rig fit tracker (section 22) and the subject fit tracker
-// (section 29) in their host and _device forms.  Kernels: k_fit_track.hip, k_rig_fit_track.hip, k_subject_track.hip, and the _sched
-// launches of k_fit.hip and k_fit_views.hip.  Shares
+// host form of a step), the camera fit tracker, the rig fit tracker (section 22), the subject fit tracker
+// (section 29) and the rig subject fit tracker (section 30) in their host and _device forms.  Kernels: k_fit_track.hip,
+// k_rig_fit_track.hip, k_subject_track.hip, k_rig_subject_track.hip, and the _sched launches of k_fit.hip and k_fit_views.hip.  Shares
 // dh_runtime.h with every runtime unit, dh_runtime_fit.h with the fit family (dh_api_fit.hip), and dh_runtime_track.h with the
 // trackers in dh_api.hip, which also defines the three functions of that header a whole step calls.
 #include <math.h>
@@ -271,7 +271,8 @@ static int rig_fit_track_params_default_(dh_rig_fit_track_params *p) {
 
 // A FitTrackerCore (section 19) whose state is per rig (DH_RIG_MAX_TRACKS entries each) and whose units are the slots; every
 // device buffer of a step is sized by the rig table and allocated at creation.
-struct dh_rig_fit_tracker : FitTrackerCore {
+// What the rig fit tracker and the rig subject fit tracker (section 30) share: everything but the records and what a binding needs.
+struct RigFitTrackerBase : FitTrackerCore {
     const dh_rig *rig = nullptr;
     const dh_fit_views *views = nullptr;
     dh_rig_fit_track_params prm{};
@@ -283,11 +284,24 @@ struct dh_rig_fit_tracker : FitTrackerCore {
     Buf<uint32_t> n_heads, ids, n_persons;
     Buf<dh_rig_person> persons;          // [n_rigs][DH_RIG_MAX_PERSONS]
     Buf<dh_rig_track> tracks;            // [n_rigs][DH_RIG_MAX_TRACKS]
-    Buf<dh_rig_fit_record> records;      // [slots]
+    // the tables, the params and every buffer above for n cameras
+    int alloc_rig(const dh_rig *rig_, const dh_fit_views *views_, const dh_rig_fit_track_params &prm_, size_t n) {
+        rig = rig_; views = views_; prm = prm_;
+        const size_t ng = (size_t)rig->n_rigs, slots = ng * DH_RIG_MAX_TRACKS;
+        TRY(state.alloc(slots));
+        TRY(start.alloc(slots)); TRY(fit_out.alloc(slots)); TRY(fit_rec.alloc(slots));
+        TRY(who.alloc(slots));
+        TRY(heads.alloc(n * DH_MAX_HEADS)); TRY(n_heads.alloc(n)); TRY(ids.alloc(n * DH_MAX_HEADS));
+        TRY(n_persons.alloc(ng)); TRY(persons.alloc(ng * DH_RIG_MAX_PERSONS)); TRY(tracks.alloc(ng * DH_RIG_MAX_TRACKS));
+        return DH_OK;
+    }
     int clear(size_t g0, size_t m, hipStream_t st) {
         HIP_TRY(hipMemsetAsync(state.get() + g0 * DH_RIG_MAX_TRACKS, 0, m * DH_RIG_MAX_TRACKS * sizeof(dh_rig_fit_state), st));
         return DH_OK;
     }
+};
+struct dh_rig_fit_tracker : RigFitTrackerBase {
+    Buf<dh_rig_fit_record> records;      // [slots]
 };
 static int rig_fit_tracker_create_(const dh_rig *rig, const dh_fit_views *views, const dh_fit_model *m, float scale, uint32_t flags,
                                    const dh_rig_fit_track_params *params, dh_rig_fit_tracker **out) {
@@ -316,12 +330,7 @@ static int rig_fit_tracker_create_(const dh_rig *rig, const dh_fit_views *views,
                     (unsigned long long)((uint64_t)largest * m->n), m->n, DH_FIT_MAX_POINTS);
     const size_t ng = (size_t)rig->n_rigs, slots = ng * DH_RIG_MAX_TRACKS;
     return create_tracker(rig->cams, out, [&](dh_rig_fit_tracker &t, size_t n) -> int {
-        t.rig = rig; t.views = views; t.prm = prm;
-        TRY(t.state.alloc(slots));
-        TRY(t.start.alloc(slots)); TRY(t.fit_out.alloc(slots)); TRY(t.fit_rec.alloc(slots));
-        TRY(t.who.alloc(slots));
-        TRY(t.heads.alloc(n * DH_MAX_HEADS)); TRY(t.n_heads.alloc(n)); TRY(t.ids.alloc(n * DH_MAX_HEADS));
-        TRY(t.n_persons.alloc(ng)); TRY(t.persons.alloc(ng * DH_RIG_MAX_PERSONS)); TRY(t.tracks.alloc(ng * DH_RIG_MAX_TRACKS));
+        TRY(t.alloc_rig(rig, views, prm, n));
         TRY(t.records.alloc(slots));
         return t.init_fit(m, scale, flags, prm.rms_max, prm.max_jump, slots);
     }, ng);
@@ -338,7 +347,7 @@ static int rig_fit_tracker_state_(dh_rig_fit_tracker *t, dh_rig_fit_state *state
     });
 }
 // The refusals of a step that are the tracker's own, before anything is launched.
-static int rig_fit_check(const dh_rig_fit_tracker *t, const void *frames, int w, int h, int max_heads, const void *n_heads, const void *heads,
+static int rig_fit_check(const RigFitTrackerBase *t, const void *frames, int w, int h, int max_heads, const void *n_heads, const void *heads,
                          const void *n_persons, const void *persons, const dh_fit_params *in, const void *records, dh_fit_params *prm,
                          const char *who) {
     if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
@@ -350,12 +359,10 @@ static int rig_fit_check(const dh_rig_fit_tracker *t, const void *frames, int w,
     if (max_heads < 1 || max_heads > DH_MAX_HEADS) return fail(DH_EINVAL, "%s: max_heads %d outside 1 .. %d", who, max_heads, DH_MAX_HEADS);
     return fit_params_check(in, prm, who);
 }
-// Steps 0 - 6 for every rig, on device arrays and stream s (arguments checked, device selected): three launches, and nothing
-// uploaded but their arguments.
-static int rig_fit_enqueue(dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
-                           const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons,
-                           const dh_fit_params &prm, dh_rig_fit_record *records, hipStream_t s) {
-    RigFitArgs a;
+// The argument blocks of a step's seed and update kernels (a; its records are the caller's to set) and of the fit between them (f).
+static void rig_fit_args(RigFitTrackerBase *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
+                         const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons,
+                         const dh_fit_params &prm, RigFitArgs &a, FitViewsSchedArgs &f) {
     memset(&a, 0, sizeof a);
     a.n_rigs = t->rig->n_rigs; a.n_cams = t->n; a.max_heads = max_heads;
     a.flags = t->flags; a.scale = t->scale; a.prm = t->prm; a.rms_lim = t->rms_lim; a.jump2 = t->jump2;
@@ -363,8 +370,7 @@ static int rig_fit_enqueue(dh_rig_fit_tracker *t, const uint16_t *frames, int w,
     a.angles = t->angles.get(); a.rig_begin = t->rig->rig_begin.get(); a.views = t->views->dev.get();
     a.present = present; a.n_heads = n_heads; a.heads = heads; a.n_persons = n_persons; a.persons = persons;
     a.state = t->state.get(); a.start = t->start.get(); a.sched = t->sched.get(); a.seed = t->seed.get(); a.who = t->who.get();
-    a.fit_out = t->fit_out.get(); a.fit_rec = t->fit_rec.get(); a.records = records;
-    FitViewsSchedArgs f;
+    a.fit_out = t->fit_out.get(); a.fit_rec = t->fit_rec.get();
     memset(&f, 0, sizeof f);
     f.f.frames = frames; f.f.n = t->n; f.f.w = w; f.f.h = h;
     f.f.cams = t->cams->dev.get(); f.f.views = t->views->dev.get(); f.f.models = t->models.get();
@@ -372,6 +378,16 @@ static int rig_fit_enqueue(dh_rig_fit_tracker *t, const uint16_t *frames, int w,
     fit_args_params(f.f, prm);                                   // (k_fit_views_sched reads coarse and full per slot from sched)
     f.f.out = t->fit_out.get(); f.f.rec = t->fit_rec.get();
     f.sched = t->sched.get(); f.seed = t->seed.get(); f.group = DH_RIG_MAX_TRACKS;
+}
+// Steps 0 - 6 for every rig, on device arrays and stream s (arguments checked, device selected): three launches, and nothing
+// uploaded but their arguments.
+static int rig_fit_enqueue(dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
+                           const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons,
+                           const dh_fit_params &prm, dh_rig_fit_record *records, hipStream_t s) {
+    RigFitArgs a;
+    FitViewsSchedArgs f;
+    rig_fit_args(t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, prm, a, f);
+    a.records = records;
     TRY(hip_step(dh_launch_rig_fit_seed(a, s), "k_rig_fit_seed"));
     TRY(hip_step(dh_launch_fit_views_sched(f, s), "k_fit_views_sched"));
     TRY(hip_step(dh_launch_rig_fit_update(a, s), "k_rig_fit_update"));
@@ -389,7 +405,7 @@ static int rig_fit_tracker_step_persons_device_(dh_rig_fit_tracker *t, const uin
 }
 // The refusals of the whole step beyond the core step's: the rig tracker must step the tracker's own rig table and must not
 // drop an id sooner than the tracker stops coasting on it.
-static int rig_fit_step_check(const dh_predictor *p, const dh_rig_fit_tracker *t, const dh_rig_tracker *rt, const void *frames, int w, int h,
+static int rig_fit_step_check(const dh_predictor *p, const RigFitTrackerBase *t, const dh_rig_tracker *rt, const void *frames, int w, int h,
                               const void *n_heads, const void *heads, const void *ids, const void *n_persons, const void *persons,
                               const dh_fit_params *in, const void *records, dh_fit_params *prm, const char *who) {
     if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
@@ -416,9 +432,11 @@ static int rig_fit_tracker_step_device_(dh_predictor *p, dh_rig_fit_tracker *t, 
 }
 // The host forms: everything staged through the tracker's buffers on its own stream; synchronous.  p NULL: the core step on
 // the caller's heads and persons; else the rig step first (its device form, on the staged frames), its outputs copied back too.
-static int rig_fit_host(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present,
+// T: either rig tracker; enqueue: its core step on device arrays (rig_fit_enqueue's parameter list).
+template <typename T, typename Rec, typename Enqueue>
+static int rig_fit_host(dh_predictor *p, T *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present,
                         int max_heads, const dh_fit_params &prm, uint32_t *n_heads, dh_head *heads, uint32_t *ids, uint32_t *n_persons,
-                        dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records) {
+                        dh_rig_person *persons, dh_rig_track *tracks, Rec *records, Enqueue enqueue) {
     const size_t n = (size_t)t->n, ng = (size_t)t->rig->n_rigs, mh = (size_t)max_heads;
     return fit_tracker_host(t, frames, w, h, present, [&](hipStream_t s) -> int {
         if (p) return DH_OK;
@@ -430,8 +448,8 @@ static int rig_fit_host(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *
     }, [&](const uint16_t *fr, const uint8_t *pr, hipStream_t s) -> int {
         if (p) TRY(dh_rig_tracker_step_device_(p, rt, fr, w, h, pr, t->n_heads.get(), t->heads.get(), t->ids.get(), t->n_persons.get(),
                                             t->persons.get(), tracks ? t->tracks.get() : nullptr, s));
-        return rig_fit_enqueue(t, fr, w, h, pr, max_heads, t->n_heads.get(), t->heads.get(), t->n_persons.get(), t->persons.get(), prm,
-                               t->records.get(), s);
+        return enqueue(t, fr, w, h, pr, max_heads, t->n_heads.get(), t->heads.get(), t->n_persons.get(), t->persons.get(), prm,
+                       t->records.get(), s);
     }, [&](hipStream_t s) -> int {
         if (!p) return DH_OK;
         HIP_TRY(hipMemcpyAsync(n_heads, t->n_heads.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -449,7 +467,7 @@ static int rig_fit_tracker_step_persons_(dh_rig_fit_tracker *t, const uint16_t *
     dh_fit_params prm;
     TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm, "dh_rig_fit_tracker_step_persons"));
     return rig_fit_host(nullptr, t, nullptr, frames, w, h, present, max_heads, prm, const_cast<uint32_t *>(n_heads), const_cast<dh_head *>(heads),
-                        nullptr, const_cast<uint32_t *>(n_persons), const_cast<dh_rig_person *>(persons), nullptr, records);
+                        nullptr, const_cast<uint32_t *>(n_persons), const_cast<dh_rig_person *>(persons), nullptr, records, rig_fit_enqueue);
 }
 static int rig_fit_tracker_step_(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
                                  const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *ids,
@@ -459,7 +477,7 @@ static int rig_fit_tracker_step_(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_
     TRY(rig_fit_step_check(p, t, rt, frames, w, h, n_heads, heads, ids, n_persons, persons, fit_params, records, &prm, who));
     if (t->cams->device != dh_predictor_device_(p))
         return fail(DH_EINVAL, "%s: rig table on device %d, predictor on device %d", who, t->cams->device, dh_predictor_device_(p));
-    return rig_fit_host(p, t, rt, frames, w, h, present, rt->prm.max_heads, prm, n_heads, heads, ids, n_persons, persons, tracks, records);
+    return rig_fit_host(p, t, rt, frames, w, h, present, rt->prm.max_heads, prm, n_heads, heads, ids, n_persons, persons, tracks, records, rig_fit_enqueue);
 }
 
 // ------------------------------------------------------------------ following each tracked head with its own subject's model
@@ -470,22 +488,69 @@ static int subject_track_params_default_(dh_subject_track_params *p) {
     return DH_OK;
 }
 
-// A FitTrackerCore whose model table holds the set's S models and the generic one at index S (core.model: the generic one), whose
-// state carries each camera's binding, and which owns what an identification needs: the mask, the list and the pair scratch.
-struct dh_subject_fit_tracker : FitTrackerCore {
+// What the subject fit tracker and the rig subject fit tracker (section 30) hold beside their fit tracker: the set and the params
+// of a binding, and what an identification needs whatever its score record is -- the mask, the list and the poses of the pair
+// scratch.  A unit is what may want identification: a camera, a slot of a rig.
+struct SubjectParts {
     const dh_fit_subjects *set = nullptr;
     SubjectsView sv{};
-    dh_fit_track_params prm{};
     dh_ident_params iprm{};
     dh_subject_track_params sprm{};
-    uint32_t grid = 0;                   // workgroups of k_subject_track_score
+    uint32_t grid = 0;                   // workgroups of the score kernel
+    Buf<uint8_t> enrolled;               // [S]: ones for "all"
+    Buf<uint32_t> want, n_want, wants;   // [units], [1], [units]
+    Buf<float> pose;                     // [units][S][12]
+    // the mask on the device, ordered on st; the caller's memory is free when this returns
+    int put_enrolled(const uint8_t *mask, hipStream_t st) {
+        if (!mask) { HIP_TRY(hipMemsetAsync(enrolled.get(), 1, sv.n_subjects, st)); return DH_OK; }
+        HIP_TRY(hipMemcpyAsync(enrolled.get(), mask, sv.n_subjects, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return DH_OK;
+    }
+    // Everything above for `units` units on `device` (the grid: min(units * S, 2 * the compute units)), and in `models` the table
+    // of S + 1 models -- the set's, then the generic one -- in place of a FitTrackerCore's one.
+    int init_subjects(const dh_fit_subjects *set_, const dh_fit_model *m, const dh_ident_params &iprm_, const dh_subject_track_params &sprm_,
+                      size_t units, int device, Buf<FitModel> &models, const uint8_t *mask) {
+        set = set_; iprm = iprm_; sprm = sprm_;
+        std::vector<FitModel> table;
+        dh_fit_subjects_view_(set, &sv, nullptr);
+        const uint32_t S = sv.n_subjects;
+        table.resize((size_t)S + 1);
+        dh_fit_subjects_view_(set, &sv, table.data());
+        table[S] = FitModel{m->pts.get(), m->nrm.get(), m->n, 0};
+        const uint64_t pairs = (uint64_t)units * S;
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, device));
+        grid = (uint32_t)std::min<uint64_t>(pairs, 2ull * (uint64_t)std::max(prop.multiProcessorCount, 1));
+        TRY(enrolled.alloc(S)); TRY(want.alloc(units)); TRY(n_want.alloc(1)); TRY(wants.alloc(units));
+        TRY(pose.alloc((size_t)pairs * 12));
+        TRY(models.alloc((size_t)S + 1));
+        HIP_TRY(hipMemcpy(models.get(), table.data(), table.size() * sizeof(FitModel), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(n_want.get(), 0, sizeof(uint32_t)));
+        HIP_TRY(hipMemset(wants.get(), 0, units * sizeof(uint32_t)));
+        return put_enrolled(mask, nullptr);
+    }
+    // The half of an IdentArgs or IdentViewsArgs that the set and the tracker's params fill.
+    template <typename G>
+    void ident_args(G &q) const {
+        q.f.coarse = 0; q.f.full = iprm.iterations; q.f.min_points = iprm.min_points;
+        q.f.gate[0] = iprm.gate; q.f.gate[1] = iprm.gate;
+        q.f.lam1 = 1.0 + iprm.lambda;
+        q.models = sv.table; q.np = sv.n; q.n_subjects = sv.n_subjects;
+        q.radius = sv.radius; q.largest = sv.largest;
+        q.enrolled = enrolled.get(); q.pose = pose.get();
+        q.max_ms = iprm.max_rms * iprm.max_rms; q.min_ratio = iprm.min_ratio;
+    }
+};
+
+// A FitTrackerCore whose model table holds the set's S models and the generic one at index S (core.model: the generic one), whose
+// state carries each camera's binding, and which owns what an identification needs: the mask, the list and the pair scratch.
+struct dh_subject_fit_tracker : FitTrackerCore, SubjectParts {
+    dh_fit_track_params prm{};
     Buf<dh_subject_track_state> state;   // [n]
     Buf<dh_render_instance> start, fit_out;
     Buf<dh_fit_record> fit_rec;
-    Buf<uint8_t> enrolled;               // [S]: ones for "all"
-    Buf<uint32_t> want, n_want, wants;   // [n], [1], [n]
     Buf<dh_fit_record> score;            // [n][S]
-    Buf<float> pose;                     // [n][S][12]
     Buf<dh_pose> poses;                  // host forms
     Buf<dh_support> support;
     Buf<dh_subject_track_record> records;
@@ -493,13 +558,6 @@ struct dh_subject_fit_tracker : FitTrackerCore {
     int clear(size_t c0, size_t m, hipStream_t st) {
         HIP_TRY(hipMemsetAsync(state.get() + c0, 0, m * sizeof(dh_subject_track_state), st));
         HIP_TRY(hipMemset2DAsync(&state.get()[c0].subject, sizeof(dh_subject_track_state), 0xFF, sizeof(uint32_t), m, st));
-        return DH_OK;
-    }
-    // the mask on the device, ordered on st; the caller's memory is free when this returns
-    int put_enrolled(const uint8_t *mask, hipStream_t st) {
-        if (!mask) { HIP_TRY(hipMemsetAsync(enrolled.get(), 1, sv.n_subjects, st)); return DH_OK; }
-        HIP_TRY(hipMemcpyAsync(enrolled.get(), mask, sv.n_subjects, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
         return DH_OK;
     }
 };
@@ -540,26 +598,13 @@ static int subject_fit_tracker_create_(const dh_cameras *c, const dh_fit_subject
     if (pairs > DH_IDENT_MAX_PAIRS)
         return fail(DH_EINVAL, "%s: %d cameras times %u subjects exceed %u pairs", who, c->n, sv.n_subjects, DH_IDENT_MAX_PAIRS);
     return create_tracker(c, out, [&](dh_subject_fit_tracker &t, size_t n) -> int {
-        const uint32_t S = sv.n_subjects;
-        t.set = set; t.sv = sv; t.prm = prm; t.iprm = iprm; t.sprm = sprm;
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, c->device));
-        t.grid = (uint32_t)std::min<uint64_t>(pairs, 2ull * (uint64_t)std::max(prop.multiProcessorCount, 1));
+        t.prm = prm;
         TRY(t.state.alloc(n));
         TRY(t.start.alloc(n)); TRY(t.fit_out.alloc(n)); TRY(t.fit_rec.alloc(n));
-        TRY(t.enrolled.alloc(S)); TRY(t.want.alloc(n)); TRY(t.n_want.alloc(1)); TRY(t.wants.alloc(n));
-        TRY(t.score.alloc((size_t)pairs)); TRY(t.pose.alloc((size_t)pairs * 12));
+        TRY(t.score.alloc((size_t)pairs));
         TRY(t.poses.alloc(n)); TRY(t.support.alloc(n)); TRY(t.records.alloc(n));
         TRY(t.init_fit(m, scale, flags, prm.rms_max, prm.max_jump, n));
-        // the table of S + 1 models in place of the core's one
-        std::vector<FitModel> table((size_t)S + 1);
-        dh_fit_subjects_view_(set, &t.sv, table.data());
-        table[S] = FitModel{m->pts.get(), m->nrm.get(), m->n, 0};
-        TRY(t.models.alloc((size_t)S + 1));
-        HIP_TRY(hipMemcpy(t.models.get(), table.data(), table.size() * sizeof(FitModel), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(t.n_want.get(), 0, sizeof(uint32_t)));
-        HIP_TRY(hipMemset(t.wants.get(), 0, n * sizeof(uint32_t)));
-        return t.put_enrolled(enrolled, nullptr);
+        return t.init_subjects(set, m, iprm, sprm, n, c->device, t.models, enrolled);
     });
 }
 static int subject_fit_tracker_destroy_(dh_subject_fit_tracker *t) { return destroy_fit_tracker(t); }
@@ -630,14 +675,8 @@ static int subject_track_enqueue(dh_subject_fit_tracker *t, const uint16_t *fram
     IdentArgs &q = g.q;
     q.f.frames = frames; q.f.n = t->n; q.f.w = w; q.f.h = h;
     q.f.cams = t->cams->dev.get(); q.f.inst = t->fit_out.get(); q.f.n_inst = (uint32_t)t->n;
-    q.f.coarse = 0; q.f.full = t->iprm.iterations; q.f.min_points = t->iprm.min_points;
-    q.f.gate[0] = t->iprm.gate; q.f.gate[1] = t->iprm.gate;
-    q.f.lam1 = 1.0 + t->iprm.lambda;
-    q.models = t->sv.table; q.np = t->sv.n; q.n_subjects = t->sv.n_subjects;
-    q.radius = t->sv.radius; q.largest = t->sv.largest;
-    q.enrolled = t->enrolled.get(); q.fit_rec = t->fit_rec.get();
-    q.score = t->score.get(); q.pose = t->pose.get();
-    q.max_ms = t->iprm.max_rms * t->iprm.max_rms; q.min_ratio = t->iprm.min_ratio;
+    t->ident_args(q);
+    q.fit_rec = t->fit_rec.get(); q.score = t->score.get();
     g.state = t->state.get(); g.records = records;
     g.retry = t->sprm.retry; g.max_tries = t->sprm.max_tries;
     g.want = t->want.get(); g.n_want = t->n_want.get(); g.wants = t->wants.get();
@@ -710,6 +749,185 @@ static int subject_fit_tracker_step_(dh_predictor *p, dh_subject_fit_tracker *t,
     return subject_track_host(p, t, frames, w, h, present, radius, prm, poses_out, support_out, records);
 }
 
+// ------------------------------------------------------------------ following each rig person with its own subject's model
+// The rig fit tracker's core with the subject trackers' parts: the entries' dh_rig_fit_state in `state`, the four words of their
+// bindings beside it in `bound`, and the pair scratch of slots * S multi-view scores.
+struct dh_rig_subject_fit_tracker : RigFitTrackerBase, SubjectParts {
+    Buf<SubjectBinding> bound;           // [slots]
+    Buf<dh_view_fit_record> score;       // [slots][S]
+    Buf<dh_rig_subject_record> records;  // host forms: [slots]
+    // zeros, and DH_IDENT_UNKNOWN (every byte 0xFF) in the subject word of each binding
+    int clear(size_t g0, size_t m, hipStream_t st) {
+        TRY(RigFitTrackerBase::clear(g0, m, st));
+        SubjectBinding *b = bound.get() + g0 * DH_RIG_MAX_TRACKS;
+        HIP_TRY(hipMemsetAsync(b, 0, m * DH_RIG_MAX_TRACKS * sizeof(SubjectBinding), st));
+        HIP_TRY(hipMemset2DAsync(&b->subject, sizeof(SubjectBinding), 0xFF, sizeof(uint32_t), m * DH_RIG_MAX_TRACKS, st));
+        return DH_OK;
+    }
+};
+static int rig_subject_fit_tracker_create_(const dh_rig *rig, const dh_fit_views *views, const dh_fit_subjects *set, const dh_fit_model *m,
+                                           float scale, uint32_t flags, const dh_rig_fit_track_params *track_params,
+                                           const dh_ident_params *ident_params, const dh_subject_track_params *params,
+                                           const uint8_t *enrolled, dh_rig_subject_fit_tracker **out) {
+    const char *who = "dh_rig_subject_fit_tracker_create";
+    if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
+    *out = nullptr;
+    dh_rig_fit_track_params prm;
+    (void)rig_fit_track_params_default_(&prm);
+    if (track_params) prm = *track_params;
+    dh_subject_track_params sprm;
+    (void)subject_track_params_default_(&sprm);
+    if (params) sprm = *params;
+    dh_ident_params iprm;
+    SubjectsView sv{};
+    TRY(fit_tracker_create_check(prm, scale, flags, m, [&]() -> int {
+        if (prm.max_coast > prm.max_misses)
+            return fail(DH_EINVAL, "%s: max_coast %u above the max_misses %u the ids come from", who, prm.max_coast, prm.max_misses);
+        return DH_OK;
+    }, [&]() -> int {
+        if (!rig) return fail(DH_EINVAL, "%s: NULL rig table", who);
+        if (!views) return fail(DH_EINVAL, "%s: NULL view table", who);
+        if (!set) return fail(DH_EINVAL, "%s: NULL subject set", who);
+        if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
+        if (views->cams != rig->cams) return fail(DH_EINVAL, "%s: the rig table and the view table are bound to different camera tables", who);
+        TRY(dh_ident_views_params_check_(ident_params, &iprm, who));
+        if (sprm.reserved[0] || sprm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the dh_subject_track_params is not 0", who);
+        dh_fit_subjects_view_(set, &sv, nullptr);
+        const int device = rig->cams->device;
+        if (sv.device != device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the tables on %d", who, sv.device, device);
+        if (m->device != device) return fail(DH_EINVAL, "%s: the model lives on device %d, the tables on %d", who, m->device, device);
+        if (m->n != sv.n) return fail(DH_EINVAL, "%s: the generic model has %u points, a model of the set %u", who, m->n, sv.n);
+        const double extent = fabs((double)scale) * sv.radius;
+        if (extent > DH_FIT_MAX_EXTENT)
+            return fail(DH_EINVAL, "%s: a model of the set may span %g mm from its origin (limit %g)", who, extent, DH_FIT_MAX_EXTENT);
+        return DH_OK;
+    }, who));
+    const int64_t largest = rig->largest;
+    if ((uint64_t)largest * sv.n > DH_FIT_MAX_POINTS)
+        return fail(DH_EINVAL, "%s: a rig of %lld cameras sums %llu terms of a %u-point model, above %u", who, (long long)largest,
+                    (unsigned long long)((uint64_t)largest * sv.n), sv.n, DH_FIT_MAX_POINTS);
+    const size_t ng = (size_t)rig->n_rigs, slots = ng * DH_RIG_MAX_TRACKS;
+    const uint64_t pairs = (uint64_t)slots * sv.n_subjects;
+    if (pairs > DH_IDENT_MAX_PAIRS)
+        return fail(DH_EINVAL, "%s: %d rigs of %d slots times %u subjects exceed %u pairs", who, rig->n_rigs, DH_RIG_MAX_TRACKS, sv.n_subjects,
+                    DH_IDENT_MAX_PAIRS);
+    return create_tracker(rig->cams, out, [&](dh_rig_subject_fit_tracker &t, size_t n) -> int {
+        TRY(t.alloc_rig(rig, views, prm, n));
+        TRY(t.bound.alloc(slots)); TRY(t.score.alloc((size_t)pairs)); TRY(t.records.alloc(slots));
+        TRY(t.init_fit(m, scale, flags, prm.rms_max, prm.max_jump, slots));
+        return t.init_subjects(set, m, iprm, sprm, slots, rig->cams->device, t.models, enrolled);
+    }, ng);
+}
+static int rig_subject_fit_tracker_destroy_(dh_rig_subject_fit_tracker *t) { return destroy_fit_tracker(t); }
+static int rig_subject_fit_tracker_reset_(dh_rig_subject_fit_tracker *t, int rig, void *stream) {
+    return reset_tracker(t, rig, stream, "dh_rig_subject_fit_tracker_reset", t ? t->rig->n_rigs : 0, "rig");
+}
+// (the two device arrays of an entry, interleaved)
+static int rig_subject_fit_tracker_state_(dh_rig_subject_fit_tracker *t, dh_rig_subject_state *states) {
+    if (t && !states) return fail(DH_EINVAL, "dh_rig_subject_fit_tracker_state: NULL argument");
+    return read_tracker(t, "dh_rig_subject_fit_tracker_state", [&](size_t) -> int {
+        const size_t slots = (size_t)t->rig->n_rigs * DH_RIG_MAX_TRACKS;
+        HIP_TRY(hipMemcpy2D(&states->fit, sizeof *states, t->state.get(), sizeof(dh_rig_fit_state), sizeof(dh_rig_fit_state), slots,
+                            hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy2D(&states->subject, sizeof *states, t->bound.get(), sizeof(SubjectBinding), sizeof(SubjectBinding), slots,
+                            hipMemcpyDeviceToHost));
+        return DH_OK;
+    });
+}
+static int rig_subject_fit_tracker_info_(const dh_rig_subject_fit_tracker *t, int *n_rigs, uint32_t *n_subjects, uint32_t *score_workgroups) {
+    if (!t) return fail(DH_EINVAL, "dh_rig_subject_fit_tracker_info: NULL tracker");
+    if (n_rigs) *n_rigs = t->rig->n_rigs;
+    if (n_subjects) *n_subjects = t->sv.n_subjects;
+    if (score_workgroups) *score_workgroups = t->grid;
+    return DH_OK;
+}
+static int rig_subject_fit_tracker_set_enrolled_(dh_rig_subject_fit_tracker *t, const uint8_t *enrolled, void *stream) {
+    if (!t) return fail(DH_EINVAL, "dh_rig_subject_fit_tracker_set_enrolled: NULL tracker");
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return t->put_enrolled(enrolled, (hipStream_t)stream);
+}
+static int rig_subject_fit_tracker_bind_(dh_rig_subject_fit_tracker *t, int rig, uint32_t id, uint32_t subject, void *stream) {
+    const char *who = "dh_rig_subject_fit_tracker_bind";
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
+    if (rig < 0 || rig >= t->rig->n_rigs) return fail(DH_EINVAL, "%s: rig %d of %d", who, rig, t->rig->n_rigs);
+    if (id == 0) return fail(DH_EINVAL, "%s: id 0 names no entry", who);
+    if (subject >= t->sv.n_subjects && subject != DH_IDENT_UNKNOWN)
+        return fail(DH_EINVAL, "%s: subject %u of %u (DH_IDENT_UNKNOWN unbinds)", who, subject, t->sv.n_subjects);
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return hip_step(dh_launch_rig_subject_set(t->state.get(), t->bound.get(), rig, id, subject, (hipStream_t)stream), "k_rig_subject_set");
+}
+// One step of every rig on device arrays and stream s (arguments checked, device selected): five launches, a linear chain.
+static int rig_subject_enqueue(dh_rig_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
+                               const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons,
+                               const dh_fit_params &prm, dh_rig_subject_record *records, hipStream_t s) {
+    RigSubjectArgs g;
+    memset(&g, 0, sizeof g);
+    FitViewsSchedArgs f;
+    rig_fit_args(t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, prm, g.a, f);
+    IdentViewsArgs &q = g.q;
+    q.f.frames = frames; q.f.n = t->n; q.f.w = w; q.f.h = h;
+    q.f.cams = t->cams->dev.get(); q.f.views = t->views->dev.get();
+    q.f.inst = t->fit_out.get(); q.f.n_inst = f.f.n_inst;
+    t->ident_args(q);
+    q.n_sets = 1;
+    q.fit_rec = t->fit_rec.get(); q.score = t->score.get();
+    g.bound = t->bound.get(); g.records = records;
+    g.retry = t->sprm.retry; g.max_tries = t->sprm.max_tries;
+    g.want = t->want.get(); g.n_want = t->n_want.get(); g.wants = t->wants.get();
+    g.grid = t->grid;
+    TRY(hip_step(dh_launch_rig_subject_seed(g, s), "k_rig_subject_seed"));
+    TRY(hip_step(dh_launch_fit_views_sched(f, s), "k_fit_views_sched"));
+    TRY(hip_step(dh_launch_rig_subject_update(g, s), "k_rig_subject_update"));
+    TRY(hip_step(dh_launch_rig_subject_score(g, s), "k_rig_subject_score"));
+    TRY(hip_step(dh_launch_rig_subject_bind(g, s), "k_rig_subject_bind"));
+    return DH_OK;
+}
+static int rig_subject_fit_tracker_step_persons_device_(dh_rig_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                                        int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons,
+                                                        const dh_rig_person *persons, const dh_fit_params *fit_params,
+                                                        dh_rig_subject_record *records, void *stream) {
+    dh_fit_params prm;
+    TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm,
+                      "dh_rig_subject_fit_tracker_step_persons_device"));
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return rig_subject_enqueue(t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, prm, records, (hipStream_t)stream);
+}
+static int rig_subject_fit_tracker_step_device_(dh_predictor *p, dh_rig_subject_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w,
+                                                int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads,
+                                                uint32_t *ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks,
+                                                dh_rig_subject_record *records, void *stream) {
+    const char *who = "dh_rig_subject_fit_tracker_step_device";
+    dh_fit_params prm;
+    TRY(rig_fit_step_check(p, t, rt, frames, w, h, n_heads, heads, ids, n_persons, persons, fit_params, records, &prm, who));
+    TRY(dh_rig_tracker_step_device_(p, rt, frames, w, h, present, n_heads, heads, ids, n_persons, persons, tracks, stream));
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return rig_subject_enqueue(t, frames, w, h, present, rt->prm.max_heads, n_heads, heads, n_persons, persons, prm, records, (hipStream_t)stream);
+}
+static int rig_subject_fit_tracker_step_persons_(dh_rig_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                                 int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons,
+                                                 const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_subject_record *records) {
+    dh_fit_params prm;
+    TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm,
+                      "dh_rig_subject_fit_tracker_step_persons"));
+    return rig_fit_host(nullptr, t, nullptr, frames, w, h, present, max_heads, prm, const_cast<uint32_t *>(n_heads), const_cast<dh_head *>(heads),
+                        nullptr, const_cast<uint32_t *>(n_persons), const_cast<dh_rig_person *>(persons), nullptr, records, rig_subject_enqueue);
+}
+static int rig_subject_fit_tracker_step_(dh_predictor *p, dh_rig_subject_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
+                                         const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *ids,
+                                         uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_subject_record *records) {
+    const char *who = "dh_rig_subject_fit_tracker_step";
+    dh_fit_params prm;
+    TRY(rig_fit_step_check(p, t, rt, frames, w, h, n_heads, heads, ids, n_persons, persons, fit_params, records, &prm, who));
+    if (t->cams->device != dh_predictor_device_(p))
+        return fail(DH_EINVAL, "%s: rig table on device %d, predictor on device %d", who, t->cams->device, dh_predictor_device_(p));
+    return rig_fit_host(p, t, rt, frames, w, h, present, rt->prm.max_heads, prm, n_heads, heads, ids, n_persons, persons, tracks, records,
+                        rig_subject_enqueue);
+}
+
 // ------------------------------------------------------------------ the C ABI (DH_API: dh_runtime.h)
 DH_API(fit_track_params_default, (dh_fit_track_params *p), (p))
 DH_API(fit_tracker_angles, (double out[DH_FIT_TRACK_ANGLES][2]), (out))
@@ -742,3 +960,14 @@ DH_API(subject_fit_tracker_step_poses, (dh_subject_fit_tracker *t, const uint16_
 DH_API(subject_fit_tracker_step_poses_device, (dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params, dh_subject_track_record *records, void *stream), (t, frames, w, h, present, poses, support, fit_params, records, stream))
 DH_API(subject_fit_tracker_step, (dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_subject_track_record *records), (p, t, frames, w, h, present, radius, fit_params, poses_out, support_out, records))
 DH_API(subject_fit_tracker_step_device, (dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_subject_track_record *records, void *stream), (p, t, frames, w, h, present, radius, fit_params, poses_out, support_out, records, stream))
+DH_API(rig_subject_fit_tracker_create, (const dh_rig *rig, const dh_fit_views *views, const dh_fit_subjects *set, const dh_fit_model *generic, float scale, uint32_t flags, const dh_rig_fit_track_params *track_params, const dh_ident_params *ident_params, const dh_subject_track_params *params, const uint8_t *enrolled, dh_rig_subject_fit_tracker **out), (rig, views, set, generic, scale, flags, track_params, ident_params, params, enrolled, out))
+DH_API(rig_subject_fit_tracker_destroy, (dh_rig_subject_fit_tracker *t), (t))
+DH_API(rig_subject_fit_tracker_reset, (dh_rig_subject_fit_tracker *t, int rig, void *stream), (t, rig, stream))
+DH_API(rig_subject_fit_tracker_state, (dh_rig_subject_fit_tracker *t, dh_rig_subject_state *states), (t, states))
+DH_API(rig_subject_fit_tracker_info, (const dh_rig_subject_fit_tracker *t, int *n_rigs, uint32_t *n_subjects, uint32_t *score_workgroups), (t, n_rigs, n_subjects, score_workgroups))
+DH_API(rig_subject_fit_tracker_set_enrolled, (dh_rig_subject_fit_tracker *t, const uint8_t *enrolled, void *stream), (t, enrolled, stream))
+DH_API(rig_subject_fit_tracker_bind, (dh_rig_subject_fit_tracker *t, int rig, uint32_t id, uint32_t subject, void *stream), (t, rig, id, subject, stream))
+DH_API(rig_subject_fit_tracker_step_persons, (dh_rig_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_subject_record *records), (t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, fit_params, records))
+DH_API(rig_subject_fit_tracker_step_persons_device, (dh_rig_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_subject_record *records, void *stream), (t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, fit_params, records, stream))
+DH_API(rig_subject_fit_tracker_step, (dh_predictor *p, dh_rig_subject_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_subject_record *records), (p, t, rt, frames, w, h, present, fit_params, n_heads, heads, rig_ids, n_persons, persons, tracks, records))
+DH_API(rig_subject_fit_tracker_step_device, (dh_predictor *p, dh_rig_subject_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_subject_record *records, void *stream), (p, t, rt, frames, w, h, present, fit_params, n_heads, heads, rig_ids, n_persons, persons, tracks, records, stream))

@@ -1,9 +1,9 @@
 // dh_fit.h -- what the fit family's kernels (k_fit.hip, k_fit_track.hip, k_fit_shape.hip, k_fit_views.hip, k_rig_fit_track.hip,
-// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip, k_ident.hip, k_ident_views.hip, k_subject_track.hip) share with the host runtime (dh_api_fit.hip, dh_api_fit_track.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
+// k_fit_shape_views.hip, k_calib_views.hip, k_subjects.hip, k_surface.hip, k_ident.hip, k_ident_views.hip, k_subject_track.hip, k_rig_subject_track.hip) share with the host runtime (dh_api_fit.hip, dh_api_fit_track.hip): the argument blocks, table layouts and launchers, the layout of the sums, the seed
 // words of both trackers, and the one test of whether an instance may be fitted (dh_fit_instance_fault: the host's refusals and
 // the shape kernel's skips).  The device arithmetic the kernels share among themselves is in dh_fit_device.h.  Not part of the
 // ABI.  The rules are stated in include/depthhead_hip.h (sections "fitting posed models to depth frames" and after) and
-// DESIGN.md sections 18 - 29.
+// DESIGN.md sections 18 - 30.
 #pragma once
 #include "dh_internal.h"
 #include "dh_rig_fit.h"
@@ -723,6 +723,33 @@ static_assert(sizeof(dh_subject_track_record) == 160, "dh_subject_track_record: 
 // refuses a scale whose product with the set's bound or with the generic radius exceeds DH_FIT_MAX_EXTENT, so every start
 // instance passes the extent test for whichever entry it names.  A wanted pair is section 27's as it stands.
 
+// The four words of a binding (the tail of dh_subject_track_state and of dh_rig_subject_state), and the two places of the rule that
+// change them, stated once for k_subject_track.hip, k_rig_subject_track.hip and tests/host/subject_bind_check.cpp.
+struct SubjectBinding {
+    uint32_t subject, wait, tries, bound_age;
+};
+__host__ __device__ inline uint32_t dh_sat_inc(uint32_t v) { return v == 0xffffffffu ? v : v + 1u; }
+__host__ __device__ inline void dh_subject_unbind(uint32_t &subject, uint32_t &wait, uint32_t &tries, uint32_t &bound_age) {
+    subject = DH_IDENT_UNKNOWN; wait = 0; tries = 0; bound_age = 0;
+}
+// THE BINDING LIFECYCLE (rule 2) of one camera or entry on the state the fit's outcome left: tracked, and whether this step's fit
+// was accepted.  true: the camera or entry wants identification in this step.
+__host__ __device__ inline bool dh_subject_lifecycle(bool tracked, bool accepted, uint32_t max_tries, uint32_t &subject, uint32_t &wait,
+                                                     uint32_t &tries, uint32_t &bound_age) {
+    if (!tracked) { dh_subject_unbind(subject, wait, tries, bound_age); return false; }
+    if (!accepted) return false;
+    if (subject != DH_IDENT_UNKNOWN) { bound_age = dh_sat_inc(bound_age); return false; }
+    if (wait == 0 && (max_tries == 0 || tries < max_tries)) return true;
+    if (wait > 0) wait -= 1;
+    return false;
+}
+// What an identification that ran makes of the words (rule 3): DH_IDENT_OK binds `best`, any other status counts a try and waits.
+__host__ __device__ inline void dh_subject_bind_or_retry(uint32_t status, uint32_t best, uint32_t retry, uint32_t &subject, uint32_t &wait,
+                                                         uint32_t &tries, uint32_t &bound_age) {
+    if (status == DH_IDENT_OK) { subject = best; bound_age = 0; }
+    else { tries = dh_sat_inc(tries); wait = retry; }
+}
+
 // One step's four launches beside k_fit_sched share one block: section 19's (its state and records unused: the state here is
 // 92 bytes a camera, the record 160), section 27's (inst and fit_rec: the step's fitted instances and their records, n_inst the
 // cameras; score and pose: the tracker's scratch of cameras * S pairs; subjects_out, rec and poses_out unused) and the tracker's own.
@@ -741,3 +768,35 @@ hipError_t dh_launch_subject_track_seed(const SubjectTrackArgs &g, hipStream_t s
 hipError_t dh_launch_subject_track_update(const SubjectTrackArgs &g, hipStream_t s);   // one lane per camera
 hipError_t dh_launch_subject_track_score(const SubjectTrackArgs &g, hipStream_t s);    // g.grid workgroups over the list's pairs
 hipError_t dh_launch_subject_track_bind(const SubjectTrackArgs &g, hipStream_t s);     // one wave per camera
+
+// ---- following each rig person with its own subject's model (k_rig_subject_track.hip)
+static_assert(sizeof(dh_rig_subject_state) == 104, "dh_rig_subject_state: 104 bytes");
+static_assert(sizeof(dh_rig_subject_record) == 184, "dh_rig_subject_record: 184 bytes");
+static_assert(sizeof(SubjectBinding) == 16, "the four words of an entry, beside its dh_rig_fit_state");
+// Magnitudes.  The step's fit is section 21's over a table whose entries are the set's models and the generic one: creation
+// refuses a scale whose product with the set's bound or with the generic radius exceeds DH_FIT_MAX_EXTENT, and (cameras of the
+// largest rig) * points above DH_FIT_MAX_POINTS, so every start and every wanted pair sums below section 21's 2^62 for whichever
+// entry it names and whichever mask it holds.  A wanted pair is section 28's as it stands.
+
+// The state of an entry lives in two device arrays -- section 22's dh_rig_fit_state, on which dh_rig_fit_bind and the shared
+// pieces of dh_fit_device.h run as they are, and the SubjectBinding beside it; dh_rig_subject_fit_tracker_state interleaves them.
+// One step's four launches beside k_fit_views_sched share one block: section 22's (its records unused: the record here is 184
+// bytes a slot), section 28's (inst and fit_rec: the step's fitted instances and their records, n_inst the slots, sets NULL and
+// n_sets 1; score and pose: the tracker's scratch of slots * S pairs; subjects_out, rec and poses_out unused) and the tracker's own.
+struct RigSubjectArgs {
+    RigFitArgs a;
+    IdentViewsArgs q;             // q.enrolled is never NULL here: the tracker holds a mask of ones for "all"
+    SubjectBinding *bound;        // [slots]
+    dh_rig_subject_record *records;      // [slots]
+    uint32_t retry, max_tries;
+    uint32_t *want;               // [slots] the slots that want identification, in no particular order
+    uint32_t *n_want;             // [1] how many: cleared by the seed kernel, grown by the update kernel
+    uint32_t *wants;              // [slots] 0 or 1 per slot: what the list holds, indexed by slot
+    uint32_t grid;                // workgroups of the score kernel, fixed at creation
+};
+hipError_t dh_launch_rig_subject_seed(const RigSubjectArgs &g, hipStream_t s);     // one workgroup per rig
+hipError_t dh_launch_rig_subject_update(const RigSubjectArgs &g, hipStream_t s);   // one lane per slot
+hipError_t dh_launch_rig_subject_score(const RigSubjectArgs &g, hipStream_t s);    // g.grid workgroups over the list's pairs
+hipError_t dh_launch_rig_subject_bind(const RigSubjectArgs &g, hipStream_t s);     // one wave per slot
+// dh_rig_subject_fit_tracker_bind: the entry of `rig` that holds `id` (none: nothing) gets (subject, 0, 0, 0); one wave.
+hipError_t dh_launch_rig_subject_set(const dh_rig_fit_state *state, SubjectBinding *bound, int rig, uint32_t id, uint32_t subject, hipStream_t s);

@@ -4,9 +4,12 @@
 //   the pose, the modes of a pass, the step's helpers      k_fit.hip, k_fit_views.hip (each with its *_sched instance)
 //   the single-view pass                                   k_fit.hip, k_ident.hip, k_subject_track.hip
 //   a pair of the identification                           k_ident.hip, k_subject_track.hip
-//   the multi-view pass                                    k_fit_views.hip, k_ident_views.hip
+//   the multi-view pass                                    k_fit_views.hip, k_ident_views.hip, k_rig_subject_track.hip
+//   a pair of the multi-view identification                k_ident_views.hip, k_rig_subject_track.hip
+//   the decision of an identification by one wave          k_ident.hip, k_ident_views.hip, k_subject_track.hip, k_rig_subject_track.hip
 //   the trackers' rule: table rotation, carried start,
-//   acceptance, jump test and the state updates            k_fit_track.hip, k_rig_fit_track.hip
+//   acceptance, jump test and the state updates            k_fit_track.hip, k_rig_fit_track.hip, k_subject_track.hip, k_rig_subject_track.hip
+//   the seed of one rig                                    k_rig_fit_track.hip, k_rig_subject_track.hip
 // f64 (the trackers: f32 too) with + - * /, compares and casts only; every operation is rounded on its own, so the expression
 // trees below are the contract (tests/fit_ref.py, shape_ref.py, view_fit_ref.py, fit_track_ref.py and rig_fit_track_ref.py and
 // shape_views_ref.py restate them).  Not part of the ABI.
@@ -452,9 +455,106 @@ __device__ __forceinline__ void fit_views_pass(const FitViewsArgs &a, const FitM
     __syncthreads();
 }
 
+// ---- a pair of the multi-view identification (k_ident_views.hip and k_rig_subject_track.hip; DESIGN.md sections 28 and 30)
+// Whether instance `in` (number i) takes part, and in *set the set its frames are in (< n_sets where it does).
+__device__ __forceinline__ bool ident_views_takes_part(const IdentViewsArgs &q, const dh_view_instance *in, uint32_t i, uint32_t *set) {
+    *set = q.sets ? q.sets[i] : 0u;
+    return dh_ident_views_part(*in, *set, q.fit_rec ? q.fit_rec + i : nullptr, (uint32_t)q.f.n, q.n_sets, q.np, q.radius, q.largest).why ==
+           DH_IDENT_VIEWS_OK;
+}
+
+// One pair's refit over the views of its instance: the full steps, then the last pass; the score and the pose written by lane 0.
+// a: the call's FitViewsArgs with the frames of the instance's set.
+template <bool STAGED>
+__device__ __forceinline__ void ident_views_run(const IdentViewsArgs &q, const FitViewsArgs &a, const dh_view_instance *in, const FitModel &m,
+                                                const float *s_pts, unsigned long long *s_sum, size_t pair) {
+    const uint32_t first_cam = in->first_cam;
+    const uint64_t views = in->views;
+    const uint64_t mask = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(views >> 32)) << 32) |
+                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)views);
+    FitPose pose;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) pose.R[c] = (double)in->R[c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pose.t[c] = (double)in->t[c];
+    const double scale = (double)in->scale;
+    uint32_t steps = 0, status = DH_FIT_OK;
+    for (uint32_t it = 0; it < a.full; ++it) {
+        fit_views_pass<FIT_FULL, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[1], s_sum);
+        if ((uint32_t)s_sum[DH_FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; break; }
+        double x[6];
+        if (!fit_solve_tri<6, 6>(s_sum, DH_FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
+        fit_cayley(pose.R, x + 3);
+        ++steps;
+        if (fit_small(x, 6)) break;
+    }
+    fit_views_pass<FIT_LAST, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[1], s_sum);
+    if (threadIdx.x == 0) {
+        dh_view_fit_record rec;
+        rec.points = (uint32_t)s_sum[DH_FIT_COUNT];
+        rec.steps = steps;
+        rec.status = status;
+        rec.reserved = 0;
+        rec.sum_r2_fixed = (int64_t)s_sum[DH_FIT_E];
+        rec.views_used = (uint64_t)s_sum[DH_FIT_USED];
+        q.score[pair] = rec;
+        float *o = q.pose + pair * 12;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) o[c] = (float)pose.R[c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[9 + c] = (float)pose.t[c];
+    }
+}
+
+// ---- the decision of an identification by one wave (k_ident_decide, k_ident_views_decide, k_subject_track_bind and
+// k_rig_subject_bind; DESIGN.md sections 27 - 30).  row: the instance's n_subjects scores (Score: dh_fit_record or
+// dh_view_fit_record; a pair that did not run holds zeros: 0 points, never eligible); part: whether the instance takes part
+// (uniform over the wave).  Lanes stride over the candidates with dh_fit.h's picks, the picks are merged by an xor butterfly, and
+// every lane returns the instance's dh_ident_record.
+template <typename Score>
+__device__ __forceinline__ dh_ident_record ident_decide(const Score *row, uint32_t n_subjects, uint32_t min_points, bool part, double max_ms,
+                                                        double min_ratio) {
+    IdentPick pick = dh_ident_pick_none();
+    uint32_t eligible = 0;
+    if (part)
+        for (uint32_t sj = threadIdx.x; sj < n_subjects; sj += DH_IDENT_THREADS) {
+            const Score r = row[sj];
+            if (r.status != DH_FIT_OK || r.points < min_points) continue;
+            dh_ident_pick_add(pick, dh_ident_mean(r.sum_r2_fixed, r.points), sj);
+            ++eligible;
+        }
+#pragma unroll
+    for (int o = WAVE / 2; o; o >>= 1) {
+        IdentPick other;
+        other.m_best = shfl_xor_f64(pick.m_best, o);
+        other.m_second = shfl_xor_f64(pick.m_second, o);
+        other.best = (uint32_t)__shfl_xor((int)pick.best, o);
+        other.second = (uint32_t)__shfl_xor((int)pick.second, o);
+        dh_ident_pick_merge(pick, other);
+        eligible += (uint32_t)__shfl_xor((int)eligible, o);
+    }
+    dh_ident_record rec;
+    rec.status = part ? dh_ident_status(eligible, pick.m_best, pick.m_second, max_ms, min_ratio) : DH_IDENT_SKIPPED;
+    rec.best = pick.best; rec.second = pick.second;
+    rec.eligible = eligible;
+    rec.points_best = 0; rec.points_second = 0; rec.sum_r2_best = 0; rec.sum_r2_second = 0;
+    if (pick.best != DH_IDENT_UNKNOWN) { rec.points_best = row[pick.best].points; rec.sum_r2_best = row[pick.best].sum_r2_fixed; }
+    if (pick.second != DH_IDENT_UNKNOWN) { rec.points_second = row[pick.second].points; rec.sum_r2_second = row[pick.second].sum_r2_fixed; }
+    return rec;
+}
+// The record of an instance for which no identification ran.
+__device__ __forceinline__ dh_ident_record ident_skipped() {
+    dh_ident_record rec;
+    rec.status = DH_IDENT_SKIPPED; rec.best = 0; rec.second = 0; rec.eligible = 0;
+    rec.points_best = 0; rec.points_second = 0; rec.sum_r2_best = 0; rec.sum_r2_second = 0;
+    return rec;
+}
+
 // ---- the trackers' rule (k_fit_track.hip: one lane per camera; k_rig_fit_track.hip: one lane per slot of a rig; DESIGN.md
 // sections 19 and 22).  State: dh_fit_track_state or dh_rig_fit_state; Instance: dh_render_instance or dh_view_instance.
-__device__ __forceinline__ uint32_t fit_sat_inc(uint32_t v) { return v == 0xffffffffu ? v : v + 1u; }
+__device__ __forceinline__ uint32_t fit_sat_inc(uint32_t v) { return dh_sat_inc(v); }
 
 // o = A B, each element as (A[i][0] * B[0][j] + A[i][1] * B[1][j]) + A[i][2] * B[2][j]
 __device__ __forceinline__ void fit_mat3_mul(const double A[9], const double B[9], double o[9]) {
@@ -525,4 +625,91 @@ template <typename State>
 __device__ __forceinline__ void fit_track_reject(State &st) {
     st.tracked = 0; st.have_prev = 0; st.age = 0;
     st.lost = fit_sat_inc(st.lost);
+}
+
+// ---- the seed of one rig (k_rig_fit_seed and k_rig_subject_seed; DESIGN.md sections 22 and 30): section 22's steps 0 - 2 by the
+// one workgroup of DH_RIG_FIT_THREADS lanes of rig blockIdx.x (the grid is n_rigs).  s_st, s_p, s_role, s_who: the kernel's own
+// __shared__ arrays of DH_RIG_MAX_TRACKS entries, DH_RIG_MAX_PERSONS persons and two words per slot.  The rig's entries and persons
+// are copied to LDS, lane 0 binds persons to entries (dh_rig_fit_bind, dh_rig_fit.h), then one lane per slot composes the slot's
+// start instance, its schedule and its kind.  model_of(slot, old, st, role) gives the start's `model`: old points at the entry as
+// it stood before the bind (still in global memory), st is what the bind made of it, role the slot's DH_RIG_FIT_*.
+template <typename ModelOf>
+__device__ __forceinline__ void rig_fit_seed_rig(const RigFitArgs &a, dh_rig_fit_state *s_st, dh_rig_person *s_p, uint32_t *s_role, uint32_t *s_who,
+                                                 ModelOf model_of) {
+    const int g = blockIdx.x, lane = threadIdx.x;                  // g < n_rigs: the grid is n_rigs
+    const int c0 = a.rig_begin[g], nc = a.rig_begin[g + 1] - c0;   // 1 .. DH_RIG_MAX_CAMERAS cameras (dh_rig_create)
+    // pm: one present camera per lane (nc <= 64 = the lanes of the one wave)
+    const bool here = lane < nc && (!a.present || a.present[c0 + lane] != 0);
+    const uint64_t pm = __ballot(here);
+    const size_t slot = (size_t)g * DH_RIG_MAX_TRACKS + lane;
+    if (pm == 0) {                                                 // (uniform) step 0: the state is kept
+        if (lane < DH_RIG_MAX_TRACKS) {
+            a.seed[slot] = DH_FIT_SEED_ABSENT;
+            a.who[slot] = DH_RIG_FIT_NO_PERSON;
+            a.sched[2 * slot] = 0; a.sched[2 * slot + 1] = 0;
+        }
+        return;
+    }
+    dh_rig_fit_state *gst = a.state + (size_t)g * DH_RIG_MAX_TRACKS;
+    {
+        const uint32_t *src = (const uint32_t *)gst;
+        uint32_t *dst = (uint32_t *)s_st;
+        for (uint32_t k = lane; k < DH_RIG_MAX_TRACKS * sizeof(dh_rig_fit_state) / 4; k += DH_RIG_FIT_THREADS) dst[k] = src[k];
+        src = (const uint32_t *)(a.persons + (size_t)g * DH_RIG_MAX_PERSONS);
+        dst = (uint32_t *)s_p;
+        for (uint32_t k = lane; k < DH_RIG_MAX_PERSONS * sizeof(dh_rig_person) / 4; k += DH_RIG_FIT_THREADS) dst[k] = src[k];
+    }
+    __syncthreads();
+    if (lane == 0) dh_rig_fit_bind(s_st, s_p, a.n_persons[g], a.n_heads, a.n_cams, a.max_heads, s_role, s_who);
+    __syncthreads();
+    if (lane >= DH_RIG_MAX_TRACKS) return;
+    const uint32_t role = s_role[lane], pi = s_who[lane];
+    const dh_rig_fit_state st = s_st[lane];
+    dh_view_instance in;
+    in.first_cam = (uint32_t)c0; in.model = model_of(slot, gst + lane, st, role); in.views = 0; in.scale = a.scale; in.flags = 0;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) in.R[q] = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) in.t[q] = 0.0f;
+    uint32_t kind = DH_FIT_SEED_NONE, coarse = 0, full = 0;
+    if (role != DH_RIG_FIT_UNUSED) {
+        const bool seen = pi != DH_RIG_FIT_NO_PERSON;
+        const bool entry = role != DH_RIG_FIT_UNBOUND;
+        if (entry && st.tracked) {
+            in.views = (st.views_used | (seen ? s_p[pi].views : 0ull)) & pm;
+            if (in.views == 0) kind = DH_FIT_SEED_COAST;
+            else {
+                kind = DH_FIT_SEED_CARRIED;
+                full = a.prm.iterations_tracked;
+                fit_track_carried_start(st, a.flags, in);
+            }
+        } else {                                                   // detected: the slot has a person (the bind freed the rest)
+            const dh_rig_person &p = s_p[pi];
+            kind = DH_FIT_SEED_DETECTED;
+            coarse = a.coarse; full = a.full;
+            in.views = p.views & pm;
+            // best_cam < n_cams and best_head < max_heads: the bind ignores every other person
+            const dh_pose &po = a.heads[(size_t)p.best_cam * a.max_heads + p.best_head].pose;
+            double R[9], Rh[9], V[9];
+            fit_track_rotation(po.rotation, a.angles, R);
+#pragma unroll
+            for (int q = 0; q < 9; ++q) {
+                Rh[q] = (double)(float)R[q];
+                V[q] = (double)a.views[p.best_cam].V[q];
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) in.R[3 * i + j] = (float)((V[i] * Rh[j] + V[3 + i] * Rh[3 + j]) + V[6 + i] * Rh[6 + j]);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) in.t[q] = p.world[q];
+        }
+        if (seen) kind |= DH_RIG_FIT_SEED_IS_SEEN;
+        if (entry) kind |= DH_RIG_FIT_SEED_IS_ENTRY;
+    }
+    gst[lane] = st;                                                // what the bind made of the entry
+    a.start[slot] = in;
+    a.sched[2 * slot] = coarse; a.sched[2 * slot + 1] = full;
+    a.seed[slot] = kind;
+    a.who[slot] = pi;
 }

@@ -67,3 +67,5 @@ struct SubjectsView {
 void dh_fit_subjects_view_(const dh_fit_subjects *set, SubjectsView *v, FitModel *models);
 // ident_params_check with section 27's default max_rms.
 int dh_ident_params_check_(const dh_ident_params *in, dh_ident_params *out, const char *who);
+// the same with section 28's default max_rms (the rig subject fit tracker's)
+int dh_ident_views_params_check_(const dh_ident_params *in, dh_ident_params *out, const char *who);

@@ -44,46 +44,19 @@ __global__ __launch_bounds__(DH_FIT_THREADS) void k_ident_score(const IdentArgs 
     } else ident_run<false>(q, in, m, s_pts, s_sum, pair);
 }
 
-// (k_ident_views_decide, k_ident_views.hip, is this kernel over rows of dh_view_fit_record with a dh_view_instance pose: the strided
-// picks, the shuffle reduction and lane 0's record are the same statements there, and a change to either belongs in both)
+// (the strided picks, the shuffle reduction and the record are ident_decide, dh_fit_device.h's, for every kernel that decides)
 __global__ __launch_bounds__(DH_IDENT_THREADS) void k_ident_decide(const IdentArgs q) {
     const uint32_t i = blockIdx.x;
     const dh_render_instance *in = q.f.inst + i;
     const bool part = ident_takes_part(q, in, i);    // uniform over the wave
-    const dh_fit_record *row = q.score + (size_t)i * q.n_subjects;
-    IdentPick pick = dh_ident_pick_none();
-    uint32_t eligible = 0;
-    if (part)
-        for (uint32_t sj = threadIdx.x; sj < q.n_subjects; sj += DH_IDENT_THREADS) {
-            const dh_fit_record r = row[sj];         // a pair that did not run holds zeros: 0 points, never eligible
-            if (r.status != DH_FIT_OK || r.points < q.f.min_points) continue;
-            dh_ident_pick_add(pick, dh_ident_mean(r.sum_r2_fixed, r.points), sj);
-            ++eligible;
-        }
-#pragma unroll
-    for (int o = WAVE / 2; o; o >>= 1) {
-        IdentPick other;
-        other.m_best = shfl_xor_f64(pick.m_best, o);
-        other.m_second = shfl_xor_f64(pick.m_second, o);
-        other.best = (uint32_t)__shfl_xor((int)pick.best, o);
-        other.second = (uint32_t)__shfl_xor((int)pick.second, o);
-        dh_ident_pick_merge(pick, other);
-        eligible += (uint32_t)__shfl_xor((int)eligible, o);
-    }
+    const dh_ident_record rec = ident_decide(q.score + (size_t)i * q.n_subjects, q.n_subjects, q.f.min_points, part, q.max_ms, q.min_ratio);
     if (threadIdx.x != 0) return;
-    dh_ident_record rec;
-    rec.status = part ? dh_ident_status(eligible, pick.m_best, pick.m_second, q.max_ms, q.min_ratio) : DH_IDENT_SKIPPED;
-    rec.best = pick.best; rec.second = pick.second;
-    rec.eligible = eligible;
-    rec.points_best = 0; rec.points_second = 0; rec.sum_r2_best = 0; rec.sum_r2_second = 0;
-    if (pick.best != DH_IDENT_UNKNOWN) { rec.points_best = row[pick.best].points; rec.sum_r2_best = row[pick.best].sum_r2_fixed; }
-    if (pick.second != DH_IDENT_UNKNOWN) { rec.points_second = row[pick.second].points; rec.sum_r2_second = row[pick.second].sum_r2_fixed; }
     q.rec[i] = rec;
-    q.subjects_out[i] = rec.status == DH_IDENT_OK ? pick.best : DH_IDENT_UNKNOWN;
+    q.subjects_out[i] = rec.status == DH_IDENT_OK ? rec.best : DH_IDENT_UNKNOWN;
     if (q.poses_out) {
         dh_render_instance o = *in;
-        if (pick.best != DH_IDENT_UNKNOWN) {
-            const float *p = q.pose + ((size_t)i * q.n_subjects + pick.best) * 12;
+        if (rec.best != DH_IDENT_UNKNOWN) {
+            const float *p = q.pose + ((size_t)i * q.n_subjects + rec.best) * 12;
 #pragma unroll
             for (int c = 0; c < 9; ++c) o.R[c] = p[c];
 #pragma unroll

@@ -10,67 +10,18 @@
 //                         frames of the instance's set: the pass gets a copy of the FitViewsArgs whose `frames` is advanced by
 //                         set * n * h * w and is itself what k_fit_views runs.  Lane 0 writes the pair's dh_view_fit_record and
 //                         its world pose rounded to f32.
-//   k_ident_views_decide  one wave per instance over its row of 32-byte scores: k_ident_decide's strided picks and shuffle
-//                         reduction with dh_fit.h's __host__ __device__ order and status (tests/host/ident_check.cpp compiles them
-//                         as they are); lane 0 writes subjects_out, the record and poses_out, a dh_view_instance.
+//   k_ident_views_decide  one wave per instance over its row of 32-byte scores: ident_decide (dh_fit_device.h: the strided picks and
+//                         the shuffle reduction every deciding kernel runs) with dh_fit.h's __host__ __device__ order and status
+//                         (tests/host/ident_check.cpp compiles them as they are); lane 0 writes subjects_out, the record and
+//                         poses_out, a dh_view_instance.
 // f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free: bit-identical
 // run to run and to tests/ident_views_ref.py.
 #include "dh_fit_device.h"
 
 #pragma clang fp contract(off)
 
-// Whether instance `in` (number i) takes part, and in *set the set its frames are in (< n_sets where it does).
-__device__ __forceinline__ bool ident_views_takes_part(const IdentViewsArgs &q, const dh_view_instance *in, uint32_t i, uint32_t *set) {
-    *set = q.sets ? q.sets[i] : 0u;
-    return dh_ident_views_part(*in, *set, q.fit_rec ? q.fit_rec + i : nullptr, (uint32_t)q.f.n, q.n_sets, q.np, q.radius, q.largest).why ==
-           DH_IDENT_VIEWS_OK;
-}
-
-// One pair's refit over the views of its instance: the full steps, then the last pass; the score and the pose written by lane 0.
-// a: the call's FitViewsArgs with the frames of the instance's set.
-template <bool STAGED>
-__device__ __forceinline__ void ident_views_run(const IdentViewsArgs &q, const FitViewsArgs &a, const dh_view_instance *in, const FitModel &m,
-                                                const float *s_pts, unsigned long long *s_sum, size_t pair) {
-    const uint32_t first_cam = in->first_cam;
-    const uint64_t views = in->views;
-    const uint64_t mask = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(views >> 32)) << 32) |
-                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)views);
-    FitPose pose;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) pose.R[c] = (double)in->R[c];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) pose.t[c] = (double)in->t[c];
-    const double scale = (double)in->scale;
-    uint32_t steps = 0, status = DH_FIT_OK;
-    for (uint32_t it = 0; it < a.full; ++it) {
-        fit_views_pass<FIT_FULL, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[1], s_sum);
-        if ((uint32_t)s_sum[DH_FIT_COUNT] < a.min_points) { status = DH_FIT_FEW_POINTS; break; }
-        double x[6];
-        if (!fit_solve_tri<6, 6>(s_sum, DH_FIT_B, a.lam1, x)) { status = DH_FIT_SINGULAR; break; }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) pose.t[j] = pose.t[j] + x[j];
-        fit_cayley(pose.R, x + 3);
-        ++steps;
-        if (fit_small(x, 6)) break;
-    }
-    fit_views_pass<FIT_LAST, STAGED>(a, m, s_pts, first_cam, mask, scale, pose, a.gate[1], s_sum);
-    if (threadIdx.x == 0) {
-        dh_view_fit_record rec;
-        rec.points = (uint32_t)s_sum[DH_FIT_COUNT];
-        rec.steps = steps;
-        rec.status = status;
-        rec.reserved = 0;
-        rec.sum_r2_fixed = (int64_t)s_sum[DH_FIT_E];
-        rec.views_used = (uint64_t)s_sum[DH_FIT_USED];
-        q.score[pair] = rec;
-        float *o = q.pose + pair * 12;
-#pragma unroll
-        for (int c = 0; c < 9; ++c) o[c] = (float)pose.R[c];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[9 + c] = (float)pose.t[c];
-    }
-}
-
+// (ident_views_takes_part and ident_views_run, one pair's refit, are dh_fit_device.h's: k_rig_subject_track.hip runs them over its
+// compact list)
 __global__ __launch_bounds__(DH_FIT_THREADS) void k_ident_views_score(const IdentViewsArgs q) {
     __shared__ float s_pts[6 * DH_FIT_LDS_POINTS];
     __shared__ unsigned long long s_sum[32];
@@ -105,40 +56,14 @@ __global__ __launch_bounds__(DH_IDENT_THREADS) void k_ident_views_decide(const I
     const dh_view_instance *in = q.f.inst + i;
     uint32_t set;
     const bool part = ident_views_takes_part(q, in, i, &set);    // uniform over the wave
-    const dh_view_fit_record *row = q.score + (size_t)i * q.n_subjects;
-    IdentPick pick = dh_ident_pick_none();
-    uint32_t eligible = 0;
-    if (part)
-        for (uint32_t sj = threadIdx.x; sj < q.n_subjects; sj += DH_IDENT_THREADS) {
-            const dh_view_fit_record r = row[sj];    // a pair that did not run holds zeros: 0 points, never eligible
-            if (r.status != DH_FIT_OK || r.points < q.f.min_points) continue;
-            dh_ident_pick_add(pick, dh_ident_mean(r.sum_r2_fixed, r.points), sj);
-            ++eligible;
-        }
-#pragma unroll
-    for (int o = WAVE / 2; o; o >>= 1) {
-        IdentPick other;
-        other.m_best = shfl_xor_f64(pick.m_best, o);
-        other.m_second = shfl_xor_f64(pick.m_second, o);
-        other.best = (uint32_t)__shfl_xor((int)pick.best, o);
-        other.second = (uint32_t)__shfl_xor((int)pick.second, o);
-        dh_ident_pick_merge(pick, other);
-        eligible += (uint32_t)__shfl_xor((int)eligible, o);
-    }
+    const dh_ident_record rec = ident_decide(q.score + (size_t)i * q.n_subjects, q.n_subjects, q.f.min_points, part, q.max_ms, q.min_ratio);
     if (threadIdx.x != 0) return;
-    dh_ident_record rec;
-    rec.status = part ? dh_ident_status(eligible, pick.m_best, pick.m_second, q.max_ms, q.min_ratio) : DH_IDENT_SKIPPED;
-    rec.best = pick.best; rec.second = pick.second;
-    rec.eligible = eligible;
-    rec.points_best = 0; rec.points_second = 0; rec.sum_r2_best = 0; rec.sum_r2_second = 0;
-    if (pick.best != DH_IDENT_UNKNOWN) { rec.points_best = row[pick.best].points; rec.sum_r2_best = row[pick.best].sum_r2_fixed; }
-    if (pick.second != DH_IDENT_UNKNOWN) { rec.points_second = row[pick.second].points; rec.sum_r2_second = row[pick.second].sum_r2_fixed; }
     q.rec[i] = rec;
-    q.subjects_out[i] = rec.status == DH_IDENT_OK ? pick.best : DH_IDENT_UNKNOWN;
+    q.subjects_out[i] = rec.status == DH_IDENT_OK ? rec.best : DH_IDENT_UNKNOWN;
     if (q.poses_out) {
         dh_view_instance o = *in;
-        if (pick.best != DH_IDENT_UNKNOWN) {
-            const float *p = q.pose + ((size_t)i * q.n_subjects + pick.best) * 12;
+        if (rec.best != DH_IDENT_UNKNOWN) {
+            const float *p = q.pose + ((size_t)i * q.n_subjects + rec.best) * 12;
 #pragma unroll
             for (int c = 0; c < 9; ++c) o.R[c] = p[c];
 #pragma unroll

@@ -16,86 +16,12 @@
 static_assert(DH_RIG_MAX_TRACKS <= DH_RIG_FIT_THREADS, "one lane per slot of a rig");
 static_assert(sizeof(dh_rig_fit_state) % 4 == 0 && sizeof(dh_rig_person) % 4 == 0, "copied to LDS word by word");
 
+// (the seed of a rig, rig_fit_seed_rig, is dh_fit_device.h's: k_rig_subject_seed runs it with a model word per entry)
 __global__ __launch_bounds__(DH_RIG_FIT_THREADS) void k_rig_fit_seed(const RigFitArgs a) {
     __shared__ dh_rig_fit_state s_st[DH_RIG_MAX_TRACKS];
     __shared__ dh_rig_person s_p[DH_RIG_MAX_PERSONS];
     __shared__ uint32_t s_role[DH_RIG_MAX_TRACKS], s_who[DH_RIG_MAX_TRACKS];
-    const int g = blockIdx.x, lane = threadIdx.x;                  // g < n_rigs: the grid is n_rigs
-    const int c0 = a.rig_begin[g], nc = a.rig_begin[g + 1] - c0;   // 1 .. DH_RIG_MAX_CAMERAS cameras (dh_rig_create)
-    // pm: one present camera per lane (nc <= 64 = the lanes of the one wave)
-    const bool here = lane < nc && (!a.present || a.present[c0 + lane] != 0);
-    const uint64_t pm = __ballot(here);
-    const size_t slot = (size_t)g * DH_RIG_MAX_TRACKS + lane;
-    if (pm == 0) {                                                 // (uniform) step 0: the state is kept
-        if (lane < DH_RIG_MAX_TRACKS) {
-            a.seed[slot] = DH_FIT_SEED_ABSENT;
-            a.who[slot] = DH_RIG_FIT_NO_PERSON;
-            a.sched[2 * slot] = 0; a.sched[2 * slot + 1] = 0;
-        }
-        return;
-    }
-    dh_rig_fit_state *gst = a.state + (size_t)g * DH_RIG_MAX_TRACKS;
-    {
-        const uint32_t *src = (const uint32_t *)gst;
-        uint32_t *dst = (uint32_t *)s_st;
-        for (uint32_t k = lane; k < sizeof(s_st) / 4; k += DH_RIG_FIT_THREADS) dst[k] = src[k];
-        src = (const uint32_t *)(a.persons + (size_t)g * DH_RIG_MAX_PERSONS);
-        dst = (uint32_t *)s_p;
-        for (uint32_t k = lane; k < sizeof(s_p) / 4; k += DH_RIG_FIT_THREADS) dst[k] = src[k];
-    }
-    __syncthreads();
-    if (lane == 0) dh_rig_fit_bind(s_st, s_p, a.n_persons[g], a.n_heads, a.n_cams, a.max_heads, s_role, s_who);
-    __syncthreads();
-    if (lane >= DH_RIG_MAX_TRACKS) return;
-    const uint32_t role = s_role[lane], pi = s_who[lane];
-    const dh_rig_fit_state st = s_st[lane];
-    dh_view_instance in;
-    in.first_cam = (uint32_t)c0; in.model = 0; in.views = 0; in.scale = a.scale; in.flags = 0;
-#pragma unroll
-    for (int q = 0; q < 9; ++q) in.R[q] = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) in.t[q] = 0.0f;
-    uint32_t kind = DH_FIT_SEED_NONE, coarse = 0, full = 0;
-    if (role != DH_RIG_FIT_UNUSED) {
-        const bool seen = pi != DH_RIG_FIT_NO_PERSON;
-        const bool entry = role != DH_RIG_FIT_UNBOUND;
-        if (entry && st.tracked) {
-            in.views = (st.views_used | (seen ? s_p[pi].views : 0ull)) & pm;
-            if (in.views == 0) kind = DH_FIT_SEED_COAST;
-            else {
-                kind = DH_FIT_SEED_CARRIED;
-                full = a.prm.iterations_tracked;
-                fit_track_carried_start(st, a.flags, in);
-            }
-        } else {                                                   // detected: the slot has a person (the bind freed the rest)
-            const dh_rig_person &p = s_p[pi];
-            kind = DH_FIT_SEED_DETECTED;
-            coarse = a.coarse; full = a.full;
-            in.views = p.views & pm;
-            // best_cam < n_cams and best_head < max_heads: the bind ignores every other person
-            const dh_pose &po = a.heads[(size_t)p.best_cam * a.max_heads + p.best_head].pose;
-            double R[9], Rh[9], V[9];
-            fit_track_rotation(po.rotation, a.angles, R);
-#pragma unroll
-            for (int q = 0; q < 9; ++q) {
-                Rh[q] = (double)(float)R[q];
-                V[q] = (double)a.views[p.best_cam].V[q];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) in.R[3 * i + j] = (float)((V[i] * Rh[j] + V[3 + i] * Rh[3 + j]) + V[6 + i] * Rh[6 + j]);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) in.t[q] = p.world[q];
-        }
-        if (seen) kind |= DH_RIG_FIT_SEED_IS_SEEN;
-        if (entry) kind |= DH_RIG_FIT_SEED_IS_ENTRY;
-    }
-    gst[lane] = st;                                                // what the bind made of the entry
-    a.start[slot] = in;
-    a.sched[2 * slot] = coarse; a.sched[2 * slot + 1] = full;
-    a.seed[slot] = kind;
-    a.who[slot] = pi;
+    rig_fit_seed_rig(a, s_st, s_p, s_role, s_who, [](size_t, const dh_rig_fit_state *, const dh_rig_fit_state &, uint32_t) { return 0u; });
 }
 
 __global__ __launch_bounds__(DH_RIG_FIT_THREADS) void k_rig_fit_update(const RigFitArgs a) {

@@ -15,8 +15,8 @@
 //                           of the tracker's scratch.  The trip count depends on blockIdx and the list's length alone, so it
 //                           is uniform over the workgroup; a barrier closes every trip before the next one stages its model
 //                           over the LDS the last pass read;
-//   k_subject_track_bind    one wave per camera: for a camera on the list k_ident_decide's strided picks and shuffle reduction
-//                           through dh_fit.h's functions, then the binding and the record's identification half by lane 0; for
+//   k_subject_track_bind    one wave per camera: for a camera on the list the decision (ident_decide, dh_fit_device.h), then the
+//                           binding (dh_subject_bind_or_retry, dh_fit.h) and the record's identification half by lane 0; for
 //                           every other camera lane 0 writes the SKIPPED record.
 // f32 and f64 with + - * /, compares and casts only, every operation rounded on its own; int64 sums whose order is free; one
 // integer atomic per wave: bit-identical run to run and to tests/subject_track_ref.py.
@@ -117,12 +117,7 @@ __global__ __launch_bounds__(DH_FIT_TRACK_THREADS) void k_subject_track_update(c
         }
         rec.age = st.age; rec.lost = st.lost;
         // ---- the binding lifecycle
-        if (st.tracked == 0) { ss.subject = DH_IDENT_UNKNOWN; ss.wait = 0; ss.tries = 0; ss.bound_age = 0; }
-        else if (accepted) {
-            if (ss.subject != DH_IDENT_UNKNOWN) ss.bound_age = fit_sat_inc(ss.bound_age);
-            else if (ss.wait == 0 && (g.max_tries == 0 || ss.tries < g.max_tries)) want = true;
-            else if (ss.wait > 0) ss.wait -= 1;
-        }
+        want = dh_subject_lifecycle(st.tracked != 0, accepted, g.max_tries, ss.subject, ss.wait, ss.tries, ss.bound_age);
         g.state[c] = ss;
         g.records[c].track = rec;
         g.records[c].model = model;
@@ -179,49 +174,20 @@ __global__ __launch_bounds__(DH_IDENT_THREADS) void k_subject_track_bind(const S
     dh_subject_track_record *out = g.records + i;
     if (g.wants[i] == 0) {                               // uniform over the wave
         if (threadIdx.x != 0) return;
-        dh_ident_record rec;
-        rec.status = DH_IDENT_SKIPPED; rec.best = 0; rec.second = 0; rec.eligible = 0;
-        rec.points_best = 0; rec.points_second = 0; rec.sum_r2_best = 0; rec.sum_r2_second = 0;
-        out->ident = rec;
+        out->ident = ident_skipped();
         out->subject = g.state[i].subject; out->identified = 0; out->tries = g.state[i].tries;
         return;
     }
     const dh_render_instance *in = q.f.inst + i;
     const bool part = ident_takes_part(q, in, i);        // uniform over the wave
-    const dh_fit_record *row = q.score + (size_t)i * q.n_subjects;
-    IdentPick pick = dh_ident_pick_none();
-    uint32_t eligible = 0;
-    if (part)
-        for (uint32_t sj = threadIdx.x; sj < q.n_subjects; sj += DH_IDENT_THREADS) {
-            const dh_fit_record r = row[sj];             // a pair that did not run holds zeros: 0 points, never eligible
-            if (r.status != DH_FIT_OK || r.points < q.f.min_points) continue;
-            dh_ident_pick_add(pick, dh_ident_mean(r.sum_r2_fixed, r.points), sj);
-            ++eligible;
-        }
-#pragma unroll
-    for (int o = WAVE / 2; o; o >>= 1) {
-        IdentPick other;
-        other.m_best = shfl_xor_f64(pick.m_best, o);
-        other.m_second = shfl_xor_f64(pick.m_second, o);
-        other.best = (uint32_t)__shfl_xor((int)pick.best, o);
-        other.second = (uint32_t)__shfl_xor((int)pick.second, o);
-        dh_ident_pick_merge(pick, other);
-        eligible += (uint32_t)__shfl_xor((int)eligible, o);
-    }
+    const dh_ident_record rec = ident_decide(q.score + (size_t)i * q.n_subjects, q.n_subjects, q.f.min_points, part, q.max_ms, q.min_ratio);
     if (threadIdx.x != 0) return;
-    dh_ident_record rec;
-    rec.status = part ? dh_ident_status(eligible, pick.m_best, pick.m_second, q.max_ms, q.min_ratio) : DH_IDENT_SKIPPED;
-    rec.best = pick.best; rec.second = pick.second;
-    rec.eligible = eligible;
-    rec.points_best = 0; rec.points_second = 0; rec.sum_r2_best = 0; rec.sum_r2_second = 0;
-    if (pick.best != DH_IDENT_UNKNOWN) { rec.points_best = row[pick.best].points; rec.sum_r2_best = row[pick.best].sum_r2_fixed; }
-    if (pick.second != DH_IDENT_UNKNOWN) { rec.points_second = row[pick.second].points; rec.sum_r2_second = row[pick.second].sum_r2_fixed; }
-    dh_subject_track_state *ss = g.state + i;
-    uint32_t subject = DH_IDENT_UNKNOWN, tries = ss->tries;
-    if (rec.status == DH_IDENT_OK) { subject = pick.best; ss->subject = subject; ss->bound_age = 0; }
-    else { tries = fit_sat_inc(tries); ss->tries = tries; ss->wait = g.retry; }
+    dh_subject_track_state *ss = g.state + i;            // (a camera on the list is unbound)
+    SubjectBinding b{ss->subject, ss->wait, ss->tries, ss->bound_age};
+    dh_subject_bind_or_retry(rec.status, rec.best, g.retry, b.subject, b.wait, b.tries, b.bound_age);
+    ss->subject = b.subject; ss->wait = b.wait; ss->tries = b.tries; ss->bound_age = b.bound_age;
     out->ident = rec;
-    out->subject = subject; out->identified = 1; out->tries = tries;
+    out->subject = b.subject; out->identified = 1; out->tries = b.tries;
 }
 
 // ------------------------------------------------------------------ launchers

@@ -1153,3 +1153,105 @@ class SubjectFitTracker(_StepInputs, _lib._Handle):
     def set_enrolled(self, enrolled, stream: int = 0) -> None:
         """Replace the candidates' mask ([S], None: all); stream-ordered."""
         check(self._lib.dh_subject_fit_tracker_set_enrolled(self._h, vp(self._mask(enrolled)), C.c_void_p(int(stream))))
+
+
+class RigSubjectFitTracker(_StepInputs, _lib._Handle):
+    """One dh_rig_subject_fit_tracker: a `RigFitTracker` bound to a `Subjects` set.  An entry that starts is
+    followed with `model` (the generic head), identified over all its present views against the set's enrolled subjects on the
+    device, and from the next step on fitted with its own subject's model as the set holds it.  `enrolled` [S] (None: all) says
+    which subjects are candidates.  The state stays on the device; a step never waits on the host.  Steps, resets, binds and mask
+    changes of one tracker must be stream-ordered with one another and with the set's updates; the tables, the set and the model
+    must outlive it."""
+    _handles = (("_h", "dh_rig_subject_fit_tracker_destroy"),)
+
+    def __init__(self, rig, views: Views, subjects: Subjects, model: Model, w: int, h: int, scale: float = 1.0, motion: bool = False,
+                 params=None, ident_params=None, subject_params=None, enrolled=None):
+        self._lib = _lib.load()
+        self.rig, self.views, self.subjects, self.model, self.w, self.h = rig, views, subjects, model, int(w), int(h)
+        self.n, self.n_rigs = rig.n, rig.n_rigs
+        self.flags = FIT_TRACK_MOTION if motion else 0
+        self._h = C.c_void_p()
+        check(self._lib.dh_rig_subject_fit_tracker_create(rig._h, views._h, subjects._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
+                                                          _lib.ref(params), _lib.ref(ident_params), _lib.ref(subject_params),
+                                                          vp(self._mask(enrolled)), C.byref(self._h)))
+
+    def _mask(self, enrolled):
+        return None if enrolled is None else np.ascontiguousarray(enrolled, dtype=np.uint8).reshape(len(self.subjects))
+
+    def _records(self) -> np.ndarray:
+        return np.zeros((self.n_rigs, RIG_MAX_TRACKS), _lib.RIG_SUBJECT_RECORD_DTYPE)
+
+    def step_persons(self, frames, n_heads, heads, n_persons, persons, present=None, fit_params=None) -> np.ndarray:
+        """The core step from the outputs of a rig tracker step (as `RigFitTracker.step_persons`) and host frames [n_cams, h, w] u16:
+        -> RIG_SUBJECT_RECORD_DTYPE [n_rigs, RIG_MAX_TRACKS]."""
+        frames, pr = self._frames(frames), self._present(present)
+        heads = np.ascontiguousarray(heads, dtype=HEAD_DTYPE)
+        if heads.ndim != 2 or heads.shape[0] != self.n:
+            raise ValueError(f"heads must be [{self.n}, max_heads]")
+        n_heads = np.ascontiguousarray(n_heads, dtype=np.uint32).reshape(self.n)
+        n_persons = np.ascontiguousarray(n_persons, dtype=np.uint32).reshape(self.n_rigs)
+        persons = np.ascontiguousarray(persons, dtype=RIG_PERSON_DTYPE).reshape(self.n_rigs, RIG_MAX_PERSONS)
+        rec = self._records()
+        check(self._lib.dh_rig_subject_fit_tracker_step_persons(self._h, vp(frames), self.w, self.h, vp(pr), C.c_int(heads.shape[1]),
+                                                                vp(n_heads), vp(heads), vp(n_persons), vp(persons), _lib.ref(fit_params),
+                                                                vp(rec)))
+        return rec
+
+    def step(self, rig_tracker, frames, present=None, tracks: bool = True, fit_params=None):
+        """The whole step: `rig_tracker` (a `tracking.RigTracker` of the same rig table) steps on the frames, then the core step, on
+        one stream.  -> (what RigTracker.step returns: n_heads, heads, rig_ids, n_persons, persons, tracks or None;
+        RIG_SUBJECT_RECORD_DTYPE [n_rigs, RIG_MAX_TRACKS])."""
+        frames, pr = self._frames(frames), self._present(present)
+        mh = rig_tracker.max_heads
+        n_heads, heads = np.zeros(self.n, np.uint32), np.zeros((self.n, mh), HEAD_DTYPE)
+        ids = np.zeros((self.n, mh), np.uint32)
+        n_persons, persons = np.zeros(self.n_rigs, np.uint32), np.zeros((self.n_rigs, RIG_MAX_PERSONS), RIG_PERSON_DTYPE)
+        tr = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_TRACK_DTYPE) if tracks else None
+        rec = self._records()
+        check(self._lib.dh_rig_subject_fit_tracker_step(rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames), self.w, self.h, vp(pr),
+                                                        _lib.ref(fit_params), vp(n_heads), vp(heads), vp(ids), vp(n_persons), vp(persons),
+                                                        vp(tr), vp(rec)))
+        return (n_heads, heads, ids, n_persons, persons, tr), rec
+
+    def step_device(self, frames_ptr: int, n_heads_ptr: int, heads_ptr: int, n_persons_ptr: int, persons_ptr: int, records_ptr: int,
+                    max_heads: int = MAX_HEADS, rig_tracker=None, ids_ptr: int = 0, tracks_ptr: int = 0, present_ptr: int = 0,
+                    fit_params=None, stream: int = 0) -> None:
+        """`RigFitTracker.step_device` with records [n_rigs][RIG_MAX_TRACKS] of dh_rig_subject_record: five launches on `stream`
+        (after the rig tracker's, with `rig_tracker`), no allocation and no host wait."""
+        prm = _lib.ref(fit_params)
+        if rig_tracker is None:
+            check(self._lib.dh_rig_subject_fit_tracker_step_persons_device(self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
+                                                                           C.c_int(int(max_heads)), vp(n_heads_ptr), vp(heads_ptr),
+                                                                           vp(n_persons_ptr), vp(persons_ptr), prm, vp(records_ptr),
+                                                                           C.c_void_p(int(stream))))
+        else:
+            check(self._lib.dh_rig_subject_fit_tracker_step_device(rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames_ptr), self.w, self.h,
+                                                                   vp(present_ptr or None), prm, vp(n_heads_ptr), vp(heads_ptr),
+                                                                   vp(ids_ptr or None), vp(n_persons_ptr), vp(persons_ptr),
+                                                                   vp(tracks_ptr or None), vp(records_ptr), C.c_void_p(int(stream))))
+
+    def reset(self, rig: int | None = None, stream: int = 0) -> None:
+        """One rig or all back to the initial state (every entry free, nobody bound); stream-ordered."""
+        check(self._lib.dh_rig_subject_fit_tracker_reset(self._h, C.c_int(-1 if rig is None else int(rig)), C.c_void_p(int(stream))))
+
+    def state(self) -> np.ndarray:
+        """Synchronous copy of the state: RIG_SUBJECT_STATE_DTYPE [n_rigs, RIG_MAX_TRACKS]."""
+        st = np.zeros((self.n_rigs, RIG_MAX_TRACKS), _lib.RIG_SUBJECT_STATE_DTYPE)
+        check(self._lib.dh_rig_subject_fit_tracker_state(self._h, vp(st)))
+        return st
+
+    def info(self):
+        """(rigs, S, the workgroups of the score kernel's grid)."""
+        n, s, g = C.c_int(), C.c_uint32(), C.c_uint32()
+        check(self._lib.dh_rig_subject_fit_tracker_info(self._h, C.byref(n), C.byref(s), C.byref(g)))
+        return n.value, s.value, g.value
+
+    def bind(self, rig: int, rig_id: int, subject: int | None, stream: int = 0) -> None:
+        """The caller's own binding of the entry of `rig` that holds `rig_id` to `subject`; None unbinds; an id nobody holds changes
+        nothing.  Stream-ordered."""
+        check(self._lib.dh_rig_subject_fit_tracker_bind(self._h, C.c_int(int(rig)), C.c_uint32(int(rig_id)),
+                                                        C.c_uint32(IDENT_UNKNOWN if subject is None else int(subject)), C.c_void_p(int(stream))))
+
+    def set_enrolled(self, enrolled, stream: int = 0) -> None:
+        """Replace the candidates' mask ([S], None: all); stream-ordered."""
+        check(self._lib.dh_rig_subject_fit_tracker_set_enrolled(self._h, vp(self._mask(enrolled)), C.c_void_p(int(stream))))

@@ -1770,6 +1770,120 @@ int dh_subject_fit_tracker_step_device(dh_predictor *p, dh_subject_fit_tracker *
                                        const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out,
                                        dh_support *support_out, dh_subject_track_record *records, void *stream);
 
+/* ---- following each rig person with its own subject's model ----
+ * The rig twin of the section above: a dh_rig_subject_fit_tracker is section 22's rig fit tracker bound to a subject set.  An entry
+ * that starts is followed with the generic model, identified OVER ALL ITS PRESENT VIEWS against the enrolled subjects on the device
+ * (section 28), and from the next step on fitted with its own subject's model as the set holds it then -- with no host wait and no
+ * allocation in a step.  Not in the reference: PARITY UNPINNED, the definition below is this library's.  It composes sections 22, 28
+ * and 29 and restates none of them; the arithmetic conventions are theirs (f32 and f64 with + - * /, compares and casts, every
+ * operation rounded on its own; int64 sums whose order is free; no sine, cosine or floating-point atomic on the device).
+ * tests/rig_subject_track_ref.py restates it; the GPU equals it byte for byte.
+ * CREATION: a rig table and a view table bound to ONE dh_cameras handle (section 22's contract on their consistency holds); a
+ *   subject set of S subjects (ordinary or surface); a GENERIC dh_fit_model of the set's point count; scale and flags
+ *   (DH_FIT_TRACK_MOTION); a dh_rig_fit_track_params (NULL: section 22's defaults), a dh_ident_params (NULL:
+ *   dh_fit_ident_views_params_default) and a dh_subject_track_params (NULL: section 29's defaults); enrolled[S], u8, host memory,
+ *   NULL meaning every subject is a candidate.  The tracker builds section 29's device table of S + 1 models -- entries 0 .. S - 1
+ *   name the set's buffers, so an update of the set enqueued on the stream of the steps is seen by the next step; entry S is the
+ *   generic model -- and allocates every device buffer of a step: the pair scratch [n_rigs * DH_RIG_MAX_TRACKS][S] of scores and
+ *   poses, the want list and the per-slot words.  The tables, the set and the generic model must outlive the tracker.
+ * STATE of rig g: DH_RIG_MAX_TRACKS entries of dh_rig_subject_state (104 bytes): section 22's dh_rig_fit_state, then section 29's
+ *   `subject`, `wait`, `tries` and `bound_age`.  A free entry is zeros with subject = DH_IDENT_UNKNOWN: EVERY PLACE where section 22
+ *   zeroes an entry -- a free entry taken for a new id, an unseen untracked entry freed by the bind, an entry freed after a coast past
+ *   max_coast, an unseen entry freed after a rejection, reset -- also sets the four words to (DH_IDENT_UNKNOWN, 0, 0, 0).
+ * ONE STEP of rig g, from the inputs of section 22's step:
+ * 1. Section 22's steps 0 - 6 on the first 88 bytes of every entry, unchanged but for the start's `model`: the entry's subject (after
+ *    the bind of step 1) where it is < S, else S.  An UNBOUND PERSON (one with no entry) is always fitted with model S, is never
+ *    identified and carries nothing.  With pm == 0 the whole state of the rig, bindings included, is kept.
+ * 2. BINDING LIFECYCLE: section 29's rule 2, per entry, on the state step 1 left.  tracked == 0 (a rejected fit; a freed entry is
+ *    zeros): the binding is dropped, the four words (DH_IDENT_UNKNOWN, 0, 0, 0).  Else, when this step's fit was ACCEPTED (an unseen
+ *    entry's too): a bound entry has bound_age = bound_age + 1 (saturating); an unbound entry WANTS IDENTIFICATION when wait == 0 and
+ *    (max_tries == 0 or tries < max_tries), and otherwise, when wait > 0, has wait = wait - 1.  Else (a coast within max_coast)
+ *    nothing changes.
+ * 3. IDENTIFICATION of a slot that wants it is section 28's rule exactly: the one instance is the slot's accepted fitted
+ *    dh_view_instance (its `views` are the start's mask), its fit record DH_FIT_OK, the frames the step's with n_sets = 1 and set 0,
+ *    the candidates the tracker's enrolled subjects among all S, the parameters the tracker's dh_ident_params; TAKING PART (test 6
+ *    holds for every mask: creation secures it), THE SCORE of every (slot, candidate) pair and THE DECISION as stated there, with the
+ *    set's models as they are at this point of the stream.  DH_IDENT_OK: subject = best, bound_age = 0.  Any other status, SKIPPED
+ *    from a failed test of taking part included: tries = tries + 1 (saturating), wait = retry.  The refitted pose is not taken.  Two
+ *    slots of one rig MAY BIND ONE SUBJECT: a rule across the slots of a rig is not part of this section.
+ * 4. OUTPUT.  records[g][s], one dh_rig_subject_record (184 bytes) per slot: `track`, section 22's record of the slot (its instance
+ *    names the model of the table the fit used); `ident`, the identification's dh_ident_record, or where none ran all zeros with
+ *    status DH_IDENT_SKIPPED; `subject`, the subject word of the slot's entry after the step; `model`, the subject whose model this
+ *    step's fit used, DH_IDENT_UNKNOWN for the generic model or where no fit ran; `identified`, 1 where an identification ran, else
+ *    0; `tries`, the entry's after the step.  A slot that is no entry after the step -- unused, an unbound person, a freed entry, and
+ *    every slot of a rig with pm == 0 whose entry is free -- so reads subject = DH_IDENT_UNKNOWN and tries = 0: an UNUSED SLOT IS
+ *    ZEROS BUT FOR ident.status = DH_IDENT_SKIPPED, subject = DH_IDENT_UNKNOWN and model = DH_IDENT_UNKNOWN.  In a rig with pm == 0
+ *    track is section 22's (zeros, status DH_FIT_TRACK_ABSENT) and subject and tries are the kept entry's.
+ * A binding takes effect at the NEXT step's start.  dh_rig_subject_fit_tracker_bind is the caller's own binding: it acts on the
+ *   entry of `rig` that holds `id` -- subject < S binds it, DH_IDENT_UNKNOWN unbinds it, wait = tries = bound_age = 0 either way --
+ *   and where no entry holds the id it does nothing; ordered on `stream` (one small launch).  Rule 2 holds for it as for any
+ *   binding.  set_enrolled, reset (a rig, or -1), state, info (the rigs, S, the workgroups of k_rig_subject_score) are section 29's
+ *   with a rig for a camera.  Section 22's condition on max_coast and max_misses holds unchanged.
+ * A _device step allocates nothing, never waits on the host and is five launches on `stream`, a linear chain: k_rig_subject_seed,
+ *   the per-instance-schedule instance of k_fit_views over the S + 1 table, k_rig_subject_update (which appends the slots that want
+ *   identification to a device list), k_rig_subject_score -- a grid fixed at creation of min(n_rigs * DH_RIG_MAX_TRACKS * S, 2 * the
+ *   device's compute units) workgroups that loop over the list's (slot, subject) pairs -- and k_rig_subject_bind.  Steps, resets,
+ *   binds and mask changes of one tracker must be stream-ordered with one another and with the updates of its set.  The step
+ *   functions take the arguments of dh_rig_fit_tracker_step* with records [n_rigs][DH_RIG_MAX_TRACKS] of dh_rig_subject_record.
+ * DH_EINVAL before anything is launched or allocated, with the outputs untouched (create: *out NULL).  create, in this order: NULL
+ *   out; unknown flags; a scale that is not finite; iterations_tracked above 64; rms_max or max_jump outside (0, 4096] (NaN included);
+ *   max_coast above max_misses; a reserved word of the dh_rig_fit_track_params that is not 0; NULL rig, views, set or generic model;
+ *   a view table bound to another dh_cameras handle than the rig table; the dh_ident_params' refusals of section 27 in its order; a
+ *   reserved word of the dh_subject_track_params that is not 0; a set or a generic model on another device than the tables; a
+ *   generic model whose point count is not the set's; |scale| * (the set's bound) above DH_FIT_MAX_EXTENT; |scale| * (the generic
+ *   model's largest |v|) above DH_FIT_MAX_EXTENT; (cameras of the largest rig) * (the set's points) above DH_FIT_MAX_POINTS;
+ *   n_rigs * DH_RIG_MAX_TRACKS * S above DH_IDENT_MAX_PAIRS.  step: section 22's step refusals.  reset: NULL tracker, a rig outside
+ *   -1 .. n_rigs - 1.  bind: NULL tracker, a rig outside 0 .. n_rigs - 1, id 0, a subject that is neither < S nor DH_IDENT_UNKNOWN.
+ *   set_enrolled, state, info: NULL tracker / argument (info's outputs are each nullable).
+ * THE DEFAULTS.  retry and max_tries are section 29's; max_rms NULL-selected is section 28's DH_IDENT_VIEWS_DEFAULT_MAX_RMS
+ *   (DESIGN.md section 30 holds the measurement on moving frames that keeps it). */
+typedef struct dh_rig_subject_state {
+    dh_rig_fit_state fit;         /* offset 0 */
+    uint32_t subject;             /* offset 88: < S, or DH_IDENT_UNKNOWN */
+    uint32_t wait;                /* offset 92 */
+    uint32_t tries;               /* offset 96 */
+    uint32_t bound_age;           /* offset 100 */
+} dh_rig_subject_state;     /* 104 bytes, no padding */
+typedef struct dh_rig_subject_record {
+    dh_rig_fit_record track;      /* offset 0 */
+    dh_ident_record   ident;      /* offset 128 */
+    uint32_t subject;             /* offset 168: the entry's after the step */
+    uint32_t model;               /* offset 172: whose model the step's fit used, or DH_IDENT_UNKNOWN */
+    uint32_t identified;          /* offset 176: 0 or 1 */
+    uint32_t tries;               /* offset 180 */
+} dh_rig_subject_record;    /* 184 bytes, no padding */
+typedef struct dh_rig_subject_fit_tracker dh_rig_subject_fit_tracker;
+/* track_params, ident_params, params, enrolled: each NULL selects its default (enrolled: all S subjects) */
+int dh_rig_subject_fit_tracker_create(const dh_rig *rig, const dh_fit_views *views, const dh_fit_subjects *set, const dh_fit_model *generic,
+                                      float scale, uint32_t flags, const dh_rig_fit_track_params *track_params,
+                                      const dh_ident_params *ident_params, const dh_subject_track_params *params, const uint8_t *enrolled,
+                                      dh_rig_subject_fit_tracker **out);
+int dh_rig_subject_fit_tracker_destroy(dh_rig_subject_fit_tracker *t);
+/* rig, or -1 for all, back to the initial state; ordered on `stream` */
+int dh_rig_subject_fit_tracker_reset(dh_rig_subject_fit_tracker *t, int rig, void *stream);
+/* states [n_rigs][DH_RIG_MAX_TRACKS]; synchronises the device */
+int dh_rig_subject_fit_tracker_state(dh_rig_subject_fit_tracker *t, dh_rig_subject_state *states);
+/* the rigs, S, and the workgroups of k_rig_subject_score; each output nullable */
+int dh_rig_subject_fit_tracker_info(const dh_rig_subject_fit_tracker *t, int *n_rigs, uint32_t *n_subjects, uint32_t *score_workgroups);
+/* enrolled [S] u8, host memory, or NULL for all */
+int dh_rig_subject_fit_tracker_set_enrolled(dh_rig_subject_fit_tracker *t, const uint8_t *enrolled, void *stream);
+int dh_rig_subject_fit_tracker_bind(dh_rig_subject_fit_tracker *t, int rig, uint32_t id, uint32_t subject, void *stream);
+int dh_rig_subject_fit_tracker_step_persons(dh_rig_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                            int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons,
+                                            const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_subject_record *records);
+int dh_rig_subject_fit_tracker_step_persons_device(dh_rig_subject_fit_tracker *t, const uint16_t *frames, int w, int h,
+                                                   const uint8_t *present, int max_heads, const uint32_t *n_heads, const dh_head *heads,
+                                                   const uint32_t *n_persons, const dh_rig_person *persons,
+                                                   const dh_fit_params *fit_params, dh_rig_subject_record *records, void *stream);
+int dh_rig_subject_fit_tracker_step(dh_predictor *p, dh_rig_subject_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
+                                    const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads,
+                                    uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks,
+                                    dh_rig_subject_record *records);
+int dh_rig_subject_fit_tracker_step_device(dh_predictor *p, dh_rig_subject_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w,
+                                           int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads,
+                                           dh_head *heads, uint32_t *rig_ids, uint32_t *n_persons, dh_rig_person *persons,
+                                           dh_rig_track *tracks, dh_rig_subject_record *records, void *stream);
+
 /* ---- BIWI Kinect Head Pose Database formats (frame ingest, src/db_reader/biwi.rs) ----
  * read_depth (biwi.rs:81-103): run-length coded depth `.bin` -> row-major u16.  Call with out == NULL
  * to obtain *w, *h.  Where the reference returns an io::Error (truncated file) or panics (a run
