@@ -1,9 +1,12 @@
-// dh_api_fit_track.hip -- the fit trackers' runtime: what both share (the angle table, FitTrackerCore, the creation check, the
-// host form of a step), the camera fit tracker, the rig fit tracker (section 22), the subject fit tracker
-// (section 29) and the rig subject fit tracker (section 30) in their host and _device forms.  Kernels: k_fit_track.hip,
-// k_rig_fit_track.hip, k_subject_track.hip, k_rig_subject_track.hip, and the _sched launches of k_fit.hip and k_fit_views.hip.  Shares
-// dh_runtime.h with every runtime unit, dh_runtime_fit.h with the fit family (dh_api_fit.hip), and dh_runtime_track.h with the
-// trackers in dh_api.hip, which also defines the three functions of that header a whole step calls.
+// dh_api_fit_track.hip -- the fit trackers' runtime, four trackers in two pairs.  What all four share: the angle table,
+// FitTrackerCore, the creation check, the staging of a host step (fit_tracker_host).  The camera pair -- the camera fit tracker
+//  and the subject fit tracker (section 29) -- stands on CamFitTrackerBase, the rig pair -- the rig fit
+// tracker (section 22) and the rig subject fit tracker (section 30) -- on RigFitTrackerBase; each pair has one step check, one
+// function that fills the argument blocks, one host form and its four step forms written once (section 31), with the tracker's
+// core step (its launches) handed in.  The two subject trackers share SubjectParts and what goes with a binding.  Kernels:
+// k_fit_track.hip, k_rig_fit_track.hip, k_subject_track.hip, k_rig_subject_track.hip, and the _sched launches of k_fit.hip and
+// k_fit_views.hip.  Shares dh_runtime.h with every runtime unit, dh_runtime_fit.h with the fit family (dh_api_fit.hip), and
+// dh_runtime_track.h with the trackers in dh_api.hip, which also defines the three functions of that header a whole step calls.
 #include <math.h>
 #include <string.h>
 
@@ -41,6 +44,13 @@ static int fit_track_params_default_(dh_fit_track_params *p) {
     p->min_windows = 1; p->max_coast = 3;
     return DH_OK;
 }
+// What a creation runs with: the defaults of P, or the caller's params where given.
+template <typename P>
+static P params_or_default(int (*defaults)(P *), const P *given) {
+    P p;
+    (void)defaults(&p);
+    return given ? *given : p;
+}
 
 // What the camera's fit tracker (below) and the rig's (section 22) share: the model and what the acceptance rule reads, the
 // tables every step reads, and for the host forms the tracker's own stream and the frames staged on it (they come with the first
@@ -72,16 +82,27 @@ struct FitTrackerCore : TrackerCore {
         return hip_step(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
     }
 };
-// The refusals of a fit tracker's creation in the header's order.  P: dh_fit_track_params or dh_rig_fit_track_params; own() gives
-// the refusals of the fields that only P has, tables() those of the tables and of the model beside them (NULL, device).
-template <typename P, typename Own, typename Tables>
-static int fit_tracker_create_check(const P &prm, float scale, uint32_t flags, const dh_fit_model *m, Own own, Tables tables, const char *who) {
+// The refusals of the fields that only one params type has: the confidence fraction of a camera's, max_coast of a rig's.
+static int fit_track_own_check(const dh_fit_track_params &prm, const char *who) {
+    if (prm.conf_den == 0 || prm.conf_num > prm.conf_den)
+        return fail(DH_EINVAL, "%s: confidence %u / %u, expected a fraction in [0, 1]", who, prm.conf_num, prm.conf_den);
+    return DH_OK;
+}
+static int fit_track_own_check(const dh_rig_fit_track_params &prm, const char *who) {
+    if (prm.max_coast > prm.max_misses)
+        return fail(DH_EINVAL, "%s: max_coast %u above the max_misses %u the ids come from", who, prm.max_coast, prm.max_misses);
+    return DH_OK;
+}
+// The refusals of a fit tracker's creation in the header's order.  P: dh_fit_track_params or dh_rig_fit_track_params (its own
+// fields: fit_track_own_check); tables() gives the refusals of the tables and of the model beside them (NULL, device).
+template <typename P, typename Tables>
+static int fit_tracker_create_check(const P &prm, float scale, uint32_t flags, const dh_fit_model *m, Tables tables, const char *who) {
     if (flags & ~DH_FIT_TRACK_MOTION) return fail(DH_EINVAL, "%s: unknown flags 0x%x", who, flags);
     if (!std::isfinite(scale)) return fail(DH_EINVAL, "%s: scale is not finite", who);
     if (prm.iterations_tracked > 64) return fail(DH_EINVAL, "%s: iterations_tracked %u above 64", who, prm.iterations_tracked);
     if (!(prm.rms_max > 0.0 && prm.rms_max <= 4096.0)) return fail(DH_EINVAL, "%s: rms_max = %g outside (0, 4096]", who, prm.rms_max);
     if (!(prm.max_jump > 0.0 && prm.max_jump <= 4096.0)) return fail(DH_EINVAL, "%s: max_jump = %g outside (0, 4096]", who, prm.max_jump);
-    TRY(own());
+    TRY(fit_track_own_check(prm, who));
     if (prm.reserved[0] || prm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the params is not 0", who);
     TRY(tables());
     if (!m) return fail(DH_EINVAL, "%s: NULL model", who);     // (tables() refuses it in its place: m is never read unchecked)
@@ -98,7 +119,8 @@ static int destroy_fit_tracker(T *t) {
     }
     return destroy_tracker(t);
 }
-// The host form of a step of fit tracker t, synchronous on its own stream: the frames and the present bytes are staged,
+// The host form of a step of fit tracker t (any of the four; the pairs' host forms, cam_fit_host and rig_fit_host, fill in the
+// three functions), synchronous on its own stream: the frames and the present bytes are staged,
 // upload(s) stages the caller's other inputs, step(frames, present, s) enqueues the step on the staged arrays (present: the
 // staged bytes or NULL), download(s) copies back what the step reports beside its records, and the n_rec records follow.
 template <typename T, typename Up, typename Step, typename Down, typename Rec>
@@ -120,14 +142,25 @@ static int fit_tracker_host(T *t, const uint16_t *frames, int w, int h, const ui
     return DH_OK;
 }
 
-struct dh_fit_tracker : FitTrackerCore {
+// A FitTrackerCore whose units are the cameras.  What the camera fit tracker and the subject fit tracker (section 29) share:
+// everything but the state, the records and what a binding needs.
+struct CamFitTrackerBase : FitTrackerCore {
     dh_fit_track_params prm{};
-    Buf<dh_fit_track_state> state;       // [n]
-    Buf<dh_render_instance> start, fit_out;
+    Buf<dh_render_instance> start, fit_out;  // [n]
     Buf<dh_fit_record> fit_rec;
     Buf<dh_pose> poses;                  // host forms
     Buf<dh_support> support;
-    Buf<dh_fit_track_record> records;
+    // the params and every buffer above for n cameras
+    int alloc_cam(const dh_fit_track_params &prm_, size_t n) {
+        prm = prm_;
+        TRY(start.alloc(n)); TRY(fit_out.alloc(n)); TRY(fit_rec.alloc(n));
+        TRY(poses.alloc(n)); TRY(support.alloc(n));
+        return DH_OK;
+    }
+};
+struct dh_fit_tracker : CamFitTrackerBase {
+    Buf<dh_fit_track_state> state;       // [n]
+    Buf<dh_fit_track_record> records;    // host forms
     int clear(size_t c0, size_t m, hipStream_t st) {
         HIP_TRY(hipMemsetAsync(state.get() + c0, 0, m * sizeof(dh_fit_track_state), st));
         return DH_OK;
@@ -138,39 +171,34 @@ static int fit_tracker_create_(const dh_cameras *c, const dh_fit_model *m, float
     const char *who = "dh_fit_tracker_create";
     if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
     *out = nullptr;
-    dh_fit_track_params prm;
-    (void)fit_track_params_default_(&prm);
-    if (params) prm = *params;
+    const dh_fit_track_params prm = params_or_default(fit_track_params_default_, params);
     TRY(fit_tracker_create_check(prm, scale, flags, m, [&]() -> int {
-        if (prm.conf_den == 0 || prm.conf_num > prm.conf_den)
-            return fail(DH_EINVAL, "%s: confidence %u / %u, expected a fraction in [0, 1]", who, prm.conf_num, prm.conf_den);
-        return DH_OK;
-    }, [&]() -> int {
         if (!c) return fail(DH_EINVAL, "%s: NULL camera table", who);
         if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
         if (m->device != c->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the camera table on %d", who, m->device, c->device);
         return DH_OK;
     }, who));
     return create_tracker(c, out, [&](dh_fit_tracker &t, size_t n) -> int {
-        t.prm = prm;
-        TRY(t.state.alloc(n));
-        TRY(t.start.alloc(n)); TRY(t.fit_out.alloc(n)); TRY(t.fit_rec.alloc(n));
-        TRY(t.poses.alloc(n)); TRY(t.support.alloc(n)); TRY(t.records.alloc(n));
+        TRY(t.alloc_cam(prm, n));
+        TRY(t.state.alloc(n)); TRY(t.records.alloc(n));
         return t.init_fit(m, scale, flags, prm.rms_max, prm.max_jump, n);
     });
 }
 static int fit_tracker_destroy_(dh_fit_tracker *t) { return destroy_fit_tracker(t); }
 static int fit_tracker_reset_(dh_fit_tracker *t, int camera, void *stream) { return reset_tracker(t, camera, stream, "dh_fit_tracker_reset"); }
-static int fit_tracker_state_(dh_fit_tracker *t, dh_fit_track_state *states) {
-    if (t && !states) return fail(DH_EINVAL, "dh_fit_tracker_state: NULL argument");
-    return read_tracker(t, "dh_fit_tracker_state", [&](size_t n) -> int {
-        HIP_TRY(hipMemcpy(states, t->state.get(), n * sizeof(dh_fit_track_state), hipMemcpyDeviceToHost));
+// The synchronous copy of the state of tracker t of the camera pair, [n] entries of St; who names the entry point.
+template <typename T, typename St>
+static int cam_fit_state(T *t, St *states, const char *who) {
+    if (t && !states) return fail(DH_EINVAL, "%s: NULL argument", who);
+    return read_tracker(t, who, [&](size_t n) -> int {
+        HIP_TRY(hipMemcpy(states, t->state.get(), n * sizeof(St), hipMemcpyDeviceToHost));
         return DH_OK;
     });
 }
-// The refusals of a step that are the tracker's own, before anything is launched.
-static int fit_track_check(const dh_fit_tracker *t, const void *frames, int w, int h, const void *poses, const void *support,
-                           const dh_fit_params *in, const void *records, dh_fit_params *prm, const char *who) {
+static int fit_tracker_state_(dh_fit_tracker *t, dh_fit_track_state *states) { return cam_fit_state(t, states, "dh_fit_tracker_state"); }
+// The refusals of a step that are the tracker's own, before anything is launched: one rule for both trackers of the pair.
+static int cam_fit_check(const CamFitTrackerBase *t, const void *frames, int w, int h, const void *poses, const void *support,
+                         const dh_fit_params *in, const void *records, dh_fit_params *prm, const char *who) {
     if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
     if (!frames) return fail(DH_EINVAL, "%s: NULL frames", who);
     if (!poses || !support) return fail(DH_EINVAL, "%s: NULL poses or support", who);
@@ -178,52 +206,65 @@ static int fit_track_check(const dh_fit_tracker *t, const void *frames, int w, i
     TRY(check_frame_size(w, h, who));
     return fit_params_check(in, prm, who);
 }
-// Steps 0 - 6 for every camera, on device arrays and stream s (arguments checked, device selected): three launches.
-static int fit_track_enqueue(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
-                             const dh_support *support, const dh_fit_params &prm, dh_fit_track_record *records, hipStream_t s) {
-    FitTrackArgs a;
+// The argument blocks of a step's seed and update kernels (a; its state and records are the caller's to set) and of the fit
+// between them (f).
+static void cam_fit_args(CamFitTrackerBase *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
+                         const dh_support *support, const dh_fit_params &prm, FitTrackArgs &a, FitSchedArgs &f) {
     memset(&a, 0, sizeof a);
     a.n = t->n; a.flags = t->flags; a.scale = t->scale; a.prm = t->prm; a.rms_lim = t->rms_lim; a.jump2 = t->jump2;
     a.coarse = prm.coarse_iterations; a.full = prm.iterations;
-    a.angles = t->angles.get(); a.present = present; a.poses = poses; a.support = support; a.state = t->state.get();
+    a.angles = t->angles.get(); a.present = present; a.poses = poses; a.support = support;
     a.start = t->start.get(); a.sched = t->sched.get(); a.seed = t->seed.get();
-    a.fit_out = t->fit_out.get(); a.fit_rec = t->fit_rec.get(); a.records = records;
-    FitSchedArgs f;
+    a.fit_out = t->fit_out.get(); a.fit_rec = t->fit_rec.get();
     memset(&f, 0, sizeof f);
     f.f.frames = frames; f.f.n = t->n; f.f.w = w; f.f.h = h;
     f.f.cams = t->cams->dev.get(); f.f.models = t->models.get(); f.f.inst = t->start.get(); f.f.n_inst = (uint32_t)t->n;
     fit_args_params(f.f, prm);                             // (k_fit_sched reads coarse and full per instance from sched)
     f.f.out = t->fit_out.get(); f.f.rec = t->fit_rec.get();
     f.sched = t->sched.get(); f.seed = t->seed.get();
+}
+// Steps 0 - 6 for every camera, on device arrays and stream s (arguments checked, device selected): three launches.
+static int fit_track_enqueue(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
+                             const dh_support *support, const dh_fit_params &prm, dh_fit_track_record *records, hipStream_t s) {
+    FitTrackArgs a;
+    FitSchedArgs f;
+    cam_fit_args(t, frames, w, h, present, poses, support, prm, a, f);
+    a.state = t->state.get(); a.records = records;
     TRY(hip_step(dh_launch_fit_track_seed(a, s), "k_fit_track_seed"));
     TRY(hip_step(dh_launch_fit_sched(f, s), "k_fit_sched"));
     TRY(hip_step(dh_launch_fit_track_update(a, s), "k_fit_track_update"));
     return DH_OK;
 }
-static int fit_tracker_step_poses_device_(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
-                                          const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records, void *stream) {
+// The four forms of a step, written once for the camera pair.  T: either tracker; Rec: its record; enqueue: its core step on
+// device arrays (fit_track_enqueue's parameter list); who names the entry point.  The _device forms allocate nothing and never
+// wait on the host.
+template <typename T, typename Rec, typename Enqueue>
+static int cam_fit_step_poses_device(const char *who, Enqueue enqueue, T *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                     const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params, Rec *records,
+                                     void *stream) {
     dh_fit_params prm;
-    TRY(fit_track_check(t, frames, w, h, poses, support, fit_params, records, &prm, "dh_fit_tracker_step_poses_device"));
+    TRY(cam_fit_check(t, frames, w, h, poses, support, fit_params, records, &prm, who));
     DeviceGuard guard(t->cams->device);
     if (!guard.ok) return DH_EHIP;
-    return fit_track_enqueue(t, frames, w, h, present, poses, support, prm, records, (hipStream_t)stream);
+    return enqueue(t, frames, w, h, present, poses, support, prm, records, (hipStream_t)stream);
 }
-static int fit_tracker_step_device_(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
-                                    const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records,
-                                    void *stream) {
-    const char *who = "dh_fit_tracker_step_device";
+template <typename T, typename Rec, typename Enqueue>
+static int cam_fit_step_device(const char *who, Enqueue enqueue, dh_predictor *p, T *t, const uint16_t *frames, int w, int h,
+                               const uint8_t *present, uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out,
+                               dh_support *support_out, Rec *records, void *stream) {
     dh_fit_params prm;
     if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
-    TRY(fit_track_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
+    TRY(cam_fit_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
     TRY(dh_predict_batch_cameras_support_device_(p, frames, t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, poses_out, support_out, stream));
     DeviceGuard guard(t->cams->device);
     if (!guard.ok) return DH_EHIP;
-    return fit_track_enqueue(t, frames, w, h, present, poses_out, support_out, prm, records, (hipStream_t)stream);
+    return enqueue(t, frames, w, h, present, poses_out, support_out, prm, records, (hipStream_t)stream);
 }
 // The host forms: everything staged through the tracker's buffers on its own stream; synchronous.  p NULL: the core step on
 // the caller's poses and support; else the prediction first, its poses and support copied back too.
-static int fit_track_host(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
-                          const dh_fit_params &prm, dh_pose *poses, dh_support *support, dh_fit_track_record *records) {
+template <typename T, typename Rec, typename Enqueue>
+static int cam_fit_host(dh_predictor *p, T *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
+                        const dh_fit_params &prm, dh_pose *poses, dh_support *support, Rec *records, Enqueue enqueue) {
     const size_t n = (size_t)t->n;
     return fit_tracker_host(t, frames, w, h, present, [&](hipStream_t s) -> int {
         if (p) return DH_OK;
@@ -233,7 +274,7 @@ static int fit_track_host(dh_predictor *p, dh_fit_tracker *t, const uint16_t *fr
     }, [&](const uint16_t *fr, const uint8_t *pr, hipStream_t s) -> int {
         if (p) TRY(dh_predict_batch_cameras_support_device_(p, fr, t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, t->poses.get(),
                                                          t->support.get(), s));
-        return fit_track_enqueue(t, fr, w, h, pr, t->poses.get(), t->support.get(), prm, t->records.get(), s);
+        return enqueue(t, fr, w, h, pr, t->poses.get(), t->support.get(), prm, t->records.get(), s);
     }, [&](hipStream_t s) -> int {
         if (!p) return DH_OK;
         HIP_TRY(hipMemcpyAsync(poses, t->poses.get(), n * sizeof(dh_pose), hipMemcpyDeviceToHost, s));
@@ -241,23 +282,29 @@ static int fit_track_host(dh_predictor *p, dh_fit_tracker *t, const uint16_t *fr
         return DH_OK;
     }, records, n);
 }
-static int fit_tracker_step_poses_(dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
-                                   const dh_support *support, const dh_fit_params *fit_params, dh_fit_track_record *records) {
+template <typename T, typename Rec, typename Enqueue>
+static int cam_fit_step_poses(const char *who, Enqueue enqueue, T *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                              const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params, Rec *records) {
     dh_fit_params prm;
-    TRY(fit_track_check(t, frames, w, h, poses, support, fit_params, records, &prm, "dh_fit_tracker_step_poses"));
-    return fit_track_host(nullptr, t, frames, w, h, present, 0, prm, const_cast<dh_pose *>(poses), const_cast<dh_support *>(support), records);
+    TRY(cam_fit_check(t, frames, w, h, poses, support, fit_params, records, &prm, who));
+    return cam_fit_host(nullptr, t, frames, w, h, present, 0, prm, const_cast<dh_pose *>(poses), const_cast<dh_support *>(support), records, enqueue);
 }
-static int fit_tracker_step_(dh_predictor *p, dh_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, uint32_t radius,
-                             const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, dh_fit_track_record *records) {
-    const char *who = "dh_fit_tracker_step";
+template <typename T, typename Rec, typename Enqueue>
+static int cam_fit_step(const char *who, Enqueue enqueue, dh_predictor *p, T *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                        uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out, Rec *records) {
     dh_fit_params prm;
     if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
-    TRY(fit_track_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
+    TRY(cam_fit_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
     if (radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u (a negative int?); expected 0 .. 2^31 - 1", who, radius);
     if (t->cams->device != dh_predictor_device_(p))
         return fail(DH_EINVAL, "%s: camera table on device %d, predictor on device %d", who, t->cams->device, dh_predictor_device_(p));
-    return fit_track_host(p, t, frames, w, h, present, radius, prm, poses_out, support_out, records);
+    return cam_fit_host(p, t, frames, w, h, present, radius, prm, poses_out, support_out, records, enqueue);
 }
+// The entry points' forwards (DH_API below gives each its parameter list, which the shared form checks against its own).
+template <typename... A> static int fit_tracker_step_poses_device_(A... a) { return cam_fit_step_poses_device("dh_fit_tracker_step_poses_device", fit_track_enqueue, a...); }
+template <typename... A> static int fit_tracker_step_device_(A... a) { return cam_fit_step_device("dh_fit_tracker_step_device", fit_track_enqueue, a...); }
+template <typename... A> static int fit_tracker_step_poses_(A... a) { return cam_fit_step_poses("dh_fit_tracker_step_poses", fit_track_enqueue, a...); }
+template <typename... A> static int fit_tracker_step_(A... a) { return cam_fit_step("dh_fit_tracker_step", fit_track_enqueue, a...); }
 
 // ------------------------------------------------------------------ carrying each rig person's fitted world pose
 static int rig_fit_track_params_default_(dh_rig_fit_track_params *p) {
@@ -303,19 +350,22 @@ struct RigFitTrackerBase : FitTrackerCore {
 struct dh_rig_fit_tracker : RigFitTrackerBase {
     Buf<dh_rig_fit_record> records;      // [slots]
 };
+// The refusal of a rig whose largest view sum is above what a multi-view fit takes: `points` per view (the model's, which the
+// models of a set share).
+static int rig_terms_check(const dh_rig *rig, uint32_t points, const char *who) {
+    const int64_t largest = rig->largest;
+    if ((uint64_t)largest * points > DH_FIT_MAX_POINTS)
+        return fail(DH_EINVAL, "%s: a rig of %lld cameras sums %llu terms of a %u-point model, above %u", who, (long long)largest,
+                    (unsigned long long)((uint64_t)largest * points), points, DH_FIT_MAX_POINTS);
+    return DH_OK;
+}
 static int rig_fit_tracker_create_(const dh_rig *rig, const dh_fit_views *views, const dh_fit_model *m, float scale, uint32_t flags,
                                    const dh_rig_fit_track_params *params, dh_rig_fit_tracker **out) {
     const char *who = "dh_rig_fit_tracker_create";
     if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
     *out = nullptr;
-    dh_rig_fit_track_params prm;
-    (void)rig_fit_track_params_default_(&prm);
-    if (params) prm = *params;
+    const dh_rig_fit_track_params prm = params_or_default(rig_fit_track_params_default_, params);
     TRY(fit_tracker_create_check(prm, scale, flags, m, [&]() -> int {
-        if (prm.max_coast > prm.max_misses)
-            return fail(DH_EINVAL, "%s: max_coast %u above the max_misses %u the ids come from", who, prm.max_coast, prm.max_misses);
-        return DH_OK;
-    }, [&]() -> int {
         if (!rig) return fail(DH_EINVAL, "%s: NULL rig table", who);
         if (!views) return fail(DH_EINVAL, "%s: NULL view table", who);
         if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
@@ -324,10 +374,7 @@ static int rig_fit_tracker_create_(const dh_rig *rig, const dh_fit_views *views,
             return fail(DH_EINVAL, "%s: the model lives on device %d, the tables on %d", who, m->device, rig->cams->device);
         return DH_OK;
     }, who));
-    const int64_t largest = rig->largest;
-    if ((uint64_t)largest * m->n > DH_FIT_MAX_POINTS)
-        return fail(DH_EINVAL, "%s: a rig of %lld cameras sums %llu terms of a %u-point model, above %u", who, (long long)largest,
-                    (unsigned long long)((uint64_t)largest * m->n), m->n, DH_FIT_MAX_POINTS);
+    TRY(rig_terms_check(rig, m->n, who));
     const size_t ng = (size_t)rig->n_rigs, slots = ng * DH_RIG_MAX_TRACKS;
     return create_tracker(rig->cams, out, [&](dh_rig_fit_tracker &t, size_t n) -> int {
         TRY(t.alloc_rig(rig, views, prm, n));
@@ -393,15 +440,18 @@ static int rig_fit_enqueue(dh_rig_fit_tracker *t, const uint16_t *frames, int w,
     TRY(hip_step(dh_launch_rig_fit_update(a, s), "k_rig_fit_update"));
     return DH_OK;
 }
-static int rig_fit_tracker_step_persons_device_(dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
-                                                const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons,
-                                                const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_fit_record *records,
-                                                void *stream) {
+// The four forms of a step, written once for the rig pair.  T: either rig tracker; Rec: its record; enqueue: its core step on
+// device arrays (rig_fit_enqueue's parameter list); who names the entry point.  The _device forms allocate nothing and never
+// wait on the host.
+template <typename T, typename Rec, typename Enqueue>
+static int rig_fit_step_persons_device(const char *who, Enqueue enqueue, T *t, const uint16_t *frames, int w, int h, const uint8_t *present,
+                                       int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons,
+                                       const dh_rig_person *persons, const dh_fit_params *fit_params, Rec *records, void *stream) {
     dh_fit_params prm;
-    TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm, "dh_rig_fit_tracker_step_persons_device"));
+    TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm, who));
     DeviceGuard guard(t->cams->device);
     if (!guard.ok) return DH_EHIP;
-    return rig_fit_enqueue(t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, prm, records, (hipStream_t)stream);
+    return enqueue(t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, prm, records, (hipStream_t)stream);
 }
 // The refusals of the whole step beyond the core step's: the rig tracker must step the tracker's own rig table and must not
 // drop an id sooner than the tracker stops coasting on it.
@@ -418,17 +468,16 @@ static int rig_fit_step_check(const dh_predictor *p, const RigFitTrackerBase *t,
         return fail(DH_EINVAL, "%s: the rig tracker's max_misses %u is below the fit tracker's max_coast %u", who, rt->prm.max_misses, t->prm.max_coast);
     return DH_OK;
 }
-static int rig_fit_tracker_step_device_(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
-                                        const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *ids,
-                                        uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records,
-                                        void *stream) {
-    const char *who = "dh_rig_fit_tracker_step_device";
+template <typename T, typename Rec, typename Enqueue>
+static int rig_fit_step_device(const char *who, Enqueue enqueue, dh_predictor *p, T *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
+                               const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *ids,
+                               uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, Rec *records, void *stream) {
     dh_fit_params prm;
     TRY(rig_fit_step_check(p, t, rt, frames, w, h, n_heads, heads, ids, n_persons, persons, fit_params, records, &prm, who));
     TRY(dh_rig_tracker_step_device_(p, rt, frames, w, h, present, n_heads, heads, ids, n_persons, persons, tracks, stream));
     DeviceGuard guard(t->cams->device);
     if (!guard.ok) return DH_EHIP;
-    return rig_fit_enqueue(t, frames, w, h, present, rt->prm.max_heads, n_heads, heads, n_persons, persons, prm, records, (hipStream_t)stream);
+    return enqueue(t, frames, w, h, present, rt->prm.max_heads, n_heads, heads, n_persons, persons, prm, records, (hipStream_t)stream);
 }
 // The host forms: everything staged through the tracker's buffers on its own stream; synchronous.  p NULL: the core step on
 // the caller's heads and persons; else the rig step first (its device form, on the staged frames), its outputs copied back too.
@@ -461,24 +510,30 @@ static int rig_fit_host(dh_predictor *p, T *t, dh_rig_tracker *rt, const uint16_
         return DH_OK;
     }, records, ng * DH_RIG_MAX_TRACKS);
 }
-static int rig_fit_tracker_step_persons_(dh_rig_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
-                                         const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons,
-                                         const dh_fit_params *fit_params, dh_rig_fit_record *records) {
+template <typename T, typename Rec, typename Enqueue>
+static int rig_fit_step_persons(const char *who, Enqueue enqueue, T *t, const uint16_t *frames, int w, int h, const uint8_t *present, int max_heads,
+                                const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons, const dh_rig_person *persons,
+                                const dh_fit_params *fit_params, Rec *records) {
     dh_fit_params prm;
-    TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm, "dh_rig_fit_tracker_step_persons"));
+    TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm, who));
     return rig_fit_host(nullptr, t, nullptr, frames, w, h, present, max_heads, prm, const_cast<uint32_t *>(n_heads), const_cast<dh_head *>(heads),
-                        nullptr, const_cast<uint32_t *>(n_persons), const_cast<dh_rig_person *>(persons), nullptr, records, rig_fit_enqueue);
+                        nullptr, const_cast<uint32_t *>(n_persons), const_cast<dh_rig_person *>(persons), nullptr, records, enqueue);
 }
-static int rig_fit_tracker_step_(dh_predictor *p, dh_rig_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
-                                 const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *ids,
-                                 uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_fit_record *records) {
-    const char *who = "dh_rig_fit_tracker_step";
+template <typename T, typename Rec, typename Enqueue>
+static int rig_fit_step(const char *who, Enqueue enqueue, dh_predictor *p, T *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
+                        const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *ids,
+                        uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, Rec *records) {
     dh_fit_params prm;
     TRY(rig_fit_step_check(p, t, rt, frames, w, h, n_heads, heads, ids, n_persons, persons, fit_params, records, &prm, who));
     if (t->cams->device != dh_predictor_device_(p))
         return fail(DH_EINVAL, "%s: rig table on device %d, predictor on device %d", who, t->cams->device, dh_predictor_device_(p));
-    return rig_fit_host(p, t, rt, frames, w, h, present, rt->prm.max_heads, prm, n_heads, heads, ids, n_persons, persons, tracks, records, rig_fit_enqueue);
+    return rig_fit_host(p, t, rt, frames, w, h, present, rt->prm.max_heads, prm, n_heads, heads, ids, n_persons, persons, tracks, records, enqueue);
 }
+// The entry points' forwards, as the camera fit tracker's.
+template <typename... A> static int rig_fit_tracker_step_persons_device_(A... a) { return rig_fit_step_persons_device("dh_rig_fit_tracker_step_persons_device", rig_fit_enqueue, a...); }
+template <typename... A> static int rig_fit_tracker_step_device_(A... a) { return rig_fit_step_device("dh_rig_fit_tracker_step_device", rig_fit_enqueue, a...); }
+template <typename... A> static int rig_fit_tracker_step_persons_(A... a) { return rig_fit_step_persons("dh_rig_fit_tracker_step_persons", rig_fit_enqueue, a...); }
+template <typename... A> static int rig_fit_tracker_step_(A... a) { return rig_fit_step("dh_rig_fit_tracker_step", rig_fit_enqueue, a...); }
 
 // ------------------------------------------------------------------ following each tracked head with its own subject's model
 static int subject_track_params_default_(dh_subject_track_params *p) {
@@ -543,17 +598,47 @@ struct SubjectParts {
     }
 };
 
-// A FitTrackerCore whose model table holds the set's S models and the generic one at index S (core.model: the generic one), whose
+// What the creation of either subject tracker refuses after its NULL handles (set and m are not NULL), in the header's order: the
+// ident params by ident_check (dh_ident_params_check_ or dh_ident_views_params_check_; *iprm is what the tracker runs with), the
+// reserved words of sprm, and the set (*sv) and the generic model against `device`, where `tables` live, and against each other.
+static int subject_create_check(const dh_fit_subjects *set, const dh_fit_model *m, float scale, const dh_ident_params *ident_params,
+                                int (*ident_check)(const dh_ident_params *, dh_ident_params *, const char *),
+                                const dh_subject_track_params &sprm, int device, const char *tables, dh_ident_params *iprm, SubjectsView *sv,
+                                const char *who) {
+    TRY(ident_check(ident_params, iprm, who));
+    if (sprm.reserved[0] || sprm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the dh_subject_track_params is not 0", who);
+    dh_fit_subjects_view_(set, sv, nullptr);
+    if (sv->device != device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the %s on %d", who, sv->device, tables, device);
+    if (m->device != device) return fail(DH_EINVAL, "%s: the model lives on device %d, the %s on %d", who, m->device, tables, device);
+    if (m->n != sv->n) return fail(DH_EINVAL, "%s: the generic model has %u points, a model of the set %u", who, m->n, sv->n);
+    const double extent = fabs((double)scale) * sv->radius;
+    if (extent > DH_FIT_MAX_EXTENT)
+        return fail(DH_EINVAL, "%s: a model of the set may span %g mm from its origin (limit %g)", who, extent, DH_FIT_MAX_EXTENT);
+    return DH_OK;
+}
+// What either subject tracker T reports of itself (`units`: its cameras or its rigs) and the change of its mask.
+template <typename T>
+static int subject_tracker_info(const T *t, int units, int *n_units, uint32_t *n_subjects, uint32_t *score_workgroups, const char *who) {
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
+    if (n_units) *n_units = units;
+    if (n_subjects) *n_subjects = t->sv.n_subjects;
+    if (score_workgroups) *score_workgroups = t->grid;
+    return DH_OK;
+}
+template <typename T>
+static int subject_tracker_set_enrolled(T *t, const uint8_t *enrolled, void *stream, const char *who) {
+    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
+    DeviceGuard guard(t->cams->device);
+    if (!guard.ok) return DH_EHIP;
+    return t->put_enrolled(enrolled, (hipStream_t)stream);
+}
+
+// A CamFitTrackerBase whose model table holds the set's S models and the generic one at index S (core.model: the generic one), whose
 // state carries each camera's binding, and which owns what an identification needs: the mask, the list and the pair scratch.
-struct dh_subject_fit_tracker : FitTrackerCore, SubjectParts {
-    dh_fit_track_params prm{};
+struct dh_subject_fit_tracker : CamFitTrackerBase, SubjectParts {
     Buf<dh_subject_track_state> state;   // [n]
-    Buf<dh_render_instance> start, fit_out;
-    Buf<dh_fit_record> fit_rec;
     Buf<dh_fit_record> score;            // [n][S]
-    Buf<dh_pose> poses;                  // host forms
-    Buf<dh_support> support;
-    Buf<dh_subject_track_record> records;
+    Buf<dh_subject_track_record> records;    // host forms
     // zeros, and DH_IDENT_UNKNOWN (every byte 0xFF) in the subject word of each state
     int clear(size_t c0, size_t m, hipStream_t st) {
         HIP_TRY(hipMemsetAsync(state.get() + c0, 0, m * sizeof(dh_subject_track_state), st));
@@ -567,42 +652,22 @@ static int subject_fit_tracker_create_(const dh_cameras *c, const dh_fit_subject
     const char *who = "dh_subject_fit_tracker_create";
     if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
     *out = nullptr;
-    dh_fit_track_params prm;
-    (void)fit_track_params_default_(&prm);
-    if (track_params) prm = *track_params;
-    dh_subject_track_params sprm;
-    (void)subject_track_params_default_(&sprm);
-    if (params) sprm = *params;
+    const dh_fit_track_params prm = params_or_default(fit_track_params_default_, track_params);
+    const dh_subject_track_params sprm = params_or_default(subject_track_params_default_, params);
     dh_ident_params iprm;
     SubjectsView sv{};
     TRY(fit_tracker_create_check(prm, scale, flags, m, [&]() -> int {
-        if (prm.conf_den == 0 || prm.conf_num > prm.conf_den)
-            return fail(DH_EINVAL, "%s: confidence %u / %u, expected a fraction in [0, 1]", who, prm.conf_num, prm.conf_den);
-        return DH_OK;
-    }, [&]() -> int {
         if (!c) return fail(DH_EINVAL, "%s: NULL camera table", who);
         if (!set) return fail(DH_EINVAL, "%s: NULL subject set", who);
         if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
-        TRY(dh_ident_params_check_(ident_params, &iprm, who));
-        if (sprm.reserved[0] || sprm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the dh_subject_track_params is not 0", who);
-        dh_fit_subjects_view_(set, &sv, nullptr);
-        if (sv.device != c->device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the camera table on %d", who, sv.device, c->device);
-        if (m->device != c->device) return fail(DH_EINVAL, "%s: the model lives on device %d, the camera table on %d", who, m->device, c->device);
-        if (m->n != sv.n) return fail(DH_EINVAL, "%s: the generic model has %u points, a model of the set %u", who, m->n, sv.n);
-        const double extent = fabs((double)scale) * sv.radius;
-        if (extent > DH_FIT_MAX_EXTENT)
-            return fail(DH_EINVAL, "%s: a model of the set may span %g mm from its origin (limit %g)", who, extent, DH_FIT_MAX_EXTENT);
-        return DH_OK;
+        return subject_create_check(set, m, scale, ident_params, dh_ident_params_check_, sprm, c->device, "camera table", &iprm, &sv, who);
     }, who));
     const uint64_t pairs = (uint64_t)c->n * sv.n_subjects;
     if (pairs > DH_IDENT_MAX_PAIRS)
         return fail(DH_EINVAL, "%s: %d cameras times %u subjects exceed %u pairs", who, c->n, sv.n_subjects, DH_IDENT_MAX_PAIRS);
     return create_tracker(c, out, [&](dh_subject_fit_tracker &t, size_t n) -> int {
-        t.prm = prm;
-        TRY(t.state.alloc(n));
-        TRY(t.start.alloc(n)); TRY(t.fit_out.alloc(n)); TRY(t.fit_rec.alloc(n));
-        TRY(t.score.alloc((size_t)pairs));
-        TRY(t.poses.alloc(n)); TRY(t.support.alloc(n)); TRY(t.records.alloc(n));
+        TRY(t.alloc_cam(prm, n));
+        TRY(t.state.alloc(n)); TRY(t.score.alloc((size_t)pairs)); TRY(t.records.alloc(n));
         TRY(t.init_fit(m, scale, flags, prm.rms_max, prm.max_jump, n));
         return t.init_subjects(set, m, iprm, sprm, n, c->device, t.models, enrolled);
     });
@@ -612,24 +677,13 @@ static int subject_fit_tracker_reset_(dh_subject_fit_tracker *t, int camera, voi
     return reset_tracker(t, camera, stream, "dh_subject_fit_tracker_reset");
 }
 static int subject_fit_tracker_state_(dh_subject_fit_tracker *t, dh_subject_track_state *states) {
-    if (t && !states) return fail(DH_EINVAL, "dh_subject_fit_tracker_state: NULL argument");
-    return read_tracker(t, "dh_subject_fit_tracker_state", [&](size_t n) -> int {
-        HIP_TRY(hipMemcpy(states, t->state.get(), n * sizeof(dh_subject_track_state), hipMemcpyDeviceToHost));
-        return DH_OK;
-    });
+    return cam_fit_state(t, states, "dh_subject_fit_tracker_state");
 }
 static int subject_fit_tracker_info_(const dh_subject_fit_tracker *t, int *n_cams, uint32_t *n_subjects, uint32_t *score_workgroups) {
-    if (!t) return fail(DH_EINVAL, "dh_subject_fit_tracker_info: NULL tracker");
-    if (n_cams) *n_cams = t->n;
-    if (n_subjects) *n_subjects = t->sv.n_subjects;
-    if (score_workgroups) *score_workgroups = t->grid;
-    return DH_OK;
+    return subject_tracker_info(t, t ? t->n : 0, n_cams, n_subjects, score_workgroups, "dh_subject_fit_tracker_info");
 }
 static int subject_fit_tracker_set_enrolled_(dh_subject_fit_tracker *t, const uint8_t *enrolled, void *stream) {
-    if (!t) return fail(DH_EINVAL, "dh_subject_fit_tracker_set_enrolled: NULL tracker");
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    return t->put_enrolled(enrolled, (hipStream_t)stream);
+    return subject_tracker_set_enrolled(t, enrolled, stream, "dh_subject_fit_tracker_set_enrolled");
 }
 static int subject_fit_tracker_bind_(dh_subject_fit_tracker *t, int camera, uint32_t subject, void *stream) {
     const char *who = "dh_subject_fit_tracker_bind";
@@ -644,34 +698,14 @@ static int subject_fit_tracker_bind_(dh_subject_fit_tracker *t, int camera, uint
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&st->wait, 0, 3, (hipStream_t)stream));      // wait, tries, bound_age
     return DH_OK;
 }
-// The refusals of a step that are the tracker's own: section 19's.
-static int subject_track_check(const dh_subject_fit_tracker *t, const void *frames, int w, int h, const void *poses, const void *support,
-                               const dh_fit_params *in, const void *records, dh_fit_params *prm, const char *who) {
-    if (!t) return fail(DH_EINVAL, "%s: NULL tracker", who);
-    if (!frames) return fail(DH_EINVAL, "%s: NULL frames", who);
-    if (!poses || !support) return fail(DH_EINVAL, "%s: NULL poses or support", who);
-    if (!records) return fail(DH_EINVAL, "%s: NULL records", who);
-    TRY(check_frame_size(w, h, who));
-    return fit_params_check(in, prm, who);
-}
 // One step of every camera on device arrays and stream s (arguments checked, device selected): five launches, a linear chain.
+// (g.a.state and g.a.records stay 0: the state and the records of this tracker travel in g itself.)
 static int subject_track_enqueue(dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present, const dh_pose *poses,
                                  const dh_support *support, const dh_fit_params &prm, dh_subject_track_record *records, hipStream_t s) {
     SubjectTrackArgs g;
     memset(&g, 0, sizeof g);
-    FitTrackArgs &a = g.a;
-    a.n = t->n; a.flags = t->flags; a.scale = t->scale; a.prm = t->prm; a.rms_lim = t->rms_lim; a.jump2 = t->jump2;
-    a.coarse = prm.coarse_iterations; a.full = prm.iterations;
-    a.angles = t->angles.get(); a.present = present; a.poses = poses; a.support = support;
-    a.start = t->start.get(); a.sched = t->sched.get(); a.seed = t->seed.get();
-    a.fit_out = t->fit_out.get(); a.fit_rec = t->fit_rec.get();
     FitSchedArgs f;
-    memset(&f, 0, sizeof f);
-    f.f.frames = frames; f.f.n = t->n; f.f.w = w; f.f.h = h;
-    f.f.cams = t->cams->dev.get(); f.f.models = t->models.get(); f.f.inst = t->start.get(); f.f.n_inst = (uint32_t)t->n;
-    fit_args_params(f.f, prm);                             // (k_fit_sched reads coarse and full per instance from sched)
-    f.f.out = t->fit_out.get(); f.f.rec = t->fit_rec.get();
-    f.sched = t->sched.get(); f.seed = t->seed.get();
+    cam_fit_args(t, frames, w, h, present, poses, support, prm, g.a, f);
     IdentArgs &q = g.q;
     q.f.frames = frames; q.f.n = t->n; q.f.w = w; q.f.h = h;
     q.f.cams = t->cams->dev.get(); q.f.inst = t->fit_out.get(); q.f.n_inst = (uint32_t)t->n;
@@ -688,66 +722,11 @@ static int subject_track_enqueue(dh_subject_fit_tracker *t, const uint16_t *fram
     TRY(hip_step(dh_launch_subject_track_bind(g, s), "k_subject_track_bind"));
     return DH_OK;
 }
-static int subject_fit_tracker_step_poses_device_(dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
-                                                  const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params,
-                                                  dh_subject_track_record *records, void *stream) {
-    dh_fit_params prm;
-    TRY(subject_track_check(t, frames, w, h, poses, support, fit_params, records, &prm, "dh_subject_fit_tracker_step_poses_device"));
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    return subject_track_enqueue(t, frames, w, h, present, poses, support, prm, records, (hipStream_t)stream);
-}
-static int subject_fit_tracker_step_device_(dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
-                                            uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out,
-                                            dh_subject_track_record *records, void *stream) {
-    const char *who = "dh_subject_fit_tracker_step_device";
-    dh_fit_params prm;
-    if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
-    TRY(subject_track_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
-    TRY(dh_predict_batch_cameras_support_device_(p, frames, t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, poses_out, support_out, stream));
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    return subject_track_enqueue(t, frames, w, h, present, poses_out, support_out, prm, records, (hipStream_t)stream);
-}
-// The host forms, as the camera fit tracker's: p NULL: the core step on the caller's poses and support; else the prediction first.
-static int subject_track_host(dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
-                              uint32_t radius, const dh_fit_params &prm, dh_pose *poses, dh_support *support, dh_subject_track_record *records) {
-    const size_t n = (size_t)t->n;
-    return fit_tracker_host(t, frames, w, h, present, [&](hipStream_t s) -> int {
-        if (p) return DH_OK;
-        HIP_TRY(hipMemcpyAsync(t->poses.get(), poses, n * sizeof(dh_pose), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(t->support.get(), support, n * sizeof(dh_support), hipMemcpyHostToDevice, s));
-        return DH_OK;
-    }, [&](const uint16_t *fr, const uint8_t *pr, hipStream_t s) -> int {
-        if (p) TRY(dh_predict_batch_cameras_support_device_(p, fr, t->n, w, h, t->cams, nullptr, nullptr, nullptr, radius, t->poses.get(),
-                                                         t->support.get(), s));
-        return subject_track_enqueue(t, fr, w, h, pr, t->poses.get(), t->support.get(), prm, t->records.get(), s);
-    }, [&](hipStream_t s) -> int {
-        if (!p) return DH_OK;
-        HIP_TRY(hipMemcpyAsync(poses, t->poses.get(), n * sizeof(dh_pose), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(support, t->support.get(), n * sizeof(dh_support), hipMemcpyDeviceToHost, s));
-        return DH_OK;
-    }, records, n);
-}
-static int subject_fit_tracker_step_poses_(dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
-                                           const dh_pose *poses, const dh_support *support, const dh_fit_params *fit_params,
-                                           dh_subject_track_record *records) {
-    dh_fit_params prm;
-    TRY(subject_track_check(t, frames, w, h, poses, support, fit_params, records, &prm, "dh_subject_fit_tracker_step_poses"));
-    return subject_track_host(nullptr, t, frames, w, h, present, 0, prm, const_cast<dh_pose *>(poses), const_cast<dh_support *>(support), records);
-}
-static int subject_fit_tracker_step_(dh_predictor *p, dh_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
-                                     uint32_t radius, const dh_fit_params *fit_params, dh_pose *poses_out, dh_support *support_out,
-                                     dh_subject_track_record *records) {
-    const char *who = "dh_subject_fit_tracker_step";
-    dh_fit_params prm;
-    if (!p) return fail(DH_EINVAL, "%s: NULL predictor", who);
-    TRY(subject_track_check(t, frames, w, h, poses_out, support_out, fit_params, records, &prm, who));
-    if (radius > 0x7fffffffu) return fail(DH_EINVAL, "%s: radius %u (a negative int?); expected 0 .. 2^31 - 1", who, radius);
-    if (t->cams->device != dh_predictor_device_(p))
-        return fail(DH_EINVAL, "%s: camera table on device %d, predictor on device %d", who, t->cams->device, dh_predictor_device_(p));
-    return subject_track_host(p, t, frames, w, h, present, radius, prm, poses_out, support_out, records);
-}
+// The entry points' forwards to the camera pair's forms (section 19's step check, host form and refusals) with this core step.
+template <typename... A> static int subject_fit_tracker_step_poses_device_(A... a) { return cam_fit_step_poses_device("dh_subject_fit_tracker_step_poses_device", subject_track_enqueue, a...); }
+template <typename... A> static int subject_fit_tracker_step_device_(A... a) { return cam_fit_step_device("dh_subject_fit_tracker_step_device", subject_track_enqueue, a...); }
+template <typename... A> static int subject_fit_tracker_step_poses_(A... a) { return cam_fit_step_poses("dh_subject_fit_tracker_step_poses", subject_track_enqueue, a...); }
+template <typename... A> static int subject_fit_tracker_step_(A... a) { return cam_fit_step("dh_subject_fit_tracker_step", subject_track_enqueue, a...); }
 
 // ------------------------------------------------------------------ following each rig person with its own subject's model
 // The rig fit tracker's core with the subject trackers' parts: the entries' dh_rig_fit_state in `state`, the four words of their
@@ -772,40 +751,19 @@ static int rig_subject_fit_tracker_create_(const dh_rig *rig, const dh_fit_views
     const char *who = "dh_rig_subject_fit_tracker_create";
     if (!out) return fail(DH_EINVAL, "%s: NULL argument", who);
     *out = nullptr;
-    dh_rig_fit_track_params prm;
-    (void)rig_fit_track_params_default_(&prm);
-    if (track_params) prm = *track_params;
-    dh_subject_track_params sprm;
-    (void)subject_track_params_default_(&sprm);
-    if (params) sprm = *params;
+    const dh_rig_fit_track_params prm = params_or_default(rig_fit_track_params_default_, track_params);
+    const dh_subject_track_params sprm = params_or_default(subject_track_params_default_, params);
     dh_ident_params iprm;
     SubjectsView sv{};
     TRY(fit_tracker_create_check(prm, scale, flags, m, [&]() -> int {
-        if (prm.max_coast > prm.max_misses)
-            return fail(DH_EINVAL, "%s: max_coast %u above the max_misses %u the ids come from", who, prm.max_coast, prm.max_misses);
-        return DH_OK;
-    }, [&]() -> int {
         if (!rig) return fail(DH_EINVAL, "%s: NULL rig table", who);
         if (!views) return fail(DH_EINVAL, "%s: NULL view table", who);
         if (!set) return fail(DH_EINVAL, "%s: NULL subject set", who);
         if (!m) return fail(DH_EINVAL, "%s: NULL model", who);
         if (views->cams != rig->cams) return fail(DH_EINVAL, "%s: the rig table and the view table are bound to different camera tables", who);
-        TRY(dh_ident_views_params_check_(ident_params, &iprm, who));
-        if (sprm.reserved[0] || sprm.reserved[1]) return fail(DH_EINVAL, "%s: a reserved word of the dh_subject_track_params is not 0", who);
-        dh_fit_subjects_view_(set, &sv, nullptr);
-        const int device = rig->cams->device;
-        if (sv.device != device) return fail(DH_EINVAL, "%s: the subject set lives on device %d, the tables on %d", who, sv.device, device);
-        if (m->device != device) return fail(DH_EINVAL, "%s: the model lives on device %d, the tables on %d", who, m->device, device);
-        if (m->n != sv.n) return fail(DH_EINVAL, "%s: the generic model has %u points, a model of the set %u", who, m->n, sv.n);
-        const double extent = fabs((double)scale) * sv.radius;
-        if (extent > DH_FIT_MAX_EXTENT)
-            return fail(DH_EINVAL, "%s: a model of the set may span %g mm from its origin (limit %g)", who, extent, DH_FIT_MAX_EXTENT);
-        return DH_OK;
+        return subject_create_check(set, m, scale, ident_params, dh_ident_views_params_check_, sprm, rig->cams->device, "tables", &iprm, &sv, who);
     }, who));
-    const int64_t largest = rig->largest;
-    if ((uint64_t)largest * sv.n > DH_FIT_MAX_POINTS)
-        return fail(DH_EINVAL, "%s: a rig of %lld cameras sums %llu terms of a %u-point model, above %u", who, (long long)largest,
-                    (unsigned long long)((uint64_t)largest * sv.n), sv.n, DH_FIT_MAX_POINTS);
+    TRY(rig_terms_check(rig, sv.n, who));
     const size_t ng = (size_t)rig->n_rigs, slots = ng * DH_RIG_MAX_TRACKS;
     const uint64_t pairs = (uint64_t)slots * sv.n_subjects;
     if (pairs > DH_IDENT_MAX_PAIRS)
@@ -835,17 +793,10 @@ static int rig_subject_fit_tracker_state_(dh_rig_subject_fit_tracker *t, dh_rig_
     });
 }
 static int rig_subject_fit_tracker_info_(const dh_rig_subject_fit_tracker *t, int *n_rigs, uint32_t *n_subjects, uint32_t *score_workgroups) {
-    if (!t) return fail(DH_EINVAL, "dh_rig_subject_fit_tracker_info: NULL tracker");
-    if (n_rigs) *n_rigs = t->rig->n_rigs;
-    if (n_subjects) *n_subjects = t->sv.n_subjects;
-    if (score_workgroups) *score_workgroups = t->grid;
-    return DH_OK;
+    return subject_tracker_info(t, t ? t->rig->n_rigs : 0, n_rigs, n_subjects, score_workgroups, "dh_rig_subject_fit_tracker_info");
 }
 static int rig_subject_fit_tracker_set_enrolled_(dh_rig_subject_fit_tracker *t, const uint8_t *enrolled, void *stream) {
-    if (!t) return fail(DH_EINVAL, "dh_rig_subject_fit_tracker_set_enrolled: NULL tracker");
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    return t->put_enrolled(enrolled, (hipStream_t)stream);
+    return subject_tracker_set_enrolled(t, enrolled, stream, "dh_rig_subject_fit_tracker_set_enrolled");
 }
 static int rig_subject_fit_tracker_bind_(dh_rig_subject_fit_tracker *t, int rig, uint32_t id, uint32_t subject, void *stream) {
     const char *who = "dh_rig_subject_fit_tracker_bind";
@@ -884,49 +835,11 @@ static int rig_subject_enqueue(dh_rig_subject_fit_tracker *t, const uint16_t *fr
     TRY(hip_step(dh_launch_rig_subject_bind(g, s), "k_rig_subject_bind"));
     return DH_OK;
 }
-static int rig_subject_fit_tracker_step_persons_device_(dh_rig_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
-                                                        int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons,
-                                                        const dh_rig_person *persons, const dh_fit_params *fit_params,
-                                                        dh_rig_subject_record *records, void *stream) {
-    dh_fit_params prm;
-    TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm,
-                      "dh_rig_subject_fit_tracker_step_persons_device"));
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    return rig_subject_enqueue(t, frames, w, h, present, max_heads, n_heads, heads, n_persons, persons, prm, records, (hipStream_t)stream);
-}
-static int rig_subject_fit_tracker_step_device_(dh_predictor *p, dh_rig_subject_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w,
-                                                int h, const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads,
-                                                uint32_t *ids, uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks,
-                                                dh_rig_subject_record *records, void *stream) {
-    const char *who = "dh_rig_subject_fit_tracker_step_device";
-    dh_fit_params prm;
-    TRY(rig_fit_step_check(p, t, rt, frames, w, h, n_heads, heads, ids, n_persons, persons, fit_params, records, &prm, who));
-    TRY(dh_rig_tracker_step_device_(p, rt, frames, w, h, present, n_heads, heads, ids, n_persons, persons, tracks, stream));
-    DeviceGuard guard(t->cams->device);
-    if (!guard.ok) return DH_EHIP;
-    return rig_subject_enqueue(t, frames, w, h, present, rt->prm.max_heads, n_heads, heads, n_persons, persons, prm, records, (hipStream_t)stream);
-}
-static int rig_subject_fit_tracker_step_persons_(dh_rig_subject_fit_tracker *t, const uint16_t *frames, int w, int h, const uint8_t *present,
-                                                 int max_heads, const uint32_t *n_heads, const dh_head *heads, const uint32_t *n_persons,
-                                                 const dh_rig_person *persons, const dh_fit_params *fit_params, dh_rig_subject_record *records) {
-    dh_fit_params prm;
-    TRY(rig_fit_check(t, frames, w, h, max_heads, n_heads, heads, n_persons, persons, fit_params, records, &prm,
-                      "dh_rig_subject_fit_tracker_step_persons"));
-    return rig_fit_host(nullptr, t, nullptr, frames, w, h, present, max_heads, prm, const_cast<uint32_t *>(n_heads), const_cast<dh_head *>(heads),
-                        nullptr, const_cast<uint32_t *>(n_persons), const_cast<dh_rig_person *>(persons), nullptr, records, rig_subject_enqueue);
-}
-static int rig_subject_fit_tracker_step_(dh_predictor *p, dh_rig_subject_fit_tracker *t, dh_rig_tracker *rt, const uint16_t *frames, int w, int h,
-                                         const uint8_t *present, const dh_fit_params *fit_params, uint32_t *n_heads, dh_head *heads, uint32_t *ids,
-                                         uint32_t *n_persons, dh_rig_person *persons, dh_rig_track *tracks, dh_rig_subject_record *records) {
-    const char *who = "dh_rig_subject_fit_tracker_step";
-    dh_fit_params prm;
-    TRY(rig_fit_step_check(p, t, rt, frames, w, h, n_heads, heads, ids, n_persons, persons, fit_params, records, &prm, who));
-    if (t->cams->device != dh_predictor_device_(p))
-        return fail(DH_EINVAL, "%s: rig table on device %d, predictor on device %d", who, t->cams->device, dh_predictor_device_(p));
-    return rig_fit_host(p, t, rt, frames, w, h, present, rt->prm.max_heads, prm, n_heads, heads, ids, n_persons, persons, tracks, records,
-                        rig_subject_enqueue);
-}
+// The entry points' forwards to the rig pair's forms (section 22's checks, host form and refusals) with this core step.
+template <typename... A> static int rig_subject_fit_tracker_step_persons_device_(A... a) { return rig_fit_step_persons_device("dh_rig_subject_fit_tracker_step_persons_device", rig_subject_enqueue, a...); }
+template <typename... A> static int rig_subject_fit_tracker_step_device_(A... a) { return rig_fit_step_device("dh_rig_subject_fit_tracker_step_device", rig_subject_enqueue, a...); }
+template <typename... A> static int rig_subject_fit_tracker_step_persons_(A... a) { return rig_fit_step_persons("dh_rig_subject_fit_tracker_step_persons", rig_subject_enqueue, a...); }
+template <typename... A> static int rig_subject_fit_tracker_step_(A... a) { return rig_fit_step("dh_rig_subject_fit_tracker_step", rig_subject_enqueue, a...); }
 
 // ------------------------------------------------------------------ the C ABI (DH_API: dh_runtime.h)
 DH_API(fit_track_params_default, (dh_fit_track_params *p), (p))

@@ -902,8 +902,32 @@ def angles() -> np.ndarray:
     return out
 
 
-class _StepInputs:
-    """What the host steps of both fit trackers make of their frames and present bytes (self.n cameras of self.h x self.w)."""
+def rig_fit_track_params(iterations_tracked=None, keep_points=None, rms_max=None, max_jump=None, max_coast=None,
+                         max_misses=None) -> "_lib.RigFitTrackParams":
+    """dh_rig_fit_track_params_default with the given fields replaced; `max_misses` is the rig tracker's, which the ids come from."""
+    return _params(_lib.RigFitTrackParams, "dh_rig_fit_track_params_default", iterations_tracked=iterations_tracked, keep_points=keep_points,
+                   rms_max=rms_max, max_jump=max_jump, max_coast=max_coast, max_misses=max_misses)
+
+
+def subject_track_params(retry=None, max_tries=None) -> "_lib.SubjectTrackParams":
+    """dh_subject_track_params_default with the given fields replaced."""
+    return _params(_lib.SubjectTrackParams, "dh_subject_track_params_default", retry=retry, max_tries=max_tries)
+
+
+class _FitTrackerBase(_lib._Handle):
+    """What the four fit trackers share: the handle, self.n cameras of self.h x self.w, and what a host step
+    makes of its frames and present bytes.  A class sets _prefix, the C name its entry points begin with, and the dtypes of its
+    records and of its state."""
+    _prefix = _record_dtype = _state_dtype = None
+
+    def _open(self, model: Model, w: int, h: int, motion: bool, n: int) -> None:
+        self._lib = _lib.load()
+        self.model, self.w, self.h, self.n = model, int(w), int(h), n
+        self.flags = FIT_TRACK_MOTION if motion else 0
+        self._h = C.c_void_p()
+
+    def _call(self, name: str, *args) -> None:
+        check(getattr(self._lib, f"{self._prefix}_{name}")(*args))
 
     def _frames(self, frames) -> np.ndarray:
         frames = np.ascontiguousarray(frames, dtype=np.uint16)
@@ -914,165 +938,99 @@ class _StepInputs:
     def _present(self, present):
         return None if present is None else np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n)
 
+    def _reset(self, unit, stream) -> None:
+        self._call("reset", self._h, C.c_int(-1 if unit is None else int(unit)), C.c_void_p(int(stream)))
 
-class FitTracker(_StepInputs, _lib._Handle):
+    def _state(self, *shape) -> np.ndarray:
+        st = np.zeros(shape, self._state_dtype)
+        self._call("state", self._h, vp(st))
+        return st
+
+
+class _SubjectBound:
+    """What a binding to a `Subjects` set (self.subjects, S subjects) adds to a fit tracker; `bind` is the tracker's own."""
+
+    def _mask(self, enrolled):
+        return None if enrolled is None else np.ascontiguousarray(enrolled, dtype=np.uint8).reshape(len(self.subjects))
+
+    def info(self):
+        """(cameras of a SubjectFitTracker, rigs of a RigSubjectFitTracker; S; the workgroups of the score kernel's grid), ints."""
+        n, s, g = C.c_int(), C.c_uint32(), C.c_uint32()
+        self._call("info", self._h, C.byref(n), C.byref(s), C.byref(g))
+        return n.value, s.value, g.value
+
+    def set_enrolled(self, enrolled, stream: int = 0) -> None:
+        """Replace the candidates' mask (u8 [S], None: all); stream-ordered."""
+        self._call("set_enrolled", self._h, vp(self._mask(enrolled)), C.c_void_p(int(stream)))
+
+
+class _CameraFitTracker(_FitTrackerBase):
+    """The steps of the camera pair.  Records: FIT_TRACK_RECORD_DTYPE [n] of a FitTracker, SUBJECT_TRACK_RECORD_DTYPE [n] of a
+    SubjectFitTracker (dh_fit_track_record, dh_subject_track_record on the device)."""
+
+    def step_poses(self, frames, poses, support, present=None, fit_params=None) -> np.ndarray:
+        """The core step from the forest's POSE_DTYPE [n] and SUPPORT_DTYPE [n] of host frames [n, h, w] u16 (present: u8 [n] or
+        None): -> the records [n], FIT_TRACK_RECORD_DTYPE or SUBJECT_TRACK_RECORD_DTYPE."""
+        frames, pr = self._frames(frames), self._present(present)
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(self.n)
+        support = np.ascontiguousarray(support, dtype=SUPPORT_DTYPE).reshape(self.n)
+        rec = np.zeros(self.n, self._record_dtype)
+        self._call("step_poses", self._h, vp(frames), self.w, self.h, vp(pr), vp(poses), vp(support), _lib.ref(fit_params), vp(rec))
+        return rec
+
+    def step(self, hp, frames, present=None, radius: int = SUPPORT_RADIUS, fit_params=None):
+        """The whole step: `hp` (a HoughPrediction) predicts every camera's pose and support without guesses, then the core
+        step, on one stream.  -> (POSE_DTYPE [n], SUPPORT_DTYPE [n], the records [n], FIT_TRACK_RECORD_DTYPE or
+        SUBJECT_TRACK_RECORD_DTYPE)."""
+        frames, pr = self._frames(frames), self._present(present)
+        poses, support = np.zeros(self.n, POSE_DTYPE), np.zeros(self.n, SUPPORT_DTYPE)
+        rec = np.zeros(self.n, self._record_dtype)
+        self._call("step", hp._ph, self._h, vp(frames), self.w, self.h, vp(pr), C.c_uint32(int(radius) & 0xFFFFFFFF),
+                   _lib.ref(fit_params), vp(poses), vp(support), vp(rec))
+        return poses, support, rec
+
+    def step_device(self, frames_ptr: int, poses_ptr: int, support_ptr: int, records_ptr: int, hp=None, present_ptr: int = 0,
+                    radius: int = SUPPORT_RADIUS, fit_params=None, stream: int = 0) -> None:
+        """Device frames [n][h][w] u16, poses [n] dh_pose, support [n] dh_support, records [n] dh_fit_track_record (of a
+        SubjectFitTracker: dh_subject_track_record), present [n] u8 or 0.  With `hp` the whole step (poses and support are
+        outputs), without it the core step (they are inputs).  Asynchronous on `stream`: three launches (of a SubjectFitTracker:
+        five) after the prediction's; allocates nothing and never waits on the host."""
+        prm, present, stream = _lib.ref(fit_params), vp(present_ptr or None), C.c_void_p(int(stream))
+        if hp is None:
+            self._call("step_poses_device", self._h, vp(frames_ptr), self.w, self.h, present, vp(poses_ptr), vp(support_ptr), prm,
+                       vp(records_ptr), stream)
+        else:
+            self._call("step_device", hp._ph, self._h, vp(frames_ptr), self.w, self.h, present, C.c_uint32(int(radius) & 0xFFFFFFFF), prm,
+                       vp(poses_ptr), vp(support_ptr), vp(records_ptr), stream)
+
+    def reset(self, camera: int | None = None, stream: int = 0) -> None:
+        """One camera or all back to the initial state (nothing tracked, and of a SubjectFitTracker nobody bound); stream-ordered."""
+        self._reset(camera, stream)
+
+    def state(self) -> np.ndarray:
+        """Synchronous copy of the state: FIT_TRACK_STATE_DTYPE [n], of a SubjectFitTracker SUBJECT_TRACK_STATE_DTYPE [n]."""
+        return self._state(self.n)
+
+
+class FitTracker(_CameraFitTracker):
     """One dh_fit_tracker: each camera of `cameras` (a `tracking.Cameras`) carries its fitted head pose from
     step to step.  A step fits `model` to every present camera's frame -- from the carried pose, or from the forest's where
     there is none -- and decides whether the fit is believed; a rejected fit sends the camera back to the forest.  The state
     stays on the device.  Steps of one tracker must be stream-ordered; the camera table and the model must outlive it."""
     _handles = (("_h", "dh_fit_tracker_destroy"),)
+    _prefix, _record_dtype, _state_dtype = "dh_fit_tracker", FIT_TRACK_RECORD_DTYPE, FIT_TRACK_STATE_DTYPE
 
     def __init__(self, cameras, model: Model, w: int, h: int, scale: float = 1.0, motion: bool = False, params=None):
-        self._lib = _lib.load()
-        self.cameras, self.model, self.w, self.h, self.n = cameras, model, int(w), int(h), len(cameras)
-        self.flags = FIT_TRACK_MOTION if motion else 0
-        self._h = C.c_void_p()
-        check(self._lib.dh_fit_tracker_create(cameras._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
-                                              _lib.ref(params), C.byref(self._h)))
-
-    def step_poses(self, frames, poses, support, present=None, fit_params=None) -> np.ndarray:
-        """The core step from the forest's POSE_DTYPE [n] and SUPPORT_DTYPE [n] of host frames [n, h, w] u16:
-        -> FIT_TRACK_RECORD_DTYPE [n]."""
-        frames, pr = self._frames(frames), self._present(present)
-        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(self.n)
-        support = np.ascontiguousarray(support, dtype=SUPPORT_DTYPE).reshape(self.n)
-        rec = np.zeros(self.n, FIT_TRACK_RECORD_DTYPE)
-        check(self._lib.dh_fit_tracker_step_poses(self._h, vp(frames), self.w, self.h, vp(pr), vp(poses), vp(support),
-                                                  _lib.ref(fit_params), vp(rec)))
-        return rec
-
-    def step(self, hp, frames, present=None, radius: int = SUPPORT_RADIUS, fit_params=None):
-        """The whole step: `hp` (a HoughPrediction) predicts every camera's pose and support without guesses, then the core
-        step, on one stream.  -> (POSE_DTYPE [n], SUPPORT_DTYPE [n], FIT_TRACK_RECORD_DTYPE [n])."""
-        frames, pr = self._frames(frames), self._present(present)
-        poses, support = np.zeros(self.n, POSE_DTYPE), np.zeros(self.n, SUPPORT_DTYPE)
-        rec = np.zeros(self.n, FIT_TRACK_RECORD_DTYPE)
-        check(self._lib.dh_fit_tracker_step(hp._ph, self._h, vp(frames), self.w, self.h, vp(pr), C.c_uint32(int(radius) & 0xFFFFFFFF),
-                                            _lib.ref(fit_params), vp(poses), vp(support), vp(rec)))
-        return poses, support, rec
-
-    def step_device(self, frames_ptr: int, poses_ptr: int, support_ptr: int, records_ptr: int, hp=None, present_ptr: int = 0,
-                    radius: int = SUPPORT_RADIUS, fit_params=None, stream: int = 0) -> None:
-        """Device frames [n][h][w] u16, poses [n] dh_pose, support [n] dh_support, records [n] dh_fit_track_record, present [n]
-        u8 or 0.  With `hp` the whole step (poses and support are outputs), without it the core step (they are inputs).
-        Asynchronous on `stream`; allocates nothing and never waits on the host."""
-        prm = _lib.ref(fit_params)
-        if hp is None:
-            check(self._lib.dh_fit_tracker_step_poses_device(self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None), vp(poses_ptr),
-                                                             vp(support_ptr), prm, vp(records_ptr), C.c_void_p(int(stream))))
-        else:
-            check(self._lib.dh_fit_tracker_step_device(hp._ph, self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
-                                                       C.c_uint32(int(radius) & 0xFFFFFFFF), prm, vp(poses_ptr), vp(support_ptr),
-                                                       vp(records_ptr), C.c_void_p(int(stream))))
-
-    def reset(self, camera: int | None = None, stream: int = 0) -> None:
-        """One camera or all back to the initial state (nothing tracked); stream-ordered."""
-        check(self._lib.dh_fit_tracker_reset(self._h, C.c_int(-1 if camera is None else int(camera)), C.c_void_p(int(stream))))
-
-    def state(self) -> np.ndarray:
-        """Synchronous copy of the state: FIT_TRACK_STATE_DTYPE [n]."""
-        st = np.zeros(self.n, FIT_TRACK_STATE_DTYPE)
-        check(self._lib.dh_fit_tracker_state(self._h, vp(st)))
-        return st
+        self._open(model, w, h, motion, len(cameras))
+        self.cameras = cameras
+        self._call("create", cameras._h, model._h, C.c_float(scale), C.c_uint32(self.flags), _lib.ref(params), C.byref(self._h))
 
     @staticmethod
     def angles() -> np.ndarray:
         return angles()
 
 
-def rig_fit_track_params(iterations_tracked=None, keep_points=None, rms_max=None, max_jump=None, max_coast=None,
-                         max_misses=None) -> "_lib.RigFitTrackParams":
-    """dh_rig_fit_track_params_default with the given fields replaced; `max_misses` is the rig tracker's, which the ids come from."""
-    return _params(_lib.RigFitTrackParams, "dh_rig_fit_track_params_default", iterations_tracked=iterations_tracked, keep_points=keep_points,
-                   rms_max=rms_max, max_jump=max_jump, max_coast=max_coast, max_misses=max_misses)
-
-
-class RigFitTracker(_StepInputs, _lib._Handle):
-    """One dh_rig_fit_tracker (DESIGN.md section 22): every person of every rig of `rig` (a `tracking.Rig`) keeps one fitted pose in
-    the world frame under the id a `tracking.RigTracker` gave it.  A step refits `model` against all the views (`views`, a `Views`
-    of the rig's camera table, consistent with the rig: `views_from_rig`) from the carried pose, or from the person record where
-    there is none, and decides whether the fit is believed.  The state stays on the device.  Steps of one tracker must be
-    stream-ordered; the tables and the model must outlive it."""
-    _handles = (("_h", "dh_rig_fit_tracker_destroy"),)
-
-    def __init__(self, rig, views: Views, model: Model, w: int, h: int, scale: float = 1.0, motion: bool = False, params=None):
-        self._lib = _lib.load()
-        self.rig, self.views, self.model, self.w, self.h = rig, views, model, int(w), int(h)
-        self.n, self.n_rigs = rig.n, rig.n_rigs
-        self.flags = FIT_TRACK_MOTION if motion else 0
-        self._h = C.c_void_p()
-        check(self._lib.dh_rig_fit_tracker_create(rig._h, views._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
-                                                  _lib.ref(params), C.byref(self._h)))
-
-    def step_persons(self, frames, n_heads, heads, n_persons, persons, present=None, fit_params=None) -> np.ndarray:
-        """The core step from the outputs of a rig tracker step -- n_heads u32 [n_cams], HEAD_DTYPE [n_cams, max_heads], n_persons
-        u32 [n_rigs], RIG_PERSON_DTYPE [n_rigs, RIG_MAX_PERSONS] -- and host frames [n_cams, h, w] u16:
-        -> RIG_FIT_RECORD_DTYPE [n_rigs, RIG_MAX_TRACKS]."""
-        frames, pr = self._frames(frames), self._present(present)
-        heads = np.ascontiguousarray(heads, dtype=HEAD_DTYPE)
-        if heads.ndim != 2 or heads.shape[0] != self.n:
-            raise ValueError(f"heads must be [{self.n}, max_heads]")
-        n_heads = np.ascontiguousarray(n_heads, dtype=np.uint32).reshape(self.n)
-        n_persons = np.ascontiguousarray(n_persons, dtype=np.uint32).reshape(self.n_rigs)
-        persons = np.ascontiguousarray(persons, dtype=RIG_PERSON_DTYPE).reshape(self.n_rigs, RIG_MAX_PERSONS)
-        rec = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_FIT_RECORD_DTYPE)
-        check(self._lib.dh_rig_fit_tracker_step_persons(self._h, vp(frames), self.w, self.h, vp(pr), C.c_int(heads.shape[1]), vp(n_heads),
-                                                        vp(heads), vp(n_persons), vp(persons),
-                                                        _lib.ref(fit_params), vp(rec)))
-        return rec
-
-    def step(self, rig_tracker, frames, present=None, tracks: bool = True, fit_params=None):
-        """The whole step: `rig_tracker` (a `tracking.RigTracker` of the same rig table) steps on the frames, then the core
-        step, on one stream.  -> (what RigTracker.step returns: n_heads, heads, rig_ids, n_persons, persons, tracks or None;
-        RIG_FIT_RECORD_DTYPE [n_rigs, RIG_MAX_TRACKS])."""
-        frames, pr = self._frames(frames), self._present(present)
-        mh = rig_tracker.max_heads
-        n_heads, heads = np.zeros(self.n, np.uint32), np.zeros((self.n, mh), HEAD_DTYPE)
-        ids = np.zeros((self.n, mh), np.uint32)
-        n_persons, persons = np.zeros(self.n_rigs, np.uint32), np.zeros((self.n_rigs, RIG_MAX_PERSONS), RIG_PERSON_DTYPE)
-        tr = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_TRACK_DTYPE) if tracks else None
-        rec = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_FIT_RECORD_DTYPE)
-        check(self._lib.dh_rig_fit_tracker_step(rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames), self.w, self.h, vp(pr),
-                                                _lib.ref(fit_params), vp(n_heads), vp(heads), vp(ids),
-                                                vp(n_persons), vp(persons), vp(tr), vp(rec)))
-        return (n_heads, heads, ids, n_persons, persons, tr), rec
-
-    def step_device(self, frames_ptr: int, n_heads_ptr: int, heads_ptr: int, n_persons_ptr: int, persons_ptr: int, records_ptr: int,
-                    max_heads: int = MAX_HEADS, rig_tracker=None, ids_ptr: int = 0, tracks_ptr: int = 0, present_ptr: int = 0,
-                    fit_params=None, stream: int = 0) -> None:
-        """Device frames [n_cams][h][w] u16, n_heads [n_cams] u32, heads [n_cams][max_heads] dh_head, n_persons [n_rigs] u32,
-        persons [n_rigs][RIG_MAX_PERSONS] dh_rig_person, records [n_rigs][RIG_MAX_TRACKS] dh_rig_fit_record, present [n_cams] u8
-        or 0.  With `rig_tracker` the whole step (heads and persons are outputs, as are rig_ids [n_cams][max_heads] u32 and, unless
-        0, tracks; max_heads is the rig tracker's), without it the core step (they are inputs).  Asynchronous on `stream`;
-        allocates nothing and never waits on the host."""
-        prm = _lib.ref(fit_params)
-        if rig_tracker is None:
-            check(self._lib.dh_rig_fit_tracker_step_persons_device(self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
-                                                                   C.c_int(int(max_heads)), vp(n_heads_ptr), vp(heads_ptr), vp(n_persons_ptr),
-                                                                   vp(persons_ptr), prm, vp(records_ptr), C.c_void_p(int(stream))))
-        else:
-            check(self._lib.dh_rig_fit_tracker_step_device(rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames_ptr), self.w, self.h,
-                                                           vp(present_ptr or None), prm, vp(n_heads_ptr), vp(heads_ptr), vp(ids_ptr or None),
-                                                           vp(n_persons_ptr), vp(persons_ptr), vp(tracks_ptr or None), vp(records_ptr),
-                                                           C.c_void_p(int(stream))))
-
-    def reset(self, rig: int | None = None, stream: int = 0) -> None:
-        """One rig or all back to the initial state (every entry free); stream-ordered."""
-        check(self._lib.dh_rig_fit_tracker_reset(self._h, C.c_int(-1 if rig is None else int(rig)), C.c_void_p(int(stream))))
-
-    def state(self) -> np.ndarray:
-        """Synchronous copy of the state: RIG_FIT_STATE_DTYPE [n_rigs, RIG_MAX_TRACKS]."""
-        st = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_FIT_STATE_DTYPE)
-        check(self._lib.dh_rig_fit_tracker_state(self._h, vp(st)))
-        return st
-
-
-def subject_track_params(retry=None, max_tries=None) -> "_lib.SubjectTrackParams":
-    """dh_subject_track_params_default with the given fields replaced."""
-    return _params(_lib.SubjectTrackParams, "dh_subject_track_params_default", retry=retry, max_tries=max_tries)
-
-
-class SubjectFitTracker(_StepInputs, _lib._Handle):
+class SubjectFitTracker(_SubjectBound, _CameraFitTracker):
     """One dh_subject_fit_tracker: a `FitTracker` bound to a `Subjects` set.  A track that starts is
     followed with `model` (the generic head), identified against the set's enrolled subjects on the device, and from the next
     step on followed with its own subject's model as the set holds it.  `enrolled` [S] (None: all) says which subjects are
@@ -1080,110 +1038,37 @@ class SubjectFitTracker(_StepInputs, _lib._Handle):
     tracker must be stream-ordered with one another and with the set's updates; the camera table, the set and the model must
     outlive it."""
     _handles = (("_h", "dh_subject_fit_tracker_destroy"),)
+    _prefix, _record_dtype, _state_dtype = "dh_subject_fit_tracker", _lib.SUBJECT_TRACK_RECORD_DTYPE, _lib.SUBJECT_TRACK_STATE_DTYPE
 
     def __init__(self, cameras, subjects: Subjects, model: Model, w: int, h: int, scale: float = 1.0, motion: bool = False, params=None,
                  ident_params=None, subject_params=None, enrolled=None):
-        self._lib = _lib.load()
-        self.cameras, self.subjects, self.model, self.w, self.h, self.n = cameras, subjects, model, int(w), int(h), len(cameras)
-        self.flags = FIT_TRACK_MOTION if motion else 0
-        self._h = C.c_void_p()
-        check(self._lib.dh_subject_fit_tracker_create(cameras._h, subjects._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
-                                                      _lib.ref(params), _lib.ref(ident_params), _lib.ref(subject_params),
-                                                      vp(self._mask(enrolled)), C.byref(self._h)))
-
-    def _mask(self, enrolled):
-        return None if enrolled is None else np.ascontiguousarray(enrolled, dtype=np.uint8).reshape(len(self.subjects))
-
-    def step_poses(self, frames, poses, support, present=None, fit_params=None) -> np.ndarray:
-        """The core step from the forest's POSE_DTYPE [n] and SUPPORT_DTYPE [n] of host frames [n, h, w] u16:
-        -> SUBJECT_TRACK_RECORD_DTYPE [n]."""
-        frames, pr = self._frames(frames), self._present(present)
-        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(self.n)
-        support = np.ascontiguousarray(support, dtype=SUPPORT_DTYPE).reshape(self.n)
-        rec = np.zeros(self.n, _lib.SUBJECT_TRACK_RECORD_DTYPE)
-        check(self._lib.dh_subject_fit_tracker_step_poses(self._h, vp(frames), self.w, self.h, vp(pr), vp(poses), vp(support),
-                                                          _lib.ref(fit_params), vp(rec)))
-        return rec
-
-    def step(self, hp, frames, present=None, radius: int = SUPPORT_RADIUS, fit_params=None):
-        """The whole step: `hp` (a HoughPrediction) predicts every camera's pose and support without guesses, then the core
-        step, on one stream.  -> (POSE_DTYPE [n], SUPPORT_DTYPE [n], SUBJECT_TRACK_RECORD_DTYPE [n])."""
-        frames, pr = self._frames(frames), self._present(present)
-        poses, support = np.zeros(self.n, POSE_DTYPE), np.zeros(self.n, SUPPORT_DTYPE)
-        rec = np.zeros(self.n, _lib.SUBJECT_TRACK_RECORD_DTYPE)
-        check(self._lib.dh_subject_fit_tracker_step(hp._ph, self._h, vp(frames), self.w, self.h, vp(pr), C.c_uint32(int(radius) & 0xFFFFFFFF),
-                                                    _lib.ref(fit_params), vp(poses), vp(support), vp(rec)))
-        return poses, support, rec
-
-    def step_device(self, frames_ptr: int, poses_ptr: int, support_ptr: int, records_ptr: int, hp=None, present_ptr: int = 0,
-                    radius: int = SUPPORT_RADIUS, fit_params=None, stream: int = 0) -> None:
-        """`FitTracker.step_device` with records [n] of dh_subject_track_record: five launches on `stream`, no allocation and no
-        host wait."""
-        prm = _lib.ref(fit_params)
-        if hp is None:
-            check(self._lib.dh_subject_fit_tracker_step_poses_device(self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
-                                                                     vp(poses_ptr), vp(support_ptr), prm, vp(records_ptr),
-                                                                     C.c_void_p(int(stream))))
-        else:
-            check(self._lib.dh_subject_fit_tracker_step_device(hp._ph, self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
-                                                               C.c_uint32(int(radius) & 0xFFFFFFFF), prm, vp(poses_ptr), vp(support_ptr),
-                                                               vp(records_ptr), C.c_void_p(int(stream))))
-
-    def reset(self, camera: int | None = None, stream: int = 0) -> None:
-        """One camera or all back to the initial state (nothing tracked, nobody bound); stream-ordered."""
-        check(self._lib.dh_subject_fit_tracker_reset(self._h, C.c_int(-1 if camera is None else int(camera)), C.c_void_p(int(stream))))
-
-    def state(self) -> np.ndarray:
-        """Synchronous copy of the state: SUBJECT_TRACK_STATE_DTYPE [n]."""
-        st = np.zeros(self.n, _lib.SUBJECT_TRACK_STATE_DTYPE)
-        check(self._lib.dh_subject_fit_tracker_state(self._h, vp(st)))
-        return st
-
-    def info(self):
-        """(cameras, S, the workgroups of the score kernel's grid)."""
-        n, s, g = C.c_int(), C.c_uint32(), C.c_uint32()
-        check(self._lib.dh_subject_fit_tracker_info(self._h, C.byref(n), C.byref(s), C.byref(g)))
-        return n.value, s.value, g.value
+        self._open(model, w, h, motion, len(cameras))
+        self.cameras, self.subjects = cameras, subjects
+        self._call("create", cameras._h, subjects._h, model._h, C.c_float(scale), C.c_uint32(self.flags), _lib.ref(params),
+                   _lib.ref(ident_params), _lib.ref(subject_params), vp(self._mask(enrolled)), C.byref(self._h))
 
     def bind(self, camera: int, subject: int | None, stream: int = 0) -> None:
         """The caller's own binding of `camera` to `subject`; None unbinds.  Stream-ordered."""
-        check(self._lib.dh_subject_fit_tracker_bind(self._h, C.c_int(int(camera)), C.c_uint32(IDENT_UNKNOWN if subject is None else int(subject)),
-                                                    C.c_void_p(int(stream))))
-
-    def set_enrolled(self, enrolled, stream: int = 0) -> None:
-        """Replace the candidates' mask ([S], None: all); stream-ordered."""
-        check(self._lib.dh_subject_fit_tracker_set_enrolled(self._h, vp(self._mask(enrolled)), C.c_void_p(int(stream))))
+        self._call("bind", self._h, C.c_int(int(camera)), C.c_uint32(IDENT_UNKNOWN if subject is None else int(subject)),
+                   C.c_void_p(int(stream)))
 
 
-class RigSubjectFitTracker(_StepInputs, _lib._Handle):
-    """One dh_rig_subject_fit_tracker (DESIGN.md section 30): a `RigFitTracker` bound to a `Subjects` set.  An entry that starts is
-    followed with `model` (the generic head), identified over all its present views against the set's enrolled subjects on the
-    device, and from the next step on fitted with its own subject's model as the set holds it.  `enrolled` [S] (None: all) says
-    which subjects are candidates.  The state stays on the device; a step never waits on the host.  Steps, resets, binds and mask
-    changes of one tracker must be stream-ordered with one another and with the set's updates; the tables, the set and the model
-    must outlive it."""
-    _handles = (("_h", "dh_rig_subject_fit_tracker_destroy"),)
+class _RigFitTracker(_FitTrackerBase):
+    """The steps of the rig pair over self.n_rigs rigs of self.n cameras in all.  Records: RIG_FIT_RECORD_DTYPE [n_rigs,
+    RIG_MAX_TRACKS] of a RigFitTracker, RIG_SUBJECT_RECORD_DTYPE [n_rigs, RIG_MAX_TRACKS] of a RigSubjectFitTracker
+    (dh_rig_fit_record, dh_rig_subject_record on the device)."""
 
-    def __init__(self, rig, views: Views, subjects: Subjects, model: Model, w: int, h: int, scale: float = 1.0, motion: bool = False,
-                 params=None, ident_params=None, subject_params=None, enrolled=None):
-        self._lib = _lib.load()
-        self.rig, self.views, self.subjects, self.model, self.w, self.h = rig, views, subjects, model, int(w), int(h)
-        self.n, self.n_rigs = rig.n, rig.n_rigs
-        self.flags = FIT_TRACK_MOTION if motion else 0
-        self._h = C.c_void_p()
-        check(self._lib.dh_rig_subject_fit_tracker_create(rig._h, views._h, subjects._h, model._h, C.c_float(scale), C.c_uint32(self.flags),
-                                                          _lib.ref(params), _lib.ref(ident_params), _lib.ref(subject_params),
-                                                          vp(self._mask(enrolled)), C.byref(self._h)))
-
-    def _mask(self, enrolled):
-        return None if enrolled is None else np.ascontiguousarray(enrolled, dtype=np.uint8).reshape(len(self.subjects))
+    def _open_rig(self, rig, views: Views, model: Model, w: int, h: int, motion: bool) -> None:
+        self._open(model, w, h, motion, rig.n)
+        self.rig, self.views, self.n_rigs = rig, views, rig.n_rigs
 
     def _records(self) -> np.ndarray:
-        return np.zeros((self.n_rigs, RIG_MAX_TRACKS), _lib.RIG_SUBJECT_RECORD_DTYPE)
+        return np.zeros((self.n_rigs, RIG_MAX_TRACKS), self._record_dtype)
 
     def step_persons(self, frames, n_heads, heads, n_persons, persons, present=None, fit_params=None) -> np.ndarray:
-        """The core step from the outputs of a rig tracker step (as `RigFitTracker.step_persons`) and host frames [n_cams, h, w] u16:
-        -> RIG_SUBJECT_RECORD_DTYPE [n_rigs, RIG_MAX_TRACKS]."""
+        """The core step from the outputs of a rig tracker step -- n_heads u32 [n_cams], HEAD_DTYPE [n_cams, max_heads], n_persons
+        u32 [n_rigs], RIG_PERSON_DTYPE [n_rigs, RIG_MAX_PERSONS] -- and host frames [n_cams, h, w] u16 (present: u8 [n_cams] or
+        None): -> the records [n_rigs, RIG_MAX_TRACKS], RIG_FIT_RECORD_DTYPE or RIG_SUBJECT_RECORD_DTYPE."""
         frames, pr = self._frames(frames), self._present(present)
         heads = np.ascontiguousarray(heads, dtype=HEAD_DTYPE)
         if heads.ndim != 2 or heads.shape[0] != self.n:
@@ -1192,15 +1077,14 @@ class RigSubjectFitTracker(_StepInputs, _lib._Handle):
         n_persons = np.ascontiguousarray(n_persons, dtype=np.uint32).reshape(self.n_rigs)
         persons = np.ascontiguousarray(persons, dtype=RIG_PERSON_DTYPE).reshape(self.n_rigs, RIG_MAX_PERSONS)
         rec = self._records()
-        check(self._lib.dh_rig_subject_fit_tracker_step_persons(self._h, vp(frames), self.w, self.h, vp(pr), C.c_int(heads.shape[1]),
-                                                                vp(n_heads), vp(heads), vp(n_persons), vp(persons), _lib.ref(fit_params),
-                                                                vp(rec)))
+        self._call("step_persons", self._h, vp(frames), self.w, self.h, vp(pr), C.c_int(heads.shape[1]), vp(n_heads), vp(heads),
+                   vp(n_persons), vp(persons), _lib.ref(fit_params), vp(rec))
         return rec
 
     def step(self, rig_tracker, frames, present=None, tracks: bool = True, fit_params=None):
-        """The whole step: `rig_tracker` (a `tracking.RigTracker` of the same rig table) steps on the frames, then the core step, on
-        one stream.  -> (what RigTracker.step returns: n_heads, heads, rig_ids, n_persons, persons, tracks or None;
-        RIG_SUBJECT_RECORD_DTYPE [n_rigs, RIG_MAX_TRACKS])."""
+        """The whole step: `rig_tracker` (a `tracking.RigTracker` of the same rig table) steps on the frames, then the core
+        step, on one stream.  -> (what RigTracker.step returns: n_heads, heads, rig_ids, n_persons, persons, tracks or None;
+        the records [n_rigs, RIG_MAX_TRACKS], RIG_FIT_RECORD_DTYPE or RIG_SUBJECT_RECORD_DTYPE)."""
         frames, pr = self._frames(frames), self._present(present)
         mh = rig_tracker.max_heads
         n_heads, heads = np.zeros(self.n, np.uint32), np.zeros((self.n, mh), HEAD_DTYPE)
@@ -1208,50 +1092,71 @@ class RigSubjectFitTracker(_StepInputs, _lib._Handle):
         n_persons, persons = np.zeros(self.n_rigs, np.uint32), np.zeros((self.n_rigs, RIG_MAX_PERSONS), RIG_PERSON_DTYPE)
         tr = np.zeros((self.n_rigs, RIG_MAX_TRACKS), RIG_TRACK_DTYPE) if tracks else None
         rec = self._records()
-        check(self._lib.dh_rig_subject_fit_tracker_step(rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames), self.w, self.h, vp(pr),
-                                                        _lib.ref(fit_params), vp(n_heads), vp(heads), vp(ids), vp(n_persons), vp(persons),
-                                                        vp(tr), vp(rec)))
+        self._call("step", rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames), self.w, self.h, vp(pr), _lib.ref(fit_params),
+                   vp(n_heads), vp(heads), vp(ids), vp(n_persons), vp(persons), vp(tr), vp(rec))
         return (n_heads, heads, ids, n_persons, persons, tr), rec
 
     def step_device(self, frames_ptr: int, n_heads_ptr: int, heads_ptr: int, n_persons_ptr: int, persons_ptr: int, records_ptr: int,
                     max_heads: int = MAX_HEADS, rig_tracker=None, ids_ptr: int = 0, tracks_ptr: int = 0, present_ptr: int = 0,
                     fit_params=None, stream: int = 0) -> None:
-        """`RigFitTracker.step_device` with records [n_rigs][RIG_MAX_TRACKS] of dh_rig_subject_record: five launches on `stream`
-        (after the rig tracker's, with `rig_tracker`), no allocation and no host wait."""
-        prm = _lib.ref(fit_params)
+        """Device frames [n_cams][h][w] u16, n_heads [n_cams] u32, heads [n_cams][max_heads] dh_head, n_persons [n_rigs] u32,
+        persons [n_rigs][RIG_MAX_PERSONS] dh_rig_person, records [n_rigs][RIG_MAX_TRACKS] dh_rig_fit_record (of a
+        RigSubjectFitTracker: dh_rig_subject_record), present [n_cams] u8 or 0.  With `rig_tracker` the whole step (heads and
+        persons are outputs, as are rig_ids [n_cams][max_heads] u32 and, unless 0, tracks; max_heads is the rig tracker's),
+        without it the core step (they are inputs).  Asynchronous on `stream`: three launches (of a RigSubjectFitTracker: five)
+        after the rig tracker's; allocates nothing and never waits on the host."""
+        prm, present, stream = _lib.ref(fit_params), vp(present_ptr or None), C.c_void_p(int(stream))
         if rig_tracker is None:
-            check(self._lib.dh_rig_subject_fit_tracker_step_persons_device(self._h, vp(frames_ptr), self.w, self.h, vp(present_ptr or None),
-                                                                           C.c_int(int(max_heads)), vp(n_heads_ptr), vp(heads_ptr),
-                                                                           vp(n_persons_ptr), vp(persons_ptr), prm, vp(records_ptr),
-                                                                           C.c_void_p(int(stream))))
+            self._call("step_persons_device", self._h, vp(frames_ptr), self.w, self.h, present, C.c_int(int(max_heads)), vp(n_heads_ptr),
+                       vp(heads_ptr), vp(n_persons_ptr), vp(persons_ptr), prm, vp(records_ptr), stream)
         else:
-            check(self._lib.dh_rig_subject_fit_tracker_step_device(rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames_ptr), self.w, self.h,
-                                                                   vp(present_ptr or None), prm, vp(n_heads_ptr), vp(heads_ptr),
-                                                                   vp(ids_ptr or None), vp(n_persons_ptr), vp(persons_ptr),
-                                                                   vp(tracks_ptr or None), vp(records_ptr), C.c_void_p(int(stream))))
+            self._call("step_device", rig_tracker.hp._ph, self._h, rig_tracker._h, vp(frames_ptr), self.w, self.h, present, prm,
+                       vp(n_heads_ptr), vp(heads_ptr), vp(ids_ptr or None), vp(n_persons_ptr), vp(persons_ptr), vp(tracks_ptr or None),
+                       vp(records_ptr), stream)
 
     def reset(self, rig: int | None = None, stream: int = 0) -> None:
-        """One rig or all back to the initial state (every entry free, nobody bound); stream-ordered."""
-        check(self._lib.dh_rig_subject_fit_tracker_reset(self._h, C.c_int(-1 if rig is None else int(rig)), C.c_void_p(int(stream))))
+        """One rig or all back to the initial state (every entry free, and of a RigSubjectFitTracker nobody bound); stream-ordered."""
+        self._reset(rig, stream)
 
     def state(self) -> np.ndarray:
-        """Synchronous copy of the state: RIG_SUBJECT_STATE_DTYPE [n_rigs, RIG_MAX_TRACKS]."""
-        st = np.zeros((self.n_rigs, RIG_MAX_TRACKS), _lib.RIG_SUBJECT_STATE_DTYPE)
-        check(self._lib.dh_rig_subject_fit_tracker_state(self._h, vp(st)))
-        return st
+        """Synchronous copy of the state: RIG_FIT_STATE_DTYPE [n_rigs, RIG_MAX_TRACKS], of a RigSubjectFitTracker
+        RIG_SUBJECT_STATE_DTYPE [n_rigs, RIG_MAX_TRACKS]."""
+        return self._state(self.n_rigs, RIG_MAX_TRACKS)
 
-    def info(self):
-        """(rigs, S, the workgroups of the score kernel's grid)."""
-        n, s, g = C.c_int(), C.c_uint32(), C.c_uint32()
-        check(self._lib.dh_rig_subject_fit_tracker_info(self._h, C.byref(n), C.byref(s), C.byref(g)))
-        return n.value, s.value, g.value
+
+class RigFitTracker(_RigFitTracker):
+    """One dh_rig_fit_tracker (DESIGN.md section 22): every person of every rig of `rig` (a `tracking.Rig`) keeps one fitted pose in
+    the world frame under the id a `tracking.RigTracker` gave it.  A step refits `model` against all the views (`views`, a `Views`
+    of the rig's camera table, consistent with the rig: `views_from_rig`) from the carried pose, or from the person record where
+    there is none, and decides whether the fit is believed.  The state stays on the device.  Steps of one tracker must be
+    stream-ordered; the tables and the model must outlive it."""
+    _handles = (("_h", "dh_rig_fit_tracker_destroy"),)
+    _prefix, _record_dtype, _state_dtype = "dh_rig_fit_tracker", RIG_FIT_RECORD_DTYPE, RIG_FIT_STATE_DTYPE
+
+    def __init__(self, rig, views: Views, model: Model, w: int, h: int, scale: float = 1.0, motion: bool = False, params=None):
+        self._open_rig(rig, views, model, w, h, motion)
+        self._call("create", rig._h, views._h, model._h, C.c_float(scale), C.c_uint32(self.flags), _lib.ref(params), C.byref(self._h))
+
+
+class RigSubjectFitTracker(_SubjectBound, _RigFitTracker):
+    """One dh_rig_subject_fit_tracker (DESIGN.md section 30): a `RigFitTracker` bound to a `Subjects` set.  An entry that starts is
+    followed with `model` (the generic head), identified over all its present views against the set's enrolled subjects on the
+    device, and from the next step on fitted with its own subject's model as the set holds it.  `enrolled` [S] (None: all) says
+    which subjects are candidates.  The state stays on the device; a step never waits on the host.  Steps, resets, binds and mask
+    changes of one tracker must be stream-ordered with one another and with the set's updates; the tables, the set and the model
+    must outlive it."""
+    _handles = (("_h", "dh_rig_subject_fit_tracker_destroy"),)
+    _prefix, _record_dtype, _state_dtype = "dh_rig_subject_fit_tracker", _lib.RIG_SUBJECT_RECORD_DTYPE, _lib.RIG_SUBJECT_STATE_DTYPE
+
+    def __init__(self, rig, views: Views, subjects: Subjects, model: Model, w: int, h: int, scale: float = 1.0, motion: bool = False,
+                 params=None, ident_params=None, subject_params=None, enrolled=None):
+        self._open_rig(rig, views, model, w, h, motion)
+        self.subjects = subjects
+        self._call("create", rig._h, views._h, subjects._h, model._h, C.c_float(scale), C.c_uint32(self.flags), _lib.ref(params),
+                   _lib.ref(ident_params), _lib.ref(subject_params), vp(self._mask(enrolled)), C.byref(self._h))
 
     def bind(self, rig: int, rig_id: int, subject: int | None, stream: int = 0) -> None:
         """The caller's own binding of the entry of `rig` that holds `rig_id` to `subject`; None unbinds; an id nobody holds changes
         nothing.  Stream-ordered."""
-        check(self._lib.dh_rig_subject_fit_tracker_bind(self._h, C.c_int(int(rig)), C.c_uint32(int(rig_id)),
-                                                        C.c_uint32(IDENT_UNKNOWN if subject is None else int(subject)), C.c_void_p(int(stream))))
-
-    def set_enrolled(self, enrolled, stream: int = 0) -> None:
-        """Replace the candidates' mask ([S], None: all); stream-ordered."""
-        check(self._lib.dh_rig_subject_fit_tracker_set_enrolled(self._h, vp(self._mask(enrolled)), C.c_void_p(int(stream))))
+        self._call("bind", self._h, C.c_int(int(rig)), C.c_uint32(int(rig_id)), C.c_uint32(IDENT_UNKNOWN if subject is None else int(subject)),
+                   C.c_void_p(int(stream)))
