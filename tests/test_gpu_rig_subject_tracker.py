@@ -201,7 +201,10 @@ def test_want_counts_of_several_none_and_one_at_the_edges_of_the_update_wave(ang
 @pytest.mark.parametrize("name,points,cams,iterations", [("257", 257, 1, 4), ("lathe31x33", 1025, 2, 1)])
 def test_more_wanted_pairs_than_the_score_grid_has_workgroups(angles, name, points, cams, iterations):
     """Every slot in use wants identification against 64 candidates, and the slots are one more than fill the grid: some workgroup
-    makes a second trip, re-staging its model (257 points) or streaming it (1025 points: above the LDS budget; 2 views, 1 iteration)."""
+    makes a second trip, staged (257 points) or streamed (1025 points: above the LDS budget; 2 views, 1 iteration).  Where the grid
+    is a multiple of 64 -- 512 on an MI355X -- that second trip has the SAME subject as the first and only the instance changes, so
+    this shows a second trip, not a second model: a model staged on the first trip only would pass.  test_gpu_score_trips.py has
+    the trips whose subject changes."""
     import torch
     S = 64
     units = 2 * torch.cuda.get_device_properties(0).multi_processor_count

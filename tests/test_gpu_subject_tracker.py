@@ -125,8 +125,10 @@ def test_want_counts_of_all_none_and_one(angles):
 @pytest.mark.parametrize("name,points", [("257", 257), ("lathe31x33", 1025)])
 def test_more_wanted_pairs_than_the_score_grid_has_workgroups(angles, name, points):
     """Every camera wants identification against 64 candidates, and the cameras are one more than fill the grid: some workgroup
-    makes a second trip, re-staging its model (257 points) or streaming it (1025 points: above the LDS budget).  One set holds
-    models of one size, so the two kinds alternate over the two cases, not within a step."""
+    makes a second trip, staged (257 points) or streamed (1025 points: above the LDS budget).  Where the grid is a multiple of 64
+    -- 512 on an MI355X -- that second trip has the SAME subject as the first and only the instance changes, so this shows a second
+    trip, not a second model: a model staged on the first trip only would pass.  test_gpu_score_trips.py has the trips whose
+    subject changes.  One set holds models of one size, so the two kinds alternate over the two cases, not within a step."""
     import torch
     S = 64
     grid = 2 * torch.cuda.get_device_properties(0).multi_processor_count
