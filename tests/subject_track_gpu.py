@@ -1,15 +1,14 @@
 """What the subject tracker's GPU tests share (test_gpu_subject_tracker.py, test_gpu_tracker_waves.py): a
-tracker on the GPU beside its restated twin over one gallery and camera table, the byte compare of records and state, and the
-device buffers of the _device forms -- uploads and guard bands."""
+tracker on the GPU beside its restated twin over one gallery and camera table, and one step of both compared byte for byte
+(gpu_kit.same_records).  The device buffers of the _device forms -- uploads and guard bands -- are gpu_kit's."""
 import contextlib
-
-import numpy as np
 
 import fit_ref as fr
 import fit_track_ref as ft
 import ident_ref as ir
 import subject_track_ref as stf
 import subject_track_scenes as sts
+from gpu_kit import same_records
 from depthhead_amd import fit, tracking
 
 # The splatted scenes are coarser than a rendered frame (tests/test_subject_track_ref.py): the identification's limit lies between a
@@ -50,35 +49,13 @@ def pair(angles, name, n_subjects, Ks, w, h, enrolled=None, sub=None, track=None
         yield trs if trackers > 1 else trs[0], ref, got, st, cams, model
 
 
-def same(got, want, what):
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert len(got) == len(want) and got.dtype.itemsize == want.dtype.itemsize, what
-    for i in range(len(want)):
-        assert got[i].tobytes() == want[i].tobytes(), (what, i, got[i], want[i])
-
-
 def both(tr, ref, frames, poses, sup, present=None, what="step", fit_kw=None):
     """One step on the GPU (host call) and in the restatement `ref` (anything with the restated tracker's step() and state);
     records and state compared.  fit_kw: the fit's parameters as keywords of fit.fit_params and fit_ref.params, None: the defaults."""
     got = tr.step_poses(frames, poses, sup, present, None if fit_kw is None else fit.fit_params(**fit_kw))
     want = ref.step(frames, poses, sup, present, None if fit_kw is None else fr.params(**fit_kw))
-    same(got, want, f"records of {what}")
-    same(tr.state(), ref.state, f"state after {what}")
+    same_records(got, want, f"records of {what}")
+    same_records(tr.state(), ref.state, f"state after {what}")
     return got
 
 
-def to_dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def guarded(nbytes, skew):
-    """A device buffer of 4 KB guard bands around `nbytes` at a skewed start: (tensor, pointer, offset)."""
-    import torch
-    buf = torch.full((4096 + skew + nbytes + 4096,), 0xA5, dtype=torch.uint8, device="cuda")
-    return buf, buf.data_ptr() + 4096 + skew, 4096 + skew
-
-
-def untouched(buf, off, nbytes):
-    host = buf.cpu().numpy()
-    return (host[:off] == 0xA5).all() and (host[off + nbytes:] == 0xA5).all()

@@ -6,21 +6,20 @@ table two words and a pointer (device, n cameras, its camera table: again two wo
 is decided before the handle's device memory would be used.  The refusals that need a real model (the extent, the term limits)
 are in tests/test_gpu_calibrate.py."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 
+import abi_kit
+from abi_kit import err as _err, Cameras as FakeCameras, Model as FakeModel, Views as FakeViews
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_calib_params_default", "dh_fit_calibrate_views", "dh_fit_calibrate_views_device"]
 EINVAL = -1
 
 
 def test_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     from depthhead_amd import fit
     assert callable(fit.Fitter.calibrate_step) and callable(fit.calibrate_views) and callable(fit.views_from_records)
     assert callable(fit.calib_params)
@@ -28,12 +27,8 @@ def test_entry_points_are_exported(hip_lib):
 
 
 def test_header_and_exports_are_equal():
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert f"int {n}(" in text, n
-    declared = set(re.findall(r"^(?:int|const char \*)\s*(dh_\w+)\(", text, re.M))
-    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
-    assert "calibrating a view table" in text
+    text = abi_kit.header()
+    abi_kit.assert_header_equals_exports(NEW, "calibrating a view table")
     # the two declarations differ in the stream alone
     host = re.search(r"int dh_fit_calibrate_views\((.*?)\);", text, re.S).group(1)
     device = re.search(r"int dh_fit_calibrate_views_device\((.*?)\);", text, re.S).group(1)
@@ -56,7 +51,7 @@ def test_struct_layouts():
     assert [(n, getattr(P, n).offset) for n, _ in P._fields_] == [("gate", 0), ("lam", 8), ("pivot", 16), ("min_points", 40), ("reserved0", 44),
                                                                   ("reserved", 48)]
     # the struct of the header, field for field
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
+    text = abi_kit.header()
     body = re.search(r"typedef struct dh_calib_record \{(.*?)\} dh_calib_record;", text, re.S).group(1)
     fields = re.findall(r"^\s*(\w+)\s+([^;]+);", body, re.M)
     assert [(t, " ".join(n.split())) for t, n in fields] == [("float", "V[9], u[3]"), ("uint32_t", "points"), ("uint32_t", "pairs"), ("uint32_t", "status"),
@@ -76,22 +71,6 @@ def test_defaults(hip_lib):
     from depthhead_amd import fit
     q = fit.calib_params(gate=60.0, lam=0.0, min_points=7, pivot=(1.0, -2.0, 3.5))
     assert (q.gate, q.lam, q.min_points, list(q.pivot)) == (60.0, 0.0, 7, [1.0, -2.0, 3.5])
-
-
-class FakeCameras(C.Structure):
-    _fields_ = [("device", C.c_int), ("n", C.c_int), ("rest", C.c_uint8 * 248)]
-
-
-class FakeViews(C.Structure):
-    _fields_ = [("device", C.c_int), ("n", C.c_int), ("cams", C.c_void_p), ("rest", C.c_uint8 * 240)]
-
-
-class FakeModel(C.Structure):
-    _fields_ = [("device", C.c_int), ("n", C.c_uint32), ("radius", C.c_double), ("rest", C.c_uint8 * 240)]
-
-
-def _err(lib):
-    return lib.dh_last_error().decode()
 
 
 def test_refusals_leave_the_records_untouched(hip_lib):

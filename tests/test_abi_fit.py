@@ -6,16 +6,13 @@ refusals that need a real model (the extent limit, a camera table of another len
 refusals of the header are tested nowhere, because they take two devices: a model and a camera table that live on another
 device than the fitter."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_fit_model_create", "dh_fit_model_destroy", "dh_fit_model_info", "dh_fit_params_default", "dh_fitter_create", "dh_fitter_destroy",
        "dh_fit_depth", "dh_fit_depth_cameras", "dh_fit_depth_device", "dh_fit_depth_cameras_device"]
 EINVAL = -1
@@ -38,8 +35,7 @@ int main() {
 
 
 def test_fit_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     import depthhead_amd
     from depthhead_amd import fit
     for name in ("Fitter", "Model"):
@@ -50,22 +46,12 @@ def test_fit_entry_points_are_exported(hip_lib):
 
 
 def test_header_declares_every_fit_export():
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert f"int {n}(" in text, n
+    abi_kit.assert_header_equals_exports(NEW)
 
 
 def test_layouts_match_the_header(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line and not line.startswith("consts")}
-    consts = [int(v) for v in next(line for line in out if line.startswith("consts")).split()[1:]]
+    c, consts = abi_kit.layouts(tmp_path, LAYOUT_CPP)
+    consts = [int(v) for v in consts]
     assert consts == [0, 1, 2, _lib.FIT_MAX_POINTS, _lib.FIT_MAX_EXTENT] == [0, 1, 2, 32768, 4096]
     dt = _lib.FIT_RECORD_DTYPE
     assert c[("dh_fit_record", "size")] == dt.itemsize == 24
@@ -74,10 +60,6 @@ def test_layouts_match_the_header(tmp_path):
     assert c[("dh_fit_params", "size")] == C.sizeof(_lib.FitParams) == 56
     for f, _ in _lib.FitParams._fields_:
         assert c[("dh_fit_params", "lambda" if f == "lam" else f)] == getattr(_lib.FitParams, f).offset, f
-
-
-def _err(lib):
-    return lib.dh_last_error().decode()
 
 
 def default_params(lib):

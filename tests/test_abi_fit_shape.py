@@ -5,16 +5,13 @@ Models and bases live on a device, so where a refusal only needs a handle that i
 every refusal tested here is decided before the handle's device memory would be used (a model of 0 points on device 0).  The
 refusals that need a real model or basis (another n, the field limit, the term limit) are in tests/test_gpu_fit_shape.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_fit_basis_create", "dh_fit_basis_destroy", "dh_fit_basis_info", "dh_shape_params_default", "dh_fit_shape", "dh_fit_shape_cameras",
        "dh_fit_shape_device", "dh_fit_shape_cameras_device"]
 EINVAL = -1
@@ -38,8 +35,7 @@ int main() {
 
 
 def test_shape_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     import depthhead_amd
     from depthhead_amd import fit, synth
     assert hasattr(depthhead_amd, "ShapeBasis") and "ShapeBasis" in depthhead_amd.__all__
@@ -51,25 +47,12 @@ def test_shape_entry_points_are_exported(hip_lib):
 
 
 def test_header_and_exports_are_equal():
-    import re
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert f"int {n}(" in text, n
-    declared = set(re.findall(r"^(?:int|const char \*)\s*(dh_\w+)\(", text, re.M))
-    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
+    abi_kit.assert_header_equals_exports(NEW)
 
 
 def test_layouts_match_the_header(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line and not line.startswith("consts")}
-    consts = [int(v) for v in next(line for line in out if line.startswith("consts")).split()[1:]]
+    c, consts = abi_kit.layouts(tmp_path, LAYOUT_CPP)
+    consts = [int(v) for v in consts]
     assert consts == [0, 1, 2, _lib.SHAPE_MAX_FIELDS, _lib.SHAPE_MAX_SUBJECTS, _lib.SHAPE_SKIP, _lib.SHAPE_MAX_FIELD, _lib.SHAPE_MAX_GATE,
                       _lib.SHAPE_MAX_TERMS] == [0, 1, 2, 8, 256, 0xFFFFFFFF, 256, 256, 1 << 23]
     dt = _lib.SHAPE_RECORD_DTYPE
@@ -79,10 +62,6 @@ def test_layouts_match_the_header(tmp_path):
     assert c[("dh_shape_params", "size")] == C.sizeof(_lib.ShapeParams) == 40
     for f, _ in _lib.ShapeParams._fields_:
         assert c[("dh_shape_params", "lambda" if f == "lam" else f)] == getattr(_lib.ShapeParams, f).offset, f
-
-
-def _err(lib):
-    return lib.dh_last_error().decode()
 
 
 def default_params(lib):

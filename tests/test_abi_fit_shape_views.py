@@ -6,48 +6,31 @@ its camera table: again two words, device and n) -- every refusal tested here is
 be used.  The refusals that need a real model or basis (the extent, the field limit, the term limits) are in
 tests/test_gpu_fit_shape_views.py."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 
+import abi_kit
+from abi_kit import err as _err, Cameras as FakeCameras, Views as FakeViews
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_fit_shape_views", "dh_fit_shape_views_device"]
 EINVAL = -1
 
 
 def test_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     from depthhead_amd import fit
     assert callable(fit.Fitter.shape_step_views) and callable(fit.adapt_views)
 
 
 def test_header_and_exports_are_equal():
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert f"int {n}(" in text, n
-    declared = set(re.findall(r"^(?:int|const char \*)\s*(dh_\w+)\(", text, re.M))
-    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
-    assert "adapting a model's shape across views" in text and "COUNTS PAIRS" in text
+    text = abi_kit.header()
+    abi_kit.assert_header_equals_exports(NEW, "adapting a model's shape across views", "COUNTS PAIRS")
     # the two declarations differ in the stream alone
     host = re.search(r"int dh_fit_shape_views\((.*?)\);", text, re.S).group(1)
     device = re.search(r"int dh_fit_shape_views_device\((.*?)\);", text, re.S).group(1)
     assert " ".join(device.split()) == " ".join(host.split()) + ", void *stream"
-
-
-class FakeCameras(C.Structure):
-    _fields_ = [("device", C.c_int), ("n", C.c_int), ("rest", C.c_uint8 * 248)]
-
-
-class FakeViews(C.Structure):
-    _fields_ = [("device", C.c_int), ("n", C.c_int), ("cams", C.c_void_p), ("rest", C.c_uint8 * 240)]
-
-
-def _err(lib):
-    return lib.dh_last_error().decode()
 
 
 def test_refusals_leave_the_records_untouched(hip_lib):

@@ -6,16 +6,13 @@ parameter refusals are decided before the table and the model are looked at, and
 NULL arguments, frame size and dh_fit_params, reset's camera index, a model too large for `scale`) are in
 tests/test_gpu_fit_tracker.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_fit_track_params_default", "dh_fit_tracker_angles", "dh_fit_tracker_create", "dh_fit_tracker_destroy", "dh_fit_tracker_reset",
        "dh_fit_tracker_state", "dh_fit_tracker_step_poses", "dh_fit_tracker_step_poses_device", "dh_fit_tracker_step",
        "dh_fit_tracker_step_device"]
@@ -45,14 +42,10 @@ int main() {
 """
 
 
-def _err(lib):
-    return lib.dh_last_error().decode()
-
-
 def test_fit_tracker_entry_points_are_exported_and_declared(hip_lib):
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n) and f"int {n}(" in text, n
+    text = abi_kit.header()
+    abi_kit.assert_exported(hip_lib, NEW)
+    abi_kit.assert_header_equals_exports(NEW)
     import depthhead_amd
     from depthhead_amd import fit
     assert hasattr(depthhead_amd, "FitTracker") and "FitTracker" in depthhead_amd.__all__
@@ -63,16 +56,8 @@ def test_fit_tracker_entry_points_are_exported_and_declared(hip_lib):
 
 
 def test_layouts_match_the_header(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line and not line.startswith("consts")}
-    consts = [int(v) for v in next(line for line in out if line.startswith("consts")).split()[1:]]
+    c, consts = abi_kit.layouts(tmp_path, LAYOUT_CPP)
+    consts = [int(v) for v in consts]
     from depthhead_amd import fit
     assert consts == [fit.FIT_TRACK_NONE, fit.FIT_TRACK_FITTED, fit.FIT_TRACK_CARRIED, fit.FIT_TRACK_REJECTED, fit.FIT_TRACK_ABSENT,
                       fit.FIT_TRACK_BAD_STATUS, fit.FIT_TRACK_BAD_POINTS, fit.FIT_TRACK_BAD_RMS, fit.FIT_TRACK_BAD_JUMP,

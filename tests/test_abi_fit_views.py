@@ -4,17 +4,14 @@ from include/depthhead_hip.h), the refusals that need no device, and fit.views_f
 table, which lives on a device: every refusal that comes after "NULL view table" in the header's order -- the frame size, the
 params, the per-instance ones, dh_fit_views_create's own -- is in tests/test_gpu_fit_views.py."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib, fit
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_fit_views_create", "dh_fit_views_destroy", "dh_fit_views_info", "dh_fit_depth_views", "dh_fit_depth_views_device"]
 EINVAL = -1
 
@@ -37,8 +34,7 @@ int main() {
 
 
 def test_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     for name in ("Views", "views_from_rig", "view_instances_from_persons"):
         assert callable(getattr(fit, name)), name
     assert callable(fit.Fitter.fit_views)
@@ -46,34 +42,17 @@ def test_entry_points_are_exported(hip_lib):
 
 
 def test_header_and_exports_are_equal():
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert f"int {n}(" in text, n
-    declared = set(re.findall(r"^(?:int|const char \*)\s*(dh_\w+)\(", text, flags=re.M))
-    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
+    abi_kit.assert_header_equals_exports(NEW)
 
 
 def test_layouts_match_the_header(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line and not line.startswith("consts")}
-    consts = next(line for line in out if line.startswith("consts")).split()[1:]
+    c, consts = abi_kit.layouts(tmp_path, LAYOUT_CPP)
     assert float(consts[0]) == _lib.FIT_VIEW_TOLERANCE == 0.001 and int(consts[1]) == _lib.FIT_MAX_POINTS
     for name, dt, size in (("dh_view_instance", _lib.VIEW_INSTANCE_DTYPE, 72), ("dh_view_fit_record", _lib.VIEW_FIT_RECORD_DTYPE, 32)):
         assert c[(name, "size")] == dt.itemsize == size
         for f in dt.names:
             assert c[(name, f)] == dt.fields[f][1], (name, f)
         assert sum(dt.fields[f][0].itemsize for f in dt.names) == size, name          # no padding
-
-
-def _err(lib):
-    return lib.dh_last_error().decode()
 
 
 def test_refusals_that_need_no_device(hip_lib):

@@ -6,26 +6,20 @@ on a device, so the calls get blocks that read as one (dh_api_fit.hip): a view t
 memory is never touched -- every refusal made here comes before the set's models are read.  What needs a real set and a real rig
 is in tests/test_gpu_ident_views.py."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 
+import abi_kit
+from abi_kit import err as _err, Basis as FakeBasis, Cameras as FakeCameras, SubjectSet as FakeSet, Views as FakeViews
 from depthhead_amd import _lib
-import runtime_units
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_fit_ident_views_params_default", "dh_fit_identify_subjects_views", "dh_fit_identify_subjects_views_device"]
 EINVAL = -1
 
 
-def _err(lib):
-    return lib.dh_last_error().decode()
-
-
 def test_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     from depthhead_amd import fit
     for name in ("recognise_subjects_views", "ident_views_params"):
         assert callable(getattr(fit, name)), name
@@ -33,26 +27,13 @@ def test_entry_points_are_exported(hip_lib):
 
 
 def test_header_and_exports_are_equal():
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert f"int {n}(" in text, n
-    declared = set(re.findall(r"^(?:int|const char \*)\s*(dh_\w+)\(", text, re.M))
-    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
-    assert len(_lib.EXPORTS) == len(set(_lib.EXPORTS))
-    assert "identifying enrolled subjects across the views of a rig" in text and "MUST BE STREAM-ORDERED" in text
-    api = runtime_units.text()
-    for n in NEW:
-        assert f"DH_API({n[3:]}," in api, n                                         # through the guard, as every export
+    abi_kit.assert_header_equals_exports(NEW, "identifying enrolled subjects across the views of a rig", "MUST BE STREAM-ORDERED")
 
 
 def test_the_argument_lists():
     """The two declarations differ in the stream alone; the order is dh_fit_shape_views' up to `sets` (the set in place of the model
     and its basis), then section 27's from `enrolled` on, with the view types for the instances, the fit records, poses and scores."""
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-
-    def args(name):
-        return [" ".join(a.split()) for a in re.search(r"int %s\((.*?)\);" % name, text, re.S).group(1).split(",")]
-
+    args = abi_kit.declared_args
     host, device = args("dh_fit_identify_subjects_views"), args("dh_fit_identify_subjects_views_device")
     assert device == host + ["void *stream"]
     shape, ident = args("dh_fit_shape_views"), args("dh_fit_identify_subjects_cameras")
@@ -78,30 +59,13 @@ def test_the_two_defaults(hip_lib):
     assert q.max_rms == _lib.IDENT_DEFAULT_MAX_RMS == 1.68                          # section 27's stays what it was
     q.max_rms = p.max_rms
     assert bytes(p) == bytes(q)                                                     # max_rms is the one difference
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
+    text = abi_kit.header()
     assert float(re.search(r"#define DH_IDENT_VIEWS_DEFAULT_MAX_RMS\s+([0-9.]+)", text).group(1)) == _lib.IDENT_VIEWS_DEFAULT_MAX_RMS
     assert hip_lib.dh_fit_ident_views_params_default(None) == EINVAL and "NULL" in _err(hip_lib)
     from depthhead_amd import fit
     r = fit.ident_views_params(iterations=7, min_points=9, gate=30.0, lam=0.5, min_ratio=1.25)
     assert (r.iterations, r.min_points, r.gate, r.lam, r.max_rms, r.min_ratio) == (7, 9, 30.0, 0.5, _lib.IDENT_VIEWS_DEFAULT_MAX_RMS, 1.25)
     assert fit.ident_views_params(max_rms=np.inf).max_rms == np.inf
-
-
-class FakeCameras(C.Structure):
-    _fields_ = [("device", C.c_int), ("n", C.c_int), ("rest", C.c_uint8 * 248)]
-
-
-class FakeViews(C.Structure):
-    _fields_ = [("device", C.c_int), ("n", C.c_int), ("cams", C.c_void_p), ("rest", C.c_uint8 * 240)]
-
-
-class FakeBasis(C.Structure):
-    _fields_ = [("device", C.c_int), ("n", C.c_uint32), ("k", C.c_uint32), ("pad", C.c_uint32), ("largest", C.c_double), ("rest", C.c_uint8 * 232)]
-
-
-class FakeSet(C.Structure):
-    _fields_ = [("device", C.c_int), ("n", C.c_uint32), ("n_tris", C.c_uint32), ("n_subjects", C.c_uint32), ("max_coeff", C.c_double),
-                ("radius", C.c_double), ("basis", C.c_void_p), ("rest", C.c_uint8 * 472)]
 
 
 def bad_params(reserved=0, **kw):

@@ -2,16 +2,13 @@
 of the Python dtypes equal the C layout (a g++ program prints sizeof and offsetof from include/depthhead_hip.h), and the
 refusals that need no device answer DH_EINVAL with a message."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_multi_tracker_create", "dh_multi_tracker_destroy", "dh_multi_tracker_reset", "dh_multi_tracker_step",
        "dh_multi_tracker_step_device", "dh_multi_tracker_state", "dh_multi_tracker_capture"]
 EINVAL = -1
@@ -36,24 +33,15 @@ int main() {
 
 
 def test_multi_tracker_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     from depthhead_amd import tracking
     for m in ("step", "step_device", "capture", "reset", "state", "close", "__enter__", "__exit__"):
         assert hasattr(tracking.MultiHeadTracker, m), m
 
 
 def test_layouts_match_the_header(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line and not line.startswith("consts")}
-    consts = [int(v) for v in next(line for line in out if line.startswith("consts")).split()[1:]]
+    c, consts = abi_kit.layouts(tmp_path, LAYOUT_CPP)
+    consts = [int(v) for v in consts]
     assert consts == [_lib.MAX_TRACKS, _lib.TRACK_GATE, _lib.TRACK_MAX_MISSES, _lib.MAX_HEADS]
     for name, dt in (("dh_head_track", _lib.TRACK_DTYPE), ("dh_head", _lib.HEAD_DTYPE)):
         assert c[(name, "size")] == dt.itemsize, name
@@ -67,10 +55,6 @@ def test_layouts_match_the_header(tmp_path):
 
 def _params(max_heads=4, radius=30, gate=100, max_misses=3):
     return _lib.MultiTrackParams(max_heads, radius & 0xFFFFFFFF, gate & 0xFFFFFFFF, max_misses)
-
-
-def _err(lib):
-    return lib.dh_last_error().decode()
 
 
 def test_create_refusals(hip_lib):

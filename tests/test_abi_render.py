@@ -2,16 +2,13 @@
 side equal the C layout (a g++ program prints sizeof and offsetof from include/depthhead_hip.h), and every refusal answers
 DH_EINVAL with a message and leaves the output buffers untouched."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_mesh_create", "dh_mesh_destroy", "dh_mesh_info", "dh_renderer_create", "dh_renderer_destroy", "dh_renderer_set_profiling",
        "dh_renderer_timing", "dh_render_depth", "dh_render_depth_cameras", "dh_render_depth_device", "dh_render_depth_cameras_device"]
 EINVAL = -1
@@ -35,8 +32,7 @@ int main() {
 
 
 def test_render_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     import depthhead_amd
     from depthhead_amd import render, synth, training
     for name in ("Mesh", "Renderer", "euler_to_matrix"):
@@ -46,23 +42,12 @@ def test_render_entry_points_are_exported(hip_lib):
 
 
 def test_header_declares_every_render_export():
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert f"int {n}(" in text, n
-    assert "#define DH_VERSION 100" in text
+    abi_kit.assert_header_equals_exports(NEW, "#define DH_VERSION 100")
 
 
 def test_layouts_match_the_header(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line and not line.startswith("consts")}
-    consts = [int(v) for v in next(line for line in out if line.startswith("consts")).split()[1:]]
+    c, consts = abi_kit.layouts(tmp_path, LAYOUT_CPP)
+    consts = [int(v) for v in consts]
     assert consts == [_lib.RENDER_HEAD, _lib.RENDER_MAX_SIZE, 100] == [1, 16384, 100]
     dt = _lib.RENDER_INSTANCE_DTYPE
     assert c[("dh_render_instance", "size")] == dt.itemsize == 64
@@ -72,10 +57,6 @@ def test_layouts_match_the_header(tmp_path):
     assert c[("dh_render_params", "size")] == C.sizeof(_lib.RenderParams) == 40
     for f, _ in _lib.RenderParams._fields_:
         assert c[("dh_render_params", f)] == getattr(_lib.RenderParams, f).offset, f
-
-
-def _err(lib):
-    return lib.dh_last_error().decode()
 
 
 def test_mesh_create_refusals(hip_lib):

@@ -2,16 +2,13 @@
 the Python dtypes equal the C layout (a g++ program prints sizeof and offsetof from include/depthhead_hip.h), and the refusals
 that need no device answer DH_EINVAL with a message."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_rig_create", "dh_rig_destroy", "dh_rig_tracker_create", "dh_rig_tracker_destroy", "dh_rig_tracker_reset",
        "dh_rig_tracker_step", "dh_rig_tracker_step_device", "dh_rig_tracker_state", "dh_rig_tracker_capture"]
 EINVAL = -1
@@ -39,8 +36,7 @@ int main() {
 
 
 def test_rig_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     from depthhead_amd import tracking
     for m in ("step", "step_device", "capture", "reset", "state", "close", "__enter__", "__exit__"):
         assert hasattr(tracking.RigTracker, m), m
@@ -48,22 +44,12 @@ def test_rig_entry_points_are_exported(hip_lib):
 
 
 def test_header_declares_every_rig_export():
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert f"int {n}(" in text, n
+    abi_kit.assert_header_equals_exports(NEW)
 
 
 def test_layouts_match_the_header(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line and not line.startswith("consts")}
-    consts = [int(v) for v in next(line for line in out if line.startswith("consts")).split()[1:]]
+    c, consts = abi_kit.layouts(tmp_path, LAYOUT_CPP)
+    consts = [int(v) for v in consts]
     assert consts == [_lib.RIG_MAX_CAMERAS, _lib.RIG_MAX_PERSONS, _lib.RIG_MAX_TRACKS, _lib.RIG_FUSE_GATE] == [64, 16, 16, 100]
     for name, dt in (("dh_rig_person", _lib.RIG_PERSON_DTYPE), ("dh_rig_track", _lib.RIG_TRACK_DTYPE)):
         assert c[(name, "size")] == dt.itemsize and c[(name, "align")] == 8, name
@@ -78,10 +64,6 @@ def test_layouts_match_the_header(tmp_path):
 
 def _params(max_heads=4, radius=30, fuse_gate=100, gate=100, max_misses=3):
     return _lib.RigTrackParams(max_heads, radius & 0xFFFFFFFF, fuse_gate & 0xFFFFFFFF, gate & 0xFFFFFFFF, max_misses)
-
-
-def _err(lib):
-    return lib.dh_last_error().decode()
 
 
 def test_create_refusals(hip_lib):

@@ -5,17 +5,13 @@ message and leaves its outputs untouched.  The tables and a model need a device,
 parameter refusals are decided before the tables and the model are looked at, and the refusals that need a tracker are in
 tests/test_gpu_rig_fit_tracker.py."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_rig_fit_track_params_default", "dh_rig_fit_tracker_create", "dh_rig_fit_tracker_destroy", "dh_rig_fit_tracker_reset",
        "dh_rig_fit_tracker_state", "dh_rig_fit_tracker_step_persons", "dh_rig_fit_tracker_step_persons_device", "dh_rig_fit_tracker_step",
        "dh_rig_fit_tracker_step_device"]
@@ -43,17 +39,10 @@ int main() {
 """
 
 
-def _err(lib):
-    return lib.dh_last_error().decode()
-
-
 def test_entry_points_are_exported_and_the_header_equals_the_export_list(hip_lib):
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n) and f"int {n}(" in text, n
-    declared = set(re.findall(r"^(?:int|const char \*)\s*(dh_[a-z0-9_]+)\(", text, re.M))
-    assert declared == set(_lib.EXPORTS), (declared ^ set(_lib.EXPORTS))
-    assert len(_lib.EXPORTS) == len(set(_lib.EXPORTS))
+    text = abi_kit.header()
+    abi_kit.assert_exported(hip_lib, NEW)
+    abi_kit.assert_header_equals_exports(NEW)
     import depthhead_amd
     from depthhead_amd import fit
     assert hasattr(depthhead_amd, "RigFitTracker") and "RigFitTracker" in depthhead_amd.__all__
@@ -65,16 +54,8 @@ def test_entry_points_are_exported_and_the_header_equals_the_export_list(hip_lib
 
 
 def test_layouts_match_the_header(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line and not line.startswith("consts")}
-    consts = [int(v) for v in next(line for line in out if line.startswith("consts")).split()[1:]]
+    c, consts = abi_kit.layouts(tmp_path, LAYOUT_CPP)
+    consts = [int(v) for v in consts]
     assert consts == [_lib.RIG_MAX_TRACKS, _lib.RIG_MAX_PERSONS, _lib.TRACK_MAX_MISSES] == [16, 16, 3]
     for name, dt, size in (("dh_rig_fit_state", _lib.RIG_FIT_STATE_DTYPE, 88), ("dh_rig_fit_record", _lib.RIG_FIT_RECORD_DTYPE, 128)):
         assert c[(name, "size")] == dt.itemsize == size

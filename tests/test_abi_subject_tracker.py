@@ -6,16 +6,13 @@ model need a device, so a tracker cannot exist here: the refusals past the NULL 
 the dh_subject_track_params, devices, point counts, extents, pairs) and those that need a tracker are in
 tests/test_gpu_subject_tracker.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_subject_track_params_default", "dh_subject_fit_tracker_create", "dh_subject_fit_tracker_destroy", "dh_subject_fit_tracker_reset",
        "dh_subject_fit_tracker_state", "dh_subject_fit_tracker_info", "dh_subject_fit_tracker_set_enrolled", "dh_subject_fit_tracker_bind",
        "dh_subject_fit_tracker_step_poses", "dh_subject_fit_tracker_step_poses_device", "dh_subject_fit_tracker_step",
@@ -41,14 +38,10 @@ int main() {
 """
 
 
-def _err(lib):
-    return lib.dh_last_error().decode()
-
-
 def test_subject_tracker_entry_points_are_exported_and_declared(hip_lib):
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n) and f"int {n}(" in text, n
+    text = abi_kit.header()
+    abi_kit.assert_exported(hip_lib, NEW)
+    abi_kit.assert_header_equals_exports(NEW)
     import depthhead_amd
     from depthhead_amd import fit
     assert hasattr(depthhead_amd, "SubjectFitTracker") and "SubjectFitTracker" in depthhead_amd.__all__
@@ -61,15 +54,7 @@ def test_subject_tracker_entry_points_are_exported_and_declared(hip_lib):
 
 
 def test_layouts_match_the_header(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line}
+    c, _ = abi_kit.layouts(tmp_path, LAYOUT_CPP)
     import subject_track_ref as stf
     for name, dt, ref, size in (("dh_subject_track_state", _lib.SUBJECT_TRACK_STATE_DTYPE, stf.STATE, 92),
                                 ("dh_subject_track_record", _lib.SUBJECT_TRACK_RECORD_DTYPE, stf.RECORD, 160)):

@@ -6,17 +6,13 @@ zeros (a basis of 0 points on device 0): the basis is the LAST thing the call lo
 with it, and the call ends at "the basis is one of 0 points" before anything is allocated.  The refusals that need a real set are
 in tests/test_gpu_subjects.py."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_fit_subjects_create", "dh_fit_subjects_destroy", "dh_fit_subjects_info", "dh_fit_subjects_model", "dh_fit_subjects_set_coeffs",
        "dh_fit_subjects_state", "dh_fit_subjects_read", "dh_fit_subjects_update", "dh_fit_subjects_update_device", "dh_fit_shape_subjects", "dh_fit_shape_subjects_cameras",
        "dh_fit_shape_subjects_device", "dh_fit_shape_subjects_cameras_device", "dh_fit_depth_carried_device", "dh_fit_depth_cameras_carried_device"]
@@ -36,13 +32,8 @@ int main() {
 """
 
 
-def _err(lib):
-    return lib.dh_last_error().decode()
-
-
 def test_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     import depthhead_amd
     from depthhead_amd import fit
     assert hasattr(depthhead_amd, "Subjects") and "Subjects" in depthhead_amd.__all__
@@ -54,25 +45,12 @@ def test_entry_points_are_exported(hip_lib):
 
 
 def test_header_and_exports_are_equal():
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert f"int {n}(" in text, n
-    declared = set(re.findall(r"^(?:int|const char \*)\s*(dh_\w+)\(", text, re.M))
-    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
-    assert len(_lib.EXPORTS) == len(set(_lib.EXPORTS))
+    abi_kit.assert_header_equals_exports(NEW)
 
 
 def test_state_layout_matches_the_header(tmp_path):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line and not line.startswith("consts")}
-    consts = [int(v) for v in next(line for line in out if line.startswith("consts")).split()[1:]]
+    c, consts = abi_kit.layouts(tmp_path, LAYOUT_CPP)
+    consts = [int(v) for v in consts]
     assert consts == [_lib.SUBJECTS_MAX_TRIS, _lib.SUBJECT_CLAMPED, _lib.SUBJECT_NONFINITE] == [131072, 1, 2]
     dt = _lib.SUBJECT_STATE_DTYPE
     assert c[("dh_subject_state", "size")] == dt.itemsize == 80 == sum(dt.fields[f][0].itemsize for f in dt.names)      # no padding

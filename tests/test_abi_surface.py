@@ -7,17 +7,13 @@ the surface adds come after the basis's, so they are reached with it, and the ca
 of either kind cannot be made without a device: the surface calls refused on an ordinary set, and the refusals that need a real
 surface set, are in tests/test_gpu_surface.py."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
+import abi_kit
+from abi_kit import err as _err
 from depthhead_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["dh_fit_subjects_create_surface", "dh_fit_subjects_set_offsets", "dh_fit_subjects_read_offsets", "dh_fit_surface_params_default",
        "dh_fit_surface_subjects", "dh_fit_surface_subjects_cameras", "dh_fit_surface_subjects_device", "dh_fit_surface_subjects_cameras_device"]
 EINVAL = -1
@@ -42,13 +38,8 @@ int main() {
 """
 
 
-def _err(lib):
-    return lib.dh_last_error().decode()
-
-
 def test_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
     from depthhead_amd import fit
     for name in ("refine_subjects", "surface_params"):
         assert callable(getattr(fit, name)), name
@@ -58,25 +49,12 @@ def test_entry_points_are_exported(hip_lib):
 
 
 def test_header_and_exports_are_equal():
-    text = open(os.path.join(ROOT, "include", "depthhead_hip.h")).read()
-    for n in NEW:
-        assert f"int {n}(" in text, n
-    declared = set(re.findall(r"^(?:int|const char \*)\s*(dh_\w+)\(", text, re.M))
-    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
-    assert len(_lib.EXPORTS) == len(set(_lib.EXPORTS))
+    abi_kit.assert_header_equals_exports(NEW)
 
 
 def test_record_and_params_layouts_match_the_header(tmp_path, hip_lib):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
-    src.write_text(LAYOUT_CPP)
-    res = subprocess.run([gxx, "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split("\n")
-    c = {tuple(line.split()[:2]): int(line.split()[2]) for line in out if line and not line.startswith("consts")}
-    consts = [float(v) for v in next(line for line in out if line.startswith("consts")).split()[1:]]
+    c, consts = abi_kit.layouts(tmp_path, LAYOUT_CPP)
+    consts = [float(v) for v in consts]
     assert consts == [_lib.SURFACE_OK, _lib.SURFACE_FEW_POINTS, _lib.SURFACE_MAX_OFFSET, _lib.SURFACE_MAX_SCALE, _lib.SURFACE_MAX_CELLS,
                       _lib.SURFACE_MAX_ITERATIONS] == [0, 1, 64, 64, 1 << 22, 256]
     dt = _lib.SURFACE_RECORD_DTYPE

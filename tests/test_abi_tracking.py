@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from depthhead_amd import _lib
+import abi_kit
 
 NEW = ["dh_cameras_create", "dh_cameras_destroy", "dh_predict_batch_cameras", "dh_predict_batch_cameras_device",
        "dh_tracker_create", "dh_tracker_destroy", "dh_tracker_reset", "dh_tracker_step", "dh_tracker_step_device",
@@ -12,8 +12,7 @@ NEW = ["dh_cameras_create", "dh_cameras_destroy", "dh_predict_batch_cameras", "d
 
 
 def test_tracking_entry_points_are_exported(hip_lib):
-    for n in NEW:
-        assert n in _lib.EXPORTS and hasattr(hip_lib, n), n
+    abi_kit.assert_exported(hip_lib, NEW)
 
 
 def test_cameras_create_argument_checks(hip_lib):

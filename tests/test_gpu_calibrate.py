@@ -15,6 +15,7 @@ import fit_ref as fr
 import fit_scenes as fs
 import shape_scenes as ss
 import view_fit_scenes as vs
+from gpu_kit import fit_models, same_records
 from depthhead_amd import _lib, fit, synth
 from depthhead_amd.tracking import Cameras
 
@@ -44,12 +45,8 @@ def host_models():
 
 @pytest.fixture(scope="module")
 def gpu():
-    ms = {k: fit.Model(p, n) for k, (p, n) in host_models().items()}
-    ft = fit.Fitter()
-    yield ms, ft
-    ft.close()
-    for m in ms.values():
-        m.close()
+    with fit_models(host_models()) as both:
+        yield both
 
 
 @contextlib.contextmanager
@@ -63,10 +60,8 @@ def ref_params(prm):
 
 
 def same(got, want, what):
-    assert got.dtype == REC and want.dtype.itemsize == REC.itemsize
-    for i in range(len(want)):
-        assert got[i].tobytes() == want[i].tobytes(), (what, i, got[i], want[i])
-    assert got.tobytes() == want.tobytes(), what
+    assert got.dtype == REC
+    same_records(got, want, what)
 
 
 def check(gpu, scene, points, inst, sets=None, take=None, hold=None, prm=None):

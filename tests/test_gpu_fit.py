@@ -15,6 +15,7 @@ import pytest
 import fit_ref as fr
 import fit_scenes as fs
 import render_ref as rr
+from gpu_kit import fit_models, same_records
 from depthhead_amd import _lib, fit, render, synth
 
 pytestmark = pytest.mark.gpu
@@ -41,12 +42,8 @@ def host_models():
 
 @pytest.fixture(scope="module")
 def gpu():
-    ms = [fit.Model(p, n) for p, n in host_models()]
-    ft = fit.Fitter()
-    yield ms, ft
-    ft.close()
-    for m in ms:
-        m.close()
+    with fit_models(host_models()) as both:
+        yield both
 
 
 def instances(items):
@@ -76,19 +73,13 @@ def expected(frames, Ks, inst, prm=None):
     return out, rec
 
 
-def same(got, want, what):
-    for i in range(len(want)):
-        assert got[i].tobytes() == want[i].tobytes(), (what, i, got[i], want[i])
-    assert got.tobytes() == want.tobytes(), what
-
-
 def check(gpu, frames, K, inst, prm=None, K_gpu=None):
     ms, ft = gpu
     out, rec = ft.fit(frames, ms, inst, K if K_gpu is None else K_gpu, params=prm)
     want_out, want_rec = expected(frames, K, inst, prm)
     assert out.dtype == INST and rec.dtype == REC and len(out) == len(rec) == len(inst)
-    same(rec, want_rec, "record")
-    same(out, want_out, "instance")
+    same_records(rec, want_rec, "record")
+    same_records(out, want_out, "instance")
     return out, rec
 
 
@@ -157,7 +148,7 @@ def test_twelve_instances_over_five_frames(gpu):
     frames, K, inst = five_frames()
     out, rec = ft.fit(frames, ms, inst, K)
     want_out, want_rec = five_frames_expected()
-    same(rec, want_rec, "record"); same(out, want_out, "instance")
+    same_records(rec, want_rec, "record"); same_records(out, want_out, "instance")
     assert rec["status"][9] == fit.FIT_FEW_POINTS and rec["points"][9] == 0 and out[9].tobytes() == inst[9].tobytes()
     assert (np.delete(rec["status"], 9) == fit.FIT_OK).all() and (np.delete(rec["points"], 9) >= 30).all()
     assert np.linalg.norm(out["t"][6] - (-150.0, -10.0, 900.0)) < 10 and np.linalg.norm(out["t"][7] - (140.0, 20.0, 1000.0)) < 10
@@ -169,7 +160,7 @@ def test_two_runs_are_byte_identical(gpu):
     a = ft.fit(frames, ms, inst, K)
     b = ft.fit(frames, ms, inst, K)
     assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
-    same(a[1], five_frames_expected()[1], "record")
+    same_records(a[1], five_frames_expected()[1], "record")
 
 
 @pytest.mark.parametrize("model,points", [(1, 1), (2, 257), (3, 2562), (5, 255), (6, 256), (7, 1023), (8, 1024), (9, 1025)])
@@ -308,8 +299,8 @@ def test_device_twins_chained_after_a_device_render(gpu):
         host = frames.cpu().view(torch.int16).numpy().view(np.uint16)
         got = [x.cpu().numpy().view(dt) for x, dt in ((d_out, INST), (d_rec, REC), (c_out, INST), (c_rec, REC))]
     h_out, h_rec = check(gpu, host, K, inst)
-    same(got[0], h_out, "device instance"); same(got[1], h_rec, "device record")
-    same(got[2], h_out, "camera device instance"); same(got[3], h_rec, "camera device record")
+    same_records(got[0], h_out, "device instance"); same_records(got[1], h_rec, "device record")
+    same_records(got[2], h_out, "camera device instance"); same_records(got[3], h_rec, "camera device record")
     assert h_rec["status"].tolist() == [fit.FIT_OK, fit.FIT_OK, fit.FIT_FEW_POINTS]
     for f, (p, R) in enumerate(truth):
         assert np.linalg.norm(h_out["t"][f] - p) < 10.0
@@ -324,9 +315,9 @@ def test_smaller_then_larger_then_smaller_batch_in_one_fitter(gpu):
     with fit.Fitter() as ft:
         for _ in range(2):
             out, rec = ft.fit(small_f[None], ms, small, small_K)
-            same(rec, want_small[1], "small record"); same(out, want_small[0], "small instance")
+            same_records(rec, want_small[1], "small record"); same_records(out, want_small[0], "small instance")
             out, rec = ft.fit(frames, ms, inst, K)
-            same(rec, five_frames_expected()[1], "large record"); same(out, five_frames_expected()[0], "large instance")
+            same_records(rec, five_frames_expected()[1], "large record"); same_records(out, five_frames_expected()[0], "large instance")
         out, rec = ft.fit(small_f[None], ms, [], small_K)
         assert len(out) == 0 and len(rec) == 0
 

@@ -23,6 +23,7 @@ import shape_views_ref as svr
 import subjects_ref as sb
 import surface_ref as ur
 import view_fit_ref as vr
+from gpu_kit import between_guards, same_records, to_device
 from depthhead_amd import _lib, fit
 from depthhead_amd.tracking import Cameras
 
@@ -78,31 +79,10 @@ def literals(tb):
     return p, e, ([r.name for r in tb.rows] if isinstance(tb.points, list) else ["all rows"])
 
 
-def to_device(array):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def between_guards(frames):
-    """The frames on the device inside a larger allocation: GUARD elements of fe.BACK (inside every gate of a row that could
-    read them) before and after.  Returns (the tensor of the frames' shape, the allocation, which must stay alive)."""
-    import torch
-    flat = np.full(frames.size + 2 * GUARD, fe.BACK, np.uint16)
-    flat[GUARD:GUARD + frames.size] = frames.reshape(-1)
-    whole = torch.from_numpy(flat.view(np.int16)).cuda()
-    return whole[GUARD:GUARD + frames.size].view(*frames.shape), whole
-
-
 def host(tensor, dtype):
     import torch
     torch.cuda.synchronize()
     return tensor.cpu().numpy().view(dtype)
-
-
-def same(got, want, what):
-    assert len(got) == len(want)
-    for i in range(len(want)):
-        assert got[i].tobytes() == want[i].tobytes(), (what, i, got[i], want[i])
 
 
 # ---------------------------------------------------------------- Fitter.fit
@@ -142,7 +122,7 @@ def run_fit(ft, ms, tb, gate, form, prm=None):
     if form == "cameras":
         with Cameras(tb.Ks) as cams:
             return ft.fit(tb.frames, ms, tb.inst, cams, params=prm)
-    frames, whole = between_guards(tb.frames)
+    frames, whole = between_guards(tb.frames, GUARD, fe.BACK)
     with Cameras(tb.Ks) as cams:
         if form == "carried":                          # the start comes from the carried poses, not from the instances
             off = tb.inst.copy()
@@ -163,7 +143,7 @@ def test_fit_row_by_row(gpu, gate, mirrored, form):
     out, rec = run_fit(ft, bank.rows(tb, mirrored), tb, gate, form)
     hold_fit(out, rec, tb, form)
     want_out, want_rec = fit_restated("rows", gate, mirrored, own)
-    same(rec, want_rec, "record"); same(out, want_out, "instance")
+    same_records(rec, want_rec, "record"); same_records(out, want_out, "instance")
 
 
 @pytest.mark.parametrize("form", ("cameras", "cameras_device"))
@@ -176,7 +156,7 @@ def test_fit_row_by_row_at_the_widest_gate(gpu, form):
     out, rec = run_fit(ft, bank.rows(tb, False), tb, 4096.0, form)
     hold_fit(out, rec, tb, form)
     want_out, want_rec = fit_restated("rows", 4096.0, False, True)
-    same(rec, want_rec, "record"); same(out, want_out, "instance")
+    same_records(rec, want_rec, "record"); same_records(out, want_out, "instance")
 
 
 @pytest.mark.parametrize("form", ("one_k", "device", "carried"))
@@ -191,7 +171,7 @@ def test_fit_aggregated(gpu, gate, n, mirrored, form):
     out, rec = run_fit(ft, ms, tb, gate, form)
     hold_fit(out, rec, tb, form)
     want_out, want_rec = fit_restated(n, gate, mirrored, True)
-    same(rec, want_rec, "record"); same(out, want_out, "instance")
+    same_records(rec, want_rec, "record"); same_records(out, want_out, "instance")
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -203,7 +183,7 @@ def test_fit_aggregated_one_coarse_step_is_the_restated_one(gpu, gate, n):
     tb = table(n, gate)
     out, rec = run_fit(ft, models_of(bank, n, gate, False, tb), tb, gate, "one_k", fit_prm(gate, coarse=1, min_points=6))
     want_out, want_rec = fit_restated(n, gate, False, True, coarse=1)
-    same(rec, want_rec, "record"); same(out, want_out, "instance")
+    same_records(rec, want_rec, "record"); same_records(out, want_out, "instance")
     assert rec["steps"][0] == 1
 
 
@@ -263,7 +243,7 @@ def run_views(ft, ms, frames, Ks, inst, gate, device):
     with identity_views(Ks) as views:
         if not device:
             return ft.fit_views(frames, ms, inst, views, params=fit_prm(gate))
-        d_frames, whole = between_guards(frames)
+        d_frames, whole = between_guards(frames, GUARD, fe.BACK)
         out, rec = ft.fit_views(d_frames, ms, inst, views, params=fit_prm(gate), device_out=True)
         return host(out, VINST), host(rec, VREC)
 
@@ -281,7 +261,7 @@ def test_fit_views_row_by_row_each_through_its_own_camera(gpu, gate, mirrored, d
     for i, r in enumerate(tb.rows):
         got = (rec["points"][i], rec["sum_r2_fixed"][i], rec["views_used"][i], rec["steps"][i], rec["status"][i])
         assert got == (r.points, r.e, r.points, 0, fit.FIT_OK), (r.name, got)
-    same(rec, views_restated(tb.frames, tb.Ks, inst, tb.models, gate), "record")
+    same_records(rec, views_restated(tb.frames, tb.Ks, inst, tb.models, gate), "record")
 
 
 @pytest.mark.parametrize("device", [False, True])
@@ -295,7 +275,7 @@ def test_fit_views_aggregated(gpu, gate, n, mirrored, device):
     out, rec = run_views(ft, models_of(bank, n, gate, mirrored, tb), tb.frames, tb.Ks, inst, gate, device)
     assert out.tobytes() == inst.tobytes()
     assert (rec["points"][0], rec["sum_r2_fixed"][0], rec["views_used"][0], rec["steps"][0]) == (tb.points, tb.e, 1, 0)
-    same(rec, views_restated(tb.frames, tb.Ks, inst, tb.models, gate), "record")
+    same_records(rec, views_restated(tb.frames, tb.Ks, inst, tb.models, gate), "record")
 
 
 @pytest.mark.parametrize("index", [0, 64, 128, 192, 256])
@@ -315,7 +295,7 @@ def test_fit_views_second_view_sees_one_row_in_one_wave(gpu, name, index):
     out, rec = run_views(ft, models_of(bank, 257, 25.0, False, tb, pin=(name, index)), frames, Ks, inst, 25.0, device=index == 128)
     got = (rec["points"][0], rec["sum_r2_fixed"][0], rec["views_used"][0])
     assert got == (tb.points + row.points, tb.e + row.e, 0b11 if row.points else 0b01), got
-    same(rec, views_restated(frames, Ks, inst, tb.models, 25.0), "record")
+    same_records(rec, views_restated(frames, Ks, inst, tb.models, 25.0), "record")
     assert out.tobytes() == inst.tobytes()
 
 
@@ -372,7 +352,7 @@ def test_shape_steps_aggregated_host_and_device(gpu, gate, n, mirrored):
     want_views = svr.shape_step(tb.frames[None], tb.Ks, EYE[None], np.zeros((1, 3), np.float32), pts, nrm, B, vinst, prm=ref_prm)
     hold_sums(want[0], tb.points, tb.e, "the restatement")
     assert want.tobytes() == want_views.tobytes()
-    d_frames, whole = between_guards(tb.frames)
+    d_frames, whole = between_guards(tb.frames, GUARD, fe.BACK)
     with fit.ShapeBasis(B) as basis, identity_views(tb.Ks) as views:
         for what, got in (("shape_step", ft.shape_step(tb.frames, model, basis, tb.inst, fe.K, params=prm)),
                           ("shape_step, cameras", ft.shape_step(tb.frames, model, basis, tb.inst, views.cameras, params=prm)),
@@ -420,7 +400,7 @@ def test_calibrate_step_aggregated_host_and_device(gpu, gate, n, mirrored):
     prm, ref_prm = calib_prm(gate)
     vinst = view_instances(tb.inst, [0], [1])
     want = cr.calib_step(tb.frames[None], tb.Ks, EYE[None], np.zeros((1, 3), np.float32), *tb.models[0], vinst, prm=ref_prm)
-    d_frames, whole = between_guards(tb.frames)
+    d_frames, whole = between_guards(tb.frames, GUARD, fe.BACK)
     with identity_views(tb.Ks) as views:
         got = ft.calibrate_step(tb.frames[None], views, model, vinst, params=prm)
         dev = host(ft.calibrate_step(d_frames[None], views, model, to_device(vinst), params=prm, device_out=True), CREC)
@@ -452,7 +432,7 @@ def test_shape_step_subjects_and_identify_subjects_aggregated(gpu, gate, n, mirr
     st = sb.Set(mesh.verts, mesh.tris, field_of(n), 1)
     want = sb.shape_step(tb.frames, fe.K, st, tb.inst, prm=sr.params(gate=gate))
     w_sub, w_rec, _, w_scores = ir.identify(tb.frames, fe.K, st, fe.as_dicts(tb.inst), prm=ir.params(iterations=0, gate=gate))
-    d_frames, whole = between_guards(tb.frames)
+    d_frames, whole = between_guards(tb.frames, GUARD, fe.BACK)
     with subject_set(mesh, n, st) as got:
         prm = fit.shape_params(gate=gate)
         for what, rec in (("host", ft.shape_step_subjects(tb.frames, got, tb.inst, fe.K, params=prm)),
@@ -481,7 +461,7 @@ def test_surface_step_subjects_aggregated(gpu, gate, n, mirrored):
     tb = mesh.table
     st = ur.Set(mesh.verts, mesh.tris, field_of(n), 1)
     want = ur.surface_step(tb.frames, fe.K, st, fe.as_dicts(tb.inst), prm=ur.params(gate=gate, min_cos2=0.0))
-    d_frames, whole = between_guards(tb.frames)
+    d_frames, whole = between_guards(tb.frames, GUARD, fe.BACK)
     prm = fit.surface_params(gate=gate, min_cos2=0.0)
     with subject_set(mesh, n, st) as got:
         for what, rec in (("host", ft.surface_step_subjects(tb.frames, got, tb.inst, fe.K, params=prm)),
@@ -500,7 +480,7 @@ def test_surface_step_subjects_grazing_rows(gpu, n, mirrored):
     mesh = fe.aggregated_mesh(n, 256.0, mirrored, only=fe.GRAZING)
     tb = mesh.table
     st = ur.Set(mesh.verts, mesh.tris, field_of(n), 1)
-    d_frames, whole = between_guards(tb.frames)
+    d_frames, whole = between_guards(tb.frames, GUARD, fe.BACK)
     with subject_set(mesh, n, st) as got:
         for min_cos2, points in ((fe.GRAZE, 2), (0.0, 3)):
             want = ur.surface_step(tb.frames, fe.K, st, fe.as_dicts(tb.inst), prm=ur.params(gate=256.0, min_cos2=min_cos2))

@@ -12,6 +12,7 @@ import fit_scenes as fs
 import render_ref as rr
 import shape_ref as sr
 import shape_scenes as ss
+from gpu_kit import fit_models, same_records
 from depthhead_amd import _lib, fit, render, synth
 
 pytestmark = pytest.mark.gpu
@@ -45,12 +46,8 @@ def host_models():
 
 @pytest.fixture(scope="module")
 def gpu():
-    ms = {k: fit.Model(p, n) for k, (p, n, _) in host_models().items()}
-    ft = fit.Fitter()
-    yield ms, ft
-    ft.close()
-    for m in ms.values():
-        m.close()
+    with fit_models(host_models()) as both:
+        yield both
 
 
 def ref_params(prm):
@@ -58,10 +55,8 @@ def ref_params(prm):
 
 
 def same(got, want, what):
-    assert got.dtype == REC and want.dtype.itemsize == REC.itemsize
-    for i in range(len(want)):
-        assert got[i].tobytes() == want[i].tobytes(), (what, i, got[i], want[i])
-    assert got.tobytes() == want.tobytes(), what
+    assert got.dtype == REC
+    same_records(got, want, what)
 
 
 def check(gpu, frames, K, points, nk, inst, subjects=None, ns=1, prm=None, K_gpu=None):

@@ -16,6 +16,7 @@ import shape_scenes as ss
 import shape_views_ref as svr
 import shape_views_scenes as sv
 import view_fit_ref as vr
+from gpu_kit import fit_models, same_records
 from depthhead_amd import _lib, fit, synth
 from depthhead_amd.tracking import Cameras
 
@@ -50,12 +51,8 @@ def host_models():
 
 @pytest.fixture(scope="module")
 def gpu():
-    ms = {k: fit.Model(p, n) for k, (p, n, _) in host_models().items()}
-    ft = fit.Fitter()
-    yield ms, ft
-    ft.close()
-    for m in ms.values():
-        m.close()
+    with fit_models(host_models()) as both:
+        yield both
 
 
 @contextlib.contextmanager
@@ -69,10 +66,8 @@ def ref_params(prm):
 
 
 def same(got, want, what):
-    assert got.dtype == REC and want.dtype.itemsize == REC.itemsize
-    for i in range(len(want)):
-        assert got[i].tobytes() == want[i].tobytes(), (what, i, got[i], want[i])
-    assert got.tobytes() == want.tobytes(), what
+    assert got.dtype == REC
+    same_records(got, want, what)
 
 
 def check(gpu, scene, points, nk, inst, sets=None, subjects=None, ns=1, prm=None):

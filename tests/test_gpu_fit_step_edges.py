@@ -21,6 +21,7 @@ import fit_track_ref as tkr
 import rig_fit_track_ref as rf
 import shape_ref as sr
 import view_fit_ref as vr
+from gpu_kit import between_guards, to_device
 from depthhead_amd import _lib, fit, tracking
 
 pytestmark = pytest.mark.gpu
@@ -61,20 +62,6 @@ def gpu():
     with fit.Fitter() as ft:
         yield ft, bank, angles
     bank.close()
-
-
-def to_device(array):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def between_guards(frames):
-    """The frames on the device inside a larger allocation (GUARD elements of an in-gate depth before and after)."""
-    import torch
-    flat = np.full(frames.size + 2 * GUARD, fe.BACK, np.uint16)
-    flat[GUARD:GUARD + frames.size] = frames.reshape(-1)
-    whole = torch.from_numpy(flat.view(np.int16)).cuda()
-    return whole[GUARD:GUARD + frames.size].view(*frames.shape), whole
 
 
 def host(tensor, dtype):
@@ -124,7 +111,7 @@ def test_fit(gpu, case, n, form):
     if form == "host":
         out, rec = ft.fit(case.frame[None], [model], inst, fe.K, params=gpu_params(case))
     else:
-        frames, whole = between_guards(case.frame[None])
+        frames, whole = between_guards(case.frame[None], GUARD, fe.BACK)
         out, rec = ft.fit(frames, [model], inst, fe.K, params=gpu_params(case), device_out=True)
         out, rec = host(out, INST), host(rec, REC)
     hold_step(case, rec[0], out[0]["R"], out[0]["t"], form)
@@ -149,7 +136,7 @@ def test_fit_views(gpu, case, n, views, form):
         if form == "host":
             out, rec = ft.fit_views(frames, [model], inst, vw, params=gpu_params(case))
         else:
-            d_frames, whole = between_guards(frames)
+            d_frames, whole = between_guards(frames, GUARD, fe.BACK)
             out, rec = ft.fit_views(d_frames, [model], inst, vw, params=gpu_params(case), device_out=True)
             out, rec = host(out, VINST), host(rec, VREC)
     hold_step(case, rec[0], out[0]["R"], out[0]["t"], form)
@@ -169,7 +156,7 @@ def track_step(tracker, form, frames, poses, support, present=None, fit_params=N
     if form == "host":
         return tracker.step_poses(frames, poses, support, present=present, fit_params=fit_params)
     import torch
-    d_frames, whole = between_guards(frames)
+    d_frames, whole = between_guards(frames, GUARD, fe.BACK)
     d = [to_device(poses), to_device(support), to_device(np.asarray(present, np.uint8)) if present is not None else None]
     rec = torch.zeros(len(frames) * TREC.itemsize, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
@@ -259,7 +246,7 @@ def rig_step(tr, form, frames, inputs, present=None, fit_params=None):
     if form == "host":
         return tr.step_persons(frames, n_heads, heads, n_persons, persons, present=present, fit_params=fit_params)
     import torch
-    d_frames, whole = between_guards(frames)
+    d_frames, whole = between_guards(frames, GUARD, fe.BACK)
     d = [to_device(a) for a in (n_heads, heads, n_persons, persons)]
     d_pr = to_device(np.asarray(present, np.uint8)) if present is not None else None
     rec = torch.zeros(len(n_persons) * 16 * RREC.itemsize, dtype=torch.uint8, device="cuda")
@@ -335,7 +322,7 @@ def test_shape_step_solve(gpu, case, n, form):
         if form == "host":
             rec = ft.shape_step(se.F65[None], model, basis, inst, fe.K, params=prm)
         else:
-            d_frames, whole = between_guards(se.F65[None])
+            d_frames, whole = between_guards(se.F65[None], GUARD, fe.BACK)
             rec = host(ft.shape_step(d_frames, model, basis, to_device(inst), fe.K, params=prm, device_out=True), _lib.SHAPE_RECORD_DTYPE)
     got = (rec["status"][0], rec["points"][0], rec["sum_r2_fixed"][0], rec["instances"][0], rec["reserved"][0])
     assert got == (case.status, case.points, case.e, 1, 0), (case.name, got)
@@ -359,7 +346,7 @@ def test_calibrate_step_solve(gpu, case, n, form):
         if form == "host":
             rec = ft.calibrate_step(frames, vw, model, inst, params=prm)
         else:
-            d_frames, whole = between_guards(se.F65[None])
+            d_frames, whole = between_guards(se.F65[None], GUARD, fe.BACK)
             rec = host(ft.calibrate_step(d_frames[None], vw, model, to_device(inst), params=prm, device_out=True), _lib.CALIB_RECORD_DTYPE)
     got = (rec["status"][0], rec["points"][0], rec["sum_r2_fixed"][0], rec["pairs"][0])
     assert got == (case.status, case.points, case.e, 1), (case.name, got)

@@ -15,6 +15,7 @@ import fit_ref as fr
 import fit_scenes as fs
 import fit_track_ref as ft
 import fit_track_scenes as sc
+from gpu_kit import guarded, same_records, to_device, untouched
 from depthhead_amd import _lib, fit, prediction, synth, tracking
 
 pytestmark = pytest.mark.gpu
@@ -82,13 +83,6 @@ def ref_fit_params(prm):
     return fr.params() if prm is None else fr.params(prm.coarse_iterations, prm.iterations, (prm.gate[0], prm.gate[1]), prm.lam, prm.min_points)
 
 
-def same(got, want, what):
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert len(got) == len(want) and got.dtype.itemsize == want.dtype.itemsize, what
-    for i in range(len(want)):
-        assert got[i].tobytes() == want[i].tobytes(), (what, i, got[i], want[i])
-
-
 def kinds(rec):
     return (np.asarray(rec["status"]) & 0xFF).tolist()
 
@@ -100,8 +94,8 @@ def run_both(tr, ref, frames, poses, sup, present, fit_params=None, steps=None):
         pr = None if present is None else present[k]
         got = tr.step_poses(frames[k], poses[k], sup[k], pr, fit_params)
         want = ref.step(frames[k], poses[k], sup[k], pr, ref_fit_params(fit_params))
-        same(got, want, f"records of step {k}")
-        same(tr.state(), ref.state, f"state after step {k}")
+        same_records(got, want, f"records of step {k}")
+        same_records(tr.state(), ref.state, f"state after step {k}")
         out.append(got)
     return np.stack(out)
 
@@ -152,10 +146,10 @@ def test_whole_step_behind_a_synth_forest(gpu, radius, conf):
         for k in range(STEPS):
             poses, sup, got = tr.step(hp, frames[k], present[k], radius=radius)
             plain_p, plain_s = hp.predict_batch_cameras_support(frames[k], cams, radius=radius)
-            same(poses, plain_p, "poses"); same(sup, plain_s, "support")
+            same_records(poses, plain_p, "poses"); same_records(sup, plain_s, "support")
             want = ref.step(frames[k], poses, sup, present[k])
-            same(got, want, f"records of step {k}")
-            same(tr.state(), ref.state, f"state after step {k}")
+            same_records(got, want, f"records of step {k}")
+            same_records(tr.state(), ref.state, f"state after step {k}")
             seen.append(kinds(got))
     print(radius, conf, seen)
     assert all(s[2] == ft.ABSENT for s in seen[2:4])
@@ -200,23 +194,6 @@ def test_carried_start_skips_the_coarse_phase(gpu):
     assert (second["status"] == ft.CARRIED).all() and (second["fit"]["steps"] <= 6).all() and (second["age"] == 2).all()
 
 
-def to_dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def guarded(nbytes, skew):
-    """A device buffer of 4 KB guard bands around `nbytes` at a skewed start: (tensor, pointer, offset)."""
-    import torch
-    buf = torch.full((4096 + skew + nbytes + 4096,), 0xA5, dtype=torch.uint8, device="cuda")
-    return buf, buf.data_ptr() + 4096 + skew, 4096 + skew
-
-
-def untouched(buf, off, nbytes):
-    host = buf.cpu().numpy()
-    return (host[:off] == 0xA5).all() and (host[off + nbytes:] == 0xA5).all()
-
-
 def test_host_calls_against_device_twins_between_guard_bands(gpu):
     """The core step and the whole step, host call against _device twin on a side stream; the twin's outputs lie between 4 KB
     guard bands at skewed pointers (8 bytes off for the records, the poses and the support) and nothing outside them changes."""
@@ -229,7 +206,7 @@ def test_host_calls_against_device_twins_between_guard_bands(gpu):
         for k in range(4):
             want = th.step_poses(frames[k], poses[k], sup[k], present[k])
             w_poses, w_sup, w_rec = wh.step(hp, frames[k], present[k])
-            d_frames, d_poses, d_sup, d_pr = to_dev(frames[k]), to_dev(poses[k]), to_dev(sup[k]), to_dev(present[k])
+            d_frames, d_poses, d_sup, d_pr = to_device(frames[k]), to_device(poses[k]), to_device(sup[k]), to_device(present[k])
             rec, rec_p, rec_o = guarded(3 * REC.itemsize, 8)
             rec2, rec2_p, rec2_o = guarded(3 * REC.itemsize, 24)
             po, po_p, po_o = guarded(3 * POSE.itemsize, 8)
@@ -243,8 +220,8 @@ def test_host_calls_against_device_twins_between_guard_bands(gpu):
                                                   (po, po_o, POSE, w_poses, "poses"), (so, so_o, SUP, w_sup, "support")):
                 nb = 3 * dt.itemsize
                 assert untouched(buf, off, nb), what
-                same(buf.cpu().numpy()[off:off + nb].view(dt), ref_bytes, f"{what} of step {k}")
-            same(td.state(), th.state(), "core state"); same(wd.state(), wh.state(), "whole-step state")
+                same_records(buf.cpu().numpy()[off:off + nb].view(dt), ref_bytes, f"{what} of step {k}")
+            same_records(td.state(), th.state(), "core state"); same_records(wd.state(), wh.state(), "whole-step state")
 
 
 def test_reset_and_two_runs_of_one_sequence(gpu):
@@ -255,7 +232,7 @@ def test_reset_and_two_runs_of_one_sequence(gpu):
         first = run_both(tr, ref, frames, poses, sup, present)
         state = tr.state()
         tr.reset(1); ref.reset(1)
-        same(tr.state(), ref.state, "state after the reset of camera 1")
+        same_records(tr.state(), ref.state, "state after the reset of camera 1")
         assert not np.frombuffer(tr.state()[1].tobytes(), np.uint8).any() and tr.state()[0].tobytes() == state[0].tobytes()
         run_both(tr, ref, frames, poses, sup, present, steps=2)
         tr.reset(); ref.reset()
@@ -270,7 +247,7 @@ def test_one_step_captured_in_a_graph(gpu):
     cams, model, angles = gpu
     frames, poses, sup, present = main_sequence()
     with fit.FitTracker(cams, model, W, H) as eager, fit.FitTracker(cams, model, W, H) as tr:
-        d_frames, d_poses, d_sup = to_dev(frames[0]), to_dev(poses[0]), to_dev(sup[0])
+        d_frames, d_poses, d_sup = to_device(frames[0]), to_device(poses[0]), to_device(sup[0])
         d_rec = torch.zeros(3 * REC.itemsize, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -281,12 +258,12 @@ def test_one_step_captured_in_a_graph(gpu):
         tr.reset()                                                     # whatever the capture itself ran or did not run
         torch.cuda.synchronize()
         for k in range(3):
-            d_frames.copy_(to_dev(frames[k])); d_poses.copy_(to_dev(poses[k])); d_sup.copy_(to_dev(sup[k]))
+            d_frames.copy_(to_device(frames[k])); d_poses.copy_(to_device(poses[k])); d_sup.copy_(to_device(sup[k]))
             g.replay()
             torch.cuda.synchronize()
             want = eager.step_poses(frames[k], poses[k], sup[k])
-            same(d_rec.cpu().numpy().view(REC), want, f"replay {k}")
-            same(tr.state(), eager.state(), f"state after replay {k}")
+            same_records(d_rec.cpu().numpy().view(REC), want, f"replay {k}")
+            same_records(tr.state(), eager.state(), f"state after replay {k}")
 
 
 def test_refusals_that_need_a_tracker(gpu):

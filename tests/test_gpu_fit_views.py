@@ -16,6 +16,7 @@ import fit_scenes as fs
 import render_ref as rr
 import view_fit_ref as vr
 import view_fit_scenes as vs
+from gpu_kit import fit_models, same_records
 from depthhead_amd import _lib, fit, render, synth
 from depthhead_amd.tracking import Cameras
 
@@ -43,12 +44,8 @@ def host_models():
 
 @pytest.fixture(scope="module")
 def gpu():
-    ms = [fit.Model(p, n) for p, n in host_models()]
-    ft = fit.Fitter()
-    yield ms, ft
-    ft.close()
-    for m in ms:
-        m.close()
+    with fit_models(host_models()) as both:
+        yield both
 
 
 def instances(items):
@@ -75,12 +72,6 @@ def expected(frames, Ks, V, u, inst, prm=None):
     return out, rec
 
 
-def same(got, want, what):
-    for i in range(len(want)):
-        assert got[i].tobytes() == want[i].tobytes(), (what, i, got[i], want[i])
-    assert got.tobytes() == want.tobytes(), what
-
-
 def check(gpu, frames, Ks, V, u, inst, prm=None):
     ms, ft = gpu
     with Cameras(Ks) as cams, fit.Views(cams, V, u) as views:
@@ -88,8 +79,8 @@ def check(gpu, frames, Ks, V, u, inst, prm=None):
         out, rec = ft.fit_views(frames, ms, inst, views, params=prm)
     want_out, want_rec = expected(frames, Ks, V, u, inst, prm)
     assert out.dtype == INST and rec.dtype == REC and len(out) == len(rec) == len(inst)
-    same(rec, want_rec, "record")
-    same(out, want_out, "instance")
+    same_records(rec, want_rec, "record")
+    same_records(out, want_out, "instance")
     return out, rec
 
 
@@ -211,7 +202,7 @@ def test_four_instances_over_two_rigs_in_one_launch(gpu):
         a = ft.fit_views(frames, ms, inst, views)
         b = ft.fit_views(frames, ms, inst, views)
     want_out, want_rec = two_rigs_expected()
-    same(a[1], want_rec, "record"); same(a[0], want_out, "instance")
+    same_records(a[1], want_rec, "record"); same_records(a[0], want_out, "instance")
     assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()                   # two runs of one call
     assert a[1]["status"].tolist() == [fit.FIT_OK] * 3 + [fit.FIT_FEW_POINTS] and a[1]["views_used"].tolist() == [0b111, 0b110, 0b011, 0]
     assert a[0][3].tobytes() == inst[3].tobytes() and a[1]["points"][3] == 0
@@ -303,12 +294,12 @@ def test_host_form_against_the_device_twin_chained_after_a_device_render(gpu):
         host = frames.cpu().view(torch.int16).numpy().view(np.uint16)
         h_out, h_rec = ft.fit_views(host, ms, inst, views)
     want_out, want_rec = expected(host, Ks, V, u, inst)
-    same(h_rec, want_rec, "host record"); same(h_out, want_out, "host instance")
+    same_records(h_rec, want_rec, "host record"); same_records(h_out, want_out, "host instance")
     for buf, size, dt, want in ((bufs[0], sizes[0], INST, want_out), (bufs[1], sizes[1], REC, want_rec)):
         raw = buf.cpu().numpy()
         assert (raw[:GUARD + 8] == 0xEE).all() and (raw[GUARD + 8 + size:] == 0xEE).all()
-        same(raw[GUARD + 8:GUARD + 8 + size].copy().view(dt), want, "device form")
-    same(d_out.cpu().numpy().view(INST), want_out, "device instance"); same(d_rec.cpu().numpy().view(REC), want_rec, "device record")
+        same_records(raw[GUARD + 8:GUARD + 8 + size].copy().view(dt), want, "device form")
+    same_records(d_out.cpu().numpy().view(INST), want_out, "device instance"); same_records(d_rec.cpu().numpy().view(REC), want_rec, "device record")
     assert h_rec["status"].tolist() == [fit.FIT_OK, fit.FIT_OK, fit.FIT_FEW_POINTS] and h_rec["views_used"].tolist() == [0b111, 0b0010, 0]
     assert np.linalg.norm(h_out["t"][0] - pos) < 10.0
 
@@ -327,9 +318,9 @@ def test_a_fitter_reused_with_a_smaller_a_larger_and_an_empty_call(gpu):
         before = ft.fit(frame[None], ms, single, K)
         for _ in range(2):
             out, rec = ft.fit_views(sf, ms, small, v2)
-            same(rec, want_small[1], "small record"); same(out, want_small[0], "small instance")
+            same_records(rec, want_small[1], "small record"); same_records(out, want_small[0], "small instance")
             out, rec = ft.fit_views(frames, ms, inst, v7)
-            same(rec, two_rigs_expected()[1], "large record"); same(out, two_rigs_expected()[0], "large instance")
+            same_records(rec, two_rigs_expected()[1], "large record"); same_records(out, two_rigs_expected()[0], "large instance")
         out, rec = ft.fit_views(sf, ms, [], v2)
         assert len(out) == 0 and len(rec) == 0
         after = ft.fit(frame[None], ms, single, K)
@@ -350,7 +341,7 @@ def test_one_call_captured_in_a_graph_and_replayed_twice(gpu):
         with torch.cuda.stream(stream):
             out, rec = ft.fit_views(d_frames, ms, inst, views, device_out=True)
         stream.synchronize()
-        same(rec.cpu().numpy().view(REC), want_rec, "eager")
+        same_records(rec.cpu().numpy().view(REC), want_rec, "eager")
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             out, rec = ft.fit_views(d_frames, ms, inst, views, device_out=True)
@@ -361,7 +352,7 @@ def test_one_call_captured_in_a_graph_and_replayed_twice(gpu):
             out.fill_(0xEE); rec.fill_(0xEE)
             g.replay()
             torch.cuda.synchronize()
-            same(rec.cpu().numpy().view(REC), want_rec, "replay record"); same(out.cpu().numpy().view(INST), want_out, "replay instance")
+            same_records(rec.cpu().numpy().view(REC), want_rec, "replay record"); same_records(out.cpu().numpy().view(INST), want_out, "replay instance")
         del g
 
 

@@ -13,6 +13,7 @@ import ident_scenes as isc
 import shape_scenes as ss
 import surface_ref as su
 import surface_scenes as us
+from gpu_kit import to_device
 from depthhead_amd import _lib, fit
 
 pytestmark = pytest.mark.gpu
@@ -27,11 +28,6 @@ SMALL = dict(min_points=16, max_rms=np.inf)
 def ft():
     with fit.Fitter() as f:
         yield f
-
-
-def to_device(array):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
 
 
 @contextlib.contextmanager

@@ -14,6 +14,7 @@ import ident_views_ref as ivr
 import ident_views_scenes as ivs
 import shape_scenes as ss
 import shape_views_scenes as svs
+from gpu_kit import to_device
 from depthhead_amd import _lib, fit
 from depthhead_amd.tracking import Cameras
 
@@ -28,11 +29,6 @@ SMALL = dict(min_points=16, max_rms=np.inf)
 def ft():
     with fit.Fitter() as f:
         yield f
-
-
-def to_device(array):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
 
 
 @contextlib.contextmanager

@@ -17,6 +17,7 @@ import fit_scenes as fs
 import fit_track_scenes as fts
 import rig_fit_track_ref as rf
 import rig_fit_track_scenes as sc
+from gpu_kit import guarded, same_records
 from depthhead_amd import _lib, fit, render, synth, tracking
 
 pytestmark = pytest.mark.gpu
@@ -88,13 +89,6 @@ def ref_run(name, seed, motion, steps):
     return out
 
 
-def same(got, want, what):
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert len(got) == len(want) and got.dtype.itemsize == want.dtype.itemsize, what
-    for i in range(len(want)):
-        assert got[i].tobytes() == want[i].tobytes(), (what, i, got[i], want[i])
-
-
 def gpu_step(tr, st):
     return tr.step_persons(st["frames"], *st["inputs"], present=st["present"], fit_params=fit.fit_params(*st["fit"]) if st["fit"] else None)
 
@@ -109,8 +103,8 @@ def test_scripts_equal_the_restatement_after_every_step(gpu, name, seed, motion,
         for k, st in enumerate(s["steps"][:steps]):
             got = gpu_step(tr, st)
             assert got.dtype == REC and got.shape == (len(s["rig_begin"]) - 1, 16)
-            same(got, want_rec[k], f"{name}: records of step {k}")
-            same(tr.state(), want_state[k], f"{name}: state after step {k}")
+            same_records(got, want_rec[k], f"{name}: records of step {k}")
+            same_records(tr.state(), want_state[k], f"{name}: state after step {k}")
     kinds = set((want_rec["status"] & 0xFF).reshape(-1).tolist())
     assert {"carried": {0, 1, 2}, "absent": {0, 1, 2, 4}, "coast": {0, 1, 2, 4}, "gone": {0, 1, 2, 3}}.get(name, kinds) <= kinds
 
@@ -118,13 +112,6 @@ def test_scripts_equal_the_restatement_after_every_step(gpu, name, seed, motion,
 def dev(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def guarded(nbytes, skew=0):
-    """A device buffer of nbytes between two 4 KB guard bands of 0xA5, its first byte `skew` bytes past a 256-byte boundary."""
-    import torch
-    buf = torch.full((4096 + skew + nbytes + 4096,), 0xA5, dtype=torch.uint8, device="cuda")
-    return buf, buf.data_ptr() + 4096 + skew, 4096 + skew
 
 
 def test_host_steps_against_device_twins_between_guard_bands(gpu):
@@ -148,8 +135,8 @@ def test_host_steps_against_device_twins_between_guard_bands(gpu):
             stream.synchronize()
             host = buf.cpu().numpy()
             assert (host[:off] == 0xA5).all() and (host[off + 16 * REC.itemsize:] == 0xA5).all()
-            same(np.frombuffer(host[off:off + 16 * REC.itemsize].tobytes(), REC), want_rec[k], f"device records of step {k}")
-            same(td.state(), want_state[k], f"device state after step {k}")
+            same_records(np.frombuffer(host[off:off + 16 * REC.itemsize].tobytes(), REC), want_rec[k], f"device records of step {k}")
+            same_records(td.state(), want_state[k], f"device state after step {k}")
 
 
 def test_reset_of_one_rig_in_mid_sequence(gpu):
@@ -166,8 +153,8 @@ def test_reset_of_one_rig_in_mid_sequence(gpu):
                 tr.reset(0)                                   # the other rig's reset leaves this one alone
                 ref.reset(0)
             got, want = gpu_step(tr, st), ref_step(ref, st)
-            same(got, want, f"records of step {k}")
-            same(tr.state(), ref.state, f"state after step {k}")
+            same_records(got, want, f"records of step {k}")
+            same_records(tr.state(), ref.state, f"state after step {k}")
             if k == 2:
                 assert got[1, 0]["status"] == fit.FIT_TRACK_FITTED and got[1, 0]["age"] == 1
         for rig in (2, -2):
@@ -185,8 +172,8 @@ def test_a_model_of_2562_points_is_streamed(gpu):
     with fit.Model(*model_points("2562")) as big, Rigged(s, big) as tr:
         for k, st in enumerate(s["steps"][:2]):
             got, want = gpu_step(tr, st), ref_step(ref, st)
-            same(got, want, f"records of step {k}")
-            same(tr.state(), ref.state, f"state after step {k}")
+            same_records(got, want, f"records of step {k}")
+            same_records(tr.state(), ref.state, f"state after step {k}")
         assert (got[0, 0]["status"], got[0, 0]["age"]) == (fit.FIT_TRACK_CARRIED, 2) and got[0, 0]["fit"]["points"] > 1000
 
 
@@ -266,8 +253,8 @@ def test_one_whole_step_with_a_rig_tracker_on_three_cameras_in_two_rigs(gpu):
                     assert a.tobytes() == b.tobytes(), (k, what)
                 n_heads, heads, ids, n_persons, persons, tracks = outs
                 assert (n_persons >= 1).all() and (persons["id"][:, 0] != 0).all()
-                same(rec, ref.step(frames, n_heads, heads, n_persons, persons), f"records of step {k}")
-                same(tr.state(), ref.state, f"state after step {k}")
+                same_records(rec, ref.step(frames, n_heads, heads, n_persons, persons), f"records of step {k}")
+                same_records(tr.state(), ref.state, f"state after step {k}")
                 # the _device twin on device arrays
                 mh = rt.max_heads
                 d_frames = dev(frames)
@@ -293,7 +280,7 @@ def test_one_whole_step_with_a_rig_tracker_on_three_cameras_in_two_rigs(gpu):
             with tracking.RigTracker(hp, rig, w, h, max_misses=2) as rt_short:
                 with pytest.raises(_lib.DepthheadError, match="max_misses 2 is below the fit tracker's max_coast 3"):
                     tr.step(rt_short, frames)
-            same(tr.state(), ref.state, "state after the refusals")
+            same_records(tr.state(), ref.state, "state after the refusals")
 
 
 def test_refusals_that_need_a_device(gpu):

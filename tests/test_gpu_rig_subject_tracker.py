@@ -27,7 +27,8 @@ import rig_subject_track_scenes as sc
 import subject_track_scenes as sts
 import view_fit_ref as vr
 from depthhead_amd import _lib, fit, tracking
-from subject_track_gpu import gpu_set, guarded, same, to_dev, untouched
+from gpu_kit import guarded, same_records, to_device, untouched
+from subject_track_gpu import gpu_set
 
 pytestmark = pytest.mark.gpu
 
@@ -79,8 +80,8 @@ def both(tr, ref, s, k, items, present=None, what=None, fit_kw=None):
     got = tr.step_persons(s.frames[k], *inputs, present=present, fit_params=None if fit_kw is None else fit.fit_params(**fit_kw))
     want = ref.step(s.frames[k], *inputs, present=present, fit_prm=None if fit_kw is None else fr.params(**fit_kw))
     assert got.dtype == REC and got.shape == (s.n_rigs, SLOTS)
-    same(got, want, f"records of {what or f'step {k}'}")
-    same(tr.state(), ref.state, f"state after {what or f'step {k}'}")
+    same_records(got, want, f"records of {what or f'step {k}'}")
+    same_records(tr.state(), ref.state, f"state after {what or f'step {k}'}")
     return got
 
 
@@ -149,7 +150,7 @@ def run_main(tr, ref, s, steps=6):
             inputs[2][g] += 1
             got = tr.step_persons(s.frames[k], *inputs, present=present)
             want = ref.step(s.frames[k], *inputs, present=present)
-            same(got, want, "records of step 4"); same(tr.state(), ref.state, "state after step 4")
+            same_records(got, want, "records of step 4"); same_records(tr.state(), ref.state, "state after step 4")
             recs.append(got)
         else:
             recs.append(both(tr, ref, s, k, items, present))
@@ -241,15 +242,15 @@ def test_nobody_enrolled_and_the_mask_replaced(angles):
         tr.set_enrolled(None); ref.set_enrolled(None)
         tr.bind(0, 7, None); ref.bind(0, 7, None)
         tr.bind(0, 99, 1); ref.bind(0, 99, 1)                          # an id nobody holds
-        same(tr.state(), ref.state, "state after the binds")
+        same_records(tr.state(), ref.state, "state after the binds")
         r2 = both(tr, ref, s, 2, items(2))[0, :2]
         assert r2["identified"].tolist() == [1, 0] and r2["ident"]["eligible"][0] == 3 and r2["model"].tolist() == [UNKNOWN, 2]
 
 
 def device_inputs(s, k, items, present=None):
     n_heads, heads, n_persons, persons = s.inputs(items)
-    d = [to_dev(a) for a in (s.frames[k], n_heads, heads, n_persons, persons)]
-    return d, heads.shape[1], None if present is None else to_dev(np.asarray(present, np.uint8))
+    d = [to_device(a) for a in (s.frames[k], n_heads, heads, n_persons, persons)]
+    return d, heads.shape[1], None if present is None else to_device(np.asarray(present, np.uint8))
 
 
 def step_dev(tr, d, mh, rec_ptr, d_pr=None, stream=0):
@@ -270,7 +271,7 @@ def test_the_set_updated_on_the_stream_between_two_steps(angles):
         stream = torch.cuda.Stream()
         d_rec = [torch.zeros(SLOTS * REC.itemsize, dtype=torch.uint8, device="cuda") for _ in range(2)]
         d_in = [device_inputs(s, k, items(k)) for k in range(2)]
-        d_shape = to_dev(shape)
+        d_shape = to_device(shape)
         torch.cuda.synchronize()
         with torch.cuda.stream(stream):
             step_dev(tr, d_in[0][0], d_in[0][1], d_rec[0].data_ptr(), stream=stream.cuda_stream)
@@ -282,9 +283,9 @@ def test_the_set_updated_on_the_stream_between_two_steps(angles):
         st.update(shape)
         assert st.pts[0].tobytes() != before.tobytes() and got.read(0)[0].tobytes() == st.pts[0].tobytes()
         want1 = ref.step(s.frames[1], *s.inputs(items(1)))
-        same(d_rec[0].cpu().numpy().view(REC), want0, "step 0")
-        same(d_rec[1].cpu().numpy().view(REC), want1, "step 1, after the update")
-        same(tr.state(), ref.state, "state")
+        same_records(d_rec[0].cpu().numpy().view(REC), want0, "step 0")
+        same_records(d_rec[1].cpu().numpy().view(REC), want1, "step 1, after the update")
+        same_records(tr.state(), ref.state, "state")
     assert (want1["model"][0, :2] < 3).all()
 
 
@@ -302,8 +303,8 @@ def test_the_identification_half_equals_the_existing_call(angles):
             frec = rec["track"]["fit"].copy()
             frec["status"][rec["identified"] == 0] = fr.FEW_POINTS
             d_frames = torch.from_numpy(s.frames[k].view(np.int16).copy()[None]).cuda()
-            out = ftr.identify_subjects_views(d_frames, views, got, to_dev(rec["track"]["instance"]), enrolled=to_dev(enrolled),
-                                              fit_records=to_dev(frec), params=fit.ident_views_params(**IDENT), device_out=True)
+            out = ftr.identify_subjects_views(d_frames, views, got, to_device(rec["track"]["instance"]), enrolled=to_device(enrolled),
+                                              fit_records=to_device(frec), params=fit.ident_views_params(**IDENT), device_out=True)
             torch.cuda.synchronize()
             subjects, irec = out[0].cpu().numpy().view(np.uint32), out[1].cpu().numpy().view(_lib.IDENT_RECORD_DTYPE)
             for i in range(len(rec)):
@@ -333,8 +334,8 @@ def test_host_calls_against_device_twins_between_guard_bands(angles):
                 step_dev(td, d, mh, ptr, d_pr, stream.cuda_stream)
             stream.synchronize()
             assert untouched(buf, off, nb)
-            same(buf.cpu().numpy()[off:off + nb].view(REC), want, f"device records of step {k}")
-            same(td.state(), th.state(), f"device state after step {k}")
+            same_records(buf.cpu().numpy()[off:off + nb].view(REC), want, f"device records of step {k}")
+            same_records(td.state(), th.state(), f"device state after step {k}")
 
 
 def test_reset_and_two_runs_of_one_sequence(angles):
@@ -343,7 +344,7 @@ def test_reset_and_two_runs_of_one_sequence(angles):
         first = run_main(tr, ref, s)
         state = tr.state()
         tr.reset(0); ref.reset(0)
-        same(tr.state(), ref.state, "state after the reset of rig 0")
+        same_records(tr.state(), ref.state, "state after the reset of rig 0")
         assert tr.state()[0].tobytes() == rs.initial(SLOTS).tobytes() and tr.state()[1].tobytes() == state[1].tobytes()
         run_main(tr, ref, s, steps=2)
         tr.reset(); ref.reset()
@@ -377,8 +378,8 @@ def test_one_step_captured_in_a_graph(angles):
             g.replay()
             torch.cuda.synchronize()
             want = both(eager, ref, s, k, items(k), what=f"eager step {k}")
-            same(d_rec.cpu().numpy().view(REC), want, f"replay {k}")
-            same(tr.state(), eager.state(), f"state after replay {k}")
+            same_records(d_rec.cpu().numpy().view(REC), want, f"replay {k}")
+            same_records(tr.state(), eager.state(), f"state after replay {k}")
 
 
 def test_a_rig_of_one_camera_through_the_identity_is_the_subject_fit_tracker(angles):
@@ -453,13 +454,13 @@ def test_one_whole_step_with_a_rig_tracker_on_three_cameras_in_two_rigs(angles):
                     assert a.tobytes() == b.tobytes(), (k, what)
                 n_heads, heads, ids, n_persons, persons, tracks = outs
                 assert (n_persons >= 1).all() and (persons["id"][:, 0] != 0).all()
-                same(rec, ref.step(frames, n_heads, heads, n_persons, persons), f"records of step {k}")
-                same(tr.state(), ref.state, f"state after step {k}")
+                same_records(rec, ref.step(frames, n_heads, heads, n_persons, persons), f"records of step {k}")
+                same_records(tr.state(), ref.state, f"state after step {k}")
                 mh = rt.max_heads
                 d = {n: torch.zeros(b, dtype=torch.uint8, device="cuda") for n, b in
                      (("n_heads", 3 * 4), ("heads", 3 * mh * 80), ("ids", 3 * mh * 4), ("n_persons", 2 * 4), ("persons", 2 * 16 * 56),
                       ("tracks", 2 * 16 * 72), ("rec", 2 * SLOTS * REC.itemsize))}
-                d_frames = to_dev(frames)
+                d_frames = to_device(frames)
                 tr_dev.step_device(d_frames.data_ptr(), d["n_heads"].data_ptr(), d["heads"].data_ptr(), d["n_persons"].data_ptr(),
                                    d["persons"].data_ptr(), d["rec"].data_ptr(), rig_tracker=rt_dev, ids_ptr=d["ids"].data_ptr(),
                                    tracks_ptr=d["tracks"].data_ptr())
@@ -474,7 +475,7 @@ def test_one_whole_step_with_a_rig_tracker_on_three_cameras_in_two_rigs(angles):
             with tracking.RigTracker(hp, rig, w, h, max_misses=2) as rt_short:
                 with pytest.raises(_lib.DepthheadError, match="max_misses 2 is below the fit tracker's max_coast 3"):
                     tr.step(rt_short, frames)
-            same(tr.state(), ref.state, "state after the refusals")
+            same_records(tr.state(), ref.state, "state after the refusals")
 
 
 def test_refusals_that_need_a_tracker(angles):

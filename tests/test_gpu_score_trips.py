@@ -21,7 +21,7 @@ import subject_track_gpu as stg
 import subject_track_scenes as sts
 import tracker_wave_scenes as tws
 from depthhead_amd import _lib, fit, tracking
-from subject_track_gpu import guarded, same, to_dev, untouched
+from gpu_kit import guarded, same_records, to_device, untouched
 
 pytestmark = pytest.mark.gpu
 
@@ -101,9 +101,9 @@ def run_case(kind, angles, grid, name, units, masks, ident="never"):
         assert tr.info() == (units, S, G)
         for k, m in enumerate(masks):
             tr.set_enrolled(list(m))
-            same(tr.state(), run.placed[k], f"state before step {k}")
-            same(step(kind, tr, inputs(kind, name, S, units, k)), run.records[k], f"records of step {k}")
-            same(tr.state(), run.state[k], f"state after step {k}")
+            same_records(tr.state(), run.placed[k], f"state before step {k}")
+            same_records(step(kind, tr, inputs(kind, name, S, units, k)), run.records[k], f"records of step {k}")
+            same_records(tr.state(), run.state[k], f"state after step {k}")
     return run
 
 
@@ -198,7 +198,7 @@ def test_device_form_between_guard_bands(kind, angles, grid):
     with trackers(kind, angles, ssc.NAME, S, units, m, count=2) as (th, td):
         assert th.info() == td.info() == (units, S, G)
         want = step(kind, th, args)
-        d = [to_dev(a) for a in args]
+        d = [to_device(a) for a in args]
         rec, rec_p, rec_o = guarded(nbytes, 8)
         torch.cuda.synchronize()
         with torch.cuda.stream(stream):
@@ -207,10 +207,10 @@ def test_device_form_between_guard_bands(kind, angles, grid):
         stream.synchronize()
         assert untouched(rec, rec_o, nbytes)
         got = rec.cpu().numpy()[rec_o:rec_o + nbytes].view(REC[kind])
-        same(got, want, "records of the _device step against the host form")
-        same(got, run.records[0], "records of the _device step against the restatement")
-        same(td.state(), th.state(), "state")
-        same(td.state(), run.state[0], "state against the restatement")
+        same_records(got, want, "records of the _device step against the host form")
+        same_records(got, run.records[0], "records of the _device step against the restatement")
+        same_records(td.state(), th.state(), "state")
+        same_records(td.state(), run.state[0], "state against the restatement")
 
 
 def test_a_rig_of_34_cameras_seen_through_the_high_word_of_the_view_mask(angles):
@@ -223,8 +223,8 @@ def test_a_rig_of_34_cameras_seen_through_the_high_word_of_the_view_mask(angles)
         assert tr.info()[:2] == (1, ssc.WIDE_S)
         for k in range(2):
             got = tr.step_persons(s.frames[k], *s.inputs(ssc.wide_items(s, k)), fit_params=fit.fit_params(**ssc.FIT))
-            same(got, run.records[k], f"records of step {k}")
-            same(tr.state(), run.state[k], f"state after step {k}")
+            same_records(got, run.records[k], f"records of step {k}")
+            same_records(tr.state(), run.state[k], f"state after step {k}")
             assert got[0, :2]["track"]["fit"]["views_used"].tolist() == list(ssc.WIDE_VIEWS)
             assert got[0, :2]["track"]["instance"]["views"].tolist() == list(ssc.WIDE_VIEWS)
             assert got[0, :2]["identified"].tolist() == ([1, 1] if k == 0 else [0, 0])

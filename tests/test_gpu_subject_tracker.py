@@ -19,7 +19,8 @@ import ident_ref as ir
 import subject_track_ref as stf
 import subject_track_scenes as sts
 from depthhead_amd import _lib, fit, tracking
-from subject_track_gpu import IDENT, TRACK, both, gpu_set, guarded, pair, same, to_dev, untouched
+from gpu_kit import guarded, same_records, to_device, untouched
+from subject_track_gpu import IDENT, TRACK, both, gpu_set, pair
 
 pytestmark = pytest.mark.gpu
 
@@ -177,7 +178,7 @@ def test_every_bound_and_unbound_start_kind_in_one_launch(angles):
         for c in (2, 3):
             tr.reset(c); ref.reset(c)
         tr.bind(3, 2); ref.bind(3, 2)
-        same(tr.state(), ref.state, "state after the reset and the bind")
+        same_records(tr.state(), ref.state, "state after the reset and the bind")
         rec = both(tr, ref, frames[1], poses[1], sup)
     assert kinds(rec) == [ft.CARRIED, ft.CARRIED, ft.FITTED, ft.FITTED, ft.REJECTED]
     assert rec["model"].tolist() == [0, UNKNOWN, UNKNOWN, 2, 2] and rec["identified"].tolist() == [0, 1, 1, 0, 0]
@@ -196,8 +197,8 @@ def test_the_set_updated_on_the_stream_between_two_steps(angles):
     with pair(angles, "642", 3, Ks, 96, 96) as (tr, ref, got, st, *_):
         stream = torch.cuda.Stream()
         d_rec = [torch.zeros(2 * REC.itemsize, dtype=torch.uint8, device="cuda") for _ in range(2)]
-        d_in = [(to_dev(frames[k]), to_dev(poses[k]), to_dev(sup)) for k in range(2)]
-        d_shape = to_dev(shape)
+        d_in = [(to_device(frames[k]), to_device(poses[k]), to_device(sup)) for k in range(2)]
+        d_shape = to_device(shape)
         torch.cuda.synchronize()
         with torch.cuda.stream(stream):
             tr.step_device(d_in[0][0].data_ptr(), d_in[0][1].data_ptr(), d_in[0][2].data_ptr(), d_rec[0].data_ptr(), stream=stream.cuda_stream)
@@ -209,9 +210,9 @@ def test_the_set_updated_on_the_stream_between_two_steps(angles):
         st.update(shape)
         assert st.pts[0].tobytes() != before.tobytes() and got.read(0)[0].tobytes() == st.pts[0].tobytes()
         want1 = ref.step(frames[1], poses[1], sup)
-        same(d_rec[0].cpu().numpy().view(REC), want0, "step 0")
-        same(d_rec[1].cpu().numpy().view(REC), want1, "step 1, after the update")
-        same(tr.state(), ref.state, "state")
+        same_records(d_rec[0].cpu().numpy().view(REC), want0, "step 0")
+        same_records(d_rec[1].cpu().numpy().view(REC), want1, "step 1, after the update")
+        same_records(tr.state(), ref.state, "state")
     assert want1["model"].tolist() == [0, 2]
 
 
@@ -228,7 +229,7 @@ def test_the_identification_half_equals_the_existing_call(angles):
             frec = rec["track"]["fit"].copy()
             frec["status"][rec["identified"] == 0] = fr.FEW_POINTS
             d_frames = torch.from_numpy(frames[k].view(np.int16).copy()).cuda()
-            out = ftr.identify_subjects(d_frames, got, to_dev(rec["track"]["instance"]), cams, enrolled=to_dev(enrolled), fit_records=to_dev(frec),
+            out = ftr.identify_subjects(d_frames, got, to_device(rec["track"]["instance"]), cams, enrolled=to_device(enrolled), fit_records=to_device(frec),
                                         params=fit.ident_params(**IDENT), device_out=True)
             torch.cuda.synchronize()
             subjects, irec = out[0].cpu().numpy().view(np.uint32), out[1].cpu().numpy().view(_lib.IDENT_RECORD_DTYPE)
@@ -259,9 +260,9 @@ def test_host_calls_against_device_twins_between_guard_bands(angles):
             pair(angles, "642", 4, Ks, W, H, enrolled=[1, 1, 1, 0], trackers=4) as ((th, td, wh, wd), ref, *_):
         for k in range(4):
             want = th.step_poses(frames[k], poses[k], sup[k], present[k])
-            same(want, ref.step(frames[k], poses[k], sup[k], present[k]), f"host records of step {k}")
+            same_records(want, ref.step(frames[k], poses[k], sup[k], present[k]), f"host records of step {k}")
             w_poses, w_sup, w_rec = wh.step(hp, frames[k], present[k])
-            d_frames, d_poses, d_sup, d_pr = to_dev(frames[k]), to_dev(poses[k]), to_dev(sup[k]), to_dev(present[k])
+            d_frames, d_poses, d_sup, d_pr = to_device(frames[k]), to_device(poses[k]), to_device(sup[k]), to_device(present[k])
             rec, rec_p, rec_o = guarded(3 * REC.itemsize, 8)
             rec2, rec2_p, rec2_o = guarded(3 * REC.itemsize, 24)
             po, po_p, po_o = guarded(3 * POSE.itemsize, 8)
@@ -275,8 +276,8 @@ def test_host_calls_against_device_twins_between_guard_bands(angles):
                                                   (po, po_o, POSE, w_poses, "poses"), (so, so_o, SUP, w_sup, "support")):
                 nb = 3 * dt.itemsize
                 assert untouched(buf, off, nb), what
-                same(buf.cpu().numpy()[off:off + nb].view(dt), ref_bytes, f"{what} of step {k}")
-            same(td.state(), th.state(), "core state"); same(wd.state(), wh.state(), "whole-step state")
+                same_records(buf.cpu().numpy()[off:off + nb].view(dt), ref_bytes, f"{what} of step {k}")
+            same_records(td.state(), th.state(), "core state"); same_records(wd.state(), wh.state(), "whole-step state")
 
 
 def test_reset_and_two_runs_of_one_sequence(angles):
@@ -285,7 +286,7 @@ def test_reset_and_two_runs_of_one_sequence(angles):
         first = run_both(tr, ref, frames, poses, sup, present)
         state = tr.state()
         tr.reset(0); ref.reset(0)
-        same(tr.state(), ref.state, "state after the reset of camera 0")
+        same_records(tr.state(), ref.state, "state after the reset of camera 0")
         assert tr.state()[0].tobytes() == stf.initial(1)[0].tobytes() and tr.state()[1].tobytes() == state[1].tobytes()
         run_both(tr, ref, frames, poses, sup, present, steps=2)
         tr.reset(); ref.reset()
@@ -300,7 +301,7 @@ def test_one_step_captured_in_a_graph(angles):
     frames, Ks, _, _, poses = sts.sequence("642", 3, 96, 96, (0, sts.STRANGER, 2), 3)
     sup = fts.good_support(3)
     with pair(angles, "642", 3, Ks, 96, 96, sub=dict(retry=1, max_tries=0), trackers=2) as ((eager, tr), ref, *_):
-        d_frames, d_poses, d_sup = to_dev(frames[0]), to_dev(poses[0]), to_dev(sup)
+        d_frames, d_poses, d_sup = to_device(frames[0]), to_device(poses[0]), to_device(sup)
         d_rec = torch.zeros(3 * REC.itemsize, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -311,13 +312,13 @@ def test_one_step_captured_in_a_graph(angles):
         tr.reset()                                                     # whatever the capture itself ran or did not run
         torch.cuda.synchronize()
         for k in range(3):
-            d_frames.copy_(to_dev(frames[k])); d_poses.copy_(to_dev(poses[k]))
+            d_frames.copy_(to_device(frames[k])); d_poses.copy_(to_device(poses[k]))
             g.replay()
             torch.cuda.synchronize()
             want = eager.step_poses(frames[k], poses[k], sup)
-            same(want, ref.step(frames[k], poses[k], sup), f"eager step {k}")
-            same(d_rec.cpu().numpy().view(REC), want, f"replay {k}")
-            same(tr.state(), eager.state(), f"state after replay {k}")
+            same_records(want, ref.step(frames[k], poses[k], sup), f"eager step {k}")
+            same_records(d_rec.cpu().numpy().view(REC), want, f"replay {k}")
+            same_records(tr.state(), eager.state(), f"state after replay {k}")
 
 
 def test_refusals_that_need_a_tracker(angles):

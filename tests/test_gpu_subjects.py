@@ -12,6 +12,7 @@ import shape_ref as sr
 import shape_scenes as ss
 import subjects_ref as sb
 import subjects_scenes as sc
+from gpu_kit import to_device
 from depthhead_amd import _lib, fit, synth
 
 pytestmark = pytest.mark.gpu
@@ -57,11 +58,6 @@ def records(deltas, statuses=None):
     rec["status"] = sr.OK if statuses is None else statuses
     rec["points"], rec["instances"], rec["sum_r2_fixed"] = 1000, 8, 123456        # what an update does not read
     return rec
-
-
-def to_device(array):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
 
 
 CASES = [("4", 4, 3), ("255", 4, 3), ("256", 4, 3), ("257", 4, 3), ("2562", 4, 3), ("fan", 4, 3), ("257", 1, 1), ("257", 8, 1), ("257", 1, 65),

@@ -13,6 +13,7 @@ import subjects_ref as sb
 import subjects_scenes as sc
 import surface_ref as su
 import surface_scenes as us
+from gpu_kit import to_device
 from depthhead_amd import _lib, fit, synth
 
 pytestmark = pytest.mark.gpu
@@ -56,11 +57,6 @@ def same(got, want, what):
         assert (c == want.counts[s]).all(), (what, "counts", s)
         assert pts.tobytes() == want.pts[s].tobytes(), (what, "points", s, int((pts != want.pts[s]).sum()))
         assert nrm.tobytes() == want.nrm[s].tobytes(), (what, "normals", s, int((nrm != want.nrm[s]).sum()))
-
-
-def to_device(array):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
 
 
 def scene(name, n_subjects, w, h, per_subject=2, seed=3, max_offset=16.0, coeffs=True):

@@ -18,7 +18,8 @@ import subject_track_ref as stf
 import subject_track_scenes as sts
 import tracker_wave_scenes as tws
 from depthhead_amd import _lib, fit, tracking
-from subject_track_gpu import both, guarded, pair, same, to_dev, untouched
+from gpu_kit import guarded, same_records, to_device, untouched
+from subject_track_gpu import both, pair
 
 pytestmark = pytest.mark.gpu
 
@@ -50,7 +51,7 @@ def run_script(tr, run, n, steps, binds=True):
         for c in tws.unbinds(k, n) if binds else ():
             tr.bind(c, None)
         ref.placed(k)
-        same(tr.state(), ref.state, f"state before step {k}")
+        same_records(tr.state(), ref.state, f"state before step {k}")
         out.append(both(tr, ref, frames[k, :n], poses[k, :n], sup, what=f"step {k}", fit_kw=tws.FIT))
     return np.stack(out)
 
@@ -104,7 +105,7 @@ def test_every_start_kind_on_both_sides_of_a_wave_boundary(angles):
         both(tr, ref, frames[0], poses[0], fts.good_support(N), what="step 0", fit_kw=tws.FIT)
         present, sup = tws.arrange_start_kinds(tr)
         ref.placed(1)
-        same(tr.state(), ref.state, "state after the resets and the binds")
+        same_records(tr.state(), ref.state, "state after the resets and the binds")
         rec = both(tr, ref, frames[1], poses[1], sup, present, what="step 1", fit_kw=tws.FIT)
     got = kinds(rec["track"])
     for c, kind in tws.START_KINDS.items():
@@ -123,13 +124,13 @@ def test_device_form_65_cameras_between_guard_bands(angles):
     with trackers(angles, n, count=2) as ((th, td), *_):
         sup0 = fts.good_support(n)
         first = th.step_poses(frames[0, :n], poses[0, :n], sup0, None, fit.fit_params(**tws.FIT))
-        same(td.step_poses(frames[0, :n], poses[0, :n], sup0, None, fit.fit_params(**tws.FIT)), first, "step 0 of the twin")
+        same_records(td.step_poses(frames[0, :n], poses[0, :n], sup0, None, fit.fit_params(**tws.FIT)), first, "step 0 of the twin")
         for t in (th, td):
             t.bind(64, None); t.bind(63, None); t.reset(0)
         present = np.ones(n, np.uint8)
         present[1] = 0
         want = th.step_poses(frames[1, :n], poses[1, :n], sup0, present, fit.fit_params(**tws.FIT))
-        d_in = [to_dev(a) for a in (frames[1, :n], poses[1, :n], sup0, present)]
+        d_in = [to_device(a) for a in (frames[1, :n], poses[1, :n], sup0, present)]
         rec, rec_p, rec_o = guarded(n * REC.itemsize, 8)
         torch.cuda.synchronize()
         with torch.cuda.stream(stream):
@@ -137,11 +138,11 @@ def test_device_form_65_cameras_between_guard_bands(angles):
                            fit_params=fit.fit_params(**tws.FIT), stream=stream.cuda_stream)
         stream.synchronize()
         assert untouched(rec, rec_o, n * REC.itemsize)
-        same(rec.cpu().numpy()[rec_o:rec_o + n * REC.itemsize].view(REC), want, "records of the _device step")
-        same(td.state(), th.state(), "state")
+        same_records(rec.cpu().numpy()[rec_o:rec_o + n * REC.itemsize].view(REC), want, "records of the _device step")
+        same_records(td.state(), th.state(), "state")
     assert want["identified"].tolist() == [1] + [0] * 62 + [1, 1] and kinds(want["track"])[:2] == [ft.FITTED, ft.ABSENT]
     run = tws.first_cameras(tws.want_run(tws.angles_key(angles)), n)
-    same(first, run.records[0], "step 0 against the restatement")
+    same_records(first, run.records[0], "step 0 against the restatement")
 
 
 # ---- the plain fit tracker
@@ -157,8 +158,8 @@ def test_fit_tracker_camera_counts(angles, n):
     with cams, model, fit.FitTracker(cams, model, W, H, params=fit.fit_track_params(**tws.TRACK)) as tr:
         for k in range(tws.FIT_STEPS):
             got = tr.step_poses(frames[k], poses[k], sup[k], present[k], fit.fit_params(**tws.FIT))
-            same(got, run.records[k], f"records of step {k}")
-            same(tr.state(), run.state[k], f"state after step {k}")
+            same_records(got, run.records[k], f"records of step {k}")
+            same_records(tr.state(), run.state[k], f"state after step {k}")
             assert kinds(got) == tws.fit_kinds(n)[k]
 
 
@@ -172,9 +173,9 @@ def test_fit_tracker_device_form_65_cameras_between_guard_bands(angles):
     with cams, model, fit.FitTracker(cams, model, W, H, params=fit.fit_track_params(**tws.TRACK)) as th, \
             fit.FitTracker(cams, model, W, H, params=fit.fit_track_params(**tws.TRACK)) as td:
         for t in (th, td):
-            same(t.step_poses(frames[0], poses[0], sup[0], present[0], fit.fit_params(**tws.FIT)), run.records[0], "step 0")
+            same_records(t.step_poses(frames[0], poses[0], sup[0], present[0], fit.fit_params(**tws.FIT)), run.records[0], "step 0")
         want = th.step_poses(frames[1], poses[1], sup[1], present[1], fit.fit_params(**tws.FIT))
-        d_in = [to_dev(a) for a in (frames[1], poses[1], sup[1], present[1])]
+        d_in = [to_device(a) for a in (frames[1], poses[1], sup[1], present[1])]
         rec, rec_p, rec_o = guarded(n * FIT_REC.itemsize, 8)
         torch.cuda.synchronize()
         with torch.cuda.stream(stream):
@@ -183,7 +184,7 @@ def test_fit_tracker_device_form_65_cameras_between_guard_bands(angles):
         stream.synchronize()
         assert untouched(rec, rec_o, n * FIT_REC.itemsize)
         got = rec.cpu().numpy()[rec_o:rec_o + n * FIT_REC.itemsize].view(FIT_REC)
-        same(got, want, "records of the _device step against the host form")
-        same(got, run.records[1], "records of the _device step against the restatement")
-        same(td.state(), th.state(), "state")
-        same(td.state(), run.state[1], "state against the restatement")
+        same_records(got, want, "records of the _device step against the host form")
+        same_records(got, run.records[1], "records of the _device step against the restatement")
+        same_records(td.state(), th.state(), "state")
+        same_records(td.state(), run.state[1], "state against the restatement")

@@ -3,49 +3,26 @@ selection, upload chunk plans, run-length payload validation / packing, the exce
 sanitizers: tests/host/host_check.cpp built with g++ -fsanitize=address,undefined and once more with -fsanitize=thread.
 (GPU AddressSanitizer is not available on the pool; sanitizers run on the CPU build only.)"""
 import os
-import platform
-import shutil
-import subprocess
 
 import numpy as np
 
-import pytest
+import host_program as hp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "depthhead_amd", "csrc")
-SOURCES = [os.path.join(ROOT, "tests", "host", "host_check.cpp"), os.path.join(CSRC, "dh_host.cpp"), os.path.join(CSRC, "dh_biwi.cpp")]
+CSRC = hp.CSRC
+SOURCES = [hp.host("host_check.cpp"), *hp.csrc("dh_host.cpp", "dh_biwi.cpp")]
 
 
-def _build_and_run(tmp_path, sanitize, env_extra, fixed_layout=False):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "host_check")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", f"-fsanitize={sanitize}",
-           "-fno-sanitize-recover=undefined", "-pthread", *SOURCES, "-o", exe]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if res.returncode != 0 and ("cannot find -l" in res.stderr or "unrecognized" in res.stderr):
-        pytest.skip(f"sanitizer runtime for {sanitize} not installed: {res.stderr[-200:]}")
-    assert res.returncode == 0, res.stderr[-3000:]
-    env = dict(os.environ, **env_extra)
-    for k in [k for k in env if k.startswith("DH_")]:
-        env.pop(k)
-    argv = [exe]
-    if fixed_layout and shutil.which("setarch"):
-        # ThreadSanitizer's runtime (gcc 11) only knows the address-space layout of up to 28 bits of mmap randomisation; on
-        # kernels set to more it dies before main ("FATAL: ThreadSanitizer: unexpected memory mapping", or a bare SIGSEGV).
-        # `setarch -R` turns randomisation off for this one process
-        argv = [shutil.which("setarch"), platform.machine(), "-R", exe]
-    run = subprocess.run(argv, capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "host_check ok" in run.stdout, (run.stdout[-2000:], run.stderr[-6000:])
+def _build_and_run(tmp_path, sanitize, env=None, fixed_layout=False):
+    exe = hp.build(tmp_path, "host_check", SOURCES, sanitize, ("-pthread",))
+    assert "host_check ok" in hp.run(exe, timeout=600, env=env, fixed_layout=fixed_layout).stdout
 
 
 def test_host_logic_under_asan_ubsan(tmp_path):
-    _build_and_run(tmp_path, "address,undefined", {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
+    _build_and_run(tmp_path, "address,undefined")
 
 
 def test_host_logic_under_tsan(tmp_path):
-    _build_and_run(tmp_path, "thread", {"HOST_CHECK_LIGHT": "1", "TSAN_OPTIONS": "halt_on_error=1"}, fixed_layout=True)
+    _build_and_run(tmp_path, "thread", {"HOST_CHECK_LIGHT": "1"}, fixed_layout=True)
 
 
 def test_host_translation_units_have_no_hip_in_them():
@@ -75,18 +52,13 @@ def test_vote_cell_fast_keeps_the_benchmark_intrinsics(tmp_path):
     widths away, where the quotient is known to pick wrong cells (tests/edge_families.py), does not."""
     import edge_families as ef
     from depthhead_amd import synth
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    src, exe = tmp_path / "cell_fast.cpp", str(tmp_path / "cell_fast")
+    src = tmp_path / "cell_fast.cpp"
     src.write_text(_CELL_FAST_DRIVER)
-    res = subprocess.run([gxx, "-std=c++17", "-O1", "-ffp-contract=off", "-pthread", f"-I{CSRC}", str(src), os.path.join(CSRC, "dh_host.cpp"),
-                          "-o", exe], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
+    exe = hp.build(tmp_path, "cell_fast", [src, *hp.csrc("dh_host.cpp")], extra=("-pthread", f"-I{CSRC}"))
 
     def fast(K, w, h):
         args = [repr(float(v)) for v in np.asarray(K, dtype=np.float32).reshape(-1)]   # (repr of a float32 widened: exact)
-        return subprocess.run([exe, str(w), str(h), *args], capture_output=True, text=True, timeout=60).stdout.strip() == "1"
+        return hp.run(exe, timeout=60, args=(w, h, *args)).stdout.strip() == "1"
     assert fast(synth.default_intrinsic(640, 480), 640, 480)
     for name, expect in (("principal_point_beside_the_frame", True), ("principal_point_far_off_the_frame", False)):
         fam = ef.FAMILIES[name]()

@@ -4,8 +4,6 @@ orders, crossing heads, coasting and expiry (max_misses 3 and 0), slot exhaustio
 saturating midpoints, empty frames, absent cameras and saturating counters.  The header is compiled by plain g++
 (tests/host/multi_track_check.cpp), and again under ASan / UBSan."""
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -14,10 +12,9 @@ import pytest
 from depthhead_amd._lib import HEAD_DTYPE, TRACK_DTYPE
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_program as hp  # noqa: E402
 import multi_track_ref as mr  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "depthhead_amd", "csrc")
 U32 = 0xFFFFFFFF
 INF, NAN = float("inf"), float("nan")
 
@@ -128,19 +125,7 @@ def random_sequences(count=60, seed=11):
 
 
 def _build(tmp_path, sanitize):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / ("multi_track_check" + ("_san" if sanitize else "")))
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", "-Wall", "-Werror", "-I" + CSRC,
-           os.path.join(ROOT, "tests", "host", "multi_track_check.cpp"), "-o", exe]
-    if sanitize:
-        cmd[1:1] = [f"-fsanitize={sanitize}", "-fno-sanitize-recover=undefined"]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if sanitize and res.returncode != 0 and ("cannot find -l" in res.stderr or "unrecognized" in res.stderr):
-        pytest.skip(f"sanitizer runtime for {sanitize} not installed: {res.stderr[-200:]}")
-    assert res.returncode == 0, res.stderr[-3000:]
-    return exe
+    return hp.build(tmp_path, "multi_track_check", [hp.host("multi_track_check.cpp")], sanitize, (*hp.WARN, "-I" + hp.CSRC))
 
 
 def run_checker(exe, cases):
@@ -149,9 +134,7 @@ def run_checker(exe, cases):
     for mh, hs, n, gate, mm, nid, pres, tr in cases:
         buf += np.array([mh, n, gate, mm, nid, int(pres)], dtype=np.uint32).tobytes()
         buf += np.ascontiguousarray(tr).tobytes() + np.ascontiguousarray(hs).tobytes()
-    run = subprocess.run([exe], input=bytes(buf), capture_output=True, timeout=120,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert run.returncode == 0, run.stderr[-3000:]
+    run = hp.run(exe, stdin=bytes(buf), timeout=120)
     out, pos, res = run.stdout, 0, []
     for mh, *_ in cases:
         tr = np.frombuffer(out, dtype=TRACK_DTYPE, count=mr.MAX_TRACKS, offset=pos).copy()

@@ -3,46 +3,26 @@ depthhead_amd/csrc/dh_rig_fit.h, what lane 0 of k_rig_fit_seed runs -- against t
 written from the header text in Python ints).  The header is compiled by plain g++ into tests/host/rig_fit_check.cpp, a
 stand-alone program with its own main, once as it is and once with -fsanitize=address,undefined; nothing is loaded into Python.
 No GPU."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
-import pytest
 
+import host_program as hp
 import rig_fit_track_ref as rf
 from depthhead_amd import _lib, synth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "depthhead_amd", "csrc")
 STATE, PERSON = _lib.RIG_FIT_STATE_DTYPE, _lib.RIG_PERSON_DTYPE
 UNUSED, SEEN, UNSEEN, UNBOUND = 0, 1, 2, 3
 MAX_HEADS = 2
 
 
 def build(tmp_path, sanitize=None):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / ("rig_fit_check" + ("_san" if sanitize else "")))
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", "-Wall", "-Werror", "-I" + CSRC,
-           os.path.join(ROOT, "tests", "host", "rig_fit_check.cpp"), "-o", exe]
-    if sanitize:
-        cmd[1:1] = [f"-fsanitize={sanitize}", "-fno-sanitize-recover=undefined"]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if res.returncode != 0 and sanitize and ("cannot find -l" in res.stderr or "unrecognized" in res.stderr):
-        pytest.skip(f"sanitizer runtime for {sanitize} not installed: {res.stderr[-200:]}")
-    assert res.returncode == 0, res.stderr[-3000:]
-    return exe
+    return hp.build(tmp_path, "rig_fit_check", [hp.host("rig_fit_check.cpp")], sanitize, (*hp.WARN, "-I" + hp.CSRC))
 
 
 def run_cases(exe, cases):
     buf = bytearray()
     for st, persons, n_persons, n_heads in cases:
         buf += np.array([n_persons, len(n_heads), MAX_HEADS], np.uint32).tobytes() + st.tobytes() + persons.tobytes() + n_heads.tobytes()
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], input=bytes(buf), capture_output=True, timeout=300, env=env)
-    assert run.returncode == 0, run.stderr[-3000:].decode()
+    run = hp.run(exe, stdin=bytes(buf), timeout=300)
     out, size = [], 16 * STATE.itemsize + 128
     assert len(run.stdout) == size * len(cases)
     for i in range(len(cases)):

@@ -7,8 +7,6 @@ saturating midpoints, extrinsics that overflow f32, rigs of 1 and of 64 cameras,
 rig with R = I, t = 0 gives every head the id tests/multi_track_ref.py gives it.  The header is compiled by plain g++
 (tests/host/rig_check.cpp), and again under ASan / UBSan."""
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -17,11 +15,10 @@ import pytest
 from depthhead_amd._lib import HEAD_DTYPE, RIG_PERSON_DTYPE, RIG_TRACK_DTYPE, TRACK_DTYPE
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_program as hp  # noqa: E402
 import multi_track_ref as mr  # noqa: E402
 import rig_track_ref as rr  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "depthhead_amd", "csrc")
 U32, U64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
 INF, NAN = float("inf"), float("nan")
 EYE = np.eye(3, dtype=np.float32).reshape(9)
@@ -173,19 +170,7 @@ def random_sequences(count=64, seed=17, big=True):
 
 
 def _build(tmp_path, sanitize):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / ("rig_check" + ("_san" if sanitize else "")))
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", "-Wall", "-Werror", "-I" + CSRC,
-           os.path.join(ROOT, "tests", "host", "rig_check.cpp"), "-o", exe]
-    if sanitize:
-        cmd[1:1] = [f"-fsanitize={sanitize}", "-fno-sanitize-recover=undefined"]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if sanitize and res.returncode != 0 and ("cannot find -l" in res.stderr or "unrecognized" in res.stderr):
-        pytest.skip(f"sanitizer runtime for {sanitize} not installed: {res.stderr[-200:]}")
-    assert res.returncode == 0, res.stderr[-3000:]
-    return exe
+    return hp.build(tmp_path, "rig_check", [hp.host("rig_check.cpp")], sanitize, (*hp.WARN, "-I" + hp.CSRC))
 
 
 def run_checker(exe, cases):
@@ -196,9 +181,7 @@ def run_checker(exe, cases):
         buf += np.ascontiguousarray(tr).tobytes() + s.R.tobytes() + s.t.tobytes()
         buf += (np.zeros(s.n_cams, np.uint32) if pres is None else pres.astype(np.uint32)).tobytes()
         buf += nh.tobytes() + np.ascontiguousarray(hs).tobytes()
-    run = subprocess.run([exe], input=bytes(buf), capture_output=True, timeout=300,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert run.returncode == 0, run.stderr[-3000:]
+    run = hp.run(exe, stdin=bytes(buf), timeout=300)
     out, pos, res = run.stdout, 0, []
 
     def take(dtype, count):

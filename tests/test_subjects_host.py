@@ -1,61 +1,18 @@
 """The host side of a subject set that is plain functions (depthhead_amd/csrc/dh_fit.h) -- the corner lists
 dh_fit_subjects_create builds, the base mesh's zero-normal test and the radius bound -- checked by tests/host/subjects_check.cpp, a
-stand-alone program with its own main: built by plain g++ once as it is and once with -fsanitize=address,undefined, and run, the
-way tests/test_calibrate_rule.py runs its program (the sanitizer's presence is probed with a trivial program first).  Nothing of HIP is linked or run, and nothing is loaded into Python.  No GPU."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
-from depthhead_amd import build as dh_build
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "depthhead_amd", "csrc")
+stand-alone program with its own main: built by plain g++ once as it is and once with -fsanitize=address,undefined, and run, by
+tests/host_program.py (the sanitizer's presence is probed with a trivial program first).  Nothing of HIP is linked or run, and nothing is loaded into Python.  No GPU."""
+import host_program as hp
 
 
-def hip_include():
-    inc = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(dh_build.hipcc()))), "include")
-    assert os.path.exists(os.path.join(inc, "hip", "hip_runtime.h")), inc
-    return inc
-
-
-def sanitizer_available(gxx, tmp_path, sanitize):
-    """Whether g++ can build and link a trivial program with -fsanitize=`sanitize`: asked BEFORE the program under test is built, so
-    that a failure to build that program is never taken for a missing runtime."""
-    src = tmp_path / "probe.cpp"
-    src.write_text("int main() { return 0; }\n")
-    return subprocess.run([gxx, f"-fsanitize={sanitize}", str(src), "-o", str(tmp_path / "probe")], capture_output=True).returncode == 0
-
-
-def build(tmp_path, sanitize=None):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    if sanitize and not sanitizer_available(gxx, tmp_path, sanitize):
-        pytest.skip(f"g++ cannot link a program with -fsanitize={sanitize}")
-    exe = str(tmp_path / ("subjects_check" + ("_san" if sanitize else "")))
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__",
-           "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-isystem", hip_include(),
-           os.path.join(ROOT, "tests", "host", "subjects_check.cpp"), "-o", exe]
-    if sanitize:
-        cmd[1:1] = [f"-fsanitize={sanitize}", "-fno-sanitize-recover=undefined"]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
-    return exe
-
-
-def run(exe):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-    assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
-    assert res.stdout.startswith("ok ") and int(res.stdout.split()[1]) > 2000, res.stdout
-    return res.stdout
+def check(tmp_path, sanitize=None):
+    exe = hp.build(tmp_path, "subjects_check", [hp.host("subjects_check.cpp")], sanitize, hp.fit_header_flags())
+    hp.run(exe, min_ok=2000, timeout=300)
 
 
 def test_corner_lists_zero_normals_and_the_radius_bound_on_the_host(tmp_path):
-    run(build(tmp_path))
+    check(tmp_path)
 
 
 def test_the_same_under_asan_ubsan(tmp_path):
-    run(build(tmp_path, "address,undefined"))
+    check(tmp_path, "address,undefined")

@@ -3,15 +3,10 @@ Python restatement of the reference's live loop, examples/live_prediction.rs:79-
 exactly 100.0f and its f32 neighbours, a stored z of exactly 500.0f, the first frame, -0.0, a large jump while the stored z
 is below 500, and all four flag combinations.  The header is compiled by plain g++ (tests/host/track_check.cpp), under
 ASan / UBSan."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "depthhead_amd", "csrc")
+import host_program as hp
+
 PREV, SLUG = 1, 2
 f32 = np.float32
 
@@ -71,24 +66,11 @@ def cases():
 
 
 def _build_and_run(tmp_path, sanitize):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "track_check")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", "-I" + CSRC,
-           os.path.join(ROOT, "tests", "host", "track_check.cpp"), "-o", exe]
-    if sanitize:
-        cmd[1:1] = [f"-fsanitize={sanitize}", "-fno-sanitize-recover=undefined"]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if sanitize and res.returncode != 0 and ("cannot find -l" in res.stderr or "unrecognized" in res.stderr):
-        pytest.skip(f"sanitizer runtime for {sanitize} not installed: {res.stderr[-200:]}")
-    assert res.returncode == 0, res.stderr[-3000:]
+    exe = hp.build(tmp_path, "track_check", [hp.host("track_check.cpp")], sanitize, ("-I" + hp.CSRC,))
     cs = cases()
     lines = "".join("%x %x %x %x %x %x %x %x\n" % ((fl,) + tuple(bits(v) for v in m) + tuple(bits(v) for v in s) + (hr,))
                     for fl, m, s, hr in cs)
-    run = subprocess.run([exe], input=lines, capture_output=True, text=True, timeout=120,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert run.returncode == 0, run.stderr[-3000:]
+    run = hp.run(exe, stdin=lines, timeout=120)
     out = run.stdout.strip().splitlines()
     assert len(out) == len(cs)
     for (fl, m, s, hr), line in zip(cs, out):

@@ -1,44 +1,25 @@
 """The host half of the trainer (depthhead_amd/csrc/dh_train.cpp) under the CPU sanitizers: tests/host/train_check.cpp built
 with g++ -fsanitize=address,undefined and once more with -fsanitize=thread, as tests/test_host_sanitize.py does for
-dh_host.cpp."""
+dh_host.cpp (both through tests/host_program.py)."""
 import os
-import platform
-import shutil
-import subprocess
 
-import pytest
+import host_program as hp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "depthhead_amd", "csrc")
-SOURCES = [os.path.join(ROOT, "tests", "host", "train_check.cpp"), os.path.join(CSRC, "dh_train.cpp"),
-           os.path.join(CSRC, "dh_host.cpp"), os.path.join(CSRC, "dh_biwi.cpp")]
+CSRC = hp.CSRC
+SOURCES = [hp.host("train_check.cpp"), *hp.csrc("dh_train.cpp", "dh_host.cpp", "dh_biwi.cpp")]
 
 
-def _build_and_run(tmp_path, sanitize, env_extra, fixed_layout=False):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "train_check")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", f"-fsanitize={sanitize}",
-           "-fno-sanitize-recover=undefined", "-pthread", *SOURCES, "-o", exe]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if res.returncode != 0 and ("cannot find -l" in res.stderr or "unrecognized" in res.stderr):
-        pytest.skip(f"sanitizer runtime for {sanitize} not installed: {res.stderr[-200:]}")
-    assert res.returncode == 0, res.stderr[-3000:]
-    env = dict(os.environ, **env_extra)
-    argv = [exe]
-    if fixed_layout and shutil.which("setarch"):
-        argv = [shutil.which("setarch"), platform.machine(), "-R", exe]   # (see test_host_sanitize.py: TSan and mmap randomisation)
-    run = subprocess.run(argv, capture_output=True, text=True, env=env, timeout=600)
-    assert run.returncode == 0 and "train_check ok" in run.stdout, (run.stdout[-2000:], run.stderr[-6000:])
+def _build_and_run(tmp_path, sanitize, env=None, fixed_layout=False):
+    exe = hp.build(tmp_path, "train_check", SOURCES, sanitize, ("-pthread",))
+    assert "train_check ok" in hp.run(exe, timeout=600, env=env, fixed_layout=fixed_layout).stdout
 
 
 def test_train_host_logic_under_asan_ubsan(tmp_path):
-    _build_and_run(tmp_path, "address,undefined", {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
+    _build_and_run(tmp_path, "address,undefined")
 
 
 def test_train_host_logic_under_tsan(tmp_path):
-    _build_and_run(tmp_path, "thread", {"TRAIN_CHECK_LIGHT": "1", "TSAN_OPTIONS": "halt_on_error=1"}, fixed_layout=True)
+    _build_and_run(tmp_path, "thread", {"TRAIN_CHECK_LIGHT": "1"}, fixed_layout=True)   # (see host_program.run: TSan and mmap randomisation)
 
 
 def test_train_host_unit_has_no_hip_in_it():
