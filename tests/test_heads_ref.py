@@ -16,30 +16,14 @@ import numpy as np
 import pytest
 
 from depthhead_amd import synth
-from depthhead_amd.forest import Forest, NODE_DTYPE
 from oracle import pyref
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import heads_ref as hr  # noqa: E402
 import support_ref as sr  # noqa: E402
+from heads_scenes import one_leaf_forest  # noqa: E402
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "depthhead_hip.h")
-
-
-def one_leaf_forest(offsets, rots=((0.0, 0.0, 0.0), (3.0, 0.0, 0.0))):
-    """One tree whose every non-zero window reaches leaf 0 (prob 1, the given offsets and rotations: at least two of each, or
-    the covariance gates read NaN)."""
-    nodes = np.zeros(1, dtype=NODE_DTYPE)
-    nodes[0]["r1"] = (0, 0, 1, 1)
-    nodes[0]["r2"] = (0, 0, 1, 1)
-    nodes[0]["threshold"] = -1.0
-    nodes[0]["child_zero"] = ~1
-    nodes[0]["child_one"] = ~0
-    offs = np.vstack([np.asarray(offsets, np.float32).reshape(-1, 3), [[0, 0, 0]]]).astype(np.float32)
-    rr = np.vstack([np.asarray(rots, np.float64).reshape(-1, 3), [[0, 0, 0]]])
-    k, q = len(offsets), len(rots)
-    return Forest(np.array([0], np.int32), nodes, np.array([1.0, 0.0]), np.array([0, k, k + 1], np.uint32),
-                  np.array([0, q, q + 1], np.uint32), offs, rr)
 
 
 def two_blocks(w=128, h=96, near=800, far=1000):
